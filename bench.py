@@ -4,6 +4,8 @@
     python bench.py --gpus N --steps K --warmup W            # N > 1: this process only spawns the N ranks (no GPU call in it)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --gpus 2 --dry-launch                    # CPU rehearsal of the launch path: gloo rendezvous, one line, no GPU
+    python bench.py --gpus 1 --steps K --warmup W --full     # + every secondary measurement and check (below)
+    python bench.py ... --dump-outputs DIR                   # + the parameters after the last timed step, DIR/<name>.npy
 
 Workload (BASELINE.json configs[1]): synthetic MNIST-shape 28x28x1 u8 images (16 384 per rank,
 seeded), the default rcn net conv(Same),pool,conv(Same),pool -> 784 -> 30 -> 10 (sigmoid, quadratic cost), N(0,1)
@@ -16,10 +18,14 @@ Warm-up steps are the first W steps of that session, the timed K steps follow th
 fall inside the timed region are paid inside it.  N > 1: one process per GPU, weak scaling (global batch 256*N), summed
 shard gradients exchanged once per step (include/rcn_hip.h: rcn_hip_dp_*).
 
-Rank 0 prints ONE JSON line.  Extra objects on it: "roofline" (dominant kernel, HIP events), "cpu_baseline" (the oracle's
-restatement of rcn's rayon loop timed on this host -- a reported baseline, not the target), config.steady_state_* (>= 4096
-device-timed steps in the same process), config.f64_* (the reference's own arithmetic type), config.loss_curve (256 steps
-against the CPU restatement on the same batches) and "trackx" (the north-star's trainable-convolution extension, CIFAR shape).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and reports them (value, ms_per_step); with
+--dump-outputs DIR it also writes weights_<l>.npy / biases_<l>.npy, the parameters the last timed step left, in the run's
+dtype (the inputs are seeded: two builds given the same arguments can be compared array for array).  With --full the line
+also carries: "roofline" (dominant kernel, HIP events), "cpu_baseline" (the oracle's restatement of rcn's rayon loop timed
+on this host -- a reported baseline, not the target), config.device_ms_per_step_rank0 (a second, event-timed pass),
+config.steady_state_* (>= 4096 device-timed steps in the same process), config.end_to_end_*, config.f64_* (the reference's
+own arithmetic type), config.loss_curve (256 steps against the CPU restatement on the same batches), "trackx" (the
+north-star's trainable-convolution extension, CIFAR shape) and, at N > 1, the replica check and the phase clocks.
 """
 from __future__ import annotations
 
@@ -149,9 +155,14 @@ def main():
     ap.add_argument("--steps", type=int, default=4096)
     ap.add_argument("--warmup", type=int, default=128)
     ap.add_argument("--dtype", choices=["f32", "f64"], default="f32")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the secondary end-to-end (u8 image -> features -> step) measurement")
-    ap.add_argument("--no-extras", action="store_true", help="skip the f64 / loss-curve / Track X legs (headline, roofline and steady state only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the secondary measurements and checks after the headline: device-timed pass, steady state, end-to-end, roofline, "
+                         "f64 / small-batch / test-net / loss-curve / Track X legs, CPU baseline, data-parallel phase clocks and replica check")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the parameters the last timed step left (what a caller of the training loop receives) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the secondary end-to-end (u8 image -> features -> step) measurement")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the f64 / loss-curve / Track X legs (roofline and steady state only)")
     ap.add_argument("--path", type=int, default=0, help="0 auto, 1 sample-tile kernels, 2 feature-sliced pipeline")
     ap.add_argument("--dp-impl", choices=["native", "torch"], default="native",
                     help="data-parallel loop: native = exchange inside librcn_hip (rcn_hip_dp_*), torch = torch.distributed all_reduce per step")
@@ -503,8 +514,9 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    def timed(k: int):
-        """k steps bracketed by barrier + synchronise on both sides: (wall seconds [max over ranks], device ms on this rank)"""
+    def timed(k: int, device_pass: bool = True, after=None):
+        """k steps bracketed by barrier + synchronise on both sides: (wall seconds [max over ranks], device ms on this rank or None
+        without the device-timed pass); after() runs once the k steps are done, before anything else touches the session"""
         prime(k)
         prime(k)            # twice: a call shape that needs a larger workspace moves it, which drops the graphs captured before it
         sync()
@@ -516,36 +528,57 @@ def main():
             dist.barrier()                # the closing barrier + synchronise of the bracket: the slowest rank's clock has stopped by now,
             torch.cuda.synchronize()      # and the barrier's own latency (an all-reduce launch) is not training time
         d.synchronize()                   # (outside the bracket: reports a sticky in-kernel time-out of the timed steps, if any)
-        # the device-side time of the same k steps, from a second pass of the session (event records are host calls of several
-        # microseconds each: kept out of the wall-clock bracket above, which is the contract's figure)
-        prime(k)
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record(d.stream)
-        run(k)
-        ev1.record(d.stream)
-        sync()
-        dev_ms = ev0.elapsed_time(ev1)
+        if after is not None:
+            after()
+        dev_ms = None
+        if device_pass:
+            # the device-side time of the same k steps, from a second pass of the session (event records are host calls of several
+            # microseconds each: kept out of the wall-clock bracket above, which is the contract's figure)
+            prime(k)
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record(d.stream)
+            run(k)
+            ev1.record(d.stream)
+            sync()
+            dev_ms = ev0.elapsed_time(ev1)
         if use_dp:
             t = torch.tensor([el], dtype=torch.float64, device=vdev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
         return el, dev_ms
 
+    outputs = {}
+
+    def keep_outputs():
+        """--dump-outputs: what the training loop hands its caller after the last timed step, the network's parameters (rank 0's copy;
+        the replicas of a data-parallel run are identical), in the run's arithmetic type"""
+        if args.dump_outputs and rank == 0:
+            npdt = np.float64 if args.dtype == "f64" else np.float32
+            wl, bl = d.get_params()
+            for l, (w, b) in enumerate(zip(wl, bl)):
+                outputs[f"weights_{l}"] = np.ascontiguousarray(w, dtype=npdt)
+                outputs[f"biases_{l}"] = np.ascontiguousarray(b, dtype=npdt)
+
     prime(args.warmup)
     run(args.warmup)
     start_pos = step_no[0] % nb_epoch
     epoch_boundary_in_bracket = start_pos == 0 or start_pos + args.steps > nb_epoch      # a shuffle + gather of the epoch falls inside the timed steps
-    elapsed, dev_ms = timed(args.steps)
-    loss_t = d.empty(1)
-    d.train_batch(X[:B], Y[:B], 0.0, loss_t)                             # eta = 0: reads the current cost, changes nothing
-    d.synchronize()
-    final_loss = float(loss_t.item())
-    if not use_dp:
-        step_no[0] = (step_no[0] + nb_epoch - 1) // nb_epoch * nb_epoch     # train_batch re-packed the image: the session resumes at the next epoch
-        begun["live"] = False
+    elapsed, dev_ms = timed(args.steps, device_pass=args.full, after=keep_outputs)
+    # everything below up to the result line is --full only: a plain run reports the timed steps and stops
+    final_loss = None
+    if args.full:
+        loss_t = d.empty(1)
+        d.train_batch(X[:B], Y[:B], 0.0, loss_t)                         # eta = 0: reads the current cost, changes nothing
+        d.synchronize()
+        final_loss = float(loss_t.item())
+        if not use_dp:
+            step_no[0] = (step_no[0] + nb_epoch - 1) // nb_epoch * nb_epoch     # train_batch re-packed the image: the session resumes at the next epoch
+            begun["live"] = False
 
     # ---- steady state: the same session carried on for >= 4096 more steps, in this process, device-timed ----
-    if args.steps >= STEADY_STEPS:
+    if not args.full:
+        steady_el = steady_dev_ms = steady_k = None
+    elif args.steps >= STEADY_STEPS:
         steady_el, steady_dev_ms, steady_k = elapsed, dev_ms, args.steps
     else:
         steady_k = STEADY_STEPS
@@ -555,7 +588,7 @@ def main():
     # semantics) and END-TO-END: u8 image -> feature kernel (+ standardise, fused) -> train_batch, i.e. the features of
     # every pass are recomputed from the resident u8 images inside the timed region.
     e2e = e2e_steady = None
-    if not use_dp and not args.no_e2e:
+    if args.full and not use_dp and not args.no_e2e:
         perm1 = perm
         try:
             d.train_epoch_images(imgs_d, Y, perm1, B, nb_epoch, ETA, None, prepare_only=True)
@@ -610,7 +643,7 @@ def main():
     # where a data-parallel step on the resident kernel waits (diagnostic launches with per-worker clocks, AFTER everything timed): what a
     # first run on more than one GPU needs to explain itself -- rcn_hip_dp_phase_us
     dp_phase = None
-    if use_dp and args.dp_impl == "native":
+    if args.full and use_dp and args.dp_impl == "native":
         def clocked():
             if not (d.dp_p2p_mode() != 0 and d.dp_resident(B)):
                 return None
@@ -628,7 +661,7 @@ def main():
 
     # data-parallel runs: every rank must hold bit-identical parameters (identical update from rank-ordered sums); a stale or
     # torn read in the exchange would show up here as diverged replicas
-    replicas_identical = replicas_check() if use_dp else None
+    replicas_identical = replicas_check() if args.full and use_dp else None
 
     images = args.steps * B * world
     result = {
@@ -645,11 +678,13 @@ def main():
                                  if (not use_dp and gathers) else "+ one gather of the shuffled order at every epoch boundary")
                               + ", inside the timed region whenever it is crossed -- see epoch_boundary_in_bracket; steady_state_* always carries its 1/64 share)",
                    "epoch_boundary_in_bracket": bool(epoch_boundary_in_bracket),
-                   "device_ms_per_step_rank0": round(dev_ms / args.steps, 6), "final_cost_rank0": final_loss,
+                   # the secondary figures and checks below are taken with --full only (null otherwise)
+                   "full": bool(args.full),
+                   "device_ms_per_step_rank0": round(dev_ms / args.steps, 6) if args.full else None, "final_cost_rank0": final_loss,
                    "steady_state_steps": steady_k,
-                   "steady_state_images_per_s": round(steady_k * B * world / steady_el, 1),
-                   "steady_state_us_per_step": round(steady_el * 1e6 / steady_k, 4),
-                   "steady_state_device_us_per_step_rank0": round(steady_dev_ms * 1e3 / steady_k, 4),
+                   "steady_state_images_per_s": round(steady_k * B * world / steady_el, 1) if args.full else None,
+                   "steady_state_us_per_step": round(steady_el * 1e6 / steady_k, 4) if args.full else None,
+                   "steady_state_device_us_per_step_rank0": round(steady_dev_ms * 1e3 / steady_k, 4) if args.full else None,
                    "end_to_end_images_per_s": round(e2e, 1) if e2e else None,                       # same steps, bracket and clock as `value`
                    "end_to_end_steady_state_images_per_s": round(e2e_steady, 1) if e2e_steady else None,   # 32 passes over the set, device-timed
                    "allreduce": allreduce_kind if use_dp else None, "replicas_identical": replicas_identical,
@@ -669,7 +704,7 @@ def main():
                               "synchronise; value uses the MAX over the ranks") if use_dp else "synchronise; K steps; one device-wide synchronise"},
     }
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel (HIP events on the stream the kernels run on) ----
         # HIP events on the kernels' own stream: each kernel back to back with itself, and the alternating pair as the epoch
         # loop issues it (walking the last epoch's packed batches).  A kernel's duration inside the real loop is the pair
@@ -813,6 +848,11 @@ def main():
         if not args.no_cpu_baseline and world == 1:      # the CPU path is timed beside the N = 1 run only
             result["cpu_baseline"] = cpu_baseline()
             result["config"]["gpu_over_cpu"] = round(result["value"] / max(result["cpu_baseline"]["value"], 1e-9), 1)
+    if rank == 0:
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in outputs.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
         line = json.dumps(result) + "\n"
         if real_stdout is not None:
             sys.stdout.flush()

@@ -66,3 +66,22 @@ def test_spawning_parent_never_imports_torch_or_loads_hip():
 def test_bench_convnet_spawns_too():
     src = open(os.path.join(ROOT, "bench_convnet.py")).read()
     assert "spawn_ranks" in src and "launch with torch.distributed.run" not in src
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_its_steps_and_dumps_the_trained_parameters(tmp_path):
+    """A plain `bench.py --gpus 1` run: the line reports exactly --steps timed steps and their ms_per_step, takes none of the --full
+    figures, and --dump-outputs writes the parameters the last timed step left, in the run's dtype."""
+    import numpy as np
+    r = _run("bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path / "out"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 20 and line["warmup"] == 5 and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert line["ms_per_step"] > 0 and abs(line["value"] - 20 * 256 / (line["ms_per_step"] * 20e-3)) <= 1e-3 * line["value"]
+    assert line["config"]["full"] is False and "roofline" not in line and "cpu_baseline" not in line and "trackx" not in line
+    from mercer_research_amd.synth import synthetic_params
+    ws, bs = synthetic_params([784, 30, 10], seed=42)
+    for name, start in [("weights_0", ws[0]), ("weights_1", ws[1]), ("biases_0", bs[0]), ("biases_1", bs[1])]:
+        a = np.load(tmp_path / "out" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == np.shape(start) and np.isfinite(a).all(), name
+        assert not np.array_equal(a, np.asarray(start, dtype=np.float32)), f"{name}: 25 steps of eta = 3 left it unchanged"
