@@ -42,6 +42,9 @@ def main():
     ap.add_argument("--dp-graph", type=int, default=1, help="data-parallel step: 1 = replay it as a captured hipGraph (the all-reduce inside), 0 = launch it eagerly")
     ap.add_argument("--dp-buckets", type=int, default=1 << 20, help="data-parallel step: gradient buckets of at least this many bytes, each all-reduced on a second stream "
                                                                      "while the backward pass of the layers below runs (0: ONE all-reduce of the whole gradient after the backward pass)")
+    ap.add_argument("--momentum", type=float, default=0.0, help="SGD momentum (rcn_hipx_set_sgd; 0: plain SGD)")
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="SGD weight decay, on every parameter")
+    ap.add_argument("--nesterov", action="store_true", help="Nesterov momentum (needs --momentum > 0)")
     args = ap.parse_args()
     from mercer_research_amd.launch import spawn_ranks, under_launcher
     if args.gpus > 1 and not under_launcher():
@@ -71,6 +74,9 @@ def main():
     for kv in args.set:
         net.set_option(kv.split("=")[0], int(kv.split("=")[1]))
     net.set_precision(args.precision)
+    sgd = args.momentum != 0.0 or args.weight_decay != 0.0 or args.nesterov
+    if sgd:
+        net.set_sgd(args.momentum, args.weight_decay, args.nesterov)
     rng = np.random.default_rng(rank)
     nbuf = 8 if args.config != "synth224" else 2           # rotate over several resident batches
     xs = [net.to_device(rng.standard_normal((B,) + in_shape).astype(np.float32)) for _ in range(nbuf)]
@@ -102,7 +108,10 @@ def main():
                         dist.all_reduce(piece, op=dist.ReduceOp.SUM)
                 net.gradients_bucketed(x, y, grad, loss, args.dp_buckets, on_bucket)
                 net.stream.wait_stream(comm)
-            net.apply(grad, lr / world)
+            if sgd:
+                net.apply_sgd(grad, 1.0 / world, lr)
+            else:
+                net.apply(grad, lr / world)
 
         def eager_step(i):
             with torch.cuda.stream(net.stream):

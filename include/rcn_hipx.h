@@ -90,13 +90,34 @@ int  rcn_hipx_get_params(rcn_hipx_net* net, float* flat);
 int  rcn_hipx_init_params(rcn_hipx_net* net, uint64_t seed);            /* He-normal weights, zero biases */
 /* logits_dev: [B][classes] */
 int  rcn_hipx_forward_dev(rcn_hipx_net* net, const float* x_dev, int B, float* logits_dev);
-/* one SGD step on mean cross-entropy: forward, backward, W <- W - lr * dW.  loss_dev (nullable): mean loss before the step.
- * Replayed as one hipGraph per (pointers, B, lr). */
+/* one SGD step on mean cross-entropy: forward, backward, W <- W - lr * dW (or the update rcn_hipx_set_sgd chose, in the same launch).
+ * loss_dev (nullable): mean loss before the step.  Replayed as one hipGraph per (pointers, B, lr). */
 int  rcn_hipx_train_step_dev(rcn_hipx_net* net, const float* x_dev, const int32_t* labels_dev, int B, float lr, float* loss_dev);
 /* data-parallel halves: gradients of the MEAN loss over this shard into the padded flat layout (rcn_hipx_param_count's
  * `padded`), and p <- p - scale * g from such a buffer. */
 int  rcn_hipx_gradients_dev(rcn_hipx_net* net, const float* x_dev, const int32_t* labels_dev, int B, float* grad_dev, float* loss_dev);
 int  rcn_hipx_apply_dev(rcn_hipx_net* net, const float* grad_dev, float scale);
+/* The optimiser of the training step: SGD with momentum, weight decay and Nesterov, as torch.optim.SGD with dampening 0.  Per element,
+ * fp32, every operation rounded once (no fused multiply-add), weight decay on every parameter, biases included:
+ *     d = grad_scale * g;  if (wd) d = d + wd * p;  if (mu) { v = mu * v + d;  d = nesterov ? d + mu * v : v; }  p = p - lr * d
+ * (grad_scale = 1 in rcn_hipx_train_step_dev; v starts at 0, so the first step gives v = d).  The update runs inside the step's one
+ * reduction launch (k_reduce_all_sgd), so the step stays one captured graph.  (0, 0, 0) is the default: plain SGD, the same kernels and
+ * arguments as a net never configured.  Accepts 0 <= momentum < 1, a finite weight_decay >= 0 and nesterov 0 / 1 (1 needs momentum > 0);
+ * anything else returns -1 and changes nothing.  The first nonzero momentum allocates the velocity buffer (zeroed).  Changing a value
+ * synchronises the net's stream and drops its captured graphs.  The velocity survives rcn_hipx_set_params, rcn_hipx_init_params and
+ * changes of precision, tiling, overlap or options (as a torch.optim.SGD state survives a load of the parameters); the learning rate
+ * stays part of a captured graph's key, so a per-step schedule re-captures. */
+int  rcn_hipx_set_sgd(rcn_hipx_net* net, float momentum, float weight_decay, int nesterov);
+int  rcn_hipx_get_sgd(const rcn_hipx_net* net, float* momentum, float* weight_decay, int* nesterov);
+/* the velocity in the logical layout of rcn_hipx_get_params / _set_params.  get: zeros while no velocity buffer exists; set: -6 while the
+ * momentum is 0; reset: zeroes it, enqueued on the net's stream (a no-op without a buffer). */
+int  rcn_hipx_get_velocity(rcn_hipx_net* net, float* flat);
+int  rcn_hipx_set_velocity(rcn_hipx_net* net, const float* flat);
+int  rcn_hipx_reset_velocity(rcn_hipx_net* net);
+/* data-parallel half of that optimiser: the same update from a padded gradient buffer (16-byte aligned; e.g. the all-reduced sum of the
+ * ranks' gradients with grad_scale = 1 / ranks).  With the default setting it is rcn_hipx_apply_dev(grad_dev, grad_scale * lr).
+ * rcn_hipx_apply_dev itself stays the plain p <- p - scale * g and never touches the velocity. */
+int  rcn_hipx_apply_sgd_dev(rcn_hipx_net* net, const float* grad_dev, float grad_scale, float lr);
 /* The same gradients in BUCKETS, so that a data-parallel step can all-reduce one bucket of layers while the backward pass of the layers
  * below it still runs (6.7 MB of gradient for BASELINE configs[3]).  The layers with parameters, in the order the
  * backward pass finishes them (last to first), are cut into buckets of at least min_bucket_bytes of gradient; the padded flat layout
@@ -121,7 +142,8 @@ int  rcn_hipx_unpad_host(rcn_hipx_net* net, const float* padded_dev, float* logi
  * covered by the kernels that take bf16 tensors. */
 int  rcn_hipx_plan(int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, int n_layers, int batch, int precision, int tiling, char* out, int cap);
 /* The same walk for an EXISTING net at batch `batch` (<= max_batch) with that net's own precision, tiling and options: the plan and the
- * step that follows agree by construction (rcn_hipx_plan describes a net created now, seeded from the environment). */
+ * step that follows agree by construction (rcn_hipx_plan describes a net created now, seeded from the environment).  A net with a
+ * non-default rcn_hipx_set_sgd setting names its optimiser and the values on the update line. */
 int  rcn_hipx_plan_net(const rcn_hipx_net* net, int batch, char* out, int cap);
 /* algorithmic FLOPs of one training step at batch B (2 * MACs; forward + dgrad + wgrad) */
 int  rcn_hipx_step_flops(const rcn_hipx_net* net, int B, double* flops);

@@ -46,6 +46,12 @@ SIGNATURES = {
     "rcn_hipx_plan_net": (_i, [_vp, _i, C.c_char_p, _i]),
     "rcn_hipx_step_flops": (_i, [_vp, _i, C.POINTER(C.c_double)]),
     "rcn_hipx_plan": (_i, [_i, _i, _i, C.POINTER(XLayer), _i, _i, _i, _i, C.c_char_p, _i]),
+    "rcn_hipx_set_sgd": (_i, [_vp, C.c_float, C.c_float, _i]),
+    "rcn_hipx_get_sgd": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "rcn_hipx_get_velocity": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rcn_hipx_set_velocity": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rcn_hipx_reset_velocity": (_i, [_vp]),
+    "rcn_hipx_apply_sgd_dev": (_i, [_vp, _vp, C.c_float, C.c_float]),
 }
 _libx = None
 
@@ -222,6 +228,34 @@ class ConvNet:
 
     def apply(self, grad, scale: float):
         self._ck(self.lib.rcn_hipx_apply_dev(self.net, C.c_void_p(grad.data_ptr()), scale))
+
+    def set_sgd(self, momentum: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False):
+        """The optimiser of train_step / apply_sgd: SGD with momentum, weight decay and Nesterov, as torch.optim.SGD with dampening 0
+        (include/rcn_hipx.h, rcn_hipx_set_sgd).  (0, 0, False) is plain SGD, the default."""
+        self._ck(self.lib.rcn_hipx_set_sgd(self.net, float(momentum), float(weight_decay), int(bool(nesterov))))
+
+    def get_sgd(self) -> Tuple[float, float, bool]:
+        mu, wd, nest = C.c_float(), C.c_float(), C.c_int()
+        self._ck(self.lib.rcn_hipx_get_sgd(self.net, C.byref(mu), C.byref(wd), C.byref(nest)))
+        return float(mu.value), float(wd.value), bool(nest.value)
+
+    def get_velocity(self) -> np.ndarray:
+        """The momentum buffer in the logical layout of get_params (zeros while the net has none)."""
+        f = np.zeros(self.n_logical, dtype=np.float32)
+        self._ck(self.lib.rcn_hipx_get_velocity(self.net, f.ctypes.data_as(C.POINTER(C.c_float))))
+        return f
+
+    def set_velocity(self, flat: np.ndarray):
+        f = np.ascontiguousarray(flat, dtype=np.float32)
+        assert f.size == self.n_logical
+        self._ck(self.lib.rcn_hipx_set_velocity(self.net, f.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def reset_velocity(self):
+        self._ck(self.lib.rcn_hipx_reset_velocity(self.net))
+
+    def apply_sgd(self, grad, grad_scale: float, lr: float):
+        """The data-parallel half of set_sgd's optimiser: the same update from a padded gradient buffer, scaled by grad_scale first."""
+        self._ck(self.lib.rcn_hipx_apply_sgd_dev(self.net, C.c_void_p(grad.data_ptr()), grad_scale, lr))
 
     def unpad(self, padded) -> np.ndarray:
         f = np.zeros(self.n_logical, dtype=np.float32)

@@ -483,7 +483,10 @@ constexpr int kReduceThreads = 1024;
 __host__ __device__ inline int reduce_job_groups(int chunks) { int g = 1; while (g < chunks && g < 32) g <<= 1; return g; }
 __host__ __device__ inline int reduce_job_elems(int chunks) { return 4 * kReduceThreads / reduce_job_groups(chunks); }
 
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all(ReduceJobs J) {
+// The reduction itself, shared by k_reduce_all (plain SGD) and k_reduce_all_sgd (convnet_sgd.hpp: momentum, weight decay, Nesterov).
+// `update(J, jb, i, t)` returns the four new parameters [i, i + 4) of job jb from their summed gradient t; it may keep state of its own.
+template <class Update>
+__device__ __forceinline__ void reduce_all_body(const ReduceJobs& J, const Update& update) {
     __shared__ f32x4 red[kReduceThreads];
     int q = 0;
     while (q + 1 < J.njobs && (int)blockIdx.x >= J.j[q + 1].first_block) ++q;
@@ -515,15 +518,25 @@ __global__ __launch_bounds__(kReduceThreads) void k_reduce_all(ReduceJobs J) {
         const f32x4 t = red[threadIdx.x];
         if (jb.grad) *reinterpret_cast<f32x4*>(jb.grad + i) = t;
         if (J.apply) {
-            f32x4 v = *reinterpret_cast<const f32x4*>(jb.p + i);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = v[k] - J.lr * t[k];
+            const f32x4 v = update(J, jb, i, t);
             *reinterpret_cast<f32x4*>(jb.p + i) = v;
 #pragma unroll
             for (int k = 0; k < 4; ++k) store_flipped(jb.flip, i + k, v[k]);
         }
     }
 }
+
+// p <- p - lr * g
+struct PlainUpdate {
+    __device__ __forceinline__ f32x4 operator()(const ReduceJobs& J, const ReduceJob& jb, long long i, const f32x4& t) const {
+        f32x4 v = *reinterpret_cast<const f32x4*>(jb.p + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = v[k] - J.lr * t[k];
+        return v;
+    }
+};
+
+__global__ __launch_bounds__(kReduceThreads) void k_reduce_all(ReduceJobs J) { reduce_all_body(J, PlainUpdate{}); }
 
 // db[co] = sum_m dZ[m][co]: one workgroup per 32-column block, rows strided over threads, fixed-order tree
 __global__ __launch_bounds__(256) void k_bias_grad(const float* __restrict__ dZ, long long M, int Cout, float* __restrict__ b, float* __restrict__ grad_out,

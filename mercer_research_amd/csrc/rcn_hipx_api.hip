@@ -20,6 +20,7 @@
 #include "convnet_bf16.hpp"
 #include "convnet_halo.hpp"
 #include "convnet_halo_bf16.hpp"
+#include "convnet_sgd.hpp"
 
 using namespace rcnx;
 
@@ -131,6 +132,10 @@ struct rcn_hipx_net {
     // kept in memory as bf16.  precision == RCN_HIPX_BF16 then too: what is ROUNDED does not change, only where.
     bool store16 = false;
     int tiling = RCN_HIPX_TILING_AUTO;      // fp32 3x3 kernels: implicit GEMM only / by shape / LDS-tiled wherever they apply (rcn_hipx_set_tiling)
+    // the optimiser (rcn_hipx_set_sgd; convnet_sgd.hpp): (0, 0, 0) is plain SGD through k_reduce_all / k_axpy.  `vel` (n_pad floats, laid out
+    // like params) is allocated by the first nonzero momentum and never moved afterwards: captured graphs hold its pointer.
+    float sgd_mu = 0.f, sgd_wd = 0.f; int sgd_nesterov = 0;
+    Buf vel;
     std::map<Key, hipGraphExec_t> graphs;
     // the backward pass as a resumable walk (rcn_hipx_gradients_begin_dev / _bucket_dev: a data-parallel step whose all-reduce of one bucket
     // of layers overlaps the backward pass of the layers below it)
@@ -773,11 +778,23 @@ int reduce_slab(rcn_hipx_net* n, size_t i, int chunks, int ks, const ConvShape& 
     return 0;
 }
 
+bool sgd_default(const rcn_hipx_net* n) { return n->sgd_mu == 0.f && n->sgd_wd == 0.f && !n->sgd_nesterov; }
+SgdParams sgd_params(const rcn_hipx_net* n) { return SgdParams{(float*)n->vel.p, (const float*)n->params.p, n->sgd_mu, n->sgd_wd, n->sgd_nesterov}; }
+
 int run_reduce_jobs(rcn_hipx_net* n, float lr, bool apply) {
     if (!n->jobs.njobs) return 0;
     const ReduceJob& last = n->jobs.j[n->jobs.njobs - 1];
     const long long blocks = last.first_block + (last.n + reduce_job_elems(last.chunks) - 1) / reduce_job_elems(last.chunks);
     n->jobs.lr = lr; n->jobs.apply = apply ? 1 : 0;
+    if (apply && !sgd_default(n)) {
+        // the net's optimiser in the same launch (convnet_sgd.hpp); gradients-only walks never get here
+        if (dry_note(n, "  update: k_reduce_all_sgd, %d layers' slabs in one launch, %lld workgroups (SGD: momentum %g, weight decay %g, nesterov %s)",
+                     n->jobs.njobs, blocks, (double)n->sgd_mu, (double)n->sgd_wd, n->sgd_nesterov ? "on" : "off")) { n->jobs.njobs = 0; return 0; }
+        hipLaunchKernelGGL(k_reduce_all_sgd, dim3((unsigned)blocks), dim3(kReduceThreads), 0, n->stream, n->jobs, sgd_params(n));
+        XTRY(n, hipGetLastError());
+        n->jobs.njobs = 0;
+        return 0;
+    }
     if (dry_note(n, "  update: k_reduce_all, %d layers' slabs in one launch, %lld workgroups", n->jobs.njobs, blocks)) { n->jobs.njobs = 0; return 0; }
     hipLaunchKernelGGL(k_reduce_all, dim3((unsigned)blocks), dim3(kReduceThreads), 0, n->stream, n->jobs);
     XTRY(n, hipGetLastError());
@@ -1138,7 +1155,7 @@ void rcn_hipx_destroy(rcn_hipx_net* n) {
         if (n->stream) (void)hipStreamSynchronize(n->stream);
         drop_graphs(n);
         for (Layer& l : n->L) { l.out.release(); l.idx.release(); l.dout.release(); l.slab.release(); }
-        for (Buf* b : {&n->params, &n->wt, &n->wb16, &n->dz, &n->loss_part, &n->grad_tmp, &n->dlogits, &n->skbuf, &n->wb}) b->release();
+        for (Buf* b : {&n->params, &n->wt, &n->wb16, &n->dz, &n->loss_part, &n->grad_tmp, &n->dlogits, &n->skbuf, &n->wb, &n->vel}) b->release();
         if (n->side) { (void)hipStreamSynchronize(n->side); (void)hipStreamDestroy(n->side); }
         for (hipEvent_t e : n->events) (void)hipEventDestroy(e);
         if (n->own_stream && n->stream) (void)hipStreamDestroy(n->stream);
@@ -1334,6 +1351,79 @@ int rcn_hipx_apply_dev(rcn_hipx_net* n, const float* grad, float scale) {
     return refresh_flipped(n);
 }
 
+int rcn_hipx_set_sgd(rcn_hipx_net* n, float momentum, float weight_decay, int nesterov) {
+    if (!n) return -1;
+    if (!(momentum >= 0.f && momentum < 1.f)) return fail(n, -1, "set_sgd: momentum must be in [0, 1)");
+    if (!(std::isfinite(weight_decay) && weight_decay >= 0.f)) return fail(n, -1, "set_sgd: weight_decay must be finite and >= 0");
+    if (nesterov != 0 && nesterov != 1) return fail(n, -1, "set_sgd: nesterov must be 0 or 1");
+    if (nesterov && momentum == 0.f) return fail(n, -1, "set_sgd: nesterov needs a momentum > 0");
+    if (momentum == n->sgd_mu && weight_decay == n->sgd_wd && nesterov == n->sgd_nesterov) return 0;
+    Dev g(n->device);
+    XTRY(n, hipStreamSynchronize(n->stream));
+    if (momentum != 0.f && !n->vel.p) {
+        // once, outside any capture: captured graphs hold this pointer, so the buffer never moves afterwards
+        XTRY(n, n->vel.ensure((size_t)n->n_pad * sizeof(float)));
+        XTRY(n, hipMemsetAsync(n->vel.p, 0, (size_t)n->n_pad * sizeof(float), n->stream));
+        XTRY(n, hipStreamSynchronize(n->stream));
+    }
+    drop_graphs(n);                                     // captured graphs bake in the update kernel and its arguments
+    n->sgd_mu = momentum; n->sgd_wd = weight_decay; n->sgd_nesterov = nesterov;
+    return 0;
+}
+
+int rcn_hipx_get_sgd(const rcn_hipx_net* n, float* momentum, float* weight_decay, int* nesterov) {
+    if (!n) return -1;
+    if (momentum) *momentum = n->sgd_mu;
+    if (weight_decay) *weight_decay = n->sgd_wd;
+    if (nesterov) *nesterov = n->sgd_nesterov;
+    return 0;
+}
+
+int rcn_hipx_get_velocity(rcn_hipx_net* n, float* flat) {
+    if (!n || !flat) return -1;
+    if (!n->vel.p) { std::memset(flat, 0, (size_t)n->n_log * sizeof(float)); return 0; }
+    Dev g(n->device);
+    return unpad(n, (const float*)n->vel.p, flat);
+}
+
+int rcn_hipx_set_velocity(rcn_hipx_net* n, const float* flat) {
+    if (!n || !flat) return -1;
+    if (n->sgd_mu == 0.f || !n->vel.p) return fail(n, -6, "set_velocity: the net has no momentum (rcn_hipx_set_sgd first)");
+    Dev g(n->device);
+    std::vector<float> pad((size_t)n->n_pad, 0.f);
+    for (const Layer& l : n->L) {
+        if (l.kind == RCN_HIPX_MAXPOOL2) continue;
+        for (int k = 0; k < l.K; ++k) std::memcpy(&pad[l.w_off + (long long)k * l.CoutP], &flat[l.lw_off + (long long)k * l.Cout], sizeof(float) * l.Cout);
+        std::memcpy(&pad[l.b_off], &flat[l.lb_off], sizeof(float) * l.Cout);
+    }
+    XTRY(n, hipMemcpyAsync(n->vel.p, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice, n->stream));
+    XTRY(n, hipStreamSynchronize(n->stream));
+    return 0;
+}
+
+int rcn_hipx_reset_velocity(rcn_hipx_net* n) {
+    if (!n) return -1;
+    if (!n->vel.p) return 0;
+    Dev g(n->device);
+    XTRY(n, hipMemsetAsync(n->vel.p, 0, (size_t)n->n_pad * sizeof(float), n->stream));
+    return 0;
+}
+
+int rcn_hipx_apply_sgd_dev(rcn_hipx_net* n, const float* grad, float grad_scale, float lr) {
+    if (!n || !grad) return -1;
+    Dev g(n->device);
+    if (sgd_default(n)) {
+        // plain SGD: exactly rcn_hipx_apply_dev(grad, grad_scale * lr)
+        hipLaunchKernelGGL(k_axpy, dim3(grid1d(n->n_pad, 256)), dim3(256), 0, n->stream, (float*)n->params.p, grad, grad_scale * lr, n->n_pad);
+        XTRY(n, hipGetLastError());
+        return refresh_flipped(n);
+    }
+    if ((uintptr_t)grad % 16 != 0) return fail(n, -1, "apply_sgd: the gradient buffer must be 16-byte aligned");
+    hipLaunchKernelGGL(k_sgd_apply, dim3(grid1d(n->n_pad / 4, 256)), dim3(256), 0, n->stream, (float*)n->params.p, grad, grad_scale, lr, sgd_params(n), n->n_pad);
+    XTRY(n, hipGetLastError());
+    return refresh_flipped(n);
+}
+
 int rcn_hipx_step_flops(const rcn_hipx_net* n, int B, double* flops) {
     if (!n || !flops) return -1;
     double f = 0;
@@ -1398,6 +1488,7 @@ int rcn_hipx_plan_net(const rcn_hipx_net* n, int batch, char* out, int cap) {
     net.in_h = n->in_h; net.in_w = n->in_w; net.in_c = n->in_c; net.max_batch = batch; net.classes = n->classes;
     net.precision = n->precision; net.store16 = n->store16; net.tiling = n->tiling; net.overlap = 0; net.dry = true;
     net.opt = n->opt;
+    net.sgd_mu = n->sgd_mu; net.sgd_wd = n->sgd_wd; net.sgd_nesterov = n->sgd_nesterov;
     copy_layer_table(net, *n);
     net.plan = "forward + loss + backward of one batch of " + std::to_string(batch) + " (" + precision_name(net.precision, net.store16) + "), launch by launch:\n";
     const int st = step_core(&net, nullptr, nullptr, batch, 0.f, nullptr, true, nullptr);
