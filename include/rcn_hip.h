@@ -324,8 +324,8 @@ int  rcn_hip_classify_images(rcn_hip_ctx* ctx, const uint8_t* imgs, size_t n, in
  * rows the library shuffled or uploaded itself are re-created, everything else those calls read must be unchanged, the usual
  * contract of an asynchronous call.  rcn_hip_fallbacks_taken counts these step-downs; option "xcd_auto_fallback" = 0 restores the
  * sticky RCN_HIP_ERR_HIP (cleared by rcn_hip_set_params / rcn_hip_init_params / rcn_hip_set_dense_path(ctx, 1 or 2)).
- * 3 and 4 are parked experiments compiled only into librcn_hip_exp.so.  All compute the same step (summation grouping differs,
- * within the stated tolerances). */
+ * 3 and 4 (one resident kernel per epoch segment, one launch per step) were removed: RCN_HIP_ERR_UNSUPPORTED.  All modes compute the
+ * same step (summation grouping differs, within the stated tolerances). */
 int  rcn_hip_set_dense_path(rcn_hip_ctx* ctx, int mode);
 int  rcn_hip_fallbacks_taken(const rcn_hip_ctx* ctx);      /* not a status: the number of step-downs described above */
 /* The record of the newest bounded wait of the resident one-XCD kernel that expired in this context -- written by the first worker that

@@ -9,7 +9,6 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "librcn_hip.so")
-LIB_EXP_PATH = os.path.join(HERE, "librcn_hip_exp.so")      # + the parked experiments (tests / tools only; build.py: build_experiments)
 
 F32, F64 = 0, 1
 
@@ -123,7 +122,6 @@ SIGNATURES = {
 
 FALLBACKS_SEEN = 0          # step-downs from the resident kernel counted over every context this process has closed (rcn.py: RCN.close)
 _lib = None
-_lib_exp = None
 _hip_preloaded = False
 
 
@@ -172,14 +170,6 @@ def load(path: str | None = None) -> C.CDLL:
     if path is None:
         _lib = lib
     return lib
-
-
-def load_experiments() -> C.CDLL:
-    """The build that also carries the parked experiments (dense paths 3 and 4).  Not used by the product path."""
-    global _lib_exp
-    if _lib_exp is None:
-        _lib_exp = load(LIB_EXP_PATH)
-    return _lib_exp
 
 
 def check(lib, ctx, status: int) -> None:

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librcn_hip.so")
 SOURCES = ["rcn_hip_api.hip"]
-DEPS = ["rcn_hip_api_shapes.ipp", "rcn_hip_api_dense_launch.ipp", "rcn_hip_api_xcd.ipp", "rcn_hip_api_p2p.ipp", "rcn_hip_api_params.ipp", "rcn_hip_api_operators.ipp", "rcn_hip_api_features.ipp", "rcn_hip_api_dense.ipp", "rcn_hip_api_dp.ipp", "rcn_hip_api_sets.ipp", "common.hpp", "dense.hpp", "dense_pipe.hpp", "dense_p2.hpp", "features.hpp", "ops.hpp", "dp_rccl.hpp", "serve.hpp", "dp_p2p.hpp", "dense_p2_dp.hpp", "dense_xcd.hpp", "dense_wide.hpp", "dense_p2_persist.hpp", "dense_p2_step.hpp", os.path.join("..", "..", "include", "rcn_hip.h")]
+DEPS = ["rcn_hip_api_shapes.ipp", "rcn_hip_api_dense_launch.ipp", "rcn_hip_api_xcd.ipp", "rcn_hip_api_p2p.ipp", "rcn_hip_api_params.ipp", "rcn_hip_api_operators.ipp", "rcn_hip_api_features.ipp", "rcn_hip_api_dense.ipp", "rcn_hip_api_dp.ipp", "rcn_hip_api_sets.ipp", "common.hpp", "dense.hpp", "dense_pipe.hpp", "dense_p2.hpp", "features.hpp", "ops.hpp", "dp_rccl.hpp", "serve.hpp", "dp_p2p.hpp", "dense_p2_dp.hpp", "dense_xcd.hpp", "dense_wide.hpp", os.path.join("..", "..", "include", "rcn_hip.h")]
 # -ffp-contract=off: the reference (rustc) never fuses a*b+c; the operator kernels reproduce its f64 rounding.
 FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wno-unused-result",
          "-Wno-pass-failed"]
@@ -30,20 +30,6 @@ def stale() -> bool:
         return True
     t = os.path.getmtime(LIB)
     return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + DEPS)
-
-
-LIB_EXP = os.path.join(HERE, "librcn_hip_exp.so")   # the same library + the parked experiments (dense paths 3, 4, one-object step); tests / tools only
-
-
-def build_experiments(force: bool = False, verbose: bool = False) -> str:
-    deps = [os.path.join(CSRC, f) for f in SOURCES + DEPS]
-    if not force and os.path.exists(LIB_EXP) and all(os.path.getmtime(f) <= os.path.getmtime(LIB_EXP) for f in deps):
-        return LIB_EXP
-    cmd = [hipcc()] + FLAGS + ["-DRCN_HIP_EXPERIMENTS", "-o", LIB_EXP] + [os.path.join(CSRC, s) for s in SOURCES]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    return LIB_EXP
 
 
 LIBX = os.path.join(HERE, "librcn_hipx.so")          # Track X (trainable conv net; include/rcn_hipx.h)
@@ -85,7 +71,6 @@ def build(force: bool = False, verbose: bool = False) -> str:
         subprocess.run(cmd, check=True)
     build_cli(force, verbose)
     build_x(force, verbose)
-    build_experiments(force, verbose)
     return LIB
 
 

@@ -14,10 +14,6 @@
 #include "convnet_bf16.hpp"
 #include "convnet_halo.hpp"
 
-#ifndef RCNX_ABL
-#define RCNX_ABL 0
-#endif
-
 namespace rcnx {
 
 // TS: storage type of X, Y, EPI 3's gate tensor (passed through `bias`) and the pooled-resolution input (convnet.hpp, Chunk4): with
@@ -162,30 +158,22 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((CB ==
         int cb = 0, kh = 0;
 #pragma unroll 1
         for (int ph = 0; ph < nph; ++ph) {
-            // RCNX_ABL (diagnostic builds only, tools/ablate_halo_bf16.sh; never defined in the library): what a phase costs without its
-            // global loads (1), without its LDS stores too (2), without its barriers too (3); 4: everything but the MFMAs
-            const bool abl_first = first;
-            if (!first && RCNX_ABL != 3) __syncthreads();             // the previous phase's operands have been consumed
+            if (!first) __syncthreads();                               // the previous phase's operands have been consumed
             first = false;
-            if (RCNX_ABL < 2 || RCNX_ABL >= 4 || abl_first) {
-                if (kh == 0) halo_store();
-                b_store();
-            }
-            if (RCNX_ABL != 3) __syncthreads();
+            if (kh == 0) halo_store();
+            b_store();
+            __syncthreads();
             const int nkh = kh == 2 ? 0 : kh + 1, ncb = kh == 2 ? cb + CB : cb;
-            if (RCNX_ABL == 0 || RCNX_ABL >= 4) {
-                // ONE load site for "this item's next phase" and "the next item's first phase": as two sites the compiler loaded the
-                // second one into other registers, copied them over behind an s_waitcnt vmcnt(0), and -- those registers doubling as
-                // LDS-read destinations -- made every phase wait for most of its just-issued loads BEFORE its MFMAs (ISA, round 4)
-                const bool same = ph + 1 < nph;
-                const Item li = same ? cur : nxt;
-                const int lcb = same ? ncb : 0, lkh = same ? nkh : 0;
-                if (same || nitem < n_items) {
-                    b_load(li, lcb, lkh);
-                    if (lkh == 0) halo_load(li, lcb);
-                }
+            // ONE load site for "this item's next phase" and "the next item's first phase": as two sites the compiler loaded the
+            // second one into other registers, copied them over behind an s_waitcnt vmcnt(0), and -- those registers doubling as
+            // LDS-read destinations -- made every phase wait for most of its just-issued loads BEFORE its MFMAs (ISA, round 4)
+            const bool same = ph + 1 < nph;
+            const Item li = same ? cur : nxt;
+            const int lcb = same ? ncb : 0, lkh = same ? nkh : 0;
+            if (same || nitem < n_items) {
+                b_load(li, lcb, lkh);
+                if (lkh == 0) halo_load(li, lcb);
             }
-            if (RCNX_ABL != 4)
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
                 const __bf16* a = &Hs[((py + kh) * Gm::HWD + px + kw) * LDC + 8 * h];
@@ -194,19 +182,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((CB ==
                 for (int ks = 0; ks < CB / 16; ++ks) {
                     bf16x8 af[MG];
 #pragma unroll
-                    for (int g = 0; g < MG; ++g) {
-                        if (RCNX_ABL == 5) { asm volatile("" : "=v"(af[g])); continue; }                 // 5: the MFMAs without their LDS reads
-                        af[g] = *reinterpret_cast<const bf16x8*>(a + g * 8 * Gm::HWD * LDC + 16 * ks);
-                    }
+                    for (int g = 0; g < MG; ++g) af[g] = *reinterpret_cast<const bf16x8*>(a + g * 8 * Gm::HWD * LDC + 16 * ks);
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
-                        bf16x8 bf;
-                        if (RCNX_ABL == 5) asm volatile("" : "=v"(bf));
-                        else bf = *reinterpret_cast<const bf16x8*>(b + 32 * t * LDC + 16 * ks);
-                        if (RCNX_ABL == 6) {                                                             // 6: the LDS reads without the MFMAs
-                            asm volatile("" :: "v"(bf), "v"(af[0]));
-                            continue;
-                        }
+                        const bf16x8 bf = *reinterpret_cast<const bf16x8*>(b + 32 * t * LDC + 16 * ks);
 #pragma unroll
                         for (int g = 0; g < MG; ++g) acc[g][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[g], bf, acc[g][t], 0, 0, 0);
                     }

@@ -42,7 +42,7 @@ __device__ __forceinline__ void p2_a_body(
     const NetDesc& nd, T* __restrict__ params, const T* __restrict__ Xp, const T* __restrict__ Xn, int B,
     const T* __restrict__ a1, const T* __restrict__ d1, const T* __restrict__ d2, T scale, T* __restrict__ slab, int G,
     const T* __restrict__ loss_part, int n_loss, T loss_scale, T* __restrict__ loss_out, int do_update, int do_fwd, unsigned char* smem_raw,
-    T* __restrict__ fragimg = nullptr) {
+    T* __restrict__ fragimg) {
     using acc_t = typename Mfma16<T>::acc_t;
     using vec4 = typename Vec4<T>::type;
     T* red = reinterpret_cast<T*>(smem_raw);
@@ -165,7 +165,7 @@ template <typename T>
 __device__ __forceinline__ void p2_b_body(
     const NetDesc& nd, const T* __restrict__ params, const T* __restrict__ slab, int G, const T* __restrict__ Ys, int B,
     T* __restrict__ a1g, T* __restrict__ d1g, T* __restrict__ d2g, T* __restrict__ loss_part, unsigned char* smem_raw,
-    const T* __restrict__ fragimg = nullptr) {
+    const T* __restrict__ fragimg) {
     using acc_t = typename Mfma16<T>::acc_t;
     using vec4 = typename Vec4<T>::type;
     constexpr int kFrag = kP2BFrag;
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(512) void k_p2_fragimg(NetDesc nd, const float* __r
     for (int e = threadIdx.x; e < H; e += 512) p2_frag_scatter(0, F, e, H, params[nd.w_off[0] + H * F + e], img);
 }
 
-// ---- the two kernels of a step, and both in ONE kernel object -------------------------------------------------------
+// ---- the two kernels of a step -------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(kDenseThreads) void k_p2_a(
     NetDesc nd, T* __restrict__ params, const T* __restrict__ Xp, const T* __restrict__ Xn, int B,
@@ -358,25 +358,5 @@ __global__ __launch_bounds__(kP2BThreads) void k_p2_b(
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_dyn[];
     p2_b_body<T>(nd, params, slab, G, Ys, B, a1g, d1g, d2g, loss_part, smem_dyn, fragimg);
 }
-
-#ifdef RCN_HIP_EXPERIMENTS
-// The epoch loop alternates the two strictly, and the pair costs ~0.9 us more than the two back to back with themselves
-// (9.2 us vs 3.85 + 4.45).  Hypothesis tested here: the switch of kernel object (code, descriptor, LDS / register allocation)
-// between launches.  As two ROLES of one kernel object the step is 2 % SLOWER (9.75 vs 9.55 us), so that is not it; kept
-// behind RCN_HIP_P2_ONE_OBJECT=1 as the record of the experiment.
-static_assert(kDenseThreads == kP2BThreads, "one launch shape for both roles");
-inline size_t p2_ab_lds_elems() { return p2_a_lds_elems() > p2_b_lds_elems() ? p2_a_lds_elems() : p2_b_lds_elems(); }
-
-template <typename T>
-__global__ __launch_bounds__(kDenseThreads) void k_p2_ab(
-    int role, NetDesc nd, T* __restrict__ params, const T* __restrict__ Xp, const T* __restrict__ Xn, const T* __restrict__ Ys, int B,
-    T* __restrict__ a1, T* __restrict__ d1, T* __restrict__ d2, T scale, T* __restrict__ slab, int G, T* __restrict__ loss_part, int n_loss,
-    T loss_scale, T* __restrict__ loss_out, int do_update, int do_fwd) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_dyn[];
-    if (role == 0) p2_b_body<T>(nd, params, slab, G, Ys, B, a1, d1, d2, loss_part, smem_dyn);
-    else p2_a_body<T>(nd, params, Xp, Xn, B, a1, d1, d2, scale, slab, G, loss_part, n_loss, loss_scale, loss_out, do_update, do_fwd, smem_dyn);
-}
-
-#endif  // RCN_HIP_EXPERIMENTS
 
 }  // namespace rcn

@@ -30,14 +30,6 @@
 #include "dp_p2p.hpp"
 #include "dense_p2_dp.hpp"
 #include "dense_xcd.hpp"
-// Parked experiments (a resident kernel per epoch segment, one launch per step, both step kernels as roles of one kernel object):
-// correct, measured, slower than or equal to the default two-kernel pipeline.  They are compiled only into
-// librcn_hip_exp.so (-DRCN_HIP_EXPERIMENTS; mercer_research_amd/build.py: build_experiments), which their tests and the stamp tools
-// load; the shipping library does not carry them.
-#ifdef RCN_HIP_EXPERIMENTS
-#include "dense_p2_persist.hpp"
-#include "dense_p2_step.hpp"
-#endif
 #include <atomic>
 #include <chrono>
 
@@ -136,17 +128,10 @@ struct rcn_hip_ctx {
     int feat_kernel = 0;                    // 0 auto, 1 always the generic k_features (tests compare the two)
     float fd_mean = 0.f, fd_sd = 0.f, fd_rcp = 0.f;   // last (mean, sd) checked by standardise_fast_is_exact; fd_rcp = 0: divide
     bool fd_checked = false;
-    DevBuf pll;                             // persistent epoch kernel: tagged-word exchange buffers (dense_p2_persist.hpp)
-    size_t pll_B = 0;
-    unsigned ptag = 0;                      // last tag handed out; monotonic for the life of the context
-    unsigned* perr_dev = nullptr;           // sticky timeout word of the persistent kernel, and its pinned mirror
-    unsigned* perr_host = nullptr;
     int dense_path = 0;                     // 0 auto, 1 sample-tile kernels (dense.hpp), 2 feature-sliced pipeline (dense_pipe.hpp)
     DevBuf slab, xpack, ypack, p2buf;
     DevBuf fragimg;                         // tail parameters as k_p2_b's operand fragments (dense.hpp: p2_frag_scatter), f32 pipeline only
     bool frag_on = false;                   // set while enqueue_pipe_steps<float> runs: its k_p2_a / k_p2_b launches use the image
-    DevBuf stepx;                           // one-launch step (dense_p2_step.hpp): flags of the sample groups, then the tag word
-    size_t stepx_B = 0;
     size_t packed_B = 0, packed_nb = 0;     // what the epoch image currently holds (k_pack_epoch)
     size_t epoch_B = 0, epoch_nb = 0, epoch_seg = 0;   // rcn_hip_epoch_begin*_dev: the image holds batches 0..epoch_nb of a begun epoch
                                                        // (epoch_nb = 0: none; any other call that re-packs the image ends it)
@@ -340,9 +325,6 @@ void rcn_hip_destroy(rcn_hip_ctx* c) {
         if (c->xerrd) (void)hipFree(c->xerrd);
         for (auto& rs : c->sets) { rs.imgs.release(); rs.X.release(); rs.Y.release(); rs.perm.release(); rs.loss.release(); }
         if (c->pin_host) (void)hipHostFree(c->pin_host);
-        c->pll.release();
-        if (c->perr_dev) (void)hipFree(c->perr_dev);
-        if (c->perr_host) (void)hipHostFree(c->perr_host);
         if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     }
     delete c;
@@ -371,10 +353,8 @@ int rcn_hip_set_dense_path(rcn_hip_ctx* c, int mode) {
     RCN_TRY(check_ctx(c));
     if (mode < 0 || mode > 5)
         return fail(c, RCN_HIP_ERR_INVALID_ARG, "set_dense_path: mode must be 0 (auto), 1 (sample-tile), 2 (feature-sliced, two kernels per step), 5 (feature-sliced, resident "
-                                                "one-XCD kernel) -- or 3 / 4, parked experiments of librcn_hip_exp.so");
-#ifndef RCN_HIP_EXPERIMENTS
-    if (mode == 3 || mode == 4) return fail(c, RCN_HIP_ERR_UNSUPPORTED, "set_dense_path: modes 3 and 4 are parked experiments, compiled only into librcn_hip_exp.so (RCN_HIP_EXPERIMENTS)");
-#endif
+                                                "one-XCD kernel)");
+    if (mode == 3 || mode == 4) return fail(c, RCN_HIP_ERR_UNSUPPORTED, "set_dense_path: modes 3 and 4 (one resident kernel per epoch segment, one launch per step) were removed");
     if (mode >= 2 && !pipe_supported(c->nd)) return fail(c, RCN_HIP_ERR_UNSUPPORTED, "feature-sliced path needs >= 2 dense layers whose tail fits LDS");
     DevGuard g(c->device);
     if (mode == 5) {

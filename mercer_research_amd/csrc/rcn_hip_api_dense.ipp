@@ -37,10 +37,6 @@ static int epoch_impl(rcn_hip_ctx* c, const void* X, const void* Y, const int32_
     RCN_TRY(xcd_entry_check(c));
     RCN_TRY(ensure_dense_ws(c, B));
     if (use_pipe(c, B)) { RCN_TRY(ensure_pipe_ws(c, B)); RCN_TRY(ensure_pack_ws(c, B, nb)); }
-    const bool step = use_pipe(c, B) && use_step(c, B);
-#ifdef RCN_HIP_EXPERIMENTS
-    if (step) RCN_TRY(ensure_step_ws(c, B));
-#endif
     if (from_images && !(use_pipe(c, B) && feat_is_cpcp28(c)))
         return fail(c, RCN_HIP_ERR_UNSUPPORTED, "train_epoch_images: needs the default conv/pool stack on 28x28 input and a layer stack / batch size the "
                                                   "feature-sliced pipeline covers; use rcn_hip_features_dev + rcn_hip_train_epoch_dev otherwise");
@@ -50,13 +46,6 @@ static int epoch_impl(rcn_hip_ctx* c, const void* X, const void* Y, const int32_
         if (!launch) return RCN_HIP_OK;
         return enqueue_xcd_epoch(c, X, Y, perm, B, nb, eta, loss_dev, from_images, false, 0, 0);
     }
-#ifdef RCN_HIP_EXPERIMENTS
-    if (use_persist(c, B) && !from_images) {
-        // no graph: one resident kernel per segment of the epoch image runs all of its steps
-        if (!launch) return RCN_HIP_OK;
-        return enqueue_persist_epoch(c, X, Y, perm, B, nb, eta, loss_dev);
-    }
-#endif
     // LDS attributes are per kernel variant and cached (set_dyn_lds); hipFuncSetAttribute is not a stream operation,
     // so the first capture of a variant may set it while capturing.
 
@@ -68,11 +57,6 @@ static int epoch_impl(rcn_hip_ctx* c, const void* X, const void* Y, const int32_
         hipGraph_t graph = nullptr;
         HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         int st = RCN_HIP_OK;
-#ifdef RCN_HIP_EXPERIMENTS
-        if (step) {
-            st = enqueue_step_epoch(c, X, Y, perm, B, nb, eta, loss_dev, from_images);
-        } else
-#endif
         if (use_pipe(c, B)) {
             st = c->dtype == RCN_HIP_F64 ? enqueue_pipe_steps<double>(c, X, Y, perm, B, nb, eta, loss_dev, from_images)
                                          : enqueue_pipe_steps<float>(c, X, Y, perm, B, nb, eta, loss_dev, from_images);

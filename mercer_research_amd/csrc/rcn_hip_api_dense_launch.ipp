@@ -1,5 +1,5 @@
 // rcn_hip_api_dense_launch.ipp -- part of the ONE translation unit rcn_hip_api.hip (included there, in this order; shares its anonymous namespace and the
-// extern "C" block): dense launches: sample-tile / pipeline / two-kernel forms, the parked one-launch-per-step and one-kernel-per-segment experiments.
+// extern "C" block): dense launches: sample-tile / pipeline / two-kernel forms.
 // ---- dense launches ---------------------------------------------------------------------------------------------
 void drop_graphs(rcn_hip_ctx* c);
 void drop_img_graphs(rcn_hip_ctx* c);
@@ -112,14 +112,6 @@ int ensure_pipe_ws(rcn_hip_ctx* c, size_t B) {
     return RCN_HIP_OK;
 }
 
-// RCN_HIP_P2_ONE_OBJECT=1: both kernels of a pipelined step as roles of one kernel object (dense_p2.hpp: k_p2_ab).  Measured 2 % slower
-// than two kernels (9.75 vs 9.55 us/step), so off by default: the cost of alternating is not the switch of kernel object.
-#ifdef RCN_HIP_EXPERIMENTS
-static bool p2_one_object() { static const int v = [] { const char* e = std::getenv("RCN_HIP_P2_ONE_OBJECT"); return e ? std::atoi(e) : 0; }(); return v != 0; }
-#else
-static constexpr bool p2_one_object() { return false; }
-#endif
-
 template <typename T>
 int launch_pipe_a(rcn_hip_ctx* c, const void* xp, const void* xn, size_t B, double scale, void* loss_out, double loss_scale, bool do_update, bool do_fwd) {
     const NetDesc& nd = c->nd;
@@ -128,16 +120,9 @@ int launch_pipe_a(rcn_hip_ctx* c, const void* xp, const void* xn, size_t B, doub
     const int n_loss = (int)((B + kPipeTs - 1) / kPipeTs);
     if (p2_supported(nd, B)) {       // lean specialisation: one hidden layer <= 32, classes <= 16, B % 256 == 0
         T* a1 = (T*)c->p2buf.p; T* d1 = a1 + B * kP2H; T* d2 = d1 + B * kP2H;
-#ifdef RCN_HIP_EXPERIMENTS
-        if (p2_one_object())
-            hipLaunchKernelGGL((k_p2_ab<T>), dim3(grid), dim3(kDenseThreads), p2_ab_lds_elems() * sizeof(T), c->stream, 1, nd, (T*)c->params.p, (const T*)xp,
-                               (const T*)xn, (const T*)nullptr, (int)B, a1, d1, d2, (T)scale, (T*)c->slab.p, G, (T*)c->loss_part.p, n_loss, (T)loss_scale,
-                               (T*)loss_out, do_update ? 1 : 0, do_fwd ? 1 : 0);
-        else
-#endif
-            hipLaunchKernelGGL((k_p2_a<T>), dim3(grid), dim3(kDenseThreads), p2_a_lds_elems() * sizeof(T), c->stream, nd, (T*)c->params.p, (const T*)xp,
-                               (const T*)xn, (int)B, (const T*)a1, (const T*)d1, (const T*)d2, (T)scale, (T*)c->slab.p, G, (const T*)c->loss_part.p, n_loss,
-                               (T)loss_scale, (T*)loss_out, do_update ? 1 : 0, do_fwd ? 1 : 0, c->frag_on ? (T*)c->fragimg.p : (T*)nullptr);
+        hipLaunchKernelGGL((k_p2_a<T>), dim3(grid), dim3(kDenseThreads), p2_a_lds_elems() * sizeof(T), c->stream, nd, (T*)c->params.p, (const T*)xp,
+                           (const T*)xn, (int)B, (const T*)a1, (const T*)d1, (const T*)d2, (T)scale, (T*)c->slab.p, G, (const T*)c->loss_part.p, n_loss,
+                           (T)loss_scale, (T*)loss_out, do_update ? 1 : 0, do_fwd ? 1 : 0, c->frag_on ? (T*)c->fragimg.p : (T*)nullptr);
         HIP_TRY(c, hipGetLastError());
         return RCN_HIP_OK;
     }
@@ -154,16 +139,9 @@ int launch_pipe_b(rcn_hip_ctx* c, const void* ys, size_t B) {
     const NetDesc& nd = c->nd;
     if (p2_supported(nd, B)) {
         T* a1 = (T*)c->p2buf.p; T* d1 = a1 + B * kP2H; T* d2 = d1 + B * kP2H;
-#ifdef RCN_HIP_EXPERIMENTS
-        if (p2_one_object())
-            hipLaunchKernelGGL((k_p2_ab<T>), dim3((unsigned)(B / kP2Ts)), dim3(kDenseThreads), p2_ab_lds_elems() * sizeof(T), c->stream, 0, nd, (T*)c->params.p,
-                               (const T*)nullptr, (const T*)nullptr, (const T*)ys, (int)B, a1, d1, d2, (T)0, (T*)c->slab.p, pipe_slices(nd), (T*)c->loss_part.p, 0,
-                               (T)0, (T*)nullptr, 0, 0);
-        else
-#endif
-            hipLaunchKernelGGL((k_p2_b<T>), dim3((unsigned)(B / kP2Ts)), dim3(kP2BThreads), p2_b_lds_elems() * sizeof(T), c->stream, nd, (const T*)c->params.p,
-                               (const T*)c->slab.p, pipe_slices(nd), (const T*)ys, (int)B, a1, d1, d2, (T*)c->loss_part.p,
-                               c->frag_on ? (const T*)c->fragimg.p : (const T*)nullptr);
+        hipLaunchKernelGGL((k_p2_b<T>), dim3((unsigned)(B / kP2Ts)), dim3(kP2BThreads), p2_b_lds_elems() * sizeof(T), c->stream, nd, (const T*)c->params.p,
+                           (const T*)c->slab.p, pipe_slices(nd), (const T*)ys, (int)B, a1, d1, d2, (T*)c->loss_part.p,
+                           c->frag_on ? (const T*)c->fragimg.p : (const T*)nullptr);
         HIP_TRY(c, hipGetLastError());
         return RCN_HIP_OK;
     }
@@ -294,7 +272,7 @@ int enqueue_pipe_steps(rcn_hip_ctx* c, const void* X, const void* Y, const int32
     // parameter vector and kept current by k_p2_a's tail tiles for the rest of this call
     struct FragGuard { rcn_hip_ctx* c; ~FragGuard() { c->frag_on = false; } } frag_guard{c};
     if constexpr (std::is_same<T, float>::value) {
-        if (p2_supported(c->nd, B) && !p2_one_object() && !c->opt.no_fragimg && c->fragimg.p) {
+        if (p2_supported(c->nd, B) && !c->opt.no_fragimg && c->fragimg.p) {
             hipLaunchKernelGGL(k_p2_fragimg, dim3(1), dim3(512), 0, c->stream, c->nd, (const float*)c->params.p, (float*)c->fragimg.p);
             HIP_TRY(c, hipGetLastError());
             c->frag_on = true;
@@ -311,140 +289,3 @@ int enqueue_pipe_steps(rcn_hip_ctx* c, const void* X, const void* Y, const int32
     }
     return RCN_HIP_OK;
 }
-
-#ifdef RCN_HIP_EXPERIMENTS
-constexpr long long kPersistTimeoutTicks = 5000000LL;        // 50 ms of the 100 MHz wall clock per wait
-
-// ---- one launch per step (dense_p2_step.hpp): A(F0) S0 S1 ... S_{nb-1}, S_j = sample groups of batch j + feature slices
-// (update from batch j, partials of batch j+1) + tail tiles in ONE kernel; the last node advances the tag word so the
-// captured graph can be replayed.
-bool use_step(const rcn_hip_ctx* c, size_t B) {
-    if (c->dtype != RCN_HIP_F32 || !step_supported(c->nd, B)) return false;
-    if (c->dense_path == 4) return true;
-    if (c->dense_path != 0) return false;
-    static const int auto_on = [] { const char* e = std::getenv("RCN_HIP_STEP_KERNEL"); return e ? std::atoi(e) : 0; }();
-    return auto_on != 0;
-}
-
-int ensure_step_ws(rcn_hip_ctx* c, size_t B) {
-    const size_t NS = B / kP2Ts, bytes = (NS * kStepFlagStride + 64) * sizeof(unsigned) + B * kP2H * sizeof(pw_t);
-    if (!c->perr_dev) {
-        HIP_TRY(c, hipMalloc((void**)&c->perr_dev, 256));
-        HIP_TRY(c, hipHostMalloc((void**)&c->perr_host, 64, hipHostMallocDefault));
-        *c->perr_host = 0;
-        HIP_TRY(c, hipMemsetAsync(c->perr_dev, 0, 256, c->stream));
-    }
-    if (*c->perr_host != 0)
-        return fail(c, RCN_HIP_ERR_HIP, "train_epoch: a wait inside the one-launch step timed out in an earlier call; the parameters are no longer "
-                                        "consistent.  rcn_hip_set_dense_path(ctx, 2) avoids this kernel");
-    if (c->stepx_B != B || c->stepx.cap < bytes) {
-        HIP_TRY(c, ws_ensure(c, c->stepx, bytes));
-        HIP_TRY(c, hipMemsetAsync(c->stepx.p, 0, c->stepx.cap, c->stream));       // flags 0, tag word 0: the first tag is 1
-        drop_graphs(c);                                                            // cached graphs count on the tag word's history
-        c->stepx_B = B;
-    }
-    return RCN_HIP_OK;
-}
-
-int enqueue_step_epoch(rcn_hip_ctx* c, const void* X, const void* Y, const int32_t* perm, size_t B, size_t nb, double eta, void* loss_dev, bool from_images) {
-    using T = float;
-    const NetDesc& nd = c->nd;
-    const size_t G = pipe_slices(nd), Cc = nd.dims[nd.L], es = sizeof(T), NS = B / kP2Ts;
-    const double scale = eta / (double)B, loss_scale = 1.0 / (2.0 * (double)B);
-    const size_t seg = nb <= pack_segment(c, B) ? nb : pack_segment(c, B);
-    auto slot = [&](size_t j) { return ((j / seg) % 2) * seg + j % seg; };
-    auto xb = [&](size_t j) { return (const T*)((const char*)c->xpack.p + slot(j) * G * B * 16 * es); };
-    auto yb = [&](size_t j) { return (const T*)((const char*)c->ypack.p + slot(j) * B * Cc * es); };
-    auto pack = [&](size_t j0) {
-        const size_t n = nb - j0 < seg ? nb - j0 : seg;
-        return from_images ? launch_feat_pack<T>(c, (const uint8_t*)X, Y, perm, B, j0, n, (int)((j0 / seg) % 2), seg)
-                           : launch_pack<T>(c, X, Y, perm, B, j0, n, (int)((j0 / seg) % 2), seg);
-    };
-    StepBufs sb;
-    sb.slab = (T*)c->slab.p;
-    sb.a1 = (T*)c->p2buf.p; sb.d1 = sb.a1 + B * kP2H; sb.d2 = sb.d1 + B * kP2H;
-    sb.loss = (T*)c->loss_part.p;
-    sb.oflag = (unsigned*)c->stepx.p;
-    unsigned* tagw = sb.oflag + NS * kStepFlagStride + 32;
-    sb.tag = tagw;
-    sb.d1w = (pw_t*)(sb.oflag + NS * kStepFlagStride + 64);
-    static const int first_look = [] { const char* e = std::getenv("RCN_HIP_STEP_FIRST_LOOK"); return e ? std::atoi(e) : 320; }();   // 100 MHz ticks
-    const int grid = step_grid(nd, B);
-    RCN_TRY(pack(0));
-    RCN_TRY(launch_pipe_a<T>(c, xb(0), xb(0), B, scale, nullptr, loss_scale, false, true));
-    for (size_t j = 0; j < nb; ++j) {
-        const bool more = j + 1 < nb;
-        if (more && (j + 1) % seg == 0) RCN_TRY(pack(j + 1));
-        T* lj = loss_dev ? (T*)loss_dev + j : nullptr;
-        hipLaunchKernelGGL(k_p2_step, dim3(grid), dim3(kPersistThreads), 0, c->stream, nd, (T*)c->params.p, xb(j), more ? xb(j + 1) : xb(j), yb(j), (int)B,
-                           (int)G, (T)scale, (T)loss_scale, lj, sb, (unsigned)(j + 1), more ? 1 : 0, c->perr_dev, kPersistTimeoutTicks, first_look);
-        HIP_TRY(c, hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_add_u32, dim3(1), dim3(1), 0, c->stream, tagw, (unsigned)(nb + 1));
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->perr_host, c->perr_dev, 4, hipMemcpyDeviceToHost, c->stream));     // looked at by the next call
-    return RCN_HIP_OK;
-}
-
-// ---- one resident kernel per epoch segment (dense_p2_persist.hpp) ------------------------------------------------
-bool use_persist(const rcn_hip_ctx* c, size_t B) {
-    if (c->dtype != RCN_HIP_F32 || !persist_supported(c->nd, B)) return false;
-    if (c->dense_path == 3) return true;
-    if (c->dense_path != 0) return false;
-    static const int auto_on = [] { const char* e = std::getenv("RCN_HIP_PERSIST"); return e ? std::atoi(e) : 0; }();
-    return auto_on != 0;
-}
-
-
-int enqueue_persist_epoch(rcn_hip_ctx* c, const void* X, const void* Y, const int32_t* perm, size_t B, size_t nb, double eta, void* loss_dev) {
-    const NetDesc& nd = c->nd;
-    const size_t G = pipe_slices(nd), Cc = nd.dims[nd.L];
-    if (!c->perr_dev) {
-        HIP_TRY(c, hipMalloc((void**)&c->perr_dev, 256));
-        HIP_TRY(c, hipHostMalloc((void**)&c->perr_host, 64, hipHostMallocDefault));
-        *c->perr_host = 0;
-        HIP_TRY(c, hipMemsetAsync(c->perr_dev, 0, 256, c->stream));
-    }
-    if (*c->perr_host != 0)
-        return fail(c, RCN_HIP_ERR_HIP, "train_epoch: a resident epoch kernel timed out in an earlier call (its workgroups were not all on the GPU at "
-                                        "once -- is the device shared?); the parameters are no longer consistent.  rcn_hip_set_dense_path(ctx, 2) avoids this kernel");
-    const size_t bytes = persist_bytes(B, G);
-    if (c->pll_B != B || c->pll.cap < bytes) {
-        HIP_TRY(c, c->pll.ensure(bytes));
-        HIP_TRY(c, hipMemsetAsync(c->pll.p, 0, c->pll.cap, c->stream));      // flag / tag 0 never matches (tags start at 1)
-        c->pll_B = B;
-    }
-    const size_t NS = B / kP2Ts;
-    PersistBufs pb;
-    float* f = (float*)c->pll.p;
-    pb.slab = f; f += 2 * NS * G * kP2Ts * kP2H;
-    pb.d1 = f;   f += 2 * B * kP2H;
-    pb.a1 = f;   f += 2 * B * kP2H;
-    pb.d2 = f;   f += 2 * B * kP2C;
-    pb.loss = f; f += 2 * NS;
-    unsigned* u = (unsigned*)f;
-    pb.sflag = u; u += 64;
-    pb.oflag = u; u += NS;
-    pb.tail = (pw_t*)(((uintptr_t)u + 63) & ~(uintptr_t)63);
-    const size_t seg = nb <= pack_segment(c, B) ? nb : pack_segment(c, B);
-    const float scale = (float)(eta / (double)B), loss_scale = (float)(1.0 / (2.0 * (double)B));
-    const int grid = persist_grid(nd, B);
-    for (size_t j0 = 0; j0 < nb; j0 += seg) {
-        const size_t n = nb - j0 < seg ? nb - j0 : seg;
-        const int half = (int)((j0 / seg) % 2);
-        RCN_TRY(launch_pack<float>(c, X, Y, perm, B, j0, n, half, seg));
-        const float* xs = (const float*)c->xpack.p + (size_t)half * seg * G * B * 16;
-        const float* ys = (const float*)c->ypack.p + (size_t)half * seg * B * Cc;
-        hipLaunchKernelGGL(k_p2_epoch, dim3(grid), dim3(kPersistThreads), 0, c->stream, nd, (float*)c->params.p, xs, ys, (int)B, (int)n, (int)G, scale,
-                           loss_scale, loss_dev ? (float*)loss_dev + j0 : (float*)nullptr, pb, c->ptag, c->perr_dev, kPersistTimeoutTicks);
-        HIP_TRY(c, hipGetLastError());
-        c->ptag += (unsigned)n + 2;
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->perr_host, c->perr_dev, 4, hipMemcpyDeviceToHost, c->stream));     // looked at by the next call
-    return RCN_HIP_OK;
-}
-
-#else
-static bool use_step(const rcn_hip_ctx*, size_t) { return false; }
-static bool use_persist(const rcn_hip_ctx*, size_t) { return false; }
-#endif

@@ -168,7 +168,7 @@ int enqueue_pipe_steps_dp(rcn_hip_ctx* c, const void* X, const void* Y, const in
     // the in-kernel exchange form keeps k_p2_b's operand image current too (its tail tiles apply the summed gradient themselves)
     struct FragGuard { rcn_hip_ctx* c; ~FragGuard() { c->frag_on = false; } } frag_guard{c};
     if constexpr (std::is_same<T, float>::value) {
-        if (fused && !p2_one_object() && !c->opt.no_fragimg && c->fragimg.p) {
+        if (fused && !c->opt.no_fragimg && c->fragimg.p) {
             hipLaunchKernelGGL(k_p2_fragimg, dim3(1), dim3(512), 0, c->stream, c->nd, (const float*)c->params.p, (float*)c->fragimg.p);
             HIP_TRY(c, hipGetLastError());
             c->frag_on = true;

@@ -62,6 +62,6 @@ int rcn_hip_params_dev(rcn_hip_ctx* c, void** p, int64_t* count) {
     if (!c || !p || !count) return RCN_HIP_ERR_INVALID_ARG;
     *p = c->params.p; *count = c->nd.P;
     c->params_set = true;      // the caller may fill the buffer directly (e.g. a DP broadcast)
-    if ((c->p2p.err_host && *c->p2p.err_host != 0) || (c->perr_host && *c->perr_host != 0) || (c->xerr_host && *c->xerr_host != 0)) return sticky_errors(c);   // no sync here: last known state
+    if ((c->p2p.err_host && *c->p2p.err_host != 0) || (c->xerr_host && *c->xerr_host != 0)) return sticky_errors(c);   // no sync here: last known state
     return RCN_HIP_OK;
 }

@@ -488,7 +488,7 @@ int xcd_heal(rcn_hip_ctx* c) {
     return RCN_HIP_OK;
 }
 
-// The in-kernel waits (peer exchange, resident / one-launch step kernels) are bounded: a wait that expires sets a sticky
+// The in-kernel waits (peer exchange, resident one-XCD kernel) are bounded: a wait that expires sets a sticky
 // device word, every later kernel of that family drains, and the updates of the call are only partly applied.  The word is
 // copied back asynchronously at the end of each epoch call; after a stream synchronise it is current.  Every entry point
 // that tells the caller "the work is complete / here are the parameters" calls this behind its synchronise.
@@ -498,8 +498,6 @@ int sticky_errors(rcn_hip_ctx* c) {
             return fail(c, RCN_HIP_ERR_HIP, "data-parallel exchange: rank " + std::to_string(c->dp_rank) + " timed out waiting for peer data (sticky word " +
                                                 std::to_string(*c->p2p.err_host) + "); the last call's updates are incomplete and the replicas are no longer in step");
     }
-    if (c->perr_host && *c->perr_host != 0)
-        return fail(c, RCN_HIP_ERR_HIP, "a bounded wait inside the resident / one-launch step kernel expired; the last call's updates are incomplete");
     if (c->xerr_host && *c->xerr_host != 0) {
         if (!c->xcd_dp_used && c->opt.xcd_auto_fallback && !c->replaying) return xcd_heal(c);
         c->xlast = xcd_describe(c, true);

@@ -80,8 +80,8 @@ class RCN:
 
     def __init__(self, classes: int, convpool_cfg: Sequence[RCNLayer], feedforward_cfg: Sequence[int],
                  training_path: str = "", testing_path: str = "", *, input_shape: Tuple[int, int] = (28, 28),
-                 dtype: int = F32, device: int = 0, stream: Optional[int] = None, experiments: bool = False):
-        self._lib = _lib.load_experiments() if experiments else _lib.load()
+                 dtype: int = F32, device: int = 0, stream: Optional[int] = None):
+        self._lib = _lib.load()
         self._ctx = C.c_void_p()
         self.classes = int(classes)
         self.convpool_cfg = list(convpool_cfg)
@@ -136,7 +136,7 @@ class RCN:
         self._ck(self._lib.rcn_hip_synchronize(self._ctx))
 
     def set_dense_path(self, mode: int):
-        """0 auto, 1 sample-tile kernels, 2 feature-sliced pipeline, 3 resident epoch kernel, 4 one launch per step (include/rcn_hip.h)."""
+        """0 auto, 1 sample-tile kernels, 2 feature-sliced pipeline, 5 resident one-XCD kernel; 3 and 4 were removed (include/rcn_hip.h)."""
         self._ck(self._lib.rcn_hip_set_dense_path(self._ctx, int(mode)))
 
     def set_option(self, name: str, value: int):
