@@ -14,12 +14,14 @@
 #include <random>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "convnet.hpp"
 #include "convnet_bf16.hpp"
 #include "convnet_halo.hpp"
 #include "convnet_halo_bf16.hpp"
+#include "convnet_select.hpp"
 #include "convnet_sgd.hpp"
 
 using namespace rcnx;
@@ -59,57 +61,8 @@ struct Key { const void* x; const void* y; int B; float lr; const void* loss;
 
 }  // namespace
 
-// Kernel-selection knobs, PER NET (round 4; before, most were read from the environment into function-local statics at first use:
-// frozen process-wide, two nets of one process could not differ, and rcn_hipx_plan reported whatever the first call had latched).
-// The environment variable of the same meaning only seeds the default when a net (or a plan) is created.
-struct XOptions {
-    int halo = 1;             // "halo"            RCN_HIPX_HALO            bf16: the LDS-tiled 3x3 kernels (0: implicit GEMM only)
-    int bf16_pipe = 1;        // "bf16_pipe"       RCN_HIPX_BF16_PIPE       bf16: the software-pipelined LDS-tiled kernel (k_conv3x3_halo_bf16p)
-    int bf16_1cb = 1;         // "bf16_1cb"        RCN_HIPX_BF16_1CB        bf16: the resident-weights form for 32-channel layers
-    int bf16_rows16 = 0;      // "bf16_rows16"     RCN_HIPX_BF16_ROWS16     bf16 storage: 16 x 16 pixel blocks (two row groups per wave) where the map's height allows
-    int halo_wgrad = 1;       // "halo_wgrad"      RCN_HIPX_HALO_WGRAD      the LDS-tiled weight-gradient kernels
-    int fuse_pool_bwd = 1;    // "fuse_pool_bwd"   RCN_HIPX_FUSE_POOL_BWD   gradient kernels unpool while staging (no k_pool_bwd)
-    int head = 1;             // "head"            RCN_HIPX_HEAD            the classifier head as one launch (k_head_f32)
-    int xcd_remap = 0;        // "xcd_remap"       RCN_HIPX_XCD_REMAP       implicit-GEMM weight gradient: XCD-aware block order
-    int pix_per_chunk = 0;    // "pix_per_chunk"   RCN_HIPX_PIX_PER_CHUNK   pixels per weight-gradient chunk (0: by the workgroup target)
-    int wg_target = 4096;     // "wg_target"       RCN_HIPX_WG_TARGET       workgroups aimed at by the implicit-GEMM weight gradient
-    int wgh_f32_target = 512; // "wgh_f32_target"  RCN_HIPX_WGH_F32_TARGET  ... by the fp32 LDS-tiled weight gradient
-    int wgh_target = 256;     // "wgh_target"      RCN_HIPX_WGH_TARGET      ... by the bf16 LDS-tiled weight gradient
-    int wgb_policy = 1;       // "wgb_policy"      RCN_HIPX_WGB_POLICY      bf16 implicit-GEMM weight gradient: narrower tiles / shorter chunks below 2 waves per SIMD
-    int wgf_policy = 1;       // "wgf_policy"      RCN_HIPX_WGF_POLICY      fp32: the same
-    int halo_f32_slots = 0;   // "halo_f32_slots"  RCN_HIPX_HALO_F32_SLOTS  resident workgroups assumed for the looping kernels (0: asked from the runtime)
-};
-namespace {
-struct XOptDesc { const char* name; const char* env; int XOptions::*field; int lo, hi; };
-const XOptDesc kXOptTable[] = {
-    {"halo", "RCN_HIPX_HALO", &XOptions::halo, 0, 1},
-    {"bf16_pipe", "RCN_HIPX_BF16_PIPE", &XOptions::bf16_pipe, 0, 1},
-    {"bf16_1cb", "RCN_HIPX_BF16_1CB", &XOptions::bf16_1cb, 0, 1},
-    {"bf16_rows16", "RCN_HIPX_BF16_ROWS16", &XOptions::bf16_rows16, 0, 1},
-    {"halo_wgrad", "RCN_HIPX_HALO_WGRAD", &XOptions::halo_wgrad, 0, 1},
-    {"fuse_pool_bwd", "RCN_HIPX_FUSE_POOL_BWD", &XOptions::fuse_pool_bwd, 0, 1},
-    {"head", "RCN_HIPX_HEAD", &XOptions::head, 0, 1},
-    {"xcd_remap", "RCN_HIPX_XCD_REMAP", &XOptions::xcd_remap, 0, 1},
-    {"pix_per_chunk", "RCN_HIPX_PIX_PER_CHUNK", &XOptions::pix_per_chunk, 0, 1 << 20},
-    {"wg_target", "RCN_HIPX_WG_TARGET", &XOptions::wg_target, 1, 1 << 20},
-    {"wgh_f32_target", "RCN_HIPX_WGH_F32_TARGET", &XOptions::wgh_f32_target, 1, 1 << 20},
-    {"wgh_target", "RCN_HIPX_WGH_TARGET", &XOptions::wgh_target, 1, 1 << 20},
-    {"wgb_policy", "RCN_HIPX_WGB_POLICY", &XOptions::wgb_policy, 0, 1},
-    {"wgf_policy", "RCN_HIPX_WGF_POLICY", &XOptions::wgf_policy, 0, 1},
-    {"halo_f32_slots", "RCN_HIPX_HALO_F32_SLOTS", &XOptions::halo_f32_slots, 0, 1 << 20},
-};
-void seed_options(XOptions& o) {
-    for (const XOptDesc& d : kXOptTable) {
-        const char* e = std::getenv(d.env);
-        if (!e || !*e) continue;
-        const long long v = std::atoll(e);
-        if (v >= d.lo && v <= d.hi) o.*(d.field) = (int)v;
-    }
-}
-}  // namespace
-
-struct rcn_hipx_net {
-    XOptions opt;
+// precision, store16, tiling and the kernel-selection options are the net's Selection (convnet_select.hpp): all that choosing a kernel reads
+struct rcn_hipx_net : Selection {
     int device = 0, in_h = 0, in_w = 0, in_c = 0, max_batch = 0, classes = 0;
     hipStream_t stream = nullptr; bool own_stream = false;
     // The backward pass can run a layer's weight gradient on a second stream beside the input-gradient chain: the two only share dZ,
@@ -127,11 +80,6 @@ struct rcn_hipx_net {
     Buf* slab_sel = nullptr;                // where the weight-gradient launch in progress puts its partial tiles (a layer's slab)
     ReduceJobs jobs{};                      // the step's pending slab reductions
     Buf wb16; PrepJobs prep{}; long long prep_blocks = 0;      // bf16 mode: every layer's bf16 operand copies, made by ONE launch per step
-    int precision = RCN_HIPX_FP32;          // GEMM operand precision of forward / dgrad (rcn_hipx_set_precision)
-    // RCN_HIPX_BF16_STORED: bf16 operands AND the convolutional stage's activations / gradients (every conv and pool layer's out and dout)
-    // kept in memory as bf16.  precision == RCN_HIPX_BF16 then too: what is ROUNDED does not change, only where.
-    bool store16 = false;
-    int tiling = RCN_HIPX_TILING_AUTO;      // fp32 3x3 kernels: implicit GEMM only / by shape / LDS-tiled wherever they apply (rcn_hipx_set_tiling)
     // the optimiser (rcn_hipx_set_sgd; convnet_sgd.hpp): (0, 0, 0) is plain SGD through k_reduce_all / k_axpy.  `vel` (n_pad floats, laid out
     // like params) is allocated by the first nonzero momentum and never moved afterwards: captured graphs hold its pointer.
     float sgd_mu = 0.f, sgd_wd = 0.f; int sgd_nesterov = 0;
@@ -185,12 +133,6 @@ struct Dev { int prev = -1; explicit Dev(int d) { (void)hipGetDevice(&prev); if 
 
 int grid1d(long long total, int block) { long long g = (total + block - 1) / block; return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
 
-// Y = act(conv(X) + b) as implicit GEMM; `ks` = 1 or 3; epi 0 raw / 1 bias / 2 bias + relu.
-// Few output tiles and a long contraction (the dense layers: M = batch) -> split-K over gridDim.z into raw partial tiles
-// (slab `skbuf`) that k_splitk_epilogue sums in order.
-// epi 4 (bias + ReLU + the following 2x2 max-pool, written to Y = pooled map and pool_idx) exists only in the LDS-tiled bf16 kernel:
-// callers ask conv_pool_fusable() first
-static bool halo_enabled(const rcn_hipx_net* n) { return n->opt.halo != 0; }
 // RCN_HIPX_HALO_F32 only seeds a new net's tiling mode (rcn_hipx_create); rcn_hipx_set_tiling changes it per net
 static int halo_f32_default() { const char* e = std::getenv("RCN_HIPX_HALO_F32"); const int v = e ? std::atoi(e) : 1; return v < 0 || v > 2 ? 1 : v; }
 
@@ -211,436 +153,187 @@ long long resident_slots(rcn_hipx_net* n, const void* kernel) {
     cache.emplace(key, v);
     return v;
 }
-
-// split-K factor of the implicit-GEMM kernels: few output tiles and a long contraction
-int splitk_z(long long M, int Cout, int bn, int nkt) {
-    const long long tiles = ((M + kBM - 1) / kBM) * (Cout / bn);
-    int Z = 1;
-    if (tiles < 256 && nkt >= 8) { Z = (int)(512 / tiles); if (Z > nkt / 4) Z = nkt / 4; if (Z < 1) Z = 1; }
-    // every partial is summed by ONE thread per element in k_splitk_epilogue: 392 of them on a 128 x 32 output (the 50176 -> 10 layer of the
-    // 224 x 224 net) made that kernel 101 us for 4096 sums
-    if (Z > 64) Z = 64;
-    return Z;
+// a looping kernel over `items` work items: at most as many workgroups as the chip holds at once, each taking items blockIdx.x, + gridDim.x, ...
+template <typename... P, typename... A> void launch_resident(rcn_hipx_net* n, void (*kernel)(P...), long long items, A... args) {
+    const long long slots = resident_slots(n, (const void*)kernel);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(items < slots ? items : slots)), dim3(kThreads), 0, n->stream, args...);
 }
 
-// Pixel-block geometry of the fp32 LDS-tiled kernels for an H x W map: 8 x 16 blocks of one image, or 8 x 8 blocks of two images
-// side by side where that wastes fewer MFMA rows (8-, 24-, 56-pixel-wide maps).  Not used when less than 70 % of a block's rows
-// are real pixels (the implicit-GEMM kernels have no such waste).
-struct HaloPlan { bool ok; int tw; };
-HaloPlan halo_plan(const rcn_hipx_net* n, const ConvShape& s) {
-    const double uh = (double)s.H / ((s.H + 7) / 8 * 8);
-    const double u16 = (double)s.W / ((s.W + 15) / 16 * 16);
-    const double u8 = (double)s.W / ((s.W + 7) / 8 * 8) * ((double)s.N / ((s.N + 1) / 2 * 2));
-    const int tw = u8 > u16 ? 8 : 16;
-    // the LDS-tiled kernels address with 32-bit element offsets
-    const bool fits = (long long)(s.N + 1) * s.H * s.W * (s.Cin > s.Cout ? s.Cin : s.Cout) < 0x7fffffffLL;
-    return HaloPlan{fits && (n->tiling == RCN_HIPX_TILING_LDS || uh * (tw == 8 ? u8 : u16) >= 0.7), tw};
-}
-// the first layer's own kernels (k_conv1_*_f32): 1 or 3 input channels
-bool conv1_f32_shape(const rcn_hipx_net* n, const ConvShape& s) { return n->tiling != RCN_HIPX_TILING_GEMM && (s.Cin == 1 || s.Cin == 3) && s.Cout % 32 == 0 && halo_plan(n, s).ok; }
-bool conv_halo_f32_shape(const rcn_hipx_net* n, const ConvShape& s) { return n->tiling != RCN_HIPX_TILING_GEMM && s.Cin % 32 == 0 && s.Cout % 32 == 0 && halo_plan(n, s).ok; }
-// split-K factor of a fp32 3x3 layer as launch_conv decides it (the LDS-tiled kernels have no split-K form)
-int conv3_f32_z(const rcn_hipx_net* n, const ConvShape& s) {
-    if (n->tiling == RCN_HIPX_TILING_LDS && conv_halo_f32_shape(n, s)) return 1;
-    return splitk_z((long long)s.N * s.H * s.W, s.Cout, s.Cout % 64 == 0 ? 64 : 32, 9 * s.Cin / 32);
-}
-
-// does the 2x2 max-pool that follows this 3x3 convolution run in the convolution kernel's epilogue (EPI 4: LDS-tiled kernels only)?
-bool conv_pool_fusable(const rcn_hipx_net* n, const ConvShape& s) {
-    if (s.H % 2 || s.W % 2) return false;
-    if (conv1_f32_shape(n, s)) return true;                            // the first layer's kernels serve both precisions
-    if (n->precision == RCN_HIPX_BF16) return halo_enabled(n) && (s.Cin == 32 || s.Cin % 64 == 0);
-    return conv_halo_f32_shape(n, s);
-}
-
-// can the LDS-tiled kernel run this 3x3 convolution (as launch_conv would decide)?  Mirrors launch_conv's split-K rule.
-bool conv_halo_runs(const rcn_hipx_net* n, const ConvShape& s) {
-    const long long M = (long long)s.N * s.H * s.W;
-    if (n->precision != RCN_HIPX_BF16) return conv_halo_f32_shape(n, s) && conv3_f32_z(n, s) == 1;
-    if (!halo_enabled(n) || !(s.Cin == 32 || s.Cin % 64 == 0) || s.Cout % 32) return false;
-    const int bn = s.Cout % 128 == 0 ? 128 : s.Cout % 64 == 0 ? 64 : 32;
-    return n->store16 || splitk_z(M, s.Cout, bn, 9 * s.Cin / 32) == 1;
-}
-
-// Storage of a launch's tensors (RCN_HIPX_BF16_STORED): x16 -- the input X (and a pooled-resolution input) is bf16; y16 -- the output Y and
-// epilogue 3's gate tensor (both belong to the layer below in the input-gradient pass) are bf16.  The host passes every tensor as
-// float*; the launch sites cast.
-struct Store { bool x16 = false, y16 = false; };
-// layer i's out / dout (i < 0: the net's input, always fp32)
+// layer i's out / dout are bf16 tensors (i < 0: the net's input, always fp32)
 bool stage16(const rcn_hipx_net* n, int i) { return n->store16 && i >= 0 && (n->L[i].kind == RCN_HIPX_CONV3X3_RELU || n->L[i].kind == RCN_HIPX_MAXPOOL2); }
-static const char* kStoreGap = "bf16 storage (RCN_HIPX_BF16_STORED) covers nets whose convolutions run on the LDS-tiled kernels with fused pooling: this layer does not (rcn_hipx_plan shows the kernels chosen)";
 
+// From a run-time value to a template argument: f(std::integral_constant<int, V>{}) for the V of the list that equals v -- the LAST of the
+// list when none does (the selectors only hand out listed values).  The lists at the call sites are the set of kernels the library holds.
+template <int V, int... Rest, typename F> void with_const(int v, F&& f) {
+    if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, V>{});
+    else if (v == V) f(std::integral_constant<int, V>{});
+    else with_const<Rest...>(v, f);
+}
+template <typename F> void with_bool(bool v, F&& f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+// a tensor's storage type: __bf16 or float
+template <typename T> struct Type { using type = T; };
+template <typename F> void with_storage(bool is16, F&& f) { if (is16) f(Type<__bf16>{}); else f(Type<float>{}); }
+// (epilogue, pooled-resolution input) of the LDS-tiled forward kernels: a pooled-resolution input only occurs in the input-gradient pass
+// (EPI 0 / 3); false: no such kernel
+template <typename F> bool with_epi_pin(int kepi, bool pin, F&& f) {
+    if (pin && kepi != 0 && kepi != 3) return false;
+    if (pin) with_const<3, 0>(kepi, [&](auto EPI) { f(EPI, std::true_type{}); });
+    else with_const<0, 1, 2, 3, 4>(kepi, [&](auto EPI) { f(EPI, std::false_type{}); });
+    return true;
+}
+#define CV(c_) (decltype(c_)::value)        /* the value of one of those constants, as a template argument */
+#define CT(t_) typename decltype(t_)::type   /* ... and the type in a Type<> */
+
+// Y = act(conv(X) + b): the kernel select_conv chooses (convnet_select.hpp).  Split-K launches leave raw partial tiles in `skbuf` that
+// k_splitk_epilogue sums in order.
 int launch_conv(rcn_hipx_net* n, const float* X, const float* Wk, const float* bias, float* Y, ConvShape s, int ks, int epi, uint8_t* pool_idx = nullptr,
                 const PooledGrad* pin = nullptr, bool force_fp32 = false, const __bf16* wb_ready = nullptr, Store st = Store{}) {
+    const bool pooled = pin != nullptr;
+    const ConvChoice c = select_conv(*n, s, ks, epi, pooled, force_fp32, st);
+    if (c.error) return fail(n, -3, c.error);
+    if (dry_note(n, "%s", describe(c, s, ks, epi, pooled).c_str())) return 0;
     const long long M = (long long)s.N * s.H * s.W;
-    const bool smallc = ks * ks * s.Cin <= 32 && s.Cin % 32 != 0;   // the per-element gather loader: only where a k-tile is not 32 whole channels
-    if (!smallc && s.Cin % 32) return fail(n, -3, "input channels must be a multiple of 32 (or the whole 3x3xCin patch <= 32)");
-    if (s.Cout % 32) return fail(n, -3, "output channels must be a multiple of 32");
-    // bf16 mode rounds the operands of every GEMM EXCEPT the first layer's (its whole 3 x 3 x Cin patch is one k-block: nothing of the
-    // MFMA rate to gain, and its own fp32 kernels are the fast ones) and the fused classifier head's (head_fusable)
-    const bool bf16 = n->precision == RCN_HIPX_BF16 && !(ks == 3 && smallc) && !force_fp32;
-    const int bn = (bf16 && s.Cout % 128 == 0) ? 128 : (s.Cout % 64 == 0) ? 64 : 32;
-    const int nkt = smallc ? 1 : ks * ks * s.Cin / 32;
-    // (bf16 storage: a 3x3 layer never splits K -- whatever the batch size, it stays on the LDS-tiled kernels, the ones that take bf16 tensors)
-    const int Z = (epi == 4 || (n->store16 && ks == 3)) ? 1 : (!bf16 && ks == 3 && !smallc) ? conv3_f32_z(n, s) : splitk_z(M, s.Cout, bn, nkt);
     float* out = Y;
-    int kepi = epi;
-    if (Z > 1) {
-        XTRY(n, scratch_ensure(n, n->skbuf, (size_t)Z * M * s.Cout * sizeof(float)));
-        out = (float*)n->skbuf.p; kepi = 0;
+    if (c.Z > 1) {
+        XTRY(n, scratch_ensure(n, n->skbuf, (size_t)c.Z * M * s.Cout * sizeof(float)));
+        out = (float*)n->skbuf.p;
     }
-    const dim3 grid((unsigned)((M + kBM - 1) / kBM), (unsigned)(s.Cout / bn), (unsigned)Z);
-    if (bf16) {
+    const __bf16* WB = wb_ready;                    // made for all layers at the start of the step (prep_bf16_weights)
+    if (c.bf16 && !WB) {
         // operands rounded to bf16: the weights once here, transposed to [Cout][Kp]; the activations inside the kernel
         const int K = ks * ks * s.Cin, Kp = (K + 31) / 32 * 32;
-        const __bf16* WB = wb_ready;                                    // made for all layers at the start of the step (prep_bf16_weights)
-        if (!WB) {
-            XTRY(n, scratch_ensure(n, n->wb, (size_t)s.Cout * Kp * sizeof(__bf16)));
-            if (!n->dry) hipLaunchKernelGGL(k_prep_weights_bf16, dim3(grid1d((long long)s.Cout * Kp, 256)), dim3(256), 0, n->stream, Wk, K, s.Cout, (__bf16*)n->wb.p, Kp);
-            WB = (const __bf16*)n->wb.p;
-        }
-        // thin 3x3 layers: the LDS-tiled kernel (one halo per 8x16 output block serves all nine taps)
-        if (epi == 4 && !(ks == 3 && conv_pool_fusable(n, s))) return fail(n, -3, "internal: fused conv+pool epilogue requested for a layer the LDS-tiled kernel does not cover");
-        if (halo_enabled(n) && ks == 3 && !smallc && Z == 1 && (s.Cin == 32 || s.Cin % 64 == 0)) {
-            const int hbn = (s.Cout % 64 == 0) ? 64 : 32;
-            const int tw = (s.W + kHaloTW - 1) / kHaloTW, th = (s.H + kHaloTH - 1) / kHaloTH;
-            const dim3 hgrid((unsigned)(tw * th * s.N), (unsigned)(s.Cout / hbn));
-            const PooledGrad pg = pin ? *pin : PooledGrad{nullptr, nullptr, nullptr};
-            const int pipe = n->opt.bf16_pipe;
-            if (pipe && (long long)(s.N + 1) * s.H * s.W * (s.Cin > s.Cout ? s.Cin : s.Cout) < 0x7fffffffLL) {
-                // the pipelined form (convnet_halo_bf16.hpp): work items (pixel block, column block) on a resident grid, operands loaded a
-                // phase ahead; same LDS images, rounding and MFMA order as k_conv3x3_halo_bf16 below
-                const long long items = (long long)tw * th * s.N * (s.Cout / hbn);
-#define HBP_LAUNCH_T(CI_, BN_, EPI_, PIN_, TS_) do { const long long slots = resident_slots(n, (const void*)k_conv3x3_halo_bf16p<CI_, BN_, EPI_, PIN_, TS_>); \
-                hipLaunchKernelGGL((k_conv3x3_halo_bf16p<CI_, BN_, EPI_, PIN_, TS_>), dim3((unsigned)(items < slots ? items : slots)), dim3(kThreads), 0, n->stream, (const TS_*)X, WB, bias, (TS_*)out, s, tw, th, (int)items, pool_idx, \
-                                   PooledGradT<TS_>{(const TS_*)pg.dP, (const TS_*)pg.P, pg.idx}); } while (0)
-#define HBP_LAUNCH(CI_, BN_, EPI_, PIN_) do { if (st.x16) HBP_LAUNCH_T(CI_, BN_, EPI_, PIN_, __bf16); else HBP_LAUNCH_T(CI_, BN_, EPI_, PIN_, float); } while (0)
-#define HBP_EPI(CI_, BN_) do { if (pin) { if (kepi == 3) HBP_LAUNCH(CI_, BN_, 3, true); else if (kepi == 0) HBP_LAUNCH(CI_, BN_, 0, true); else return fail(n, -3, "internal: pooled-resolution input with a forward epilogue"); } \
-                               else if (kepi == 0) HBP_LAUNCH(CI_, BN_, 0, false); else if (kepi == 1) HBP_LAUNCH(CI_, BN_, 1, false); else if (kepi == 2) HBP_LAUNCH(CI_, BN_, 2, false); \
-                               else if (kepi == 3) HBP_LAUNCH(CI_, BN_, 3, false); else HBP_LAUNCH(CI_, BN_, 4, false); } while (0)
-#define HB1_LAUNCH_T(BN_, EPI_, PIN_, TS_) do { const long long slots = resident_slots(n, (const void*)k_conv3x3_halo_bf16_1cb<BN_, EPI_, PIN_, TS_>); \
-                hipLaunchKernelGGL((k_conv3x3_halo_bf16_1cb<BN_, EPI_, PIN_, TS_>), dim3((unsigned)(items < slots ? items : slots)), dim3(kThreads), 0, n->stream, (const TS_*)X, WB, bias, (TS_*)out, s, tw, th, (int)items, pool_idx, \
-                                   PooledGradT<TS_>{(const TS_*)pg.dP, (const TS_*)pg.P, pg.idx}); } while (0)
-#define HB1_LAUNCH(BN_, EPI_, PIN_) do { if (st.x16) HB1_LAUNCH_T(BN_, EPI_, PIN_, __bf16); else HB1_LAUNCH_T(BN_, EPI_, PIN_, float); } while (0)
-#define HB1_EPI(BN_) do { if (pin) { if (kepi == 3) HB1_LAUNCH(BN_, 3, true); else if (kepi == 0) HB1_LAUNCH(BN_, 0, true); else return fail(n, -3, "internal: pooled-resolution input with a forward epilogue"); } \
-                          else if (kepi == 0) HB1_LAUNCH(BN_, 0, false); else if (kepi == 1) HB1_LAUNCH(BN_, 1, false); else if (kepi == 2) HB1_LAUNCH(BN_, 2, false); \
-                          else if (kepi == 3) HB1_LAUNCH(BN_, 3, false); else HB1_LAUNCH(BN_, 4, false); } while (0)
-                const int onecb = n->opt.bf16_1cb;
-                if (st.x16 != st.y16) return fail(n, -3, kStoreGap);
-                // 16 x 16 pixel blocks (k_conv3x3_halo_bf16p<..., MG = 2>): bf16 tensors, 64-wide column blocks, a height that 16-row blocks
-                // cover with no more padding than 8-row blocks do, and still at least one item per resident workgroup
-                const int th2 = (s.H + 15) / 16;
-                const long long items2 = (long long)tw * th2 * s.N * (s.Cout / hbn);
-                const bool mg2 = n->opt.bf16_rows16 && st.x16 && hbn == 64 && !(s.Cin == 32 && onecb && hbn == 32) && th2 * 16 == th * kHaloTH && items2 >= 512;
-                if (mg2 && dry_note(n, "  conv3x3 %dx%dx%d->%d epi %d%s: k_conv3x3_halo_bf16p (16 x 16 pixel blocks), %lld items", s.H, s.W, s.Cin, s.Cout, kepi, pin ? " pooled-in" : "", items2)) return 0;
-                if (mg2) {
-#define HB2_LAUNCH(CI_, EPI_, PIN_) do { const long long slots = resident_slots(n, (const void*)k_conv3x3_halo_bf16p<CI_, 64, EPI_, PIN_, __bf16, 2>); \
-                    hipLaunchKernelGGL((k_conv3x3_halo_bf16p<CI_, 64, EPI_, PIN_, __bf16, 2>), dim3((unsigned)(items2 < slots ? items2 : slots)), dim3(kThreads), 0, n->stream, (const __bf16*)X, WB, bias, (__bf16*)out, s, tw, th2, (int)items2, pool_idx, \
-                                       PooledGradT<__bf16>{(const __bf16*)pg.dP, (const __bf16*)pg.P, pg.idx}); } while (0)
-#define HB2_EPI(CI_) do { if (pin) { if (kepi == 3) HB2_LAUNCH(CI_, 3, true); else if (kepi == 0) HB2_LAUNCH(CI_, 0, true); else return fail(n, -3, "internal: pooled-resolution input with a forward epilogue"); } \
-                          else if (kepi == 0) HB2_LAUNCH(CI_, 0, false); else if (kepi == 1) HB2_LAUNCH(CI_, 1, false); else if (kepi == 2) HB2_LAUNCH(CI_, 2, false); \
-                          else if (kepi == 3) HB2_LAUNCH(CI_, 3, false); else HB2_LAUNCH(CI_, 4, false); } while (0)
-                    if (s.Cin == 32) HB2_EPI(32); else HB2_EPI(64);
-#undef HB2_EPI
-#undef HB2_LAUNCH
-                    XTRY(n, hipGetLastError());
-                    return 0;
-                }
-                if (items <= 0x7fffffffLL && dry_note(n, "  %s %dx%dx%d->%d epi %d%s: %s, %lld items", ks == 3 ? "conv3x3" : "dense", s.H, s.W, s.Cin, s.Cout, kepi, pin ? " pooled-in" : "",
-                                                      (s.Cin == 32 && onecb && hbn == 32) ? "k_conv3x3_halo_bf16_1cb<32>" : "k_conv3x3_halo_bf16p", items)) return 0;
-                if (items <= 0x7fffffffLL) {
-                    // one channel block and one 32-wide column tile: all nine taps' weights stay in LDS (with a 64-wide tile the 46 KB of weights
-                    // cost a third workgroup per CU: measured 190 vs 158 us on the 32 -> 64 layer of the 224 x 224 net)
-                    if (s.Cin == 32 && onecb && hbn == 32) HB1_EPI(32);
-                    else if (s.Cin == 32) { if (hbn == 64) HBP_EPI(32, 64); else HBP_EPI(32, 32); }
-                    else { if (hbn == 64) HBP_EPI(64, 64); else HBP_EPI(64, 32); }
-                    XTRY(n, hipGetLastError());
-                    return 0;
-                }
-#undef HB1_EPI
-#undef HB1_LAUNCH
-#undef HB1_LAUNCH_T
-#undef HBP_EPI
-#undef HBP_LAUNCH
-#undef HBP_LAUNCH_T
-            }
-            if (st.x16 || st.y16) return fail(n, -3, kStoreGap);
-#define HALO_CASE(CI_, BN_, EPI_) do { if (pin) hipLaunchKernelGGL((k_conv3x3_halo_bf16<CI_, BN_, EPI_, true>), hgrid, dim3(kThreads), 0, n->stream, X, WB, bias, out, s, tw, th, pool_idx, pg); \
-                                       else hipLaunchKernelGGL((k_conv3x3_halo_bf16<CI_, BN_, EPI_, false>), hgrid, dim3(kThreads), 0, n->stream, X, WB, bias, out, s, tw, th, pool_idx, pg); } while (0)
-#define HALO_EPI(CI_, BN_) do { if (kepi == 0) HALO_CASE(CI_, BN_, 0); else if (kepi == 1) HALO_CASE(CI_, BN_, 1); else if (kepi == 2) HALO_CASE(CI_, BN_, 2); else if (kepi == 3) HALO_CASE(CI_, BN_, 3); else HALO_CASE(CI_, BN_, 4); } while (0)
-            if (dry_note(n, "  conv3x3 %dx%dx%d->%d epi %d%s: k_conv3x3_halo_bf16", s.H, s.W, s.Cin, s.Cout, kepi, pin ? " pooled-in" : "")) return 0;
-            if (s.Cin == 32) { if (hbn == 64) HALO_EPI(32, 64); else HALO_EPI(32, 32); }
-            else { if (hbn == 64) HALO_EPI(64, 64); else HALO_EPI(64, 32); }
-#undef HALO_EPI
-#undef HALO_CASE
-            XTRY(n, hipGetLastError());
-            return 0;
-        }
-        if (pin) return fail(n, -3, "internal: pooled-resolution input requested for a layer the LDS-tiled kernel does not cover");
-        if (st.x16 || st.y16) {
-            // the dense layer on top of the convolutional stage: its forward pass and weight gradient READ a bf16 map, its input gradient
-            // WRITES one (gated by the map, epilogue 3, or raw into a pooled gradient, epilogue 0).  A split-K launch leaves float partials.
-            if (ks != 1 || smallc || (st.x16 && st.y16)) return fail(n, -3, kStoreGap);
-            const bool y16k = st.y16 && Z == 1;                     // the kernel itself writes the bf16 tensor
-#define CONVS_CASE(BN_, EPI_) do { if (st.x16) hipLaunchKernelGGL((k_conv_fwd_bf16<1, false, BN_, EPI_, __bf16, float>), grid, dim3(kThreads), 0, n->stream, (const __bf16*)X, WB, bias, out, s); \
-                                   else if (y16k) hipLaunchKernelGGL((k_conv_fwd_bf16<1, false, BN_, EPI_, float, __bf16>), grid, dim3(kThreads), 0, n->stream, X, WB, bias, (__bf16*)out, s); \
-                                   else hipLaunchKernelGGL((k_conv_fwd_bf16<1, false, BN_, EPI_>), grid, dim3(kThreads), 0, n->stream, X, WB, bias, out, s); } while (0)
-#define CONVS_EPI(BN_) do { if (kepi == 0) CONVS_CASE(BN_, 0); else if (kepi == 1) CONVS_CASE(BN_, 1); else if (kepi == 2) CONVS_CASE(BN_, 2); else CONVS_CASE(BN_, 3); } while (0)
-            if (dry_note(n, "  dense %d->%d epi %d: k_conv_fwd_bf16<1, tile, %d>%s, %s", s.Cin, s.Cout, epi, bn, Z > 1 ? (" split-K " + std::to_string(Z) + " + k_splitk_epilogue").c_str() : "",
-                         st.x16 ? "bf16 input map" : "bf16 output map")) return 0;
-            if (bn == 128) CONVS_EPI(128); else if (bn == 64) CONVS_EPI(64); else CONVS_EPI(32);
-#undef CONVS_EPI
-#undef CONVS_CASE
-            XTRY(n, hipGetLastError());
-            if (Z > 1) {
-                if (st.y16) hipLaunchKernelGGL(k_splitk_epilogue<__bf16>, dim3(grid1d(M * s.Cout, 256)), dim3(256), 0, n->stream, (const float*)n->skbuf.p, bias, (__bf16*)Y, M * s.Cout, s.Cout, Z, epi);
-                else hipLaunchKernelGGL(k_splitk_epilogue<float>, dim3(grid1d(M * s.Cout, 256)), dim3(256), 0, n->stream, (const float*)n->skbuf.p, bias, Y, M * s.Cout, s.Cout, Z, epi);
-                XTRY(n, hipGetLastError());
-            }
-            return 0;
-        }
-#define CONVB_CASE(KS_, SM_, BN_, EPI_) hipLaunchKernelGGL((k_conv_fwd_bf16<KS_, SM_, BN_, EPI_>), grid, dim3(kThreads), 0, n->stream, X, WB, bias, out, s)
-#define CONVB_EPI(KS_, SM_, BN_) do { if (kepi == 0) CONVB_CASE(KS_, SM_, BN_, 0); else if (kepi == 1) CONVB_CASE(KS_, SM_, BN_, 1); else if (kepi == 2) CONVB_CASE(KS_, SM_, BN_, 2); else CONVB_CASE(KS_, SM_, BN_, 3); } while (0)
-#define CONVB_BN(KS_, SM_) do { if (bn == 128) CONVB_EPI(KS_, SM_, 128); else if (bn == 64) CONVB_EPI(KS_, SM_, 64); else CONVB_EPI(KS_, SM_, 32); } while (0)
-        if (dry_note(n, "  %s %dx%dx%d->%d epi %d: k_conv_fwd_bf16<%d, %s, %d>%s", ks == 3 ? "conv3x3" : "dense", s.H, s.W, s.Cin, s.Cout, epi, ks, smallc ? "gather" : "tile", bn,
-                     Z > 1 ? (" split-K " + std::to_string(Z) + " + k_splitk_epilogue").c_str() : "")) return 0;
-        if (ks == 3) { if (smallc) CONVB_BN(3, true); else CONVB_BN(3, false); }
-        else { if (smallc) CONVB_BN(1, true); else CONVB_BN(1, false); }
-#undef CONVB_BN
-#undef CONVB_EPI
-#undef CONVB_CASE
-    } else {
-        if (epi == 4 && !(ks == 3 && conv_pool_fusable(n, s))) return fail(n, -3, "internal: fused conv+pool epilogue requested for a layer the LDS-tiled kernel does not cover");
-        if (st.x16 || (st.y16 && !(ks == 3 && smallc && (epi == 2 || epi == 4) && conv1_f32_shape(n, s)))) return fail(n, -3, kStoreGap);
-        if (ks == 3 && smallc && (epi == 2 || epi == 4) && conv1_f32_shape(n, s)) {
-            // first layer (convnet_halo.hpp): weights in registers, the block's input halo in LDS
-            const int tw = halo_plan(n, s).tw, nimg = 16 / tw;
-            const int tiles_w = (s.W + tw - 1) / tw, tiles_h = (s.H + 7) / 8;
-            const long long items = (long long)tiles_w * tiles_h * ((s.N + nimg - 1) / nimg) * (s.Cout / 32);
-            if (items > 0x7fffffffLL) return fail(n, -3, "too many pixel blocks in one layer");
-#define C1_LAUNCH_T(CIN_, TW_, EPI_, TY_) do { const long long slots = resident_slots(n, (const void*)k_conv1_fwd_f32<CIN_, TW_, EPI_, TY_>); \
-            hipLaunchKernelGGL((k_conv1_fwd_f32<CIN_, TW_, EPI_, TY_>), dim3((unsigned)(items < slots ? items : slots)), dim3(kThreads), 0, n->stream, X, Wk, bias, (TY_*)Y, s, tiles_w, tiles_h, (int)items, pool_idx); } while (0)
-#define C1_LAUNCH(CIN_, TW_, EPI_) do { if (st.y16) C1_LAUNCH_T(CIN_, TW_, EPI_, __bf16); else C1_LAUNCH_T(CIN_, TW_, EPI_, float); } while (0)
-#define C1_EPI(CIN_, TW_) do { if (epi == 4) C1_LAUNCH(CIN_, TW_, 4); else C1_LAUNCH(CIN_, TW_, 2); } while (0)
-            if (dry_note(n, "  conv3x3 %dx%dx%d->%d epi %d: k_conv1_fwd_f32<%d, %d>, %lld items", s.H, s.W, s.Cin, s.Cout, epi, s.Cin, tw, items)) return 0;
-            if (s.Cin == 3) { if (tw == 16) C1_EPI(3, 16); else C1_EPI(3, 8); }
-            else { if (tw == 16) C1_EPI(1, 16); else C1_EPI(1, 8); }
-#undef C1_EPI
-#undef C1_LAUNCH
-#undef C1_LAUNCH_T
-            XTRY(n, hipGetLastError());
-            return 0;
-        }
-        if (ks == 3 && !smallc && Z == 1 && conv_halo_f32_shape(n, s)) {
-            // LDS-tiled (convnet_halo.hpp): one staged halo per block of 128 output pixels serves all nine taps
-            const int tw = halo_plan(n, s).tw, nimg = 16 / tw;
-            const int tiles_w = (s.W + tw - 1) / tw, tiles_h = (s.H + 7) / 8;
-            // work items = (pixel block, bn-wide column block); at most as many workgroups as the chip holds at once (three per CU), each
-            // taking items blockIdx.x, + gridDim.x, ...
-            const long long items = (long long)tiles_w * tiles_h * ((s.N + nimg - 1) / nimg) * (s.Cout / bn);
-            if (items > 0x7fffffffLL) return fail(n, -3, "too many pixel blocks in one layer");
-            const PooledGrad pg = pin ? *pin : PooledGrad{nullptr, nullptr, nullptr};
-#define HF_LAUNCH(TW_, BN_, EPI_, PIN_) do { const long long slots = resident_slots(n, (const void*)k_conv3x3_halo_f32<TW_, BN_, EPI_, PIN_>); \
-            hipLaunchKernelGGL((k_conv3x3_halo_f32<TW_, BN_, EPI_, PIN_>), dim3((unsigned)(items < slots ? items : slots)), dim3(kThreads), 0, n->stream, X, Wk, bias, out, s, tiles_w, tiles_h, (int)items, pool_idx, pg); } while (0)
-            // a pooled-resolution input only occurs in the input-gradient pass (EPI 0 / 3)
-#define HF_EPI(TW_, BN_) do { if (pin) { if (kepi == 3) HF_LAUNCH(TW_, BN_, 3, true); else if (kepi == 0) HF_LAUNCH(TW_, BN_, 0, true); else return fail(n, -3, "internal: pooled-resolution input with a forward epilogue"); } \
-                              else if (kepi == 0) HF_LAUNCH(TW_, BN_, 0, false); else if (kepi == 1) HF_LAUNCH(TW_, BN_, 1, false); else if (kepi == 2) HF_LAUNCH(TW_, BN_, 2, false); \
-                              else if (kepi == 3) HF_LAUNCH(TW_, BN_, 3, false); else HF_LAUNCH(TW_, BN_, 4, false); } while (0)
-            if (dry_note(n, "  conv3x3 %dx%dx%d->%d epi %d%s: k_conv3x3_halo_f32<%d, %d>, %lld items", s.H, s.W, s.Cin, s.Cout, kepi, pin ? " pooled-in" : "", tw, bn, items)) return 0;
-            if (tw == 16) { if (bn == 64) HF_EPI(16, 64); else HF_EPI(16, 32); }
-            else { if (bn == 64) HF_EPI(8, 64); else HF_EPI(8, 32); }
-#undef HF_EPI
-#undef HF_LAUNCH
-            XTRY(n, hipGetLastError());
-            return 0;
-        }
-        if (pin) return fail(n, -3, "internal: pooled-resolution input requested for a layer the LDS-tiled kernel does not cover");
-#define CONV_CASE(KS_, SM_, BN_, EPI_) hipLaunchKernelGGL((k_conv_fwd<KS_, SM_, BN_, EPI_>), grid, dim3(kThreads), 0, n->stream, X, Wk, bias, out, s)
-#define CONV_EPI(KS_, SM_, BN_) do { if (kepi == 0) CONV_CASE(KS_, SM_, BN_, 0); else if (kepi == 1) CONV_CASE(KS_, SM_, BN_, 1); else if (kepi == 2) CONV_CASE(KS_, SM_, BN_, 2); else CONV_CASE(KS_, SM_, BN_, 3); } while (0)
-#define CONV_BN(KS_, SM_) do { if (bn == 64) CONV_EPI(KS_, SM_, 64); else CONV_EPI(KS_, SM_, 32); } while (0)
-        if (dry_note(n, "  %s %dx%dx%d->%d epi %d: k_conv_fwd<%d, %s, %d>%s", ks == 3 ? "conv3x3" : "dense", s.H, s.W, s.Cin, s.Cout, epi, ks, smallc ? "gather" : "tile", bn,
-                     Z > 1 ? (" split-K " + std::to_string(Z) + " + k_splitk_epilogue").c_str() : "")) return 0;
-        if (ks == 3) { if (smallc) CONV_BN(3, true); else CONV_BN(3, false); }
-        else { if (smallc) CONV_BN(1, true); else CONV_BN(1, false); }
-#undef CONV_BN
-#undef CONV_EPI
-#undef CONV_CASE
+        XTRY(n, scratch_ensure(n, n->wb, (size_t)s.Cout * Kp * sizeof(__bf16)));
+        hipLaunchKernelGGL(k_prep_weights_bf16, dim3(grid1d((long long)s.Cout * Kp, 256)), dim3(256), 0, n->stream, Wk, K, s.Cout, (__bf16*)n->wb.p, Kp);
+        WB = (const __bf16*)n->wb.p;
     }
+    const PooledGrad pg = pin ? *pin : PooledGrad{nullptr, nullptr, nullptr};
+    const dim3 grid((unsigned)((M + kBM - 1) / kBM), (unsigned)(s.Cout / c.bn), (unsigned)c.Z);      // the implicit-GEMM kernels'
+    const int items = (int)c.items;
+    bool found = true;
+    switch (c.kernel) {
+    case ConvKernel::conv1_fwd_f32:
+        with_const<3, 1>(s.Cin, [&](auto CIN) { with_const<16, 8>(c.tile_w, [&](auto TW) { with_const<4, 2>(epi, [&](auto EPI) { with_storage(st.y16, [&](auto T) {
+            launch_resident(n, k_conv1_fwd_f32<CV(CIN), CV(TW), CV(EPI), CT(T)>, c.items, X, Wk, bias, (CT(T)*)Y, s, c.tiles_w, c.tiles_h, items, pool_idx);
+        }); }); }); });
+        break;
+    case ConvKernel::halo_f32:
+        with_const<16, 8>(c.tile_w, [&](auto TW) { with_const<64, 32>(c.bn, [&](auto BN) { found = with_epi_pin(c.kepi, pooled, [&](auto EPI, auto PIN) {
+            launch_resident(n, k_conv3x3_halo_f32<CV(TW), CV(BN), CV(EPI), CV(PIN)>, c.items, X, Wk, bias, out, s, c.tiles_w, c.tiles_h, items, pool_idx, pg);
+        }); }); });
+        break;
+    case ConvKernel::halo_bf16p:
+        with_const<32, 64>(s.Cin, [&](auto CI) { with_const<64, 32>(c.bn, [&](auto BN) { found = with_epi_pin(c.kepi, pooled, [&](auto EPI, auto PIN) { with_storage(st.x16, [&](auto T) {
+            launch_resident(n, k_conv3x3_halo_bf16p<CV(CI), CV(BN), CV(EPI), CV(PIN), CT(T)>, c.items, (const CT(T)*)X, WB, bias, (CT(T)*)out, s, c.tiles_w, c.tiles_h, items, pool_idx,
+                            PooledGradT<CT(T)>{(const CT(T)*)pg.dP, (const CT(T)*)pg.P, pg.idx});
+        }); }); }); });
+        break;
+    case ConvKernel::halo_bf16p_rows16:
+        with_const<32, 64>(s.Cin, [&](auto CI) { found = with_epi_pin(c.kepi, pooled, [&](auto EPI, auto PIN) {
+            launch_resident(n, k_conv3x3_halo_bf16p<CV(CI), 64, CV(EPI), CV(PIN), __bf16, 2>, c.items, (const __bf16*)X, WB, bias, (__bf16*)out, s, c.tiles_w, c.tiles_h, items, pool_idx,
+                            PooledGradT<__bf16>{(const __bf16*)pg.dP, (const __bf16*)pg.P, pg.idx});
+        }); });
+        break;
+    case ConvKernel::halo_bf16_1cb:
+        found = with_epi_pin(c.kepi, pooled, [&](auto EPI, auto PIN) { with_storage(st.x16, [&](auto T) {
+            launch_resident(n, k_conv3x3_halo_bf16_1cb<32, CV(EPI), CV(PIN), CT(T)>, c.items, (const CT(T)*)X, WB, bias, (CT(T)*)out, s, c.tiles_w, c.tiles_h, items, pool_idx,
+                            PooledGradT<CT(T)>{(const CT(T)*)pg.dP, (const CT(T)*)pg.P, pg.idx});
+        }); });
+        break;
+    case ConvKernel::halo_bf16: {
+        const dim3 hgrid((unsigned)(c.tiles_w * c.tiles_h * s.N), (unsigned)(s.Cout / c.bn));
+        with_const<32, 64>(s.Cin, [&](auto CI) { with_const<64, 32>(c.bn, [&](auto BN) { with_const<0, 1, 2, 3, 4>(c.kepi, [&](auto EPI) { with_bool(pooled, [&](auto PIN) {
+            hipLaunchKernelGGL((k_conv3x3_halo_bf16<CV(CI), CV(BN), CV(EPI), CV(PIN)>), hgrid, dim3(kThreads), 0, n->stream, X, WB, bias, out, s, c.tiles_w, c.tiles_h, pool_idx, pg);
+        }); }); }); });
+        break;
+    }
+    case ConvKernel::fwd_bf16_map:
+        // x16: reads the bf16 map; y16: writes one -- the kernel itself where it does not split K, else k_splitk_epilogue
+        with_const<128, 64, 32>(c.bn, [&](auto BN) { with_const<0, 1, 2, 3>(c.kepi, [&](auto EPI) {
+            if (st.x16) hipLaunchKernelGGL((k_conv_fwd_bf16<1, false, CV(BN), CV(EPI), __bf16, float>), grid, dim3(kThreads), 0, n->stream, (const __bf16*)X, WB, bias, out, s);
+            else if (c.Z == 1) hipLaunchKernelGGL((k_conv_fwd_bf16<1, false, CV(BN), CV(EPI), float, __bf16>), grid, dim3(kThreads), 0, n->stream, X, WB, bias, (__bf16*)out, s);
+            else hipLaunchKernelGGL((k_conv_fwd_bf16<1, false, CV(BN), CV(EPI)>), grid, dim3(kThreads), 0, n->stream, X, WB, bias, out, s);
+        }); });
+        break;
+    case ConvKernel::fwd_bf16:
+        with_const<3, 1>(ks, [&](auto KS) { with_bool(c.smallc, [&](auto SM) { with_const<128, 64, 32>(c.bn, [&](auto BN) { with_const<0, 1, 2, 3>(c.kepi, [&](auto EPI) {
+            hipLaunchKernelGGL((k_conv_fwd_bf16<CV(KS), CV(SM), CV(BN), CV(EPI)>), grid, dim3(kThreads), 0, n->stream, X, WB, bias, out, s);
+        }); }); }); });
+        break;
+    case ConvKernel::fwd_f32:
+        with_const<3, 1>(ks, [&](auto KS) { with_bool(c.smallc, [&](auto SM) { with_const<64, 32>(c.bn, [&](auto BN) { with_const<0, 1, 2, 3>(c.kepi, [&](auto EPI) {
+            hipLaunchKernelGGL((k_conv_fwd<CV(KS), CV(SM), CV(BN), CV(EPI)>), grid, dim3(kThreads), 0, n->stream, X, Wk, bias, out, s);
+        }); }); }); });
+        break;
+    }
+    if (!found) return fail(n, -3, "internal: pooled-resolution input with a forward epilogue");
     XTRY(n, hipGetLastError());
-    if (Z > 1) {
-        hipLaunchKernelGGL(k_splitk_epilogue<float>, dim3(grid1d(M * s.Cout, 256)), dim3(256), 0, n->stream, (const float*)n->skbuf.p, bias, Y, M * s.Cout, s.Cout, Z, epi);
+    if (c.Z > 1) {
+        if (st.y16) hipLaunchKernelGGL(k_splitk_epilogue<__bf16>, dim3(grid1d(M * s.Cout, 256)), dim3(256), 0, n->stream, (const float*)n->skbuf.p, bias, (__bf16*)Y, M * s.Cout, s.Cout, c.Z, epi);
+        else hipLaunchKernelGGL(k_splitk_epilogue<float>, dim3(grid1d(M * s.Cout, 256)), dim3(256), 0, n->stream, (const float*)n->skbuf.p, bias, Y, M * s.Cout, s.Cout, c.Z, epi);
         XTRY(n, hipGetLastError());
     }
     return 0;
 }
 
-static int xcd_remap(const rcn_hipx_net* n) { return n->opt.xcd_remap; }
-// Pixels per weight-gradient chunk.  Every chunk costs one (K+1) x Cout partial tile written to the slab and read back by
-// k_reduce_all, and a chunk is worked on by `tiles` workgroups (k-blocks x n-tiles), so the chunk size aims at a
-// total number of workgroups -- wide layers need few chunks -- with 1024 pixels as the floor (measured best on the small
-// CIFAR / MNIST nets, where parallelism is what matters).
-static int pix_per_chunk(const rcn_hipx_net* n, long long M, long long tiles) {
-    const int v = n->opt.pix_per_chunk >= 128 ? n->opt.pix_per_chunk / 128 * 128 : 0;
-    if (v) return v;
-    const long long target = n->opt.wg_target;
-    long long pix = (M * tiles / target + 127) / 128 * 128;
-    if (pix < 1024) pix = 1024;
-    if (pix > 32768) pix = 32768;
-    return (int)pix;
-}
-#define kPixPerChunk (pix_per_chunk(n, M, (long long)(smallc ? 1 : K / 32) * (s.Cout / bn)))
-
-static bool wgrad_halo_on(const rcn_hipx_net* n) { return n->opt.halo_wgrad != 0; }
-bool wgrad_halo_f32_runs(const rcn_hipx_net* n, const ConvShape& s, int ks) { return ks == 3 && ((ks * ks * s.Cin > 32 && conv_halo_f32_shape(n, s)) || conv1_f32_shape(n, s)); }
-bool wgrad_halo_runs(const rcn_hipx_net* n, const ConvShape& s, int ks) {
-    if (ks == 3 && ks * ks * s.Cin <= 32 && conv1_f32_shape(n, s)) return wgrad_halo_on(n);      // first layer: fp32 kernels in either precision
-    if (n->precision != RCN_HIPX_BF16) return wgrad_halo_on(n) && wgrad_halo_f32_runs(n, s, ks);
-    return n->precision == RCN_HIPX_BF16 && wgrad_halo_on(n) && ks == 3 && ks * ks * s.Cin > 32 && (s.Cin == 32 || s.Cin % 64 == 0) && s.H >= kHaloTH / 2 && s.W >= kHaloTW / 2;
-}
-
+// the partial [W | b] tiles of a layer's weight gradient into its slab (n->slab_sel), by the kernel select_wgrad chooses; *chunks_out: how many
 // st.x16: X is a bf16 tensor; st.y16: dZ (and a pooled-resolution dZ) is
 int launch_wgrad(rcn_hipx_net* n, const float* X, const float* dZ, ConvShape s, int ks, int* chunks_out, const PooledGrad* pdz = nullptr, Store st = Store{}) {
-    const long long M = (long long)s.N * s.H * s.W;
+    const bool pooled = pdz != nullptr;
+    const WgradChoice c = select_wgrad(*n, s, ks, pooled, st);
+    if (c.error) return fail(n, -3, c.error);
+    *chunks_out = c.chunks;
+    if (dry_note(n, "%s", describe(c, s, ks, pooled).c_str())) return 0;
     const int K = ks * ks * s.Cin;
-    const bool smallc = K <= 32 && s.Cin % 32 != 0;
-    const int bn = (s.Cout % 64 == 0) ? 64 : 32, bn0 = bn;
-    if (M > 0x7fff0000LL) return fail(n, -3, "too many output pixels in one layer (N*H*W must stay below 2^31)");
-    const int chunks = (int)((M + kPixPerChunk - 1) / kPixPerChunk), chunks0 = chunks;
-    XTRY(n, scratch_ensure(n, (*n->slab_sel), (size_t)chunks * (K + 1) * s.Cout * sizeof(float)));
-    if (pdz && !wgrad_halo_runs(n, s, ks)) return fail(n, -3, "internal: pooled-resolution dZ requested for a layer the LDS-tiled weight-gradient kernel does not cover");
-    if (wgrad_halo_runs(n, s, ks) && smallc) {
-        // first layer (convnet_halo.hpp): one 32 x 32 tile (rows = patch entries) per (co block, chunk of pixel blocks)
-        const int tw = halo_plan(n, s).tw, nimg = 16 / tw;
-        const int tiles_w = (s.W + tw - 1) / tw, tiles_h = (s.H + 7) / 8;
-        const long long blocks = (long long)tiles_w * tiles_h * ((s.N + nimg - 1) / nimg);
-        long long want = (1024 + s.Cout / 32 - 1) / (s.Cout / 32);
-        if (want > blocks) want = blocks;
-        const int bpc = (int)((blocks + want - 1) / want);
-        const int hchunks = (int)((blocks + bpc - 1) / bpc);
-        XTRY(n, scratch_ensure(n, (*n->slab_sel), (size_t)hchunks * (K + 1) * s.Cout * sizeof(float)));
-        const dim3 hgrid((unsigned)(s.Cout / 32), (unsigned)hchunks);
-        const PooledGrad pg = pdz ? *pdz : PooledGrad{nullptr, nullptr, nullptr};
-#define W1_CASE_T(CIN_, TW_, TD_) do { const PooledGradT<TD_> pgt{(const TD_*)pg.dP, (const TD_*)pg.P, pg.idx}; \
-                                if (pdz) hipLaunchKernelGGL((k_conv1_wgrad_f32<CIN_, TW_, true, TD_>), hgrid, dim3(kThreads), 0, n->stream, X, (const TD_*)dZ, (float*)(*n->slab_sel).p, s, tiles_w, tiles_h, bpc, pgt); \
-                                else hipLaunchKernelGGL((k_conv1_wgrad_f32<CIN_, TW_, false, TD_>), hgrid, dim3(kThreads), 0, n->stream, X, (const TD_*)dZ, (float*)(*n->slab_sel).p, s, tiles_w, tiles_h, bpc, pgt); } while (0)
-#define W1_CASE(CIN_, TW_) do { if (st.y16) W1_CASE_T(CIN_, TW_, __bf16); else W1_CASE_T(CIN_, TW_, float); } while (0)
-        if (st.x16) return fail(n, -3, kStoreGap);
-        if (dry_note(n, "  wgrad conv3x3 %dx%dx%d->%d%s: k_conv1_wgrad_f32<%d, %d>, %d chunks", s.H, s.W, s.Cin, s.Cout, pdz ? " pooled-dZ" : "", s.Cin, tw, hchunks)) { *chunks_out = hchunks; return 0; }
-        if (s.Cin == 3) { if (tw == 16) W1_CASE(3, 16); else W1_CASE(3, 8); }
-        else { if (tw == 16) W1_CASE(1, 16); else W1_CASE(1, 8); }
-#undef W1_CASE
-#undef W1_CASE_T
-        XTRY(n, hipGetLastError());
-        *chunks_out = hchunks;
-        return 0;
+    XTRY(n, scratch_ensure(n, *n->slab_sel, (size_t)c.chunks * (K + 1) * s.Cout * sizeof(float)));
+    float* const slab = (float*)n->slab_sel->p;
+    const PooledGrad pg = pdz ? *pdz : PooledGrad{nullptr, nullptr, nullptr};
+    switch (c.kernel) {
+    case WgradKernel::conv1_wgrad_f32: {
+        const dim3 grid((unsigned)(s.Cout / 32), (unsigned)c.chunks);
+        with_const<3, 1>(s.Cin, [&](auto CIN) { with_const<16, 8>(c.tile_w, [&](auto TW) { with_bool(pooled, [&](auto PDZ) { with_storage(st.y16, [&](auto T) {
+            hipLaunchKernelGGL((k_conv1_wgrad_f32<CV(CIN), CV(TW), CV(PDZ), CT(T)>), grid, dim3(kThreads), 0, n->stream, X, (const CT(T)*)dZ, slab, s, c.tiles_w, c.tiles_h, c.bpc,
+                               PooledGradT<CT(T)>{(const CT(T)*)pg.dP, (const CT(T)*)pg.P, pg.idx});
+        }); }); }); });
+        break;
     }
-    if ((st.x16 || st.y16) && n->precision != RCN_HIPX_BF16) return fail(n, -3, kStoreGap);
-    if (n->precision != RCN_HIPX_BF16 && wgrad_halo_runs(n, s, ks)) {
-        // fp32 LDS-tiled (convnet_halo.hpp): workgroup = (32 input channels, 32 output channels, chunk of pixel blocks), all nine taps.
-        // Every chunk costs one (K+1) x Cout partial written and read back by the reduce whatever the number of (ci, co) workgroups
-        // that share it, so: as few chunks as fill the chip twice over.
-        const int tw = halo_plan(n, s).tw, nimg = 16 / tw;
-        const int tiles_w = (s.W + tw - 1) / tw, tiles_h = (s.H + 7) / 8;
-        const long long blocks = (long long)tiles_w * tiles_h * ((s.N + nimg - 1) / nimg);
-        const int target = n->opt.wgh_f32_target;
-        const long long combos = (long long)(s.Cin / 32) * (s.Cout / 32);
-        long long want = (target + combos - 1) / combos;
-        if (want > blocks) want = blocks;
-        if (want > 32768) want = 32768;
-        const int bpc = (int)((blocks + want - 1) / want);
-        const int hchunks = (int)((blocks + bpc - 1) / bpc);
-        XTRY(n, scratch_ensure(n, (*n->slab_sel), (size_t)hchunks * (K + 1) * s.Cout * sizeof(float)));
-        const dim3 hgrid((unsigned)(s.Cin / 32), (unsigned)(s.Cout / 32), (unsigned)hchunks);
-        const PooledGrad pg = pdz ? *pdz : PooledGrad{nullptr, nullptr, nullptr};
-#define WGF_CASE(TW_) do { if (pdz) hipLaunchKernelGGL((k_wgrad3x3_halo_f32<TW_, true>), hgrid, dim3(kThreads), 0, n->stream, X, dZ, (float*)(*n->slab_sel).p, s, tiles_w, tiles_h, bpc, pg); \
-                           else hipLaunchKernelGGL((k_wgrad3x3_halo_f32<TW_, false>), hgrid, dim3(kThreads), 0, n->stream, X, dZ, (float*)(*n->slab_sel).p, s, tiles_w, tiles_h, bpc, pg); } while (0)
-        if (dry_note(n, "  wgrad conv3x3 %dx%dx%d->%d%s: k_wgrad3x3_halo_f32<%d>, %d chunks x %lld tiles", s.H, s.W, s.Cin, s.Cout, pdz ? " pooled-dZ" : "", tw, hchunks, combos)) { *chunks_out = hchunks; return 0; }
-        if (tw == 16) WGF_CASE(16); else WGF_CASE(8);
-#undef WGF_CASE
-        XTRY(n, hipGetLastError());
-        *chunks_out = hchunks;
-        return 0;
+    case WgradKernel::halo_f32: {
+        const dim3 grid((unsigned)(s.Cin / 32), (unsigned)(s.Cout / 32), (unsigned)c.chunks);
+        with_const<16, 8>(c.tile_w, [&](auto TW) { with_bool(pooled, [&](auto PDZ) {
+            hipLaunchKernelGGL((k_wgrad3x3_halo_f32<CV(TW), CV(PDZ)>), grid, dim3(kThreads), 0, n->stream, X, dZ, slab, s, c.tiles_w, c.tiles_h, c.bpc, pg);
+        }); });
+        break;
     }
-    if (wgrad_halo_runs(n, s, ks)) {
-        // LDS-tiled: input halo + dZ block staged once per 8x16 pixel block, nine waves = nine filter taps (convnet_bf16.hpp)
-        const int tw = (s.W + kHaloTW - 1) / kHaloTW, th = (s.H + kHaloTH - 1) / kHaloTH;
-        const long long blocks = (long long)tw * th * s.N;
-        const int hb = s.Cin == 32 ? 32 : 64, hbn = (s.Cout % 64 == 0) ? 64 : 32;
-        // Pixel blocks per chunk: every chunk costs one (K+1) x Cout partial tile written and read back by the reduce, so aim at
-        // `target` workgroups in total (tiles per chunk x chunks) rather than at a fixed chunk count -- wide layers have many
-        // tiles per chunk and need few chunks.
-        // (256 = one per CU: the 576-thread workgroup with its 64+ accumulator registers per wave is alone on its CU anyway, and every
-        // chunk fewer is a partial [W | b] less to write and reduce: synth-224 bf16 5.20 ms at 512, 5.05 at 256, 5.49 at 384 -- 1.5 per CU)
-        const int target = n->opt.wgh_target;
-        const long long tiles = (long long)(s.Cin / hb) * (s.Cout / hbn);
-        int bpc = (int)((blocks * tiles + target - 1) / target);
-        if (bpc < 8) bpc = blocks < 8 ? (int)blocks : 8;
-        const int hchunks = (int)((blocks + bpc - 1) / bpc);
-        XTRY(n, scratch_ensure(n, (*n->slab_sel), (size_t)hchunks * (K + 1) * s.Cout * sizeof(float)));
-        const dim3 hgrid((unsigned)(s.Cin / hb), (unsigned)(s.Cout / hbn), (unsigned)hchunks);
-        const PooledGrad pg = pdz ? *pdz : PooledGrad{nullptr, nullptr, nullptr};
-#define WGH_CASE_T(CB_, BN_, TS_) do { const PooledGradT<TS_> pgt{(const TS_*)pg.dP, (const TS_*)pg.P, pg.idx}; \
-                                if (pdz) hipLaunchKernelGGL((k_wgrad3x3_halo_bf16<CB_, BN_, true, TS_>), hgrid, dim3(kWgHaloThreads), 0, n->stream, (const TS_*)X, (const TS_*)dZ, (float*)(*n->slab_sel).p, s, tw, th, bpc, hchunks, pgt); \
-                                else hipLaunchKernelGGL((k_wgrad3x3_halo_bf16<CB_, BN_, false, TS_>), hgrid, dim3(kWgHaloThreads), 0, n->stream, (const TS_*)X, (const TS_*)dZ, (float*)(*n->slab_sel).p, s, tw, th, bpc, hchunks, pgt); } while (0)
-#define WGH_CASE(CB_, BN_) do { if (st.x16) WGH_CASE_T(CB_, BN_, __bf16); else WGH_CASE_T(CB_, BN_, float); } while (0)
-        if (st.x16 != st.y16) return fail(n, -3, kStoreGap);
-        if (dry_note(n, "  wgrad conv3x3 %dx%dx%d->%d%s: k_wgrad3x3_halo_bf16<%d, %d>, %d chunks x %lld tiles", s.H, s.W, s.Cin, s.Cout, pdz ? " pooled-dZ" : "", hb, hbn, hchunks, tiles)) { *chunks_out = hchunks; return 0; }
-        if (hb == 32) { if (hbn == 64) WGH_CASE(32, 64); else WGH_CASE(32, 32); }
-        else { if (hbn == 64) WGH_CASE(64, 64); else WGH_CASE(64, 32); }
-#undef WGH_CASE
-#undef WGH_CASE_T
-        XTRY(n, hipGetLastError());
-        *chunks_out = hchunks;
-        return 0;
+    case WgradKernel::halo_bf16: {
+        const dim3 grid((unsigned)(s.Cin / c.cb), (unsigned)(s.Cout / c.bn), (unsigned)c.chunks);
+        with_const<32, 64>(c.cb, [&](auto CB) { with_const<64, 32>(c.bn, [&](auto BN) { with_bool(pooled, [&](auto PDZ) { with_storage(st.x16, [&](auto T) {
+            hipLaunchKernelGGL((k_wgrad3x3_halo_bf16<CV(CB), CV(BN), CV(PDZ), CT(T)>), grid, dim3(kWgHaloThreads), 0, n->stream, (const CT(T)*)X, (const CT(T)*)dZ, slab, s, c.tiles_w, c.tiles_h,
+                               c.bpc, c.chunks, PooledGradT<CT(T)>{(const CT(T)*)pg.dP, (const CT(T)*)pg.P, pg.idx});
+        }); }); }); });
+        break;
     }
-    if (n->precision == RCN_HIPX_BF16 && !smallc) {
-        // bf16 operands, transposed LDS reads (convnet_bf16.hpp); NKB waves per workgroup, one 32-row k-block each
-        const int nkb = K / 32;
-        const int nk = nkb % 4 == 0 ? 4 : nkb % 3 == 0 ? 3 : nkb % 2 == 0 ? 2 : 1;
-        // A wave owns one 32-row k-block x bn columns over the chunk's pixels, so a dense layer behind a pooled map is FEW waves (MNIST shape
-        // 3136 -> 128 at B = 4096: 98 x 2 x 4 chunks = 784 on the chip's 1024 SIMDs, 62 us for 7 us of traffic).  Below two waves per SIMD
-        // take 32-wide column blocks (no more slab, X re-read from L2), below one per SIMD also shorter chunks (down to 256 pixels).
-        const int policy = n->opt.wgb_policy;
-        int bn = bn0, ppc = kPixPerChunk, chunks = chunks0;
-        if (policy) {
-            if ((long long)nkb * (s.Cout / bn) * chunks < 2048) bn = 32;
-            while ((long long)nkb * (s.Cout / bn) * chunks < 1024 && ppc > 256) { ppc /= 2; chunks = (int)((M + ppc - 1) / ppc); }
-            XTRY(n, scratch_ensure(n, (*n->slab_sel), (size_t)chunks * (K + 1) * s.Cout * sizeof(float)));
-        }
-        const WgradGrid gdb{nkb / nk, s.Cout / bn, chunks, xcd_remap(n)};
-        const dim3 gridb(gdb.launch_blocks());
-#define WGB_CASE(KS_, BN_, NK_) do { if (st.x16) hipLaunchKernelGGL((k_conv_wgrad_bf16<KS_, BN_, NK_, __bf16>), gridb, dim3(64 * NK_), 0, n->stream, (const __bf16*)X, dZ, (float*)(*n->slab_sel).p, s, ppc, gdb); \
-                                     else hipLaunchKernelGGL((k_conv_wgrad_bf16<KS_, BN_, NK_>), gridb, dim3(64 * NK_), 0, n->stream, X, dZ, (float*)(*n->slab_sel).p, s, ppc, gdb); } while (0)
-        if (st.y16 || (st.x16 && ks != 1)) return fail(n, -3, kStoreGap);
-#define WGB_NK(KS_, BN_) do { if (nk == 4) WGB_CASE(KS_, BN_, 4); else if (nk == 3) WGB_CASE(KS_, BN_, 3); else if (nk == 2) WGB_CASE(KS_, BN_, 2); else WGB_CASE(KS_, BN_, 1); } while (0)
-#define WGB_BN(KS_) do { if (bn == 64) WGB_NK(KS_, 64); else WGB_NK(KS_, 32); } while (0)
-        if (dry_note(n, "  wgrad %s %dx%dx%d->%d: k_conv_wgrad_bf16<%d, %d, %d>, %d chunks", ks == 3 ? "conv3x3" : "dense", s.H, s.W, s.Cin, s.Cout, ks, bn, nk, chunks)) { *chunks_out = chunks; return 0; }
-        if (ks == 3) WGB_BN(3); else WGB_BN(1);
-#undef WGB_BN
-#undef WGB_NK
-#undef WGB_CASE
-        XTRY(n, hipGetLastError());
-        *chunks_out = chunks;
-        return 0;
+    case WgradKernel::wgrad_bf16: {
+        const WgradGrid gd{K / 32 / c.nk, s.Cout / c.bn, c.chunks, n->opt.xcd_remap};
+        const dim3 grid(gd.launch_blocks());
+        with_const<3, 1>(ks, [&](auto KS) { with_const<64, 32>(c.bn, [&](auto BN) { with_const<4, 3, 2, 1>(c.nk, [&](auto NK) {
+            if (st.x16) hipLaunchKernelGGL((k_conv_wgrad_bf16<CV(KS), CV(BN), CV(NK), __bf16>), grid, dim3(64 * CV(NK)), 0, n->stream, (const __bf16*)X, dZ, slab, s, c.ppc, gd);
+            else hipLaunchKernelGGL((k_conv_wgrad_bf16<CV(KS), CV(BN), CV(NK)>), grid, dim3(64 * CV(NK)), 0, n->stream, X, dZ, slab, s, c.ppc, gd);
+        }); }); });
+        break;
     }
-    // (as in the bf16 branch above: below two waves per SIMD the column blocks are 32 wide -- CIFAR net's 2048 -> 256 at B = 512: 256 -> 512
-    // workgroups, step 0.419 -> 0.417 ms; MNIST shape B = 256: 0.165 -> 0.1625 ms)
-    if (st.x16 || st.y16) return fail(n, -3, kStoreGap);
-    const int f32_policy = n->opt.wgf_policy;
-    const int bnf = (f32_policy && !smallc && 4LL * (K / 32) * (s.Cout / bn0) * chunks < 2048) ? 32 : bn0;
-    const WgradGrid gd{smallc ? 1 : K / 32, s.Cout / bnf, chunks, xcd_remap(n)};
-    const dim3 grid(gd.launch_blocks());
-#define WG_CASE(KS_, SM_, BN_) hipLaunchKernelGGL((k_conv_wgrad<KS_, SM_, BN_>), grid, dim3(kThreads), 0, n->stream, X, dZ, (float*)(*n->slab_sel).p, s, kPixPerChunk, gd)
-#define WG_BN(KS_, SM_) do { if (bnf == 64) WG_CASE(KS_, SM_, 64); else WG_CASE(KS_, SM_, 32); } while (0)
-    if (dry_note(n, "  wgrad %s %dx%dx%d->%d: k_conv_wgrad<%d, %s, %d>, %d chunks", ks == 3 ? "conv3x3" : "dense", s.H, s.W, s.Cin, s.Cout, ks, smallc ? "gather" : "tile", bnf, chunks)) { *chunks_out = chunks; return 0; }
-    if (ks == 3) { if (smallc) WG_BN(3, true); else WG_BN(3, false); }
-    else { if (smallc) WG_BN(1, true); else WG_BN(1, false); }
-#undef WG_BN
-#undef WG_CASE
+    case WgradKernel::wgrad_f32: {
+        const WgradGrid gd{c.smallc ? 1 : K / 32, s.Cout / c.bn, c.chunks, n->opt.xcd_remap};
+        const dim3 grid(gd.launch_blocks());
+        with_const<3, 1>(ks, [&](auto KS) { with_bool(c.smallc, [&](auto SM) { with_const<64, 32>(c.bn, [&](auto BN) {
+            hipLaunchKernelGGL((k_conv_wgrad<CV(KS), CV(SM), CV(BN)>), grid, dim3(kThreads), 0, n->stream, X, dZ, slab, s, c.ppc, gd);
+        }); }); });
+        break;
+    }
+    }
     XTRY(n, hipGetLastError());
-    *chunks_out = chunks;
     return 0;
 }
+#undef CT
+#undef CV
 
 float* P(rcn_hipx_net* n, long long off) { return (float*)n->params.p + off; }
 
@@ -732,7 +425,7 @@ int forward(rcn_hipx_net* n, const float* x, int B, size_t n_layers = (size_t)-1
             XTRY(n, hipGetLastError());
         } else if (l.kind == RCN_HIPX_CONV3X3_RELU) {
             const ConvShape cs{B, l.H, l.W, l.Cin, l.CoutP};
-            if (l.pool_follows && conv_pool_fusable(n, cs)) {
+            if (l.pool_follows && conv_pool_fusable(*n, cs)) {
                 // the pool that follows runs in this kernel's epilogue: only the pooled map (and its arg-max image) is written
                 Layer& pl = n->L[i + 1];
                 RTRY(launch_conv(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)pl.out.p, cs, 3, 4, (uint8_t*)pl.idx.p, nullptr, false, wb_of(n, l.wbf_off), Store{cur16, n->store16}));
@@ -759,8 +452,7 @@ int forward(rcn_hipx_net* n, const float* x, int B, size_t n_layers = (size_t)-1
 // The slab of partial [W | b] tiles of layer i (chunks x (K + 1) x Cout, as the weight-gradient kernels leave it in the layer's slab)
 // is queued for the step's ONE reduction launch (run_reduce_jobs): summed in chunk order, and either applied (p <- p - lr g, the flipped
 // copy of the weights kept current) or written to grad.  [W | b] is contiguous (b_off == w_off + K * CoutP): one job finishes both.
-int reduce_slab(rcn_hipx_net* n, size_t i, int chunks, int ks, const ConvShape& s, float lr, float* grad, bool apply) {
-    (void)lr;
+int reduce_slab(rcn_hipx_net* n, size_t i, int chunks, int ks, const ConvShape& s, float* grad, bool apply) {
     Layer& l = n->L[i];
     if (n->jobs.njobs >= kMaxReduceJobs) return fail(n, -3, "too many layers with parameters for one reduction launch");
     ReduceJob& jb = n->jobs.j[n->jobs.njobs];
@@ -822,7 +514,7 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             const int fuse_on = n->opt.fuse_pool_bwd;
             const Layer& cl = n->L[i - 1];
             const ConvShape cs{B, cl.H, cl.W, cl.Cin, cl.CoutP};
-            const bool fusable = fuse_on && wgrad_halo_runs(n, cs, 3) && (i - 1 == 0 || conv_halo_runs(n, ConvShape{B, cl.H, cl.W, cl.CoutP, cl.Cin}));
+            const bool fusable = fuse_on && wgrad_halo_runs(*n, cs, 3) && (i - 1 == 0 || conv_halo_runs(*n, ConvShape{B, cl.H, cl.W, cl.CoutP, cl.Cin}));
             if (fusable) {
                 pooled[i - 1] = PooledGrad{(const float*)l.dout.p, (const float*)l.out.p, (const uint8_t*)l.idx.p};
                 if (dry_note(n, "  pool-bwd %dx%dx%d: none (the convolution's gradient kernels unpool while staging)", l.H, l.W, l.Cin))
@@ -874,7 +566,7 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
         if (on_side) n->stream = n->side;
         n->slab_sel = &l.slab;
         RTRY(launch_wgrad(n, in, dZ, s, ks, &chunks, pooled[i].dP ? &pooled[i] : nullptr, Store{stage16(n, i - 1), stage16(n, i)}));
-        RTRY(reduce_slab(n, (size_t)i, chunks, ks, s, lr, grad, apply));
+        RTRY(reduce_slab(n, (size_t)i, chunks, ks, s, grad, apply));
         n->stream = main_s;
     }
     return 0;
@@ -888,9 +580,9 @@ void backward_reset(rcn_hipx_net* n, int first, bool first_gated) {
     n->ev_next = 0;
 }
 
-int backward(rcn_hipx_net* n, const float* x, int B, float lr, float* grad, bool apply, int first = -1, bool first_gated = false) {
+int backward(rcn_hipx_net* n, const float* x, int B, float lr, float* grad, bool apply, int first, bool first_gated) {
     backward_reset(n, first, first_gated);
-    RTRY(backward_layers(n, x, B, lr, grad, apply, first >= 0 ? first : (int)n->L.size() - 1, 0, true));
+    RTRY(backward_layers(n, x, B, lr, grad, apply, first, 0, true));
     if (n->bw.side_busy) RTRY(stream_after(n, n->side, n->stream));   // join: the step's next kernels (and an end of capture) find everything on the main stream
     return run_reduce_jobs(n, lr, apply);                             // every layer's slab in one launch; no weight was written before this point
 }
@@ -966,25 +658,32 @@ int refresh_flipped(rcn_hipx_net* n) {
     return 0;
 }
 
-int backward(rcn_hipx_net* n, const float* x, int B, float lr, float* grad, bool apply, int first, bool first_gated);
-int forward(rcn_hipx_net* n, const float* x, int B, size_t n_layers);
+// The front half of a step: bf16 operand copies, forward pass, loss and d logits -- where the classifier head is the fused one, k_head_f32
+// instead, which also does that layer's share of the backward pass (its slab is queued for the reduction).  *first: the layer the backward
+// walk starts at; *gated: its dout already holds dZ.
+int step_front(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float* grad, bool apply, float* loss_dev, int* first, bool* gated) {
+    n->jobs.njobs = 0;
+    RTRY(prep_bf16_weights(n));
+    const int last = (int)n->L.size() - 1;
+    *gated = head_fusable(n);
+    *first = *gated ? last - 1 : last;
+    if (!*gated) {
+        RTRY(forward(n, x, B));
+        return loss_and_dlogits(n, labels, B, loss_dev, true);
+    }
+    RTRY(forward(n, x, B, (size_t)last));
+    int chunks = 0;
+    n->slab_sel = &n->L[last].slab;
+    RTRY(launch_head(n, labels, B, loss_dev, &chunks));
+    return reduce_slab(n, (size_t)last, chunks, 1, ConvShape{B, 1, 1, n->L[last].K, n->L[last].CoutP}, grad, apply);
+}
 
 // forward + loss + backward of one batch: parameters updated in place (apply) or gradients written to grad (padded layout)
 int step_core(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float lr, float* grad, bool apply, float* loss_dev) {
-    n->jobs.njobs = 0;
-    RTRY(prep_bf16_weights(n));
-    if (head_fusable(n)) {
-        const int last = (int)n->L.size() - 1;
-        RTRY(forward(n, x, B, (size_t)last));
-        int chunks = 0;
-        n->slab_sel = &n->L[last].slab;
-        RTRY(launch_head(n, labels, B, loss_dev, &chunks));
-        RTRY(reduce_slab(n, (size_t)last, chunks, 1, ConvShape{B, 1, 1, n->L[last].K, n->L[last].CoutP}, lr, grad, apply));
-        return backward(n, x, B, lr, grad, apply, last - 1, true);
-    }
-    RTRY(forward(n, x, B, (size_t)-1));
-    RTRY(loss_and_dlogits(n, labels, B, loss_dev, true));
-    return backward(n, x, B, lr, grad, apply, -1, false);
+    int first = 0;
+    bool gated = false;
+    RTRY(step_front(n, x, labels, B, grad, apply, loss_dev, &first, &gated));
+    return backward(n, x, B, lr, grad, apply, first, gated);
 }
 
 void drop_graphs(rcn_hipx_net* n) { for (auto& kv : n->graphs) (void)hipGraphExecDestroy(kv.second); n->graphs.clear(); }
@@ -1019,25 +718,11 @@ int bucket_layout(rcn_hipx_net* n, long long min_bytes) {
 
 // forward, loss (and, where the classifier head is the fused one, its share of the backward pass): everything in front of bucket 0
 int grad_begin(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float* grad, float* loss_dev, long long min_bytes) {
-    n->jobs.njobs = 0;
     const int nb = bucket_layout(n, min_bytes);
     n->bw.x = x; n->bw.B = B; n->bw.grad = grad; n->bw.taken = 0;
-    RTRY(prep_bf16_weights(n));
-    if (head_fusable(n)) {
-        const int last = (int)n->L.size() - 1;
-        RTRY(forward(n, x, B, (size_t)last));
-        int chunks = 0;
-        n->slab_sel = &n->L[last].slab;
-        RTRY(launch_head(n, labels, B, loss_dev, &chunks));
-        RTRY(reduce_slab(n, (size_t)last, chunks, 1, ConvShape{B, 1, 1, n->L[last].K, n->L[last].CoutP}, 0.f, grad, false));
-        backward_reset(n, last - 1, true);
-        n->bw.next = last - 1;
-    } else {
-        RTRY(forward(n, x, B, (size_t)-1));
-        RTRY(loss_and_dlogits(n, labels, B, loss_dev, true));
-        backward_reset(n, -1, false);
-        n->bw.next = (int)n->L.size() - 1;
-    }
+    bool gated = false;
+    RTRY(step_front(n, x, labels, B, grad, false, loss_dev, &n->bw.next, &gated));
+    backward_reset(n, n->bw.next, gated);
     return nb;
 }
 
@@ -1112,6 +797,33 @@ void copy_layer_table(rcn_hipx_net& to, const rcn_hipx_net& from) {
     to.n_pad = from.n_pad; to.n_log = from.n_log;
 }
 
+// Host-only nets for dry runs (no device, no stream, no buffers).  From a description: what rcn_hipx_create would make of it now (options
+// seeded from the environment), `mode` being a rcn_hipx_set_precision mode; returns describe_layers' status ...
+int make_dry_net(rcn_hipx_net& net, int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, int n_layers, int batch, int mode, int tiling) {
+    net.in_h = in_h; net.in_w = in_w; net.in_c = in_c; net.max_batch = batch; net.dry = true;
+    net.precision = mode == RCN_HIPX_FP32 ? RCN_HIPX_FP32 : RCN_HIPX_BF16; net.store16 = mode == RCN_HIPX_BF16_STORED; net.tiling = tiling;
+    seed_options(net.opt);
+    return describe_layers(&net, in_h, in_w, in_c, layers, n_layers);
+}
+// ... or from an existing net: its layers, precision, tiling, options and optimiser -- the plan and the step agree by construction
+void make_dry_net(rcn_hipx_net& net, const rcn_hipx_net& from, int batch) {
+    net.in_h = from.in_h; net.in_w = from.in_w; net.in_c = from.in_c; net.max_batch = batch; net.classes = from.classes; net.dry = true;
+    static_cast<Selection&>(net) = from;
+    net.sgd_mu = from.sgd_mu; net.sgd_wd = from.sgd_wd; net.sgd_nesterov = from.sgd_nesterov;
+    copy_layer_table(net, from);
+}
+
+// Would every layer of this net run on kernels that take bf16 tensors (RCN_HIPX_BF16_STORED)?  Asked of the plan, the same walk as the step
+// at the net's largest batch: 0, or the step's status with its message in *why.
+int store16_covered(const rcn_hipx_net& n, std::string* why) {
+    rcn_hipx_net probe;
+    make_dry_net(probe, n, n.max_batch);
+    probe.precision = RCN_HIPX_BF16; probe.store16 = true;
+    const int st = step_core(&probe, nullptr, nullptr, n.max_batch, 0.f, nullptr, true, nullptr);
+    if (st != 0) *why = probe.err;
+    return st;
+}
+
 const char* precision_name(int precision, bool store16) { return precision != RCN_HIPX_BF16 ? "fp32 operands" : store16 ? "bf16 operands, the convolutional stage's tensors stored as bf16" : "bf16 operands"; }
 
 }  // namespace
@@ -1174,14 +886,10 @@ int rcn_hipx_set_precision(rcn_hipx_net* n, int mode) {
         return fail(n, -1, "set_precision: mode must be RCN_HIPX_FP32, RCN_HIPX_BF16 or RCN_HIPX_BF16_STORED");
     const int prec = mode == RCN_HIPX_FP32 ? RCN_HIPX_FP32 : RCN_HIPX_BF16;
     const bool st16 = mode == RCN_HIPX_BF16_STORED;
-    if (st16) {
-        // does every layer of this net run on kernels that take bf16 tensors?  Asked of the plan (the same walk as the step), before anything changes.
-        rcn_hipx_net probe;
-        probe.in_h = n->in_h; probe.in_w = n->in_w; probe.in_c = n->in_c; probe.max_batch = n->max_batch; probe.classes = n->classes;
-        probe.precision = prec; probe.store16 = true; probe.tiling = n->tiling; probe.overlap = 0; probe.dry = true; probe.opt = n->opt;
-        copy_layer_table(probe, *n);
-        const int ps = step_core(&probe, nullptr, nullptr, n->max_batch, 0.f, nullptr, true, nullptr);
-        if (ps != 0) return fail(n, ps, probe.err);
+    if (st16) {                                         // before anything changes
+        std::string why;
+        const int ps = store16_covered(*n, &why);
+        if (ps != 0) return fail(n, ps, why);
     }
     Dev g(n->device);
     if (prec != n->precision || st16 != n->store16) { XTRY(n, hipStreamSynchronize(n->stream)); drop_graphs(n); }
@@ -1440,15 +1148,10 @@ int rcn_hipx_step_flops(const rcn_hipx_net* n, int B, double* flops) {
 int rcn_hipx_plan(int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, int n_layers, int batch, int precision, int tiling, char* out, int cap) {
     if (!layers || n_layers < 1 || in_h < 1 || in_w < 1 || in_c < 1 || batch < 1 || !out || cap < 1) return -1;
     if ((precision != RCN_HIPX_FP32 && precision != RCN_HIPX_BF16 && precision != RCN_HIPX_BF16_STORED) || tiling < RCN_HIPX_TILING_GEMM || tiling > RCN_HIPX_TILING_LDS) return -1;
-    rcn_hipx_net net;                                   // host-only: no device, no stream, no buffers
-    net.in_h = in_h; net.in_w = in_w; net.in_c = in_c; net.max_batch = batch;
-    net.store16 = precision == RCN_HIPX_BF16_STORED;
-    if (net.store16) precision = RCN_HIPX_BF16;
-    net.precision = precision; net.tiling = tiling; net.overlap = 0; net.dry = true;
-    seed_options(net.opt);                              // as a net created now would be (rcn_hipx_plan_net: an existing net's own options)
-    int st = describe_layers(&net, in_h, in_w, in_c, layers, n_layers);
+    rcn_hipx_net net;                                   // (its options: as a net created now would have them; rcn_hipx_plan_net: an existing net's own)
+    int st = make_dry_net(net, in_h, in_w, in_c, layers, n_layers, batch, precision, tiling);
     if (st == 0) {
-        net.plan = "forward + loss + backward of one batch of " + std::to_string(batch) + " (" + precision_name(precision, net.store16) + "), launch by launch:\n";
+        net.plan = "forward + loss + backward of one batch of " + std::to_string(batch) + " (" + precision_name(net.precision, net.store16) + "), launch by launch:\n";
         st = step_core(&net, nullptr, nullptr, batch, 0.f, nullptr, true, nullptr);
     }
     const std::string& text = st == 0 ? net.plan : net.err;
@@ -1463,12 +1166,7 @@ int rcn_hipx_plan_buckets(int in_h, int in_w, int in_c, const rcn_hipx_layer* la
     if (!layers || n_layers < 1 || in_h < 1 || in_w < 1 || in_c < 1 || batch < 1 || !out || cap < 1 || min_bucket_bytes < 0) return -1;
     if ((precision != RCN_HIPX_FP32 && precision != RCN_HIPX_BF16 && precision != RCN_HIPX_BF16_STORED) || tiling < RCN_HIPX_TILING_GEMM || tiling > RCN_HIPX_TILING_LDS) return -1;
     rcn_hipx_net net;
-    net.in_h = in_h; net.in_w = in_w; net.in_c = in_c; net.max_batch = batch;
-    net.store16 = precision == RCN_HIPX_BF16_STORED;
-    if (net.store16) precision = RCN_HIPX_BF16;
-    net.precision = precision; net.tiling = tiling; net.overlap = 0; net.dry = true;
-    seed_options(net.opt);
-    int st = describe_layers(&net, in_h, in_w, in_c, layers, n_layers);
+    int st = make_dry_net(net, in_h, in_w, in_c, layers, n_layers, batch, precision, tiling);
     if (st == 0) {
         net.plan = "gradients of one batch of " + std::to_string(batch) + " in buckets of at least " + std::to_string((long long)min_bucket_bytes) +
                    " bytes (data-parallel step: a bucket's all-reduce overlaps the backward pass below it):\n";
@@ -1481,15 +1179,11 @@ int rcn_hipx_plan_buckets(int in_h, int in_w, int in_c, const rcn_hipx_layer* la
     return st;
 }
 
-// the same walk for an EXISTING net, with that net's own precision, tiling and options: the plan and the step agree by construction
+// the same walk for an EXISTING net, with that net's own precision, tiling, options and optimiser
 int rcn_hipx_plan_net(const rcn_hipx_net* n, int batch, char* out, int cap) {
     if (!n || batch < 1 || batch > n->max_batch || !out || cap < 1) return -1;
     rcn_hipx_net net;
-    net.in_h = n->in_h; net.in_w = n->in_w; net.in_c = n->in_c; net.max_batch = batch; net.classes = n->classes;
-    net.precision = n->precision; net.store16 = n->store16; net.tiling = n->tiling; net.overlap = 0; net.dry = true;
-    net.opt = n->opt;
-    net.sgd_mu = n->sgd_mu; net.sgd_wd = n->sgd_wd; net.sgd_nesterov = n->sgd_nesterov;
-    copy_layer_table(net, *n);
+    make_dry_net(net, *n, batch);
     net.plan = "forward + loss + backward of one batch of " + std::to_string(batch) + " (" + precision_name(net.precision, net.store16) + "), launch by launch:\n";
     const int st = step_core(&net, nullptr, nullptr, batch, 0.f, nullptr, true, nullptr);
     const std::string& text = st == 0 ? net.plan : net.err;

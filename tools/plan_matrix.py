@@ -1,0 +1,87 @@
+"""The text (or the error) of rcn_hipx_plan / rcn_hipx_plan_buckets over a matrix of nets, batches, precisions, tilings and options, in a
+fixed order.  No GPU needed.  Two builds choose the same kernels for every layer exactly when their outputs are equal:
+
+    python tools/plan_matrix.py > after.txt          # and the same in a checkout of the commit to compare with (--root)
+    diff before.txt after.txt
+
+The output is not committed: it would pin every intended change of a dispatch rule.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+CONV_TAIL = (("dense_relu", 128), ("dense", 10))
+# small nets that reach the branches the benchmark nets do not (name -> (input shape, layers))
+SMALL = {
+    # maps too small for the LDS-tiled weight gradient: bf16 storage refuses this one
+    "w8": ((8, 8, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense", 10))),
+    "w12": ((12, 12, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",)) + CONV_TAIL),
+    "w14": ((14, 14, 3), (("conv", 32), ("pool",), ("conv", 32), ("dense", 10))),
+    "w24": ((24, 24, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("conv", 128), ("pool",), ("dense_relu", 256), ("dense", 10))),
+    "w56": ((56, 56, 3), (("conv", 32), ("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense", 10))),
+    # a third convolution on the 7 x 7 map of the mnist shape (odd sides: no pool can follow)
+    "odd7": ((28, 28, 1), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("conv", 64)) + CONV_TAIL),
+    # two input channels: the gather loader without the first layer's own kernels
+    "cin2": ((16, 16, 2), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 64), ("dense", 10))),
+    # channel pairs 32->32, 32->64, 64->128; convolutions in a row and one with no pool behind it
+    "pairs": ((16, 16, 3), (("conv", 32), ("conv", 32), ("pool",), ("conv", 64), ("pool",), ("conv", 128)) + CONV_TAIL),
+    # 96->96, and a hidden layer of 512 (no fused head)
+    "c96": ((16, 16, 3), (("conv", 96), ("conv", 96), ("pool",), ("dense_relu", 512), ("dense", 10))),
+    # 128->256, and no hidden dense layer (no fused head)
+    "c256": ((16, 16, 1), (("conv", 128), ("conv", 256), ("pool",), ("dense", 10))),
+    # refused by the layer table
+    "bad_c48": ((16, 16, 3), (("conv", 48), ("pool",), ("dense", 10))),
+    "bad_cin4": ((16, 16, 4), (("conv", 32), ("pool",), ("dense", 10))),
+    "bad_oddpool": ((7, 7, 1), (("conv", 32), ("pool",), ("dense", 10))),
+}
+BATCHES = (1, 2, 7, 16, 128, 512, 4096)
+PRECISIONS = ("fp32", "bf16", "bf16_stored")
+TILINGS = ("gemm", "auto", "lds")
+# one at a time, through the environment (a plan seeds its options from it on every call)
+OPTIONS = (("HALO", 0), ("BF16_PIPE", 0), ("BF16_1CB", 0), ("BF16_ROWS16", 1), ("HALO_WGRAD", 0), ("FUSE_POOL_BWD", 0), ("HEAD", 0), ("XCD_REMAP", 1),
+           ("PIX_PER_CHUNK", 256), ("WG_TARGET", 1024), ("WGH_F32_TARGET", 128), ("WGH_TARGET", 512), ("WGB_POLICY", 0), ("WGF_POLICY", 0))
+BUCKETS = (0, 256 << 10, 1 << 20, 1 << 30)
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="the checkout whose built library is asked (default: this one)")
+    root = os.path.abspath(ap.parse_args().root)
+    sys.path.insert(0, root)
+    import bench_convnet as bc
+    from mercer_research_amd.convnet import ConvNetError, plan
+    for k in list(os.environ):
+        if k.startswith("RCN_HIPX_"):
+            del os.environ[k]
+
+    def show(title, in_shape, layers, batch, **kw):
+        print(f"==== {title}")
+        try:
+            print("status 0\n" + plan(in_shape, layers, batch, **kw))
+        except ConvNetError as e:
+            print(e)
+
+    nets = [(name, shape, layers, tuple(b for b in BATCHES if b <= 128) if name == "synth224" else BATCHES) for name, (shape, layers, _) in bc.CONFIGS.items()]
+    nets += [(name, shape, layers, BATCHES) for name, (shape, layers) in SMALL.items()]
+    for name, shape, layers, batches in nets:
+        for b in batches:
+            for p in PRECISIONS:
+                for t in TILINGS:
+                    show(f"{name} B={b} {p} {t}", shape, layers, b, precision=p, tiling=t)
+    for env, value in OPTIONS:
+        os.environ["RCN_HIPX_" + env] = str(value)
+        for name, (shape, layers, b0) in bc.CONFIGS.items():
+            for b in (16, b0):
+                for p in PRECISIONS:
+                    show(f"{name} B={b} {p} auto RCN_HIPX_{env}={value}", shape, layers, b, precision=p)
+        del os.environ["RCN_HIPX_" + env]
+    for name, (shape, layers, b0) in bc.CONFIGS.items():
+        for p in PRECISIONS:
+            for nbytes in BUCKETS:
+                show(f"{name} B={b0} {p} auto buckets>={nbytes}", shape, layers, b0, precision=p, buckets=nbytes)
+
+
+if __name__ == "__main__":
+    main()
