@@ -233,6 +233,32 @@ __device__ inline unsigned long long xcd_wait(const unsigned* f0, int n0, const 
         // first is looked at, measured slower -- 6.64 -- the extra loads queue in front of the payload loads that follow)
     }
 }
+// The same wait for a wave that reads the payload of a FEW producers only and names just those: entries first, first + stride,
+// first + 2 stride, ... below n of one flag table, one per lane (none named: returns at once).  Same bounded loop, same clock check,
+// same look at the error word.  Returns the LANES still behind; xcd_missing turns them into producers for the time-out record (outside
+// the loop, so that `first` and `stride` are not live in it).
+// (A function of its own instead of a more general xcd_wait: the f64 instantiations sit at the 256-register ceiling and keep the
+// whole-table wait above exactly as it was -- any change to its text moved their spills.)
+__device__ inline unsigned long long xcd_wait_some(const unsigned* f0, int first, int stride, int n, unsigned tag, long long timeout, const unsigned* err) {
+    const int prod = first + (int)(threadIdx.x & 63) * stride;
+    const unsigned* p = prod < n ? f0 + prod * kXcdFlagStride : nullptr;
+    long long t0 = 0;
+    for (unsigned it = 0;; ++it) {
+        const unsigned f = p ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : tag;
+        if (__all((int)(f - tag) >= 0)) return 0ull;
+        if ((it & 255u) == 255u) {
+            const long long now = wall_clock64();
+            if (t0 == 0) t0 = now;
+            else if (now - t0 > timeout || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return __ballot((int)(f - tag) < 0);
+        }
+    }
+}
+// bit p of a time-out record's mask is PRODUCER p (entry p of the flag table), whichever lane of whichever wave polled its flag
+__device__ inline unsigned long long xcd_missing(unsigned long long lanes, int first, int stride) {
+    unsigned long long missing = 0ull;
+    for (; lanes; lanes &= lanes - 1ull) missing |= 1ull << (first + __builtin_ctzll(lanes) * stride);
+    return missing;
+}
 
 // The closing round as ONE decision every worker reads the same way (round 4; before, every worker waited for all flagD under its own
 // clock, and a worker that arrived just after another had given up saw all flags set and wrote its slice: a torn parameter vector
@@ -382,6 +408,13 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
     static_assert(sizeof(T) == 4 || (!DP && !GA && BT <= kXcdMaxB64), "f64: single-GPU forms on the packed image");
     constexpr bool SB = xcd_single_buffer<T, BT>();                 // one batch buffer, delta_1 staged in DH parts (f64 at 256 samples)
     constexpr int DH = SB ? 2 : 1, BH = BT / DH;
+    // The delta hand-off's waits per wave, and the prefetched batch moved into LDS behind the forward's stores (both below): the f32
+    // forms for 64 samples and more.  The f64 forms and the phase-clocked diagnostic form have no register to spare (256 VGPRs, most
+    // of them with scratch already) and keep the per-workgroup wait and the copy in front of the forward, as they were.  So do the
+    // forms for 32 samples: four sample groups, so waves 4..7 of a feature worker stage nothing and name no flag, the copy is one quadruple
+    // on half the threads -- nothing to gain, and the epoch loop at B = 32 measured 0.03 us slower with both.
+    constexpr bool kWaveWaits = sizeof(T) == 4 && !PH && BT >= 64;
+    constexpr bool kLateCopy = sizeof(T) == 4 && !PH && !SB && BT >= 64;
     static_assert(!PH || DP, "the phase clocks exist for the data-parallel form");
     constexpr int ES = (int)sizeof(T), VS = 4 * ES;                  // bytes of an element / of a quadruple in the L2 buffers
     constexpr int RI = sizeof(T) == 4 ? 1 : 4;                       // Mfma16<T>::row(lane, i) = row(lane, 0) + RI * i
@@ -556,7 +589,10 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
     __syncthreads();
 
     // partial z_1 of batch `jn` (LDS buffer jn & 1) from the slice pair in LDS -> this worker's part of the slab
-    auto forward = [&](int jn) {
+    // `behind_stores`: what the caller has for every wave between its slab stores and their drain (the stores take ~0.4 us to be
+    // acknowledged; LDS traffic issued here runs under that)
+    auto nothing = [] {};
+    auto forward = [&](int jn, auto&& behind_stores) {
         const T* xb = xbuf + (SB ? (size_t)0 : (size_t)(jn & 1) * kXs);
         constexpr int NTILE = BT / 16, UT = NTILE > kDenseWaves ? NTILE / kDenseWaves : 1;      // sample tiles, and how many a wave takes
         T wf[kXcdSl][4][kMtp];
@@ -586,11 +622,12 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
 #pragma unroll
             for (int t = 0; t < kMtp; ++t) store4<T>(dst + t * 16, lane, acc[t]);
         }
+        behind_stores();
         xcd_drain();                                                  // every storing wave, before the barrier in front of the flag
     };
 
     if (is_a) {
-        forward(0);
+        forward(0, nothing);
         __syncthreads();
         if (tid == 0) xcd_flag(bufs.flagA + w * kXcdFlagStride, tag0);
     } else if (is_t) {
@@ -832,19 +869,59 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
         }
 
         // =============================================================== second half of step j: needs every sample group's outputs
-        if (is_a || is_t) {
-            if (wave == 1) {
-                const unsigned long long mB = xcd_wait(bufs.flagB, NS, nullptr, 0, tag, timeout, bufs.errd);
-                if (mB != 0ull && lane == 0) {
+        bool waited = true;                                                // (kWaveWaits: this wave's own wait returned with every flag it named)
+        if constexpr (kWaveWaits) {
+            // Every wave waits for itself, for the sample groups whose rows it reads, and issues its loads as soon as ITS wait returns:
+            // no workgroup barrier between the flags and the loads.  A wait that expired sets s_abort in front of the next workgroup
+            // barrier (behind the staging / behind the tail tile's partials), and every wave leaves behind that one.
+            // The barrier that stood here also kept waves 1..7 out of LDS while wave 0 is still in the sample group's tail: what they
+            // write before the next barrier (d1s, the tail tiles' `red`) does not overlap wave 0's scratch (zred, a1s, d2s, frag, a2s,
+            // d3s) -- `red` is laid over the batch buffers in the f64 forms only, which keep the barrier.
+            // Failure path only: the waves of a worker give up on clocks of their own.  If another wave of the first tail tile gives up
+            // and the flag arrives before wave 0's last look, wave 0 still publishes this step's cost (and, data-parallel, exchanges
+            // it) although the step is abandoned at the tile's barrier; the launch fails as a whole and commits nothing either way.
+            if (is_a || is_t) {
+                int g0 = wave, gs = kXcdThreads / 64, gn = NS;
+                // feature worker: the staging below -- thread tid's r-th quadruple is sample 64 r + tid / 8, so wave k touches the
+                // rows of the groups k, k + 8, k + 16, ... only.  Tail tile: wave k contracts the samples of its own K-range
+                // kc .. kc + BT / 8, and wave 0 of the first tile also sums every group's share of the cost.
+                if (is_t) {
+                    const int kc = wave * (BT >> 3);
+                    g0 = kc >> 3; gs = 1; gn = ((kc + (BT >> 3) - 1) >> 3) + 1;
+                    if (e == 0 && wave == 0 && (loss_dev || DP)) { g0 = 0; gn = NS; }
+                }
+                const unsigned long long mB = xcd_wait_some(bufs.flagB, g0, gs, gn, tag, timeout, bufs.errd);
+                waited = mB == 0ull;
+                if (!waited && lane == 0) {
                     s_abort = 1;
-                    xcd_raise(err, bufs.errd, 1u, kXcdSiteDeltaFlag, w, j, launch_id, mB, tag, dp_rank, dp_world, xsel, NW);
+                    xcd_raise(err, bufs.errd, 1u, kXcdSiteDeltaFlag, w, j, launch_id, xcd_missing(mB, g0, gs), tag, dp_rank, dp_world, xsel, NW);
+                }
+                if (wave == 1) XSTAMP(6);
+            } else {
+                // The barrier that stood here for everybody also ordered wave 0's LDS scratch against the next step's.  A feature worker
+                // or tail tile passes two or three workgroup barriers below, which do that.  A worker that is a sample group and nothing
+                // else has no other barrier in its step than the two of its first half, so it keeps this one (off every critical path:
+                // the worker is idle until the next slab): without it wave 6 of step j + 1 could overwrite frag (the targets), and the
+                // waves their parts of zred, while wave 0 of step j has not read them yet.  (a1s, d2s, a2s, d3s: wave 0 alone.  Between
+                // WORKERS the flags order everything: nobody sees tag j + 1 before this group's wave 0 has stored flagB of step j.)
+                __syncthreads();
+                if (s_abort) return;
+            }
+        } else {
+            if (is_a || is_t) {
+                if (wave == 1) {
+                    const unsigned long long mB = xcd_wait(bufs.flagB, NS, nullptr, 0, tag, timeout, bufs.errd);
+                    if (mB != 0ull && lane == 0) {
+                        s_abort = 1;
+                        xcd_raise(err, bufs.errd, 1u, kXcdSiteDeltaFlag, w, j, launch_id, mB, tag, dp_rank, dp_world, xsel, NW);
+                    }
                 }
             }
+            if (wave == 1) XSTAMP(6);
+            __syncthreads();                                               // (also orders wave 0's LDS scratch against the next step's)
+            if (s_abort) return;
+            if (wave == 1) XSTAMP(7);
         }
-        if (wave == 1) XSTAMP(6);
-        __syncthreads();                                                   // (also orders wave 0's LDS scratch against the next step's)
-        if (s_abort) return;
-        if (wave == 1) XSTAMP(7);
 
         if (is_a) {
             // ---- U: dW_0[:, slice pair] = sum_s delta_1[s] (x) x_s[slice pair]; W_0 <- W_0 - (eta/B) dW_0            rcn.rs:310, 214
@@ -866,13 +943,17 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                     if (BH * 8 >= kXcdThreads || idx < BH * 8) *reinterpret_cast<vec4*>(d1s + (idx >> 3) * kXcdD1Ld + (idx & 7) * 4) = dv[r];
                 }
             }
+            // (d1s was last read by the gradient of step j - 1, behind the barriers that follow the update and the forward)
+            if (kWaveWaits && wave == 1 && dh == 0) XSTAMP(7);
             __syncthreads();
+            if (kWaveWaits && dh == 0 && s_abort) return;                  // (a wave's own wait expired: everybody leaves here)
             if (wave == 1 && dh == 0) XSTAMP(8);
             if constexpr (SB) { if (dh == 0 && pre) prefetch(j + 1); }
             // Four 16 x 16 tiles, 64 k-steps each: 256 MFMAs = 2048 cycles of the CU's four matrix pipes whichever way they are cut.
             // Waves 0..3 (one per SIMD) each run ONE tile over the WHOLE batch -- no K-split, so no cross-wave reduction, no partials
             // in LDS, no second barrier -- on two interleaved accumulators (a single chain would be paced by the 40-cycle dependent
-            // latency instead of the 32-cycle issue rate).  Waves 4..7 have no arithmetic here; they move the prefetched batch into LDS.
+            // latency instead of the 32-cycle issue rate).  Waves 4..7 have no arithmetic here.  (Staging delta_1 in chunks on them,
+            // under these MFMAs, measured 0.19 us SLOWER: DESIGN.md 4.2a.)
             if (kh == 0) {
                 const T* xb = xbuf + (SB ? (size_t)0 : (size_t)(j & 1) * kXs) + (size_t)usl * BT * 16 + (size_t)dh * BH * 16;
                 constexpr int NQB = BH / 32;                               // blocks of eight k-steps (four samples each)
@@ -941,15 +1022,32 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
             if (wave == 1) XSTAMP(10);
             // the LDS buffer of batch j is free now (every wave is past its reads): the batch after next moves in; its first reader is
             // the forward of the NEXT iteration, several barriers away
-            if (pre) {
-                vec4* dst = reinterpret_cast<vec4*>(xbuf + (SB ? (size_t)0 : (size_t)(j & 1) * kXs));
+            // (kLateCopy: not on the step's path.  Buffer j & 1 was last read by the gradient of step j, behind the barrier above; the
+            // forward below reads the OTHER buffer; the copy's first reader is the forward of the next iteration, behind the barrier in
+            // front of flagA.  So the copy goes behind the forward's slab stores, under the time they take to be acknowledged -- `pre`
+            // implies `more`, the forward below runs whenever there is something to copy.)
+            if constexpr (!kLateCopy) {
+                if (pre) {
+                    vec4* dst = reinterpret_cast<vec4*>(xbuf + (SB ? (size_t)0 : (size_t)(j & 1) * kXs));
 #pragma unroll
-                for (int r = 0; r < XR; ++r)
-                    if (kXcdSl * BT * 4 >= kXcdThreads || tid + r * kXcdThreads < kXcdSl * BT * 4) dst[tid + r * kXcdThreads] = xr[r];
+                    for (int r = 0; r < XR; ++r)
+                        if (kXcdSl * BT * 4 >= kXcdThreads || tid + r * kXcdThreads < kXcdSl * BT * 4) dst[tid + r * kXcdThreads] = xr[r];
+                }
             }
             if constexpr (SB) __syncthreads();                             // (one buffer: the forward below is its first reader)
             if (more) {
-                forward(j + 1);
+                if constexpr (kLateCopy) {
+                    forward(j + 1, [&]() {
+                        if (pre) {
+                            vec4* dst = reinterpret_cast<vec4*>(xbuf + (size_t)(j & 1) * kXs);
+#pragma unroll
+                            for (int r = 0; r < XR; ++r)
+                                if (kXcdSl * BT * 4 >= kXcdThreads || tid + r * kXcdThreads < kXcdSl * BT * 4) dst[tid + r * kXcdThreads] = xr[r];
+                        }
+                    });
+                } else {
+                    forward(j + 1, nothing);
+                }
                 if (wave == 1) XSTAMP(11);
                 if (wave == 0) XSTAMP(13);
                 if (wave == 4) XSTAMP(14);
@@ -960,7 +1058,7 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
             }
         } else if (is_t) {
             // ---- tail tile e: e == 0 the bias column of W_0 (db_0 = sum_s delta_1); e >= 1 a 16-column tile of [W_1 | b_1]
-            if (e == 0 && wave == 0 && (loss_dev || DP)) {
+            if (e == 0 && wave == 0 && (loss_dev || DP) && waited) {        // (not after an expired wait: nothing is published or exchanged)
                 // the batch's cost: the sample groups' NS (<= 32) shares, one per lane, summed by a fixed butterfly (every lane ends
                 // with the same bits); lane 0 publishes.  One load latency, not NS of them, between flagB and this tile's gradient
                 T t = lane < NS ? xcd_ld1<T>(r_loss, lane * ES) : (T)0;
@@ -1013,6 +1111,7 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
             }
             store_partials<T>(red, wave, lane, acc);
             __syncthreads();
+            if (kWaveWaits && s_abort) return;                             // (a wave's own wait expired: nothing of this step is applied or exchanged)
             {
                 const int o = tid & 255, tcl = o >> 4, tml = o & 15, tm = mt * 16 + tml, cc = n0 + tcl;
                 if (tvalid) {

@@ -39,14 +39,18 @@ lib.rcn_hip_debug_read_stamps(d.ctx, st.ctypes.data_as(C.c_void_p))
 r = st[0].astype(np.int64)[:32, :16]
 t0 = r[r > 0].min()
 rel = np.where(r > 0, (r - t0) / 100.0, np.nan)
-names = ["0 step top", "1 slab+tail flags seen", "2 slab part sums in LDS (wave 7)", "3 past barrier (wave 0)", "4 tail done", "5 flagB stored", "6 all flagB seen (wave 1)",
-         "7 past barrier", "8 gradient MFMA done", "9 partials summed barrier", "10 slice updated barrier", "11 forward stored+drained", "12 flagA / flagT stored", "13 forward done wave 0", "14 forward done wave 4", "15 forward done wave 7"]
+# (6, 7: the f32 forms wait per wave -- wave 1 for the groups 1, 9, 17, 25 whose rows it stages, no barrier in front of the loads;
+# the f64 forms wait for all flagB on wave 1 and pass a barrier: there 7 is "past that barrier")
+names = ["0 step top", "1 slab+tail flags seen", "2 slab part sums in LDS (wave 7)", "3 past barrier (wave 0)", "4 tail done", "5 flagB stored", "6 flagB seen (wave 1: its own groups)",
+         "7 wave 1's delta_1 rows in LDS", "8 past staging barrier", "9 gradient MFMAs done, slice updated", "10 past barrier behind the update", "11 forward stored, batch moved in, drained",
+         "12 flagA / flagT stored", "13 forward done wave 0", "14 forward done wave 4", "15 forward done wave 7"]
 np.set_printoptions(linewidth=200, precision=2, suppress=True)
 for i, nme in enumerate(names):
     col = rel[:, i]
     print(f"{nme:38s} feature workers 0-24: mean {np.nanmean(col[:25]):5.2f} min {np.nanmin(col[:25]):5.2f} max {np.nanmax(col[:25]):5.2f} | tail 25-27: {np.round(col[25:28], 2)} | sample-only 28-31: {np.round(col[28:32], 2)}")
 
 c = st[1].astype(np.int64)[:32, :4]
-ghz = (c[:, 2] - c[:, 0]) / ((c[:, 3] - c[:, 1]) * 10.0)      # shader cycles per ns
+with np.errstate(invalid="ignore", divide="ignore"):           # (workers without clocks at this batch size: nan)
+    ghz = (c[:, 2] - c[:, 0]) / ((c[:, 3] - c[:, 1]) * 10.0)  # shader cycles per ns
 print("in-kernel shader clock over steps 8..56 (GHz), per worker:", np.round(ghz, 3))
 print("us per step over that stretch:", np.round((c[:, 3] - c[:, 1]) / 100.0 / 48, 3)[:4])
