@@ -27,6 +27,47 @@ BF16_MFMA_PEAK_TFLOPS = 2516.8    # same guide: dense bf16 MFMA = 16x the fp32 M
 HBM_PEAK_GBS = 8000.0
 
 
+def resident_set_figures(net, args, in_shape, B, lr):
+    """--dataset N: whole epochs of train_epoch over a resident synthetic set (a fresh device permutation per epoch, its range check and
+    the gather included), then evaluate over the set.  Whole-call rates from a host clock around work that ends in a synchronise."""
+    import torch
+    N = args.dataset
+    nb = N // B
+    if nb < 1:
+        sys.exit(f"--dataset {N}: smaller than one batch of {B}")
+    gen = torch.Generator(device=net.device).manual_seed(1)
+    with torch.cuda.stream(net.stream):
+        if args.config == "synth224":
+            X = torch.randn((N,) + tuple(in_shape), generator=gen, device=net.device, dtype=torch.float32)
+        else:
+            X = torch.randint(0, 256, (N,) + tuple(in_shape), generator=gen, device=net.device, dtype=torch.uint8)
+        Y = torch.randint(0, 10, (N,), generator=gen, device=net.device, dtype=torch.int32)
+        losses = torch.zeros(nb, dtype=torch.float32, device=net.device)
+
+        def epoch():
+            perm = torch.randperm(N, generator=gen, device=net.device).int()
+            net.train_epoch(X, Y, perm, B, lr, losses=losses)
+
+        epoch()                                            # the first step of the first epoch instantiates the (B, lr) graph
+        net.synchronize()
+        epochs = max(1, -(-args.steps // nb))
+        t0 = time.perf_counter()
+        for _ in range(epochs):
+            epoch()
+        net.synchronize()
+        el = time.perf_counter() - t0
+        net.evaluate(X, Y)
+        reps = max(1, -(-args.steps * B // (4 * N)))       # about a quarter of the timed steps' images
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            loss_sum, correct, _ = net.evaluate_async(X, Y, want_pred=False)
+        net.synchronize()
+        ev = time.perf_counter() - t0
+    return {"dataset": N, "dataset_dtype": str(X.dtype).replace("torch.", ""), "epochs_timed": epochs, "epoch_ms_per_step": round(el / (epochs * nb) * 1e3, 4),
+            "epoch_images_per_s": round(epochs * nb * B / el, 1), "eval_images_per_s": round(reps * N / ev, 1),
+            "eval_mean_loss": round(float(loss_sum.item()) / N, 4), "eval_correct": int(correct.item()), "graphs_instantiated": net.graphs_instantiated()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", choices=list(CONFIGS), default="cifar")
@@ -45,6 +86,10 @@ def main():
     ap.add_argument("--momentum", type=float, default=0.0, help="SGD momentum (rcn_hipx_set_sgd; 0: plain SGD)")
     ap.add_argument("--weight-decay", type=float, default=0.0, help="SGD weight decay, on every parameter")
     ap.add_argument("--nesterov", action="store_true", help="Nesterov momentum (needs --momentum > 0)")
+    ap.add_argument("--dataset", type=int, default=0, metavar="N",
+                    help="also keep a synthetic set of N images resident (uint8 for mnist / cifar, fp32 for synth224), time train_epoch over whole epochs with a fresh "
+                         "device permutation each, then evaluate over the set: the line gains epoch_ms_per_step, epoch_images_per_s, eval_images_per_s, graphs_instantiated "
+                         "(single GPU only)")
     args = ap.parse_args()
     from mercer_research_amd.launch import spawn_ranks, under_launcher
     if args.gpus > 1 and not under_launcher():
@@ -58,6 +103,8 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     real_stdout = None
     dp = world > 1 or args.force_dp
+    if dp and args.dataset:
+        sys.exit("--dataset times the single-GPU epoch; a data-parallel epoch does not exist")
     if dp:
         sys.stdout.flush()
         real_stdout = os.dup(1)                # RCCL's version banner goes to stdout: keep rank 0's stdout to the one JSON line
@@ -171,6 +218,7 @@ def main():
         el = float(t.item())
     flops = net.step_flops(B)
     tf = flops * args.steps / el / 1e12                    # per GPU
+    extra = resident_set_figures(net, args, in_shape, B, lr) if args.dataset else {}
     if rank == 0:
         # the peak a fraction is quoted against is the peak of the MFMA the GEMMs actually issue: fp32 MFMA (157.3 TF) in fp32
         # mode, dense bf16 MFMA (~2.5 PF) in bf16 mode -- and for the bf16 path, which is HBM-bound, the step's HBM floor
@@ -188,7 +236,8 @@ def main():
                           "dtype": "f32" if not bf16 else "bf16 MFMA operands (fwd, dgrad, wgrad), f32 accumulate/update" + (", conv-stage activations and gradients stored as bf16" if args.precision == "bf16_stored" else ""), "data": "synthetic", "final_loss": round(loss.item(), 4),
                           "data_parallel_step": dp_mode,
                           "data_parallel_allreduce": (None if not dp else "one all-reduce of the flat gradient after the backward pass" if args.dp_buckets <= 0 else
-                                                      f"{n_buckets[0]} buckets of >= {args.dp_buckets} bytes, each all-reduced on a second stream under the backward pass of the layers below")}) + "\n"
+                                                      f"{n_buckets[0]} buckets of >= {args.dp_buckets} bytes, each all-reduced on a second stream under the backward pass of the layers below"),
+                          **extra}) + "\n"
         if real_stdout is not None:
             os.write(real_stdout, out_line.encode())
         else:

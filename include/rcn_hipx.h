@@ -93,6 +93,60 @@ int  rcn_hipx_forward_dev(rcn_hipx_net* net, const float* x_dev, int B, float* l
 /* one SGD step on mean cross-entropy: forward, backward, W <- W - lr * dW (or the update rcn_hipx_set_sgd chose, in the same launch).
  * loss_dev (nullable): mean loss before the step.  Replayed as one hipGraph per (pointers, B, lr). */
 int  rcn_hipx_train_step_dev(rcn_hipx_net* net, const float* x_dev, const int32_t* labels_dev, int B, float lr, float* loss_dev);
+/* ---- the loop around the step: an epoch over a device-resident set, and evaluation ----
+ * How the rows of a resident set are stored: */
+enum { RCN_HIPX_X_F32 = 0,    /* [n][H][W][C] fp32, as rcn_hipx_train_step_dev takes a batch                                       */
+       RCN_HIPX_X_U8  = 1 };  /* [n][H][W][C] uint8; x = fl(fl(u8 * x_scale) + x_shift): two fp32 roundings, no fused multiply-add
+                                 (as the SGD update is written); x_scale / x_shift are ignored for RCN_HIPX_X_F32                  */
+/* n_batches steps of rcn_hipx_train_step_dev over batches first_batch .. first_batch + n_batches - 1 of a resident set of n rows:
+ * batch s is rows perm_dev[s*B .. s*B + B - 1] (perm_dev == NULL: rows s*B .. s*B + B - 1) and their labels, gathered into a batch
+ * buffer the NET owns (k_gather_rows), then the ordinary step on that buffer -- the same kernels, reduction and optimiser
+ * (rcn_hipx_set_sgd) in all three precisions, so an epoch is bit-identical to the same batches fed to rcn_hipx_train_step_dev one by one.
+ * (first_batch + n_batches) * B <= n: a remainder of fewer than B rows is not trained on.  loss_dev (nullable): [n_batches] floats,
+ * loss_dev[s - first_batch] = mean loss of step s before its update.  Nothing blocks; everything is enqueued on the net's stream.
+ * ONE graph: the step always sees the net's own batch, labels and loss buffers, so every step of every call with the same (B, lr)
+ * replays one instantiated hipGraph (a single chain of launches), whatever X_dev, perm_dev, first_batch and loss_dev are; the gather
+ * and the 4-byte copy of the loss into its slot are launched eagerly around it.  rcn_hipx_train_step_dev on the caller's own pointers
+ * keeps its own graph cache and key.  At most eight (B, lr) pairs are kept.
+ * No wild reads: every perm_dev entry is clamped into [0, n) before it forms an address.  An entry outside that range is a caller error
+ * (the clamped row is trained on), but it cannot fault.  labels are int32 class indices as for rcn_hipx_train_step_dev.
+ * -1 (nothing enqueued): B outside 1 .. max_batch, n < 1, X_dev or labels_dev NULL, an unknown x_kind, first_batch or n_batches
+ * negative, (first_batch + n_batches) * B > n. */
+int  rcn_hipx_train_epoch_dev(rcn_hipx_net* net, const void* X_dev, int x_kind, float x_scale, float x_shift, const int32_t* labels_dev, int64_t n,
+                              const int32_t* perm_dev, int B, int64_t first_batch, int64_t n_batches, float lr, float* loss_dev);
+/* Forward pass + loss + arg-max over ALL n rows (any n >= 1: chunks of at most max_batch rows, a short last chunk included); no backward
+ * pass, parameters untouched.  Enqueued on the net's stream, nothing blocks; results on the device:
+ *     *loss_sum_dev (double) = sum over samples of -log softmax(logits)[label]
+ *     *correct_dev  (int64)  = number of samples whose arg-max equals the label
+ *     pred_dev (nullable)    = [n] int32 arg-max class
+ * labels_dev may be NULL (prediction only): then loss_sum_dev and correct_dev may be NULL too (given, they are zeroed) and pred_dev must
+ * not be; with labels, loss_sum_dev and correct_dev must not be NULL.  The two accumulators are zeroed once per call, before the first chunk.
+ * The logits are those rcn_hipx_forward_dev returns (the same forward launches).  RCN_HIPX_X_U8 chunks are widened into the net's batch
+ * buffer first; RCN_HIPX_X_F32 is read in place.
+ * Arg-max tie rule: the FIRST maximum (what numpy.argmax / torch.argmax return, and oracle/convnet_oracle.py's pooling rule).  This
+ * differs ON PURPOSE from the main track's k_argmax_last, which follows the reference's max_by (rcn.rs:92-97): Track X has no reference
+ * to follow.
+ * A label outside [0, classes) never indexes a logits row: that sample counts as incorrect and adds nothing to the loss sum (a caller
+ * error, but not a fault).
+ * Deterministic: correct and pred are exact integers, independent of chunking.  The loss is summed in a fixed order -- per workgroup
+ * (8 samples) in sample order in fp32, the chunk's last-arriving workgroup adds the partials in a fixed block order in double and adds
+ * the chunk's total to *loss_sum_dev -- so two calls on the same data return the same bits.
+ * State: between two training steps it changes nothing the next step reads (a step recomputes its forward pass).  Between
+ * rcn_hipx_gradients_begin_dev and the last rcn_hipx_gradients_bucket_dev it would overwrite activations the backward walk still needs:
+ * it returns -6 there and does nothing (any entry point that runs a step or a gradient pass ends such a walk).  It launches eagerly and
+ * captures nothing; like every launch path it drops the captured graphs only if a scratch buffer they point into has to grow (a first
+ * evaluation at a larger batch than any step so far), and they are re-captured on demand.
+ * -1 (nothing enqueued): n < 1, X_dev NULL, an unknown x_kind, a NULL that the rules above do not allow. */
+int  rcn_hipx_evaluate_dev(rcn_hipx_net* net, const void* X_dev, int x_kind, float x_scale, float x_shift, const int32_t* labels_dev, int64_t n,
+                           double* loss_sum_dev, int64_t* correct_dev, int32_t* pred_dev);
+/* how many hipGraphs this net has instantiated since it was created (monotonic; tests and the bench read it to see that an epoch does
+ * not re-capture) */
+int  rcn_hipx_graphs_instantiated(const rcn_hipx_net* net, int64_t* count);
+/* rcn_hipx_plan's dry walk for ONE evaluation chunk of `batch` rows: the forward launches and the evaluation kernel, one line per launch;
+ * no GPU needed.  Status and texts for a net that cannot be built are rcn_hipx_plan's.  _net: the same for an existing net, with its own
+ * precision, tiling and options (batch <= max_batch). */
+int  rcn_hipx_plan_eval(int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, int n_layers, int batch, int precision, int tiling, char* out, int cap);
+int  rcn_hipx_plan_eval_net(const rcn_hipx_net* net, int batch, char* out, int cap);
 /* data-parallel halves: gradients of the MEAN loss over this shard into the padded flat layout (rcn_hipx_param_count's
  * `padded`), and p <- p - scale * g from such a buffer. */
 int  rcn_hipx_gradients_dev(rcn_hipx_net* net, const float* x_dev, const int32_t* labels_dev, int B, float* grad_dev, float* loss_dev);

@@ -52,6 +52,11 @@ SIGNATURES = {
     "rcn_hipx_set_velocity": (_i, [_vp, C.POINTER(C.c_float)]),
     "rcn_hipx_reset_velocity": (_i, [_vp]),
     "rcn_hipx_apply_sgd_dev": (_i, [_vp, _vp, C.c_float, C.c_float]),
+    "rcn_hipx_train_epoch_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _vp, _i, C.c_int64, C.c_int64, C.c_float, _vp]),
+    "rcn_hipx_evaluate_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _vp, _vp, _vp]),
+    "rcn_hipx_graphs_instantiated": (_i, [_vp, C.POINTER(C.c_int64)]),
+    "rcn_hipx_plan_eval": (_i, [_i, _i, _i, C.POINTER(XLayer), _i, _i, _i, _i, C.c_char_p, _i]),
+    "rcn_hipx_plan_eval_net": (_i, [_vp, _i, C.c_char_p, _i]),
 }
 _libx = None
 
@@ -99,6 +104,23 @@ def plan(in_shape: Tuple[int, int, int], layers: Sequence[tuple], batch: int, pr
     if st != 0:
         raise ConvNetError(f"rcn_hipx_plan: {st}: {buf.value.decode()}")
     return buf.value.decode()
+
+
+def plan_eval(in_shape: Tuple[int, int, int], layers: Sequence[tuple], batch: int, precision: str = "fp32", tiling: str = "auto") -> str:
+    """Which kernels ONE evaluation chunk of `batch` rows would launch (rcn_hipx_plan_eval): the forward launches of `plan` and the
+    evaluation kernel, one line per launch.  Needs no GPU."""
+    lib = load()
+    arr = (XLayer * len(layers))()
+    for i, l in enumerate(layers):
+        arr[i].kind, arr[i].out = KIND[l[0]], int(l[1]) if len(l) > 1 else 0
+    buf = C.create_string_buffer(1 << 16)
+    st = lib.rcn_hipx_plan_eval(in_shape[0], in_shape[1], in_shape[2], arr, len(layers), batch, PRECISIONS[precision], {"gemm": 0, "auto": 1, "lds": 2}[tiling], buf, len(buf))
+    if st != 0:
+        raise ConvNetError(f"rcn_hipx_plan_eval: {st}: {buf.value.decode()}")
+    return buf.value.decode()
+
+
+X_KIND = {"float32": 0, "uint8": 1}      # RCN_HIPX_X_F32 / RCN_HIPX_X_U8, by the set's torch dtype
 
 
 class ConvNet:
@@ -205,6 +227,92 @@ class ConvNet:
     def train_step(self, x, labels, lr: float, loss=None):
         self._ck(self.lib.rcn_hipx_train_step_dev(self.net, C.c_void_p(x.data_ptr()), C.c_void_p(labels.data_ptr()), x.shape[0], lr,
                                                   C.c_void_p(loss.data_ptr()) if loss is not None else None))
+
+    def _resident_set(self, X, labels):
+        """(x_kind, rows) of a device-resident set after checking its dtype, shape, device and contiguity (labels: int32, one per row)."""
+        t = self.torch
+        kind = X_KIND.get(str(X.dtype).replace("torch.", ""))
+        if kind is None:
+            raise ValueError(f"a resident set is torch.float32 or torch.uint8, not {X.dtype}")
+        if tuple(X.shape[1:]) != self.in_shape or X.shape[0] < 1:
+            raise ValueError(f"a resident set is [n, {self.in_shape[0]}, {self.in_shape[1]}, {self.in_shape[2]}] with n >= 1, not {tuple(X.shape)}")
+        if X.device != self.device or not X.is_contiguous():
+            raise ValueError("a resident set is a contiguous tensor on the net's device")
+        if labels is not None:
+            if labels.dtype != t.int32 or tuple(labels.shape) != (X.shape[0],) or labels.device != self.device or not labels.is_contiguous():
+                raise ValueError("labels: a contiguous int32 tensor on the net's device, one per row of the set")
+        return kind, int(X.shape[0])
+
+    def train_epoch(self, X, labels, perm, B: int, lr: float, n_batches: Optional[int] = None, first_batch: int = 0, losses=None,
+                    x_scale: float = 1.0 / 255.0, x_shift: float = 0.0):
+        """n_batches training steps over a device-resident set (rcn_hipx_train_epoch_dev): batch s is rows perm[s*B : (s+1)*B] (perm None:
+        rows in order), gathered on the device into the net's own batch buffer, then the step of train_step -- bit-identical to it, and ONE
+        captured graph per (B, lr) whatever X, perm, first_batch and losses are.  X: torch.float32 or torch.uint8 [n, H, W, C] (uint8 rows
+        become fl(fl(u8 * x_scale) + x_shift); both are ignored for float32); perm: int32 device tensor with entries in [0, n) (checked here,
+        once per call: one device reduction, which synchronises) or None; n_batches defaults to n // B - first_batch; losses (optional):
+        float32 device tensor of at least n_batches elements, losses[i] = mean loss of the call's i-th step before its update."""
+        t = self.torch
+        kind, n = self._resident_set(X, labels)
+        if labels is None:
+            raise ValueError("train_epoch needs labels")
+        B, first_batch = int(B), int(first_batch)
+        n_batches = (n // B - first_batch if B >= 1 else 0) if n_batches is None else int(n_batches)
+        if perm is not None:
+            if perm.dtype != t.int32 or perm.dim() != 1 or perm.device != self.device or not perm.is_contiguous():
+                raise ValueError("perm: a contiguous one-dimensional int32 tensor on the net's device")
+            if perm.numel() < (first_batch + n_batches) * B <= n:        # (batches beyond the set itself: the library's refusal below)
+                raise ValueError(f"perm has {perm.numel()} entries; batches {first_batch} .. {first_batch + n_batches - 1} of {B} rows need {(first_batch + n_batches) * B}")
+            if perm.numel():
+                lo, hi = t.aminmax(perm)
+                if int(lo) < 0 or int(hi) >= n:
+                    raise ValueError(f"perm entries must lie in [0, {n}); found {int(lo)} .. {int(hi)}")
+        if losses is not None:
+            if losses.dtype != t.float32 or losses.device != self.device or not losses.is_contiguous() or losses.numel() < n_batches:
+                raise ValueError("losses: a contiguous float32 tensor on the net's device with at least n_batches elements")
+        self._ck(self.lib.rcn_hipx_train_epoch_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift), C.c_void_p(labels.data_ptr()), n,
+                                                   C.c_void_p(perm.data_ptr()) if perm is not None else None, B, first_batch, n_batches, float(lr),
+                                                   C.c_void_p(losses.data_ptr()) if losses is not None else None))
+
+    def evaluate_async(self, X, labels=None, x_scale: float = 1.0 / 255.0, x_shift: float = 0.0, want_pred: bool = True):
+        """Forward pass, loss and arg-max over ALL rows of a resident set (rcn_hipx_evaluate_dev), enqueued on the net's stream: returns the
+        device tensors (loss_sum: float64[1], correct: int64[1], pred: int32[n] or None), valid once the net's stream has got there
+        (`synchronize`).  labels None: prediction only (loss_sum and correct stay zero)."""
+        t = self.torch
+        kind, n = self._resident_set(X, labels)
+        with t.cuda.stream(self.stream):
+            loss_sum = t.zeros(1, dtype=t.float64, device=self.device)
+            correct = t.zeros(1, dtype=t.int64, device=self.device)
+            pred = t.empty(n, dtype=t.int32, device=self.device) if (want_pred or labels is None) else None
+        self._ck(self.lib.rcn_hipx_evaluate_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift),
+                                                C.c_void_p(labels.data_ptr()) if labels is not None else None, n,
+                                                C.c_void_p(loss_sum.data_ptr()), C.c_void_p(correct.data_ptr()), C.c_void_p(pred.data_ptr()) if pred is not None else None))
+        return loss_sum, correct, pred
+
+    def evaluate(self, X, labels, x_scale: float = 1.0 / 255.0, x_shift: float = 0.0) -> Tuple[float, int]:
+        """(mean loss, number of rows whose arg-max equals the label) over all rows of a resident set; synchronises."""
+        if labels is None:
+            raise ValueError("evaluate needs labels (predict: arg-max only)")
+        loss_sum, correct, _ = self.evaluate_async(X, labels, x_scale, x_shift, want_pred=False)
+        self.synchronize()
+        return float(loss_sum.item()) / X.shape[0], int(correct.item())
+
+    def predict(self, X, x_scale: float = 1.0 / 255.0, x_shift: float = 0.0):
+        """The arg-max class of every row (the FIRST maximum, as torch.argmax): an int32 device tensor, valid on the net's stream."""
+        return self.evaluate_async(X, None, x_scale, x_shift)[2]
+
+    def graphs_instantiated(self) -> int:
+        """hipGraphs this net has instantiated since it was created (an epoch with a (B, lr) seen before adds none)."""
+        c = C.c_int64()
+        self._ck(self.lib.rcn_hipx_graphs_instantiated(self.net, C.byref(c)))
+        return int(c.value)
+
+    def plan_eval_of_this_net(self, batch: int) -> str:
+        """The launches one evaluation chunk of THIS net would make, with its own precision, tiling and options (rcn_hipx_plan_eval_net)."""
+        buf = C.create_string_buffer(1 << 16)
+        st = self.lib.rcn_hipx_plan_eval_net(self.net, int(batch), buf, len(buf))
+        if st != 0:
+            raise ConvNetError(f"rcn_hipx_plan_eval_net: {st}: {buf.value.decode()}")
+        return buf.value.decode()
 
     def gradients(self, x, labels, grad=None, loss=None):
         grad = grad if grad is not None else self.torch.empty(self.n_padded, dtype=self.torch.float32, device=self.device)

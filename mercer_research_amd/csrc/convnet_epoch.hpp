@@ -1,0 +1,177 @@
+// convnet_epoch.hpp -- Track X: the loop around the training step (rcn_hipx_train_epoch_dev, rcn_hipx_evaluate_dev).  No reference
+// counterpart; the main track's counterparts are rcn_hip_shuffle_dev / rcn_hip_evaluate*.
+//
+//   k_gather_rows<TS, VEC>  rows of a device-resident set (fp32 or uint8), selected by an int32 index row, into the net's contiguous
+//                           fp32 batch buffer, and their labels into its int32 labels buffer.  Every index is clamped into [0, n)
+//                           before it forms an address.
+//   k_eval_ce               soft-max cross-entropy, first-maximum arg-max and correct count of one chunk of logits, without d logits;
+//                           its last-arriving workgroup ADDS the chunk's totals into a double / int64 pair.
+#pragma once
+
+#include <type_traits>
+
+#include "convnet.hpp"
+
+namespace rcnx {
+
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+
+// how the values of a resident set become the fp32 values the net reads (RCN_HIPX_X_U8: two roundings, no fused multiply-add)
+struct RowScale { float scale, shift; };
+
+template <typename TS> struct RowPiece;
+// 16 bytes of an fp32 row: four values, copied
+template <> struct RowPiece<float> {
+    static constexpr int kVec = 4;
+    using type = f32x4;
+    __device__ static inline void store(float* __restrict__ dst, const f32x4& v, const RowScale&) { *reinterpret_cast<f32x4*>(dst) = v; }
+    __device__ static inline float widen1(float v, const RowScale&) { return v; }
+};
+// 16 bytes of a uint8 row: sixteen values, widened in registers, stored as four 16-byte pieces
+template <> struct RowPiece<uint8_t> {
+    static constexpr int kVec = 16;
+    using type = u32x4;
+    __device__ static inline float widen1(uint8_t v, const RowScale& rs) {
+#pragma clang fp contract(off)
+        const float m = (float)v * rs.scale;
+        return m + rs.shift;
+    }
+    __device__ static inline void store(float* __restrict__ dst, const u32x4& v, const RowScale& rs) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            f32x4 o;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) o[b] = widen1((uint8_t)((v[q] >> (8 * b)) & 0xffu), rs);
+            *reinterpret_cast<f32x4*>(dst + 4 * q) = o;
+        }
+    }
+};
+
+constexpr int kGatherSlots = 4;        // 64-lane pieces a wave has in flight: four short rows at once, or 4 KiB of a long one
+constexpr int kGatherThreads = 256;
+
+// dst[r][0 .. E) = widen(X[row(r)][0 .. E)) and labels_out[r] = labels[row(r)] for r < B, where row(r) = clamp(idx ? idx[r] : base + r, 0, n - 1).
+// One wave takes kGatherSlots consecutive slots of the flattened (destination row, 64-piece slot) space: rows shorter than a wave's 64
+// pieces (MNIST as uint8: 49 pieces of 16 bytes) travel four to a wave, long rows (CIFAR as fp32: 768 pieces) are cut into runs of
+// 4 KiB; either way every load of the wave is issued before its first store.  VEC = RowPiece<TS>::kVec: 16-byte loads and stores (the host
+// checks E % VEC == 0 and the bases' alignment); VEC = 1: element by element, for rows whose length or base does not allow them.
+template <typename TS, int VEC>
+__global__ __launch_bounds__(kGatherThreads) void k_gather_rows(const TS* __restrict__ X, const int* __restrict__ labels, long long n, const int* __restrict__ idx, long long base,
+                                                                int B, int E, RowScale rs, float* __restrict__ dst, int* __restrict__ labels_out) {
+    using Piece = typename std::conditional<VEC == 1, TS, typename RowPiece<TS>::type>::type;
+    const int lane = threadIdx.x & 63;
+    const unsigned wave = blockIdx.x * (kGatherThreads / 64) + (threadIdx.x >> 6);
+    const int P = E / VEC;                              // pieces per row
+    const unsigned S = (unsigned)(P + 63) / 64;         // slots per row
+    const unsigned total = (unsigned)B * S;             // (B * S < 2^31: gather_blocks checks it)
+    Piece v[kGatherSlots];
+    long long at[kGatherSlots];                         // destination element offset; -1: nothing to do
+#pragma unroll
+    for (int j = 0; j < kGatherSlots; ++j) {
+        const unsigned g = wave * kGatherSlots + j;
+        at[j] = -1;
+        if (g >= total) continue;
+        const int r = (int)(g / S);
+        const int piece = (int)(g % S) * 64 + lane;
+        long long row = idx ? (long long)idx[r] : base + r;
+        row = row < 0 ? 0 : (row >= n ? n - 1 : row);   // an index out of range is a caller error; it must not become an address
+        if (labels && piece == 0) labels_out[r] = labels[row];
+        if (piece >= P) continue;
+        v[j] = *reinterpret_cast<const Piece*>(X + row * E + (long long)piece * VEC);
+        at[j] = (long long)r * E + (long long)piece * VEC;
+    }
+#pragma unroll
+    for (int j = 0; j < kGatherSlots; ++j) {
+        if (at[j] < 0) continue;
+        if constexpr (VEC == 1) dst[at[j]] = RowPiece<TS>::widen1(v[j], rs);
+        else RowPiece<TS>::store(dst + at[j], v[j], rs);
+    }
+}
+
+// workgroups of k_gather_rows for a batch of B rows of E elements; 0: more slots than the kernel's 32-bit slot index counts
+inline long long gather_blocks(int B, int E, int vec) {
+    const long long S = (E / vec + 63) / 64, waves = ((long long)B * S + kGatherSlots - 1) / kGatherSlots;
+    if ((long long)B * S >= (1ll << 31) - kGatherSlots * (kGatherThreads / 64)) return 0;
+    return (waves + kGatherThreads / 64 - 1) / (kGatherThreads / 64);
+}
+
+constexpr int kEvalSamples = 8;        // samples per 256-thread workgroup of k_eval_ce (k_softmax_ce's grouping)
+inline int eval_blocks(int B) { return (B + kEvalSamples - 1) / kEvalSamples; }
+
+// Evaluation of one chunk of B logits rows (ldl floats apart): 32 lanes per sample as in k_softmax_ce, no d logits.  Per sample the
+// maximum, the FIRST class that attains it (pred, nullable), and -(z[y] - max - log(sum exp)); a label outside [0, C) never indexes the
+// row: the sample counts as incorrect and adds nothing to the loss.  loss_part[block] = the block's losses summed in sample order,
+// correct_part[block] its correct count; the workgroup that arrives LAST adds the partials in a fixed order (thread t takes blocks
+// t, t + 256, ...; thread 0 adds the 256 sums in order), in double, and ADDS the chunk's totals into *loss_sum / *correct -- chunks run
+// one after the other on the net's stream, so the accumulators need no atomics.  It leaves the counter at zero.  labels == nullptr:
+// prediction only, no partials and no counter.
+__global__ __launch_bounds__(256) void k_eval_ce(const float* __restrict__ logits, const int* __restrict__ labels, int B, int C, int ldl, float* loss_part, int* correct_part,
+                                                 unsigned* counter, double* loss_sum, long long* correct, int* __restrict__ pred) {
+    __shared__ float red[kEvalSamples];
+    __shared__ int hit[kEvalSamples];
+    __shared__ double dsum[256];
+    __shared__ long long csum[256];
+    __shared__ int last;
+    const int grp = threadIdx.x >> 5, ln = threadIdx.x & 31;
+    const int s = blockIdx.x * kEvalSamples + grp;
+    float loss = 0.f;
+    int ok = 0;
+    if (s < B) {
+        const float* z = logits + (long long)s * ldl;
+        float mx = -3.0e38f;
+        int ix = 0x7fffffff;
+        for (int c = ln; c < C; c += 32)
+            if (z[c] > mx) { mx = z[c]; ix = c; }       // strictly greater: the first maximum of this lane's classes
+#pragma unroll
+        for (int off = 16; off > 0; off >>= 1) {
+            const float o = __shfl_xor(mx, off, 32);
+            const int oi = __shfl_xor(ix, off, 32);
+            if (o > mx || (o == mx && oi < ix)) { mx = o; ix = oi; }
+        }
+        if (ix >= C) ix = 0;                            // (no class above -3e38: a row of NaN or -inf)
+        if (pred && ln == 0) pred[s] = ix;
+        if (labels) {
+            const int y = labels[s];
+            if (y >= 0 && y < C) {
+                float sum = 0.f;
+                for (int c = ln; c < C; c += 32) sum += expf(z[c] - mx);
+#pragma unroll
+                for (int off = 16; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 32);
+                loss = -(z[y] - mx - logf(sum));
+                ok = ix == y;
+            }
+        }
+    }
+    if (!labels) return;
+    if (ln == 0) { red[grp] = loss; hit[grp] = ok; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+        int h = 0;
+        for (int g = 0; g < kEvalSamples; ++g) { t += red[g]; h += hit[g]; }
+        __hip_atomic_store(&loss_part[blockIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&correct_part[blockIdx.x], h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    double t = 0.0;
+    long long h = 0;
+    for (int b = threadIdx.x; b < (int)gridDim.x; b += 256) {
+        t += (double)__hip_atomic_load(&loss_part[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        h += __hip_atomic_load(&correct_part[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    dsum[threadIdx.x] = t;
+    csum[threadIdx.x] = h;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+        long long hits = 0;
+        for (int i = 0; i < 256; ++i) { tot += dsum[i]; hits += csum[i]; }
+        *loss_sum = *loss_sum + tot;
+        *correct = *correct + hits;
+        __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+}  // namespace rcnx

@@ -19,6 +19,7 @@
 
 #include "convnet.hpp"
 #include "convnet_bf16.hpp"
+#include "convnet_epoch.hpp"
 #include "convnet_halo.hpp"
 #include "convnet_halo_bf16.hpp"
 #include "convnet_select.hpp"
@@ -85,6 +86,14 @@ struct rcn_hipx_net : Selection {
     float sgd_mu = 0.f, sgd_wd = 0.f; int sgd_nesterov = 0;
     Buf vel;
     std::map<Key, hipGraphExec_t> graphs;
+    // rcn_hipx_train_epoch_dev / rcn_hipx_evaluate_dev: the batch the gather kernel fills (max_batch rows, fp32), its labels and the step's
+    // loss scalar.  Allocated once, never moved: the epoch's step always sees these three pointers, so ONE captured graph per (B, lr)
+    // serves every batch of every epoch, whatever set, permutation and loss slots the caller passes.
+    Buf xb, yb, eloss;
+    std::map<std::pair<int, float>, hipGraphExec_t> epoch_graphs;
+    Buf eval_part;                          // k_eval_ce: [loss partials][correct partials][counter: zero between launches]
+    long long n_instantiated = 0;           // hipGraphs instantiated since the net was created (rcn_hipx_graphs_instantiated)
+    bool walk_open = false;                 // between rcn_hipx_gradients_begin_dev and its last bucket: the activations belong to that walk
     // the backward pass as a resumable walk (rcn_hipx_gradients_begin_dev / _bucket_dev: a data-parallel step whose all-reduce of one bucket
     // of layers overlaps the backward pass of the layers below it)
     struct BwState {
@@ -686,7 +695,9 @@ int step_core(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, flo
     return backward(n, x, B, lr, grad, apply, first, gated);
 }
 
-void drop_graphs(rcn_hipx_net* n) { for (auto& kv : n->graphs) (void)hipGraphExecDestroy(kv.second); n->graphs.clear(); }
+template <typename M> void drop_all(M& graphs) { for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second); graphs.clear(); }
+// every captured graph of the net: the steps on callers' pointers and the epoch's steps on the net's own batch buffer
+void drop_graphs(rcn_hipx_net* n) { drop_all(n->graphs); drop_all(n->epoch_graphs); }
 
 // ---- gradient buckets: the data-parallel step with its all-reduce overlapped with the backward pass -------------------------------------
 // The layers with parameters, walked from the last to the first (the order the backward pass finishes them), are cut into buckets of at
@@ -867,7 +878,7 @@ void rcn_hipx_destroy(rcn_hipx_net* n) {
         if (n->stream) (void)hipStreamSynchronize(n->stream);
         drop_graphs(n);
         for (Layer& l : n->L) { l.out.release(); l.idx.release(); l.dout.release(); l.slab.release(); }
-        for (Buf* b : {&n->params, &n->wt, &n->wb16, &n->dz, &n->loss_part, &n->grad_tmp, &n->dlogits, &n->skbuf, &n->wb, &n->vel}) b->release();
+        for (Buf* b : {&n->params, &n->wt, &n->wb16, &n->dz, &n->loss_part, &n->grad_tmp, &n->dlogits, &n->skbuf, &n->wb, &n->vel, &n->xb, &n->yb, &n->eloss, &n->eval_part}) b->release();
         if (n->side) { (void)hipStreamSynchronize(n->side); (void)hipStreamDestroy(n->side); }
         for (hipEvent_t e : n->events) (void)hipEventDestroy(e);
         if (n->own_stream && n->stream) (void)hipStreamDestroy(n->stream);
@@ -991,30 +1002,174 @@ int rcn_hipx_forward_dev(rcn_hipx_net* n, const float* x, int B, float* logits) 
     return 0;
 }
 
+// One eager step (it sizes every scratch buffer outside capture: hipMalloc is illegal while capturing -- and it IS the caller's step),
+// then the same step captured and instantiated for the replays that follow.
+static int step_and_capture(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float lr, float* loss_dev, hipGraphExec_t* exec_out) {
+    RTRY(step_core(n, x, labels, B, lr, nullptr, true, loss_dev));
+    hipGraph_t graph = nullptr;
+    XTRY(n, hipStreamBeginCapture(n->stream, hipStreamCaptureModeThreadLocal));
+    const int st = step_core(n, x, labels, B, lr, nullptr, true, loss_dev);
+    hipError_t e = hipStreamEndCapture(n->stream, &graph);
+    if (st != 0) { if (graph) (void)hipGraphDestroy(graph); return st; }
+    XTRY(n, e);
+    hipGraphExec_t exec = nullptr;
+    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    XTRY(n, e);
+    ++n->n_instantiated;
+    *exec_out = exec;
+    return 0;
+}
+
 int rcn_hipx_train_step_dev(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float lr, float* loss_dev) {
     if (!n || !x || !labels) return -1;
     RTRY(ensure_batch(n, B));
     Dev g(n->device);
+    n->walk_open = false;                               // (a step in between abandons an open bucket walk's activations)
     const Key key{x, labels, B, lr, loss_dev};
     auto it = n->graphs.find(key);
     if (it == n->graphs.end()) {
-        // one eager step first: sizes every scratch buffer outside capture (hipMalloc is illegal while capturing)
-        RTRY(step_core(n, x, labels, B, lr, nullptr, true, loss_dev));
-        hipGraph_t graph = nullptr;
-        XTRY(n, hipStreamBeginCapture(n->stream, hipStreamCaptureModeThreadLocal));
-        const int st = step_core(n, x, labels, B, lr, nullptr, true, loss_dev);
-        hipError_t e = hipStreamEndCapture(n->stream, &graph);
-        if (st != 0) { if (graph) (void)hipGraphDestroy(graph); return st; }
-        XTRY(n, e);
         hipGraphExec_t exec = nullptr;
-        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        XTRY(n, e);
-        if (n->graphs.size() >= 8) drop_graphs(n);
+        RTRY(step_and_capture(n, x, labels, B, lr, loss_dev, &exec));
+        if (n->graphs.size() >= 8) drop_all(n->graphs);
         n->graphs.emplace(key, exec);
-        return 0;                                       // the eager step above WAS this call's step
+        return 0;                                       // the eager step WAS this call's step
     }
     XTRY(n, hipGraphLaunch(it->second, n->stream));
+    return 0;
+}
+
+// ---- the loop around the step: an epoch over a device-resident set, and evaluation --------------------------------------------------------
+namespace {
+
+bool x_kind_ok(int k) { return k == RCN_HIPX_X_F32 || k == RCN_HIPX_X_U8; }
+long long row_elems(const rcn_hipx_net* n) { return (long long)n->in_h * n->in_w * n->in_c; }
+
+// the net's own batch, labels and loss buffers: sized for max_batch once, so they never move under a captured graph
+int ensure_epoch_bufs(rcn_hipx_net* n) {
+    XTRY(n, n->xb.ensure((size_t)n->max_batch * row_elems(n) * sizeof(float)));
+    XTRY(n, n->yb.ensure((size_t)n->max_batch * sizeof(int32_t)));
+    XTRY(n, n->eloss.ensure(sizeof(float)));
+    return 0;
+}
+
+// rows idx[0 .. B) (idx == NULL: base .. base + B - 1) of the set into the net's batch buffer, their labels (nullable) into its labels buffer
+int launch_gather(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, long long rows, const int32_t* idx, long long base, int B) {
+    const int E = (int)row_elems(n);
+    const RowScale rs{x_scale, x_shift};
+    float* const dst = (float*)n->xb.p;
+    int* const ydst = (int*)n->yb.p;
+    if (!gather_blocks(B, E, 1)) return fail(n, -3, "a batch of more than 2^37 elements");
+    // 16-byte pieces where every row starts on a 16-byte boundary and is a whole number of them; element by element otherwise
+    if (x_kind == RCN_HIPX_X_U8) {
+        const bool vec = E % RowPiece<uint8_t>::kVec == 0 && (uintptr_t)X % 16 == 0;
+        if (vec) hipLaunchKernelGGL((k_gather_rows<uint8_t, RowPiece<uint8_t>::kVec>), dim3((unsigned)gather_blocks(B, E, RowPiece<uint8_t>::kVec)), dim3(kGatherThreads), 0, n->stream,
+                                    (const uint8_t*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
+        else hipLaunchKernelGGL((k_gather_rows<uint8_t, 1>), dim3((unsigned)gather_blocks(B, E, 1)), dim3(kGatherThreads), 0, n->stream, (const uint8_t*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
+    } else {
+        const bool vec = E % RowPiece<float>::kVec == 0 && (uintptr_t)X % 16 == 0;
+        if (vec) hipLaunchKernelGGL((k_gather_rows<float, RowPiece<float>::kVec>), dim3((unsigned)gather_blocks(B, E, RowPiece<float>::kVec)), dim3(kGatherThreads), 0, n->stream,
+                                    (const float*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
+        else hipLaunchKernelGGL((k_gather_rows<float, 1>), dim3((unsigned)gather_blocks(B, E, 1)), dim3(kGatherThreads), 0, n->stream, (const float*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
+    }
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+
+// loss sum, correct count and arg-max of the B logits rows the forward pass has just left in the last layer's output
+int launch_eval(rcn_hipx_net* n, const int32_t* labels, int B, double* loss_sum, long long* correct, int32_t* pred) {
+    const int blocks = eval_blocks(B);
+    if (dry_note(n, "  eval: k_eval_ce, %d workgroups (loss sum, correct count, first-maximum arg-max; no gradient)", blocks)) return 0;
+    const Layer& l = n->L.back();
+    const size_t parts = (size_t)eval_blocks(n->max_batch);
+    if (!n->eval_part.p) {
+        XTRY(n, n->eval_part.ensure((2 * parts + 1) * sizeof(float)));
+        XTRY(n, hipMemsetAsync(n->eval_part.p, 0, n->eval_part.cap, n->stream));
+    }
+    float* const lp = (float*)n->eval_part.p;
+    hipLaunchKernelGGL(k_eval_ce, dim3(blocks), dim3(256), 0, n->stream, (const float*)l.out.p, labels, B, n->classes, l.CoutP, lp, (int*)(lp + parts), (unsigned*)(lp + 2 * parts),
+                       loss_sum, correct, pred);
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+
+// one evaluation chunk: the forward pass over all layers (rcn_hipx_forward_dev's) and the evaluation kernel
+int eval_chunk(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, double* loss_sum, long long* correct, int32_t* pred) {
+    RTRY(forward(n, x, B));
+    return launch_eval(n, labels, B, loss_sum, correct, pred);
+}
+
+int plan_eval_walk(rcn_hipx_net& net, int batch) {
+    net.plan = "forward + evaluation of one chunk of " + std::to_string(batch) + " rows (" + precision_name(net.precision, net.store16) + "), launch by launch:\n";
+    RTRY(prep_bf16_weights(&net));
+    return eval_chunk(&net, nullptr, nullptr, batch, nullptr, nullptr, nullptr);
+}
+
+}  // namespace
+
+int rcn_hipx_train_epoch_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows, const int32_t* perm,
+                             int B, int64_t first_batch, int64_t n_batches, float lr, float* loss_dev) {
+    if (!n) return -1;
+    if (!X || !labels) return fail(n, -1, "train_epoch: X_dev and labels_dev must not be NULL");
+    if (!x_kind_ok(x_kind)) return fail(n, -1, "train_epoch: x_kind must be RCN_HIPX_X_F32 or RCN_HIPX_X_U8");
+    RTRY(ensure_batch(n, B));
+    if (rows < 1 || first_batch < 0 || n_batches < 0 || first_batch > rows / B || n_batches > rows / B - first_batch)
+        return fail(n, -1, "train_epoch: (first_batch + n_batches) * B must not exceed n (a remainder of less than B rows is not trained on)");
+    if (n_batches == 0) return 0;
+    Dev g(n->device);
+    RTRY(ensure_epoch_bufs(n));
+    n->walk_open = false;
+    float* const xb = (float*)n->xb.p;
+    const int32_t* const yb = (const int32_t*)n->yb.p;
+    float* const el = (float*)n->eloss.p;
+    const std::pair<int, float> key{B, lr};
+    for (int64_t s = first_batch; s < first_batch + n_batches; ++s) {
+        RTRY(launch_gather(n, X, x_kind, x_scale, x_shift, labels, (long long)rows, perm ? perm + s * B : nullptr, (long long)s * B, B));
+        // (looked up per step: the eager step of a first use can grow a scratch buffer, which drops every graph)
+        auto it = n->epoch_graphs.find(key);
+        if (it == n->epoch_graphs.end()) {
+            hipGraphExec_t exec = nullptr;
+            RTRY(step_and_capture(n, xb, yb, B, lr, el, &exec));
+            if (n->epoch_graphs.size() >= 8) drop_all(n->epoch_graphs);     // (eight (B, lr) pairs: a caller that varies lr per step)
+            n->epoch_graphs.emplace(key, exec);
+        } else {
+            XTRY(n, hipGraphLaunch(it->second, n->stream));
+        }
+        if (loss_dev) XTRY(n, hipMemcpyAsync(loss_dev + (s - first_batch), el, sizeof(float), hipMemcpyDeviceToDevice, n->stream));
+    }
+    return 0;
+}
+
+int rcn_hipx_evaluate_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows,
+                          double* loss_sum, int64_t* correct, int32_t* pred) {
+    if (!n) return -1;
+    if (!X) return fail(n, -1, "evaluate: X_dev must not be NULL");
+    if (!x_kind_ok(x_kind)) return fail(n, -1, "evaluate: x_kind must be RCN_HIPX_X_F32 or RCN_HIPX_X_U8");
+    if (rows < 1) return fail(n, -1, "evaluate: n must be at least 1");
+    if (labels && (!loss_sum || !correct)) return fail(n, -1, "evaluate: with labels, loss_sum_dev and correct_dev must not be NULL");
+    if (!labels && !pred) return fail(n, -1, "evaluate: without labels there is only pred_dev to fill; it must not be NULL");
+    if (n->walk_open) return fail(n, -6, "evaluate: a bucket walk is open (rcn_hipx_gradients_begin_dev): its activations are still needed; take the remaining buckets first");
+    Dev g(n->device);
+    if (x_kind == RCN_HIPX_X_U8) RTRY(ensure_epoch_bufs(n));
+    if (loss_sum) XTRY(n, hipMemsetAsync(loss_sum, 0, sizeof(double), n->stream));
+    if (correct) XTRY(n, hipMemsetAsync(correct, 0, sizeof(int64_t), n->stream));
+    RTRY(prep_bf16_weights(n));
+    const long long E = row_elems(n);
+    for (int64_t off = 0; off < rows; off += n->max_batch) {
+        const int B = (int)(rows - off < n->max_batch ? rows - off : n->max_batch);
+        const float* x = (const float*)X + off * E;
+        if (x_kind == RCN_HIPX_X_U8) {
+            RTRY(launch_gather(n, X, x_kind, x_scale, x_shift, nullptr, (long long)rows, nullptr, (long long)off, B));
+            x = (const float*)n->xb.p;
+        }
+        RTRY(eval_chunk(n, x, labels ? labels + off : nullptr, B, loss_sum, (long long*)correct, pred ? pred + off : nullptr));
+    }
+    return 0;
+}
+
+int rcn_hipx_graphs_instantiated(const rcn_hipx_net* n, int64_t* count) {
+    if (!n || !count) return -1;
+    *count = n->n_instantiated;
     return 0;
 }
 
@@ -1022,6 +1177,7 @@ int rcn_hipx_gradients_dev(rcn_hipx_net* n, const float* x, const int32_t* label
     if (!n || !x || !labels || !grad) return -1;
     RTRY(ensure_batch(n, B));
     Dev g(n->device);
+    n->walk_open = false;
     XTRY(n, hipMemsetAsync(grad, 0, (size_t)n->n_pad * sizeof(float), n->stream));
     return step_core(n, x, labels, B, 0.f, grad, false, loss_dev);
 }
@@ -1030,10 +1186,12 @@ int rcn_hipx_gradients_begin_dev(rcn_hipx_net* n, const float* x, const int32_t*
     if (!n || !x || !labels || !grad || !n_buckets || min_bucket_bytes < 0) return -1;
     RTRY(ensure_batch(n, B));
     Dev g(n->device);
+    n->walk_open = false;
     XTRY(n, hipMemsetAsync(grad, 0, (size_t)n->n_pad * sizeof(float), n->stream));
     const int nb = grad_begin(n, x, labels, B, grad, loss_dev, (long long)min_bucket_bytes);
     if (nb < 0) return nb;
     *n_buckets = nb;
+    n->walk_open = true;
     return 0;
 }
 
@@ -1042,6 +1200,7 @@ int rcn_hipx_gradients_bucket_dev(rcn_hipx_net* n, int k, int64_t* off, int64_t*
     Dev g(n->device);
     long long o = 0, l = 0;
     RTRY(grad_bucket(n, k, &o, &l));
+    if (n->bw.taken == (int)n->bw.lo.size()) n->walk_open = false;      // the last bucket: the walk is over
     if (off) *off = o;
     if (len) *len = l;
     return 0;
@@ -1186,6 +1345,35 @@ int rcn_hipx_plan_net(const rcn_hipx_net* n, int batch, char* out, int cap) {
     make_dry_net(net, *n, batch);
     net.plan = "forward + loss + backward of one batch of " + std::to_string(batch) + " (" + precision_name(net.precision, net.store16) + "), launch by launch:\n";
     const int st = step_core(&net, nullptr, nullptr, batch, 0.f, nullptr, true, nullptr);
+    const std::string& text = st == 0 ? net.plan : net.err;
+    std::snprintf(out, (size_t)cap, "%s", text.c_str());
+    return st;
+}
+
+// rcn_hipx_plan's dry walk for ONE evaluation chunk: the forward pass over all layers and the evaluation kernel.  A net that
+// rcn_hipx_set_precision would refuse (RCN_HIPX_BF16_STORED on layers the bf16-tensor kernels do not cover) is refused here with the same text.
+int rcn_hipx_plan_eval(int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, int n_layers, int batch, int precision, int tiling, char* out, int cap) {
+    if (!layers || n_layers < 1 || in_h < 1 || in_w < 1 || in_c < 1 || batch < 1 || !out || cap < 1) return -1;
+    if ((precision != RCN_HIPX_FP32 && precision != RCN_HIPX_BF16 && precision != RCN_HIPX_BF16_STORED) || tiling < RCN_HIPX_TILING_GEMM || tiling > RCN_HIPX_TILING_LDS) return -1;
+    rcn_hipx_net net;
+    int st = make_dry_net(net, in_h, in_w, in_c, layers, n_layers, batch, precision, tiling);
+    if (st == 0 && net.store16) {
+        std::string why;
+        st = store16_covered(net, &why);
+        if (st != 0) net.err = why;
+    }
+    if (st == 0) st = plan_eval_walk(net, batch);
+    const std::string& text = st == 0 ? net.plan : net.err;
+    std::snprintf(out, (size_t)cap, "%s", text.c_str());
+    return st;
+}
+
+// the same walk for an EXISTING net, with that net's own precision, tiling and options
+int rcn_hipx_plan_eval_net(const rcn_hipx_net* n, int batch, char* out, int cap) {
+    if (!n || batch < 1 || batch > n->max_batch || !out || cap < 1) return -1;
+    rcn_hipx_net net;
+    make_dry_net(net, *n, batch);
+    const int st = plan_eval_walk(net, batch);
     const std::string& text = st == 0 ? net.plan : net.err;
     std::snprintf(out, (size_t)cap, "%s", text.c_str());
     return st;

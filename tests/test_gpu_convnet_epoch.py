@@ -1,0 +1,489 @@
+"""GPU tests of Track X's loop around the training step (include/rcn_hipx.h): rcn_hipx_train_epoch_dev -- an epoch over a permutation of
+a device-resident set, gathered on the device into the net's own batch buffer and trained on ONE captured graph per (B, lr) -- and
+rcn_hipx_evaluate_dev -- loss sum, correct count and first-maximum arg-max over a whole set without a backward pass.
+
+Both reuse the step's and the forward pass's own kernels, so most checks are exact: an epoch against the same batches fed to train_step
+one by one (bit for bit), uint8 rows against the fp32 set built with two roundings (bit for bit), predictions and the correct count
+against the arg-max of the device's own logits (integers).  The loss is held to the project's tolerances against an f64 evaluation."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from oracle import convnet_oracle as co
+
+pytestmark = pytest.mark.gpu
+
+FUSED_HEAD = ((8, 8, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 32), ("dense", 10)), 5)
+PLAIN_HEAD = ((6, 6, 1), (("conv", 32), ("conv", 32), ("pool",), ("dense", 7)), 3)
+POOL_PAIRS = ((16, 16, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 128), ("dense", 10)), 64)     # bf16 storage covers it
+CIFAR = ((32, 32, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("conv", 128), ("pool",), ("dense_relu", 256), ("dense", 10)), 512)
+MNIST = ((28, 28, 1), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 128), ("dense", 10)), 4096)
+SMALL = [(FUSED_HEAD, "fp32"), (PLAIN_HEAD, "bf16"), (POOL_PAIRS, "bf16_stored")]
+SMALL_IDS = ["fused_head-fp32", "plain_head-bf16", "pool_pairs-bf16_stored"]
+LOSS_RTOL = {"fp32": 2e-4, "bf16": 5e-3, "bf16_stored": 5e-3}       # tests/test_gpu_convnet.py: loss and logits tolerances of each mode
+SCALE, SHIFT = 1.0 / 255.0, -0.1307                                 # neither is a power of two
+
+
+def _net(spec, precision="fp32"):
+    from mercer_research_amd.convnet import ConvNet
+    in_shape, layers, B = spec
+    net = ConvNet(in_shape, layers, B)
+    net.set_precision(precision)
+    return net
+
+
+def _twins(spec, precision, seed=1):
+    a = _net(spec, precision)
+    a.init_params(seed)
+    b = _net(spec, precision)
+    b.set_params(a.get_params())
+    return a, b
+
+
+def _sync():
+    import torch
+    torch.cuda.synchronize()
+
+
+def _dev(net, a):
+    t = net.to_device(a)
+    _sync()
+    return t
+
+
+def _random_set(net, spec, n, seed=0, u8=False):
+    in_shape, layers, _ = spec
+    rng = np.random.default_rng(seed)
+    X = rng.integers(0, 256, (n,) + in_shape).astype(np.uint8) if u8 else rng.standard_normal((n,) + in_shape).astype(np.float32)
+    y = rng.integers(0, layers[-1][1], n).astype(np.int32)
+    return _dev(net, X), _dev(net, y)
+
+
+def _widen(u8):
+    """The fp32 set a uint8 set stands for: fl(fl(u8 * scale) + shift), two roundings, built with torch on the host."""
+    import torch
+    t = torch.from_numpy(u8).float() * torch.tensor(SCALE, dtype=torch.float32)
+    return (t.float() + torch.tensor(SHIFT, dtype=torch.float32)).numpy()
+
+
+def _epoch(net, X, y, perm, B, lr, **kw):
+    import torch
+    with torch.cuda.stream(net.stream):
+        net.train_epoch(X, y, perm, B, lr, **kw)
+    net.synchronize()
+
+
+def _steps(net, X, y, perm, B, lr, n_batches):
+    """The same batches fed to train_step one by one, gathered with torch; returns the per-step losses."""
+    import torch
+    losses = torch.zeros(n_batches, dtype=torch.float32, device=net.device)
+    _sync()
+    keep = []
+    with torch.cuda.stream(net.stream):
+        for s in range(n_batches):
+            idx = (perm[s * B:(s + 1) * B] if perm is not None else torch.arange(s * B, (s + 1) * B, device=net.device)).long()
+            xb, yb = X[idx].contiguous(), y[idx].contiguous()
+            keep.append((xb, yb))
+            net.train_step(xb, yb, lr, losses[s:s + 1])
+    net.synchronize()
+    return losses.cpu().numpy()
+
+
+def _evaluate_all(net, X, y, **kw):
+    """(loss_sum as float64 bits, correct, pred) of one evaluation call."""
+    loss_sum, correct, pred = net.evaluate_async(X, y, **kw)
+    net.synchronize()
+    return loss_sum.cpu().numpy().copy(), int(correct.item()), pred.cpu().numpy().copy()
+
+
+def _device_logits(net, X):
+    """forward() chunk by chunk: the device's own logits of every row."""
+    import torch
+    out = []
+    with torch.cuda.stream(net.stream):
+        for off in range(0, X.shape[0], net.max_batch):
+            out.append(net.forward(X[off:off + net.max_batch].contiguous()))
+    net.synchronize()
+    return torch.cat(out).cpu()
+
+
+def _host_ce(logits64, y):
+    z = logits64 - logits64.max(axis=1, keepdims=True)
+    logp = z - np.log(np.exp(z).sum(axis=1, keepdims=True))
+    return -logp[np.arange(len(y)), y]
+
+
+# ---- 1. an epoch is its steps, bit for bit ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("spec,precision,sgd", [(FUSED_HEAD, "fp32", False), (PLAIN_HEAD, "bf16", True), (POOL_PAIRS, "bf16_stored", False)], ids=SMALL_IDS)
+def test_epoch_is_the_same_batches_fed_to_train_step_bit_for_bit(spec, precision, sgd):
+    import torch
+    B, lr = spec[2], 0.05
+    a, b = _twins(spec, precision)
+    if sgd:
+        a.set_sgd(0.9, 5e-4, True)
+        b.set_sgd(0.9, 5e-4, True)
+    n = 11 * B + 3
+    nb = n // B                                          # 11 whole batches and a remainder (B = 3: the three extra rows are a twelfth batch)
+    X, y = _random_set(a, spec, n, seed=3)
+    perm = _dev(a, np.random.default_rng(5).permutation(n).astype(np.int32))
+    la = torch.zeros(nb, dtype=torch.float32, device=a.device)
+    _sync()
+    p0 = a.get_params()
+    _epoch(a, X, y, perm, B, lr, losses=la)
+    lb = _steps(b, X, y, perm, B, lr, nb)
+    assert np.array_equal(la.cpu().numpy(), lb), (la.cpu().numpy(), lb)
+    assert np.array_equal(a.get_params(), b.get_params())
+    assert np.array_equal(a.get_velocity(), b.get_velocity())
+    assert not np.array_equal(a.get_params(), p0) and np.all(np.isfinite(lb)) and (not sgd or np.abs(a.get_velocity()).max() > 0)
+    a.close(); b.close()
+
+
+def test_no_permutation_split_calls_and_the_remainder():
+    """perm=None is the identity permutation; first_batch / n_batches split an epoch into calls without changing it; the rows past the
+    last whole batch are never read into a step (NaN there changes nothing)."""
+    import torch
+    spec, B, nb, lr = FUSED_HEAD, FUSED_HEAD[2], 11, 0.05
+    a, b = _twins(spec, "fp32")
+    c, d = _twins(spec, "fp32")
+    for net in (b, c, d):
+        net.set_params(a.get_params())
+    n = nb * B + 3
+    X, y = _random_set(a, spec, n, seed=8)
+    ident = _dev(a, np.arange(n, dtype=np.int32))
+    perm = _dev(a, np.random.default_rng(9).permutation(n).astype(np.int32))
+    _epoch(a, X, y, None, B, lr)
+    _epoch(b, X, y, ident, B, lr)
+    assert np.array_equal(a.get_params(), b.get_params())
+    # one call of 11 == calls of 5 and 6; the losses land in the call's own slots
+    l1 = torch.zeros(nb, dtype=torch.float32, device=a.device)
+    l2 = torch.zeros(nb, dtype=torch.float32, device=a.device)
+    _sync()
+    for net in (a, b):
+        net.set_params(c.get_params())
+    _epoch(a, X, y, perm, B, lr, losses=l1)
+    _epoch(b, X, y, perm, B, lr, first_batch=0, n_batches=5, losses=l2)
+    _epoch(b, X, y, perm, B, lr, first_batch=5, n_batches=6, losses=l2[5:])
+    assert np.array_equal(a.get_params(), b.get_params())
+    assert np.array_equal(l1.cpu().numpy(), l2.cpu().numpy())
+    # the three remainder rows (perm[11 * B:]) replaced by NaN
+    Xn = X.clone()
+    Xn[perm[nb * B:].long()] = float("nan")
+    _sync()
+    _epoch(c, X, y, perm, B, lr)
+    _epoch(d, Xn, y, perm, B, lr)
+    pc, pd = c.get_params(), d.get_params()
+    assert np.all(np.isfinite(pd)) and np.array_equal(pc, pd) and np.array_equal(pc, a.get_params())
+    for net in (a, b, c, d):
+        net.close()
+
+
+# ---- 2. one graph ----------------------------------------------------------------------------------------------------------------------
+
+def test_an_epoch_replays_one_graph_where_train_step_on_slices_captures_twelve():
+    import torch
+    spec, B, nb, lr = FUSED_HEAD, FUSED_HEAD[2], 12, 0.05            # 12 batches: more than train_step's cache of 8 graphs
+    net = _net(spec)
+    net.init_params(1)
+    n = nb * B
+    X, y = _random_set(net, spec, n, seed=1)
+    rng = np.random.default_rng(2)
+    g0 = net.graphs_instantiated()
+    l1 = torch.zeros(nb, dtype=torch.float32, device=net.device)
+    _epoch(net, X, y, _dev(net, rng.permutation(n).astype(np.int32)), B, lr, losses=l1)
+    g1 = net.graphs_instantiated()
+    assert 0 <= g1 - g0 <= 1, (g0, g1)
+    # another permutation, another X tensor, another losses tensor: nothing is instantiated
+    X2, l2 = X.clone(), torch.zeros(nb, dtype=torch.float32, device=net.device)
+    _sync()
+    _epoch(net, X2, y, _dev(net, rng.permutation(n).astype(np.int32)), B, lr, losses=l2)
+    _epoch(net, X, y, None, B, lr, first_batch=3, n_batches=4)
+    assert net.graphs_instantiated() == g1
+    # the trap the feature removes: train_step keys its graph by the batch's pointers, so walking a set re-captures on every step
+    with torch.cuda.stream(net.stream):
+        for s in range(nb):
+            net.train_step(X[s * B:(s + 1) * B], y[s * B:(s + 1) * B], lr)
+    net.synchronize()
+    assert net.graphs_instantiated() == g1 + nb
+    # ... and the epoch's graph survived those captures
+    _epoch(net, X, y, None, B, lr)
+    assert net.graphs_instantiated() == g1 + nb
+    net.close()
+
+
+# ---- 3. uint8 rows ---------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("spec,precision", SMALL, ids=SMALL_IDS)
+def test_uint8_rows_are_the_twice_rounded_fp32_set_bit_for_bit(spec, precision):
+    import torch
+    B, nb, lr = spec[2], 4, 0.05
+    a, b = _twins(spec, precision)
+    n = nb * B + 2
+    Xu, y = _random_set(a, spec, n, seed=11, u8=True)
+    Xf = _dev(a, _widen(Xu.cpu().numpy()))
+    perm = _dev(a, np.random.default_rng(12).permutation(n).astype(np.int32))
+    la = torch.zeros(nb, dtype=torch.float32, device=a.device)
+    lb = torch.zeros(nb, dtype=torch.float32, device=a.device)
+    _sync()
+    _epoch(a, Xu, y, perm, B, lr, losses=la, x_scale=SCALE, x_shift=SHIFT)
+    _epoch(b, Xf, y, perm, B, lr, losses=lb)
+    assert np.array_equal(la.cpu().numpy(), lb.cpu().numpy())
+    assert np.array_equal(a.get_params(), b.get_params())
+    sa, ca, pa = _evaluate_all(a, Xu, y, x_scale=SCALE, x_shift=SHIFT)
+    sb, cb, pb = _evaluate_all(b, Xf, y)
+    assert sa.tobytes() == sb.tobytes() and ca == cb and np.array_equal(pa, pb)
+    a.close(); b.close()
+
+
+# ---- 4. evaluation is exact against the device's own logits ----------------------------------------------------------------------------
+
+def _check_eval_against_device_logits(net, spec, N, seed, u8=False):
+    classes = spec[1][-1][1]
+    X, y = _random_set(net, spec, N, seed=seed, u8=u8)
+    kw = dict(x_scale=SCALE, x_shift=SHIFT) if u8 else {}
+    Xf = _dev(net, _widen(X.cpu().numpy())) if u8 else X
+    logits = _device_logits(net, Xf)
+    want_pred = logits.argmax(1).numpy().astype(np.int32)            # torch's arg-max returns the first maximum
+    yh = y.cpu().numpy()
+    loss_sum, correct, pred = _evaluate_all(net, X, y, **kw)
+    assert np.array_equal(pred, want_pred)
+    assert correct == int((want_pred == yh).sum())
+    ref = float(_host_ce(logits.numpy().astype(np.float64), yh).mean())
+    got = float(loss_sum[0]) / N
+    assert abs(got - ref) <= 2e-4 * max(1.0, ref), f"mean loss {got} against f64 soft-max cross-entropy of the device's logits {ref}: deviation {abs(got - ref):.3e}"
+    print(f"evaluate: N = {N}, mean loss {got:.9g}, f64 reference {ref:.9g}, deviation {abs(got - ref):.3e} (bound {2e-4 * max(1.0, ref):.3e})")
+    mean_loss, correct2 = net.evaluate(X, y, **kw)
+    assert mean_loss == got and correct2 == correct
+    again = _evaluate_all(net, X, y, **kw)
+    assert again[0].tobytes() == loss_sum.tobytes() and again[1] == correct and np.array_equal(again[2], pred)
+    p = net.predict(X, **kw)
+    net.synchronize()
+    assert np.array_equal(p.cpu().numpy(), pred)
+    # labels outside [0, classes) on two rows: incorrect, nothing added to the loss, nothing indexed
+    yb = yh.copy()
+    yb[1], yb[N - 2] = -1, classes
+    good = np.ones(N, dtype=bool)
+    good[[1, N - 2]] = False
+    s2, c2, p2 = _evaluate_all(net, X, _dev(net, yb), **kw)
+    assert np.array_equal(p2, pred) and c2 == int((want_pred[good] == yh[good]).sum())
+    ref2 = float(_host_ce(logits.numpy().astype(np.float64)[good], yh[good]).sum())
+    assert abs(float(s2[0]) - ref2) <= 2e-4 * max(1.0, ref2 / N) * N
+    return abs(got - ref)
+
+
+@pytest.mark.parametrize("spec,precision", SMALL, ids=SMALL_IDS)
+def test_evaluation_is_exact_against_the_devices_own_logits(spec, precision):
+    """N = 2 * max_batch + 13 rows: chunked, a short last chunk, N % 8 != 0."""
+    net = _net(spec, precision)
+    net.init_params(3)
+    N = 2 * spec[2] + 13
+    assert N % 8 != 0 and N % spec[2] != 0
+    _check_eval_against_device_logits(net, spec, N, seed=21)
+    net.close()
+
+
+def test_ties_go_to_the_first_maximum():
+    spec = FUSED_HEAD
+    in_shape, layers, B = spec
+    net = _net(spec)
+    ws = [np.zeros(k) for k, _ in co.param_shapes(in_shape, layers)]
+    bs = [np.zeros(n) for _, n in co.param_shapes(in_shape, layers)]
+    rng = np.random.default_rng(1)
+    for w in ws[:-1]:
+        w[...] = rng.standard_normal(w.shape) * 0.1
+    bs[-1][:4] = [1, 3, 3, 2]                                        # zero weights in the last layer: every row's logits are its biases
+    net.set_params(co.flatten(ws, bs).astype(np.float32))
+    X, _ = _random_set(net, spec, 2 * B + 3, seed=2)
+    p = net.predict(X)
+    net.synchronize()
+    assert np.array_equal(p.cpu().numpy(), np.full(2 * B + 3, 1, dtype=np.int32))
+    net.close()
+
+
+# ---- 5. evaluation against the f64 oracle ----------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("spec,precision", SMALL, ids=SMALL_IDS)
+def test_evaluation_matches_the_oracle(spec, precision):
+    """300 rows; He-scaled weights, the last bias centred on the oracle's logits so that every class is predicted; labels: the oracle's
+    arg-max on even rows, uniformly random on odd rows.  pred is compared on every row whose oracle top-two margin exceeds twice the
+    logits tolerance of the mode; the rows that rule leaves out may be at most 10 % of the set."""
+    in_shape, layers, _ = spec
+    N, classes, rtol = 300, layers[-1][1], LOSS_RTOL[precision]
+    kw = {} if precision == "fp32" else dict(operand="bf16", stored=precision == "bf16_stored")
+    rng = np.random.default_rng(7)
+    shapes = co.param_shapes(in_shape, layers)
+    ws = [(rng.standard_normal(k) * np.sqrt(2.0 / k[0])).astype(np.float32).astype(np.float64) for k, _ in shapes]
+    bs = [np.zeros(n) for _, n in shapes]
+    x = rng.standard_normal((N,) + in_shape).astype(np.float32)
+    x64 = x.astype(np.float64)
+    bs[-1] = (-co.forward(x64, ws, bs, layers, **kw).mean(axis=0)).astype(np.float32).astype(np.float64)
+    logits = co.forward(x64, ws, bs, layers, **kw)
+    top = logits.argmax(1)
+    counts = np.bincount(top, minlength=classes)
+    assert counts.min() >= 5, counts                                 # every class is predicted: the accuracy check is not empty
+    y = np.where(np.arange(N) % 2 == 0, top, rng.integers(0, classes, N)).astype(np.int32)
+    srt = np.sort(logits, axis=1)
+    margin = srt[:, -1] - srt[:, -2]
+    sure = margin > 2 * (rtol * np.abs(logits).max() + 1e-6)
+    assert (~sure).sum() <= 0.10 * N, int((~sure).sum())             # asserted before anything is compared
+    net = _net(spec, precision)
+    net.set_params(co.flatten(ws, bs).astype(np.float32))
+    loss_sum, correct, pred = _evaluate_all(net, _dev(net, x), _dev(net, y))
+    ref = float(_host_ce(logits, y).mean())
+    got = float(loss_sum[0]) / N
+    assert abs(got - ref) <= rtol * max(1.0, ref), (got, ref)
+    assert np.array_equal(pred[sure], top[sure].astype(np.int32)), int((pred[sure] != top[sure]).sum())
+    assert correct == int((pred == y).sum())
+    assert correct >= int(sure[::2].sum())                           # (the even rows carry the oracle's own arg-max as their label)
+    net.close()
+
+
+# ---- 6. evaluation leaves training alone -----------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("spec,precision", SMALL, ids=SMALL_IDS)
+def test_evaluation_between_steps_changes_nothing(spec, precision):
+    import torch
+    B, lr = spec[2], 0.05
+    a, b = _twins(spec, precision)
+    a.set_sgd(0.9, 5e-4, False)
+    b.set_sgd(0.9, 5e-4, False)
+    X, y = _random_set(a, spec, 3 * B + 1, seed=4)
+    xb, yb = X[:B].contiguous(), y[:B].contiguous()
+    _sync()
+    for net in (a, b):                                               # the graph exists on both sides and has been replayed
+        with torch.cuda.stream(net.stream):
+            net.train_step(xb, yb, lr)
+            net.train_step(xb, yb, lr)
+        net.synchronize()
+    assert np.array_equal(a.get_params(), b.get_params())
+    with torch.cuda.stream(a.stream):
+        a.train_step(xb, yb, lr)
+    a.evaluate(X, y)
+    with torch.cuda.stream(a.stream):
+        a.train_step(xb, yb, lr)
+    a.synchronize()
+    with torch.cuda.stream(b.stream):
+        b.train_step(xb, yb, lr)
+        b.train_step(xb, yb, lr)
+    b.synchronize()
+    assert np.array_equal(a.get_params(), b.get_params()) and np.array_equal(a.get_velocity(), b.get_velocity())
+    # the same around an epoch's steps
+    _epoch(a, X, y, None, B, lr, n_batches=2)
+    a.evaluate(X, y)
+    _epoch(a, X, y, None, B, lr, first_batch=2, n_batches=1)
+    _epoch(b, X, y, None, B, lr)
+    assert np.array_equal(a.get_params(), b.get_params())
+    a.close(); b.close()
+
+
+def test_evaluation_inside_an_open_bucket_walk_is_refused_and_the_walk_finishes():
+    import torch
+    from mercer_research_amd.convnet import ConvNetError
+    spec = POOL_PAIRS
+    B = spec[2]
+    net = _net(spec)
+    net.init_params(2)
+    X, y = _random_set(net, spec, B, seed=6)
+    with torch.cuda.stream(net.stream):
+        want = net.gradients(X, y).clone()
+        grad = torch.empty(net.n_padded, dtype=torch.float32, device=net.device)
+    net.synchronize()
+    nb, off, ln = C.c_int(), C.c_int64(), C.c_int64()
+    net._ck(net.lib.rcn_hipx_gradients_begin_dev(net.net, C.c_void_p(X.data_ptr()), C.c_void_p(y.data_ptr()), B, C.c_void_p(grad.data_ptr()), None, 0, C.byref(nb)))
+    assert nb.value >= 2
+    net._ck(net.lib.rcn_hipx_gradients_bucket_dev(net.net, 0, C.byref(off), C.byref(ln)))
+    with pytest.raises(ConvNetError, match="status -6"):
+        net.evaluate(X, y)
+    with pytest.raises(ConvNetError, match="status -6"):
+        net.predict(X)
+    for k in range(1, nb.value):
+        net._ck(net.lib.rcn_hipx_gradients_bucket_dev(net.net, k, C.byref(off), C.byref(ln)))
+    net.synchronize()
+    assert np.array_equal(grad.cpu().numpy(), want.cpu().numpy())
+    net.evaluate(X, y)                                               # the walk is over: evaluation runs again
+    net.close()
+
+
+# ---- 7. BASELINE shapes ----------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("spec,precision", [(CIFAR, "fp32"), (MNIST, "bf16_stored")], ids=["cifar-b512-fp32", "mnist-b4096-bf16_stored"])
+def test_epoch_and_evaluation_at_baseline_shapes(spec, precision):
+    import torch
+    B, nb, lr = spec[2], 3, 0.02
+    a, b = _twins(spec, precision)
+    n = nb * B + 5
+    Xu, y = _random_set(a, spec, n, seed=31, u8=True)
+    Xf = _dev(a, _widen(Xu.cpu().numpy()))
+    perm = _dev(a, np.random.default_rng(32).permutation(n).astype(np.int32))
+    la = torch.zeros(nb, dtype=torch.float32, device=a.device)
+    _sync()
+    _epoch(a, Xu, y, perm, B, lr, losses=la, x_scale=SCALE, x_shift=SHIFT)
+    lb = _steps(b, Xf, y, perm, B, lr, nb)
+    assert np.array_equal(la.cpu().numpy(), lb)
+    assert np.array_equal(a.get_params(), b.get_params())
+    b.close()
+    del Xu, Xf
+    _check_eval_against_device_logits(a, spec, 2 * B + 17, seed=33, u8=True)
+    a.close()
+
+
+# ---- 8. refusals -----------------------------------------------------------------------------------------------------------------------
+
+def test_refusals_enqueue_nothing_and_change_nothing():
+    import torch
+    from mercer_research_amd.convnet import ConvNetError
+    spec = FUSED_HEAD
+    B = spec[2]
+    net = _net(spec)
+    net.init_params(4)
+    n = 4 * B + 1
+    X, y = _random_set(net, spec, n, seed=13)
+    perm = _dev(net, np.arange(n, dtype=np.int32))
+    _epoch(net, X, y, perm, B, 0.05)                                  # (so that a graph exists and the counter could move)
+    p0, g0 = net.get_params(), net.graphs_instantiated()
+    lib, h = net.lib, net.net
+    xp, yp, pp = C.c_void_p(X.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(perm.data_ptr())
+    ls = torch.zeros(1, dtype=torch.float64, device=net.device)
+    cs = torch.zeros(1, dtype=torch.int64, device=net.device)
+    pr = torch.zeros(n, dtype=torch.int32, device=net.device)
+    _sync()
+    lp, cp, prp = C.c_void_p(ls.data_ptr()), C.c_void_p(cs.data_ptr()), C.c_void_p(pr.data_ptr())
+    epoch = lambda X_=xp, kind=0, y_=yp, n_=n, B_=B, first=0, nb=4: lib.rcn_hipx_train_epoch_dev(h, X_, kind, 1.0, 0.0, y_, n_, pp, B_, first, nb, 0.05, None)
+    assert epoch(B_=0) == -1 and epoch(B_=B + 1) == -1 and epoch(n_=0) == -1
+    assert epoch(X_=None) == -1 and epoch(y_=None) == -1 and epoch(kind=2) == -1 and epoch(kind=-1) == -1
+    assert epoch(nb=5) == -1 and epoch(first=1, nb=4) == -1 and epoch(first=-1, nb=1) == -1 and epoch(first=0, nb=-1) == -1
+    assert epoch(first=1 << 62, nb=1 << 62) == -1
+    ev = lambda X_=xp, kind=0, y_=yp, n_=n, l_=lp, c_=cp, p_=prp: lib.rcn_hipx_evaluate_dev(h, X_, kind, 1.0, 0.0, y_, n_, l_, c_, p_)
+    assert ev(X_=None) == -1 and ev(kind=2) == -1 and ev(n_=0) == -1 and ev(n_=-3) == -1
+    assert ev(l_=None) == -1 and ev(c_=None) == -1 and ev(y_=None, l_=None, c_=None, p_=None) == -1
+    assert b"must not" in lib.rcn_hipx_last_error(h)
+    # the Python face: the library's refusals are ConvNetError, an out-of-range permutation is a ValueError (checked once per call)
+    with pytest.raises(ConvNetError):
+        net.train_epoch(X, y, perm, B + 1, 0.05)
+    with pytest.raises(ConvNetError):
+        net.train_epoch(X, y, perm, B, 0.05, n_batches=5)
+    with pytest.raises(ConvNetError):
+        net.train_epoch(X, y, None, B, 0.05, first_batch=2, n_batches=3)
+    with pytest.raises(ConvNetError):
+        net.train_epoch(X, y, None, 0, 0.05)
+    for bad in (n, -1):
+        pb = perm.clone()
+        pb[3] = bad
+        _sync()
+        with pytest.raises(ValueError):
+            net.train_epoch(X, y, pb, B, 0.05)
+    with pytest.raises(ValueError):
+        net.train_epoch(X.double(), y, perm, B, 0.05)
+    with pytest.raises(ValueError):
+        net.train_epoch(X, y.long(), perm, B, 0.05)
+    with pytest.raises(ValueError):
+        net.evaluate(X[:, :4], y)
+    net.synchronize()
+    assert net.graphs_instantiated() == g0 and np.array_equal(net.get_params(), p0)
+    assert ls.item() == 0.0 and cs.item() == 0 and not pr.any().item()
+    # what the checks let through still works
+    assert ev() == 0
+    net.synchronize()
+    assert cs.item() == int((pr == y).sum().item())
+    net.close()
