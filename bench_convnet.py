@@ -29,7 +29,9 @@ HBM_PEAK_GBS = 8000.0
 
 def resident_set_figures(net, args, in_shape, B, lr):
     """--dataset N: whole epochs of train_epoch over a resident synthetic set (a fresh device permutation per epoch, its range check and
-    the gather included), then evaluate over the set.  Whole-call rates from a host clock around work that ends in a synchronise."""
+    the gather included), then evaluate over the set.  Whole-call rates from a host clock around work that ends in a synchronise.
+    --lr-schedule / --augment: the same epochs once more as that recipe -- a warm-up + cosine rate per step from a device tensor, the
+    gather through a random crop and flip -- timed the same way, beside the plain figure."""
     import torch
     N = args.dataset
     nb = N // B
@@ -56,6 +58,39 @@ def resident_set_figures(net, args, in_shape, B, lr):
             epoch()
         net.synchronize()
         el = time.perf_counter() - t0
+        recipe = {}
+        if args.lr_schedule != "none" or args.augment >= 0:
+            from mercer_research_amd.convnet import Augment, warmup_cosine
+            sched = torch.from_numpy(warmup_cosine(nb, lr, max(1, nb // 20))).to(net.device) if args.lr_schedule == "warmup_cosine" else lr
+            seen = [0]
+
+            def recipe_epoch():
+                perm = torch.randperm(N, generator=gen, device=net.device).int()
+                net.train_epoch(X, Y, perm, B, sched, losses=losses, augment=Augment(args.augment, True, 1, seen[0]) if args.augment >= 0 else None)
+                seen[0] += 1
+
+            recipe_epoch()                                 # a scheduled rate has its own graph: instantiated here, once
+            net.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(epochs):
+                recipe_epoch()
+            net.synchronize()
+            rel = time.perf_counter() - t0
+            recipe = {"recipe": {"lr_schedule": args.lr_schedule, "augment_pad": args.augment if args.augment >= 0 else None, "hflip": args.augment >= 0},
+                      "recipe_epoch_ms_per_step": round(rel / (epochs * nb) * 1e3, 4)}
+        graphs = net.graphs_instantiated()                 # read here: the trap below instantiates one per step on purpose
+        if args.trap:
+            # what the scheduled path removes: the same kind of schedule as one-batch calls with a new float rate each -- the rate is part
+            # of a constant-rate graph's key, so every step pays an eager step, a capture and an instantiate
+            from mercer_research_amd.convnet import warmup_cosine
+            rates = [float(v) + 1e-6 for v in warmup_cosine(nb, lr, max(1, nb // 20))]
+            perm = torch.randperm(N, generator=gen, device=net.device).int()
+            net.synchronize()
+            t0 = time.perf_counter()
+            for s, rate in enumerate(rates):
+                net.train_epoch(X, Y, perm, B, rate, n_batches=1, first_batch=s)
+            net.synchronize()
+            recipe.update({"trap_ms_per_step": round((time.perf_counter() - t0) / nb * 1e3, 4), "trap_graphs_instantiated": net.graphs_instantiated() - graphs})
         net.evaluate(X, Y)
         reps = max(1, -(-args.steps * B // (4 * N)))       # about a quarter of the timed steps' images
         t0 = time.perf_counter()
@@ -63,9 +98,9 @@ def resident_set_figures(net, args, in_shape, B, lr):
             loss_sum, correct, _ = net.evaluate_async(X, Y, want_pred=False)
         net.synchronize()
         ev = time.perf_counter() - t0
-    return {"dataset": N, "dataset_dtype": str(X.dtype).replace("torch.", ""), "epochs_timed": epochs, "epoch_ms_per_step": round(el / (epochs * nb) * 1e3, 4),
+    return {"dataset": N, "dataset_dtype": str(X.dtype).replace("torch.", ""), "epochs_timed": epochs, "epoch_ms_per_step": round(el / (epochs * nb) * 1e3, 4), **recipe,
             "epoch_images_per_s": round(epochs * nb * B / el, 1), "eval_images_per_s": round(reps * N / ev, 1),
-            "eval_mean_loss": round(float(loss_sum.item()) / N, 4), "eval_correct": int(correct.item()), "graphs_instantiated": net.graphs_instantiated()}
+            "eval_mean_loss": round(float(loss_sum.item()) / N, 4), "eval_correct": int(correct.item()), "graphs_instantiated": graphs}
 
 
 def main():
@@ -90,7 +125,17 @@ def main():
                     help="also keep a synthetic set of N images resident (uint8 for mnist / cifar, fp32 for synth224), time train_epoch over whole epochs with a fresh "
                          "device permutation each, then evaluate over the set: the line gains epoch_ms_per_step, epoch_images_per_s, eval_images_per_s, graphs_instantiated "
                          "(single GPU only)")
+    ap.add_argument("--lr-schedule", choices=["none", "warmup_cosine"], default="none",
+                    help="with --dataset: time the epochs once more with a per-step rate (warm-up over 5 %% of an epoch, then cosine to 0) from a device tensor: "
+                         "recipe_epoch_ms_per_step beside epoch_ms_per_step; graphs_instantiated, after it, shows that no step captured again")
+    ap.add_argument("--augment", type=int, default=-1, metavar="PAD",
+                    help="with --dataset: those epochs gather through a random crop with PAD zeros of padding and a horizontal flip (k_gather_aug)")
+    ap.add_argument("--trap", action="store_true",
+                    help="with --dataset: also run one epoch of a warm-up + cosine schedule as one-batch calls with a new FLOAT rate each (a capture per step): "
+                         "trap_ms_per_step, trap_graphs_instantiated")
     args = ap.parse_args()
+    if (args.lr_schedule != "none" or args.augment >= 0 or args.trap) and not args.dataset:
+        ap.error("--lr-schedule, --augment and --trap time the resident epoch: they need --dataset N")
     from mercer_research_amd.launch import spawn_ranks, under_launcher
     if args.gpus > 1 and not under_launcher():
         # `python bench_convnet.py --gpus N`: the parent makes no GPU call; it starts N fresh ranks and relays rank 0's line

@@ -107,13 +107,67 @@ enum { RCN_HIPX_X_F32 = 0,    /* [n][H][W][C] fp32, as rcn_hipx_train_step_dev t
  * ONE graph: the step always sees the net's own batch, labels and loss buffers, so every step of every call with the same (B, lr)
  * replays one instantiated hipGraph (a single chain of launches), whatever X_dev, perm_dev, first_batch and loss_dev are; the gather
  * and the 4-byte copy of the loss into its slot are launched eagerly around it.  rcn_hipx_train_step_dev on the caller's own pointers
- * keeps its own graph cache and key.  At most eight (B, lr) pairs are kept.
+ * keeps its own graph cache and key.  At most eight (B, lr) pairs are kept.  It is rcn_hipx_train_epoch_ex_dev(..., lr, NULL, NULL, ...),
+ * which also takes a per-step learning rate from the device and an augmentation without capturing again.
  * No wild reads: every perm_dev entry is clamped into [0, n) before it forms an address.  An entry outside that range is a caller error
  * (the clamped row is trained on), but it cannot fault.  labels are int32 class indices as for rcn_hipx_train_step_dev.
  * -1 (nothing enqueued): B outside 1 .. max_batch, n < 1, X_dev or labels_dev NULL, an unknown x_kind, first_batch or n_batches
  * negative, (first_batch + n_batches) * B > n. */
 int  rcn_hipx_train_epoch_dev(rcn_hipx_net* net, const void* X_dev, int x_kind, float x_scale, float x_shift, const int32_t* labels_dev, int64_t n,
                               const int32_t* perm_dev, int B, int64_t first_batch, int64_t n_batches, float lr, float* loss_dev);
+/* Augmentation of a gathered batch: a random translation with zero padding (torchvision's RandomCrop(padding = pad)), then a horizontal
+ * flip with probability 1/2 (RandomHorizontalFlip).  The sample at position q = s * B + r of the epoch (absolute batch s, row r) draws,
+ * in wrapping uint64 arithmetic (one splitmix64 output of a counter; no state in memory):
+ *     z  = seed ^ (epoch * 0xD1342543DE82EF95);  z += (q + 1) * 0x9E3779B97F4A7C15
+ *     z  = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^= z >> 31
+ *     dy = (int)(((z & 0xffff) * (2*pad + 1)) >> 16) - pad
+ *     dx = (int)((((z >> 16) & 0xffff) * (2*pad + 1)) >> 16) - pad
+ *     flip = hflip ? (z >> 32) & 1 : 0
+ * (the multiply-shift is not exactly uniform: an outcome's probability is off by less than 1 / 65536, the ratio of two outcomes' by less
+ * than (2*pad + 1) / 65536).  With S(h, w, c) the STORED value of the source row, or the stored value 0 outside the image,
+ *     out[r][h][w][c] = widen(S(h + dy, (flip ? W-1-w : w) + dx, c))
+ * where widen is what the un-augmented gather does to a stored value: a padded pixel of a uint8 set is fl(fl(0 * x_scale) + x_shift), of an
+ * fp32 set 0.0f.  No source address is formed from a coordinate outside the image.  pad = 0, hflip = 0 gives the bytes of no augmentation.
+ * q is absolute, so splitting an epoch into calls does not change a draw.  Evaluation is never augmented. */
+typedef struct rcn_hipx_augment {
+    int32_t  pad;     /* random translation: dy, dx each in [-pad, pad]; 0 <= pad <= 16 and pad < min(H, W) */
+    int32_t  hflip;   /* 0 | 1: mirror left-right with probability 1/2 */
+    uint64_t seed;
+    uint64_t epoch;   /* stream id: a different value gives different draws for the same positions */
+} rcn_hipx_augment;
+/* rcn_hipx_train_epoch_dev with a per-step learning rate and an augmentation, both outside the captured graph.
+ * lr_dev (nullable): [n_batches] floats on the device, lr_dev[i] = the rate of the call's i-th step (call-relative, like loss_dev); `lr`
+ * is then ignored.  The net owns one more 4-byte scalar beside its loss scalar; before each step lr_dev[i] is copied into it on the net's
+ * stream, and the step's update launch (k_reduce_all_dlr / k_reduce_all_sgd_dlr) reads its rate from there.  The graph key is then
+ * (B, "lr from device"): ONE instantiated graph serves every schedule, every epoch and every call, beside the constant-lr graphs and
+ * dropped whenever they are.  The arithmetic is the same p - lr * d on the same float, so a scheduled epoch is bit-identical to the same
+ * batches fed to rcn_hipx_train_step_dev with lr = lr_dev[i].  The values are not inspected: a non-finite rate is a caller error (it
+ * reaches the parameters), not a fault.
+ * aug (nullable): the gather in front of each step runs k_gather_aug with q = s * B + r for absolute batch s; labels are gathered as ever.
+ * lr_dev == NULL and aug == NULL: exactly rcn_hipx_train_epoch_dev -- the same launches, the same graph key.
+ * -1 (nothing enqueued, nothing changed): what rcn_hipx_train_epoch_dev refuses; aug->pad outside 0 .. 16 or >= min(H, W); aug->hflip
+ * not 0 / 1. */
+int  rcn_hipx_train_epoch_ex_dev(rcn_hipx_net* net, const void* X_dev, int x_kind, float x_scale, float x_shift, const int32_t* labels_dev, int64_t n,
+                                 const int32_t* perm_dev, int B, int64_t first_batch, int64_t n_batches, float lr, const float* lr_dev,
+                                 const rcn_hipx_augment* aug, float* loss_dev);
+/* The epoch's gather on its own (the piece a data-parallel epoch needs): rows idx_dev[0 .. B) (idx_dev == NULL: rows base .. base + B - 1,
+ * which must lie inside the set) of a resident set into x_out_dev ([B][H][W][C] fp32), widened as RCN_HIPX_X_U8 says, and -- when labels_dev
+ * and labels_out_dev are both given -- their labels into labels_out_dev.  aug (nullable): augmented, row r drawing with q = q0 + r.
+ * Enqueued on the net's stream; the net's own buffers and graphs are not touched.  Every index is clamped into [0, n) before it forms an
+ * address.  -1 (nothing enqueued): X_dev or x_out_dev NULL, an unknown x_kind, n < 1, B outside 1 .. max_batch, base < 0 or
+ * base + B > n without idx_dev, an aug that rcn_hipx_train_epoch_ex_dev refuses. */
+int  rcn_hipx_gather_batch_dev(rcn_hipx_net* net, const void* X_dev, int x_kind, float x_scale, float x_shift, const int32_t* labels_dev, int64_t n,
+                               const int32_t* idx_dev, int64_t base, int B, const rcn_hipx_augment* aug, uint64_t q0, float* x_out_dev,
+                               int32_t* labels_out_dev);
+/* the draw of position q (pure host code, no GPU: the function the kernel runs).  -1: aug NULL, pad outside 0 .. 16, hflip not 0 / 1.
+ * dy, dx, flip are nullable. */
+int  rcn_hipx_augment_draw(const rcn_hipx_augment* aug, uint64_t q, int* dy, int* dx, int* flip);
+/* What ONE step of such an epoch launches for an existing net at batch `batch` (no GPU needed): a line for the gather launch (kernel,
+ * stored type, elements per piece, workgroups, and the augmentation if any; the set and the batch buffer are taken to be 16-byte aligned,
+ * as allocators return them), a line for the 4-byte copy of the rate if lr_from_device, a line naming the graph's key, then
+ * rcn_hipx_plan_net's text -- with the _dlr update kernel if lr_from_device.  -1: net NULL, batch outside 1 .. max_batch, an unknown
+ * x_kind, lr_from_device not 0 / 1, an aug that rcn_hipx_train_epoch_ex_dev refuses (the reason in `out`). */
+int  rcn_hipx_plan_epoch_net(const rcn_hipx_net* net, int batch, int x_kind, int lr_from_device, const rcn_hipx_augment* aug, char* out, int cap);
 /* Forward pass + loss + arg-max over ALL n rows (any n >= 1: chunks of at most max_batch rows, a short last chunk included); no backward
  * pass, parameters untouched.  Enqueued on the net's stream, nothing blocks; results on the device:
  *     *loss_sum_dev (double) = sum over samples of -log softmax(logits)[label]
@@ -159,8 +213,9 @@ int  rcn_hipx_apply_dev(rcn_hipx_net* net, const float* grad_dev, float scale);
  * arguments as a net never configured.  Accepts 0 <= momentum < 1, a finite weight_decay >= 0 and nesterov 0 / 1 (1 needs momentum > 0);
  * anything else returns -1 and changes nothing.  The first nonzero momentum allocates the velocity buffer (zeroed).  Changing a value
  * synchronises the net's stream and drops its captured graphs.  The velocity survives rcn_hipx_set_params, rcn_hipx_init_params and
- * changes of precision, tiling, overlap or options (as a torch.optim.SGD state survives a load of the parameters); the learning rate
- * stays part of a captured graph's key, so a per-step schedule re-captures. */
+ * changes of precision, tiling, overlap or options (as a torch.optim.SGD state survives a load of the parameters).  A constant learning
+ * rate is part of a captured graph's key; a per-step schedule goes through rcn_hipx_train_epoch_ex_dev's lr_dev, whose one graph reads the
+ * rate from a device scalar. */
 int  rcn_hipx_set_sgd(rcn_hipx_net* net, float momentum, float weight_decay, int nesterov);
 int  rcn_hipx_get_sgd(const rcn_hipx_net* net, float* momentum, float* weight_decay, int* nesterov);
 /* the velocity in the logical layout of rcn_hipx_get_params / _set_params.  get: zeros while no velocity buffer exists; set: -6 while the

@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -17,6 +18,32 @@ KIND = {"conv": 0, "pool": 1, "dense_relu": 2, "dense": 3}
 
 class XLayer(C.Structure):
     _fields_ = [("kind", C.c_int32), ("out", C.c_int32)]
+
+
+class AugmentStruct(C.Structure):
+    """rcn_hipx_augment"""
+    _fields_ = [("pad", C.c_int32), ("hflip", C.c_int32), ("seed", C.c_uint64), ("epoch", C.c_uint64)]
+
+
+@dataclass(frozen=True)
+class Augment:
+    """Random crop with zero padding (dy, dx in [-pad, pad]) and a horizontal flip with probability 1/2, drawn per sample from
+    (seed, epoch, position in the epoch): include/rcn_hipx.h, rcn_hipx_augment.  A new `epoch` value gives new draws."""
+    pad: int = 4
+    hflip: bool = True
+    seed: int = 0
+    epoch: int = 0
+
+    def struct(self) -> AugmentStruct:
+        return AugmentStruct(int(self.pad), int(bool(self.hflip)), int(self.seed) & (2 ** 64 - 1), int(self.epoch) & (2 ** 64 - 1))
+
+
+def _aug_ref(augment: Optional[Augment]):
+    """(ctypes struct kept alive by the caller, pointer or None)"""
+    if augment is None:
+        return None, None
+    a = augment.struct()
+    return a, C.byref(a)
 
 
 _vp, _i = C.c_void_p, C.c_int
@@ -53,6 +80,10 @@ SIGNATURES = {
     "rcn_hipx_reset_velocity": (_i, [_vp]),
     "rcn_hipx_apply_sgd_dev": (_i, [_vp, _vp, C.c_float, C.c_float]),
     "rcn_hipx_train_epoch_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _vp, _i, C.c_int64, C.c_int64, C.c_float, _vp]),
+    "rcn_hipx_train_epoch_ex_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _vp, _i, C.c_int64, C.c_int64, C.c_float, _vp, C.POINTER(AugmentStruct), _vp]),
+    "rcn_hipx_gather_batch_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _vp, C.c_int64, _i, C.POINTER(AugmentStruct), C.c_uint64, _vp, _vp]),
+    "rcn_hipx_augment_draw": (_i, [C.POINTER(AugmentStruct), C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rcn_hipx_plan_epoch_net": (_i, [_vp, _i, _i, _i, C.POINTER(AugmentStruct), C.c_char_p, _i]),
     "rcn_hipx_evaluate_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _vp, _vp, _vp]),
     "rcn_hipx_graphs_instantiated": (_i, [_vp, C.POINTER(C.c_int64)]),
     "rcn_hipx_plan_eval": (_i, [_i, _i, _i, C.POINTER(XLayer), _i, _i, _i, _i, C.c_char_p, _i]),
@@ -121,6 +152,34 @@ def plan_eval(in_shape: Tuple[int, int, int], layers: Sequence[tuple], batch: in
 
 
 X_KIND = {"float32": 0, "uint8": 1}      # RCN_HIPX_X_F32 / RCN_HIPX_X_U8, by the set's torch dtype
+
+
+def augment_draws(aug: Augment, q0: int, count: int) -> np.ndarray:
+    """The (dy, dx, flip) draws of positions q0 .. q0 + count - 1 as an int array [count, 3], from rcn_hipx_augment_draw: the host side
+    of the one function the gather kernel runs.  Needs no GPU."""
+    lib = load()
+    a = aug.struct()
+    out = np.zeros((int(count), 3), dtype=np.int64)
+    dy, dx, fl = C.c_int(), C.c_int(), C.c_int()
+    for k in range(int(count)):
+        if lib.rcn_hipx_augment_draw(C.byref(a), (int(q0) + k) & (2 ** 64 - 1), C.byref(dy), C.byref(dx), C.byref(fl)) != 0:
+            raise ConvNetError(f"rcn_hipx_augment_draw refuses {aug}")
+        out[k] = (dy.value, dx.value, fl.value)
+    return out
+
+
+def warmup_cosine(n_steps: int, peak: float, warmup_steps: int, floor: float = 0.0) -> np.ndarray:
+    """A learning-rate schedule of n_steps float32 values, computed in float64: linear from peak / warmup_steps to peak over the first
+    warmup_steps steps, then floor + (peak - floor) * 0.5 * (1 + cos(pi * t)) with t running from 0 to 1 over the remaining steps."""
+    n_steps, warmup_steps = int(n_steps), int(warmup_steps)
+    if n_steps < 1 or not 0 <= warmup_steps <= n_steps:
+        raise ValueError("warmup_cosine: n_steps >= 1 and 0 <= warmup_steps <= n_steps")
+    lr = np.empty(n_steps, dtype=np.float64)
+    lr[:warmup_steps] = float(peak) * np.arange(1, warmup_steps + 1, dtype=np.float64) / max(warmup_steps, 1)
+    rest = n_steps - warmup_steps
+    t = np.arange(rest, dtype=np.float64) / max(rest - 1, 1)
+    lr[warmup_steps:] = float(floor) + (float(peak) - float(floor)) * 0.5 * (1.0 + np.cos(np.pi * t))
+    return lr.astype(np.float32)
 
 
 class ConvNet:
@@ -243,14 +302,17 @@ class ConvNet:
                 raise ValueError("labels: a contiguous int32 tensor on the net's device, one per row of the set")
         return kind, int(X.shape[0])
 
-    def train_epoch(self, X, labels, perm, B: int, lr: float, n_batches: Optional[int] = None, first_batch: int = 0, losses=None,
-                    x_scale: float = 1.0 / 255.0, x_shift: float = 0.0):
+    def train_epoch(self, X, labels, perm, B: int, lr, n_batches: Optional[int] = None, first_batch: int = 0, losses=None,
+                    x_scale: float = 1.0 / 255.0, x_shift: float = 0.0, augment: Optional[Augment] = None):
         """n_batches training steps over a device-resident set (rcn_hipx_train_epoch_dev): batch s is rows perm[s*B : (s+1)*B] (perm None:
         rows in order), gathered on the device into the net's own batch buffer, then the step of train_step -- bit-identical to it, and ONE
         captured graph per (B, lr) whatever X, perm, first_batch and losses are.  X: torch.float32 or torch.uint8 [n, H, W, C] (uint8 rows
         become fl(fl(u8 * x_scale) + x_shift); both are ignored for float32); perm: int32 device tensor with entries in [0, n) (checked here,
         once per call: one device reduction, which synchronises) or None; n_batches defaults to n // B - first_batch; losses (optional):
-        float32 device tensor of at least n_batches elements, losses[i] = mean loss of the call's i-th step before its update."""
+        float32 device tensor of at least n_batches elements, losses[i] = mean loss of the call's i-th step before its update.
+        lr: a float, or a contiguous float32 device tensor of at least n_batches elements -- lr[i] is the rate of the call's i-th step
+        (rcn_hipx_train_epoch_ex_dev: ONE graph per B whatever the schedule; checked finite here, once per call, which synchronises).
+        augment: an Augment -- every batch is gathered through its random crop and flip, drawn from (seed, epoch, s*B + r)."""
         t = self.torch
         kind, n = self._resident_set(X, labels)
         if labels is None:
@@ -269,9 +331,53 @@ class ConvNet:
         if losses is not None:
             if losses.dtype != t.float32 or losses.device != self.device or not losses.is_contiguous() or losses.numel() < n_batches:
                 raise ValueError("losses: a contiguous float32 tensor on the net's device with at least n_batches elements")
-        self._ck(self.lib.rcn_hipx_train_epoch_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift), C.c_void_p(labels.data_ptr()), n,
-                                                   C.c_void_p(perm.data_ptr()) if perm is not None else None, B, first_batch, n_batches, float(lr),
-                                                   C.c_void_p(losses.data_ptr()) if losses is not None else None))
+        lr_dev = None
+        if t.is_tensor(lr):
+            if lr.dtype != t.float32 or lr.dim() != 1 or lr.device != self.device or not lr.is_contiguous() or lr.numel() < n_batches:
+                raise ValueError("lr: a float, or a contiguous one-dimensional float32 tensor on the net's device with at least n_batches elements")
+            if n_batches > 0 and not bool(t.isfinite(lr[:n_batches]).all()):
+                raise ValueError("lr: the schedule holds a value that is not finite")
+            lr_dev, lr = C.c_void_p(lr.data_ptr()), 0.0
+        if lr_dev is None and augment is None:
+            self._ck(self.lib.rcn_hipx_train_epoch_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift), C.c_void_p(labels.data_ptr()), n,
+                                                       C.c_void_p(perm.data_ptr()) if perm is not None else None, B, first_batch, n_batches, float(lr),
+                                                       C.c_void_p(losses.data_ptr()) if losses is not None else None))
+            return
+        keep, aug = _aug_ref(augment)
+        self._ck(self.lib.rcn_hipx_train_epoch_ex_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift), C.c_void_p(labels.data_ptr()), n,
+                                                      C.c_void_p(perm.data_ptr()) if perm is not None else None, B, first_batch, n_batches, float(lr), lr_dev, aug,
+                                                      C.c_void_p(losses.data_ptr()) if losses is not None else None))
+
+    def gather_batch(self, X, labels, idx, B: int, base: int = 0, augment: Optional[Augment] = None, q0: int = 0,
+                     x_scale: float = 1.0 / 255.0, x_shift: float = 0.0):
+        """One batch as train_epoch gathers it (rcn_hipx_gather_batch_dev): rows idx[0 : B] (idx None: rows base .. base + B - 1) of a
+        resident set as a float32 [B, H, W, C] tensor, and their labels (None without labels), enqueued on the net's stream.  augment: row r
+        draws with position q0 + r (train_epoch's batch s has q0 = s * B)."""
+        t = self.torch
+        kind, n = self._resident_set(X, labels)
+        B = int(B)
+        if idx is not None:
+            if idx.dtype != t.int32 or idx.dim() != 1 or idx.device != self.device or not idx.is_contiguous() or idx.numel() < B:
+                raise ValueError("idx: a contiguous one-dimensional int32 tensor on the net's device with at least B entries")
+        with t.cuda.stream(self.stream):
+            x = t.empty((max(B, 0),) + self.in_shape, dtype=t.float32, device=self.device)
+            y = t.empty(max(B, 0), dtype=t.int32, device=self.device) if labels is not None else None
+        keep, aug = _aug_ref(augment)
+        self._ck(self.lib.rcn_hipx_gather_batch_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift),
+                                                    C.c_void_p(labels.data_ptr()) if labels is not None else None, n,
+                                                    C.c_void_p(idx.data_ptr()) if idx is not None else None, int(base), B, aug, int(q0) & (2 ** 64 - 1),
+                                                    C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None))
+        return x, y
+
+    def plan_epoch_of_this_net(self, batch: int, x_dtype: str = "uint8", lr_from_device: bool = False, augment: Optional[Augment] = None) -> str:
+        """What one step of train_epoch launches for THIS net (rcn_hipx_plan_epoch_net): the gather, the copy of a scheduled rate, the
+        graph's key, then plan_of_this_net's text.  x_dtype: "uint8" or "float32", the set's storage."""
+        buf = C.create_string_buffer(1 << 16)
+        keep, aug = _aug_ref(augment)
+        st = self.lib.rcn_hipx_plan_epoch_net(self.net, int(batch), X_KIND[x_dtype], int(bool(lr_from_device)), aug, buf, len(buf))
+        if st != 0:
+            raise ConvNetError(f"rcn_hipx_plan_epoch_net: {st}: {buf.value.decode()}")
+        return buf.value.decode()
 
     def evaluate_async(self, X, labels=None, x_scale: float = 1.0 / 255.0, x_shift: float = 0.0, want_pred: bool = True):
         """Forward pass, loss and arg-max over ALL rows of a resident set (rcn_hipx_evaluate_dev), enqueued on the net's stream: returns the

@@ -485,6 +485,7 @@ __host__ __device__ inline int reduce_job_elems(int chunks) { return 4 * kReduce
 
 // The reduction itself, shared by k_reduce_all (plain SGD) and k_reduce_all_sgd (convnet_sgd.hpp: momentum, weight decay, Nesterov).
 // `update(J, jb, i, t)` returns the four new parameters [i, i + 4) of job jb from their summed gradient t; it may keep state of its own.
+// Of J an update functor may read ONLY J.lr (the job is its jb): DeviceLr below hands it a ReduceJobs in which nothing else is set.
 template <class Update>
 __device__ __forceinline__ void reduce_all_body(const ReduceJobs& J, const Update& update) {
     __shared__ f32x4 red[kReduceThreads];
@@ -537,6 +538,21 @@ struct PlainUpdate {
 };
 
 __global__ __launch_bounds__(kReduceThreads) void k_reduce_all(ReduceJobs J) { reduce_all_body(J, PlainUpdate{}); }
+// The same launch with the learning rate read from a device scalar (one uniform load): the step of a per-step schedule
+// (rcn_hipx_train_epoch_ex_dev with lr_dev), whose captured graph then does not depend on the rate.  The update functors read the rate
+// as J.lr, and J is the kernel's argument: writing J.lr would copy all of ReduceJobs into scratch (measured: 1048 bytes per lane, the job
+// table being indexed at run time).  DeviceLr instead hands the wrapped functor a ReduceJobs of which only lr is set and only lr is
+// read -- it folds to one register -- so reduce_all_body, its argument and the functors stay as they are and nothing spills.
+template <class Update> struct DeviceLr {
+    Update u;
+    float lr;
+    __device__ __forceinline__ f32x4 operator()(const ReduceJobs&, const ReduceJob& jb, long long i, const f32x4& t) const {
+        ReduceJobs K;
+        K.lr = lr;
+        return u(K, jb, i, t);
+    }
+};
+__global__ __launch_bounds__(kReduceThreads) void k_reduce_all_dlr(ReduceJobs J, const float* __restrict__ lr) { reduce_all_body(J, DeviceLr<PlainUpdate>{PlainUpdate{}, *lr}); }
 
 // db[co] = sum_m dZ[m][co]: one workgroup per 32-column block, rows strided over threads, fixed-order tree
 __global__ __launch_bounds__(256) void k_bias_grad(const float* __restrict__ dZ, long long M, int Cout, float* __restrict__ b, float* __restrict__ grad_out,

@@ -1,9 +1,12 @@
-// convnet_epoch.hpp -- Track X: the loop around the training step (rcn_hipx_train_epoch_dev, rcn_hipx_evaluate_dev).  No reference
-// counterpart; the main track's counterparts are rcn_hip_shuffle_dev / rcn_hip_evaluate*.
+// convnet_epoch.hpp -- Track X: the loop around the training step (rcn_hipx_train_epoch_dev / _ex_dev, rcn_hipx_gather_batch_dev,
+// rcn_hipx_evaluate_dev).  No reference counterpart; the main track's counterparts are rcn_hip_shuffle_dev / rcn_hip_evaluate*.
 //
 //   k_gather_rows<TS, VEC>  rows of a device-resident set (fp32 or uint8), selected by an int32 index row, into the net's contiguous
 //                           fp32 batch buffer, and their labels into its int32 labels buffer.  Every index is clamped into [0, n)
 //                           before it forms an address.
+//   k_gather_aug<TS, VEC>   the same rows through a random translation with zero padding and a horizontal flip (rcn_hipx_augment): the
+//                           sample's draw is computed from its position in the epoch in registers; element by element on the read side,
+//                           16-byte stores on the write side.
 //   k_eval_ce               soft-max cross-entropy, first-maximum arg-max and correct count of one chunk of logits, without d logits;
 //                           its last-arriving workgroup ADDS the chunk's totals into a double / int64 pair.
 #pragma once
@@ -93,6 +96,88 @@ inline long long gather_blocks(int B, int E, int vec) {
     const long long S = (E / vec + 63) / 64, waves = ((long long)B * S + kGatherSlots - 1) / kGatherSlots;
     if ((long long)B * S >= (1ll << 31) - kGatherSlots * (kGatherThreads / 64)) return 0;
     return (waves + kGatherThreads / 64 - 1) / (kGatherThreads / 64);
+}
+
+// ---- augmentation: random crop with zero padding, horizontal flip (rcn_hipx_augment) ---------------------------------------------------
+struct AugSpec { unsigned long long seed, epoch; int pad, hflip; };
+struct AugDraw { int dy, dx, flip; };
+
+// The draw of the sample at absolute position q of the epoch: one splitmix64 output of a counter, nothing kept in memory, so the kernel
+// and rcn_hipx_augment_draw (host) share this one function and splitting an epoch into calls changes nothing.  All arithmetic wraps in
+// uint64.  dy and dx take 16 bits each through a multiply-shift, (bits * (2 pad + 1)) >> 16: of the 65536 inputs each of the 2 pad + 1
+// outcomes gets floor or ceil of 65536 / (2 pad + 1), so an outcome's probability is off by less than 1 / 65536 and the ratio of two
+// outcomes' probabilities by less than (2 pad + 1) / 65536 (pad <= 16: 5e-4).  flip is bit 32.
+__host__ __device__ inline AugDraw augment_draw(const AugSpec& a, unsigned long long q) {
+    unsigned long long z = a.seed ^ (a.epoch * 0xD1342543DE82EF95ull);
+    z += (q + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    const unsigned span = 2u * (unsigned)a.pad + 1u;
+    AugDraw d;
+    d.dy = (int)((((unsigned)z & 0xffffu) * span) >> 16) - a.pad;
+    d.dx = (int)((((unsigned)(z >> 16) & 0xffffu) * span) >> 16) - a.pad;
+    d.flip = a.hflip ? (int)((z >> 32) & 1u) : 0;
+    return d;
+}
+
+// dst[r][h][w][c] = widen(S(h + dy, (flip ? W - 1 - w : w) + dx, c)) for r < B, where S is the stored value of row(r) of the set -- the
+// stored value 0 outside the image -- (dy, dx, flip) = augment_draw(aug, q0 + r) and row(r) is k_gather_rows' clamped row; labels as there.
+// This is a crop of the image padded with `pad` zeros on every side, then a mirror (torchvision: RandomCrop(padding = pad), then
+// RandomHorizontalFlip).  One thread per VEC consecutive outputs of a row (VEC = 4: one 16-byte store, the host checks E % 4 == 0 and the
+// destination's alignment; VEC = 1 otherwise): for each it decodes (h, w, c), loads ONE source element -- a shifted, mirrored NHWC row of 1
+// or 3 channels has no 16-byte pieces to move -- or takes the stored 0, and widens it.  The write side (4 bytes per element, 4x the read
+// side of a uint8 set) is fully coalesced; the source batch is a few MB read once.  No address is formed from a coordinate outside the
+// image.  total = B * (E / VEC) threads (gather_aug_blocks).
+template <typename TS, int VEC>
+__global__ __launch_bounds__(kGatherThreads) void k_gather_aug(const TS* __restrict__ X, const int* __restrict__ labels, long long n, const int* __restrict__ idx, long long base,
+                                                               int B, int H, int W, int C, RowScale rs, AugSpec aug, unsigned long long q0, float* __restrict__ dst,
+                                                               int* __restrict__ labels_out) {
+    const int E = H * W * C, P = E / VEC;               // pieces per row
+    const long long g = (long long)blockIdx.x * kGatherThreads + threadIdx.x;
+    if (g >= (long long)B * P) return;
+    const int r = (int)(g / P), piece = (int)(g - (long long)r * P);
+    long long row = idx ? (long long)idx[r] : base + r;
+    row = row < 0 ? 0 : (row >= n ? n - 1 : row);       // as in k_gather_rows: an index out of range must not become an address
+    if (labels && piece == 0) labels_out[r] = labels[row];
+    const AugDraw d = augment_draw(aug, q0 + (unsigned long long)r);
+    const TS* __restrict__ src = X + row * E;
+    float o[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        const int e = piece * VEC + k;
+        const int hw = e / C, c = e - hw * C;
+        const int h = hw / W, w = hw - h * W;
+        const int sh = h + d.dy, sw = (d.flip ? W - 1 - w : w) + d.dx;
+        TS v = (TS)0;
+        if (sh >= 0 && sh < H && sw >= 0 && sw < W) v = src[(sh * W + sw) * C + c];
+        o[k] = RowPiece<TS>::widen1(v, rs);
+    }
+    float* const out = dst + (long long)r * E + (long long)piece * VEC;
+    if constexpr (VEC == 4) *reinterpret_cast<f32x4*>(out) = f32x4{o[0], o[1], o[2], o[3]};
+    else out[0] = o[0];
+}
+
+// workgroups of k_gather_aug; 0: more than a 32-bit grid counts
+inline long long gather_aug_blocks(int B, int E, int vec) {
+    const long long blocks = ((long long)B * (E / vec) + kGatherThreads - 1) / kGatherThreads;
+    return blocks >= (1ll << 31) ? 0 : blocks;
+}
+
+// Which gather launch a batch gets.  Un-augmented: k_gather_rows, 16-byte pieces where every row starts on a 16-byte boundary and is a
+// whole number of them, element by element otherwise.  Augmented: k_gather_aug, 16-byte stores where a row is a whole number of them.
+struct GatherChoice { bool aug, u8; int vec; long long blocks; };
+inline GatherChoice select_gather(bool u8, int B, int E, bool src_aligned16, bool dst_aligned16, bool aug) {
+    GatherChoice c{aug, u8, 1, 0};
+    if (aug) {
+        c.vec = (E % 4 == 0 && dst_aligned16) ? 4 : 1;
+        c.blocks = gather_aug_blocks(B, E, c.vec);
+        return c;
+    }
+    const int piece = u8 ? RowPiece<uint8_t>::kVec : RowPiece<float>::kVec;
+    c.vec = (E % piece == 0 && src_aligned16 && dst_aligned16) ? piece : 1;
+    c.blocks = gather_blocks(B, E, c.vec);
+    return c;
 }
 
 constexpr int kEvalSamples = 8;        // samples per 256-thread workgroup of k_eval_ce (k_softmax_ce's grouping)

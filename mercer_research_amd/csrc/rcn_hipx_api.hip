@@ -91,6 +91,10 @@ struct rcn_hipx_net : Selection {
     // serves every batch of every epoch, whatever set, permutation and loss slots the caller passes.
     Buf xb, yb, eloss;
     std::map<std::pair<int, float>, hipGraphExec_t> epoch_graphs;
+    // a per-step schedule (rcn_hipx_train_epoch_ex_dev with lr_dev): the rate of the step lives in this 4-byte scalar, allocated once and
+    // never moved, the update launch reads it (k_reduce_all_dlr), and ONE graph per B serves every schedule
+    Buf elr;
+    std::map<int, hipGraphExec_t> epoch_graphs_dlr;
     Buf eval_part;                          // k_eval_ce: [loss partials][correct partials][counter: zero between launches]
     long long n_instantiated = 0;           // hipGraphs instantiated since the net was created (rcn_hipx_graphs_instantiated)
     bool walk_open = false;                 // between rcn_hipx_gradients_begin_dev and its last bucket: the activations belong to that walk
@@ -482,22 +486,25 @@ int reduce_slab(rcn_hipx_net* n, size_t i, int chunks, int ks, const ConvShape& 
 bool sgd_default(const rcn_hipx_net* n) { return n->sgd_mu == 0.f && n->sgd_wd == 0.f && !n->sgd_nesterov; }
 SgdParams sgd_params(const rcn_hipx_net* n) { return SgdParams{(float*)n->vel.p, (const float*)n->params.p, n->sgd_mu, n->sgd_wd, n->sgd_nesterov}; }
 
-int run_reduce_jobs(rcn_hipx_net* n, float lr, bool apply) {
+// lr_dev (nullable): the update reads its rate from this device scalar instead of `lr` (the _dlr kernels; same arithmetic on the same float)
+int run_reduce_jobs(rcn_hipx_net* n, float lr, bool apply, const float* lr_dev = nullptr) {
     if (!n->jobs.njobs) return 0;
     const ReduceJob& last = n->jobs.j[n->jobs.njobs - 1];
     const long long blocks = last.first_block + (last.n + reduce_job_elems(last.chunks) - 1) / reduce_job_elems(last.chunks);
     n->jobs.lr = lr; n->jobs.apply = apply ? 1 : 0;
     if (apply && !sgd_default(n)) {
         // the net's optimiser in the same launch (convnet_sgd.hpp); gradients-only walks never get here
-        if (dry_note(n, "  update: k_reduce_all_sgd, %d layers' slabs in one launch, %lld workgroups (SGD: momentum %g, weight decay %g, nesterov %s)",
+        if (dry_note(n, "  update: k_reduce_all_sgd%s, %d layers' slabs in one launch, %lld workgroups (SGD: momentum %g, weight decay %g, nesterov %s)", lr_dev ? "_dlr" : "",
                      n->jobs.njobs, blocks, (double)n->sgd_mu, (double)n->sgd_wd, n->sgd_nesterov ? "on" : "off")) { n->jobs.njobs = 0; return 0; }
-        hipLaunchKernelGGL(k_reduce_all_sgd, dim3((unsigned)blocks), dim3(kReduceThreads), 0, n->stream, n->jobs, sgd_params(n));
+        if (lr_dev) hipLaunchKernelGGL(k_reduce_all_sgd_dlr, dim3((unsigned)blocks), dim3(kReduceThreads), 0, n->stream, n->jobs, sgd_params(n), lr_dev);
+        else hipLaunchKernelGGL(k_reduce_all_sgd, dim3((unsigned)blocks), dim3(kReduceThreads), 0, n->stream, n->jobs, sgd_params(n));
         XTRY(n, hipGetLastError());
         n->jobs.njobs = 0;
         return 0;
     }
-    if (dry_note(n, "  update: k_reduce_all, %d layers' slabs in one launch, %lld workgroups", n->jobs.njobs, blocks)) { n->jobs.njobs = 0; return 0; }
-    hipLaunchKernelGGL(k_reduce_all, dim3((unsigned)blocks), dim3(kReduceThreads), 0, n->stream, n->jobs);
+    if (dry_note(n, "  update: k_reduce_all%s, %d layers' slabs in one launch, %lld workgroups", apply && lr_dev ? "_dlr" : "", n->jobs.njobs, blocks)) { n->jobs.njobs = 0; return 0; }
+    if (apply && lr_dev) hipLaunchKernelGGL(k_reduce_all_dlr, dim3((unsigned)blocks), dim3(kReduceThreads), 0, n->stream, n->jobs, lr_dev);
+    else hipLaunchKernelGGL(k_reduce_all, dim3((unsigned)blocks), dim3(kReduceThreads), 0, n->stream, n->jobs);
     XTRY(n, hipGetLastError());
     n->jobs.njobs = 0;
     return 0;
@@ -589,11 +596,11 @@ void backward_reset(rcn_hipx_net* n, int first, bool first_gated) {
     n->ev_next = 0;
 }
 
-int backward(rcn_hipx_net* n, const float* x, int B, float lr, float* grad, bool apply, int first, bool first_gated) {
+int backward(rcn_hipx_net* n, const float* x, int B, float lr, float* grad, bool apply, int first, bool first_gated, const float* lr_dev = nullptr) {
     backward_reset(n, first, first_gated);
     RTRY(backward_layers(n, x, B, lr, grad, apply, first, 0, true));
     if (n->bw.side_busy) RTRY(stream_after(n, n->side, n->stream));   // join: the step's next kernels (and an end of capture) find everything on the main stream
-    return run_reduce_jobs(n, lr, apply);                             // every layer's slab in one launch; no weight was written before this point
+    return run_reduce_jobs(n, lr, apply, lr_dev);                     // every layer's slab in one launch; no weight was written before this point
 }
 
 // [partial sums of the loss, one per workgroup][counter of finished workgroups: zero between launches]
@@ -688,16 +695,17 @@ int step_front(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, fl
 }
 
 // forward + loss + backward of one batch: parameters updated in place (apply) or gradients written to grad (padded layout)
-int step_core(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float lr, float* grad, bool apply, float* loss_dev) {
+// (lr_dev, nullable: the update's rate comes from that device scalar instead of lr)
+int step_core(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float lr, float* grad, bool apply, float* loss_dev, const float* lr_dev = nullptr) {
     int first = 0;
     bool gated = false;
     RTRY(step_front(n, x, labels, B, grad, apply, loss_dev, &first, &gated));
-    return backward(n, x, B, lr, grad, apply, first, gated);
+    return backward(n, x, B, lr, grad, apply, first, gated, lr_dev);
 }
 
 template <typename M> void drop_all(M& graphs) { for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second); graphs.clear(); }
 // every captured graph of the net: the steps on callers' pointers and the epoch's steps on the net's own batch buffer
-void drop_graphs(rcn_hipx_net* n) { drop_all(n->graphs); drop_all(n->epoch_graphs); }
+void drop_graphs(rcn_hipx_net* n) { drop_all(n->graphs); drop_all(n->epoch_graphs); drop_all(n->epoch_graphs_dlr); }
 
 // ---- gradient buckets: the data-parallel step with its all-reduce overlapped with the backward pass -------------------------------------
 // The layers with parameters, walked from the last to the first (the order the backward pass finishes them), are cut into buckets of at
@@ -878,7 +886,7 @@ void rcn_hipx_destroy(rcn_hipx_net* n) {
         if (n->stream) (void)hipStreamSynchronize(n->stream);
         drop_graphs(n);
         for (Layer& l : n->L) { l.out.release(); l.idx.release(); l.dout.release(); l.slab.release(); }
-        for (Buf* b : {&n->params, &n->wt, &n->wb16, &n->dz, &n->loss_part, &n->grad_tmp, &n->dlogits, &n->skbuf, &n->wb, &n->vel, &n->xb, &n->yb, &n->eloss, &n->eval_part}) b->release();
+        for (Buf* b : {&n->params, &n->wt, &n->wb16, &n->dz, &n->loss_part, &n->grad_tmp, &n->dlogits, &n->skbuf, &n->wb, &n->vel, &n->xb, &n->yb, &n->eloss, &n->elr, &n->eval_part}) b->release();
         if (n->side) { (void)hipStreamSynchronize(n->side); (void)hipStreamDestroy(n->side); }
         for (hipEvent_t e : n->events) (void)hipEventDestroy(e);
         if (n->own_stream && n->stream) (void)hipStreamDestroy(n->stream);
@@ -1004,11 +1012,11 @@ int rcn_hipx_forward_dev(rcn_hipx_net* n, const float* x, int B, float* logits) 
 
 // One eager step (it sizes every scratch buffer outside capture: hipMalloc is illegal while capturing -- and it IS the caller's step),
 // then the same step captured and instantiated for the replays that follow.
-static int step_and_capture(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float lr, float* loss_dev, hipGraphExec_t* exec_out) {
-    RTRY(step_core(n, x, labels, B, lr, nullptr, true, loss_dev));
+static int step_and_capture(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float lr, float* loss_dev, hipGraphExec_t* exec_out, const float* lr_dev = nullptr) {
+    RTRY(step_core(n, x, labels, B, lr, nullptr, true, loss_dev, lr_dev));
     hipGraph_t graph = nullptr;
     XTRY(n, hipStreamBeginCapture(n->stream, hipStreamCaptureModeThreadLocal));
-    const int st = step_core(n, x, labels, B, lr, nullptr, true, loss_dev);
+    const int st = step_core(n, x, labels, B, lr, nullptr, true, loss_dev, lr_dev);
     hipError_t e = hipStreamEndCapture(n->stream, &graph);
     if (st != 0) { if (graph) (void)hipGraphDestroy(graph); return st; }
     XTRY(n, e);
@@ -1050,27 +1058,50 @@ int ensure_epoch_bufs(rcn_hipx_net* n) {
     XTRY(n, n->xb.ensure((size_t)n->max_batch * row_elems(n) * sizeof(float)));
     XTRY(n, n->yb.ensure((size_t)n->max_batch * sizeof(int32_t)));
     XTRY(n, n->eloss.ensure(sizeof(float)));
+    XTRY(n, n->elr.ensure(sizeof(float)));
     return 0;
 }
 
-// rows idx[0 .. B) (idx == NULL: base .. base + B - 1) of the set into the net's batch buffer, their labels (nullable) into its labels buffer
-int launch_gather(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, long long rows, const int32_t* idx, long long base, int B) {
+// nullptr, or why this rcn_hipx_augment is refused for a net of this input shape (H = W = 0: the shape-free part, for the host draw)
+const char* augment_refusal(const rcn_hipx_augment* a, int H, int W) {
+    if (a->pad < 0 || a->pad > 16) return "augment: pad must be in 0 .. 16";
+    if (H > 0 && a->pad >= (H < W ? H : W)) return "augment: pad must be smaller than the image's height and width";
+    if (a->hflip != 0 && a->hflip != 1) return "augment: hflip must be 0 or 1";
+    return nullptr;
+}
+
+// rows idx[0 .. B) (idx == NULL: base .. base + B - 1) of the set into dst ([B][row] fp32), their labels (nullable) into ydst; aug
+// (nullable): through the augmentation, row r drawing with q0 + r.  The launch is select_gather's (convnet_epoch.hpp).
+int launch_gather(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, long long rows, const int32_t* idx, long long base, int B,
+                  const rcn_hipx_augment* aug, unsigned long long q0, float* dst, int* ydst) {
     const int E = (int)row_elems(n);
     const RowScale rs{x_scale, x_shift};
-    float* const dst = (float*)n->xb.p;
-    int* const ydst = (int*)n->yb.p;
-    if (!gather_blocks(B, E, 1)) return fail(n, -3, "a batch of more than 2^37 elements");
-    // 16-byte pieces where every row starts on a 16-byte boundary and is a whole number of them; element by element otherwise
-    if (x_kind == RCN_HIPX_X_U8) {
-        const bool vec = E % RowPiece<uint8_t>::kVec == 0 && (uintptr_t)X % 16 == 0;
-        if (vec) hipLaunchKernelGGL((k_gather_rows<uint8_t, RowPiece<uint8_t>::kVec>), dim3((unsigned)gather_blocks(B, E, RowPiece<uint8_t>::kVec)), dim3(kGatherThreads), 0, n->stream,
-                                    (const uint8_t*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
-        else hipLaunchKernelGGL((k_gather_rows<uint8_t, 1>), dim3((unsigned)gather_blocks(B, E, 1)), dim3(kGatherThreads), 0, n->stream, (const uint8_t*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
+    const bool u8 = x_kind == RCN_HIPX_X_U8;
+    const bool dry = n->dry;                            // (a plan: the set and the batch buffer are taken to be aligned, as allocators return them)
+    const GatherChoice c = select_gather(u8, B, E, dry || (uintptr_t)X % 16 == 0, dry || (uintptr_t)dst % 16 == 0, aug != nullptr);
+    if (!c.blocks) return fail(n, -3, "a batch of more than 2^37 elements");
+    if (aug) {
+        if (dry_note(n, "  gather: k_gather_aug<%s, %d>, %s, %lld workgroups, augment pad %d hflip %d", u8 ? "uint8" : "float", c.vec,
+                     c.vec == 4 ? "one source element per output, 16-byte stores" : "element by element", c.blocks, (int)aug->pad, (int)aug->hflip)) return 0;
+        const AugSpec as{aug->seed, aug->epoch, aug->pad, aug->hflip};
+        const dim3 grid((unsigned)c.blocks), block(kGatherThreads);
+        const int H = n->in_h, W = n->in_w, Cc = n->in_c;
+        if (u8 && c.vec == 4) hipLaunchKernelGGL((k_gather_aug<uint8_t, 4>), grid, block, 0, n->stream, (const uint8_t*)X, labels, rows, idx, base, B, H, W, Cc, rs, as, q0, dst, ydst);
+        else if (u8) hipLaunchKernelGGL((k_gather_aug<uint8_t, 1>), grid, block, 0, n->stream, (const uint8_t*)X, labels, rows, idx, base, B, H, W, Cc, rs, as, q0, dst, ydst);
+        else if (c.vec == 4) hipLaunchKernelGGL((k_gather_aug<float, 4>), grid, block, 0, n->stream, (const float*)X, labels, rows, idx, base, B, H, W, Cc, rs, as, q0, dst, ydst);
+        else hipLaunchKernelGGL((k_gather_aug<float, 1>), grid, block, 0, n->stream, (const float*)X, labels, rows, idx, base, B, H, W, Cc, rs, as, q0, dst, ydst);
+        XTRY(n, hipGetLastError());
+        return 0;
+    }
+    if (dry_note(n, "  gather: k_gather_rows<%s, %d>, %s, %lld workgroups", u8 ? "uint8" : "float", c.vec, c.vec > 1 ? "16-byte loads and stores" : "element by element", c.blocks)) return 0;
+    if (u8) {
+        if (c.vec > 1) hipLaunchKernelGGL((k_gather_rows<uint8_t, RowPiece<uint8_t>::kVec>), dim3((unsigned)c.blocks), dim3(kGatherThreads), 0, n->stream,
+                                          (const uint8_t*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
+        else hipLaunchKernelGGL((k_gather_rows<uint8_t, 1>), dim3((unsigned)c.blocks), dim3(kGatherThreads), 0, n->stream, (const uint8_t*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
     } else {
-        const bool vec = E % RowPiece<float>::kVec == 0 && (uintptr_t)X % 16 == 0;
-        if (vec) hipLaunchKernelGGL((k_gather_rows<float, RowPiece<float>::kVec>), dim3((unsigned)gather_blocks(B, E, RowPiece<float>::kVec)), dim3(kGatherThreads), 0, n->stream,
-                                    (const float*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
-        else hipLaunchKernelGGL((k_gather_rows<float, 1>), dim3((unsigned)gather_blocks(B, E, 1)), dim3(kGatherThreads), 0, n->stream, (const float*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
+        if (c.vec > 1) hipLaunchKernelGGL((k_gather_rows<float, RowPiece<float>::kVec>), dim3((unsigned)c.blocks), dim3(kGatherThreads), 0, n->stream,
+                                          (const float*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
+        else hipLaunchKernelGGL((k_gather_rows<float, 1>), dim3((unsigned)c.blocks), dim3(kGatherThreads), 0, n->stream, (const float*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
     }
     XTRY(n, hipGetLastError());
     return 0;
@@ -1107,36 +1138,81 @@ int plan_eval_walk(rcn_hipx_net& net, int batch) {
 
 }  // namespace
 
-int rcn_hipx_train_epoch_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows, const int32_t* perm,
-                             int B, int64_t first_batch, int64_t n_batches, float lr, float* loss_dev) {
+int rcn_hipx_train_epoch_ex_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows, const int32_t* perm,
+                                int B, int64_t first_batch, int64_t n_batches, float lr, const float* lr_dev, const rcn_hipx_augment* aug, float* loss_dev) {
     if (!n) return -1;
     if (!X || !labels) return fail(n, -1, "train_epoch: X_dev and labels_dev must not be NULL");
     if (!x_kind_ok(x_kind)) return fail(n, -1, "train_epoch: x_kind must be RCN_HIPX_X_F32 or RCN_HIPX_X_U8");
     RTRY(ensure_batch(n, B));
     if (rows < 1 || first_batch < 0 || n_batches < 0 || first_batch > rows / B || n_batches > rows / B - first_batch)
         return fail(n, -1, "train_epoch: (first_batch + n_batches) * B must not exceed n (a remainder of less than B rows is not trained on)");
+    if (aug) { const char* why = augment_refusal(aug, n->in_h, n->in_w); if (why) return fail(n, -1, std::string("train_epoch: ") + why); }
     if (n_batches == 0) return 0;
     Dev g(n->device);
     RTRY(ensure_epoch_bufs(n));
     n->walk_open = false;
     float* const xb = (float*)n->xb.p;
-    const int32_t* const yb = (const int32_t*)n->yb.p;
+    int32_t* const yb = (int32_t*)n->yb.p;
     float* const el = (float*)n->eloss.p;
+    float* const elr = (float*)n->elr.p;
     const std::pair<int, float> key{B, lr};
     for (int64_t s = first_batch; s < first_batch + n_batches; ++s) {
-        RTRY(launch_gather(n, X, x_kind, x_scale, x_shift, labels, (long long)rows, perm ? perm + s * B : nullptr, (long long)s * B, B));
-        // (looked up per step: the eager step of a first use can grow a scratch buffer, which drops every graph)
-        auto it = n->epoch_graphs.find(key);
-        if (it == n->epoch_graphs.end()) {
-            hipGraphExec_t exec = nullptr;
-            RTRY(step_and_capture(n, xb, yb, B, lr, el, &exec));
-            if (n->epoch_graphs.size() >= 8) drop_all(n->epoch_graphs);     // (eight (B, lr) pairs: a caller that varies lr per step)
-            n->epoch_graphs.emplace(key, exec);
+        RTRY(launch_gather(n, X, x_kind, x_scale, x_shift, labels, (long long)rows, perm ? perm + s * B : nullptr, (long long)s * B, B, aug, (unsigned long long)s * (unsigned long long)B, xb, yb));
+        // (the graphs are looked up per step: the eager step of a first use can grow a scratch buffer, which drops every graph)
+        if (lr_dev) {
+            // the step's rate into the net's scalar, outside the graph: the eager step and every replay read it there
+            XTRY(n, hipMemcpyAsync(elr, lr_dev + (s - first_batch), sizeof(float), hipMemcpyDeviceToDevice, n->stream));
+            auto it = n->epoch_graphs_dlr.find(B);
+            if (it == n->epoch_graphs_dlr.end()) {
+                hipGraphExec_t exec = nullptr;
+                RTRY(step_and_capture(n, xb, yb, B, 0.f, el, &exec, elr));
+                if (n->epoch_graphs_dlr.size() >= 8) drop_all(n->epoch_graphs_dlr);
+                n->epoch_graphs_dlr.emplace(B, exec);
+            } else {
+                XTRY(n, hipGraphLaunch(it->second, n->stream));
+            }
         } else {
-            XTRY(n, hipGraphLaunch(it->second, n->stream));
+            auto it = n->epoch_graphs.find(key);
+            if (it == n->epoch_graphs.end()) {
+                hipGraphExec_t exec = nullptr;
+                RTRY(step_and_capture(n, xb, yb, B, lr, el, &exec));
+                if (n->epoch_graphs.size() >= 8) drop_all(n->epoch_graphs);     // (eight (B, lr) pairs: a caller that varies lr per call)
+                n->epoch_graphs.emplace(key, exec);
+            } else {
+                XTRY(n, hipGraphLaunch(it->second, n->stream));
+            }
         }
         if (loss_dev) XTRY(n, hipMemcpyAsync(loss_dev + (s - first_batch), el, sizeof(float), hipMemcpyDeviceToDevice, n->stream));
     }
+    return 0;
+}
+
+int rcn_hipx_train_epoch_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows, const int32_t* perm,
+                             int B, int64_t first_batch, int64_t n_batches, float lr, float* loss_dev) {
+    return rcn_hipx_train_epoch_ex_dev(n, X, x_kind, x_scale, x_shift, labels, rows, perm, B, first_batch, n_batches, lr, nullptr, nullptr, loss_dev);
+}
+
+int rcn_hipx_gather_batch_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows, const int32_t* idx, int64_t base,
+                              int B, const rcn_hipx_augment* aug, uint64_t q0, float* x_out, int32_t* labels_out) {
+    if (!n) return -1;
+    if (!X || !x_out) return fail(n, -1, "gather_batch: X_dev and x_out_dev must not be NULL");
+    if (!x_kind_ok(x_kind)) return fail(n, -1, "gather_batch: x_kind must be RCN_HIPX_X_F32 or RCN_HIPX_X_U8");
+    RTRY(ensure_batch(n, B));
+    if (rows < 1) return fail(n, -1, "gather_batch: n must be at least 1");
+    if (!idx && (base < 0 || base > rows - B)) return fail(n, -1, "gather_batch: without idx_dev, rows base .. base + B - 1 must lie inside the set");
+    if (aug) { const char* why = augment_refusal(aug, n->in_h, n->in_w); if (why) return fail(n, -1, std::string("gather_batch: ") + why); }
+    Dev g(n->device);
+    const bool with_labels = labels && labels_out;
+    return launch_gather(n, X, x_kind, x_scale, x_shift, with_labels ? labels : nullptr, (long long)rows, idx, (long long)base, B, aug, (unsigned long long)q0, x_out,
+                         with_labels ? labels_out : nullptr);
+}
+
+int rcn_hipx_augment_draw(const rcn_hipx_augment* aug, uint64_t q, int* dy, int* dx, int* flip) {
+    if (!aug || augment_refusal(aug, 0, 0)) return -1;
+    const AugDraw d = augment_draw(AugSpec{aug->seed, aug->epoch, aug->pad, aug->hflip}, (unsigned long long)q);
+    if (dy) *dy = d.dy;
+    if (dx) *dx = d.dx;
+    if (flip) *flip = d.flip;
     return 0;
 }
 
@@ -1159,7 +1235,7 @@ int rcn_hipx_evaluate_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_sc
         const int B = (int)(rows - off < n->max_batch ? rows - off : n->max_batch);
         const float* x = (const float*)X + off * E;
         if (x_kind == RCN_HIPX_X_U8) {
-            RTRY(launch_gather(n, X, x_kind, x_scale, x_shift, nullptr, (long long)rows, nullptr, (long long)off, B));
+            RTRY(launch_gather(n, X, x_kind, x_scale, x_shift, nullptr, (long long)rows, nullptr, (long long)off, B, nullptr, 0, (float*)n->xb.p, (int*)n->yb.p));
             x = (const float*)n->xb.p;
         }
         RTRY(eval_chunk(n, x, labels ? labels + off : nullptr, B, loss_sum, (long long*)correct, pred ? pred + off : nullptr));
@@ -1345,6 +1421,29 @@ int rcn_hipx_plan_net(const rcn_hipx_net* n, int batch, char* out, int cap) {
     make_dry_net(net, *n, batch);
     net.plan = "forward + loss + backward of one batch of " + std::to_string(batch) + " (" + precision_name(net.precision, net.store16) + "), launch by launch:\n";
     const int st = step_core(&net, nullptr, nullptr, batch, 0.f, nullptr, true, nullptr);
+    const std::string& text = st == 0 ? net.plan : net.err;
+    std::snprintf(out, (size_t)cap, "%s", text.c_str());
+    return st;
+}
+
+// One step of an epoch of an EXISTING net (rcn_hipx_train_epoch_ex_dev): what is launched around the captured graph -- the gather, the copy
+// of a scheduled rate -- the graph's key, then the step's own plan (rcn_hipx_plan_net's walk; the _dlr update kernel for a scheduled rate).
+int rcn_hipx_plan_epoch_net(const rcn_hipx_net* n, int batch, int x_kind, int lr_from_device, const rcn_hipx_augment* aug, char* out, int cap) {
+    if (!n || batch < 1 || batch > n->max_batch || !out || cap < 1) return -1;
+    if (!x_kind_ok(x_kind) || (lr_from_device != 0 && lr_from_device != 1)) return -1;
+    if (aug) { const char* why = augment_refusal(aug, n->in_h, n->in_w); if (why) { std::snprintf(out, (size_t)cap, "%s", why); return -1; } }
+    rcn_hipx_net net;
+    make_dry_net(net, *n, batch);
+    net.plan = "one step of an epoch over a resident " + std::string(x_kind == RCN_HIPX_X_U8 ? "uint8" : "fp32") + " set at batch " + std::to_string(batch) +
+               ": the launches around the captured graph, its key, then the graph's own launches:\n";
+    const float* const marker = reinterpret_cast<const float*>(sizeof(float));      // (dry run: no buffers; any non-null marks "the rate comes from the device")
+    int st = launch_gather(&net, nullptr, x_kind, 1.f, 0.f, nullptr, 1, nullptr, 0, batch, aug, 0, nullptr, nullptr);
+    if (st == 0) {
+        if (lr_from_device) (void)dry_note(&net, "  lr: 4-byte device copy of lr_dev[i] into the net's rate scalar (hipMemcpyAsync, outside the graph)");
+        (void)dry_note(&net, lr_from_device ? "  graph: one graph per B, lr from device" : "  graph: one graph per (B, lr)");
+        net.plan += "forward + loss + backward of one batch of " + std::to_string(batch) + " (" + precision_name(net.precision, net.store16) + "), launch by launch:\n";
+        st = step_core(&net, nullptr, nullptr, batch, 0.f, nullptr, true, nullptr, lr_from_device ? marker : nullptr);
+    }
     const std::string& text = st == 0 ? net.plan : net.err;
     std::snprintf(out, (size_t)cap, "%s", text.c_str());
     return st;
