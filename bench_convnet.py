@@ -31,7 +31,9 @@ def resident_set_figures(net, args, in_shape, B, lr):
     """--dataset N: whole epochs of train_epoch over a resident synthetic set (a fresh device permutation per epoch, its range check and
     the gather included), then evaluate over the set.  Whole-call rates from a host clock around work that ends in a synchronise.
     --lr-schedule / --augment: the same epochs once more as that recipe -- a warm-up + cosine rate per step from a device tensor, the
-    gather through a random crop and flip -- timed the same way, beside the plain figure."""
+    gather through a random crop and flip -- timed the same way, beside the plain figure.
+    --label-smoothing / --mix: those recipe epochs a third time with the smoothed loss and / or mixup / CutMix records (mix_plan, made and
+    moved to the device before the clock starts), beside the recipe figure: mix_epoch_ms_per_step."""
     import torch
     N = args.dataset
     nb = N // B
@@ -78,6 +80,31 @@ def resident_set_figures(net, args, in_shape, B, lr):
             rel = time.perf_counter() - t0
             recipe = {"recipe": {"lr_schedule": args.lr_schedule, "augment_pad": args.augment if args.augment >= 0 else None, "hflip": args.augment >= 0},
                       "recipe_epoch_ms_per_step": round(rel / (epochs * nb) * 1e3, 4)}
+        if args.label_smoothing > 0 or args.mix != "none":
+            from mercer_research_amd.convnet import Augment, mix_plan, warmup_cosine
+            sched = torch.from_numpy(warmup_cosine(nb, lr, max(1, nb // 20))).to(net.device) if args.lr_schedule == "warmup_cosine" else lr
+            alphas = {"mixup": (0.8, 0.0), "cutmix": (0.0, 1.0), "both": (0.8, 1.0)}.get(args.mix)
+            plans = [net.mix_to_device(mix_plan(nb, in_shape[0], in_shape[1], alphas[0], alphas[1], seed=e)) for e in range(epochs + 1)] if alphas else None
+            net.set_loss(args.label_smoothing)
+            done = [0]
+
+            def mix_epoch():
+                perm = torch.randperm(N, generator=gen, device=net.device).int()
+                net.train_epoch(X, Y, perm, B, sched, losses=losses, augment=Augment(args.augment, True, 2, done[0]) if args.augment >= 0 else None,
+                                mix=plans[done[0]] if plans else None)
+                done[0] += 1
+
+            mix_epoch()                                    # pair labels (and a new loss setting) have their own graph: instantiated here, once
+            net.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(epochs):
+                mix_epoch()
+            net.synchronize()
+            mel = time.perf_counter() - t0
+            net.set_loss(0.0)                              # the figures below are those of the plain loss, as without these flags
+            recipe.update({"mix": {"label_smoothing": args.label_smoothing, "mix": args.mix, "mixup_alpha": alphas[0] if alphas else None,
+                                   "cutmix_alpha": alphas[1] if alphas else None},
+                           "mix_epoch_ms_per_step": round(mel / (epochs * nb) * 1e3, 4)})
         graphs = net.graphs_instantiated()                 # read here: the trap below instantiates one per step on purpose
         if args.trap:
             # what the scheduled path removes: the same kind of schedule as one-batch calls with a new float rate each -- the rate is part
@@ -133,7 +160,15 @@ def main():
     ap.add_argument("--trap", action="store_true",
                     help="with --dataset: also run one epoch of a warm-up + cosine schedule as one-batch calls with a new FLOAT rate each (a capture per step): "
                          "trap_ms_per_step, trap_graphs_instantiated")
+    ap.add_argument("--label-smoothing", type=float, default=0.0, metavar="E",
+                    help="with --dataset: time the recipe's epochs once more with the smoothed loss (rcn_hipx_set_loss): mix_epoch_ms_per_step beside recipe_epoch_ms_per_step")
+    ap.add_argument("--mix", choices=["none", "mixup", "cutmix", "both"], default="none",
+                    help="with --dataset: those epochs mix every batch with its mirror image by mix_plan's records (mixup alpha 0.8, CutMix alpha 1.0; k_gather_mix, pair labels)")
     args = ap.parse_args()
+    if (args.label_smoothing != 0.0 or args.mix != "none") and not args.dataset:
+        ap.error("--label-smoothing and --mix time the resident epoch: they need --dataset N")
+    if not 0.0 <= args.label_smoothing < 1.0:
+        ap.error("--label-smoothing: 0 <= E < 1")
     if (args.lr_schedule != "none" or args.augment >= 0 or args.trap) and not args.dataset:
         ap.error("--lr-schedule, --augment and --trap time the resident epoch: they need --dataset N")
     from mercer_research_amd.launch import spawn_ranks, under_launcher

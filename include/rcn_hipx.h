@@ -168,6 +168,62 @@ int  rcn_hipx_augment_draw(const rcn_hipx_augment* aug, uint64_t q, int* dy, int
  * rcn_hipx_plan_net's text -- with the _dlr update kernel if lr_from_device.  -1: net NULL, batch outside 1 .. max_batch, an unknown
  * x_kind, lr_from_device not 0 / 1, an aug that rcn_hipx_train_epoch_ex_dev refuses (the reason in `out`). */
 int  rcn_hipx_plan_epoch_net(const rcn_hipx_net* net, int batch, int x_kind, int lr_from_device, const rcn_hipx_augment* aug, char* out, int cap);
+/* The loss of the training step: cross-entropy against a smoothed target, as torch.nn.CrossEntropyLoss(label_smoothing = eps).  Per sample,
+ * with lp_c = (z_c - max) - log(sum exp) and C classes, in fp32, every operation rounded once (no fused multiply-add):
+ *     t_c  = (1 - eps) * (w * [c == ya] + (1 - w) * [c == yb]) + eps / C
+ *     loss = -((1 - eps) * (w * lp_ya + (1 - w) * lp_yb) + (eps / C) * sum_c lp_c),      d logits_c = (softmax_c - t_c) / B
+ * (ya, yb, w): the sample's pair of labels and the weight of ya (rcn_hipx_train_step_pair_dev, rcn_hipx_train_epoch_mix_dev); every other
+ * entry point has yb = ya, w = 1.  Net state like rcn_hipx_set_sgd: it applies to every entry point that computes the training loss --
+ * rcn_hipx_train_step_dev, both epoch entries, rcn_hipx_gradients_dev and rcn_hipx_gradients_begin_dev.  rcn_hipx_evaluate_dev stays the
+ * plain cross-entropy against the label, whatever is set here.  eps == 0 (the default): the hard kernels, the same launches and arguments
+ * as a net never configured.  eps > 0: k_softmax_ce_soft, or k_head_f32's soft instantiation, in the same place of the step -- the loss sum
+ * keeps its fixed order.  In the soft kernels a label outside [0, C) never indexes a logits row: its indicator is 0 everywhere and its lp
+ * term is dropped.  Accepts a finite 0 <= eps < 1; anything else returns -1 and changes nothing.  A change synchronises the net's stream
+ * and drops its captured graphs. */
+int  rcn_hipx_set_loss(rcn_hipx_net* net, float label_smoothing);
+int  rcn_hipx_get_loss(const rcn_hipx_net* net, float* label_smoothing);
+/* Mixed samples (mixup, CutMix) of ONE training step: every row r of the batch is mixed with row B - 1 - r of the same batch (the middle
+ * row of an odd batch with itself).  The gather writes, at output pixel (h, w), all channels,
+ *     y0 <= h < y1 && x0 <= w < x1 ?  b  :  blend == 1 ?  a  :  fl(fl(blend * a) + fl(fl(1 - blend) * b))
+ * where a is what the un-mixed gather writes for row r and b what it writes for its partner (each with its own augmentation draw), and
+ * the loss takes `weight` as the target weight of the row's own label, 1 - weight for the partner's.  mixup: blend = weight = lambda and
+ * an empty box; CutMix: blend = 1, the box, weight = 1 - box area / (H W).  (1, 1, empty box) mixes nothing.  The record is never
+ * inspected: any box -- inverted, or with corners outside the image -- only chooses between the two rows. */
+typedef struct rcn_hipx_mix_step {
+    float   blend;            /* weight of the row's own pixels outside the box */
+    float   weight;           /* target weight of the row's own label */
+    int32_t y0, y1, x0, x1;   /* the partner's pixels replace rows y0 .. y1 - 1, columns x0 .. x1 - 1 of the output */
+} rcn_hipx_mix_step;
+/* rcn_hipx_train_step_dev on pair labels: sample s has the target (1 - eps) * (w onehot(labels_a[s]) + (1 - w) onehot(labels_b[s])) + eps / C
+ * with w = *weight_dev, ONE float on the device read by the loss launch (NULL: w = 1), and eps of rcn_hipx_set_loss.  Always the soft loss
+ * kernels.  Its captured graphs are entries of their own, keyed on (x, labels_a, labels_b, weight, B, lr, loss) as rcn_hipx_train_step_dev's
+ * are on its pointers, kept to eight and dropped whenever the others are; the values behind the pointers may change between calls.
+ * -1: net, x_dev, labels_a_dev or labels_b_dev NULL, B outside 1 .. max_batch. */
+int  rcn_hipx_train_step_pair_dev(rcn_hipx_net* net, const float* x_dev, const int32_t* labels_a_dev, const int32_t* labels_b_dev, const float* weight_dev,
+                                  int B, float lr, float* loss_dev);
+/* rcn_hipx_gather_batch_dev through k_gather_mix: *mix_dev is ONE record on the device; x_out_dev gets the mixed batch, labels_out_dev
+ * the rows' own labels and labels_b_out_dev their partners' (both written when labels_dev is given; each nullable).  aug (nullable): row r
+ * draws with q0 + r, its partner with q0 + (B - 1 - r).  A record of (blend 1, empty box) gives rcn_hipx_gather_batch_dev's bytes.
+ * -1 (nothing enqueued): what rcn_hipx_gather_batch_dev refuses; mix_dev NULL. */
+int  rcn_hipx_gather_mix_dev(rcn_hipx_net* net, const void* X_dev, int x_kind, float x_scale, float x_shift, const int32_t* labels_dev, int64_t n,
+                             const int32_t* idx_dev, int64_t base, int B, const rcn_hipx_augment* aug, uint64_t q0, const rcn_hipx_mix_step* mix_dev,
+                             float* x_out_dev, int32_t* labels_out_dev, int32_t* labels_b_out_dev);
+/* rcn_hipx_train_epoch_ex_dev with mixed samples.  mix_dev (nullable): [n_batches] records on the device, mix_dev[i] = the record of the
+ * call's i-th step (call-relative, like lr_dev).  mix_dev == NULL: exactly rcn_hipx_train_epoch_ex_dev, which is this call with NULL.
+ * With records the net owns one more labels buffer (the partners' labels) and one more 4-byte scalar (the target weight), allocated once
+ * and never moved.  In front of each step the gather is k_gather_mix reading record i, and mix_dev[i].weight is copied into the scalar on
+ * the net's stream, as the rate is; the graph's loss launch is the soft one on the net's own two labels buffers and that scalar.  So
+ * there is ONE more graph per (B, lr) -- per B with lr_dev -- whatever the records are, beside the un-mixed graphs, kept to eight and
+ * dropped whenever they are.  A mixed epoch is bit-identical to rcn_hipx_gather_mix_dev + rcn_hipx_train_step_pair_dev on the same
+ * floats; with records of (1, 1, empty box) and eps = 0 it is bit-identical to the un-mixed epoch.
+ * -1 (nothing enqueued, nothing changed): what rcn_hipx_train_epoch_ex_dev refuses. */
+int  rcn_hipx_train_epoch_mix_dev(rcn_hipx_net* net, const void* X_dev, int x_kind, float x_scale, float x_shift, const int32_t* labels_dev, int64_t n,
+                                  const int32_t* perm_dev, int B, int64_t first_batch, int64_t n_batches, float lr, const float* lr_dev,
+                                  const rcn_hipx_augment* aug, const rcn_hipx_mix_step* mix_dev, float* loss_dev);
+/* rcn_hipx_plan_epoch_net with mix = 0 | 1.  1: the gather's line names k_gather_mix, a line for the 4-byte copy of the target weight
+ * follows the rate's, the graph's key says "pair labels", and the step's plan has the soft loss kernel.  0: rcn_hipx_plan_epoch_net's text.
+ * -1: what rcn_hipx_plan_epoch_net refuses; mix not 0 / 1. */
+int  rcn_hipx_plan_epoch_mix_net(const rcn_hipx_net* net, int batch, int x_kind, int lr_from_device, const rcn_hipx_augment* aug, int mix, char* out, int cap);
 /* Forward pass + loss + arg-max over ALL n rows (any n >= 1: chunks of at most max_batch rows, a short last chunk included); no backward
  * pass, parameters untouched.  Enqueued on the net's stream, nothing blocks; results on the device:
  *     *loss_sum_dev (double) = sum over samples of -log softmax(logits)[label]
@@ -190,6 +246,7 @@ int  rcn_hipx_plan_epoch_net(const rcn_hipx_net* net, int batch, int x_kind, int
  * it returns -6 there and does nothing (any entry point that runs a step or a gradient pass ends such a walk).  It launches eagerly and
  * captures nothing; like every launch path it drops the captured graphs only if a scratch buffer they point into has to grow (a first
  * evaluation at a larger batch than any step so far), and they are re-captured on demand.
+ * The loss is always the plain cross-entropy against the label: rcn_hipx_set_loss does not change it.
  * -1 (nothing enqueued): n < 1, X_dev NULL, an unknown x_kind, a NULL that the rules above do not allow. */
 int  rcn_hipx_evaluate_dev(rcn_hipx_net* net, const void* X_dev, int x_kind, float x_scale, float x_shift, const int32_t* labels_dev, int64_t n,
                            double* loss_sum_dev, int64_t* correct_dev, int32_t* pred_dev);
@@ -252,7 +309,8 @@ int  rcn_hipx_unpad_host(rcn_hipx_net* net, const float* padded_dev, float* logi
 int  rcn_hipx_plan(int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, int n_layers, int batch, int precision, int tiling, char* out, int cap);
 /* The same walk for an EXISTING net at batch `batch` (<= max_batch) with that net's own precision, tiling and options: the plan and the
  * step that follows agree by construction (rcn_hipx_plan describes a net created now, seeded from the environment).  A net with a
- * non-default rcn_hipx_set_sgd setting names its optimiser and the values on the update line. */
+ * non-default rcn_hipx_set_sgd setting names its optimiser and the values on the update line; one with rcn_hipx_set_loss eps > 0 names the
+ * soft loss kernel and eps on the loss (or head) line. */
 int  rcn_hipx_plan_net(const rcn_hipx_net* net, int batch, char* out, int cap);
 /* algorithmic FLOPs of one training step at batch B (2 * MACs; forward + dgrad + wgrad) */
 int  rcn_hipx_step_flops(const rcn_hipx_net* net, int B, double* flops);

@@ -38,6 +38,42 @@ class Augment:
         return AugmentStruct(int(self.pad), int(bool(self.hflip)), int(self.seed) & (2 ** 64 - 1), int(self.epoch) & (2 ** 64 - 1))
 
 
+class MixStep(C.Structure):
+    """rcn_hipx_mix_step: one training step's mixing record (24 bytes)"""
+    _fields_ = [("blend", C.c_float), ("weight", C.c_float), ("y0", C.c_int32), ("y1", C.c_int32), ("x0", C.c_int32), ("x1", C.c_int32)]
+
+
+# the same record as a NumPy structured dtype: an array of it, moved to the device as bytes, is train_epoch's `mix`
+MIX_DTYPE = np.dtype([("blend", np.float32), ("weight", np.float32), ("y0", np.int32), ("y1", np.int32), ("x0", np.int32), ("x1", np.int32)])
+
+
+def mix_plan(n_steps: int, H: int, W: int, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0, switch_prob: float = 0.5, seed: int = 0) -> np.ndarray:
+    """n_steps mixing records (MIX_DTYPE) for images of H x W, drawn with np.random.default_rng(seed); pure NumPy.  Per step: CutMix with
+    probability switch_prob when both alphas are positive, else whichever is positive; lam ~ Beta(alpha, alpha).  mixup: blend = weight =
+    float32(lam), empty box.  CutMix (the paper's box): cut = int(dim * sqrt(1 - lam)) per dimension around a centre uniform in the image,
+    corners clipped to the image; blend = 1, weight = float32(1 - area / (H W))."""
+    n_steps, H, W = int(n_steps), int(H), int(W)
+    mixup_alpha, cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+    if n_steps < 1:
+        raise ValueError("mix_plan: n_steps >= 1")
+    if mixup_alpha < 0 or cutmix_alpha < 0 or (mixup_alpha == 0 and cutmix_alpha == 0):
+        raise ValueError("mix_plan: alphas >= 0, at least one of them positive")
+    rng = np.random.default_rng(seed)
+    out = np.zeros(n_steps, dtype=MIX_DTYPE)
+    for i in range(n_steps):
+        cut = rng.random() < switch_prob if (mixup_alpha > 0 and cutmix_alpha > 0) else cutmix_alpha > 0
+        lam = float(rng.beta(cutmix_alpha, cutmix_alpha) if cut else rng.beta(mixup_alpha, mixup_alpha))
+        if not cut:
+            out[i] = (lam, lam, 0, 0, 0, 0)
+            continue
+        ch, cw = int(H * np.sqrt(1.0 - lam)), int(W * np.sqrt(1.0 - lam))
+        cy, cx = int(rng.integers(0, H)), int(rng.integers(0, W))
+        y0, y1 = int(np.clip(cy - ch // 2, 0, H)), int(np.clip(cy + ch // 2, 0, H))
+        x0, x1 = int(np.clip(cx - cw // 2, 0, W)), int(np.clip(cx + cw // 2, 0, W))
+        out[i] = (1.0, np.float32(1.0 - (y1 - y0) * (x1 - x0) / (H * W)), y0, y1, x0, x1)
+    return out
+
+
 def _aug_ref(augment: Optional[Augment]):
     """(ctypes struct kept alive by the caller, pointer or None)"""
     if augment is None:
@@ -84,6 +120,12 @@ SIGNATURES = {
     "rcn_hipx_gather_batch_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _vp, C.c_int64, _i, C.POINTER(AugmentStruct), C.c_uint64, _vp, _vp]),
     "rcn_hipx_augment_draw": (_i, [C.POINTER(AugmentStruct), C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rcn_hipx_plan_epoch_net": (_i, [_vp, _i, _i, _i, C.POINTER(AugmentStruct), C.c_char_p, _i]),
+    "rcn_hipx_set_loss": (_i, [_vp, C.c_float]),
+    "rcn_hipx_get_loss": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rcn_hipx_train_step_pair_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i, C.c_float, _vp]),
+    "rcn_hipx_gather_mix_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _vp, C.c_int64, _i, C.POINTER(AugmentStruct), C.c_uint64, _vp, _vp, _vp, _vp]),
+    "rcn_hipx_train_epoch_mix_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _vp, _i, C.c_int64, C.c_int64, C.c_float, _vp, C.POINTER(AugmentStruct), _vp, _vp]),
+    "rcn_hipx_plan_epoch_mix_net": (_i, [_vp, _i, _i, _i, C.POINTER(AugmentStruct), _i, C.c_char_p, _i]),
     "rcn_hipx_evaluate_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _vp, _vp, _vp]),
     "rcn_hipx_graphs_instantiated": (_i, [_vp, C.POINTER(C.c_int64)]),
     "rcn_hipx_plan_eval": (_i, [_i, _i, _i, C.POINTER(XLayer), _i, _i, _i, _i, C.c_char_p, _i]),
@@ -287,6 +329,27 @@ class ConvNet:
         self._ck(self.lib.rcn_hipx_train_step_dev(self.net, C.c_void_p(x.data_ptr()), C.c_void_p(labels.data_ptr()), x.shape[0], lr,
                                                   C.c_void_p(loss.data_ptr()) if loss is not None else None))
 
+    def train_step_pair(self, x, labels_a, labels_b, weight, lr: float, loss=None):
+        """train_step on pair labels (rcn_hipx_train_step_pair_dev): sample s has the target w * onehot(labels_a[s]) + (1 - w) *
+        onehot(labels_b[s]), smoothed by set_loss's label_smoothing.  weight: a one-element float32 device tensor holding w, read by the
+        loss launch (None: w = 1)."""
+        self._ck(self.lib.rcn_hipx_train_step_pair_dev(self.net, C.c_void_p(x.data_ptr()), C.c_void_p(labels_a.data_ptr()), C.c_void_p(labels_b.data_ptr()),
+                                                       C.c_void_p(weight.data_ptr()) if weight is not None else None, x.shape[0], lr,
+                                                       C.c_void_p(loss.data_ptr()) if loss is not None else None))
+
+    def _mix_records(self, mix, count: int):
+        """the pointer of `count` rcn_hipx_mix_step records in a contiguous device tensor (any dtype: the bytes of a MIX_DTYPE array)"""
+        if not self.torch.is_tensor(mix) or mix.device != self.device or not mix.is_contiguous() or mix.numel() * mix.element_size() < count * MIX_DTYPE.itemsize:
+            raise ValueError(f"mix: a contiguous tensor on the net's device holding at least {count} records of {MIX_DTYPE.itemsize} bytes (MIX_DTYPE)")
+        if mix.data_ptr() % 4:
+            raise ValueError("mix: the records must be 4-byte aligned")
+        return C.c_void_p(mix.data_ptr())
+
+    def mix_to_device(self, records: np.ndarray):
+        """a MIX_DTYPE array (mix_plan's) as a device tensor of its bytes: train_epoch's and gather_mix's `mix`"""
+        rec = np.ascontiguousarray(records, dtype=MIX_DTYPE).reshape(-1)
+        return self.to_device(rec.view(np.uint8).reshape(rec.size, MIX_DTYPE.itemsize))
+
     def _resident_set(self, X, labels):
         """(x_kind, rows) of a device-resident set after checking its dtype, shape, device and contiguity (labels: int32, one per row)."""
         t = self.torch
@@ -303,7 +366,7 @@ class ConvNet:
         return kind, int(X.shape[0])
 
     def train_epoch(self, X, labels, perm, B: int, lr, n_batches: Optional[int] = None, first_batch: int = 0, losses=None,
-                    x_scale: float = 1.0 / 255.0, x_shift: float = 0.0, augment: Optional[Augment] = None):
+                    x_scale: float = 1.0 / 255.0, x_shift: float = 0.0, augment: Optional[Augment] = None, mix=None):
         """n_batches training steps over a device-resident set (rcn_hipx_train_epoch_dev): batch s is rows perm[s*B : (s+1)*B] (perm None:
         rows in order), gathered on the device into the net's own batch buffer, then the step of train_step -- bit-identical to it, and ONE
         captured graph per (B, lr) whatever X, perm, first_batch and losses are.  X: torch.float32 or torch.uint8 [n, H, W, C] (uint8 rows
@@ -312,7 +375,10 @@ class ConvNet:
         float32 device tensor of at least n_batches elements, losses[i] = mean loss of the call's i-th step before its update.
         lr: a float, or a contiguous float32 device tensor of at least n_batches elements -- lr[i] is the rate of the call's i-th step
         (rcn_hipx_train_epoch_ex_dev: ONE graph per B whatever the schedule; checked finite here, once per call, which synchronises).
-        augment: an Augment -- every batch is gathered through its random crop and flip, drawn from (seed, epoch, s*B + r)."""
+        augment: an Augment -- every batch is gathered through its random crop and flip, drawn from (seed, epoch, s*B + r).
+        mix: a contiguous device tensor holding at least n_batches records of MIX_DTYPE (mix_plan's array through mix_to_device) -- the
+        call's i-th step is mixed by record i (rcn_hipx_train_epoch_mix_dev: mixup / CutMix with the mirrored row of the same batch, ONE
+        more graph whatever the records are)."""
         t = self.torch
         kind, n = self._resident_set(X, labels)
         if labels is None:
@@ -338,6 +404,13 @@ class ConvNet:
             if n_batches > 0 and not bool(t.isfinite(lr[:n_batches]).all()):
                 raise ValueError("lr: the schedule holds a value that is not finite")
             lr_dev, lr = C.c_void_p(lr.data_ptr()), 0.0
+        if mix is not None:
+            recs = self._mix_records(mix, n_batches)
+            keep, aug = _aug_ref(augment)
+            self._ck(self.lib.rcn_hipx_train_epoch_mix_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift), C.c_void_p(labels.data_ptr()), n,
+                                                           C.c_void_p(perm.data_ptr()) if perm is not None else None, B, first_batch, n_batches, float(lr), lr_dev, aug, recs,
+                                                           C.c_void_p(losses.data_ptr()) if losses is not None else None))
+            return
         if lr_dev is None and augment is None:
             self._ck(self.lib.rcn_hipx_train_epoch_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift), C.c_void_p(labels.data_ptr()), n,
                                                        C.c_void_p(perm.data_ptr()) if perm is not None else None, B, first_batch, n_batches, float(lr),
@@ -369,12 +442,39 @@ class ConvNet:
                                                     C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None))
         return x, y
 
-    def plan_epoch_of_this_net(self, batch: int, x_dtype: str = "uint8", lr_from_device: bool = False, augment: Optional[Augment] = None) -> str:
-        """What one step of train_epoch launches for THIS net (rcn_hipx_plan_epoch_net): the gather, the copy of a scheduled rate, the
-        graph's key, then plan_of_this_net's text.  x_dtype: "uint8" or "float32", the set's storage."""
+    def gather_mix(self, X, labels, idx, B: int, mix, base: int = 0, augment: Optional[Augment] = None, q0: int = 0,
+                   x_scale: float = 1.0 / 255.0, x_shift: float = 0.0):
+        """One batch as train_epoch(mix=...) gathers it (rcn_hipx_gather_mix_dev): gather_batch's rows, row r mixed with row B - 1 - r by the
+        ONE record `mix` holds (a device tensor, as train_epoch's).  Returns (x, labels of the rows, labels of their partners); the two
+        labels are None without labels."""
+        t = self.torch
+        kind, n = self._resident_set(X, labels)
+        B = int(B)
+        if idx is not None:
+            if idx.dtype != t.int32 or idx.dim() != 1 or idx.device != self.device or not idx.is_contiguous() or idx.numel() < B:
+                raise ValueError("idx: a contiguous one-dimensional int32 tensor on the net's device with at least B entries")
+        rec = self._mix_records(mix, 1)
+        with t.cuda.stream(self.stream):
+            x = t.empty((max(B, 0),) + self.in_shape, dtype=t.float32, device=self.device)
+            ya = t.empty(max(B, 0), dtype=t.int32, device=self.device) if labels is not None else None
+            yb = t.empty(max(B, 0), dtype=t.int32, device=self.device) if labels is not None else None
+        keep, aug = _aug_ref(augment)
+        self._ck(self.lib.rcn_hipx_gather_mix_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift),
+                                                  C.c_void_p(labels.data_ptr()) if labels is not None else None, n,
+                                                  C.c_void_p(idx.data_ptr()) if idx is not None else None, int(base), B, aug, int(q0) & (2 ** 64 - 1), rec,
+                                                  C.c_void_p(x.data_ptr()), C.c_void_p(ya.data_ptr()) if ya is not None else None,
+                                                  C.c_void_p(yb.data_ptr()) if yb is not None else None))
+        return x, ya, yb
+
+    def plan_epoch_of_this_net(self, batch: int, x_dtype: str = "uint8", lr_from_device: bool = False, augment: Optional[Augment] = None, mix: bool = False) -> str:
+        """What one step of train_epoch launches for THIS net (rcn_hipx_plan_epoch_net / _mix_net): the gather, the copy of a scheduled rate
+        (and, mix: of the step's target weight), the graph's key, then plan_of_this_net's text.  x_dtype: "uint8" or "float32", the set's storage."""
         buf = C.create_string_buffer(1 << 16)
         keep, aug = _aug_ref(augment)
-        st = self.lib.rcn_hipx_plan_epoch_net(self.net, int(batch), X_KIND[x_dtype], int(bool(lr_from_device)), aug, buf, len(buf))
+        if mix:
+            st = self.lib.rcn_hipx_plan_epoch_mix_net(self.net, int(batch), X_KIND[x_dtype], int(bool(lr_from_device)), aug, 1, buf, len(buf))
+        else:
+            st = self.lib.rcn_hipx_plan_epoch_net(self.net, int(batch), X_KIND[x_dtype], int(bool(lr_from_device)), aug, buf, len(buf))
         if st != 0:
             raise ConvNetError(f"rcn_hipx_plan_epoch_net: {st}: {buf.value.decode()}")
         return buf.value.decode()
@@ -447,6 +547,16 @@ class ConvNet:
         """The optimiser of train_step / apply_sgd: SGD with momentum, weight decay and Nesterov, as torch.optim.SGD with dampening 0
         (include/rcn_hipx.h, rcn_hipx_set_sgd).  (0, 0, False) is plain SGD, the default."""
         self._ck(self.lib.rcn_hipx_set_sgd(self.net, float(momentum), float(weight_decay), int(bool(nesterov))))
+
+    def set_loss(self, label_smoothing: float = 0.0):
+        """The training loss: cross-entropy against the target smoothed by label_smoothing, as torch.nn.CrossEntropyLoss(label_smoothing=)
+        (include/rcn_hipx.h, rcn_hipx_set_loss).  0 is the default: the hard loss kernels.  evaluate stays the plain cross-entropy."""
+        self._ck(self.lib.rcn_hipx_set_loss(self.net, float(label_smoothing)))
+
+    def get_loss(self) -> float:
+        eps = C.c_float()
+        self._ck(self.lib.rcn_hipx_get_loss(self.net, C.byref(eps)))
+        return float(eps.value)
 
     def get_sgd(self) -> Tuple[float, float, bool]:
         mu, wd, nest = C.c_float(), C.c_float(), C.c_int()

@@ -7,6 +7,8 @@
 //   k_gather_aug<TS, VEC>   the same rows through a random translation with zero padding and a horizontal flip (rcn_hipx_augment): the
 //                           sample's draw is computed from its position in the epoch in registers; element by element on the read side,
 //                           16-byte stores on the write side.
+//   k_gather_mix<TS, VEC>   mixup / CutMix (rcn_hipx_mix_step): every output row blended with, or inside a box replaced by, the row that
+//                           mirrors it in the SAME batch, each gathered (and augmented) as the kernels above would; both labels out.
 //   k_eval_ce               soft-max cross-entropy, first-maximum arg-max and correct count of one chunk of logits, without d logits;
 //                           its last-arriving workgroup ADDS the chunk's totals into a double / int64 pair.
 #pragma once
@@ -164,12 +166,77 @@ inline long long gather_aug_blocks(int B, int E, int vec) {
     return blocks >= (1ll << 31) ? 0 : blocks;
 }
 
+// ---- mixed samples: mixup and CutMix (rcn_hipx_mix_step) --------------------------------------------------------------------------------
+struct MixStep { float blend, weight; int y0, y1, x0, x1; };      // rcn_hipx_mix_step, one per training step; the gather never reads `weight`
+
+// the value k_gather_aug writes at (h, w, c) of a row drawn d -- k_gather_rows' value for the draw (0, 0, no flip)
+template <typename TS>
+__device__ inline float gathered_value(const TS* __restrict__ src, int h, int w, int c, int H, int W, int C, const AugDraw& d, const RowScale& rs) {
+    const int sh = h + d.dy, sw = (d.flip ? W - 1 - w : w) + d.dx;
+    TS v = (TS)0;
+    if (sh >= 0 && sh < H && sw >= 0 && sw < W) v = src[(sh * W + sw) * C + c];
+    return RowPiece<TS>::widen1(v, rs);
+}
+
+// Output row r of a batch of B mixed with its partner r' = B - 1 - r of the same batch (the middle row of an odd batch: itself).  With
+// a = the value the un-mixed gather writes for row r at position q0 + r (k_gather_aug's if has_aug, else k_gather_rows') and b = the same
+// for row r' at q0 + r' -- the counter-based draw makes the partner's augmentation free to recompute --
+//     dst[r][h][w][c] = (mix->y0 <= h < mix->y1 && mix->x0 <= w < mix->x1) ? b              (CutMix's box, output coordinates, all channels)
+//                     : mix->blend == 1 ? a : fl(fl(blend * a) + fl(fl(1 - blend) * b))     (mixup; no fused multiply-add)
+//     labels_out[r] = label(row r), labels_b_out[r] = label(row r')                          (each nullable)
+// *mix is ONE record on the device, never inspected: the box only chooses between two in-range sources, so any integers are safe, an
+// inverted or outlying box included.  Indices are clamped as in the other gathers; no address is formed from a coordinate outside the
+// image.  Only the sources an output needs are loaded (one inside the box or at blend 1, two where it blends).  Threads and stores as in
+// k_gather_aug: one thread per VEC consecutive outputs, total = B * (E / VEC) (gather_aug_blocks).
+template <typename TS, int VEC>
+__global__ __launch_bounds__(kGatherThreads) void k_gather_mix(const TS* __restrict__ X, const int* __restrict__ labels, long long n, const int* __restrict__ idx, long long base,
+                                                               int B, int H, int W, int C, RowScale rs, int has_aug, AugSpec aug, unsigned long long q0,
+                                                               const MixStep* __restrict__ mix, float* __restrict__ dst, int* __restrict__ labels_out,
+                                                               int* __restrict__ labels_b_out) {
+    const int E = H * W * C, P = E / VEC;               // pieces per row
+    const long long g = (long long)blockIdx.x * kGatherThreads + threadIdx.x;
+    if (g >= (long long)B * P) return;
+    const int r = (int)(g / P), piece = (int)(g - (long long)r * P), rp = B - 1 - r;
+    long long row_a = idx ? (long long)idx[r] : base + r, row_b = idx ? (long long)idx[rp] : base + rp;
+    row_a = row_a < 0 ? 0 : (row_a >= n ? n - 1 : row_a);      // as in k_gather_rows: an index out of range must not become an address
+    row_b = row_b < 0 ? 0 : (row_b >= n ? n - 1 : row_b);
+    if (labels && piece == 0) {
+        if (labels_out) labels_out[r] = labels[row_a];
+        if (labels_b_out) labels_b_out[r] = labels[row_b];
+    }
+    const MixStep m = *mix;
+    const AugDraw none{0, 0, 0};
+    const AugDraw da = has_aug ? augment_draw(aug, q0 + (unsigned long long)r) : none;
+    const AugDraw db = has_aug ? augment_draw(aug, q0 + (unsigned long long)rp) : none;
+    const TS* __restrict__ src_a = X + row_a * E;
+    const TS* __restrict__ src_b = X + row_b * E;
+    float o[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        const int e = piece * VEC + k;
+        const int hw = e / C, c = e - hw * C;
+        const int h = hw / W, w = hw - h * W;
+        if (h >= m.y0 && h < m.y1 && w >= m.x0 && w < m.x1) o[k] = gathered_value(src_b, h, w, c, H, W, C, db, rs);
+        else if (m.blend == 1.0f) o[k] = gathered_value(src_a, h, w, c, H, W, C, da, rs);
+        else {
+#pragma clang fp contract(off)
+            const float pa = m.blend * gathered_value(src_a, h, w, c, H, W, C, da, rs);
+            const float pb = (1.0f - m.blend) * gathered_value(src_b, h, w, c, H, W, C, db, rs);
+            o[k] = pa + pb;
+        }
+    }
+    float* const out = dst + (long long)r * E + (long long)piece * VEC;
+    if constexpr (VEC == 4) *reinterpret_cast<f32x4*>(out) = f32x4{o[0], o[1], o[2], o[3]};
+    else out[0] = o[0];
+}
+
 // Which gather launch a batch gets.  Un-augmented: k_gather_rows, 16-byte pieces where every row starts on a 16-byte boundary and is a
 // whole number of them, element by element otherwise.  Augmented: k_gather_aug, 16-byte stores where a row is a whole number of them.
-struct GatherChoice { bool aug, u8; int vec; long long blocks; };
-inline GatherChoice select_gather(bool u8, int B, int E, bool src_aligned16, bool dst_aligned16, bool aug) {
-    GatherChoice c{aug, u8, 1, 0};
-    if (aug) {
+// Mixed (augmented or not): k_gather_mix, by k_gather_aug's rule.
+struct GatherChoice { bool aug, u8; int vec; long long blocks; bool mix = false; };
+inline GatherChoice select_gather(bool u8, int B, int E, bool src_aligned16, bool dst_aligned16, bool aug, bool mix = false) {
+    GatherChoice c{aug, u8, 1, 0, mix};
+    if (aug || mix) {
         c.vec = (E % 4 == 0 && dst_aligned16) ? 4 : 1;
         c.blocks = gather_aug_blocks(B, E, c.vec);
         return c;

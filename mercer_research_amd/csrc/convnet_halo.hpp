@@ -971,11 +971,13 @@ __global__ __launch_bounds__(kThreads) void k_conv1_wgrad_f32(const float* __res
 // steps.  F = hidden width (multiple of 32, <= 256: LDS), classes <= 32 (one padded column block).  The weight-gradient partials go
 // to slab[workgroup][F + 1][32] like k_conv_wgrad's, so k_reduce_all finishes; the loss like k_softmax_ce (last workgroup
 // adds the partials in order).
-template <bool GATE>
+// SOFT: the soft-max stage takes a soft target (k_softmax_ce_soft's expressions and label guard) from ONE trailing SoftTarget argument;
+// the hard instantiation has no such argument: its launch is unchanged.
+template <bool GATE, bool SOFT = false, typename... Soft>
 __global__ __launch_bounds__(kThreads) void k_head_f32(const float* __restrict__ Hin, const float* __restrict__ Wk, const float* __restrict__ Wt,
                                                        const float* __restrict__ bias, const int* __restrict__ labels, int B, int F, int C,
                                                        float* __restrict__ logits, float* __restrict__ dH, float* __restrict__ slab, float* loss_part,
-                                                       unsigned* counter, float inv_b, float* __restrict__ loss_out) {
+                                                       unsigned* counter, float inv_b, float* __restrict__ loss_out, Soft... soft) {
     extern __shared__ __attribute__((aligned(16))) float head_smem[];
     const int LDH = F + 1, LDT = F + 32;
     float* Hs = head_smem;                       // [32 samples][F + 1]: odd rows, read along samples (logits) and along features (weight gradient)
@@ -1025,18 +1027,44 @@ __global__ __launch_bounds__(kThreads) void k_head_f32(const float* __restrict__
         for (int j = 0; j < 4; ++j) { ex[j] = cg + j < C ? expf(v[j] - mx) : 0.f; sum += ex[j]; }
 #pragma unroll
         for (int off = 4; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 8);
-        const int y = s < B ? labels[s] : 0;
-        float zy = 0.f;
+        if constexpr (SOFT) {
+#pragma clang fp contract(off)
+            const SoftTarget tg{soft...};
+            const int ya = s < B ? labels[s] : 0, yb = (s < B && tg.labels_b) ? tg.labels_b[s] : ya;
+            const float w = tg.weight ? *tg.weight : 1.f;
+            const float lse = logf(sum), keep = 1.f - tg.eps, wb = 1.f - w, u = tg.eps / (float)C;
+            float slp = 0.f, lpa = 0.f, lpb = 0.f;              // sum over the classes of lp_c; lp of the two labels (0: outside [0, C))
 #pragma unroll
-        for (int j = 0; j < 4; ++j) zy += cg + j == y ? v[j] : 0.f;
+            for (int j = 0; j < 4; ++j) {
+                const float lp = cg + j < C ? (v[j] - mx) - lse : 0.f;
+                slp += lp;
+                lpa += cg + j == ya ? lp : 0.f;
+                lpb += cg + j == yb ? lp : 0.f;
+            }
 #pragma unroll
-        for (int off = 4; off > 0; off >>= 1) zy += __shfl_xor(zy, off, 8);
-        if ((tid & 7) == 0) red[sm] = s < B ? -(zy - mx - logf(sum)) : 0.f;
+            for (int off = 4; off > 0; off >>= 1) { slp += __shfl_xor(slp, off, 8); lpa += __shfl_xor(lpa, off, 8); lpb += __shfl_xor(lpb, off, 8); }
+            if ((tid & 7) == 0) red[sm] = s < B ? -(keep * (w * lpa + wb * lpb) + u * slp) : 0.f;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float d = (s < B && cg + j < C) ? (ex[j] / sum - (cg + j == y ? 1.f : 0.f)) * inv_b : 0.f;
-            Ds[sm * 32 + cg + j] = d;
-            DsA[sm * 33 + cg + j] = d;
+            for (int j = 0; j < 4; ++j) {
+                const float t = keep * (w * (cg + j == ya ? 1.f : 0.f) + wb * (cg + j == yb ? 1.f : 0.f)) + u;
+                const float d = (s < B && cg + j < C) ? (ex[j] / sum - t) * inv_b : 0.f;
+                Ds[sm * 32 + cg + j] = d;
+                DsA[sm * 33 + cg + j] = d;
+            }
+        } else {
+            const int y = s < B ? labels[s] : 0;
+            float zy = 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) zy += cg + j == y ? v[j] : 0.f;
+#pragma unroll
+            for (int off = 4; off > 0; off >>= 1) zy += __shfl_xor(zy, off, 8);
+            if ((tid & 7) == 0) red[sm] = s < B ? -(zy - mx - logf(sum)) : 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float d = (s < B && cg + j < C) ? (ex[j] / sum - (cg + j == y ? 1.f : 0.f)) * inv_b : 0.f;
+                Ds[sm * 32 + cg + j] = d;
+                DsA[sm * 33 + cg + j] = d;
+            }
         }
     }
     __syncthreads();

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -59,6 +60,11 @@ struct Layer {
 
 struct Key { const void* x; const void* y; int B; float lr; const void* loss;
     bool operator<(const Key& o) const { return std::tie(x, y, B, lr, loss) < std::tie(o.x, o.y, o.B, o.lr, o.loss); } };
+// rcn_hipx_train_step_pair_dev's
+struct PairKey { const void* x; const void* ya; const void* yb; const void* w; int B; float lr; const void* loss;
+    bool operator<(const PairKey& o) const { return std::tie(x, ya, yb, w, B, lr, loss) < std::tie(o.x, o.ya, o.yb, o.w, o.B, o.lr, o.loss); } };
+// the second label of every sample and the weight of the first (a device scalar; nullptr: 1) of a step on pair labels; none: labels_b == nullptr
+struct Pair { const int32_t* labels_b = nullptr; const float* weight = nullptr; };
 
 }  // namespace
 
@@ -95,6 +101,14 @@ struct rcn_hipx_net : Selection {
     // never moved, the update launch reads it (k_reduce_all_dlr), and ONE graph per B serves every schedule
     Buf elr;
     std::map<int, hipGraphExec_t> epoch_graphs_dlr;
+    // the loss (rcn_hipx_set_loss): 0 is the hard cross-entropy through k_softmax_ce / k_head_f32<true>
+    float loss_eps = 0.f;
+    std::map<PairKey, hipGraphExec_t> pair_graphs;      // rcn_hipx_train_step_pair_dev
+    // mixed samples (rcn_hipx_train_epoch_mix_dev with records): the partners' labels beside yb and the step's target weight, allocated
+    // once and never moved; the mixed step's loss launch reads (yb, yb2, emixw), so ONE more graph per (B, lr) / per B serves every record
+    Buf yb2, emixw;
+    std::map<std::pair<int, float>, hipGraphExec_t> epoch_graphs_mix;
+    std::map<int, hipGraphExec_t> epoch_graphs_mix_dlr;
     Buf eval_part;                          // k_eval_ce: [loss partials][correct partials][counter: zero between launches]
     long long n_instantiated = 0;           // hipGraphs instantiated since the net was created (rcn_hipx_graphs_instantiated)
     bool walk_open = false;                 // between rcn_hipx_gradients_begin_dev and its last bucket: the activations belong to that walk
@@ -612,9 +626,27 @@ int ensure_loss_buf(rcn_hipx_net* n, unsigned** counter) {
     return 0;
 }
 
-int loss_and_dlogits(rcn_hipx_net* n, const int32_t* labels, int B, float* loss_dev, bool want_grad) {
+// does the step's loss take a soft target (label smoothing, pair labels)?  No: the hard kernels, launched as ever
+bool soft_loss(const rcn_hipx_net* n, const Pair& pair) { return n->loss_eps > 0.f || pair.labels_b != nullptr; }
+// ... the plan's words for it
+std::string soft_note(const rcn_hipx_net* n, const Pair& pair) {
+    char buf[64];
+    std::snprintf(buf, sizeof buf, ", label smoothing %g%s", (double)n->loss_eps, pair.labels_b ? ", pair labels" : "");
+    return buf;
+}
+
+int loss_and_dlogits(rcn_hipx_net* n, const int32_t* labels, int B, float* loss_dev, bool want_grad, const Pair& pair = Pair{}) {
     Layer& l = n->L.back();
     const int blocks = (B + 7) / 8;                       // eight samples per workgroup
+    if (soft_loss(n, pair)) {
+        if (dry_note(n, "  loss: k_softmax_ce_soft, %d workgroups%s", blocks, soft_note(n, pair).c_str())) return 0;
+        unsigned* counter = nullptr;
+        RTRY(ensure_loss_buf(n, &counter));
+        hipLaunchKernelGGL(k_softmax_ce_soft, dim3(blocks), dim3(256), 0, n->stream, (const float*)l.out.p, labels, SoftTarget{pair.labels_b, pair.weight, n->loss_eps}, B, n->classes,
+                           l.CoutP, want_grad ? (float*)l.dout.p : (float*)nullptr, (float*)n->loss_part.p, counter, 1.0f / (float)B, loss_dev);
+        XTRY(n, hipGetLastError());
+        return 0;
+    }
     if (dry_note(n, "  loss: k_softmax_ce, %d workgroups", blocks)) return 0;
     unsigned* counter = nullptr;
     RTRY(ensure_loss_buf(n, &counter));
@@ -637,11 +669,14 @@ bool head_fusable(const rcn_hipx_net* n) {
 }
 
 // logits, loss, d logits, gradient into the hidden layer below (gated by its ReLU) and the logits layer's weight-gradient partials
-int launch_head(rcn_hipx_net* n, const int32_t* labels, int B, float* loss_dev, int* chunks_out) {
+int launch_head(rcn_hipx_net* n, const int32_t* labels, int B, float* loss_dev, int* chunks_out, const Pair& pair = Pair{}) {
     Layer& l = n->L.back();
     Layer& b = n->L[n->L.size() - 2];
     const int F = l.K, blocks = (B + 31) / 32;
-    if (dry_note(n, "  head %d -> %d classes (logits, softmax + cross-entropy, gradient into the hidden layer, weight-gradient partials): k_head_f32, %d workgroups", F, n->classes, blocks)) {
+    const bool soft = soft_loss(n, pair);
+    if (soft ? dry_note(n, "  head %d -> %d classes (logits, softmax + cross-entropy, gradient into the hidden layer, weight-gradient partials): k_head_f32<true, true>, %d workgroups%s",
+                        F, n->classes, blocks, soft_note(n, pair).c_str())
+             : dry_note(n, "  head %d -> %d classes (logits, softmax + cross-entropy, gradient into the hidden layer, weight-gradient partials): k_head_f32, %d workgroups", F, n->classes, blocks)) {
         *chunks_out = blocks;
         return 0;
     }
@@ -650,6 +685,16 @@ int launch_head(rcn_hipx_net* n, const int32_t* labels, int B, float* loss_dev, 
     RTRY(ensure_loss_buf(n, &counter));
     const size_t lds = ((size_t)32 * (F + 1) + (size_t)F * 32 + (size_t)32 * (F + 32) + 4 * 1024 + 1024 + 32 * 33) * sizeof(float);
     // more than 64 KB of dynamic LDS has to be asked for (at most 127 KB here: F <= 256)
+    if (soft) {
+        static const hipError_t attr_soft = hipFuncSetAttribute((const void*)k_head_f32<true, true, SoftTarget>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        XTRY(n, attr_soft);
+        hipLaunchKernelGGL((k_head_f32<true, true, SoftTarget>), dim3(blocks), dim3(kThreads), lds, n->stream, (const float*)b.out.p, (const float*)P(n, l.w_off),
+                           (const float*)n->wt.p + l.w_off, (const float*)P(n, l.b_off), labels, B, F, n->classes, (float*)l.out.p, (float*)b.dout.p, (float*)(*n->slab_sel).p,
+                           (float*)n->loss_part.p, counter, 1.0f / (float)B, loss_dev, SoftTarget{pair.labels_b, pair.weight, n->loss_eps});
+        XTRY(n, hipGetLastError());
+        *chunks_out = blocks;
+        return 0;
+    }
     static const hipError_t attr = hipFuncSetAttribute((const void*)k_head_f32<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
     XTRY(n, attr);
     hipLaunchKernelGGL((k_head_f32<true>), dim3(blocks), dim3(kThreads), lds, n->stream, (const float*)b.out.p, (const float*)P(n, l.w_off), (const float*)n->wt.p + l.w_off,
@@ -677,7 +722,7 @@ int refresh_flipped(rcn_hipx_net* n) {
 // The front half of a step: bf16 operand copies, forward pass, loss and d logits -- where the classifier head is the fused one, k_head_f32
 // instead, which also does that layer's share of the backward pass (its slab is queued for the reduction).  *first: the layer the backward
 // walk starts at; *gated: its dout already holds dZ.
-int step_front(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float* grad, bool apply, float* loss_dev, int* first, bool* gated) {
+int step_front(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float* grad, bool apply, float* loss_dev, int* first, bool* gated, const Pair& pair = Pair{}) {
     n->jobs.njobs = 0;
     RTRY(prep_bf16_weights(n));
     const int last = (int)n->L.size() - 1;
@@ -685,27 +730,31 @@ int step_front(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, fl
     *first = *gated ? last - 1 : last;
     if (!*gated) {
         RTRY(forward(n, x, B));
-        return loss_and_dlogits(n, labels, B, loss_dev, true);
+        return loss_and_dlogits(n, labels, B, loss_dev, true, pair);
     }
     RTRY(forward(n, x, B, (size_t)last));
     int chunks = 0;
     n->slab_sel = &n->L[last].slab;
-    RTRY(launch_head(n, labels, B, loss_dev, &chunks));
+    RTRY(launch_head(n, labels, B, loss_dev, &chunks, pair));
     return reduce_slab(n, (size_t)last, chunks, 1, ConvShape{B, 1, 1, n->L[last].K, n->L[last].CoutP}, grad, apply);
 }
 
 // forward + loss + backward of one batch: parameters updated in place (apply) or gradients written to grad (padded layout)
-// (lr_dev, nullable: the update's rate comes from that device scalar instead of lr)
-int step_core(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float lr, float* grad, bool apply, float* loss_dev, const float* lr_dev = nullptr) {
+// (lr_dev, nullable: the update's rate comes from that device scalar instead of lr; pair: a step on pair labels)
+int step_core(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float lr, float* grad, bool apply, float* loss_dev, const float* lr_dev = nullptr,
+              const Pair& pair = Pair{}) {
     int first = 0;
     bool gated = false;
-    RTRY(step_front(n, x, labels, B, grad, apply, loss_dev, &first, &gated));
+    RTRY(step_front(n, x, labels, B, grad, apply, loss_dev, &first, &gated, pair));
     return backward(n, x, B, lr, grad, apply, first, gated, lr_dev);
 }
 
 template <typename M> void drop_all(M& graphs) { for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second); graphs.clear(); }
 // every captured graph of the net: the steps on callers' pointers and the epoch's steps on the net's own batch buffer
-void drop_graphs(rcn_hipx_net* n) { drop_all(n->graphs); drop_all(n->epoch_graphs); drop_all(n->epoch_graphs_dlr); }
+void drop_graphs(rcn_hipx_net* n) {
+    drop_all(n->graphs); drop_all(n->epoch_graphs); drop_all(n->epoch_graphs_dlr);
+    drop_all(n->pair_graphs); drop_all(n->epoch_graphs_mix); drop_all(n->epoch_graphs_mix_dlr);
+}
 
 // ---- gradient buckets: the data-parallel step with its all-reduce overlapped with the backward pass -------------------------------------
 // The layers with parameters, walked from the last to the first (the order the backward pass finishes them), are cut into buckets of at
@@ -824,11 +873,12 @@ int make_dry_net(rcn_hipx_net& net, int in_h, int in_w, int in_c, const rcn_hipx
     seed_options(net.opt);
     return describe_layers(&net, in_h, in_w, in_c, layers, n_layers);
 }
-// ... or from an existing net: its layers, precision, tiling, options and optimiser -- the plan and the step agree by construction
+// ... or from an existing net: its layers, precision, tiling, options, optimiser and loss -- the plan and the step agree by construction
 void make_dry_net(rcn_hipx_net& net, const rcn_hipx_net& from, int batch) {
     net.in_h = from.in_h; net.in_w = from.in_w; net.in_c = from.in_c; net.max_batch = batch; net.classes = from.classes; net.dry = true;
     static_cast<Selection&>(net) = from;
     net.sgd_mu = from.sgd_mu; net.sgd_wd = from.sgd_wd; net.sgd_nesterov = from.sgd_nesterov;
+    net.loss_eps = from.loss_eps;
     copy_layer_table(net, from);
 }
 
@@ -886,7 +936,7 @@ void rcn_hipx_destroy(rcn_hipx_net* n) {
         if (n->stream) (void)hipStreamSynchronize(n->stream);
         drop_graphs(n);
         for (Layer& l : n->L) { l.out.release(); l.idx.release(); l.dout.release(); l.slab.release(); }
-        for (Buf* b : {&n->params, &n->wt, &n->wb16, &n->dz, &n->loss_part, &n->grad_tmp, &n->dlogits, &n->skbuf, &n->wb, &n->vel, &n->xb, &n->yb, &n->eloss, &n->elr, &n->eval_part}) b->release();
+        for (Buf* b : {&n->params, &n->wt, &n->wb16, &n->dz, &n->loss_part, &n->grad_tmp, &n->dlogits, &n->skbuf, &n->wb, &n->vel, &n->xb, &n->yb, &n->eloss, &n->elr, &n->yb2, &n->emixw, &n->eval_part}) b->release();
         if (n->side) { (void)hipStreamSynchronize(n->side); (void)hipStreamDestroy(n->side); }
         for (hipEvent_t e : n->events) (void)hipEventDestroy(e);
         if (n->own_stream && n->stream) (void)hipStreamDestroy(n->stream);
@@ -1012,11 +1062,12 @@ int rcn_hipx_forward_dev(rcn_hipx_net* n, const float* x, int B, float* logits) 
 
 // One eager step (it sizes every scratch buffer outside capture: hipMalloc is illegal while capturing -- and it IS the caller's step),
 // then the same step captured and instantiated for the replays that follow.
-static int step_and_capture(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float lr, float* loss_dev, hipGraphExec_t* exec_out, const float* lr_dev = nullptr) {
-    RTRY(step_core(n, x, labels, B, lr, nullptr, true, loss_dev, lr_dev));
+static int step_and_capture(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float lr, float* loss_dev, hipGraphExec_t* exec_out, const float* lr_dev = nullptr,
+                            const Pair& pair = Pair{}) {
+    RTRY(step_core(n, x, labels, B, lr, nullptr, true, loss_dev, lr_dev, pair));
     hipGraph_t graph = nullptr;
     XTRY(n, hipStreamBeginCapture(n->stream, hipStreamCaptureModeThreadLocal));
-    const int st = step_core(n, x, labels, B, lr, nullptr, true, loss_dev, lr_dev);
+    const int st = step_core(n, x, labels, B, lr, nullptr, true, loss_dev, lr_dev, pair);
     hipError_t e = hipStreamEndCapture(n->stream, &graph);
     if (st != 0) { if (graph) (void)hipGraphDestroy(graph); return st; }
     XTRY(n, e);
@@ -1047,6 +1098,24 @@ int rcn_hipx_train_step_dev(rcn_hipx_net* n, const float* x, const int32_t* labe
     return 0;
 }
 
+int rcn_hipx_train_step_pair_dev(rcn_hipx_net* n, const float* x, const int32_t* labels_a, const int32_t* labels_b, const float* weight, int B, float lr, float* loss_dev) {
+    if (!n || !x || !labels_a || !labels_b) return -1;
+    RTRY(ensure_batch(n, B));
+    Dev g(n->device);
+    n->walk_open = false;
+    const PairKey key{x, labels_a, labels_b, weight, B, lr, loss_dev};
+    auto it = n->pair_graphs.find(key);
+    if (it == n->pair_graphs.end()) {
+        hipGraphExec_t exec = nullptr;
+        RTRY(step_and_capture(n, x, labels_a, B, lr, loss_dev, &exec, nullptr, Pair{labels_b, weight}));
+        if (n->pair_graphs.size() >= 8) drop_all(n->pair_graphs);
+        n->pair_graphs.emplace(key, exec);
+        return 0;                                       // the eager step WAS this call's step
+    }
+    XTRY(n, hipGraphLaunch(it->second, n->stream));
+    return 0;
+}
+
 // ---- the loop around the step: an epoch over a device-resident set, and evaluation --------------------------------------------------------
 namespace {
 
@@ -1061,6 +1130,13 @@ int ensure_epoch_bufs(rcn_hipx_net* n) {
     XTRY(n, n->elr.ensure(sizeof(float)));
     return 0;
 }
+// ... and, for mixed samples, the partners' labels and the target weight
+int ensure_mix_bufs(rcn_hipx_net* n) {
+    XTRY(n, n->yb2.ensure((size_t)n->max_batch * sizeof(int32_t)));
+    XTRY(n, n->emixw.ensure(sizeof(float)));
+    return 0;
+}
+static_assert(sizeof(rcn_hipx_mix_step) == 24 && sizeof(MixStep) == 24 && offsetof(rcn_hipx_mix_step, y0) == offsetof(MixStep, y0), "MixStep is rcn_hipx_mix_step");
 
 // nullptr, or why this rcn_hipx_augment is refused for a net of this input shape (H = W = 0: the shape-free part, for the host draw)
 const char* augment_refusal(const rcn_hipx_augment* a, int H, int W) {
@@ -1071,15 +1147,32 @@ const char* augment_refusal(const rcn_hipx_augment* a, int H, int W) {
 }
 
 // rows idx[0 .. B) (idx == NULL: base .. base + B - 1) of the set into dst ([B][row] fp32), their labels (nullable) into ydst; aug
-// (nullable): through the augmentation, row r drawing with q0 + r.  The launch is select_gather's (convnet_epoch.hpp).
+// (nullable): through the augmentation, row r drawing with q0 + r.  mix (nullable; one record on the device): mixed with the mirrored row
+// of the batch, whose labels go to ydst_b.  The launch is select_gather's (convnet_epoch.hpp).
 int launch_gather(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, long long rows, const int32_t* idx, long long base, int B,
-                  const rcn_hipx_augment* aug, unsigned long long q0, float* dst, int* ydst) {
+                  const rcn_hipx_augment* aug, unsigned long long q0, float* dst, int* ydst, const rcn_hipx_mix_step* mix = nullptr, int* ydst_b = nullptr) {
     const int E = (int)row_elems(n);
     const RowScale rs{x_scale, x_shift};
     const bool u8 = x_kind == RCN_HIPX_X_U8;
     const bool dry = n->dry;                            // (a plan: the set and the batch buffer are taken to be aligned, as allocators return them)
-    const GatherChoice c = select_gather(u8, B, E, dry || (uintptr_t)X % 16 == 0, dry || (uintptr_t)dst % 16 == 0, aug != nullptr);
+    const GatherChoice c = select_gather(u8, B, E, dry || (uintptr_t)X % 16 == 0, dry || (uintptr_t)dst % 16 == 0, aug != nullptr, mix != nullptr);
     if (!c.blocks) return fail(n, -3, "a batch of more than 2^37 elements");
+    if (mix) {
+        char augtext[48] = "no augmentation";
+        if (aug) std::snprintf(augtext, sizeof augtext, "augment pad %d hflip %d", (int)aug->pad, (int)aug->hflip);
+        if (dry_note(n, "  gather: k_gather_mix<%s, %d>, %s, %lld workgroups, partner row B - 1 - r, %s", u8 ? "uint8" : "float", c.vec,
+                     c.vec == 4 ? "one or two source elements per output, 16-byte stores" : "element by element", c.blocks, augtext)) return 0;
+        const AugSpec as = aug ? AugSpec{aug->seed, aug->epoch, aug->pad, aug->hflip} : AugSpec{0, 0, 0, 0};
+        const dim3 grid((unsigned)c.blocks), block(kGatherThreads);
+        const int H = n->in_h, W = n->in_w, Cc = n->in_c, has_aug = aug ? 1 : 0;
+        const MixStep* const m = reinterpret_cast<const MixStep*>(mix);
+        if (u8 && c.vec == 4) hipLaunchKernelGGL((k_gather_mix<uint8_t, 4>), grid, block, 0, n->stream, (const uint8_t*)X, labels, rows, idx, base, B, H, W, Cc, rs, has_aug, as, q0, m, dst, ydst, ydst_b);
+        else if (u8) hipLaunchKernelGGL((k_gather_mix<uint8_t, 1>), grid, block, 0, n->stream, (const uint8_t*)X, labels, rows, idx, base, B, H, W, Cc, rs, has_aug, as, q0, m, dst, ydst, ydst_b);
+        else if (c.vec == 4) hipLaunchKernelGGL((k_gather_mix<float, 4>), grid, block, 0, n->stream, (const float*)X, labels, rows, idx, base, B, H, W, Cc, rs, has_aug, as, q0, m, dst, ydst, ydst_b);
+        else hipLaunchKernelGGL((k_gather_mix<float, 1>), grid, block, 0, n->stream, (const float*)X, labels, rows, idx, base, B, H, W, Cc, rs, has_aug, as, q0, m, dst, ydst, ydst_b);
+        XTRY(n, hipGetLastError());
+        return 0;
+    }
     if (aug) {
         if (dry_note(n, "  gather: k_gather_aug<%s, %d>, %s, %lld workgroups, augment pad %d hflip %d", u8 ? "uint8" : "float", c.vec,
                      c.vec == 4 ? "one source element per output, 16-byte stores" : "element by element", c.blocks, (int)aug->pad, (int)aug->hflip)) return 0;
@@ -1138,8 +1231,26 @@ int plan_eval_walk(rcn_hipx_net& net, int batch) {
 
 }  // namespace
 
-int rcn_hipx_train_epoch_ex_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows, const int32_t* perm,
-                                int B, int64_t first_batch, int64_t n_batches, float lr, const float* lr_dev, const rcn_hipx_augment* aug, float* loss_dev) {
+extern "C++" {                                          // (a template, inside the header's extern "C" block)
+namespace {
+// One step of an epoch on the net's own buffers: the eager step and its capture at the first use of `key`, a replay afterwards.  (The
+// graphs are looked up per step: the eager step of a first use can grow a scratch buffer, which drops every graph.)
+template <typename M, typename K>
+int epoch_step(rcn_hipx_net* n, M& graphs, const K& key, int B, float lr, const float* lr_dev, const Pair& pair) {
+    auto it = graphs.find(key);
+    if (it != graphs.end()) { XTRY(n, hipGraphLaunch(it->second, n->stream)); return 0; }
+    hipGraphExec_t exec = nullptr;
+    RTRY(step_and_capture(n, (const float*)n->xb.p, (const int32_t*)n->yb.p, B, lr, (float*)n->eloss.p, &exec, lr_dev, pair));
+    if (graphs.size() >= 8) drop_all(graphs);           // (eight keys: a caller that varies lr per call)
+    graphs.emplace(key, exec);
+    return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int rcn_hipx_train_epoch_mix_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows, const int32_t* perm,
+                                 int B, int64_t first_batch, int64_t n_batches, float lr, const float* lr_dev, const rcn_hipx_augment* aug, const rcn_hipx_mix_step* mix_dev,
+                                 float* loss_dev) {
     if (!n) return -1;
     if (!X || !labels) return fail(n, -1, "train_epoch: X_dev and labels_dev must not be NULL");
     if (!x_kind_ok(x_kind)) return fail(n, -1, "train_epoch: x_kind must be RCN_HIPX_X_F32 or RCN_HIPX_X_U8");
@@ -1150,41 +1261,32 @@ int rcn_hipx_train_epoch_ex_dev(rcn_hipx_net* n, const void* X, int x_kind, floa
     if (n_batches == 0) return 0;
     Dev g(n->device);
     RTRY(ensure_epoch_bufs(n));
+    if (mix_dev) RTRY(ensure_mix_bufs(n));
     n->walk_open = false;
     float* const xb = (float*)n->xb.p;
     int32_t* const yb = (int32_t*)n->yb.p;
     float* const el = (float*)n->eloss.p;
     float* const elr = (float*)n->elr.p;
+    // mixed: the step's loss launch reads the net's own two labels buffers and its weight scalar
+    const Pair pair = mix_dev ? Pair{(const int32_t*)n->yb2.p, (const float*)n->emixw.p} : Pair{};
     const std::pair<int, float> key{B, lr};
     for (int64_t s = first_batch; s < first_batch + n_batches; ++s) {
-        RTRY(launch_gather(n, X, x_kind, x_scale, x_shift, labels, (long long)rows, perm ? perm + s * B : nullptr, (long long)s * B, B, aug, (unsigned long long)s * (unsigned long long)B, xb, yb));
-        // (the graphs are looked up per step: the eager step of a first use can grow a scratch buffer, which drops every graph)
-        if (lr_dev) {
-            // the step's rate into the net's scalar, outside the graph: the eager step and every replay read it there
-            XTRY(n, hipMemcpyAsync(elr, lr_dev + (s - first_batch), sizeof(float), hipMemcpyDeviceToDevice, n->stream));
-            auto it = n->epoch_graphs_dlr.find(B);
-            if (it == n->epoch_graphs_dlr.end()) {
-                hipGraphExec_t exec = nullptr;
-                RTRY(step_and_capture(n, xb, yb, B, 0.f, el, &exec, elr));
-                if (n->epoch_graphs_dlr.size() >= 8) drop_all(n->epoch_graphs_dlr);
-                n->epoch_graphs_dlr.emplace(B, exec);
-            } else {
-                XTRY(n, hipGraphLaunch(it->second, n->stream));
-            }
-        } else {
-            auto it = n->epoch_graphs.find(key);
-            if (it == n->epoch_graphs.end()) {
-                hipGraphExec_t exec = nullptr;
-                RTRY(step_and_capture(n, xb, yb, B, lr, el, &exec));
-                if (n->epoch_graphs.size() >= 8) drop_all(n->epoch_graphs);     // (eight (B, lr) pairs: a caller that varies lr per call)
-                n->epoch_graphs.emplace(key, exec);
-            } else {
-                XTRY(n, hipGraphLaunch(it->second, n->stream));
-            }
-        }
+        const rcn_hipx_mix_step* const rec = mix_dev ? mix_dev + (s - first_batch) : nullptr;
+        RTRY(launch_gather(n, X, x_kind, x_scale, x_shift, labels, (long long)rows, perm ? perm + s * B : nullptr, (long long)s * B, B, aug, (unsigned long long)s * (unsigned long long)B, xb, yb,
+                           rec, (int*)n->yb2.p));
+        // the step's rate (and target weight) into the net's scalars, outside the graph: the eager step and every replay read them there
+        if (lr_dev) XTRY(n, hipMemcpyAsync(elr, lr_dev + (s - first_batch), sizeof(float), hipMemcpyDeviceToDevice, n->stream));
+        if (rec) XTRY(n, hipMemcpyAsync(n->emixw.p, &rec->weight, sizeof(float), hipMemcpyDeviceToDevice, n->stream));
+        if (lr_dev) RTRY(mix_dev ? epoch_step(n, n->epoch_graphs_mix_dlr, B, B, 0.f, elr, pair) : epoch_step(n, n->epoch_graphs_dlr, B, B, 0.f, elr, pair));
+        else RTRY(mix_dev ? epoch_step(n, n->epoch_graphs_mix, key, B, lr, nullptr, pair) : epoch_step(n, n->epoch_graphs, key, B, lr, nullptr, pair));
         if (loss_dev) XTRY(n, hipMemcpyAsync(loss_dev + (s - first_batch), el, sizeof(float), hipMemcpyDeviceToDevice, n->stream));
     }
     return 0;
+}
+
+int rcn_hipx_train_epoch_ex_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows, const int32_t* perm,
+                                int B, int64_t first_batch, int64_t n_batches, float lr, const float* lr_dev, const rcn_hipx_augment* aug, float* loss_dev) {
+    return rcn_hipx_train_epoch_mix_dev(n, X, x_kind, x_scale, x_shift, labels, rows, perm, B, first_batch, n_batches, lr, lr_dev, aug, nullptr, loss_dev);
 }
 
 int rcn_hipx_train_epoch_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows, const int32_t* perm,
@@ -1205,6 +1307,19 @@ int rcn_hipx_gather_batch_dev(rcn_hipx_net* n, const void* X, int x_kind, float 
     const bool with_labels = labels && labels_out;
     return launch_gather(n, X, x_kind, x_scale, x_shift, with_labels ? labels : nullptr, (long long)rows, idx, (long long)base, B, aug, (unsigned long long)q0, x_out,
                          with_labels ? labels_out : nullptr);
+}
+
+int rcn_hipx_gather_mix_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows, const int32_t* idx, int64_t base,
+                            int B, const rcn_hipx_augment* aug, uint64_t q0, const rcn_hipx_mix_step* mix_dev, float* x_out, int32_t* labels_out, int32_t* labels_b_out) {
+    if (!n) return -1;
+    if (!X || !x_out || !mix_dev) return fail(n, -1, "gather_mix: X_dev, mix_dev and x_out_dev must not be NULL");
+    if (!x_kind_ok(x_kind)) return fail(n, -1, "gather_mix: x_kind must be RCN_HIPX_X_F32 or RCN_HIPX_X_U8");
+    RTRY(ensure_batch(n, B));
+    if (rows < 1) return fail(n, -1, "gather_mix: n must be at least 1");
+    if (!idx && (base < 0 || base > rows - B)) return fail(n, -1, "gather_mix: without idx_dev, rows base .. base + B - 1 must lie inside the set");
+    if (aug) { const char* why = augment_refusal(aug, n->in_h, n->in_w); if (why) return fail(n, -1, std::string("gather_mix: ") + why); }
+    Dev g(n->device);
+    return launch_gather(n, X, x_kind, x_scale, x_shift, labels, (long long)rows, idx, (long long)base, B, aug, (unsigned long long)q0, x_out, labels_out, mix_dev, labels_b_out);
 }
 
 int rcn_hipx_augment_draw(const rcn_hipx_augment* aug, uint64_t q, int* dy, int* dx, int* flip) {
@@ -1311,6 +1426,23 @@ int rcn_hipx_set_sgd(rcn_hipx_net* n, float momentum, float weight_decay, int ne
     }
     drop_graphs(n);                                     // captured graphs bake in the update kernel and its arguments
     n->sgd_mu = momentum; n->sgd_wd = weight_decay; n->sgd_nesterov = nesterov;
+    return 0;
+}
+
+int rcn_hipx_set_loss(rcn_hipx_net* n, float label_smoothing) {
+    if (!n) return -1;
+    if (!(std::isfinite(label_smoothing) && label_smoothing >= 0.f && label_smoothing < 1.f)) return fail(n, -1, "set_loss: label_smoothing must be finite and in [0, 1)");
+    if (label_smoothing == n->loss_eps) return 0;
+    Dev g(n->device);
+    XTRY(n, hipStreamSynchronize(n->stream));
+    drop_graphs(n);                                     // captured graphs bake in the loss kernel and its arguments
+    n->loss_eps = label_smoothing;
+    return 0;
+}
+
+int rcn_hipx_get_loss(const rcn_hipx_net* n, float* label_smoothing) {
+    if (!n) return -1;
+    if (label_smoothing) *label_smoothing = n->loss_eps;
     return 0;
 }
 
@@ -1426,27 +1558,36 @@ int rcn_hipx_plan_net(const rcn_hipx_net* n, int batch, char* out, int cap) {
     return st;
 }
 
-// One step of an epoch of an EXISTING net (rcn_hipx_train_epoch_ex_dev): what is launched around the captured graph -- the gather, the copy
-// of a scheduled rate -- the graph's key, then the step's own plan (rcn_hipx_plan_net's walk; the _dlr update kernel for a scheduled rate).
-int rcn_hipx_plan_epoch_net(const rcn_hipx_net* n, int batch, int x_kind, int lr_from_device, const rcn_hipx_augment* aug, char* out, int cap) {
+// One step of an epoch of an EXISTING net (rcn_hipx_train_epoch_mix_dev): what is launched around the captured graph -- the gather, the copy
+// of a scheduled rate, the copy of a mixed step's target weight -- the graph's key, then the step's own plan (rcn_hipx_plan_net's walk; the _dlr update kernel for a scheduled rate).
+int rcn_hipx_plan_epoch_mix_net(const rcn_hipx_net* n, int batch, int x_kind, int lr_from_device, const rcn_hipx_augment* aug, int mix, char* out, int cap) {
     if (!n || batch < 1 || batch > n->max_batch || !out || cap < 1) return -1;
-    if (!x_kind_ok(x_kind) || (lr_from_device != 0 && lr_from_device != 1)) return -1;
+    if (!x_kind_ok(x_kind) || (lr_from_device != 0 && lr_from_device != 1) || (mix != 0 && mix != 1)) return -1;
     if (aug) { const char* why = augment_refusal(aug, n->in_h, n->in_w); if (why) { std::snprintf(out, (size_t)cap, "%s", why); return -1; } }
     rcn_hipx_net net;
     make_dry_net(net, *n, batch);
     net.plan = "one step of an epoch over a resident " + std::string(x_kind == RCN_HIPX_X_U8 ? "uint8" : "fp32") + " set at batch " + std::to_string(batch) +
                ": the launches around the captured graph, its key, then the graph's own launches:\n";
     const float* const marker = reinterpret_cast<const float*>(sizeof(float));      // (dry run: no buffers; any non-null marks "the rate comes from the device")
-    int st = launch_gather(&net, nullptr, x_kind, 1.f, 0.f, nullptr, 1, nullptr, 0, batch, aug, 0, nullptr, nullptr);
+    // (... and "a record" / "pair labels")
+    const rcn_hipx_mix_step* const rec = mix ? reinterpret_cast<const rcn_hipx_mix_step*>(sizeof(float)) : nullptr;
+    const Pair pair = mix ? Pair{reinterpret_cast<const int32_t*>(sizeof(float)), marker} : Pair{};
+    int st = launch_gather(&net, nullptr, x_kind, 1.f, 0.f, nullptr, 1, nullptr, 0, batch, aug, 0, nullptr, nullptr, rec, nullptr);
     if (st == 0) {
         if (lr_from_device) (void)dry_note(&net, "  lr: 4-byte device copy of lr_dev[i] into the net's rate scalar (hipMemcpyAsync, outside the graph)");
-        (void)dry_note(&net, lr_from_device ? "  graph: one graph per B, lr from device" : "  graph: one graph per (B, lr)");
+        if (mix) (void)dry_note(&net, "  weight: 4-byte device copy of mix_dev[i].weight into the net's target-weight scalar (hipMemcpyAsync, outside the graph)");
+        if (mix) (void)dry_note(&net, lr_from_device ? "  graph: one graph per B, lr from device, pair labels" : "  graph: one graph per (B, lr), pair labels");
+        else (void)dry_note(&net, lr_from_device ? "  graph: one graph per B, lr from device" : "  graph: one graph per (B, lr)");
         net.plan += "forward + loss + backward of one batch of " + std::to_string(batch) + " (" + precision_name(net.precision, net.store16) + "), launch by launch:\n";
-        st = step_core(&net, nullptr, nullptr, batch, 0.f, nullptr, true, nullptr, lr_from_device ? marker : nullptr);
+        st = step_core(&net, nullptr, nullptr, batch, 0.f, nullptr, true, nullptr, lr_from_device ? marker : nullptr, pair);
     }
     const std::string& text = st == 0 ? net.plan : net.err;
     std::snprintf(out, (size_t)cap, "%s", text.c_str());
     return st;
+}
+
+int rcn_hipx_plan_epoch_net(const rcn_hipx_net* n, int batch, int x_kind, int lr_from_device, const rcn_hipx_augment* aug, char* out, int cap) {
+    return rcn_hipx_plan_epoch_mix_net(n, batch, x_kind, lr_from_device, aug, 0, out, cap);
 }
 
 // rcn_hipx_plan's dry walk for ONE evaluation chunk: the forward pass over all layers and the evaluation kernel.  A net that
