@@ -166,7 +166,8 @@ int  rcn_hip_train_epoch_dev(rcn_hip_ctx* ctx, const void* X_dev, const void* Y_
  * pass into perm_dev (each pass is rcn.rs:146-149 once). */
 int  rcn_hip_prepare_epoch_dev(rcn_hip_ctx* ctx, const void* X_dev, const void* Y_dev, const int32_t* perm_dev,
                                size_t B, size_t n_batches, double eta, void* loss_dev);
-/* (Opt-in form, option "xcd_gather" = 1; measured slower than the packed image on MI355X -- csrc/rcn_hip_api_xcd.ipp.)
+/* (Opt-in form, option "xcd_gather" = 1; measured slower than the packed image on MI355X, 6.64 against 6.17 us per step in the epoch
+ * loop at B = 256 once both forms fetch their rows behind the delta_1 staging barrier -- csrc/rcn_hip_api_xcd.ipp.)
  * 1 when rcn_hip_train_epoch_dev at this batch size runs on the resident one-XCD kernel in its GATHER form: no packed epoch image is
  * written -- one launch walks the whole call and every worker fetches its 128 bytes of each row of the batch after next while it
  * works on the current one (csrc/dense_xcd.hpp).  The feature matrix is then read from memory exactly once per step and
@@ -347,7 +348,8 @@ const char* rcn_hip_last_timeout_text(const rcn_hip_ctx* ctx);
  *                                                               launch are its workers -- 0..7: blockIdx.x % 8 == value; 8..15: the blocks that landed on
  *                                                               PHYSICAL XCD value - 8 (which XCD a dispatch starts its round-robin on differs from queue
  *                                                               to queue: profiles/r4_dp_4rank_timeout_record.txt); a GPU per rank keeps 0
- *   "xcd_gather"          RCN_HIP_XCD_GATHER          0 | 1     rows fetched by the resident kernel itself, batch 256 (measured slower; 0)
+ *   "xcd_gather"          RCN_HIP_XCD_GATHER          0 | 1     rows fetched by the resident kernel itself, batch 256 (re-measured with its indices a step ahead:
+ *                                                               still 0.47 us per step slower than the packed image; 0)
  *   "xcd_timeout_ticks"   RCN_HIP_XCD_TIMEOUT_TICKS   >= 1      bound of every wait inside the resident kernel, 100 MHz ticks (20000000 = 0.2 s)
  *   "xcd_exact_lds"       RCN_HIP_XCD_EXACT_LDS       0 | 1     TEST-ONLY (same harness): the resident kernel asks for exactly the LDS it uses, so that
  *                                                               two contexts' kernels fit on one device at batches <= 64 (0: one worker per CU)

@@ -415,6 +415,14 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
     // on half the threads -- nothing to gain, and the epoch loop at B = 32 measured 0.03 us slower with both.
     constexpr bool kWaveWaits = sizeof(T) == 4 && !PH && BT >= 64;
     constexpr bool kLateCopy = sizeof(T) == 4 && !PH && !SB && BT >= 64;
+    // The batch after next fetched behind the delta_1 staging barrier instead of at the step top, and wave 6's targets fetched a step
+    // ahead (both below): nothing that comes from HBM is then in flight in front of the step-top polls and barrier.  The single-GPU f32
+    // forms for 64 samples and more, as above.  The data-parallel forms keep the step-top prefetch: at 256 samples the form sits at 256
+    // VGPRs and either change puts 32 bytes of scratch into it, and the others were not measured on more than one GPU.
+    constexpr bool kLatePrefetch = sizeof(T) == 4 && !PH && !SB && !DP && BT >= 64;
+    constexpr bool kLateTargets = kLatePrefetch;
+    // (gather form: the row indices a step ahead of the rows -- needs the late issue point, where a step's slack is)
+    constexpr bool kGatherAhead = GA && kLatePrefetch;
     static_assert(!PH || DP, "the phase clocks exist for the data-parallel form");
     constexpr int ES = (int)sizeof(T), VS = 4 * ES;                  // bytes of an element / of a quadruple in the L2 buffers
     constexpr int RI = sizeof(T) == 4 ? 1 : 4;                       // Mfma16<T>::row(lane, i) = row(lane, 0) + RI * i
@@ -531,6 +539,27 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
         const vec4 v = *reinterpret_cast<const vec4*>(xs_all + (size_t)row * F + (col < F ? col : 0));
         return (sl < nsl && col < F) ? v : vec4{0, 0, 0, 0};
     };
+    // kGatherAhead: the same elements with the row indices fetched ahead of the rows.  Thread tid's four pieces tid + 512 r of a batch
+    // are chunk tid % 4 of two samples (tid / 4 and tid / 4 + 128: r & 1) in the two slices (r >> 1), so a thread needs TWO row indices
+    // per batch: grow[] holds those of the next batch to fetch, loaded a step before its rows are, and the row loads are four loads
+    // with nothing but a multiply-add in front of them (xrow4: an index load and the row load through it, two round trips in a row).
+    static_assert(!GA || (kXcdThreads == 512 && kXcdSl == 2), "the gather form's element map");
+    unsigned grow[2] = {0u, 0u};
+    auto gidx = [&](int b, unsigned (&g)[2]) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const unsigned at = (unsigned)(b * B + (tid >> 2) + 128 * k);
+            g[k] = gperm ? (unsigned)gperm[at] : at;
+        }
+    };
+    auto grows4 = [&](const unsigned (&g)[2], vec4 (&x)[4]) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int sl = r >> 1, col = (kXcdSl * w + sl) * 16 + 4 * (tid & 3);
+            const vec4 v = *reinterpret_cast<const vec4*>(xs_all + (size_t)g[r & 1] * F + (col < F ? col : 0));
+            x[r] = (sl < nsl && col < F) ? v : vec4{0, 0, 0, 0};
+        }
+    };
     T* W0 = params + nd.w_off[0];
     const int mt = tid >> 8;                                        // (tail tiles: M-tile of this thread's parameter)
     const int tl = wave & 3, kh = wave >> 2, usl = tl >> 1, umt = tl & 1;
@@ -553,6 +582,24 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
         }
         // batches 0 and 1 of this launch: [slice pair][sample][16] is one contiguous run of nsl * B * 16 floats per batch
         // (in LDS a slice holds BT rows: rows B .. BT-1, and a missing second slice, are zeros)
+        if constexpr (kGatherAhead) {
+            // (the indices of batches 0, 1 and 2 first, then the rows of 0 and 1: two round trips, not four)
+            unsigned g0[2] = {0u, 0u}, g1[2] = {0u, 0u};
+            gidx(0, g0);
+            if (nb > 1) gidx(1, g1);
+            if (nb > 2) gidx(2, grow);
+            vec4 x0[4], x1[4];
+            grows4(g0, x0);
+            if (nb > 1) grows4(g1, x1);
+            vec4* dst = reinterpret_cast<vec4*>(xbuf);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dst[tid + r * kXcdThreads] = x0[r];
+            if (nb > 1) {
+                dst = reinterpret_cast<vec4*>(xbuf + kXs);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) dst[tid + r * kXcdThreads] = x1[r];
+            }
+        } else
         for (int b = 0; b < (SB ? 1 : 2) && b < nb; ++b) {
             vec4* dst = reinterpret_cast<vec4*>(xbuf + (size_t)(b & 1) * kXs);
             if constexpr (gather) {
@@ -650,6 +697,24 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
         const unsigned at = (unsigned)(w * kP2Ts + (n & 7));
         yrow = gperm ? (unsigned)gperm[at] : at;
     }
+    // kLateTargets: wave 6 of a sample group holds the four target words of its lane for the NEXT step in registers (fetched behind the
+    // barriers of the group's first half, a step ahead), so that no load from HBM stands in front of the step-top barrier
+    T ynext[4] = {0, 0, 0, 0};
+    auto targets = [&](int jb) {                                      // (gather form: yrow is batch jb's row; then the row of batch jb + 1)
+        const int s0 = w * kP2Ts;
+        const int srow = (FULL || s0 + (n & 7) < B) ? s0 + (n & 7) : B - 1;
+        const T* Ys = gather ? ys_all + (size_t)yrow * C : ys_all + (size_t)jb * ys_stride + (size_t)srow * C;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = Mfma16<T>::row(lane, i);
+            ynext[i] = Ys[c < C ? c : 0];
+        }
+        if (gather && jb + 1 < nb) {
+            const unsigned at = (unsigned)((jb + 1) * B + s0 + (n & 7));
+            yrow = gperm ? (unsigned)gperm[at] : at;
+        }
+    };
+    if constexpr (kLateTargets) { if (is_s && wave == 6) targets(0); }
     long long ph_x = 0, ph_t0 = 0;                                    // (PH) ticks inside the exchange; the loop's start
     if constexpr (PH) { if (tid == 0) ph_t0 = wall_clock64(); }
     for (int j = 0; j < nb; ++j) {
@@ -657,7 +722,8 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
         if (j == 8) XCLOCK(0);
         if (j == nb - 8) XCLOCK(1);
         const bool more = j + 1 < nb;
-        // (1) the batch after next, a whole step ahead: into registers now, into the LDS buffer step j's gradient frees
+        // (1) the batch after next, a whole step ahead: into registers (here, or -- kLatePrefetch -- behind the delta_1 staging barrier),
+        // then into the LDS buffer step j's gradient frees
         constexpr int XR = (kXcdSl * BT * 4 + kXcdThreads - 1) / kXcdThreads;      // 16-byte pieces of a batch's slice pair per thread: 4 at BT = 256
         vec4 xr[XR];
         const bool pre = is_a && (SB ? j + 1 < nb : j + 2 < nb);       // (SB: the NEXT batch, fetched further down, under the gradient MFMAs)
@@ -669,6 +735,10 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                 xr[r] = (sl < nsl && (rr >> 2) < B) ? src[sl * B * 4 + rr] : vec4{0, 0, 0, 0};
             }
         };
+        // (kLatePrefetch: not here.  A wave's vector loads return in order and a workgroup barrier waits for all of them, so wave 0's
+        // first look at the flags, wave 6's targets and the barrier in front of the slab loads would all wait for these four 16-byte
+        // loads from HBM: they are issued behind the delta_1 staging barrier instead, under the gradient MFMAs.)
+        if constexpr (!kLatePrefetch)
         if (pre && !SB) {
             if constexpr (gather) {
 #pragma unroll
@@ -712,6 +782,10 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                 }
                 XSTAMP(1);
             } else if (wave == 6) {                                   // targets per accumulator element: no flag to wait for
+                if constexpr (kLateTargets) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) frag[i * 64 + lane] = ynext[i];
+                } else {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int c = Mfma16<T>::row(lane, i);
@@ -720,6 +794,7 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                 if (gather && more) {                                 // the next step's row of this lane's sample: its index a step ahead
                     const unsigned at = (unsigned)((j + 1) * B + s0 + (n & 7));
                     yrow = gperm ? (unsigned)gperm[at] : at;
+                }
                 }
             }
             __syncthreads();
@@ -740,6 +815,7 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
             zred[wave * 64 + lane] = z;
             if (wave == 7) XSTAMP(2);
             __syncthreads();
+            if constexpr (kLateTargets) { if (wave == 6 && more) targets(j + 1); }      // (behind both barriers of the group's first half)
             if (wave == 0) {
                 XSTAMP(3);
                 {   // fixed order across waves (as k_p2_b)
@@ -949,6 +1025,25 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
             if (kWaveWaits && dh == 0 && s_abort) return;                  // (a wave's own wait expired: everybody leaves here)
             if (wave == 1 && dh == 0) XSTAMP(8);
             if constexpr (SB) { if (dh == 0 && pre) prefetch(j + 1); }
+            // (kLatePrefetch: the batch after next into registers here -- the next barrier, which waits for these loads, is the one
+            // behind the update, a gradient's worth of MFMAs away, and waves 4..7 have nothing else to do until then)
+            if constexpr (kLatePrefetch) {
+                if (pre) {
+                    if constexpr (kGatherAhead) {
+                        grows4(grow, xr);                             // (grow: the rows of batch j + 2, fetched a step ago)
+                        if (j + 3 < nb) gidx(j + 3, grow);
+                    } else if constexpr (FULL) {
+                        const vec4* src = reinterpret_cast<const vec4*>(xs_all + (size_t)(j + 2) * xs_stride + (size_t)(kXcdSl * w) * B * 16);
+#pragma unroll
+                        for (int r = 0; r < XR; ++r) {
+                            const int i = tid + r * kXcdThreads;
+                            xr[r] = i < nsl * BT * 4 ? src[i] : vec4{0, 0, 0, 0};
+                        }
+                    } else {
+                        prefetch(j + 2);
+                    }
+                }
+            }
             // Four 16 x 16 tiles, 64 k-steps each: 256 MFMAs = 2048 cycles of the CU's four matrix pipes whichever way they are cut.
             // Waves 0..3 (one per SIMD) each run ONE tile over the WHOLE batch -- no K-split, so no cross-wave reduction, no partials
             // in LDS, no second barrier -- on two interleaved accumulators (a single chain would be paced by the 40-cycle dependent

@@ -283,10 +283,14 @@ int enqueue_xcd_steps(rcn_hip_ctx* c, const T* xs, const T* ys, size_t B, size_t
 }
 
 // The gather form of the resident kernel (rows fetched by the workers themselves; f32 feature vectors whose rows are whole 16-byte
-// chunks) is OFF unless RCN_HIP_XCD_GATHER=1.  Measured on MI355X (bench workload): the kernel's step takes 7.4 us this way against
-// 6.45 us on the packed image -- a wave's loads retire in order, so every wait for a slab or flag word that follows the prefetch also
-// waits for 256 scattered 128-byte reads, where the packed image gives it one 32 KB run -- and k_pack_epoch's gather costs only
-// 0.39 us per step amortised: 7.39 vs 6.80 us per step in the bench's steady state.
+// chunks) is OFF unless RCN_HIP_XCD_GATHER=1.  Measured on MI355X (bench workload, epoch loop of 64 steps; profiles/
+// resident_prefetch_ab.txt): 7.18 us per step this way against 6.64 us on the packed image (k_pack_epoch included)
+// before the row fetch was re-scheduled.  With the rows issued behind the delta_1 staging barrier, their indices fetched a step ahead
+// of them and the targets a step ahead (dense_xcd.hpp: kLatePrefetch, kGatherAhead, kLateTargets) it takes 6.64 -- but the packed
+// form gained more from the same moves (6.17), bench.py reads 6.66 against 6.20 us per step, and the default stays 0.  What is left
+// is not the dependent index load any more: the stamps put the feature workers' step top 0.6 us later than on the packed image, i.e.
+// the 256 scattered 128-byte reads per worker and batch themselves return later than one 32 KB run does, and the barrier behind the
+// update waits for them.  k_pack_epoch's gather costs 0.35 us per step amortised, less than that.
 constexpr size_t kXcdMaxStepsPerLaunch = 1u << 20;
 static bool xcd_gather(const rcn_hip_ctx* c) {
     return c->opt.xcd_gather != 0 && c->nd.dims[0] % 4 == 0 && c->nd.L == 2;
