@@ -33,7 +33,8 @@ def resident_set_figures(net, args, in_shape, B, lr):
     --lr-schedule / --augment: the same epochs once more as that recipe -- a warm-up + cosine rate per step from a device tensor, the
     gather through a random crop and flip -- timed the same way, beside the plain figure.
     --label-smoothing / --mix: those recipe epochs a third time with the smoothed loss and / or mixup / CutMix records (mix_plan, made and
-    moved to the device before the clock starts), beside the recipe figure: mix_epoch_ms_per_step."""
+    moved to the device before the clock starts), beside the recipe figure: mix_epoch_ms_per_step.
+    --ema: the evaluation once more on the average of the parameters (two exchange launches per call), beside the live figures."""
     import torch
     N = args.dataset
     nb = N // B
@@ -125,9 +126,18 @@ def resident_set_figures(net, args, in_shape, B, lr):
             loss_sum, correct, _ = net.evaluate_async(X, Y, want_pred=False)
         net.synchronize()
         ev = time.perf_counter() - t0
+        ema = {}
+        if args.ema > 0:
+            net.evaluate(X, Y, weights="ema")
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                ema_loss_sum, ema_correct, _ = net.evaluate_async(X, Y, want_pred=False, weights="ema")
+            net.synchronize()
+            ema = {"eval_ema_images_per_s": round(reps * N / (time.perf_counter() - t0), 1), "eval_ema_mean_loss": round(float(ema_loss_sum.item()) / N, 4),
+                   "eval_ema_correct": int(ema_correct.item())}
     return {"dataset": N, "dataset_dtype": str(X.dtype).replace("torch.", ""), "epochs_timed": epochs, "epoch_ms_per_step": round(el / (epochs * nb) * 1e3, 4), **recipe,
             "epoch_images_per_s": round(epochs * nb * B / el, 1), "eval_images_per_s": round(reps * N / ev, 1),
-            "eval_mean_loss": round(float(loss_sum.item()) / N, 4), "eval_correct": int(correct.item()), "graphs_instantiated": graphs}
+            "eval_mean_loss": round(float(loss_sum.item()) / N, 4), "eval_correct": int(correct.item()), **ema, "graphs_instantiated": graphs}
 
 
 def main():
@@ -148,6 +158,9 @@ def main():
     ap.add_argument("--momentum", type=float, default=0.0, help="SGD momentum (rcn_hipx_set_sgd; 0: plain SGD)")
     ap.add_argument("--weight-decay", type=float, default=0.0, help="SGD weight decay, on every parameter")
     ap.add_argument("--nesterov", action="store_true", help="Nesterov momentum (needs --momentum > 0)")
+    ap.add_argument("--ema", type=float, default=0.0, metavar="D",
+                    help="keep an exponential moving average of the parameters with decay D inside the update launch (rcn_hipx_set_ema; 0: none), set before the "
+                         "timed steps; with --dataset the line gains eval_ema_images_per_s and the average's loss / accuracy beside the live ones")
     ap.add_argument("--dataset", type=int, default=0, metavar="N",
                     help="also keep a synthetic set of N images resident (uint8 for mnist / cifar, fp32 for synth224), time train_epoch over whole epochs with a fresh "
                          "device permutation each, then evaluate over the set: the line gains epoch_ms_per_step, epoch_images_per_s, eval_images_per_s, graphs_instantiated "
@@ -167,6 +180,8 @@ def main():
     args = ap.parse_args()
     if (args.label_smoothing != 0.0 or args.mix != "none") and not args.dataset:
         ap.error("--label-smoothing and --mix time the resident epoch: they need --dataset N")
+    if not 0.0 <= args.ema < 1.0:
+        ap.error("--ema: 0 <= D < 1")
     if not 0.0 <= args.label_smoothing < 1.0:
         ap.error("--label-smoothing: 0 <= E < 1")
     if (args.lr_schedule != "none" or args.augment >= 0 or args.trap) and not args.dataset:
@@ -204,6 +219,8 @@ def main():
     sgd = args.momentum != 0.0 or args.weight_decay != 0.0 or args.nesterov
     if sgd:
         net.set_sgd(args.momentum, args.weight_decay, args.nesterov)
+    if args.ema > 0:
+        net.set_ema(args.ema)
     rng = np.random.default_rng(rank)
     nbuf = 8 if args.config != "synth224" else 2           # rotate over several resident batches
     xs = [net.to_device(rng.standard_normal((B,) + in_shape).astype(np.float32)) for _ in range(nbuf)]
@@ -235,7 +252,7 @@ def main():
                         dist.all_reduce(piece, op=dist.ReduceOp.SUM)
                 net.gradients_bucketed(x, y, grad, loss, args.dp_buckets, on_bucket)
                 net.stream.wait_stream(comm)
-            if sgd:
+            if sgd or args.ema > 0:                        # (apply_sgd keeps the average; apply is the plain axpy and does not)
                 net.apply_sgd(grad, 1.0 / world, lr)
             else:
                 net.apply(grad, lr / world)
@@ -314,6 +331,7 @@ def main():
                           "frac_of_mfma_peak": round(tf / peak, 4),
                           "hbm_floor_ms": round(floor_ms, 4) if floor_ms else None, "frac_of_hbm_floor": round(floor_ms / (el / args.steps * 1e3), 4) if floor_ms else None,
                           "dtype": "f32" if not bf16 else "bf16 MFMA operands (fwd, dgrad, wgrad), f32 accumulate/update" + (", conv-stage activations and gradients stored as bf16" if args.precision == "bf16_stored" else ""), "data": "synthetic", "final_loss": round(loss.item(), 4),
+                          "ema_decay": args.ema,
                           "data_parallel_step": dp_mode,
                           "data_parallel_allreduce": (None if not dp else "one all-reduce of the flat gradient after the backward pass" if args.dp_buckets <= 0 else
                                                       f"{n_buckets[0]} buckets of >= {args.dp_buckets} bytes, each all-reduced on a second stream under the backward pass of the layers below"),

@@ -250,6 +250,18 @@ int  rcn_hipx_plan_epoch_mix_net(const rcn_hipx_net* net, int batch, int x_kind,
  * -1 (nothing enqueued): n < 1, X_dev NULL, an unknown x_kind, a NULL that the rules above do not allow. */
 int  rcn_hipx_evaluate_dev(rcn_hipx_net* net, const void* X_dev, int x_kind, float x_scale, float x_shift, const int32_t* labels_dev, int64_t n,
                            double* loss_sum_dev, int64_t* correct_dev, int32_t* pred_dev);
+/* rcn_hipx_evaluate_dev with a choice of weights: RCN_HIPX_WEIGHTS_LIVE is rcn_hipx_evaluate_dev itself (the same launches);
+ * RCN_HIPX_WEIGHTS_EMA scores the average of the parameters that rcn_hipx_set_ema keeps.  On the net's stream: k_swap4 exchanges the
+ * contents of the parameter buffer and the average, the evaluation runs as above (it begins with the bf16 operand copies, so in the bf16
+ * modes those are made from the average), and k_swap4 exchanges them back -- enqueued on every way out once the first exchange is, an
+ * error in a chunk included.  The forward pass does not read the tap-flipped weight copy, so that copy is left alone and matches the
+ * live parameters again after the second exchange; the next training step re-makes the bf16 operand copies, as every step does.
+ * Afterwards the live parameters, the average and the velocity hold the bits they held before, and nothing is captured.
+ * -6: RCN_HIPX_WEIGHTS_EMA while no average exists; an open bucket walk (either mode).  -1: any other `weights`; what
+ * rcn_hipx_evaluate_dev refuses. */
+enum { RCN_HIPX_WEIGHTS_LIVE = 0, RCN_HIPX_WEIGHTS_EMA = 1 };
+int  rcn_hipx_evaluate_ex_dev(rcn_hipx_net* net, const void* X_dev, int x_kind, float x_scale, float x_shift, const int32_t* labels_dev, int64_t n,
+                              int weights, double* loss_sum_dev, int64_t* correct_dev, int32_t* pred_dev);
 /* how many hipGraphs this net has instantiated since it was created (monotonic; tests and the bench read it to see that an epoch does
  * not re-capture) */
 int  rcn_hipx_graphs_instantiated(const rcn_hipx_net* net, int64_t* count);
@@ -284,6 +296,32 @@ int  rcn_hipx_reset_velocity(rcn_hipx_net* net);
  * ranks' gradients with grad_scale = 1 / ranks).  With the default setting it is rcn_hipx_apply_dev(grad_dev, grad_scale * lr).
  * rcn_hipx_apply_dev itself stays the plain p <- p - scale * g and never touches the velocity. */
 int  rcn_hipx_apply_sgd_dev(rcn_hipx_net* net, const float* grad_dev, float grad_scale, float lr);
+/* An exponential moving average (EMA) of the parameters, kept by the launch that updates them: timm's ModelEmaV2,
+ * torch.optim.swa_utils.AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(decay)).  Per element, fp32, every operation rounded once (no fused
+ * multiply-add):
+ *     e = e + a * (p_new - e),    a = fl(1.0f - decay), computed once on the host
+ * p_new being the value the update stores into the parameter buffer in that same step: torch.lerp(e, p_new, 1 - decay) in its
+ * weight < 0.5 form (tests/_ema_ref.py restates it in float32 NumPy, bit for bit).  Biases are averaged too; padding elements of the
+ * padded layout have p = e = 0 and stay 0.
+ * Start value: the first decay > 0 on a net allocates the average (laid out like the padded parameters; allocated once and never moved,
+ * captured graphs hold its pointer) and fills it with a device copy of the live parameters at that moment.  This is AveragedModel's copy
+ * on its first update_parameters, taken when the average is switched on rather than after the first step.
+ * Updated by every entry point in which the library applies a training update: rcn_hipx_train_step_dev, rcn_hipx_train_step_pair_dev, the
+ * three epoch entries (inside the step's one reduction launch: k_reduce_all_ema / _sgd_ema and their _dlr forms, so the step stays one
+ * captured graph with no launch added) and rcn_hipx_apply_sgd_dev (one k_ema_lerp launch after its update launch).  Never touched by
+ * rcn_hipx_apply_dev (as it never touches the velocity), the gradient / bucket entries, rcn_hipx_set_params, rcn_hipx_init_params or
+ * changes of precision, tiling, overlap or options: the average survives all of these, like the velocity.
+ * Switching the average on never changes one bit of the live parameters, the tap-flipped copy or the velocity.
+ * decay == 0 is the default: the same kernels, launches, arguments and plan text as a net never configured; an existing average is kept
+ * (readable, evaluable) but no longer updated.  Accepts a finite 0 <= decay < 1; anything else returns -1 and changes nothing.  A changed
+ * value synchronises the net's stream and drops its captured graphs (the constant is a kernel argument), as rcn_hipx_set_sgd does. */
+int  rcn_hipx_set_ema(rcn_hipx_net* net, float decay);
+int  rcn_hipx_get_ema(const rcn_hipx_net* net, float* decay);
+/* the average in the logical layout of rcn_hipx_get_params / _set_params.  get / set: -6 while no average exists (zeros would read as a
+ * valid average); reset: copies the live parameters into it, enqueued on the net's stream (a no-op without an average). */
+int  rcn_hipx_get_ema_params(rcn_hipx_net* net, float* flat);
+int  rcn_hipx_set_ema_params(rcn_hipx_net* net, const float* flat);
+int  rcn_hipx_reset_ema(rcn_hipx_net* net);
 /* The same gradients in BUCKETS, so that a data-parallel step can all-reduce one bucket of layers while the backward pass of the layers
  * below it still runs (6.7 MB of gradient for BASELINE configs[3]).  The layers with parameters, in the order the
  * backward pass finishes them (last to first), are cut into buckets of at least min_bucket_bytes of gradient; the padded flat layout
@@ -310,7 +348,8 @@ int  rcn_hipx_plan(int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, i
 /* The same walk for an EXISTING net at batch `batch` (<= max_batch) with that net's own precision, tiling and options: the plan and the
  * step that follows agree by construction (rcn_hipx_plan describes a net created now, seeded from the environment).  A net with a
  * non-default rcn_hipx_set_sgd setting names its optimiser and the values on the update line; one with rcn_hipx_set_loss eps > 0 names the
- * soft loss kernel and eps on the loss (or head) line. */
+ * soft loss kernel and eps on the loss (or head) line; one with rcn_hipx_set_ema decay > 0 names the _ema update kernel and
+ * "(EMA: decay %g)" on the update line (rcn_hipx_plan_epoch_net / _mix_net likewise). */
 int  rcn_hipx_plan_net(const rcn_hipx_net* net, int batch, char* out, int cap);
 /* algorithmic FLOPs of one training step at batch B (2 * MACs; forward + dgrad + wgrad) */
 int  rcn_hipx_step_flops(const rcn_hipx_net* net, int B, double* flops);

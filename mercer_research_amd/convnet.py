@@ -130,6 +130,12 @@ SIGNATURES = {
     "rcn_hipx_graphs_instantiated": (_i, [_vp, C.POINTER(C.c_int64)]),
     "rcn_hipx_plan_eval": (_i, [_i, _i, _i, C.POINTER(XLayer), _i, _i, _i, _i, C.c_char_p, _i]),
     "rcn_hipx_plan_eval_net": (_i, [_vp, _i, C.c_char_p, _i]),
+    "rcn_hipx_set_ema": (_i, [_vp, C.c_float]),
+    "rcn_hipx_get_ema": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rcn_hipx_get_ema_params": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rcn_hipx_set_ema_params": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rcn_hipx_reset_ema": (_i, [_vp]),
+    "rcn_hipx_evaluate_ex_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _i, _vp, _vp, _vp]),
 }
 _libx = None
 
@@ -156,6 +162,7 @@ DEFAULT_BUCKET_BYTES = 1 << 20      # gradient buckets of the data-parallel step
 
 
 PRECISIONS = {"fp32": 0, "bf16": 1, "bf16_stored": 2}
+WEIGHTS = {"live": 0, "ema": 1}     # RCN_HIPX_WEIGHTS_*: which parameters an evaluation scores
 
 
 def plan(in_shape: Tuple[int, int, int], layers: Sequence[tuple], batch: int, precision: str = "fp32", tiling: str = "auto", buckets: Optional[int] = None) -> str:
@@ -479,32 +486,35 @@ class ConvNet:
             raise ConvNetError(f"rcn_hipx_plan_epoch_net: {st}: {buf.value.decode()}")
         return buf.value.decode()
 
-    def evaluate_async(self, X, labels=None, x_scale: float = 1.0 / 255.0, x_shift: float = 0.0, want_pred: bool = True):
-        """Forward pass, loss and arg-max over ALL rows of a resident set (rcn_hipx_evaluate_dev), enqueued on the net's stream: returns the
+    def evaluate_async(self, X, labels=None, x_scale: float = 1.0 / 255.0, x_shift: float = 0.0, want_pred: bool = True, weights: str = "live"):
+        """Forward pass, loss and arg-max over ALL rows of a resident set (rcn_hipx_evaluate_ex_dev), enqueued on the net's stream: returns the
         device tensors (loss_sum: float64[1], correct: int64[1], pred: int32[n] or None), valid once the net's stream has got there
-        (`synchronize`).  labels None: prediction only (loss_sum and correct stay zero)."""
+        (`synchronize`).  labels None: prediction only (loss_sum and correct stay zero).  weights: "live" (the parameters of the last step)
+        or "ema" (set_ema's average of them; the live parameters are back in place when the call's work is done)."""
         t = self.torch
+        if weights not in WEIGHTS:
+            raise ValueError(f"weights must be one of {sorted(WEIGHTS)}, not {weights!r}")
         kind, n = self._resident_set(X, labels)
         with t.cuda.stream(self.stream):
             loss_sum = t.zeros(1, dtype=t.float64, device=self.device)
             correct = t.zeros(1, dtype=t.int64, device=self.device)
             pred = t.empty(n, dtype=t.int32, device=self.device) if (want_pred or labels is None) else None
-        self._ck(self.lib.rcn_hipx_evaluate_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift),
-                                                C.c_void_p(labels.data_ptr()) if labels is not None else None, n,
-                                                C.c_void_p(loss_sum.data_ptr()), C.c_void_p(correct.data_ptr()), C.c_void_p(pred.data_ptr()) if pred is not None else None))
+        self._ck(self.lib.rcn_hipx_evaluate_ex_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift),
+                                                   C.c_void_p(labels.data_ptr()) if labels is not None else None, n, WEIGHTS[weights],
+                                                   C.c_void_p(loss_sum.data_ptr()), C.c_void_p(correct.data_ptr()), C.c_void_p(pred.data_ptr()) if pred is not None else None))
         return loss_sum, correct, pred
 
-    def evaluate(self, X, labels, x_scale: float = 1.0 / 255.0, x_shift: float = 0.0) -> Tuple[float, int]:
+    def evaluate(self, X, labels, x_scale: float = 1.0 / 255.0, x_shift: float = 0.0, weights: str = "live") -> Tuple[float, int]:
         """(mean loss, number of rows whose arg-max equals the label) over all rows of a resident set; synchronises."""
         if labels is None:
             raise ValueError("evaluate needs labels (predict: arg-max only)")
-        loss_sum, correct, _ = self.evaluate_async(X, labels, x_scale, x_shift, want_pred=False)
+        loss_sum, correct, _ = self.evaluate_async(X, labels, x_scale, x_shift, want_pred=False, weights=weights)
         self.synchronize()
         return float(loss_sum.item()) / X.shape[0], int(correct.item())
 
-    def predict(self, X, x_scale: float = 1.0 / 255.0, x_shift: float = 0.0):
+    def predict(self, X, x_scale: float = 1.0 / 255.0, x_shift: float = 0.0, weights: str = "live"):
         """The arg-max class of every row (the FIRST maximum, as torch.argmax): an int32 device tensor, valid on the net's stream."""
-        return self.evaluate_async(X, None, x_scale, x_shift)[2]
+        return self.evaluate_async(X, None, x_scale, x_shift, weights=weights)[2]
 
     def graphs_instantiated(self) -> int:
         """hipGraphs this net has instantiated since it was created (an epoch with a (B, lr) seen before adds none)."""
@@ -576,6 +586,32 @@ class ConvNet:
 
     def reset_velocity(self):
         self._ck(self.lib.rcn_hipx_reset_velocity(self.net))
+
+    def set_ema(self, decay: float = 0.0):
+        """An exponential moving average of the parameters, e <- e + (1 - decay) * (p_new - e), kept by the launch that updates them
+        (include/rcn_hipx.h, rcn_hipx_set_ema).  The first decay > 0 starts it as a copy of the live parameters.  0 is the default: off; an
+        average that exists is kept but no longer updated.  evaluate / predict score it with weights="ema"."""
+        self._ck(self.lib.rcn_hipx_set_ema(self.net, float(decay)))
+
+    def get_ema_decay(self) -> float:
+        d = C.c_float()
+        self._ck(self.lib.rcn_hipx_get_ema(self.net, C.byref(d)))
+        return float(d.value)
+
+    def get_ema(self) -> np.ndarray:
+        """The average in the logical layout of get_params (ConvNetError, status -6, while the net has none)."""
+        f = np.zeros(self.n_logical, dtype=np.float32)
+        self._ck(self.lib.rcn_hipx_get_ema_params(self.net, f.ctypes.data_as(C.POINTER(C.c_float))))
+        return f
+
+    def set_ema_params(self, flat: np.ndarray):
+        f = np.ascontiguousarray(flat, dtype=np.float32)
+        assert f.size == self.n_logical
+        self._ck(self.lib.rcn_hipx_set_ema_params(self.net, f.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def reset_ema(self):
+        """The average becomes a copy of the live parameters (a no-op while the net has none)."""
+        self._ck(self.lib.rcn_hipx_reset_ema(self.net))
 
     def apply_sgd(self, grad, grad_scale: float, lr: float):
         """The data-parallel half of set_sgd's optimiser: the same update from a padded gradient buffer, scaled by grad_scale first."""

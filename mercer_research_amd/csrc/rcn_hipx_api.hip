@@ -25,6 +25,7 @@
 #include "convnet_halo_bf16.hpp"
 #include "convnet_select.hpp"
 #include "convnet_sgd.hpp"
+#include "convnet_ema.hpp"
 
 using namespace rcnx;
 
@@ -91,6 +92,10 @@ struct rcn_hipx_net : Selection {
     // like params) is allocated by the first nonzero momentum and never moved afterwards: captured graphs hold its pointer.
     float sgd_mu = 0.f, sgd_wd = 0.f; int sgd_nesterov = 0;
     Buf vel;
+    // the average of the parameters (rcn_hipx_set_ema; convnet_ema.hpp): 0 is off, the update launches of a net never configured.  `ema`
+    // (n_pad floats, laid out like params) is allocated by the first decay > 0 and never moved afterwards: captured graphs hold its pointer.
+    float ema_decay = 0.f;
+    Buf ema;
     std::map<Key, hipGraphExec_t> graphs;
     // rcn_hipx_train_epoch_dev / rcn_hipx_evaluate_dev: the batch the gather kernel fills (max_batch rows, fp32), its labels and the step's
     // loss scalar.  Allocated once, never moved: the epoch's step always sees these three pointers, so ONE captured graph per (B, lr)
@@ -499,6 +504,8 @@ int reduce_slab(rcn_hipx_net* n, size_t i, int chunks, int ks, const ConvShape& 
 
 bool sgd_default(const rcn_hipx_net* n) { return n->sgd_mu == 0.f && n->sgd_wd == 0.f && !n->sgd_nesterov; }
 SgdParams sgd_params(const rcn_hipx_net* n) { return SgdParams{(float*)n->vel.p, (const float*)n->params.p, n->sgd_mu, n->sgd_wd, n->sgd_nesterov}; }
+bool ema_on(const rcn_hipx_net* n) { return n->ema_decay != 0.f; }
+EmaParams ema_params(const rcn_hipx_net* n) { return EmaParams{(float*)n->ema.p, (const float*)n->params.p, 1.0f - n->ema_decay}; }
 
 // lr_dev (nullable): the update reads its rate from this device scalar instead of `lr` (the _dlr kernels; same arithmetic on the same float)
 int run_reduce_jobs(rcn_hipx_net* n, float lr, bool apply, const float* lr_dev = nullptr) {
@@ -506,19 +513,27 @@ int run_reduce_jobs(rcn_hipx_net* n, float lr, bool apply, const float* lr_dev =
     const ReduceJob& last = n->jobs.j[n->jobs.njobs - 1];
     const long long blocks = last.first_block + (last.n + reduce_job_elems(last.chunks) - 1) / reduce_job_elems(last.chunks);
     n->jobs.lr = lr; n->jobs.apply = apply ? 1 : 0;
-    if (apply && !sgd_default(n)) {
-        // the net's optimiser in the same launch (convnet_sgd.hpp); gradients-only walks never get here
-        if (dry_note(n, "  update: k_reduce_all_sgd%s, %d layers' slabs in one launch, %lld workgroups (SGD: momentum %g, weight decay %g, nesterov %s)", lr_dev ? "_dlr" : "",
-                     n->jobs.njobs, blocks, (double)n->sgd_mu, (double)n->sgd_wd, n->sgd_nesterov ? "on" : "off")) { n->jobs.njobs = 0; return 0; }
-        if (lr_dev) hipLaunchKernelGGL(k_reduce_all_sgd_dlr, dim3((unsigned)blocks), dim3(kReduceThreads), 0, n->stream, n->jobs, sgd_params(n), lr_dev);
-        else hipLaunchKernelGGL(k_reduce_all_sgd, dim3((unsigned)blocks), dim3(kReduceThreads), 0, n->stream, n->jobs, sgd_params(n));
-        XTRY(n, hipGetLastError());
+    // the update kernel of this launch, chosen here and nowhere else: (the net's optimiser?, the average on?, the rate from the device?)
+    const bool sgd = apply && !sgd_default(n), ema = apply && ema_on(n), dlr = apply && lr_dev;
+    char what[192] = "";
+    if (sgd) std::snprintf(what, sizeof what, " (SGD: momentum %g, weight decay %g, nesterov %s)", (double)n->sgd_mu, (double)n->sgd_wd, n->sgd_nesterov ? "on" : "off");
+    if (ema) std::snprintf(what + std::strlen(what), sizeof what - std::strlen(what), " (EMA: decay %g)", (double)n->ema_decay);
+    if (dry_note(n, "  update: k_reduce_all%s%s%s, %d layers' slabs in one launch, %lld workgroups%s", sgd ? "_sgd" : "", ema ? "_ema" : "", dlr ? "_dlr" : "", n->jobs.njobs, blocks, what)) {
         n->jobs.njobs = 0;
         return 0;
     }
-    if (dry_note(n, "  update: k_reduce_all%s, %d layers' slabs in one launch, %lld workgroups", apply && lr_dev ? "_dlr" : "", n->jobs.njobs, blocks)) { n->jobs.njobs = 0; return 0; }
-    if (apply && lr_dev) hipLaunchKernelGGL(k_reduce_all_dlr, dim3((unsigned)blocks), dim3(kReduceThreads), 0, n->stream, n->jobs, lr_dev);
-    else hipLaunchKernelGGL(k_reduce_all, dim3((unsigned)blocks), dim3(kReduceThreads), 0, n->stream, n->jobs);
+    const dim3 grid((unsigned)blocks), block(kReduceThreads);
+    // gradients-only walks (apply == false) take k_reduce_all
+    switch ((sgd ? 4 : 0) | (ema ? 2 : 0) | (dlr ? 1 : 0)) {
+        case 0: hipLaunchKernelGGL(k_reduce_all, grid, block, 0, n->stream, n->jobs); break;
+        case 1: hipLaunchKernelGGL(k_reduce_all_dlr, grid, block, 0, n->stream, n->jobs, lr_dev); break;
+        case 2: hipLaunchKernelGGL(k_reduce_all_ema, grid, block, 0, n->stream, n->jobs, ema_params(n)); break;
+        case 3: hipLaunchKernelGGL(k_reduce_all_ema_dlr, grid, block, 0, n->stream, n->jobs, ema_params(n), lr_dev); break;
+        case 4: hipLaunchKernelGGL(k_reduce_all_sgd, grid, block, 0, n->stream, n->jobs, sgd_params(n)); break;
+        case 5: hipLaunchKernelGGL(k_reduce_all_sgd_dlr, grid, block, 0, n->stream, n->jobs, sgd_params(n), lr_dev); break;
+        case 6: hipLaunchKernelGGL(k_reduce_all_sgd_ema, grid, block, 0, n->stream, n->jobs, sgd_params(n), ema_params(n)); break;
+        default: hipLaunchKernelGGL(k_reduce_all_sgd_ema_dlr, grid, block, 0, n->stream, n->jobs, sgd_params(n), ema_params(n), lr_dev); break;
+    }
     XTRY(n, hipGetLastError());
     n->jobs.njobs = 0;
     return 0;
@@ -873,12 +888,13 @@ int make_dry_net(rcn_hipx_net& net, int in_h, int in_w, int in_c, const rcn_hipx
     seed_options(net.opt);
     return describe_layers(&net, in_h, in_w, in_c, layers, n_layers);
 }
-// ... or from an existing net: its layers, precision, tiling, options, optimiser and loss -- the plan and the step agree by construction
+// ... or from an existing net: its layers, precision, tiling, options, optimiser, loss and average -- the plan and the step agree by construction
 void make_dry_net(rcn_hipx_net& net, const rcn_hipx_net& from, int batch) {
     net.in_h = from.in_h; net.in_w = from.in_w; net.in_c = from.in_c; net.max_batch = batch; net.classes = from.classes; net.dry = true;
     static_cast<Selection&>(net) = from;
     net.sgd_mu = from.sgd_mu; net.sgd_wd = from.sgd_wd; net.sgd_nesterov = from.sgd_nesterov;
     net.loss_eps = from.loss_eps;
+    net.ema_decay = from.ema_decay;
     copy_layer_table(net, from);
 }
 
@@ -936,7 +952,7 @@ void rcn_hipx_destroy(rcn_hipx_net* n) {
         if (n->stream) (void)hipStreamSynchronize(n->stream);
         drop_graphs(n);
         for (Layer& l : n->L) { l.out.release(); l.idx.release(); l.dout.release(); l.slab.release(); }
-        for (Buf* b : {&n->params, &n->wt, &n->wb16, &n->dz, &n->loss_part, &n->grad_tmp, &n->dlogits, &n->skbuf, &n->wb, &n->vel, &n->xb, &n->yb, &n->eloss, &n->elr, &n->yb2, &n->emixw, &n->eval_part}) b->release();
+        for (Buf* b : {&n->params, &n->wt, &n->wb16, &n->dz, &n->loss_part, &n->grad_tmp, &n->dlogits, &n->skbuf, &n->wb, &n->vel, &n->ema, &n->xb, &n->yb, &n->eloss, &n->elr, &n->yb2, &n->emixw, &n->eval_part}) b->release();
         if (n->side) { (void)hipStreamSynchronize(n->side); (void)hipStreamDestroy(n->side); }
         for (hipEvent_t e : n->events) (void)hipEventDestroy(e);
         if (n->own_stream && n->stream) (void)hipStreamDestroy(n->stream);
@@ -1223,6 +1239,21 @@ int eval_chunk(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, do
     return launch_eval(n, labels, B, loss_sum, correct, pred);
 }
 
+// params <-> average, on the net's stream
+int launch_ema_swap(rcn_hipx_net* n) {
+    hipLaunchKernelGGL(k_swap4, dim3(grid1d(n->n_pad / 4, 256)), dim3(256), 0, n->stream, (float*)n->params.p, (float*)n->ema.p, n->n_pad);
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+// An evaluation on the average: once the first exchange is enqueued, the second one is enqueued on EVERY way out of the scope -- an error in
+// a chunk must not leave the net training on the average.  (net == nullptr: the live parameters, nothing to do.)
+struct EmaSwap {
+    rcn_hipx_net* net;
+    bool armed = false;
+    int begin() { if (!net) return 0; RTRY(launch_ema_swap(net)); armed = true; return 0; }
+    ~EmaSwap() { if (armed) (void)launch_ema_swap(net); }
+};
+
 int plan_eval_walk(rcn_hipx_net& net, int batch) {
     net.plan = "forward + evaluation of one chunk of " + std::to_string(batch) + " rows (" + precision_name(net.precision, net.store16) + "), launch by launch:\n";
     RTRY(prep_bf16_weights(&net));
@@ -1333,17 +1364,31 @@ int rcn_hipx_augment_draw(const rcn_hipx_augment* aug, uint64_t q, int* dy, int*
 
 int rcn_hipx_evaluate_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows,
                           double* loss_sum, int64_t* correct, int32_t* pred) {
+    return rcn_hipx_evaluate_ex_dev(n, X, x_kind, x_scale, x_shift, labels, rows, RCN_HIPX_WEIGHTS_LIVE, loss_sum, correct, pred);
+}
+
+int rcn_hipx_evaluate_ex_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows, int weights,
+                             double* loss_sum, int64_t* correct, int32_t* pred) {
     if (!n) return -1;
+    if (weights != RCN_HIPX_WEIGHTS_LIVE && weights != RCN_HIPX_WEIGHTS_EMA) return fail(n, -1, "evaluate: weights must be RCN_HIPX_WEIGHTS_LIVE or RCN_HIPX_WEIGHTS_EMA");
     if (!X) return fail(n, -1, "evaluate: X_dev must not be NULL");
     if (!x_kind_ok(x_kind)) return fail(n, -1, "evaluate: x_kind must be RCN_HIPX_X_F32 or RCN_HIPX_X_U8");
     if (rows < 1) return fail(n, -1, "evaluate: n must be at least 1");
     if (labels && (!loss_sum || !correct)) return fail(n, -1, "evaluate: with labels, loss_sum_dev and correct_dev must not be NULL");
     if (!labels && !pred) return fail(n, -1, "evaluate: without labels there is only pred_dev to fill; it must not be NULL");
     if (n->walk_open) return fail(n, -6, "evaluate: a bucket walk is open (rcn_hipx_gradients_begin_dev): its activations are still needed; take the remaining buckets first");
+    if (weights == RCN_HIPX_WEIGHTS_EMA && !n->ema.p) return fail(n, -6, "evaluate: the net has no average (rcn_hipx_set_ema with a decay > 0 first)");
     Dev g(n->device);
     if (x_kind == RCN_HIPX_X_U8) RTRY(ensure_epoch_bufs(n));
     if (loss_sum) XTRY(n, hipMemsetAsync(loss_sum, 0, sizeof(double), n->stream));
     if (correct) XTRY(n, hipMemsetAsync(correct, 0, sizeof(int64_t), n->stream));
+    // On the average: the parameter buffer and the average trade contents for the length of the call, so every pointer the forward pass and
+    // k_prep_all_bf16 hold (prep jobs, layer offsets) stays what it is.  The forward pass reads the parameters and, in bf16 mode, the
+    // operand copies that the prep launch below makes from them; it never reads the tap-flipped copy `wt` (only the input-gradient pass,
+    // the fused training head and the prep job of the input-gradient operand do), so wt is left alone and matches the live parameters
+    // again once they are back.  The bf16 operand copies are re-made by the next step, as by every step.
+    EmaSwap swapped{weights == RCN_HIPX_WEIGHTS_EMA ? n : nullptr};
+    RTRY(swapped.begin());
     RTRY(prep_bf16_weights(n));
     const long long E = row_elems(n);
     for (int64_t off = 0; off < rows; off += n->max_batch) {
@@ -1484,6 +1529,69 @@ int rcn_hipx_reset_velocity(rcn_hipx_net* n) {
     return 0;
 }
 
+// the average follows the parameters that rcn_hipx_apply_sgd_dev's update launch has just stored (one more launch: this path is not the
+// captured step, and it leaves the update launches exactly what they are without an average)
+static int apply_ema(rcn_hipx_net* n) {
+    if (!ema_on(n)) return 0;
+    const EmaParams m = ema_params(n);
+    hipLaunchKernelGGL(k_ema_lerp, dim3(grid1d(n->n_pad / 4, 256)), dim3(256), 0, n->stream, m.e, m.p0, m.a, n->n_pad);
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+
+int rcn_hipx_set_ema(rcn_hipx_net* n, float decay) {
+    if (!n) return -1;
+    if (!(std::isfinite(decay) && decay >= 0.f && decay < 1.f)) return fail(n, -1, "set_ema: decay must be finite and in [0, 1)");
+    if (decay == n->ema_decay) return 0;
+    Dev g(n->device);
+    XTRY(n, hipStreamSynchronize(n->stream));
+    if (decay != 0.f && !n->ema.p) {
+        // once, outside any capture: captured graphs hold this pointer, so the buffer never moves afterwards.  It starts as the live parameters.
+        XTRY(n, n->ema.ensure((size_t)n->n_pad * sizeof(float)));
+        XTRY(n, hipMemcpyAsync(n->ema.p, n->params.p, (size_t)n->n_pad * sizeof(float), hipMemcpyDeviceToDevice, n->stream));
+        XTRY(n, hipStreamSynchronize(n->stream));
+    }
+    drop_graphs(n);                                     // captured graphs bake in the update kernel and its arguments
+    n->ema_decay = decay;
+    return 0;
+}
+
+int rcn_hipx_get_ema(const rcn_hipx_net* n, float* decay) {
+    if (!n) return -1;
+    if (decay) *decay = n->ema_decay;
+    return 0;
+}
+
+int rcn_hipx_get_ema_params(rcn_hipx_net* n, float* flat) {
+    if (!n || !flat) return -1;
+    if (!n->ema.p) return fail(n, -6, "get_ema_params: the net has no average (rcn_hipx_set_ema with a decay > 0 first)");
+    Dev g(n->device);
+    return unpad(n, (const float*)n->ema.p, flat);
+}
+
+int rcn_hipx_set_ema_params(rcn_hipx_net* n, const float* flat) {
+    if (!n || !flat) return -1;
+    if (!n->ema.p) return fail(n, -6, "set_ema_params: the net has no average (rcn_hipx_set_ema with a decay > 0 first)");
+    Dev g(n->device);
+    std::vector<float> pad((size_t)n->n_pad, 0.f);
+    for (const Layer& l : n->L) {
+        if (l.kind == RCN_HIPX_MAXPOOL2) continue;
+        for (int k = 0; k < l.K; ++k) std::memcpy(&pad[l.w_off + (long long)k * l.CoutP], &flat[l.lw_off + (long long)k * l.Cout], sizeof(float) * l.Cout);
+        std::memcpy(&pad[l.b_off], &flat[l.lb_off], sizeof(float) * l.Cout);
+    }
+    XTRY(n, hipMemcpyAsync(n->ema.p, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice, n->stream));
+    XTRY(n, hipStreamSynchronize(n->stream));
+    return 0;
+}
+
+int rcn_hipx_reset_ema(rcn_hipx_net* n) {
+    if (!n) return -1;
+    if (!n->ema.p) return 0;
+    Dev g(n->device);
+    XTRY(n, hipMemcpyAsync(n->ema.p, n->params.p, (size_t)n->n_pad * sizeof(float), hipMemcpyDeviceToDevice, n->stream));
+    return 0;
+}
+
 int rcn_hipx_apply_sgd_dev(rcn_hipx_net* n, const float* grad, float grad_scale, float lr) {
     if (!n || !grad) return -1;
     Dev g(n->device);
@@ -1491,11 +1599,13 @@ int rcn_hipx_apply_sgd_dev(rcn_hipx_net* n, const float* grad, float grad_scale,
         // plain SGD: exactly rcn_hipx_apply_dev(grad, grad_scale * lr)
         hipLaunchKernelGGL(k_axpy, dim3(grid1d(n->n_pad, 256)), dim3(256), 0, n->stream, (float*)n->params.p, grad, grad_scale * lr, n->n_pad);
         XTRY(n, hipGetLastError());
+        RTRY(apply_ema(n));
         return refresh_flipped(n);
     }
     if ((uintptr_t)grad % 16 != 0) return fail(n, -1, "apply_sgd: the gradient buffer must be 16-byte aligned");
     hipLaunchKernelGGL(k_sgd_apply, dim3(grid1d(n->n_pad / 4, 256)), dim3(256), 0, n->stream, (float*)n->params.p, grad, grad_scale, lr, sgd_params(n), n->n_pad);
     XTRY(n, hipGetLastError());
+    RTRY(apply_ema(n));
     return refresh_flipped(n);
 }
 
