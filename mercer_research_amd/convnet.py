@@ -162,7 +162,34 @@ DEFAULT_BUCKET_BYTES = 1 << 20      # gradient buckets of the data-parallel step
 
 
 PRECISIONS = {"fp32": 0, "bf16": 1, "bf16_stored": 2}
+TILINGS = {"gemm": 0, "auto": 1, "lds": 2}      # RCN_HIPX_TILING_*
 WEIGHTS = {"live": 0, "ema": 1}     # RCN_HIPX_WEIGHTS_*: which parameters an evaluation scores
+
+
+def _layer_array(layers: Sequence[tuple]):
+    """a net's description as the rcn_hipx_layer array the library takes"""
+    arr = (XLayer * len(layers))()
+    for i, l in enumerate(layers):
+        arr[i].kind, arr[i].out = KIND[l[0]], int(l[1]) if len(l) > 1 else 0
+    return arr
+
+
+def _ptr(t):
+    """a tensor's device pointer (None: NULL)"""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _fptr(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _plan_text(name: str, fn, *args) -> str:
+    """The text a plan entry `fn` writes for `args` (its buffer and capacity come last); its refusal as a ConvNetError under `name`."""
+    buf = C.create_string_buffer(1 << 16)
+    st = fn(*args, buf, len(buf))
+    if st != 0:
+        raise ConvNetError(f"{name}: {st}: {buf.value.decode()}")
+    return buf.value.decode()
 
 
 def plan(in_shape: Tuple[int, int, int], layers: Sequence[tuple], batch: int, precision: str = "fp32", tiling: str = "auto", buckets: Optional[int] = None) -> str:
@@ -170,34 +197,17 @@ def plan(in_shape: Tuple[int, int, int], layers: Sequence[tuple], batch: int, pr
     with its launches replaced by notes.  Needs no GPU.  buckets = N: the bucketed GRADIENT step of a data-parallel rank instead
     (rcn_hipx_plan_buckets, buckets of at least N bytes): per bucket its launches and the slice of the flat gradient that becomes final."""
     lib = load()
-    arr = (XLayer * len(layers))()
-    for i, l in enumerate(layers):
-        arr[i].kind, arr[i].out = KIND[l[0]], int(l[1]) if len(l) > 1 else 0
-    buf = C.create_string_buffer(1 << 16)
+    args = (in_shape[0], in_shape[1], in_shape[2], _layer_array(layers), len(layers), batch, PRECISIONS[precision], TILINGS[tiling])
     if buckets is not None:
-        st = lib.rcn_hipx_plan_buckets(in_shape[0], in_shape[1], in_shape[2], arr, len(layers), batch, PRECISIONS[precision], {"gemm": 0, "auto": 1, "lds": 2}[tiling],
-                                       int(buckets), buf, len(buf))
-        if st != 0:
-            raise ConvNetError(f"rcn_hipx_plan_buckets: {st}: {buf.value.decode()}")
-        return buf.value.decode()
-    st = lib.rcn_hipx_plan(in_shape[0], in_shape[1], in_shape[2], arr, len(layers), batch, PRECISIONS[precision], {"gemm": 0, "auto": 1, "lds": 2}[tiling], buf, len(buf))
-    if st != 0:
-        raise ConvNetError(f"rcn_hipx_plan: {st}: {buf.value.decode()}")
-    return buf.value.decode()
+        return _plan_text("rcn_hipx_plan_buckets", lib.rcn_hipx_plan_buckets, *args, int(buckets))
+    return _plan_text("rcn_hipx_plan", lib.rcn_hipx_plan, *args)
 
 
 def plan_eval(in_shape: Tuple[int, int, int], layers: Sequence[tuple], batch: int, precision: str = "fp32", tiling: str = "auto") -> str:
     """Which kernels ONE evaluation chunk of `batch` rows would launch (rcn_hipx_plan_eval): the forward launches of `plan` and the
     evaluation kernel, one line per launch.  Needs no GPU."""
-    lib = load()
-    arr = (XLayer * len(layers))()
-    for i, l in enumerate(layers):
-        arr[i].kind, arr[i].out = KIND[l[0]], int(l[1]) if len(l) > 1 else 0
-    buf = C.create_string_buffer(1 << 16)
-    st = lib.rcn_hipx_plan_eval(in_shape[0], in_shape[1], in_shape[2], arr, len(layers), batch, PRECISIONS[precision], {"gemm": 0, "auto": 1, "lds": 2}[tiling], buf, len(buf))
-    if st != 0:
-        raise ConvNetError(f"rcn_hipx_plan_eval: {st}: {buf.value.decode()}")
-    return buf.value.decode()
+    return _plan_text("rcn_hipx_plan_eval", load().rcn_hipx_plan_eval, in_shape[0], in_shape[1], in_shape[2], _layer_array(layers), len(layers), batch,
+                      PRECISIONS[precision], TILINGS[tiling])
 
 
 X_KIND = {"float32": 0, "uint8": 1}      # RCN_HIPX_X_F32 / RCN_HIPX_X_U8, by the set's torch dtype
@@ -244,11 +254,9 @@ class ConvNet:
         torch.cuda.set_device(self.device)
         self.stream = torch.cuda.Stream(device=self.device)
         self.in_shape, self.layers, self.max_batch = tuple(in_shape), [tuple(l) for l in layers], max_batch
-        arr = (XLayer * len(layers))()
-        for i, l in enumerate(layers):
-            arr[i].kind, arr[i].out = KIND[l[0]], int(l[1]) if len(l) > 1 else 0
         self.net = C.c_void_p()
-        st = self.lib.rcn_hipx_create(device, in_shape[0], in_shape[1], in_shape[2], arr, len(layers), max_batch, C.c_void_p(self.stream.cuda_stream), C.byref(self.net))
+        st = self.lib.rcn_hipx_create(device, in_shape[0], in_shape[1], in_shape[2], _layer_array(layers), len(layers), max_batch, C.c_void_p(self.stream.cuda_stream),
+                                      C.byref(self.net))
         if st != 0:
             msg = self.lib.rcn_hipx_last_error(self.net).decode() if self.net.value else f"status {st}"
             if self.net.value:
@@ -285,7 +293,7 @@ class ConvNet:
 
     def set_tiling(self, mode: str):
         """fp32 3x3 kernels: "gemm" (implicit GEMM only), "auto" (by shape, the default) or "lds" (LDS-tiled wherever they apply)."""
-        self._ck(self.lib.rcn_hipx_set_tiling(self.net, {"gemm": 0, "auto": 1, "lds": 2}[mode]))
+        self._ck(self.lib.rcn_hipx_set_tiling(self.net, TILINGS[mode]))
 
     def set_overlap(self, mode):
         """Backward pass: weight gradients on a second stream beside the input-gradient chain: 0 / False = no (default: measured no
@@ -304,21 +312,23 @@ class ConvNet:
 
     def plan_of_this_net(self, batch: int) -> str:
         """The launches a training step of THIS net would make, with its own precision, tiling and options (rcn_hipx_plan_net)."""
-        buf = C.create_string_buffer(1 << 16)
-        st = self.lib.rcn_hipx_plan_net(self.net, int(batch), buf, len(buf))
-        if st != 0:
-            raise ConvNetError(f"rcn_hipx_plan_net: {st}: {buf.value.decode()}")
-        return buf.value.decode()
+        return _plan_text("rcn_hipx_plan_net", self.lib.rcn_hipx_plan_net, self.net, int(batch))
 
-    def set_params(self, flat: np.ndarray):
+    def _set_flat(self, fn, flat: np.ndarray):
         f = np.ascontiguousarray(flat, dtype=np.float32)
         assert f.size == self.n_logical
-        self._ck(self.lib.rcn_hipx_set_params(self.net, f.ctypes.data_as(C.POINTER(C.c_float))))
+        self._ck(fn(self.net, _fptr(f)))
+
+    def _get_flat(self, fn) -> np.ndarray:
+        f = np.zeros(self.n_logical, dtype=np.float32)
+        self._ck(fn(self.net, _fptr(f)))
+        return f
+
+    def set_params(self, flat: np.ndarray):
+        self._set_flat(self.lib.rcn_hipx_set_params, flat)
 
     def get_params(self) -> np.ndarray:
-        f = np.zeros(self.n_logical, dtype=np.float32)
-        self._ck(self.lib.rcn_hipx_get_params(self.net, f.ctypes.data_as(C.POINTER(C.c_float))))
-        return f
+        return self._get_flat(self.lib.rcn_hipx_get_params)
 
     def init_params(self, seed: int = 1):
         self._ck(self.lib.rcn_hipx_init_params(self.net, seed))
@@ -329,20 +339,17 @@ class ConvNet:
 
     def forward(self, x):
         out = self.torch.empty(x.shape[0], self.classes, dtype=self.torch.float32, device=self.device)
-        self._ck(self.lib.rcn_hipx_forward_dev(self.net, C.c_void_p(x.data_ptr()), x.shape[0], C.c_void_p(out.data_ptr())))
+        self._ck(self.lib.rcn_hipx_forward_dev(self.net, _ptr(x), x.shape[0], _ptr(out)))
         return out
 
     def train_step(self, x, labels, lr: float, loss=None):
-        self._ck(self.lib.rcn_hipx_train_step_dev(self.net, C.c_void_p(x.data_ptr()), C.c_void_p(labels.data_ptr()), x.shape[0], lr,
-                                                  C.c_void_p(loss.data_ptr()) if loss is not None else None))
+        self._ck(self.lib.rcn_hipx_train_step_dev(self.net, _ptr(x), _ptr(labels), x.shape[0], lr, _ptr(loss)))
 
     def train_step_pair(self, x, labels_a, labels_b, weight, lr: float, loss=None):
         """train_step on pair labels (rcn_hipx_train_step_pair_dev): sample s has the target w * onehot(labels_a[s]) + (1 - w) *
         onehot(labels_b[s]), smoothed by set_loss's label_smoothing.  weight: a one-element float32 device tensor holding w, read by the
         loss launch (None: w = 1)."""
-        self._ck(self.lib.rcn_hipx_train_step_pair_dev(self.net, C.c_void_p(x.data_ptr()), C.c_void_p(labels_a.data_ptr()), C.c_void_p(labels_b.data_ptr()),
-                                                       C.c_void_p(weight.data_ptr()) if weight is not None else None, x.shape[0], lr,
-                                                       C.c_void_p(loss.data_ptr()) if loss is not None else None))
+        self._ck(self.lib.rcn_hipx_train_step_pair_dev(self.net, _ptr(x), _ptr(labels_a), _ptr(labels_b), _ptr(weight), x.shape[0], lr, _ptr(loss)))
 
     def _mix_records(self, mix, count: int):
         """the pointer of `count` rcn_hipx_mix_step records in a contiguous device tensor (any dtype: the bytes of a MIX_DTYPE array)"""
@@ -350,7 +357,7 @@ class ConvNet:
             raise ValueError(f"mix: a contiguous tensor on the net's device holding at least {count} records of {MIX_DTYPE.itemsize} bytes (MIX_DTYPE)")
         if mix.data_ptr() % 4:
             raise ValueError("mix: the records must be 4-byte aligned")
-        return C.c_void_p(mix.data_ptr())
+        return _ptr(mix)
 
     def mix_to_device(self, records: np.ndarray):
         """a MIX_DTYPE array (mix_plan's) as a device tensor of its bytes: train_epoch's and gather_mix's `mix`"""
@@ -410,23 +417,17 @@ class ConvNet:
                 raise ValueError("lr: a float, or a contiguous one-dimensional float32 tensor on the net's device with at least n_batches elements")
             if n_batches > 0 and not bool(t.isfinite(lr[:n_batches]).all()):
                 raise ValueError("lr: the schedule holds a value that is not finite")
-            lr_dev, lr = C.c_void_p(lr.data_ptr()), 0.0
-        if mix is not None:
-            recs = self._mix_records(mix, n_batches)
-            keep, aug = _aug_ref(augment)
-            self._ck(self.lib.rcn_hipx_train_epoch_mix_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift), C.c_void_p(labels.data_ptr()), n,
-                                                           C.c_void_p(perm.data_ptr()) if perm is not None else None, B, first_batch, n_batches, float(lr), lr_dev, aug, recs,
-                                                           C.c_void_p(losses.data_ptr()) if losses is not None else None))
-            return
-        if lr_dev is None and augment is None:
-            self._ck(self.lib.rcn_hipx_train_epoch_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift), C.c_void_p(labels.data_ptr()), n,
-                                                       C.c_void_p(perm.data_ptr()) if perm is not None else None, B, first_batch, n_batches, float(lr),
-                                                       C.c_void_p(losses.data_ptr()) if losses is not None else None))
-            return
+            lr_dev, lr = _ptr(lr), 0.0
+        recs = self._mix_records(mix, n_batches) if mix is not None else None
         keep, aug = _aug_ref(augment)
-        self._ck(self.lib.rcn_hipx_train_epoch_ex_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift), C.c_void_p(labels.data_ptr()), n,
-                                                      C.c_void_p(perm.data_ptr()) if perm is not None else None, B, first_batch, n_batches, float(lr), lr_dev, aug,
-                                                      C.c_void_p(losses.data_ptr()) if losses is not None else None))
+        # (rcn_hipx_train_epoch_dev and _ex_dev are this entry with NULLs)
+        self._ck(self.lib.rcn_hipx_train_epoch_mix_dev(self.net, _ptr(X), kind, float(x_scale), float(x_shift), _ptr(labels), n, _ptr(perm), B, first_batch, n_batches, float(lr),
+                                                       lr_dev, aug, recs, _ptr(losses)))
+
+    def _index_row(self, idx, B: int):
+        """gather_batch's and gather_mix's idx: None, or B row numbers"""
+        if idx is not None and (idx.dtype != self.torch.int32 or idx.dim() != 1 or idx.device != self.device or not idx.is_contiguous() or idx.numel() < B):
+            raise ValueError("idx: a contiguous one-dimensional int32 tensor on the net's device with at least B entries")
 
     def gather_batch(self, X, labels, idx, B: int, base: int = 0, augment: Optional[Augment] = None, q0: int = 0,
                      x_scale: float = 1.0 / 255.0, x_shift: float = 0.0):
@@ -436,17 +437,13 @@ class ConvNet:
         t = self.torch
         kind, n = self._resident_set(X, labels)
         B = int(B)
-        if idx is not None:
-            if idx.dtype != t.int32 or idx.dim() != 1 or idx.device != self.device or not idx.is_contiguous() or idx.numel() < B:
-                raise ValueError("idx: a contiguous one-dimensional int32 tensor on the net's device with at least B entries")
+        self._index_row(idx, B)
         with t.cuda.stream(self.stream):
             x = t.empty((max(B, 0),) + self.in_shape, dtype=t.float32, device=self.device)
             y = t.empty(max(B, 0), dtype=t.int32, device=self.device) if labels is not None else None
         keep, aug = _aug_ref(augment)
-        self._ck(self.lib.rcn_hipx_gather_batch_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift),
-                                                    C.c_void_p(labels.data_ptr()) if labels is not None else None, n,
-                                                    C.c_void_p(idx.data_ptr()) if idx is not None else None, int(base), B, aug, int(q0) & (2 ** 64 - 1),
-                                                    C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None))
+        self._ck(self.lib.rcn_hipx_gather_batch_dev(self.net, _ptr(X), kind, float(x_scale), float(x_shift), _ptr(labels), n, _ptr(idx), int(base), B, aug,
+                                                    int(q0) & (2 ** 64 - 1), _ptr(x), _ptr(y)))
         return x, y
 
     def gather_mix(self, X, labels, idx, B: int, mix, base: int = 0, augment: Optional[Augment] = None, q0: int = 0,
@@ -457,34 +454,23 @@ class ConvNet:
         t = self.torch
         kind, n = self._resident_set(X, labels)
         B = int(B)
-        if idx is not None:
-            if idx.dtype != t.int32 or idx.dim() != 1 or idx.device != self.device or not idx.is_contiguous() or idx.numel() < B:
-                raise ValueError("idx: a contiguous one-dimensional int32 tensor on the net's device with at least B entries")
+        self._index_row(idx, B)
         rec = self._mix_records(mix, 1)
         with t.cuda.stream(self.stream):
             x = t.empty((max(B, 0),) + self.in_shape, dtype=t.float32, device=self.device)
             ya = t.empty(max(B, 0), dtype=t.int32, device=self.device) if labels is not None else None
             yb = t.empty(max(B, 0), dtype=t.int32, device=self.device) if labels is not None else None
         keep, aug = _aug_ref(augment)
-        self._ck(self.lib.rcn_hipx_gather_mix_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift),
-                                                  C.c_void_p(labels.data_ptr()) if labels is not None else None, n,
-                                                  C.c_void_p(idx.data_ptr()) if idx is not None else None, int(base), B, aug, int(q0) & (2 ** 64 - 1), rec,
-                                                  C.c_void_p(x.data_ptr()), C.c_void_p(ya.data_ptr()) if ya is not None else None,
-                                                  C.c_void_p(yb.data_ptr()) if yb is not None else None))
+        self._ck(self.lib.rcn_hipx_gather_mix_dev(self.net, _ptr(X), kind, float(x_scale), float(x_shift), _ptr(labels), n, _ptr(idx), int(base), B, aug,
+                                                  int(q0) & (2 ** 64 - 1), rec, _ptr(x), _ptr(ya), _ptr(yb)))
         return x, ya, yb
 
     def plan_epoch_of_this_net(self, batch: int, x_dtype: str = "uint8", lr_from_device: bool = False, augment: Optional[Augment] = None, mix: bool = False) -> str:
         """What one step of train_epoch launches for THIS net (rcn_hipx_plan_epoch_net / _mix_net): the gather, the copy of a scheduled rate
         (and, mix: of the step's target weight), the graph's key, then plan_of_this_net's text.  x_dtype: "uint8" or "float32", the set's storage."""
-        buf = C.create_string_buffer(1 << 16)
         keep, aug = _aug_ref(augment)
-        if mix:
-            st = self.lib.rcn_hipx_plan_epoch_mix_net(self.net, int(batch), X_KIND[x_dtype], int(bool(lr_from_device)), aug, 1, buf, len(buf))
-        else:
-            st = self.lib.rcn_hipx_plan_epoch_net(self.net, int(batch), X_KIND[x_dtype], int(bool(lr_from_device)), aug, buf, len(buf))
-        if st != 0:
-            raise ConvNetError(f"rcn_hipx_plan_epoch_net: {st}: {buf.value.decode()}")
-        return buf.value.decode()
+        # (rcn_hipx_plan_epoch_net is this entry with mix = 0)
+        return _plan_text("rcn_hipx_plan_epoch_net", self.lib.rcn_hipx_plan_epoch_mix_net, self.net, int(batch), X_KIND[x_dtype], int(bool(lr_from_device)), aug, int(bool(mix)))
 
     def evaluate_async(self, X, labels=None, x_scale: float = 1.0 / 255.0, x_shift: float = 0.0, want_pred: bool = True, weights: str = "live"):
         """Forward pass, loss and arg-max over ALL rows of a resident set (rcn_hipx_evaluate_ex_dev), enqueued on the net's stream: returns the
@@ -499,9 +485,8 @@ class ConvNet:
             loss_sum = t.zeros(1, dtype=t.float64, device=self.device)
             correct = t.zeros(1, dtype=t.int64, device=self.device)
             pred = t.empty(n, dtype=t.int32, device=self.device) if (want_pred or labels is None) else None
-        self._ck(self.lib.rcn_hipx_evaluate_ex_dev(self.net, C.c_void_p(X.data_ptr()), kind, float(x_scale), float(x_shift),
-                                                   C.c_void_p(labels.data_ptr()) if labels is not None else None, n, WEIGHTS[weights],
-                                                   C.c_void_p(loss_sum.data_ptr()), C.c_void_p(correct.data_ptr()), C.c_void_p(pred.data_ptr()) if pred is not None else None))
+        self._ck(self.lib.rcn_hipx_evaluate_ex_dev(self.net, _ptr(X), kind, float(x_scale), float(x_shift), _ptr(labels), n, WEIGHTS[weights], _ptr(loss_sum), _ptr(correct),
+                                                   _ptr(pred)))
         return loss_sum, correct, pred
 
     def evaluate(self, X, labels, x_scale: float = 1.0 / 255.0, x_shift: float = 0.0, weights: str = "live") -> Tuple[float, int]:
@@ -524,16 +509,11 @@ class ConvNet:
 
     def plan_eval_of_this_net(self, batch: int) -> str:
         """The launches one evaluation chunk of THIS net would make, with its own precision, tiling and options (rcn_hipx_plan_eval_net)."""
-        buf = C.create_string_buffer(1 << 16)
-        st = self.lib.rcn_hipx_plan_eval_net(self.net, int(batch), buf, len(buf))
-        if st != 0:
-            raise ConvNetError(f"rcn_hipx_plan_eval_net: {st}: {buf.value.decode()}")
-        return buf.value.decode()
+        return _plan_text("rcn_hipx_plan_eval_net", self.lib.rcn_hipx_plan_eval_net, self.net, int(batch))
 
     def gradients(self, x, labels, grad=None, loss=None):
         grad = grad if grad is not None else self.torch.empty(self.n_padded, dtype=self.torch.float32, device=self.device)
-        self._ck(self.lib.rcn_hipx_gradients_dev(self.net, C.c_void_p(x.data_ptr()), C.c_void_p(labels.data_ptr()), x.shape[0], C.c_void_p(grad.data_ptr()),
-                                                 C.c_void_p(loss.data_ptr()) if loss is not None else None))
+        self._ck(self.lib.rcn_hipx_gradients_dev(self.net, _ptr(x), _ptr(labels), x.shape[0], _ptr(grad), _ptr(loss)))
         return grad
 
     def gradients_bucketed(self, x, labels, grad, loss=None, min_bucket_bytes: int = DEFAULT_BUCKET_BYTES, on_bucket=None):
@@ -541,8 +521,8 @@ class ConvNet:
         enqueued, on_bucket(slice_of_grad, k, n) is called -- a data-parallel step starts that slice's all-reduce there, on another stream,
         behind an event of this net's stream.  Bit-identical to `gradients`."""
         nb = C.c_int()
-        self._ck(self.lib.rcn_hipx_gradients_begin_dev(self.net, C.c_void_p(x.data_ptr()), C.c_void_p(labels.data_ptr()), x.shape[0], C.c_void_p(grad.data_ptr()),
-                                                       C.c_void_p(loss.data_ptr()) if loss is not None else None, int(min_bucket_bytes), C.byref(nb)))
+        self._ck(self.lib.rcn_hipx_gradients_begin_dev(self.net, _ptr(x), _ptr(labels), x.shape[0], _ptr(grad), _ptr(loss), int(min_bucket_bytes),
+                                                       C.byref(nb)))
         off, ln = C.c_int64(), C.c_int64()
         for k in range(nb.value):
             self._ck(self.lib.rcn_hipx_gradients_bucket_dev(self.net, k, C.byref(off), C.byref(ln)))
@@ -551,7 +531,7 @@ class ConvNet:
         return grad
 
     def apply(self, grad, scale: float):
-        self._ck(self.lib.rcn_hipx_apply_dev(self.net, C.c_void_p(grad.data_ptr()), scale))
+        self._ck(self.lib.rcn_hipx_apply_dev(self.net, _ptr(grad), scale))
 
     def set_sgd(self, momentum: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False):
         """The optimiser of train_step / apply_sgd: SGD with momentum, weight decay and Nesterov, as torch.optim.SGD with dampening 0
@@ -575,14 +555,10 @@ class ConvNet:
 
     def get_velocity(self) -> np.ndarray:
         """The momentum buffer in the logical layout of get_params (zeros while the net has none)."""
-        f = np.zeros(self.n_logical, dtype=np.float32)
-        self._ck(self.lib.rcn_hipx_get_velocity(self.net, f.ctypes.data_as(C.POINTER(C.c_float))))
-        return f
+        return self._get_flat(self.lib.rcn_hipx_get_velocity)
 
     def set_velocity(self, flat: np.ndarray):
-        f = np.ascontiguousarray(flat, dtype=np.float32)
-        assert f.size == self.n_logical
-        self._ck(self.lib.rcn_hipx_set_velocity(self.net, f.ctypes.data_as(C.POINTER(C.c_float))))
+        self._set_flat(self.lib.rcn_hipx_set_velocity, flat)
 
     def reset_velocity(self):
         self._ck(self.lib.rcn_hipx_reset_velocity(self.net))
@@ -600,14 +576,10 @@ class ConvNet:
 
     def get_ema(self) -> np.ndarray:
         """The average in the logical layout of get_params (ConvNetError, status -6, while the net has none)."""
-        f = np.zeros(self.n_logical, dtype=np.float32)
-        self._ck(self.lib.rcn_hipx_get_ema_params(self.net, f.ctypes.data_as(C.POINTER(C.c_float))))
-        return f
+        return self._get_flat(self.lib.rcn_hipx_get_ema_params)
 
     def set_ema_params(self, flat: np.ndarray):
-        f = np.ascontiguousarray(flat, dtype=np.float32)
-        assert f.size == self.n_logical
-        self._ck(self.lib.rcn_hipx_set_ema_params(self.net, f.ctypes.data_as(C.POINTER(C.c_float))))
+        self._set_flat(self.lib.rcn_hipx_set_ema_params, flat)
 
     def reset_ema(self):
         """The average becomes a copy of the live parameters (a no-op while the net has none)."""
@@ -615,11 +587,11 @@ class ConvNet:
 
     def apply_sgd(self, grad, grad_scale: float, lr: float):
         """The data-parallel half of set_sgd's optimiser: the same update from a padded gradient buffer, scaled by grad_scale first."""
-        self._ck(self.lib.rcn_hipx_apply_sgd_dev(self.net, C.c_void_p(grad.data_ptr()), grad_scale, lr))
+        self._ck(self.lib.rcn_hipx_apply_sgd_dev(self.net, _ptr(grad), grad_scale, lr))
 
     def unpad(self, padded) -> np.ndarray:
         f = np.zeros(self.n_logical, dtype=np.float32)
-        self._ck(self.lib.rcn_hipx_unpad_host(self.net, C.c_void_p(padded.data_ptr()), f.ctypes.data_as(C.POINTER(C.c_float))))
+        self._ck(self.lib.rcn_hipx_unpad_host(self.net, _ptr(padded), _fptr(f)))
         return f
 
     def step_hbm_floor_bytes(self, B: int, stored16: bool = False) -> float:

@@ -31,8 +31,12 @@ using namespace rcnx;
 
 namespace {
 
+// device memory that frees itself (the device that allocated it must be current: rcn_hipx_destroy); move-only
 struct Buf {
     void* p = nullptr; size_t cap = 0;
+    Buf() = default;
+    Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    ~Buf() { if (p) (void)hipFree(p); }
     hipError_t ensure(size_t bytes) {
         if (bytes <= cap) return hipSuccess;
         if (p) (void)hipFree(p);
@@ -42,10 +46,10 @@ struct Buf {
         if (e == hipSuccess) cap = want;
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
-struct Layer {
+// what a layer IS (all that a dry-run net copies: copy_layer_table) ...
+struct LayerShape {
     int kind;
     int H, W, Cin;          // input of the layer
     int oH, oW, Cout;       // output (logical Cout)
@@ -54,16 +58,20 @@ struct Layer {
     long long w_off = 0, b_off = 0;       // padded flat layout
     long long lw_off = 0, lb_off = 0;     // logical flat layout
     bool pool_follows = false;
+};
+// ... and what it holds on the device
+struct Layer : LayerShape {
     Buf out, idx, dout;     // activation (post-ReLU / pooled), pool arg-max, gradient wrt the layer's OUTPUT
     Buf slab;               // partial [W | b] tiles of the weight-gradient kernels (reduced for all layers at once: k_reduce_all)
     long long wbf_off = -1, wbb_off = -1;   // bf16 mode: this layer's transposed bf16 weight copies in net->wb16 (forward / input-gradient operand)
 };
 
-struct Key { const void* x; const void* y; int B; float lr; const void* loss;
-    bool operator<(const Key& o) const { return std::tie(x, y, B, lr, loss) < std::tie(o.x, o.y, o.B, o.lr, o.loss); } };
-// rcn_hipx_train_step_pair_dev's
-struct PairKey { const void* x; const void* ya; const void* yb; const void* w; int B; float lr; const void* loss;
-    bool operator<(const PairKey& o) const { return std::tie(x, ya, yb, w, B, lr, loss) < std::tie(o.x, o.ya, o.yb, o.w, o.B, o.lr, o.loss); } };
+// everything a captured step bakes in: its arguments are step_core's
+struct StepKey {
+    const float* x; const int32_t* labels; const int32_t* labels_b; const float* weight; int B; float lr; const float* lr_dev; float* loss;
+    auto tie() const { return std::tie(x, labels, labels_b, weight, B, lr, lr_dev, loss); }
+    bool operator<(const StepKey& o) const { return tie() < o.tie(); }
+};
 // the second label of every sample and the weight of the first (a device scalar; nullptr: 1) of a step on pair labels; none: labels_b == nullptr
 struct Pair { const int32_t* labels_b = nullptr; const float* weight = nullptr; };
 
@@ -96,24 +104,23 @@ struct rcn_hipx_net : Selection {
     // (n_pad floats, laid out like params) is allocated by the first decay > 0 and never moved afterwards: captured graphs hold its pointer.
     float ema_decay = 0.f;
     Buf ema;
-    std::map<Key, hipGraphExec_t> graphs;
+    // The captured steps, one cache per family (family_of): the caller's pointers plain or on pair labels (rcn_hipx_train_step_dev /
+    // _pair_dev), and the epoch's steps on the net's own buffers x (rate from the host | from the device) x (mixed or not).  A family
+    // that holds eight graphs and needs a ninth drops its own; drop_graphs drops them all.
+    static constexpr int kFamilies = 6;
+    std::map<StepKey, hipGraphExec_t> graphs[kFamilies];
     // rcn_hipx_train_epoch_dev / rcn_hipx_evaluate_dev: the batch the gather kernel fills (max_batch rows, fp32), its labels and the step's
     // loss scalar.  Allocated once, never moved: the epoch's step always sees these three pointers, so ONE captured graph per (B, lr)
     // serves every batch of every epoch, whatever set, permutation and loss slots the caller passes.
     Buf xb, yb, eloss;
-    std::map<std::pair<int, float>, hipGraphExec_t> epoch_graphs;
     // a per-step schedule (rcn_hipx_train_epoch_ex_dev with lr_dev): the rate of the step lives in this 4-byte scalar, allocated once and
     // never moved, the update launch reads it (k_reduce_all_dlr), and ONE graph per B serves every schedule
     Buf elr;
-    std::map<int, hipGraphExec_t> epoch_graphs_dlr;
     // the loss (rcn_hipx_set_loss): 0 is the hard cross-entropy through k_softmax_ce / k_head_f32<true>
     float loss_eps = 0.f;
-    std::map<PairKey, hipGraphExec_t> pair_graphs;      // rcn_hipx_train_step_pair_dev
     // mixed samples (rcn_hipx_train_epoch_mix_dev with records): the partners' labels beside yb and the step's target weight, allocated
     // once and never moved; the mixed step's loss launch reads (yb, yb2, emixw), so ONE more graph per (B, lr) / per B serves every record
     Buf yb2, emixw;
-    std::map<std::pair<int, float>, hipGraphExec_t> epoch_graphs_mix;
-    std::map<int, hipGraphExec_t> epoch_graphs_mix_dlr;
     Buf eval_part;                          // k_eval_ce: [loss partials][correct partials][counter: zero between launches]
     long long n_instantiated = 0;           // hipGraphs instantiated since the net was created (rcn_hipx_graphs_instantiated)
     bool walk_open = false;                 // between rcn_hipx_gradients_begin_dev and its last bucket: the activations belong to that walk
@@ -205,6 +212,8 @@ template <typename F> void with_bool(bool v, F&& f) { if (v) f(std::true_type{})
 // a tensor's storage type: __bf16 or float
 template <typename T> struct Type { using type = T; };
 template <typename F> void with_storage(bool is16, F&& f) { if (is16) f(Type<__bf16>{}); else f(Type<float>{}); }
+// ... and a resident set's row type: uint8_t or float
+template <typename F> void with_row_type(bool u8, F&& f) { if (u8) f(Type<uint8_t>{}); else f(Type<float>{}); }
 // (epilogue, pooled-resolution input) of the LDS-tiled forward kernels: a pooled-resolution input only occurs in the input-gradient pass
 // (EPI 0 / 3); false: no such kernel
 template <typename F> bool with_epi_pin(int kepi, bool pin, F&& f) {
@@ -364,8 +373,6 @@ int launch_wgrad(rcn_hipx_net* n, const float* X, const float* dZ, ConvShape s, 
     XTRY(n, hipGetLastError());
     return 0;
 }
-#undef CT
-#undef CV
 
 float* P(rcn_hipx_net* n, long long off) { return (float*)n->params.p + off; }
 
@@ -653,20 +660,17 @@ std::string soft_note(const rcn_hipx_net* n, const Pair& pair) {
 int loss_and_dlogits(rcn_hipx_net* n, const int32_t* labels, int B, float* loss_dev, bool want_grad, const Pair& pair = Pair{}) {
     Layer& l = n->L.back();
     const int blocks = (B + 7) / 8;                       // eight samples per workgroup
-    if (soft_loss(n, pair)) {
-        if (dry_note(n, "  loss: k_softmax_ce_soft, %d workgroups%s", blocks, soft_note(n, pair).c_str())) return 0;
-        unsigned* counter = nullptr;
-        RTRY(ensure_loss_buf(n, &counter));
-        hipLaunchKernelGGL(k_softmax_ce_soft, dim3(blocks), dim3(256), 0, n->stream, (const float*)l.out.p, labels, SoftTarget{pair.labels_b, pair.weight, n->loss_eps}, B, n->classes,
-                           l.CoutP, want_grad ? (float*)l.dout.p : (float*)nullptr, (float*)n->loss_part.p, counter, 1.0f / (float)B, loss_dev);
-        XTRY(n, hipGetLastError());
-        return 0;
-    }
-    if (dry_note(n, "  loss: k_softmax_ce, %d workgroups", blocks)) return 0;
+    const bool soft = soft_loss(n, pair);
+    if (dry_note(n, "  loss: k_softmax_ce%s, %d workgroups%s", soft ? "_soft" : "", blocks, soft ? soft_note(n, pair).c_str() : "")) return 0;
     unsigned* counter = nullptr;
     RTRY(ensure_loss_buf(n, &counter));
-    hipLaunchKernelGGL(k_softmax_ce, dim3(blocks), dim3(256), 0, n->stream, (const float*)l.out.p, labels, B, n->classes, l.CoutP, want_grad ? (float*)l.dout.p : (float*)nullptr,
-                       (float*)n->loss_part.p, counter, 1.0f / (float)B, loss_dev);
+    const float* const logits = (const float*)l.out.p;
+    float* const dlogits = want_grad ? (float*)l.dout.p : (float*)nullptr;
+    float* const part = (float*)n->loss_part.p;
+    const float inv_b = 1.0f / (float)B;
+    if (soft) hipLaunchKernelGGL(k_softmax_ce_soft, dim3(blocks), dim3(256), 0, n->stream, logits, labels, SoftTarget{pair.labels_b, pair.weight, n->loss_eps}, B, n->classes, l.CoutP,
+                                 dlogits, part, counter, inv_b, loss_dev);
+    else hipLaunchKernelGGL(k_softmax_ce, dim3(blocks), dim3(256), 0, n->stream, logits, labels, B, n->classes, l.CoutP, dlogits, part, counter, inv_b, loss_dev);
     XTRY(n, hipGetLastError());
     return 0;
 }
@@ -689,34 +693,30 @@ int launch_head(rcn_hipx_net* n, const int32_t* labels, int B, float* loss_dev, 
     Layer& b = n->L[n->L.size() - 2];
     const int F = l.K, blocks = (B + 31) / 32;
     const bool soft = soft_loss(n, pair);
-    if (soft ? dry_note(n, "  head %d -> %d classes (logits, softmax + cross-entropy, gradient into the hidden layer, weight-gradient partials): k_head_f32<true, true>, %d workgroups%s",
-                        F, n->classes, blocks, soft_note(n, pair).c_str())
-             : dry_note(n, "  head %d -> %d classes (logits, softmax + cross-entropy, gradient into the hidden layer, weight-gradient partials): k_head_f32, %d workgroups", F, n->classes, blocks)) {
-        *chunks_out = blocks;
-        return 0;
-    }
+    *chunks_out = blocks;
+    if (dry_note(n, "  head %d -> %d classes (logits, softmax + cross-entropy, gradient into the hidden layer, weight-gradient partials): k_head_f32%s, %d workgroups%s",
+                 F, n->classes, soft ? "<true, true>" : "", blocks, soft ? soft_note(n, pair).c_str() : "")) return 0;
     XTRY(n, scratch_ensure(n, (*n->slab_sel), (size_t)blocks * (F + 1) * 32 * sizeof(float)));
     unsigned* counter = nullptr;
     RTRY(ensure_loss_buf(n, &counter));
     const size_t lds = ((size_t)32 * (F + 1) + (size_t)F * 32 + (size_t)32 * (F + 32) + 4 * 1024 + 1024 + 32 * 33) * sizeof(float);
-    // more than 64 KB of dynamic LDS has to be asked for (at most 127 KB here: F <= 256)
+    // the hard kernel, or the soft one with its one trailing argument
+    auto launch = [&](auto kernel, auto... target) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kThreads), lds, n->stream, (const float*)b.out.p, (const float*)P(n, l.w_off), (const float*)n->wt.p + l.w_off,
+                           (const float*)P(n, l.b_off), labels, B, F, n->classes, (float*)l.out.p, (float*)b.dout.p, (float*)(*n->slab_sel).p, (float*)n->loss_part.p, counter,
+                           1.0f / (float)B, loss_dev, target...);
+    };
+    // more than 64 KB of dynamic LDS has to be asked for (at most 127 KB here: F <= 256), once per kernel
     if (soft) {
         static const hipError_t attr_soft = hipFuncSetAttribute((const void*)k_head_f32<true, true, SoftTarget>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         XTRY(n, attr_soft);
-        hipLaunchKernelGGL((k_head_f32<true, true, SoftTarget>), dim3(blocks), dim3(kThreads), lds, n->stream, (const float*)b.out.p, (const float*)P(n, l.w_off),
-                           (const float*)n->wt.p + l.w_off, (const float*)P(n, l.b_off), labels, B, F, n->classes, (float*)l.out.p, (float*)b.dout.p, (float*)(*n->slab_sel).p,
-                           (float*)n->loss_part.p, counter, 1.0f / (float)B, loss_dev, SoftTarget{pair.labels_b, pair.weight, n->loss_eps});
-        XTRY(n, hipGetLastError());
-        *chunks_out = blocks;
-        return 0;
+        launch(k_head_f32<true, true, SoftTarget>, SoftTarget{pair.labels_b, pair.weight, n->loss_eps});
+    } else {
+        static const hipError_t attr = hipFuncSetAttribute((const void*)k_head_f32<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        XTRY(n, attr);
+        launch(k_head_f32<true>);
     }
-    static const hipError_t attr = hipFuncSetAttribute((const void*)k_head_f32<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    XTRY(n, attr);
-    hipLaunchKernelGGL((k_head_f32<true>), dim3(blocks), dim3(kThreads), lds, n->stream, (const float*)b.out.p, (const float*)P(n, l.w_off), (const float*)n->wt.p + l.w_off,
-                       (const float*)P(n, l.b_off), labels, B, F, n->classes, (float*)l.out.p, (float*)b.dout.p, (float*)(*n->slab_sel).p, (float*)n->loss_part.p, counter,
-                       1.0f / (float)B, loss_dev);
     XTRY(n, hipGetLastError());
-    *chunks_out = blocks;
     return 0;
 }
 
@@ -764,12 +764,9 @@ int step_core(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, flo
     return backward(n, x, B, lr, grad, apply, first, gated, lr_dev);
 }
 
-template <typename M> void drop_all(M& graphs) { for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second); graphs.clear(); }
-// every captured graph of the net: the steps on callers' pointers and the epoch's steps on the net's own batch buffer
-void drop_graphs(rcn_hipx_net* n) {
-    drop_all(n->graphs); drop_all(n->epoch_graphs); drop_all(n->epoch_graphs_dlr);
-    drop_all(n->pair_graphs); drop_all(n->epoch_graphs_mix); drop_all(n->epoch_graphs_mix_dlr);
-}
+void drop_all(std::map<StepKey, hipGraphExec_t>& graphs) { for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second); graphs.clear(); }
+// every captured graph of the net, whatever its family
+void drop_graphs(rcn_hipx_net* n) { for (auto& family : n->graphs) drop_all(family); }
 
 // ---- gradient buckets: the data-parallel step with its all-reduce overlapped with the backward pass -------------------------------------
 // The layers with parameters, walked from the last to the first (the order the backward pass finishes them), are cut into buckets of at
@@ -862,7 +859,7 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
             l.w_off = n->n_pad; n->n_pad += (long long)l.K * l.CoutP; l.b_off = n->n_pad; n->n_pad += l.CoutP;
             l.lw_off = n->n_log; n->n_log += (long long)l.K * l.Cout; l.lb_off = n->n_log; n->n_log += l.Cout;
         }
-        n->L.push_back(l);
+        n->L.push_back(std::move(l));
     }
     if (n->L.back().kind != RCN_HIPX_DENSE) return fail(n, -2, "the last layer must be RCN_HIPX_DENSE (logits)");
     n->classes = n->L.back().Cout;
@@ -871,12 +868,7 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
 
 // the layer descriptions of `from` without their buffers (host-only dry-run nets)
 void copy_layer_table(rcn_hipx_net& to, const rcn_hipx_net& from) {
-    for (const Layer& l : from.L) {
-        Layer c;
-        c.kind = l.kind; c.H = l.H; c.W = l.W; c.Cin = l.Cin; c.oH = l.oH; c.oW = l.oW; c.Cout = l.Cout; c.CoutP = l.CoutP; c.K = l.K;
-        c.w_off = l.w_off; c.b_off = l.b_off; c.lw_off = l.lw_off; c.lb_off = l.lb_off; c.pool_follows = l.pool_follows;
-        to.L.push_back(c);
-    }
+    for (const Layer& l : from.L) { to.L.emplace_back(); static_cast<LayerShape&>(to.L.back()) = l; }
     to.n_pad = from.n_pad; to.n_log = from.n_log;
 }
 
@@ -910,6 +902,22 @@ int store16_covered(const rcn_hipx_net& n, std::string* why) {
 }
 
 const char* precision_name(int precision, bool store16) { return precision != RCN_HIPX_BF16 ? "fp32 operands" : store16 ? "bf16 operands, the convolutional stage's tensors stored as bf16" : "bf16 operands"; }
+
+// ---- the plans' shared pieces
+// the arguments every plan of a description shares
+bool plan_args_ok(int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, int n_layers, int batch, int precision, int tiling, const char* out, int cap) {
+    return layers && n_layers >= 1 && in_h >= 1 && in_w >= 1 && in_c >= 1 && batch >= 1 && out && cap >= 1 &&
+           (precision == RCN_HIPX_FP32 || precision == RCN_HIPX_BF16 || precision == RCN_HIPX_BF16_STORED) && tiling >= RCN_HIPX_TILING_GEMM && tiling <= RCN_HIPX_TILING_LDS;
+}
+// the sentence in front of a training step's launches
+std::string step_header(const rcn_hipx_net& net, int batch) {
+    return "forward + loss + backward of one batch of " + std::to_string(batch) + " (" + precision_name(net.precision, net.store16) + "), launch by launch:\n";
+}
+// a dry walk's text, or why it stopped, into the caller's buffer; returns the walk's status
+int emit(const rcn_hipx_net& net, int st, char* out, int cap) {
+    std::snprintf(out, (size_t)cap, "%s", (st == 0 ? net.plan : net.err).c_str());
+    return st;
+}
 
 }  // namespace
 
@@ -947,17 +955,13 @@ int rcn_hipx_create(int device, int in_h, int in_w, int in_c, const rcn_hipx_lay
 
 void rcn_hipx_destroy(rcn_hipx_net* n) {
     if (!n) return;
-    {
-        Dev g(n->device);
-        if (n->stream) (void)hipStreamSynchronize(n->stream);
-        drop_graphs(n);
-        for (Layer& l : n->L) { l.out.release(); l.idx.release(); l.dout.release(); l.slab.release(); }
-        for (Buf* b : {&n->params, &n->wt, &n->wb16, &n->dz, &n->loss_part, &n->grad_tmp, &n->dlogits, &n->skbuf, &n->wb, &n->vel, &n->ema, &n->xb, &n->yb, &n->eloss, &n->elr, &n->yb2, &n->emixw, &n->eval_part}) b->release();
-        if (n->side) { (void)hipStreamSynchronize(n->side); (void)hipStreamDestroy(n->side); }
-        for (hipEvent_t e : n->events) (void)hipEventDestroy(e);
-        if (n->own_stream && n->stream) (void)hipStreamDestroy(n->stream);
-    }
-    delete n;
+    Dev g(n->device);
+    if (n->stream) (void)hipStreamSynchronize(n->stream);
+    drop_graphs(n);
+    if (n->side) { (void)hipStreamSynchronize(n->side); (void)hipStreamDestroy(n->side); }
+    for (hipEvent_t e : n->events) (void)hipEventDestroy(e);
+    if (n->own_stream && n->stream) (void)hipStreamDestroy(n->stream);
+    delete n;                                           // every Buf frees its memory here: the device current, the streams drained
 }
 
 const char* rcn_hipx_last_error(const rcn_hipx_net* n) { return n ? n->err.c_str() : "null net"; }
@@ -1022,16 +1026,24 @@ int rcn_hipx_get_option(const rcn_hipx_net* n, const char* name, int* value) {
     return -1;
 }
 
-int rcn_hipx_set_params(rcn_hipx_net* n, const float* flat) {
-    if (!n || !flat) return -1;
-    Dev g(n->device);
+// a flat logical array (rcn_hipx_get_params' layout) into a padded buffer of the net, the padding zero; unpad is its inverse.  Returns
+// with the copy done: the staging array must outlive it.
+static int upload_padded(rcn_hipx_net* n, Buf& to, const float* flat) {
     std::vector<float> pad((size_t)n->n_pad, 0.f);
     for (const Layer& l : n->L) {
         if (l.kind == RCN_HIPX_MAXPOOL2) continue;
         for (int k = 0; k < l.K; ++k) std::memcpy(&pad[l.w_off + (long long)k * l.CoutP], &flat[l.lw_off + (long long)k * l.Cout], sizeof(float) * l.Cout);
         std::memcpy(&pad[l.b_off], &flat[l.lb_off], sizeof(float) * l.Cout);
     }
-    XTRY(n, hipMemcpyAsync(n->params.p, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice, n->stream));
+    XTRY(n, hipMemcpyAsync(to.p, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice, n->stream));
+    XTRY(n, hipStreamSynchronize(n->stream));
+    return 0;
+}
+
+int rcn_hipx_set_params(rcn_hipx_net* n, const float* flat) {
+    if (!n || !flat) return -1;
+    Dev g(n->device);
+    RTRY(upload_padded(n, n->params, flat));
     RTRY(refresh_flipped(n));
     XTRY(n, hipStreamSynchronize(n->stream));
     return 0;
@@ -1078,12 +1090,12 @@ int rcn_hipx_forward_dev(rcn_hipx_net* n, const float* x, int B, float* logits) 
 
 // One eager step (it sizes every scratch buffer outside capture: hipMalloc is illegal while capturing -- and it IS the caller's step),
 // then the same step captured and instantiated for the replays that follow.
-static int step_and_capture(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float lr, float* loss_dev, hipGraphExec_t* exec_out, const float* lr_dev = nullptr,
-                            const Pair& pair = Pair{}) {
-    RTRY(step_core(n, x, labels, B, lr, nullptr, true, loss_dev, lr_dev, pair));
+static int step_and_capture(rcn_hipx_net* n, const StepKey& k, hipGraphExec_t* exec_out) {
+    const Pair pair{k.labels_b, k.weight};
+    RTRY(step_core(n, k.x, k.labels, k.B, k.lr, nullptr, true, k.loss, k.lr_dev, pair));
     hipGraph_t graph = nullptr;
     XTRY(n, hipStreamBeginCapture(n->stream, hipStreamCaptureModeThreadLocal));
-    const int st = step_core(n, x, labels, B, lr, nullptr, true, loss_dev, lr_dev, pair);
+    const int st = step_core(n, k.x, k.labels, k.B, k.lr, nullptr, true, k.loss, k.lr_dev, pair);
     hipError_t e = hipStreamEndCapture(n->stream, &graph);
     if (st != 0) { if (graph) (void)hipGraphDestroy(graph); return st; }
     XTRY(n, e);
@@ -1096,22 +1108,30 @@ static int step_and_capture(rcn_hipx_net* n, const float* x, const int32_t* labe
     return 0;
 }
 
+// which of the net's caches a step belongs to: on the caller's pointers (plain 0, pair labels 1), or on the net's own batch buffer with
+// its rate from the host (2, mixed 3) or from the device (4, mixed 5)
+static int family_of(const rcn_hipx_net* n, const StepKey& k) { return (k.x != n->xb.p ? 0 : k.lr_dev ? 4 : 2) + (k.labels_b ? 1 : 0); }
+static_assert(rcn_hipx_net::kFamilies == 6, "family_of hands out 0 .. 5");
+
+// One training step through the cache: a replay of the graph captured for `key`, or -- at its first use -- the eager step (which IS the
+// caller's step) and its capture.  Looked up per step: the eager step of a first use can grow a scratch buffer, which drops every graph.
+static int captured_step(rcn_hipx_net* n, const StepKey& key) {
+    auto& graphs = n->graphs[family_of(n, key)];
+    auto it = graphs.find(key);
+    if (it != graphs.end()) { XTRY(n, hipGraphLaunch(it->second, n->stream)); return 0; }
+    hipGraphExec_t exec = nullptr;
+    RTRY(step_and_capture(n, key, &exec));
+    if (graphs.size() >= 8) drop_all(graphs);           // (eight keys: a caller that varies lr per call)
+    graphs.emplace(key, exec);
+    return 0;
+}
+
 int rcn_hipx_train_step_dev(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float lr, float* loss_dev) {
     if (!n || !x || !labels) return -1;
     RTRY(ensure_batch(n, B));
     Dev g(n->device);
     n->walk_open = false;                               // (a step in between abandons an open bucket walk's activations)
-    const Key key{x, labels, B, lr, loss_dev};
-    auto it = n->graphs.find(key);
-    if (it == n->graphs.end()) {
-        hipGraphExec_t exec = nullptr;
-        RTRY(step_and_capture(n, x, labels, B, lr, loss_dev, &exec));
-        if (n->graphs.size() >= 8) drop_all(n->graphs);
-        n->graphs.emplace(key, exec);
-        return 0;                                       // the eager step WAS this call's step
-    }
-    XTRY(n, hipGraphLaunch(it->second, n->stream));
-    return 0;
+    return captured_step(n, StepKey{x, labels, nullptr, nullptr, B, lr, nullptr, loss_dev});
 }
 
 int rcn_hipx_train_step_pair_dev(rcn_hipx_net* n, const float* x, const int32_t* labels_a, const int32_t* labels_b, const float* weight, int B, float lr, float* loss_dev) {
@@ -1119,17 +1139,7 @@ int rcn_hipx_train_step_pair_dev(rcn_hipx_net* n, const float* x, const int32_t*
     RTRY(ensure_batch(n, B));
     Dev g(n->device);
     n->walk_open = false;
-    const PairKey key{x, labels_a, labels_b, weight, B, lr, loss_dev};
-    auto it = n->pair_graphs.find(key);
-    if (it == n->pair_graphs.end()) {
-        hipGraphExec_t exec = nullptr;
-        RTRY(step_and_capture(n, x, labels_a, B, lr, loss_dev, &exec, nullptr, Pair{labels_b, weight}));
-        if (n->pair_graphs.size() >= 8) drop_all(n->pair_graphs);
-        n->pair_graphs.emplace(key, exec);
-        return 0;                                       // the eager step WAS this call's step
-    }
-    XTRY(n, hipGraphLaunch(it->second, n->stream));
-    return 0;
+    return captured_step(n, StepKey{x, labels_a, labels_b, weight, B, lr, nullptr, loss_dev});
 }
 
 // ---- the loop around the step: an epoch over a device-resident set, and evaluation --------------------------------------------------------
@@ -1173,48 +1183,35 @@ int launch_gather(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, flo
     const bool dry = n->dry;                            // (a plan: the set and the batch buffer are taken to be aligned, as allocators return them)
     const GatherChoice c = select_gather(u8, B, E, dry || (uintptr_t)X % 16 == 0, dry || (uintptr_t)dst % 16 == 0, aug != nullptr, mix != nullptr);
     if (!c.blocks) return fail(n, -3, "a batch of more than 2^37 elements");
+    const AugSpec as = aug ? AugSpec{aug->seed, aug->epoch, aug->pad, aug->hflip} : AugSpec{0, 0, 0, 0};
+    const dim3 grid((unsigned)c.blocks), block(kGatherThreads);
+    const int H = n->in_h, W = n->in_w, Cc = n->in_c;
     if (mix) {
         char augtext[48] = "no augmentation";
         if (aug) std::snprintf(augtext, sizeof augtext, "augment pad %d hflip %d", (int)aug->pad, (int)aug->hflip);
         if (dry_note(n, "  gather: k_gather_mix<%s, %d>, %s, %lld workgroups, partner row B - 1 - r, %s", u8 ? "uint8" : "float", c.vec,
                      c.vec == 4 ? "one or two source elements per output, 16-byte stores" : "element by element", c.blocks, augtext)) return 0;
-        const AugSpec as = aug ? AugSpec{aug->seed, aug->epoch, aug->pad, aug->hflip} : AugSpec{0, 0, 0, 0};
-        const dim3 grid((unsigned)c.blocks), block(kGatherThreads);
-        const int H = n->in_h, W = n->in_w, Cc = n->in_c, has_aug = aug ? 1 : 0;
-        const MixStep* const m = reinterpret_cast<const MixStep*>(mix);
-        if (u8 && c.vec == 4) hipLaunchKernelGGL((k_gather_mix<uint8_t, 4>), grid, block, 0, n->stream, (const uint8_t*)X, labels, rows, idx, base, B, H, W, Cc, rs, has_aug, as, q0, m, dst, ydst, ydst_b);
-        else if (u8) hipLaunchKernelGGL((k_gather_mix<uint8_t, 1>), grid, block, 0, n->stream, (const uint8_t*)X, labels, rows, idx, base, B, H, W, Cc, rs, has_aug, as, q0, m, dst, ydst, ydst_b);
-        else if (c.vec == 4) hipLaunchKernelGGL((k_gather_mix<float, 4>), grid, block, 0, n->stream, (const float*)X, labels, rows, idx, base, B, H, W, Cc, rs, has_aug, as, q0, m, dst, ydst, ydst_b);
-        else hipLaunchKernelGGL((k_gather_mix<float, 1>), grid, block, 0, n->stream, (const float*)X, labels, rows, idx, base, B, H, W, Cc, rs, has_aug, as, q0, m, dst, ydst, ydst_b);
-        XTRY(n, hipGetLastError());
-        return 0;
-    }
-    if (aug) {
+        with_row_type(u8, [&](auto T) { with_const<4, 1>(c.vec, [&](auto VEC) {
+            hipLaunchKernelGGL((k_gather_mix<CT(T), CV(VEC)>), grid, block, 0, n->stream, (const CT(T)*)X, labels, rows, idx, base, B, H, W, Cc, rs, aug ? 1 : 0, as, q0,
+                               reinterpret_cast<const MixStep*>(mix), dst, ydst, ydst_b);
+        }); });
+    } else if (aug) {
         if (dry_note(n, "  gather: k_gather_aug<%s, %d>, %s, %lld workgroups, augment pad %d hflip %d", u8 ? "uint8" : "float", c.vec,
                      c.vec == 4 ? "one source element per output, 16-byte stores" : "element by element", c.blocks, (int)aug->pad, (int)aug->hflip)) return 0;
-        const AugSpec as{aug->seed, aug->epoch, aug->pad, aug->hflip};
-        const dim3 grid((unsigned)c.blocks), block(kGatherThreads);
-        const int H = n->in_h, W = n->in_w, Cc = n->in_c;
-        if (u8 && c.vec == 4) hipLaunchKernelGGL((k_gather_aug<uint8_t, 4>), grid, block, 0, n->stream, (const uint8_t*)X, labels, rows, idx, base, B, H, W, Cc, rs, as, q0, dst, ydst);
-        else if (u8) hipLaunchKernelGGL((k_gather_aug<uint8_t, 1>), grid, block, 0, n->stream, (const uint8_t*)X, labels, rows, idx, base, B, H, W, Cc, rs, as, q0, dst, ydst);
-        else if (c.vec == 4) hipLaunchKernelGGL((k_gather_aug<float, 4>), grid, block, 0, n->stream, (const float*)X, labels, rows, idx, base, B, H, W, Cc, rs, as, q0, dst, ydst);
-        else hipLaunchKernelGGL((k_gather_aug<float, 1>), grid, block, 0, n->stream, (const float*)X, labels, rows, idx, base, B, H, W, Cc, rs, as, q0, dst, ydst);
-        XTRY(n, hipGetLastError());
-        return 0;
-    }
-    if (dry_note(n, "  gather: k_gather_rows<%s, %d>, %s, %lld workgroups", u8 ? "uint8" : "float", c.vec, c.vec > 1 ? "16-byte loads and stores" : "element by element", c.blocks)) return 0;
-    if (u8) {
-        if (c.vec > 1) hipLaunchKernelGGL((k_gather_rows<uint8_t, RowPiece<uint8_t>::kVec>), dim3((unsigned)c.blocks), dim3(kGatherThreads), 0, n->stream,
-                                          (const uint8_t*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
-        else hipLaunchKernelGGL((k_gather_rows<uint8_t, 1>), dim3((unsigned)c.blocks), dim3(kGatherThreads), 0, n->stream, (const uint8_t*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
+        with_row_type(u8, [&](auto T) { with_const<4, 1>(c.vec, [&](auto VEC) {
+            hipLaunchKernelGGL((k_gather_aug<CT(T), CV(VEC)>), grid, block, 0, n->stream, (const CT(T)*)X, labels, rows, idx, base, B, H, W, Cc, rs, as, q0, dst, ydst);
+        }); });
     } else {
-        if (c.vec > 1) hipLaunchKernelGGL((k_gather_rows<float, RowPiece<float>::kVec>), dim3((unsigned)c.blocks), dim3(kGatherThreads), 0, n->stream,
-                                          (const float*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
-        else hipLaunchKernelGGL((k_gather_rows<float, 1>), dim3((unsigned)c.blocks), dim3(kGatherThreads), 0, n->stream, (const float*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
+        if (dry_note(n, "  gather: k_gather_rows<%s, %d>, %s, %lld workgroups", u8 ? "uint8" : "float", c.vec, c.vec > 1 ? "16-byte loads and stores" : "element by element", c.blocks)) return 0;
+        with_row_type(u8, [&](auto T) { with_bool(c.vec > 1, [&](auto PIECES) {
+            hipLaunchKernelGGL((k_gather_rows<CT(T), CV(PIECES) ? RowPiece<CT(T)>::kVec : 1>), grid, block, 0, n->stream, (const CT(T)*)X, labels, rows, idx, base, B, E, rs, dst, ydst);
+        }); });
     }
     XTRY(n, hipGetLastError());
     return 0;
 }
+#undef CT
+#undef CV
 
 // loss sum, correct count and arg-max of the B logits rows the forward pass has just left in the last layer's output
 int launch_eval(rcn_hipx_net* n, const int32_t* labels, int B, double* loss_sum, long long* correct, int32_t* pred) {
@@ -1262,23 +1259,6 @@ int plan_eval_walk(rcn_hipx_net& net, int batch) {
 
 }  // namespace
 
-extern "C++" {                                          // (a template, inside the header's extern "C" block)
-namespace {
-// One step of an epoch on the net's own buffers: the eager step and its capture at the first use of `key`, a replay afterwards.  (The
-// graphs are looked up per step: the eager step of a first use can grow a scratch buffer, which drops every graph.)
-template <typename M, typename K>
-int epoch_step(rcn_hipx_net* n, M& graphs, const K& key, int B, float lr, const float* lr_dev, const Pair& pair) {
-    auto it = graphs.find(key);
-    if (it != graphs.end()) { XTRY(n, hipGraphLaunch(it->second, n->stream)); return 0; }
-    hipGraphExec_t exec = nullptr;
-    RTRY(step_and_capture(n, (const float*)n->xb.p, (const int32_t*)n->yb.p, B, lr, (float*)n->eloss.p, &exec, lr_dev, pair));
-    if (graphs.size() >= 8) drop_all(graphs);           // (eight keys: a caller that varies lr per call)
-    graphs.emplace(key, exec);
-    return 0;
-}
-}  // namespace
-}  // extern "C++"
-
 int rcn_hipx_train_epoch_mix_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows, const int32_t* perm,
                                  int B, int64_t first_batch, int64_t n_batches, float lr, const float* lr_dev, const rcn_hipx_augment* aug, const rcn_hipx_mix_step* mix_dev,
                                  float* loss_dev) {
@@ -1298,9 +1278,9 @@ int rcn_hipx_train_epoch_mix_dev(rcn_hipx_net* n, const void* X, int x_kind, flo
     int32_t* const yb = (int32_t*)n->yb.p;
     float* const el = (float*)n->eloss.p;
     float* const elr = (float*)n->elr.p;
-    // mixed: the step's loss launch reads the net's own two labels buffers and its weight scalar
-    const Pair pair = mix_dev ? Pair{(const int32_t*)n->yb2.p, (const float*)n->emixw.p} : Pair{};
-    const std::pair<int, float> key{B, lr};
+    // the step on the net's own buffers -- mixed: its loss launch reads the two labels buffers and the weight scalar; scheduled: its update
+    // reads the rate scalar -- so ONE graph serves every batch
+    const StepKey key{xb, yb, mix_dev ? (const int32_t*)n->yb2.p : nullptr, mix_dev ? (const float*)n->emixw.p : nullptr, B, lr_dev ? 0.f : lr, lr_dev ? elr : nullptr, el};
     for (int64_t s = first_batch; s < first_batch + n_batches; ++s) {
         const rcn_hipx_mix_step* const rec = mix_dev ? mix_dev + (s - first_batch) : nullptr;
         RTRY(launch_gather(n, X, x_kind, x_scale, x_shift, labels, (long long)rows, perm ? perm + s * B : nullptr, (long long)s * B, B, aug, (unsigned long long)s * (unsigned long long)B, xb, yb,
@@ -1308,8 +1288,7 @@ int rcn_hipx_train_epoch_mix_dev(rcn_hipx_net* n, const void* X, int x_kind, flo
         // the step's rate (and target weight) into the net's scalars, outside the graph: the eager step and every replay read them there
         if (lr_dev) XTRY(n, hipMemcpyAsync(elr, lr_dev + (s - first_batch), sizeof(float), hipMemcpyDeviceToDevice, n->stream));
         if (rec) XTRY(n, hipMemcpyAsync(n->emixw.p, &rec->weight, sizeof(float), hipMemcpyDeviceToDevice, n->stream));
-        if (lr_dev) RTRY(mix_dev ? epoch_step(n, n->epoch_graphs_mix_dlr, B, B, 0.f, elr, pair) : epoch_step(n, n->epoch_graphs_dlr, B, B, 0.f, elr, pair));
-        else RTRY(mix_dev ? epoch_step(n, n->epoch_graphs_mix, key, B, lr, nullptr, pair) : epoch_step(n, n->epoch_graphs, key, B, lr, nullptr, pair));
+        RTRY(captured_step(n, key));
         if (loss_dev) XTRY(n, hipMemcpyAsync(loss_dev + (s - first_batch), el, sizeof(float), hipMemcpyDeviceToDevice, n->stream));
     }
     return 0;
@@ -1446,12 +1425,18 @@ __global__ void k_axpy(float* __restrict__ p, const float* __restrict__ g, float
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) p[i] = p[i] - scale * g[i];
 }
 
+// p <- p - scale * g over the padded parameters
+static int launch_axpy(rcn_hipx_net* n, const float* grad, float scale) {
+    hipLaunchKernelGGL(k_axpy, dim3(grid1d(n->n_pad, 256)), dim3(256), 0, n->stream, (float*)n->params.p, grad, scale, n->n_pad);
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+
 int rcn_hipx_apply_dev(rcn_hipx_net* n, const float* grad, float scale) {
     if (!n || !grad) return -1;
     Dev g(n->device);
-    hipLaunchKernelGGL(k_axpy, dim3(grid1d(n->n_pad, 256)), dim3(256), 0, n->stream, (float*)n->params.p, grad, scale, n->n_pad);
-    XTRY(n, hipGetLastError());
-    return refresh_flipped(n);
+    RTRY(launch_axpy(n, grad, scale));
+    return refresh_flipped(n);                          // (the plain axpy: neither the velocity nor the average moves)
 }
 
 int rcn_hipx_set_sgd(rcn_hipx_net* n, float momentum, float weight_decay, int nesterov) {
@@ -1510,15 +1495,7 @@ int rcn_hipx_set_velocity(rcn_hipx_net* n, const float* flat) {
     if (!n || !flat) return -1;
     if (n->sgd_mu == 0.f || !n->vel.p) return fail(n, -6, "set_velocity: the net has no momentum (rcn_hipx_set_sgd first)");
     Dev g(n->device);
-    std::vector<float> pad((size_t)n->n_pad, 0.f);
-    for (const Layer& l : n->L) {
-        if (l.kind == RCN_HIPX_MAXPOOL2) continue;
-        for (int k = 0; k < l.K; ++k) std::memcpy(&pad[l.w_off + (long long)k * l.CoutP], &flat[l.lw_off + (long long)k * l.Cout], sizeof(float) * l.Cout);
-        std::memcpy(&pad[l.b_off], &flat[l.lb_off], sizeof(float) * l.Cout);
-    }
-    XTRY(n, hipMemcpyAsync(n->vel.p, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice, n->stream));
-    XTRY(n, hipStreamSynchronize(n->stream));
-    return 0;
+    return upload_padded(n, n->vel, flat);
 }
 
 int rcn_hipx_reset_velocity(rcn_hipx_net* n) {
@@ -1573,15 +1550,7 @@ int rcn_hipx_set_ema_params(rcn_hipx_net* n, const float* flat) {
     if (!n || !flat) return -1;
     if (!n->ema.p) return fail(n, -6, "set_ema_params: the net has no average (rcn_hipx_set_ema with a decay > 0 first)");
     Dev g(n->device);
-    std::vector<float> pad((size_t)n->n_pad, 0.f);
-    for (const Layer& l : n->L) {
-        if (l.kind == RCN_HIPX_MAXPOOL2) continue;
-        for (int k = 0; k < l.K; ++k) std::memcpy(&pad[l.w_off + (long long)k * l.CoutP], &flat[l.lw_off + (long long)k * l.Cout], sizeof(float) * l.Cout);
-        std::memcpy(&pad[l.b_off], &flat[l.lb_off], sizeof(float) * l.Cout);
-    }
-    XTRY(n, hipMemcpyAsync(n->ema.p, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice, n->stream));
-    XTRY(n, hipStreamSynchronize(n->stream));
-    return 0;
+    return upload_padded(n, n->ema, flat);
 }
 
 int rcn_hipx_reset_ema(rcn_hipx_net* n) {
@@ -1595,16 +1564,12 @@ int rcn_hipx_reset_ema(rcn_hipx_net* n) {
 int rcn_hipx_apply_sgd_dev(rcn_hipx_net* n, const float* grad, float grad_scale, float lr) {
     if (!n || !grad) return -1;
     Dev g(n->device);
-    if (sgd_default(n)) {
-        // plain SGD: exactly rcn_hipx_apply_dev(grad, grad_scale * lr)
-        hipLaunchKernelGGL(k_axpy, dim3(grid1d(n->n_pad, 256)), dim3(256), 0, n->stream, (float*)n->params.p, grad, grad_scale * lr, n->n_pad);
+    if (sgd_default(n)) RTRY(launch_axpy(n, grad, grad_scale * lr));      // plain SGD: rcn_hipx_apply_dev(grad, grad_scale * lr)'s launch
+    else {
+        if ((uintptr_t)grad % 16 != 0) return fail(n, -1, "apply_sgd: the gradient buffer must be 16-byte aligned");
+        hipLaunchKernelGGL(k_sgd_apply, dim3(grid1d(n->n_pad / 4, 256)), dim3(256), 0, n->stream, (float*)n->params.p, grad, grad_scale, lr, sgd_params(n), n->n_pad);
         XTRY(n, hipGetLastError());
-        RTRY(apply_ema(n));
-        return refresh_flipped(n);
     }
-    if ((uintptr_t)grad % 16 != 0) return fail(n, -1, "apply_sgd: the gradient buffer must be 16-byte aligned");
-    hipLaunchKernelGGL(k_sgd_apply, dim3(grid1d(n->n_pad / 4, 256)), dim3(256), 0, n->stream, (float*)n->params.p, grad, grad_scale, lr, sgd_params(n), n->n_pad);
-    XTRY(n, hipGetLastError());
     RTRY(apply_ema(n));
     return refresh_flipped(n);
 }
@@ -1623,25 +1588,21 @@ int rcn_hipx_step_flops(const rcn_hipx_net* n, int B, double* flops) {
 }
 
 int rcn_hipx_plan(int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, int n_layers, int batch, int precision, int tiling, char* out, int cap) {
-    if (!layers || n_layers < 1 || in_h < 1 || in_w < 1 || in_c < 1 || batch < 1 || !out || cap < 1) return -1;
-    if ((precision != RCN_HIPX_FP32 && precision != RCN_HIPX_BF16 && precision != RCN_HIPX_BF16_STORED) || tiling < RCN_HIPX_TILING_GEMM || tiling > RCN_HIPX_TILING_LDS) return -1;
+    if (!plan_args_ok(in_h, in_w, in_c, layers, n_layers, batch, precision, tiling, out, cap)) return -1;
     rcn_hipx_net net;                                   // (its options: as a net created now would have them; rcn_hipx_plan_net: an existing net's own)
     int st = make_dry_net(net, in_h, in_w, in_c, layers, n_layers, batch, precision, tiling);
     if (st == 0) {
-        net.plan = "forward + loss + backward of one batch of " + std::to_string(batch) + " (" + precision_name(net.precision, net.store16) + "), launch by launch:\n";
+        net.plan = step_header(net, batch);
         st = step_core(&net, nullptr, nullptr, batch, 0.f, nullptr, true, nullptr);
     }
-    const std::string& text = st == 0 ? net.plan : net.err;
-    std::snprintf(out, (size_t)cap, "%s", text.c_str());
-    return st;
+    return emit(net, st, out, cap);
 }
 
 // The bucketed gradient step of a data-parallel rank, launch by launch and bucket by bucket (no GPU needed): forward + loss, then for every
 // bucket the backward pass of its layers, the ONE reduction launch of their slabs, and the slice of the flat gradient that is final there.
 int rcn_hipx_plan_buckets(int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, int n_layers, int batch, int precision, int tiling, int64_t min_bucket_bytes,
                           char* out, int cap) {
-    if (!layers || n_layers < 1 || in_h < 1 || in_w < 1 || in_c < 1 || batch < 1 || !out || cap < 1 || min_bucket_bytes < 0) return -1;
-    if ((precision != RCN_HIPX_FP32 && precision != RCN_HIPX_BF16 && precision != RCN_HIPX_BF16_STORED) || tiling < RCN_HIPX_TILING_GEMM || tiling > RCN_HIPX_TILING_LDS) return -1;
+    if (!plan_args_ok(in_h, in_w, in_c, layers, n_layers, batch, precision, tiling, out, cap) || min_bucket_bytes < 0) return -1;
     rcn_hipx_net net;
     int st = make_dry_net(net, in_h, in_w, in_c, layers, n_layers, batch, precision, tiling);
     if (st == 0) {
@@ -1651,9 +1612,7 @@ int rcn_hipx_plan_buckets(int in_h, int in_w, int in_c, const rcn_hipx_layer* la
         st = nb < 0 ? nb : 0;
         for (int k = 0; st == 0 && k < nb; ++k) st = grad_bucket(&net, k, nullptr, nullptr);
     }
-    const std::string& text = st == 0 ? net.plan : net.err;
-    std::snprintf(out, (size_t)cap, "%s", text.c_str());
-    return st;
+    return emit(net, st, out, cap);
 }
 
 // the same walk for an EXISTING net, with that net's own precision, tiling, options and optimiser
@@ -1661,11 +1620,9 @@ int rcn_hipx_plan_net(const rcn_hipx_net* n, int batch, char* out, int cap) {
     if (!n || batch < 1 || batch > n->max_batch || !out || cap < 1) return -1;
     rcn_hipx_net net;
     make_dry_net(net, *n, batch);
-    net.plan = "forward + loss + backward of one batch of " + std::to_string(batch) + " (" + precision_name(net.precision, net.store16) + "), launch by launch:\n";
+    net.plan = step_header(net, batch);
     const int st = step_core(&net, nullptr, nullptr, batch, 0.f, nullptr, true, nullptr);
-    const std::string& text = st == 0 ? net.plan : net.err;
-    std::snprintf(out, (size_t)cap, "%s", text.c_str());
-    return st;
+    return emit(net, st, out, cap);
 }
 
 // One step of an epoch of an EXISTING net (rcn_hipx_train_epoch_mix_dev): what is launched around the captured graph -- the gather, the copy
@@ -1688,12 +1645,10 @@ int rcn_hipx_plan_epoch_mix_net(const rcn_hipx_net* n, int batch, int x_kind, in
         if (mix) (void)dry_note(&net, "  weight: 4-byte device copy of mix_dev[i].weight into the net's target-weight scalar (hipMemcpyAsync, outside the graph)");
         if (mix) (void)dry_note(&net, lr_from_device ? "  graph: one graph per B, lr from device, pair labels" : "  graph: one graph per (B, lr), pair labels");
         else (void)dry_note(&net, lr_from_device ? "  graph: one graph per B, lr from device" : "  graph: one graph per (B, lr)");
-        net.plan += "forward + loss + backward of one batch of " + std::to_string(batch) + " (" + precision_name(net.precision, net.store16) + "), launch by launch:\n";
+        net.plan += step_header(net, batch);
         st = step_core(&net, nullptr, nullptr, batch, 0.f, nullptr, true, nullptr, lr_from_device ? marker : nullptr, pair);
     }
-    const std::string& text = st == 0 ? net.plan : net.err;
-    std::snprintf(out, (size_t)cap, "%s", text.c_str());
-    return st;
+    return emit(net, st, out, cap);
 }
 
 int rcn_hipx_plan_epoch_net(const rcn_hipx_net* n, int batch, int x_kind, int lr_from_device, const rcn_hipx_augment* aug, char* out, int cap) {
@@ -1703,8 +1658,7 @@ int rcn_hipx_plan_epoch_net(const rcn_hipx_net* n, int batch, int x_kind, int lr
 // rcn_hipx_plan's dry walk for ONE evaluation chunk: the forward pass over all layers and the evaluation kernel.  A net that
 // rcn_hipx_set_precision would refuse (RCN_HIPX_BF16_STORED on layers the bf16-tensor kernels do not cover) is refused here with the same text.
 int rcn_hipx_plan_eval(int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, int n_layers, int batch, int precision, int tiling, char* out, int cap) {
-    if (!layers || n_layers < 1 || in_h < 1 || in_w < 1 || in_c < 1 || batch < 1 || !out || cap < 1) return -1;
-    if ((precision != RCN_HIPX_FP32 && precision != RCN_HIPX_BF16 && precision != RCN_HIPX_BF16_STORED) || tiling < RCN_HIPX_TILING_GEMM || tiling > RCN_HIPX_TILING_LDS) return -1;
+    if (!plan_args_ok(in_h, in_w, in_c, layers, n_layers, batch, precision, tiling, out, cap)) return -1;
     rcn_hipx_net net;
     int st = make_dry_net(net, in_h, in_w, in_c, layers, n_layers, batch, precision, tiling);
     if (st == 0 && net.store16) {
@@ -1713,9 +1667,7 @@ int rcn_hipx_plan_eval(int in_h, int in_w, int in_c, const rcn_hipx_layer* layer
         if (st != 0) net.err = why;
     }
     if (st == 0) st = plan_eval_walk(net, batch);
-    const std::string& text = st == 0 ? net.plan : net.err;
-    std::snprintf(out, (size_t)cap, "%s", text.c_str());
-    return st;
+    return emit(net, st, out, cap);
 }
 
 // the same walk for an EXISTING net, with that net's own precision, tiling and options
@@ -1724,9 +1676,7 @@ int rcn_hipx_plan_eval_net(const rcn_hipx_net* n, int batch, char* out, int cap)
     rcn_hipx_net net;
     make_dry_net(net, *n, batch);
     const int st = plan_eval_walk(net, batch);
-    const std::string& text = st == 0 ? net.plan : net.err;
-    std::snprintf(out, (size_t)cap, "%s", text.c_str());
-    return st;
+    return emit(net, st, out, cap);
 }
 
 }  // extern "C"

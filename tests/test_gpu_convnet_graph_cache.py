@@ -1,0 +1,214 @@
+"""GPU tests of Track X's cache of captured steps (csrc/rcn_hipx_api.hip): the six families of graphs -- train_step, train_step_pair and
+train_epoch with its rate from the host or the device, mixed or not -- live side by side, each evicts only itself when it holds eight,
+every setter that changes what a step launches drops all of them, and the epoch and evaluation entries that forward to their extended
+forms give what ConvNet's own calls give.
+
+Every comparison is exact: a count of instantiated graphs, or the bits of parameters, velocity and average of two nets that ran the
+same launches."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+FUSED_HEAD = ((8, 8, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 32), ("dense", 10)), 5)
+PLAIN_HEAD = ((6, 6, 1), (("conv", 32), ("conv", 32), ("pool",), ("dense", 7)), 3)
+SPECS = [FUSED_HEAD, PLAIN_HEAD]
+SPEC_IDS = ["fused_head", "plain_head"]
+SCALE, SHIFT = 1.0 / 255.0, -0.1307
+LR = 0.05
+NB = 4                                                             # batches of the set: 4 * B rows
+
+
+def _net(spec, params=None):
+    from mercer_research_amd.convnet import ConvNet
+    in_shape, layers, B = spec
+    net = ConvNet(in_shape, layers, B)
+    if params is None:
+        net.init_params(7)
+    else:
+        net.set_params(params)
+    return net
+
+
+def _sync():
+    import torch
+    torch.cuda.synchronize()
+
+
+def _dev(net, a):
+    t = net.to_device(a)
+    _sync()
+    return t
+
+
+class _Calls:
+    """The tensors of "the six calls" on one net, all at B = spec[2] and the rate LR.  The batch and labels of train_step / train_step_pair
+    stay the same tensors for the net's life (their pointers are those graphs' keys); round(v) picks the v-th set tensor, permutation,
+    schedule and mixing records of the four train_epoch calls."""
+
+    def __init__(self, net, spec):
+        from mercer_research_amd.convnet import mix_plan
+        self.net, self.B = net, spec[2]
+        (H, W, Cc), layers, B = spec
+        n, classes = NB * B, layers[-1][1]
+        rng = np.random.default_rng(11)
+        self.x = _dev(net, rng.standard_normal((B, H, W, Cc)).astype(np.float32))
+        self.ya = _dev(net, rng.integers(0, classes, B).astype(np.int32))
+        self.yb = _dev(net, rng.integers(0, classes, B).astype(np.int32))
+        self.w = _dev(net, np.array([0.7], dtype=np.float32))
+        self.y = _dev(net, rng.integers(0, classes, n).astype(np.int32))
+        X = rng.integers(0, 256, (n, H, W, Cc)).astype(np.uint8)
+        self.rounds = []
+        for v in range(2):
+            r = np.random.default_rng(100 + v)
+            self.rounds.append((_dev(net, X.copy()), _dev(net, r.permutation(n).astype(np.int32)),
+                                _dev(net, (LR * (1 + v) * (1 + np.arange(NB)) / NB).astype(np.float32)),
+                                net.mix_to_device(mix_plan(NB, H, W, mixup_alpha=0.4, cutmix_alpha=1.0, seed=v))))
+        _sync()
+
+    def call(self, k, v=0, lr=LR):
+        import torch
+        net, B = self.net, self.B
+        X, perm, sched, recs = self.rounds[v]
+        kw = dict(x_scale=SCALE, x_shift=SHIFT)
+        with torch.cuda.stream(net.stream):
+            if k == 1:
+                net.train_step(self.x, self.ya, lr)
+            elif k == 2:
+                net.train_step_pair(self.x, self.ya, self.yb, self.w, lr)
+            elif k == 3:
+                net.train_epoch(X, self.y, perm, B, lr, **kw)
+            elif k == 4:
+                net.train_epoch(X, self.y, perm, B, sched, **kw)
+            elif k == 5:
+                net.train_epoch(X, self.y, perm, B, lr, mix=recs, **kw)
+            else:
+                net.train_epoch(X, self.y, perm, B, sched, mix=recs, **kw)
+        net.synchronize()
+
+    def six(self, v=0):
+        for k in range(1, 7):
+            self.call(k, v)
+
+
+# ---- 1. the families live side by side -------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("spec", SPECS, ids=SPEC_IDS)
+def test_six_families_live_side_by_side(spec):
+    net = _net(spec)
+    c = _Calls(net, spec)
+    g0 = net.graphs_instantiated()
+    c.six(0)
+    g1 = net.graphs_instantiated()
+    print("first round instantiated", g1 - g0)
+    assert 0 <= g1 - g0 <= 6, (g0, g1)
+    c.six(1)                                                       # another set tensor, permutation, schedule and records
+    print("second round instantiated", net.graphs_instantiated() - g1)
+    assert net.graphs_instantiated() == g1
+    net.close()
+
+
+# ---- 2. eviction is per family ---------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("spec", SPECS, ids=SPEC_IDS)
+def test_a_full_family_evicts_only_itself(spec):
+    net = _net(spec)
+    c = _Calls(net, spec)
+    c.six(0)
+    g1 = net.graphs_instantiated()
+    rates = [float(v) for v in (0.001 * (1 + np.arange(9))).astype(np.float32)]
+    assert LR not in rates and len(set(rates)) == 9
+    for lr in rates:
+        c.call(1, lr=lr)
+    g2 = net.graphs_instantiated()
+    print("nine rates instantiated", g2 - g1)
+    assert g2 == g1 + 9
+    for k in range(2, 7):                                          # the other five families kept their graphs
+        c.call(k, 1)
+    assert net.graphs_instantiated() == g2
+    c.call(1, lr=rates[8])                                         # in the cache: it came after the eviction
+    assert net.graphs_instantiated() == g2
+    c.call(1, lr=rates[0])                                         # dropped with the eight
+    assert net.graphs_instantiated() == g2 + 1
+    net.close()
+
+
+# ---- 3. every setter drops every family, and nothing stale replays ---------------------------------------------------------------------
+
+SETTERS = [("set_sgd", (0.9, 5e-4, True)), ("set_loss", (0.1,)), ("set_ema", (0.99,)), ("set_precision", ("bf16",))]
+
+
+@pytest.mark.parametrize("spec", SPECS, ids=SPEC_IDS)
+@pytest.mark.parametrize("setter,args", SETTERS, ids=[s for s, _ in SETTERS])
+def test_a_setter_drops_every_family_and_nothing_stale_replays(spec, setter, args):
+    a = _net(spec)
+    ca = _Calls(a, spec)
+    ca.six(0)
+    before = a.get_params()
+    getattr(a, setter)(*args)
+    g1 = a.graphs_instantiated()
+    ca.six(1)
+    ga = a.graphs_instantiated() - g1
+    b = _net(spec, before)                                         # fresh: the parameters first, then the setter (an average starts as their copy)
+    getattr(b, setter)(*args)
+    cb = _Calls(b, spec)
+    cb.six(1)
+    print("second round instantiated", ga)
+    assert np.array_equal(a.get_params(), b.get_params())
+    assert not np.array_equal(a.get_params(), before)
+    assert np.array_equal(a.get_velocity(), b.get_velocity())
+    if setter == "set_sgd":
+        assert np.abs(a.get_velocity()).max() > 0
+    if setter == "set_ema":
+        assert np.array_equal(a.get_ema(), b.get_ema()) and not np.array_equal(a.get_ema(), a.get_params())
+    assert ga == 6
+    a.close(); b.close()
+
+
+# ---- 4. the forwarding entries, called directly ----------------------------------------------------------------------------------------
+
+def _p(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+@pytest.mark.parametrize("spec", SPECS, ids=SPEC_IDS)
+def test_forwarding_entries_called_directly_are_convnets_own_calls(spec):
+    import torch
+    from mercer_research_amd.convnet import Augment
+    B = spec[2]
+    a = _net(spec)
+    b = _net(spec, a.get_params())
+    ca, cb = _Calls(a, spec), _Calls(b, spec)
+    n = NB * B
+    # rcn_hipx_train_epoch_dev against train_epoch with a float rate
+    X, perm, sched, _ = ca.rounds[0]
+    a._ck(a.lib.rcn_hipx_train_epoch_dev(a.net, _p(X), 1, SCALE, SHIFT, _p(ca.y), n, _p(perm), B, 0, NB, LR, None))
+    a.synchronize()
+    cb.call(3, 0)
+    assert np.array_equal(a.get_params(), b.get_params())
+    # rcn_hipx_train_epoch_ex_dev against train_epoch with a rate tensor and an augmentation
+    aug = Augment(1, True, 3, 0)
+    s = aug.struct()
+    a._ck(a.lib.rcn_hipx_train_epoch_ex_dev(a.net, _p(X), 1, SCALE, SHIFT, _p(ca.y), n, _p(perm), B, 0, NB, 0.0, _p(sched), C.byref(s), None))
+    a.synchronize()
+    Xb, permb, schedb, _ = cb.rounds[0]
+    with torch.cuda.stream(b.stream):
+        b.train_epoch(Xb, cb.y, permb, B, schedb, x_scale=SCALE, x_shift=SHIFT, augment=aug)
+    b.synchronize()
+    assert np.array_equal(a.get_params(), b.get_params())
+    # rcn_hipx_evaluate_dev against evaluate_async
+    with torch.cuda.stream(a.stream):
+        loss_sum = torch.zeros(1, dtype=torch.float64, device=a.device)
+        correct = torch.zeros(1, dtype=torch.int64, device=a.device)
+        pred = torch.full((n,), -1, dtype=torch.int32, device=a.device)
+    _sync()
+    a._ck(a.lib.rcn_hipx_evaluate_dev(a.net, _p(X), 1, SCALE, SHIFT, _p(ca.y), n, _p(loss_sum), _p(correct), _p(pred)))
+    a.synchronize()
+    l2, c2, p2 = b.evaluate_async(Xb, cb.y, x_scale=SCALE, x_shift=SHIFT)
+    b.synchronize()
+    assert np.array_equal(loss_sum.cpu().numpy(), l2.cpu().numpy()) and np.isfinite(loss_sum.item()) and loss_sum.item() > 0
+    assert int(correct.item()) == int(c2.item())
+    assert np.array_equal(pred.cpu().numpy(), p2.cpu().numpy()) and pred.min().item() >= 0
+    a.close(); b.close()

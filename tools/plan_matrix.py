@@ -1,4 +1,4 @@
-"""The text (or the error) of rcn_hipx_plan / rcn_hipx_plan_buckets over a matrix of nets, batches, precisions, tilings and options, in a
+"""The text (or the error) of rcn_hipx_plan / rcn_hipx_plan_buckets / rcn_hipx_plan_eval over a matrix of nets, batches, precisions, tilings and options, in a
 fixed order.  No GPU needed.  Two builds choose the same kernels for every layer exactly when their outputs are equal:
 
     python tools/plan_matrix.py > after.txt          # and the same in a checkout of the commit to compare with (--root)
@@ -51,17 +51,19 @@ def main() -> None:
     root = os.path.abspath(ap.parse_args().root)
     sys.path.insert(0, root)
     import bench_convnet as bc
-    from mercer_research_amd.convnet import ConvNetError, plan
+    from mercer_research_amd.convnet import ConvNetError, plan, plan_eval
     for k in list(os.environ):
         if k.startswith("RCN_HIPX_"):
             del os.environ[k]
 
     def show(title, in_shape, layers, batch, **kw):
-        print(f"==== {title}")
-        try:
-            print("status 0\n" + plan(in_shape, layers, batch, **kw))
-        except ConvNetError as e:
-            print(e)
+        # the training step (or its bucketed gradient walk), then -- where it is a step -- one evaluation chunk of the same net
+        for what, fn in (("", plan), (" eval", plan_eval)) if "buckets" not in kw else (("", plan),):
+            print(f"==== {title}{what}")
+            try:
+                print("status 0\n" + fn(in_shape, layers, batch, **kw))
+            except ConvNetError as e:
+                print(e)
 
     nets = [(name, shape, layers, tuple(b for b in BATCHES if b <= 128) if name == "synth224" else BATCHES) for name, (shape, layers, _) in bc.CONFIGS.items()]
     nets += [(name, shape, layers, BATCHES) for name, (shape, layers) in SMALL.items()]
