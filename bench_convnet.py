@@ -161,6 +161,9 @@ def main():
     ap.add_argument("--ema", type=float, default=0.0, metavar="D",
                     help="keep an exponential moving average of the parameters with decay D inside the update launch (rcn_hipx_set_ema; 0: none), set before the "
                          "timed steps; with --dataset the line gains eval_ema_images_per_s and the average's loss / accuracy beside the live ones")
+    ap.add_argument("--clip", type=float, default=0.0, metavar="M",
+                    help="clip the gradient to a global L2 norm of at most M in front of the update (rcn_hipx_set_clip; 0: off; inf: measure the norm only), set before "
+                         "the timed steps: three launches in the step's graph instead of one; the line gains clip_max_norm and grad_norm_last")
     ap.add_argument("--dataset", type=int, default=0, metavar="N",
                     help="also keep a synthetic set of N images resident (uint8 for mnist / cifar, fp32 for synth224), time train_epoch over whole epochs with a fresh "
                          "device permutation each, then evaluate over the set: the line gains epoch_ms_per_step, epoch_images_per_s, eval_images_per_s, graphs_instantiated "
@@ -182,6 +185,8 @@ def main():
         ap.error("--label-smoothing and --mix time the resident epoch: they need --dataset N")
     if not 0.0 <= args.ema < 1.0:
         ap.error("--ema: 0 <= D < 1")
+    if not args.clip >= 0.0:
+        ap.error("--clip: M >= 0 (inf allowed)")
     if not 0.0 <= args.label_smoothing < 1.0:
         ap.error("--label-smoothing: 0 <= E < 1")
     if (args.lr_schedule != "none" or args.augment >= 0 or args.trap) and not args.dataset:
@@ -221,6 +226,8 @@ def main():
         net.set_sgd(args.momentum, args.weight_decay, args.nesterov)
     if args.ema > 0:
         net.set_ema(args.ema)
+    if args.clip > 0:
+        net.set_clip(args.clip)
     rng = np.random.default_rng(rank)
     nbuf = 8 if args.config != "synth224" else 2           # rotate over several resident batches
     xs = [net.to_device(rng.standard_normal((B,) + in_shape).astype(np.float32)) for _ in range(nbuf)]
@@ -252,7 +259,7 @@ def main():
                         dist.all_reduce(piece, op=dist.ReduceOp.SUM)
                 net.gradients_bucketed(x, y, grad, loss, args.dp_buckets, on_bucket)
                 net.stream.wait_stream(comm)
-            if sgd or args.ema > 0:                        # (apply_sgd keeps the average; apply is the plain axpy and does not)
+            if sgd or args.ema > 0 or args.clip > 0:       # (apply_sgd keeps the average and clips; apply is the plain axpy and does neither)
                 net.apply_sgd(grad, 1.0 / world, lr)
             else:
                 net.apply(grad, lr / world)
@@ -332,6 +339,7 @@ def main():
                           "hbm_floor_ms": round(floor_ms, 4) if floor_ms else None, "frac_of_hbm_floor": round(floor_ms / (el / args.steps * 1e3), 4) if floor_ms else None,
                           "dtype": "f32" if not bf16 else "bf16 MFMA operands (fwd, dgrad, wgrad), f32 accumulate/update" + (", conv-stage activations and gradients stored as bf16" if args.precision == "bf16_stored" else ""), "data": "synthetic", "final_loss": round(loss.item(), 4),
                           "ema_decay": args.ema,
+                          "clip_max_norm": args.clip, "grad_norm_last": round(net.grad_norm()[0], 6) if args.clip > 0 else None,
                           "data_parallel_step": dp_mode,
                           "data_parallel_allreduce": (None if not dp else "one all-reduce of the flat gradient after the backward pass" if args.dp_buckets <= 0 else
                                                       f"{n_buckets[0]} buckets of >= {args.dp_buckets} bytes, each all-reduced on a second stream under the backward pass of the layers below"),

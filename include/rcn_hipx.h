@@ -322,6 +322,50 @@ int  rcn_hipx_get_ema(const rcn_hipx_net* net, float* decay);
 int  rcn_hipx_get_ema_params(rcn_hipx_net* net, float* flat);
 int  rcn_hipx_set_ema_params(rcn_hipx_net* net, const float* flat);
 int  rcn_hipx_reset_ema(rcn_hipx_net* net);
+/* Gradient clipping by global L2 norm, and the norm as a logged quantity: torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2,
+ * error_if_nonfinite=False) over all parameters, biases included.  With g the step's summed gradient in the padded flat layout (padding
+ * elements are 0) and `scale` a factor (1 inside the training step); fp32 unless it says double, every operation rounded once (no fused
+ * multiply-add):
+ *     x_i        = fl(scale * g_i)
+ *     block b    = elements [4096 b, 4096 b + 4096) of the padded buffer, missing ones counting as 0; thread t of 1024 owns 4t .. 4t + 3
+ *     s_t        = ((double)x0*x0 + (double)x1*x1) + ((double)x2*x2 + (double)x3*x3)
+ *     partial[b] = the 1024 s_t combined by the halving tree: strides 512, 256, .., 1; s[t] += s[t + stride] for t < stride
+ *     S          = acc[t] = partial[t] + partial[t + 1024] + ... (increasing index, in double), then the same tree over acc[0 .. 1024)
+ *     norm       = (float)sqrt(S)                          (double square root, one rounding to float)
+ *     coef       = min(1.0f, max_norm / (norm + 1e-6f))    (a NaN quotient stays NaN, as torch.clamp(max=1) keeps it)
+ *     g'_i       = fl(coef * x_i)                          (always multiplied, as torch does; coef == 1 changes no bit)
+ * g' is what the configured update sees as its gradient: plain SGD or rcn_hipx_set_sgd's, the average of rcn_hipx_set_ema behind it, the
+ * rate a constant or from the device scalar; weight decay is added after clipping, as in torch.  tests/_clip_ref.py restates it in NumPy,
+ * bit for bit.  Values are never inspected: a non-finite gradient gives a non-finite norm and reaches the parameters (torch's behaviour
+ * with error_if_nonfinite=False) -- a caller error, not a fault.
+ * With clipping on, the step's one reduction launch becomes three inside the same captured graph: the gradients-only reduction
+ * (k_reduce_all) into a buffer the net owns, k_grad_sumsq over that buffer, and a k_reduce_all_clip[_sgd][_ema][_dlr] launch in which every
+ * workgroup sums the partials in the fixed order above and applies the coefficient in front of the update.
+ * rcn_hipx_set_clip: net state, like rcn_hipx_set_sgd.  Accepts 0 (off, the default: the same kernels, launches, arguments, graph keys and
+ * plan text as a net never configured) and any max_norm > 0; +inf means "measure only" (coef == 1 exactly, the parameters those of an
+ * unclipped step bit for bit).  NaN and negatives return -1 and change nothing.  The first max_norm > 0 allocates the gradient buffer, the
+ * partials and the (norm, coef) / counter state, once; they never move.  A changed value synchronises the net's stream and drops its
+ * captured graphs.  Applies wherever the library applies a training update: rcn_hipx_train_step_dev, rcn_hipx_train_step_pair_dev, the
+ * three epoch entries and rcn_hipx_apply_sgd_dev (k_grad_sumsq of fl(grad_scale * g), then k_sgd_apply_clip -- also with the default
+ * optimiser, where the unclipped path is the axpy; then the average's k_ema_lerp and the flipped copy as ever; with grad_scale = 1
+ * bit-identical to the fused step).  Never applies in rcn_hipx_apply_dev, the gradient / bucket entries (they return the raw gradient) or
+ * evaluation.  The state survives rcn_hipx_set_params and changes of precision, like the velocity. */
+int  rcn_hipx_set_clip(rcn_hipx_net* net, float max_norm);
+int  rcn_hipx_get_clip(const rcn_hipx_net* net, float* max_norm);
+/* (norm, coef) of the last clipped update, after a synchronise of the net's stream (either pointer may be NULL); -6 while clipping was
+ * never switched on. */
+int  rcn_hipx_get_grad_norm(rcn_hipx_net* net, float* norm, float* coef);
+/* A ring of cap >= 1 floats on the device: the k-th clipped update since this call writes its norm into slot k % cap (the update launch's
+ * one writer; no copy, no extra launch) -- how an epoch returns per-step norms.  log_dev == NULL switches it off; cap < 1 with a non-NULL
+ * pointer returns -1.  Setting it synchronises, zeroes the counter and drops the captured graphs (the pointer is a kernel argument).
+ * _count: clipped updates since then, read after a synchronise (0 while clipping was never switched on). */
+int  rcn_hipx_set_grad_norm_log(rcn_hipx_net* net, float* log_dev, int64_t cap);
+int  rcn_hipx_get_grad_norm_count(rcn_hipx_net* net, int64_t* count);
+/* The norm above of ANY device buffer, *norm_dev = (float)sqrt(S) of fl(scale * g_dev[0 .. n)), enqueued on the net's stream (k_grad_sumsq +
+ * k_grad_norm_finish): a data-parallel caller gets the norm of an all-reduced gradient from it.  Requires n >= 0, n % 4 == 0 and a
+ * 16-byte aligned buffer (n == 0: the norm is 0, g_dev may be NULL), else -1.  It uses a scratch of its own, which may grow between
+ * calls, never the step's partials; it neither reads nor changes the net's clip state and works with clipping off. */
+int  rcn_hipx_grad_norm_dev(rcn_hipx_net* net, const float* g_dev, int64_t n, float scale, float* norm_dev);
 /* The same gradients in BUCKETS, so that a data-parallel step can all-reduce one bucket of layers while the backward pass of the layers
  * below it still runs (6.7 MB of gradient for BASELINE configs[3]).  The layers with parameters, in the order the
  * backward pass finishes them (last to first), are cut into buckets of at least min_bucket_bytes of gradient; the padded flat layout
@@ -349,7 +393,9 @@ int  rcn_hipx_plan(int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, i
  * step that follows agree by construction (rcn_hipx_plan describes a net created now, seeded from the environment).  A net with a
  * non-default rcn_hipx_set_sgd setting names its optimiser and the values on the update line; one with rcn_hipx_set_loss eps > 0 names the
  * soft loss kernel and eps on the loss (or head) line; one with rcn_hipx_set_ema decay > 0 names the _ema update kernel and
- * "(EMA: decay %g)" on the update line (rcn_hipx_plan_epoch_net / _mix_net likewise). */
+ * "(EMA: decay %g)" on the update line; one with rcn_hipx_set_clip max_norm > 0 names the three launches of the clipped reduction
+ * (k_reduce_all into the gradient buffer, k_grad_sumsq, k_reduce_all_clip...) and "(clip: max norm %g)" on the update line
+ * (rcn_hipx_plan_epoch_net / _mix_net likewise). */
 int  rcn_hipx_plan_net(const rcn_hipx_net* net, int batch, char* out, int cap);
 /* algorithmic FLOPs of one training step at batch B (2 * MACs; forward + dgrad + wgrad) */
 int  rcn_hipx_step_flops(const rcn_hipx_net* net, int B, double* flops);

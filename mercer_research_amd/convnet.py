@@ -136,6 +136,12 @@ SIGNATURES = {
     "rcn_hipx_set_ema_params": (_i, [_vp, C.POINTER(C.c_float)]),
     "rcn_hipx_reset_ema": (_i, [_vp]),
     "rcn_hipx_evaluate_ex_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _i, _vp, _vp, _vp]),
+    "rcn_hipx_set_clip": (_i, [_vp, C.c_float]),
+    "rcn_hipx_get_clip": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rcn_hipx_get_grad_norm": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "rcn_hipx_set_grad_norm_log": (_i, [_vp, _vp, C.c_int64]),
+    "rcn_hipx_get_grad_norm_count": (_i, [_vp, C.POINTER(C.c_int64)]),
+    "rcn_hipx_grad_norm_dev": (_i, [_vp, _vp, C.c_int64, C.c_float, _vp]),
 }
 _libx = None
 
@@ -584,6 +590,51 @@ class ConvNet:
     def reset_ema(self):
         """The average becomes a copy of the live parameters (a no-op while the net has none)."""
         self._ck(self.lib.rcn_hipx_reset_ema(self.net))
+
+    def set_clip(self, max_norm: float = 0.0):
+        """Gradient clipping by global L2 norm in front of the update, as torch.nn.utils.clip_grad_norm_(params, max_norm) over all
+        parameters (include/rcn_hipx.h, rcn_hipx_set_clip): three launches in the step's graph instead of one.  0 is the default: off.
+        float("inf") measures only: grad_norm() and the log are filled, the parameters are those of an unclipped step bit for bit."""
+        self._ck(self.lib.rcn_hipx_set_clip(self.net, float(max_norm)))
+
+    def get_clip(self) -> float:
+        m = C.c_float()
+        self._ck(self.lib.rcn_hipx_get_clip(self.net, C.byref(m)))
+        return float(m.value)
+
+    def grad_norm(self) -> Tuple[float, float]:
+        """(norm, coef) of the last clipped update as float32 values; synchronises.  ConvNetError, status -6, while clipping was never on."""
+        norm, coef = C.c_float(), C.c_float()
+        self._ck(self.lib.rcn_hipx_get_grad_norm(self.net, C.byref(norm), C.byref(coef)))
+        return float(norm.value), float(coef.value)
+
+    def set_grad_norm_log(self, log):
+        """A ring of norms on the device (rcn_hipx_set_grad_norm_log): the k-th clipped update since this call writes log[k % log.numel()].
+        log: a contiguous float32 tensor on the net's device with at least one element (the net keeps a reference), or None: off."""
+        t = self.torch
+        if log is not None and (not t.is_tensor(log) or log.dtype != t.float32 or log.device != self.device or not log.is_contiguous()):
+            raise ValueError("log: a contiguous float32 tensor on the net's device, or None")
+        if log is not None and log.numel() < 1:          # (an empty tensor's pointer is NULL, which the library reads as "off")
+            raise ValueError("log: at least one element")
+        self._ck(self.lib.rcn_hipx_set_grad_norm_log(self.net, _ptr(log), int(log.numel()) if log is not None else 0))
+        self._grad_norm_log = log
+
+    def grad_norm_count(self) -> int:
+        """Clipped updates since set_grad_norm_log (or since clipping was first switched on); synchronises."""
+        c = C.c_int64()
+        self._ck(self.lib.rcn_hipx_get_grad_norm_count(self.net, C.byref(c)))
+        return int(c.value)
+
+    def grad_norm_of(self, g, scale: float = 1.0):
+        """The clip's norm of any float32 device tensor, (float)sqrt(sum of fl(scale * g)^2 in double), as a one-element device tensor valid
+        on the net's stream (rcn_hipx_grad_norm_dev): numel % 4 == 0 and 16-byte aligned, else ConvNetError (status -1)."""
+        t = self.torch
+        if not t.is_tensor(g) or g.dtype != t.float32 or g.device != self.device or not g.is_contiguous():
+            raise ValueError("grad_norm_of: a contiguous float32 tensor on the net's device")
+        with t.cuda.stream(self.stream):
+            out = t.empty(1, dtype=t.float32, device=self.device)
+        self._ck(self.lib.rcn_hipx_grad_norm_dev(self.net, _ptr(g), int(g.numel()), float(scale), _ptr(out)))
+        return out
 
     def apply_sgd(self, grad, grad_scale: float, lr: float):
         """The data-parallel half of set_sgd's optimiser: the same update from a padded gradient buffer, scaled by grad_scale first."""

@@ -26,6 +26,7 @@
 #include "convnet_select.hpp"
 #include "convnet_sgd.hpp"
 #include "convnet_ema.hpp"
+#include "convnet_clip.hpp"
 
 using namespace rcnx;
 
@@ -104,6 +105,15 @@ struct rcn_hipx_net : Selection {
     // (n_pad floats, laid out like params) is allocated by the first decay > 0 and never moved afterwards: captured graphs hold its pointer.
     float ema_decay = 0.f;
     Buf ema;
+    // clipping by global norm (rcn_hipx_set_clip; convnet_clip.hpp): 0 is off, the update launch of a net never configured.  The first
+    // max_norm > 0 allocates, once and outside any capture, the step's gradient buffer (n_pad floats), k_grad_sumsq's partials
+    // (ceil(n_pad / 4096) doubles) and the state [8-byte step counter][norm][coef]; none of them ever moves: captured graphs hold their
+    // pointers.  clip_log: the caller's ring of norms (rcn_hipx_set_grad_norm_log), a kernel argument.  norm_part: the scratch of
+    // rcn_hipx_grad_norm_dev, its own (it may grow; no graph of the net points into it).
+    float clip_max = 0.f;
+    Buf clip_grad, clip_part, clip_state;
+    float* clip_log = nullptr; long long clip_log_cap = 0;
+    Buf norm_part;
     // The captured steps, one cache per family (family_of): the caller's pointers plain or on pair labels (rcn_hipx_train_step_dev /
     // _pair_dev), and the epoch's steps on the net's own buffers x (rate from the host | from the device) x (mixed or not).  A family
     // that holds eight graphs and needs a ninth drops its own; drop_graphs drops them all.
@@ -513,6 +523,40 @@ bool sgd_default(const rcn_hipx_net* n) { return n->sgd_mu == 0.f && n->sgd_wd =
 SgdParams sgd_params(const rcn_hipx_net* n) { return SgdParams{(float*)n->vel.p, (const float*)n->params.p, n->sgd_mu, n->sgd_wd, n->sgd_nesterov}; }
 bool ema_on(const rcn_hipx_net* n) { return n->ema_decay != 0.f; }
 EmaParams ema_params(const rcn_hipx_net* n) { return EmaParams{(float*)n->ema.p, (const float*)n->params.p, 1.0f - n->ema_decay}; }
+bool clip_on(const rcn_hipx_net* n) { return n->clip_max != 0.f; }
+// the clipped launch's view of the net's clip state; the partials are those of the buffer k_grad_sumsq has just summed
+ClipParams clip_params(const rcn_hipx_net* n) {
+    unsigned long long* const count = (unsigned long long*)n->clip_state.p;
+    return ClipParams{(const double*)n->clip_part.p, (int)clip_blocks(n->n_pad), n->clip_max, (float*)(count + 1), n->clip_log, n->clip_log_cap, count};
+}
+// partial[b] of every 4096-element block of g[0, len) (len % 4 == 0, g 16-byte aligned), on the net's stream
+void launch_sumsq(rcn_hipx_net* n, const float* g, long long len, float scale, double* partial) {
+    if (len > 0) hipLaunchKernelGGL(k_grad_sumsq, dim3((unsigned)clip_blocks(len)), dim3(kClipThreads), 0, n->stream, g, len, scale, partial);
+}
+
+// The clipped step's reduction is three launches in place of one (convnet_clip.hpp): the queued jobs first run as the gradients-only
+// reduction into the net's gradient buffer; k_grad_sumsq sums its squares; then the same jobs, each reading its slice of that buffer as a
+// one-chunk slab, run as the clipped update -- so the flipped weight copy, the velocity and the average are kept as the unclipped launch
+// keeps them.  This turns n->jobs into the first launch's table and fills *U with the update launch's; returns the latter's workgroups.
+int clipped_tables(rcn_hipx_net* n, float lr, ReduceJobs* U) {
+    ReduceJobs& J = n->jobs;
+    *U = J;
+    U->lr = lr; U->apply = 1;
+    J.lr = 0.f; J.apply = 0;
+    int next = 0;
+    for (int q = 0; q < J.njobs; ++q) {
+        ReduceJob& u = U->j[q];
+        const long long off = u.p - (float*)n->params.p;
+        u.grad = nullptr;
+        u.slab = (const float*)n->clip_grad.p + off;
+        u.chunks = 1;
+        u.first_block = next;
+        next += (int)((u.n + reduce_job_elems(1) - 1) / reduce_job_elems(1));
+        J.j[q].grad = (float*)n->clip_grad.p + off;
+        J.j[q].flip.wt = nullptr;
+    }
+    return next;
+}
 
 // lr_dev (nullable): the update reads its rate from this device scalar instead of `lr` (the _dlr kernels; same arithmetic on the same float)
 int run_reduce_jobs(rcn_hipx_net* n, float lr, bool apply, const float* lr_dev = nullptr) {
@@ -520,18 +564,35 @@ int run_reduce_jobs(rcn_hipx_net* n, float lr, bool apply, const float* lr_dev =
     const ReduceJob& last = n->jobs.j[n->jobs.njobs - 1];
     const long long blocks = last.first_block + (last.n + reduce_job_elems(last.chunks) - 1) / reduce_job_elems(last.chunks);
     n->jobs.lr = lr; n->jobs.apply = apply ? 1 : 0;
-    // the update kernel of this launch, chosen here and nowhere else: (the net's optimiser?, the average on?, the rate from the device?)
-    const bool sgd = apply && !sgd_default(n), ema = apply && ema_on(n), dlr = apply && lr_dev;
-    char what[192] = "";
+    // the update kernel of this launch, chosen here and nowhere else: (clipping on?, the net's optimiser?, the average on?, the rate from the device?)
+    const bool sgd = apply && !sgd_default(n), ema = apply && ema_on(n), dlr = apply && lr_dev, clip = apply && clip_on(n);
+    char what[256] = "";
     if (sgd) std::snprintf(what, sizeof what, " (SGD: momentum %g, weight decay %g, nesterov %s)", (double)n->sgd_mu, (double)n->sgd_wd, n->sgd_nesterov ? "on" : "off");
     if (ema) std::snprintf(what + std::strlen(what), sizeof what - std::strlen(what), " (EMA: decay %g)", (double)n->ema_decay);
+    if (clip) std::snprintf(what + std::strlen(what), sizeof what - std::strlen(what), " (clip: max norm %g)", (double)n->clip_max);
+    ReduceJobs U;                                       // clipping: the update launch's table, n->jobs being the gradients-only launch's
+    const int ublocks = clip ? clipped_tables(n, lr, &U) : 0;
+    if (clip && n->dry) {
+        (void)dry_note(n, "  gradient: k_reduce_all, %d layers' slabs in one launch, %lld workgroups, into the net's gradient buffer (no update)", n->jobs.njobs, blocks);
+        (void)dry_note(n, "  norm: k_grad_sumsq, %lld elements, %lld workgroups (partial sums of squares in double, fixed order)", n->n_pad, clip_blocks(n->n_pad));
+        (void)dry_note(n, "  update: k_reduce_all_clip%s%s%s, %d layers' gradients as one-chunk slabs, %d workgroups%s", sgd ? "_sgd" : "", ema ? "_ema" : "", dlr ? "_dlr" : "", U.njobs, ublocks, what);
+        n->jobs.njobs = 0;
+        return 0;
+    }
     if (dry_note(n, "  update: k_reduce_all%s%s%s, %d layers' slabs in one launch, %lld workgroups%s", sgd ? "_sgd" : "", ema ? "_ema" : "", dlr ? "_dlr" : "", n->jobs.njobs, blocks, what)) {
         n->jobs.njobs = 0;
         return 0;
     }
-    const dim3 grid((unsigned)blocks), block(kReduceThreads);
+    const dim3 grid((unsigned)(clip ? ublocks : blocks)), block(kReduceThreads);
+    if (clip) {
+        hipLaunchKernelGGL(k_reduce_all, dim3((unsigned)blocks), block, 0, n->stream, n->jobs);
+        XTRY(n, hipGetLastError());
+        launch_sumsq(n, (const float*)n->clip_grad.p, n->n_pad, 1.0f, (double*)n->clip_part.p);
+        XTRY(n, hipGetLastError());
+    }
+    const ClipParams Cp = clip ? clip_params(n) : ClipParams{};
     // gradients-only walks (apply == false) take k_reduce_all
-    switch ((sgd ? 4 : 0) | (ema ? 2 : 0) | (dlr ? 1 : 0)) {
+    switch ((clip ? 8 : 0) | (sgd ? 4 : 0) | (ema ? 2 : 0) | (dlr ? 1 : 0)) {
         case 0: hipLaunchKernelGGL(k_reduce_all, grid, block, 0, n->stream, n->jobs); break;
         case 1: hipLaunchKernelGGL(k_reduce_all_dlr, grid, block, 0, n->stream, n->jobs, lr_dev); break;
         case 2: hipLaunchKernelGGL(k_reduce_all_ema, grid, block, 0, n->stream, n->jobs, ema_params(n)); break;
@@ -539,7 +600,15 @@ int run_reduce_jobs(rcn_hipx_net* n, float lr, bool apply, const float* lr_dev =
         case 4: hipLaunchKernelGGL(k_reduce_all_sgd, grid, block, 0, n->stream, n->jobs, sgd_params(n)); break;
         case 5: hipLaunchKernelGGL(k_reduce_all_sgd_dlr, grid, block, 0, n->stream, n->jobs, sgd_params(n), lr_dev); break;
         case 6: hipLaunchKernelGGL(k_reduce_all_sgd_ema, grid, block, 0, n->stream, n->jobs, sgd_params(n), ema_params(n)); break;
-        default: hipLaunchKernelGGL(k_reduce_all_sgd_ema_dlr, grid, block, 0, n->stream, n->jobs, sgd_params(n), ema_params(n), lr_dev); break;
+        case 7: hipLaunchKernelGGL(k_reduce_all_sgd_ema_dlr, grid, block, 0, n->stream, n->jobs, sgd_params(n), ema_params(n), lr_dev); break;
+        case 8: hipLaunchKernelGGL(k_reduce_all_clip, grid, block, 0, n->stream, U, Cp); break;
+        case 9: hipLaunchKernelGGL(k_reduce_all_clip_dlr, grid, block, 0, n->stream, U, Cp, lr_dev); break;
+        case 10: hipLaunchKernelGGL(k_reduce_all_clip_ema, grid, block, 0, n->stream, U, ema_params(n), Cp); break;
+        case 11: hipLaunchKernelGGL(k_reduce_all_clip_ema_dlr, grid, block, 0, n->stream, U, ema_params(n), Cp, lr_dev); break;
+        case 12: hipLaunchKernelGGL(k_reduce_all_clip_sgd, grid, block, 0, n->stream, U, sgd_params(n), Cp); break;
+        case 13: hipLaunchKernelGGL(k_reduce_all_clip_sgd_dlr, grid, block, 0, n->stream, U, sgd_params(n), Cp, lr_dev); break;
+        case 14: hipLaunchKernelGGL(k_reduce_all_clip_sgd_ema, grid, block, 0, n->stream, U, sgd_params(n), ema_params(n), Cp); break;
+        default: hipLaunchKernelGGL(k_reduce_all_clip_sgd_ema_dlr, grid, block, 0, n->stream, U, sgd_params(n), ema_params(n), Cp, lr_dev); break;
     }
     XTRY(n, hipGetLastError());
     n->jobs.njobs = 0;
@@ -880,13 +949,14 @@ int make_dry_net(rcn_hipx_net& net, int in_h, int in_w, int in_c, const rcn_hipx
     seed_options(net.opt);
     return describe_layers(&net, in_h, in_w, in_c, layers, n_layers);
 }
-// ... or from an existing net: its layers, precision, tiling, options, optimiser, loss and average -- the plan and the step agree by construction
+// ... or from an existing net: its layers, precision, tiling, options, optimiser, loss, average and clipping -- the plan and the step agree by construction
 void make_dry_net(rcn_hipx_net& net, const rcn_hipx_net& from, int batch) {
     net.in_h = from.in_h; net.in_w = from.in_w; net.in_c = from.in_c; net.max_batch = batch; net.classes = from.classes; net.dry = true;
     static_cast<Selection&>(net) = from;
     net.sgd_mu = from.sgd_mu; net.sgd_wd = from.sgd_wd; net.sgd_nesterov = from.sgd_nesterov;
     net.loss_eps = from.loss_eps;
     net.ema_decay = from.ema_decay;
+    net.clip_max = from.clip_max;
     copy_layer_table(net, from);
 }
 
@@ -1564,7 +1634,16 @@ int rcn_hipx_reset_ema(rcn_hipx_net* n) {
 int rcn_hipx_apply_sgd_dev(rcn_hipx_net* n, const float* grad, float grad_scale, float lr) {
     if (!n || !grad) return -1;
     Dev g(n->device);
-    if (sgd_default(n)) RTRY(launch_axpy(n, grad, grad_scale * lr));      // plain SGD: rcn_hipx_apply_dev(grad, grad_scale * lr)'s launch
+    if (clip_on(n)) {
+        // clipping on, whatever the optimiser: the norm of fl(grad_scale * g), then k_sgd_apply with the coefficient in front of the update
+        if ((uintptr_t)grad % 16 != 0) return fail(n, -1, "apply_sgd: the gradient buffer must be 16-byte aligned");
+        launch_sumsq(n, grad, n->n_pad, grad_scale, (double*)n->clip_part.p);
+        XTRY(n, hipGetLastError());
+        const dim3 grid(grid1d(n->n_pad / 4, kClipThreads)), block(kClipThreads);
+        if (sgd_default(n)) hipLaunchKernelGGL(k_sgd_apply_clip<true>, grid, block, 0, n->stream, (float*)n->params.p, grad, grad_scale, lr, sgd_params(n), n->n_pad, clip_params(n));
+        else hipLaunchKernelGGL(k_sgd_apply_clip<false>, grid, block, 0, n->stream, (float*)n->params.p, grad, grad_scale, lr, sgd_params(n), n->n_pad, clip_params(n));
+        XTRY(n, hipGetLastError());
+    } else if (sgd_default(n)) RTRY(launch_axpy(n, grad, grad_scale * lr));      // plain SGD: rcn_hipx_apply_dev(grad, grad_scale * lr)'s launch
     else {
         if ((uintptr_t)grad % 16 != 0) return fail(n, -1, "apply_sgd: the gradient buffer must be 16-byte aligned");
         hipLaunchKernelGGL(k_sgd_apply, dim3(grid1d(n->n_pad / 4, 256)), dim3(256), 0, n->stream, (float*)n->params.p, grad, grad_scale, lr, sgd_params(n), n->n_pad);
@@ -1572,6 +1651,85 @@ int rcn_hipx_apply_sgd_dev(rcn_hipx_net* n, const float* grad, float grad_scale,
     }
     RTRY(apply_ema(n));
     return refresh_flipped(n);
+}
+
+int rcn_hipx_set_clip(rcn_hipx_net* n, float max_norm) {
+    if (!n) return -1;
+    if (!(max_norm >= 0.f)) return fail(n, -1, "set_clip: max_norm must be 0 (off) or > 0 (+inf: measure only)");
+    if (max_norm == 0.f) max_norm = 0.f;                // (-0)
+    if (max_norm == n->clip_max) return 0;
+    Dev g(n->device);
+    XTRY(n, hipStreamSynchronize(n->stream));
+    if (max_norm != 0.f && !n->clip_state.p) {
+        // once, outside any capture: captured graphs hold these pointers, so the buffers never move afterwards
+        XTRY(n, n->clip_grad.ensure((size_t)n->n_pad * sizeof(float)));
+        XTRY(n, n->clip_part.ensure((size_t)clip_blocks(n->n_pad) * sizeof(double)));
+        XTRY(n, n->clip_state.ensure(sizeof(unsigned long long) + 2 * sizeof(float)));
+        XTRY(n, hipMemsetAsync(n->clip_grad.p, 0, n->clip_grad.cap, n->stream));
+        XTRY(n, hipMemsetAsync(n->clip_part.p, 0, n->clip_part.cap, n->stream));
+        XTRY(n, hipMemsetAsync(n->clip_state.p, 0, n->clip_state.cap, n->stream));
+        XTRY(n, hipStreamSynchronize(n->stream));
+    }
+    drop_graphs(n);                                     // captured graphs bake in the update's launches and their arguments
+    n->clip_max = max_norm;
+    return 0;
+}
+
+int rcn_hipx_get_clip(const rcn_hipx_net* n, float* max_norm) {
+    if (!n) return -1;
+    if (max_norm) *max_norm = n->clip_max;
+    return 0;
+}
+
+int rcn_hipx_get_grad_norm(rcn_hipx_net* n, float* norm, float* coef) {
+    if (!n) return -1;
+    if (!n->clip_state.p) return fail(n, -6, "get_grad_norm: clipping was never switched on (rcn_hipx_set_clip with a max_norm > 0 first)");
+    Dev g(n->device);
+    float pair[2] = {0.f, 0.f};
+    XTRY(n, hipMemcpyAsync(pair, (const char*)n->clip_state.p + sizeof(unsigned long long), sizeof pair, hipMemcpyDeviceToHost, n->stream));
+    XTRY(n, hipStreamSynchronize(n->stream));
+    if (norm) *norm = pair[0];
+    if (coef) *coef = pair[1];
+    return 0;
+}
+
+int rcn_hipx_set_grad_norm_log(rcn_hipx_net* n, float* log_dev, int64_t cap) {
+    if (!n) return -1;
+    if (log_dev && cap < 1) return fail(n, -1, "set_grad_norm_log: a log needs cap >= 1");
+    Dev g(n->device);
+    XTRY(n, hipStreamSynchronize(n->stream));
+    if (n->clip_state.p) {                              // (none yet: the counter starts at zero when rcn_hipx_set_clip makes it)
+        XTRY(n, hipMemsetAsync(n->clip_state.p, 0, sizeof(unsigned long long), n->stream));
+        XTRY(n, hipStreamSynchronize(n->stream));
+    }
+    drop_graphs(n);                                     // the pointer is a kernel argument
+    n->clip_log = log_dev; n->clip_log_cap = log_dev ? (long long)cap : 0;
+    return 0;
+}
+
+int rcn_hipx_get_grad_norm_count(rcn_hipx_net* n, int64_t* count) {
+    if (!n || !count) return -1;
+    Dev g(n->device);
+    unsigned long long c = 0;
+    if (n->clip_state.p) XTRY(n, hipMemcpyAsync(&c, n->clip_state.p, sizeof c, hipMemcpyDeviceToHost, n->stream));
+    XTRY(n, hipStreamSynchronize(n->stream));
+    *count = (int64_t)c;
+    return 0;
+}
+
+int rcn_hipx_grad_norm_dev(rcn_hipx_net* n, const float* g_dev, int64_t len, float scale, float* norm_dev) {
+    if (!n) return -1;
+    if (!norm_dev || len < 0 || len % 4 != 0 || (len > 0 && (!g_dev || (uintptr_t)g_dev % 16 != 0)))
+        return fail(n, -1, "grad_norm: n >= 0, n % 4 == 0, a 16-byte aligned buffer and a device float for the norm");
+    Dev g(n->device);
+    const long long nblk = clip_blocks((long long)len);
+    if (nblk > 0x7fffffffLL) return fail(n, -1, "grad_norm: more than 2^43 elements");
+    XTRY(n, n->norm_part.ensure((size_t)(nblk > 0 ? nblk : 1) * sizeof(double)));
+    launch_sumsq(n, g_dev, (long long)len, scale, (double*)n->norm_part.p);
+    XTRY(n, hipGetLastError());
+    hipLaunchKernelGGL(k_grad_norm_finish, dim3(1), dim3(kClipThreads), 0, n->stream, (const double*)n->norm_part.p, (int)nblk, norm_dev);
+    XTRY(n, hipGetLastError());
+    return 0;
 }
 
 int rcn_hipx_step_flops(const rcn_hipx_net* n, int B, double* flops) {
