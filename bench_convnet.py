@@ -34,12 +34,23 @@ def resident_set_figures(net, args, in_shape, B, lr):
     gather through a random crop and flip -- timed the same way, beside the plain figure.
     --label-smoothing / --mix: those recipe epochs a third time with the smoothed loss and / or mixup / CutMix records (mix_plan, made and
     moved to the device before the clock starts), beside the recipe figure: mix_epoch_ms_per_step.
-    --ema: the evaluation once more on the average of the parameters (two exchange launches per call), beside the live figures."""
+    --ema: the evaluation once more on the average of the parameters (two exchange launches per call), beside the live figures.
+    --accumulate K: B is the micro-batch and an epoch is a whole number of cycles (N // B rounded down to a multiple of K); the recipe's
+    schedule has one rate per UPDATE, repeated for the K micro-steps of its cycle."""
     import torch
     N = args.dataset
-    nb = N // B
+    K = args.accumulate
+    nb = N // B // K * K
     if nb < 1:
-        sys.exit(f"--dataset {N}: smaller than one batch of {B}")
+        sys.exit(f"--dataset {N}: smaller than one batch of {B}" + (f" times --accumulate {K}" if K > 1 else ""))
+
+    def schedule():
+        """the recipe's rate per micro-step: warm-up + cosine over the epoch's updates, as a device tensor (or the constant rate)"""
+        from mercer_research_amd.convnet import warmup_cosine
+        if args.lr_schedule != "warmup_cosine":
+            return lr
+        updates = nb // K
+        return torch.from_numpy(np.repeat(warmup_cosine(updates, lr, max(1, updates // 20)), K)).to(net.device)
     gen = torch.Generator(device=net.device).manual_seed(1)
     with torch.cuda.stream(net.stream):
         if args.config == "synth224":
@@ -51,7 +62,7 @@ def resident_set_figures(net, args, in_shape, B, lr):
 
         def epoch():
             perm = torch.randperm(N, generator=gen, device=net.device).int()
-            net.train_epoch(X, Y, perm, B, lr, losses=losses)
+            net.train_epoch(X, Y, perm, B, lr, n_batches=nb, losses=losses)
 
         epoch()                                            # the first step of the first epoch instantiates the (B, lr) graph
         net.synchronize()
@@ -63,13 +74,13 @@ def resident_set_figures(net, args, in_shape, B, lr):
         el = time.perf_counter() - t0
         recipe = {}
         if args.lr_schedule != "none" or args.augment >= 0:
-            from mercer_research_amd.convnet import Augment, warmup_cosine
-            sched = torch.from_numpy(warmup_cosine(nb, lr, max(1, nb // 20))).to(net.device) if args.lr_schedule == "warmup_cosine" else lr
+            from mercer_research_amd.convnet import Augment
+            sched = schedule()
             seen = [0]
 
             def recipe_epoch():
                 perm = torch.randperm(N, generator=gen, device=net.device).int()
-                net.train_epoch(X, Y, perm, B, sched, losses=losses, augment=Augment(args.augment, True, 1, seen[0]) if args.augment >= 0 else None)
+                net.train_epoch(X, Y, perm, B, sched, n_batches=nb, losses=losses, augment=Augment(args.augment, True, 1, seen[0]) if args.augment >= 0 else None)
                 seen[0] += 1
 
             recipe_epoch()                                 # a scheduled rate has its own graph: instantiated here, once
@@ -82,8 +93,8 @@ def resident_set_figures(net, args, in_shape, B, lr):
             recipe = {"recipe": {"lr_schedule": args.lr_schedule, "augment_pad": args.augment if args.augment >= 0 else None, "hflip": args.augment >= 0},
                       "recipe_epoch_ms_per_step": round(rel / (epochs * nb) * 1e3, 4)}
         if args.label_smoothing > 0 or args.mix != "none":
-            from mercer_research_amd.convnet import Augment, mix_plan, warmup_cosine
-            sched = torch.from_numpy(warmup_cosine(nb, lr, max(1, nb // 20))).to(net.device) if args.lr_schedule == "warmup_cosine" else lr
+            from mercer_research_amd.convnet import Augment, mix_plan
+            sched = schedule()
             alphas = {"mixup": (0.8, 0.0), "cutmix": (0.0, 1.0), "both": (0.8, 1.0)}.get(args.mix)
             plans = [net.mix_to_device(mix_plan(nb, in_shape[0], in_shape[1], alphas[0], alphas[1], seed=e)) for e in range(epochs + 1)] if alphas else None
             net.set_loss(args.label_smoothing)
@@ -91,7 +102,7 @@ def resident_set_figures(net, args, in_shape, B, lr):
 
             def mix_epoch():
                 perm = torch.randperm(N, generator=gen, device=net.device).int()
-                net.train_epoch(X, Y, perm, B, sched, losses=losses, augment=Augment(args.augment, True, 2, done[0]) if args.augment >= 0 else None,
+                net.train_epoch(X, Y, perm, B, sched, n_batches=nb, losses=losses, augment=Augment(args.augment, True, 2, done[0]) if args.augment >= 0 else None,
                                 mix=plans[done[0]] if plans else None)
                 done[0] += 1
 
@@ -164,6 +175,10 @@ def main():
     ap.add_argument("--clip", type=float, default=0.0, metavar="M",
                     help="clip the gradient to a global L2 norm of at most M in front of the update (rcn_hipx_set_clip; 0: off; inf: measure the norm only), set before "
                          "the timed steps: three launches in the step's graph instead of one; the line gains clip_max_norm and grad_norm_last")
+    ap.add_argument("--accumulate", type=int, default=1, metavar="K",
+                    help="gradient accumulation: every K steps form one update on the mean of their gradients (rcn_hipx_set_accumulate; 1: off), set before the "
+                         "warm-up; --warmup and --steps are rounded up to multiples of K; ms_per_step and images/s stay per micro-step, the line gains accumulate "
+                         "and ms_per_update (single GPU: the data-parallel step does not accumulate)")
     ap.add_argument("--dataset", type=int, default=0, metavar="N",
                     help="also keep a synthetic set of N images resident (uint8 for mnist / cifar, fp32 for synth224), time train_epoch over whole epochs with a fresh "
                          "device permutation each, then evaluate over the set: the line gains epoch_ms_per_step, epoch_images_per_s, eval_images_per_s, graphs_instantiated "
@@ -187,6 +202,8 @@ def main():
         ap.error("--ema: 0 <= D < 1")
     if not args.clip >= 0.0:
         ap.error("--clip: M >= 0 (inf allowed)")
+    if not 1 <= args.accumulate <= 65536:
+        ap.error("--accumulate: 1 <= K <= 65536")
     if not 0.0 <= args.label_smoothing < 1.0:
         ap.error("--label-smoothing: 0 <= E < 1")
     if (args.lr_schedule != "none" or args.augment >= 0 or args.trap) and not args.dataset:
@@ -205,6 +222,10 @@ def main():
     dp = world > 1 or args.force_dp
     if dp and args.dataset:
         sys.exit("--dataset times the single-GPU epoch; a data-parallel epoch does not exist")
+    if dp and args.accumulate > 1:
+        sys.exit("--accumulate: the data-parallel step (gradients -> all-reduce -> apply) does not accumulate; accumulation across ranks does not exist")
+    K = args.accumulate
+    args.steps = -(-args.steps // K) * K                   # whole cycles: the timed steps end on an update
     if dp:
         sys.stdout.flush()
         real_stdout = os.dup(1)                # RCCL's version banner goes to stdout: keep rank 0's stdout to the one JSON line
@@ -228,6 +249,8 @@ def main():
         net.set_ema(args.ema)
     if args.clip > 0:
         net.set_clip(args.clip)
+    if K > 1:
+        net.set_accumulate(K)
     rng = np.random.default_rng(rank)
     nbuf = 8 if args.config != "synth224" else 2           # rotate over several resident batches
     xs = [net.to_device(rng.standard_normal((B,) + in_shape).astype(np.float32)) for _ in range(nbuf)]
@@ -299,10 +322,15 @@ def main():
                 dp_graphs.clear()
             dp_mode = "hipGraph" if dp_graphs else "eager"
     else:
+        def buffer_of(i):
+            """The batch of step i.  A captured step is keyed by its tensors and its kind of micro-step, eight keys at the most: where K does
+            not divide the number of buffers, each position in the cycle has one fixed buffer (the late positions share one)."""
+            return i % nbuf if nbuf % K == 0 else min(i % K, max(nbuf - 2, 0))
+
         def step(i):
-            net.train_step(xs[i % nbuf], ys[i % nbuf], lr, loss)
+            net.train_step(xs[buffer_of(i)], ys[buffer_of(i)], lr, loss)
     net.synchronize()
-    for i in range(max(args.warmup, 2 * nbuf)):            # first use of each (x, y) pair instantiates its graph
+    for i in range(-(-max(args.warmup, 2 * nbuf) // K) * K):      # first use of each (x, y) pair instantiates its graph; whole cycles
         step(i)
     net.synchronize()
     if dp:
@@ -339,6 +367,7 @@ def main():
                           "hbm_floor_ms": round(floor_ms, 4) if floor_ms else None, "frac_of_hbm_floor": round(floor_ms / (el / args.steps * 1e3), 4) if floor_ms else None,
                           "dtype": "f32" if not bf16 else "bf16 MFMA operands (fwd, dgrad, wgrad), f32 accumulate/update" + (", conv-stage activations and gradients stored as bf16" if args.precision == "bf16_stored" else ""), "data": "synthetic", "final_loss": round(loss.item(), 4),
                           "ema_decay": args.ema,
+                          "accumulate": K, "ms_per_update": round(el / args.steps * 1e3 * K, 4),
                           "clip_max_norm": args.clip, "grad_norm_last": round(net.grad_norm()[0], 6) if args.clip > 0 else None,
                           "data_parallel_step": dp_mode,
                           "data_parallel_allreduce": (None if not dp else "one all-reduce of the flat gradient after the backward pass" if args.dp_buckets <= 0 else

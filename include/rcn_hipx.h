@@ -366,6 +366,41 @@ int  rcn_hipx_get_grad_norm_count(rcn_hipx_net* net, int64_t* count);
  * 16-byte aligned buffer (n == 0: the norm is 0, g_dev may be NULL), else -1.  It uses a scratch of its own, which may grow between
  * calls, never the step's partials; it neither reads nor changes the net's clip state and works with clipping off. */
 int  rcn_hipx_grad_norm_dev(rcn_hipx_net* net, const float* g_dev, int64_t n, float scale, float* norm_dev);
+/* Gradient accumulation over micro-batches: what torch users write as (loss / k).backward() k times, then clip_grad_norm_, opt.step() and
+ * zero_grad().  Every k consecutive training micro-steps -- a micro-step is one call of the step on one batch of B rows -- form ONE update.
+ * With c = fl(1.0f / k) computed once on the host and g_j the summed gradient of micro-batch j (the padded gradient of that batch's mean
+ * loss: the value rcn_hipx_gradients_dev returns for it, bit for bit); fp32, every operation rounded once (no fused multiply-add):
+ *     acc = fl(c * g_0)                   the first micro-step of a cycle: a store, so nothing needs zeroing
+ *     acc = fl(acc + fl(c * g_j))         micro-steps j = 1 .. k - 1, in order
+ * After micro-step k - 1 acc IS the step's gradient and the existing machinery runs unchanged: with clipping on k_grad_sumsq(acc, scale 1)
+ * and the net's k_reduce_all_clip[_sgd][_ema][_dlr], else the net's k_reduce_all[_sgd][_ema][_dlr], every layer's slice of acc read as a
+ * one-chunk slab.  tests/_accum_ref.py restates acc in NumPy, bit for bit.  Micro-steps 0 .. k - 2 change nothing but acc: the parameters
+ * and their tap-flipped copy, the velocity, the average, the clip state, the norm log and its counter stay as they were until the update.
+ * The loss written for a micro-step is that micro-batch's own mean loss, unscaled.  The rate of an update is the rate of the micro-step
+ * that applies it (that call's lr, or lr_dev[i] of that micro-step in the epoch entries); rates passed to the other micro-steps are
+ * ignored and are not part of their graphs' keys.  A micro-step's reduction is one launch, k_reduce_all_acc<first> or <next>; the last one
+ * of a cycle is followed by the norm (clipping on) and the update launch: one captured graph per kind of micro-step (first, middle -- only
+ * for k >= 3 --, last) and B serves every rate from the device, the last kind per (B, lr) with a host rate.
+ * rcn_hipx_set_accumulate: net state, like rcn_hipx_set_clip.  Accepts 1 <= k <= 65536; anything else returns -1 and changes nothing.
+ * k = 1 is the default: the same kernels, launches, arguments, graph keys, plan text and bits as a net never configured.  The first k > 1
+ * allocates acc (the padded parameter count, in floats), once; it never moves.  A changed k synchronises the net's stream, drops its
+ * captured graphs and discards a pending cycle; setting the k the net already has is a no-op.  Applies in rcn_hipx_train_step_dev,
+ * rcn_hipx_train_step_pair_dev and the three epoch entries, where B stays the micro-batch and n_batches, loss_dev, lr_dev, mix_dev and the
+ * augmentation position all stay per micro-batch.  Never applies in the gradient / bucket entries, rcn_hipx_apply_dev,
+ * rcn_hipx_apply_sgd_dev or evaluation.  The position in the cycle is host state of the net: it advances only when a micro-step was
+ * enqueued (also where the call then fails to capture that step for replay: the accumulator and the position always agree), persists
+ * across calls (an epoch split into calls at any micro-batch gives the bits of the unsplit epoch; a cycle left open at
+ * the end of a call stays pending), and, like acc, survives rcn_hipx_set_params, rcn_hipx_init_params, changes of optimiser, average,
+ * clipping, loss, precision, tiling and options, and evaluation between micro-steps.
+ * _get_accumulate: k and the number of micro-steps already accumulated in the open cycle, 0 .. k - 1 (either pointer may be NULL).
+ * _reset_accumulation: drops a pending cycle, as zero_grad would -- host state only, the next micro-step being a first one, which stores; a
+ * no-op when nothing is pending.
+ * _get_accumulated: acc in the logical layout of rcn_hipx_get_params, after a synchronise of the net's stream; -6 while accumulation was
+ * never switched on. */
+int  rcn_hipx_set_accumulate(rcn_hipx_net* net, int k);
+int  rcn_hipx_get_accumulate(const rcn_hipx_net* net, int* k, int* pending);
+int  rcn_hipx_reset_accumulation(rcn_hipx_net* net);
+int  rcn_hipx_get_accumulated(rcn_hipx_net* net, float* flat);
 /* The same gradients in BUCKETS, so that a data-parallel step can all-reduce one bucket of layers while the backward pass of the layers
  * below it still runs (6.7 MB of gradient for BASELINE configs[3]).  The layers with parameters, in the order the
  * backward pass finishes them (last to first), are cut into buckets of at least min_bucket_bytes of gradient; the padded flat layout
@@ -395,8 +430,14 @@ int  rcn_hipx_plan(int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, i
  * soft loss kernel and eps on the loss (or head) line; one with rcn_hipx_set_ema decay > 0 names the _ema update kernel and
  * "(EMA: decay %g)" on the update line; one with rcn_hipx_set_clip max_norm > 0 names the three launches of the clipped reduction
  * (k_reduce_all into the gradient buffer, k_grad_sumsq, k_reduce_all_clip...) and "(clip: max norm %g)" on the update line
- * (rcn_hipx_plan_epoch_net / _mix_net likewise). */
+ * (rcn_hipx_plan_epoch_net / _mix_net likewise).  On a net with rcn_hipx_set_accumulate k > 1 the three describe the LAST micro-step of a
+ * cycle: the k_reduce_all_acc<next> reduction, the norm where clipping is on, and the update over the accumulator as one-chunk slabs, its
+ * line gaining "(accumulate: k micro-batches, scale %g)"; the epoch plans' graph line names the graph per kind of micro-step. */
 int  rcn_hipx_plan_net(const rcn_hipx_net* net, int batch, char* out, int cap);
+/* The launches of one kind of micro-step of an accumulating net: kind 0 the first of a cycle, 1 a middle one, 2 the last.  The reduction
+ * line names k_reduce_all_acc<first> or <next> and says "(accumulate: micro-batch of k, no update)"; the last kind is followed by the norm
+ * and update lines of rcn_hipx_plan_net.  -1: net NULL, a net with k = 1, an unknown kind, batch outside 1 .. max_batch. */
+int  rcn_hipx_plan_micro_net(const rcn_hipx_net* net, int batch, int kind, char* out, int cap);
 /* algorithmic FLOPs of one training step at batch B (2 * MACs; forward + dgrad + wgrad) */
 int  rcn_hipx_step_flops(const rcn_hipx_net* net, int B, double* flops);
 

@@ -142,6 +142,11 @@ SIGNATURES = {
     "rcn_hipx_set_grad_norm_log": (_i, [_vp, _vp, C.c_int64]),
     "rcn_hipx_get_grad_norm_count": (_i, [_vp, C.POINTER(C.c_int64)]),
     "rcn_hipx_grad_norm_dev": (_i, [_vp, _vp, C.c_int64, C.c_float, _vp]),
+    "rcn_hipx_set_accumulate": (_i, [_vp, _i]),
+    "rcn_hipx_get_accumulate": (_i, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rcn_hipx_reset_accumulation": (_i, [_vp]),
+    "rcn_hipx_get_accumulated": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rcn_hipx_plan_micro_net": (_i, [_vp, _i, _i, C.c_char_p, _i]),
 }
 _libx = None
 
@@ -170,6 +175,7 @@ DEFAULT_BUCKET_BYTES = 1 << 20      # gradient buckets of the data-parallel step
 PRECISIONS = {"fp32": 0, "bf16": 1, "bf16_stored": 2}
 TILINGS = {"gemm": 0, "auto": 1, "lds": 2}      # RCN_HIPX_TILING_*
 WEIGHTS = {"live": 0, "ema": 1}     # RCN_HIPX_WEIGHTS_*: which parameters an evaluation scores
+MICRO_KINDS = {"first": 0, "middle": 1, "last": 2}      # rcn_hipx_plan_micro_net's kinds of micro-step
 
 
 def _layer_array(layers: Sequence[tuple]):
@@ -398,7 +404,10 @@ class ConvNet:
         augment: an Augment -- every batch is gathered through its random crop and flip, drawn from (seed, epoch, s*B + r).
         mix: a contiguous device tensor holding at least n_batches records of MIX_DTYPE (mix_plan's array through mix_to_device) -- the
         call's i-th step is mixed by record i (rcn_hipx_train_epoch_mix_dev: mixup / CutMix with the mirrored row of the same batch, ONE
-        more graph whatever the records are)."""
+        more graph whatever the records are).
+        On an accumulating net (set_accumulate(k), k > 1) B is the micro-batch and lr, mix and losses are all per micro-batch: every k-th
+        step applies an update, at ITS entry of lr (the other entries are ignored), so a schedule of U updates is np.repeat(schedule, k).
+        Pick n_batches % k == 0, or the tail stays pending (get_accumulate) and the next call's first steps complete its cycle."""
         t = self.torch
         kind, n = self._resident_set(X, labels)
         if labels is None:
@@ -635,6 +644,33 @@ class ConvNet:
             out = t.empty(1, dtype=t.float32, device=self.device)
         self._ck(self.lib.rcn_hipx_grad_norm_dev(self.net, _ptr(g), int(g.numel()), float(scale), _ptr(out)))
         return out
+
+    def set_accumulate(self, k: int = 1):
+        """Gradient accumulation: every k consecutive training micro-steps (train_step, train_step_pair, the steps of train_epoch) form one
+        update on the mean of their gradients, as (loss / k).backward() k times, then clipping, opt.step() and zero_grad()
+        (include/rcn_hipx.h, rcn_hipx_set_accumulate).  1 is the default: off.  A changed k discards a pending cycle."""
+        self._ck(self.lib.rcn_hipx_set_accumulate(self.net, int(k)))
+
+    def get_accumulate(self) -> Tuple[int, int]:
+        """(k, pending): pending is the number of micro-steps already accumulated in the open cycle, 0 .. k - 1."""
+        k, pending = C.c_int(), C.c_int()
+        self._ck(self.lib.rcn_hipx_get_accumulate(self.net, C.byref(k), C.byref(pending)))
+        return int(k.value), int(pending.value)
+
+    def reset_accumulation(self):
+        """Drops a pending cycle, as zero_grad would: the next micro-step starts a new one (a no-op when nothing is pending)."""
+        self._ck(self.lib.rcn_hipx_reset_accumulation(self.net))
+
+    def get_accumulated(self) -> np.ndarray:
+        """The accumulator in the logical layout of get_params; synchronises.  ConvNetError, status -6, while accumulation was never on."""
+        return self._get_flat(self.lib.rcn_hipx_get_accumulated)
+
+    def plan_micro_of_this_net(self, batch: int, kind: str) -> str:
+        """The launches of one kind of micro-step of THIS accumulating net (rcn_hipx_plan_micro_net): kind "first", "middle" or "last".
+        plan_of_this_net describes the last one."""
+        if kind not in MICRO_KINDS:
+            raise ValueError(f"kind must be one of {sorted(MICRO_KINDS)}, not {kind!r}")
+        return _plan_text("rcn_hipx_plan_micro_net", self.lib.rcn_hipx_plan_micro_net, self.net, int(batch), MICRO_KINDS[kind])
 
     def apply_sgd(self, grad, grad_scale: float, lr: float):
         """The data-parallel half of set_sgd's optimiser: the same update from a padded gradient buffer, scaled by grad_scale first."""

@@ -27,6 +27,7 @@
 #include "convnet_sgd.hpp"
 #include "convnet_ema.hpp"
 #include "convnet_clip.hpp"
+#include "convnet_accum.hpp"
 
 using namespace rcnx;
 
@@ -67,10 +68,15 @@ struct Layer : LayerShape {
     long long wbf_off = -1, wbb_off = -1;   // bf16 mode: this layer's transposed bf16 weight copies in net->wb16 (forward / input-gradient operand)
 };
 
-// everything a captured step bakes in: its arguments are step_core's
+// what a training step does with its gradient: the whole update (a net that does not accumulate), or one micro-step of a cycle of
+// rcn_hipx_set_accumulate -- the first stores into the accumulator, a middle one adds, the last adds and applies the update
+enum Micro { kWholeStep = 0, kMicroFirst = 1, kMicroMiddle = 2, kMicroLast = 3 };
+
+// everything a captured step bakes in: its arguments are step_core's (a first or middle micro-step keys with lr = 0 and no lr_dev: it
+// applies no rate, so one graph per B serves every rate and schedule)
 struct StepKey {
-    const float* x; const int32_t* labels; const int32_t* labels_b; const float* weight; int B; float lr; const float* lr_dev; float* loss;
-    auto tie() const { return std::tie(x, labels, labels_b, weight, B, lr, lr_dev, loss); }
+    const float* x; const int32_t* labels; const int32_t* labels_b; const float* weight; int B; float lr; const float* lr_dev; float* loss; int micro = kWholeStep;
+    auto tie() const { return std::tie(x, labels, labels_b, weight, B, lr, lr_dev, loss, micro); }
     bool operator<(const StepKey& o) const { return tie() < o.tie(); }
 };
 // the second label of every sample and the weight of the first (a device scalar; nullptr: 1) of a step on pair labels; none: labels_b == nullptr
@@ -114,6 +120,13 @@ struct rcn_hipx_net : Selection {
     Buf clip_grad, clip_part, clip_state;
     float* clip_log = nullptr; long long clip_log_cap = 0;
     Buf norm_part;
+    // gradient accumulation (rcn_hipx_set_accumulate; convnet_accum.hpp): every accum_k consecutive training micro-steps form one update;
+    // 1 is off, the launches of a net never configured.  `accum` (n_pad floats, laid out like params) is allocated by the first k > 1,
+    // outside any capture, and never moved afterwards: captured graphs hold its pointer.  accum_c = fl(1.0f / k); accum_pos: micro-steps
+    // already accumulated in the open cycle, 0 .. k - 1 -- host state, advanced when a micro-step has been enqueued.
+    int accum_k = 1, accum_pos = 0;
+    float accum_c = 1.f;
+    Buf accum;
     // The captured steps, one cache per family (family_of): the caller's pointers plain or on pair labels (rcn_hipx_train_step_dev /
     // _pair_dev), and the epoch's steps on the net's own buffers x (rate from the host | from the device) x (mixed or not).  A family
     // that holds eight graphs and needs a ninth drops its own; drop_graphs drops them all.
@@ -534,81 +547,127 @@ void launch_sumsq(rcn_hipx_net* n, const float* g, long long len, float scale, d
     if (len > 0) hipLaunchKernelGGL(k_grad_sumsq, dim3((unsigned)clip_blocks(len)), dim3(kClipThreads), 0, n->stream, g, len, scale, partial);
 }
 
+// The update launch over a gradient that already lies summed in a buffer `g` laid out like the parameters (the clipped step's gradient
+// buffer, the accumulator): the queued jobs, each reading its layer's slice of g as a one-chunk slab.  Fills *U from n->jobs (which it
+// leaves alone); returns U's workgroups.
+int slab_tables(rcn_hipx_net* n, const float* g, float lr, ReduceJobs* U) {
+    *U = n->jobs;
+    U->lr = lr; U->apply = 1;
+    int next = 0;
+    for (int q = 0; q < U->njobs; ++q) {
+        ReduceJob& u = U->j[q];
+        u.grad = nullptr;
+        u.slab = g + (u.p - (float*)n->params.p);
+        u.chunks = 1;
+        u.first_block = next;
+        next += (int)((u.n + reduce_job_elems(1) - 1) / reduce_job_elems(1));
+    }
+    return next;
+}
+
 // The clipped step's reduction is three launches in place of one (convnet_clip.hpp): the queued jobs first run as the gradients-only
 // reduction into the net's gradient buffer; k_grad_sumsq sums its squares; then the same jobs, each reading its slice of that buffer as a
 // one-chunk slab, run as the clipped update -- so the flipped weight copy, the velocity and the average are kept as the unclipped launch
 // keeps them.  This turns n->jobs into the first launch's table and fills *U with the update launch's; returns the latter's workgroups.
 int clipped_tables(rcn_hipx_net* n, float lr, ReduceJobs* U) {
     ReduceJobs& J = n->jobs;
-    *U = J;
-    U->lr = lr; U->apply = 1;
+    const int ublocks = slab_tables(n, (const float*)n->clip_grad.p, lr, U);
     J.lr = 0.f; J.apply = 0;
-    int next = 0;
     for (int q = 0; q < J.njobs; ++q) {
-        ReduceJob& u = U->j[q];
-        const long long off = u.p - (float*)n->params.p;
-        u.grad = nullptr;
-        u.slab = (const float*)n->clip_grad.p + off;
-        u.chunks = 1;
-        u.first_block = next;
-        next += (int)((u.n + reduce_job_elems(1) - 1) / reduce_job_elems(1));
-        J.j[q].grad = (float*)n->clip_grad.p + off;
+        J.j[q].grad = (float*)n->clip_grad.p + (J.j[q].p - (float*)n->params.p);
         J.j[q].flip.wt = nullptr;
     }
-    return next;
+    return ublocks;
+}
+
+// A micro-step of an accumulating net (convnet_accum.hpp): the queued jobs run as k_reduce_all_acc, each job's "parameters" being its
+// layer's slice of the accumulator -- no gradient destination, no flipped copy.  This turns n->jobs into that launch's table.  The last
+// micro-step of a cycle then takes its update launch's table from slab_tables over the accumulator.
+void accum_tables(rcn_hipx_net* n) {
+    ReduceJobs& J = n->jobs;
+    J.lr = 0.f; J.apply = 1;
+    for (int q = 0; q < J.njobs; ++q) {
+        ReduceJob& a = J.j[q];
+        a.p = (float*)n->accum.p + (a.p - (float*)n->params.p);
+        a.grad = nullptr;
+        a.flip.wt = nullptr;
+    }
 }
 
 // lr_dev (nullable): the update reads its rate from this device scalar instead of `lr` (the _dlr kernels; same arithmetic on the same float)
-int run_reduce_jobs(rcn_hipx_net* n, float lr, bool apply, const float* lr_dev = nullptr) {
+// micro: which micro-step of an accumulating net this is (kWholeStep: the net does not accumulate, or a gradients-only walk)
+int run_reduce_jobs(rcn_hipx_net* n, float lr, bool apply, const float* lr_dev = nullptr, int micro = kWholeStep) {
     if (!n->jobs.njobs) return 0;
     const ReduceJob& last = n->jobs.j[n->jobs.njobs - 1];
     const long long blocks = last.first_block + (last.n + reduce_job_elems(last.chunks) - 1) / reduce_job_elems(last.chunks);
     n->jobs.lr = lr; n->jobs.apply = apply ? 1 : 0;
+    const bool acc = apply && micro != kWholeStep, update = apply && (!acc || micro == kMicroLast);
     // the update kernel of this launch, chosen here and nowhere else: (clipping on?, the net's optimiser?, the average on?, the rate from the device?)
-    const bool sgd = apply && !sgd_default(n), ema = apply && ema_on(n), dlr = apply && lr_dev, clip = apply && clip_on(n);
-    char what[256] = "";
+    const bool sgd = update && !sgd_default(n), ema = update && ema_on(n), dlr = update && lr_dev, clip = update && clip_on(n);
+    char what[320] = "";
     if (sgd) std::snprintf(what, sizeof what, " (SGD: momentum %g, weight decay %g, nesterov %s)", (double)n->sgd_mu, (double)n->sgd_wd, n->sgd_nesterov ? "on" : "off");
     if (ema) std::snprintf(what + std::strlen(what), sizeof what - std::strlen(what), " (EMA: decay %g)", (double)n->ema_decay);
     if (clip) std::snprintf(what + std::strlen(what), sizeof what - std::strlen(what), " (clip: max norm %g)", (double)n->clip_max);
-    ReduceJobs U;                                       // clipping: the update launch's table, n->jobs being the gradients-only launch's
-    const int ublocks = clip ? clipped_tables(n, lr, &U) : 0;
-    if (clip && n->dry) {
-        (void)dry_note(n, "  gradient: k_reduce_all, %d layers' slabs in one launch, %lld workgroups, into the net's gradient buffer (no update)", n->jobs.njobs, blocks);
-        (void)dry_note(n, "  norm: k_grad_sumsq, %lld elements, %lld workgroups (partial sums of squares in double, fixed order)", n->n_pad, clip_blocks(n->n_pad));
-        (void)dry_note(n, "  update: k_reduce_all_clip%s%s%s, %d layers' gradients as one-chunk slabs, %d workgroups%s", sgd ? "_sgd" : "", ema ? "_ema" : "", dlr ? "_dlr" : "", U.njobs, ublocks, what);
+    if (acc) std::snprintf(what + std::strlen(what), sizeof what - std::strlen(what), " (accumulate: %d micro-batches, scale %g)", n->accum_k, (double)n->accum_c);
+    // the update launch's table where it is not n->jobs: clipping (n->jobs being the gradients-only launch's), accumulation (the k_reduce_all_acc launch's)
+    ReduceJobs U;
+    int ublocks = 0;
+    const bool buffered = acc || clip;                  // the update reads the step's gradient from a buffer, as one-chunk slabs ...
+    const float* summed = nullptr;                      // ... this one (a dry run has no buffers), and so does the norm
+    if (acc) {
+        summed = (const float*)n->accum.p;
+        if (update) ublocks = slab_tables(n, summed, lr, &U);
+        accum_tables(n);
+    } else if (clip) {
+        summed = (const float*)n->clip_grad.p;
+        ublocks = clipped_tables(n, lr, &U);
+    }
+    if (n->dry) {
+        if (acc) (void)dry_note(n, "  reduction: k_reduce_all_acc<%s>, %d layers' slabs in one launch, %lld workgroups (accumulate: micro-batch of %d, no update)",
+                                micro == kMicroFirst ? "first" : "next", n->jobs.njobs, blocks, n->accum_k);
+        else if (clip) (void)dry_note(n, "  gradient: k_reduce_all, %d layers' slabs in one launch, %lld workgroups, into the net's gradient buffer (no update)", n->jobs.njobs, blocks);
+        if (clip) (void)dry_note(n, "  norm: k_grad_sumsq, %lld elements, %lld workgroups (partial sums of squares in double, fixed order)", n->n_pad, clip_blocks(n->n_pad));
+        if (buffered && update) (void)dry_note(n, "  update: k_reduce_all%s%s%s%s, %d layers' gradients as one-chunk slabs, %d workgroups%s", clip ? "_clip" : "", sgd ? "_sgd" : "", ema ? "_ema" : "",
+                                             dlr ? "_dlr" : "", U.njobs, ublocks, what);
+        else if (!buffered) (void)dry_note(n, "  update: k_reduce_all%s%s%s, %d layers' slabs in one launch, %lld workgroups%s", sgd ? "_sgd" : "", ema ? "_ema" : "", dlr ? "_dlr" : "", n->jobs.njobs, blocks, what);
         n->jobs.njobs = 0;
         return 0;
     }
-    if (dry_note(n, "  update: k_reduce_all%s%s%s, %d layers' slabs in one launch, %lld workgroups%s", sgd ? "_sgd" : "", ema ? "_ema" : "", dlr ? "_dlr" : "", n->jobs.njobs, blocks, what)) {
-        n->jobs.njobs = 0;
-        return 0;
-    }
-    const dim3 grid((unsigned)(clip ? ublocks : blocks)), block(kReduceThreads);
-    if (clip) {
+    const dim3 block(kReduceThreads);
+    if (acc) {
+        if (micro == kMicroFirst) hipLaunchKernelGGL(k_reduce_all_acc<true>, dim3((unsigned)blocks), block, 0, n->stream, n->jobs, n->accum_c);
+        else hipLaunchKernelGGL(k_reduce_all_acc<false>, dim3((unsigned)blocks), block, 0, n->stream, n->jobs, n->accum_c);
+        XTRY(n, hipGetLastError());
+        if (!update) { n->jobs.njobs = 0; return 0; }
+    } else if (clip) {
         hipLaunchKernelGGL(k_reduce_all, dim3((unsigned)blocks), block, 0, n->stream, n->jobs);
         XTRY(n, hipGetLastError());
-        launch_sumsq(n, (const float*)n->clip_grad.p, n->n_pad, 1.0f, (double*)n->clip_part.p);
+    }
+    if (clip) {
+        launch_sumsq(n, summed, n->n_pad, 1.0f, (double*)n->clip_part.p);
         XTRY(n, hipGetLastError());
     }
+    const dim3 grid((unsigned)(buffered ? ublocks : blocks));
+    const ReduceJobs& T = buffered ? U : n->jobs;       // the update launch's table
     const ClipParams Cp = clip ? clip_params(n) : ClipParams{};
     // gradients-only walks (apply == false) take k_reduce_all
     switch ((clip ? 8 : 0) | (sgd ? 4 : 0) | (ema ? 2 : 0) | (dlr ? 1 : 0)) {
-        case 0: hipLaunchKernelGGL(k_reduce_all, grid, block, 0, n->stream, n->jobs); break;
-        case 1: hipLaunchKernelGGL(k_reduce_all_dlr, grid, block, 0, n->stream, n->jobs, lr_dev); break;
-        case 2: hipLaunchKernelGGL(k_reduce_all_ema, grid, block, 0, n->stream, n->jobs, ema_params(n)); break;
-        case 3: hipLaunchKernelGGL(k_reduce_all_ema_dlr, grid, block, 0, n->stream, n->jobs, ema_params(n), lr_dev); break;
-        case 4: hipLaunchKernelGGL(k_reduce_all_sgd, grid, block, 0, n->stream, n->jobs, sgd_params(n)); break;
-        case 5: hipLaunchKernelGGL(k_reduce_all_sgd_dlr, grid, block, 0, n->stream, n->jobs, sgd_params(n), lr_dev); break;
-        case 6: hipLaunchKernelGGL(k_reduce_all_sgd_ema, grid, block, 0, n->stream, n->jobs, sgd_params(n), ema_params(n)); break;
-        case 7: hipLaunchKernelGGL(k_reduce_all_sgd_ema_dlr, grid, block, 0, n->stream, n->jobs, sgd_params(n), ema_params(n), lr_dev); break;
-        case 8: hipLaunchKernelGGL(k_reduce_all_clip, grid, block, 0, n->stream, U, Cp); break;
-        case 9: hipLaunchKernelGGL(k_reduce_all_clip_dlr, grid, block, 0, n->stream, U, Cp, lr_dev); break;
-        case 10: hipLaunchKernelGGL(k_reduce_all_clip_ema, grid, block, 0, n->stream, U, ema_params(n), Cp); break;
-        case 11: hipLaunchKernelGGL(k_reduce_all_clip_ema_dlr, grid, block, 0, n->stream, U, ema_params(n), Cp, lr_dev); break;
-        case 12: hipLaunchKernelGGL(k_reduce_all_clip_sgd, grid, block, 0, n->stream, U, sgd_params(n), Cp); break;
-        case 13: hipLaunchKernelGGL(k_reduce_all_clip_sgd_dlr, grid, block, 0, n->stream, U, sgd_params(n), Cp, lr_dev); break;
-        case 14: hipLaunchKernelGGL(k_reduce_all_clip_sgd_ema, grid, block, 0, n->stream, U, sgd_params(n), ema_params(n), Cp); break;
-        default: hipLaunchKernelGGL(k_reduce_all_clip_sgd_ema_dlr, grid, block, 0, n->stream, U, sgd_params(n), ema_params(n), Cp, lr_dev); break;
+        case 0: hipLaunchKernelGGL(k_reduce_all, grid, block, 0, n->stream, T); break;
+        case 1: hipLaunchKernelGGL(k_reduce_all_dlr, grid, block, 0, n->stream, T, lr_dev); break;
+        case 2: hipLaunchKernelGGL(k_reduce_all_ema, grid, block, 0, n->stream, T, ema_params(n)); break;
+        case 3: hipLaunchKernelGGL(k_reduce_all_ema_dlr, grid, block, 0, n->stream, T, ema_params(n), lr_dev); break;
+        case 4: hipLaunchKernelGGL(k_reduce_all_sgd, grid, block, 0, n->stream, T, sgd_params(n)); break;
+        case 5: hipLaunchKernelGGL(k_reduce_all_sgd_dlr, grid, block, 0, n->stream, T, sgd_params(n), lr_dev); break;
+        case 6: hipLaunchKernelGGL(k_reduce_all_sgd_ema, grid, block, 0, n->stream, T, sgd_params(n), ema_params(n)); break;
+        case 7: hipLaunchKernelGGL(k_reduce_all_sgd_ema_dlr, grid, block, 0, n->stream, T, sgd_params(n), ema_params(n), lr_dev); break;
+        case 8: hipLaunchKernelGGL(k_reduce_all_clip, grid, block, 0, n->stream, T, Cp); break;
+        case 9: hipLaunchKernelGGL(k_reduce_all_clip_dlr, grid, block, 0, n->stream, T, Cp, lr_dev); break;
+        case 10: hipLaunchKernelGGL(k_reduce_all_clip_ema, grid, block, 0, n->stream, T, ema_params(n), Cp); break;
+        case 11: hipLaunchKernelGGL(k_reduce_all_clip_ema_dlr, grid, block, 0, n->stream, T, ema_params(n), Cp, lr_dev); break;
+        case 12: hipLaunchKernelGGL(k_reduce_all_clip_sgd, grid, block, 0, n->stream, T, sgd_params(n), Cp); break;
+        case 13: hipLaunchKernelGGL(k_reduce_all_clip_sgd_dlr, grid, block, 0, n->stream, T, sgd_params(n), Cp, lr_dev); break;
+        case 14: hipLaunchKernelGGL(k_reduce_all_clip_sgd_ema, grid, block, 0, n->stream, T, sgd_params(n), ema_params(n), Cp); break;
+        default: hipLaunchKernelGGL(k_reduce_all_clip_sgd_ema_dlr, grid, block, 0, n->stream, T, sgd_params(n), ema_params(n), Cp, lr_dev); break;
     }
     XTRY(n, hipGetLastError());
     n->jobs.njobs = 0;
@@ -701,11 +760,11 @@ void backward_reset(rcn_hipx_net* n, int first, bool first_gated) {
     n->ev_next = 0;
 }
 
-int backward(rcn_hipx_net* n, const float* x, int B, float lr, float* grad, bool apply, int first, bool first_gated, const float* lr_dev = nullptr) {
+int backward(rcn_hipx_net* n, const float* x, int B, float lr, float* grad, bool apply, int first, bool first_gated, const float* lr_dev = nullptr, int micro = kWholeStep) {
     backward_reset(n, first, first_gated);
     RTRY(backward_layers(n, x, B, lr, grad, apply, first, 0, true));
     if (n->bw.side_busy) RTRY(stream_after(n, n->side, n->stream));   // join: the step's next kernels (and an end of capture) find everything on the main stream
-    return run_reduce_jobs(n, lr, apply, lr_dev);                     // every layer's slab in one launch; no weight was written before this point
+    return run_reduce_jobs(n, lr, apply, lr_dev, micro);              // every layer's slab in one launch; no weight was written before this point
 }
 
 // [partial sums of the loss, one per workgroup][counter of finished workgroups: zero between launches]
@@ -824,13 +883,14 @@ int step_front(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, fl
 }
 
 // forward + loss + backward of one batch: parameters updated in place (apply) or gradients written to grad (padded layout)
-// (lr_dev, nullable: the update's rate comes from that device scalar instead of lr; pair: a step on pair labels)
+// (lr_dev, nullable: the update's rate comes from that device scalar instead of lr; pair: a step on pair labels; micro: the micro-step of
+// an accumulating net -- the front half and the backward pass are the same, only the reduction at the end differs)
 int step_core(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float lr, float* grad, bool apply, float* loss_dev, const float* lr_dev = nullptr,
-              const Pair& pair = Pair{}) {
+              const Pair& pair = Pair{}, int micro = kWholeStep) {
     int first = 0;
     bool gated = false;
     RTRY(step_front(n, x, labels, B, grad, apply, loss_dev, &first, &gated, pair));
-    return backward(n, x, B, lr, grad, apply, first, gated, lr_dev);
+    return backward(n, x, B, lr, grad, apply, first, gated, lr_dev, micro);
 }
 
 void drop_all(std::map<StepKey, hipGraphExec_t>& graphs) { for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second); graphs.clear(); }
@@ -949,7 +1009,7 @@ int make_dry_net(rcn_hipx_net& net, int in_h, int in_w, int in_c, const rcn_hipx
     seed_options(net.opt);
     return describe_layers(&net, in_h, in_w, in_c, layers, n_layers);
 }
-// ... or from an existing net: its layers, precision, tiling, options, optimiser, loss, average and clipping -- the plan and the step agree by construction
+// ... or from an existing net: its layers, precision, tiling, options, optimiser, loss, average, clipping and accumulation -- the plan and the step agree by construction
 void make_dry_net(rcn_hipx_net& net, const rcn_hipx_net& from, int batch) {
     net.in_h = from.in_h; net.in_w = from.in_w; net.in_c = from.in_c; net.max_batch = batch; net.classes = from.classes; net.dry = true;
     static_cast<Selection&>(net) = from;
@@ -957,6 +1017,7 @@ void make_dry_net(rcn_hipx_net& net, const rcn_hipx_net& from, int batch) {
     net.loss_eps = from.loss_eps;
     net.ema_decay = from.ema_decay;
     net.clip_max = from.clip_max;
+    net.accum_k = from.accum_k; net.accum_c = from.accum_c;
     copy_layer_table(net, from);
 }
 
@@ -1160,12 +1221,14 @@ int rcn_hipx_forward_dev(rcn_hipx_net* n, const float* x, int B, float* logits) 
 
 // One eager step (it sizes every scratch buffer outside capture: hipMalloc is illegal while capturing -- and it IS the caller's step),
 // then the same step captured and instantiated for the replays that follow.
-static int step_and_capture(rcn_hipx_net* n, const StepKey& k, hipGraphExec_t* exec_out) {
+// *enqueued (nullable) is set once the caller's step is on the stream, whatever becomes of its capture.
+static int step_and_capture(rcn_hipx_net* n, const StepKey& k, hipGraphExec_t* exec_out, bool* enqueued = nullptr) {
     const Pair pair{k.labels_b, k.weight};
-    RTRY(step_core(n, k.x, k.labels, k.B, k.lr, nullptr, true, k.loss, k.lr_dev, pair));
+    RTRY(step_core(n, k.x, k.labels, k.B, k.lr, nullptr, true, k.loss, k.lr_dev, pair, k.micro));
+    if (enqueued) *enqueued = true;
     hipGraph_t graph = nullptr;
     XTRY(n, hipStreamBeginCapture(n->stream, hipStreamCaptureModeThreadLocal));
-    const int st = step_core(n, k.x, k.labels, k.B, k.lr, nullptr, true, k.loss, k.lr_dev, pair);
+    const int st = step_core(n, k.x, k.labels, k.B, k.lr, nullptr, true, k.loss, k.lr_dev, pair, k.micro);
     hipError_t e = hipStreamEndCapture(n->stream, &graph);
     if (st != 0) { if (graph) (void)hipGraphDestroy(graph); return st; }
     XTRY(n, e);
@@ -1180,20 +1243,41 @@ static int step_and_capture(rcn_hipx_net* n, const StepKey& k, hipGraphExec_t* e
 
 // which of the net's caches a step belongs to: on the caller's pointers (plain 0, pair labels 1), or on the net's own batch buffer with
 // its rate from the host (2, mixed 3) or from the device (4, mixed 5)
+// (a first or middle micro-step of an accumulating net has no lr_dev: it sits with the host-rate steps of its buffers)
 static int family_of(const rcn_hipx_net* n, const StepKey& k) { return (k.x != n->xb.p ? 0 : k.lr_dev ? 4 : 2) + (k.labels_b ? 1 : 0); }
 static_assert(rcn_hipx_net::kFamilies == 6, "family_of hands out 0 .. 5");
 
 // One training step through the cache: a replay of the graph captured for `key`, or -- at its first use -- the eager step (which IS the
 // caller's step) and its capture.  Looked up per step: the eager step of a first use can grow a scratch buffer, which drops every graph.
-static int captured_step(rcn_hipx_net* n, const StepKey& key) {
+// *enqueued (nullable): the step itself is on the stream -- true on success, and also where only the capture behind the eager step failed.
+static int captured_step(rcn_hipx_net* n, const StepKey& key, bool* enqueued = nullptr) {
     auto& graphs = n->graphs[family_of(n, key)];
     auto it = graphs.find(key);
-    if (it != graphs.end()) { XTRY(n, hipGraphLaunch(it->second, n->stream)); return 0; }
+    if (it != graphs.end()) { XTRY(n, hipGraphLaunch(it->second, n->stream)); if (enqueued) *enqueued = true; return 0; }
     hipGraphExec_t exec = nullptr;
-    RTRY(step_and_capture(n, key, &exec));
+    RTRY(step_and_capture(n, key, &exec, enqueued));
     if (graphs.size() >= 8) drop_all(graphs);           // (eight keys: a caller that varies lr per call)
     graphs.emplace(key, exec);
     return 0;
+}
+
+// which micro-step the next training step of the net is (kWholeStep: the net does not accumulate)
+static int next_micro(const rcn_hipx_net* n) {
+    if (n->accum_k == 1) return kWholeStep;
+    return n->accum_pos == 0 ? kMicroFirst : n->accum_pos == n->accum_k - 1 ? kMicroLast : kMicroMiddle;
+}
+
+// One training step of a net that may accumulate: the step `key` describes as the micro-step the net's position in its cycle makes it.
+// Only the micro-step that applies the update keeps the key's rate.  The position advances once the micro-step is on the stream: a first use
+// runs the step eagerly and then captures it, and a failure of that capture must not leave the position behind the accumulator (a retry
+// would add the batch twice).  A step that fails before its reduction launch has changed neither.
+static int training_step(rcn_hipx_net* n, StepKey key) {
+    key.micro = next_micro(n);
+    if (key.micro == kMicroFirst || key.micro == kMicroMiddle) { key.lr = 0.f; key.lr_dev = nullptr; }
+    bool enqueued = false;
+    const int st = captured_step(n, key, &enqueued);
+    if (enqueued && key.micro != kWholeStep) n->accum_pos = (n->accum_pos + 1) % n->accum_k;
+    return st;
 }
 
 int rcn_hipx_train_step_dev(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float lr, float* loss_dev) {
@@ -1201,7 +1285,7 @@ int rcn_hipx_train_step_dev(rcn_hipx_net* n, const float* x, const int32_t* labe
     RTRY(ensure_batch(n, B));
     Dev g(n->device);
     n->walk_open = false;                               // (a step in between abandons an open bucket walk's activations)
-    return captured_step(n, StepKey{x, labels, nullptr, nullptr, B, lr, nullptr, loss_dev});
+    return training_step(n, StepKey{x, labels, nullptr, nullptr, B, lr, nullptr, loss_dev});
 }
 
 int rcn_hipx_train_step_pair_dev(rcn_hipx_net* n, const float* x, const int32_t* labels_a, const int32_t* labels_b, const float* weight, int B, float lr, float* loss_dev) {
@@ -1209,7 +1293,7 @@ int rcn_hipx_train_step_pair_dev(rcn_hipx_net* n, const float* x, const int32_t*
     RTRY(ensure_batch(n, B));
     Dev g(n->device);
     n->walk_open = false;
-    return captured_step(n, StepKey{x, labels_a, labels_b, weight, B, lr, nullptr, loss_dev});
+    return training_step(n, StepKey{x, labels_a, labels_b, weight, B, lr, nullptr, loss_dev});
 }
 
 // ---- the loop around the step: an epoch over a device-resident set, and evaluation --------------------------------------------------------
@@ -1356,9 +1440,11 @@ int rcn_hipx_train_epoch_mix_dev(rcn_hipx_net* n, const void* X, int x_kind, flo
         RTRY(launch_gather(n, X, x_kind, x_scale, x_shift, labels, (long long)rows, perm ? perm + s * B : nullptr, (long long)s * B, B, aug, (unsigned long long)s * (unsigned long long)B, xb, yb,
                            rec, (int*)n->yb2.p));
         // the step's rate (and target weight) into the net's scalars, outside the graph: the eager step and every replay read them there
-        if (lr_dev) XTRY(n, hipMemcpyAsync(elr, lr_dev + (s - first_batch), sizeof(float), hipMemcpyDeviceToDevice, n->stream));
+        // (an accumulating net: only the micro-step that applies the update reads a rate)
+        const int micro = next_micro(n);
+        if (lr_dev && (micro == kWholeStep || micro == kMicroLast)) XTRY(n, hipMemcpyAsync(elr, lr_dev + (s - first_batch), sizeof(float), hipMemcpyDeviceToDevice, n->stream));
         if (rec) XTRY(n, hipMemcpyAsync(n->emixw.p, &rec->weight, sizeof(float), hipMemcpyDeviceToDevice, n->stream));
-        RTRY(captured_step(n, key));
+        RTRY(training_step(n, key));
         if (loss_dev) XTRY(n, hipMemcpyAsync(loss_dev + (s - first_batch), el, sizeof(float), hipMemcpyDeviceToDevice, n->stream));
     }
     return 0;
@@ -1681,6 +1767,45 @@ int rcn_hipx_get_clip(const rcn_hipx_net* n, float* max_norm) {
     return 0;
 }
 
+int rcn_hipx_set_accumulate(rcn_hipx_net* n, int k) {
+    if (!n) return -1;
+    if (k < 1 || k > 65536) return fail(n, -1, "set_accumulate: k must be in 1 .. 65536");
+    if (k == n->accum_k) return 0;
+    Dev g(n->device);
+    XTRY(n, hipStreamSynchronize(n->stream));
+    if (k > 1 && !n->accum.p) {
+        // once, outside any capture: captured graphs hold this pointer, so the buffer never moves afterwards.  The memset stays although a
+        // cycle's first micro-step stores: k_grad_sumsq and rcn_hipx_get_accumulated read all n_pad floats, so any element outside the
+        // reduction jobs' [W | b] ranges has to be zero, and a read before the first micro-step has to be defined.
+        XTRY(n, n->accum.ensure((size_t)n->n_pad * sizeof(float)));
+        XTRY(n, hipMemsetAsync(n->accum.p, 0, n->accum.cap, n->stream));
+        XTRY(n, hipStreamSynchronize(n->stream));
+    }
+    drop_graphs(n);                                     // captured graphs bake in the reduction's launches and their arguments
+    n->accum_k = k; n->accum_c = 1.0f / (float)k; n->accum_pos = 0;      // (a pending cycle is discarded: the next micro-step is a first one and stores)
+    return 0;
+}
+
+int rcn_hipx_get_accumulate(const rcn_hipx_net* n, int* k, int* pending) {
+    if (!n) return -1;
+    if (k) *k = n->accum_k;
+    if (pending) *pending = n->accum_pos;
+    return 0;
+}
+
+int rcn_hipx_reset_accumulation(rcn_hipx_net* n) {
+    if (!n) return -1;
+    n->accum_pos = 0;                                   // host state only: the next micro-step is a first one and stores
+    return 0;
+}
+
+int rcn_hipx_get_accumulated(rcn_hipx_net* n, float* flat) {
+    if (!n || !flat) return -1;
+    if (!n->accum.p) return fail(n, -6, "get_accumulated: accumulation was never switched on (rcn_hipx_set_accumulate with k > 1 first)");
+    Dev g(n->device);
+    return unpad(n, (const float*)n->accum.p, flat);
+}
+
 int rcn_hipx_get_grad_norm(rcn_hipx_net* n, float* norm, float* coef) {
     if (!n) return -1;
     if (!n->clip_state.p) return fail(n, -6, "get_grad_norm: clipping was never switched on (rcn_hipx_set_clip with a max_norm > 0 first)");
@@ -1779,7 +1904,18 @@ int rcn_hipx_plan_net(const rcn_hipx_net* n, int batch, char* out, int cap) {
     rcn_hipx_net net;
     make_dry_net(net, *n, batch);
     net.plan = step_header(net, batch);
-    const int st = step_core(&net, nullptr, nullptr, batch, 0.f, nullptr, true, nullptr);
+    // (an accumulating net: the last micro-step of a cycle, the one that applies the update; rcn_hipx_plan_micro_net: the others)
+    const int st = step_core(&net, nullptr, nullptr, batch, 0.f, nullptr, true, nullptr, nullptr, Pair{}, n->accum_k > 1 ? kMicroLast : kWholeStep);
+    return emit(net, st, out, cap);
+}
+
+// One micro-step of an accumulating net, by kind: 0 the first of a cycle, 1 a middle one, 2 the last
+int rcn_hipx_plan_micro_net(const rcn_hipx_net* n, int batch, int kind, char* out, int cap) {
+    if (!n || batch < 1 || batch > n->max_batch || !out || cap < 1 || kind < 0 || kind > 2 || n->accum_k == 1) return -1;
+    rcn_hipx_net net;
+    make_dry_net(net, *n, batch);
+    net.plan = step_header(net, batch);
+    const int st = step_core(&net, nullptr, nullptr, batch, 0.f, nullptr, true, nullptr, nullptr, Pair{}, kind == 0 ? kMicroFirst : kind == 1 ? kMicroMiddle : kMicroLast);
     return emit(net, st, out, cap);
 }
 
@@ -1801,10 +1937,14 @@ int rcn_hipx_plan_epoch_mix_net(const rcn_hipx_net* n, int batch, int x_kind, in
     if (st == 0) {
         if (lr_from_device) (void)dry_note(&net, "  lr: 4-byte device copy of lr_dev[i] into the net's rate scalar (hipMemcpyAsync, outside the graph)");
         if (mix) (void)dry_note(&net, "  weight: 4-byte device copy of mix_dev[i].weight into the net's target-weight scalar (hipMemcpyAsync, outside the graph)");
-        if (mix) (void)dry_note(&net, lr_from_device ? "  graph: one graph per B, lr from device, pair labels" : "  graph: one graph per (B, lr), pair labels");
+        if (n->accum_k > 1)
+            // an accumulating net keeps a graph per kind of micro-step; only the last kind applies a rate
+            (void)dry_note(&net, "  graph: one graph per kind of micro-step (first%s, last) and B; the last kind %s%s -- below: the last kind", n->accum_k > 2 ? ", middle" : "",
+                           lr_from_device ? "with lr from device" : "per (B, lr)", mix ? ", pair labels" : "");
+        else if (mix) (void)dry_note(&net, lr_from_device ? "  graph: one graph per B, lr from device, pair labels" : "  graph: one graph per (B, lr), pair labels");
         else (void)dry_note(&net, lr_from_device ? "  graph: one graph per B, lr from device" : "  graph: one graph per (B, lr)");
         net.plan += step_header(net, batch);
-        st = step_core(&net, nullptr, nullptr, batch, 0.f, nullptr, true, nullptr, lr_from_device ? marker : nullptr, pair);
+        st = step_core(&net, nullptr, nullptr, batch, 0.f, nullptr, true, nullptr, lr_from_device ? marker : nullptr, pair, n->accum_k > 1 ? kMicroLast : kWholeStep);
     }
     return emit(net, st, out, cap);
 }
