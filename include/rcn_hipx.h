@@ -432,7 +432,9 @@ int  rcn_hipx_plan(int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, i
  * (k_reduce_all into the gradient buffer, k_grad_sumsq, k_reduce_all_clip...) and "(clip: max norm %g)" on the update line
  * (rcn_hipx_plan_epoch_net / _mix_net likewise).  On a net with rcn_hipx_set_accumulate k > 1 the three describe the LAST micro-step of a
  * cycle: the k_reduce_all_acc<next> reduction, the norm where clipping is on, and the update over the accumulator as one-chunk slabs, its
- * line gaining "(accumulate: k micro-batches, scale %g)"; the epoch plans' graph line names the graph per kind of micro-step. */
+ * line gaining "(accumulate: k micro-batches, scale %g)"; the epoch plans' graph line names the graph per kind of micro-step.
+ * The update's kernel name here, in the plans and throughout this header, k_reduce_all[_clip][_sgd][_ema][_dlr], is the display name of an
+ * instantiation of ONE kernel template, k_reduce_update<CLIP, SGD, EMA, DLR> (csrc/convnet_update.hpp): one suffix per flag that is set. */
 int  rcn_hipx_plan_net(const rcn_hipx_net* net, int batch, char* out, int cap);
 /* The launches of one kind of micro-step of an accumulating net: kind 0 the first of a cycle, 1 a middle one, 2 the last.  The reduction
  * line names k_reduce_all_acc<first> or <next> and says "(accumulate: micro-batch of k, no update)"; the last kind is followed by the norm

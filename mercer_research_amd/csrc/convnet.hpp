@@ -12,7 +12,7 @@
 //                  register-staged double buffering, bias + ReLU epilogue.
 //   dgrad          the same kernel on dZ with the tap-flipped, transposed weights Wt[(kh',kw',co)][ci] (k_flip_weights).
 //   k_conv_wgrad   dW[k][co] = sum_m A[m][k] dZ[m][co]: contraction over the output pixels, split over workgroups in
-//                  chunks whose partial tiles go to a slab; k_reduce_all sums every layer's slab in chunk order (bit-
+//                  chunks whose partial tiles go to a slab; the reduction launch (convnet_update.hpp) sums every layer's slab in chunk order (bit-
 //                  reproducible) and applies the SGD step.
 //   k_pool_fwd/bwd 2x2/2 max-pool with a 2-bit arg-max image; backward also applies the ReLU mask.
 //   k_softmax_ce   fused softmax + cross-entropy forward and (p - onehot)/B backward.
@@ -280,7 +280,7 @@ struct WgradGrid {
 // dW partial tiles: workgroup (kb, nb, chunk) computes rows [32 kb, +32) x cols [BN nb, +BN) of dW over the pixels of
 // its chunk and writes them to slab[chunk][K + 1][Cout]; row K is the chunk's partial bias gradient (column sums of dZ,
 // taken by the kb == 0 workgroups from the dZ tiles they stage anyway).  [W | b] is contiguous in the parameter buffer,
-// so ONE k_reduce_all job over (K + 1) * Cout elements finishes both.
+// so ONE reduction job over (K + 1) * Cout elements finishes both.
 template <int KS, bool SMALLC, int BN>
 __global__ __launch_bounds__(kThreads) void k_conv_wgrad(const float* __restrict__ X, const float* __restrict__ dZ,
                                                          float* __restrict__ slab, ConvShape s, int pix_per_chunk, WgradGrid gd) {
@@ -484,7 +484,7 @@ constexpr int kReduceThreads = 1024;
 __host__ __device__ inline int reduce_job_groups(int chunks) { int g = 1; while (g < chunks && g < 32) g <<= 1; return g; }
 __host__ __device__ inline int reduce_job_elems(int chunks) { return 4 * kReduceThreads / reduce_job_groups(chunks); }
 
-// The reduction itself, shared by k_reduce_all (plain SGD) and k_reduce_all_sgd (convnet_sgd.hpp: momentum, weight decay, Nesterov).
+// The reduction itself, shared by every form of k_reduce_update (convnet_update.hpp) and by k_reduce_all_acc (convnet_accum.hpp).
 // `update(J, jb, i, t)` returns the four new parameters [i, i + 4) of job jb from their summed gradient t; it may keep state of its own.
 // Of J an update functor may read ONLY J.lr (the job is its jb): DeviceLr below hands it a ReduceJobs in which nothing else is set.
 template <class Update>
@@ -538,8 +538,7 @@ struct PlainUpdate {
     }
 };
 
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all(ReduceJobs J) { reduce_all_body(J, PlainUpdate{}); }
-// The same launch with the learning rate read from a device scalar (one uniform load): the step of a per-step schedule
+// The kernel is k_reduce_update (convnet_update.hpp).  It may read the learning rate from a device scalar (one uniform load): the step of a per-step schedule
 // (rcn_hipx_train_epoch_ex_dev with lr_dev), whose captured graph then does not depend on the rate.  The update functors read the rate
 // as J.lr, and J is the kernel's argument: writing J.lr would copy all of ReduceJobs into scratch (measured: 1048 bytes per lane, the job
 // table being indexed at run time).  DeviceLr instead hands the wrapped functor a ReduceJobs of which only lr is set and only lr is
@@ -553,7 +552,6 @@ template <class Update> struct DeviceLr {
         return u(K, jb, i, t);
     }
 };
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all_dlr(ReduceJobs J, const float* __restrict__ lr) { reduce_all_body(J, DeviceLr<PlainUpdate>{PlainUpdate{}, *lr}); }
 
 // db[co] = sum_m dZ[m][co]: one workgroup per 32-column block, rows strided over threads, fixed-order tree
 __global__ __launch_bounds__(256) void k_bias_grad(const float* __restrict__ dZ, long long M, int Cout, float* __restrict__ b, float* __restrict__ grad_out,

@@ -15,7 +15,7 @@
 //                        of acc and has neither a gradient destination nor a flipped copy
 //   k_reduce_all_acc<FIRST>
 //                        the step's ONE slab reduction of a micro-step: the grid, the 16-byte accesses and the fixed summation order of
-//                        k_reduce_all; FIRST stores fl(c * t), the other form reads acc and adds
+//                        the update launch (k_reduce_update); FIRST stores fl(c * t), the other form reads acc and adds
 #pragma once
 
 #include "convnet.hpp"

@@ -20,11 +20,11 @@
 //                        from L2) and gets the same bits: no grid-wide hand-off.  Workgroup 0, thread 0 also records (norm, coef), the
 //                        ring log's slot and the step counter with plain stores: one writer, stream-ordered.
 //   Clipped<Update>      wraps an update functor of reduce_all_body: hands it fl(coef * t) and returns its parameters
-//   k_reduce_all_clip[_sgd][_ema][_dlr]
+//   k_reduce_update<CLIP = true, ..>   (convnet_update.hpp)
 //                        the clipped update launch over the net's gradient buffer, each layer's slice a one-chunk slab, so the flipped
 //                        weight copy, the velocity and the average are kept exactly as the unclipped launch keeps them.  The plain and the
 //                        configured optimiser do NOT share an instantiation: PlainUpdate's p - lr * g compiles to one fused multiply-add
-//                        (k_reduce_all and k_axpy have always rounded it once), SgdUpdate with mu = wd = 0 rounds the product and the
+//                        (the unclipped step and k_axpy have always rounded it once), SgdUpdate with mu = wd = 0 rounds the product and the
 //                        difference, and a measure-only step (max_norm = +inf) has to leave an unclipped step's bits.
 //   k_sgd_apply_clip<PLAIN>
 //                        the data-parallel half: k_sgd_apply with d = fl(coef * fl(grad_scale * g)); PLAIN (the default optimiser):
@@ -117,30 +117,6 @@ template <class Update> struct Clipped {
         return u(J, jb, i, c);
     }
 };
-
-// the update functors are those of the unclipped launches (convnet.hpp, convnet_sgd.hpp, convnet_ema.hpp), in the same nesting
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all_clip(ReduceJobs J, ClipParams C) { reduce_all_body(J, Clipped<PlainUpdate>{PlainUpdate{}, clip_coef_all(C)}); }
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all_clip_dlr(ReduceJobs J, ClipParams C, const float* __restrict__ lr) {
-    reduce_all_body(J, Clipped<DeviceLr<PlainUpdate>>{DeviceLr<PlainUpdate>{PlainUpdate{}, *lr}, clip_coef_all(C)});
-}
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all_clip_ema(ReduceJobs J, EmaParams M, ClipParams C) {
-    reduce_all_body(J, Clipped<WithEma<PlainUpdate>>{WithEma<PlainUpdate>{PlainUpdate{}, M}, clip_coef_all(C)});
-}
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all_clip_ema_dlr(ReduceJobs J, EmaParams M, ClipParams C, const float* __restrict__ lr) {
-    reduce_all_body(J, Clipped<WithEma<DeviceLr<PlainUpdate>>>{WithEma<DeviceLr<PlainUpdate>>{DeviceLr<PlainUpdate>{PlainUpdate{}, *lr}, M}, clip_coef_all(C)});
-}
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all_clip_sgd(ReduceJobs J, SgdParams S, ClipParams C) {
-    reduce_all_body(J, Clipped<SgdUpdate>{SgdUpdate{S}, clip_coef_all(C)});
-}
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all_clip_sgd_dlr(ReduceJobs J, SgdParams S, ClipParams C, const float* __restrict__ lr) {
-    reduce_all_body(J, Clipped<DeviceLr<SgdUpdate>>{DeviceLr<SgdUpdate>{SgdUpdate{S}, *lr}, clip_coef_all(C)});
-}
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all_clip_sgd_ema(ReduceJobs J, SgdParams S, EmaParams M, ClipParams C) {
-    reduce_all_body(J, Clipped<WithEma<SgdUpdate>>{WithEma<SgdUpdate>{SgdUpdate{S}, M}, clip_coef_all(C)});
-}
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all_clip_sgd_ema_dlr(ReduceJobs J, SgdParams S, EmaParams M, ClipParams C, const float* __restrict__ lr) {
-    reduce_all_body(J, Clipped<WithEma<DeviceLr<SgdUpdate>>>{WithEma<DeviceLr<SgdUpdate>>{DeviceLr<SgdUpdate>{SgdUpdate{S}, *lr}, M}, clip_coef_all(C)});
-}
 
 // n % 4 == 0 and p, v, g 16-byte aligned (host); workgroups of 1024 threads
 template <bool PLAIN>

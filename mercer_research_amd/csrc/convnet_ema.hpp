@@ -11,9 +11,7 @@
 //   WithEma<Update>       wraps an update functor of reduce_all_body: the wrapped update's four new parameters are in registers on their way
 //                         to the parameter buffer; the average's four are read, moved towards them and written back.  The parameters pass
 //                         through unchanged, so the live parameters, the flipped copy and the velocity are those of a net without an average.
-//   k_reduce_all_ema[_dlr], k_reduce_all_sgd_ema[_dlr]
-//                         the step's ONE slab reduction with the plain / the configured update and the average (_dlr: the rate from a
-//                         device scalar, as k_reduce_all_dlr)
+//                         The step's ONE slab reduction carries it: k_reduce_update<.., EMA = true, ..> (convnet_update.hpp).
 //   k_ema_lerp            the data-parallel half: the same line over the whole padded buffer, after rcn_hipx_apply_sgd_dev's update launch
 //   k_swap4               exchanges two padded buffers (parameters <-> average, around an evaluation on the average)
 #pragma once
@@ -46,15 +44,6 @@ template <class Update> struct WithEma {
         return p;
     }
 };
-
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all_ema(ReduceJobs J, EmaParams M) { reduce_all_body(J, WithEma<PlainUpdate>{PlainUpdate{}, M}); }
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all_ema_dlr(ReduceJobs J, EmaParams M, const float* __restrict__ lr) {
-    reduce_all_body(J, WithEma<DeviceLr<PlainUpdate>>{DeviceLr<PlainUpdate>{PlainUpdate{}, *lr}, M});
-}
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all_sgd_ema(ReduceJobs J, SgdParams S, EmaParams M) { reduce_all_body(J, WithEma<SgdUpdate>{SgdUpdate{S}, M}); }
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all_sgd_ema_dlr(ReduceJobs J, SgdParams S, EmaParams M, const float* __restrict__ lr) {
-    reduce_all_body(J, WithEma<DeviceLr<SgdUpdate>>{DeviceLr<SgdUpdate>{SgdUpdate{S}, *lr}, M});
-}
 
 // n % 4 == 0 and e, p 16-byte aligned (host: whole padded buffers)
 __global__ void k_ema_lerp(float* __restrict__ e, const float* __restrict__ p, float a, long long n) {

@@ -969,7 +969,7 @@ __global__ __launch_bounds__(kThreads) void k_conv1_wgrad_f32(const float* __res
 // gradient 14.8, weight gradient 10.6 us: latency, not arithmetic).  Here a workgroup owns 32 samples: their hidden activations,
 // the weights in both orientations (the flipped copy is kept current by the update kernels) and d logits stay in LDS between the
 // steps.  F = hidden width (multiple of 32, <= 256: LDS), classes <= 32 (one padded column block).  The weight-gradient partials go
-// to slab[workgroup][F + 1][32] like k_conv_wgrad's, so k_reduce_all finishes; the loss like k_softmax_ce (last workgroup
+// to slab[workgroup][F + 1][32] like k_conv_wgrad's, so the reduction launch finishes; the loss like k_softmax_ce (last workgroup
 // adds the partials in order).
 // SOFT: the soft-max stage takes a soft target (k_softmax_ce_soft's expressions and label guard) from ONE trailing SoftTarget argument;
 // the hard instantiation has no such argument: its launch is unchanged.

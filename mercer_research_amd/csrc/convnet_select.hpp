@@ -1,6 +1,7 @@
-// convnet_select.hpp -- Track X: WHICH kernel runs a layer.  Host functions only, pure: no launch, no runtime call, no allocation, every
-// input const.  rcn_hipx_api.hip launches what these choose (one switch per launcher), the plan prints it (describe), and the layer walk
-// asks the same selectors what it needs to know of a neighbouring layer.
+// convnet_select.hpp -- Track X: WHICH kernel runs a layer, and which launches make a step's update (Recipe, select_update, describe_update
+// at the end).  Host functions only, pure: no launch, no runtime call, no allocation, every input const.  rcn_hipx_api.hip launches what
+// these choose (one switch per launcher), the plan prints it (describe...), and the layer walk asks the same selectors what it needs to
+// know of a neighbouring layer.
 #pragma once
 
 #include <cstdarg>
@@ -282,7 +283,7 @@ struct WgradChoice {
 };
 
 // Pixels per weight-gradient chunk.  Every chunk costs one (K+1) x Cout partial tile written to the slab and read back by
-// k_reduce_all, and a chunk is worked on by `tiles` workgroups (k-blocks x n-tiles), so the chunk size aims at a
+// the reduction launch, and a chunk is worked on by `tiles` workgroups (k-blocks x n-tiles), so the chunk size aims at a
 // total number of workgroups -- wide layers need few chunks -- with 1024 pixels as the floor (measured best on the small
 // CIFAR / MNIST nets, where parallelism is what matters).
 inline int pix_per_chunk(const Selection& sel, long long M, long long tiles) {
@@ -390,5 +391,58 @@ inline std::string describe(const WgradChoice& c, const ConvShape& s, int ks, bo
 }
 // does an LDS-tiled kernel run this layer's weight gradient?
 inline bool wgrad_halo_runs(const Selection& sel, const ConvShape& s, int ks) { return lds_tiled(select_wgrad(sel, s, ks, false, Store{}).kernel); }
+
+// ---- the step's update launch (convnet_update.hpp)
+// what a training step does with its gradient: the whole update (a net that does not accumulate), or one micro-step of a cycle of
+// rcn_hipx_set_accumulate -- the first stores into the accumulator, a middle one adds, the last adds and applies the update
+enum Micro { kWholeStep = 0, kMicroFirst = 1, kMicroMiddle = 2, kMicroLast = 3 };
+
+// Everything an update is configured with (rcn_hipx_net derives from it; a dry-run net copies it in one assignment, so the plan and the
+// step agree by construction).  The buffers and the state these settings need stay members of the net.
+struct Recipe {
+    float sgd_mu = 0.f, sgd_wd = 0.f; int sgd_nesterov = 0;      // rcn_hipx_set_sgd: (0, 0, 0) is plain SGD
+    float loss_eps = 0.f;                   // rcn_hipx_set_loss: 0 is the hard cross-entropy through k_softmax_ce / k_head_f32<true>
+    float ema_decay = 0.f;                  // rcn_hipx_set_ema: 0 is off
+    float clip_max = 0.f;                   // rcn_hipx_set_clip: 0 is off
+    int accum_k = 1; float accum_c = 1.f;   // rcn_hipx_set_accumulate: 1 is off; accum_c = fl(1.0f / k)
+};
+inline bool sgd_default(const Recipe& r) { return r.sgd_mu == 0.f && r.sgd_wd == 0.f && !r.sgd_nesterov; }
+inline bool ema_on(const Recipe& r) { return r.ema_decay != 0.f; }
+inline bool clip_on(const Recipe& r) { return r.clip_max != 0.f; }
+
+// The launches of a step's reduction, chosen here and nowhere else.  acc: the queued slabs go through k_reduce_all_acc<first> into the
+// accumulator; update: an update launch runs, k_reduce_update<clip, sgd, ema, dlr>; buffered: it reads the step's gradient from a buffer
+// (the accumulator, the clipped step's gradient buffer) as one-chunk slabs, behind a first launch that fills that buffer.
+struct UpdateChoice { bool acc, first, update, clip, sgd, ema, dlr, buffered; };
+// apply false: a gradients-only walk; micro: which micro-step of an accumulating net (kWholeStep: the net does not accumulate)
+inline UpdateChoice select_update(const Recipe& r, bool apply, int micro, bool lr_from_device) {
+    UpdateChoice c{};
+    c.acc = apply && micro != kWholeStep;
+    c.first = micro == kMicroFirst;
+    c.update = apply && (!c.acc || micro == kMicroLast);
+    c.clip = c.update && clip_on(r);
+    c.sgd = c.update && !sgd_default(r);
+    c.ema = c.update && ema_on(r);
+    c.dlr = c.update && lr_from_device;
+    c.buffered = c.acc || c.clip;
+    return c;
+}
+
+// The plan's lines for it.  An instantiation of k_reduce_update is printed as k_reduce_all[_clip][_sgd][_ema][_dlr], its display name.
+// blocks: workgroups over the queued slabs; ublocks: over the one-chunk slabs of a buffered update; nblocks: of the norm over n_pad elements.
+inline std::string describe_update(const UpdateChoice& c, const Recipe& r, int njobs, long long blocks, int ublocks, long long n_pad, long long nblocks) {
+    std::string s;
+    if (c.acc) s += strf("  reduction: k_reduce_all_acc<%s>, %d layers' slabs in one launch, %lld workgroups (accumulate: micro-batch of %d, no update)\n", c.first ? "first" : "next", njobs, blocks, r.accum_k);
+    else if (c.clip) s += strf("  gradient: k_reduce_all, %d layers' slabs in one launch, %lld workgroups, into the net's gradient buffer (no update)\n", njobs, blocks);
+    if (c.clip) s += strf("  norm: k_grad_sumsq, %lld elements, %lld workgroups (partial sums of squares in double, fixed order)\n", n_pad, nblocks);
+    if (c.buffered && !c.update) return s;
+    s += strf("  update: k_reduce_all%s%s%s%s, ", c.clip ? "_clip" : "", c.sgd ? "_sgd" : "", c.ema ? "_ema" : "", c.dlr ? "_dlr" : "");
+    s += c.buffered ? strf("%d layers' gradients as one-chunk slabs, %d workgroups", njobs, ublocks) : strf("%d layers' slabs in one launch, %lld workgroups", njobs, blocks);
+    if (c.sgd) s += strf(" (SGD: momentum %g, weight decay %g, nesterov %s)", (double)r.sgd_mu, (double)r.sgd_wd, r.sgd_nesterov ? "on" : "off");
+    if (c.ema) s += strf(" (EMA: decay %g)", (double)r.ema_decay);
+    if (c.clip) s += strf(" (clip: max norm %g)", (double)r.clip_max);
+    if (c.acc) s += strf(" (accumulate: %d micro-batches, scale %g)", r.accum_k, (double)r.accum_c);
+    return s + "\n";
+}
 
 }  // namespace rcnx

@@ -9,9 +9,9 @@
 // Every operation rounds once (no fused multiply-add), so a float32 NumPy restatement reproduces it bit for bit
 // (tests/_sgd_ref.py).  Padding elements of the padded layout have g = p = v = 0 and stay 0.
 //
-//   k_reduce_all_sgd  the step's ONE slab reduction (k_reduce_all's body) with this update in place of p <- p - lr g: the training
-//                     step of a net with a non-default setting.  The tap-flipped weight copy is kept current as in k_reduce_all.
-//   k_reduce_all_sgd_dlr  the same with the learning rate read from a device scalar (a per-step schedule on one captured graph).
+//   SgdUpdate         an update functor of reduce_all_body: this update in place of p <- p - lr g in the step's ONE slab reduction
+//                     (k_reduce_update<.., SGD = true, ..>, convnet_update.hpp), the training step of a net with a non-default setting.
+//                     The tap-flipped weight copy is kept current as with PlainUpdate.
 //   k_sgd_apply       the data-parallel half: the same update from an all-reduced padded gradient buffer, grid-stride, 16-byte accesses.
 #pragma once
 
@@ -54,10 +54,6 @@ struct SgdUpdate {
         return p;
     }
 };
-
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all_sgd(ReduceJobs J, SgdParams S) { reduce_all_body(J, SgdUpdate{S}); }
-// ... with the learning rate read from a device scalar (k_reduce_all_dlr)
-__global__ __launch_bounds__(kReduceThreads) void k_reduce_all_sgd_dlr(ReduceJobs J, SgdParams S, const float* __restrict__ lr) { reduce_all_body(J, DeviceLr<SgdUpdate>{SgdUpdate{S}, *lr}); }
 
 // n % 4 == 0 and p, v, g 16-byte aligned (host)
 __global__ void k_sgd_apply(float* __restrict__ p, const float* __restrict__ g, float grad_scale, float lr, SgdParams s, long long n) {

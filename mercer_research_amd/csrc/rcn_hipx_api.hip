@@ -24,9 +24,7 @@
 #include "convnet_halo.hpp"
 #include "convnet_halo_bf16.hpp"
 #include "convnet_select.hpp"
-#include "convnet_sgd.hpp"
-#include "convnet_ema.hpp"
-#include "convnet_clip.hpp"
+#include "convnet_update.hpp"
 #include "convnet_accum.hpp"
 
 using namespace rcnx;
@@ -64,13 +62,9 @@ struct LayerShape {
 // ... and what it holds on the device
 struct Layer : LayerShape {
     Buf out, idx, dout;     // activation (post-ReLU / pooled), pool arg-max, gradient wrt the layer's OUTPUT
-    Buf slab;               // partial [W | b] tiles of the weight-gradient kernels (reduced for all layers at once: k_reduce_all)
+    Buf slab;               // partial [W | b] tiles of the weight-gradient kernels (reduced for all layers at once: run_reduce_jobs)
     long long wbf_off = -1, wbb_off = -1;   // bf16 mode: this layer's transposed bf16 weight copies in net->wb16 (forward / input-gradient operand)
 };
-
-// what a training step does with its gradient: the whole update (a net that does not accumulate), or one micro-step of a cycle of
-// rcn_hipx_set_accumulate -- the first stores into the accumulator, a middle one adds, the last adds and applies the update
-enum Micro { kWholeStep = 0, kMicroFirst = 1, kMicroMiddle = 2, kMicroLast = 3 };
 
 // everything a captured step bakes in: its arguments are step_core's (a first or middle micro-step keys with lr = 0 and no lr_dev: it
 // applies no rate, so one graph per B serves every rate and schedule)
@@ -84,8 +78,9 @@ struct Pair { const int32_t* labels_b = nullptr; const float* weight = nullptr; 
 
 }  // namespace
 
-// precision, store16, tiling and the kernel-selection options are the net's Selection (convnet_select.hpp): all that choosing a kernel reads
-struct rcn_hipx_net : Selection {
+// precision, store16, tiling and the kernel-selection options are the net's Selection (convnet_select.hpp): all that choosing a kernel reads;
+// the optimiser, the loss, the average, clipping and accumulation are its Recipe: all that choosing and describing an update reads
+struct rcn_hipx_net : Selection, Recipe {
     int device = 0, in_h = 0, in_w = 0, in_c = 0, max_batch = 0, classes = 0;
     hipStream_t stream = nullptr; bool own_stream = false;
     // The backward pass can run a layer's weight gradient on a second stream beside the input-gradient chain: the two only share dZ,
@@ -103,29 +98,23 @@ struct rcn_hipx_net : Selection {
     Buf* slab_sel = nullptr;                // where the weight-gradient launch in progress puts its partial tiles (a layer's slab)
     ReduceJobs jobs{};                      // the step's pending slab reductions
     Buf wb16; PrepJobs prep{}; long long prep_blocks = 0;      // bf16 mode: every layer's bf16 operand copies, made by ONE launch per step
-    // the optimiser (rcn_hipx_set_sgd; convnet_sgd.hpp): (0, 0, 0) is plain SGD through k_reduce_all / k_axpy.  `vel` (n_pad floats, laid out
-    // like params) is allocated by the first nonzero momentum and never moved afterwards: captured graphs hold its pointer.
-    float sgd_mu = 0.f, sgd_wd = 0.f; int sgd_nesterov = 0;
+    // The buffers and the state behind the Recipe.  Each is allocated once and outside any capture by the first setting that needs it
+    // (reconfigure, rcn_hipx_api_update.ipp) and never moved afterwards: captured graphs hold its pointer.
+    // the optimiser (convnet_sgd.hpp): `vel` (n_pad floats, laid out like params), by the first nonzero momentum
     Buf vel;
-    // the average of the parameters (rcn_hipx_set_ema; convnet_ema.hpp): 0 is off, the update launches of a net never configured.  `ema`
-    // (n_pad floats, laid out like params) is allocated by the first decay > 0 and never moved afterwards: captured graphs hold its pointer.
-    float ema_decay = 0.f;
+    // the average of the parameters (convnet_ema.hpp): `ema` (n_pad floats, laid out like params), by the first decay > 0
     Buf ema;
-    // clipping by global norm (rcn_hipx_set_clip; convnet_clip.hpp): 0 is off, the update launch of a net never configured.  The first
-    // max_norm > 0 allocates, once and outside any capture, the step's gradient buffer (n_pad floats), k_grad_sumsq's partials
-    // (ceil(n_pad / 4096) doubles) and the state [8-byte step counter][norm][coef]; none of them ever moves: captured graphs hold their
-    // pointers.  clip_log: the caller's ring of norms (rcn_hipx_set_grad_norm_log), a kernel argument.  norm_part: the scratch of
-    // rcn_hipx_grad_norm_dev, its own (it may grow; no graph of the net points into it).
-    float clip_max = 0.f;
+    // clipping by global norm (convnet_clip.hpp): the first max_norm > 0 allocates the step's gradient buffer (n_pad floats), k_grad_sumsq's partials
+    // (ceil(n_pad / 4096) doubles) and the state [8-byte step counter][norm][coef].  clip_log: the caller's ring of norms
+    // (rcn_hipx_set_grad_norm_log), a kernel argument.  norm_part: the scratch of rcn_hipx_grad_norm_dev, its own (it may grow; no graph
+    // of the net points into it).
     Buf clip_grad, clip_part, clip_state;
     float* clip_log = nullptr; long long clip_log_cap = 0;
     Buf norm_part;
-    // gradient accumulation (rcn_hipx_set_accumulate; convnet_accum.hpp): every accum_k consecutive training micro-steps form one update;
-    // 1 is off, the launches of a net never configured.  `accum` (n_pad floats, laid out like params) is allocated by the first k > 1,
-    // outside any capture, and never moved afterwards: captured graphs hold its pointer.  accum_c = fl(1.0f / k); accum_pos: micro-steps
-    // already accumulated in the open cycle, 0 .. k - 1 -- host state, advanced when a micro-step has been enqueued.
-    int accum_k = 1, accum_pos = 0;
-    float accum_c = 1.f;
+    // gradient accumulation (convnet_accum.hpp): every accum_k consecutive training micro-steps form one update.  `accum` (n_pad floats,
+    // laid out like params), by the first k > 1.  accum_pos: micro-steps already accumulated in the open cycle, 0 .. k - 1 -- host state,
+    // advanced when a micro-step has been enqueued.
+    int accum_pos = 0;
     Buf accum;
     // The captured steps, one cache per family (family_of): the caller's pointers plain or on pair labels (rcn_hipx_train_step_dev /
     // _pair_dev), and the epoch's steps on the net's own buffers x (rate from the host | from the device) x (mixed or not).  A family
@@ -137,10 +126,8 @@ struct rcn_hipx_net : Selection {
     // serves every batch of every epoch, whatever set, permutation and loss slots the caller passes.
     Buf xb, yb, eloss;
     // a per-step schedule (rcn_hipx_train_epoch_ex_dev with lr_dev): the rate of the step lives in this 4-byte scalar, allocated once and
-    // never moved, the update launch reads it (k_reduce_all_dlr), and ONE graph per B serves every schedule
+    // never moved, the update launch reads it (the _dlr forms of k_reduce_update), and ONE graph per B serves every schedule
     Buf elr;
-    // the loss (rcn_hipx_set_loss): 0 is the hard cross-entropy through k_softmax_ce / k_head_f32<true>
-    float loss_eps = 0.f;
     // mixed samples (rcn_hipx_train_epoch_mix_dev with records): the partners' labels beside yb and the step's target weight, allocated
     // once and never moved; the mixed step's loss launch reads (yb, yb2, emixw), so ONE more graph per (B, lr) / per B serves every record
     Buf yb2, emixw;
@@ -532,147 +519,10 @@ int reduce_slab(rcn_hipx_net* n, size_t i, int chunks, int ks, const ConvShape& 
     return 0;
 }
 
-bool sgd_default(const rcn_hipx_net* n) { return n->sgd_mu == 0.f && n->sgd_wd == 0.f && !n->sgd_nesterov; }
-SgdParams sgd_params(const rcn_hipx_net* n) { return SgdParams{(float*)n->vel.p, (const float*)n->params.p, n->sgd_mu, n->sgd_wd, n->sgd_nesterov}; }
-bool ema_on(const rcn_hipx_net* n) { return n->ema_decay != 0.f; }
-EmaParams ema_params(const rcn_hipx_net* n) { return EmaParams{(float*)n->ema.p, (const float*)n->params.p, 1.0f - n->ema_decay}; }
-bool clip_on(const rcn_hipx_net* n) { return n->clip_max != 0.f; }
-// the clipped launch's view of the net's clip state; the partials are those of the buffer k_grad_sumsq has just summed
-ClipParams clip_params(const rcn_hipx_net* n) {
-    unsigned long long* const count = (unsigned long long*)n->clip_state.p;
-    return ClipParams{(const double*)n->clip_part.p, (int)clip_blocks(n->n_pad), n->clip_max, (float*)(count + 1), n->clip_log, n->clip_log_cap, count};
-}
-// partial[b] of every 4096-element block of g[0, len) (len % 4 == 0, g 16-byte aligned), on the net's stream
-void launch_sumsq(rcn_hipx_net* n, const float* g, long long len, float scale, double* partial) {
-    if (len > 0) hipLaunchKernelGGL(k_grad_sumsq, dim3((unsigned)clip_blocks(len)), dim3(kClipThreads), 0, n->stream, g, len, scale, partial);
-}
-
-// The update launch over a gradient that already lies summed in a buffer `g` laid out like the parameters (the clipped step's gradient
-// buffer, the accumulator): the queued jobs, each reading its layer's slice of g as a one-chunk slab.  Fills *U from n->jobs (which it
-// leaves alone); returns U's workgroups.
-int slab_tables(rcn_hipx_net* n, const float* g, float lr, ReduceJobs* U) {
-    *U = n->jobs;
-    U->lr = lr; U->apply = 1;
-    int next = 0;
-    for (int q = 0; q < U->njobs; ++q) {
-        ReduceJob& u = U->j[q];
-        u.grad = nullptr;
-        u.slab = g + (u.p - (float*)n->params.p);
-        u.chunks = 1;
-        u.first_block = next;
-        next += (int)((u.n + reduce_job_elems(1) - 1) / reduce_job_elems(1));
-    }
-    return next;
-}
-
-// The clipped step's reduction is three launches in place of one (convnet_clip.hpp): the queued jobs first run as the gradients-only
-// reduction into the net's gradient buffer; k_grad_sumsq sums its squares; then the same jobs, each reading its slice of that buffer as a
-// one-chunk slab, run as the clipped update -- so the flipped weight copy, the velocity and the average are kept as the unclipped launch
-// keeps them.  This turns n->jobs into the first launch's table and fills *U with the update launch's; returns the latter's workgroups.
-int clipped_tables(rcn_hipx_net* n, float lr, ReduceJobs* U) {
-    ReduceJobs& J = n->jobs;
-    const int ublocks = slab_tables(n, (const float*)n->clip_grad.p, lr, U);
-    J.lr = 0.f; J.apply = 0;
-    for (int q = 0; q < J.njobs; ++q) {
-        J.j[q].grad = (float*)n->clip_grad.p + (J.j[q].p - (float*)n->params.p);
-        J.j[q].flip.wt = nullptr;
-    }
-    return ublocks;
-}
-
-// A micro-step of an accumulating net (convnet_accum.hpp): the queued jobs run as k_reduce_all_acc, each job's "parameters" being its
-// layer's slice of the accumulator -- no gradient destination, no flipped copy.  This turns n->jobs into that launch's table.  The last
-// micro-step of a cycle then takes its update launch's table from slab_tables over the accumulator.
-void accum_tables(rcn_hipx_net* n) {
-    ReduceJobs& J = n->jobs;
-    J.lr = 0.f; J.apply = 1;
-    for (int q = 0; q < J.njobs; ++q) {
-        ReduceJob& a = J.j[q];
-        a.p = (float*)n->accum.p + (a.p - (float*)n->params.p);
-        a.grad = nullptr;
-        a.flip.wt = nullptr;
-    }
-}
-
-// lr_dev (nullable): the update reads its rate from this device scalar instead of `lr` (the _dlr kernels; same arithmetic on the same float)
+// the step's ONE reduction launch over the queued jobs, or the launches that stand for it (rcn_hipx_api_update.ipp)
+// lr_dev (nullable): the update reads its rate from this device scalar instead of `lr` (same arithmetic on the same float)
 // micro: which micro-step of an accumulating net this is (kWholeStep: the net does not accumulate, or a gradients-only walk)
-int run_reduce_jobs(rcn_hipx_net* n, float lr, bool apply, const float* lr_dev = nullptr, int micro = kWholeStep) {
-    if (!n->jobs.njobs) return 0;
-    const ReduceJob& last = n->jobs.j[n->jobs.njobs - 1];
-    const long long blocks = last.first_block + (last.n + reduce_job_elems(last.chunks) - 1) / reduce_job_elems(last.chunks);
-    n->jobs.lr = lr; n->jobs.apply = apply ? 1 : 0;
-    const bool acc = apply && micro != kWholeStep, update = apply && (!acc || micro == kMicroLast);
-    // the update kernel of this launch, chosen here and nowhere else: (clipping on?, the net's optimiser?, the average on?, the rate from the device?)
-    const bool sgd = update && !sgd_default(n), ema = update && ema_on(n), dlr = update && lr_dev, clip = update && clip_on(n);
-    char what[320] = "";
-    if (sgd) std::snprintf(what, sizeof what, " (SGD: momentum %g, weight decay %g, nesterov %s)", (double)n->sgd_mu, (double)n->sgd_wd, n->sgd_nesterov ? "on" : "off");
-    if (ema) std::snprintf(what + std::strlen(what), sizeof what - std::strlen(what), " (EMA: decay %g)", (double)n->ema_decay);
-    if (clip) std::snprintf(what + std::strlen(what), sizeof what - std::strlen(what), " (clip: max norm %g)", (double)n->clip_max);
-    if (acc) std::snprintf(what + std::strlen(what), sizeof what - std::strlen(what), " (accumulate: %d micro-batches, scale %g)", n->accum_k, (double)n->accum_c);
-    // the update launch's table where it is not n->jobs: clipping (n->jobs being the gradients-only launch's), accumulation (the k_reduce_all_acc launch's)
-    ReduceJobs U;
-    int ublocks = 0;
-    const bool buffered = acc || clip;                  // the update reads the step's gradient from a buffer, as one-chunk slabs ...
-    const float* summed = nullptr;                      // ... this one (a dry run has no buffers), and so does the norm
-    if (acc) {
-        summed = (const float*)n->accum.p;
-        if (update) ublocks = slab_tables(n, summed, lr, &U);
-        accum_tables(n);
-    } else if (clip) {
-        summed = (const float*)n->clip_grad.p;
-        ublocks = clipped_tables(n, lr, &U);
-    }
-    if (n->dry) {
-        if (acc) (void)dry_note(n, "  reduction: k_reduce_all_acc<%s>, %d layers' slabs in one launch, %lld workgroups (accumulate: micro-batch of %d, no update)",
-                                micro == kMicroFirst ? "first" : "next", n->jobs.njobs, blocks, n->accum_k);
-        else if (clip) (void)dry_note(n, "  gradient: k_reduce_all, %d layers' slabs in one launch, %lld workgroups, into the net's gradient buffer (no update)", n->jobs.njobs, blocks);
-        if (clip) (void)dry_note(n, "  norm: k_grad_sumsq, %lld elements, %lld workgroups (partial sums of squares in double, fixed order)", n->n_pad, clip_blocks(n->n_pad));
-        if (buffered && update) (void)dry_note(n, "  update: k_reduce_all%s%s%s%s, %d layers' gradients as one-chunk slabs, %d workgroups%s", clip ? "_clip" : "", sgd ? "_sgd" : "", ema ? "_ema" : "",
-                                             dlr ? "_dlr" : "", U.njobs, ublocks, what);
-        else if (!buffered) (void)dry_note(n, "  update: k_reduce_all%s%s%s, %d layers' slabs in one launch, %lld workgroups%s", sgd ? "_sgd" : "", ema ? "_ema" : "", dlr ? "_dlr" : "", n->jobs.njobs, blocks, what);
-        n->jobs.njobs = 0;
-        return 0;
-    }
-    const dim3 block(kReduceThreads);
-    if (acc) {
-        if (micro == kMicroFirst) hipLaunchKernelGGL(k_reduce_all_acc<true>, dim3((unsigned)blocks), block, 0, n->stream, n->jobs, n->accum_c);
-        else hipLaunchKernelGGL(k_reduce_all_acc<false>, dim3((unsigned)blocks), block, 0, n->stream, n->jobs, n->accum_c);
-        XTRY(n, hipGetLastError());
-        if (!update) { n->jobs.njobs = 0; return 0; }
-    } else if (clip) {
-        hipLaunchKernelGGL(k_reduce_all, dim3((unsigned)blocks), block, 0, n->stream, n->jobs);
-        XTRY(n, hipGetLastError());
-    }
-    if (clip) {
-        launch_sumsq(n, summed, n->n_pad, 1.0f, (double*)n->clip_part.p);
-        XTRY(n, hipGetLastError());
-    }
-    const dim3 grid((unsigned)(buffered ? ublocks : blocks));
-    const ReduceJobs& T = buffered ? U : n->jobs;       // the update launch's table
-    const ClipParams Cp = clip ? clip_params(n) : ClipParams{};
-    // gradients-only walks (apply == false) take k_reduce_all
-    switch ((clip ? 8 : 0) | (sgd ? 4 : 0) | (ema ? 2 : 0) | (dlr ? 1 : 0)) {
-        case 0: hipLaunchKernelGGL(k_reduce_all, grid, block, 0, n->stream, T); break;
-        case 1: hipLaunchKernelGGL(k_reduce_all_dlr, grid, block, 0, n->stream, T, lr_dev); break;
-        case 2: hipLaunchKernelGGL(k_reduce_all_ema, grid, block, 0, n->stream, T, ema_params(n)); break;
-        case 3: hipLaunchKernelGGL(k_reduce_all_ema_dlr, grid, block, 0, n->stream, T, ema_params(n), lr_dev); break;
-        case 4: hipLaunchKernelGGL(k_reduce_all_sgd, grid, block, 0, n->stream, T, sgd_params(n)); break;
-        case 5: hipLaunchKernelGGL(k_reduce_all_sgd_dlr, grid, block, 0, n->stream, T, sgd_params(n), lr_dev); break;
-        case 6: hipLaunchKernelGGL(k_reduce_all_sgd_ema, grid, block, 0, n->stream, T, sgd_params(n), ema_params(n)); break;
-        case 7: hipLaunchKernelGGL(k_reduce_all_sgd_ema_dlr, grid, block, 0, n->stream, T, sgd_params(n), ema_params(n), lr_dev); break;
-        case 8: hipLaunchKernelGGL(k_reduce_all_clip, grid, block, 0, n->stream, T, Cp); break;
-        case 9: hipLaunchKernelGGL(k_reduce_all_clip_dlr, grid, block, 0, n->stream, T, Cp, lr_dev); break;
-        case 10: hipLaunchKernelGGL(k_reduce_all_clip_ema, grid, block, 0, n->stream, T, ema_params(n), Cp); break;
-        case 11: hipLaunchKernelGGL(k_reduce_all_clip_ema_dlr, grid, block, 0, n->stream, T, ema_params(n), Cp, lr_dev); break;
-        case 12: hipLaunchKernelGGL(k_reduce_all_clip_sgd, grid, block, 0, n->stream, T, sgd_params(n), Cp); break;
-        case 13: hipLaunchKernelGGL(k_reduce_all_clip_sgd_dlr, grid, block, 0, n->stream, T, sgd_params(n), Cp, lr_dev); break;
-        case 14: hipLaunchKernelGGL(k_reduce_all_clip_sgd_ema, grid, block, 0, n->stream, T, sgd_params(n), ema_params(n), Cp); break;
-        default: hipLaunchKernelGGL(k_reduce_all_clip_sgd_ema_dlr, grid, block, 0, n->stream, T, sgd_params(n), ema_params(n), Cp, lr_dev); break;
-    }
-    XTRY(n, hipGetLastError());
-    n->jobs.njobs = 0;
-    return 0;
-}
+int run_reduce_jobs(rcn_hipx_net* n, float lr, bool apply, const float* lr_dev = nullptr, int micro = kWholeStep);
 
 // backward from dlogits (already in L.back().dout); apply: update parameters with lr, else write gradients to grad (padded layout).
 // backward_layers handles the layers hi .. lo (downwards) and queues their slab reductions; the state that travels from layer to layer
@@ -1013,11 +863,7 @@ int make_dry_net(rcn_hipx_net& net, int in_h, int in_w, int in_c, const rcn_hipx
 void make_dry_net(rcn_hipx_net& net, const rcn_hipx_net& from, int batch) {
     net.in_h = from.in_h; net.in_w = from.in_w; net.in_c = from.in_c; net.max_batch = batch; net.classes = from.classes; net.dry = true;
     static_cast<Selection&>(net) = from;
-    net.sgd_mu = from.sgd_mu; net.sgd_wd = from.sgd_wd; net.sgd_nesterov = from.sgd_nesterov;
-    net.loss_eps = from.loss_eps;
-    net.ema_decay = from.ema_decay;
-    net.clip_max = from.clip_max;
-    net.accum_k = from.accum_k; net.accum_c = from.accum_c;
+    static_cast<Recipe&>(net) = from;
     copy_layer_table(net, from);
 }
 
@@ -1577,286 +1423,6 @@ int rcn_hipx_gradients_bucket_dev(rcn_hipx_net* n, int k, int64_t* off, int64_t*
     return 0;
 }
 
-__global__ void k_axpy(float* __restrict__ p, const float* __restrict__ g, float scale, long long n) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) p[i] = p[i] - scale * g[i];
-}
-
-// p <- p - scale * g over the padded parameters
-static int launch_axpy(rcn_hipx_net* n, const float* grad, float scale) {
-    hipLaunchKernelGGL(k_axpy, dim3(grid1d(n->n_pad, 256)), dim3(256), 0, n->stream, (float*)n->params.p, grad, scale, n->n_pad);
-    XTRY(n, hipGetLastError());
-    return 0;
-}
-
-int rcn_hipx_apply_dev(rcn_hipx_net* n, const float* grad, float scale) {
-    if (!n || !grad) return -1;
-    Dev g(n->device);
-    RTRY(launch_axpy(n, grad, scale));
-    return refresh_flipped(n);                          // (the plain axpy: neither the velocity nor the average moves)
-}
-
-int rcn_hipx_set_sgd(rcn_hipx_net* n, float momentum, float weight_decay, int nesterov) {
-    if (!n) return -1;
-    if (!(momentum >= 0.f && momentum < 1.f)) return fail(n, -1, "set_sgd: momentum must be in [0, 1)");
-    if (!(std::isfinite(weight_decay) && weight_decay >= 0.f)) return fail(n, -1, "set_sgd: weight_decay must be finite and >= 0");
-    if (nesterov != 0 && nesterov != 1) return fail(n, -1, "set_sgd: nesterov must be 0 or 1");
-    if (nesterov && momentum == 0.f) return fail(n, -1, "set_sgd: nesterov needs a momentum > 0");
-    if (momentum == n->sgd_mu && weight_decay == n->sgd_wd && nesterov == n->sgd_nesterov) return 0;
-    Dev g(n->device);
-    XTRY(n, hipStreamSynchronize(n->stream));
-    if (momentum != 0.f && !n->vel.p) {
-        // once, outside any capture: captured graphs hold this pointer, so the buffer never moves afterwards
-        XTRY(n, n->vel.ensure((size_t)n->n_pad * sizeof(float)));
-        XTRY(n, hipMemsetAsync(n->vel.p, 0, (size_t)n->n_pad * sizeof(float), n->stream));
-        XTRY(n, hipStreamSynchronize(n->stream));
-    }
-    drop_graphs(n);                                     // captured graphs bake in the update kernel and its arguments
-    n->sgd_mu = momentum; n->sgd_wd = weight_decay; n->sgd_nesterov = nesterov;
-    return 0;
-}
-
-int rcn_hipx_set_loss(rcn_hipx_net* n, float label_smoothing) {
-    if (!n) return -1;
-    if (!(std::isfinite(label_smoothing) && label_smoothing >= 0.f && label_smoothing < 1.f)) return fail(n, -1, "set_loss: label_smoothing must be finite and in [0, 1)");
-    if (label_smoothing == n->loss_eps) return 0;
-    Dev g(n->device);
-    XTRY(n, hipStreamSynchronize(n->stream));
-    drop_graphs(n);                                     // captured graphs bake in the loss kernel and its arguments
-    n->loss_eps = label_smoothing;
-    return 0;
-}
-
-int rcn_hipx_get_loss(const rcn_hipx_net* n, float* label_smoothing) {
-    if (!n) return -1;
-    if (label_smoothing) *label_smoothing = n->loss_eps;
-    return 0;
-}
-
-int rcn_hipx_get_sgd(const rcn_hipx_net* n, float* momentum, float* weight_decay, int* nesterov) {
-    if (!n) return -1;
-    if (momentum) *momentum = n->sgd_mu;
-    if (weight_decay) *weight_decay = n->sgd_wd;
-    if (nesterov) *nesterov = n->sgd_nesterov;
-    return 0;
-}
-
-int rcn_hipx_get_velocity(rcn_hipx_net* n, float* flat) {
-    if (!n || !flat) return -1;
-    if (!n->vel.p) { std::memset(flat, 0, (size_t)n->n_log * sizeof(float)); return 0; }
-    Dev g(n->device);
-    return unpad(n, (const float*)n->vel.p, flat);
-}
-
-int rcn_hipx_set_velocity(rcn_hipx_net* n, const float* flat) {
-    if (!n || !flat) return -1;
-    if (n->sgd_mu == 0.f || !n->vel.p) return fail(n, -6, "set_velocity: the net has no momentum (rcn_hipx_set_sgd first)");
-    Dev g(n->device);
-    return upload_padded(n, n->vel, flat);
-}
-
-int rcn_hipx_reset_velocity(rcn_hipx_net* n) {
-    if (!n) return -1;
-    if (!n->vel.p) return 0;
-    Dev g(n->device);
-    XTRY(n, hipMemsetAsync(n->vel.p, 0, (size_t)n->n_pad * sizeof(float), n->stream));
-    return 0;
-}
-
-// the average follows the parameters that rcn_hipx_apply_sgd_dev's update launch has just stored (one more launch: this path is not the
-// captured step, and it leaves the update launches exactly what they are without an average)
-static int apply_ema(rcn_hipx_net* n) {
-    if (!ema_on(n)) return 0;
-    const EmaParams m = ema_params(n);
-    hipLaunchKernelGGL(k_ema_lerp, dim3(grid1d(n->n_pad / 4, 256)), dim3(256), 0, n->stream, m.e, m.p0, m.a, n->n_pad);
-    XTRY(n, hipGetLastError());
-    return 0;
-}
-
-int rcn_hipx_set_ema(rcn_hipx_net* n, float decay) {
-    if (!n) return -1;
-    if (!(std::isfinite(decay) && decay >= 0.f && decay < 1.f)) return fail(n, -1, "set_ema: decay must be finite and in [0, 1)");
-    if (decay == n->ema_decay) return 0;
-    Dev g(n->device);
-    XTRY(n, hipStreamSynchronize(n->stream));
-    if (decay != 0.f && !n->ema.p) {
-        // once, outside any capture: captured graphs hold this pointer, so the buffer never moves afterwards.  It starts as the live parameters.
-        XTRY(n, n->ema.ensure((size_t)n->n_pad * sizeof(float)));
-        XTRY(n, hipMemcpyAsync(n->ema.p, n->params.p, (size_t)n->n_pad * sizeof(float), hipMemcpyDeviceToDevice, n->stream));
-        XTRY(n, hipStreamSynchronize(n->stream));
-    }
-    drop_graphs(n);                                     // captured graphs bake in the update kernel and its arguments
-    n->ema_decay = decay;
-    return 0;
-}
-
-int rcn_hipx_get_ema(const rcn_hipx_net* n, float* decay) {
-    if (!n) return -1;
-    if (decay) *decay = n->ema_decay;
-    return 0;
-}
-
-int rcn_hipx_get_ema_params(rcn_hipx_net* n, float* flat) {
-    if (!n || !flat) return -1;
-    if (!n->ema.p) return fail(n, -6, "get_ema_params: the net has no average (rcn_hipx_set_ema with a decay > 0 first)");
-    Dev g(n->device);
-    return unpad(n, (const float*)n->ema.p, flat);
-}
-
-int rcn_hipx_set_ema_params(rcn_hipx_net* n, const float* flat) {
-    if (!n || !flat) return -1;
-    if (!n->ema.p) return fail(n, -6, "set_ema_params: the net has no average (rcn_hipx_set_ema with a decay > 0 first)");
-    Dev g(n->device);
-    return upload_padded(n, n->ema, flat);
-}
-
-int rcn_hipx_reset_ema(rcn_hipx_net* n) {
-    if (!n) return -1;
-    if (!n->ema.p) return 0;
-    Dev g(n->device);
-    XTRY(n, hipMemcpyAsync(n->ema.p, n->params.p, (size_t)n->n_pad * sizeof(float), hipMemcpyDeviceToDevice, n->stream));
-    return 0;
-}
-
-int rcn_hipx_apply_sgd_dev(rcn_hipx_net* n, const float* grad, float grad_scale, float lr) {
-    if (!n || !grad) return -1;
-    Dev g(n->device);
-    if (clip_on(n)) {
-        // clipping on, whatever the optimiser: the norm of fl(grad_scale * g), then k_sgd_apply with the coefficient in front of the update
-        if ((uintptr_t)grad % 16 != 0) return fail(n, -1, "apply_sgd: the gradient buffer must be 16-byte aligned");
-        launch_sumsq(n, grad, n->n_pad, grad_scale, (double*)n->clip_part.p);
-        XTRY(n, hipGetLastError());
-        const dim3 grid(grid1d(n->n_pad / 4, kClipThreads)), block(kClipThreads);
-        if (sgd_default(n)) hipLaunchKernelGGL(k_sgd_apply_clip<true>, grid, block, 0, n->stream, (float*)n->params.p, grad, grad_scale, lr, sgd_params(n), n->n_pad, clip_params(n));
-        else hipLaunchKernelGGL(k_sgd_apply_clip<false>, grid, block, 0, n->stream, (float*)n->params.p, grad, grad_scale, lr, sgd_params(n), n->n_pad, clip_params(n));
-        XTRY(n, hipGetLastError());
-    } else if (sgd_default(n)) RTRY(launch_axpy(n, grad, grad_scale * lr));      // plain SGD: rcn_hipx_apply_dev(grad, grad_scale * lr)'s launch
-    else {
-        if ((uintptr_t)grad % 16 != 0) return fail(n, -1, "apply_sgd: the gradient buffer must be 16-byte aligned");
-        hipLaunchKernelGGL(k_sgd_apply, dim3(grid1d(n->n_pad / 4, 256)), dim3(256), 0, n->stream, (float*)n->params.p, grad, grad_scale, lr, sgd_params(n), n->n_pad);
-        XTRY(n, hipGetLastError());
-    }
-    RTRY(apply_ema(n));
-    return refresh_flipped(n);
-}
-
-int rcn_hipx_set_clip(rcn_hipx_net* n, float max_norm) {
-    if (!n) return -1;
-    if (!(max_norm >= 0.f)) return fail(n, -1, "set_clip: max_norm must be 0 (off) or > 0 (+inf: measure only)");
-    if (max_norm == 0.f) max_norm = 0.f;                // (-0)
-    if (max_norm == n->clip_max) return 0;
-    Dev g(n->device);
-    XTRY(n, hipStreamSynchronize(n->stream));
-    if (max_norm != 0.f && !n->clip_state.p) {
-        // once, outside any capture: captured graphs hold these pointers, so the buffers never move afterwards
-        XTRY(n, n->clip_grad.ensure((size_t)n->n_pad * sizeof(float)));
-        XTRY(n, n->clip_part.ensure((size_t)clip_blocks(n->n_pad) * sizeof(double)));
-        XTRY(n, n->clip_state.ensure(sizeof(unsigned long long) + 2 * sizeof(float)));
-        XTRY(n, hipMemsetAsync(n->clip_grad.p, 0, n->clip_grad.cap, n->stream));
-        XTRY(n, hipMemsetAsync(n->clip_part.p, 0, n->clip_part.cap, n->stream));
-        XTRY(n, hipMemsetAsync(n->clip_state.p, 0, n->clip_state.cap, n->stream));
-        XTRY(n, hipStreamSynchronize(n->stream));
-    }
-    drop_graphs(n);                                     // captured graphs bake in the update's launches and their arguments
-    n->clip_max = max_norm;
-    return 0;
-}
-
-int rcn_hipx_get_clip(const rcn_hipx_net* n, float* max_norm) {
-    if (!n) return -1;
-    if (max_norm) *max_norm = n->clip_max;
-    return 0;
-}
-
-int rcn_hipx_set_accumulate(rcn_hipx_net* n, int k) {
-    if (!n) return -1;
-    if (k < 1 || k > 65536) return fail(n, -1, "set_accumulate: k must be in 1 .. 65536");
-    if (k == n->accum_k) return 0;
-    Dev g(n->device);
-    XTRY(n, hipStreamSynchronize(n->stream));
-    if (k > 1 && !n->accum.p) {
-        // once, outside any capture: captured graphs hold this pointer, so the buffer never moves afterwards.  The memset stays although a
-        // cycle's first micro-step stores: k_grad_sumsq and rcn_hipx_get_accumulated read all n_pad floats, so any element outside the
-        // reduction jobs' [W | b] ranges has to be zero, and a read before the first micro-step has to be defined.
-        XTRY(n, n->accum.ensure((size_t)n->n_pad * sizeof(float)));
-        XTRY(n, hipMemsetAsync(n->accum.p, 0, n->accum.cap, n->stream));
-        XTRY(n, hipStreamSynchronize(n->stream));
-    }
-    drop_graphs(n);                                     // captured graphs bake in the reduction's launches and their arguments
-    n->accum_k = k; n->accum_c = 1.0f / (float)k; n->accum_pos = 0;      // (a pending cycle is discarded: the next micro-step is a first one and stores)
-    return 0;
-}
-
-int rcn_hipx_get_accumulate(const rcn_hipx_net* n, int* k, int* pending) {
-    if (!n) return -1;
-    if (k) *k = n->accum_k;
-    if (pending) *pending = n->accum_pos;
-    return 0;
-}
-
-int rcn_hipx_reset_accumulation(rcn_hipx_net* n) {
-    if (!n) return -1;
-    n->accum_pos = 0;                                   // host state only: the next micro-step is a first one and stores
-    return 0;
-}
-
-int rcn_hipx_get_accumulated(rcn_hipx_net* n, float* flat) {
-    if (!n || !flat) return -1;
-    if (!n->accum.p) return fail(n, -6, "get_accumulated: accumulation was never switched on (rcn_hipx_set_accumulate with k > 1 first)");
-    Dev g(n->device);
-    return unpad(n, (const float*)n->accum.p, flat);
-}
-
-int rcn_hipx_get_grad_norm(rcn_hipx_net* n, float* norm, float* coef) {
-    if (!n) return -1;
-    if (!n->clip_state.p) return fail(n, -6, "get_grad_norm: clipping was never switched on (rcn_hipx_set_clip with a max_norm > 0 first)");
-    Dev g(n->device);
-    float pair[2] = {0.f, 0.f};
-    XTRY(n, hipMemcpyAsync(pair, (const char*)n->clip_state.p + sizeof(unsigned long long), sizeof pair, hipMemcpyDeviceToHost, n->stream));
-    XTRY(n, hipStreamSynchronize(n->stream));
-    if (norm) *norm = pair[0];
-    if (coef) *coef = pair[1];
-    return 0;
-}
-
-int rcn_hipx_set_grad_norm_log(rcn_hipx_net* n, float* log_dev, int64_t cap) {
-    if (!n) return -1;
-    if (log_dev && cap < 1) return fail(n, -1, "set_grad_norm_log: a log needs cap >= 1");
-    Dev g(n->device);
-    XTRY(n, hipStreamSynchronize(n->stream));
-    if (n->clip_state.p) {                              // (none yet: the counter starts at zero when rcn_hipx_set_clip makes it)
-        XTRY(n, hipMemsetAsync(n->clip_state.p, 0, sizeof(unsigned long long), n->stream));
-        XTRY(n, hipStreamSynchronize(n->stream));
-    }
-    drop_graphs(n);                                     // the pointer is a kernel argument
-    n->clip_log = log_dev; n->clip_log_cap = log_dev ? (long long)cap : 0;
-    return 0;
-}
-
-int rcn_hipx_get_grad_norm_count(rcn_hipx_net* n, int64_t* count) {
-    if (!n || !count) return -1;
-    Dev g(n->device);
-    unsigned long long c = 0;
-    if (n->clip_state.p) XTRY(n, hipMemcpyAsync(&c, n->clip_state.p, sizeof c, hipMemcpyDeviceToHost, n->stream));
-    XTRY(n, hipStreamSynchronize(n->stream));
-    *count = (int64_t)c;
-    return 0;
-}
-
-int rcn_hipx_grad_norm_dev(rcn_hipx_net* n, const float* g_dev, int64_t len, float scale, float* norm_dev) {
-    if (!n) return -1;
-    if (!norm_dev || len < 0 || len % 4 != 0 || (len > 0 && (!g_dev || (uintptr_t)g_dev % 16 != 0)))
-        return fail(n, -1, "grad_norm: n >= 0, n % 4 == 0, a 16-byte aligned buffer and a device float for the norm");
-    Dev g(n->device);
-    const long long nblk = clip_blocks((long long)len);
-    if (nblk > 0x7fffffffLL) return fail(n, -1, "grad_norm: more than 2^43 elements");
-    XTRY(n, n->norm_part.ensure((size_t)(nblk > 0 ? nblk : 1) * sizeof(double)));
-    launch_sumsq(n, g_dev, (long long)len, scale, (double*)n->norm_part.p);
-    XTRY(n, hipGetLastError());
-    hipLaunchKernelGGL(k_grad_norm_finish, dim3(1), dim3(kClipThreads), 0, n->stream, (const double*)n->norm_part.p, (int)nblk, norm_dev);
-    XTRY(n, hipGetLastError());
-    return 0;
-}
-
 int rcn_hipx_step_flops(const rcn_hipx_net* n, int B, double* flops) {
     if (!n || !flops) return -1;
     double f = 0;
@@ -1978,3 +1544,5 @@ int rcn_hipx_plan_eval_net(const rcn_hipx_net* n, int batch, char* out, int cap)
 }
 
 }  // extern "C"
+
+#include "rcn_hipx_api_update.ipp"
