@@ -2,22 +2,11 @@
 batch built from tests/_recipe_ref.py's augmented rows with one np.float32 operation per rounding, the dense soft target, and the oracle's
 loss and backward walk (oracle/convnet_oracle.py) restated from d = (p - T) / B for a dense target matrix T.  Nothing here calls the library.
 tests/test_convnet_mix_plan.py pins soft_loss_and_grads to the oracle bit for bit (one-hot T) and to finite differences (soft T)."""
-import os
-import sys
-
 import numpy as np
+from _convnet_util import CIFAR, FUSED_HEAD, ODD_WIDTH, PLAIN_HEAD, POOL_PAIRS  # noqa: F401  (the nets: its importers take them from here too)
+from _recipe_ref import augment_ref
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from _recipe_ref import augment_ref  # noqa: E402
-
-from oracle import convnet_oracle as co  # noqa: E402
-
-# the nets of tests/test_gpu_convnet_recipe.py: (input shape, layers, batch)
-FUSED_HEAD = ((8, 8, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 32), ("dense", 10)), 5)
-PLAIN_HEAD = ((6, 6, 1), (("conv", 32), ("conv", 32), ("pool",), ("dense", 7)), 3)
-POOL_PAIRS = ((16, 16, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 128), ("dense", 10)), 64)
-ODD_WIDTH = ((5, 7, 1), (("conv", 32), ("dense", 6)), 4)
-CIFAR = ((32, 32, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("conv", 128), ("pool",), ("dense_relu", 256), ("dense", 10)), 512)
+from oracle import convnet_oracle as co
 
 
 def mix_rows(a, rec):

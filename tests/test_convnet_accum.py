@@ -2,23 +2,16 @@
 equal micro-batch's MEAN loss scaled by 1 / k (the f64 oracle's identity with the concatenated batch), the NumPy restatement the GPU tests
 compare with (tests/_accum_ref.py) and its edge cases, and the new entry points exist, are bound and refuse a null net without a GPU."""
 import ctypes as C
-import os
 import re
-import sys
 
 import numpy as np
 import pytest
+from _accum_ref import accumulate, scale_of
+from _convnet_util import FUSED_HEAD, HEADER, libx  # noqa: F401  (libx: a fixture)
 
 from oracle import convnet_oracle as co
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-from _accum_ref import accumulate, scale_of  # noqa: E402
-
 NEW = ["rcn_hipx_set_accumulate", "rcn_hipx_get_accumulate", "rcn_hipx_reset_accumulation", "rcn_hipx_get_accumulated", "rcn_hipx_plan_micro_net"]
-FUSED_HEAD = ((8, 8, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 32), ("dense", 10)), 5)
 
 
 @pytest.mark.parametrize("k", [2, 3])
@@ -73,13 +66,6 @@ def test_the_scale_goes_in_per_micro_batch_not_at_the_end():
     assert np.array_equal(accumulate(g[:2], 2), (np.float32(0.5) * g[0]) + (np.float32(0.5) * g[1]))
 
 
-@pytest.fixture(scope="module")
-def libx():
-    from mercer_research_amd import build as hipbuild, convnet
-    hipbuild.build_x()
-    return convnet.load()
-
-
 def test_null_net_is_refused_without_a_gpu(libx):
     k, pending = C.c_int(9), C.c_int(7)
     for v in (0, 1, 2, 65536, 65537, -1):
@@ -95,7 +81,7 @@ def test_null_net_is_refused_without_a_gpu(libx):
 
 def test_header_declares_the_entries_and_the_binding_table_has_them(libx):
     from mercer_research_amd import convnet
-    raw_text = open(os.path.join(ROOT, "include", "rcn_hipx.h")).read()
+    raw_text = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", raw_text, flags=re.S)
     declared = set(re.findall(r"\b(rcn_hipx_[a-z0-9_]+)\s*\(", text))
     raw = C.CDLL(convnet.LIBX_PATH)

@@ -2,18 +2,12 @@
 compare with (tests/_clip_ref.py) is torch.nn.utils.clip_grad_norm_ on float64 tensors, its edge cases, and the new entry points exist, are
 bound and refuse a null net without a GPU."""
 import ctypes as C
-import os
 import re
-import sys
 
 import numpy as np
 import pytest
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-from _clip_ref import apply_coef, clip, clip_coef, grad_norm, grad_sumsq, plain_update  # noqa: E402
+from _clip_ref import apply_coef, clip, clip_coef, grad_norm, grad_sumsq, plain_update
+from _convnet_util import HEADER, libx  # noqa: F401  (libx: a fixture)
 
 NEW = ["rcn_hipx_set_clip", "rcn_hipx_get_clip", "rcn_hipx_get_grad_norm", "rcn_hipx_set_grad_norm_log", "rcn_hipx_get_grad_norm_count", "rcn_hipx_grad_norm_dev"]
 SIZES = [864, 32, 18432, 64, 73728, 128, 524288, 256, 2208]      # several tensors, 620 000 elements in all
@@ -110,13 +104,6 @@ def test_plain_update_rounds_once():
     assert not np.array_equal(got, p - lr * g)
 
 
-@pytest.fixture(scope="module")
-def libx():
-    from mercer_research_amd import build as hipbuild, convnet
-    hipbuild.build_x()
-    return convnet.load()
-
-
 def test_null_net_is_refused_without_a_gpu(libx):
     a, b = C.c_float(9.0), C.c_float(7.0)
     cnt = C.c_int64(5)
@@ -132,7 +119,7 @@ def test_null_net_is_refused_without_a_gpu(libx):
 
 def test_header_declares_the_entries_and_the_binding_table_has_them(libx):
     from mercer_research_amd import convnet
-    raw_text = open(os.path.join(ROOT, "include", "rcn_hipx.h")).read()
+    raw_text = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", raw_text, flags=re.S)
     declared = set(re.findall(r"\b(rcn_hipx_[a-z0-9_]+)\s*\(", text))
     raw = C.CDLL(convnet.LIBX_PATH)

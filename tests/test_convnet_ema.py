@@ -2,18 +2,12 @@
 with is torch.optim.swa_utils.AveragedModel's EMA, it rounds every operation in float32, and the new entry points exist, are bound and
 refuse a null net without a GPU."""
 import ctypes as C
-import os
 import re
-import sys
 
 import numpy as np
 import pytest
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-from _ema_ref import ema_update  # noqa: E402
+from _ema_ref import ema_update
+from _convnet_util import HEADER, libx  # noqa: F401  (libx: a fixture)
 
 NEW = ["rcn_hipx_set_ema", "rcn_hipx_get_ema", "rcn_hipx_get_ema_params", "rcn_hipx_set_ema_params", "rcn_hipx_reset_ema", "rcn_hipx_evaluate_ex_dev"]
 
@@ -69,13 +63,6 @@ def test_restatement_rounds_every_operation_in_float32():
     assert not np.array_equal(ema_update(e2, p2, 0.999), dbl)
 
 
-@pytest.fixture(scope="module")
-def libx():
-    from mercer_research_amd import build as hipbuild, convnet
-    hipbuild.build_x()
-    return convnet.load()
-
-
 def test_null_net_is_refused_without_a_gpu(libx):
     flat = (C.c_float * 4)(1.0, 2.0, 3.0, 4.0)
     d = C.c_float(9.0)
@@ -90,7 +77,7 @@ def test_null_net_is_refused_without_a_gpu(libx):
 
 def test_header_declares_the_average_and_the_binding_table_has_it(libx):
     from mercer_research_amd import convnet
-    raw_text = open(os.path.join(ROOT, "include", "rcn_hipx.h")).read()
+    raw_text = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", raw_text, flags=re.S)
     declared = set(re.findall(r"\b(rcn_hipx_[a-z0-9_]+)\s*\(", text))
     raw = C.CDLL(convnet.LIBX_PATH)

@@ -5,21 +5,11 @@ import ctypes as C
 import re
 
 import pytest
+from _convnet_util import convnet_built, plan_lines  # noqa: F401  (convnet_built: the fixture `convnet`)
 
 from bench_convnet import CONFIGS
 
 PRECISIONS = ("fp32", "bf16", "bf16_stored")
-
-
-@pytest.fixture(scope="module")
-def convnet():
-    from mercer_research_amd import build as hipbuild, convnet
-    hipbuild.build_x()
-    return convnet
-
-
-def _lines(text):
-    return [l.strip() for l in text.splitlines()[1:] if l.strip()]
 
 
 def _forward_part(lines):
@@ -35,12 +25,12 @@ def _forward_part(lines):
 def test_evaluation_runs_the_training_plans_forward_launches_and_one_eval_kernel(convnet, config, precision):
     shp, layers, B = CONFIGS[config]
     try:
-        train = _lines(convnet.plan(shp, layers, B, precision, "auto"))
+        train = plan_lines(convnet.plan(shp, layers, B, precision, "auto"))
     except convnet.ConvNetError as e:
         if "rcn_hipx_plan: -3" in str(e):
             pytest.skip("rcn_hipx_plan itself refuses this pair")
         raise
-    ev = _lines(convnet.plan_eval(shp, layers, B, precision, "auto"))
+    ev = plan_lines(convnet.plan_eval(shp, layers, B, precision, "auto"))
     keep = lambda ls: [l for l in ls if l.startswith("conv3x3") or l.startswith("pool")]
     assert keep(ev) == keep(_forward_part(train)) and len(keep(ev)) >= 2
     if precision != "fp32":
@@ -59,7 +49,7 @@ def test_evaluation_runs_the_training_plans_forward_launches_and_one_eval_kernel
 def test_eval_workgroups_follow_the_batch(convnet):
     shp, layers, _ = CONFIGS["mnist"]
     for B in (1, 8, 9, 4096):
-        last = _lines(convnet.plan_eval(shp, layers, B, "fp32", "auto"))[-1]
+        last = plan_lines(convnet.plan_eval(shp, layers, B, "fp32", "auto"))[-1]
         assert f"k_eval_ce, {(B + 7) // 8} workgroups" in last, last
 
 

@@ -3,24 +3,13 @@ rcn_hipx_mix_step): the record's layout, mix_plan's draws, the refusals of the n
 restatement the GPU comparisons rest on (tests/_mix_ref.py) -- bit for bit against oracle/convnet_oracle.py for a one-hot target, and
 against central finite differences for a soft one."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
+from _convnet_util import FUSED_HEAD, PLAIN_HEAD, convnet_loaded, oracle_params  # noqa: F401  (convnet_loaded: the fixture `convnet`)
+from _mix_ref import soft_loss_and_grads, soft_loss_f64, soft_targets
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from _mix_ref import FUSED_HEAD, PLAIN_HEAD, soft_loss_and_grads, soft_loss_f64, soft_targets  # noqa: E402
-
-from oracle import convnet_oracle as co  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def convnet():
-    from mercer_research_amd import build as hipbuild, convnet
-    hipbuild.build_x()
-    convnet.load()
-    return convnet
+from oracle import convnet_oracle as co
 
 
 def test_mix_step_is_the_headers_24_bytes(convnet):
@@ -81,19 +70,12 @@ def test_new_entry_points_refuse_null_nets_and_touch_nothing(convnet):
     assert lib.rcn_hipx_plan_epoch_mix_net(None, 1, 1, 1, C.byref(a), 0, buf, len(buf)) == -1 and buf.value == b"untouched"
 
 
-def _params(rng, in_shape, layers):
-    shapes = co.param_shapes(in_shape, layers)
-    ws = [rng.standard_normal(k) * np.sqrt(2.0 / k[0]) for k, _ in shapes]
-    bs = [rng.standard_normal(n) * 0.1 for _, n in shapes]
-    return ws, bs
-
-
 @pytest.mark.parametrize("operand,stored", [("f64", False), ("bf16", False), ("bf16", True)], ids=["f64", "bf16", "bf16_stored"])
 @pytest.mark.parametrize("spec", [FUSED_HEAD, PLAIN_HEAD], ids=["fused_head", "plain_head"])
 def test_restatement_with_a_one_hot_target_is_the_oracle_bit_for_bit(spec, operand, stored):
     in_shape, layers, B = spec
     rng = np.random.default_rng(11)
-    ws, bs = _params(rng, in_shape, layers)
+    ws, bs = oracle_params(rng, in_shape, layers)[:2]
     x = rng.standard_normal((B,) + in_shape)
     y = rng.integers(0, layers[-1][1], B)
     want = co.loss_and_grads(x, y, ws, bs, layers, operand, stored)

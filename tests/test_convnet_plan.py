@@ -4,6 +4,7 @@ tests' business (tests/test_gpu_convnet*.py)."""
 import re
 
 import pytest
+from _convnet_util import plan_lines
 
 from bench_convnet import CONFIGS
 
@@ -15,13 +16,9 @@ def plan():
     return convnet.plan
 
 
-def _lines(text):
-    return [l.strip() for l in text.splitlines()[1:] if l.strip()]
-
-
 def test_cifar_fp32_step_runs_on_the_lds_tiled_kernels_with_pooling_fused_both_ways(plan):
     shp, layers, B = CONFIGS["cifar"]
-    L = _lines(plan(shp, layers, B, "fp32", "auto"))
+    L = plan_lines(plan(shp, layers, B, "fp32", "auto"))
     assert L[0].startswith("conv3x3 32x32x3->32 epi 4: k_conv1_fwd_f32<3, 16>")                # first layer, pool fused into its epilogue
     assert L[1].startswith("conv3x3 16x16x32->64 epi 4: k_conv3x3_halo_f32<16, 64>, 1024 items")
     assert L[2].startswith("conv3x3 8x8x64->128 epi 4: k_conv3x3_halo_f32<8, 64>")              # 8-wide maps: two images per block
@@ -36,7 +33,7 @@ def test_cifar_fp32_step_runs_on_the_lds_tiled_kernels_with_pooling_fused_both_w
 
 def test_gemm_tiling_keeps_every_layer_on_the_implicit_gemm_kernels(plan):
     shp, layers, B = CONFIGS["cifar"]
-    L = _lines(plan(shp, layers, B, "fp32", "gemm"))
+    L = plan_lines(plan(shp, layers, B, "fp32", "gemm"))
     assert not any(re.search(r"halo|k_conv1_|k_head_f32", l) for l in L)
     assert sum("k_pool_fwd" in l for l in L) == 3 and sum("k_pool_bwd" in l for l in L) == 3
     assert any("k_softmax_ce" in l for l in L)
@@ -44,7 +41,7 @@ def test_gemm_tiling_keeps_every_layer_on_the_implicit_gemm_kernels(plan):
 
 def test_bf16_mode_keeps_the_first_layer_and_the_head_on_fp32_kernels(plan):
     shp, layers, B = CONFIGS["mnist"]
-    L = _lines(plan(shp, layers, 4096, "bf16", "auto"))                                           # BASELINE configs[4]
+    L = plan_lines(plan(shp, layers, 4096, "bf16", "auto"))                                           # BASELINE configs[4]
     assert L[0].startswith("bf16 operand copies") and "k_prep_all_bf16" in L[0]
     assert L[1].startswith("conv3x3 28x28x1->32 epi 4: k_conv1_fwd_f32<1, 16>")
     assert any("k_head_f32" in l for l in L) and any(l.startswith("wgrad conv3x3 28x28x1->32 pooled-dZ: k_conv1_wgrad_f32<1, 16>") for l in L)
@@ -53,7 +50,7 @@ def test_bf16_mode_keeps_the_first_layer_and_the_head_on_fp32_kernels(plan):
 
 def test_synth224_bf16_uses_the_resident_weights_form_only_for_the_32_channel_32_wide_layer(plan):
     shp, layers, B = CONFIGS["synth224"]
-    L = _lines(plan(shp, layers, B, "bf16", "auto"))
+    L = plan_lines(plan(shp, layers, B, "bf16", "auto"))
     one_cb = [l for l in L if "k_conv3x3_halo_bf16_1cb<32>" in l]
     assert len(one_cb) == 2 and all("224x224x32->32" in l for l in one_cb)                         # its forward and its input gradient
     assert any(l.startswith("conv3x3 112x112x32->64 epi 2: k_conv3x3_halo_bf16p") for l in L)      # 64-wide tile: the pipelined form
@@ -79,16 +76,16 @@ def test_dense_weight_gradients_are_sized_by_waves(plan):
     """A wave of the generic weight-gradient kernels owns one 32-row k-block x bn columns over a chunk: the dense layer behind a pooled map is
     few waves.  Below two waves per SIMD the column blocks are 32 wide, below one per SIMD (bf16 kernel) the chunks shorten too."""
     shp, layers, _ = CONFIGS["mnist"]
-    L = _lines(plan(shp, layers, 4096, "bf16", "auto"))
+    L = plan_lines(plan(shp, layers, 4096, "bf16", "auto"))
     assert any(l.startswith("wgrad dense 1x1x3136->128: k_conv_wgrad_bf16<1, 32, 2>, 4 chunks") for l in L)      # 98 x 4 x 4 = 1568 waves, chunks of 1024 kept
     shp, layers, B = CONFIGS["cifar"]
-    L = _lines(plan(shp, layers, B, "bf16", "auto"))
+    L = plan_lines(plan(shp, layers, B, "bf16", "auto"))
     assert any(l.startswith("wgrad dense 1x1x2048->256: k_conv_wgrad_bf16<1, 32, 4>, 2 chunks") for l in L)      # 64 x 8 x 1 = 512 waves -> chunks of 256
-    L = _lines(plan(shp, layers, B, "fp32", "auto"))
+    L = plan_lines(plan(shp, layers, B, "fp32", "auto"))
     assert any(l.startswith("wgrad dense 1x1x2048->256: k_conv_wgrad<1, tile, 32>, 1 chunks") for l in L)
     # a large layer keeps the 64-wide blocks: synth-224's convolutions never reach this kernel, its dense layer has 32 padded columns anyway
     shp, layers, B = CONFIGS["synth224"]
-    assert not any("k_conv_wgrad_bf16<3" in l for l in _lines(plan(shp, layers, B, "bf16", "auto")))
+    assert not any("k_conv_wgrad_bf16<3" in l for l in plan_lines(plan(shp, layers, B, "bf16", "auto")))
 
 
 def test_bucket_plan_cuts_the_gradient_into_contiguous_slices_in_backward_order(plan):

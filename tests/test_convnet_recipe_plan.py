@@ -3,22 +3,11 @@ rcn_hipx_augment_draw -- the host side of the one function k_gather_aug runs -- 
 restatement of the formula, the warm-up + cosine schedule, and the refusals of the new entry points.  rcn_hipx_plan_epoch_net walks an
 EXISTING net, which only a GPU machine can create: its lines are held in tests/test_gpu_convnet_recipe.py."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
-
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from _recipe_ref import M64, draw_ref  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def convnet():
-    from mercer_research_amd import build as hipbuild, convnet
-    hipbuild.build_x()
-    convnet.load()
-    return convnet
+from _convnet_util import convnet_loaded  # noqa: F401  (the fixture `convnet`)
+from _recipe_ref import M64, draw_ref
 
 
 def _draws(convnet, pad, hflip, seed, epoch, q0, count):

@@ -1,18 +1,12 @@
 """CPU checks of the Track-X optimiser (include/rcn_hipx.h, rcn_hipx_set_sgd): the NumPy restatement the GPU tests compare with is
 torch.optim.SGD's update, and the new entry points exist, are bound and refuse a null net without a GPU."""
 import ctypes as C
-import os
 import re
-import sys
 
 import numpy as np
 import pytest
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-from _sgd_ref import sgd_update  # noqa: E402
+from _sgd_ref import sgd_update
+from _convnet_util import HEADER, libx  # noqa: F401  (libx: a fixture)
 
 NEW = ["rcn_hipx_set_sgd", "rcn_hipx_get_sgd", "rcn_hipx_get_velocity", "rcn_hipx_set_velocity", "rcn_hipx_reset_velocity", "rcn_hipx_apply_sgd_dev"]
 
@@ -52,13 +46,6 @@ def test_restatement_rounds_every_operation_in_float32():
     assert np.array_equal(nv, vv) and np.array_equal(np_, p - f(0.1) * d)
 
 
-@pytest.fixture(scope="module")
-def libx():
-    from mercer_research_amd import build as hipbuild, convnet
-    hipbuild.build_x()
-    return convnet.load()
-
-
 def test_null_net_is_refused_without_a_gpu(libx):
     flat = (C.c_float * 4)()
     mu, wd, nest = C.c_float(), C.c_float(), C.c_int()
@@ -72,7 +59,7 @@ def test_null_net_is_refused_without_a_gpu(libx):
 
 def test_header_declares_the_optimiser_and_the_binding_table_has_it(libx):
     from mercer_research_amd import convnet
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rcn_hipx.h")).read(), flags=re.S)
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     declared = set(re.findall(r"\b(rcn_hipx_[a-z0-9_]+)\s*\(", text))
     raw = C.CDLL(convnet.LIBX_PATH)
     for name in NEW:

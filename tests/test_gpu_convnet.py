@@ -2,21 +2,11 @@
 No reference counterpart exists ("parity unpinned"); tolerance: fp32 MFMA vs f64, |d| <= 2e-4 * scale + 1e-6."""
 import numpy as np
 import pytest
+from _convnet_util import close, make_net
 
 from oracle import convnet_oracle as co
 
 pytestmark = pytest.mark.gpu
-
-
-def _net(in_shape, layers, B):
-    from mercer_research_amd.convnet import ConvNet
-    return ConvNet(in_shape, layers, B)
-
-
-def _close(a, b, rtol=2e-4):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    scale = max(1e-3, float(np.abs(b).max()))
-    assert np.abs(a - b).max() <= rtol * scale + 1e-6, (float(np.abs(a - b).max()), scale)
 
 
 @pytest.mark.parametrize("in_shape,layers,B", [
@@ -30,7 +20,7 @@ def _close(a, b, rtol=2e-4):
 ])
 def test_forward_gradients_and_step_match_oracle(in_shape, layers, B):
     rng = np.random.default_rng(B)
-    net = _net(in_shape, layers, B)
+    net = make_net((in_shape, layers, B), precision=None)
     shapes = co.param_shapes(in_shape, layers)
     ws = [rng.standard_normal(k) * np.sqrt(2.0 / k[0]) for k, _ in shapes]
     bs = [rng.standard_normal(n) * 0.1 for _, n in shapes]
@@ -52,21 +42,21 @@ def test_forward_gradients_and_step_match_oracle(in_shape, layers, B):
         loss = torch.zeros(1, dtype=torch.float32, device=net.device)
         grad = net.gradients(xd, yd, loss=loss)
     net.synchronize()
-    _close(logits.cpu().numpy(), logits_ref)
+    close(logits.cpu().numpy(), logits_ref)
     assert abs(loss.item() - loss_ref) <= 2e-4 * max(1.0, loss_ref)
-    _close(net.unpad(grad), co.flatten(gws, gbs))
+    close(net.unpad(grad), co.flatten(gws, gbs))
     # one SGD step (eager first call, then the cached graph for the second)
     lr = 0.05
     with torch.cuda.stream(net.stream):
         net.train_step(xd, yd, lr, loss)
     net.synchronize()
     nw, nb, _ = co.sgd_step(x64, y, w32, b32, layers, lr)
-    _close(net.get_params(), co.flatten(nw, nb))
+    close(net.get_params(), co.flatten(nw, nb))
     with torch.cuda.stream(net.stream):
         net.train_step(xd, yd, lr, loss)            # graph replay
     net.synchronize()
     nw2, nb2, l2 = co.sgd_step(x64, y, nw, nb, layers, lr)
-    _close(net.get_params(), co.flatten(nw2, nb2), rtol=4e-4)
+    close(net.get_params(), co.flatten(nw2, nb2), rtol=4e-4)
     assert abs(loss.item() - l2) <= 4e-4 * max(1.0, l2)
     # data-parallel halves: apply(gradients) == train_step
     net.set_params(flat)
@@ -74,7 +64,7 @@ def test_forward_gradients_and_step_match_oracle(in_shape, layers, B):
         g = net.gradients(xd, yd)
         net.apply(g, lr)
     net.synchronize()
-    _close(net.get_params(), co.flatten(nw, nb))
+    close(net.get_params(), co.flatten(nw, nb))
 
 
 @pytest.mark.parametrize("in_shape,layers,B", [
@@ -93,7 +83,7 @@ def test_bf16_mfma_path_matches_bf16_operand_oracle(in_shape, layers, B):
     within 3e-2 (the price of 8-bit mantissas), and switching back to fp32 restores the 2e-4 agreement."""
     import torch
     rng = np.random.default_rng(B + 1)
-    net = _net(in_shape, layers, B)
+    net = make_net((in_shape, layers, B), precision=None)
     shapes = co.param_shapes(in_shape, layers)
     ws = [rng.standard_normal(k) * np.sqrt(2.0 / k[0]) for k, _ in shapes]
     bs = [rng.standard_normal(n) * 0.1 for _, n in shapes]
@@ -113,16 +103,16 @@ def test_bf16_mfma_path_matches_bf16_operand_oracle(in_shape, layers, B):
         loss = torch.zeros(1, dtype=torch.float32, device=net.device)
         grad = net.gradients(xd, yd, loss=loss)
     net.synchronize()
-    _close(logits.cpu().numpy(), logits_ref, rtol=5e-3)
-    _close(logits.cpu().numpy(), logits_f64, rtol=3e-2)
+    close(logits.cpu().numpy(), logits_ref, rtol=5e-3)
+    close(logits.cpu().numpy(), logits_f64, rtol=3e-2)
     assert abs(loss.item() - loss_ref) <= 5e-3 * max(1.0, loss_ref)
-    _close(net.unpad(grad), co.flatten(gws, gbs), rtol=5e-3)
+    close(net.unpad(grad), co.flatten(gws, gbs), rtol=5e-3)
     # it really is a different arithmetic: not bit-equal to the fp32 path, which still holds its own tolerance
     net.set_precision("fp32")
     with torch.cuda.stream(net.stream):
         logits32 = net.forward(xd)
     net.synchronize()
-    _close(logits32.cpu().numpy(), logits_f64)
+    close(logits32.cpu().numpy(), logits_f64)
     assert not np.array_equal(logits32.cpu().numpy(), logits.cpu().numpy())
     # two training steps in bf16 mode (eager, then the cached graph) follow the bf16-operand oracle's steps
     net.set_precision("bf16")
@@ -133,7 +123,7 @@ def test_bf16_mfma_path_matches_bf16_operand_oracle(in_shape, layers, B):
     nw, nb, _ = co.sgd_step(x64, y, w32, b32, layers, 0.05, operand="bf16")
     nw, nb, _ = co.sgd_step(x64, y, nw, nb, layers, 0.05, operand="bf16")
     # second step: operands that round the other way after step one move a few weights by a bf16 ulp of their gradient; 2e-2 of scale
-    _close(net.get_params(), co.flatten(nw, nb), rtol=2e-2)
+    close(net.get_params(), co.flatten(nw, nb), rtol=2e-2)
 
 
 def test_cached_step_graphs_survive_scratch_growth():
@@ -143,7 +133,7 @@ def test_cached_step_graphs_survive_scratch_growth():
     in_shape = (8, 8, 3)
     layers = (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 32), ("dense", 10))
     rng = np.random.default_rng(44)
-    net = _net(in_shape, layers, 48)
+    net = make_net((in_shape, layers, 48), precision=None)
     shapes = co.param_shapes(in_shape, layers)
     ws = [rng.standard_normal(k) * np.sqrt(2.0 / k[0]) for k, _ in shapes]
     bs = [rng.standard_normal(n) * 0.1 for _, n in shapes]
@@ -162,7 +152,7 @@ def test_cached_step_graphs_survive_scratch_growth():
             net.train_step(xd, yd, 0.05, loss)
         w, b, _ = co.sgd_step(x.astype(np.float64), y, w, b, layers, 0.05)
     net.synchronize()
-    _close(net.get_params(), co.flatten(w, b), rtol=1e-3)
+    close(net.get_params(), co.flatten(w, b), rtol=1e-3)
 
 
 def test_training_reduces_loss_on_cifar_shape():
@@ -170,7 +160,7 @@ def test_training_reduces_loss_on_cifar_shape():
     import torch
     layers = (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("conv", 128), ("pool",), ("dense_relu", 256), ("dense", 10))
     B = 64
-    net = _net((32, 32, 3), layers, B)
+    net = make_net(((32, 32, 3), layers, B), precision=None)
     net.init_params(3)
     rng = np.random.default_rng(0)
     protos = rng.standard_normal((10, 32, 32, 3)).astype(np.float32)
@@ -192,8 +182,8 @@ def test_training_reduces_loss_on_cifar_shape():
 def test_unsupported_shapes_are_rejected():
     from mercer_research_amd.convnet import ConvNetError
     with pytest.raises(ConvNetError):
-        _net((8, 8, 3), (("conv", 30), ("dense", 10)), 4)            # channels not a multiple of 32
+        make_net(((8, 8, 3), (("conv", 30), ("dense", 10)), 4), precision=None)            # channels not a multiple of 32
     with pytest.raises(ConvNetError):
-        _net((7, 8, 3), (("conv", 32), ("pool",), ("dense", 10)), 4)   # odd height under the pool
+        make_net(((7, 8, 3), (("conv", 32), ("pool",), ("dense", 10)), 4), precision=None)   # odd height under the pool
     with pytest.raises(ConvNetError):
-        _net((8, 8, 3), (("conv", 32), ("pool",), ("dense_relu", 32)), 4)   # no logits layer
+        make_net(((8, 8, 3), (("conv", 32), ("pool",), ("dense_relu", 32)), 4), precision=None)   # no logits layer

@@ -6,103 +6,26 @@ The twin-net method of tests/test_gpu_convnet_clip.py: net A takes the library's
 micro-batch at the same parameters (the same kernels and sums as the step); the host applies tests/_accum_ref.py, then _clip_ref, then
 _sgd_ref.sgd_update / _clip_ref.plain_update and _ema_ref.ema_update.  Every micro-batch of a cycle holds different data: a step that
 re-read one batch would otherwise pass."""
-import os
-import sys
-
 import numpy as np
 import pytest
+from _accum_ref import accumulate, scale_of
+from _clip_ref import apply_coef, grad_norm, plain_update
+from _convnet_util import (FUSED_HEAD, INF, NESTEROV, PLAIN, PLAIN_HEAD, POOL_PAIRS, batch, batches_by_seed, bits, check_norm, close, epoch, grad, make_net,
+                           same_bits, same_state, step, twins)
+from _ema_ref import ema_update
+from _sgd_ref import sgd_update
 
 from oracle import convnet_oracle as co
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-from _accum_ref import accumulate, scale_of  # noqa: E402
-from _clip_ref import apply_coef, clip_coef, grad_norm, plain_update  # noqa: E402
-from _ema_ref import ema_update  # noqa: E402
-from _sgd_ref import sgd_update  # noqa: E402
-
 pytestmark = pytest.mark.gpu
 
-FUSED_HEAD = ((8, 8, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 32), ("dense", 10)), 5)
-PLAIN_HEAD = ((6, 6, 1), (("conv", 32), ("conv", 32), ("pool",), ("dense", 7)), 3)
-POOL_PAIRS = ((16, 16, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 128), ("dense", 10)), 64)
-MU, WD = 0.9, 5e-4
 LRS = [0.05, 0.05, 0.02]                                # three cycles: eager, replays, a second graph of the last kind
 IGNORED = 1e3                                           # the rate handed to micro-steps that apply no update
-INF = float("inf")
-DEFAULT = (0.0, 0.0, False)                             # rcn_hipx_set_sgd's default: plain SGD
-NESTEROV = (MU, WD, True)
-
-
-def _net(spec, precision="fp32"):
-    from mercer_research_amd.convnet import ConvNet
-    in_shape, layers, B = spec
-    net = ConvNet(in_shape, layers, B)
-    net.set_precision(precision)
-    return net
-
-
-def _twins(spec, precision, count=2, seed=1):
-    nets = [_net(spec, precision)]
-    nets[0].init_params(seed)
-    for _ in range(count - 1):
-        nets.append(_net(spec, precision))
-        nets[-1].set_params(nets[0].get_params())
-    return nets
-
-
-def _batch(net, spec, seed=0):
-    in_shape, layers, B = spec
-    rng = np.random.default_rng(seed)
-    x = net.to_device(rng.standard_normal((B,) + in_shape).astype(np.float32))
-    y = net.to_device(rng.integers(0, layers[-1][1], B).astype(np.int32))
-    net.synchronize()
-    return x, y
-
-
-def _batches(net, spec, k, seed=20):
-    return [_batch(net, spec, seed + j) for j in range(k)]
-
-
-def _step(net, x, y, lr, loss=None):
-    import torch
-    with torch.cuda.stream(net.stream):
-        net.train_step(x, y, lr, loss)
-    net.synchronize()
-
-
-def _grad(net, x, y, p=None):
-    """the padded gradient (device tensor, host array) of `net` at parameters p (None: its own)"""
-    import torch
-    if p is not None:
-        net.set_params(p)
-    with torch.cuda.stream(net.stream):
-        g = net.gradients(x, y)
-    net.synchronize()
-    return g, g.cpu().numpy()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _same_bits(a, b):
-    return np.array_equal(_bits(a), _bits(b))
-
-
-def _check_norm(tag, norm_dev, coef_dev, norm_ref, max_norm):
-    """as tests/test_gpu_convnet_clip.py: the device's coef is clip_coef(norm_dev, max_norm) bit for bit; norm_dev is within one float32 ulp
-    of the restatement's norm (the double square root's last bit on the device is the one thing the restatement cannot promise)"""
-    norm_dev, coef_dev = np.float32(norm_dev), np.float32(coef_dev)
-    print(f"{tag}: norm_dev {norm_dev!r} restatement {norm_ref!r} {'exact' if norm_dev == norm_ref else 'one ulp off'}; coef {coef_dev!r}")
-    assert np.array_equal(coef_dev.view(np.uint32), clip_coef(norm_dev, max_norm).view(np.uint32)), (tag, coef_dev, clip_coef(norm_dev, max_norm))
-    assert abs(float(norm_dev) - float(norm_ref)) <= float(np.spacing(norm_ref)), (tag, norm_dev, norm_ref)
 
 
 def _host_update(p, v, e, acc, lr, sgd, decay, coef=None):
     g = acc if coef is None else apply_coef(acc, coef)
-    if sgd == DEFAULT:
+    if sgd == PLAIN:
         p = plain_update(p, g, lr)
     else:
         p, v = sgd_update(p, g, v, lr, *sgd)
@@ -116,34 +39,34 @@ def _cycle(a, b, batches, k, p, lr):
     v0, e0 = a.get_velocity(), (a.get_ema() if a.get_ema_decay() else None)
     logical, padded = [], []
     for j, (x, y) in enumerate(batches):
-        gdev, gpad = _grad(b, x, y, p)
+        gdev, gpad = grad(b, x, y, p)
         logical.append(b.unpad(gdev))
         padded.append(gpad)
         assert a.get_accumulate() == (k, j)
-        _step(a, x, y, lr if j == k - 1 else IGNORED)
+        step(a, x, y, lr if j == k - 1 else IGNORED)
         assert a.get_accumulate() == (k, (j + 1) % k)
-        assert _same_bits(a.get_accumulated(), accumulate(logical, k)), (j, float(np.abs(a.get_accumulated() - accumulate(logical, k)).max()))
+        assert same_bits(a.get_accumulated(), accumulate(logical, k)), (j, float(np.abs(a.get_accumulated() - accumulate(logical, k)).max()))
         if j < k - 1:
-            assert _same_bits(a.get_params(), p), j
-            assert _same_bits(a.get_velocity(), v0), j
+            assert same_bits(a.get_params(), p), j
+            assert same_bits(a.get_velocity(), v0), j
             if e0 is not None:
-                assert _same_bits(a.get_ema(), e0), j
+                assert same_bits(a.get_ema(), e0), j
     return accumulate(logical, k), accumulate(padded, k)
 
 
 def _check_against_host(spec, precision, k, sgd, decay=0.0, clip=False):
-    a, b = _twins(spec, precision)
+    a, b = twins(spec, precision)
     a.set_sgd(*sgd)
     if decay:
         a.set_ema(decay)
     a.set_accumulate(k)
     assert a.get_accumulate() == (k, 0)
-    batches = _batches(a, spec, k)
+    batches = batches_by_seed(a, spec, k)
     p = a.get_params()
     v, e = np.zeros(a.n_logical, dtype=np.float32), p.copy()
     max_norm = None
     if clip:
-        first = accumulate([_grad(b, x, y, p)[1] for x, y in batches], k)
+        first = accumulate([grad(b, x, y, p)[1] for x, y in batches], k)
         max_norm = float(grad_norm(first) / np.float32(2))          # half the first cycle's norm of acc
         a.set_clip(max_norm)
         assert a.get_accumulate() == (k, 0)
@@ -154,14 +77,14 @@ def _check_against_host(spec, precision, k, sgd, decay=0.0, clip=False):
         coef = None
         if clip:
             norm, coef = a.grad_norm()
-            _check_norm(f"cycle {cyc}", norm, coef, grad_norm(acc_pad), max_norm)
+            check_norm(f"cycle {cyc}", norm, coef, grad_norm(acc_pad), max_norm)
             assert cyc > 0 or coef < 1.0
             assert a.grad_norm_count() == count + 1 == cyc + 1      # updates, not micro-steps
         p, v, e = _host_update(p, v, e, acc, lr, sgd, decay, coef)
-        assert _same_bits(a.get_params(), p), (cyc, float(np.abs(a.get_params() - p).max()))
-        assert _same_bits(a.get_velocity(), v), cyc
+        assert same_bits(a.get_params(), p), (cyc, float(np.abs(a.get_params() - p).max()))
+        assert same_bits(a.get_velocity(), v), cyc
         if decay:
-            assert _same_bits(a.get_ema(), e), cyc
+            assert same_bits(a.get_ema(), e), cyc
     # one graph per kind of micro-step (and tensors), the last kind once per host rate
     assert a.graphs_instantiated() == g0 + k + 1
     a.close(); b.close()
@@ -169,7 +92,7 @@ def _check_against_host(spec, precision, k, sgd, decay=0.0, clip=False):
 
 def test_off_is_off():
     from mercer_research_amd.convnet import ConvNetError
-    a, b = _twins(FUSED_HEAD, "fp32")
+    a, b = twins(FUSED_HEAD, "fp32")
     a.set_accumulate(1)
     assert a.get_accumulate() == (1, 0)
     B = FUSED_HEAD[2]
@@ -178,13 +101,13 @@ def test_off_is_off():
     assert "accumulate" not in a.plan_of_this_net(B) and "k_reduce_all_acc" not in a.plan_of_this_net(B)
     with pytest.raises(ConvNetError, match="-1"):
         a.plan_micro_of_this_net(B, "first")
-    x, y = _batch(a, FUSED_HEAD)
+    x, y = batch(a, FUSED_HEAD)
     p0 = a.get_params()
     for _ in range(4):                                   # eager, then graph replays
-        _step(a, x, y, 0.05)
-        _step(b, x, y, 0.05)
+        step(a, x, y, 0.05)
+        step(b, x, y, 0.05)
         assert a.get_accumulate() == (1, 0)
-    assert _same_bits(a.get_params(), b.get_params()) and not _same_bits(a.get_params(), p0)
+    assert same_bits(a.get_params(), b.get_params()) and not same_bits(a.get_params(), p0)
     assert a.graphs_instantiated() == b.graphs_instantiated() == 1
     with pytest.raises(ConvNetError, match="status -6"):
         a.get_accumulated()
@@ -193,7 +116,7 @@ def test_off_is_off():
 
 
 @pytest.mark.parametrize("k", [2, 3])
-@pytest.mark.parametrize("sgd", [DEFAULT, NESTEROV], ids=["default", "nesterov"])
+@pytest.mark.parametrize("sgd", [PLAIN, NESTEROV], ids=["default", "nesterov"])
 @pytest.mark.parametrize("spec,precision", [(FUSED_HEAD, "fp32"), (PLAIN_HEAD, "fp32"), (FUSED_HEAD, "bf16"), (POOL_PAIRS, "bf16_stored")],
                          ids=["fused_head-fp32", "plain_head-fp32", "fused_head-bf16", "pool_pairs-bf16_stored"])
 def test_accumulated_update_is_the_host_update_bit_for_bit(spec, precision, sgd, k):
@@ -206,35 +129,28 @@ def test_with_the_average(k):
 
 
 @pytest.mark.parametrize("k", [2, 3])
-@pytest.mark.parametrize("sgd,decay", [(DEFAULT, 0.0), (NESTEROV, 0.9)], ids=["default", "nesterov-ema"])
+@pytest.mark.parametrize("sgd,decay", [(PLAIN, 0.0), (NESTEROV, 0.9)], ids=["default", "nesterov-ema"])
 def test_with_clipping(sgd, decay, k):
     _check_against_host(FUSED_HEAD, "fp32", k, sgd, decay=decay, clip=True)
 
 
-@pytest.mark.parametrize("sgd", [DEFAULT, NESTEROV], ids=["default", "nesterov"])
+@pytest.mark.parametrize("sgd", [PLAIN, NESTEROV], ids=["default", "nesterov"])
 def test_measure_only_leaves_the_unclipped_accumulating_twin(sgd):
     spec, k = PLAIN_HEAD, 2
-    a, u = _twins(spec, "fp32")
+    a, u = twins(spec, "fp32")
     for n in (a, u):
         n.set_sgd(*sgd)
         n.set_accumulate(k)
     a.set_clip(INF)
-    batches = _batches(a, spec, k)
+    batches = batches_by_seed(a, spec, k)
     for cyc in range(2):
         for x, y in batches:
-            _step(a, x, y, 0.05)
-            _step(u, x, y, 0.05)
+            step(a, x, y, 0.05)
+            step(u, x, y, 0.05)
         assert a.grad_norm()[1] == 1.0 and a.grad_norm_count() == cyc + 1
-        assert _same_bits(a.get_params(), u.get_params()) and _same_bits(a.get_velocity(), u.get_velocity()), cyc
-    assert _same_bits(a.get_accumulated(), u.get_accumulated())
+        assert same_bits(a.get_params(), u.get_params()) and same_bits(a.get_velocity(), u.get_velocity()), cyc
+    assert same_bits(a.get_accumulated(), u.get_accumulated())
     a.close(); u.close()
-
-
-def _close(a, b, rtol=2e-4):
-    """tests/test_gpu_convnet.py's _close, at its default: what that file allows one fp32 step against the f64 oracle"""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    scale = max(1e-3, float(np.abs(b).max()))
-    assert np.abs(a - b).max() <= rtol * scale + 1e-6, (float(np.abs(a - b).max()), scale)
 
 
 def test_one_cycle_against_the_f64_oracle_on_the_concatenated_batch():
@@ -243,7 +159,7 @@ def test_one_cycle_against_the_f64_oracle_on_the_concatenated_batch():
     in_shape, layers, B = FUSED_HEAD
     k, lr = 3, 0.05
     rng = np.random.default_rng(15)
-    net = _net(FUSED_HEAD)
+    net = make_net(FUSED_HEAD)
     shapes = co.param_shapes(in_shape, layers)
     ws = [rng.standard_normal(s) * np.sqrt(2.0 / s[0]) for s, _ in shapes]
     bs = [rng.standard_normal(n) * 0.1 for _, n in shapes]
@@ -257,11 +173,11 @@ def test_one_cycle_against_the_f64_oracle_on_the_concatenated_batch():
     parts = [(net.to_device(x[j * B:(j + 1) * B]), net.to_device(y[j * B:(j + 1) * B])) for j in range(k)]
     net.synchronize()
     for xd, yd in parts:
-        _step(net, xd, yd, lr)
+        step(net, xd, yd, lr)
     assert net.get_accumulate() == (k, 0)
     err = float(np.abs(net.get_params().astype(np.float64) - co.flatten(nw, nb)).max())
     print(f"max |device - oracle| after one cycle of {k}: {err:.3e}")
-    _close(net.get_params(), co.flatten(nw, nb))
+    close(net.get_params(), co.flatten(nw, nb))
     net.close()
 
 
@@ -271,32 +187,32 @@ def test_data_parallel_identity(clip):
     velocity bit for bit"""
     import torch
     spec, k, lr = FUSED_HEAD, 2, 0.03
-    a, b, d = _twins(spec, "fp32", 3)
-    batches = _batches(a, spec, k)
+    a, b, d = twins(spec, "fp32", 3)
+    batches = batches_by_seed(a, spec, k)
     p0 = a.get_params()
     for n in (a, d):
         n.set_sgd(*NESTEROV)
     if clip:
-        first = accumulate([_grad(b, x, y, p0)[1] for x, y in batches], k)
+        first = accumulate([grad(b, x, y, p0)[1] for x, y in batches], k)
         max_norm = float(grad_norm(first) / np.float32(2))
         for n in (a, d):
             n.set_clip(max_norm)
     a.set_accumulate(k)
     for cyc in range(2):                                 # the second cycle on a velocity that is not zero
         p = a.get_params()
-        acc_pad = accumulate([_grad(b, x, y, p)[1] for x, y in batches], k)
+        acc_pad = accumulate([grad(b, x, y, p)[1] for x, y in batches], k)
         for x, y in batches:
-            _step(a, x, y, lr)
+            step(a, x, y, lr)
         acc_dev = d.to_device(acc_pad)
         d.synchronize()
-        assert acc_dev.data_ptr() % 16 == 0 and _same_bits(d.unpad(acc_dev), a.get_accumulated())
+        assert acc_dev.data_ptr() % 16 == 0 and same_bits(d.unpad(acc_dev), a.get_accumulated())
         with torch.cuda.stream(d.stream):
             d.apply_sgd(acc_dev, 1.0, lr)
         d.synchronize()
         if clip:
             assert a.grad_norm() == d.grad_norm() and (cyc > 0 or a.grad_norm()[1] < 1.0)
-        assert _same_bits(a.get_params(), d.get_params()) and not _same_bits(a.get_params(), p), cyc
-        assert _same_bits(a.get_velocity(), d.get_velocity()), cyc
+        assert same_bits(a.get_params(), d.get_params()) and not same_bits(a.get_params(), p), cyc
+        assert same_bits(a.get_velocity(), d.get_velocity()), cyc
     a.close(); b.close(); d.close()
 
 
@@ -315,19 +231,8 @@ def _set(net, seed=6):
     return X, Y, perm
 
 
-def _epoch(net, *args, **kw):
-    import torch
-    with torch.cuda.stream(net.stream):
-        net.train_epoch(*args, **kw)
-    net.synchronize()
-
-
-def _same_state(a, b):
-    return _same_bits(a.get_params(), b.get_params()) and _same_bits(a.get_velocity(), b.get_velocity())
-
-
 def _epoch_twins(count, k):
-    nets = _twins(FUSED_HEAD, "fp32", count)
+    nets = twins(FUSED_HEAD, "fp32", count)
     for n in nets:
         n.set_sgd(*NESTEROV)
         n.set_accumulate(k)
@@ -346,7 +251,7 @@ def test_epoch_is_the_micro_batches_fed_one_by_one(k):
     la = torch.zeros(NB, dtype=torch.float32, device=a.device)
     a.synchronize()
     g0 = a.graphs_instantiated()
-    _epoch(a, X, Y, perm, EB, lr, losses=la)
+    epoch(a, X, Y, perm, EB, lr, losses=la)
     assert a.graphs_instantiated() == g0 + k
     assert a.get_accumulate() == (k, NB % k) == (k, 0)
     lt = torch.zeros(NB, dtype=torch.float32, device=t.device)
@@ -357,19 +262,19 @@ def test_epoch_is_the_micro_batches_fed_one_by_one(k):
             keep.append((x, y))
             t.train_step(x, y, float(RATES[s]), lt[s:s + 1])
     t.synchronize()
-    assert _same_state(a, t) and not _same_bits(a.get_params(), p0)
-    assert _same_bits(a.get_accumulated(), t.get_accumulated())
+    assert same_state(a, t) and not same_bits(a.get_params(), p0)
+    assert same_bits(a.get_accumulated(), t.get_accumulated())
     losses = la.cpu().numpy()
-    assert np.array_equal(_bits(losses), _bits(lt.cpu().numpy())), (losses, lt.cpu().numpy())
+    assert np.array_equal(bits(losses), bits(lt.cpu().numpy())), (losses, lt.cpu().numpy())
     assert np.all(np.isfinite(losses)) and np.all(losses > 0) and len(set(losses.tolist())) == NB      # every micro-batch's own loss
     # the rates of the micro-steps that apply no update: not one bit changes
     junk = RATES.copy()
     junk[[s for s in range(NB) if s % k != k - 1]] = IGNORED
-    _epoch(c, X, Y, perm, EB, c.to_device(junk))
-    assert _same_state(a, c)
+    epoch(c, X, Y, perm, EB, c.to_device(junk))
+    assert same_state(a, c)
     # a second epoch with another schedule: no new graph
     lr2 = a.to_device((RATES[::-1] * np.float32(0.5)).astype(np.float32))
-    _epoch(a, X, Y, perm, EB, lr2)
+    epoch(a, X, Y, perm, EB, lr2)
     assert a.graphs_instantiated() == g0 + k
     for n in (a, t, c):
         n.close()
@@ -381,21 +286,21 @@ def test_epoch_split_calls_and_a_pending_tail():
     X, Y, perm = _set(a)
     lr = a.to_device(RATES)
     a.synchronize()
-    _epoch(a, X, Y, perm, EB, lr)
+    epoch(a, X, Y, perm, EB, lr)
     # 3 + 3 micro-batches: the first call ends inside a cycle
-    _epoch(s, X, Y, perm, EB, lr[:3].contiguous(), n_batches=3)
+    epoch(s, X, Y, perm, EB, lr[:3].contiguous(), n_batches=3)
     assert s.get_accumulate() == (k, 1)
-    _epoch(s, X, Y, perm, EB, lr[3:].contiguous(), first_batch=3, n_batches=3)
-    assert s.get_accumulate() == (k, 0) and _same_state(a, s)
+    epoch(s, X, Y, perm, EB, lr[3:].contiguous(), first_batch=3, n_batches=3)
+    assert s.get_accumulate() == (k, 0) and same_state(a, s)
     # five micro-batches leave one pending; reset_accumulation drops it: the next cycle is that of a twin that never saw the fifth
-    _epoch(r, X, Y, perm, EB, lr, n_batches=5)
-    _epoch(w, X, Y, perm, EB, lr, n_batches=4)
-    assert r.get_accumulate() == (k, 1) and w.get_accumulate() == (k, 0) and _same_state(r, w)
+    epoch(r, X, Y, perm, EB, lr, n_batches=5)
+    epoch(w, X, Y, perm, EB, lr, n_batches=4)
+    assert r.get_accumulate() == (k, 1) and w.get_accumulate() == (k, 0) and same_state(r, w)
     r.reset_accumulation()
     assert r.get_accumulate() == (k, 0)
     for n in (r, w):
-        _epoch(n, X, Y, perm, EB, lr, n_batches=2)
-    assert _same_state(r, w) and _same_bits(r.get_accumulated(), w.get_accumulated())
+        epoch(n, X, Y, perm, EB, lr, n_batches=2)
+    assert same_state(r, w) and same_bits(r.get_accumulated(), w.get_accumulated())
     for n in (a, s, r, w):
         n.close()
 
@@ -415,7 +320,7 @@ def test_mixed_epoch_is_gather_mix_and_train_step_pair_one_by_one():
     la = torch.zeros(NB, dtype=torch.float32, device=a.device)
     a.synchronize()
     g0 = a.graphs_instantiated()
-    _epoch(a, X, Y, perm, EB, lr, losses=la, mix=recs)
+    epoch(a, X, Y, perm, EB, lr, losses=la, mix=recs)
     assert a.graphs_instantiated() == g0 + k
     lt = torch.zeros(NB, dtype=torch.float32, device=t.device)
     keep = []
@@ -426,8 +331,8 @@ def test_mixed_epoch_is_gather_mix_and_train_step_pair_one_by_one():
             keep.append((x, ya, yb, wgt))
             t.train_step_pair(x, ya, yb, wgt, float(RATES[s]), lt[s:s + 1])
     t.synchronize()
-    assert _same_state(a, t)
-    assert np.array_equal(_bits(la.cpu().numpy()), _bits(lt.cpu().numpy()))
+    assert same_state(a, t)
+    assert np.array_equal(bits(la.cpu().numpy()), bits(lt.cpu().numpy()))
     a.close(); t.close()
 
 
@@ -436,10 +341,10 @@ def test_state():
     from mercer_research_amd.convnet import ConvNetError
     spec = FUSED_HEAD
     B = spec[2]
-    a, f, c = _twins(spec, "fp32", 3)
+    a, f, c = twins(spec, "fp32", 3)
     for n in (a, f, c):
         n.set_sgd(*NESTEROV)
-    xs = _batches(a, spec, 3)
+    xs = batches_by_seed(a, spec, 3)
     X, Y, _ = _set(a)
     # refusals change nothing
     a.set_accumulate(3)
@@ -465,7 +370,7 @@ def test_state():
     with pytest.raises(ValueError):
         a.plan_micro_of_this_net(B, "whole")
     # a changed k with a cycle open discards it: the next update is a fresh twin's
-    _step(a, *xs[0], 0.05)
+    step(a, *xs[0], 0.05)
     assert a.get_accumulate() == (3, 1) and a.graphs_instantiated() == graphs + 1
     a.set_accumulate(3)                                  # the k it has: a no-op
     assert a.get_accumulate() == (3, 1) and a.graphs_instantiated() == graphs + 1
@@ -476,28 +381,28 @@ def test_state():
         n.set_accumulate(2)
     for x, y in xs[1:]:
         for n in (a, f, c):
-            _step(n, x, y, 0.05)
-    assert a.get_accumulate() == (2, 0) and _same_state(a, f)
+            step(n, x, y, 0.05)
+    assert a.get_accumulate() == (2, 0) and same_state(a, f)
     # evaluation, set_params and a change of precision between two micro-steps: acc and the position stay, and so does the cycle's result
     p = a.get_params()
-    _step(a, *xs[0], IGNORED)
-    _step(c, *xs[0], IGNORED)                            # (c: the same cycle without the calls in between)
+    step(a, *xs[0], IGNORED)
+    step(c, *xs[0], IGNORED)                            # (c: the same cycle without the calls in between)
     acc = a.get_accumulated()
     assert a.evaluate(X, Y) == f.evaluate(X, Y)
-    assert _same_bits(a.get_accumulated(), acc) and a.get_accumulate() == (2, 1)
+    assert same_bits(a.get_accumulated(), acc) and a.get_accumulate() == (2, 1)
     a.set_params(p)
     a.set_precision("bf16")
     a.set_precision("fp32")
-    assert _same_bits(a.get_accumulated(), acc) and a.get_accumulate() == (2, 1) and _same_bits(a.get_params(), p)
-    _step(a, *xs[2], 0.02)
-    _step(c, *xs[2], 0.02)
-    assert a.get_accumulate() == (2, 0) and _same_state(a, c) and not _same_bits(a.get_params(), p)
+    assert same_bits(a.get_accumulated(), acc) and a.get_accumulate() == (2, 1) and same_bits(a.get_params(), p)
+    step(a, *xs[2], 0.02)
+    step(c, *xs[2], 0.02)
+    assert a.get_accumulate() == (2, 0) and same_state(a, c) and not same_bits(a.get_params(), p)
     # back to 1: the whole step again, the accumulator kept
     a.set_accumulate(1)
     c.set_accumulate(1)
     acc = a.get_accumulated()
-    _step(a, *xs[0], 0.05)
-    _step(c, *xs[0], 0.05)
-    assert _same_state(a, c) and _same_bits(a.get_accumulated(), acc) and a.get_accumulate() == (1, 0)
+    step(a, *xs[0], 0.05)
+    step(c, *xs[0], 0.05)
+    assert same_state(a, c) and same_bits(a.get_accumulated(), acc) and a.get_accumulate() == (1, 0)
     for n in (a, f, c):
         n.close()

@@ -7,87 +7,23 @@ The twin-net method of tests/test_gpu_convnet_sgd.py: net A takes the library's 
 coefficient the host uses the value the device reports, and three things are asserted: the device's coef is clip_coef(norm_dev, max_norm)
 bit for bit; norm_dev is within one float32 ulp of the restatement's norm of B's gradient (whether it was exact is printed: the double
 square root's last bit on the device is the one thing the restatement cannot promise); parameters, velocity and average are equal bit for bit."""
-import os
-import sys
-
 import numpy as np
 import pytest
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-from _clip_ref import apply_coef, clip_coef, grad_norm, plain_update  # noqa: E402
-from _ema_ref import ema_update  # noqa: E402
-from _sgd_ref import sgd_update  # noqa: E402
+from _clip_ref import apply_coef, grad_norm, plain_update
+from _convnet_util import FUSED_HEAD, INF, MU, PLAIN, PLAIN_HEAD, POOL_PAIRS, WD, batch, check_norm, grad, make_net, same_bits, step, twins
+from _ema_ref import ema_update
+from _sgd_ref import sgd_update
 
 pytestmark = pytest.mark.gpu
 
-FUSED_HEAD = ((8, 8, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 32), ("dense", 10)), 5)
-PLAIN_HEAD = ((6, 6, 1), (("conv", 32), ("conv", 32), ("pool",), ("dense", 7)), 3)
-POOL_PAIRS = ((16, 16, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 128), ("dense", 10)), 64)
-MU, WD = 0.9, 5e-4
 LRS = [0.05, 0.05, 0.05, 0.02, 0.05]                   # eager, replays, a second graph, back to the first
-INF = float("inf")
-DEFAULT = (0.0, 0.0, False)                             # rcn_hipx_set_sgd's default: plain SGD
-
-
-def _net(spec, precision="fp32"):
-    from mercer_research_amd.convnet import ConvNet
-    in_shape, layers, B = spec
-    net = ConvNet(in_shape, layers, B)
-    net.set_precision(precision)
-    return net
-
-
-def _twins(spec, precision, count=2, seed=1):
-    nets = [_net(spec, precision)]
-    nets[0].init_params(seed)
-    for _ in range(count - 1):
-        nets.append(_net(spec, precision))
-        nets[-1].set_params(nets[0].get_params())
-    return nets
-
-
-def _batch(net, spec, seed=0):
-    in_shape, layers, B = spec
-    rng = np.random.default_rng(seed)
-    x = net.to_device(rng.standard_normal((B,) + in_shape).astype(np.float32))
-    y = net.to_device(rng.integers(0, layers[-1][1], B).astype(np.int32))
-    net.synchronize()
-    return x, y
-
-
-def _step(net, x, y, lr):
-    import torch
-    with torch.cuda.stream(net.stream):
-        net.train_step(x, y, lr)
-    net.synchronize()
-
-
-def _grad(net, x, y, p=None):
-    """the padded gradient (a host array) of `net` at parameters p (None: its own)"""
-    import torch
-    if p is not None:
-        net.set_params(p)
-    with torch.cuda.stream(net.stream):
-        g = net.gradients(x, y)
-    net.synchronize()
-    return g, g.cpu().numpy()
-
-
-def _check_norm(tag, norm_dev, coef_dev, norm_ref, max_norm):
-    """the first two assertions of the module docstring"""
-    norm_dev, coef_dev = np.float32(norm_dev), np.float32(coef_dev)
-    print(f"{tag}: norm_dev {norm_dev!r} restatement {norm_ref!r} {'exact' if norm_dev == norm_ref else 'one ulp off'}; coef {coef_dev!r}")
-    assert np.array_equal(coef_dev.view(np.uint32), clip_coef(norm_dev, max_norm).view(np.uint32)), (tag, coef_dev, clip_coef(norm_dev, max_norm))
-    assert abs(float(norm_dev) - float(norm_ref)) <= float(np.spacing(norm_ref)), (tag, norm_dev, norm_ref)
 
 
 def _host_step(b, x, y, p, v, e, lr, coef, sgd, decay, scale=1.0):
     """B's gradient at p, clipped by the device's coefficient, then the float32 restatements of the update and the average"""
-    gdev, gpad = _grad(b, x, y, p)
+    gdev, gpad = grad(b, x, y, p)
     g = apply_coef(b.unpad(gdev), coef, scale)
-    if sgd == DEFAULT:
+    if sgd == PLAIN:
         p = plain_update(p, g, lr)                       # (the default optimiser rounds p - lr g once: _clip_ref.plain_update)
     else:
         p, v = sgd_update(p, g, v, lr, *sgd)
@@ -96,12 +32,8 @@ def _host_step(b, x, y, p, v, e, lr, coef, sgd, decay, scale=1.0):
     return p, v, e, grad_norm(gpad, scale)
 
 
-def _same_bits(a, b):
-    return np.array_equal(a, b)
-
-
 def test_off_is_off():
-    a, b = _twins(FUSED_HEAD, "fp32")
+    a, b = twins(FUSED_HEAD, "fp32")
     from mercer_research_amd.convnet import ConvNetError
     a.set_clip(0.0)
     assert a.get_clip() == 0.0
@@ -109,12 +41,12 @@ def test_off_is_off():
     assert a.plan_of_this_net(B) == b.plan_of_this_net(B)
     assert a.plan_epoch_of_this_net(B, lr_from_device=True) == b.plan_epoch_of_this_net(B, lr_from_device=True)
     assert "clip" not in a.plan_of_this_net(B) and "k_grad_sumsq" not in a.plan_of_this_net(B)
-    x, y = _batch(a, FUSED_HEAD)
+    x, y = batch(a, FUSED_HEAD)
     p0 = a.get_params()
     for _ in range(4):                                   # eager, then graph replays
-        _step(a, x, y, 0.05)
-        _step(b, x, y, 0.05)
-    assert _same_bits(a.get_params(), b.get_params()) and not _same_bits(a.get_params(), p0)
+        step(a, x, y, 0.05)
+        step(b, x, y, 0.05)
+    assert same_bits(a.get_params(), b.get_params()) and not same_bits(a.get_params(), p0)
     assert a.graphs_instantiated() == b.graphs_instantiated()
     with pytest.raises(ConvNetError, match="status -6"):
         a.grad_norm()
@@ -122,61 +54,61 @@ def test_off_is_off():
     a.close(); b.close()
 
 
-@pytest.mark.parametrize("sgd", [DEFAULT, (MU, WD, True)], ids=["default", "nesterov"])
+@pytest.mark.parametrize("sgd", [PLAIN, (MU, WD, True)], ids=["default", "nesterov"])
 def test_measure_only_changes_no_bit(sgd):
     """max_norm = +inf: coef == 1 and the parameters of an unclipped twin, with the default optimiser too -- the clipped launches are
     instantiated on the unclipped launches' own functors (PlainUpdate rounds p - lr g once, SgdUpdate with mu = wd = 0 twice: they cannot
     share one)."""
     spec = FUSED_HEAD
-    a, u, b = _twins(spec, "fp32", 3)
+    a, u, b = twins(spec, "fp32", 3)
     for n in (a, u):
         n.set_sgd(*sgd)
     a.set_clip(INF)
     assert a.get_clip() == INF
-    x, y = _batch(a, spec)
+    x, y = batch(a, spec)
     for k, lr in enumerate(LRS):
         p = a.get_params()
-        _, gpad = _grad(b, x, y, p)
-        _step(a, x, y, lr)
-        _step(u, x, y, lr)
+        _, gpad = grad(b, x, y, p)
+        step(a, x, y, lr)
+        step(u, x, y, lr)
         norm, coef = a.grad_norm()
         assert coef == 1.0
-        _check_norm(f"measure-only step {k}", norm, coef, grad_norm(gpad), INF)
-        assert _same_bits(a.get_params(), u.get_params()), k
-        assert _same_bits(a.get_velocity(), u.get_velocity()), k
+        check_norm(f"measure-only step {k}", norm, coef, grad_norm(gpad), INF)
+        assert same_bits(a.get_params(), u.get_params()), k
+        assert same_bits(a.get_velocity(), u.get_velocity()), k
     assert a.grad_norm_count() == len(LRS)
     assert a.graphs_instantiated() == u.graphs_instantiated()
     a.close(); u.close(); b.close()
 
 
 def _check_clipped_against_host(spec, precision, nesterov, decay, sgd=None):
-    a, b = _twins(spec, precision)
+    a, b = twins(spec, precision)
     sgd = sgd or (MU, WD, nesterov)
     a.set_sgd(*sgd)
     if decay:
         a.set_ema(decay)
-    x, y = _batch(a, spec)
+    x, y = batch(a, spec)
     p = a.get_params()
     v, e = np.zeros(a.n_logical, dtype=np.float32), p.copy()
-    max_norm = float(grad_norm(_grad(b, x, y, p)[1]) / np.float32(2))       # half the first step's norm
+    max_norm = float(grad_norm(grad(b, x, y, p)[1]) / np.float32(2))       # half the first step's norm
     a.set_clip(max_norm)
     assert a.get_clip() == np.float32(max_norm)
     plan = a.plan_of_this_net(spec[2])
     assert "k_grad_sumsq" in plan and "k_reduce_all_clip" in plan and "clip: max norm" in plan, plan
-    kernel = "k_reduce_all_clip" + ("_sgd" if sgd != DEFAULT else "") + ("_ema" if decay else "") + ","
+    kernel = "k_reduce_all_clip" + ("_sgd" if sgd != PLAIN else "") + ("_ema" if decay else "") + ","
     assert kernel in plan, (kernel, plan)
     assert "(clip: max norm %g)" % max_norm in plan, plan
     for k, lr in enumerate(LRS):
-        _step(a, x, y, lr)
+        step(a, x, y, lr)
         norm, coef = a.grad_norm()
         p, v, e, norm_ref = _host_step(b, x, y, p, v, e, lr, coef, sgd, decay)
-        _check_norm(f"step {k}", norm, coef, norm_ref, max_norm)
+        check_norm(f"step {k}", norm, coef, norm_ref, max_norm)
         if k == 0:
             assert coef < 1.0
-        assert _same_bits(a.get_params(), p), (k, float(np.abs(a.get_params() - p).max()))
-        assert _same_bits(a.get_velocity(), v), k
+        assert same_bits(a.get_params(), p), (k, float(np.abs(a.get_params() - p).max()))
+        assert same_bits(a.get_velocity(), v), k
         if decay:
-            assert _same_bits(a.get_ema(), e), k
+            assert same_bits(a.get_ema(), e), k
     a.close(); b.close()
 
 
@@ -194,7 +126,7 @@ def test_clipped_step_with_the_average():
 @pytest.mark.parametrize("decay", [0.0, 0.9], ids=["plain", "ema"])
 def test_clipped_step_of_the_default_optimiser(decay):
     """plain SGD behind the coefficient: p - lr g' rounded once, as k_reduce_all rounds it (_clip_ref.plain_update)"""
-    _check_clipped_against_host(PLAIN_HEAD, "fp32", False, decay, sgd=DEFAULT)
+    _check_clipped_against_host(PLAIN_HEAD, "fp32", False, decay, sgd=PLAIN)
 
 
 @pytest.mark.parametrize("decay", [0.0, 0.9], ids=["plain", "ema"])
@@ -204,7 +136,7 @@ def test_one_graph_epoch_with_device_rate_and_ring_log(decay):
     import torch
     spec = FUSED_HEAD
     in_shape, layers, B = spec
-    a, t, b = _twins(spec, "fp32", 3)
+    a, t, b = twins(spec, "fp32", 3)
     rng = np.random.default_rng(6)
     X = a.to_device(rng.integers(0, 256, (6 * B,) + in_shape).astype(np.uint8))
     Y = a.to_device(rng.integers(0, 10, 6 * B).astype(np.int32))
@@ -214,7 +146,7 @@ def test_one_graph_epoch_with_device_rate_and_ring_log(decay):
     a.synchronize()
     with torch.cuda.stream(b.stream):
         x0, y0 = b.gather_batch(X, Y, None, B)
-    max_norm = float(grad_norm(_grad(b, x0, y0)[1]) / np.float32(2))
+    max_norm = float(grad_norm(grad(b, x0, y0)[1]) / np.float32(2))
     for n in (a, t):
         n.set_sgd(MU, WD, True)
         if decay:
@@ -240,9 +172,9 @@ def test_one_graph_epoch_with_device_rate_and_ring_log(decay):
     want = np.array([norms[4], norms[5], norms[2], norms[3]], dtype=np.float32)      # step k in slot k % 4
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (got, want)
     assert a.grad_norm()[0] == norms[5]
-    assert _same_bits(a.get_params(), t.get_params()) and _same_bits(a.get_velocity(), t.get_velocity())
+    assert same_bits(a.get_params(), t.get_params()) and same_bits(a.get_velocity(), t.get_velocity())
     if decay:
-        assert _same_bits(a.get_ema(), t.get_ema())
+        assert same_bits(a.get_ema(), t.get_ema())
     with torch.cuda.stream(a.stream):
         a.train_epoch(X, Y, None, B, lr)
     a.synchronize()
@@ -258,11 +190,11 @@ def test_data_parallel_half(precision):
     scale = 0.5; with the default optimiser and clipping on, apply_sgd still clips (it does not take the axpy)."""
     import torch
     spec = POOL_PAIRS
-    a, b, c, d = _twins(spec, precision, 4)
+    a, b, c, d = twins(spec, precision, 4)
     sgd = (MU, WD, True)
-    x, y = _batch(a, spec)
+    x, y = batch(a, spec)
     p0 = a.get_params()
-    max_norm = float(grad_norm(_grad(b, x, y)[1]) / np.float32(2))
+    max_norm = float(grad_norm(grad(b, x, y)[1]) / np.float32(2))
     for n in (a, b, c):
         n.set_sgd(*sgd)
         n.set_ema(0.9)
@@ -270,37 +202,37 @@ def test_data_parallel_half(precision):
         n.set_clip(max_norm)
     lr = 0.03
     for k in range(3):
-        _step(a, x, y, lr)
+        step(a, x, y, lr)
         with torch.cuda.stream(b.stream):
             g = b.gradients(x, y)
             b.apply_sgd(g, 1.0, lr)
         b.synchronize()
         assert a.grad_norm() == b.grad_norm() and (k > 0 or a.grad_norm()[1] < 1.0)
-        assert _same_bits(a.get_params(), b.get_params()) and _same_bits(a.get_velocity(), b.get_velocity()) and _same_bits(a.get_ema(), b.get_ema()), k
+        assert same_bits(a.get_params(), b.get_params()) and same_bits(a.get_velocity(), b.get_velocity()) and same_bits(a.get_ema(), b.get_ema()), k
     assert b.grad_norm_count() == 3
     # grad_scale = 0.5 on c (first step: v = 0, e = p0); d: the default optimiser
-    for net, opt, decay in ((c, sgd, 0.9), (d, DEFAULT, 0.0)):
+    for net, opt, decay in ((c, sgd, 0.9), (d, PLAIN, 0.0)):
         with torch.cuda.stream(net.stream):
             g = net.gradients(x, y)
             net.apply_sgd(g, 0.5, lr)
         net.synchronize()
         norm, coef = net.grad_norm()
         gpad = g.cpu().numpy()
-        _check_norm(f"apply_sgd scale 0.5 {opt}", norm, coef, grad_norm(gpad, 0.5), max_norm)
+        check_norm(f"apply_sgd scale 0.5 {opt}", norm, coef, grad_norm(gpad, 0.5), max_norm)
         gc = apply_coef(net.unpad(g), coef, 0.5)
         p, v = sgd_update(p0, gc, np.zeros_like(p0), lr, *opt) if decay else (plain_update(p0, gc, lr), None)
-        assert _same_bits(net.get_params(), p)
+        assert same_bits(net.get_params(), p)
         if decay:
-            assert _same_bits(net.get_velocity(), v) and _same_bits(net.get_ema(), ema_update(p0, p, decay))
+            assert same_bits(net.get_velocity(), v) and same_bits(net.get_ema(), ema_update(p0, p, decay))
         else:
-            assert coef < 1.0 and not _same_bits(p, sgd_update(p0, net.unpad(g), np.zeros_like(p0), lr, grad_scale=0.5)[0])      # (the axpy's result)
+            assert coef < 1.0 and not same_bits(p, sgd_update(p0, net.unpad(g), np.zeros_like(p0), lr, grad_scale=0.5)[0])      # (the axpy's result)
     for n in (a, b, c, d):
         n.close()
 
 
 @pytest.fixture(scope="module")
 def norm_net():
-    net = _net(PLAIN_HEAD)
+    net = make_net(PLAIN_HEAD)
     yield net
     net.close()
 
@@ -357,32 +289,32 @@ def test_state():
     from mercer_research_amd.convnet import ConvNetError
     spec = FUSED_HEAD
     in_shape, layers, B = spec
-    a, b = _twins(spec, "fp32")
+    a, b = twins(spec, "fp32")
     sgd = (MU, WD, False)
     a.set_sgd(*sgd)
     a.set_ema(0.9)
-    x, y = _batch(a, spec)
+    x, y = batch(a, spec)
     p = a.get_params()
     v, e = np.zeros_like(p), p.copy()
-    gdev, gpad = _grad(b, x, y)
+    gdev, gpad = grad(b, x, y)
     m1 = float(grad_norm(gpad) / np.float32(2))
     m2 = float(grad_norm(gpad) / np.float32(8))
     a.set_clip(m1)
     lr = 0.05
     for k in range(3):                                   # eager, replays
-        _step(a, x, y, lr)
+        step(a, x, y, lr)
         norm, coef = a.grad_norm()
         p, v, e, norm_ref = _host_step(b, x, y, p, v, e, lr, coef, sgd, 0.9)
-        _check_norm(f"m1 step {k}", norm, coef, norm_ref, m1)
+        check_norm(f"m1 step {k}", norm, coef, norm_ref, m1)
     graphs = a.graphs_instantiated()
     # a changed max_norm between two replays reaches the next step: a new coefficient, the graphs dropped
     a.set_clip(m2)
-    _step(a, x, y, lr)
+    step(a, x, y, lr)
     norm, coef = a.grad_norm()
     p, v, e, norm_ref = _host_step(b, x, y, p, v, e, lr, coef, sgd, 0.9)
-    _check_norm("m2", norm, coef, norm_ref, m2)
+    check_norm("m2", norm, coef, norm_ref, m2)
     assert coef < 1.0 and a.graphs_instantiated() == graphs + 1
-    assert _same_bits(a.get_params(), p) and _same_bits(a.get_velocity(), v) and _same_bits(a.get_ema(), e)
+    assert same_bits(a.get_params(), p) and same_bits(a.get_velocity(), v) and same_bits(a.get_ema(), e)
     # refusals change nothing
     count = a.grad_norm_count()
     for bad in (float("nan"), -1.0, -INF):
@@ -395,19 +327,19 @@ def test_state():
     with pytest.raises(ValueError):                                                    # an empty tensor (its pointer is NULL): the wrapper
         a.set_grad_norm_log(torch.empty(0, dtype=torch.float32, device=a.device))
     assert a.grad_norm_count() == count == 4 and a.graphs_instantiated() == graphs + 1
-    _step(a, x, y, lr)                                   # (a replay: nothing was dropped by the refusals)
+    step(a, x, y, lr)                                   # (a replay: nothing was dropped by the refusals)
     norm, coef = a.grad_norm()
     p, v, e, norm_ref = _host_step(b, x, y, p, v, e, lr, coef, sgd, 0.9)
-    assert a.graphs_instantiated() == graphs + 1 and _same_bits(a.get_params(), p)
+    assert a.graphs_instantiated() == graphs + 1 and same_bits(a.get_params(), p)
     # gradients() returns the raw gradient with clipping on, evaluate is unchanged
     b.set_params(p)
-    _, ga = _grad(a, x, y)
-    _, gb = _grad(b, x, y)
+    _, ga = grad(a, x, y)
+    _, gb = grad(b, x, y)
     assert np.array_equal(ga.view(np.uint32), gb.view(np.uint32))
-    a0 = _net(spec)
+    a0 = make_net(spec)
     a0.set_params(p)
     a0.set_clip(m1)
-    assert np.array_equal(_grad(a0, x, y)[1].view(np.uint32), gb.view(np.uint32))
+    assert np.array_equal(grad(a0, x, y)[1].view(np.uint32), gb.view(np.uint32))
     rng = np.random.default_rng(8)
     X = a.to_device(rng.integers(0, 256, (4 * B,) + in_shape).astype(np.uint8))
     Y = a.to_device(rng.integers(0, 10, 4 * B).astype(np.int32))
@@ -419,10 +351,10 @@ def test_state():
     a.set_precision("bf16")
     a.set_precision("fp32")
     after = (a.get_velocity(), a.get_ema(), a.grad_norm(), a.get_clip(), a.grad_norm_count())
-    assert _same_bits(before[0], after[0]) and _same_bits(before[1], after[1]) and before[2:] == after[2:]
-    _step(a, x, y, lr)
+    assert same_bits(before[0], after[0]) and same_bits(before[1], after[1]) and before[2:] == after[2:]
+    step(a, x, y, lr)
     norm, coef = a.grad_norm()
     p, v, e, norm_ref = _host_step(b, x, y, p, v, e, lr, coef, sgd, 0.9)
-    _check_norm("after set_params / set_precision", norm, coef, norm_ref, m2)
-    assert _same_bits(a.get_params(), p) and _same_bits(a.get_velocity(), v) and _same_bits(a.get_ema(), e)
+    check_norm("after set_params / set_precision", norm, coef, norm_ref, m2)
+    assert same_bits(a.get_params(), p) and same_bits(a.get_velocity(), v) and same_bits(a.get_ema(), e)
     a.close(); b.close(); a0.close()

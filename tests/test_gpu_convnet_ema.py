@@ -7,85 +7,22 @@ rounded once) reproduces it from the parameters a twin WITHOUT an average reads 
 the average on changes no bit of the parameters or the velocity.  An evaluation on the average runs the launches of an evaluation on
 the same bits held as live parameters, so it equals a twin's live evaluation after set_params(get_ema())."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-from _ema_ref import ema_update  # noqa: E402
+from _convnet_util import FUSED_HEAD, KW, LR, MOMENTUM, NESTEROV, PLAIN, PLAIN_HEAD, POOL_PAIRS, close, dev, epoch, make_net, random_set, step, sync, twins
+from _ema_ref import ema_update
 
 pytestmark = pytest.mark.gpu
 
-FUSED_HEAD = ((8, 8, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 32), ("dense", 10)), 5)
-PLAIN_HEAD = ((6, 6, 1), (("conv", 32), ("conv", 32), ("pool",), ("dense", 7)), 3)        # padded class columns, one chunk per job
-# 16 chunks in the first layer's job: reduce_all_body's GR > 1 / threadIdx.x < EL branch and its i < jb.n edge; bf16 storage covers it
-POOL_PAIRS = ((16, 16, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 128), ("dense", 10)), 64)
-DECAY, LR = 0.5, 0.05
-PLAIN, MOMENTUM, NESTEROV = (0.0, 0.0, False), (0.9, 0.0, False), (0.9, 5e-4, True)
-SCALE, SHIFT = 1.0 / 255.0, -0.1307
-KW = dict(x_scale=SCALE, x_shift=SHIFT)
-
-
-def _net(spec, precision="fp32", sgd=PLAIN, max_batch=None):
-    from mercer_research_amd.convnet import ConvNet
-    in_shape, layers, B = spec
-    net = ConvNet(in_shape, layers, max_batch or B)
-    net.set_precision(precision)
-    net.set_sgd(*sgd)
-    return net
-
-
-def _family(count, spec, precision, sgd=PLAIN, seed=1, max_batch=None):
-    """`count` nets with the same parameters, precision and optimiser"""
-    nets = [_net(spec, precision, sgd, max_batch) for _ in range(count)]
-    nets[0].init_params(seed)
-    for n in nets[1:]:
-        n.set_params(nets[0].get_params())
-    return nets
-
-
-def _sync():
-    import torch
-    torch.cuda.synchronize()
-
-
-def _dev(net, a):
-    t = net.to_device(a)
-    _sync()
-    return t
+DECAY = 0.5
 
 
 def _batches(net, spec, n, seed=0, B=None):
     in_shape, layers, B0 = spec
     B = B or B0
     rng = np.random.default_rng(seed)
-    return [(_dev(net, rng.standard_normal((B,) + in_shape).astype(np.float32)), _dev(net, rng.integers(0, layers[-1][1], B).astype(np.int32))) for _ in range(n)]
-
-
-def _random_set(net, spec, n, seed=0, u8=False):
-    in_shape, layers, _ = spec
-    rng = np.random.default_rng(seed)
-    X = rng.integers(0, 256, (n,) + in_shape).astype(np.uint8) if u8 else rng.standard_normal((n,) + in_shape).astype(np.float32)
-    y = rng.integers(0, layers[-1][1], n).astype(np.int32)
-    return _dev(net, X), _dev(net, y)
-
-
-def _step(net, x, y, lr):
-    import torch
-    with torch.cuda.stream(net.stream):
-        net.train_step(x, y, lr)
-    net.synchronize()
-
-
-def _epoch(net, X, y, perm, B, lr, **kw):
-    import torch
-    with torch.cuda.stream(net.stream):
-        net.train_epoch(X, y, perm, B, lr, **kw)
-    net.synchronize()
+    return [(dev(net, rng.standard_normal((B,) + in_shape).astype(np.float32)), dev(net, rng.integers(0, layers[-1][1], B).astype(np.int32))) for _ in range(n)]
 
 
 def _state(net):
@@ -104,7 +41,7 @@ def _kernel(sgd, dlr=False):
 
 def test_decay_zero_is_a_net_never_configured():
     from mercer_research_amd.convnet import ConvNetError
-    a, b = _family(2, FUSED_HEAD, "fp32")
+    a, b = twins(FUSED_HEAD, "fp32", 2, PLAIN, configured_first=True)
     a.set_ema(0.0)
     assert a.get_ema_decay() == 0.0 and b.get_ema_decay() == 0.0
     B = FUSED_HEAD[2]
@@ -113,8 +50,8 @@ def test_decay_zero_is_a_net_never_configured():
     p0 = a.get_params()
     x, y = _batches(a, FUSED_HEAD, 1)[0]
     for _ in range(4):                                   # eager, then graph replays
-        _step(a, x, y, LR)
-        _step(b, x, y, LR)
+        step(a, x, y, LR)
+        step(b, x, y, LR)
         assert np.array_equal(a.get_params(), b.get_params())
     assert not np.array_equal(a.get_params(), p0)
     assert a.graphs_instantiated() == b.graphs_instantiated()
@@ -132,7 +69,7 @@ def test_decay_zero_is_a_net_never_configured():
 def test_fused_step_keeps_the_average_and_changes_nothing_else(spec, precision, sgd):
     """Five steps: eager, graph replays, one step at a second lr (a second graph), and back to the first graph.  A has the average, twin B
     has not: the same parameters and velocity after every step, and A's average is the restatement applied to B's parameters."""
-    a, b = _family(2, spec, precision, sgd)
+    a, b = twins(spec, precision, 2, sgd, configured_first=True)
     a.set_ema(DECAY)
     assert a.get_ema_decay() == DECAY
     plan = a.plan_of_this_net(spec[2])
@@ -142,8 +79,8 @@ def test_fused_step_keeps_the_average_and_changes_nothing_else(spec, precision, 
     assert np.array_equal(a.get_ema(), e)
     x, y = _batches(a, spec, 1)[0]
     for k, lr in enumerate([0.05, 0.05, 0.05, 0.02, 0.05]):
-        _step(a, x, y, lr)
-        _step(b, x, y, lr)
+        step(a, x, y, lr)
+        step(b, x, y, lr)
         pb = b.get_params()
         e = ema_update(e, pb, DECAY)
         assert np.array_equal(a.get_params(), pb), k
@@ -164,26 +101,26 @@ def test_epoch_with_schedule_augmentation_and_mixing_keeps_the_average(sgd):
     from mercer_research_amd.convnet import Augment, mix_plan
     spec = ((8, 8, 3), FUSED_HEAD[1], 8)
     B, nb, n = 8, 5, 40
-    a, b = _family(2, spec, "fp32", sgd)
+    a, b = twins(spec, "fp32", 2, sgd, configured_first=True)
     a.set_ema(DECAY)
     plan = a.plan_epoch_of_this_net(B, "uint8", True, Augment(2, True, 3, 0), True)
     assert _kernel(sgd, dlr=True) in plan and "(EMA: decay 0.5)" in plan, plan
-    X, y = _random_set(a, spec, n, seed=7, u8=True)
-    perm = _dev(a, np.random.default_rng(8).permutation(n).astype(np.int32))
+    X, y = random_set(a, spec, n, seed=7, u8=True)
+    perm = dev(a, np.random.default_rng(8).permutation(n).astype(np.int32))
     rates = np.array([0.05, 0.05, 0.02, 0.05, 0.03], dtype=np.float32)
-    lr = _dev(a, rates)
+    lr = dev(a, rates)
     aug = Augment(2, True, 3, 0)
     rec = mix_plan(nb, 8, 8, mixup_alpha=0.8, cutmix_alpha=1.0, seed=5)
     rec[0] = (0.4, 0.4, 0, 0, 0, 0)                                  # whatever the draws are: one mixup step and one CutMix step
     rec[1] = (1.0, np.float32(1.0 - 6.0 / 64.0), 1, 3, 2, 5)
     recs = a.mix_to_device(rec)
     one = [b.mix_to_device(rec[s:s + 1]) for s in range(nb)]
-    _sync()
+    sync()
     e = a.get_params()
     ga, gb = a.graphs_instantiated(), b.graphs_instantiated()
-    _epoch(a, X, y, perm, B, lr, augment=aug, mix=recs, **KW)
+    epoch(a, X, y, perm, B, lr, augment=aug, mix=recs, **KW)
     for s in range(nb):
-        _epoch(b, X, y, perm, B, lr[s:s + 1].contiguous(), first_batch=s, n_batches=1, augment=aug, mix=one[s], **KW)
+        epoch(b, X, y, perm, B, lr[s:s + 1].contiguous(), first_batch=s, n_batches=1, augment=aug, mix=one[s], **KW)
         e = ema_update(e, b.get_params(), DECAY)
     assert np.array_equal(a.get_params(), b.get_params()) and np.array_equal(a.get_velocity(), b.get_velocity())
     got = a.get_ema()
@@ -191,9 +128,9 @@ def test_epoch_with_schedule_augmentation_and_mixing_keeps_the_average(sgd):
     assert not np.array_equal(e, a.get_params())
     assert a.graphs_instantiated() - ga == b.graphs_instantiated() - gb
     # the un-mixed scheduled epoch (the other _dlr graph) goes on from there, bit for bit
-    _epoch(a, X, y, perm, B, lr, augment=aug, **KW)
+    epoch(a, X, y, perm, B, lr, augment=aug, **KW)
     for s in range(nb):
-        _epoch(b, X, y, perm, B, lr[s:s + 1].contiguous(), first_batch=s, n_batches=1, augment=aug, **KW)
+        epoch(b, X, y, perm, B, lr[s:s + 1].contiguous(), first_batch=s, n_batches=1, augment=aug, **KW)
         e = ema_update(e, b.get_params(), DECAY)
     assert np.array_equal(a.get_params(), b.get_params()) and np.array_equal(a.get_velocity(), b.get_velocity())
     assert np.array_equal(a.get_ema(), e)
@@ -203,14 +140,6 @@ def test_epoch_with_schedule_augmentation_and_mixing_keeps_the_average(sgd):
 
 # ---- 4. the data-parallel half ---------------------------------------------------------------------------------------------------------
 
-def _close(a, b, rtol=2e-4):
-    """tests/test_gpu_convnet.py's rule for apply(gradients) against train_step"""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    scale = max(1e-3, float(np.abs(b).max()))
-    print("max |d| =", float(np.abs(a - b).max()), "scale =", scale, "rtol =", rtol)
-    assert np.abs(a - b).max() <= rtol * scale + 1e-6, (float(np.abs(a - b).max()), scale)
-
-
 @pytest.mark.parametrize("sgd", [PLAIN, NESTEROV], ids=["plain-k_axpy", "nesterov-k_sgd_apply"])
 def test_data_parallel_half_keeps_the_average_of_the_fused_step(sgd):
     """gradients on a twin + apply_sgd on A against train_step on a third net, two steps.  With the configured optimiser (k_sgd_apply, the
@@ -219,7 +148,7 @@ def test_data_parallel_half_keeps_the_average_of_the_fused_step(sgd):
     rounding per operation in either launch -- to the restatement on that net's OWN parameters, bit for bit."""
     import torch
     spec = POOL_PAIRS
-    a, twin, c = _family(3, spec, "fp32", sgd)
+    a, twin, c = twins(spec, "fp32", 3, sgd, configured_first=True)
     a.set_ema(DECAY)
     c.set_ema(DECAY)
     x, y = _batches(a, spec, 1)[0]
@@ -233,13 +162,13 @@ def test_data_parallel_half_keeps_the_average_of_the_fused_step(sgd):
         with torch.cuda.stream(a.stream):
             a.apply_sgd(grad, 1.0, lr)
         a.synchronize()
-        _step(c, x, y, lr)
+        step(c, x, y, lr)
         ea, ec = ema_update(ea, a.get_params(), DECAY), ema_update(ec, c.get_params(), DECAY)
         assert np.array_equal(a.get_ema(), ea) and np.array_equal(c.get_ema(), ec), k
         assert not np.array_equal(ea, a.get_params())
         if sgd == PLAIN:
-            _close(a.get_params(), c.get_params())
-            _close(a.get_ema(), c.get_ema())
+            close(a.get_params(), c.get_params())
+            close(a.get_ema(), c.get_ema())
         else:
             assert _same(_state(a), _state(c)), k
     # rcn_hipx_apply_dev stays the plain axpy: neither the velocity nor the average moves
@@ -258,14 +187,14 @@ def test_data_parallel_half_keeps_the_average_of_the_fused_step(sgd):
                          ids=["fused_head-fp32", "fused_head-bf16", "pool_pairs-bf16_stored"])
 def test_evaluation_on_the_average_is_a_twins_live_evaluation_and_leaves_training_alone(spec, precision, max_batch, rows, u8):
     """Two full chunks and a short one.  A and N train three steps with the average; A evaluates on it, N never evaluates."""
-    a, n, twin = _family(3, spec, precision, MOMENTUM, max_batch=max_batch)
+    a, n, twin = twins(spec, precision, 3, MOMENTUM, max_batch=max_batch, configured_first=True)
     for net in (a, n):
         net.set_ema(DECAY)
     batches = _batches(a, spec, 2, seed=3)
     for k in range(3):
         for net in (a, n):
-            _step(net, *batches[k % 2], LR)
-    X, y = _random_set(a, spec, rows, seed=9, u8=u8)
+            step(net, *batches[k % 2], LR)
+    X, y = random_set(a, spec, rows, seed=9, u8=u8)
     before = _state(a)
     twin.set_params(before[2])
     g0 = a.graphs_instantiated()
@@ -290,7 +219,7 @@ def test_evaluation_on_the_average_is_a_twins_live_evaluation_and_leaves_trainin
     # training goes on as if nothing had happened: a stale bf16 operand copy or a missed exchange would show here
     for k in range(3, 5):
         for net in (a, n):
-            _step(net, *batches[k % 2], LR)
+            step(net, *batches[k % 2], LR)
         assert _same(_state(a), _state(n)), k
     assert not np.array_equal(a.get_ema(), a.get_params())
     a.close(); n.close(); twin.close()
@@ -301,17 +230,17 @@ def test_evaluation_on_the_average_is_a_twins_live_evaluation_and_leaves_trainin
 def test_state_saved_and_loaded_continues_and_survives_and_changes_reach_the_replay():
     from mercer_research_amd.convnet import ConvNetError
     spec = FUSED_HEAD
-    a, b = _family(2, spec, "fp32", MOMENTUM)
+    a, b = twins(spec, "fp32", 2, MOMENTUM, configured_first=True)
     for net in (a, b):
         net.set_ema(DECAY)
     batches = _batches(a, spec, 3, seed=4)
     for k in range(6):
-        _step(a, *batches[k % 3], LR)
+        step(a, *batches[k % 3], LR)
     for k in range(3):
-        _step(b, *batches[k % 3], LR)
+        step(b, *batches[k % 3], LR)
     p3, v3, e3 = _state(b)
     b.close()
-    c = _net(spec, "fp32", MOMENTUM)
+    c = make_net(spec, "fp32", MOMENTUM)
     with pytest.raises(ConvNetError, match="status -6"):
         c.set_ema_params(e3)                             # no average yet
     c.reset_ema()                                        # ... and nothing to reset: a no-op
@@ -321,7 +250,7 @@ def test_state_saved_and_loaded_continues_and_survives_and_changes_reach_the_rep
     assert np.array_equal(c.get_ema(), p3)               # the start value
     c.set_ema_params(e3)
     for k in range(3, 6):
-        _step(c, *batches[k % 3], LR)
+        step(c, *batches[k % 3], LR)
     assert _same(_state(c), _state(a))
     # the average survives set_params, init_params and a change of precision
     e = c.get_ema()
@@ -336,26 +265,26 @@ def test_state_saved_and_loaded_continues_and_survives_and_changes_reach_the_rep
     # decay 0 on a net whose step is a captured graph: the updates stop (the replay does not touch the average), the buffer stays evaluable
     x, y = batches[0]
     for _ in range(3):
-        _step(c, x, y, LR)
+        step(c, x, y, LR)
     e = c.get_ema()
     assert not np.array_equal(e, c.get_params())
     c.set_ema(0.0)
     assert c.get_ema_decay() == 0.0 and "_ema" not in c.plan_of_this_net(spec[2])
     for _ in range(3):
-        _step(c, x, y, LR)
+        step(c, x, y, LR)
     assert np.array_equal(c.get_ema(), e)
-    X, yy = _random_set(c, spec, 11, seed=2)
-    twin = _net(spec)
+    X, yy = random_set(c, spec, 11, seed=2)
+    twin = make_net(spec, sgd=PLAIN)
     twin.set_params(e)
     assert c.evaluate(X, yy, weights="ema") == twin.evaluate(X, yy)
     # a changed decay reaches the step although (x, y, lr) has a captured graph: graphs that were not dropped would show here
     c.set_ema(0.75)
     for _ in range(3):
-        _step(c, x, y, LR)
+        step(c, x, y, LR)
         e = ema_update(e, c.get_params(), 0.75)
         assert np.array_equal(c.get_ema(), e)
     c.set_ema(0.25)
-    _step(c, x, y, LR)
+    step(c, x, y, LR)
     e = ema_update(e, c.get_params(), 0.25)
     assert np.array_equal(c.get_ema(), e) and c.get_ema_decay() == 0.25
     a.close(); c.close(); twin.close()
@@ -368,9 +297,9 @@ def test_refusals():
     from mercer_research_amd.convnet import ConvNetError
     spec = POOL_PAIRS
     B = spec[2]
-    net = _net(spec)
+    net = make_net(spec, sgd=PLAIN)
     net.init_params(2)
-    X, y = _random_set(net, spec, B, seed=6)
+    X, y = random_set(net, spec, B, seed=6)
     with pytest.raises(ConvNetError, match="status -6"):
         net.evaluate(X, y, weights="ema")                # no average
     with pytest.raises(ConvNetError, match="status -6"):

@@ -9,76 +9,22 @@ import ctypes as C
 
 import numpy as np
 import pytest
+from _convnet_util import CIFAR, FUSED_HEAD, MNIST, PLAIN_HEAD, POOL_PAIRS, SCALE, SHIFT, dev, epoch, make_net, random_set, sync, twins, widen
 
 from oracle import convnet_oracle as co
 
 pytestmark = pytest.mark.gpu
 
-FUSED_HEAD = ((8, 8, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 32), ("dense", 10)), 5)
-PLAIN_HEAD = ((6, 6, 1), (("conv", 32), ("conv", 32), ("pool",), ("dense", 7)), 3)
-POOL_PAIRS = ((16, 16, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 128), ("dense", 10)), 64)     # bf16 storage covers it
-CIFAR = ((32, 32, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("conv", 128), ("pool",), ("dense_relu", 256), ("dense", 10)), 512)
-MNIST = ((28, 28, 1), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 128), ("dense", 10)), 4096)
 SMALL = [(FUSED_HEAD, "fp32"), (PLAIN_HEAD, "bf16"), (POOL_PAIRS, "bf16_stored")]
 SMALL_IDS = ["fused_head-fp32", "plain_head-bf16", "pool_pairs-bf16_stored"]
 LOSS_RTOL = {"fp32": 2e-4, "bf16": 5e-3, "bf16_stored": 5e-3}       # tests/test_gpu_convnet.py: loss and logits tolerances of each mode
-SCALE, SHIFT = 1.0 / 255.0, -0.1307                                 # neither is a power of two
-
-
-def _net(spec, precision="fp32"):
-    from mercer_research_amd.convnet import ConvNet
-    in_shape, layers, B = spec
-    net = ConvNet(in_shape, layers, B)
-    net.set_precision(precision)
-    return net
-
-
-def _twins(spec, precision, seed=1):
-    a = _net(spec, precision)
-    a.init_params(seed)
-    b = _net(spec, precision)
-    b.set_params(a.get_params())
-    return a, b
-
-
-def _sync():
-    import torch
-    torch.cuda.synchronize()
-
-
-def _dev(net, a):
-    t = net.to_device(a)
-    _sync()
-    return t
-
-
-def _random_set(net, spec, n, seed=0, u8=False):
-    in_shape, layers, _ = spec
-    rng = np.random.default_rng(seed)
-    X = rng.integers(0, 256, (n,) + in_shape).astype(np.uint8) if u8 else rng.standard_normal((n,) + in_shape).astype(np.float32)
-    y = rng.integers(0, layers[-1][1], n).astype(np.int32)
-    return _dev(net, X), _dev(net, y)
-
-
-def _widen(u8):
-    """The fp32 set a uint8 set stands for: fl(fl(u8 * scale) + shift), two roundings, built with torch on the host."""
-    import torch
-    t = torch.from_numpy(u8).float() * torch.tensor(SCALE, dtype=torch.float32)
-    return (t.float() + torch.tensor(SHIFT, dtype=torch.float32)).numpy()
-
-
-def _epoch(net, X, y, perm, B, lr, **kw):
-    import torch
-    with torch.cuda.stream(net.stream):
-        net.train_epoch(X, y, perm, B, lr, **kw)
-    net.synchronize()
 
 
 def _steps(net, X, y, perm, B, lr, n_batches):
     """The same batches fed to train_step one by one, gathered with torch; returns the per-step losses."""
     import torch
     losses = torch.zeros(n_batches, dtype=torch.float32, device=net.device)
-    _sync()
+    sync()
     keep = []
     with torch.cuda.stream(net.stream):
         for s in range(n_batches):
@@ -120,18 +66,18 @@ def _host_ce(logits64, y):
 def test_epoch_is_the_same_batches_fed_to_train_step_bit_for_bit(spec, precision, sgd):
     import torch
     B, lr = spec[2], 0.05
-    a, b = _twins(spec, precision)
+    a, b = twins(spec, precision)
     if sgd:
         a.set_sgd(0.9, 5e-4, True)
         b.set_sgd(0.9, 5e-4, True)
     n = 11 * B + 3
     nb = n // B                                          # 11 whole batches and a remainder (B = 3: the three extra rows are a twelfth batch)
-    X, y = _random_set(a, spec, n, seed=3)
-    perm = _dev(a, np.random.default_rng(5).permutation(n).astype(np.int32))
+    X, y = random_set(a, spec, n, seed=3)
+    perm = dev(a, np.random.default_rng(5).permutation(n).astype(np.int32))
     la = torch.zeros(nb, dtype=torch.float32, device=a.device)
-    _sync()
+    sync()
     p0 = a.get_params()
-    _epoch(a, X, y, perm, B, lr, losses=la)
+    epoch(a, X, y, perm, B, lr, losses=la)
     lb = _steps(b, X, y, perm, B, lr, nb)
     assert np.array_equal(la.cpu().numpy(), lb), (la.cpu().numpy(), lb)
     assert np.array_equal(a.get_params(), b.get_params())
@@ -145,34 +91,34 @@ def test_no_permutation_split_calls_and_the_remainder():
     last whole batch are never read into a step (NaN there changes nothing)."""
     import torch
     spec, B, nb, lr = FUSED_HEAD, FUSED_HEAD[2], 11, 0.05
-    a, b = _twins(spec, "fp32")
-    c, d = _twins(spec, "fp32")
+    a, b = twins(spec, "fp32")
+    c, d = twins(spec, "fp32")
     for net in (b, c, d):
         net.set_params(a.get_params())
     n = nb * B + 3
-    X, y = _random_set(a, spec, n, seed=8)
-    ident = _dev(a, np.arange(n, dtype=np.int32))
-    perm = _dev(a, np.random.default_rng(9).permutation(n).astype(np.int32))
-    _epoch(a, X, y, None, B, lr)
-    _epoch(b, X, y, ident, B, lr)
+    X, y = random_set(a, spec, n, seed=8)
+    ident = dev(a, np.arange(n, dtype=np.int32))
+    perm = dev(a, np.random.default_rng(9).permutation(n).astype(np.int32))
+    epoch(a, X, y, None, B, lr)
+    epoch(b, X, y, ident, B, lr)
     assert np.array_equal(a.get_params(), b.get_params())
     # one call of 11 == calls of 5 and 6; the losses land in the call's own slots
     l1 = torch.zeros(nb, dtype=torch.float32, device=a.device)
     l2 = torch.zeros(nb, dtype=torch.float32, device=a.device)
-    _sync()
+    sync()
     for net in (a, b):
         net.set_params(c.get_params())
-    _epoch(a, X, y, perm, B, lr, losses=l1)
-    _epoch(b, X, y, perm, B, lr, first_batch=0, n_batches=5, losses=l2)
-    _epoch(b, X, y, perm, B, lr, first_batch=5, n_batches=6, losses=l2[5:])
+    epoch(a, X, y, perm, B, lr, losses=l1)
+    epoch(b, X, y, perm, B, lr, first_batch=0, n_batches=5, losses=l2)
+    epoch(b, X, y, perm, B, lr, first_batch=5, n_batches=6, losses=l2[5:])
     assert np.array_equal(a.get_params(), b.get_params())
     assert np.array_equal(l1.cpu().numpy(), l2.cpu().numpy())
     # the three remainder rows (perm[11 * B:]) replaced by NaN
     Xn = X.clone()
     Xn[perm[nb * B:].long()] = float("nan")
-    _sync()
-    _epoch(c, X, y, perm, B, lr)
-    _epoch(d, Xn, y, perm, B, lr)
+    sync()
+    epoch(c, X, y, perm, B, lr)
+    epoch(d, Xn, y, perm, B, lr)
     pc, pd = c.get_params(), d.get_params()
     assert np.all(np.isfinite(pd)) and np.array_equal(pc, pd) and np.array_equal(pc, a.get_params())
     for net in (a, b, c, d):
@@ -184,21 +130,21 @@ def test_no_permutation_split_calls_and_the_remainder():
 def test_an_epoch_replays_one_graph_where_train_step_on_slices_captures_twelve():
     import torch
     spec, B, nb, lr = FUSED_HEAD, FUSED_HEAD[2], 12, 0.05            # 12 batches: more than train_step's cache of 8 graphs
-    net = _net(spec)
+    net = make_net(spec)
     net.init_params(1)
     n = nb * B
-    X, y = _random_set(net, spec, n, seed=1)
+    X, y = random_set(net, spec, n, seed=1)
     rng = np.random.default_rng(2)
     g0 = net.graphs_instantiated()
     l1 = torch.zeros(nb, dtype=torch.float32, device=net.device)
-    _epoch(net, X, y, _dev(net, rng.permutation(n).astype(np.int32)), B, lr, losses=l1)
+    epoch(net, X, y, dev(net, rng.permutation(n).astype(np.int32)), B, lr, losses=l1)
     g1 = net.graphs_instantiated()
     assert 0 <= g1 - g0 <= 1, (g0, g1)
     # another permutation, another X tensor, another losses tensor: nothing is instantiated
     X2, l2 = X.clone(), torch.zeros(nb, dtype=torch.float32, device=net.device)
-    _sync()
-    _epoch(net, X2, y, _dev(net, rng.permutation(n).astype(np.int32)), B, lr, losses=l2)
-    _epoch(net, X, y, None, B, lr, first_batch=3, n_batches=4)
+    sync()
+    epoch(net, X2, y, dev(net, rng.permutation(n).astype(np.int32)), B, lr, losses=l2)
+    epoch(net, X, y, None, B, lr, first_batch=3, n_batches=4)
     assert net.graphs_instantiated() == g1
     # the trap the feature removes: train_step keys its graph by the batch's pointers, so walking a set re-captures on every step
     with torch.cuda.stream(net.stream):
@@ -207,7 +153,7 @@ def test_an_epoch_replays_one_graph_where_train_step_on_slices_captures_twelve()
     net.synchronize()
     assert net.graphs_instantiated() == g1 + nb
     # ... and the epoch's graph survived those captures
-    _epoch(net, X, y, None, B, lr)
+    epoch(net, X, y, None, B, lr)
     assert net.graphs_instantiated() == g1 + nb
     net.close()
 
@@ -218,16 +164,16 @@ def test_an_epoch_replays_one_graph_where_train_step_on_slices_captures_twelve()
 def test_uint8_rows_are_the_twice_rounded_fp32_set_bit_for_bit(spec, precision):
     import torch
     B, nb, lr = spec[2], 4, 0.05
-    a, b = _twins(spec, precision)
+    a, b = twins(spec, precision)
     n = nb * B + 2
-    Xu, y = _random_set(a, spec, n, seed=11, u8=True)
-    Xf = _dev(a, _widen(Xu.cpu().numpy()))
-    perm = _dev(a, np.random.default_rng(12).permutation(n).astype(np.int32))
+    Xu, y = random_set(a, spec, n, seed=11, u8=True)
+    Xf = dev(a, widen(Xu.cpu().numpy()))
+    perm = dev(a, np.random.default_rng(12).permutation(n).astype(np.int32))
     la = torch.zeros(nb, dtype=torch.float32, device=a.device)
     lb = torch.zeros(nb, dtype=torch.float32, device=a.device)
-    _sync()
-    _epoch(a, Xu, y, perm, B, lr, losses=la, x_scale=SCALE, x_shift=SHIFT)
-    _epoch(b, Xf, y, perm, B, lr, losses=lb)
+    sync()
+    epoch(a, Xu, y, perm, B, lr, losses=la, x_scale=SCALE, x_shift=SHIFT)
+    epoch(b, Xf, y, perm, B, lr, losses=lb)
     assert np.array_equal(la.cpu().numpy(), lb.cpu().numpy())
     assert np.array_equal(a.get_params(), b.get_params())
     sa, ca, pa = _evaluate_all(a, Xu, y, x_scale=SCALE, x_shift=SHIFT)
@@ -240,9 +186,9 @@ def test_uint8_rows_are_the_twice_rounded_fp32_set_bit_for_bit(spec, precision):
 
 def _check_eval_against_device_logits(net, spec, N, seed, u8=False):
     classes = spec[1][-1][1]
-    X, y = _random_set(net, spec, N, seed=seed, u8=u8)
+    X, y = random_set(net, spec, N, seed=seed, u8=u8)
     kw = dict(x_scale=SCALE, x_shift=SHIFT) if u8 else {}
-    Xf = _dev(net, _widen(X.cpu().numpy())) if u8 else X
+    Xf = dev(net, widen(X.cpu().numpy())) if u8 else X
     logits = _device_logits(net, Xf)
     want_pred = logits.argmax(1).numpy().astype(np.int32)            # torch's arg-max returns the first maximum
     yh = y.cpu().numpy()
@@ -265,7 +211,7 @@ def _check_eval_against_device_logits(net, spec, N, seed, u8=False):
     yb[1], yb[N - 2] = -1, classes
     good = np.ones(N, dtype=bool)
     good[[1, N - 2]] = False
-    s2, c2, p2 = _evaluate_all(net, X, _dev(net, yb), **kw)
+    s2, c2, p2 = _evaluate_all(net, X, dev(net, yb), **kw)
     assert np.array_equal(p2, pred) and c2 == int((want_pred[good] == yh[good]).sum())
     ref2 = float(_host_ce(logits.numpy().astype(np.float64)[good], yh[good]).sum())
     assert abs(float(s2[0]) - ref2) <= 2e-4 * max(1.0, ref2 / N) * N
@@ -275,7 +221,7 @@ def _check_eval_against_device_logits(net, spec, N, seed, u8=False):
 @pytest.mark.parametrize("spec,precision", SMALL, ids=SMALL_IDS)
 def test_evaluation_is_exact_against_the_devices_own_logits(spec, precision):
     """N = 2 * max_batch + 13 rows: chunked, a short last chunk, N % 8 != 0."""
-    net = _net(spec, precision)
+    net = make_net(spec, precision)
     net.init_params(3)
     N = 2 * spec[2] + 13
     assert N % 8 != 0 and N % spec[2] != 0
@@ -286,7 +232,7 @@ def test_evaluation_is_exact_against_the_devices_own_logits(spec, precision):
 def test_ties_go_to_the_first_maximum():
     spec = FUSED_HEAD
     in_shape, layers, B = spec
-    net = _net(spec)
+    net = make_net(spec)
     ws = [np.zeros(k) for k, _ in co.param_shapes(in_shape, layers)]
     bs = [np.zeros(n) for _, n in co.param_shapes(in_shape, layers)]
     rng = np.random.default_rng(1)
@@ -294,7 +240,7 @@ def test_ties_go_to_the_first_maximum():
         w[...] = rng.standard_normal(w.shape) * 0.1
     bs[-1][:4] = [1, 3, 3, 2]                                        # zero weights in the last layer: every row's logits are its biases
     net.set_params(co.flatten(ws, bs).astype(np.float32))
-    X, _ = _random_set(net, spec, 2 * B + 3, seed=2)
+    X, _ = random_set(net, spec, 2 * B + 3, seed=2)
     p = net.predict(X)
     net.synchronize()
     assert np.array_equal(p.cpu().numpy(), np.full(2 * B + 3, 1, dtype=np.int32))
@@ -327,9 +273,9 @@ def test_evaluation_matches_the_oracle(spec, precision):
     margin = srt[:, -1] - srt[:, -2]
     sure = margin > 2 * (rtol * np.abs(logits).max() + 1e-6)
     assert (~sure).sum() <= 0.10 * N, int((~sure).sum())             # asserted before anything is compared
-    net = _net(spec, precision)
+    net = make_net(spec, precision)
     net.set_params(co.flatten(ws, bs).astype(np.float32))
-    loss_sum, correct, pred = _evaluate_all(net, _dev(net, x), _dev(net, y))
+    loss_sum, correct, pred = _evaluate_all(net, dev(net, x), dev(net, y))
     ref = float(_host_ce(logits, y).mean())
     got = float(loss_sum[0]) / N
     assert abs(got - ref) <= rtol * max(1.0, ref), (got, ref)
@@ -345,12 +291,12 @@ def test_evaluation_matches_the_oracle(spec, precision):
 def test_evaluation_between_steps_changes_nothing(spec, precision):
     import torch
     B, lr = spec[2], 0.05
-    a, b = _twins(spec, precision)
+    a, b = twins(spec, precision)
     a.set_sgd(0.9, 5e-4, False)
     b.set_sgd(0.9, 5e-4, False)
-    X, y = _random_set(a, spec, 3 * B + 1, seed=4)
+    X, y = random_set(a, spec, 3 * B + 1, seed=4)
     xb, yb = X[:B].contiguous(), y[:B].contiguous()
-    _sync()
+    sync()
     for net in (a, b):                                               # the graph exists on both sides and has been replayed
         with torch.cuda.stream(net.stream):
             net.train_step(xb, yb, lr)
@@ -369,10 +315,10 @@ def test_evaluation_between_steps_changes_nothing(spec, precision):
     b.synchronize()
     assert np.array_equal(a.get_params(), b.get_params()) and np.array_equal(a.get_velocity(), b.get_velocity())
     # the same around an epoch's steps
-    _epoch(a, X, y, None, B, lr, n_batches=2)
+    epoch(a, X, y, None, B, lr, n_batches=2)
     a.evaluate(X, y)
-    _epoch(a, X, y, None, B, lr, first_batch=2, n_batches=1)
-    _epoch(b, X, y, None, B, lr)
+    epoch(a, X, y, None, B, lr, first_batch=2, n_batches=1)
+    epoch(b, X, y, None, B, lr)
     assert np.array_equal(a.get_params(), b.get_params())
     a.close(); b.close()
 
@@ -382,9 +328,9 @@ def test_evaluation_inside_an_open_bucket_walk_is_refused_and_the_walk_finishes(
     from mercer_research_amd.convnet import ConvNetError
     spec = POOL_PAIRS
     B = spec[2]
-    net = _net(spec)
+    net = make_net(spec)
     net.init_params(2)
-    X, y = _random_set(net, spec, B, seed=6)
+    X, y = random_set(net, spec, B, seed=6)
     with torch.cuda.stream(net.stream):
         want = net.gradients(X, y).clone()
         grad = torch.empty(net.n_padded, dtype=torch.float32, device=net.device)
@@ -411,14 +357,14 @@ def test_evaluation_inside_an_open_bucket_walk_is_refused_and_the_walk_finishes(
 def test_epoch_and_evaluation_at_baseline_shapes(spec, precision):
     import torch
     B, nb, lr = spec[2], 3, 0.02
-    a, b = _twins(spec, precision)
+    a, b = twins(spec, precision)
     n = nb * B + 5
-    Xu, y = _random_set(a, spec, n, seed=31, u8=True)
-    Xf = _dev(a, _widen(Xu.cpu().numpy()))
-    perm = _dev(a, np.random.default_rng(32).permutation(n).astype(np.int32))
+    Xu, y = random_set(a, spec, n, seed=31, u8=True)
+    Xf = dev(a, widen(Xu.cpu().numpy()))
+    perm = dev(a, np.random.default_rng(32).permutation(n).astype(np.int32))
     la = torch.zeros(nb, dtype=torch.float32, device=a.device)
-    _sync()
-    _epoch(a, Xu, y, perm, B, lr, losses=la, x_scale=SCALE, x_shift=SHIFT)
+    sync()
+    epoch(a, Xu, y, perm, B, lr, losses=la, x_scale=SCALE, x_shift=SHIFT)
     lb = _steps(b, Xf, y, perm, B, lr, nb)
     assert np.array_equal(la.cpu().numpy(), lb)
     assert np.array_equal(a.get_params(), b.get_params())
@@ -435,25 +381,25 @@ def test_refusals_enqueue_nothing_and_change_nothing():
     from mercer_research_amd.convnet import ConvNetError
     spec = FUSED_HEAD
     B = spec[2]
-    net = _net(spec)
+    net = make_net(spec)
     net.init_params(4)
     n = 4 * B + 1
-    X, y = _random_set(net, spec, n, seed=13)
-    perm = _dev(net, np.arange(n, dtype=np.int32))
-    _epoch(net, X, y, perm, B, 0.05)                                  # (so that a graph exists and the counter could move)
+    X, y = random_set(net, spec, n, seed=13)
+    perm = dev(net, np.arange(n, dtype=np.int32))
+    epoch(net, X, y, perm, B, 0.05)                                  # (so that a graph exists and the counter could move)
     p0, g0 = net.get_params(), net.graphs_instantiated()
     lib, h = net.lib, net.net
     xp, yp, pp = C.c_void_p(X.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(perm.data_ptr())
     ls = torch.zeros(1, dtype=torch.float64, device=net.device)
     cs = torch.zeros(1, dtype=torch.int64, device=net.device)
     pr = torch.zeros(n, dtype=torch.int32, device=net.device)
-    _sync()
+    sync()
     lp, cp, prp = C.c_void_p(ls.data_ptr()), C.c_void_p(cs.data_ptr()), C.c_void_p(pr.data_ptr())
-    epoch = lambda X_=xp, kind=0, y_=yp, n_=n, B_=B, first=0, nb=4: lib.rcn_hipx_train_epoch_dev(h, X_, kind, 1.0, 0.0, y_, n_, pp, B_, first, nb, 0.05, None)
-    assert epoch(B_=0) == -1 and epoch(B_=B + 1) == -1 and epoch(n_=0) == -1
-    assert epoch(X_=None) == -1 and epoch(y_=None) == -1 and epoch(kind=2) == -1 and epoch(kind=-1) == -1
-    assert epoch(nb=5) == -1 and epoch(first=1, nb=4) == -1 and epoch(first=-1, nb=1) == -1 and epoch(first=0, nb=-1) == -1
-    assert epoch(first=1 << 62, nb=1 << 62) == -1
+    entry = lambda X_=xp, kind=0, y_=yp, n_=n, B_=B, first=0, nb=4: lib.rcn_hipx_train_epoch_dev(h, X_, kind, 1.0, 0.0, y_, n_, pp, B_, first, nb, 0.05, None)
+    assert entry(B_=0) == -1 and entry(B_=B + 1) == -1 and entry(n_=0) == -1
+    assert entry(X_=None) == -1 and entry(y_=None) == -1 and entry(kind=2) == -1 and entry(kind=-1) == -1
+    assert entry(nb=5) == -1 and entry(first=1, nb=4) == -1 and entry(first=-1, nb=1) == -1 and entry(first=0, nb=-1) == -1
+    assert entry(first=1 << 62, nb=1 << 62) == -1
     ev = lambda X_=xp, kind=0, y_=yp, n_=n, l_=lp, c_=cp, p_=prp: lib.rcn_hipx_evaluate_dev(h, X_, kind, 1.0, 0.0, y_, n_, l_, c_, p_)
     assert ev(X_=None) == -1 and ev(kind=2) == -1 and ev(n_=0) == -1 and ev(n_=-3) == -1
     assert ev(l_=None) == -1 and ev(c_=None) == -1 and ev(y_=None, l_=None, c_=None, p_=None) == -1
@@ -470,7 +416,7 @@ def test_refusals_enqueue_nothing_and_change_nothing():
     for bad in (n, -1):
         pb = perm.clone()
         pb[3] = bad
-        _sync()
+        sync()
         with pytest.raises(ValueError):
             net.train_epoch(X, y, pb, B, 0.05)
     with pytest.raises(ValueError):

@@ -9,38 +9,22 @@ import ctypes as C
 
 import numpy as np
 import pytest
+from _convnet_util import FUSED_HEAD, KW, LR, PLAIN_HEAD, SCALE, SHIFT, dev, make_net, sync
 
 pytestmark = pytest.mark.gpu
 
-FUSED_HEAD = ((8, 8, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 32), ("dense", 10)), 5)
-PLAIN_HEAD = ((6, 6, 1), (("conv", 32), ("conv", 32), ("pool",), ("dense", 7)), 3)
 SPECS = [FUSED_HEAD, PLAIN_HEAD]
 SPEC_IDS = ["fused_head", "plain_head"]
-SCALE, SHIFT = 1.0 / 255.0, -0.1307
-LR = 0.05
 NB = 4                                                             # batches of the set: 4 * B rows
 
 
 def _net(spec, params=None):
-    from mercer_research_amd.convnet import ConvNet
-    in_shape, layers, B = spec
-    net = ConvNet(in_shape, layers, B)
+    net = make_net(spec, precision=None)
     if params is None:
         net.init_params(7)
     else:
         net.set_params(params)
     return net
-
-
-def _sync():
-    import torch
-    torch.cuda.synchronize()
-
-
-def _dev(net, a):
-    t = net.to_device(a)
-    _sync()
-    return t
 
 
 class _Calls:
@@ -54,38 +38,37 @@ class _Calls:
         (H, W, Cc), layers, B = spec
         n, classes = NB * B, layers[-1][1]
         rng = np.random.default_rng(11)
-        self.x = _dev(net, rng.standard_normal((B, H, W, Cc)).astype(np.float32))
-        self.ya = _dev(net, rng.integers(0, classes, B).astype(np.int32))
-        self.yb = _dev(net, rng.integers(0, classes, B).astype(np.int32))
-        self.w = _dev(net, np.array([0.7], dtype=np.float32))
-        self.y = _dev(net, rng.integers(0, classes, n).astype(np.int32))
+        self.x = dev(net, rng.standard_normal((B, H, W, Cc)).astype(np.float32))
+        self.ya = dev(net, rng.integers(0, classes, B).astype(np.int32))
+        self.yb = dev(net, rng.integers(0, classes, B).astype(np.int32))
+        self.w = dev(net, np.array([0.7], dtype=np.float32))
+        self.y = dev(net, rng.integers(0, classes, n).astype(np.int32))
         X = rng.integers(0, 256, (n, H, W, Cc)).astype(np.uint8)
         self.rounds = []
         for v in range(2):
             r = np.random.default_rng(100 + v)
-            self.rounds.append((_dev(net, X.copy()), _dev(net, r.permutation(n).astype(np.int32)),
-                                _dev(net, (LR * (1 + v) * (1 + np.arange(NB)) / NB).astype(np.float32)),
+            self.rounds.append((dev(net, X.copy()), dev(net, r.permutation(n).astype(np.int32)),
+                                dev(net, (LR * (1 + v) * (1 + np.arange(NB)) / NB).astype(np.float32)),
                                 net.mix_to_device(mix_plan(NB, H, W, mixup_alpha=0.4, cutmix_alpha=1.0, seed=v))))
-        _sync()
+        sync()
 
     def call(self, k, v=0, lr=LR):
         import torch
         net, B = self.net, self.B
         X, perm, sched, recs = self.rounds[v]
-        kw = dict(x_scale=SCALE, x_shift=SHIFT)
         with torch.cuda.stream(net.stream):
             if k == 1:
                 net.train_step(self.x, self.ya, lr)
             elif k == 2:
                 net.train_step_pair(self.x, self.ya, self.yb, self.w, lr)
             elif k == 3:
-                net.train_epoch(X, self.y, perm, B, lr, **kw)
+                net.train_epoch(X, self.y, perm, B, lr, **KW)
             elif k == 4:
-                net.train_epoch(X, self.y, perm, B, sched, **kw)
+                net.train_epoch(X, self.y, perm, B, sched, **KW)
             elif k == 5:
-                net.train_epoch(X, self.y, perm, B, lr, mix=recs, **kw)
+                net.train_epoch(X, self.y, perm, B, lr, mix=recs, **KW)
             else:
-                net.train_epoch(X, self.y, perm, B, sched, mix=recs, **kw)
+                net.train_epoch(X, self.y, perm, B, sched, mix=recs, **KW)
         net.synchronize()
 
     def six(self, v=0):
@@ -203,7 +186,7 @@ def test_forwarding_entries_called_directly_are_convnets_own_calls(spec):
         loss_sum = torch.zeros(1, dtype=torch.float64, device=a.device)
         correct = torch.zeros(1, dtype=torch.int64, device=a.device)
         pred = torch.full((n,), -1, dtype=torch.int32, device=a.device)
-    _sync()
+    sync()
     a._ck(a.lib.rcn_hipx_evaluate_dev(a.net, _p(X), 1, SCALE, SHIFT, _p(ca.y), n, _p(loss_sum), _p(correct), _p(pred)))
     a.synchronize()
     l2, c2, p2 = b.evaluate_async(Xb, cb.y, x_scale=SCALE, x_shift=SHIFT)

@@ -6,6 +6,7 @@ pooled-resolution gradients into the input-gradient and weight-gradient kernels,
 No reference counterpart ("parity unpinned"); tolerance as tests/test_gpu_convnet.py: |d| <= 2e-4 * scale + 1e-6."""
 import numpy as np
 import pytest
+from _convnet_util import close, make_net, oracle_params
 
 from oracle import convnet_oracle as co
 
@@ -29,27 +30,14 @@ NETS = [
 ]
 
 
-def _close(a, b, rtol=2e-4):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    scale = max(1e-3, float(np.abs(b).max()))
-    assert np.abs(a - b).max() <= rtol * scale + 1e-6, (float(np.abs(a - b).max()), scale)
-
-
 def _setup(in_shape, layers, B, tiling):
     import torch
-    from mercer_research_amd.convnet import ConvNet
     rng = np.random.default_rng(B + in_shape[0])
-    net = ConvNet(in_shape, layers, B)
-    net.set_tiling(tiling)
-    shapes = co.param_shapes(in_shape, layers)
-    ws = [rng.standard_normal(k) * np.sqrt(2.0 / k[0]) for k, _ in shapes]
-    bs = [rng.standard_normal(n) * 0.1 for _, n in shapes]
-    flat = co.flatten(ws, bs)
+    net = make_net((in_shape, layers, B), precision=None, tiling=tiling)
+    _, _, flat, w32, b32 = oracle_params(rng, in_shape, layers)
     net.set_params(flat)
     x = rng.standard_normal((B,) + in_shape).astype(np.float32)
     y = rng.integers(0, layers[-1][1], B).astype(np.int32)
-    w32 = [w.astype(np.float32).astype(np.float64) for w in ws]
-    b32 = [b.astype(np.float32).astype(np.float64) for b in bs]
     return torch, net, flat, x, y, w32, b32
 
 
@@ -64,10 +52,10 @@ def test_lds_tiled_kernels_match_oracle(in_shape, layers, B):
         loss = torch.zeros(1, dtype=torch.float32, device=net.device)
         grad = net.gradients(xd, yd, loss=loss)
     net.synchronize()
-    _close(logits.cpu().numpy(), logits_ref)
+    close(logits.cpu().numpy(), logits_ref)
     assert abs(loss.item() - loss_ref) <= 2e-4 * max(1.0, loss_ref)
     g1 = net.unpad(grad)
-    _close(g1, co.flatten(gws, gbs))
+    close(g1, co.flatten(gws, gbs))
     # fixed summation orders: a second evaluation is bit-identical
     with torch.cuda.stream(net.stream):
         grad2 = net.gradients(xd, yd)
@@ -79,12 +67,12 @@ def test_lds_tiled_kernels_match_oracle(in_shape, layers, B):
         net.train_step(xd, yd, lr, loss)
     net.synchronize()
     nw, nb, _ = co.sgd_step(x64, y, w32, b32, layers, lr)
-    _close(net.get_params(), co.flatten(nw, nb))
+    close(net.get_params(), co.flatten(nw, nb))
     with torch.cuda.stream(net.stream):
         net.train_step(xd, yd, lr, loss)
     net.synchronize()
     nw2, nb2, l2 = co.sgd_step(x64, y, nw, nb, layers, lr)
-    _close(net.get_params(), co.flatten(nw2, nb2), rtol=4e-4)
+    close(net.get_params(), co.flatten(nw2, nb2), rtol=4e-4)
     assert abs(loss.item() - l2) <= 4e-4 * max(1.0, l2)
 
 
@@ -104,8 +92,8 @@ def test_tiling_modes_agree(in_shape, layers, B):
         out[mode] = (logits.cpu().numpy(), net.unpad(grad))
         net.close()
     for mode in ("auto", "lds"):
-        _close(out[mode][0], out["gemm"][0], rtol=1e-5)
-        _close(out[mode][1], out["gemm"][1], rtol=2e-5)
+        close(out[mode][0], out["gemm"][0], rtol=1e-5)
+        close(out[mode][1], out["gemm"][1], rtol=2e-5)
 
 
 def test_set_tiling_rejects_unknown_modes():

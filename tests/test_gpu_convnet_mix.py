@@ -7,115 +7,21 @@ epoch is held bit for bit against gather_mix + train_step_pair, and an epoch tha
 and the gradients are held against the f64 restatement of tests/_mix_ref.py (pinned to the oracle and to finite differences by
 tests/test_convnet_mix_plan.py) at the tolerances tests/test_gpu_convnet.py uses for the same comparisons: loss |d| <= 2e-4 max(1, loss);
 gradients 2e-4 of scale for fp32 and 5e-3 for bf16 operands."""
-import os
 import re
-import sys
 
 import numpy as np
 import pytest
+from _convnet_util import (CIFAR, FUSED_HEAD, KW, NESTEROV, ODD_WIDTH, PLAIN_HEAD, POOL_PAIRS, close, dev, epoch, make_net, mix_records, oracle_params, random_set, same_state, sync,
+                           twins, widen, zeros)
+from _mix_ref import gather_mix_ref, soft_loss_and_grads, soft_loss_f64, soft_targets
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from _mix_ref import CIFAR, FUSED_HEAD, ODD_WIDTH, PLAIN_HEAD, POOL_PAIRS, gather_mix_ref, soft_loss_and_grads, soft_loss_f64, soft_targets  # noqa: E402
-
-from oracle import convnet_oracle as co  # noqa: E402
+from oracle import convnet_oracle as co
 
 pytestmark = pytest.mark.gpu
 
 SMALL = [(FUSED_HEAD, "fp32", False), (PLAIN_HEAD, "bf16", True), (POOL_PAIRS, "bf16_stored", False)]      # (net, precision, momentum SGD)
 SMALL_IDS = ["fused_head-fp32", "plain_head-bf16-sgd", "pool_pairs-bf16_stored"]
-SCALE, SHIFT = 1.0 / 255.0, -0.1307                                 # neither is a power of two: a padded uint8 pixel is fl(fl(0*scale)+shift) != 0
-KW = dict(x_scale=SCALE, x_shift=SHIFT)
 ORACLE_MODE = {"fp32": ("f64", False, 2e-4), "bf16": ("bf16", False, 5e-3), "bf16_stored": ("bf16", True, 5e-3)}      # (operand, stored, rtol)
-
-
-def _net(spec, precision="fp32"):
-    from mercer_research_amd.convnet import ConvNet
-    in_shape, layers, B = spec
-    net = ConvNet(in_shape, layers, B)
-    net.set_precision(precision)
-    return net
-
-
-def _twins(spec, precision, sgd=False, seed=1):
-    a = _net(spec, precision)
-    a.init_params(seed)
-    b = _net(spec, precision)
-    b.set_params(a.get_params())
-    if sgd:
-        a.set_sgd(0.9, 5e-4, True)
-        b.set_sgd(0.9, 5e-4, True)
-    return a, b
-
-
-def _sync():
-    import torch
-    torch.cuda.synchronize()
-
-
-def _dev(net, a):
-    t = net.to_device(a)
-    _sync()
-    return t
-
-
-def _random_set(net, spec, n, seed=0, u8=False):
-    in_shape, layers, _ = spec
-    rng = np.random.default_rng(seed)
-    X = rng.integers(0, 256, (n,) + in_shape).astype(np.uint8) if u8 else rng.standard_normal((n,) + in_shape).astype(np.float32)
-    y = rng.integers(0, layers[-1][1], n).astype(np.int32)
-    return _dev(net, X), _dev(net, y)
-
-
-def _widen(stored):
-    """What the gather makes of stored values: fp32 as it is; uint8 as fl(fl(u8 * scale) + shift), two roundings, built with torch."""
-    import torch
-    if stored.dtype != np.uint8:
-        return stored
-    t = torch.from_numpy(np.ascontiguousarray(stored)).float() * torch.tensor(SCALE, dtype=torch.float32)
-    return (t.float() + torch.tensor(SHIFT, dtype=torch.float32)).numpy()
-
-
-def _epoch(net, X, y, perm, B, lr, **kw):
-    import torch
-    with torch.cuda.stream(net.stream):
-        net.train_epoch(X, y, perm, B, lr, **kw)
-    net.synchronize()
-
-
-def _zeros(net, n):
-    import torch
-    t = torch.zeros(n, dtype=torch.float32, device=net.device)
-    _sync()
-    return t
-
-
-def _records(net, rows):
-    from mercer_research_amd.convnet import MIX_DTYPE
-    rec = np.array([tuple(r) for r in rows], dtype=MIX_DTYPE)
-    t = net.mix_to_device(rec)
-    _sync()
-    return rec, t
-
-
-def _same_state(a, b):
-    return np.array_equal(a.get_params(), b.get_params()) and np.array_equal(a.get_velocity(), b.get_velocity())
-
-
-def _oracle_params(rng, in_shape, layers):
-    shapes = co.param_shapes(in_shape, layers)
-    ws = [rng.standard_normal(k) * np.sqrt(2.0 / k[0]) for k, _ in shapes]
-    bs = [rng.standard_normal(n) * 0.1 for _, n in shapes]
-    w32 = [w.astype(np.float32).astype(np.float64) for w in ws]
-    b32 = [b.astype(np.float32).astype(np.float64) for b in bs]
-    return co.flatten(ws, bs), w32, b32
-
-
-def _close(a, b, rtol=2e-4):
-    """tests/test_gpu_convnet.py's"""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    scale = max(1e-3, float(np.abs(b).max()))
-    print("max |d| =", float(np.abs(a - b).max()), "scale =", scale, "rtol =", rtol)
-    assert np.abs(a - b).max() <= rtol * scale + 1e-6, (float(np.abs(a - b).max()), scale)
 
 
 # ---- 1. the mixing gather is the formula -----------------------------------------------------------------------------------------------
@@ -137,24 +43,24 @@ GATHER_IDS = ["%dx%dx%d-b%d-%s-%s" % (s[0] + (B, "uint8" if u8 else "fp32", "aug
 def test_gather_mix_is_the_blend_and_the_box_of_the_two_gathered_rows_bit_for_bit(spec, B, u8, aug):
     from mercer_research_amd.convnet import Augment
     (H, W, _), _, _ = spec
-    net = _net(spec)
+    net = make_net(spec)
     n = 2 * B + 3
-    X, y = _random_set(net, spec, n, seed=41, u8=u8)
+    X, y = random_set(net, spec, n, seed=41, u8=u8)
     Xh, yh = X.cpu().numpy(), y.cpu().numpy()
     idxh = np.random.default_rng(42).permutation(n).astype(np.int32)[:B]
-    idx = _dev(net, idxh)
+    idx = dev(net, idxh)
     augment = Augment(2, True, 7, 3) if aug else None
     q0 = 3 * B
-    recs, recs_dev = _records(net, _mix_cases(H, W))
+    recs, recs_dev = mix_records(net, _mix_cases(H, W))
     plain, yp = net.gather_batch(X, y, idx, B, augment=augment, q0=q0, **KW)
     net.synchronize()
     plain = plain.cpu().numpy()
-    assert plain.tobytes() == gather_mix_ref(Xh[idxh], recs[-1].tolist(), _widen, (2, True, 7, 3) if aug else None, q0).tobytes()
+    assert plain.tobytes() == gather_mix_ref(Xh[idxh], recs[-1].tolist(), widen, (2, True, 7, 3) if aug else None, q0).tobytes()
     seen = set()
     for k, rec in enumerate(recs):
         x, ya, yb = net.gather_mix(X, y, idx, B, recs_dev[k:k + 1], augment=augment, q0=q0, **KW)
         net.synchronize()
-        want = gather_mix_ref(Xh[idxh], rec.tolist(), _widen, (2, True, 7, 3) if aug else None, q0)
+        want = gather_mix_ref(Xh[idxh], rec.tolist(), widen, (2, True, 7, 3) if aug else None, q0)
         got = x.cpu().numpy()
         assert np.array_equal(got, want) and got.tobytes() == want.tobytes(), (k, rec)
         assert np.array_equal(ya.cpu().numpy(), yh[idxh]) and np.array_equal(yb.cpu().numpy(), yh[idxh[::-1]]), k
@@ -169,7 +75,7 @@ def test_gather_mix_is_the_blend_and_the_box_of_the_two_gathered_rows_bit_for_bi
     x, ya, yb = net.gather_mix(X, None, None, B, recs_dev[0:1], base=2, augment=augment, q0=q0, **KW)
     net.synchronize()
     assert ya is None and yb is None
-    assert np.array_equal(x.cpu().numpy(), gather_mix_ref(Xh[2:2 + B], recs[0].tolist(), _widen, (2, True, 7, 3) if aug else None, q0))
+    assert np.array_equal(x.cpu().numpy(), gather_mix_ref(Xh[2:2 + B], recs[0].tolist(), widen, (2, True, 7, 3) if aug else None, q0))
     net.close()
 
 
@@ -181,22 +87,22 @@ def _pair_batch(net, spec, seed):
     x = rng.standard_normal((B,) + in_shape).astype(np.float32)
     ya = rng.integers(0, layers[-1][1], B).astype(np.int32)
     yb = rng.integers(0, layers[-1][1], B).astype(np.int32)
-    return x, ya, yb, _dev(net, x), _dev(net, ya), _dev(net, yb)
+    return x, ya, yb, dev(net, x), dev(net, ya), dev(net, yb)
 
 
 @pytest.mark.parametrize("eps", [0.0, 0.1])
 @pytest.mark.parametrize("spec,precision,sgd", SMALL, ids=SMALL_IDS)
 def test_pair_step_reports_the_soft_loss_of_its_own_logits(spec, precision, sgd, eps):
     import torch
-    net = _net(spec, precision)
+    net = make_net(spec, precision)
     net.init_params(2)
     if sgd:
         net.set_sgd(0.9, 5e-4, True)
     net.set_loss(eps)
     assert net.get_loss() == float(np.float32(eps))
     x, ya, yb, xd, yad, ybd = _pair_batch(net, spec, 51)
-    w = _dev(net, np.array([0.3], dtype=np.float32))
-    loss = _zeros(net, 1)
+    w = dev(net, np.array([0.3], dtype=np.float32))
+    loss = zeros(net, 1)
     p0 = net.get_params()
     with torch.cuda.stream(net.stream):
         logits = net.forward(xd)
@@ -218,25 +124,25 @@ def test_smoothed_gradients_match_the_restated_oracle(spec, precision, sgd):
     in_shape, layers, B = spec
     operand, stored, rtol = ORACLE_MODE[precision]
     rng = np.random.default_rng(B + 7)
-    net = _net(spec, precision)
-    flat, w32, b32 = _oracle_params(rng, in_shape, layers)
+    net = make_net(spec, precision)
+    _, _, flat, w32, b32 = oracle_params(rng, in_shape, layers)
     net.set_params(flat)
     net.set_loss(0.1)
     x = rng.standard_normal((B,) + in_shape).astype(np.float32)
     y = rng.integers(0, layers[-1][1], B).astype(np.int32)
-    xd, yd = _dev(net, x), _dev(net, y)
+    xd, yd = dev(net, x), dev(net, y)
     T = soft_targets(y, y, 1.0, float(np.float32(0.1)), layers[-1][1])
     loss_ref, _, gws, gbs = soft_loss_and_grads(x.astype(np.float64), T, w32, b32, layers, operand, stored)
-    loss = _zeros(net, 1)
+    loss = zeros(net, 1)
     with torch.cuda.stream(net.stream):
         grad = net.gradients(xd, yd, loss=loss)
     net.synchronize()
     print("loss", loss.item(), "ref", loss_ref)
     assert abs(loss.item() - loss_ref) <= rtol * max(1.0, loss_ref)
-    _close(net.unpad(grad), co.flatten(gws, gbs), rtol=rtol)
+    close(net.unpad(grad), co.flatten(gws, gbs), rtol=rtol)
     # the bucketed walk computes the same loss and gradients
     grad2 = torch.zeros_like(grad)
-    loss2 = _zeros(net, 1)                                           # (synchronises: grad2 is ready)
+    loss2 = zeros(net, 1)                                           # (synchronises: grad2 is ready)
     with torch.cuda.stream(net.stream):
         net.gradients_bucketed(xd, yd, grad2, loss=loss2, min_bucket_bytes=0)
     net.synchronize()
@@ -251,19 +157,19 @@ def test_pair_step_moves_the_parameters_by_the_restated_gradient(spec, precision
     in_shape, layers, B = spec
     operand, stored, rtol = ORACLE_MODE[precision]
     rng = np.random.default_rng(B + 9)
-    net = _net(spec, precision)
-    flat, w32, b32 = _oracle_params(rng, in_shape, layers)
+    net = make_net(spec, precision)
+    _, _, flat, w32, b32 = oracle_params(rng, in_shape, layers)
     net.set_params(flat)
     net.set_loss(0.1)
     x, ya, yb, xd, yad, ybd = _pair_batch(net, spec, 61)
-    w = _dev(net, np.array([0.3], dtype=np.float32))
+    w = dev(net, np.array([0.3], dtype=np.float32))
     T = soft_targets(ya, yb, float(np.float32(0.3)), float(np.float32(0.1)), layers[-1][1])
     _, _, gws, gbs = soft_loss_and_grads(x.astype(np.float64), T, w32, b32, layers, operand, stored)
     p0 = net.get_params()
     with torch.cuda.stream(net.stream):
         net.train_step_pair(xd, yad, ybd, w, 1.0)
     net.synchronize()
-    _close(p0.astype(np.float64) - net.get_params().astype(np.float64), co.flatten(gws, gbs), rtol=rtol)
+    close(p0.astype(np.float64) - net.get_params().astype(np.float64), co.flatten(gws, gbs), rtol=rtol)
     net.close()
 
 
@@ -272,13 +178,13 @@ def test_pair_step_moves_the_parameters_by_the_restated_gradient(spec, precision
 @pytest.mark.parametrize("spec,precision,sgd", SMALL, ids=SMALL_IDS)
 def test_swapping_the_pair_and_the_weight_changes_no_bit(spec, precision, sgd):
     import torch
-    a, b = _twins(spec, precision, sgd)
+    a, b = twins(spec, precision, sgd=NESTEROV if sgd else None)
     for net in (a, b):
         net.set_loss(0.1)
     x, ya, yb, xd, yad, ybd = _pair_batch(a, spec, 71)
     assert not np.array_equal(ya, yb)
-    wa, wb = _dev(a, np.array([0.25], dtype=np.float32)), _dev(a, np.array([0.75], dtype=np.float32))
-    la, lb = _zeros(a, 1), _zeros(a, 1)
+    wa, wb = dev(a, np.array([0.25], dtype=np.float32)), dev(a, np.array([0.75], dtype=np.float32))
+    la, lb = zeros(a, 1), zeros(a, 1)
     p0 = a.get_params()
     for _ in range(2):                                               # the eager step, then its graph
         with torch.cuda.stream(a.stream):
@@ -286,7 +192,7 @@ def test_swapping_the_pair_and_the_weight_changes_no_bit(spec, precision, sgd):
         with torch.cuda.stream(b.stream):
             b.train_step_pair(xd, ybd, yad, wb, 0.05, lb)
         a.synchronize(); b.synchronize()
-        assert la.cpu().numpy().tobytes() == lb.cpu().numpy().tobytes() and _same_state(a, b)
+        assert la.cpu().numpy().tobytes() == lb.cpu().numpy().tobytes() and same_state(a, b)
     assert not np.array_equal(a.get_params(), p0) and np.isfinite(la.item())
     a.close(); b.close()
 
@@ -299,30 +205,30 @@ def test_mixed_epoch_is_gather_mix_and_train_step_pair_bit_for_bit(spec, precisi
     from mercer_research_amd.convnet import Augment, mix_plan
     (H, W, _), _, B = spec
     nb = 4
-    a, b = _twins(spec, precision, sgd)
+    a, b = twins(spec, precision, sgd=NESTEROV if sgd else None)
     for net in (a, b):
         net.set_loss(0.1)
     n = nb * B + 1
-    X, y = _random_set(a, spec, n, seed=81, u8=precision != "bf16")
-    perm = _dev(a, np.random.default_rng(82).permutation(n).astype(np.int32))
+    X, y = random_set(a, spec, n, seed=81, u8=precision != "bf16")
+    perm = dev(a, np.random.default_rng(82).permutation(n).astype(np.int32))
     rates = (0.002 * (1 + np.arange(nb))).astype(np.float32)
-    lr = _dev(a, rates)
+    lr = dev(a, rates)
     aug = Augment(2, True, 11, 0)
     rec = mix_plan(nb, H, W, mixup_alpha=0.8, cutmix_alpha=1.0, seed=5)
     rec[0] = (0.4, 0.4, 0, 0, 0, 0)                                  # whatever the draws are: one mixup step and one CutMix step
     rec[1] = (1.0, np.float32(1.0 - 6.0 / (H * W)), 1, 3, 2, 5)
     recs_dev = a.mix_to_device(rec)
-    _sync()
+    sync()
     # a plain epoch first: its graph must survive the mixed ones
-    _epoch(a, X, y, perm, B, lr, augment=aug, **KW)
-    _epoch(b, X, y, perm, B, lr, augment=aug, **KW)
-    assert _same_state(a, b)
+    epoch(a, X, y, perm, B, lr, augment=aug, **KW)
+    epoch(b, X, y, perm, B, lr, augment=aug, **KW)
+    assert same_state(a, b)
     g_plain = a.graphs_instantiated()
-    la = _zeros(a, nb)
-    _epoch(a, X, y, perm, B, lr, losses=la, augment=aug, mix=recs_dev, **KW)
+    la = zeros(a, nb)
+    epoch(a, X, y, perm, B, lr, losses=la, augment=aug, mix=recs_dev, **KW)
     g_mix = a.graphs_instantiated()
     assert g_mix - g_plain == 1
-    lb = _zeros(b, nb)
+    lb = zeros(b, nb)
     keep = []
     with torch.cuda.stream(b.stream):
         for s in range(nb):
@@ -332,15 +238,15 @@ def test_mixed_epoch_is_gather_mix_and_train_step_pair_bit_for_bit(spec, precisi
             b.train_step_pair(x, ya, yb, w, float(rates[s]), lb[s:s + 1])
     b.synchronize()
     assert np.array_equal(la.cpu().numpy(), lb.cpu().numpy()), (la.cpu().numpy(), lb.cpu().numpy())
-    assert _same_state(a, b)
+    assert same_state(a, b)
     assert np.all(np.isfinite(lb.cpu().numpy())) and np.all(lb.cpu().numpy() > 0)
     # other records, another schedule: the same graph; and the plain epoch still replays its own
     rec2 = mix_plan(nb, H, W, cutmix_alpha=1.0, seed=6)
-    lr2 = _dev(a, (rates * np.float32(0.37)).astype(np.float32))
-    _epoch(a, X, y, perm, B, lr2, augment=aug, mix=a.mix_to_device(rec2), **KW)
-    _epoch(a, X, y, None, B, lr2[1:3].contiguous(), first_batch=1, n_batches=2, mix=a.mix_to_device(rec2[1:3]), **KW)
+    lr2 = dev(a, (rates * np.float32(0.37)).astype(np.float32))
+    epoch(a, X, y, perm, B, lr2, augment=aug, mix=a.mix_to_device(rec2), **KW)
+    epoch(a, X, y, None, B, lr2[1:3].contiguous(), first_batch=1, n_batches=2, mix=a.mix_to_device(rec2[1:3]), **KW)
     assert a.graphs_instantiated() == g_mix
-    _epoch(a, X, y, perm, B, lr, augment=aug, **KW)
+    epoch(a, X, y, perm, B, lr, augment=aug, **KW)
     assert a.graphs_instantiated() == g_mix
     a.close(); b.close()
 
@@ -351,18 +257,18 @@ def test_mixed_epoch_is_gather_mix_and_train_step_pair_bit_for_bit(spec, precisi
 def test_records_that_mix_nothing_give_the_unmixed_epoch_bit_for_bit(spec, precision, sgd):
     from mercer_research_amd.convnet import Augment
     B, nb = spec[2], 4
-    a, b = _twins(spec, precision, sgd)
+    a, b = twins(spec, precision, sgd=NESTEROV if sgd else None)
     assert a.get_loss() == 0.0
     n = nb * B + 2
-    X, y = _random_set(a, spec, n, seed=91, u8=precision != "bf16")
-    perm = _dev(a, np.random.default_rng(92).permutation(n).astype(np.int32))
-    _, recs_dev = _records(a, [(1.0, 1.0, 0, 0, 0, 0)] * nb)
-    la, lb = _zeros(a, nb), _zeros(b, nb)
-    for lr, aug in ((0.03, None), (_dev(a, (0.01 * (1 + np.arange(nb))).astype(np.float32)), Augment(1, True, 3, 0))):
-        _epoch(a, X, y, perm, B, lr, losses=la, augment=aug, mix=recs_dev, **KW)
-        _epoch(b, X, y, perm, B, lr, losses=lb, augment=aug, **KW)
+    X, y = random_set(a, spec, n, seed=91, u8=precision != "bf16")
+    perm = dev(a, np.random.default_rng(92).permutation(n).astype(np.int32))
+    _, recs_dev = mix_records(a, [(1.0, 1.0, 0, 0, 0, 0)] * nb)
+    la, lb = zeros(a, nb), zeros(b, nb)
+    for lr, aug in ((0.03, None), (dev(a, (0.01 * (1 + np.arange(nb))).astype(np.float32)), Augment(1, True, 3, 0))):
+        epoch(a, X, y, perm, B, lr, losses=la, augment=aug, mix=recs_dev, **KW)
+        epoch(b, X, y, perm, B, lr, losses=lb, augment=aug, **KW)
         assert la.cpu().numpy().tobytes() == lb.cpu().numpy().tobytes(), (la.cpu().numpy(), lb.cpu().numpy())
-        assert _same_state(a, b)
+        assert same_state(a, b)
     a.close(); b.close()
 
 
@@ -374,8 +280,8 @@ def test_set_loss_refusals_round_trip_evaluation_and_plans():
     soft = re.compile(r"k_softmax_ce_soft|k_head_f32<true, true>")
     for spec in (FUSED_HEAD, PLAIN_HEAD):
         B = spec[2]
-        a, b = _twins(spec, "fp32")
-        X, y = _random_set(a, spec, 3 * B, seed=95, u8=True)
+        a, b = twins(spec, "fp32")
+        X, y = random_set(a, spec, 3 * B, seed=95, u8=True)
         a.set_loss(0.25)
         for bad in (-0.1, 1.0, float("nan"), float("inf"), -float("inf")):
             assert a.lib.rcn_hipx_set_loss(a.net, bad) == -1 and b"set_loss" in a.lib.rcn_hipx_last_error(a.net)
@@ -393,7 +299,7 @@ def test_set_loss_refusals_round_trip_evaluation_and_plans():
         # a smoothed step differs from a plain one ...
         x, ya, yb, xd, yad, ybd = _pair_batch(a, spec, 96)
         p0 = a.get_params()
-        la, lb = _zeros(a, 1), _zeros(b, 1)
+        la, lb = zeros(a, 1), zeros(b, 1)
         with torch.cuda.stream(a.stream):
             a.train_step(xd, yad, 0.05, la)
         a.synchronize()
@@ -433,9 +339,9 @@ def test_set_loss_refusals_round_trip_evaluation_and_plans():
                 assert a.plan_epoch_of_this_net(B, "uint8", sched, aug, mix=False) == a.plan_epoch_of_this_net(B, "uint8", sched, aug)
         a.close(); b.close()
     # the 16-byte and the scalar path of the mixing gather, as the plan names them
-    c = _net(CIFAR)
+    c = make_net(CIFAR)
     assert "k_gather_mix<uint8, 4>, one or two source elements per output, 16-byte stores, 1536 workgroups" in c.plan_epoch_of_this_net(512, "uint8", mix=True)
     c.close()
-    o = _net(ODD_WIDTH)
+    o = make_net(ODD_WIDTH)
     assert "k_gather_mix<float, 1>, element by element, 1 workgroups" in o.plan_epoch_of_this_net(4, "float32", mix=True)
     o.close()

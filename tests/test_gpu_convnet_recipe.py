@@ -7,93 +7,24 @@ train_step fed those floats one by one; the augmented gather moves stored values
 bit for bit against np.pad + slice + reverse of the stored rows (tests/_recipe_ref.py) widened with the two roundings of
 tests/test_gpu_convnet_epoch.py; an augmented epoch is held against gather_batch + train_step."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
-
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from _recipe_ref import augment_ref  # noqa: E402
+from _convnet_util import (CIFAR, FUSED_HEAD, NESTEROV, ODD_WIDTH, PLAIN_HEAD, POOL_PAIRS, SCALE, SHIFT, dev, epoch, make_net, random_set, same_state, sync, twins, widen,
+                           zeros)
+from _recipe_ref import augment_ref
 
 pytestmark = pytest.mark.gpu
 
-FUSED_HEAD = ((8, 8, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 32), ("dense", 10)), 5)
-PLAIN_HEAD = ((6, 6, 1), (("conv", 32), ("conv", 32), ("pool",), ("dense", 7)), 3)                  # E = 36: the scalar path of a uint8 set
-POOL_PAIRS = ((16, 16, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 128), ("dense", 10)), 64)
-ODD_WIDTH = ((5, 7, 1), (("conv", 32), ("dense", 6)), 4)                                            # E = 35: element by element for fp32 too
-CIFAR = ((32, 32, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("conv", 128), ("pool",), ("dense_relu", 256), ("dense", 10)), 512)
 SMALL = [(FUSED_HEAD, "fp32", False), (PLAIN_HEAD, "bf16", True), (POOL_PAIRS, "bf16_stored", False)]      # (net, precision, momentum SGD)
 SMALL_IDS = ["fused_head-fp32", "plain_head-bf16-sgd", "pool_pairs-bf16_stored"]
-SCALE, SHIFT = 1.0 / 255.0, -0.1307                                 # neither is a power of two: a padded uint8 pixel is fl(fl(0*scale)+shift) != 0
-
-
-def _net(spec, precision="fp32"):
-    from mercer_research_amd.convnet import ConvNet
-    in_shape, layers, B = spec
-    net = ConvNet(in_shape, layers, B)
-    net.set_precision(precision)
-    return net
-
-
-def _twins(spec, precision, sgd=False, seed=1):
-    a = _net(spec, precision)
-    a.init_params(seed)
-    b = _net(spec, precision)
-    b.set_params(a.get_params())
-    if sgd:
-        a.set_sgd(0.9, 5e-4, True)
-        b.set_sgd(0.9, 5e-4, True)
-    return a, b
-
-
-def _sync():
-    import torch
-    torch.cuda.synchronize()
-
-
-def _dev(net, a):
-    t = net.to_device(a)
-    _sync()
-    return t
-
-
-def _random_set(net, spec, n, seed=0, u8=False):
-    in_shape, layers, _ = spec
-    rng = np.random.default_rng(seed)
-    X = rng.integers(0, 256, (n,) + in_shape).astype(np.uint8) if u8 else rng.standard_normal((n,) + in_shape).astype(np.float32)
-    y = rng.integers(0, layers[-1][1], n).astype(np.int32)
-    return _dev(net, X), _dev(net, y)
-
-
-def _widen(stored):
-    """What the gather makes of stored values: fp32 as it is; uint8 as fl(fl(u8 * scale) + shift), two roundings, built with torch."""
-    import torch
-    if stored.dtype != np.uint8:
-        return stored
-    t = torch.from_numpy(np.ascontiguousarray(stored)).float() * torch.tensor(SCALE, dtype=torch.float32)
-    return (t.float() + torch.tensor(SHIFT, dtype=torch.float32)).numpy()
-
-
-def _epoch(net, X, y, perm, B, lr, **kw):
-    import torch
-    with torch.cuda.stream(net.stream):
-        net.train_epoch(X, y, perm, B, lr, **kw)
-    net.synchronize()
-
-
-def _zeros(net, n):
-    import torch
-    t = torch.zeros(n, dtype=torch.float32, device=net.device)
-    _sync()
-    return t
 
 
 def _steps(net, X, y, perm, B, rates, augment=None, **kw):
     """Batches 0 .. len(rates) - 1 fed to train_step one by one with rates[s] as a float; gathered with torch, or -- with an augmentation --
     with gather_batch at q0 = s * B.  Returns the per-step losses."""
     import torch
-    losses = _zeros(net, len(rates))
+    losses = zeros(net, len(rates))
     keep = []
     with torch.cuda.stream(net.stream):
         for s, lr in enumerate(rates):
@@ -116,26 +47,22 @@ def _schedule(nb):
     return lr
 
 
-def _same_state(a, b):
-    return np.array_equal(a.get_params(), b.get_params()) and np.array_equal(a.get_velocity(), b.get_velocity())
-
-
 # ---- 1. a scheduled epoch is its steps, bit for bit ------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("spec,precision,sgd", SMALL, ids=SMALL_IDS)
 def test_scheduled_epoch_is_train_step_with_those_rates_bit_for_bit(spec, precision, sgd):
     B, nb = spec[2], 11
-    a, b = _twins(spec, precision, sgd)
+    a, b = twins(spec, precision, sgd=NESTEROV if sgd else None)
     n = nb * B + 2
-    X, y = _random_set(a, spec, n, seed=3)
-    perm = _dev(a, np.random.default_rng(5).permutation(n).astype(np.int32))
+    X, y = random_set(a, spec, n, seed=3)
+    perm = dev(a, np.random.default_rng(5).permutation(n).astype(np.int32))
     rates = _schedule(nb)
-    la = _zeros(a, nb)
+    la = zeros(a, nb)
     p0 = a.get_params()
-    _epoch(a, X, y, perm, B, _dev(a, rates), losses=la)
+    epoch(a, X, y, perm, B, dev(a, rates), losses=la)
     lb = _steps(b, X, y, perm, B, rates)
     assert np.array_equal(la.cpu().numpy(), lb), (la.cpu().numpy(), lb)
-    assert _same_state(a, b)
+    assert same_state(a, b)
     assert not np.array_equal(a.get_params(), p0) and np.all(np.isfinite(lb)) and (not sgd or np.abs(a.get_velocity()).max() > 0)
     a.close(); b.close()
 
@@ -144,30 +71,30 @@ def test_scheduled_epoch_is_train_step_with_those_rates_bit_for_bit(spec, precis
 
 def test_every_schedule_replays_one_graph_where_float_rates_capture_twelve():
     spec, B, nb = FUSED_HEAD, FUSED_HEAD[2], 12
-    net = _net(spec)
+    net = make_net(spec)
     net.init_params(1)
     n = nb * B
-    X, y = _random_set(net, spec, n, seed=1)
+    X, y = random_set(net, spec, n, seed=1)
     rng = np.random.default_rng(2)
     g0 = net.graphs_instantiated()
-    _epoch(net, X, y, _dev(net, rng.permutation(n).astype(np.int32)), B, _dev(net, _schedule(nb)), losses=_zeros(net, nb))
+    epoch(net, X, y, dev(net, rng.permutation(n).astype(np.int32)), B, dev(net, _schedule(nb)), losses=zeros(net, nb))
     g1 = net.graphs_instantiated()
     assert 0 <= g1 - g0 <= 1, (g0, g1)
     # another schedule, another X tensor, a split call on a slice of the schedule: nothing is instantiated
-    other = _dev(net, (_schedule(nb) * np.float32(0.37)).astype(np.float32))
+    other = dev(net, (_schedule(nb) * np.float32(0.37)).astype(np.float32))
     X2 = X.clone()
-    _sync()
-    _epoch(net, X2, y, _dev(net, rng.permutation(n).astype(np.int32)), B, other)
-    _epoch(net, X, y, None, B, other[3:7].contiguous(), first_batch=3, n_batches=4)
+    sync()
+    epoch(net, X2, y, dev(net, rng.permutation(n).astype(np.int32)), B, other)
+    epoch(net, X, y, None, B, other[3:7].contiguous(), first_batch=3, n_batches=4)
     assert net.graphs_instantiated() == g1
     # the trap the schedule removes: a float rate is part of the graph's key, so twelve one-batch calls with twelve rates capture twelve times
     floats = [float(v) for v in (0.001 * (1 + np.arange(nb))).astype(np.float32)]
     for s, lr in enumerate(floats):
-        _epoch(net, X, y, None, B, lr, first_batch=s, n_batches=1)
+        epoch(net, X, y, None, B, lr, first_batch=s, n_batches=1)
     assert net.graphs_instantiated() == g1 + nb
     # the scheduled graph lives beside those and survived them; a constant-rate graph of an earlier call (the cache keeps eight) still replays
-    _epoch(net, X, y, None, B, other)
-    _epoch(net, X, y, None, B, floats[-1], n_batches=2)
+    epoch(net, X, y, None, B, other)
+    epoch(net, X, y, None, B, floats[-1], n_batches=2)
     assert net.graphs_instantiated() == g1 + nb
     net.close()
 
@@ -176,16 +103,16 @@ def test_every_schedule_replays_one_graph_where_float_rates_capture_twelve():
 
 def test_split_scheduled_calls_are_the_whole_call():
     spec, B, nb = FUSED_HEAD, FUSED_HEAD[2], 11
-    a, b = _twins(spec, "fp32", sgd=True)
+    a, b = twins(spec, "fp32", sgd=NESTEROV)
     n = nb * B + 1
-    X, y = _random_set(a, spec, n, seed=8)
-    perm = _dev(a, np.random.default_rng(9).permutation(n).astype(np.int32))
-    lr = _dev(a, _schedule(nb))
-    l1, l2 = _zeros(a, nb), _zeros(a, nb)
-    _epoch(a, X, y, perm, B, lr, losses=l1)
-    _epoch(b, X, y, perm, B, lr[:5], first_batch=0, n_batches=5, losses=l2)
-    _epoch(b, X, y, perm, B, lr[5:], first_batch=5, n_batches=6, losses=l2[5:])
-    assert np.array_equal(l1.cpu().numpy(), l2.cpu().numpy()) and _same_state(a, b)
+    X, y = random_set(a, spec, n, seed=8)
+    perm = dev(a, np.random.default_rng(9).permutation(n).astype(np.int32))
+    lr = dev(a, _schedule(nb))
+    l1, l2 = zeros(a, nb), zeros(a, nb)
+    epoch(a, X, y, perm, B, lr, losses=l1)
+    epoch(b, X, y, perm, B, lr[:5], first_batch=0, n_batches=5, losses=l2)
+    epoch(b, X, y, perm, B, lr[5:], first_batch=5, n_batches=6, losses=l2[5:])
+    assert np.array_equal(l1.cpu().numpy(), l2.cpu().numpy()) and same_state(a, b)
     a.close(); b.close()
 
 
@@ -196,12 +123,12 @@ def test_split_scheduled_calls_are_the_whole_call():
 def test_augmented_gather_is_pad_crop_flip_of_the_stored_rows_bit_for_bit(spec, u8):
     from mercer_research_amd.convnet import Augment
     (H, W, _), _, B = spec
-    net = _net(spec)
+    net = make_net(spec)
     n = 3 * B + 2
-    X, y = _random_set(net, spec, n, seed=17, u8=u8)
+    X, y = random_set(net, spec, n, seed=17, u8=u8)
     Xh, yh = X.cpu().numpy(), y.cpu().numpy()
     permh = np.random.default_rng(18).permutation(n).astype(np.int32)
-    perm = _dev(net, permh)
+    perm = dev(net, permh)
     kw = dict(x_scale=SCALE, x_shift=SHIFT)
     seen = set()
     for pad in (0, 1, 2, min(H, W) - 1):
@@ -211,7 +138,7 @@ def test_augmented_gather_is_pad_crop_flip_of_the_stored_rows_bit_for_bit(spec, 
                 for idx, base, rows in ((perm[B:2 * B].contiguous(), 0, permh[B:2 * B]), (None, B + 1, np.arange(B + 1, 2 * B + 1))):
                     x, yy = net.gather_batch(X, y, idx, B, base=base, augment=aug, q0=q0, **kw)
                     net.synchronize()
-                    want = _widen(augment_ref(Xh[rows], pad, hflip, 7, 2, q0))
+                    want = widen(augment_ref(Xh[rows], pad, hflip, 7, 2, q0))
                     assert x.cpu().numpy().tobytes() == want.tobytes(), (pad, hflip, q0, idx is None)
                     assert np.array_equal(yy.cpu().numpy(), yh[rows])
                     seen.add(want.tobytes())
@@ -221,9 +148,9 @@ def test_augmented_gather_is_pad_crop_flip_of_the_stored_rows_bit_for_bit(spec, 
     ident, yi = net.gather_batch(X, y, perm, B, augment=Augment(pad=0, hflip=False, seed=9, epoch=9), q0=123, **kw)
     nolab, none = net.gather_batch(X, None, perm, B, augment=Augment(pad=1, hflip=True, seed=7, epoch=2), **kw)
     net.synchronize()
-    assert plain.cpu().numpy().tobytes() == ident.cpu().numpy().tobytes() == _widen(Xh[permh[:B]]).tobytes()
+    assert plain.cpu().numpy().tobytes() == ident.cpu().numpy().tobytes() == widen(Xh[permh[:B]]).tobytes()
     assert np.array_equal(yp.cpu().numpy(), yi.cpu().numpy()) and none is None
-    assert nolab.cpu().numpy().tobytes() == _widen(augment_ref(Xh[permh[:B]], 1, True, 7, 2, 0)).tobytes()
+    assert nolab.cpu().numpy().tobytes() == widen(augment_ref(Xh[permh[:B]], 1, True, 7, 2, 0)).tobytes()
     net.close()
 
 
@@ -233,36 +160,36 @@ def test_augmented_gather_is_pad_crop_flip_of_the_stored_rows_bit_for_bit(spec, 
 def test_augmented_epoch_is_its_gathered_batches_fed_to_train_step_bit_for_bit(spec, precision, sgd):
     from mercer_research_amd.convnet import Augment
     B, nb = spec[2], 6
-    a, b = _twins(spec, precision, sgd)
-    c, d = _twins(spec, precision, sgd)
+    a, b = twins(spec, precision, sgd=NESTEROV if sgd else None)
+    c, d = twins(spec, precision, sgd=NESTEROV if sgd else None)
     p0 = a.get_params()
     for net in (c, d):
         net.set_params(p0)
     n = nb * B + 1
     u8 = precision != "bf16"                                         # two uint8 sets and an fp32 one
-    X, y = _random_set(a, spec, n, seed=23, u8=u8)
-    perm = _dev(a, np.random.default_rng(24).permutation(n).astype(np.int32))
+    X, y = random_set(a, spec, n, seed=23, u8=u8)
+    perm = dev(a, np.random.default_rng(24).permutation(n).astype(np.int32))
     rates = _schedule(nb)
-    lr = _dev(a, rates)
+    lr = dev(a, rates)
     aug = Augment(pad=2, hflip=True, seed=11, epoch=0)
     kw = dict(x_scale=SCALE, x_shift=SHIFT)
-    la, lc = _zeros(a, nb), _zeros(a, nb)
-    _epoch(a, X, y, perm, B, lr, losses=la, augment=aug, **kw)
+    la, lc = zeros(a, nb), zeros(a, nb)
+    epoch(a, X, y, perm, B, lr, losses=la, augment=aug, **kw)
     lb = _steps(b, X, y, perm, B, rates, augment=aug, **kw)
     assert np.array_equal(la.cpu().numpy(), lb), (la.cpu().numpy(), lb)
-    assert _same_state(a, b)
+    assert same_state(a, b)
     # a split call gives the same bits as the whole: a draw depends on the absolute position only
-    _epoch(c, X, y, perm, B, lr[:2], first_batch=0, n_batches=2, losses=lc, augment=aug, **kw)
-    _epoch(c, X, y, perm, B, lr[2:], first_batch=2, n_batches=4, losses=lc[2:], augment=aug, **kw)
-    assert np.array_equal(lc.cpu().numpy(), lb) and _same_state(a, c)
+    epoch(c, X, y, perm, B, lr[:2], first_batch=0, n_batches=2, losses=lc, augment=aug, **kw)
+    epoch(c, X, y, perm, B, lr[2:], first_batch=2, n_batches=4, losses=lc[2:], augment=aug, **kw)
+    assert np.array_equal(lc.cpu().numpy(), lb) and same_state(a, c)
     # the same call from the same state gives the same bits; another epoch value gives other draws, so other parameters
     pa = a.get_params()
     for net in (a, d):
         net.set_params(p0)
         if sgd:
             net.reset_velocity()
-    _epoch(a, X, y, perm, B, lr, augment=aug, **kw)
-    _epoch(d, X, y, perm, B, lr, augment=Augment(pad=2, hflip=True, seed=11, epoch=1), **kw)
+    epoch(a, X, y, perm, B, lr, augment=aug, **kw)
+    epoch(d, X, y, perm, B, lr, augment=Augment(pad=2, hflip=True, seed=11, epoch=1), **kw)
     assert np.array_equal(a.get_params(), pa)
     assert not np.array_equal(d.get_params(), pa) and np.all(np.isfinite(d.get_params()))
     for net in (a, b, c, d):
@@ -276,18 +203,18 @@ def test_wild_indices_are_clamped_and_refusals_change_nothing():
     from mercer_research_amd.convnet import Augment, AugmentStruct
     spec = FUSED_HEAD
     (H, W, _), _, B = spec
-    a, b = _twins(spec, "fp32")
+    a, b = twins(spec, "fp32")
     n = 4 * B + 1
-    X, y = _random_set(a, spec, n, seed=13, u8=True)
+    X, y = random_set(a, spec, n, seed=13, u8=True)
     Xh, yh = X.cpu().numpy(), y.cpu().numpy()
     lib, h = a.lib, a.net
     xp, yp = C.c_void_p(X.data_ptr()), C.c_void_p(y.data_ptr())
     # index entries outside [0, n) with an augmentation: the rows 0 and n - 1, nothing wild is read
     idxh = np.array([-5, n + 7, 2, -(1 << 31), (1 << 31) - 1], dtype=np.int32)
-    idx = _dev(a, idxh)
+    idx = dev(a, idxh)
     out = torch.zeros((B,) + spec[0], dtype=torch.float32, device=a.device)
     lab = torch.zeros(B, dtype=torch.int32, device=a.device)
-    _sync()
+    sync()
     ok = AugmentStruct(1, 1, 3, 0)
     gather = lambda aug=ok, o=C.c_void_p(out.data_ptr()), X_=xp, kind=1, B_=B, idx_=C.c_void_p(idx.data_ptr()), base=0: lib.rcn_hipx_gather_batch_dev(
         h, X_, kind, SCALE, SHIFT, yp, n, idx_, base, B_, C.byref(aug) if aug is not None else None, 0, o, C.c_void_p(lab.data_ptr()))
@@ -295,24 +222,24 @@ def test_wild_indices_are_clamped_and_refusals_change_nothing():
     a.synchronize()
     rows = np.clip(idxh.astype(np.int64), 0, n - 1)
     assert rows.tolist() == [0, n - 1, 2, 0, n - 1]
-    assert out.cpu().numpy().tobytes() == _widen(augment_ref(Xh[rows], 1, True, 3, 0, 0)).tobytes()
+    assert out.cpu().numpy().tobytes() == widen(augment_ref(Xh[rows], 1, True, 3, 0, 0)).tobytes()
     assert np.array_equal(lab.cpu().numpy(), yh[rows])
     # a step on both twins, so that graphs exist and the counter could move
-    perm = _dev(a, np.arange(n, dtype=np.int32))
-    lr = _dev(a, _schedule(4))
+    perm = dev(a, np.arange(n, dtype=np.int32))
+    lr = dev(a, _schedule(4))
     for net in (a, b):
-        _epoch(net, X, y, perm, B, lr, n_batches=2, augment=Augment(1, True, 3, 0), x_scale=SCALE, x_shift=SHIFT)
+        epoch(net, X, y, perm, B, lr, n_batches=2, augment=Augment(1, True, 3, 0), x_scale=SCALE, x_shift=SHIFT)
     g0, p0 = a.graphs_instantiated(), a.get_params()
     out.zero_(); lab.zero_()
-    _sync()
-    epoch = lambda aug=ok, X_=xp, nb=2: lib.rcn_hipx_train_epoch_ex_dev(h, X_, 1, SCALE, SHIFT, yp, n, C.c_void_p(perm.data_ptr()), B, 0, nb, 0.05,
+    sync()
+    entry = lambda aug=ok, X_=xp, nb=2: lib.rcn_hipx_train_epoch_ex_dev(h, X_, 1, SCALE, SHIFT, yp, n, C.c_void_p(perm.data_ptr()), B, 0, nb, 0.05,
                                                                           C.c_void_p(lr.data_ptr()), C.byref(aug), None)
     for bad in (AugmentStruct(-1, 0, 0, 0), AugmentStruct(min(H, W), 0, 0, 0), AugmentStruct(17, 0, 0, 0), AugmentStruct(1, 2, 0, 0), AugmentStruct(1, -1, 0, 0)):
         assert gather(aug=bad) == -1 and b"augment" in lib.rcn_hipx_last_error(h)
-        assert epoch(aug=bad) == -1 and b"augment" in lib.rcn_hipx_last_error(h)
+        assert entry(aug=bad) == -1 and b"augment" in lib.rcn_hipx_last_error(h)
     assert gather(o=None) == -1 and gather(X_=None) == -1 and gather(kind=2) == -1 and gather(B_=0) == -1 and gather(B_=B + 1) == -1
     assert gather(idx_=None, base=-1) == -1 and gather(idx_=None, base=n - B + 1) == -1
-    assert epoch(X_=None) == -1 and epoch(nb=5) == -1                  # (what rcn_hipx_train_epoch_dev refuses)
+    assert entry(X_=None) == -1 and entry(nb=5) == -1                  # (what rcn_hipx_train_epoch_dev refuses)
     a.synchronize()
     assert a.graphs_instantiated() == g0 and np.array_equal(a.get_params(), p0)
     assert not out.any().item() and not lab.any().item()
@@ -326,7 +253,7 @@ def test_wild_indices_are_clamped_and_refusals_change_nothing():
     # the step that follows is that of a net that never saw any of it
     assert gather(idx_=None, base=n - B) == 0
     for net in (a, b):
-        _epoch(net, X, y, perm, B, lr[2:], first_batch=2, n_batches=2, augment=Augment(1, True, 3, 0), x_scale=SCALE, x_shift=SHIFT)
+        epoch(net, X, y, perm, B, lr[2:], first_batch=2, n_batches=2, augment=Augment(1, True, 3, 0), x_scale=SCALE, x_shift=SHIFT)
     assert np.array_equal(a.get_params(), b.get_params()) and not np.array_equal(a.get_params(), p0)
     assert a.graphs_instantiated() == g0
     a.close(); b.close()
@@ -339,7 +266,7 @@ def test_plan_epoch_names_the_gather_the_rate_copy_the_graph_and_the_steps_own_p
     from mercer_research_amd.convnet import Augment, ConvNetError
     spec = CIFAR
     B = spec[2]
-    net = _net(spec)
+    net = make_net(spec)
     lines = lambda text: [l.strip() for l in text.splitlines() if l.strip()]
     for sgd in (False, True):
         if sgd:
@@ -363,7 +290,7 @@ def test_plan_epoch_names_the_gather_the_rate_copy_the_graph_and_the_steps_own_p
                     assert sum(l.startswith("update: ") for l in body) == 1 and body[-1].startswith(f"update: {update}{'_dlr' if sched else ''}, ")
                     assert [l.replace(f"{update}_dlr,", f"{update},") for l in body] == step
     # a row that is no whole number of 16-byte pieces: element by element
-    odd = _net(ODD_WIDTH)
+    odd = make_net(ODD_WIDTH)
     got = lines(odd.plan_epoch_of_this_net(4, "float32", False, Augment(2, False, 0, 0)))
     assert "k_gather_aug<float, 1>, element by element, 1 workgroups, augment pad 2 hflip 0" in got[1]
     assert "k_gather_rows<uint8, 1>, element by element" in lines(odd.plan_epoch_of_this_net(4, "uint8"))[1]
@@ -379,14 +306,14 @@ def test_plan_epoch_names_the_gather_the_rate_copy_the_graph_and_the_steps_own_p
 def test_cifar_recipe_runs_on_one_graph_and_evaluation_follows():
     from mercer_research_amd.convnet import Augment, warmup_cosine
     spec, B, nb = CIFAR, CIFAR[2], 4
-    net = _net(spec)
+    net = make_net(spec)
     net.init_params(1)
-    X, y = _random_set(net, spec, nb * B, seed=31, u8=True)
-    perm = _dev(net, np.random.default_rng(32).permutation(nb * B).astype(np.int32))
-    losses = _zeros(net, nb)
+    X, y = random_set(net, spec, nb * B, seed=31, u8=True)
+    perm = dev(net, np.random.default_rng(32).permutation(nb * B).astype(np.int32))
+    losses = zeros(net, nb)
     g0 = net.graphs_instantiated()
-    _epoch(net, X, y, perm, B, _dev(net, warmup_cosine(nb, 0.02, 2)), losses=losses, augment=Augment(4, True, 5, 0), x_scale=SCALE, x_shift=SHIFT)
-    _epoch(net, X, y, perm, B, _dev(net, warmup_cosine(nb, 0.01, 1)), losses=losses, augment=Augment(4, True, 5, 1), x_scale=SCALE, x_shift=SHIFT)
+    epoch(net, X, y, perm, B, dev(net, warmup_cosine(nb, 0.02, 2)), losses=losses, augment=Augment(4, True, 5, 0), x_scale=SCALE, x_shift=SHIFT)
+    epoch(net, X, y, perm, B, dev(net, warmup_cosine(nb, 0.01, 1)), losses=losses, augment=Augment(4, True, 5, 1), x_scale=SCALE, x_shift=SHIFT)
     assert net.graphs_instantiated() - g0 <= 1
     lh = losses.cpu().numpy()
     assert np.all(np.isfinite(lh)) and np.all(lh > 0) and np.all(np.isfinite(net.get_params()))

@@ -4,86 +4,32 @@ training step's one reduction launch (k_reduce_all_sgd), and its data-parallel h
 The exactness tests run twin nets from the same parameters: net A trains with the fused step; net B computes the same gradients
 (rcn_hipx_gradients_dev: the same kernels and sums as the step) and the update is applied on the host by tests/_sgd_ref.py, a float32
 restatement with every operation rounded once.  The GPU update uses no fused multiply-add, so parameters and velocity agree bit for bit."""
-import os
-import sys
-
 import numpy as np
 import pytest
+from _convnet_util import CIFAR, FUSED_HEAD, MNIST, MU, PLAIN_HEAD, POOL_PAIRS, WD, batches, grad, make_net, step, twins
+from _sgd_ref import sgd_update
 
 from oracle import convnet_oracle as co
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-from _sgd_ref import sgd_update  # noqa: E402
-
 pytestmark = pytest.mark.gpu
-
-FUSED_HEAD = ((8, 8, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 32), ("dense", 10)), 5)
-PLAIN_HEAD = ((6, 6, 1), (("conv", 32), ("conv", 32), ("pool",), ("dense", 7)), 3)
-POOL_PAIRS = ((16, 16, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 128), ("dense", 10)), 64)     # bf16 storage covers it
-CIFAR = ((32, 32, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("conv", 128), ("pool",), ("dense_relu", 256), ("dense", 10)), 512)
-MNIST = ((28, 28, 1), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 128), ("dense", 10)), 4096)
-MU, WD = 0.9, 5e-4
-
-
-def _net(spec, precision="fp32"):
-    from mercer_research_amd.convnet import ConvNet
-    in_shape, layers, B = spec
-    net = ConvNet(in_shape, layers, B)
-    net.set_precision(precision)
-    return net
-
-
-def _twins(spec, precision, seed=1):
-    a = _net(spec, precision)
-    a.init_params(seed)
-    b = _net(spec, precision)
-    b.set_params(a.get_params())
-    return a, b
-
-
-def _batches(net, spec, n, seed=0):
-    in_shape, layers, B = spec
-    rng = np.random.default_rng(seed)
-    out = [(net.to_device(rng.standard_normal((B,) + in_shape).astype(np.float32)), net.to_device(rng.integers(0, layers[-1][1], B).astype(np.int32)))
-           for _ in range(n)]
-    net.synchronize()
-    return out
-
-
-def _step(net, x, y, lr):
-    import torch
-    with torch.cuda.stream(net.stream):
-        net.train_step(x, y, lr)
-    net.synchronize()
-
-
-def _grad(net, x, y):
-    import torch
-    with torch.cuda.stream(net.stream):
-        g = net.gradients(x, y)
-    net.synchronize()
-    return g
-
 
 def _host_step(twin, x, y, p, v, lr, mu, wd, nesterov):
     """The reference step: twin's gradients at p, then the float32 restatement of the update on the host."""
     twin.set_params(p)
-    g = twin.unpad(_grad(twin, x, y))
+    g = twin.unpad(grad(twin, x, y)[0])
     return sgd_update(p, g, v, lr, mu, wd, nesterov)
 
 
 def _check_fused_against_host(spec, precision, nesterov, lrs):
-    a, b = _twins(spec, precision)
+    a, b = twins(spec, precision)
     a.set_sgd(MU, WD, nesterov)
     assert a.get_sgd() == (pytest.approx(MU), pytest.approx(WD), nesterov)
     plan = a.plan_of_this_net(spec[2])
     assert "k_reduce_all_sgd" in plan and "momentum 0.9" in plan and ("nesterov on" if nesterov else "nesterov off") in plan, plan
-    x, y = _batches(a, spec, 1)[0]
+    x, y = batches(a, spec, 1)[0]
     p, v = a.get_params(), np.zeros(a.n_logical, dtype=np.float32)
     for k, lr in enumerate(lrs):
-        _step(a, x, y, lr)
+        step(a, x, y, lr)
         p, v = _host_step(b, x, y, p, v, lr, MU, WD, nesterov)
         pa, va = a.get_params(), a.get_velocity()
         assert np.array_equal(pa, p), (k, float(np.abs(pa - p).max()))
@@ -94,17 +40,17 @@ def _check_fused_against_host(spec, precision, nesterov, lrs):
 
 def test_default_setting_is_plain_sgd_bit_for_bit():
     """(0, 0, False) given explicitly is a net never configured: the same kernels, the same bits, the same plan text."""
-    a, b = _twins(FUSED_HEAD, "fp32")
+    a, b = twins(FUSED_HEAD, "fp32")
     a.set_sgd(0.0, 0.0, False)
     assert a.get_sgd() == (0.0, 0.0, False)
     assert a.plan_of_this_net(FUSED_HEAD[2]) == b.plan_of_this_net(FUSED_HEAD[2])
     assert "k_reduce_all_sgd" not in a.plan_of_this_net(FUSED_HEAD[2])
     p0 = a.get_params()
-    xa, ya = _batches(a, FUSED_HEAD, 1)[0]
-    xb, yb = _batches(b, FUSED_HEAD, 1)[0]
+    xa, ya = batches(a, FUSED_HEAD, 1)[0]
+    xb, yb = batches(b, FUSED_HEAD, 1)[0]
     for _ in range(4):                                   # eager, then graph replays
-        _step(a, xa, ya, 0.05)
-        _step(b, xb, yb, 0.05)
+        step(a, xa, ya, 0.05)
+        step(b, xb, yb, 0.05)
     assert np.array_equal(a.get_params(), b.get_params())
     assert not np.array_equal(a.get_params(), p0)
     assert np.array_equal(a.get_velocity(), np.zeros(a.n_logical, dtype=np.float32))
@@ -130,7 +76,7 @@ def test_three_momentum_steps_match_the_f64_oracle_and_torch_sgd(spec):
     ws = [rng.standard_normal(k) * np.sqrt(2.0 / k[0]) for k, _ in shapes]
     bs = [rng.standard_normal(n) * 0.1 for _, n in shapes]
     flat = co.flatten(ws, bs).astype(np.float32)
-    net = _net(spec)
+    net = make_net(spec)
     net.set_params(flat)
     net.set_sgd(MU, WD, False)
     x = rng.standard_normal((B,) + in_shape).astype(np.float32)
@@ -145,7 +91,7 @@ def test_three_momentum_steps_match_the_f64_oracle_and_torch_sgd(spec):
         _, _, gws, gbs = co.loss_and_grads(x.astype(np.float64), y, w64, b64, layers)
         tp.grad = torch.tensor(co.flatten(gws, gbs))
         opt.step()
-        _step(net, xd, yd, lr)
+        step(net, xd, yd, lr)
         ref, got = tp.detach().numpy(), net.get_params().astype(np.float64)
         scale = max(1e-3, float(np.abs(ref).max()))
         assert np.abs(got - ref).max() <= 6e-4 * scale + 1e-6, (float(np.abs(got - ref).max()), scale)
@@ -161,16 +107,16 @@ def test_data_parallel_half_is_the_fused_step_bit_for_bit(precision):
     rcn_hipx_apply_dev stays the plain axpy and leaves the velocity alone."""
     import torch
     spec = POOL_PAIRS
-    a, b = _twins(spec, precision)
-    c = _net(spec, precision)
+    a, b = twins(spec, precision)
+    c = make_net(spec, precision)
     c.set_params(a.get_params())
     for n in (a, b, c):
         n.set_sgd(MU, WD, True)
-    x, y = _batches(a, spec, 1)[0]
+    x, y = batches(a, spec, 1)[0]
     grad = torch.empty(b.n_padded, dtype=torch.float32, device=b.device)
     lr = 0.03
     for _ in range(3):
-        _step(a, x, y, lr)
+        step(a, x, y, lr)
         with torch.cuda.stream(b.stream):
             b.gradients_bucketed(x, y, grad, None, 0)
             b.apply_sgd(grad, 1.0, lr)
@@ -194,18 +140,18 @@ def test_data_parallel_half_is_the_fused_step_bit_for_bit(precision):
 def test_state_saved_and_loaded_continues_bit_for_bit_and_changes_reach_the_replay():
     import torch
     spec = FUSED_HEAD
-    a, b = _twins(spec, "fp32")
-    batches = _batches(a, spec, 3, seed=4)
+    a, b = twins(spec, "fp32")
+    three = batches(a, spec, 3, seed=4)
     lr = 0.05
     for n in (a, b):
         n.set_sgd(MU, WD, False)
     for k in range(6):
-        _step(a, *batches[k % 3], lr)
+        step(a, *three[k % 3], lr)
     for k in range(3):
-        _step(b, *batches[k % 3], lr)
+        step(b, *three[k % 3], lr)
     p3, v3 = b.get_params(), b.get_velocity()
     b.close()
-    c = _net(spec)
+    c = make_net(spec)
     assert np.array_equal(c.get_velocity(), np.zeros(c.n_logical, dtype=np.float32))       # no buffer yet: zeros
     with pytest.raises(Exception):
         c.set_velocity(v3)                               # momentum 0: -6
@@ -213,7 +159,7 @@ def test_state_saved_and_loaded_continues_bit_for_bit_and_changes_reach_the_repl
     c.set_sgd(MU, WD, False)
     c.set_velocity(v3)
     for k in range(3, 6):
-        _step(c, *batches[k % 3], lr)
+        step(c, *three[k % 3], lr)
     assert np.array_equal(c.get_params(), a.get_params()) and np.array_equal(c.get_velocity(), a.get_velocity())
     # the velocity survives set_params and a change of precision
     c.set_params(p3)
@@ -222,27 +168,27 @@ def test_state_saved_and_loaded_continues_bit_for_bit_and_changes_reach_the_repl
     assert np.array_equal(c.get_velocity(), a.get_velocity())
 
     # reset_velocity and a changed setting on a net whose step is already a captured graph: the next step sees them
-    twin = _net(spec)
-    x, y = batches[0]
+    twin = make_net(spec)
+    x, y = three[0]
     for _ in range(2):
-        _step(c, x, y, lr)                               # (the graph for (x, y, lr) exists and has been replayed)
+        step(c, x, y, lr)                               # (the graph for (x, y, lr) exists and has been replayed)
     p = c.get_params()
     c.reset_velocity()
-    _step(c, x, y, lr)
+    step(c, x, y, lr)
     p, v = _host_step(twin, x, y, p, np.zeros(c.n_logical, dtype=np.float32), lr, MU, WD, False)
     assert np.array_equal(c.get_params(), p) and np.array_equal(c.get_velocity(), v)
-    _step(c, x, y, lr)                                   # replay after the reset
+    step(c, x, y, lr)                                   # replay after the reset
     p, v = _host_step(twin, x, y, p, v, lr, MU, WD, False)
     assert np.array_equal(c.get_params(), p) and np.array_equal(c.get_velocity(), v)
     c.set_sgd(0.5, 1e-3, True)
     assert c.get_sgd() == (0.5, pytest.approx(1e-3), True)
-    _step(c, x, y, lr)
+    step(c, x, y, lr)
     p, v = _host_step(twin, x, y, p, v, lr, 0.5, 1e-3, True)
     assert np.array_equal(c.get_params(), p) and np.array_equal(c.get_velocity(), v)
     # weight decay alone: the velocity is neither read nor written
     c.set_sgd(0.0, 1e-3, False)
     v_kept = c.get_velocity()
-    _step(c, x, y, lr)
+    step(c, x, y, lr)
     p, _ = _host_step(twin, x, y, p, v_kept, lr, 0.0, 1e-3, False)
     assert np.array_equal(c.get_params(), p) and np.array_equal(c.get_velocity(), v_kept)
     a.close(); c.close(); twin.close()
@@ -250,7 +196,7 @@ def test_state_saved_and_loaded_continues_bit_for_bit_and_changes_reach_the_repl
 
 def test_invalid_settings_are_refused_and_change_nothing():
     from mercer_research_amd.convnet import ConvNetError
-    net = _net(FUSED_HEAD)
+    net = make_net(FUSED_HEAD)
     net.set_sgd(0.5, 1e-4, True)
     for args in ((1.0, 0.0, False), (-0.1, 0.0, False), (float("nan"), 0.0, False), (0.9, -1e-4, False), (0.9, float("inf"), False), (0.0, 1e-4, True)):
         with pytest.raises(ConvNetError):

@@ -2,7 +2,7 @@
 one of its sixteen instantiations, over the layers' slabs and over a summed buffer read as one-chunk slabs, bit for bit; and the plan text
 of every configuration against what the library printed before the sixteen named kernels became one template.
 
-The twin-net method and the helpers of tests/test_gpu_convnet_clip.py.  tests/golden/update_plans.json was recorded on an MI355X with the
+The twin-net method of tests/test_gpu_convnet_clip.py.  tests/golden/update_plans.json was recorded on an MI355X with the
 library of the commit BEFORE the template (`python tests/test_gpu_convnet_update_forms.py OUT.json` with that commit's package on the
 path): it is the yardstick, never regenerate it from the code under test."""
 import itertools
@@ -12,19 +12,14 @@ import sys
 
 import numpy as np
 import pytest
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-from _accum_ref import accumulate  # noqa: E402
-from _clip_ref import apply_coef, grad_norm, plain_update  # noqa: E402
-from _ema_ref import ema_update  # noqa: E402
-from _sgd_ref import sgd_update  # noqa: E402
-from test_gpu_convnet_clip import DEFAULT, FUSED_HEAD, MU, PLAIN_HEAD, WD, _batch, _check_norm, _grad, _net, _same_bits, _step, _twins  # noqa: E402
+from _accum_ref import accumulate
+from _clip_ref import apply_coef, grad_norm, plain_update
+from _convnet_util import FUSED_HEAD, NESTEROV, PLAIN, PLAIN_HEAD, batch, check_norm, grad, make_net, same_bits, step, twins
+from _ema_ref import ema_update
+from _sgd_ref import sgd_update
 
 pytestmark = pytest.mark.gpu
 
-NESTEROV = (MU, WD, True)
 DECAY = 0.9
 LRS = [0.05, 0.05, 0.02, 0.05]                          # eager, replay, a second rate, back to the first
 FORMS = list(itertools.product([False, True], [False, True], [False, True], [1, 2]))      # (clip, sgd, ema, accumulate)
@@ -44,31 +39,31 @@ def _configure(net, sgd, ema, k):
 def test_train_step_is_the_host_update_bit_for_bit(clip, sgd, ema, k):
     """four updates (of k micro-batches each, every one with its own data) against the NumPy restatements: the rate from the host"""
     spec = PLAIN_HEAD
-    a, b = _twins(spec, "fp32")
+    a, b = twins(spec, "fp32")
     _configure(a, sgd, ema, k)
-    opt = NESTEROV if sgd else DEFAULT
-    batches = [_batch(a, spec, 20 + j) for j in range(k)]
+    opt = NESTEROV if sgd else PLAIN
+    batches = [batch(a, spec, 20 + j) for j in range(k)]
     p = a.get_params()
     v, e = np.zeros(a.n_logical, dtype=np.float32), p.copy()
     max_norm = None
     if clip:
-        first = [_grad(b, x, y, p)[1] for x, y in batches]
+        first = [grad(b, x, y, p)[1] for x, y in batches]
         max_norm = float(grad_norm(accumulate(first, k) if k > 1 else first[0]) / np.float32(2))       # half the first update's norm
         a.set_clip(max_norm)
     for u, lr in enumerate(LRS):
         logical, padded = [], []
         for j, (x, y) in enumerate(batches):
-            gdev, gpad = _grad(b, x, y, p)
+            gdev, gpad = grad(b, x, y, p)
             logical.append(b.unpad(gdev))
             padded.append(gpad)
-            _step(a, x, y, lr)
+            step(a, x, y, lr)
             if k > 1:
-                assert _same_bits(a.get_accumulated(), accumulate(logical, k)), (u, j)
-                assert j == k - 1 or _same_bits(a.get_params(), p), (u, j)
+                assert same_bits(a.get_accumulated(), accumulate(logical, k)), (u, j)
+                assert j == k - 1 or same_bits(a.get_params(), p), (u, j)
         g, gpad = (accumulate(logical, k), accumulate(padded, k)) if k > 1 else (logical[0], padded[0])
         if clip:
             norm, coef = a.grad_norm()
-            _check_norm(f"update {u}", norm, coef, grad_norm(gpad), max_norm)
+            check_norm(f"update {u}", norm, coef, grad_norm(gpad), max_norm)
             assert u > 0 or coef < 1.0
             g = apply_coef(g, coef)
         if sgd:
@@ -77,10 +72,10 @@ def test_train_step_is_the_host_update_bit_for_bit(clip, sgd, ema, k):
             p = plain_update(p, g, lr)
         if ema:
             e = ema_update(e, p, DECAY)
-        assert _same_bits(a.get_params(), p), (u, float(np.abs(a.get_params() - p).max()))
-        assert _same_bits(a.get_velocity(), v), u
+        assert same_bits(a.get_params(), p), (u, float(np.abs(a.get_params() - p).max()))
+        assert same_bits(a.get_velocity(), v), u
         if ema:
-            assert _same_bits(a.get_ema(), e), u
+            assert same_bits(a.get_ema(), e), u
     if clip:
         assert a.grad_norm_count() == len(LRS)
     a.close(); b.close()
@@ -93,7 +88,7 @@ def test_epoch_with_device_rate_is_the_batches_fed_one_by_one(clip, sgd, ema, k)
     import torch
     spec = PLAIN_HEAD
     in_shape, layers, B = spec
-    a, t = _twins(spec, "fp32")
+    a, t = twins(spec, "fp32")
     rng = np.random.default_rng(6)
     X = a.to_device(rng.integers(0, 256, (4 * B,) + in_shape).astype(np.uint8))
     Y = a.to_device(rng.integers(0, layers[-1][1], 4 * B).astype(np.int32))
@@ -103,7 +98,7 @@ def test_epoch_with_device_rate_is_the_batches_fed_one_by_one(clip, sgd, ema, k)
     if clip:
         with torch.cuda.stream(t.stream):
             x0, y0 = t.gather_batch(X, Y, None, B)
-        max_norm = float(grad_norm(_grad(t, x0, y0)[1]) / np.float32(4))       # a quarter of the first batch's norm: it bites on a mean of two too
+        max_norm = float(grad_norm(grad(t, x0, y0)[1]) / np.float32(4))       # a quarter of the first batch's norm: it bites on a mean of two too
     for n in (a, t):
         _configure(n, sgd, ema, k)
         if clip:
@@ -122,11 +117,11 @@ def test_epoch_with_device_rate_is_the_batches_fed_one_by_one(clip, sgd, ema, k)
         t.synchronize()
         if clip and s == k - 1:
             assert t.grad_norm()[1] < 1.0                # clipping bites on the first update
-    assert _same_bits(a.get_params(), t.get_params()) and _same_bits(a.get_velocity(), t.get_velocity())
+    assert same_bits(a.get_params(), t.get_params()) and same_bits(a.get_velocity(), t.get_velocity())
     if ema:
-        assert _same_bits(a.get_ema(), t.get_ema())
+        assert same_bits(a.get_ema(), t.get_ema())
     if k > 1:
-        assert a.get_accumulate() == t.get_accumulate() == (k, 0) and _same_bits(a.get_accumulated(), t.get_accumulated())
+        assert a.get_accumulate() == t.get_accumulate() == (k, 0) and same_bits(a.get_accumulated(), t.get_accumulated())
     if clip:
         assert a.grad_norm() == t.grad_norm() and a.grad_norm_count() == t.grad_norm_count() == 4 // k
     a.close(); t.close()
@@ -135,7 +130,7 @@ def test_epoch_with_device_rate_is_the_batches_fed_one_by_one(clip, sgd, ema, k)
 # ---- the plan text -----------------------------------------------------------------------------------------------------------------------
 PLAN_LINES = ("  reduction:", "  gradient:", "  norm:", "  update:", "  graph:")
 PLAN_CONFIGS = list(itertools.product([False, True], [False, True], [False, True], [1, 3]))        # (clip, sgd, ema, accumulate)
-GOLDEN = os.path.join(HERE, "golden", "update_plans.json")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "update_plans.json")
 
 
 def _update_plans():
@@ -143,7 +138,7 @@ def _update_plans():
     B = FUSED_HEAD[2]
     out = {}
     for clip, sgd, ema, k in PLAN_CONFIGS:
-        net = _net(FUSED_HEAD)
+        net = make_net(FUSED_HEAD)
         _configure(net, sgd, ema, k)
         if clip:
             net.set_clip(1.0)

@@ -8,33 +8,14 @@ import os
 
 import numpy as np
 import pytest
+from _convnet_util import CIFAR, MNIST, close, make_net, oracle_params
 
 from oracle import convnet_oracle as co
 
 pytestmark = pytest.mark.gpu
 
-CIFAR = ((32, 32, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("conv", 128), ("pool",), ("dense_relu", 256), ("dense", 10)), 512)
 SYNTH224 = ((224, 224, 3), (("conv", 32), ("conv", 32), ("pool",), ("conv", 64), ("conv", 64), ("pool",), ("conv", 128), ("conv", 128), ("pool",),
                             ("conv", 256), ("conv", 256), ("pool",), ("dense", 10)), 128)
-MNIST = ((28, 28, 1), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 128), ("dense", 10)), 4096)
-
-
-def _net(in_shape, layers, B):
-    from mercer_research_amd.convnet import ConvNet
-    return ConvNet(in_shape, layers, B)
-
-
-def _close(a, b, rtol=2e-4):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    scale = max(1e-3, float(np.abs(b).max()))
-    assert np.abs(a - b).max() <= rtol * scale + 1e-6, (float(np.abs(a - b).max()), scale)
-
-
-def _params(rng, in_shape, layers):
-    shapes = co.param_shapes(in_shape, layers)
-    ws = [rng.standard_normal(k) * np.sqrt(2.0 / k[0]) for k, _ in shapes]
-    bs = [rng.standard_normal(n) * 0.1 for _, n in shapes]
-    return ws, bs
 
 
 def _properties(net, x, y, flat, lr, tol, bitwise_replay=True):
@@ -53,7 +34,7 @@ def _properties(net, x, y, flat, lr, tol, bitwise_replay=True):
         gs = g1 + g2
     net.synchronize()
     # gradients of the MEAN loss: the full batch's is the mean of the halves'
-    _close(net.unpad(g_full), net.unpad(gm), rtol=tol)
+    close(net.unpad(g_full), net.unpad(gm), rtol=tol)
     assert abs(lf.item() - 0.5 * (l1.item() + l2.item())) <= tol * max(1.0, abs(lf.item()))
     # data-parallel halves (what bench_convnet.py --gpus 2 does with an all-reduce in between) == one full step
     with torch.cuda.stream(net.stream):
@@ -66,7 +47,7 @@ def _properties(net, x, y, flat, lr, tol, bitwise_replay=True):
         net.train_step(xd, yd, lr, loss)                       # first call for these arguments: eager + capture
     net.synchronize()
     p_eager, l_eager = net.get_params(), loss.item()
-    _close(p_dp, p_eager, rtol=tol)
+    close(p_dp, p_eager, rtol=tol)
     net.set_params(flat)
     with torch.cuda.stream(net.stream):
         net.train_step(xd, yd, lr, loss)                       # same arguments: the cached hipGraph replays
@@ -75,7 +56,7 @@ def _properties(net, x, y, flat, lr, tol, bitwise_replay=True):
     if bitwise_replay:
         assert np.array_equal(p_replay, p_eager) and loss.item() == l_eager      # same kernels, fixed reduction orders
     else:
-        _close(p_replay, p_eager, rtol=tol)
+        close(p_replay, p_eager, rtol=tol)
     assert np.isfinite(p_eager).all() and np.isfinite(l_eager)
     return l_eager
 
@@ -85,17 +66,14 @@ def test_cifar_b512_fp32_workload_size():
     import torch
     in_shape, layers, B = CIFAR
     rng = np.random.default_rng(512)
-    ws, bs = _params(rng, in_shape, layers)
-    flat = co.flatten(ws, bs)
-    net = _net(in_shape, layers, B)
+    _, _, flat, w32, b32 = oracle_params(rng, in_shape, layers)
+    net = make_net((in_shape, layers, B), precision=None)
     assert flat.size == net.n_logical
     x = rng.standard_normal((B,) + in_shape).astype(np.float32)
     y = rng.integers(0, 10, B).astype(np.int32)
     # the oracle on a 4-image sub-batch at the full 32x32 resolution: logits, loss, every gradient
     net.set_params(flat)
     xs, ys = x[:4], y[:4]
-    w32 = [w.astype(np.float32).astype(np.float64) for w in ws]
-    b32 = [b.astype(np.float32).astype(np.float64) for b in bs]
     loss_ref, logits_ref, gws, gbs = co.loss_and_grads(xs.astype(np.float64), ys, w32, b32, layers)
     with torch.cuda.stream(net.stream):
         xd, yd = net.to_device(xs), net.to_device(ys)
@@ -103,14 +81,14 @@ def test_cifar_b512_fp32_workload_size():
         loss = torch.zeros(1, dtype=torch.float32, device=net.device)
         grad = net.gradients(xd, yd, loss=loss)
     net.synchronize()
-    _close(logits.cpu().numpy(), logits_ref)
+    close(logits.cpu().numpy(), logits_ref)
     assert abs(loss.item() - loss_ref) <= 2e-4 * max(1.0, loss_ref)
-    _close(net.unpad(grad), co.flatten(gws, gbs))
+    close(net.unpad(grad), co.flatten(gws, gbs))
     # the full 512-image batch: logits of the first 4 images do not depend on the batch they ride in
     with torch.cuda.stream(net.stream):
         logits_full = net.forward(net.to_device(x))
     net.synchronize()
-    _close(logits_full.cpu().numpy()[:4], logits_ref)
+    close(logits_full.cpu().numpy()[:4], logits_ref)
     _properties(net, x, y, flat, 0.02, 2e-4)
     assert abs(net.step_flops(B) / 1e9 - 32.4) < 0.5             # the figure bench_convnet.py prices the step at
     net.close()
@@ -122,14 +100,11 @@ def test_synth224_8conv_workload_size():
     import torch
     in_shape, layers, B = SYNTH224
     rng = np.random.default_rng(224)
-    ws, bs = _params(rng, in_shape, layers)
-    flat = co.flatten(ws, bs)
-    net = _net(in_shape, layers, B)
+    _, _, flat, w32, b32 = oracle_params(rng, in_shape, layers)
+    net = make_net((in_shape, layers, B), precision=None)
     net.set_params(flat)
     xs = rng.standard_normal((2,) + in_shape).astype(np.float32)
     ys = rng.integers(0, 10, 2).astype(np.int32)
-    w32 = [w.astype(np.float32).astype(np.float64) for w in ws]
-    b32 = [b.astype(np.float32).astype(np.float64) for b in bs]
     loss_ref, logits_ref, gws, gbs = co.loss_and_grads(xs.astype(np.float64), ys, w32, b32, layers)
     with torch.cuda.stream(net.stream):
         xd, yd = net.to_device(xs), net.to_device(ys)
@@ -137,9 +112,9 @@ def test_synth224_8conv_workload_size():
         loss = torch.zeros(1, dtype=torch.float32, device=net.device)
         grad = net.gradients(xd, yd, loss=loss)
     net.synchronize()
-    _close(logits.cpu().numpy(), logits_ref)
+    close(logits.cpu().numpy(), logits_ref)
     assert abs(loss.item() - loss_ref) <= 2e-4 * max(1.0, loss_ref)
-    _close(net.unpad(grad), co.flatten(gws, gbs))
+    close(net.unpad(grad), co.flatten(gws, gbs))
     del xd, yd, grad
     x = rng.standard_normal((B,) + in_shape).astype(np.float32)
     y = rng.integers(0, 10, B).astype(np.int32)
@@ -157,15 +132,12 @@ def test_mnist_bf16_b4096_hipgraph_step_workload_size():
     import torch
     in_shape, layers, B = MNIST
     rng = np.random.default_rng(4096)
-    ws, bs = _params(rng, in_shape, layers)
-    flat = co.flatten(ws, bs)
-    net = _net(in_shape, layers, B)
+    _, _, flat, w32, b32 = oracle_params(rng, in_shape, layers)
+    net = make_net((in_shape, layers, B), precision=None)
     net.set_precision("bf16")
     net.set_params(flat)
     xs = rng.standard_normal((16,) + in_shape).astype(np.float32)
     ys = rng.integers(0, 10, 16).astype(np.int32)
-    w32 = [w.astype(np.float32).astype(np.float64) for w in ws]
-    b32 = [b.astype(np.float32).astype(np.float64) for b in bs]
     loss_ref, logits_ref, gws, gbs = co.loss_and_grads(xs.astype(np.float64), ys, w32, b32, layers, operand="bf16")
     with torch.cuda.stream(net.stream):
         xd, yd = net.to_device(xs), net.to_device(ys)
@@ -173,9 +145,9 @@ def test_mnist_bf16_b4096_hipgraph_step_workload_size():
         loss = torch.zeros(1, dtype=torch.float32, device=net.device)
         grad = net.gradients(xd, yd, loss=loss)
     net.synchronize()
-    _close(logits.cpu().numpy(), logits_ref, rtol=5e-3)
+    close(logits.cpu().numpy(), logits_ref, rtol=5e-3)
     assert abs(loss.item() - loss_ref) <= 5e-3 * max(1.0, loss_ref)
-    _close(net.unpad(grad), co.flatten(gws, gbs), rtol=5e-3)
+    close(net.unpad(grad), co.flatten(gws, gbs), rtol=5e-3)
     x = rng.standard_normal((B,) + in_shape).astype(np.float32)
     y = rng.integers(0, 10, B).astype(np.int32)
     l0 = _properties(net, x, y, flat, 0.05, 5e-3)
