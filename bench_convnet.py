@@ -169,6 +169,10 @@ def main():
     ap.add_argument("--momentum", type=float, default=0.0, help="SGD momentum (rcn_hipx_set_sgd; 0: plain SGD)")
     ap.add_argument("--weight-decay", type=float, default=0.0, help="SGD weight decay, on every parameter")
     ap.add_argument("--nesterov", action="store_true", help="Nesterov momentum (needs --momentum > 0)")
+    ap.add_argument("--optimizer", choices=["sgd", "adam", "adamw"], default="sgd",
+                    help="adam / adamw: rcn_hipx_set_adam (torch.optim.Adam's L2 form / torch.optim.AdamW), with --betas, --eps and --weight-decay; not with --momentum / --nesterov")
+    ap.add_argument("--betas", type=float, nargs=2, default=(0.9, 0.999), metavar=("B1", "B2"), help="Adam's betas")
+    ap.add_argument("--eps", type=float, default=1e-8, help="Adam's eps")
     ap.add_argument("--ema", type=float, default=0.0, metavar="D",
                     help="keep an exponential moving average of the parameters with decay D inside the update launch (rcn_hipx_set_ema; 0: none), set before the "
                          "timed steps; with --dataset the line gains eval_ema_images_per_s and the average's loss / accuracy beside the live ones")
@@ -198,6 +202,8 @@ def main():
     args = ap.parse_args()
     if (args.label_smoothing != 0.0 or args.mix != "none") and not args.dataset:
         ap.error("--label-smoothing and --mix time the resident epoch: they need --dataset N")
+    if args.optimizer != "sgd" and (args.momentum != 0.0 or args.nesterov):
+        ap.error("--optimizer adam / adamw: --momentum and --nesterov belong to SGD")
     if not 0.0 <= args.ema < 1.0:
         ap.error("--ema: 0 <= D < 1")
     if not args.clip >= 0.0:
@@ -243,7 +249,9 @@ def main():
         net.set_option(kv.split("=")[0], int(kv.split("=")[1]))
     net.set_precision(args.precision)
     sgd = args.momentum != 0.0 or args.weight_decay != 0.0 or args.nesterov
-    if sgd:
+    if args.optimizer != "sgd":
+        net.set_adam(tuple(args.betas), args.eps, args.weight_decay, args.optimizer == "adamw")
+    elif sgd:
         net.set_sgd(args.momentum, args.weight_decay, args.nesterov)
     if args.ema > 0:
         net.set_ema(args.ema)
@@ -256,7 +264,7 @@ def main():
     xs = [net.to_device(rng.standard_normal((B,) + in_shape).astype(np.float32)) for _ in range(nbuf)]
     ys = [net.to_device(rng.integers(0, 10, B).astype(np.int32)) for _ in range(nbuf)]
     loss = torch.zeros(1, dtype=torch.float32, device=net.device)
-    lr = 0.01 if args.config != "synth224" else 1e-6     # the un-normalised 8-conv stack on noise diverges at larger steps (speed does not depend on it)
+    lr = 1e-3 if args.optimizer != "sgd" and args.config != "synth224" else 0.01 if args.config != "synth224" else 1e-6     # the un-normalised 8-conv stack on noise diverges at larger steps (speed does not depend on it)
     dp_graphs = {}
     dp_mode = None
     if dp:
@@ -282,7 +290,7 @@ def main():
                         dist.all_reduce(piece, op=dist.ReduceOp.SUM)
                 net.gradients_bucketed(x, y, grad, loss, args.dp_buckets, on_bucket)
                 net.stream.wait_stream(comm)
-            if sgd or args.ema > 0 or args.clip > 0:       # (apply_sgd keeps the average and clips; apply is the plain axpy and does neither)
+            if sgd or args.optimizer != "sgd" or args.ema > 0 or args.clip > 0:       # (apply_sgd keeps the average and clips; apply is the plain axpy and does neither)
                 net.apply_sgd(grad, 1.0 / world, lr)
             else:
                 net.apply(grad, lr / world)
@@ -366,7 +374,7 @@ def main():
                           "frac_of_mfma_peak": round(tf / peak, 4),
                           "hbm_floor_ms": round(floor_ms, 4) if floor_ms else None, "frac_of_hbm_floor": round(floor_ms / (el / args.steps * 1e3), 4) if floor_ms else None,
                           "dtype": "f32" if not bf16 else "bf16 MFMA operands (fwd, dgrad, wgrad), f32 accumulate/update" + (", conv-stage activations and gradients stored as bf16" if args.precision == "bf16_stored" else ""), "data": "synthetic", "final_loss": round(loss.item(), 4),
-                          "ema_decay": args.ema,
+                          "optimizer": args.optimizer, "ema_decay": args.ema,
                           "accumulate": K, "ms_per_update": round(el / args.steps * 1e3 * K, 4),
                           "clip_max_norm": args.clip, "grad_norm_last": round(net.grad_norm()[0], 6) if args.clip > 0 else None,
                           "data_parallel_step": dp_mode,

@@ -296,6 +296,36 @@ int  rcn_hipx_reset_velocity(rcn_hipx_net* net);
  * ranks' gradients with grad_scale = 1 / ranks).  With the default setting it is rcn_hipx_apply_dev(grad_dev, grad_scale * lr).
  * rcn_hipx_apply_dev itself stays the plain p <- p - scale * g and never touches the velocity. */
 int  rcn_hipx_apply_sgd_dev(rcn_hipx_net* net, const float* grad_dev, float grad_scale, float lr);
+/* Adam and AdamW as the optimiser of the training step: torch.optim.Adam(betas, eps, weight_decay) in its L2 form (decoupled = 0) and
+ * torch.optim.AdamW (decoupled = 1), amsgrad and maximize off.  Host constants, computed once here, in float: b1 = (float)beta1,
+ * b2 = (float)beta2, a1 = fl(1.0f - b1), a2 = fl(1.0f - b2).  The update's ordinal lives on the device (a replayed graph's arguments are
+ * frozen) in a 32-byte state {int64 step; double b1t, b2t; float c1, c2}, starting at step = 0, b1t = b2t = 1.0; the tick, a one-thread
+ * launch of its own (k_adam_tick) directly in front of the update launch and inside the step's graph, advances it once per update, in double:
+ *     step += 1;  b1t = b1t * (double)b1;  b2t = b2t * (double)b2;  c1 = (float)(1.0 - b1t);  c2 = (float)sqrt(1.0 - b2t)
+ * (running products, not pow).  Per element, fp32, every operation rounded once (no fused multiply-add, IEEE sqrtf and /), weight decay on
+ * every parameter, biases included, lr being the step's rate:
+ *     x = g;  if (wd && !decoupled) x = x + wd * p;  if (wd && decoupled) p = p * (1.0f - lr * wd);
+ *     m = m + a1 * (x - m);  v = b2 * v + a2 * (x * x);  d = sqrtf(v) / c2 + eps;  p = p - (lr / c1) * (m / d)
+ * (tests/_adam_ref.py restates tick and update in NumPy, bit for bit).  g is the step's gradient exactly where SGD sees it: after
+ * accumulation's mean and after the clip coefficient; the average of rcn_hipx_set_ema sees the parameters this update stores.  The update
+ * runs inside the step's one reduction launch (k_reduce_all[_clip]_adam[_ema][_dlr]); an accumulating net ticks on the last micro-step of
+ * a cycle only, a gradients-only walk never.  Adam adds no graph: one per (B, lr), one per B with a device rate.
+ * rcn_hipx_set_adam accepts finite 0 <= beta < 1, a finite eps > 0, a finite weight_decay >= 0 and decoupled 0 / 1; anything else returns
+ * -1 and changes nothing.  It selects Adam, synchronises the net's stream and drops its captured graphs.  The first call allocates the
+ * moments m and v (zeroed) and the state; they are never moved and survive rcn_hipx_set_params, rcn_hipx_init_params, changes of
+ * precision, tiling, overlap or options and a switch of optimiser, like the velocity.  Betas changed at step > 0: b1t and b2t are recomputed
+ * on the host from the current step by the same repeated double multiplication.  rcn_hipx_set_sgd selects SGD again (also with unchanged
+ * values); on a net never given to rcn_hipx_set_adam it behaves as it always has.  get: `selected` is 1 while Adam is the optimiser. */
+int  rcn_hipx_set_adam(rcn_hipx_net* net, float beta1, float beta2, float eps, float weight_decay, int decoupled);
+int  rcn_hipx_get_adam(const rcn_hipx_net* net, float* beta1, float* beta2, float* eps, float* weight_decay, int* decoupled, int* selected);
+/* m, v in the logical layout of rcn_hipx_get_params / _set_params, and the update count.  -6 while no state exists (rcn_hipx_set_adam
+ * first).  get: any of the three may be NULL.  set: b1t, b2t, c1, c2 are rebuilt from `step` (>= 0) with the net's betas.  reset: m, v
+ * and the state as the first rcn_hipx_set_adam left them (a no-op without state).
+ * rcn_hipx_apply_sgd_dev on a net whose optimiser is Adam: the tick, then k_adam_apply with x = fl(grad_scale * g) -- k_grad_sumsq in front
+ * and fl(coef * x) where clipping is on --, then the average's k_ema_lerp.  rcn_hipx_apply_dev never touches m, v or the count. */
+int  rcn_hipx_get_adam_state(rcn_hipx_net* net, float* m_flat, float* v_flat, int64_t* step);
+int  rcn_hipx_set_adam_state(rcn_hipx_net* net, const float* m_flat, const float* v_flat, int64_t step);
+int  rcn_hipx_reset_adam(rcn_hipx_net* net);
 /* An exponential moving average (EMA) of the parameters, kept by the launch that updates them: timm's ModelEmaV2,
  * torch.optim.swa_utils.AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(decay)).  Per element, fp32, every operation rounded once (no fused
  * multiply-add):
@@ -426,15 +456,16 @@ int  rcn_hipx_unpad_host(rcn_hipx_net* net, const float* padded_dev, float* logi
 int  rcn_hipx_plan(int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, int n_layers, int batch, int precision, int tiling, char* out, int cap);
 /* The same walk for an EXISTING net at batch `batch` (<= max_batch) with that net's own precision, tiling and options: the plan and the
  * step that follows agree by construction (rcn_hipx_plan describes a net created now, seeded from the environment).  A net with a
- * non-default rcn_hipx_set_sgd setting names its optimiser and the values on the update line; one with rcn_hipx_set_loss eps > 0 names the
+ * non-default rcn_hipx_set_sgd setting names its optimiser and the values on the update line; one with rcn_hipx_set_adam has a
+ * "tick: k_adam_tick" line in front of the update line, the _adam update kernel and "(Adam: betas .., eps .., weight decay .., decoupled | L2)"; one with rcn_hipx_set_loss eps > 0 names the
  * soft loss kernel and eps on the loss (or head) line; one with rcn_hipx_set_ema decay > 0 names the _ema update kernel and
  * "(EMA: decay %g)" on the update line; one with rcn_hipx_set_clip max_norm > 0 names the three launches of the clipped reduction
  * (k_reduce_all into the gradient buffer, k_grad_sumsq, k_reduce_all_clip...) and "(clip: max norm %g)" on the update line
  * (rcn_hipx_plan_epoch_net / _mix_net likewise).  On a net with rcn_hipx_set_accumulate k > 1 the three describe the LAST micro-step of a
  * cycle: the k_reduce_all_acc<next> reduction, the norm where clipping is on, and the update over the accumulator as one-chunk slabs, its
  * line gaining "(accumulate: k micro-batches, scale %g)"; the epoch plans' graph line names the graph per kind of micro-step.
- * The update's kernel name here, in the plans and throughout this header, k_reduce_all[_clip][_sgd][_ema][_dlr], is the display name of an
- * instantiation of ONE kernel template, k_reduce_update<CLIP, SGD, EMA, DLR> (csrc/convnet_update.hpp): one suffix per flag that is set. */
+ * The update's kernel name here, in the plans and throughout this header, k_reduce_all[_clip][_sgd | _adam][_ema][_dlr], is the display name of an
+ * instantiation of ONE kernel template, k_reduce_update<CLIP, OPT, EMA, DLR> (csrc/convnet_update.hpp): one suffix per flag that is set. */
 int  rcn_hipx_plan_net(const rcn_hipx_net* net, int batch, char* out, int cap);
 /* The launches of one kind of micro-step of an accumulating net: kind 0 the first of a cycle, 1 a middle one, 2 the last.  The reduction
  * line names k_reduce_all_acc<first> or <next> and says "(accumulate: micro-batch of k, no update)"; the last kind is followed by the norm

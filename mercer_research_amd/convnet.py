@@ -115,6 +115,11 @@ SIGNATURES = {
     "rcn_hipx_set_velocity": (_i, [_vp, C.POINTER(C.c_float)]),
     "rcn_hipx_reset_velocity": (_i, [_vp]),
     "rcn_hipx_apply_sgd_dev": (_i, [_vp, _vp, C.c_float, C.c_float]),
+    "rcn_hipx_set_adam": (_i, [_vp, C.c_float, C.c_float, C.c_float, C.c_float, _i]),
+    "rcn_hipx_get_adam": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rcn_hipx_get_adam_state": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
+    "rcn_hipx_set_adam_state": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64]),
+    "rcn_hipx_reset_adam": (_i, [_vp]),
     "rcn_hipx_train_epoch_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _vp, _i, C.c_int64, C.c_int64, C.c_float, _vp]),
     "rcn_hipx_train_epoch_ex_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _vp, _i, C.c_int64, C.c_int64, C.c_float, _vp, C.POINTER(AugmentStruct), _vp]),
     "rcn_hipx_gather_batch_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _vp, C.c_int64, _i, C.POINTER(AugmentStruct), C.c_uint64, _vp, _vp]),
@@ -553,6 +558,34 @@ class ConvNet:
         (include/rcn_hipx.h, rcn_hipx_set_sgd).  (0, 0, False) is plain SGD, the default."""
         self._ck(self.lib.rcn_hipx_set_sgd(self.net, float(momentum), float(weight_decay), int(bool(nesterov))))
 
+    def set_adam(self, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, decoupled: bool = False):
+        """Adam as the optimiser of train_step / apply_sgd, as torch.optim.Adam(betas, eps, weight_decay); decoupled: torch.optim.AdamW
+        (include/rcn_hipx.h, rcn_hipx_set_adam).  The update count lives on the device and advances inside the step's graph.  set_sgd
+        selects SGD again; both optimisers' state survives the switch."""
+        self._ck(self.lib.rcn_hipx_set_adam(self.net, float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(decoupled)))
+
+    def get_adam(self) -> dict:
+        """{"betas", "eps", "weight_decay", "decoupled", "selected"}: the values of the last set_adam (its defaults before), and whether
+        Adam is the optimiser now."""
+        b1, b2, eps, wd, dec, sel = C.c_float(), C.c_float(), C.c_float(), C.c_float(), C.c_int(), C.c_int()
+        self._ck(self.lib.rcn_hipx_get_adam(self.net, C.byref(b1), C.byref(b2), C.byref(eps), C.byref(wd), C.byref(dec), C.byref(sel)))
+        return {"betas": (float(b1.value), float(b2.value)), "eps": float(eps.value), "weight_decay": float(wd.value), "decoupled": bool(dec.value),
+                "selected": bool(sel.value)}
+
+    def get_adam_state(self) -> Tuple[np.ndarray, np.ndarray, int]:
+        """(m, v, step): the moments in the logical layout of get_params and the number of updates so far."""
+        m, v, step = np.zeros(self.n_logical, dtype=np.float32), np.zeros(self.n_logical, dtype=np.float32), C.c_int64()
+        self._ck(self.lib.rcn_hipx_get_adam_state(self.net, _fptr(m), _fptr(v), C.byref(step)))
+        return m, v, int(step.value)
+
+    def set_adam_state(self, m: np.ndarray, v: np.ndarray, step: int):
+        m, v = np.ascontiguousarray(m, dtype=np.float32), np.ascontiguousarray(v, dtype=np.float32)
+        assert m.size == self.n_logical and v.size == self.n_logical
+        self._ck(self.lib.rcn_hipx_set_adam_state(self.net, _fptr(m), _fptr(v), int(step)))
+
+    def reset_adam(self):
+        self._ck(self.lib.rcn_hipx_reset_adam(self.net))
+
     def set_loss(self, label_smoothing: float = 0.0):
         """The training loss: cross-entropy against the target smoothed by label_smoothing, as torch.nn.CrossEntropyLoss(label_smoothing=)
         (include/rcn_hipx.h, rcn_hipx_set_loss).  0 is the default: the hard loss kernels.  evaluate stays the plain cross-entropy."""
@@ -673,7 +706,8 @@ class ConvNet:
         return _plan_text("rcn_hipx_plan_micro_net", self.lib.rcn_hipx_plan_micro_net, self.net, int(batch), MICRO_KINDS[kind])
 
     def apply_sgd(self, grad, grad_scale: float, lr: float):
-        """The data-parallel half of set_sgd's optimiser: the same update from a padded gradient buffer, scaled by grad_scale first."""
+        """The data-parallel half of the configured optimiser (set_sgd's or set_adam's): the same update from a padded gradient buffer,
+        scaled by grad_scale first."""
         self._ck(self.lib.rcn_hipx_apply_sgd_dev(self.net, _ptr(grad), grad_scale, lr))
 
     def unpad(self, padded) -> np.ndarray:

@@ -400,20 +400,25 @@ enum Micro { kWholeStep = 0, kMicroFirst = 1, kMicroMiddle = 2, kMicroLast = 3 }
 // Everything an update is configured with (rcn_hipx_net derives from it; a dry-run net copies it in one assignment, so the plan and the
 // step agree by construction).  The buffers and the state these settings need stay members of the net.
 struct Recipe {
+    int optim = 0;                          // the optimiser selected: 0 SGD (rcn_hipx_set_sgd, the default), 1 Adam (rcn_hipx_set_adam)
     float sgd_mu = 0.f, sgd_wd = 0.f; int sgd_nesterov = 0;      // rcn_hipx_set_sgd: (0, 0, 0) is plain SGD
+    // rcn_hipx_set_adam (convnet_adam.hpp): b1 = (float)beta1, b2 = (float)beta2, a1 = fl(1.0f - b1), a2 = fl(1.0f - b2); decoupled: AdamW
+    float adam_b1 = 0.9f, adam_b2 = 0.999f, adam_a1 = 1.0f - 0.9f, adam_a2 = 1.0f - 0.999f, adam_eps = 1e-8f, adam_wd = 0.f; int adam_decoupled = 0;
     float loss_eps = 0.f;                   // rcn_hipx_set_loss: 0 is the hard cross-entropy through k_softmax_ce / k_head_f32<true>
     float ema_decay = 0.f;                  // rcn_hipx_set_ema: 0 is off
     float clip_max = 0.f;                   // rcn_hipx_set_clip: 0 is off
     int accum_k = 1; float accum_c = 1.f;   // rcn_hipx_set_accumulate: 1 is off; accum_c = fl(1.0f / k)
 };
+inline bool adam_on(const Recipe& r) { return r.optim == 1; }
 inline bool sgd_default(const Recipe& r) { return r.sgd_mu == 0.f && r.sgd_wd == 0.f && !r.sgd_nesterov; }
 inline bool ema_on(const Recipe& r) { return r.ema_decay != 0.f; }
 inline bool clip_on(const Recipe& r) { return r.clip_max != 0.f; }
 
 // The launches of a step's reduction, chosen here and nowhere else.  acc: the queued slabs go through k_reduce_all_acc<first> into the
-// accumulator; update: an update launch runs, k_reduce_update<clip, sgd, ema, dlr>; buffered: it reads the step's gradient from a buffer
-// (the accumulator, the clipped step's gradient buffer) as one-chunk slabs, behind a first launch that fills that buffer.
-struct UpdateChoice { bool acc, first, update, clip, sgd, ema, dlr, buffered; };
+// accumulator; update: an update launch runs, k_reduce_update<clip, plain | sgd | adam, ema, dlr> (adam: with k_adam_tick directly in front
+// of it); buffered: it reads the step's gradient from a buffer (the accumulator, the clipped step's gradient buffer) as one-chunk slabs,
+// behind a first launch that fills that buffer.
+struct UpdateChoice { bool acc, first, update, clip, sgd, ema, dlr, buffered, adam; };
 // apply false: a gradients-only walk; micro: which micro-step of an accumulating net (kWholeStep: the net does not accumulate)
 inline UpdateChoice select_update(const Recipe& r, bool apply, int micro, bool lr_from_device) {
     UpdateChoice c{};
@@ -421,14 +426,15 @@ inline UpdateChoice select_update(const Recipe& r, bool apply, int micro, bool l
     c.first = micro == kMicroFirst;
     c.update = apply && (!c.acc || micro == kMicroLast);
     c.clip = c.update && clip_on(r);
-    c.sgd = c.update && !sgd_default(r);
+    c.adam = c.update && adam_on(r);
+    c.sgd = c.update && !c.adam && !sgd_default(r);
     c.ema = c.update && ema_on(r);
     c.dlr = c.update && lr_from_device;
     c.buffered = c.acc || c.clip;
     return c;
 }
 
-// The plan's lines for it.  An instantiation of k_reduce_update is printed as k_reduce_all[_clip][_sgd][_ema][_dlr], its display name.
+// The plan's lines for it.  An instantiation of k_reduce_update is printed as k_reduce_all[_clip][_sgd | _adam][_ema][_dlr], its display name.
 // blocks: workgroups over the queued slabs; ublocks: over the one-chunk slabs of a buffered update; nblocks: of the norm over n_pad elements.
 inline std::string describe_update(const UpdateChoice& c, const Recipe& r, int njobs, long long blocks, int ublocks, long long n_pad, long long nblocks) {
     std::string s;
@@ -436,9 +442,11 @@ inline std::string describe_update(const UpdateChoice& c, const Recipe& r, int n
     else if (c.clip) s += strf("  gradient: k_reduce_all, %d layers' slabs in one launch, %lld workgroups, into the net's gradient buffer (no update)\n", njobs, blocks);
     if (c.clip) s += strf("  norm: k_grad_sumsq, %lld elements, %lld workgroups (partial sums of squares in double, fixed order)\n", n_pad, nblocks);
     if (c.buffered && !c.update) return s;
-    s += strf("  update: k_reduce_all%s%s%s%s, ", c.clip ? "_clip" : "", c.sgd ? "_sgd" : "", c.ema ? "_ema" : "", c.dlr ? "_dlr" : "");
+    if (c.adam) s += "  tick: k_adam_tick, 1 thread (update count and bias corrections on the device)\n";
+    s += strf("  update: k_reduce_all%s%s%s%s, ", c.clip ? "_clip" : "", c.adam ? "_adam" : c.sgd ? "_sgd" : "", c.ema ? "_ema" : "", c.dlr ? "_dlr" : "");
     s += c.buffered ? strf("%d layers' gradients as one-chunk slabs, %d workgroups", njobs, ublocks) : strf("%d layers' slabs in one launch, %lld workgroups", njobs, blocks);
     if (c.sgd) s += strf(" (SGD: momentum %g, weight decay %g, nesterov %s)", (double)r.sgd_mu, (double)r.sgd_wd, r.sgd_nesterov ? "on" : "off");
+    if (c.adam) s += strf(" (Adam: betas %g %g, eps %g, weight decay %g, %s)", (double)r.adam_b1, (double)r.adam_b2, (double)r.adam_eps, (double)r.adam_wd, r.adam_decoupled ? "decoupled" : "L2");
     if (c.ema) s += strf(" (EMA: decay %g)", (double)r.ema_decay);
     if (c.clip) s += strf(" (clip: max norm %g)", (double)r.clip_max);
     if (c.acc) s += strf(" (accumulate: %d micro-batches, scale %g)", r.accum_k, (double)r.accum_c);

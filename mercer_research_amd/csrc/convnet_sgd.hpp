@@ -10,7 +10,7 @@
 // (tests/_sgd_ref.py).  Padding elements of the padded layout have g = p = v = 0 and stay 0.
 //
 //   SgdUpdate         an update functor of reduce_all_body: this update in place of p <- p - lr g in the step's ONE slab reduction
-//                     (k_reduce_update<.., SGD = true, ..>, convnet_update.hpp), the training step of a net with a non-default setting.
+//                     (k_reduce_update<.., OPT = kOptSgd, ..>, convnet_update.hpp), the training step of a net with a non-default setting.
 //                     The tap-flipped weight copy is kept current as with PlainUpdate.
 //   k_sgd_apply       the data-parallel half: the same update from an all-reduced padded gradient buffer, grid-stride, 16-byte accesses.
 #pragma once

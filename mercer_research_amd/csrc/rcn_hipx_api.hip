@@ -102,6 +102,9 @@ struct rcn_hipx_net : Selection, Recipe {
     // (reconfigure, rcn_hipx_api_update.ipp) and never moved afterwards: captured graphs hold its pointer.
     // the optimiser (convnet_sgd.hpp): `vel` (n_pad floats, laid out like params), by the first nonzero momentum
     Buf vel;
+    // Adam (convnet_adam.hpp): the moments `adam_m`, `adam_v` (n_pad floats each, laid out like params) and the 32-byte AdamTick the device
+    // advances, all three by the first rcn_hipx_set_adam; they survive a switch back to SGD, as the velocity survives a switch to Adam
+    Buf adam_m, adam_v, adam_tick;
     // the average of the parameters (convnet_ema.hpp): `ema` (n_pad floats, laid out like params), by the first decay > 0
     Buf ema;
     // clipping by global norm (convnet_clip.hpp): the first max_norm > 0 allocates the step's gradient buffer (n_pad floats), k_grad_sumsq's partials

@@ -1,10 +1,26 @@
 // rcn_hipx_api_update.ipp -- part of rcn_hipx_api.hip (one translation unit): the update path.  The step's reduction launches
 // (run_reduce_jobs: choose -- select_update, convnet_select.hpp --, make the tables, note the plan or launch) and the entry points of the
-// optimiser, the loss, the average, clipping and accumulation, with the data-parallel half (rcn_hipx_apply_sgd_dev).
+// optimisers (SGD, Adam), the loss, the average, clipping and accumulation, with the data-parallel half (rcn_hipx_apply_sgd_dev).
 
 namespace {
 
 SgdParams sgd_params(const rcn_hipx_net* n) { return SgdParams{(float*)n->vel.p, (const float*)n->params.p, n->sgd_mu, n->sgd_wd, n->sgd_nesterov}; }
+AdamParams adam_params(const rcn_hipx_net* n) {
+    return AdamParams{(float*)n->adam_m.p, (float*)n->adam_v.p, (const float*)n->params.p, (const AdamTick*)n->adam_tick.p,
+                      n->adam_b1, n->adam_b2, n->adam_a1, n->adam_a2, n->adam_eps, n->adam_wd, n->adam_decoupled};
+}
+// the update's ordinal and its bias corrections advance on the device, directly in front of the launch that reads them (convnet_adam.hpp)
+void launch_adam_tick(rcn_hipx_net* n) { hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(1), 0, n->stream, (AdamTick*)n->adam_tick.p, n->adam_b1, n->adam_b2); }
+// the tick state after `step` updates, by the device's own arithmetic
+AdamTick adam_tick_at(long long step, float b1, float b2) {
+    AdamTick t{0, 1.0, 1.0, 0.f, 0.f};
+    while (t.step < step) {
+        const AdamTick before = t;
+        adam_tick(t, b1, b2);
+        if (t.b1t == before.b1t && t.b2t == before.b2t) t.step = step;      // both products at their fixed point: every later tick only counts
+    }
+    return t;
+}
 EmaParams ema_params(const rcn_hipx_net* n) { return EmaParams{(float*)n->ema.p, (const float*)n->params.p, 1.0f - n->ema_decay}; }
 // the clipped launch's view of the net's clip state; the partials are those of the buffer k_grad_sumsq has just summed
 ClipParams clip_params(const rcn_hipx_net* n) {
@@ -55,23 +71,29 @@ int launch_reduction(rcn_hipx_net* n, const UpdateChoice& c, const ReduceTables&
         XTRY(n, hipGetLastError());
         if (!c.update) return 0;
     } else if (c.clip) {
-        hipLaunchKernelGGL((k_reduce_update<false, false, false, false>), grid, block, 0, n->stream, t.first, UpdateArgs<false, false, false, false>{});
+        hipLaunchKernelGGL((k_reduce_update<false, kOptPlain, false, false>), grid, block, 0, n->stream, t.first, UpdateArgs<false, kOptPlain, false, false>{});
         XTRY(n, hipGetLastError());
     }
     if (c.clip) {
         launch_sumsq(n, summed, n->n_pad, 1.0f, (double*)n->clip_part.p);
         XTRY(n, hipGetLastError());
     }
+    if (c.adam) {
+        launch_adam_tick(n);
+        XTRY(n, hipGetLastError());
+    }
     // gradients-only walks (apply == false) take the plain form
     const dim3 ugrid(c.buffered ? (unsigned)t.ublocks : (unsigned)t.blocks);
-    with_bool(c.clip, [&](auto CLIP) { with_bool(c.sgd, [&](auto SGD) { with_bool(c.ema, [&](auto EMA) { with_bool(c.dlr, [&](auto DLR) {
-        constexpr bool clip = decltype(CLIP)::value, sgd = decltype(SGD)::value, ema = decltype(EMA)::value, dlr = decltype(DLR)::value;
-        UpdateArgs<clip, sgd, ema, dlr> A{};            // the form's own argument list: what it reads
-        if constexpr (sgd) A.sgd() = sgd_params(n);
+    with_bool(c.clip, [&](auto CLIP) { with_const<kOptAdam, kOptSgd, kOptPlain>(c.adam ? kOptAdam : c.sgd ? kOptSgd : kOptPlain, [&](auto OPT) { with_bool(c.ema, [&](auto EMA) { with_bool(c.dlr, [&](auto DLR) {
+        constexpr bool clip = decltype(CLIP)::value, ema = decltype(EMA)::value, dlr = decltype(DLR)::value;
+        constexpr int opt = decltype(OPT)::value;
+        UpdateArgs<clip, opt, ema, dlr> A{};            // the form's own argument list: what it reads
+        if constexpr (opt == kOptSgd) A.opt() = sgd_params(n);
+        if constexpr (opt == kOptAdam) A.opt() = adam_params(n);
         if constexpr (ema) A.ema() = ema_params(n);
         if constexpr (clip) A.clip() = clip_params(n);
         if constexpr (dlr) A.lr() = lr_dev;
-        hipLaunchKernelGGL((k_reduce_update<clip, sgd, ema, dlr>), ugrid, block, 0, n->stream, t.update, A);
+        hipLaunchKernelGGL((k_reduce_update<clip, opt, ema, dlr>), ugrid, block, 0, n->stream, t.update, A);
     }); }); }); });
     XTRY(n, hipGetLastError());
     return 0;
@@ -134,11 +156,90 @@ int rcn_hipx_set_sgd(rcn_hipx_net* n, float momentum, float weight_decay, int ne
     if (!(std::isfinite(weight_decay) && weight_decay >= 0.f)) return fail(n, -1, "set_sgd: weight_decay must be finite and >= 0");
     if (nesterov != 0 && nesterov != 1) return fail(n, -1, "set_sgd: nesterov must be 0 or 1");
     if (nesterov && momentum == 0.f) return fail(n, -1, "set_sgd: nesterov needs a momentum > 0");
-    if (momentum == n->sgd_mu && weight_decay == n->sgd_wd && nesterov == n->sgd_nesterov) return 0;
+    if (!adam_on(*n) && momentum == n->sgd_mu && weight_decay == n->sgd_wd && nesterov == n->sgd_nesterov) return 0;
     Dev g(n->device);
     RTRY(reconfigure(n, {{momentum != 0.f, &n->vel, padded_bytes(n), nullptr}}));
     n->sgd_mu = momentum; n->sgd_wd = weight_decay; n->sgd_nesterov = nesterov;
+    n->optim = 0;                                       // (SGD selected again: Adam's moments and tick stay as they are)
     return 0;
+}
+
+// the tick state to and from the host, behind whatever the stream still holds
+static int read_adam_tick(rcn_hipx_net* n, AdamTick* t) {
+    XTRY(n, hipMemcpyAsync(t, n->adam_tick.p, sizeof *t, hipMemcpyDeviceToHost, n->stream));
+    XTRY(n, hipStreamSynchronize(n->stream));
+    return 0;
+}
+static int write_adam_tick(rcn_hipx_net* n, const AdamTick& t) {
+    XTRY(n, hipMemcpyAsync(n->adam_tick.p, &t, sizeof t, hipMemcpyHostToDevice, n->stream));
+    XTRY(n, hipStreamSynchronize(n->stream));
+    return 0;
+}
+
+int rcn_hipx_set_adam(rcn_hipx_net* n, float beta1, float beta2, float eps, float weight_decay, int decoupled) {
+    if (!n) return -1;
+    if (!(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f)) return fail(n, -1, "set_adam: the betas must be in [0, 1)");
+    if (!(std::isfinite(eps) && eps > 0.f)) return fail(n, -1, "set_adam: eps must be finite and > 0");
+    if (!(std::isfinite(weight_decay) && weight_decay >= 0.f)) return fail(n, -1, "set_adam: weight_decay must be finite and >= 0");
+    if (decoupled != 0 && decoupled != 1) return fail(n, -1, "set_adam: decoupled must be 0 or 1");
+    Dev g(n->device);
+    const bool fresh = !n->adam_tick.p;
+    RTRY(reconfigure(n, {{true, &n->adam_m, padded_bytes(n), nullptr}, {true, &n->adam_v, padded_bytes(n), nullptr}, {true, &n->adam_tick, sizeof(AdamTick), nullptr}}));
+    if (fresh) RTRY(write_adam_tick(n, adam_tick_at(0, beta1, beta2)));
+    else if (beta1 != n->adam_b1 || beta2 != n->adam_b2) {
+        // the running products belong to the betas: rebuilt from the update count, as the device would have made them
+        AdamTick t;
+        RTRY(read_adam_tick(n, &t));
+        if (t.step > 0) RTRY(write_adam_tick(n, adam_tick_at(t.step, beta1, beta2)));
+    }
+    n->adam_b1 = beta1; n->adam_b2 = beta2; n->adam_a1 = 1.0f - beta1; n->adam_a2 = 1.0f - beta2;
+    n->adam_eps = eps; n->adam_wd = weight_decay; n->adam_decoupled = decoupled;
+    n->optim = 1;
+    return 0;
+}
+
+int rcn_hipx_get_adam(const rcn_hipx_net* n, float* beta1, float* beta2, float* eps, float* weight_decay, int* decoupled, int* selected) {
+    if (!n) return -1;
+    if (beta1) *beta1 = n->adam_b1;
+    if (beta2) *beta2 = n->adam_b2;
+    if (eps) *eps = n->adam_eps;
+    if (weight_decay) *weight_decay = n->adam_wd;
+    if (decoupled) *decoupled = n->adam_decoupled;
+    if (selected) *selected = adam_on(*n) ? 1 : 0;
+    return 0;
+}
+
+int rcn_hipx_get_adam_state(rcn_hipx_net* n, float* m_flat, float* v_flat, int64_t* step) {
+    if (!n) return -1;
+    if (!n->adam_tick.p) return fail(n, -6, "get_adam_state: the net has no Adam state (rcn_hipx_set_adam first)");
+    Dev g(n->device);
+    if (m_flat) RTRY(unpad(n, (const float*)n->adam_m.p, m_flat));
+    if (v_flat) RTRY(unpad(n, (const float*)n->adam_v.p, v_flat));
+    if (step) {
+        AdamTick t;
+        RTRY(read_adam_tick(n, &t));
+        *step = (int64_t)t.step;
+    }
+    return 0;
+}
+
+int rcn_hipx_set_adam_state(rcn_hipx_net* n, const float* m_flat, const float* v_flat, int64_t step) {
+    if (!n || !m_flat || !v_flat) return -1;
+    if (!n->adam_tick.p) return fail(n, -6, "set_adam_state: the net has no Adam state (rcn_hipx_set_adam first)");
+    if (step < 0) return fail(n, -1, "set_adam_state: step must be >= 0");
+    Dev g(n->device);
+    RTRY(upload_padded(n, n->adam_m, m_flat));
+    RTRY(upload_padded(n, n->adam_v, v_flat));
+    return write_adam_tick(n, adam_tick_at((long long)step, n->adam_b1, n->adam_b2));      // b1t, b2t, c1, c2 rebuilt from the count
+}
+
+int rcn_hipx_reset_adam(rcn_hipx_net* n) {
+    if (!n) return -1;
+    if (!n->adam_tick.p) return 0;
+    Dev g(n->device);
+    XTRY(n, hipMemsetAsync(n->adam_m.p, 0, padded_bytes(n), n->stream));
+    XTRY(n, hipMemsetAsync(n->adam_v.p, 0, padded_bytes(n), n->stream));
+    return write_adam_tick(n, adam_tick_at(0, n->adam_b1, n->adam_b2));
 }
 
 int rcn_hipx_set_loss(rcn_hipx_net* n, float label_smoothing) {
@@ -238,7 +339,21 @@ int rcn_hipx_reset_ema(rcn_hipx_net* n) {
 int rcn_hipx_apply_sgd_dev(rcn_hipx_net* n, const float* grad, float grad_scale, float lr) {
     if (!n || !grad) return -1;
     Dev g(n->device);
-    if (clip_on(*n)) {
+    if (adam_on(*n)) {
+        // Adam: the tick, then k_adam_apply; clipping on: the norm of fl(grad_scale * g) in front, the coefficient in front of the update
+        if ((uintptr_t)grad % 16 != 0) return fail(n, -1, "apply_sgd: the gradient buffer must be 16-byte aligned");
+        const bool clip = clip_on(*n);
+        if (clip) {
+            launch_sumsq(n, grad, n->n_pad, grad_scale, (double*)n->clip_part.p);
+            XTRY(n, hipGetLastError());
+        }
+        launch_adam_tick(n);
+        XTRY(n, hipGetLastError());
+        const dim3 grid(grid1d(n->n_pad / 4, kClipThreads)), block(kClipThreads);
+        if (clip) hipLaunchKernelGGL(k_adam_apply<true>, grid, block, 0, n->stream, (float*)n->params.p, grad, grad_scale, lr, adam_params(n), n->n_pad, clip_params(n));
+        else hipLaunchKernelGGL(k_adam_apply<false>, grid, block, 0, n->stream, (float*)n->params.p, grad, grad_scale, lr, adam_params(n), n->n_pad, ClipParams{});
+        XTRY(n, hipGetLastError());
+    } else if (clip_on(*n)) {
         // clipping on, whatever the optimiser: the norm of fl(grad_scale * g), then k_sgd_apply with the coefficient in front of the update
         if ((uintptr_t)grad % 16 != 0) return fail(n, -1, "apply_sgd: the gradient buffer must be 16-byte aligned");
         launch_sumsq(n, grad, n->n_pad, grad_scale, (double*)n->clip_part.p);
