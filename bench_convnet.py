@@ -183,6 +183,10 @@ def main():
                     help="gradient accumulation: every K steps form one update on the mean of their gradients (rcn_hipx_set_accumulate; 1: off), set before the "
                          "warm-up; --warmup and --steps are rounded up to multiples of K; ms_per_step and images/s stay per micro-step, the line gains accumulate "
                          "and ms_per_update (single GPU: the data-parallel step does not accumulate)")
+    ap.add_argument("--dropout", type=float, default=0.0, metavar="P",
+                    help="inverted dropout with rate P behind every dense_relu layer, the masks drawn inside the step's graph (rcn_hipx_set_dropout; 0: off), set "
+                         "before the warm-up: a tick launch and two elementwise launches per site in the step's graph; the line gains dropout")
+    ap.add_argument("--dropout-seed", type=int, default=0, metavar="S", help="the seed of --dropout's draws; a data-parallel rank draws with S + rank")
     ap.add_argument("--dataset", type=int, default=0, metavar="N",
                     help="also keep a synthetic set of N images resident (uint8 for mnist / cifar, fp32 for synth224), time train_epoch over whole epochs with a fresh "
                          "device permutation each, then evaluate over the set: the line gains epoch_ms_per_step, epoch_images_per_s, eval_images_per_s, graphs_instantiated "
@@ -210,6 +214,8 @@ def main():
         ap.error("--clip: M >= 0 (inf allowed)")
     if not 1 <= args.accumulate <= 65536:
         ap.error("--accumulate: 1 <= K <= 65536")
+    if not 0.0 <= args.dropout < 1.0:
+        ap.error("--dropout: 0 <= P < 1")
     if not 0.0 <= args.label_smoothing < 1.0:
         ap.error("--label-smoothing: 0 <= E < 1")
     if (args.lr_schedule != "none" or args.augment >= 0 or args.trap) and not args.dataset:
@@ -259,6 +265,8 @@ def main():
         net.set_clip(args.clip)
     if K > 1:
         net.set_accumulate(K)
+    if args.dropout > 0:
+        net.set_dropout(args.dropout, args.dropout_seed + rank)      # (another seed per rank: the same one would drop the same units in every shard)
     rng = np.random.default_rng(rank)
     nbuf = 8 if args.config != "synth224" else 2           # rotate over several resident batches
     xs = [net.to_device(rng.standard_normal((B,) + in_shape).astype(np.float32)) for _ in range(nbuf)]
@@ -376,6 +384,7 @@ def main():
                           "dtype": "f32" if not bf16 else "bf16 MFMA operands (fwd, dgrad, wgrad), f32 accumulate/update" + (", conv-stage activations and gradients stored as bf16" if args.precision == "bf16_stored" else ""), "data": "synthetic", "final_loss": round(loss.item(), 4),
                           "optimizer": args.optimizer, "ema_decay": args.ema,
                           "accumulate": K, "ms_per_update": round(el / args.steps * 1e3 * K, 4),
+                          "dropout": args.dropout,
                           "clip_max_norm": args.clip, "grad_norm_last": round(net.grad_norm()[0], 6) if args.clip > 0 else None,
                           "data_parallel_step": dp_mode,
                           "data_parallel_allreduce": (None if not dp else "one all-reduce of the flat gradient after the backward pass" if args.dp_buckets <= 0 else

@@ -431,6 +431,53 @@ int  rcn_hipx_set_accumulate(rcn_hipx_net* net, int k);
 int  rcn_hipx_get_accumulate(const rcn_hipx_net* net, int* k, int* pending);
 int  rcn_hipx_reset_accumulation(rcn_hipx_net* net);
 int  rcn_hipx_get_accumulated(rcn_hipx_net* net, float* flat);
+/* Dropout behind the hidden dense layers: inverted dropout with the semantics of torch.nn.Dropout(p) in training mode behind EVERY
+ * RCN_HIPX_DENSE_RELU layer of the net (VGG / AlexNet: Linear-ReLU-Dropout).  Site d is the d-th such layer in layer order, from 0; the
+ * layer list and rcn_hipx_layer do not change.  The masks are drawn inside the step's graph from a counter-based generator of the
+ * library's own (not torch's stream) and never stored.  Host constants, computed once in rcn_hipx_set_dropout:
+ *     s = fl(1.0f / fl(1.0f - p));    thr = (uint32_t)llrint((double)p * 16777216.0), so a drop has probability thr / 2^24
+ * Element idx = r * U + u of site d (row r < B, unit u < U, U the layer's units) draws in the training forward with ordinal t, in wrapping
+ * uint64 arithmetic:
+ *     z = seed ^ (t * 0xD1342543DE82EF95);   z += ((((uint64)d << 48) + idx) + 1) * 0x9E3779B97F4A7C15
+ *     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^= z >> 31
+ *     keep = (uint32)(z >> 40) >= thr
+ * Forward (k_dropout_fwd, in place in the layer's output buffer, directly behind that layer's forward launch):
+ *     a' = keep ? fl(a * s) : +0.0f
+ * Everything downstream reads a': the next layer's forward and the fused head (k_head_f32), that layer's weight gradient, and the ReLU
+ * gate of the gradient that comes back, which compares that same buffer with 0 -- since s >= 1 is finite, a' > 0 holds exactly when the
+ * element was kept and a > 0, so the existing gate already applies the mask.  Backward (k_dropout_bwd): the gated gradient g that the
+ * layer above, or the head, writes into the site layer's gradient buffer becomes fl(g * s), in place, directly behind that launch and
+ * before anything reads it (the site layer's weight gradient and input gradient, the side stream of rcn_hipx_set_overlap).  Every
+ * operation is rounded once, no fused multiply-add (tests/_dropout_ref.py restates draw, forward and backward in NumPy, bit for bit).
+ * The ordinal t is an int64 on the device, allocated once and never moved, starting at 0.  While p > 0, k_dropout_tick (one thread) is the
+ * first launch of every training forward and does t += 1; the sites of that forward use the value it leaves, so the first forward uses
+ * t = 1.  It is captured with the step: a replayed graph draws fresh masks, and dropout adds no graph.  A training forward is the front of
+ * rcn_hipx_train_step_dev, rcn_hipx_train_step_pair_dev, every step of the three epoch entries, EACH micro-step of an accumulating net,
+ * rcn_hipx_gradients_dev and rcn_hipx_gradients_begin_dev.  Nothing else ticks.  Inference never drops and never scales:
+ * rcn_hipx_forward_dev, rcn_hipx_evaluate_dev / _ex_dev and the evaluation plans are what they were.  Data-parallel ranks give different
+ * seeds (the same seed would drop the same units in every rank's shard).
+ * rcn_hipx_set_dropout: net state, like rcn_hipx_set_sgd.  Accepts a finite 0 <= p < 1; anything else returns -1 and changes nothing;
+ * p > 0 on a net without a RCN_HIPX_DENSE_RELU layer returns -3 and changes nothing.  p == 0 is the default: the same kernels, launches,
+ * arguments, graph keys, plan text and bits as a net never configured, also after a p > 0.  A changed p or seed synchronises the net's
+ * stream and drops its captured graphs.  The ordinal survives rcn_hipx_set_params, rcn_hipx_init_params, changes of optimiser, precision,
+ * tiling, overlap, options and of p and seed, like the velocity.  _get_dropout: any pointer may be NULL; `sites` is the number of
+ * RCN_HIPX_DENSE_RELU layers.  _get_dropout_state: the training forwards counted so far, read after a synchronise of the net's stream (0
+ * while none was counted).  _set_dropout_state: forwards >= 0, else -1; the next training forward draws with forwards + 1.
+ * rcn_hipx_dropout_draw: the draw itself, pure host code (no net, no GPU): *keep = 1 or 0 for (p, seed, t, site, idx); -1 for a p outside
+ * [0, 1), a site outside 0 .. 65535 or a NULL keep.
+ * rcn_hipx_dropout_apply_dev: k_dropout_fwd with the net's p and seed on the caller's [B][U] buffer (U the units of `site`; 16-byte
+ * aligned; 1 <= B <= max_batch) with an explicit t, enqueued on the net's stream.  It does not touch the ordinal.
+ * The plans of a net (rcn_hipx_plan_net, _plan_epoch_net, _plan_epoch_mix_net, _plan_micro_net) gain, in launch order, a
+ * "tick: k_dropout_tick" line, a "dropout site d (U units, p P): k_dropout_fwd, N workgroups" line behind its layer and a
+ * "dropout-bwd site d: k_dropout_bwd" line behind the launch that writes the gradient; rcn_hipx_plan, _plan_eval and _plan_buckets, which
+ * take no net, are unchanged.
+ * Out of scope: a p per site, dropout in the convolutional stage (spatial dropout), a mask kept in memory, torch's own random stream. */
+int  rcn_hipx_set_dropout(rcn_hipx_net* net, float p, uint64_t seed);
+int  rcn_hipx_get_dropout(const rcn_hipx_net* net, float* p, uint64_t* seed, int* sites);
+int  rcn_hipx_get_dropout_state(rcn_hipx_net* net, int64_t* forwards);
+int  rcn_hipx_set_dropout_state(rcn_hipx_net* net, int64_t forwards);
+int  rcn_hipx_dropout_draw(float p, uint64_t seed, uint64_t t, int site, uint64_t idx, int* keep);
+int  rcn_hipx_dropout_apply_dev(rcn_hipx_net* net, int site, int64_t t, float* a_dev, int B);
 /* The same gradients in BUCKETS, so that a data-parallel step can all-reduce one bucket of layers while the backward pass of the layers
  * below it still runs (6.7 MB of gradient for BASELINE configs[3]).  The layers with parameters, in the order the
  * backward pass finishes them (last to first), are cut into buckets of at least min_bucket_bytes of gradient; the padded flat layout

@@ -152,6 +152,12 @@ SIGNATURES = {
     "rcn_hipx_reset_accumulation": (_i, [_vp]),
     "rcn_hipx_get_accumulated": (_i, [_vp, C.POINTER(C.c_float)]),
     "rcn_hipx_plan_micro_net": (_i, [_vp, _i, _i, C.c_char_p, _i]),
+    "rcn_hipx_set_dropout": (_i, [_vp, C.c_float, C.c_uint64]),
+    "rcn_hipx_get_dropout": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "rcn_hipx_get_dropout_state": (_i, [_vp, C.POINTER(C.c_int64)]),
+    "rcn_hipx_set_dropout_state": (_i, [_vp, C.c_int64]),
+    "rcn_hipx_dropout_draw": (_i, [C.c_float, C.c_uint64, C.c_uint64, _i, C.c_uint64, C.POINTER(C.c_int)]),
+    "rcn_hipx_dropout_apply_dev": (_i, [_vp, _i, C.c_int64, _vp, _i]),
 }
 _libx = None
 
@@ -241,6 +247,19 @@ def augment_draws(aug: Augment, q0: int, count: int) -> np.ndarray:
         if lib.rcn_hipx_augment_draw(C.byref(a), (int(q0) + k) & (2 ** 64 - 1), C.byref(dy), C.byref(dx), C.byref(fl)) != 0:
             raise ConvNetError(f"rcn_hipx_augment_draw refuses {aug}")
         out[k] = (dy.value, dx.value, fl.value)
+    return out
+
+
+def dropout_keep(p: float, seed: int, t: int, site: int, count: int) -> np.ndarray:
+    """The keep / drop draws of elements 0 .. count - 1 of dropout site `site` in the training forward with ordinal t, as a bool array
+    (True: kept), from rcn_hipx_dropout_draw: the host side of the one function k_dropout_fwd runs.  Needs no GPU."""
+    lib = load()
+    out = np.zeros(int(count), dtype=bool)
+    k = C.c_int()
+    for i in range(int(count)):
+        if lib.rcn_hipx_dropout_draw(float(p), int(seed) & (2 ** 64 - 1), int(t) & (2 ** 64 - 1), int(site), i, C.byref(k)) != 0:
+            raise ConvNetError(f"rcn_hipx_dropout_draw refuses p = {p}, site = {site}")
+        out[i] = bool(k.value)
     return out
 
 
@@ -704,6 +723,41 @@ class ConvNet:
         if kind not in MICRO_KINDS:
             raise ValueError(f"kind must be one of {sorted(MICRO_KINDS)}, not {kind!r}")
         return _plan_text("rcn_hipx_plan_micro_net", self.lib.rcn_hipx_plan_micro_net, self.net, int(batch), MICRO_KINDS[kind])
+
+    def set_dropout(self, p: float = 0.0, seed: int = 0):
+        """Inverted dropout behind every dense_relu layer, as torch.nn.Dropout(p) in training mode, the masks drawn inside the step's graph
+        from (seed, ordinal of the training forward, site, element) (include/rcn_hipx.h, rcn_hipx_set_dropout).  0 is the default: off.
+        forward, evaluate and predict never drop.  Data-parallel ranks give different seeds."""
+        self._ck(self.lib.rcn_hipx_set_dropout(self.net, float(p), int(seed) & (2 ** 64 - 1)))
+
+    def get_dropout(self) -> Tuple[float, int, int]:
+        """(p, seed, sites): sites is the number of dense_relu layers."""
+        p, seed, sites = C.c_float(), C.c_uint64(), C.c_int()
+        self._ck(self.lib.rcn_hipx_get_dropout(self.net, C.byref(p), C.byref(seed), C.byref(sites)))
+        return float(p.value), int(seed.value), int(sites.value)
+
+    def dropout_state(self) -> int:
+        """The training forwards dropout has counted so far (the ordinal of the last one); synchronises."""
+        t = C.c_int64()
+        self._ck(self.lib.rcn_hipx_get_dropout_state(self.net, C.byref(t)))
+        return int(t.value)
+
+    def set_dropout_state(self, t: int):
+        """The next training forward draws with ordinal t + 1."""
+        self._ck(self.lib.rcn_hipx_set_dropout_state(self.net, int(t)))
+
+    def dropout_apply(self, site: int, t: int, a):
+        """The forward launch of dropout site `site` with the net's p and seed and an explicit ordinal t, IN PLACE on a: a contiguous float32
+        [B, units of the site] tensor on the net's device (rcn_hipx_dropout_apply_dev), enqueued on the net's stream.  The net's own ordinal
+        is not touched.  Returns a."""
+        tt = self.torch
+        if not tt.is_tensor(a) or a.dtype != tt.float32 or a.device != self.device or not a.is_contiguous() or a.dim() != 2:
+            raise ValueError("dropout_apply: a contiguous two-dimensional float32 tensor on the net's device")
+        units = [l[1] for l in self.layers if l[0] == "dense_relu"]
+        if not 0 <= int(site) < len(units) or a.shape[1] != units[int(site)]:
+            raise ValueError(f"dropout_apply: site in 0 .. {len(units) - 1} and a of [B, units of that site]")
+        self._ck(self.lib.rcn_hipx_dropout_apply_dev(self.net, int(site), int(t), _ptr(a), int(a.shape[0])))
+        return a
 
     def apply_sgd(self, grad, grad_scale: float, lr: float):
         """The data-parallel half of the configured optimiser (set_sgd's or set_adam's): the same update from a padded gradient buffer,

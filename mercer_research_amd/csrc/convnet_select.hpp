@@ -397,7 +397,7 @@ inline bool wgrad_halo_runs(const Selection& sel, const ConvShape& s, int ks) { 
 // rcn_hipx_set_accumulate -- the first stores into the accumulator, a middle one adds, the last adds and applies the update
 enum Micro { kWholeStep = 0, kMicroFirst = 1, kMicroMiddle = 2, kMicroLast = 3 };
 
-// Everything an update is configured with (rcn_hipx_net derives from it; a dry-run net copies it in one assignment, so the plan and the
+// Everything an update is configured with, and the dropout in front of it (rcn_hipx_net derives from it; a dry-run net copies it in one assignment, so the plan and the
 // step agree by construction).  The buffers and the state these settings need stay members of the net.
 struct Recipe {
     int optim = 0;                          // the optimiser selected: 0 SGD (rcn_hipx_set_sgd, the default), 1 Adam (rcn_hipx_set_adam)
@@ -408,11 +408,14 @@ struct Recipe {
     float ema_decay = 0.f;                  // rcn_hipx_set_ema: 0 is off
     float clip_max = 0.f;                   // rcn_hipx_set_clip: 0 is off
     int accum_k = 1; float accum_c = 1.f;   // rcn_hipx_set_accumulate: 1 is off; accum_c = fl(1.0f / k)
+    // rcn_hipx_set_dropout (convnet_dropout.hpp): 0 is off; drop_s = fl(1.0f / fl(1.0f - p)), drop_thr = llrint(p * 2^24)
+    float drop_p = 0.f; unsigned long long drop_seed = 0; float drop_s = 1.f; unsigned drop_thr = 0;
 };
 inline bool adam_on(const Recipe& r) { return r.optim == 1; }
 inline bool sgd_default(const Recipe& r) { return r.sgd_mu == 0.f && r.sgd_wd == 0.f && !r.sgd_nesterov; }
 inline bool ema_on(const Recipe& r) { return r.ema_decay != 0.f; }
 inline bool clip_on(const Recipe& r) { return r.clip_max != 0.f; }
+inline bool dropout_on(const Recipe& r) { return r.drop_p != 0.f; }
 
 // The launches of a step's reduction, chosen here and nowhere else.  acc: the queued slabs go through k_reduce_all_acc<first> into the
 // accumulator; update: an update launch runs, k_reduce_update<clip, plain | sgd | adam, ema, dlr> (adam: with k_adam_tick directly in front

@@ -26,6 +26,7 @@
 #include "convnet_select.hpp"
 #include "convnet_update.hpp"
 #include "convnet_accum.hpp"
+#include "convnet_dropout.hpp"
 
 using namespace rcnx;
 
@@ -79,7 +80,8 @@ struct Pair { const int32_t* labels_b = nullptr; const float* weight = nullptr; 
 }  // namespace
 
 // precision, store16, tiling and the kernel-selection options are the net's Selection (convnet_select.hpp): all that choosing a kernel reads;
-// the optimiser, the loss, the average, clipping and accumulation are its Recipe: all that choosing and describing an update reads
+// the optimiser, the loss, the average, clipping, accumulation and dropout are its Recipe: all that choosing and describing an update (and
+// the dropout launches of a training forward) reads
 struct rcn_hipx_net : Selection, Recipe {
     int device = 0, in_h = 0, in_w = 0, in_c = 0, max_batch = 0, classes = 0;
     hipStream_t stream = nullptr; bool own_stream = false;
@@ -119,6 +121,9 @@ struct rcn_hipx_net : Selection, Recipe {
     // advanced when a micro-step has been enqueued.
     int accum_pos = 0;
     Buf accum;
+    // dropout (convnet_dropout.hpp): the ordinal of the training forward, an int64 the device advances (k_dropout_tick), by the first p > 0
+    // or the first rcn_hipx_set_dropout_state; zero at its start, never moved, and it survives what the velocity survives
+    Buf drop_tick;
     // The captured steps, one cache per family (family_of): the caller's pointers plain or on pair labels (rcn_hipx_train_step_dev /
     // _pair_dev), and the epoch's steps on the net's own buffers x (rate from the host | from the device) x (mixed or not).  A family
     // that holds eight graphs and needs a ninth drops its own; drop_graphs drops them all.
@@ -462,8 +467,42 @@ int prep_bf16_weights(rcn_hipx_net* n) {
     return 0;
 }
 
+// ---- dropout (convnet_dropout.hpp): site d is the d-th RCN_HIPX_DENSE_RELU layer
+int dropout_sites(const rcn_hipx_net* n) { int d = 0; for (const Layer& l : n->L) d += l.kind == RCN_HIPX_DENSE_RELU; return d; }
+// the site of layer i (a RCN_HIPX_DENSE_RELU layer)
+int dropout_site_of(const rcn_hipx_net* n, size_t i) { int d = 0; for (size_t k = 0; k < i; ++k) d += n->L[k].kind == RCN_HIPX_DENSE_RELU; return d; }
+unsigned dropout_blocks(long long n4) { return (unsigned)((n4 + kDropThreads - 1) / kDropThreads); }
+// t += 1 on the device: the first launch of a training forward
+int launch_dropout_tick(rcn_hipx_net* n) {
+    if (dry_note(n, "  tick: k_dropout_tick, 1 thread (the ordinal of the training forward, on the device)")) return 0;
+    hipLaunchKernelGGL(k_dropout_tick, dim3(1), dim3(1), 0, n->stream, (long long*)n->drop_tick.p);
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+// a' = keep ? fl(a * s) : +0 in place over a[B][U], the draws of site d at the ordinal *t_dev (t_dev == nullptr: at t_imm)
+int launch_dropout_fwd(rcn_hipx_net* n, int d, float* a, int B, int U, const long long* t_dev, long long t_imm) {
+    const long long n4 = (long long)B * U / 4;
+    if (dry_note(n, "  dropout site %d (%d units, p %g): k_dropout_fwd, %u workgroups", d, U, (double)n->drop_p, dropout_blocks(n4))) return 0;
+    hipLaunchKernelGGL(k_dropout_fwd, dim3(dropout_blocks(n4)), dim3(kDropThreads), 0, n->stream, a, n4, U,
+                       DropSpec{n->drop_seed, (unsigned long long)d << 48, n->drop_thr, n->drop_s}, t_dev, t_imm);
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+// g <- fl(g * s) in place over the gated gradient in layer i's dout (a site layer), directly behind the launch that wrote it
+int launch_dropout_bwd(rcn_hipx_net* n, size_t i, int B) {
+    Layer& l = n->L[i];
+    const long long n4 = (long long)B * l.CoutP / 4;
+    if (dry_note(n, "  dropout-bwd site %d: k_dropout_bwd, %u workgroups", dropout_site_of(n, i), dropout_blocks(n4))) return 0;
+    hipLaunchKernelGGL(k_dropout_bwd, dim3(dropout_blocks(n4)), dim3(kDropThreads), 0, n->stream, (float*)l.dout.p, n4, n->drop_s);
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+
 // forward for batch B; returns pointer to logits (padded rows of CoutP)
-int forward(rcn_hipx_net* n, const float* x, int B, size_t n_layers = (size_t)-1) {
+// train: the forward of a training step (step_front) -- with dropout on, every RCN_HIPX_DENSE_RELU layer's output goes through its site's
+// mask; every other forward (rcn_hipx_forward_dev, evaluation) never drops and never scales
+int forward(rcn_hipx_net* n, const float* x, int B, size_t n_layers = (size_t)-1, bool train = false) {
+    const bool drop = train && dropout_on(*n);
     const float* cur = x;
     bool cur16 = false;                                  // `cur` is a bf16 tensor (RCN_HIPX_BF16_STORED)
     if (n_layers > n->L.size()) n_layers = n->L.size();
@@ -494,6 +533,7 @@ int forward(rcn_hipx_net* n, const float* x, int B, size_t n_layers = (size_t)-1
             // (the logits layer of a head that training runs as k_head_f32 is fp32 here too: what bf16 mode rounds is a matter of shape)
             RTRY(launch_conv(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShape{B, 1, 1, l.K, l.CoutP}, 1, l.kind == RCN_HIPX_DENSE_RELU ? 2 : 1, nullptr, nullptr,
                              i + 1 == n->L.size() && head_fusable(n), wb_of(n, l.wbf_off), Store{cur16, false}));
+            if (drop && l.kind == RCN_HIPX_DENSE_RELU) RTRY(launch_dropout_fwd(n, dropout_site_of(n, i), (float*)l.out.p, B, l.CoutP, (const long long*)n->drop_tick.p, 0));
         }
         cur = (const float*)l.out.p;
         cur16 = false;
@@ -594,6 +634,7 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             RTRY(launch_conv(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, ConvShape{s.N, s.H, s.W, s.Cout, s.Cin}, ks, gate ? 3 : 0,
                              nullptr, pooled[i].dP ? &pooled[i] : nullptr, false, wb_of(n, l.wbb_off), Store{stage16(n, i), stage16(n, i - 1)}));
             gated[i - 1] = gate;
+            if (below.kind == RCN_HIPX_DENSE_RELU && dropout_on(*n)) RTRY(launch_dropout_bwd(n, (size_t)i - 1, B));      // before anything reads that gradient
         }
         int chunks = 0;
         if (on_side) n->stream = n->side;
@@ -720,18 +761,20 @@ int refresh_flipped(rcn_hipx_net* n) {
 // walk starts at; *gated: its dout already holds dZ.
 int step_front(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float* grad, bool apply, float* loss_dev, int* first, bool* gated, const Pair& pair = Pair{}) {
     n->jobs.njobs = 0;
+    if (dropout_on(*n)) RTRY(launch_dropout_tick(n));      // this forward's masks: the ordinal it leaves
     RTRY(prep_bf16_weights(n));
     const int last = (int)n->L.size() - 1;
     *gated = head_fusable(n);
     *first = *gated ? last - 1 : last;
     if (!*gated) {
-        RTRY(forward(n, x, B));
+        RTRY(forward(n, x, B, (size_t)-1, true));
         return loss_and_dlogits(n, labels, B, loss_dev, true, pair);
     }
-    RTRY(forward(n, x, B, (size_t)last));
+    RTRY(forward(n, x, B, (size_t)last, true));
     int chunks = 0;
     n->slab_sel = &n->L[last].slab;
     RTRY(launch_head(n, labels, B, loss_dev, &chunks, pair));
+    if (dropout_on(*n)) RTRY(launch_dropout_bwd(n, (size_t)last - 1, B));      // (the head wrote the gated gradient into the site layer's dout)
     return reduce_slab(n, (size_t)last, chunks, 1, ConvShape{B, 1, 1, n->L[last].K, n->L[last].CoutP}, grad, apply);
 }
 
@@ -862,7 +905,7 @@ int make_dry_net(rcn_hipx_net& net, int in_h, int in_w, int in_c, const rcn_hipx
     seed_options(net.opt);
     return describe_layers(&net, in_h, in_w, in_c, layers, n_layers);
 }
-// ... or from an existing net: its layers, precision, tiling, options, optimiser, loss, average, clipping and accumulation -- the plan and the step agree by construction
+// ... or from an existing net: its layers, precision, tiling, options, optimiser, loss, average, clipping, accumulation and dropout -- the plan and the step agree by construction
 void make_dry_net(rcn_hipx_net& net, const rcn_hipx_net& from, int batch) {
     net.in_h = from.in_h; net.in_w = from.in_w; net.in_c = from.in_c; net.max_batch = batch; net.classes = from.classes; net.dry = true;
     static_cast<Selection&>(net) = from;
@@ -1549,3 +1592,4 @@ int rcn_hipx_plan_eval_net(const rcn_hipx_net* n, int batch, char* out, int cap)
 }  // extern "C"
 
 #include "rcn_hipx_api_update.ipp"
+#include "rcn_hipx_api_dropout.ipp"
