@@ -203,10 +203,17 @@ def main():
                     help="with --dataset: time the recipe's epochs once more with the smoothed loss (rcn_hipx_set_loss): mix_epoch_ms_per_step beside recipe_epoch_ms_per_step")
     ap.add_argument("--mix", choices=["none", "mixup", "cutmix", "both"], default="none",
                     help="with --dataset: those epochs mix every batch with its mirror image by mix_plan's records (mixup alpha 0.8, CutMix alpha 1.0; k_gather_mix, pair labels)")
+    ap.add_argument("--snapshot-every", type=int, default=0, metavar="N",
+                    help="take a full snapshot of the net's state (rcn_hipx_snapshot_dev: ONE pack launch on the net's stream, no synchronise) behind every N-th timed "
+                         "step, into one body allocated before the warm-up; the line gains snapshot_sections, snapshot_bytes and snapshot_us, the mean stream time of "
+                         "the pack launch from events around it (0: none; single GPU).  With it, --momentum beside --optimizer adam / adamw is allowed: the velocity "
+                         "buffer then exists and is carried, so all six sections can be present")
     args = ap.parse_args()
     if (args.label_smoothing != 0.0 or args.mix != "none") and not args.dataset:
         ap.error("--label-smoothing and --mix time the resident epoch: they need --dataset N")
-    if args.optimizer != "sgd" and (args.momentum != 0.0 or args.nesterov):
+    if args.snapshot_every < 0:
+        ap.error("--snapshot-every: N >= 0")
+    if args.optimizer != "sgd" and (args.momentum != 0.0 or args.nesterov) and not args.snapshot_every:
         ap.error("--optimizer adam / adamw: --momentum and --nesterov belong to SGD")
     if not 0.0 <= args.ema < 1.0:
         ap.error("--ema: 0 <= D < 1")
@@ -234,6 +241,8 @@ def main():
     dp = world > 1 or args.force_dp
     if dp and args.dataset:
         sys.exit("--dataset times the single-GPU epoch; a data-parallel epoch does not exist")
+    if dp and args.snapshot_every:
+        sys.exit("--snapshot-every times the single-GPU step")
     if dp and args.accumulate > 1:
         sys.exit("--accumulate: the data-parallel step (gradients -> all-reduce -> apply) does not accumulate; accumulation across ranks does not exist")
     K = args.accumulate
@@ -256,6 +265,8 @@ def main():
     net.set_precision(args.precision)
     sgd = args.momentum != 0.0 or args.weight_decay != 0.0 or args.nesterov
     if args.optimizer != "sgd":
+        if sgd and args.snapshot_every:
+            net.set_sgd(args.momentum, args.weight_decay, args.nesterov)      # (the velocity exists under Adam: a sixth section to carry)
         net.set_adam(tuple(args.betas), args.eps, args.weight_decay, args.optimizer == "adamw")
     elif sgd:
         net.set_sgd(args.momentum, args.weight_decay, args.nesterov)
@@ -345,6 +356,10 @@ def main():
 
         def step(i):
             net.train_step(xs[buffer_of(i)], ys[buffer_of(i)], lr, loss)
+    snap_body, snap_events, snap_last = None, [], None
+    if args.snapshot_every:
+        snap_last = net.snapshot()                         # (sizes the body; every timed snapshot packs into this one buffer)
+        snap_body = snap_last.body
     net.synchronize()
     for i in range(-(-max(args.warmup, 2 * nbuf) // K) * K):      # first use of each (x, y) pair instantiates its graph; whole cycles
         step(i)
@@ -355,6 +370,13 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.steps):
         step(i)
+        if args.snapshot_every and (i + 1) % args.snapshot_every == 0:
+            with torch.cuda.stream(net.stream):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                snap_last = net.snapshot(body=snap_body)
+                e1.record()
+            snap_events.append((e0, e1))
     net.synchronize()
     if dp:
         dist.barrier()
@@ -367,6 +389,11 @@ def main():
     flops = net.step_flops(B)
     tf = flops * args.steps / el / 1e12                    # per GPU
     extra = resident_set_figures(net, args, in_shape, B, lr) if args.dataset else {}
+    if args.snapshot_every:
+        from mercer_research_amd.convnet import SECTIONS
+        extra.update({"snapshot_every": args.snapshot_every, "snapshots": len(snap_events),
+                      "snapshot_sections": [name for name, bit in SECTIONS.items() if snap_last.desc.sections & bit], "snapshot_bytes": int(snap_last.desc.body_bytes),
+                      "snapshot_us": round(sum(a.elapsed_time(b) for a, b in snap_events) / len(snap_events) * 1e3, 2) if snap_events else None})
     if rank == 0:
         # the peak a fraction is quoted against is the peak of the MFMA the GEMMs actually issue: fp32 MFMA (157.3 TF) in fp32
         # mode, dense bf16 MFMA (~2.5 PF) in bf16 mode -- and for the bf16 path, which is HBM-bound, the step's HBM floor

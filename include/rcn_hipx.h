@@ -478,6 +478,83 @@ int  rcn_hipx_get_dropout_state(rcn_hipx_net* net, int64_t* forwards);
 int  rcn_hipx_set_dropout_state(rcn_hipx_net* net, int64_t forwards);
 int  rcn_hipx_dropout_draw(float p, uint64_t seed, uint64_t t, int site, uint64_t idx, int* keep);
 int  rcn_hipx_dropout_apply_dev(rcn_hipx_net* net, int site, int64_t t, float* a_dev, int B);
+/* Save and resume: the whole training state of a net packed into ONE contiguous device buffer (the BODY, which the caller owns) by one
+ * launch on the net's stream, and put back by one launch.  A body and its descriptor are everything a run needs to continue bit for bit:
+ * an epoch split at any micro-batch across two PROCESSES gives the bits of the unsplit epoch, as it does across two calls.
+ * The body (csrc/convnet_state.hpp): 16-byte aligned; bytes [0, 256) are the scalars block -- raw copies of the 32-byte Adam tick (step,
+ * running products, bias corrections) at byte 0, of the 8-byte dropout ordinal at byte 32 and of the 16-byte clip state (update counter,
+ * norm, coef) at byte 40; a buffer the net does not have, and the rest of the block, are zero --; then the selected SECTIONS, each at a
+ * multiple of 256 bytes (section_off; zeros fill up to the next), each n_log floats in the logical layout of rcn_hipx_get_params: the parameters, the velocity,
+ * Adam's m and v, the average, the accumulator.  The tap-flipped weight copy and the bf16 operand copies are not stored: a restore re-makes
+ * the first, the next step the second.
+ * The descriptor, a plain C struct, describes a body and carries everything that is not in it: magic and version; the input shape, the layer
+ * list (RCN_HIPX_STATE_MAX_LAYERS entries; a pool's `out` is 0), classes and n_log; layer_off[i], the float offset of layer i's W inside a
+ * section (-1 for a pool; its b follows its W); the precision mode (all three) and the tiling; the section mask, section_off[s] in bytes (-1:
+ * absent) and body_bytes; `flags`: which of the three scalar copies are real, and RCN_HIPX_STATE_HAS_RECIPE; every value the recipe's
+ * setters take -- optimiser selected (0 SGD, 1 Adam), rcn_hipx_set_sgd's three, rcn_hipx_set_adam's five, rcn_hipx_set_loss, _set_ema,
+ * _set_clip, _set_accumulate, _set_dropout's two -- and accum_pos, the position in the open accumulation cycle.
+ * rcn_hipx_state_desc_size: sizeof(rcn_hipx_state_desc), for bindings.
+ * rcn_hipx_state_layout: pure host code, no net and no GPU (like rcn_hipx_plan): shape, layer offsets, section offsets and body_bytes of a
+ * body with `sections` (the parameters are always in) for a net of this description; precision, tiling and the recipe at their defaults,
+ * flags 0.  -1: a NULL pointer, a non-positive size, unknown section bits; -3: more than RCN_HIPX_STATE_MAX_LAYERS layers; -2 / -3 as
+ * rcn_hipx_create for a description it refuses.
+ * rcn_hipx_snapshot_dev: fills *desc_out on the host from the net as it is when the call is made (accum_pos included) and enqueues ONE launch,
+ * k_state_pack, on the net's stream, which reads the net's buffers and writes body_dev[0, body_bytes).  sections == 0: every section whose
+ * buffer exists; else exactly the sections named, plus the parameters.  The snapshot is the state at that point of the stream: exactly
+ * between the steps enqueued before and after it, with no synchronise; nothing blocks, nothing of the net is written, nothing is captured
+ * or dropped -- the net's graphs, their keys, rcn_hipx_graphs_instantiated and the plan texts are what they were.  The body is valid once the
+ * net's stream has got there (an event recorded behind the call).  -1: a NULL argument, unknown section bits, a body that is not 16-byte
+ * aligned, cap_bytes < body_bytes; -6: a named section whose buffer the net does not have, or an open bucket walk
+ * (rcn_hipx_gradients_begin_dev); -3: more than RCN_HIPX_STATE_MAX_LAYERS layers, or more than 16 with parameters.  Nothing is enqueued
+ * then.  A caller that wants the parameters alone names RCN_HIPX_STATE_PARAMS and clears `flags`.
+ * rcn_hipx_restore_dev: checks everything on the host BEFORE anything changes -- a wrong magic or version, unknown bits, a section outside
+ * body_bytes or not 256-byte aligned, body_bytes smaller than the descriptor's, a body that is not 16-byte aligned, a recipe value its
+ * setter would refuse: -1; an input shape, layer list, classes or n_log that is not the net's: -2; RCN_HIPX_BF16_STORED on a net whose
+ * layers the bf16-tensor kernels do not cover: -3 (rcn_hipx_set_precision's check and text); an open bucket walk: -6 -- and after a refusal
+ * the net is bit for bit what it was.  Then it applies the tiling, the precision and, with RCN_HIPX_STATE_HAS_RECIPE, the recipe through
+ * the setters themselves, each called only where its values differ from the net's: allocations, the synchronise and the graph drop happen
+ * exactly where a setter's would, and a restore into a net that already has these settings drops no graph.  It allocates, once, the buffer
+ * of a carried section or scalar copy the recipe leaves switched off (a velocity under Adam, an average with decay 0: saved and restored like
+ * the rest), sets accum_pos, and enqueues ONE launch, k_state_unpack, which writes EVERY element of each carried section's padded buffer --
+ * the logical value, or +0.0f on padding, whatever the buffer held -- and the scalar copies that are real, followed by the refresh of the
+ * tap-flipped weight copy.  Sections and scalar copies the snapshot does not carry, and without RCN_HIPX_STATE_HAS_RECIPE the recipe and
+ * accum_pos, are left alone.  body_dev is read by that launch: it must stay valid until the net's stream has got there.
+ * rcn_hipx_set_accumulated: the setter beside rcn_hipx_get_accumulated -- acc from the logical layout (padding zero) and the position in
+ * the cycle, 0 .. k - 1; synchronises.  -6 while k == 1; -1 for a NULL pointer or a position out of range.
+ * Not carried: the kernel-selection options (rcn_hipx_set_option: seeded from the environment; a caller who changed one sets it again
+ * before resuming), rcn_hipx_set_overlap, the caller's norm-log ring (rcn_hipx_set_grad_norm_log; its counter IS carried, in the clip
+ * state) and anything of a data-parallel group. */
+enum { RCN_HIPX_STATE_PARAMS = 1, RCN_HIPX_STATE_VELOCITY = 2, RCN_HIPX_STATE_ADAM_M = 4, RCN_HIPX_STATE_ADAM_V = 8, RCN_HIPX_STATE_EMA = 16,
+       RCN_HIPX_STATE_ACCUM = 32 };                                             /* section s is bit s */
+enum { RCN_HIPX_STATE_HAS_ADAM_TICK = 1, RCN_HIPX_STATE_HAS_DROPOUT_TICK = 2, RCN_HIPX_STATE_HAS_CLIP_STATE = 4, RCN_HIPX_STATE_HAS_RECIPE = 8 };
+#define RCN_HIPX_STATE_MAGIC 0x54535852u                                        /* "RXST", little endian */
+#define RCN_HIPX_STATE_VERSION 1u
+#define RCN_HIPX_STATE_MAX_LAYERS 32
+#define RCN_HIPX_STATE_SECTIONS 6
+typedef struct rcn_hipx_state_desc {
+    uint32_t magic, version;
+    int32_t  in_h, in_w, in_c, n_layers;
+    rcn_hipx_layer layers[RCN_HIPX_STATE_MAX_LAYERS];
+    int32_t  classes, precision, tiling, sections;
+    int32_t  flags, accum_pos;
+    int64_t  n_log;
+    int64_t  layer_off[RCN_HIPX_STATE_MAX_LAYERS];
+    int64_t  section_off[RCN_HIPX_STATE_SECTIONS];
+    int64_t  body_bytes;
+    int32_t  optim, sgd_nesterov;
+    float    sgd_momentum, sgd_weight_decay;
+    float    adam_beta1, adam_beta2, adam_eps, adam_weight_decay;
+    int32_t  adam_decoupled;
+    float    loss_eps, ema_decay, clip_max_norm;
+    int32_t  accum_k;
+    float    dropout_p;
+    uint64_t dropout_seed;
+} rcn_hipx_state_desc;
+int  rcn_hipx_state_desc_size(void);
+int  rcn_hipx_state_layout(int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, int n_layers, int sections, rcn_hipx_state_desc* desc);
+int  rcn_hipx_snapshot_dev(rcn_hipx_net* net, int sections, void* body_dev, int64_t cap_bytes, rcn_hipx_state_desc* desc_out);
+int  rcn_hipx_restore_dev(rcn_hipx_net* net, const rcn_hipx_state_desc* desc, const void* body_dev, int64_t body_bytes);
+int  rcn_hipx_set_accumulated(rcn_hipx_net* net, const float* flat, int pending);
 /* The same gradients in BUCKETS, so that a data-parallel step can all-reduce one bucket of layers while the backward pass of the layers
  * below it still runs (6.7 MB of gradient for BASELINE configs[3]).  The layers with parameters, in the order the
  * backward pass finishes them (last to first), are cut into buckets of at least min_bucket_bytes of gradient; the padded flat layout

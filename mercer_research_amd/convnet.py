@@ -4,6 +4,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import struct
+import zlib
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
@@ -41,6 +43,59 @@ class Augment:
 class MixStep(C.Structure):
     """rcn_hipx_mix_step: one training step's mixing record (24 bytes)"""
     _fields_ = [("blend", C.c_float), ("weight", C.c_float), ("y0", C.c_int32), ("y1", C.c_int32), ("x0", C.c_int32), ("x1", C.c_int32)]
+
+
+STATE_MAX_LAYERS, STATE_SECTIONS = 32, 6                 # RCN_HIPX_STATE_MAX_LAYERS, RCN_HIPX_STATE_SECTIONS
+STATE_MAGIC, STATE_VERSION = 0x54535852, 1               # RCN_HIPX_STATE_MAGIC, RCN_HIPX_STATE_VERSION
+SECTIONS = {"params": 1, "velocity": 2, "adam_m": 4, "adam_v": 8, "ema": 16, "accum": 32}      # RCN_HIPX_STATE_*: section s is bit s
+STATE_HAS = {"adam_tick": 1, "dropout_tick": 2, "clip_state": 4, "recipe": 8}                 # RCN_HIPX_STATE_HAS_*: the descriptor's flags
+STATE_SCALARS_BYTES = 256                                # the scalars block in front of a body: Adam tick at 0, dropout ordinal at 32, clip state at 40
+
+
+class StateDesc(C.Structure):
+    """rcn_hipx_state_desc: what describes a body and everything a snapshot carries outside it (include/rcn_hipx.h)"""
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_uint32),
+                ("in_h", C.c_int32), ("in_w", C.c_int32), ("in_c", C.c_int32), ("n_layers", C.c_int32),
+                ("layers", XLayer * STATE_MAX_LAYERS),
+                ("classes", C.c_int32), ("precision", C.c_int32), ("tiling", C.c_int32), ("sections", C.c_int32),
+                ("flags", C.c_int32), ("accum_pos", C.c_int32),
+                ("n_log", C.c_int64),
+                ("layer_off", C.c_int64 * STATE_MAX_LAYERS),
+                ("section_off", C.c_int64 * STATE_SECTIONS),
+                ("body_bytes", C.c_int64),
+                ("optim", C.c_int32), ("sgd_nesterov", C.c_int32),
+                ("sgd_momentum", C.c_float), ("sgd_weight_decay", C.c_float),
+                ("adam_beta1", C.c_float), ("adam_beta2", C.c_float), ("adam_eps", C.c_float), ("adam_weight_decay", C.c_float),
+                ("adam_decoupled", C.c_int32),
+                ("loss_eps", C.c_float), ("ema_decay", C.c_float), ("clip_max_norm", C.c_float),
+                ("accum_k", C.c_int32),
+                ("dropout_p", C.c_float),
+                ("dropout_seed", C.c_uint64)]
+
+    def shape_and_layers(self):
+        """(in_shape, layers) as ConvNet takes them"""
+        names = {v: k for k, v in KIND.items()}
+        layers = [(names[self.layers[i].kind],) if self.layers[i].kind == KIND["pool"] else (names[self.layers[i].kind], int(self.layers[i].out))
+                  for i in range(self.n_layers)]
+        return (int(self.in_h), int(self.in_w), int(self.in_c)), layers
+
+    def section(self, body: np.ndarray, name: str) -> np.ndarray:
+        """section `name` (a key of SECTIONS) of a body's bytes as n_log float32 values, in the logical layout of get_params"""
+        s = SECTIONS[name].bit_length() - 1
+        if not self.sections >> s & 1:
+            raise KeyError(f"the snapshot carries no {name!r} section")
+        return np.frombuffer(body, dtype=np.float32, count=int(self.n_log), offset=int(self.section_off[s]))
+
+    def scalars(self, body: np.ndarray) -> dict:
+        """the scalars block of a body's bytes: {"adam_step", "dropout_state", "clip_count", "grad_norm", "clip_coef"}, None where the
+        snapshot carries no such copy"""
+        b = bytes(body[:STATE_SCALARS_BYTES])
+        step, = struct.unpack_from("<q", b, 0)
+        drop, = struct.unpack_from("<q", b, 32)
+        count, norm, coef = struct.unpack_from("<Qff", b, 40)
+        tick, dt, clip = (bool(self.flags & STATE_HAS[k]) for k in ("adam_tick", "dropout_tick", "clip_state"))
+        return {"adam_step": step if tick else None, "dropout_state": drop if dt else None, "clip_count": count if clip else None,
+                "grad_norm": norm if clip else None, "clip_coef": coef if clip else None}
 
 
 # the same record as a NumPy structured dtype: an array of it, moved to the device as bytes, is train_epoch's `mix`
@@ -158,6 +213,11 @@ SIGNATURES = {
     "rcn_hipx_set_dropout_state": (_i, [_vp, C.c_int64]),
     "rcn_hipx_dropout_draw": (_i, [C.c_float, C.c_uint64, C.c_uint64, _i, C.c_uint64, C.POINTER(C.c_int)]),
     "rcn_hipx_dropout_apply_dev": (_i, [_vp, _i, C.c_int64, _vp, _i]),
+    "rcn_hipx_state_desc_size": (_i, []),
+    "rcn_hipx_state_layout": (_i, [_i, _i, _i, C.POINTER(XLayer), _i, _i, C.POINTER(StateDesc)]),
+    "rcn_hipx_snapshot_dev": (_i, [_vp, _i, _vp, C.c_int64, C.POINTER(StateDesc)]),
+    "rcn_hipx_restore_dev": (_i, [_vp, C.POINTER(StateDesc), _vp, C.c_int64]),
+    "rcn_hipx_set_accumulated": (_i, [_vp, C.POINTER(C.c_float), _i]),
 }
 _libx = None
 
@@ -231,6 +291,94 @@ def plan_eval(in_shape: Tuple[int, int, int], layers: Sequence[tuple], batch: in
     evaluation kernel, one line per launch.  Needs no GPU."""
     return _plan_text("rcn_hipx_plan_eval", load().rcn_hipx_plan_eval, in_shape[0], in_shape[1], in_shape[2], _layer_array(layers), len(layers), batch,
                       PRECISIONS[precision], TILINGS[tiling])
+
+
+def state_layout(in_shape: Tuple[int, int, int], layers: Sequence[tuple], sections: Sequence[str] = ("params",)) -> StateDesc:
+    """The descriptor of a body with these sections (keys of SECTIONS) for a net of this description (rcn_hipx_state_layout): shape, layer
+    offsets, section offsets and body_bytes; the recipe at its defaults.  Needs no GPU."""
+    d = StateDesc()
+    mask = 0
+    for name in sections:
+        mask |= SECTIONS[name]
+    st = load().rcn_hipx_state_layout(in_shape[0], in_shape[1], in_shape[2], _layer_array(layers), len(layers), mask, C.byref(d))
+    if st != 0:
+        raise ConvNetError(f"rcn_hipx_state_layout: {st}")
+    return d
+
+
+# ---- the state file: [8: magic][u32: descriptor bytes][u64: body bytes][u64: extra bytes][descriptor][body][extra][u32: CRC-32 of all before]
+STATE_FILE_MAGIC = b"RCNXSTA1"
+_STATE_HEAD = struct.Struct("<8sIQQ")
+
+
+def write_state_file(desc: StateDesc, body, extra: Optional[bytes] = None) -> bytes:
+    """One state file as bytes: the descriptor, the body (desc.body_bytes bytes: a bytes-like object or a uint8 array) and the caller's
+    `extra` blob (its loop state: epoch, next batch, permutation seed), closed by a CRC-32 (zlib) of everything before it.  Needs no GPU."""
+    body = bytes(memoryview(np.ascontiguousarray(body)).cast("B")) if isinstance(body, np.ndarray) else bytes(body)
+    extra = b"" if extra is None else bytes(extra)
+    if len(body) != int(desc.body_bytes):
+        raise ConvNetError(f"write_state_file: the descriptor describes a body of {int(desc.body_bytes)} bytes, not {len(body)}")
+    out = _STATE_HEAD.pack(STATE_FILE_MAGIC, C.sizeof(StateDesc), len(body), len(extra)) + bytes(desc) + body + extra
+    return out + struct.pack("<I", zlib.crc32(out) & 0xffffffff)
+
+
+def read_state_file(data: bytes) -> Tuple[StateDesc, np.ndarray, Optional[bytes]]:
+    """(descriptor, body as a uint8 array, extra or None) of write_state_file's bytes.  A short file, a wrong magic, sizes that do not add up
+    or a wrong CRC raise ConvNetError: nothing of such a file reaches the library.  Needs no GPU."""
+    data = bytes(data)
+    if len(data) < _STATE_HEAD.size + 4:
+        raise ConvNetError("state file: truncated (shorter than its header)")
+    magic, dsize, nbody, nextra = _STATE_HEAD.unpack_from(data, 0)
+    if magic != STATE_FILE_MAGIC:
+        raise ConvNetError("state file: wrong magic (not a Track X state file of this version)")
+    if dsize != C.sizeof(StateDesc):
+        raise ConvNetError(f"state file: a descriptor of {dsize} bytes; this library's has {C.sizeof(StateDesc)}")
+    if len(data) != _STATE_HEAD.size + dsize + nbody + nextra + 4:
+        raise ConvNetError("state file: truncated, or its sizes do not add up")
+    crc, = struct.unpack_from("<I", data, len(data) - 4)
+    if crc != zlib.crc32(data[:-4]) & 0xffffffff:
+        raise ConvNetError("state file: CRC mismatch (the file is damaged)")
+    at = _STATE_HEAD.size
+    desc = StateDesc.from_buffer_copy(data, at)
+    at += dsize
+    if nbody != int(desc.body_bytes):
+        raise ConvNetError("state file: the body's size is not the descriptor's")
+    body = np.frombuffer(data, dtype=np.uint8, count=nbody, offset=at).copy()
+    at += nbody
+    return desc, body, (data[at:at + nextra] if nextra else None)
+
+
+class Snapshot:
+    """The state of a ConvNet at one point of its stream (ConvNet.snapshot): the device body, its descriptor and an event recorded on the
+    net's stream behind the pack launch.  The body is valid once that event has happened; to_bytes and save wait for it alone."""
+
+    def __init__(self, net: "ConvNet", desc: StateDesc, body, event):
+        self.net, self.desc, self.body, self.event = net, desc, body, event
+        self._host = None
+
+    def body_bytes(self) -> np.ndarray:
+        """The body as a uint8 host array: waits for the snapshot's event only -- not for work enqueued on the net's stream later -- and
+        copies on a side stream of its own."""
+        if self._host is None:
+            t = self.net.torch
+            side = self.net._state_side_stream()
+            side.wait_event(self.event)
+            with t.cuda.stream(side):
+                host = t.empty(self.body.numel(), dtype=t.uint8, pin_memory=True)
+                host.copy_(self.body, non_blocking=True)
+            self.body.record_stream(side)
+            side.synchronize()
+            self._host = host.numpy().copy()
+        return self._host
+
+    def to_bytes(self, extra: Optional[bytes] = None) -> bytes:
+        return write_state_file(self.desc, self.body_bytes(), extra)
+
+    def save(self, path, extra: Optional[bytes] = None):
+        data = self.to_bytes(extra)
+        with open(path, "wb") as f:
+            f.write(data)
+        return len(data)
 
 
 X_KIND = {"float32": 0, "uint8": 1}      # RCN_HIPX_X_F32 / RCN_HIPX_X_U8, by the set's torch dtype
@@ -716,6 +864,88 @@ class ConvNet:
     def get_accumulated(self) -> np.ndarray:
         """The accumulator in the logical layout of get_params; synchronises.  ConvNetError, status -6, while accumulation was never on."""
         return self._get_flat(self.lib.rcn_hipx_get_accumulated)
+
+    def set_accumulated(self, flat: np.ndarray, pending: int):
+        """The accumulator from the logical layout of get_params and the position in the open cycle, 0 .. k - 1
+        (rcn_hipx_set_accumulated); synchronises.  ConvNetError, status -6, while the net does not accumulate."""
+        f = np.ascontiguousarray(flat, dtype=np.float32)
+        assert f.size == self.n_logical
+        self._ck(self.lib.rcn_hipx_set_accumulated(self.net, _fptr(f), int(pending)))
+
+    # ---- save and resume (include/rcn_hipx.h: rcn_hipx_snapshot_dev / rcn_hipx_restore_dev) ----
+    def _state_side_stream(self):
+        if getattr(self, "_state_side", None) is None:
+            self._state_side = self.torch.cuda.Stream(device=self.device)
+        return self._state_side
+
+    def snapshot(self, sections="all", body=None) -> Snapshot:
+        """The net's state at this point of its stream, packed into one device buffer by ONE launch (rcn_hipx_snapshot_dev): nothing blocks,
+        nothing of the net is written, no graph is captured or dropped, and steps enqueued afterwards do not show in it.  sections: "all"
+        (every section whose buffer exists, the scalars block and the recipe), "model" (the parameters alone: a restore leaves the
+        target's recipe as it is), or a sequence of SECTIONS keys.  body: a contiguous uint8 tensor on the net's device to pack into
+        (an earlier snapshot's, which it then overwrites) instead of a new one."""
+        t = self.torch
+        if sections == "all":
+            mask = 0
+        elif sections == "model":
+            mask = SECTIONS["params"]
+        else:
+            mask = SECTIONS["params"]
+            for name in sections:
+                mask |= SECTIONS[name]
+        if body is not None and (not t.is_tensor(body) or body.dtype != t.uint8 or body.device != self.device or not body.is_contiguous()):
+            raise ValueError("snapshot: body is a contiguous uint8 tensor on the net's device")
+        desc = StateDesc()
+        with t.cuda.stream(self.stream):
+            if body is None:
+                room = state_layout(self.in_shape, self.layers, tuple(SECTIONS)).body_bytes
+                body = t.empty(int(room), dtype=t.uint8, device=self.device)              # (room for every section; trimmed to the snapshot's own below)
+            self._ck(self.lib.rcn_hipx_snapshot_dev(self.net, mask, _ptr(body), body.numel(), C.byref(desc)))
+            event = t.cuda.Event()
+            event.record(self.stream)
+        if sections == "model":
+            desc.flags = 0
+        return Snapshot(self, desc, body[:int(desc.body_bytes)], event)
+
+    def save(self, path, extra: Optional[bytes] = None, sections="all") -> int:
+        """snapshot(sections).save(path, extra): one file holding the descriptor, the body, the caller's `extra` blob and a CRC-32.
+        Returns the file's size."""
+        return self.snapshot(sections).save(path, extra)
+
+    def _restore(self, desc: StateDesc, body):
+        self._ck(self.lib.rcn_hipx_restore_dev(self.net, C.byref(desc), _ptr(body), int(body.numel())))
+        self.synchronize()                                  # (the unpack launch has read the body: the caller may let go of it)
+
+    def load_state(self, source) -> Optional[bytes]:
+        """Restores a Snapshot (of any net of this description on this device) or a state file (a path) into THIS net
+        (rcn_hipx_restore_dev): precision, tiling, the recipe and every carried section; what the snapshot does not carry is left alone.
+        Everything is checked before anything changes: a refusal (ConvNetError) leaves the net bit for bit what it was.  Synchronises.
+        Returns the file's `extra` blob (None for a Snapshot)."""
+        if isinstance(source, Snapshot):
+            if source.body.device != self.device:
+                raise ValueError("load_state: the snapshot's body lives on another device (save it and load the file)")
+            self.stream.wait_event(source.event)
+            self._restore(source.desc, source.body)
+            return None
+        with open(source, "rb") as f:
+            desc, body, extra = read_state_file(f.read())
+        self._restore(desc, self.to_device(body))
+        return extra
+
+    @classmethod
+    def load(cls, path, max_batch: int, device: int = 0):
+        """(net, extra): a new net built from the file's descriptor -- input shape and layers -- and restored from it; `extra` is the blob
+        save was given (None without one)."""
+        with open(path, "rb") as f:
+            desc, body, extra = read_state_file(f.read())
+        in_shape, layers = desc.shape_and_layers()
+        net = cls(in_shape, layers, int(max_batch), device)
+        try:
+            net._restore(desc, net.to_device(body))
+        except Exception:
+            net.close()
+            raise
+        return net, extra
 
     def plan_micro_of_this_net(self, batch: int, kind: str) -> str:
         """The launches of one kind of micro-step of THIS accumulating net (rcn_hipx_plan_micro_net): kind "first", "middle" or "last".

@@ -27,6 +27,7 @@
 #include "convnet_update.hpp"
 #include "convnet_accum.hpp"
 #include "convnet_dropout.hpp"
+#include "convnet_state.hpp"
 
 using namespace rcnx;
 
@@ -1593,3 +1594,4 @@ int rcn_hipx_plan_eval_net(const rcn_hipx_net* n, int batch, char* out, int cap)
 
 #include "rcn_hipx_api_update.ipp"
 #include "rcn_hipx_api_dropout.ipp"
+#include "rcn_hipx_api_state.ipp"
