@@ -23,6 +23,37 @@ ODD_WIDTH = ((5, 7, 1), (("conv", 32), ("dense", 6)), 4)                        
 CIFAR = ((32, 32, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("conv", 128), ("pool",), ("dense_relu", 256), ("dense", 10)), 512)
 MNIST = ((28, 28, 1), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 128), ("dense", 10)), 4096)
 
+# the nets of tests/test_gpu_convnet.py ("auto" tiling: implicit GEMM, split-K, k_pool_fwd)
+CONVNET_NETS = [
+    FUSED_HEAD,
+    PLAIN_HEAD,
+    ((4, 8, 3), (("conv", 64), ("pool",), ("dense_relu", 64), ("dense_relu", 32), ("dense", 3)), 130),
+    ((8, 8, 32), (("conv", 32), ("pool",), ("dense", 10)), 4),
+    # the layer stack of the synthetic 224x224x3 config (BASELINE configs[3]) at 16x16: 8 conv layers, pool after each pair
+    ((16, 16, 3), (("conv", 32), ("conv", 32), ("pool",), ("conv", 64), ("conv", 64), ("pool",), ("conv", 128), ("conv", 128), ("pool",),
+                   ("conv", 256), ("conv", 256), ("pool",), ("dense", 10)), 3),
+]
+# ... and of its bf16-operand test: the third one twice as wide
+CONVNET_BF16_NETS = [CONVNET_NETS[0], CONVNET_NETS[1], ((4, 8, 3), (("conv", 128), ("pool",), ("dense_relu", 128), ("dense_relu", 32), ("dense", 3)), 130),
+                     CONVNET_NETS[4]]
+# the nets of tests/test_gpu_convnet_halo.py (tiling "lds"), chosen for the LDS-tiled kernels' corner cases
+HALO_NETS = [
+    # 8 x 16 blocks, maps 12 x 20 and 6 x 10 (partly empty blocks), first layer RGB + fused pool, 32 -> 64 + fused pool
+    ((12, 20, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense", 10)), 3),
+    # 8 x 8 blocks of two images, odd batch; 1-channel first layer WITHOUT a pool behind it, conv-conv-pool (gate epilogue + pooled input
+    # gradient), a 4 x 4 map
+    ((8, 8, 1), (("conv", 32), ("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense", 7)), 5),
+    # 32-channel input: no first-layer kernel; 96 output channels = three 32-wide column blocks; two input-channel blocks behind it
+    ((16, 16, 32), (("conv", 64), ("conv", 96), ("pool",), ("conv", 32), ("dense_relu", 32), ("dense", 10)), 2),
+    # first layer with two column blocks on an 8-wide map, then 64 -> 32
+    ((24, 8, 3), (("conv", 64), ("pool",), ("conv", 32), ("pool",), ("dense", 4)), 4),
+    # a batch of 64 (two workgroups of the fused head, one more hidden dense layer in front of it)
+    ((8, 8, 3), (("conv", 32), ("pool",), ("dense_relu", 64), ("dense_relu", 32), ("dense", 10)), 64),
+    # the MNIST-shape first layer: ONE channel with the pool right behind it (weight gradient on the 16-row MFMA from a pooled-resolution
+    # gradient), 64 filters = two column blocks, a 28 x 12 map (blocks that are not full in either direction), several blocks per chunk
+    ((28, 12, 1), (("conv", 64), ("pool",), ("conv", 32), ("pool",), ("dense", 10)), 6),
+]
+
 # ---- shared scalars ----------------------------------------------------------------------------------------------------------------------
 SCALE, SHIFT = 1.0 / 255.0, -0.1307                     # neither is a power of two: a padded uint8 pixel is fl(fl(0*scale)+shift) != 0
 KW = dict(x_scale=SCALE, x_shift=SHIFT)
@@ -180,6 +211,39 @@ def close(a, b, rtol=2e-4):
     scale = max(1e-3, float(np.abs(b).max()))
     print("max |d| =", float(np.abs(a - b).max()), "scale =", scale, "rtol =", rtol)
     assert np.abs(a - b).max() <= rtol * scale + 1e-6, (float(np.abs(a - b).max()), scale)
+
+
+def tensor_slices(in_shape, layers):
+    """every layer's (weights, biases) as slices of the logical flat layout"""
+    slices, o = [], 0
+    for (k, c), nb in co.param_shapes(in_shape, layers):
+        slices.append((slice(o, o + k * c), slice(o + k * c, o + k * c + nb)))
+        o += k * c + nb
+    return slices
+
+
+def close_per_tensor(got_logical, ref, in_shape, layers, rtol=2e-4, on_global_scale=()):
+    """`close` on every layer's weights and on every layer's biases, each at ITS OWN scale: a tensor's scale is at most the whole
+    vector's, so this asks no less than close(got_logical, ref, rtol).  Prints and returns the worst |d| / (rtol * scale + 1e-6).
+    on_global_scale: (layer, "weights" | "biases") pairs held at the whole vector's scale instead -- what close(got_logical, ref, rtol)
+    asks of them; the caller says why."""
+    got, ref = np.asarray(got_logical, dtype=np.float64).ravel(), np.asarray(ref, dtype=np.float64).ravel()
+    slices = tensor_slices(in_shape, layers)
+    assert got.size == ref.size == slices[-1][1].stop, (got.size, ref.size, slices[-1][1].stop)
+    whole = max(1e-3, float(np.abs(ref).max()))
+    worst = 0.0
+    for li, pair in enumerate(slices):
+        for name, s in zip(("weights", "biases"), pair):
+            if (li, name) in on_global_scale:
+                d = float(np.abs(got[s] - ref[s]).max())
+                print(f"layer {li} {name}: max |d| = {d} at the whole vector's scale = {whole} (its own: {float(np.abs(ref[s]).max())}) rtol = {rtol}")
+                assert d <= rtol * whole + 1e-6, (li, name, d, whole)
+                continue
+            worst = max(worst, float(np.abs(got[s] - ref[s]).max()) / (rtol * max(1e-3, float(np.abs(ref[s]).max())) + 1e-6))
+            print(f"layer {li} {name}: ", end="")
+            close(got[s], ref[s], rtol)
+    print("worst per-tensor |d| / allowance =", worst)
+    return worst
 
 
 def bits(a):

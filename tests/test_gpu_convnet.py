@@ -1,23 +1,16 @@
 """GPU tests of the Track-X trainable convolution network (include/rcn_hipx.h) against its f64 oracle.
-No reference counterpart exists ("parity unpinned"); tolerance: fp32 MFMA vs f64, |d| <= 2e-4 * scale + 1e-6."""
+No reference counterpart exists ("parity unpinned"); tolerance: fp32 MFMA vs f64, |d| <= 2e-4 * scale + 1e-6.  Gradients and the
+parameters after one step are held tensor by tensor: each layer's weights and each layer's biases at their own scale."""
 import numpy as np
 import pytest
-from _convnet_util import close, make_net
+from _convnet_util import CONVNET_BF16_NETS, CONVNET_NETS, close, close_per_tensor, make_net
 
 from oracle import convnet_oracle as co
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("in_shape,layers,B", [
-    ((8, 8, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 32), ("dense", 10)), 5),
-    ((6, 6, 1), (("conv", 32), ("conv", 32), ("pool",), ("dense", 7)), 3),
-    ((4, 8, 3), (("conv", 64), ("pool",), ("dense_relu", 64), ("dense_relu", 32), ("dense", 3)), 130),
-    ((8, 8, 32), (("conv", 32), ("pool",), ("dense", 10)), 4),
-    # the layer stack of the synthetic 224x224x3 config (BASELINE configs[3]) at 16x16: 8 conv layers, pool after each pair
-    ((16, 16, 3), (("conv", 32), ("conv", 32), ("pool",), ("conv", 64), ("conv", 64), ("pool",), ("conv", 128), ("conv", 128), ("pool",),
-                   ("conv", 256), ("conv", 256), ("pool",), ("dense", 10)), 3),
-])
+@pytest.mark.parametrize("in_shape,layers,B", CONVNET_NETS)
 def test_forward_gradients_and_step_match_oracle(in_shape, layers, B):
     rng = np.random.default_rng(B)
     net = make_net((in_shape, layers, B), precision=None)
@@ -44,14 +37,14 @@ def test_forward_gradients_and_step_match_oracle(in_shape, layers, B):
     net.synchronize()
     close(logits.cpu().numpy(), logits_ref)
     assert abs(loss.item() - loss_ref) <= 2e-4 * max(1.0, loss_ref)
-    close(net.unpad(grad), co.flatten(gws, gbs))
+    close_per_tensor(net.unpad(grad), co.flatten(gws, gbs), in_shape, layers)
     # one SGD step (eager first call, then the cached graph for the second)
     lr = 0.05
     with torch.cuda.stream(net.stream):
         net.train_step(xd, yd, lr, loss)
     net.synchronize()
     nw, nb, _ = co.sgd_step(x64, y, w32, b32, layers, lr)
-    close(net.get_params(), co.flatten(nw, nb))
+    close_per_tensor(net.get_params(), co.flatten(nw, nb), in_shape, layers)
     with torch.cuda.stream(net.stream):
         net.train_step(xd, yd, lr, loss)            # graph replay
     net.synchronize()
@@ -64,16 +57,10 @@ def test_forward_gradients_and_step_match_oracle(in_shape, layers, B):
         g = net.gradients(xd, yd)
         net.apply(g, lr)
     net.synchronize()
-    close(net.get_params(), co.flatten(nw, nb))
+    close_per_tensor(net.get_params(), co.flatten(nw, nb), in_shape, layers)
 
 
-@pytest.mark.parametrize("in_shape,layers,B", [
-    ((8, 8, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 32), ("dense", 10)), 5),
-    ((6, 6, 1), (("conv", 32), ("conv", 32), ("pool",), ("dense", 7)), 3),
-    ((4, 8, 3), (("conv", 128), ("pool",), ("dense_relu", 128), ("dense_relu", 32), ("dense", 3)), 130),
-    ((16, 16, 3), (("conv", 32), ("conv", 32), ("pool",), ("conv", 64), ("conv", 64), ("pool",), ("conv", 128), ("conv", 128), ("pool",),
-                   ("conv", 256), ("conv", 256), ("pool",), ("dense", 10)), 3),
-])
+@pytest.mark.parametrize("in_shape,layers,B", CONVNET_BF16_NETS)
 def test_bf16_mfma_path_matches_bf16_operand_oracle(in_shape, layers, B):
     """rcn_hipx_set_precision(BF16): GEMM operands of forward, dgrad and wgrad rounded to bf16 (RNE), fp32 accumulation and
     storage, fp32 bias gradients and update; the first layer (9 * Cin <= 32) and the fused classifier head stay fp32 (the oracle's
@@ -106,7 +93,7 @@ def test_bf16_mfma_path_matches_bf16_operand_oracle(in_shape, layers, B):
     close(logits.cpu().numpy(), logits_ref, rtol=5e-3)
     close(logits.cpu().numpy(), logits_f64, rtol=3e-2)
     assert abs(loss.item() - loss_ref) <= 5e-3 * max(1.0, loss_ref)
-    close(net.unpad(grad), co.flatten(gws, gbs), rtol=5e-3)
+    close_per_tensor(net.unpad(grad), co.flatten(gws, gbs), in_shape, layers, rtol=5e-3)
     # it really is a different arithmetic: not bit-equal to the fp32 path, which still holds its own tolerance
     net.set_precision("fp32")
     with torch.cuda.stream(net.stream):

@@ -9,28 +9,23 @@ proves on the CPU that each case reaches the forms it names):
      order of the sums changes with the chunk size: against the oracle, and a second evaluation bit-identical.
   C  forms only an option selects, each against the oracle in its mode; where the option changes the schedule alone, bit for bit too.
 Tolerances are the project's: fp32 vs f64 2e-4 of scale + 1e-6 (4e-4 after a second step; tests/test_gpu_convnet.py); bf16 operands vs the
-oracle with the same operand rounding 5e-3 (2e-2 after two steps); bf16 storage vs the oracle with the storage rounding mirrored 5e-3 of
-each layer's tensors (2e-2 after two steps; tests/test_gpu_round4.py).  A parameter vector after ONE step is held at the gradient's
-tolerance: it is the parameters (exact) minus LR times a gradient within that tolerance; so is that step's displacement (check_oracle)."""
+oracle with the same operand rounding 5e-3 (2e-2 after two steps); bf16 storage vs the oracle with the storage rounding mirrored 5e-3
+(2e-2 after two steps; tests/test_gpu_round4.py).  In every mode the gradient and the parameters after one step are held tensor by
+tensor, each layer's weights and each layer's biases at their own scale (close_per_tensor).  A parameter vector after ONE step is held
+at the gradient's tolerance: it is the parameters (exact) minus LR times a gradient within that tolerance; so is that step's displacement
+(check_oracle)."""
 import functools
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
-from _convnet_util import close, make_net, oracle_params, same_bits
+from _convnet_util import make_net, oracle_params, same_bits
 from _forms_cases import LOOPS, OPTIONS, SLOTS, WGRADS, names
+from _oracle_steps import KEYS, LR, MODES, check_oracle, run
 
 from oracle import convnet_oracle as co
 
 pytestmark = pytest.mark.gpu
-
-# precision -> (the oracle's mode, tolerance, tolerance after two steps)
-MODES = {"fp32": ({}, 2e-4, 4e-4), "bf16": (dict(operand="bf16"), 5e-3, 2e-2), "bf16_stored": (dict(operand="bf16", stored=True), 5e-3, 2e-2)}
-# The step rate: small enough that the first step lowers the oracle's loss on every net here.  These nets put the logits layer straight
-# on thousands of He-scaled features; at 0.05 the first step overshoots into a saturated softmax (oracle losses of 40 to 190, and inf on
-# one net), where the second step compares nothing but the overshoot.
-LR = 0.0005
-KEYS = ("logits", "loss", "grad", "params1", "loss1", "params2", "loss2")
 
 
 @functools.lru_cache(maxsize=None)
@@ -47,13 +42,8 @@ def reference(spec, precision):
     loss, logits, gws, gbs = co.loss_and_grads(x64, y, w32, b32, layers, **kw)
     w1, b1, _ = co.sgd_step(x64, y, w32, b32, layers, LR, **kw)
     w2, b2, loss1 = co.sgd_step(x64, y, w1, b1, layers, LR, **kw)
-    # every layer's (weights, biases) in the logical flat layout
-    slices, o = [], 0
-    for (k, c), nb in co.param_shapes(in_shape, layers):
-        slices.append((slice(o, o + k * c), slice(o + k * c, o + k * c + nb)))
-        o += k * c + nb
     ref = SimpleNamespace(flat=flat.astype(np.float32), x=x, y=y, logits=logits, loss=loss, grad=co.flatten(gws, gbs), params1=co.flatten(w1, b1),
-                          params2=co.flatten(w2, b2), loss1=loss1, slices=slices)
+                          params2=co.flatten(w2, b2), loss1=loss1, spec=spec)
     for a in vars(ref).values():
         if isinstance(a, np.ndarray):
             a.setflags(write=False)
@@ -73,53 +63,6 @@ def setup(case):
     xd, yd = net.to_device(ref.x.copy()), net.to_device(ref.y.copy())      # (the reference's arrays are read-only)
     net.synchronize()
     return net, ref, xd, yd
-
-
-def run(net, ref, xd, yd):
-    """from the reference's parameters: logits, loss and the whole padded gradient, then two training steps (the first eager, the second a
-    replayed graph: set_option and a new net both start without cached graphs) with the parameters and the loss after each"""
-    import torch
-    net.set_params(ref.flat)
-    with torch.cuda.stream(net.stream):
-        logits = net.forward(xd)
-        loss = torch.zeros(1, dtype=torch.float32, device=net.device)
-        g = net.gradients(xd, yd, loss=loss)
-    net.synchronize()
-    out = {"logits": logits.cpu().numpy(), "loss": loss.cpu().numpy(), "grad": g.cpu().numpy(), "grad_logical": net.unpad(g)}
-    for k in (1, 2):
-        with torch.cuda.stream(net.stream):
-            net.train_step(xd, yd, LR, loss)
-        net.synchronize()
-        out[f"params{k}"], out[f"loss{k}"] = net.get_params(), loss.cpu().numpy()     # loss{k}: the loss BEFORE update k
-    return out
-
-
-def close_loss(tag, got, want, rtol):
-    print(f"{tag}: |d| =", abs(float(got) - want), "of", want, "rtol =", rtol)
-    assert abs(float(got) - want) <= rtol * max(1.0, want), (tag, float(got), want)
-
-
-def check_oracle(out, ref, precision):
-    _, rtol, rtol2 = MODES[precision]
-    close(out["logits"], ref.logits, rtol)
-    close_loss("loss", out["loss"][0], ref.loss, rtol)
-    if precision == "bf16_stored":                    # of each layer's tensors
-        for ws, bs in ref.slices:
-            close(out["grad_logical"][ws], ref.grad[ws], rtol)
-            close(out["grad_logical"][bs], ref.grad[bs], rtol)
-    else:
-        close(out["grad_logical"], ref.grad, rtol)
-    close_loss("loss before the first update", out["loss1"][0], ref.loss, rtol)
-    close(out["params1"], ref.params1, rtol)
-    close(out["params2"], ref.params2, rtol2)
-    # ... and the first step's displacement by the same rule: at this step rate it is a few thousandths of the parameters' scale, less
-    # than the bf16 tolerance of the parameters themselves.  It is -LR times a gradient held at rtol, plus half an ulp of a parameter (6e-8
-    # of scale, inside the rule's 1e-6).  The second step has no such rule below rtol2: measured on the device (eager and replayed agree
-    # bit for bit), the gradient at the parameters after one step sits 1e-3 to 2e-2 of a layer's scale from the oracle's AT THE SAME
-    # parameters in the bf16 modes (fp32: 1e-6) -- one operand that rounds the other way leaves everything behind it 1e-4 apart, where
-    # further operands round the other way a thousand times as often.  rtol2 of the parameters' scale is the project's allowance for it.
-    close(out["params1"] - ref.flat.astype(np.float64), ref.params1 - ref.flat, rtol)
-    close_loss("loss before the second update", out["loss2"][0], ref.loss1, rtol2)
 
 
 def assert_same_bits(tag, got, want):

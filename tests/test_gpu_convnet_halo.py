@@ -6,28 +6,13 @@ pooled-resolution gradients into the input-gradient and weight-gradient kernels,
 No reference counterpart ("parity unpinned"); tolerance as tests/test_gpu_convnet.py: |d| <= 2e-4 * scale + 1e-6."""
 import numpy as np
 import pytest
-from _convnet_util import close, make_net, oracle_params
+from _convnet_util import HALO_NETS, close, close_per_tensor, make_net, oracle_params
 
 from oracle import convnet_oracle as co
 
 pytestmark = pytest.mark.gpu
 
-NETS = [
-    # 8 x 16 blocks, maps 12 x 20 and 6 x 10 (partly empty blocks), first layer RGB + fused pool, 32 -> 64 + fused pool
-    ((12, 20, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense", 10)), 3),
-    # 8 x 8 blocks of two images, odd batch; 1-channel first layer WITHOUT a pool behind it, conv-conv-pool (gate epilogue + pooled input
-    # gradient), a 4 x 4 map
-    ((8, 8, 1), (("conv", 32), ("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense", 7)), 5),
-    # 32-channel input: no first-layer kernel; 96 output channels = three 32-wide column blocks; two input-channel blocks behind it
-    ((16, 16, 32), (("conv", 64), ("conv", 96), ("pool",), ("conv", 32), ("dense_relu", 32), ("dense", 10)), 2),
-    # first layer with two column blocks on an 8-wide map, then 64 -> 32
-    ((24, 8, 3), (("conv", 64), ("pool",), ("conv", 32), ("pool",), ("dense", 4)), 4),
-    # a batch of 64 (two workgroups of the fused head, one more hidden dense layer in front of it)
-    ((8, 8, 3), (("conv", 32), ("pool",), ("dense_relu", 64), ("dense_relu", 32), ("dense", 10)), 64),
-    # the MNIST-shape first layer: ONE channel with the pool right behind it (weight gradient on the 16-row MFMA from a pooled-resolution
-    # gradient), 64 filters = two column blocks, a 28 x 12 map (blocks that are not full in either direction), several blocks per chunk
-    ((28, 12, 1), (("conv", 64), ("pool",), ("conv", 32), ("pool",), ("dense", 10)), 6),
-]
+NETS = HALO_NETS                                        # (tests/_convnet_util.py: the table, with what each net is there for)
 
 
 def _setup(in_shape, layers, B, tiling):
@@ -55,7 +40,7 @@ def test_lds_tiled_kernels_match_oracle(in_shape, layers, B):
     close(logits.cpu().numpy(), logits_ref)
     assert abs(loss.item() - loss_ref) <= 2e-4 * max(1.0, loss_ref)
     g1 = net.unpad(grad)
-    close(g1, co.flatten(gws, gbs))
+    close_per_tensor(g1, co.flatten(gws, gbs), in_shape, layers)      # every layer's weights and biases at their own scale
     # fixed summation orders: a second evaluation is bit-identical
     with torch.cuda.stream(net.stream):
         grad2 = net.gradients(xd, yd)
@@ -67,7 +52,7 @@ def test_lds_tiled_kernels_match_oracle(in_shape, layers, B):
         net.train_step(xd, yd, lr, loss)
     net.synchronize()
     nw, nb, _ = co.sgd_step(x64, y, w32, b32, layers, lr)
-    close(net.get_params(), co.flatten(nw, nb))
+    close_per_tensor(net.get_params(), co.flatten(nw, nb), in_shape, layers)
     with torch.cuda.stream(net.stream):
         net.train_step(xd, yd, lr, loss)
     net.synchronize()

@@ -3,12 +3,13 @@
 No reference counterpart exists (include/rcn_hipx.h); at these sizes the f64 oracle (oracle/convnet_oracle.py) is affordable only on
 a few images, so each config is held by: the oracle on a sub-batch at full resolution, and size-independent properties on the full
 batch -- gradient additivity over a split of the batch, data-parallel halves == the full step, hipGraph replay == eager bit for bit.
-Tolerances as in test_gpu_convnet.py: fp32 MFMA |d| <= 2e-4 * scale + 1e-6; bf16 operands 5e-3 * scale."""
+Tolerances as in test_gpu_convnet.py: fp32 MFMA |d| <= 2e-4 * scale + 1e-6; bf16 operands 5e-3 * scale; the sub-batch gradients
+tensor by tensor, each layer's weights and biases at their own scale (but for the 224 x 224 sub-batch: see there)."""
 import os
 
 import numpy as np
 import pytest
-from _convnet_util import CIFAR, MNIST, close, make_net, oracle_params
+from _convnet_util import CIFAR, MNIST, close, close_per_tensor, make_net, oracle_params
 
 from oracle import convnet_oracle as co
 
@@ -83,7 +84,7 @@ def test_cifar_b512_fp32_workload_size():
     net.synchronize()
     close(logits.cpu().numpy(), logits_ref)
     assert abs(loss.item() - loss_ref) <= 2e-4 * max(1.0, loss_ref)
-    close(net.unpad(grad), co.flatten(gws, gbs))
+    close_per_tensor(net.unpad(grad), co.flatten(gws, gbs), in_shape, layers)
     # the full 512-image batch: logits of the first 4 images do not depend on the batch they ride in
     with torch.cuda.stream(net.stream):
         logits_full = net.forward(net.to_device(x))
@@ -114,7 +115,14 @@ def test_synth224_8conv_workload_size():
     net.synchronize()
     close(logits.cpu().numpy(), logits_ref)
     assert abs(loss.item() - loss_ref) <= 2e-4 * max(1.0, loss_ref)
-    close(net.unpad(grad), co.flatten(gws, gbs))
+    # Tensor by tensor, but for the seventh convolution's two tensors, which stay on the whole vector's scale.  On this batch the oracle's
+    # pre-activation of that layer at output channel 66, pixel 1174 is 3.0e-9, the sum of terms whose absolute values add up to 64.4: no
+    # fp32 sum can place it on the right side of 0, and the device's gate closes where the f64 gate opens.  Measured on the device: that
+    # one element of dZ (6.79e-5) accounts for the whole deviation -- the bias gradient of channel 66 is off by it (1.21 x the per-tensor
+    # allowance at that tensor's scale 0.276), the weight gradient in column 66 alone, by the element times its input patch (residual
+    # 9.6e-7; max |d| 6.75e-4 = 1.32 x the allowance at that tensor's scale 2.55); every other column of the layer sits within 3.5e-6.
+    # A rounding on the other side of a threshold, not the kernel.  The layers below it inherit the element and still hold per tensor.
+    close_per_tensor(net.unpad(grad), co.flatten(gws, gbs), in_shape, layers, on_global_scale=((6, "weights"), (6, "biases")))
     del xd, yd, grad
     x = rng.standard_normal((B,) + in_shape).astype(np.float32)
     y = rng.integers(0, 10, B).astype(np.int32)
@@ -147,7 +155,7 @@ def test_mnist_bf16_b4096_hipgraph_step_workload_size():
     net.synchronize()
     close(logits.cpu().numpy(), logits_ref, rtol=5e-3)
     assert abs(loss.item() - loss_ref) <= 5e-3 * max(1.0, loss_ref)
-    close(net.unpad(grad), co.flatten(gws, gbs), rtol=5e-3)
+    close_per_tensor(net.unpad(grad), co.flatten(gws, gbs), in_shape, layers, rtol=5e-3)
     x = rng.standard_normal((B,) + in_shape).astype(np.float32)
     y = rng.integers(0, 10, B).astype(np.int32)
     l0 = _properties(net, x, y, flat, 0.05, 5e-3)
