@@ -137,6 +137,17 @@ def resident_set_figures(net, args, in_shape, B, lr):
             loss_sum, correct, _ = net.evaluate_async(X, Y, want_pred=False)
         net.synchronize()
         ev = time.perf_counter() - t0
+        metrics = {}
+        if args.eval_metrics:
+            # the same pass once more through evaluate_metrics (k_eval_metrics in the place of k_eval_ce): top-1 / top-5 counts, confusion on
+            topk = (1, 5) if net.classes >= 5 else (1,)
+            net.evaluate_metrics(X, Y, topk=topk)
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                m = net.evaluate_metrics_async(X, Y, topk=topk, confusion=True)
+            net.synchronize()
+            metrics = {"eval_ms": round(ev / reps * 1e3, 4), "eval_metrics_ms": round((time.perf_counter() - t0) / reps * 1e3, 4),
+                       "eval_top5": int(m["topk_correct"][1].item()) if len(topk) > 1 else None}
         ema = {}
         if args.ema > 0:
             net.evaluate(X, Y, weights="ema")
@@ -148,7 +159,7 @@ def resident_set_figures(net, args, in_shape, B, lr):
                    "eval_ema_correct": int(ema_correct.item())}
     return {"dataset": N, "dataset_dtype": str(X.dtype).replace("torch.", ""), "epochs_timed": epochs, "epoch_ms_per_step": round(el / (epochs * nb) * 1e3, 4), **recipe,
             "epoch_images_per_s": round(epochs * nb * B / el, 1), "eval_images_per_s": round(reps * N / ev, 1),
-            "eval_mean_loss": round(float(loss_sum.item()) / N, 4), "eval_correct": int(correct.item()), **ema, "graphs_instantiated": graphs}
+            "eval_mean_loss": round(float(loss_sum.item()) / N, 4), "eval_correct": int(correct.item()), **metrics, **ema, "graphs_instantiated": graphs}
 
 
 def main():
@@ -191,6 +202,9 @@ def main():
                     help="also keep a synthetic set of N images resident (uint8 for mnist / cifar, fp32 for synth224), time train_epoch over whole epochs with a fresh "
                          "device permutation each, then evaluate over the set: the line gains epoch_ms_per_step, epoch_images_per_s, eval_images_per_s, graphs_instantiated "
                          "(single GPU only)")
+    ap.add_argument("--eval-metrics", action="store_true",
+                    help="with --dataset: the evaluation pass once more through evaluate_metrics (top-1 / top-5 counts where the net has 5 classes, confusion matrix): "
+                         "the line gains eval_ms, eval_metrics_ms (both per pass over the set) and eval_top5")
     ap.add_argument("--lr-schedule", choices=["none", "warmup_cosine"], default="none",
                     help="with --dataset: time the epochs once more with a per-step rate (warm-up over 5 %% of an epoch, then cosine to 0) from a device tensor: "
                          "recipe_epoch_ms_per_step beside epoch_ms_per_step; graphs_instantiated, after it, shows that no step captured again")
@@ -227,6 +241,8 @@ def main():
         ap.error("--label-smoothing: 0 <= E < 1")
     if (args.lr_schedule != "none" or args.augment >= 0 or args.trap) and not args.dataset:
         ap.error("--lr-schedule, --augment and --trap time the resident epoch: they need --dataset N")
+    if args.eval_metrics and not args.dataset:
+        ap.error("--eval-metrics times the evaluation of the resident set: it needs --dataset N")
     from mercer_research_amd.launch import spawn_ranks, under_launcher
     if args.gpus > 1 and not under_launcher():
         # `python bench_convnet.py --gpus N`: the parent makes no GPU call; it starts N fresh ranks and relays rank 0's line

@@ -270,6 +270,51 @@ int  rcn_hipx_graphs_instantiated(const rcn_hipx_net* net, int64_t* count);
  * precision, tiling and options (batch <= max_batch). */
 int  rcn_hipx_plan_eval(int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, int n_layers, int batch, int precision, int tiling, char* out, int cap);
 int  rcn_hipx_plan_eval_net(const rcn_hipx_net* net, int batch, char* out, int cap);
+/* rcn_hipx_evaluate_ex_dev with more to tell: top-k counts, the confusion matrix, the per-row loss, the rank of every row's label and the
+ * logits of the whole set.  The same chunks, the same uint8 widening, the same exchange with the average, the same bf16 operand copies and
+ * the same forward launches; per chunk ONE launch of k_eval_metrics stands where k_eval_ce stood, so the call costs no launch more.
+ * Everything is on the device and enqueued on the net's stream; nothing blocks.
+ *     loss_sum, correct, pred   as rcn_hipx_evaluate_ex_dev fills them, BIT FOR BIT: the per-sample loss is computed by the routine k_eval_ce
+ *                               runs and summed in its order (8 samples per workgroup in sample order in fp32; the chunk's last-arriving
+ *                               workgroup adds the partials in the fixed block order in double; chunk after chunk).  With labels, loss_sum
+ *                               and correct must not be NULL; without labels pred or logits must not be.
+ *     rank (nullable)           [n] int32: the number of classes that BEAT the row's label y, 0 .. classes - 1.  Class c beats y when
+ *                               z[c] > z[y], or z[c] == z[y] and c < y: the label's place in a stable descending sort, and the first-maximum
+ *                               rule of the arg-max, so rank == 0 exactly where pred == y (rows free of NaN).  rcn_hipx_label_rank is the
+ *                               same function on the host.  A label outside [0, classes) never indexes the row: its rank is -1.
+ *     topk_correct              [n_topk] int64: topk_correct[j] = number of rows with 0 <= rank < topk[j].  n_topk in 0 ..
+ *                               RCN_HIPX_EVAL_MAX_TOPK; topk strictly increasing, 1 <= k <= classes; required iff n_topk > 0.
+ *     confusion (nullable)      [classes][classes] int64: confusion[y * classes + pred] = number of rows labelled y whose arg-max is pred.
+ *                               Accumulated over all chunks with vector atomic adds: integer cells, so the order of the additions cannot
+ *                               change a result.  A row whose label is outside [0, classes) is in no cell (and in no top-k count).
+ *     loss_each (nullable)      [n] float: the very float the kernel adds into its workgroup's partial, 0 for a label outside [0, classes).
+ *     logits (nullable)         [n][classes] float, compact: the bits rcn_hipx_forward_dev returns for those rows.
+ * loss_sum, correct, topk_correct and confusion are zeroed once per call, before the first chunk.  Without labels only pred and logits can
+ * be filled.  A row that holds NaN is a caller error: its results are unspecified, but nothing faults and no address is formed from it.
+ * Deterministic: two calls on the same data return the same bytes in every output.  State, graphs and the open bucket walk: as
+ * rcn_hipx_evaluate_dev (it captures nothing and changes nothing the next step reads); the per-workgroup partials live in a buffer of the
+ * metrics launch's own, sized by max_batch at the first call and never moved.
+ * -6: what rcn_hipx_evaluate_ex_dev answers -6 to.  -1 (nothing enqueued, nothing changed): out NULL; n_topk outside 0 ..
+ * RCN_HIPX_EVAL_MAX_TOPK; a k outside 1 .. classes; topk not strictly increasing; n_topk > 0 with topk_correct NULL; topk_correct (or
+ * n_topk > 0), confusion, loss_each or rank without labels; what rcn_hipx_evaluate_ex_dev refuses. */
+#define RCN_HIPX_EVAL_MAX_TOPK 8
+typedef struct rcn_hipx_eval_out {
+    double*  loss_sum;  int64_t* correct;  int32_t* pred;      /* as rcn_hipx_evaluate_ex_dev                                            */
+    int32_t  n_topk;    int32_t  topk[RCN_HIPX_EVAL_MAX_TOPK]; /* strictly increasing, 1 <= k <= classes                                */
+    int64_t* topk_correct;                                      /* [n_topk]; required iff n_topk > 0                                     */
+    int64_t* confusion;                                         /* [classes][classes], nullable                                          */
+    float*   loss_each; int32_t* rank;                          /* [n], nullable                                                         */
+    float*   logits;                                            /* [n][classes], nullable                                                */
+} rcn_hipx_eval_out;
+int  rcn_hipx_evaluate_metrics_dev(rcn_hipx_net* net, const void* X_dev, int x_kind, float x_scale, float x_shift, const int32_t* labels_dev, int64_t n,
+                                   int weights, const rcn_hipx_eval_out* out);
+/* pure host, no GPU: *rank = the rank k_eval_metrics gives `label` on the `classes` logits of `row` (-1 for a label outside [0, classes)).
+ * -1: row or rank NULL, classes < 1. */
+int  rcn_hipx_label_rank(const float* row, int classes, int label, int* rank);
+/* rcn_hipx_plan_eval_net's text for one chunk of a metrics call: its `eval:` line names k_eval_metrics and what was asked for (n_topk
+ * counts; confusion, per_row, logits: 0 / 1); every other line is rcn_hipx_plan_eval_net's.  -1: what that refuses; n_topk outside
+ * 0 .. RCN_HIPX_EVAL_MAX_TOPK. */
+int  rcn_hipx_plan_eval_metrics_net(const rcn_hipx_net* net, int batch, int n_topk, int confusion, int per_row, int logits, char* out, int cap);
 /* data-parallel halves: gradients of the MEAN loss over this shard into the padded flat layout (rcn_hipx_param_count's
  * `padded`), and p <- p - scale * g from such a buffer. */
 int  rcn_hipx_gradients_dev(rcn_hipx_net* net, const float* x_dev, const int32_t* labels_dev, int B, float* grad_dev, float* loss_dev);

@@ -45,7 +45,16 @@ class MixStep(C.Structure):
     _fields_ = [("blend", C.c_float), ("weight", C.c_float), ("y0", C.c_int32), ("y1", C.c_int32), ("x0", C.c_int32), ("x1", C.c_int32)]
 
 
-STATE_MAX_LAYERS, STATE_SECTIONS = 32, 6                 # RCN_HIPX_STATE_MAX_LAYERS, RCN_HIPX_STATE_SECTIONS
+EVAL_MAX_TOPK = 8                                        # RCN_HIPX_EVAL_MAX_TOPK
+
+
+class EvalOut(C.Structure):
+    """rcn_hipx_eval_out: the device buffers rcn_hipx_evaluate_metrics_dev fills (a NULL asks for nothing)"""
+    _fields_ = [("loss_sum", C.c_void_p), ("correct", C.c_void_p), ("pred", C.c_void_p), ("n_topk", C.c_int32), ("topk", C.c_int32 * EVAL_MAX_TOPK),
+                ("topk_correct", C.c_void_p), ("confusion", C.c_void_p), ("loss_each", C.c_void_p), ("rank", C.c_void_p), ("logits", C.c_void_p)]
+
+
+STATE_MAX_LAYERS, STATE_SECTIONS = 32, 6               # RCN_HIPX_STATE_MAX_LAYERS, RCN_HIPX_STATE_SECTIONS
 STATE_MAGIC, STATE_VERSION = 0x54535852, 1               # RCN_HIPX_STATE_MAGIC, RCN_HIPX_STATE_VERSION
 SECTIONS = {"params": 1, "velocity": 2, "adam_m": 4, "adam_v": 8, "ema": 16, "accum": 32}      # RCN_HIPX_STATE_*: section s is bit s
 STATE_HAS = {"adam_tick": 1, "dropout_tick": 2, "clip_state": 4, "recipe": 8}                 # RCN_HIPX_STATE_HAS_*: the descriptor's flags
@@ -218,6 +227,9 @@ SIGNATURES = {
     "rcn_hipx_snapshot_dev": (_i, [_vp, _i, _vp, C.c_int64, C.POINTER(StateDesc)]),
     "rcn_hipx_restore_dev": (_i, [_vp, C.POINTER(StateDesc), _vp, C.c_int64]),
     "rcn_hipx_set_accumulated": (_i, [_vp, C.POINTER(C.c_float), _i]),
+    "rcn_hipx_evaluate_metrics_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _i, C.POINTER(EvalOut)]),
+    "rcn_hipx_label_rank": (_i, [C.POINTER(C.c_float), _i, _i, C.POINTER(C.c_int)]),
+    "rcn_hipx_plan_eval_metrics_net": (_i, [_vp, _i, _i, _i, _i, _i, C.c_char_p, _i]),
 }
 _libx = None
 
@@ -291,6 +303,54 @@ def plan_eval(in_shape: Tuple[int, int, int], layers: Sequence[tuple], batch: in
     evaluation kernel, one line per launch.  Needs no GPU."""
     return _plan_text("rcn_hipx_plan_eval", load().rcn_hipx_plan_eval, in_shape[0], in_shape[1], in_shape[2], _layer_array(layers), len(layers), batch,
                       PRECISIONS[precision], TILINGS[tiling])
+
+
+def label_rank(row, label: int) -> int:
+    """How many classes BEAT `label` on the logits `row` (rcn_hipx_label_rank, the function k_eval_metrics runs, on the host): class c beats y
+    when row[c] > row[y], or row[c] == row[y] and c < y.  0 .. classes - 1; -1 for a label outside [0, classes).  Needs no GPU."""
+    r = np.ascontiguousarray(row, dtype=np.float32).reshape(-1)
+    out = C.c_int()
+    if load().rcn_hipx_label_rank(_fptr(r), int(r.size), int(label), C.byref(out)) != 0:
+        raise ValueError("label_rank: a row of at least one logit")
+    return int(out.value)
+
+
+@dataclass
+class EvalReport:
+    """What ConvNet.evaluate_metrics found over a resident set, on the host.  loss: the mean loss; correct: rows whose arg-max is the label;
+    topk: {k: rows whose label is among the k best}; confusion: int64 [classes, classes], row = label, column = prediction (None: not asked
+    for); loss_each, rank, logits, pred: one entry per row, or None."""
+    n: int
+    loss: float
+    correct: int
+    topk: dict
+    confusion: Optional[np.ndarray] = None
+    loss_each: Optional[np.ndarray] = None
+    rank: Optional[np.ndarray] = None
+    logits: Optional[np.ndarray] = None
+    pred: Optional[np.ndarray] = None
+
+    def _confusion(self) -> np.ndarray:
+        if self.confusion is None:
+            raise ValueError("this report carries no confusion matrix (evaluate_metrics(confusion=True))")
+        return self.confusion.astype(np.float64)
+
+    def accuracy(self) -> float:
+        """rows on the diagonal over rows in the matrix (a row whose label is out of range is in neither); NaN for an empty matrix"""
+        m = self._confusion()
+        return float(np.trace(m) / m.sum()) if m.sum() > 0 else float("nan")
+
+    def recall(self) -> np.ndarray:
+        """per class: rows of the class predicted as it, over rows of the class; NaN for a class without rows"""
+        m = self._confusion()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.diag(m) / m.sum(axis=1)
+
+    def precision(self) -> np.ndarray:
+        """per class: rows of the class predicted as it, over rows predicted as it; NaN for a class that is never predicted"""
+        m = self._confusion()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.diag(m) / m.sum(axis=0)
 
 
 def state_layout(in_shape: Tuple[int, int, int], layers: Sequence[tuple], sections: Sequence[str] = ("params",)) -> StateDesc:
@@ -697,6 +757,68 @@ class ConvNet:
     def plan_eval_of_this_net(self, batch: int) -> str:
         """The launches one evaluation chunk of THIS net would make, with its own precision, tiling and options (rcn_hipx_plan_eval_net)."""
         return _plan_text("rcn_hipx_plan_eval_net", self.lib.rcn_hipx_plan_eval_net, self.net, int(batch))
+
+    def _topk_list(self, topk) -> Tuple[int, ...]:
+        """`topk` as the strictly increasing tuple of 1 <= k <= classes the library takes; anything else is a ValueError (nothing is clamped)"""
+        ks = tuple(int(k) for k in topk)
+        if len(ks) > EVAL_MAX_TOPK:
+            raise ValueError(f"topk: at most {EVAL_MAX_TOPK} values, not {len(ks)}")
+        if any(k < 1 or k > self.classes for k in ks):
+            raise ValueError(f"topk: every k must lie in 1 .. {self.classes} (the net's classes), not {ks}")
+        if any(b <= a for a, b in zip(ks, ks[1:])):
+            raise ValueError(f"topk must be strictly increasing, not {ks}")
+        return ks
+
+    def evaluate_metrics_async(self, X, labels=None, topk=(1, 5), confusion: bool = True, per_row: bool = False, logits: bool = False,
+                               x_scale: float = 1.0 / 255.0, x_shift: float = 0.0, weights: str = "live") -> dict:
+        """evaluate_async with more to tell (rcn_hipx_evaluate_metrics_dev), enqueued on the net's stream: a dict of device tensors, valid once
+        the net's stream has got there -- loss_sum float64[1], correct int64[1] and pred int32[n] as evaluate_async gives them, bit for bit;
+        topk (the ks) and topk_correct int64[len(topk)] (rows whose label is among the k best; None for an empty topk); confusion int64
+        [classes, classes] (row = label, column = prediction) or None; per_row: loss_each float32[n] and rank int32[n] (classes that beat
+        the label, -1 for a label out of range), else None; logits: float32[n, classes], forward()'s bits, else None.  topk: strictly
+        increasing, 1 <= k <= classes (the default asks for top-5: a ValueError on a net with fewer classes).  labels None: pred and
+        logits only (topk=(), confusion=False, per_row=False)."""
+        t = self.torch
+        if weights not in WEIGHTS:
+            raise ValueError(f"weights must be one of {sorted(WEIGHTS)}, not {weights!r}")
+        ks = self._topk_list(topk)
+        if labels is None and (ks or confusion or per_row):
+            raise ValueError("without labels there are only pred and logits: topk=(), confusion=False, per_row=False")
+        kind, n = self._resident_set(X, labels)
+        with t.cuda.stream(self.stream):
+            new = lambda shape, dtype: t.empty(shape, dtype=dtype, device=self.device)
+            out = dict(loss_sum=t.zeros(1, dtype=t.float64, device=self.device), correct=t.zeros(1, dtype=t.int64, device=self.device), pred=new(n, t.int32), topk=ks,
+                       topk_correct=new(len(ks), t.int64) if ks else None, confusion=new((self.classes, self.classes), t.int64) if confusion else None,
+                       loss_each=new(n, t.float32) if per_row else None, rank=new(n, t.int32) if per_row else None,
+                       logits=new((n, self.classes), t.float32) if logits else None)
+        addr = lambda name: out[name].data_ptr() if out[name] is not None else None
+        eo = EvalOut(addr("loss_sum"), addr("correct"), addr("pred"), len(ks), (C.c_int32 * EVAL_MAX_TOPK)(*ks), addr("topk_correct"), addr("confusion"), addr("loss_each"),
+                     addr("rank"), addr("logits"))
+        self._ck(self.lib.rcn_hipx_evaluate_metrics_dev(self.net, _ptr(X), kind, float(x_scale), float(x_shift), _ptr(labels), n, WEIGHTS[weights], C.byref(eo)))
+        return out
+
+    def evaluate_metrics(self, X, labels, topk=(1, 5), confusion: bool = True, per_row: bool = False, logits: bool = False,
+                         x_scale: float = 1.0 / 255.0, x_shift: float = 0.0, weights: str = "live") -> EvalReport:
+        """evaluate_metrics_async, synchronised and brought to the host as an EvalReport."""
+        if labels is None:
+            raise ValueError("evaluate_metrics needs labels (predict / predict_logits: without)")
+        out = self.evaluate_metrics_async(X, labels, topk, confusion, per_row, logits, x_scale, x_shift, weights)
+        self.synchronize()
+        host = lambda name: out[name].cpu().numpy() if out[name] is not None else None
+        counts = host("topk_correct")
+        return EvalReport(n=int(X.shape[0]), loss=float(out["loss_sum"].item()) / X.shape[0], correct=int(out["correct"].item()),
+                          topk={k: int(c) for k, c in zip(out["topk"], counts)} if counts is not None else {}, confusion=host("confusion"),
+                          loss_each=host("loss_each"), rank=host("rank"), logits=host("logits"), pred=host("pred"))
+
+    def predict_logits(self, X, x_scale: float = 1.0 / 255.0, x_shift: float = 0.0, weights: str = "live"):
+        """The logits of every row of a resident set, [n, classes] float32 on the device (forward()'s bits, chunk by chunk), valid on the net's stream."""
+        return self.evaluate_metrics_async(X, None, (), False, False, True, x_scale, x_shift, weights)["logits"]
+
+    def plan_eval_metrics_of_this_net(self, batch: int, n_topk: int = 2, confusion: bool = True, per_row: bool = False, logits: bool = False) -> str:
+        """plan_eval_of_this_net for one chunk of an evaluate_metrics call (rcn_hipx_plan_eval_metrics_net): the `eval:` line names
+        k_eval_metrics and what it was asked for; every other line is plan_eval_of_this_net's."""
+        return _plan_text("rcn_hipx_plan_eval_metrics_net", self.lib.rcn_hipx_plan_eval_metrics_net, self.net, int(batch), int(n_topk), int(bool(confusion)),
+                          int(bool(per_row)), int(bool(logits)))
 
     def gradients(self, x, labels, grad=None, loss=None):
         grad = grad if grad is not None else self.torch.empty(self.n_padded, dtype=self.torch.float32, device=self.device)

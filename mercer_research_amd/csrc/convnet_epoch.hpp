@@ -250,9 +250,42 @@ inline GatherChoice select_gather(bool u8, int B, int E, bool src_aligned16, boo
 constexpr int kEvalSamples = 8;        // samples per 256-thread workgroup of k_eval_ce (k_softmax_ce's grouping)
 inline int eval_blocks(int B) { return (B + kEvalSamples - 1) / kEvalSamples; }
 
+// One sample's share of an evaluation, run by the 32 lanes (ln) of its group on its logits row z: the maximum, the FIRST class that
+// attains it (ix; written to pred[s] where pred is given), and with labels the label y, loss = -(z[y] - max - log(sum exp)) and
+// ok = (ix == y); a label outside [0, C) never indexes the row and leaves loss and ok at the caller's zeros.  The one routine of
+// k_eval_ce and k_eval_metrics (convnet_metrics.hpp): both add the same float into their workgroup's partial.
+__device__ __forceinline__ void eval_sample(const float* __restrict__ z, int C, int ln, const int* __restrict__ labels, int s, int* __restrict__ pred, float& loss, int& ok,
+                                            int& ix_out, int& y_out) {
+    float mx = -3.0e38f;
+    int ix = 0x7fffffff;
+    for (int c = ln; c < C; c += 32)
+        if (z[c] > mx) { mx = z[c]; ix = c; }           // strictly greater: the first maximum of this lane's classes
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) {
+        const float o = __shfl_xor(mx, off, 32);
+        const int oi = __shfl_xor(ix, off, 32);
+        if (o > mx || (o == mx && oi < ix)) { mx = o; ix = oi; }
+    }
+    if (ix >= C) ix = 0;                                // (no class above -3e38: a row of NaN or -inf)
+    if (pred && ln == 0) pred[s] = ix;
+    ix_out = ix;
+    if (labels) {
+        const int y = labels[s];
+        y_out = y;
+        if (y >= 0 && y < C) {
+            float sum = 0.f;
+            for (int c = ln; c < C; c += 32) sum += expf(z[c] - mx);
+#pragma unroll
+            for (int off = 16; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 32);
+            loss = -(z[y] - mx - logf(sum));
+            ok = ix == y;
+        }
+    }
+}
+
 // Evaluation of one chunk of B logits rows (ldl floats apart): 32 lanes per sample as in k_softmax_ce, no d logits.  Per sample the
 // maximum, the FIRST class that attains it (pred, nullable), and -(z[y] - max - log(sum exp)); a label outside [0, C) never indexes the
-// row: the sample counts as incorrect and adds nothing to the loss.  loss_part[block] = the block's losses summed in sample order,
+// row: the sample counts as incorrect and adds nothing to the loss (eval_sample).  loss_part[block] = the block's losses summed in sample order,
 // correct_part[block] its correct count; the workgroup that arrives LAST adds the partials in a fixed order (thread t takes blocks
 // t, t + 256, ...; thread 0 adds the 256 sums in order), in double, and ADDS the chunk's totals into *loss_sum / *correct -- chunks run
 // one after the other on the net's stream, so the accumulators need no atomics.  It leaves the counter at zero.  labels == nullptr:
@@ -269,30 +302,8 @@ __global__ __launch_bounds__(256) void k_eval_ce(const float* __restrict__ logit
     float loss = 0.f;
     int ok = 0;
     if (s < B) {
-        const float* z = logits + (long long)s * ldl;
-        float mx = -3.0e38f;
-        int ix = 0x7fffffff;
-        for (int c = ln; c < C; c += 32)
-            if (z[c] > mx) { mx = z[c]; ix = c; }       // strictly greater: the first maximum of this lane's classes
-#pragma unroll
-        for (int off = 16; off > 0; off >>= 1) {
-            const float o = __shfl_xor(mx, off, 32);
-            const int oi = __shfl_xor(ix, off, 32);
-            if (o > mx || (o == mx && oi < ix)) { mx = o; ix = oi; }
-        }
-        if (ix >= C) ix = 0;                            // (no class above -3e38: a row of NaN or -inf)
-        if (pred && ln == 0) pred[s] = ix;
-        if (labels) {
-            const int y = labels[s];
-            if (y >= 0 && y < C) {
-                float sum = 0.f;
-                for (int c = ln; c < C; c += 32) sum += expf(z[c] - mx);
-#pragma unroll
-                for (int off = 16; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 32);
-                loss = -(z[y] - mx - logf(sum));
-                ok = ix == y;
-            }
-        }
+        int ix, y;
+        eval_sample(logits + (long long)s * ldl, C, ln, labels, s, pred, loss, ok, ix, y);
     }
     if (!labels) return;
     if (ln == 0) { red[grp] = loss; hit[grp] = ok; }

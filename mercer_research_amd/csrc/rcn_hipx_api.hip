@@ -21,6 +21,7 @@
 #include "convnet.hpp"
 #include "convnet_bf16.hpp"
 #include "convnet_epoch.hpp"
+#include "convnet_metrics.hpp"
 #include "convnet_halo.hpp"
 #include "convnet_halo_bf16.hpp"
 #include "convnet_select.hpp"
@@ -141,6 +142,7 @@ struct rcn_hipx_net : Selection, Recipe {
     // once and never moved; the mixed step's loss launch reads (yb, yb2, emixw), so ONE more graph per (B, lr) / per B serves every record
     Buf yb2, emixw;
     Buf eval_part;                          // k_eval_ce: [loss partials][correct partials][counter: zero between launches]
+    Buf eval_mpart;                         // k_eval_metrics, its own: [loss partials][correct partials][counter][top-k partials: 8 rows]; sized by max_batch, never moved
     long long n_instantiated = 0;           // hipGraphs instantiated since the net was created (rcn_hipx_graphs_instantiated)
     bool walk_open = false;                 // between rcn_hipx_gradients_begin_dev and its last bucket: the activations belong to that walk
     // the backward pass as a resumable walk (rcn_hipx_gradients_begin_dev / _bucket_dev: a data-parallel step whose all-reduce of one bucket
@@ -1277,10 +1279,54 @@ int launch_eval(rcn_hipx_net* n, const int32_t* labels, int B, double* loss_sum,
     return 0;
 }
 
-// one evaluation chunk: the forward pass over all layers (rcn_hipx_forward_dev's) and the evaluation kernel
-int eval_chunk(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, double* loss_sum, long long* correct, int32_t* pred) {
+// what a metrics call asked for, in the words of its plan line
+void metrics_asked(const rcn_hipx_eval_out& o, std::string& t) {
+    if (o.n_topk > 0) t += "; top-k counts for " + std::to_string(o.n_topk) + (o.n_topk == 1 ? " k" : " ks");
+    if (o.confusion) t += "; confusion matrix";
+    if (o.loss_each || o.rank) t += "; per-row loss and rank";
+    if (o.logits) t += "; logits copy";
+}
+
+// launch_eval's launch with the outputs of `o` for the chunk's B rows, which begin at row `off` of the call: k_eval_metrics in the place of
+// k_eval_ce, on partials of its own
+int launch_eval_metrics(rcn_hipx_net* n, const int32_t* labels, int B, int64_t off, const rcn_hipx_eval_out& o) {
+    const int blocks = eval_blocks(B);
+    if (n->dry) {
+        std::string asked;
+        metrics_asked(o, asked);
+        return dry_note(n, "  eval: k_eval_metrics, %d workgroups (loss sum, correct count, first-maximum arg-max%s; no gradient)", blocks, asked.c_str()) ? 0 : -4;
+    }
+    const Layer& l = n->L.back();
+    const size_t parts = (size_t)eval_blocks(n->max_batch);
+    if (!n->eval_mpart.p) {
+        XTRY(n, n->eval_mpart.ensure(((2 + kEvalMaxTopk) * parts + 1) * sizeof(float)));
+        XTRY(n, hipMemsetAsync(n->eval_mpart.p, 0, n->eval_mpart.cap, n->stream));
+    }
+    float* const lp = (float*)n->eval_mpart.p;
+    const bool with_labels = labels != nullptr;
+    const long long C = n->classes;
+    EvalMetrics m{};
+    m.n_topk = with_labels ? o.n_topk : 0;
+    for (int j = 0; j < m.n_topk; ++j) m.topk[j] = o.topk[j];
+    m.topk_part = (int*)(lp + 2 * parts + 1);
+    m.part_stride = (int)parts;
+    m.topk_correct = (long long*)o.topk_correct;
+    m.confusion = (long long*)o.confusion;
+    m.loss_each = o.loss_each ? o.loss_each + off : nullptr;
+    m.rank = o.rank ? o.rank + off : nullptr;
+    m.logits_out = o.logits ? o.logits + off * C : nullptr;
+    hipLaunchKernelGGL(k_eval_metrics, dim3(blocks), dim3(256), 0, n->stream, (const float*)l.out.p, labels, B, n->classes, l.CoutP, lp, (int*)(lp + parts), (unsigned*)(lp + 2 * parts),
+                       o.loss_sum, (long long*)o.correct, o.pred ? o.pred + off : nullptr, m);
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+
+// one evaluation chunk: the forward pass over all layers (rcn_hipx_forward_dev's) and the evaluation kernel -- k_eval_ce, or with
+// `metrics` (the call's outputs; the chunk begins at row `off` of them) k_eval_metrics
+int eval_chunk(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, double* loss_sum, long long* correct, int32_t* pred, const rcn_hipx_eval_out* metrics = nullptr,
+               int64_t off = 0) {
     RTRY(forward(n, x, B));
-    return launch_eval(n, labels, B, loss_sum, correct, pred);
+    return metrics ? launch_eval_metrics(n, labels, B, off, *metrics) : launch_eval(n, labels, B, loss_sum, correct, pred);
 }
 
 // params <-> average, on the net's stream
@@ -1298,10 +1344,61 @@ struct EmaSwap {
     ~EmaSwap() { if (armed) (void)launch_ema_swap(net); }
 };
 
-int plan_eval_walk(rcn_hipx_net& net, int batch) {
+int plan_eval_walk(rcn_hipx_net& net, int batch, const rcn_hipx_eval_out* metrics = nullptr) {
     net.plan = "forward + evaluation of one chunk of " + std::to_string(batch) + " rows (" + precision_name(net.precision, net.store16) + "), launch by launch:\n";
     RTRY(prep_bf16_weights(&net));
-    return eval_chunk(&net, nullptr, nullptr, batch, nullptr, nullptr, nullptr);
+    return eval_chunk(&net, nullptr, nullptr, batch, nullptr, nullptr, nullptr, metrics);
+}
+
+// why a metrics call's requests are refused (nullptr: they are not); what rcn_hipx_evaluate_ex_dev checks is left to the shared path
+const char* metrics_refusal(const rcn_hipx_eval_out* o, int classes, bool with_labels) {
+    if (!o) return "out must not be NULL";
+    if (o->n_topk < 0 || o->n_topk > RCN_HIPX_EVAL_MAX_TOPK) return "n_topk must lie in 0 .. RCN_HIPX_EVAL_MAX_TOPK";
+    for (int j = 0; j < o->n_topk; ++j)
+        if (o->topk[j] < 1 || o->topk[j] > classes || (j > 0 && o->topk[j] <= o->topk[j - 1])) return "topk must be strictly increasing with 1 <= k <= classes";
+    if (o->n_topk > 0 && !o->topk_correct) return "with n_topk > 0, topk_correct must not be NULL";
+    if (!with_labels && (o->n_topk > 0 || o->topk_correct || o->confusion || o->loss_each || o->rank))
+        return "without labels only pred and logits can be filled: topk_correct, confusion, loss_each and rank must not be asked for";
+    return nullptr;
+}
+
+// rcn_hipx_evaluate_ex_dev and rcn_hipx_evaluate_metrics_dev (`metrics`: its outputs, already found in order; loss_sum, correct and pred are
+// its first three): the refusals, the zeroing of the accumulators, the exchange with the average, the operand copies and the chunk loop
+int evaluate_rows(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows, int weights,
+                  double* loss_sum, int64_t* correct, int32_t* pred, const rcn_hipx_eval_out* metrics) {
+    if (weights != RCN_HIPX_WEIGHTS_LIVE && weights != RCN_HIPX_WEIGHTS_EMA) return fail(n, -1, "evaluate: weights must be RCN_HIPX_WEIGHTS_LIVE or RCN_HIPX_WEIGHTS_EMA");
+    if (!X) return fail(n, -1, "evaluate: X_dev must not be NULL");
+    if (!x_kind_ok(x_kind)) return fail(n, -1, "evaluate: x_kind must be RCN_HIPX_X_F32 or RCN_HIPX_X_U8");
+    if (rows < 1) return fail(n, -1, "evaluate: n must be at least 1");
+    if (labels && (!loss_sum || !correct)) return fail(n, -1, "evaluate: with labels, loss_sum_dev and correct_dev must not be NULL");
+    if (!labels && !pred && !(metrics && metrics->logits)) return fail(n, -1, "evaluate: without labels there is only pred_dev to fill; it must not be NULL");
+    if (n->walk_open) return fail(n, -6, "evaluate: a bucket walk is open (rcn_hipx_gradients_begin_dev): its activations are still needed; take the remaining buckets first");
+    if (weights == RCN_HIPX_WEIGHTS_EMA && !n->ema.p) return fail(n, -6, "evaluate: the net has no average (rcn_hipx_set_ema with a decay > 0 first)");
+    Dev g(n->device);
+    if (x_kind == RCN_HIPX_X_U8) RTRY(ensure_epoch_bufs(n));
+    if (loss_sum) XTRY(n, hipMemsetAsync(loss_sum, 0, sizeof(double), n->stream));
+    if (correct) XTRY(n, hipMemsetAsync(correct, 0, sizeof(int64_t), n->stream));
+    if (metrics && metrics->n_topk > 0) XTRY(n, hipMemsetAsync(metrics->topk_correct, 0, (size_t)metrics->n_topk * sizeof(int64_t), n->stream));
+    if (metrics && metrics->confusion) XTRY(n, hipMemsetAsync(metrics->confusion, 0, (size_t)n->classes * n->classes * sizeof(int64_t), n->stream));
+    // On the average: the parameter buffer and the average trade contents for the length of the call, so every pointer the forward pass and
+    // k_prep_all_bf16 hold (prep jobs, layer offsets) stays what it is.  The forward pass reads the parameters and, in bf16 mode, the
+    // operand copies that the prep launch below makes from them; it never reads the tap-flipped copy `wt` (only the input-gradient pass,
+    // the fused training head and the prep job of the input-gradient operand do), so wt is left alone and matches the live parameters
+    // again once they are back.  The bf16 operand copies are re-made by the next step, as by every step.
+    EmaSwap swapped{weights == RCN_HIPX_WEIGHTS_EMA ? n : nullptr};
+    RTRY(swapped.begin());
+    RTRY(prep_bf16_weights(n));
+    const long long E = row_elems(n);
+    for (int64_t off = 0; off < rows; off += n->max_batch) {
+        const int B = (int)(rows - off < n->max_batch ? rows - off : n->max_batch);
+        const float* x = (const float*)X + off * E;
+        if (x_kind == RCN_HIPX_X_U8) {
+            RTRY(launch_gather(n, X, x_kind, x_scale, x_shift, nullptr, (long long)rows, nullptr, (long long)off, B, nullptr, 0, (float*)n->xb.p, (int*)n->yb.p));
+            x = (const float*)n->xb.p;
+        }
+        RTRY(eval_chunk(n, x, labels ? labels + off : nullptr, B, loss_sum, (long long*)correct, pred ? pred + off : nullptr, metrics, off));
+    }
+    return 0;
 }
 
 }  // namespace
@@ -1398,36 +1495,19 @@ int rcn_hipx_evaluate_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_sc
 int rcn_hipx_evaluate_ex_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows, int weights,
                              double* loss_sum, int64_t* correct, int32_t* pred) {
     if (!n) return -1;
-    if (weights != RCN_HIPX_WEIGHTS_LIVE && weights != RCN_HIPX_WEIGHTS_EMA) return fail(n, -1, "evaluate: weights must be RCN_HIPX_WEIGHTS_LIVE or RCN_HIPX_WEIGHTS_EMA");
-    if (!X) return fail(n, -1, "evaluate: X_dev must not be NULL");
-    if (!x_kind_ok(x_kind)) return fail(n, -1, "evaluate: x_kind must be RCN_HIPX_X_F32 or RCN_HIPX_X_U8");
-    if (rows < 1) return fail(n, -1, "evaluate: n must be at least 1");
-    if (labels && (!loss_sum || !correct)) return fail(n, -1, "evaluate: with labels, loss_sum_dev and correct_dev must not be NULL");
-    if (!labels && !pred) return fail(n, -1, "evaluate: without labels there is only pred_dev to fill; it must not be NULL");
-    if (n->walk_open) return fail(n, -6, "evaluate: a bucket walk is open (rcn_hipx_gradients_begin_dev): its activations are still needed; take the remaining buckets first");
-    if (weights == RCN_HIPX_WEIGHTS_EMA && !n->ema.p) return fail(n, -6, "evaluate: the net has no average (rcn_hipx_set_ema with a decay > 0 first)");
-    Dev g(n->device);
-    if (x_kind == RCN_HIPX_X_U8) RTRY(ensure_epoch_bufs(n));
-    if (loss_sum) XTRY(n, hipMemsetAsync(loss_sum, 0, sizeof(double), n->stream));
-    if (correct) XTRY(n, hipMemsetAsync(correct, 0, sizeof(int64_t), n->stream));
-    // On the average: the parameter buffer and the average trade contents for the length of the call, so every pointer the forward pass and
-    // k_prep_all_bf16 hold (prep jobs, layer offsets) stays what it is.  The forward pass reads the parameters and, in bf16 mode, the
-    // operand copies that the prep launch below makes from them; it never reads the tap-flipped copy `wt` (only the input-gradient pass,
-    // the fused training head and the prep job of the input-gradient operand do), so wt is left alone and matches the live parameters
-    // again once they are back.  The bf16 operand copies are re-made by the next step, as by every step.
-    EmaSwap swapped{weights == RCN_HIPX_WEIGHTS_EMA ? n : nullptr};
-    RTRY(swapped.begin());
-    RTRY(prep_bf16_weights(n));
-    const long long E = row_elems(n);
-    for (int64_t off = 0; off < rows; off += n->max_batch) {
-        const int B = (int)(rows - off < n->max_batch ? rows - off : n->max_batch);
-        const float* x = (const float*)X + off * E;
-        if (x_kind == RCN_HIPX_X_U8) {
-            RTRY(launch_gather(n, X, x_kind, x_scale, x_shift, nullptr, (long long)rows, nullptr, (long long)off, B, nullptr, 0, (float*)n->xb.p, (int*)n->yb.p));
-            x = (const float*)n->xb.p;
-        }
-        RTRY(eval_chunk(n, x, labels ? labels + off : nullptr, B, loss_sum, (long long*)correct, pred ? pred + off : nullptr));
-    }
+    return evaluate_rows(n, X, x_kind, x_scale, x_shift, labels, rows, weights, loss_sum, correct, pred, nullptr);
+}
+
+int rcn_hipx_evaluate_metrics_dev(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, float x_shift, const int32_t* labels, int64_t rows, int weights,
+                                  const rcn_hipx_eval_out* out) {
+    if (!n) return -1;
+    if (const char* why = metrics_refusal(out, n->classes, labels != nullptr)) return fail(n, -1, std::string("evaluate_metrics: ") + why);
+    return evaluate_rows(n, X, x_kind, x_scale, x_shift, labels, rows, weights, out->loss_sum, out->correct, out->pred, out);
+}
+
+int rcn_hipx_label_rank(const float* row, int classes, int label, int* rank) {
+    if (!row || !rank || classes < 1) return -1;
+    *rank = label_rank(row, classes, label);
     return 0;
 }
 
@@ -1587,6 +1667,26 @@ int rcn_hipx_plan_eval_net(const rcn_hipx_net* n, int batch, char* out, int cap)
     rcn_hipx_net net;
     make_dry_net(net, *n, batch);
     const int st = plan_eval_walk(net, batch);
+    return emit(net, st, out, cap);
+}
+
+// ... and for one chunk of a metrics call that asks for n_topk counts and (flags) the confusion matrix, the per-row results and the logits
+int rcn_hipx_plan_eval_metrics_net(const rcn_hipx_net* n, int batch, int n_topk, int confusion, int per_row, int logits, char* out, int cap) {
+    if (!n || batch < 1 || batch > n->max_batch || n_topk < 0 || n_topk > RCN_HIPX_EVAL_MAX_TOPK || !out || cap < 1) return -1;
+    rcn_hipx_net net;
+    make_dry_net(net, *n, batch);
+    // the dry walk only asks which outputs are wanted: no pointer of `ask` is read through
+    static int64_t marker64;
+    static float marker32;
+    static int32_t marker_i;
+    rcn_hipx_eval_out ask{};
+    ask.n_topk = n_topk;
+    ask.topk_correct = n_topk > 0 ? &marker64 : nullptr;
+    ask.confusion = confusion ? &marker64 : nullptr;
+    ask.loss_each = per_row ? &marker32 : nullptr;
+    ask.rank = per_row ? &marker_i : nullptr;
+    ask.logits = logits ? &marker32 : nullptr;
+    const int st = plan_eval_walk(net, batch, &ask);
     return emit(net, st, out, cap);
 }
 
