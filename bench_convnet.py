@@ -5,6 +5,7 @@ network BASELINE.json's north_star asks for, on the configs SURVEY.md §8(d) fix
   cifar   CIFAR-10 shape 32x32x3: conv3x3 3->32, pool, 32->64, pool, 64->128, pool -> 2048 -> 256 -> 10, B = 512   (configs[2])
   synth224  synthetic 224x224x3, 8 conv layers, 128 images per GPU (global batch 1024 on 8 GPUs)                    (configs[3])
   mnist   MNIST shape 28x28x1 LeNet-style: conv 1->32, pool, conv 32->64, pool -> 3136 -> 128 -> 10, B = 256      (configs[1], trainable form)
+  cifar_bn  cifar with every conv + ReLU written Conv2d -> BatchNorm2d -> ReLU: ("conv_linear", n), ("bn_relu",) (not bf16_stored)
 
 fp32 activations / weights, fp32 MFMA (v_mfma_f32_32x32x2_f32; peak 157.3 TFLOP/s).  Reports achieved TFLOP/s of the whole
 training step (algorithmic 2*MACs of forward + dgrad + wgrad) and its fraction of the fp32 MFMA peak.  The reference has no
@@ -22,6 +23,8 @@ CONFIGS = {
     "synth224": ((224, 224, 3), (("conv", 32), ("conv", 32), ("pool",), ("conv", 64), ("conv", 64), ("pool",), ("conv", 128), ("conv", 128), ("pool",),
                                  ("conv", 256), ("conv", 256), ("pool",), ("dense", 10)), 128),
 }
+# the CIFAR net as torch writes it, Conv2d -> BatchNorm2d -> ReLU: every ("conv", n) is ("conv_linear", n), ("bn_relu",)
+CONFIGS["cifar_bn"] = (CONFIGS["cifar"][0], tuple(m for l in CONFIGS["cifar"][1] for m in ((("conv_linear", l[1]), ("bn_relu",)) if l[0] == "conv" else (l,))), CONFIGS["cifar"][2])
 F32_MFMA_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD
 BF16_MFMA_PEAK_TFLOPS = 2516.8    # same guide: dense bf16 MFMA = 16x the fp32 MFMA rate (~2.5 PFLOP/s; never the 2:1-sparsity figure)
 HBM_PEAK_GBS = 8000.0

@@ -28,7 +28,13 @@ typedef enum {
     RCN_HIPX_CONV3X3_RELU = 0,   /* 3x3, stride 1, pad 1, + bias, ReLU;  out = output channels (multiple of 32)            */
     RCN_HIPX_MAXPOOL2 = 1,       /* 2x2 / stride 2 max-pool (even H, W); out ignored                                         */
     RCN_HIPX_DENSE_RELU = 2,     /* dense + bias + ReLU; out = units (multiple of 32)                                       */
-    RCN_HIPX_DENSE = 3           /* final dense + bias (logits); out = classes (any; padded to 32 internally)               */
+    RCN_HIPX_DENSE = 3,          /* final dense + bias (logits); out = classes (any; padded to 32 internally)               */
+    RCN_HIPX_CONV3X3 = 4,        /* 3x3, stride 1, pad 1, + bias, NO activation; out = output channels (multiple of 32).
+                                    It exists for batch normalisation: the layer directly behind it must be
+                                    RCN_HIPX_BN_RELU (anything else: -2 from rcn_hipx_create)                                */
+    RCN_HIPX_BN_RELU = 5         /* torch.nn.BatchNorm2d(C) + ReLU over the map of the RCN_HIPX_CONV3X3 layer directly in
+                                    front of it (anything else in front: -2 from rcn_hipx_create); out ignored.  Its
+                                    parameters are one [W | b] block with K = 1: W[1][C] = gamma, b[C] = beta               */
 } rcn_hipx_layer_kind;
 
 typedef struct rcn_hipx_layer { int32_t kind; int32_t out; } rcn_hipx_layer;
@@ -87,9 +93,13 @@ int  rcn_hipx_set_option(rcn_hipx_net* net, const char* name, int value);
 int  rcn_hipx_get_option(const rcn_hipx_net* net, const char* name, int* value);
 int  rcn_hipx_set_params(rcn_hipx_net* net, const float* flat);
 int  rcn_hipx_get_params(rcn_hipx_net* net, float* flat);
-int  rcn_hipx_init_params(rcn_hipx_net* net, uint64_t seed);            /* He-normal weights, zero biases */
+int  rcn_hipx_init_params(rcn_hipx_net* net, uint64_t seed);            /* He-normal weights, zero biases; batch norm: gamma = 1, beta = 0 */
 /* logits_dev: [B][classes] */
 int  rcn_hipx_forward_dev(rcn_hipx_net* net, const float* x_dev, int B, float* logits_dev);
+/* logits_dev: [B][classes], the rows the LAST forward pass on the net's stream left -- a training step's or a gradients call's TRAINING
+ * forward (batch statistics, dropout) among them, which rcn_hipx_forward_dev never runs; after an evaluation, its last chunk's.  Enqueued
+ * on the net's stream.  -6: no forward pass has run yet, or the last one ran another batch size than B. */
+int  rcn_hipx_last_logits_dev(rcn_hipx_net* net, int B, float* logits_dev);
 /* one SGD step on mean cross-entropy: forward, backward, W <- W - lr * dW (or the update rcn_hipx_set_sgd chose, in the same launch).
  * loss_dev (nullable): mean loss before the step.  Replayed as one hipGraph per (pointers, B, lr). */
 int  rcn_hipx_train_step_dev(rcn_hipx_net* net, const float* x_dev, const int32_t* labels_dev, int B, float lr, float* loss_dev);
@@ -568,7 +578,9 @@ int  rcn_hipx_dropout_apply_dev(rcn_hipx_net* net, int site, int64_t t, float* a
  * the cycle, 0 .. k - 1; synchronises.  -6 while k == 1; -1 for a NULL pointer or a position out of range.
  * Not carried: the kernel-selection options (rcn_hipx_set_option: seeded from the environment; a caller who changed one sets it again
  * before resuming), rcn_hipx_set_overlap, the caller's norm-log ring (rcn_hipx_set_grad_norm_log; its counter IS carried, in the clip
- * state) and anything of a data-parallel group. */
+ * state), anything of a data-parallel group, and batch normalisation's running statistics and (momentum, eps): gamma and beta travel in
+ * every section as their layer's K = 1 block, the running statistics go through rcn_hipx_get_bn_stats / _set_bn_stats (the Python
+ * layer's save / load carry them in front of the file's extra blob). */
 enum { RCN_HIPX_STATE_PARAMS = 1, RCN_HIPX_STATE_VELOCITY = 2, RCN_HIPX_STATE_ADAM_M = 4, RCN_HIPX_STATE_ADAM_V = 8, RCN_HIPX_STATE_EMA = 16,
        RCN_HIPX_STATE_ACCUM = 32 };                                             /* section s is bit s */
 enum { RCN_HIPX_STATE_HAS_ADAM_TICK = 1, RCN_HIPX_STATE_HAS_DROPOUT_TICK = 2, RCN_HIPX_STATE_HAS_CLIP_STATE = 4, RCN_HIPX_STATE_HAS_RECIPE = 8 };
@@ -642,6 +654,30 @@ int  rcn_hipx_plan_net(const rcn_hipx_net* net, int batch, char* out, int cap);
 int  rcn_hipx_plan_micro_net(const rcn_hipx_net* net, int batch, int kind, char* out, int cap);
 /* algorithmic FLOPs of one training step at batch B (2 * MACs; forward + dgrad + wgrad) */
 int  rcn_hipx_step_flops(const rcn_hipx_net* net, int B, double* flops);
+
+/* ---- batch normalisation (csrc/convnet_bn.hpp): RCN_HIPX_BN_RELU layers, torch.nn.BatchNorm2d semantics ----
+ * A training forward (every step, micro-step and gradients call) normalises with the statistics of ITS batch -- biased variance,
+ * invstd = 1 / sqrt(var + eps) -- and advances the running statistics r <- (1 - momentum) * r + momentum * s, with the unbiased variance
+ * var * M / (M - 1) for the running variance (M = B * H * W rows; M < 2: -2, nothing enqueued).  All of it is enqueued on the net's stream
+ * inside the step, so it is captured with the step and the running statistics advance on every replay.  rcn_hipx_forward_dev and every
+ * evaluation use the running statistics; weights = RCN_HIPX_WEIGHTS_EMA scores the averaged gamma and beta with the live running
+ * statistics (torch's AveragedModel with use_buffers = False).  gamma and beta are parameters like any other: weight decay, Adam, the
+ * average, clipping and accumulation treat them as torch does when all parameters share one group.  RCN_HIPX_BF16 rounds the
+ * convolutions' operands as ever and leaves batch normalisation in fp32; RCN_HIPX_BF16_STORED is refused (-3) on a net with such a layer.
+ * rcn_hipx_set_bn: momentum in [0, 1] and eps > 0, both finite (-1 otherwise); defaults 0.1 and 1e-5; -3 on a net without such a layer
+ * unless the values are the defaults; a changed value drops the net's graphs.  num_batches_tracked is not kept (momentum is never None).
+ * _get_bn_stats / _set_bn_stats: host arrays, all such layers back to back, mean[C] then var[C] per layer (rcn_hipx_bn_stats_count
+ * floats); both synchronise.  _reset_bn_stats: mean 0, variance 1 (the state of a new net). */
+int  rcn_hipx_set_bn(rcn_hipx_net* net, float momentum, float eps);
+int  rcn_hipx_get_bn(const rcn_hipx_net* net, float* momentum, float* eps, int* layers);
+int  rcn_hipx_bn_stats_count(const rcn_hipx_net* net, int64_t* floats);
+int  rcn_hipx_get_bn_stats(rcn_hipx_net* net, float* stats);
+int  rcn_hipx_set_bn_stats(rcn_hipx_net* net, const float* stats);
+int  rcn_hipx_reset_bn_stats(rcn_hipx_net* net);
+/* Pure host arithmetic behind the per-channel sums (no net, no GPU): *parts = the partial sums per channel a map of `rows` rows is cut into
+ * (a function of rows alone, not monotonic in it), *capacity = the partials a layer's buffer holds when its largest map has `rows` rows;
+ * parts(m) <= capacity(rows) for every 1 <= m <= rows.  -1: rows < 1 or a NULL pointer. */
+int  rcn_hipx_bn_partials(int64_t rows, int* parts, int* capacity);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,7 @@ from . import _lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBX_PATH = os.path.join(HERE, "librcn_hipx.so")
-KIND = {"conv": 0, "pool": 1, "dense_relu": 2, "dense": 3}
+KIND = {"conv": 0, "pool": 1, "dense_relu": 2, "dense": 3, "conv_linear": 4, "bn_relu": 5}
 
 
 class XLayer(C.Structure):
@@ -84,7 +84,7 @@ class StateDesc(C.Structure):
     def shape_and_layers(self):
         """(in_shape, layers) as ConvNet takes them"""
         names = {v: k for k, v in KIND.items()}
-        layers = [(names[self.layers[i].kind],) if self.layers[i].kind == KIND["pool"] else (names[self.layers[i].kind], int(self.layers[i].out))
+        layers = [(names[self.layers[i].kind],) if self.layers[i].kind in (KIND["pool"], KIND["bn_relu"]) else (names[self.layers[i].kind], int(self.layers[i].out))
                   for i in range(self.n_layers)]
         return (int(self.in_h), int(self.in_w), int(self.in_c)), layers
 
@@ -230,6 +230,14 @@ SIGNATURES = {
     "rcn_hipx_evaluate_metrics_dev": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _vp, C.c_int64, _i, C.POINTER(EvalOut)]),
     "rcn_hipx_label_rank": (_i, [C.POINTER(C.c_float), _i, _i, C.POINTER(C.c_int)]),
     "rcn_hipx_plan_eval_metrics_net": (_i, [_vp, _i, _i, _i, _i, _i, C.c_char_p, _i]),
+    "rcn_hipx_last_logits_dev": (_i, [_vp, _i, _vp]),
+    "rcn_hipx_set_bn": (_i, [_vp, C.c_float, C.c_float]),
+    "rcn_hipx_get_bn": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "rcn_hipx_bn_stats_count": (_i, [_vp, C.POINTER(C.c_int64)]),
+    "rcn_hipx_get_bn_stats": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rcn_hipx_set_bn_stats": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rcn_hipx_reset_bn_stats": (_i, [_vp]),
+    "rcn_hipx_bn_partials": (_i, [C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 _libx = None
 
@@ -303,6 +311,15 @@ def plan_eval(in_shape: Tuple[int, int, int], layers: Sequence[tuple], batch: in
     evaluation kernel, one line per launch.  Needs no GPU."""
     return _plan_text("rcn_hipx_plan_eval", load().rcn_hipx_plan_eval, in_shape[0], in_shape[1], in_shape[2], _layer_array(layers), len(layers), batch,
                       PRECISIONS[precision], TILINGS[tiling])
+
+
+def bn_partials(rows: int) -> Tuple[int, int]:
+    """(parts, capacity) of rcn_hipx_bn_partials: the partial sums per channel of a map of `rows` rows, and what a layer whose largest map
+    has `rows` rows makes room for.  Needs no GPU."""
+    parts, cap = C.c_int(), C.c_int()
+    if load().rcn_hipx_bn_partials(int(rows), C.byref(parts), C.byref(cap)) != 0:
+        raise ConvNetError("rcn_hipx_bn_partials: rows must be at least 1")
+    return int(parts.value), int(cap.value)
 
 
 def label_rank(row, label: int) -> int:
@@ -486,7 +503,8 @@ def warmup_cosine(n_steps: int, peak: float, warmup_steps: int, floor: float = 0
 
 
 class ConvNet:
-    """layers: sequence of ("conv", Cout) | ("pool",) | ("dense_relu", units) | ("dense", classes)."""
+    """layers: sequence of ("conv", Cout) | ("pool",) | ("dense_relu", units) | ("dense", classes) | ("conv_linear", Cout) | ("bn_relu",):
+    torch's Conv2d -> BatchNorm2d -> ReLU is ("conv_linear", Cout), ("bn_relu",)."""
 
     def __init__(self, in_shape: Tuple[int, int, int], layers: Sequence[tuple], max_batch: int, device: int = 0):
         import torch
@@ -584,6 +602,13 @@ class ConvNet:
     def forward(self, x):
         out = self.torch.empty(x.shape[0], self.classes, dtype=self.torch.float32, device=self.device)
         self._ck(self.lib.rcn_hipx_forward_dev(self.net, _ptr(x), x.shape[0], _ptr(out)))
+        return out
+
+    def last_logits(self, B: int):
+        """[B, classes]: the logits the LAST forward pass left -- after train_step or gradients, those of its TRAINING forward (batch
+        statistics, dropout), which forward never runs (rcn_hipx_last_logits_dev)"""
+        out = self.torch.empty(int(B), self.classes, dtype=self.torch.float32, device=self.device)
+        self._ck(self.lib.rcn_hipx_last_logits_dev(self.net, int(B), _ptr(out)))
         return out
 
     def train_step(self, x, labels, lr: float, loss=None):
@@ -1032,7 +1057,66 @@ class ConvNet:
     def save(self, path, extra: Optional[bytes] = None, sections="all") -> int:
         """snapshot(sections).save(path, extra): one file holding the descriptor, the body, the caller's `extra` blob and a CRC-32.
         Returns the file's size."""
-        return self.snapshot(sections).save(path, extra)
+        snap = self.snapshot(sections)
+        return snap.save(path, self._bn_pack_extra(extra))
+
+    # ---- batch normalisation (include/rcn_hipx.h: rcn_hipx_set_bn; csrc/convnet_bn.hpp) ----
+    def set_bn(self, momentum: float = 0.1, eps: float = 1e-5):
+        """momentum and eps of every bn_relu layer, torch.nn.BatchNorm2d's meaning and defaults.  A changed value drops the net's graphs."""
+        self._ck(self.lib.rcn_hipx_set_bn(self.net, float(momentum), float(eps)))
+
+    def get_bn(self) -> Tuple[float, float, int]:
+        """(momentum, eps, number of bn_relu layers)"""
+        m, e, k = C.c_float(), C.c_float(), C.c_int()
+        self._ck(self.lib.rcn_hipx_get_bn(self.net, C.byref(m), C.byref(e), C.byref(k)))
+        return float(m.value), float(e.value), int(k.value)
+
+    def _bn_count(self) -> int:
+        c = C.c_int64()
+        self._ck(self.lib.rcn_hipx_bn_stats_count(self.net, C.byref(c)))
+        return int(c.value)
+
+    def get_bn_stats(self) -> np.ndarray:
+        """The running statistics, all bn_relu layers back to back: mean[C] then var[C] per layer (float32); synchronises."""
+        f = np.zeros(self._bn_count(), dtype=np.float32)
+        if f.size:
+            self._ck(self.lib.rcn_hipx_get_bn_stats(self.net, _fptr(f)))
+        return f
+
+    def set_bn_stats(self, stats: np.ndarray):
+        f = np.ascontiguousarray(stats, dtype=np.float32).ravel()
+        if f.size != self._bn_count():
+            raise ValueError(f"set_bn_stats: {self._bn_count()} values (mean[C] then var[C] per bn_relu layer), not {f.size}")
+        if f.size:
+            self._ck(self.lib.rcn_hipx_set_bn_stats(self.net, _fptr(f)))
+
+    def reset_bn_stats(self):
+        """running mean 0, running variance 1: the state of a new net"""
+        self._ck(self.lib.rcn_hipx_reset_bn_stats(self.net))
+
+    # The state file's body has no room for the running statistics (its format is the descriptor's), so save puts them, with momentum and
+    # eps, in FRONT of the caller's extra blob behind a tag, and load / load_state take them off again.  A net without a bn_relu layer
+    # writes the caller's blob as it is: its files are what they always were.
+    _BN_TAG = struct.Struct("<8sIffI")                       # tag, number of floats, momentum, eps, 1 if a caller's blob follows the floats
+
+    def _bn_pack_extra(self, extra: Optional[bytes]) -> Optional[bytes]:
+        stats = self.get_bn_stats()
+        if not stats.size:
+            return extra
+        m, e, _ = self.get_bn()
+        return self._BN_TAG.pack(b"RCNXBNS1", stats.size, m, e, 0 if extra is None else 1) + stats.tobytes() + (b"" if extra is None else bytes(extra))
+
+    def _bn_unpack_extra(self, extra: Optional[bytes]) -> Optional[bytes]:
+        count = self._bn_count()
+        if not count or extra is None or len(extra) < self._BN_TAG.size or extra[:8] != b"RCNXBNS1":
+            return extra
+        _, n, m, e, has = self._BN_TAG.unpack_from(extra, 0)
+        at = self._BN_TAG.size
+        if n != count or len(extra) < at + 4 * n:
+            raise ConvNetError("state file: the running statistics in front of the extra blob are not this net's")
+        self.set_bn(m, e)
+        self.set_bn_stats(np.frombuffer(extra, dtype=np.float32, count=n, offset=at))
+        return extra[at + 4 * n:] if has else None
 
     def _restore(self, desc: StateDesc, body):
         self._ck(self.lib.rcn_hipx_restore_dev(self.net, C.byref(desc), _ptr(body), int(body.numel())))
@@ -1042,7 +1126,8 @@ class ConvNet:
         """Restores a Snapshot (of any net of this description on this device) or a state file (a path) into THIS net
         (rcn_hipx_restore_dev): precision, tiling, the recipe and every carried section; what the snapshot does not carry is left alone.
         Everything is checked before anything changes: a refusal (ConvNetError) leaves the net bit for bit what it was.  Synchronises.
-        Returns the file's `extra` blob (None for a Snapshot)."""
+        Returns the file's `extra` blob (None for a Snapshot).  A file written by save carries a bn_relu net's running statistics, momentum and
+        eps in front of that blob: they are restored too and taken off it.  A Snapshot carries gamma and beta, not the running statistics."""
         if isinstance(source, Snapshot):
             if source.body.device != self.device:
                 raise ValueError("load_state: the snapshot's body lives on another device (save it and load the file)")
@@ -1052,7 +1137,7 @@ class ConvNet:
         with open(source, "rb") as f:
             desc, body, extra = read_state_file(f.read())
         self._restore(desc, self.to_device(body))
-        return extra
+        return self._bn_unpack_extra(extra)
 
     @classmethod
     def load(cls, path, max_batch: int, device: int = 0):
@@ -1064,6 +1149,7 @@ class ConvNet:
         net = cls(in_shape, layers, int(max_batch), device)
         try:
             net._restore(desc, net.to_device(body))
+            extra = net._bn_unpack_extra(extra)
         except Exception:
             net.close()
             raise
@@ -1136,6 +1222,15 @@ class ConvNet:
                 i, o = H * W * Cc * es_in, H * W * l[1] * es_stage
                 total += B * ((i + o) + (0 if first else (i + o)) + (i + o)) + 3 * (9 * Cc * l[1] + l[1]) * 4
                 Cc, first, es_in = l[1], False, es_stage
+            elif l[0] == "conv_linear":
+                i, o = H * W * Cc * es_in, H * W * l[1] * 4
+                total += B * ((i + o) + (0 if first else (i + o)) + (i + o)) + 3 * (9 * Cc * l[1] + l[1]) * 4
+                Cc, first, es_in = l[1], False, 4
+            elif l[0] == "bn_relu":
+                # forward: the map read twice (statistics, apply) and written once; backward: three maps read over its two passes (x and dy
+                # by the sums, then one more pass's worth -- a re-read that hits the cache, the gate map -- is not counted) and one written
+                m = H * W * Cc * 4
+                total += B * (3 * m + 4 * m)
             elif l[0] == "pool":
                 i, o = H * W * Cc * es_stage, (H // 2) * (W // 2) * Cc * es_stage
                 total += B * 2 * (i + o)

@@ -410,6 +410,7 @@ struct Recipe {
     int accum_k = 1; float accum_c = 1.f;   // rcn_hipx_set_accumulate: 1 is off; accum_c = fl(1.0f / k)
     // rcn_hipx_set_dropout (convnet_dropout.hpp): 0 is off; drop_s = fl(1.0f / fl(1.0f - p)), drop_thr = llrint(p * 2^24)
     float drop_p = 0.f; unsigned long long drop_seed = 0; float drop_s = 1.f; unsigned drop_thr = 0;
+    float bn_momentum = 0.1f, bn_eps = 1e-5f;      // rcn_hipx_set_bn (convnet_bn.hpp): torch.nn.BatchNorm2d's defaults
 };
 inline bool adam_on(const Recipe& r) { return r.optim == 1; }
 inline bool sgd_default(const Recipe& r) { return r.sgd_mu == 0.f && r.sgd_wd == 0.f && !r.sgd_nesterov; }

@@ -29,6 +29,7 @@
 #include "convnet_accum.hpp"
 #include "convnet_dropout.hpp"
 #include "convnet_state.hpp"
+#include "convnet_bn.hpp"
 
 using namespace rcnx;
 
@@ -62,11 +63,18 @@ struct LayerShape {
     long long lw_off = 0, lb_off = 0;     // logical flat layout
     bool pool_follows = false;
 };
+// the kinds by what the walks ask of them: a 3x3 convolution (with or without ReLU), and a layer whose W is a matrix with a tap-flipped
+// copy and bf16 operand copies (every layer with a [W | b] block but batch normalisation, whose block is [gamma | beta])
+inline bool is_conv(int kind) { return kind == RCN_HIPX_CONV3X3_RELU || kind == RCN_HIPX_CONV3X3; }
+inline bool has_matrix(int kind) { return kind != RCN_HIPX_MAXPOOL2 && kind != RCN_HIPX_BN_RELU; }
 // ... and what it holds on the device
 struct Layer : LayerShape {
     Buf out, idx, dout;     // activation (post-ReLU / pooled), pool arg-max, gradient wrt the layer's OUTPUT
     Buf slab;               // partial [W | b] tiles of the weight-gradient kernels (reduced for all layers at once: run_reduce_jobs)
     long long wbf_off = -1, wbb_off = -1;   // bf16 mode: this layer's transposed bf16 weight copies in net->wb16 (forward / input-gradient operand)
+    // batch normalisation (convnet_bn.hpp), allocated by rcn_hipx_create and never moved: [batch mean | batch invstd | running mean | running var],
+    // C floats each, and the partial sums of the statistics and of the backward pass, bn_parts(max M) x 2 x C doubles
+    Buf bn, bn_part;
 };
 
 // everything a captured step bakes in: its arguments are step_core's (a first or middle micro-step keys with lr = 0 and no lr_dev: it
@@ -144,6 +152,7 @@ struct rcn_hipx_net : Selection, Recipe {
     Buf eval_part;                          // k_eval_ce: [loss partials][correct partials][counter: zero between launches]
     Buf eval_mpart;                         // k_eval_metrics, its own: [loss partials][correct partials][counter][top-k partials: 8 rows]; sized by max_batch, never moved
     long long n_instantiated = 0;           // hipGraphs instantiated since the net was created (rcn_hipx_graphs_instantiated)
+    int last_rows = 0;                      // the batch of the last forward pass (rcn_hipx_last_logits_dev); 0: none yet
     bool walk_open = false;                 // between rcn_hipx_gradients_begin_dev and its last bucket: the activations belong to that walk
     // the backward pass as a resumable walk (rcn_hipx_gradients_begin_dev / _bucket_dev: a data-parallel step whose all-reduce of one bucket
     // of layers overlaps the backward pass of the layers below it)
@@ -435,9 +444,9 @@ int prep_bf16_weights(rcn_hipx_net* n) {
         std::vector<std::tuple<size_t, int, long long>> plan;      // (layer, orientation, offset)
         for (size_t i = 1; i < n->L.size(); ++i) {
             Layer& l = n->L[i];
-            if (l.kind == RCN_HIPX_MAXPOOL2) continue;
-            const int ks = l.kind == RCN_HIPX_CONV3X3_RELU ? 3 : 1;
-            const long long cin = l.kind == RCN_HIPX_CONV3X3_RELU ? l.Cin : l.K;
+            if (!has_matrix(l.kind)) continue;
+            const int ks = is_conv(l.kind) ? 3 : 1;
+            const long long cin = is_conv(l.kind) ? l.Cin : l.K;
             const long long Kf = (long long)ks * ks * cin, Kpf = (Kf + 31) / 32 * 32;                 // forward: [CoutP][Kpf]
             const long long Kb = (long long)ks * ks * l.CoutP, Kpb = (Kb + 31) / 32 * 32;              // input gradient: [cin][Kpb]
             l.wbf_off = off; off += (long long)l.CoutP * Kpf;
@@ -450,9 +459,9 @@ int prep_bf16_weights(rcn_hipx_net* n) {
         n->prep.njobs = 0;
         for (size_t i = 1; i < n->L.size(); ++i) {
             Layer& l = n->L[i];
-            if (l.kind == RCN_HIPX_MAXPOOL2) continue;
-            const int ks = l.kind == RCN_HIPX_CONV3X3_RELU ? 3 : 1;
-            const long long cin = l.kind == RCN_HIPX_CONV3X3_RELU ? l.Cin : l.K;
+            if (!has_matrix(l.kind)) continue;
+            const int ks = is_conv(l.kind) ? 3 : 1;
+            const long long cin = is_conv(l.kind) ? l.Cin : l.K;
             const long long Kf = (long long)ks * ks * cin, Kpf = (Kf + 31) / 32 * 32, Kb = (long long)ks * ks * l.CoutP, Kpb = (Kb + 31) / 32 * 32;
             PrepJob& a = n->prep.j[n->prep.njobs++];
             a = PrepJob{(const float*)P(n, l.w_off), (__bf16*)n->wb16.p + l.wbf_off, (int)Kf, l.CoutP, (int)Kpf, (int)blocks};
@@ -501,11 +510,65 @@ int launch_dropout_bwd(rcn_hipx_net* n, size_t i, int B) {
     return 0;
 }
 
+// ---- batch normalisation (convnet_bn.hpp): a RCN_HIPX_BN_RELU layer normalises the map of the RCN_HIPX_CONV3X3 layer in front of it
+inline const char* const kBnStoreGap = "bf16 storage (RCN_HIPX_BF16_STORED) does not cover batch normalisation: its maps are fp32 (RCN_HIPX_BF16 rounds the convolutions' operands and works)";
+int bn_layers(const rcn_hipx_net* n) { int k = 0; for (const Layer& l : n->L) k += l.kind == RCN_HIPX_BN_RELU; return k; }
+// a training forward needs two rows per channel at least (the unbiased variance): asked before anything is enqueued
+int bn_rows_ok(rcn_hipx_net* n, int B) {
+    for (const Layer& l : n->L)
+        if (l.kind == RCN_HIPX_BN_RELU && (long long)B * l.oH * l.oW < 2) return fail(n, -2, "batch normalisation needs at least two rows (B * H * W >= 2) in a training forward");
+    return 0;
+}
+float* bn_mean(const Layer& l) { return (float*)l.bn.p; }
+float* bn_invstd(const Layer& l) { return (float*)l.bn.p + l.CoutP; }
+float* bn_run_mean(const Layer& l) { return (float*)l.bn.p + 2 * l.CoutP; }
+float* bn_run_var(const Layer& l) { return (float*)l.bn.p + 3 * l.CoutP; }
+// running mean 0, running variance 1 in every such layer, on the net's stream
+int bn_reset_stats(rcn_hipx_net* n) {
+    for (const Layer& l : n->L) {
+        if (l.kind != RCN_HIPX_BN_RELU) continue;
+        const std::vector<float> init = [&] { std::vector<float> v((size_t)4 * l.CoutP, 0.f); for (int c = 0; c < l.CoutP; ++c) v[(size_t)3 * l.CoutP + c] = 1.f; return v; }();
+        XTRY(n, hipMemcpyAsync(l.bn.p, init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice, n->stream));
+        XTRY(n, hipStreamSynchronize(n->stream));       // (the staging vector ends here)
+    }
+    return 0;
+}
+// layer i (RCN_HIPX_BN_RELU) of a forward pass over x[M][C]: train -- the batch's statistics (two launches; the running statistics
+// advance), then the apply launch on them; else the apply launch on the running statistics
+int launch_bn_forward(rcn_hipx_net* n, size_t i, const float* x, int B, bool train) {
+    Layer& l = n->L[i];
+    const int C = l.CoutP;
+    const long long M = (long long)B * l.oH * l.oW, n4 = M * (C / 4);
+    const int parts = bn_parts(M);
+    const unsigned blocks = bn_stream_blocks(n4, C / 4);
+    if (train && !n->dry && (size_t)parts * 2 * C * sizeof(double) > l.bn_part.cap) return fail(n, -3, "internal: more partial sums than the layer's buffer holds");
+    if (train) {
+        if (!dry_note(n, "  bn-stats %dx%dx%d: k_bn_stats, %d partials of %lld rows, then k_bn_stats_finish (one workgroup, %d threads per channel; momentum %g, eps %g)",
+                      l.oH, l.oW, C, parts, bn_rows_per_part(M), bn_team(C), (double)n->bn_momentum, (double)n->bn_eps)) {
+            hipLaunchKernelGGL(k_bn_stats, dim3((unsigned)parts, (unsigned)bn_group_blocks(C)), dim3(kBnThreads), 0, n->stream, x, M, C, (double*)l.bn_part.p);
+            XTRY(n, hipGetLastError());
+            hipLaunchKernelGGL(k_bn_stats_finish, dim3(1), dim3(kBnFinishThreads), 0, n->stream, (const double*)l.bn_part.p, parts, M, C, n->bn_momentum, n->bn_eps,
+                               bn_mean(l), bn_invstd(l), bn_run_mean(l), bn_run_var(l));
+            XTRY(n, hipGetLastError());
+        }
+        if (dry_note(n, "  bn-relu %dx%dx%d: k_bn_apply_relu, %u workgroups (the batch's mean and invstd)", l.oH, l.oW, C, blocks)) return 0;
+        hipLaunchKernelGGL(k_bn_apply_relu<false>, dim3(blocks), dim3(kBnThreads), 0, n->stream, x, (float*)l.out.p, n4, C, (const float*)bn_mean(l), (const float*)bn_invstd(l),
+                           (const float*)P(n, l.w_off), (const float*)P(n, l.b_off), n->bn_eps);
+    } else {
+        if (dry_note(n, "  bn-relu %dx%dx%d: k_bn_apply_relu<eval>, %u workgroups (scale and shift from the running statistics, eps %g)", l.oH, l.oW, C, blocks, (double)n->bn_eps)) return 0;
+        hipLaunchKernelGGL(k_bn_apply_relu<true>, dim3(blocks), dim3(kBnThreads), 0, n->stream, x, (float*)l.out.p, n4, C, (const float*)bn_run_mean(l), (const float*)bn_run_var(l),
+                           (const float*)P(n, l.w_off), (const float*)P(n, l.b_off), n->bn_eps);
+    }
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+
 // forward for batch B; returns pointer to logits (padded rows of CoutP)
 // train: the forward of a training step (step_front) -- with dropout on, every RCN_HIPX_DENSE_RELU layer's output goes through its site's
 // mask; every other forward (rcn_hipx_forward_dev, evaluation) never drops and never scales
 int forward(rcn_hipx_net* n, const float* x, int B, size_t n_layers = (size_t)-1, bool train = false) {
     const bool drop = train && dropout_on(*n);
+    n->last_rows = B;
     const float* cur = x;
     bool cur16 = false;                                  // `cur` is a bf16 tensor (RCN_HIPX_BF16_STORED)
     if (n_layers > n->L.size()) n_layers = n->L.size();
@@ -532,6 +595,13 @@ int forward(rcn_hipx_net* n, const float* x, int B, size_t n_layers = (size_t)-1
             cur = (const float*)l.out.p;
             cur16 = n->store16;
             continue;
+        } else if (l.kind == RCN_HIPX_CONV3X3) {
+            // bias only (epilogue 1), no conv+pool fusion: what follows is batch normalisation, on an fp32 map
+            if (n->store16) return fail(n, -3, kBnStoreGap);
+            RTRY(launch_conv(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShape{B, l.H, l.W, l.Cin, l.CoutP}, 3, 1, nullptr, nullptr, false, wb_of(n, l.wbf_off)));
+        } else if (l.kind == RCN_HIPX_BN_RELU) {
+            if (n->store16) return fail(n, -3, kBnStoreGap);
+            RTRY(launch_bn_forward(n, i, cur, B, train));
         } else {
             // (the logits layer of a head that training runs as k_head_f32 is fp32 here too: what bf16 mode rounds is a matter of shape)
             RTRY(launch_conv(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShape{B, 1, 1, l.K, l.CoutP}, 1, l.kind == RCN_HIPX_DENSE_RELU ? 2 : 1, nullptr, nullptr,
@@ -554,7 +624,7 @@ int reduce_slab(rcn_hipx_net* n, size_t i, int chunks, int ks, const ConvShape& 
     jb.p = P(n, l.w_off);
     jb.grad = grad ? grad + l.w_off : (float*)nullptr;
     jb.slab = (const float*)l.slab.p;
-    jb.flip = FlipSpec{(apply && i > 0) ? (float*)n->wt.p + l.w_off : (float*)nullptr, ks * ks, s.Cin, s.Cout};
+    jb.flip = FlipSpec{(apply && i > 0 && has_matrix(l.kind)) ? (float*)n->wt.p + l.w_off : (float*)nullptr, ks * ks, s.Cin, s.Cout};
     jb.n = ((long long)s.Cin * ks * ks + 1) * s.Cout;
     if (jb.n % 4 != 0 || l.w_off % 4 != 0) return fail(n, -3, "internal: a layer's [W | b] is not a whole number of 16-byte pieces");
     jb.chunks = chunks;
@@ -563,6 +633,40 @@ int reduce_slab(rcn_hipx_net* n, size_t i, int chunks, int ks, const ConvShape& 
     jb.first_block = prev_end;
     ++n->jobs.njobs;
     return 0;
+}
+
+// Layer i (RCN_HIPX_BN_RELU) of the backward pass: the two per-channel sums of g = its dout (gated: by the pool's backward or the convolution
+// above; else gated here with out > 0) into the layer's one-chunk slab [d gamma | d beta], queued for the step's reduction launch like
+// any [W | b] slab (n = 2 C, no flipped copy), then the gradient of the convolution's map into that layer's dout -- its dZ.
+int launch_bn_backward(rcn_hipx_net* n, size_t i, int B, bool gated, float* grad, bool apply) {
+    Layer& l = n->L[i];
+    Layer& cl = n->L[i - 1];
+    const int C = l.CoutP;
+    const long long M = (long long)B * l.oH * l.oW, n4 = M * (C / 4);
+    const int parts = bn_parts(M);
+    const unsigned blocks = bn_stream_blocks(n4, C / 4);
+    if (!n->dry && (size_t)parts * 2 * C * sizeof(double) > l.bn_part.cap) return fail(n, -3, "internal: more partial sums than the layer's buffer holds");
+    const char* const who = l.pool_follows ? "gated by the pool's backward" : gated ? "gated by the convolution above" : "gates itself (out > 0)";
+    const float* const x = (const float*)cl.out.p;
+    const float* const dy = (const float*)l.dout.p;
+    const float* const y = (const float*)l.out.p;
+    if (!dry_note(n, "  bn-bwd-reduce %dx%dx%d: k_bn_bwd_reduce, %d partials of %lld rows, then k_bn_bwd_finish (one workgroup) into the slab [d gamma | d beta]; %s",
+                  l.oH, l.oW, C, parts, bn_rows_per_part(M), who)) {
+        const dim3 grid((unsigned)parts, (unsigned)bn_group_blocks(C));
+        if (gated) hipLaunchKernelGGL(k_bn_bwd_reduce<false>, grid, dim3(kBnThreads), 0, n->stream, x, dy, y, M, C, (const float*)bn_mean(l), (const float*)bn_invstd(l), (double*)l.bn_part.p);
+        else hipLaunchKernelGGL(k_bn_bwd_reduce<true>, grid, dim3(kBnThreads), 0, n->stream, x, dy, y, M, C, (const float*)bn_mean(l), (const float*)bn_invstd(l), (double*)l.bn_part.p);
+        XTRY(n, hipGetLastError());
+        hipLaunchKernelGGL(k_bn_bwd_finish, dim3(1), dim3(kBnFinishThreads), 0, n->stream, (const double*)l.bn_part.p, parts, C, (float*)l.slab.p);
+        XTRY(n, hipGetLastError());
+    }
+    if (!dry_note(n, "  bn-bwd-dx %dx%dx%d: k_bn_bwd_dx, %u workgroups (the convolution's dZ)", l.oH, l.oW, C, blocks)) {
+        if (gated) hipLaunchKernelGGL(k_bn_bwd_dx<false>, dim3(blocks), dim3(kBnThreads), 0, n->stream, x, dy, y, (float*)cl.dout.p, n4, C, (float)M, (const float*)bn_mean(l),
+                                      (const float*)bn_invstd(l), (const float*)P(n, l.w_off), (const float*)l.slab.p);
+        else hipLaunchKernelGGL(k_bn_bwd_dx<true>, dim3(blocks), dim3(kBnThreads), 0, n->stream, x, dy, y, (float*)cl.dout.p, n4, C, (float)M, (const float*)bn_mean(l),
+                                (const float*)bn_invstd(l), (const float*)P(n, l.w_off), (const float*)l.slab.p);
+        XTRY(n, hipGetLastError());
+    }
+    return reduce_slab(n, i, 1, 1, ConvShape{B, 1, 1, 1, C}, grad, apply);
 }
 
 // the step's ONE reduction launch over the queued jobs, or the launches that stand for it (rcn_hipx_api_update.ipp)
@@ -590,14 +694,14 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             const int fuse_on = n->opt.fuse_pool_bwd;
             const Layer& cl = n->L[i - 1];
             const ConvShape cs{B, cl.H, cl.W, cl.Cin, cl.CoutP};
-            const bool fusable = fuse_on && wgrad_halo_runs(*n, cs, 3) && (i - 1 == 0 || conv_halo_runs(*n, ConvShape{B, cl.H, cl.W, cl.CoutP, cl.Cin}));
+            const bool fusable = fuse_on && cl.kind == RCN_HIPX_CONV3X3_RELU && wgrad_halo_runs(*n, cs, 3) && (i - 1 == 0 || conv_halo_runs(*n, ConvShape{B, cl.H, cl.W, cl.CoutP, cl.Cin}));
             if (fusable) {
                 pooled[i - 1] = PooledGrad{(const float*)l.dout.p, (const float*)l.out.p, (const uint8_t*)l.idx.p};
                 if (dry_note(n, "  pool-bwd %dx%dx%d: none (the convolution's gradient kernels unpool while staging)", l.H, l.W, l.Cin))
                     pooled[i - 1].dP = reinterpret_cast<const float*>(sizeof(float));      // (dry run: no buffers; any non-null marks "pooled")
                 continue;
             }
-            // gradient wrt the pool INPUT, with the preceding conv's ReLU mask folded in (pooled value > 0)
+            // gradient wrt the pool INPUT, with the preceding conv's (or batch normalisation's) ReLU mask folded in (pooled value > 0)
             const long long tot = (long long)B * l.oH * l.oW * (l.Cin / 4);
             if (dry_note(n, "  pool-bwd %dx%dx%d: k_pool_bwd", l.H, l.W, l.Cin)) continue;
             if (n->store16) hipLaunchKernelGGL(k_pool_bwd<__bf16>, dim3(grid1d(tot, 256)), dim3(256), 0, n->stream, (const __bf16*)l.dout.p, (const __bf16*)l.out.p, (const uint8_t*)l.idx.p,
@@ -607,13 +711,18 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             XTRY(n, hipGetLastError());
             continue;
         }
-        const bool conv = l.kind == RCN_HIPX_CONV3X3_RELU;
+        if (l.kind == RCN_HIPX_BN_RELU) {
+            // its dout is gated by the pool's backward or by the convolution above (n->bw.gated); otherwise it gates itself
+            RTRY(launch_bn_backward(n, (size_t)i, B, l.pool_follows || gated[i], grad, apply));
+            continue;
+        }
+        const bool conv = is_conv(l.kind);
         const int ks = conv ? 3 : 1;
         const ConvShape s = conv ? ConvShape{B, l.H, l.W, l.Cin, l.CoutP} : ConvShape{B, 1, 1, l.K, l.CoutP};
         const long long M = (long long)s.N * s.H * s.W;
         // dZ: gradient wrt the pre-activation
         const float* dZ = (const float*)l.dout.p;
-        if (l.kind != RCN_HIPX_DENSE && !l.pool_follows && !gated[i]) {
+        if (l.kind != RCN_HIPX_DENSE && l.kind != RCN_HIPX_CONV3X3 && !l.pool_follows && !gated[i]) {
             if (stage16(n, i)) return fail(n, -3, kStoreGap);
             XTRY(n, scratch_ensure(n, n->dz, (size_t)M * l.CoutP * sizeof(float)));
             if (!dry_note(n, "  relu-bwd: k_relu_bwd")) {
@@ -633,7 +742,8 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             // the layer below is a ReLU layer feeding this one directly (no pool in between): gate the gradient with its output in
             // this kernel's epilogue, so that layer finds its dZ ready instead of running a k_relu_bwd pass over the tensor
             const Layer& below = n->L[i - 1];
-            const bool gate = below.kind == RCN_HIPX_CONV3X3_RELU || below.kind == RCN_HIPX_DENSE_RELU;
+            // (batch normalisation below a convolution: gated here with its output, the same out > 0 rule; below a dense layer it gates itself)
+            const bool gate = below.kind == RCN_HIPX_CONV3X3_RELU || below.kind == RCN_HIPX_DENSE_RELU || (below.kind == RCN_HIPX_BN_RELU && conv);
             RTRY(launch_conv(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, ConvShape{s.N, s.H, s.W, s.Cout, s.Cin}, ks, gate ? 3 : 0,
                              nullptr, pooled[i].dP ? &pooled[i] : nullptr, false, wb_of(n, l.wbb_off), Store{stage16(n, i), stage16(n, i - 1)}));
             gated[i - 1] = gate;
@@ -749,9 +859,9 @@ int launch_head(rcn_hipx_net* n, const int32_t* labels, int B, float* loss_dev, 
 int refresh_flipped(rcn_hipx_net* n) {
     for (size_t i = 1; i < n->L.size(); ++i) {
         const Layer& l = n->L[i];
-        if (l.kind == RCN_HIPX_MAXPOOL2) continue;
-        const int ks = l.kind == RCN_HIPX_CONV3X3_RELU ? 3 : 1;
-        const int cin = l.kind == RCN_HIPX_CONV3X3_RELU ? l.Cin : l.K;
+        if (!has_matrix(l.kind)) continue;
+        const int ks = is_conv(l.kind) ? 3 : 1;
+        const int cin = is_conv(l.kind) ? l.Cin : l.K;
         const long long wn = (long long)l.K * l.CoutP;
         hipLaunchKernelGGL(k_flip_weights, dim3(grid1d(wn, 256)), dim3(256), 0, n->stream, (const float*)P(n, l.w_off), (float*)n->wt.p + l.w_off, ks, cin, l.CoutP);
     }
@@ -763,6 +873,7 @@ int refresh_flipped(rcn_hipx_net* n) {
 // instead, which also does that layer's share of the backward pass (its slab is queued for the reduction).  *first: the layer the backward
 // walk starts at; *gated: its dout already holds dZ.
 int step_front(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, float* grad, bool apply, float* loss_dev, int* first, bool* gated, const Pair& pair = Pair{}) {
+    RTRY(bn_rows_ok(n, B));                                // (before the dropout tick and the operand copies: a refused step enqueues nothing)
     n->jobs.njobs = 0;
     if (dropout_on(*n)) RTRY(launch_dropout_tick(n));      // this forward's masks: the ordinal it leaves
     RTRY(prep_bf16_weights(n));
@@ -862,18 +973,21 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
     for (int i = 0; i < n_layers; ++i) {
         Layer l{};
         l.kind = layers[i].kind; l.H = H; l.W = W; l.Cin = C;
-        if (l.kind == RCN_HIPX_CONV3X3_RELU) {
+        if (is_conv(l.kind)) {
             if (flat) return fail(n, -2, "convolution after a dense layer");
             if (layers[i].out < 32 || layers[i].out % 32) return fail(n, -3, "conv output channels must be a positive multiple of 32");
             if (!(9 * C <= 32) && C % 32) return fail(n, -3, "conv input channels must be a multiple of 32 (or 9*Cin <= 32 for the first layer)");
             l.Cout = l.CoutP = layers[i].out; l.oH = H; l.oW = W; l.K = 9 * C;
             C = l.Cout;
         } else if (l.kind == RCN_HIPX_MAXPOOL2) {
-            if (flat || i == 0 || n->L.back().kind != RCN_HIPX_CONV3X3_RELU) return fail(n, -2, "max-pool must follow a convolution");
+            if (flat || i == 0 || (n->L.back().kind != RCN_HIPX_CONV3X3_RELU && n->L.back().kind != RCN_HIPX_BN_RELU)) return fail(n, -2, "max-pool must follow a convolution");
             if (H % 2 || W % 2) return fail(n, -3, "max-pool needs even height and width");
             l.Cout = l.CoutP = C; l.oH = H / 2; l.oW = W / 2; l.K = 0;
             n->L.back().pool_follows = true;
             H = l.oH; W = l.oW;
+        } else if (l.kind == RCN_HIPX_BN_RELU) {
+            if (i == 0 || n->L.back().kind != RCN_HIPX_CONV3X3) return fail(n, -2, "batch normalisation (RCN_HIPX_BN_RELU) must directly follow a RCN_HIPX_CONV3X3 layer");
+            l.Cout = l.CoutP = C; l.oH = H; l.oW = W; l.K = 1;      // [gamma | beta]: a [W | b] block with K = 1
         } else if (l.kind == RCN_HIPX_DENSE_RELU || l.kind == RCN_HIPX_DENSE) {
             const long long feat = flat ? C : (long long)H * W * C;
             if (feat % 32 || feat > 0x7fffffff) return fail(n, -3, "dense input features must be a multiple of 32");
@@ -883,6 +997,7 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
             l.K = (int)feat; l.H = 1; l.W = 1; l.Cin = (int)feat; l.Cout = layers[i].out; l.CoutP = (l.Cout + 31) / 32 * 32; l.oH = l.oW = 1;
             C = l.Cout; flat = true; H = W = 1;
         } else return fail(n, -1, "unknown layer kind");
+        if (l.kind != RCN_HIPX_BN_RELU && i > 0 && n->L.back().kind == RCN_HIPX_CONV3X3) return fail(n, -2, "a RCN_HIPX_CONV3X3 layer must be followed by RCN_HIPX_BN_RELU");
         if (l.kind != RCN_HIPX_MAXPOOL2) {
             l.w_off = n->n_pad; n->n_pad += (long long)l.K * l.CoutP; l.b_off = n->n_pad; n->n_pad += l.CoutP;
             l.lw_off = n->n_log; n->n_log += (long long)l.K * l.Cout; l.lb_off = n->n_log; n->n_log += l.Cout;
@@ -974,7 +1089,13 @@ int rcn_hipx_create(int device, int in_h, int in_w, int in_c, const rcn_hipx_lay
         XTRY(n, l.out.ensure(elems * sizeof(float)));
         XTRY(n, l.dout.ensure(elems * sizeof(float)));
         if (l.kind == RCN_HIPX_MAXPOOL2) XTRY(n, l.idx.ensure(elems));
+        if (l.kind == RCN_HIPX_BN_RELU) {
+            XTRY(n, l.bn.ensure((size_t)4 * l.CoutP * sizeof(float)));
+            XTRY(n, l.bn_part.ensure((size_t)bn_parts_cap((long long)max_batch * l.oH * l.oW) * 2 * l.CoutP * sizeof(double)));
+            XTRY(n, l.slab.ensure((size_t)2 * l.CoutP * sizeof(float)));
+        }
     }
+    RTRY(bn_reset_stats(n));
     XTRY(n, hipStreamSynchronize(n->stream));
     return 0;
 }
@@ -1096,6 +1217,7 @@ int rcn_hipx_init_params(rcn_hipx_net* n, uint64_t seed) {
     std::vector<float> flat((size_t)n->n_log, 0.f);
     for (const Layer& l : n->L) {
         if (l.kind == RCN_HIPX_MAXPOOL2) continue;
+        if (l.kind == RCN_HIPX_BN_RELU) { for (int c = 0; c < l.Cout; ++c) flat[l.lw_off + c] = 1.f; continue; }      // gamma = 1, beta = 0
         std::normal_distribution<float> nd(0.f, std::sqrt(2.0f / (float)l.K));
         for (long long i = 0; i < (long long)l.K * l.Cout; ++i) flat[l.lw_off + i] = nd(gen);
     }
@@ -1108,6 +1230,18 @@ int rcn_hipx_forward_dev(rcn_hipx_net* n, const float* x, int B, float* logits) 
     Dev g(n->device);
     RTRY(prep_bf16_weights(n));
     RTRY(forward(n, x, B));
+    const Layer& l = n->L.back();
+    XTRY(n, hipMemcpy2DAsync(logits, (size_t)n->classes * sizeof(float), l.out.p, (size_t)l.CoutP * sizeof(float), (size_t)n->classes * sizeof(float), (size_t)B,
+                             hipMemcpyDeviceToDevice, n->stream));
+    return 0;
+}
+
+// the B logits rows the LAST forward pass left in the last layer's output -- a training step's, a gradients call's or an evaluation's
+int rcn_hipx_last_logits_dev(rcn_hipx_net* n, int B, float* logits) {
+    if (!n || !logits) return -1;
+    RTRY(ensure_batch(n, B));
+    if (B != n->last_rows) return fail(n, -6, n->last_rows ? "last_logits: the last forward pass ran another batch size" : "last_logits: no forward pass has run yet");
+    Dev g(n->device);
     const Layer& l = n->L.back();
     XTRY(n, hipMemcpy2DAsync(logits, (size_t)n->classes * sizeof(float), l.out.p, (size_t)l.CoutP * sizeof(float), (size_t)n->classes * sizeof(float), (size_t)B,
                              hipMemcpyDeviceToDevice, n->stream));
@@ -1555,8 +1689,8 @@ int rcn_hipx_step_flops(const rcn_hipx_net* n, int B, double* flops) {
     double f = 0;
     for (size_t i = 0; i < n->L.size(); ++i) {
         const Layer& l = n->L[i];
-        if (l.kind == RCN_HIPX_MAXPOOL2) continue;
-        const double macs = (double)B * l.oH * l.oW * (double)l.K * l.Cout * (l.kind == RCN_HIPX_CONV3X3_RELU ? 1.0 : 1.0);
+        if (!has_matrix(l.kind)) continue;
+        const double macs = (double)B * l.oH * l.oW * (double)l.K * l.Cout * 1.0;
         f += 2.0 * macs * (i == 0 ? 2.0 : 3.0);         // forward + wgrad (+ dgrad except for the first layer)
     }
     *flops = f;
@@ -1695,3 +1829,4 @@ int rcn_hipx_plan_eval_metrics_net(const rcn_hipx_net* n, int batch, int n_topk,
 #include "rcn_hipx_api_update.ipp"
 #include "rcn_hipx_api_dropout.ipp"
 #include "rcn_hipx_api_state.ipp"
+#include "rcn_hipx_api_bn.ipp"
