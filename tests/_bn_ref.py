@@ -222,8 +222,10 @@ def close_per_tensor(got, ref, in_shape, layers, rtol, tag="", bias_at_weight_sc
         worst = max(worst, close(got[ws], ref[ws], rtol, f"{tag} layer {li} ({kinds[li]}) weights"))
         if li in bias_at_weight_scale:
             scale, d = max(1e-3, float(np.abs(ref[ws]).max())), float(np.abs(got[bs] - ref[bs]).max())
-            print(f"{tag} layer {li} ({kinds[li]}) biases: max |d| = {d:.3e} at the weights' scale = {scale:.3e} (own: {float(np.abs(ref[bs]).max()):.3e}) rtol = {rtol}")
+            print(f"{tag} layer {li} ({kinds[li]}) biases: max |d| = {d:.3e} at the weights' scale = {scale:.3e} (own: {float(np.abs(ref[bs]).max()):.3e}) rtol = {rtol} "
+                  f"used = {d / (rtol * scale + 1e-6):.3f}")
             assert d <= rtol * scale + 1e-6, (tag, li, d, scale, rtol)
+            worst = max(worst, d / (rtol * scale + 1e-6))
         else:
             worst = max(worst, close(got[bs], ref[bs], rtol, f"{tag} layer {li} ({kinds[li]}) biases"))
     return worst
