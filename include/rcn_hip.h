@@ -368,7 +368,10 @@ const char* rcn_hip_last_timeout_text(const rcn_hip_ctx* ctx);
  *   "feat_waves"          RCN_HIP_FEAT_WAVES          1 | 2     waves per picture in k_features_cpcp (measured neutral; 1)
  *   "no_fragimg"          RCN_HIP_NO_FRAGIMG          0 | 1     k_p2_b gathers its tail parameters itself (0)
  *   "exact_div_only"      RCN_HIP_EXACT_DIV_ONLY      0 | 1     the f32 standardisation always divides (0)
- *   "pack_segment_bytes"  RCN_HIP_PACK_SEGMENT_BYTES  >= 1      one half of the epoch image (64 MiB) */
+ *   "pack_segment_bytes"  RCN_HIP_PACK_SEGMENT_BYTES  >= 1      one half of the epoch image (64 MiB)
+ *   "pack_form"           RCN_HIP_PACK_FORM           0 | 1     which kernel gathers the epoch image: 1 k_pack_rows (whole rows per workgroup, every row index
+ *                                                               loaded once ahead of the rows, loads in groups before stores: 16.9 us per 64 batches of 256
+ *                                                               against 22.0), 0 k_pack_epoch; the image is the same byte for byte (1) */
 int  rcn_hip_set_option(rcn_hip_ctx* ctx, const char* name, int64_t value);
 int  rcn_hip_get_option(const rcn_hip_ctx* ctx, const char* name, int64_t* value);
 /* Which kernel implements flatten_feature_set: 0 = automatic (the fused conv+pool kernel specialised for the default

@@ -275,6 +275,133 @@ __global__ __launch_bounds__(256) void k_pack_epoch(const T* __restrict__ X, con
     }
 }
 
+// ---- the same image from whole rows, without load chains (option "pack_form" = 1, the default) -------------------------------------
+// k_pack_epoch above cuts every row into 128-byte runs OF THE ROW: a 784-float row is 24.5 lines long, so on every odd row such a run
+// straddles two lines of memory, and the neighbouring workgroup -- on another XCD, behind another L2 -- fetches both of them again.  It
+// also pays two dependent round trips per 16-byte piece (index, then the piece through it).  Measured (profiles/pack_ab.txt): removing
+// the chains alone, in that shape, gains nothing (23.0 us against 22.0 per 64 batches of 256); reading whole rows does (16.9 us, the rate
+// of a streamed copy).  So here a workgroup reads kPackRows gathered rows of one batch IN FULL and writes them as G runs of
+// kPackRows x 16 elements, with those samples' targets.  A thread loads its row index once, ahead of everything else, and moves pieces in
+// groups: every load of a group is issued before the group's first store.  No barrier, no LDS, no inter-workgroup communication.
+//
+// A "piece" is one vec4 (4 features); piece pi of sample s goes to slice pi / 4, group pi % 4 of the image.  Pieces past F are zeros.
+constexpr int kPackLanes = 8;           // lanes that share one row: 8 pieces = one 128-byte line (f32) per wave-instruction and row
+constexpr int kPackRows = 256 / kPackLanes;   // rows per workgroup
+constexpr int kPackDepth = 9;           // pieces a thread keeps in flight: 9 x 16 B x 256 threads x 2 workgroups per CU = 72 KiB (5, 9 and 13
+                                        // measured the same: the kernel runs at the copy rate, not at a latency)
+inline int pack_rows_grid_x(size_t B) { return (int)((B + kPackRows - 1) / kPackRows); }
+
+// an edge piece: clamped into the row, so that the load is unconditional; what lies past F is zeroed at the store
+template <typename T, bool VECX>
+__device__ __forceinline__ typename Vec4<T>::type pack_load_piece(const T* __restrict__ row, int pi, int F) {
+    using vec4 = typename Vec4<T>::type;
+    if (VECX) {                                            // F % 4 == 0: whole pieces only
+        const int last = F / 4 - 1, pc = pi < 0 ? 0 : (pi > last ? last : pi);
+        return *reinterpret_cast<const vec4*>(row + 4 * (long long)pc);
+    }
+    vec4 v;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int f = 4 * pi + i;
+        v[i] = row[f < 0 ? 0 : (f < F ? f : F - 1)];
+    }
+    return v;
+}
+template <typename T>
+__device__ __forceinline__ void pack_store_piece(T* __restrict__ dst, typename Vec4<T>::type v, int pi, int F) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (4 * pi + i >= F) v[i] = (T)0;
+    *reinterpret_cast<typename Vec4<T>::type*>(dst) = v;
+}
+
+// A group is N loads followed by N stores with NO condition on either: behind a conditional store the compiler sinks the load into the
+// store's block, next to its wait, and the group becomes a chain again.  So the kernel runs whole groups of kPackDepth and hands what is
+// left (fewer, uniform over the grid) to PackTail, which picks the group of exactly that size.
+// N pieces pb, pb + 8, ... of one row, every one WHOLLY inside the row (no clamp, no zero fill): one base and constant offsets on the
+// loads, one stride (two slices) on the stores.
+template <typename T, bool VECX, int N>
+__device__ __forceinline__ void pack_row_group(const T* __restrict__ row, T* __restrict__ dst, int pb, int B) {
+    using vec4 = typename Vec4<T>::type;
+    vec4 v[N];
+    const T* __restrict__ p = row + 4 * (long long)pb;
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        if (VECX) v[u] = *reinterpret_cast<const vec4*>(p + 4 * kPackLanes * u);
+        else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[u][i] = p[4 * kPackLanes * u + i];
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);                     // the scheduler otherwise moves the first store (and its wait) up between the loads
+    T* __restrict__ d = dst + (size_t)(pb >> 2) * B * 16 + 4 * (pb & 3);
+    const size_t step = (size_t)(kPackLanes / 4) * B * 16;
+#pragma unroll
+    for (int u = 0; u < N; ++u) *reinterpret_cast<vec4*>(d + u * step) = v[u];
+}
+template <typename T, bool VECX, int N>
+struct PackTail {
+    static __device__ __forceinline__ void run(int n, const T* __restrict__ row, T* __restrict__ dst, int pb, int B) {
+        if (n == N) pack_row_group<T, VECX, N>(row, dst, pb, B);
+        else PackTail<T, VECX, N - 1>::run(n, row, dst, pb, B);
+    }
+};
+template <typename T, bool VECX>
+struct PackTail<T, VECX, 0> {
+    static __device__ __forceinline__ void run(int, const T*, T*, int, int) {}
+};
+
+// Grid: (pack_rows_grid_x(B), nb), 256 threads.  Lane q of a row's eight takes pieces 8 k + q - shift, k = 0, 1, ..., where shift is where
+// the row starts inside its line: the eight lanes then read one ALIGNED line whatever the row's parity (in the bench loop 0.015 us per
+// step better than shift = 0, three runs of three; the kernel's own time is the same).  perm == NULL: identity.
+template <typename T, bool VECX>
+__global__ __launch_bounds__(256) void k_pack_rows(const T* __restrict__ X, const T* __restrict__ Y, const int* __restrict__ perm,
+                                                   int B, int F, int C, int G, T* __restrict__ Xs, T* __restrict__ Ys) {
+    using vec4 = typename Vec4<T>::type;
+    const int j = blockIdx.y, q = threadIdx.x & (kPackLanes - 1);
+    const int s = (int)blockIdx.x * kPackRows + ((int)threadIdx.x / kPackLanes);
+    if (s >= B) return;
+    const long long r = perm ? (long long)perm[(size_t)j * B + s] : (long long)j * B + s;
+    const T* __restrict__ row = X + r * (long long)F;
+    const T* __restrict__ yrow = Y + r * (long long)C;
+    T* __restrict__ ydst = Ys + ((size_t)j * B + s) * C;
+    T t[4];                                                // the first 32 targets of the row ride with the first pieces
+#pragma unroll
+    for (int u = 0; u < 4; ++u) t[u] = yrow[q + 8 * u < C ? q + 8 * u : C - 1];
+
+    const int nv = 4 * G;
+    const int shift = VECX ? (int)((reinterpret_cast<uintptr_t>(row) / sizeof(vec4)) & (kPackLanes - 1)) : 0;
+    T* __restrict__ dst = Xs + ((size_t)j * G * B + s) * 16;
+    // steps 1 .. kfull have all eight lanes wholly inside the row for every shift; step 0 and the three behind kfull are the row's
+    // edges, where a lane may have no piece, a partial one or one of zeros: their loads are issued here, ahead of the groups, and stored
+    // behind them (the groups' loop between the two is also what keeps the compiler from sinking these loads into the stores' blocks)
+    const int nf = F / 4, kfull = nf >= kPackLanes ? (nf - kPackLanes) / kPackLanes : 0;
+    constexpr int kEdges = 4;
+    vec4 e[kEdges];
+    int epi[kEdges];
+#pragma unroll
+    for (int u = 0; u < kEdges; ++u) {
+        epi[u] = kPackLanes * (u == 0 ? 0 : kfull + u) + q - shift;
+        e[u] = pack_load_piece<T, VECX>(row, epi[u], F);
+    }
+    int k = 1;
+    for (; k + kPackDepth <= kfull + 1; k += kPackDepth) pack_row_group<T, VECX, kPackDepth>(row, dst, kPackLanes * k + q - shift, B);
+    PackTail<T, VECX, kPackDepth - 1>::run(kfull + 1 - k, row, dst, kPackLanes * k + q - shift, B);
+#pragma unroll
+    for (int u = 0; u < kEdges; ++u)
+        if (epi[u] >= 0 && epi[u] < nv) pack_store_piece<T>(dst + (size_t)(epi[u] >> 2) * B * 16 + 4 * (epi[u] & 3), e[u], epi[u], F);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+        if (q + 8 * u < C) ydst[q + 8 * u] = t[u];
+    for (int m0 = q + 32; m0 < C; m0 += 32) {              // more than 32 classes: the rest, four loads then four stores at a time
+#pragma unroll
+        for (int u = 0; u < 4; ++u) t[u] = yrow[m0 + 8 * u < C ? m0 + 8 * u : C - 1];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (m0 + 8 * u < C) ydst[m0 + 8 * u] = t[u];
+    }
+}
+
 // One workgroup per 8 samples.  Ys: this batch's targets, packed [sample][classes].
 // (f32: sigmoid_fast -- v_exp_f32 / v_rcp_f32, ~1e-7 relative, inside the 2e-6 activation tolerance and what k_p2_b uses; the
 // libm-grade expf and the IEEE division of sigmoid_ref cost ~60 instructions per value, and the waves that evaluate it run alone on

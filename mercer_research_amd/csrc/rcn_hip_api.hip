@@ -85,6 +85,7 @@ struct CtxOptions {
     long long no_fragimg = 0;           // "no_fragimg"        RCN_HIP_NO_FRAGIMG     1: k_p2_b gathers its tail parameters itself
     long long exact_div_only = 0;       // "exact_div_only"    RCN_HIP_EXACT_DIV_ONLY 1: the f32 standardisation always divides
     long long pack_segment_bytes = (long long)64 << 20;   // "pack_segment_bytes" RCN_HIP_PACK_SEGMENT_BYTES  one half of the epoch image
+    long long pack_form = 1;            // "pack_form"         RCN_HIP_PACK_FORM      1: the epoch image is gathered by k_pack_rows (whole rows, no load chains); 0: by k_pack_epoch
 };
 
 namespace {
@@ -109,6 +110,7 @@ const OptDesc kOptTable[] = {
     {"no_fragimg", "RCN_HIP_NO_FRAGIMG", &CtxOptions::no_fragimg, 0, 1},
     {"exact_div_only", "RCN_HIP_EXACT_DIV_ONLY", &CtxOptions::exact_div_only, 0, 1},
     {"pack_segment_bytes", "RCN_HIP_PACK_SEGMENT_BYTES", &CtxOptions::pack_segment_bytes, 1, 1LL << 40},
+    {"pack_form", "RCN_HIP_PACK_FORM", &CtxOptions::pack_form, 0, 1},
 };
 }  // namespace
 

@@ -161,7 +161,7 @@ size_t pack_segment(const rcn_hip_ctx* c, size_t B) {
     return seg ? seg : 1;
 }
 
-// batches [j0, j0+n) of the call -> slice-major image (k_pack_epoch) in half `half` of the context-owned scratch
+// batches [j0, j0+n) of the call -> slice-major image (k_pack_rows; k_pack_epoch with option pack_form = 0) in half `half` of the context-owned scratch
 template <typename T>
 int launch_pack(rcn_hip_ctx* c, const void* X, const void* Y, const int32_t* perm, size_t B, size_t j0, size_t n, int half, size_t seg) {
     const NetDesc& nd = c->nd;
@@ -174,8 +174,10 @@ int launch_pack(rcn_hip_ctx* c, const void* X, const void* Y, const int32_t* per
     const int32_t* pb = perm ? perm + j0 * B : nullptr;
     T* xs = (T*)c->xpack.p + (size_t)half * seg * G * B * 16;
     T* ys = (T*)c->ypack.p + (size_t)half * seg * B * Cc;
-    if (vec) hipLaunchKernelGGL((k_pack_epoch<T, true>), dim3(pack_grid_x(G), (unsigned)n), dim3(256), 0, c->stream, Xb, Yb, pb, (int)B, F, Cc, G, xs, ys);
-    else hipLaunchKernelGGL((k_pack_epoch<T, false>), dim3(pack_grid_x(G), (unsigned)n), dim3(256), 0, c->stream, Xb, Yb, pb, (int)B, F, Cc, G, xs, ys);
+#define RCN_PACK(KERN, GX) hipLaunchKernelGGL((KERN), dim3((unsigned)(GX), (unsigned)n), dim3(256), 0, c->stream, Xb, Yb, pb, (int)B, F, Cc, G, xs, ys)
+    if (c->opt.pack_form == 0) { if (vec) RCN_PACK((k_pack_epoch<T, true>), pack_grid_x(G)); else RCN_PACK((k_pack_epoch<T, false>), pack_grid_x(G)); }
+    else { if (vec) RCN_PACK((k_pack_rows<T, true>), pack_rows_grid_x(B)); else RCN_PACK((k_pack_rows<T, false>), pack_rows_grid_x(B)); }
+#undef RCN_PACK
     HIP_TRY(c, hipGetLastError());
     if (half == 0) { c->packed_B = B; c->packed_nb = n; }
     c->epoch_nb = 0;                        // whatever epoch rcn_hip_epoch_begin_dev had laid out is overwritten
