@@ -259,6 +259,25 @@ __device__ inline unsigned long long xcd_missing(unsigned long long lanes, int f
     for (; lanes; lanes &= lanes - 1ull) missing |= 1ull << (first + __builtin_ctzll(lanes) * stride);
     return missing;
 }
+// The step-top wait of a sample group that names BOTH tables in one xcd_wait (kOneTopWait: f0 = flagA, n0 = NA; f1 = flagT, n1 = NT):
+// the lanes below na polled slab producers, the lanes na .. na + nt - 1 tail tiles.  The time-out record has one site and one producer
+// mask: a slab part that is missing names the slab site (also when a tail tile is missing too -- a lost feature worker stalls the
+// tail tiles behind it, so it is the one to name), else the tail site with the mask counted from tail tile 0.
+struct XcdTopMiss { unsigned site; unsigned long long producers; };
+__host__ __device__ constexpr XcdTopMiss xcd_top_missing(unsigned long long lanes, int na, int nt) {
+    const unsigned long long slab = lanes & ((1ull << na) - 1ull), tail = (lanes >> na) & ((1ull << nt) - 1ull);
+    return slab != 0ull ? XcdTopMiss{kXcdSiteSlabFlag, slab} : XcdTopMiss{kXcdSiteTailFlag, tail};
+}
+// (the bench net 784-30-10: NA = 25, NT = 3; the reference's test net 784-10-10-10: NT = 3; the largest two-hidden-layer net: NT = 6)
+static_assert(xcd_top_missing(0x2ull, 25, 3).site == kXcdSiteSlabFlag && xcd_top_missing(0x2ull, 25, 3).producers == 0x2ull, "only a slab part missing");
+static_assert(xcd_top_missing(5ull << 25, 25, 3).site == kXcdSiteTailFlag && xcd_top_missing(5ull << 25, 25, 3).producers == 0x5ull, "only tail tiles missing, NT = 3");
+static_assert(xcd_top_missing((4ull << 25) | 0x1000002ull, 25, 3).site == kXcdSiteSlabFlag && xcd_top_missing((4ull << 25) | 0x1000002ull, 25, 3).producers == 0x1000002ull,
+              "both missing: the slab site, the slab producers only");
+static_assert(xcd_top_missing(0x21ull << 25, 25, 6).site == kXcdSiteTailFlag && xcd_top_missing(0x21ull << 25, 25, 6).producers == 0x21ull, "tail tiles 0 and 5 of NT = 6");
+static_assert(xcd_top_missing(0x3full << 2, 2, 6).site == kXcdSiteTailFlag && xcd_top_missing(0x3full << 2, 2, 6).producers == 0x3full, "every tail tile of NT = 6 behind NA = 2");
+static_assert(xcd_top_missing((1ull << 31) | 1ull, 29, 3).site == kXcdSiteSlabFlag && xcd_top_missing((1ull << 31) | 1ull, 29, 3).producers == 1ull, "NA = 29: the last tail lane is lane 31");
+static_assert(xcd_top_missing(1ull << 28, 29, 3).site == kXcdSiteSlabFlag && xcd_top_missing(1ull << 29, 29, 3).site == kXcdSiteTailFlag &&
+              xcd_top_missing(1ull << 29, 29, 3).producers == 1ull, "the boundary between the two tables");
 
 // The closing round as ONE decision every worker reads the same way (round 4; before, every worker waited for all flagD under its own
 // clock, and a worker that arrived just after another had given up saw all flags set and wrote its slice: a torn parameter vector
@@ -423,6 +442,14 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
     constexpr bool kLateTargets = kLatePrefetch;
     // (gather form: the row indices a step ahead of the rows -- needs the late issue point, where a step's slack is)
     constexpr bool kGatherAhead = GA && kLatePrefetch;
+    // The step top of a sample group as ONE wait (both flag tables in one poll), with the image words fetched behind the step-top
+    // barrier (below).  The same forms as the late prefetch; every other form keeps its text, and so its registers.
+    // (RCN_AB_TWO_TOP_WAITS: diagnostic builds of tools/ab_variants.py only -- the two waits this is measured against.)
+#ifdef RCN_AB_TWO_TOP_WAITS
+    constexpr bool kOneTopWait = false;
+#else
+    constexpr bool kOneTopWait = kLatePrefetch;
+#endif
     static_assert(!PH || DP, "the phase clocks exist for the data-parallel form");
     constexpr int ES = (int)sizeof(T), VS = 4 * ES;                  // bytes of an element / of a quadruple in the L2 buffers
     constexpr int RI = sizeof(T) == 4 ? 1 : 4;                       // Mfma16<T>::row(lane, i) = row(lane, 0) + RI * i
@@ -770,6 +797,19 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
             T fr[L3 ? kP3BFrag : kP2BFrag];
             if (wave == 0) {
                 XSTAMP(0);
+                if constexpr (kOneTopWait) {
+                    // ONE poll for both tables.  A feature worker's wave 0 arrives here when its own flagA has just been stored: the
+                    // other slab parts are a tenth of a microsecond away and the tail flags two microseconds old, so either wait is over
+                    // on arrival -- and each still cost a full L2 round trip, one after the other, with the image words' round trip
+                    // between them (a poll ends in vmcnt(0), and a wave's loads return in order).  The image words are not loaded
+                    // here any more but behind the barrier below, behind this wave's slab loads.
+                    const unsigned long long mAT = xcd_wait(bufs.flagA, NA, bufs.flagT, NT, tag, timeout, bufs.errd);
+                    if (mAT != 0ull && lane == 0) {
+                        const XcdTopMiss miss = xcd_top_missing(mAT, NA, NT);
+                        s_abort = 1;
+                        xcd_raise(err, bufs.errd, 1u, miss.site, w, j, launch_id, miss.producers, tag, dp_rank, dp_world, xsel, NW);
+                    }
+                } else {
                 // the tail tiles finish well before the feature workers: their flags first, the 24 parameter words of the image
                 // fetched under the wait for the slab
                 const unsigned long long mT = xcd_wait(bufs.flagT, NT, nullptr, 0, tag, timeout, bufs.errd);
@@ -779,6 +819,7 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                 if ((mT | mA) != 0ull && lane == 0) {
                     s_abort = 1;
                     xcd_raise(err, bufs.errd, 1u, mT ? kXcdSiteTailFlag : kXcdSiteSlabFlag, w, j, launch_id, mT ? mT : mA, tag, dp_rank, dp_world, xsel, NW);
+                }
                 }
                 XSTAMP(1);
             } else if (wave == 6) {                                   // targets per accumulator element: no flag to wait for
@@ -808,9 +849,34 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                     const int p = wave + kP2BWaves * q;
                     t[q] = xcd_ld4<T>(r_slab, (int)((((size_t)w * NA + (p < NA ? p : wave)) * 64 + lane) * VS));
                 }
+                if constexpr (kOneTopWait) {
+                    // The image words, by wave 0 alone, BEHIND its own four slab loads: the slab sums wait for a count that leaves
+                    // these in flight; fr[] is first read behind the next barrier.  Ordering: they are still loaded, in program order,
+                    // after the wait that saw flagT (this wave's, in front of the barrier above), and they are consumed by this
+                    // group's MFMAs before its flagB of this step is stored (wave 0 drains in front of that store) -- a tail tile
+                    // writes the image of step j + 1 only when it has seen flagB of step j of EVERY group, so not under them.
+                    auto sum_slab = [&] {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+                            if (wave + kP2BWaves * q < NA) z += t[q];
+                    };
+                    if (wave == 0) {
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int q = 0; q < (L3 ? kP3BFrag : kP2BFrag); ++q) fr[q] = (q >= 20 && q < 24) ? (T)0 : xcd_ld1<T>(r_img, (q * 64 + lane) * ES);
+                        __builtin_amdgcn_sched_barrier(0);
+                        sum_slab();
+                        // (opaque: keeps the two copies of the sums apart.  Folded into one behind the join they wait with the other
+                        // waves' count, which on this wave is all but three of the image words.)
+                        asm volatile("" : "+v"(z));
+                    } else {
+                        sum_slab();
+                    }
+                } else {
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
                     if (wave + kP2BWaves * q < NA) z += t[q];
+                }
             }
             zred[wave * 64 + lane] = z;
             if (wave == 7) XSTAMP(2);
