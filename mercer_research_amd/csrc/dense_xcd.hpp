@@ -131,6 +131,15 @@ static_assert((size_t)2 * kXcdSl * 128 * 16 >= (size_t)kDenseWaves * kMtp * kRed
 #define XSTAMP(i) do { } while (0)
 #define XCLOCK(k) do { } while (0)
 #endif
+// (-DRCN_STAMPS_TAIL on top: the per-wave stamps 13..15 of the forward leave their places to three points of the sample group's tail --
+// 13 sums done, 14 a_1 in LDS, 15 delta_2 in LDS; tools/stamps_xcd.py reads them the same way when it is given --tail)
+#if defined(RCN_STAMPS) && defined(RCN_STAMPS_TAIL)
+#define XSTAMP_TAIL(i) XSTAMP(i)
+#define XSTAMP_FWD(i) do { } while (0)
+#else
+#define XSTAMP_TAIL(i) do { } while (0)
+#define XSTAMP_FWD(i) XSTAMP(i)
+#endif
 
 using xu4 = __attribute__((ext_vector_type(4))) unsigned;
 #define XCD_RSRC(ptr, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)(ptr), 0, (int)(bytes), 0x00020000)
@@ -147,6 +156,13 @@ template <> __device__ inline Vec4<double>::type xcd_ld4<double>(__amdgpu_buffer
     const xu4 v[2] = {__builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 16), __builtin_amdgcn_raw_buffer_load_b128(r, byte_off + 16, 0, 16)};
     Vec4<double>::type f;
     __builtin_memcpy(&f, v, 32);
+    return f;
+}
+// (f32: a word's read with the wave-uniform part of the address in the instruction's scalar offset -- one address register for many reads)
+__device__ inline float xcd_ld1_at(__amdgpu_buffer_rsrc_t r, int lane_off, int uniform_off) {
+    const unsigned v = __builtin_amdgcn_raw_buffer_load_b32(r, lane_off, uniform_off, 16);
+    float f;
+    __builtin_memcpy(&f, &v, 4);
     return f;
 }
 template <typename T> __device__ inline T xcd_ld1(__amdgpu_buffer_rsrc_t r, int byte_off);
@@ -449,6 +465,21 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
     constexpr bool kOneTopWait = false;
 #else
     constexpr bool kOneTopWait = kLatePrefetch;
+#endif
+    // The sample group's tail, wave 0's chain between the slab sums and flagB (all below).  The same forms again; every other form keeps
+    // its text.
+    // kTailCost: the group's share of the cost only where somebody reads it, and then right behind delta_2 instead of behind delta_1.
+    // kTailWordsByUse: the image words issued in the order of their first use (b_0, W_1, b_1, W_1^T, then the second layer's).
+    // (RCN_AB_NO_*: diagnostic builds of tools/ab_variants.py only -- one part off, to measure it on top of the others.)
+#ifdef RCN_AB_NO_TAIL_COST
+    constexpr bool kTailCost = false;
+#else
+    constexpr bool kTailCost = kLatePrefetch;
+#endif
+#ifdef RCN_AB_NO_WORDS_BY_USE
+    constexpr bool kTailWordsByUse = false;
+#else
+    constexpr bool kTailWordsByUse = kOneTopWait;
 #endif
     static_assert(!PH || DP, "the phase clocks exist for the data-parallel form");
     constexpr int ES = (int)sizeof(T), VS = 4 * ES;                  // bytes of an element / of a quadruple in the L2 buffers
@@ -840,8 +871,32 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
             }
             __syncthreads();
             if (s_abort) return;
-            // slab: this group's NA x 1 KB, contiguous; wave q sums producers q, q + 8, q + 16, q + 24 in that order
+            // the image words of wave 0 (kTailWordsByUse: in the order of their first use -- a wave's loads return in order)
+            auto image_words = [&] {
+                constexpr int NFR = L3 ? kP3BFrag : kP2BFrag;
+                if constexpr (kTailWordsByUse) {
+                    // (word q of every lane at lane * 4 + q * 256: the word in the scalar offset, ONE address register instead of one per word
+                    // kept across the whole step loop)
+                    auto word = [&](int q) { fr[q] = xcd_ld1_at(r_img, lane * ES, q * 64 * ES); };
+#pragma unroll
+                    for (int q = 24; q < 28; ++q) word(q);                  // b_0
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) word(q);                    // W_1
+#pragma unroll
+                    for (int q = 16; q < 20; ++q) word(q);                  // b_1
+#pragma unroll
+                    for (int q = 8; q < 16; ++q) word(q);                   // W_1^T
+#pragma unroll
+                    for (int q = 28; q < NFR; ++q) word(q);                 // two hidden layers: W_2, W_2^T, b_2
+#pragma unroll
+                    for (int q = 20; q < 24; ++q) fr[q] = (T)0;             // (the targets: from `frag`, below)
+                } else {
+#pragma unroll
+                    for (int q = 0; q < NFR; ++q) fr[q] = (q >= 20 && q < 24) ? (T)0 : xcd_ld1<T>(r_img, (q * 64 + lane) * ES);
+                }
+            };
             vec4 z = vec4{0, 0, 0, 0};
+            // slab: this group's NA x 1 KB, contiguous; wave q sums producers q, q + 8, q + 16, q + 24 in that order
             {
                 vec4 t[4];
 #pragma unroll
@@ -862,8 +917,7 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                     };
                     if (wave == 0) {
                         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int q = 0; q < (L3 ? kP3BFrag : kP2BFrag); ++q) fr[q] = (q >= 20 && q < 24) ? (T)0 : xcd_ld1<T>(r_img, (q * 64 + lane) * ES);
+                        image_words();
                         __builtin_amdgcn_sched_barrier(0);
                         sum_slab();
                         // (opaque: keeps the two copies of the sums apart.  Folded into one behind the join they wait with the other
@@ -895,6 +949,7 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                     const h2 zl = ((lo[0] + lo[1]) + (lo[2] + lo[3])) + ((lo[4] + lo[5]) + (lo[6] + lo[7]));
                     const h2 zh = ((hi[0] + hi[1]) + (hi[2] + hi[3])) + ((hi[4] + hi[5]) + (hi[6] + hi[7]));
                     z = vec4{zl[0], zl[1], zh[0], zh[1]};
+                    XSTAMP_TAIL(13);
                 }
 #pragma unroll
                 for (int q = 20; q < 24; ++q) fr[q] = frag[(q - 20) * 64 + lane];
@@ -910,6 +965,7 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                     }
                     *reinterpret_cast<vec4*>(bufs.a1 + (size_t)(s0 + s) * kP2H + h0) = a;
                 }
+                XSTAMP_TAIL(14);
                 // z_2 = W_1 a_1 + b_1, a_2 = sigmoid, delta_2 = (a_2 - y) (*) a_2 (1 - a_2)                          rcn.rs:287-289, 299
                 acc_t acc = acc_t{0, 0, 0, 0};
                 {
@@ -920,6 +976,13 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                     for (int ks = 0; ks < 8; ++ks) acc = Mfma16<T>::mfma(fr[ks], n < kP2Ts ? bv[ks] : (T)0, acc);      // (as two interleaved chains: 6.48 vs 6.49 us, nothing)
                 }
                 T lsum = 0;
+                // The group's share of the cost.  It is read by wave 0 of the first tail tile, and only where a cost is asked for or
+                // exchanged (below: loss_dev || DP) -- kTailCost: not computed otherwise (a plain epoch loop passes no cost buffer).
+                [[maybe_unused]] const bool want_cost = loss_dev != nullptr || DP;
+                auto cost_share = [&] {
+                    lsum = wave_sum_lane0(lsum);
+                    if (lane == 0) bufs.loss[w] = lsum;
+                };
                 acc_t dv;
                 if constexpr (!L3) {
 #pragma unroll
@@ -980,6 +1043,7 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                         d2s[h2 * kLd + n] = dv[i];
                     }
                 }
+                XSTAMP_TAIL(15);
                 if (n < kP2Ts) store4<T>(bufs.d2 + (size_t)(s0 + n) * kP2C, lane, dv);
                 // delta_1 = (W_1^T delta_2) (*) a_1 (1 - a_1)                                                          rcn.rs:305-309
                 {
@@ -990,6 +1054,7 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                     for (int t = 0; t < kMtp; ++t)
 #pragma unroll
                         for (int i = 0; i < 4; ++i) av[t][i] = a1s[(t * 16 + Mfma16<T>::row(lane, i)) * kLd + (n & 7)];
+                    if constexpr (kTailCost) { if (want_cost) cost_share(); }       // (`diff` is final behind delta_2: beside the LDS reads above, not behind the MFMAs)
 #pragma unroll
                     for (int t = 0; t < kMtp; ++t) {
                         acc_t ad = acc_t{0, 0, 0, 0};
@@ -1001,8 +1066,7 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                         if (n < kP2Ts) store4<T>(bufs.d1 + (size_t)(s0 + n) * kP2H + t * 16, lane, o);
                     }
                 }
-                lsum = wave_sum_lane0(lsum);
-                if (lane == 0) bufs.loss[w] = lsum;
+                if constexpr (!kTailCost) cost_share();
                 XSTAMP(4);
                 xcd_drain();                                              // only this wave stored
                 if (lane == 0) xcd_flag(bufs.flagB + w * kXcdFlagStride, tag);
@@ -1210,9 +1274,9 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                     forward(j + 1, nothing);
                 }
                 if (wave == 1) XSTAMP(11);
-                if (wave == 0) XSTAMP(13);
-                if (wave == 4) XSTAMP(14);
-                if (wave == 7) XSTAMP(15);
+                if (wave == 0) XSTAMP_FWD(13);
+                if (wave == 4) XSTAMP_FWD(14);
+                if (wave == 7) XSTAMP_FWD(15);
                 __syncthreads();
                 if (tid == 0) xcd_flag(bufs.flagA + w * kXcdFlagStride, tag + 1);
                 if (wave == 0) XSTAMP(12);

@@ -1,14 +1,21 @@
 #!/usr/bin/env python3
 """Diagnostic only: -DRCN_STAMPS build, a few 64-step launches of the resident one-XCD kernel (dense path 5), then where each worker
-was at each point of the launch's last-but-one step (100 MHz ticks -> us relative to the earliest stamp of that step)."""
+was at each point of the launch's last-but-one step (100 MHz ticks -> us relative to the earliest stamp of that step).
+--tail: built with -DRCN_STAMPS_TAIL as well -- the per-wave stamps 13..15 are then three points of the sample group's tail on wave 0
+(sums done, a_1 in LDS, delta_2 in LDS) instead of the forward's.  STAMPS_LIB=<path>: a library built that way beforehand."""
 import ctypes as C, os, subprocess, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from mercer_research_amd import build as hb, _lib
+TAIL = "--tail" in sys.argv[1:]
+PREBUILT = os.environ.get("STAMPS_LIB")
 out = os.path.join(ROOT, "gpurun_out", "librcn_hip_stamps.so")
-os.makedirs(os.path.dirname(out), exist_ok=True)
-subprocess.run([hb.hipcc()] + hb.FLAGS + ["-w", "-DRCN_STAMPS", "-o", out, os.path.join(hb.CSRC, "rcn_hip_api.hip")], check=True)
+if PREBUILT:
+    out = PREBUILT
+else:
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    subprocess.run([hb.hipcc()] + hb.FLAGS + ["-w", "-DRCN_STAMPS"] + (["-DRCN_STAMPS_TAIL"] if TAIL else []) + ["-o", out, os.path.join(hb.CSRC, "rcn_hip_api.hip")], check=True)
 _lib.LIB_PATH = out
 import torch
 from mercer_research_amd.device import DeviceRCN
@@ -44,6 +51,8 @@ rel = np.where(r > 0, (r - t0) / 100.0, np.nan)
 names = ["0 step top", "1 slab+tail flags seen", "2 slab part sums in LDS (wave 7)", "3 past barrier (wave 0)", "4 tail done", "5 flagB stored", "6 flagB seen (wave 1: its own groups)",
          "7 wave 1's delta_1 rows in LDS", "8 past staging barrier", "9 gradient MFMAs done, slice updated", "10 past barrier behind the update", "11 forward stored, batch moved in, drained",
          "12 flagA / flagT stored", "13 forward done wave 0", "14 forward done wave 4", "15 forward done wave 7"]
+if TAIL:
+    names[13:16] = ["13 slab sums done (wave 0)", "14 a_1 in LDS (wave 0)", "15 delta_2 in LDS (wave 0)"]
 np.set_printoptions(linewidth=200, precision=2, suppress=True)
 for i, nme in enumerate(names):
     col = rel[:, i]
