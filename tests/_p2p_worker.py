@@ -1,5 +1,5 @@
-"""Worker of the multi-process peer-exchange tests (test_gpu_parity.test_peer_allreduce_two_processes_one_gpu and
-test_gpu_round2): one data-parallel rank.  Run as
+"""Worker of the multi-process peer-exchange tests (test_gpu_parity.test_peer_allreduce_two_processes_one_gpu, test_gpu_round2,
+test_gpu_round3 and test_gpu_round4, all through tests/_rcn_util.py's spawn_ranks): one data-parallel rank.  Run as
     python tests/_p2p_worker.py <rank> <world> <port> <dtype> <outdir> [case]
 ranks share GPU 0 (the dev box has one), which exercises the whole protocol -- hipIpc export/attach, flags, double buffering,
 rank-order sums, the admission votes -- except the cross-device memory path itself (that is what rcn_hip_dp_init's known-answer

@@ -174,3 +174,84 @@ def test_unsupported_shapes_are_rejected():
         make_net(((7, 8, 3), (("conv", 32), ("pool",), ("dense", 10)), 4), precision=None)   # odd height under the pool
     with pytest.raises(ConvNetError):
         make_net(((8, 8, 3), (("conv", 32), ("pool",), ("dense_relu", 32)), 4), precision=None)   # no logits layer
+
+
+# ---- kernel-selection knobs are per net; the backward pass in buckets ---------------------------------------------------------------------
+
+def test_trackx_options_are_per_net_and_the_plan_of_a_net_is_its_own(monkeypatch):
+    """RCN_HIPX_BF16_1CB / _PIPE / RCN_HIPX_HALO were read into function-local statics at first use: frozen process-wide, and rcn_hipx_plan
+    reported whatever the first call had latched.  Now fields of the net (rcn_hipx_set_option), seeded from the environment at creation:
+    two nets of ONE process run different kernels for the same layer, each net's plan (rcn_hipx_plan_net) names the kernels that net
+    runs, and the two forms of the same arithmetic agree."""
+    import torch
+    from mercer_research_amd.convnet import ConvNet, ConvNetError
+    in_shape, layers, B = (16, 16, 3), (("conv", 32), ("conv", 32), ("pool",), ("dense_relu", 64), ("dense", 10)), 32
+    a = ConvNet(in_shape, layers, B)
+    monkeypatch.setenv("RCN_HIPX_BF16_1CB", "0")                        # seeds only nets created from here on
+    b = ConvNet(in_shape, layers, B)
+    monkeypatch.delenv("RCN_HIPX_BF16_1CB")
+    assert a.get_option("bf16_1cb") == 1 and b.get_option("bf16_1cb") == 0
+    with pytest.raises(ConvNetError):
+        a.set_option("no_such_option", 1)
+    with pytest.raises(ConvNetError):
+        a.set_option("halo", 2)
+    rng = np.random.default_rng(3)
+    x = rng.standard_normal((B,) + in_shape).astype(np.float32)
+    y = rng.integers(0, 10, B).astype(np.int32)
+    outs = []
+    for net in (a, b):
+        net.init_params(7)
+        net.set_precision("bf16")
+        plan = net.plan_of_this_net(B)
+        outs.append(plan)
+        xd, yd = net.to_device(x), net.to_device(y)
+        loss = torch.zeros(1, dtype=torch.float32, device=net.device)
+        for _ in range(3):
+            net.train_step(xd, yd, 0.01, loss)
+        net.synchronize()
+        outs.append((float(loss.item()), net.get_params()))
+    assert "k_conv3x3_halo_bf16_1cb" in outs[0] and "k_conv3x3_halo_bf16_1cb" not in outs[2] and "k_conv3x3_halo_bf16p" in outs[2], (outs[0], outs[2])
+    assert abs(outs[1][0] - outs[3][0]) <= 1e-3 * abs(outs[1][0])
+    assert np.allclose(outs[1][1], outs[3][1], rtol=2e-2, atol=2e-3)
+    b.set_option("bf16_1cb", 1)                                         # settable afterwards, per net; the plan follows
+    assert "k_conv3x3_halo_bf16_1cb" in b.plan_of_this_net(B)
+    a.close(); b.close()
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16", "bf16_stored"])
+def test_trackx_bucketed_gradients_are_the_gradients_bit_for_bit(precision):
+    """rcn_hipx_gradients_begin_dev / _bucket_dev: the backward pass as a resumable walk that stops after every bucket of layers and runs
+    that bucket's slab reduction, so that a data-parallel step can all-reduce the slice while the layers below still run.  Same kernels,
+    same sums: for every bucket size the flat gradient and the loss equal rcn_hipx_gradients_dev's bit for bit, the slices arrive from
+    the top of the buffer down and cover it exactly once, and a slice is already final when its callback runs."""
+    import torch
+    from mercer_research_amd.convnet import ConvNet
+    in_shape, layers, B = (16, 16, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 128), ("dense", 10)), 64
+    net = ConvNet(in_shape, layers, B)
+    net.init_params(5)
+    net.set_precision(precision)
+    rng = np.random.default_rng(11)
+    x = net.to_device(rng.standard_normal((B,) + in_shape).astype(np.float32))
+    y = net.to_device(rng.integers(0, 10, B).astype(np.int32))
+    loss0 = torch.zeros(1, dtype=torch.float32, device=net.device)
+    ref = net.gradients(x, y, None, loss0)
+    net.synchronize()
+    ref_h, l0 = ref.cpu().numpy().copy(), float(loss0.item())
+    for min_bytes in (0, 64 << 10, 1 << 30):
+        grad = torch.full((net.n_padded,), float("nan"), dtype=torch.float32, device=net.device)
+        loss = torch.zeros(1, dtype=torch.float32, device=net.device)
+        seen = []
+
+        def on_bucket(piece, k, n):
+            net.synchronize()                                           # (a test may; a step records an event instead)
+            off = piece.storage_offset()
+            seen.append((k, n, off, piece.numel()))
+            assert np.array_equal(piece.cpu().numpy(), ref_h[off:off + piece.numel()]), (min_bytes, k)
+        net.gradients_bucketed(x, y, grad, loss, min_bytes, on_bucket)
+        net.synchronize()
+        assert np.array_equal(grad.cpu().numpy(), ref_h) and float(loss.item()) == l0
+        assert [s[0] for s in seen] == list(range(seen[0][1]))
+        assert seen[-1][2] == 0 and seen[0][2] + seen[0][3] == net.n_padded
+        assert all(seen[i][2] == seen[i + 1][2] + seen[i + 1][3] for i in range(len(seen) - 1))
+        assert (len(seen) == 1) if min_bytes == 1 << 30 else (len(seen) == 4 if min_bytes == 0 else len(seen) >= 2)
+    net.close()

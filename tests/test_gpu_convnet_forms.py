@@ -10,7 +10,7 @@ proves on the CPU that each case reaches the forms it names):
   C  forms only an option selects, each against the oracle in its mode; where the option changes the schedule alone, bit for bit too.
 Tolerances are the project's: fp32 vs f64 2e-4 of scale + 1e-6 (4e-4 after a second step; tests/test_gpu_convnet.py); bf16 operands vs the
 oracle with the same operand rounding 5e-3 (2e-2 after two steps); bf16 storage vs the oracle with the storage rounding mirrored 5e-3
-(2e-2 after two steps; tests/test_gpu_round4.py).  In every mode the gradient and the parameters after one step are held tensor by
+(2e-2 after two steps; tests/test_gpu_convnet_bf16_stored.py).  In every mode the gradient and the parameters after one step are held tensor by
 tensor, each layer's weights and each layer's biases at their own scale (close_per_tensor).  A parameter vector after ONE step is held
 at the gradient's tolerance: it is the parameters (exact) minus LR times a gradient within that tolerance; so is that step's displacement
 (check_oracle)."""

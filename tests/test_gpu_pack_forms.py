@@ -22,16 +22,14 @@ The cases are the smallest at which the new kernel can go wrong:
 One more case does not rest on k_pack_epoch being right: pack_form = 1 against the gather form of the resident kernel (xcd_gather = 1),
 which never runs a pack kernel.
 """
-import numpy as np
 import pytest
+from _rcn_util import F32, F64, FEATURE_NETS, Pair, cached_pairs, feature_net, same_bits
 
 pytestmark = pytest.mark.gpu
 
-NETS = {"784-30-10": dict(input_shape=(28, 28), convpool="default", F=784, path=0),
-        "36-30-10": dict(input_shape=(6, 6), convpool="one", F=36, path=0),
-        "100-30-10": dict(input_shape=(10, 10), convpool="one", F=100, path=0),
-        "784-30-10/unaligned": dict(input_shape=(28, 28), convpool="default", F=784, path=0, unaligned=True),
-        "36-30-10/unaligned": dict(input_shape=(6, 6), convpool="one", F=36, path=0, unaligned=True)}
+NETS = dict(FEATURE_NETS, **{"100-30-10": feature_net((10, 10), "one", 100)})
+NETS.update({f"{net}/unaligned": dict(NETS[net], unaligned=True) for net in ("784-30-10", "36-30-10")})
+DTYPES = {"f32": F32, "f64": F64}
 #        net          dtype  B    index       what
 CASES = [("784-30-10", "f32", 256, "shuffled", "3steps"),
          ("784-30-10", "f32", 256, "offset", "1step"),
@@ -60,107 +58,19 @@ CASES = [("784-30-10", "f32", 256, "shuffled", "3steps"),
          ("784-30-10", "f64", 10, "shuffled", "3steps"),
          ("784-30-10", "f64", 100, "stored", "3steps"),
          ("784-30-10", "f64", 100, "shuffled", "5steps-2seg")]
-STEPS = {"1step": 1, "3steps": 3, "5steps-2seg": 5, "begin": 3}
 
 
-def _make(net, dtype, options, path=None):
-    import mercer_research_amd as amd
-    from mercer_research_amd.device import DeviceRCN
-    spec = NETS[net]
-    L = amd.RCNLayer
-    convpool = {"default": None, "one": [L.Convolve2D(amd.Padding.SAME), L.Pool2D(amd.Pooling.MAX)]}[spec["convpool"]]
-    d = DeviceRCN(classes=10, convpool_cfg=convpool, feedforward_cfg=[30], input_shape=spec["input_shape"], dtype=amd.F64 if dtype == "f64" else amd.F32)
-    assert d.F == spec["F"]
-    path = spec["path"] if path is None else path
-    if path:
-        d.set_dense_path(path)
-    for k, v in options.items():
-        d.set_option(k, v)
-    return d
+def _data(spec, B):
+    """five batches, a draw per net and batch size"""
+    return 5 * B, 20250 + spec["F"] + B
 
 
-class _Pair:
-    """one net in one dtype: a context per pack form, and per batch size its data on the device"""
-
-    def __init__(self, net, dtype, forms=(("parent", {"pack_form": 0}), ("rows", {"pack_form": 1})), path=None):
-        from mercer_research_amd.synth import synthetic_params
-        self.net, self.dtype, self.F = net, dtype, NETS[net]["F"]
-        self.np_t = np.float64 if dtype == "f64" else np.float32
-        self.bits = np.uint64 if dtype == "f64" else np.uint32
-        ws, bs = synthetic_params([self.F, 30, 10], seed=42)
-        self.ws, self.bs = [w * 0.1 for w in ws], bs
-        self.ctx = {name: _make(net, dtype, opts, path) for name, opts in forms}
-        for name, opts in forms:
-            for k, v in opts.items():
-                assert self.ctx[name].get_option(k) == v
-        self.data = {}
-
-    def on_device(self, which, B):
-        if (which, B) not in self.data:
-            rows = 5 * B
-            rng = np.random.default_rng(20250 + self.F + B)
-            X = np.maximum(rng.standard_normal((rows, self.F)), 0.0).astype(self.np_t)
-            Y = np.eye(10, dtype=self.np_t)[rng.integers(0, 10, rows)]
-            perm = rng.permutation(rows).astype(np.int32)
-            d = self.ctx[which]
-            if NETS[self.net].get("unaligned"):            # the same rows one element into a longer buffer
-                flat = d.to_device(np.concatenate([np.zeros(1, self.np_t), X.ravel(), np.zeros(3, self.np_t)]))
-                Xd = flat[1:1 + X.size].view(rows, self.F)
-                assert Xd.data_ptr() % 16 == 4 and Xd.is_contiguous()
-            else:
-                Xd = d.to_device(X)
-                assert Xd.data_ptr() % 16 == 0
-            self.data[(which, B)] = (Xd, d.to_device(Y), d.to_device(perm))
-        return self.data[(which, B)]
-
-    def run(self, which, B, form, what):
-        """-> (parameters, per-step costs) of one call (or one begun epoch) from the starting parameters"""
-        d = self.ctx[which]
-        X, Y, perm = self.on_device(which, B)
-        nb = STEPS[what]
-        index = {"shuffled": perm, "offset": perm[B:], "stored": None}[form]
-        assert nb <= (4 if form == "offset" else 5)
-        esz = 8 if self.dtype == "f64" else 4
-        G = (self.F + 15) // 16
-        d.set_option("pack_segment_bytes", 2 * G * B * 16 * esz if what == "5steps-2seg" else 64 << 20)
-        d.set_params(self.ws, self.bs)
-        loss = d.empty(nb)
-        if what == "begin":
-            d.epoch_begin(X, Y, index, B, nb)
-            d.epoch_steps(0, 1, 3.0, loss)
-            d.epoch_steps(1, 2, 3.0, loss[1:])
-        else:
-            d.train_epoch(X, Y, index, B, nb, 3.0, loss)
-        d.synchronize()
-        assert d.fallbacks_taken() == 0, "a launch stepped down to another path"
-        return d.params_flat().cpu().numpy().copy(), loss.cpu().numpy().copy()
-
-    def close(self):
-        for d in self.ctx.values():
-            d.rcn.close()
+def _pair(net, dtype, forms=(("parent", {"pack_form": 0}), ("rows", {"pack_form": 1})), path=None):
+    """one net in one dtype: a context per pack form, on the path the library selects unless one is given"""
+    return Pair(NETS[net], DTYPES[dtype], forms, _data, path=path)
 
 
-@pytest.fixture(scope="module")
-def pairs():
-    made = {}
-
-    def get(net, dtype, **kw):
-        key = (net, dtype, repr(sorted(kw.items())))
-        if key not in made:
-            made[key] = _Pair(net, dtype, **kw)
-        return made[key]
-
-    yield get
-    for p in made.values():
-        p.close()
-
-
-def _same_bits(pair, got, want, what):
-    (got_p, got_c), (want_p, want_c) = got, want
-    assert np.all(np.isfinite(want_c)) and want_c.min() > 0.0, "the costs are not those of a training step"
-    assert np.all(np.isfinite(got_c)) and got_c.min() > 0.0, "the costs are not those of a training step"
-    assert np.array_equal(got_c.view(pair.bits), want_c.view(pair.bits)), f"{what}: per-step costs differ: {got_c - want_c}"
-    assert np.array_equal(got_p.view(pair.bits), want_p.view(pair.bits)), f"{what}: parameters differ at {np.flatnonzero(got_p != want_p)[:8]}"
+pairs = cached_pairs(_pair)
 
 
 @pytest.mark.parametrize("net,dtype,B,form,what", CASES, ids=[f"{n}-{t}-B{b}-{f}-{w}" for n, t, b, f, w in CASES])
@@ -169,9 +79,9 @@ def test_pack_rows_writes_the_image_of_pack_epoch(pairs, net, dtype, B, form, wh
     want = pair.run("parent", B, form, what)
     got = pair.run("rows", B, form, what)
     print(net, dtype, B, form, what, "resident", pair.ctx["rows"].train_epoch_resident(B), "costs", got[1].tolist())
-    _same_bits(pair, got, want, "pack_form 1 against 0")
+    same_bits(got, want, pair.bits, "pack_form 1 against 0")
     if what == "begin":                                  # ... and the begun epoch walked in two pieces is train_epoch over the same three batches
-        _same_bits(pair, got, pair.run("rows", B, form, "3steps"), "epoch_begin + epoch_steps against train_epoch")
+        same_bits(got, pair.run("rows", B, form, "3steps"), pair.bits, "epoch_begin + epoch_steps against train_epoch")
 
 
 def test_pack_rows_image_gives_the_gather_form_s_bits(pairs):
@@ -183,4 +93,4 @@ def test_pack_rows_image_gives_the_gather_form_s_bits(pairs):
     want = pair.run("gather", B, "shuffled", "3steps")
     got = pair.run("rows", B, "shuffled", "3steps")
     print("costs", got[1].tolist())
-    _same_bits(pair, got, want, "packed image against the gather form")
+    same_bits(got, want, pair.bits, "packed image against the gather form")

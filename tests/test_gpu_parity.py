@@ -9,6 +9,7 @@ import os
 
 import numpy as np
 import pytest
+from _rcn_util import amd, oracle_global_epochs, spawn_ranks  # noqa: F401  (amd: a fixture)
 
 from oracle.rcn_oracle import (DEFAULT_LAYERS, LAYER_CONV, LAYER_POOL, PAD_NONE, PAD_SAME, POOL_MAX, one_hot,
                                synthetic_images, synthetic_params)
@@ -18,12 +19,6 @@ pytestmark = pytest.mark.gpu
 F32_ACT_ATOL = 2e-6
 F32_PARAM_RTOL, F32_PARAM_ATOL = 1e-5, 1e-6
 F64_RTOL = 1e-11
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import mercer_research_amd as m
-    return m
 
 
 def _layers(amd, spec):
@@ -681,23 +676,12 @@ def test_peer_allreduce_two_processes_one_gpu(amd, oracle, dtype, Bs, nb, fused,
     """The xGMI peer-read all-reduce (csrc/dp_p2p.hpp) between two PROCESSES (hipIpc handles carried by gloo), both on this
     box's one GPU: the known-answer self-test is exact, both replicas end bit-identical, and two epochs of the sharded
     loop equal the oracle's sequential train_batch on the concatenated global batches."""
-    import socket
-    import subprocess
-    import sys
     # shard batch 16: sample-tile gradient kernels + k_p2p_allreduce; shard batch 256: the feature-sliced pipeline with the
     # exchange either in a third kernel (k_p2_dp_grad / k_p2_dp_apply) or inside the gradient kernel (k_p2_dp_fused)
     # (2 or 4 rank processes: with the test runner that stays within the box's limit of 6 processes on the GPU)
     dims = [784, 30, 10]
     if world < 0:                                                    # a second shape class member: one tail tile, odd sizes
         dims, world = [784, 12, 7], -world
-    rng = np.random.default_rng(31)
-    Xs = [np.maximum(rng.standard_normal((Bs * nb, dims[0])), 0.0) for _ in range(world)]
-    Ys = [one_hot(rng.integers(0, dims[-1], Bs * nb), dims[-1]) for _ in range(world)]
-    np.savez(tmp_path / "case.npz", dims=dims, Bs=Bs, nb=nb, seed=17, **{f"X{r}": Xs[r] for r in range(world)}, **{f"Y{r}": Ys[r] for r in range(world)})
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        port = so.getsockname()[1]
-    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_p2p_worker.py")
     # fused == 2: the resident one-XCD kernel with the exchange inside it (dense_xcd.hpp, DP form: reduce-scatter + all-gather on pushed
     # words, dp_push.hpp), every rank on an XCD of its own (tests/_p2p_worker.py).  At a shard of 64 samples: a resident launch's
     # blocks -- also the 224 idle ones -- all ask for the kernel's LDS, 66 KB at this size, so a rank's idle blocks fit beside the
@@ -706,18 +690,8 @@ def test_peer_allreduce_two_processes_one_gpu(amd, oracle, dtype, Bs, nb, fused,
     # has no peer workers on it (round 2 ran that case opt-in and saw it pass once and time out otherwise).
     resident = fused == 2
     fused = 1 if resident else fused
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", RCN_HIP_DP_FUSED=str(fused), RCN_HIP_XCD="1" if resident else "0")
-    procs = [subprocess.Popen([sys.executable, worker, str(r), str(world), str(port), str(dtype), str(tmp_path)], env=env,
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in range(world)]
-    logs = []
-    for pr in procs:
-        try:
-            out, _ = pr.communicate(timeout=240)
-        except subprocess.TimeoutExpired:
-            pr.kill()
-            out, _ = pr.communicate()
-        logs.append(out.decode(errors="replace")[-3000:])
-    assert all(pr.returncode == 0 for pr in procs), "\n----\n".join(logs)
+    # (no case name: the worker is started as it always was here, and takes its "default")
+    Xs, Ys, _ = spawn_ranks(tmp_path, world, dtype, None, {"RCN_HIP_DP_FUSED": str(fused), "RCN_HIP_XCD": "1" if resident else "0"}, dims=dims, Bs=Bs, nb=nb)
     outs = [np.load(tmp_path / f"out{r}.npz") for r in range(world)]
     for o in outs:
         assert int(o["bad"]) == 0 and int(o["timed_out"]) == 0 and int(o["active"]) == (2 if fused else 1)
@@ -725,16 +699,7 @@ def test_peer_allreduce_two_processes_one_gpu(amd, oracle, dtype, Bs, nb, fused,
     for r in range(1, world):
         for k in ("w0", "w1", "b0", "b1", "loss"):
             assert np.array_equal(outs[0][k], outs[r][k]), (r, k)     # rank-order sums: replicas are bit-identical
-    ws, bs = synthetic_params(dims, seed=17)
-    rw, rb = [w * 0.1 for w in ws], bs
-    costs = []
-    for ep in range(2):
-        for j in range(nb):
-            xb = np.concatenate([X[j * Bs:(j + 1) * Bs] for X in Xs])
-            yb = np.concatenate([Y[j * Bs:(j + 1) * Bs] for Y in Ys])
-            rw, rb, c = oracle.train_batch(rw, rb, xb, yb, 3.0)
-            if ep == 0:
-                costs.append(c)
+    rw, rb, costs = oracle_global_epochs(oracle, dims, Xs, Ys, Bs, nb)
     got = [outs[0]["w0"], outs[0]["w1"], outs[0]["b0"], outs[0]["b1"]]
     want = [rw[0], rw[1], rb[0], rb[1]]
     if dtype == 1:

@@ -13,19 +13,13 @@ import sys
 
 import numpy as np
 import pytest
+from _rcn_util import ROOT, amd, oracle_global_epochs, spawn_ranks, xcd_or_skip  # noqa: F401  (amd: a fixture)
 
 from oracle.rcn_oracle import DEFAULT_LAYERS, one_hot, synthetic_images, synthetic_params
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 BENCH_B, BENCH_N, BENCH_ETA, BENCH_DIMS = 256, 16384, 3.0, [784, 30, 10]
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import mercer_research_amd as m
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -248,35 +242,12 @@ def test_gen_scales_also_invalidates_image_epoch_graphs(amd):
         assert np.array_equal(a, b)
 
 
-def _spawn_ranks(tmp_path, world, dtype, case_name, env_extra, dims=(784, 30, 10), Bs=256, nb=2, seed=17):
-    rng = np.random.default_rng(31)
-    dims = list(dims)
-    Xs = [np.maximum(rng.standard_normal((Bs * nb, dims[0])), 0.0) for _ in range(world)]
-    Ys = [one_hot(rng.integers(0, dims[-1], Bs * nb), dims[-1]) for _ in range(world)]
-    np.savez(tmp_path / "case.npz", dims=dims, Bs=Bs, nb=nb, seed=seed, **{f"X{r}": Xs[r] for r in range(world)}, **{f"Y{r}": Ys[r] for r in range(world)})
-    port = _free_port()
-    worker = os.path.join(ROOT, "tests", "_p2p_worker.py")
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **env_extra)
-    procs = [subprocess.Popen([sys.executable, worker, str(r), str(world), str(port), str(dtype), str(tmp_path), case_name], env=env,
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in range(world)]
-    logs = []
-    for pr in procs:
-        try:
-            out, _ = pr.communicate(timeout=240)
-        except subprocess.TimeoutExpired:
-            pr.kill()
-            out, _ = pr.communicate()
-        logs.append(out.decode(errors="replace")[-3000:])
-    assert all(pr.returncode == 0 for pr in procs), "\n----\n".join(logs)
-    return Xs, Ys, logs
-
-
 @pytest.mark.parametrize("xcd", ["0", "1"], ids=["two-kernel-pipeline", "resident-one-xcd-kernel"])
 def test_sticky_timeout_of_the_peer_exchange_surfaces_from_synchronize_and_get_params(amd, tmp_path, xcd):
     """a peer wait that times out in the LAST call used to go unnoticed (the word was only looked at by the next
     epoch call).  Two ranks on this GPU; rank 1 stops after one step, rank 0's second step waits (20 ms bound) for data that never
     comes: rcn_hip_synchronize, rcn_hip_get_params and rcn_hip_dp_finalize must each report it."""
-    _, _, logs = _spawn_ranks(tmp_path, 2, 0, "sticky", {"RCN_HIP_XCD": xcd})
+    _, _, logs = spawn_ranks(tmp_path, 2, 0, "sticky", {"RCN_HIP_XCD": xcd}, dims=(784, 30, 10), Bs=256, nb=2)
     assert "STICKY synchronize=error get_params=error finalize=error" in logs[0], logs[0]
     assert f"RESIDENT {xcd}" in logs[0], logs[0]                    # ... on the step kernel this case is about
 
@@ -295,30 +266,15 @@ def test_admission_votes_land_every_rank_on_the_same_form_and_the_epoch_equals_t
     if "llskip" in fault:
         env["RCN_HIP_DP_TIMEOUT_TICKS"] = "5000000"                # 50 ms per expired wait instead of 1 s
     world, Bs, nb, dims = 2, 256, 2, [784, 30, 10]
-    Xs, Ys, logs = _spawn_ranks(tmp_path, world, 1, "admit", env, dims=dims, Bs=Bs, nb=nb)
+    Xs, Ys, logs = spawn_ranks(tmp_path, world, 1, "admit", env, dims=dims, Bs=Bs, nb=nb)
     outs = [np.load(tmp_path / f"out{r}.npz") for r in range(world)]
     assert [int(o["active"]) for o in outs] == [expect] * world, (fault, [int(o["active"]) for o in outs], logs)
     for k in ("w0", "w1", "b0", "b1", "loss"):
         assert np.array_equal(outs[0][k], outs[1][k]), k           # replicas bit-identical on every form
-    ws, bs = synthetic_params(dims, seed=17)
-    rw, rb, costs = [w * 0.1 for w in ws], bs, []
-    for ep in range(2):
-        for j in range(nb):
-            xb = np.concatenate([X[j * Bs:(j + 1) * Bs] for X in Xs])
-            yb = np.concatenate([Y[j * Bs:(j + 1) * Bs] for Y in Ys])
-            rw, rb, c = oracle.train_batch(rw, rb, xb, yb, 3.0)
-            if ep == 0:
-                costs.append(c)
+    rw, rb, costs = oracle_global_epochs(oracle, dims, Xs, Ys, Bs, nb)
     for a, b in zip([outs[0]["w0"], outs[0]["w1"], outs[0]["b0"], outs[0]["b1"]], [rw[0], rw[1], rb[0], rb[1]]):
         assert np.all(np.abs(a - b) <= 1e-11 * np.abs(b) + 1e-12)
     np.testing.assert_allclose(outs[0]["loss"], costs, rtol=1e-10)
-
-
-def _free_port():
-    import socket
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def test_workspace_growth_failure_path_leaves_no_dangling_graphs(amd):
@@ -473,14 +429,6 @@ def test_train_arrays_runs_on_resident_sets_and_prints_the_reference_line(amd, o
 
 # ------------------------------------------------------------------------------------------------ resident one-XCD kernel
 
-def _xcd_or_skip(d):
-    import mercer_research_amd as amd
-    try:
-        d.set_dense_path(5)
-    except amd.RcnHipError as e:
-        pytest.skip(f"the resident one-XCD kernel does not apply on this device: {e}")
-
-
 def test_resident_one_xcd_kernel_is_the_reference_loop(amd, oracle, monkeypatch):
     """dense path 5 (csrc/dense_xcd.hpp): ONE resident kernel per epoch segment, its 32 workgroups on one XCD, slab / deltas handed over
     through that XCD's L2.  Must be the reference's sequential train_batch loop (rcn.rs:147-149, 176-223): parameters and per-step costs
@@ -498,7 +446,7 @@ def test_resident_one_xcd_kernel_is_the_reference_loop(amd, oracle, monkeypatch)
     for path in (5, 2):
         d = DeviceRCN(dtype=0)
         if path == 5:
-            _xcd_or_skip(d)
+            xcd_or_skip(d)
         else:
             d.set_dense_path(2)
         d.set_params(ws, bs)
@@ -559,7 +507,7 @@ def test_resident_one_xcd_kernel_first_step_tight_and_reproducible(amd, oracle):
         runs = []
         for rep in range(2):
             d = DeviceRCN(dtype=0)
-            _xcd_or_skip(d)
+            xcd_or_skip(d)
             d.set_params(ws, bs)
             Xd, Yd = d.to_device(X, d.tdtype), d.to_device(Y, d.tdtype)
             loss = d.empty(4)
@@ -583,7 +531,7 @@ def test_resident_one_xcd_kernel_first_step_tight_and_reproducible(amd, oracle):
 def test_resident_kernel_is_what_auto_selects_for_the_bench_shape_and_not_for_others(amd):
     from mercer_research_amd.device import DeviceRCN
     d = DeviceRCN(dtype=0)
-    _xcd_or_skip(d)
+    xcd_or_skip(d)
     d.rcn.close()
     d64 = DeviceRCN(dtype=1)
     d64.set_dense_path(5)                                            # f64 context (round 4): the kernel's f64 instantiations, batches of 1..128
@@ -617,7 +565,7 @@ def test_resident_kernel_data_parallel_form_at_world_one_is_the_single_gpu_kerne
     got = {}
     for form in ("dp", "single"):
         d = DeviceRCN(dtype=0)
-        _xcd_or_skip(d)
+        xcd_or_skip(d)
         d.set_params(ws, bs)
         Xd, Yd, permd = d.to_device(X, d.tdtype), d.to_device(Y, d.tdtype), d.to_device(perm)
         loss, loss2 = d.empty(nb), d.empty(2)
@@ -714,7 +662,7 @@ def test_resident_kernel_with_two_hidden_layers_is_the_reference_loop(amd, oracl
     for path in (5, 2):
         d = DeviceRCN(dtype=0, feedforward_cfg=hidden)
         if path == 5:
-            _xcd_or_skip(d)
+            xcd_or_skip(d)
         else:
             d.set_dense_path(2)
         d.set_params(ws, bs)
@@ -824,7 +772,7 @@ def test_resident_kernel_many_segments_of_the_epoch_image(amd, oracle, monkeypat
     ws = [w * 0.1 for w in ws]
     perm = np.random.default_rng(8).permutation(N).astype(np.int32)
     d = DeviceRCN(dtype=0)
-    _xcd_or_skip(d)
+    xcd_or_skip(d)
     d.set_dense_path(0)
     d.set_params(ws, bs)
     dev = d.to_device(imgs)

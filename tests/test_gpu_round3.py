@@ -7,38 +7,15 @@
 * per-context options (two contexts of one process on different forms).
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
+from _rcn_util import (F32, F32_ONE_STEP, F32_SIX_STEPS, amd, check_one_and_six, one_and_six_inputs, one_and_six_steps, oracle_global_epochs,  # noqa: F401  (amd: a fixture)
+                       oracle_steps, spawn_ranks, xcd_or_skip)
 
 from oracle.rcn_oracle import DEFAULT_LAYERS, one_hot, synthetic_images, synthetic_params
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import mercer_research_amd as m
-    return m
-
-
-def _xcd_or_skip(d):
-    import mercer_research_amd as amd
-    try:
-        d.set_dense_path(5)
-    except amd.RcnHipError as e:
-        pytest.skip(f"the resident one-XCD kernel does not apply on this device: {e}")
-
-
-def _oracle_steps(oracle, ws, bs, X, Y, perm, B, nb, eta):
-    rw, rb, costs = ws, bs, []
-    for j in range(nb):
-        sel = perm[j * B:(j + 1) * B]
-        rw, rb, c = oracle.train_batch(rw, rb, X[sel], Y[sel], eta)
-        costs.append(c)
-    return rw, rb, np.array(costs)
 
 
 @pytest.mark.parametrize("hidden", [[30], [10, 10]], ids=["784-30-10", "reference-test-net-784-10-10-10"])
@@ -49,41 +26,18 @@ def test_resident_kernel_at_any_batch_of_1_to_256_is_the_reference_loop(amd, ora
     identical parameters at the one-step f32 tolerance of SURVEY 8(c) (1e-5 relative + 1e-6), six chained steps in a shuffled order
     at the chained tolerance, and the sample-tile kernels (dense path 1, any B) on the same calls."""
     from mercer_research_amd.device import DeviceRCN
-    dims = [784] + hidden + [10]
-    N, nb = 2048, 6
-    rng = np.random.default_rng(100 + B)
-    X = np.maximum(rng.standard_normal((N, 784)), 0.0).astype(np.float32).astype(np.float64)
-    Y = one_hot(rng.integers(0, 10, N))
-    ws, bs = synthetic_params(dims, seed=21)
-    ws = [w * 0.1 for w in ws]
-    perm = rng.permutation(N).astype(np.int32)
+    nb = 6
+    X, Y, perm, ws, bs = one_and_six_inputs(hidden, 100 + B, F32)
     got = {}
     for path in (5, 1):
-        d = DeviceRCN(dtype=0, feedforward_cfg=hidden)
+        d = DeviceRCN(dtype=F32, feedforward_cfg=hidden)
         if path == 5:
-            _xcd_or_skip(d)
+            xcd_or_skip(d)
         else:
             d.set_dense_path(1)
-        d.set_params(ws, bs)
-        Xd, Yd, pd = d.to_device(X, d.tdtype), d.to_device(Y, d.tdtype), d.to_device(perm)
-        loss = d.empty(nb + 1)
-        d.train_epoch(Xd, Yd, None, B, 1, 3.0, loss)                   # one step, stored order
-        p1 = sum(d.get_params(), [])
-        d.train_epoch(Xd, Yd, pd, B, nb, 3.0, loss[1:])                 # six more, shuffled
-        d.synchronize()
-        got[path] = (p1, sum(d.get_params(), []), loss.cpu().numpy().astype(np.float64))
-        assert d.fallbacks_taken() == 0
+        got[path] = one_and_six_steps(d, ws, bs, d.to_device(X, d.tdtype), d.to_device(Y, d.tdtype), d.to_device(perm), B, nb)
         d.rcn.close()
-    rw, rb, c0 = oracle.train_batch(ws, bs, X[:B], Y[:B], 3.0)
-    for path in (5, 1):
-        for a, b in zip(got[path][0], rw + rb):
-            assert np.all(np.abs(a - b) <= 1e-5 * np.abs(b) + 1e-6), (path, float(np.abs(a - b).max()))
-        assert abs(got[path][2][0] - c0) <= 1e-5 * c0
-    rw, rb, cs = _oracle_steps(oracle, rw, rb, X, Y, perm, B, nb, 3.0)
-    for path in (5, 1):
-        np.testing.assert_allclose(got[path][2][1:], cs, rtol=1e-4)
-        for a, b in zip(got[path][1], rw + rb):
-            assert np.all(np.abs(a - b) <= 1e-4 * np.abs(b) + 1e-5), (path, float(np.abs(a - b).max()))
+    check_one_and_six(oracle, got, ws, bs, X, Y, perm, B, nb, F32_ONE_STEP, F32_SIX_STEPS)
 
 
 @pytest.mark.parametrize("B", [32, 10], ids=["B32-baseline-config0", "B10-reference-default"])
@@ -99,7 +53,7 @@ def test_loss_curve_256_steps_at_the_reference_batch_sizes(amd, oracle, B):
     X, Y = oracle.standardize(feats, m, s), one_hot(labels)
     ws, bs = synthetic_params([784, 30, 10], seed=42)
     d = DeviceRCN(dtype=0)
-    _xcd_or_skip(d)
+    xcd_or_skip(d)
     d.set_params(ws, bs)
     Xd, Yd = d.load_data(d.to_device(imgs), d.to_device(labels))
     perm = torch.empty(N, dtype=torch.int32, device=d.device)
@@ -142,7 +96,7 @@ def test_resident_kernel_steps_down_by_itself_and_the_epochs_still_equal_the_ora
     ws, bs = synthetic_params([784, 30, 10], seed=3)
     ws = [w * 0.1 for w in ws]
     d = DeviceRCN(dtype=0)
-    _xcd_or_skip(d)
+    xcd_or_skip(d)
     d.set_dense_path(0)
     d.set_option("xcd_timeout_ticks", 300000)                          # 3 ms per expired wait instead of 0.2 s
     d.set_option("xcd_fault_launch", fail_launch)
@@ -173,7 +127,7 @@ def test_resident_kernel_steps_down_by_itself_and_the_epochs_still_equal_the_ora
     assert np.array_equal(perm.cpu().numpy(), perms[2])                 # the index buffer ends as the caller's last shuffle left it
     rw, rb, cs = ws, bs, []
     for e in range(3):
-        rw, rb, c = _oracle_steps(oracle, rw, rb, Xh, Yh, perms[e], B, nb, 3.0)
+        rw, rb, c = oracle_steps(oracle, rw, rb, Xh, Yh, perms[e], B, nb, 3.0)
         cs.extend(c)
     np.testing.assert_allclose(costs, cs, rtol=2e-3)
     for a, b in zip(got, rw + rb):
@@ -193,7 +147,7 @@ def test_without_auto_fallback_the_error_is_sticky_and_a_recovery_action_clears_
     X, Y = np.maximum(rng.standard_normal((N, 784)), 0.0), one_hot(rng.integers(0, 10, N))
     ws, bs = synthetic_params([784, 30, 10], seed=3)
     d = DeviceRCN(dtype=0)
-    _xcd_or_skip(d)
+    xcd_or_skip(d)
     d.set_option("xcd_auto_fallback", 0)
     d.set_option("xcd_timeout_ticks", 300000)
     d.set_option("xcd_fault_launch", 1)
@@ -225,7 +179,7 @@ def test_options_are_per_context(amd, oracle):
     ws, bs = synthetic_params([784, 30, 10], seed=5)
     ws = [w * 0.1 for w in ws]
     a, b = DeviceRCN(dtype=0), DeviceRCN(dtype=0)
-    _xcd_or_skip(a)
+    xcd_or_skip(a)
     a.set_dense_path(0)
     b.set_option("xcd", 0)
     assert a.get_option("xcd") == 1 and b.get_option("xcd") == 0
@@ -250,47 +204,6 @@ def test_options_are_per_context(amd, oracle):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the data-parallel form of the resident kernel between PROCESSES (default on)
 
-def _spawn_ranks(tmp_path, world, dtype, case_name, env_extra, dims=(784, 30, 10), Bs=64, nb=3, seed=17):
-    import socket
-    import subprocess
-    import sys
-    rng = np.random.default_rng(31)
-    dims = list(dims)
-    Xs = [np.maximum(rng.standard_normal((Bs * nb, dims[0])), 0.0) for _ in range(world)]
-    Ys = [one_hot(rng.integers(0, dims[-1], Bs * nb), dims[-1]) for _ in range(world)]
-    np.savez(tmp_path / "case.npz", dims=dims, Bs=Bs, nb=nb, seed=seed, **{f"X{r}": Xs[r] for r in range(world)}, **{f"Y{r}": Ys[r] for r in range(world)})
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        port = so.getsockname()[1]
-    worker = os.path.join(ROOT, "tests", "_p2p_worker.py")
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **env_extra)
-    procs = [subprocess.Popen([sys.executable, worker, str(r), str(world), str(port), str(dtype), str(tmp_path), case_name], env=env,
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in range(world)]
-    logs = []
-    for pr in procs:
-        try:
-            out, _ = pr.communicate(timeout=240)
-        except subprocess.TimeoutExpired:
-            pr.kill()
-            out, _ = pr.communicate()
-        logs.append(out.decode(errors="replace")[-3000:])
-    assert all(pr.returncode == 0 for pr in procs), "\n----\n".join(logs)
-    return Xs, Ys, logs
-
-
-def _oracle_global_epochs(oracle, dims, Xs, Ys, Bs, nb, seed=17):
-    ws, bs = synthetic_params(dims, seed=seed)
-    rw, rb, costs = [w * 0.1 for w in ws], bs, []
-    for ep in range(2):
-        for j in range(nb):
-            xb = np.concatenate([X[j * Bs:(j + 1) * Bs] for X in Xs])
-            yb = np.concatenate([Y[j * Bs:(j + 1) * Bs] for Y in Ys])
-            rw, rb, c = oracle.train_batch(rw, rb, xb, yb, 3.0)
-            if ep == 0:
-                costs.append(c)
-    return rw, rb, costs
-
-
 @pytest.mark.parametrize("world,Bs,dims", [(2, 64, (784, 30, 10)), (2, 32, (784, 12, 7)), (4, 32, (784, 30, 10)), (3, 64, (784, 30, 10))],
                          ids=["2-ranks-shard-64", "2-ranks-784-12-7-shard-32", "4-ranks-shard-32", "3-ranks-shard-64"])
 def test_resident_kernel_data_parallel_form_between_processes(amd, oracle, tmp_path, world, Bs, dims):
@@ -309,7 +222,7 @@ def test_resident_kernel_data_parallel_form_between_processes(amd, oracle, tmp_p
     # (the processes time-share ONE device here, which is not the product's configuration of a GPU per rank: every hand-off may cost a
     # scheduling quantum, so the bounded waits get seconds, not 0.2 s -- at three ranks with the default 0.2 s one run in a few expired)
     env = {"RCN_HIP_XCD_TIMEOUT_TICKS": "400000000", "RCN_HIP_DP_TIMEOUT_TICKS": "400000000"}
-    Xs, Ys, logs = _spawn_ranks(tmp_path, world, 0, "default", env, dims=dims, Bs=Bs, nb=nb)
+    Xs, Ys, logs = spawn_ranks(tmp_path, world, 0, "default", env, dims=dims, Bs=Bs, nb=nb)
     outs = [np.load(tmp_path / f"out{r}.npz") for r in range(world)]
     for o in outs:
         assert int(o["bad"]) == 0 and int(o["timed_out"]) == 0 and int(o["active"]) == 2, logs
@@ -317,7 +230,7 @@ def test_resident_kernel_data_parallel_form_between_processes(amd, oracle, tmp_p
     for r in range(1, world):
         for k in ("w0", "w1", "b0", "b1", "loss"):
             assert np.array_equal(outs[0][k], outs[r][k]), (r, k)
-    rw, rb, costs = _oracle_global_epochs(oracle, list(dims), Xs, Ys, Bs, nb)
+    rw, rb, costs = oracle_global_epochs(oracle, list(dims), Xs, Ys, Bs, nb)
     for a, b in zip([outs[0]["w0"], outs[0]["w1"], outs[0]["b0"], outs[0]["b1"]], [rw[0], rw[1], rb[0], rb[1]]):
         assert np.all(np.abs(a - b) <= 1e-4 * np.abs(b) + 1e-5), float(np.abs(a - b).max())     # six chained f32 steps
     np.testing.assert_allclose(outs[0]["loss"], costs, rtol=1e-4)
@@ -333,13 +246,13 @@ def test_admission_of_the_pushed_exchange_is_voted_like_the_others(amd, oracle, 
     if "skip" in fault:
         env["RCN_HIP_DP_TIMEOUT_TICKS"] = "5000000"
     world, Bs, nb, dims = 2, 256 if not resident else 64, 2, [784, 30, 10]
-    Xs, Ys, logs = _spawn_ranks(tmp_path, world, 0, "admit", env, dims=dims, Bs=Bs, nb=nb)
+    Xs, Ys, logs = spawn_ranks(tmp_path, world, 0, "admit", env, dims=dims, Bs=Bs, nb=nb)
     outs = [np.load(tmp_path / f"out{r}.npz") for r in range(world)]
     assert [int(o["active"]) for o in outs] == [2] * world, logs
     assert [int(o["resident"]) for o in outs] == [resident] * world, logs
     for k in ("w0", "w1", "b0", "b1", "loss"):
         assert np.array_equal(outs[0][k], outs[1][k]), k
-    rw, rb, costs = _oracle_global_epochs(oracle, dims, Xs, Ys, Bs, nb)
+    rw, rb, costs = oracle_global_epochs(oracle, dims, Xs, Ys, Bs, nb)
     for a, b in zip([outs[0]["w0"], outs[0]["w1"], outs[0]["b0"], outs[0]["b1"]], [rw[0], rw[1], rb[0], rb[1]]):
         assert np.all(np.abs(a - b) <= 1e-4 * np.abs(b) + 1e-5), float(np.abs(a - b).max())
     np.testing.assert_allclose(outs[0]["loss"], costs, rtol=1e-4)
