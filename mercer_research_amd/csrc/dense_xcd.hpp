@@ -109,7 +109,96 @@ inline size_t xcd_buf_bytes(const NetDesc& nd, size_t BT, size_t esz = 4) {
 // the tail tiles' K-split partials, the slice pair of W_0, and the sample group's scratch (slab partial sums, a_1 / delta_2 tiles,
 // target fragments): f32 148 KB of the CU's 160 at BT = 256 -- one worker per CU -- 94 / 66 / 51 KB at BT = 128 / 64 / 32;
 // f64 152 / 130 / 101 KB at BT = 128 / 64 / 32
+// (kD1Dma forms: the same request; delta_1 uses 32 floats of each 48 reserved, unpadded and swizzled, and lies in front of the buffers)
 constexpr int kXcdD1Ld = 48;
+// kD1Dma (the single-GPU f32 forms for 64 samples and more): delta_1 goes into LDS by loads that write LDS themselves.  Such a load
+// writes wave-uniform base + 16 lane, 1 KB per wave-instruction, so the image is lane-linear, rows of 32 floats with no pad, and what
+// the pad did for the gradient's operand reads a swizzle does, applied to the SOURCE address: the 16-byte chunk c (hidden 4c .. 4c + 3)
+// of sample row r sits at slot c ^ 4 (r & 1) -- odd rows have their two hidden halves exchanged.
+//   piece: lane L of a wave-instruction whose first row is row0 (even) writes LDS bytes 128 row0 + 16 L and reads byte xcd_d1_src_byte
+//   read:  hidden h of row r is the word xcd_d1_word(r, h)
+constexpr int kXcdD1DmaLd = 32;
+constexpr int xcd_d1_src_byte(int row0, int L) { return (row0 + (L >> 3)) * 128 + (((L & 7) ^ (4 * ((row0 + (L >> 3)) & 1))) << 4); }
+constexpr int xcd_d1_word(int row, int h) { return row * kXcdD1DmaLd + ((((h >> 2)) ^ (4 * (row & 1))) << 2) + (h & 3); }
+// the source map is a bijection of the 1 KB piece, and the read map finds every word where the piece put it
+constexpr bool xcd_d1_piece_ok(int row0) {
+    unsigned long long seen = 0ull;
+    for (int L = 0; L < 64; ++L) {
+        const int src = xcd_d1_src_byte(row0, L) - row0 * 128;
+        if (src < 0 || src >= 1024 || (src & 15) != 0) return false;
+        seen |= 1ull << (src >> 4);
+        const int row = row0 + (L >> 3), c = (src >> 4) & 7;
+        if ((src >> 7) != (L >> 3)) return false;                   // (a lane's chunk is of the row its LDS bytes belong to)
+        for (int k = 0; k < 4; ++k)
+            if (xcd_d1_word(row, 4 * c + k) != row0 * kXcdD1DmaLd + 4 * L + k) return false;
+    }
+    return seen == ~0ull;
+}
+// one ds_read_b32 of the gradient's A operand: lanes 0..31 (32..63) read hidden 16 umt + n, n = 0..15, of the rows r and r + 1 --
+// banks are dword mod 32 per 32-lane group: the two rows use disjoint 16-bank halves, so the read is conflict-free like the padded one
+constexpr bool xcd_d1_read_ok(int r, int umt) {
+    unsigned banks0 = 0u, banks1 = 0u;
+    for (int n = 0; n < 16; ++n) {
+        banks0 |= 1u << (xcd_d1_word(r, umt * 16 + n) & 31);
+        banks1 |= 1u << (xcd_d1_word(r + 1, umt * 16 + n) & 31);
+    }
+    return (banks0 & banks1) == 0u && __builtin_popcount(banks0) == 16 && __builtin_popcount(banks1) == 16;
+}
+static_assert(xcd_d1_piece_ok(0) && xcd_d1_piece_ok(8) && xcd_d1_piece_ok(64 + 56) && xcd_d1_piece_ok(192 + 56), "kD1Dma: a piece's source map");
+static_assert(xcd_d1_read_ok(0, 0) && xcd_d1_read_ok(0, 1) && xcd_d1_read_ok(1, 0) && xcd_d1_read_ok(1, 1) && xcd_d1_read_ok(2, 0) && xcd_d1_read_ok(3, 1) &&
+              xcd_d1_read_ok(254, 0) && xcd_d1_read_ok(254, 1), "kD1Dma: rows r, r + 1 of one operand read land on disjoint banks");
+// kW0ByHidden (the same forms): the slice pair of W_0 in LDS as [32 hidden][LDW] with the pair's 32 features contiguous in a row, so that
+// the four features 4 g4 .. 4 g4 + 3 of a hidden unit, which are the forward's four A operands wf[sl][0..3][t] of a lane, are ONE
+// ds_read_b128 (as [feature][hidden] they were four ds_read_b32, lanes g4 and g4 + 1 of a 32-lane group 128 words apart: a 2-way
+// conflict on each).  LDW = 32, no pad (the LDS request stays what it is for every form), and the 16-byte chunk c of row h sits at slot
+// c ^ ((h >> 1) & 7).  By the bank rules: a ds_read_b128 is served in four sets of 16 lanes, banks dword mod 64 -- the 16 lanes of a set
+// read 16 distinct quadruples mod 16: conflict-free; the gradient's ds_write_b32 (two sets of 32 lanes, dword mod 32; lanes g4 = 0 and 1
+// write the same 16-bank half) is 2-way, which costs a ds_write_b32 nothing (its 4 cycles are the data's way to the LDS, the array needs 2).
+constexpr int kXcdW0Ld = 32;
+constexpr int xcd_w0_word(int h, int f) { return h * kXcdW0Ld + ((((f >> 2)) ^ ((h >> 1) & 7)) << 2) + (f & 3); }
+// the forward's read of (sl, t): lane (n, g4) reads the quadruple at xcd_w0_word(16 t + n, 16 sl + 4 g4); the four lane sets of ds_read_b128
+constexpr bool xcd_w0_read_ok(int sl, int t) {
+    constexpr unsigned long long sets[4] = {0x000000000ff0f00full, 0x00000000f00f0ff0ull, 0x0ff0f00f00000000ull, 0xf00f0ff000000000ull};
+    for (int s = 0; s < 4; ++s) {
+        unsigned quads = 0u;
+        for (int lane = 0; lane < 64; ++lane)
+            if ((sets[s] >> lane) & 1ull) {
+                const int wd = xcd_w0_word(16 * t + (lane & 15), 16 * sl + 4 * (lane >> 4));
+                if ((wd & 3) != 0) return false;
+                quads |= 1u << ((wd >> 2) & 15);
+            }
+        if (quads != 0xffffu) return false;
+    }
+    return true;
+}
+// a gradient lane's store of element i (hidden 16 umt + 4 g4 + i, feature 16 usl + n): at most two lanes of a 32-lane set per bank
+constexpr bool xcd_w0_write_ok(int usl, int umt, int i) {
+    for (int half = 0; half < 2; ++half) {
+        int hits[32] = {};
+        for (int l = 0; l < 32; ++l) {
+            const int lane = 32 * half + l;
+            if (++hits[xcd_w0_word(16 * umt + 4 * (lane >> 4) + i, 16 * usl + (lane & 15)) & 31] > 2) return false;
+        }
+    }
+    return true;
+}
+// every word of the 32 x 32 image is some (hidden, feature)'s, once
+constexpr bool xcd_w0_bijective() {
+    for (int h = 0; h < 32; ++h) {
+        unsigned seen = 0u;
+        for (int f = 0; f < 32; ++f) {
+            const int wd = xcd_w0_word(h, f);
+            if (wd / kXcdW0Ld != h) return false;
+            seen |= 1u << (wd % kXcdW0Ld);
+        }
+        if (seen != 0xffffffffu) return false;
+    }
+    return true;
+}
+static_assert(xcd_w0_bijective(), "kW0ByHidden: the image's map");
+static_assert(xcd_w0_read_ok(0, 0) && xcd_w0_read_ok(0, 1) && xcd_w0_read_ok(1, 0) && xcd_w0_read_ok(1, 1), "kW0ByHidden: the forward's b128 reads are conflict-free");
+static_assert(xcd_w0_write_ok(0, 0, 0) && xcd_w0_write_ok(0, 0, 1) && xcd_w0_write_ok(0, 0, 2) && xcd_w0_write_ok(0, 0, 3) && xcd_w0_write_ok(1, 1, 0) &&
+              xcd_w0_write_ok(1, 1, 1) && xcd_w0_write_ok(1, 0, 2) && xcd_w0_write_ok(0, 1, 3), "kW0ByHidden: the gradient's b32 stores are at most 2-way");
 // the tail tiles' partials over the batch buffers (a tail tile is never a feature worker): only where the LDS would not fit otherwise
 template <typename T, int BT> constexpr bool xcd_red_aliased() { return sizeof(T) == 8 && BT >= 128; }
 // ONE batch buffer and delta_1 in two halves: only where two buffers and the whole delta_1 do not fit (f64, 256 samples)
@@ -481,6 +570,21 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
 #else
     constexpr bool kTailWordsByUse = kOneTopWait;
 #endif
+    // The feature worker's half.  The same forms again; every other form keeps its text.
+    // kD1Dma: delta_1 staged by loads that write LDS themselves (no registers, no ds_write pass), into the lane-linear swizzled image
+    // of xcd_d1_word instead of rows padded to 48.
+#ifdef RCN_AB_NO_D1_DMA
+    constexpr bool kD1Dma = false;
+#else
+    constexpr bool kD1Dma = kLatePrefetch;
+#endif
+    // kW0ByHidden: the slice pair's LDS image as [hidden][feature] (xcd_w0_word) -- the forward's sixteen operand words of a lane are four
+    // ds_read_b128; the prologue's and the update's store of a lane's four parameters are four ds_write_b32.
+#ifdef RCN_AB_NO_W0_BY_HIDDEN
+    constexpr bool kW0ByHidden = false;
+#else
+    constexpr bool kW0ByHidden = kLatePrefetch;
+#endif
     static_assert(!PH || DP, "the phase clocks exist for the data-parallel form");
     constexpr int ES = (int)sizeof(T), VS = 4 * ES;                  // bytes of an element / of a quadruple in the L2 buffers
     constexpr int RI = sizeof(T) == 4 ? 1 : 4;                       // Mfma16<T>::row(lane, i) = row(lane, 0) + RI * i
@@ -503,11 +607,15 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_dyn[];
     __shared__ int s_abort;
     T* smem = reinterpret_cast<T*>(smem_dyn);
-    T* xbuf = smem;                                                 // [2 | SB: 1][kXcdSl][B][16]
-    T* d1s = xbuf + (SB ? 1 : 2) * kXs;                             // delta_1 of the batch [BH][48] (32 used)
+    // (kD1Dma: the two regions in the other order, delta_1 first -- a load that writes LDS takes its LDS address from M0, and the image
+    // then lies below 64 KB at every batch size (48 KB at 256 samples) whatever width of M0 the instruction looks at; same sizes, so
+    // everything behind the two is where it was)
+    T* xbuf = kD1Dma ? smem + BH * kXcdD1Ld : smem;                 // [2 | SB: 1][kXcdSl][B][16]
+    T* d1s = kD1Dma ? smem : xbuf + (SB ? 1 : 2) * kXs;             // delta_1 of the batch [BH][48] (32 used; kD1Dma: [BH][32], xcd_d1_word)
+    T* past_d1 = smem + (SB ? 1 : 2) * kXs + BH * kXcdD1Ld;
     constexpr bool RA = xcd_red_aliased<T, BT>();                   // (f64, BT >= 128: laid over the batch buffers a tail tile never uses)
-    T* red = RA ? xbuf : d1s + BH * kXcdD1Ld;                       // tail tiles: [wave][mt][16 x kLd]
-    T* wsl = d1s + BH * kXcdD1Ld + (RA ? 0 : kDenseWaves * kMtp * kRedTile);     // [slice][feature 0..15][32]
+    T* red = RA ? xbuf : past_d1;                                   // tail tiles: [wave][mt][16 x kLd]
+    T* wsl = past_d1 + (RA ? 0 : kDenseWaves * kMtp * kRedTile);    // [slice][feature 0..15][32] (kW0ByHidden: [hidden][32 features], xcd_w0_word)
     vec4* zred = reinterpret_cast<vec4*>(wsl + kXcdSl * 16 * kP2H); // [8 waves][64 lanes]
     T* a1s = reinterpret_cast<T*>(zred) + kP2BWaves * 64 * 4;       // a_1 tile  [hidden 32][kLd]
     T* d2s = a1s + kP2H * kLd;                                      // delta_2   [class 16][kLd]
@@ -636,6 +744,10 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                 const T v = W0[wvalid[i] ? woff0 + RI * i : 0u];
                 wcur[i] = wvalid[i] ? v : (T)0;
             }
+            if constexpr (kW0ByHidden) {                               // (the four waves' lanes write all 32 x 32 words: pads are zeros, as below)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) wsl[xcd_w0_word(umt * 16 + 4 * g4 + i, usl * 16 + n)] = wcur[i];
+            } else
             store4<T>(wsl + (usl * 16 + n) * kP2H + umt * 16, lane, acc_t{wcur[0], wcur[1], wcur[2], wcur[3]});
         }
         // batches 0 and 1 of this launch: [slice pair][sample][16] is one contiguous run of nsl * B * 16 floats per batch
@@ -701,6 +813,17 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
         const T* xb = xbuf + (SB ? (size_t)0 : (size_t)(jn & 1) * kXs);
         constexpr int NTILE = BT / 16, UT = NTILE > kDenseWaves ? NTILE / kDenseWaves : 1;      // sample tiles, and how many a wave takes
         T wf[kXcdSl][4][kMtp];
+        if constexpr (kW0ByHidden) {
+            // (hidden 16 t + n, features 16 sl + 4 g4 .. + 3: one quadruple of the [hidden][feature] image)
+#pragma unroll
+            for (int sl = 0; sl < kXcdSl; ++sl)
+#pragma unroll
+                for (int t = 0; t < kMtp; ++t) {
+                    const vec4 q = *reinterpret_cast<const vec4*>(wsl + xcd_w0_word(t * 16 + n, sl * 16 + 4 * g4));
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) wf[sl][i][t] = q[i];
+                }
+        } else
 #pragma unroll
         for (int sl = 0; sl < kXcdSl; ++sl)
 #pragma unroll
@@ -1138,7 +1261,21 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
             acc_t acc0 = acc_t{0, 0, 0, 0}, acc1 = acc_t{0, 0, 0, 0};
 #pragma unroll
             for (int dh = 0; dh < DH; ++dh) {
-            {
+            if constexpr (kD1Dma) {
+                // wave k's piece r is the rows 8 k + 64 r .. + 7 (the rows of the groups it waited for, as below): 1 KB, lane L the
+                // chunk xcd_d1_src_byte of it, written at base + 16 L by the load itself.  Same descriptor, same cache bits (aux 16:
+                // sc1) as xcd_ld4; the wave-uniform part of the source address rides in the scalar offset, which the LDS address
+                // does not see.  (BT >= 64: every wave has DR whole pieces inside the buffer.)
+                constexpr int DR = BH * 8 / kXcdThreads;
+                static_assert(DR >= 1 && DR * kXcdThreads == BH * 8 && kXcdThreads == 512 && kP2H == kXcdD1DmaLd, "kD1Dma: whole 1 KB pieces, rows of 128 bytes");
+                const int voff = xcd_d1_src_byte(0, lane);
+                const int wave_u = __builtin_amdgcn_readfirstlane(wave);  // (a scalar: else the scalar offset and M0 get a loop over "distinct values" each)
+#pragma unroll
+                for (int r = 0; r < DR; ++r) {
+                    const int row0 = 8 * wave_u + 64 * r;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(r_d1, (__attribute__((address_space(3))) void*)(d1s + row0 * kXcdD1DmaLd), 16, voff, row0 * 128, 0, 16);
+                }
+            } else {
                 constexpr int DR = (BH * 8 + kXcdThreads - 1) / kXcdThreads;
                 vec4 dv[DR];
 #pragma unroll
@@ -1151,6 +1288,9 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
             }
             // (d1s was last read by the gradient of step j - 1, behind the barriers that follow the update and the forward)
             if (kWaveWaits && wave == 1 && dh == 0) XSTAMP(7);
+            // (kD1Dma: the staging barrier must see the loads retired -- they count on vmcnt like any load, and nothing else of this
+            // wave is in flight here: the prefetch is issued behind the barrier.  The image is read only behind it.)
+            if constexpr (kD1Dma) xcd_drain();
             __syncthreads();
             if (kWaveWaits && dh == 0 && s_abort) return;                  // (a wave's own wait expired: everybody leaves here)
             if (wave == 1 && dh == 0) XSTAMP(8);
@@ -1184,17 +1324,19 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                 constexpr int NQB = BH / 32;                               // blocks of eight k-steps (four samples each)
                 // hand-pipelined: the operands of block qb + 1 are requested before the MFMAs of block qb issue, and fences keep the
                 // scheduler from folding that back into load-wait-MFMA triples (which ran at ~100 cycles per MFMA instead of 32)
-                const T* ap = d1s + g4 * kXcdD1Ld + umt * 16 + n;
+                // (kD1Dma: k-step q reads row 4 q + g4, whose parity is g4's -- the swizzle is in the lane's base, the k stride an immediate)
+                constexpr int kD1Ld = kD1Dma ? kXcdD1DmaLd : kXcdD1Ld;
+                const T* ap = kD1Dma ? d1s + xcd_d1_word(g4, umt * 16 + n) : d1s + g4 * kXcdD1Ld + umt * 16 + n;
                 const T* bp = xb + g4 * 16 + n;
                 T av[2][8], bv[2][8];
 #pragma unroll
-                for (int q = 0; q < 8; ++q) { av[0][q] = ap[4 * q * kXcdD1Ld]; bv[0][q] = bp[4 * q * 16]; }
+                for (int q = 0; q < 8; ++q) { av[0][q] = ap[4 * q * kD1Ld]; bv[0][q] = bp[4 * q * 16]; }
 #pragma unroll
                 for (int qb = 0; qb < NQB; ++qb) {
                     if (qb + 1 < NQB) {
 #pragma unroll
                         for (int q = 0; q < 8; ++q) {
-                            av[(qb + 1) & 1][q] = ap[4 * (8 * (qb + 1) + q) * kXcdD1Ld];
+                            av[(qb + 1) & 1][q] = ap[4 * (8 * (qb + 1) + q) * kD1Ld];
                             bv[(qb + 1) & 1][q] = bp[4 * (8 * (qb + 1) + q) * 16];
                         }
                     }
@@ -1237,6 +1379,10 @@ __global__ __launch_bounds__(kXcdThreads) void k_xcd_epoch(
                     const T wn = wcur[i] - scale * gsum[i];
                     wcur[i] = wvalid[i] ? wn : (T)0;
                 }
+                if constexpr (kW0ByHidden) {                           // (four ds_write_b32, 4 cycles each, where the one b128 store costs 13)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) wsl[xcd_w0_word(umt * 16 + 4 * g4 + i, usl * 16 + n)] = wcur[i];
+                } else
                 store4<T>(wsl + (usl * 16 + n) * kP2H + umt * 16, lane, acc_t{wcur[0], wcur[1], wcur[2], wcur[3]});
                 if (wave == 1) XSTAMP(9);
             }

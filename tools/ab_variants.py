@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """A/B of kernel variants on one box: builds librcn_hip with extra -D flags into mercer_research_amd/variants/ (here, on the CPU:
 `python tools/ab_variants.py build name=-DFLAG1,-DFLAG2 ...`), then on the GPU box times the resident kernel's step with every variant
-found there, each in its own process (`python tools/ab_variants.py run [B] [rounds]`).  Diagnostic only."""
+found there, each in its own process (`python tools/ab_variants.py run [B] [rounds]`).  Diagnostic only.
+The switches csrc/dense_xcd.hpp knows, each one part of the resident step off on top of the others: RCN_AB_TWO_TOP_WAITS, RCN_AB_NO_TAIL_COST,
+RCN_AB_NO_WORDS_BY_USE, RCN_AB_NO_D1_DMA, RCN_AB_NO_W0_BY_HIDDEN (and RCN_AB_RAISE_INLINE), e.g.
+`build result= no_d1_dma=-DRCN_AB_NO_D1_DMA no_w0_by_hidden=-DRCN_AB_NO_W0_BY_HIDDEN`."""
 import json
 import os
 import subprocess

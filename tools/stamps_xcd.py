@@ -48,8 +48,10 @@ t0 = r[r > 0].min()
 rel = np.where(r > 0, (r - t0) / 100.0, np.nan)
 # (6, 7: the f32 forms wait per wave -- wave 1 for the groups 1, 9, 17, 25 whose rows it stages, no barrier in front of the loads;
 # the f64 forms wait for all flagB on wave 1 and pass a barrier: there 7 is "past that barrier")
+# (7 -> 8 is the delta_1 staging as the barrier sees it; 10 -> 13, 14, 15 is "barrier behind the update" to a wave's forward stored: the
+# stretch that starts with the forward's W_0 operand reads)
 names = ["0 step top", "1 slab+tail flags seen", "2 slab part sums in LDS (wave 7)", "3 past barrier (wave 0)", "4 tail done", "5 flagB stored", "6 flagB seen (wave 1: its own groups)",
-         "7 wave 1's delta_1 rows in LDS", "8 past staging barrier", "9 gradient MFMAs done, slice updated", "10 past barrier behind the update", "11 forward stored, batch moved in, drained",
+         "7 wave 1's delta_1 loads issued (they write LDS themselves; before kD1Dma: its rows in LDS)", "8 past staging barrier", "9 gradient MFMAs done, slice updated", "10 past barrier behind the update", "11 forward stored, batch moved in, drained",
          "12 flagA / flagT stored", "13 forward done wave 0", "14 forward done wave 4", "15 forward done wave 7"]
 if TAIL:
     names[13:16] = ["13 slab sums done (wave 0)", "14 a_1 in LDS (wave 0)", "15 delta_2 in LDS (wave 0)"]
