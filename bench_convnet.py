@@ -6,6 +6,7 @@ network BASELINE.json's north_star asks for, on the configs SURVEY.md §8(d) fix
   synth224  synthetic 224x224x3, 8 conv layers, 128 images per GPU (global batch 1024 on 8 GPUs)                    (configs[3])
   mnist   MNIST shape 28x28x1 LeNet-style: conv 1->32, pool, conv 32->64, pool -> 3136 -> 128 -> 10, B = 256      (configs[1], trainable form)
   cifar_bn  cifar with every conv + ReLU written Conv2d -> BatchNorm2d -> ReLU: ("conv_linear", n), ("bn_relu",) (not bf16_stored)
+  cifar_res cifar_bn with a basic residual block (identity shortcut) behind each conv_linear, bn_relu pair: ... ("bn_add_relu", 4)
 
 fp32 activations / weights, fp32 MFMA (v_mfma_f32_32x32x2_f32; peak 157.3 TFLOP/s).  Reports achieved TFLOP/s of the whole
 training step (algorithmic 2*MACs of forward + dgrad + wgrad) and its fraction of the fp32 MFMA peak.  The reference has no
@@ -25,6 +26,10 @@ CONFIGS = {
 }
 # the CIFAR net as torch writes it, Conv2d -> BatchNorm2d -> ReLU: every ("conv", n) is ("conv_linear", n), ("bn_relu",)
 CONFIGS["cifar_bn"] = (CONFIGS["cifar"][0], tuple(m for l in CONFIGS["cifar"][1] for m in ((("conv_linear", l[1]), ("bn_relu",)) if l[0] == "conv" else (l,))), CONFIGS["cifar"][2])
+# cifar_bn with one basic residual block of the stage's width behind each of its three conv_linear, bn_relu pairs, in front of the pool:
+# conv_linear n, bn_relu, conv_linear n, ("bn_add_relu", 4) -- relu(bn(conv(relu(bn(conv(x))))) + x), x the pair's output four layers back
+CONFIGS["cifar_res"] = (CONFIGS["cifar"][0], tuple(m for l in CONFIGS["cifar"][1] for m in ((("conv_linear", l[1]), ("bn_relu",), ("conv_linear", l[1]), ("bn_relu",), ("conv_linear", l[1]),
+                                                                                                  ("bn_add_relu", 4)) if l[0] == "conv" else (l,))), CONFIGS["cifar"][2])
 F32_MFMA_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD
 BF16_MFMA_PEAK_TFLOPS = 2516.8    # same guide: dense bf16 MFMA = 16x the fp32 MFMA rate (~2.5 PFLOP/s; never the 2:1-sparsity figure)
 HBM_PEAK_GBS = 8000.0

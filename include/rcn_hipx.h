@@ -31,10 +31,21 @@ typedef enum {
     RCN_HIPX_DENSE = 3,          /* final dense + bias (logits); out = classes (any; padded to 32 internally)               */
     RCN_HIPX_CONV3X3 = 4,        /* 3x3, stride 1, pad 1, + bias, NO activation; out = output channels (multiple of 32).
                                     It exists for batch normalisation: the layer directly behind it must be
-                                    RCN_HIPX_BN_RELU (anything else: -2 from rcn_hipx_create)                                */
-    RCN_HIPX_BN_RELU = 5         /* torch.nn.BatchNorm2d(C) + ReLU over the map of the RCN_HIPX_CONV3X3 layer directly in
+                                    RCN_HIPX_BN_RELU or RCN_HIPX_BN_ADD_RELU (anything else: -2 from rcn_hipx_create)        */
+    RCN_HIPX_BN_RELU = 5,        /* torch.nn.BatchNorm2d(C) + ReLU over the map of the RCN_HIPX_CONV3X3 layer directly in
                                     front of it (anything else in front: -2 from rcn_hipx_create); out ignored.  Its
                                     parameters are one [W | b] block with K = 1: W[1][C] = gamma, b[C] = beta               */
+    RCN_HIPX_BN_ADD_RELU = 6     /* the end of a residual block with an identity shortcut (torchvision's BasicBlock):
+                                    y = relu(BatchNorm2d(z) + s) over the map z of the RCN_HIPX_CONV3X3 layer directly in
+                                    front of it; parameters, running statistics and every rcn_hipx_*bn* call as for
+                                    RCN_HIPX_BN_RELU.  out is NOT a width: it is the distance d >= 2 to the skip's source,
+                                    s = the output of layer i - d (this layer being layer i).  The source must exist (not
+                                    the net's input: -2), be a RCN_HIPX_CONV3X3_RELU, RCN_HIPX_BN_RELU,
+                                    RCN_HIPX_BN_ADD_RELU or RCN_HIPX_MAXPOOL2 layer whose output has this layer's height,
+                                    width and channels (-2; so no pool lies between them), not be a convolution with a
+                                    max-pool behind it (-2: name the pool), and feed no other RCN_HIPX_BN_ADD_RELU (-3).
+                                    d < 2: -1.  A basic block behind any such layer: CONV3X3 C, BN_RELU, CONV3X3 C,
+                                    BN_ADD_RELU 4.  Not with RCN_HIPX_BF16_STORED (-3), as RCN_HIPX_BN_RELU                 */
 } rcn_hipx_layer_kind;
 
 typedef struct rcn_hipx_layer { int32_t kind; int32_t out; } rcn_hipx_layer;
@@ -655,7 +666,9 @@ int  rcn_hipx_plan_micro_net(const rcn_hipx_net* net, int batch, int kind, char*
 /* algorithmic FLOPs of one training step at batch B (2 * MACs; forward + dgrad + wgrad) */
 int  rcn_hipx_step_flops(const rcn_hipx_net* net, int B, double* flops);
 
-/* ---- batch normalisation (csrc/convnet_bn.hpp): RCN_HIPX_BN_RELU layers, torch.nn.BatchNorm2d semantics ----
+/* ---- batch normalisation (csrc/convnet_bn.hpp): RCN_HIPX_BN_RELU and RCN_HIPX_BN_ADD_RELU layers ("such a layer" below is either
+ * kind; the second adds its skip between the normalisation and the ReLU and is counted, listed and reset like the first),
+ * torch.nn.BatchNorm2d semantics ----
  * A training forward (every step, micro-step and gradients call) normalises with the statistics of ITS batch -- biased variance,
  * invstd = 1 / sqrt(var + eps) -- and advances the running statistics r <- (1 - momentum) * r + momentum * s, with the unbiased variance
  * var * M / (M - 1) for the running variance (M = B * H * W rows; M < 2: -2, nothing enqueued).  All of it is enqueued on the net's stream

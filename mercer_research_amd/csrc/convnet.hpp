@@ -466,7 +466,7 @@ __device__ inline void store_flipped(const FlipSpec& f, long long i, float v) {
 // mostly latency, seven of them per CIFAR step).  Nothing updates a weight before every input-gradient kernel has read it, so the
 // jobs are independent.  Job q owns workgroups [first_block, next job's first_block); a workgroup of 1024 threads sums 1024 / g elements
 // in g chunk groups (g = the power of two at or above the chunk count, at most 32); groups are combined as a fixed tree: bit-reproducible.
-constexpr int kMaxReduceJobs = 16;
+constexpr int kMaxReduceJobs = 32;          // (a CIFAR net of three residual blocks has 20 layers with parameters; the kernel argument stays below 2.5 KB)
 struct ReduceJob {
     float* p;                 // [W | b] of the layer
     float* grad;              // or nullptr

@@ -1,4 +1,5 @@
 // convnet_bn.hpp -- Track X: batch normalisation + ReLU behind a bias-only 3x3 convolution (RCN_HIPX_BN_RELU behind RCN_HIPX_CONV3X3),
+// and the same with an identity skip added in front of the ReLU (RCN_HIPX_BN_ADD_RELU: k_bn_apply_relu<EVAL, ADD>, k_skip_bwd_add),
 // torch.nn.BatchNorm2d(C) followed by ReLU over an NHWC fp32 map x[M][C], M = B * H * W rows, C % 32 == 0.  Every kernel is a streaming
 // pass: one thread per FOUR consecutive channels, 16-byte accesses, no atomics of any kind.
 //
@@ -180,10 +181,12 @@ __global__ __launch_bounds__(kBnFinishThreads) void k_bn_stats_finish(const doub
     }
 }
 
-// y = max(0, fl(fl(xh * gamma) + beta)), xh = fl(fl(x - mean) * invstd); EVAL: stat2 is the running variance, else the batch's invstd
-template <bool EVAL>
-__global__ __launch_bounds__(kBnThreads) void k_bn_apply_relu(const float* __restrict__ x, float* __restrict__ y, long long n4, int C, const float* __restrict__ mean,
-                                                              const float* __restrict__ stat2, const float* __restrict__ gamma, const float* __restrict__ beta, float eps) {
+// y = max(0, fl(fl(xh * gamma) + beta)), xh = fl(fl(x - mean) * invstd); EVAL: stat2 is the running variance, else the batch's invstd.
+// ADD (RCN_HIPX_BN_ADD_RELU): y = max(0, fl(fl(fl(xh * gamma) + beta) + s)), s the skip's map, loaded as 16 bytes beside x
+template <bool EVAL, bool ADD>
+__global__ __launch_bounds__(kBnThreads) void k_bn_apply_relu(const float* __restrict__ x, const float* __restrict__ s, float* __restrict__ y, long long n4, int C,
+                                                              const float* __restrict__ mean, const float* __restrict__ stat2, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, float eps) {
 #pragma clang fp contract(off)
     const int C4 = C / 4;
     long long e = (long long)blockIdx.x * kBnThreads + threadIdx.x;
@@ -193,10 +196,18 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_apply_relu(const float* __res
     f32x4 is = bn_load4(stat2 + c);
     if (EVAL) is = bn_invstd_of_var(is, eps);
     for (; e < n4; e += (long long)gridDim.x * kBnThreads) {
-        const f32x4 xh = bn_xhat(bn_load4(x + e * 4), mu, is);
+        const f32x4 xv = bn_load4(x + e * 4);
+        f32x4 sv;
+        if (ADD) sv = bn_load4(s + e * 4);
+        const f32x4 xh = bn_xhat(xv, mu, is);
         f32x4 v;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { const float t = xh[k] * ga[k]; const float u = t + be[k]; v[k] = u > 0.f ? u : 0.f; }
+        for (int k = 0; k < 4; ++k) {
+            const float t = xh[k] * ga[k];
+            float u = t + be[k];
+            if (ADD) u = u + sv[k];
+            v[k] = u > 0.f ? u : 0.f;
+        }
         *reinterpret_cast<f32x4*>(y + e * 4) = v;
     }
 }
@@ -269,6 +280,34 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_dx(const float* __restric
 #pragma unroll
         for (int k = 0; k < 4; ++k) { const float a = g[k] - k1[k]; const float b = xh[k] * k2[k]; const float d = a - b; v[k] = k0[k] * d; }
         *reinterpret_cast<f32x4*>(dx + e * 4) = v;
+    }
+}
+
+// ---- the skip's half of a RCN_HIPX_BN_ADD_RELU layer's backward pass: the gradient of the sum, g = dy of that layer (GATE_SELF: gated
+// here with its output, y_self > 0; else it arrived gated), added to the gradient of the skip's source once the input-gradient kernel of
+// the layer above the source has written it:
+//     dsrc = fl(dsrc + g)         GATE_SRC: g counts only where y_src > 0 -- dsrc already is the source's dZ, and the skip's share
+//                                 passes the same gate
+// One thread per four floats, every element read and written by the same thread, grid-stride, no atomics: one order, one result.
+template <bool GATE_SELF, bool GATE_SRC>
+__global__ __launch_bounds__(kBnThreads) void k_skip_bwd_add(float* __restrict__ dsrc, const float* __restrict__ dy, const float* __restrict__ y_self,
+                                                             const float* __restrict__ y_src, long long n4) {
+    for (long long e = (long long)blockIdx.x * kBnThreads + threadIdx.x; e < n4; e += (long long)gridDim.x * kBnThreads) {
+        f32x4 a = bn_load4(dsrc + e * 4);
+        f32x4 g = bn_load4(dy + e * 4);
+        if (GATE_SELF) {
+            const f32x4 yv = bn_load4(y_self + e * 4);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g[k] = yv[k] > 0.f ? g[k] : 0.f;
+        }
+        if (GATE_SRC) {
+            const f32x4 yv = bn_load4(y_src + e * 4);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g[k] = yv[k] > 0.f ? g[k] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a[k] = a[k] + g[k];
+        *reinterpret_cast<f32x4*>(dsrc + e * 4) = a;
     }
 }
 

@@ -29,7 +29,7 @@ namespace rcnx {
 constexpr int kStateSections = 6;           // parameters, velocity, Adam m, Adam v, average, accumulator: bit s of a section mask
 constexpr int kStateScalarsBytes = 256;     // the scalars block; the three copies sit at these byte offsets
 constexpr int kStateTickAt = 0, kStateTickBytes = 32, kStateDropAt = 32, kStateDropBytes = 8, kStateClipAt = 40, kStateClipBytes = 16;
-constexpr int kStateMaxJobs = 16;           // layers with parameters (the reduction launch takes as many: kMaxReduceJobs)
+constexpr int kStateMaxJobs = 32;           // layers with parameters (the reduction launch takes as many: kMaxReduceJobs)
 constexpr int kStateThreads = 256;
 constexpr int kStateUnit = 4096;            // elements of one layer per workgroup and trip: 256 threads x four 16-byte pieces
 constexpr int kStateMaxBlocks = 2048;       // the grid's cap; the units beyond it are reached by the stride

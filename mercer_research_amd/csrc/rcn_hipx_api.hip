@@ -62,11 +62,16 @@ struct LayerShape {
     long long w_off = 0, b_off = 0;       // padded flat layout
     long long lw_off = 0, lb_off = 0;     // logical flat layout
     bool pool_follows = false;
+    // an identity skip (RCN_HIPX_BN_ADD_RELU): the layer whose output this layer adds in front of its ReLU, and -- in that source -- the
+    // layer that adds its output; -1: none
+    int skip_src = -1, skip_by = -1;
 };
 // the kinds by what the walks ask of them: a 3x3 convolution (with or without ReLU), and a layer whose W is a matrix with a tap-flipped
 // copy and bf16 operand copies (every layer with a [W | b] block but batch normalisation, whose block is [gamma | beta])
 inline bool is_conv(int kind) { return kind == RCN_HIPX_CONV3X3_RELU || kind == RCN_HIPX_CONV3X3; }
-inline bool has_matrix(int kind) { return kind != RCN_HIPX_MAXPOOL2 && kind != RCN_HIPX_BN_RELU; }
+// batch normalisation, with or without a skip added in front of its ReLU: one [gamma | beta] block, statistics and buffers either way
+inline bool is_bn(int kind) { return kind == RCN_HIPX_BN_RELU || kind == RCN_HIPX_BN_ADD_RELU; }
+inline bool has_matrix(int kind) { return kind != RCN_HIPX_MAXPOOL2 && !is_bn(kind); }
 // ... and what it holds on the device
 struct Layer : LayerShape {
     Buf out, idx, dout;     // activation (post-ReLU / pooled), pool arg-max, gradient wrt the layer's OUTPUT
@@ -512,11 +517,11 @@ int launch_dropout_bwd(rcn_hipx_net* n, size_t i, int B) {
 
 // ---- batch normalisation (convnet_bn.hpp): a RCN_HIPX_BN_RELU layer normalises the map of the RCN_HIPX_CONV3X3 layer in front of it
 inline const char* const kBnStoreGap = "bf16 storage (RCN_HIPX_BF16_STORED) does not cover batch normalisation: its maps are fp32 (RCN_HIPX_BF16 rounds the convolutions' operands and works)";
-int bn_layers(const rcn_hipx_net* n) { int k = 0; for (const Layer& l : n->L) k += l.kind == RCN_HIPX_BN_RELU; return k; }
+int bn_layers(const rcn_hipx_net* n) { int k = 0; for (const Layer& l : n->L) k += is_bn(l.kind); return k; }
 // a training forward needs two rows per channel at least (the unbiased variance): asked before anything is enqueued
 int bn_rows_ok(rcn_hipx_net* n, int B) {
     for (const Layer& l : n->L)
-        if (l.kind == RCN_HIPX_BN_RELU && (long long)B * l.oH * l.oW < 2) return fail(n, -2, "batch normalisation needs at least two rows (B * H * W >= 2) in a training forward");
+        if (is_bn(l.kind) && (long long)B * l.oH * l.oW < 2) return fail(n, -2, "batch normalisation needs at least two rows (B * H * W >= 2) in a training forward");
     return 0;
 }
 float* bn_mean(const Layer& l) { return (float*)l.bn.p; }
@@ -526,14 +531,14 @@ float* bn_run_var(const Layer& l) { return (float*)l.bn.p + 3 * l.CoutP; }
 // running mean 0, running variance 1 in every such layer, on the net's stream
 int bn_reset_stats(rcn_hipx_net* n) {
     for (const Layer& l : n->L) {
-        if (l.kind != RCN_HIPX_BN_RELU) continue;
+        if (!is_bn(l.kind)) continue;
         const std::vector<float> init = [&] { std::vector<float> v((size_t)4 * l.CoutP, 0.f); for (int c = 0; c < l.CoutP; ++c) v[(size_t)3 * l.CoutP + c] = 1.f; return v; }();
         XTRY(n, hipMemcpyAsync(l.bn.p, init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice, n->stream));
         XTRY(n, hipStreamSynchronize(n->stream));       // (the staging vector ends here)
     }
     return 0;
 }
-// layer i (RCN_HIPX_BN_RELU) of a forward pass over x[M][C]: train -- the batch's statistics (two launches; the running statistics
+// layer i (RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU) of a forward pass over x[M][C]: train -- the batch's statistics (two launches; the running statistics
 // advance), then the apply launch on them; else the apply launch on the running statistics
 int launch_bn_forward(rcn_hipx_net* n, size_t i, const float* x, int B, bool train) {
     Layer& l = n->L[i];
@@ -542,6 +547,12 @@ int launch_bn_forward(rcn_hipx_net* n, size_t i, const float* x, int B, bool tra
     const int parts = bn_parts(M);
     const unsigned blocks = bn_stream_blocks(n4, C / 4);
     if (train && !n->dry && (size_t)parts * 2 * C * sizeof(double) > l.bn_part.cap) return fail(n, -3, "internal: more partial sums than the layer's buffer holds");
+    // RCN_HIPX_BN_ADD_RELU: the skip's map (the source layer's output, of this layer's shape: describe_layers) is added in front of the ReLU
+    const bool add = l.skip_src >= 0;
+    const float* const skip = add ? (const float*)n->L[l.skip_src].out.p : (const float*)nullptr;
+    auto apply = [&](auto kernel, const float* mean, const float* stat2) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBnThreads), 0, n->stream, x, skip, (float*)l.out.p, n4, C, mean, stat2, (const float*)P(n, l.w_off), (const float*)P(n, l.b_off), n->bn_eps);
+    };
     if (train) {
         if (!dry_note(n, "  bn-stats %dx%dx%d: k_bn_stats, %d partials of %lld rows, then k_bn_stats_finish (one workgroup, %d threads per channel; momentum %g, eps %g)",
                       l.oH, l.oW, C, parts, bn_rows_per_part(M), bn_team(C), (double)n->bn_momentum, (double)n->bn_eps)) {
@@ -551,13 +562,16 @@ int launch_bn_forward(rcn_hipx_net* n, size_t i, const float* x, int B, bool tra
                                bn_mean(l), bn_invstd(l), bn_run_mean(l), bn_run_var(l));
             XTRY(n, hipGetLastError());
         }
-        if (dry_note(n, "  bn-relu %dx%dx%d: k_bn_apply_relu, %u workgroups (the batch's mean and invstd)", l.oH, l.oW, C, blocks)) return 0;
-        hipLaunchKernelGGL(k_bn_apply_relu<false>, dim3(blocks), dim3(kBnThreads), 0, n->stream, x, (float*)l.out.p, n4, C, (const float*)bn_mean(l), (const float*)bn_invstd(l),
-                           (const float*)P(n, l.w_off), (const float*)P(n, l.b_off), n->bn_eps);
+        if (add ? dry_note(n, "  bn-add-relu %dx%dx%d: k_bn_apply_add_relu, %u workgroups (the batch's mean and invstd; skip: the output of layer %d)", l.oH, l.oW, C, blocks, l.skip_src)
+                : dry_note(n, "  bn-relu %dx%dx%d: k_bn_apply_relu, %u workgroups (the batch's mean and invstd)", l.oH, l.oW, C, blocks)) return 0;
+        if (add) apply(k_bn_apply_relu<false, true>, bn_mean(l), bn_invstd(l));
+        else apply(k_bn_apply_relu<false, false>, bn_mean(l), bn_invstd(l));
     } else {
-        if (dry_note(n, "  bn-relu %dx%dx%d: k_bn_apply_relu<eval>, %u workgroups (scale and shift from the running statistics, eps %g)", l.oH, l.oW, C, blocks, (double)n->bn_eps)) return 0;
-        hipLaunchKernelGGL(k_bn_apply_relu<true>, dim3(blocks), dim3(kBnThreads), 0, n->stream, x, (float*)l.out.p, n4, C, (const float*)bn_run_mean(l), (const float*)bn_run_var(l),
-                           (const float*)P(n, l.w_off), (const float*)P(n, l.b_off), n->bn_eps);
+        if (add ? dry_note(n, "  bn-add-relu %dx%dx%d: k_bn_apply_add_relu<eval>, %u workgroups (scale and shift from the running statistics, eps %g; skip: the output of layer %d)",
+                           l.oH, l.oW, C, blocks, (double)n->bn_eps, l.skip_src)
+                : dry_note(n, "  bn-relu %dx%dx%d: k_bn_apply_relu<eval>, %u workgroups (scale and shift from the running statistics, eps %g)", l.oH, l.oW, C, blocks, (double)n->bn_eps)) return 0;
+        if (add) apply(k_bn_apply_relu<true, true>, bn_run_mean(l), bn_run_var(l));
+        else apply(k_bn_apply_relu<true, false>, bn_run_mean(l), bn_run_var(l));
     }
     XTRY(n, hipGetLastError());
     return 0;
@@ -599,7 +613,7 @@ int forward(rcn_hipx_net* n, const float* x, int B, size_t n_layers = (size_t)-1
             // bias only (epilogue 1), no conv+pool fusion: what follows is batch normalisation, on an fp32 map
             if (n->store16) return fail(n, -3, kBnStoreGap);
             RTRY(launch_conv(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShape{B, l.H, l.W, l.Cin, l.CoutP}, 3, 1, nullptr, nullptr, false, wb_of(n, l.wbf_off)));
-        } else if (l.kind == RCN_HIPX_BN_RELU) {
+        } else if (is_bn(l.kind)) {
             if (n->store16) return fail(n, -3, kBnStoreGap);
             RTRY(launch_bn_forward(n, i, cur, B, train));
         } else {
@@ -669,6 +683,29 @@ int launch_bn_backward(rcn_hipx_net* n, size_t i, int B, bool gated, float* grad
     return reduce_slab(n, i, 1, 1, ConvShape{B, 1, 1, 1, C}, grad, apply);
 }
 
+// The skip's half of the backward pass of the RCN_HIPX_BN_ADD_RELU layer fed by layer `src`: that layer's dout (the gradient of the sum,
+// gated like its batch-normalisation half: by the pool's backward, by the convolution above, or here with out > 0) is ADDED to dout of
+// `src`, which the input-gradient kernel of layer src + 1 has just written.  src_gated: that kernel's epilogue gated dout[src] with
+// out[src], so dout[src] is the source's dZ and the skip's share passes the same gate; a pool source gates in its own backward.
+int launch_skip_bwd(rcn_hipx_net* n, size_t src, int B, bool src_gated) {
+    Layer& s = n->L[src];
+    Layer& l = n->L[s.skip_by];
+    const bool gated = l.pool_follows || n->bw.gated[s.skip_by];
+    const int C = l.CoutP;
+    const long long n4 = (long long)B * l.oH * l.oW * (C / 4);
+    const unsigned blocks = bn_stream_blocks(n4, C / 4);
+    if (dry_note(n, "  skip-bwd %dx%dx%d: k_skip_bwd_add, %u workgroups into layer %d's gradient (the skip's gradient %s; %s)", l.oH, l.oW, C, blocks, (int)src,
+                 l.pool_follows ? "gated by the pool's backward" : gated ? "gated by the convolution above" : "gated here (out > 0)",
+                 (src_gated ? "then gated by layer " + std::to_string(src) + "'s output" : "ungated: layer " + std::to_string(src) + " is a pool").c_str())) return 0;
+    auto add = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBnThreads), 0, n->stream, (float*)s.dout.p, (const float*)l.dout.p, (const float*)l.out.p, (const float*)s.out.p, n4);
+    };
+    if (gated) { if (src_gated) add(k_skip_bwd_add<false, true>); else add(k_skip_bwd_add<false, false>); }
+    else { if (src_gated) add(k_skip_bwd_add<true, true>); else add(k_skip_bwd_add<true, false>); }
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+
 // the step's ONE reduction launch over the queued jobs, or the launches that stand for it (rcn_hipx_api_update.ipp)
 // lr_dev (nullable): the update reads its rate from this device scalar instead of `lr` (same arithmetic on the same float)
 // micro: which micro-step of an accumulating net this is (kWholeStep: the net does not accumulate, or a gradients-only walk)
@@ -711,7 +748,7 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             XTRY(n, hipGetLastError());
             continue;
         }
-        if (l.kind == RCN_HIPX_BN_RELU) {
+        if (is_bn(l.kind)) {
             // its dout is gated by the pool's backward or by the convolution above (n->bw.gated); otherwise it gates itself
             RTRY(launch_bn_backward(n, (size_t)i, B, l.pool_follows || gated[i], grad, apply));
             continue;
@@ -743,11 +780,19 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             // this kernel's epilogue, so that layer finds its dZ ready instead of running a k_relu_bwd pass over the tensor
             const Layer& below = n->L[i - 1];
             // (batch normalisation below a convolution: gated here with its output, the same out > 0 rule; below a dense layer it gates itself)
-            const bool gate = below.kind == RCN_HIPX_CONV3X3_RELU || below.kind == RCN_HIPX_DENSE_RELU || (below.kind == RCN_HIPX_BN_RELU && conv);
+            const bool gate = below.kind == RCN_HIPX_CONV3X3_RELU || below.kind == RCN_HIPX_DENSE_RELU || (is_bn(below.kind) && conv);
             RTRY(launch_conv(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, ConvShape{s.N, s.H, s.W, s.Cout, s.Cin}, ks, gate ? 3 : 0,
                              nullptr, pooled[i].dP ? &pooled[i] : nullptr, false, wb_of(n, l.wbb_off), Store{stage16(n, i), stage16(n, i - 1)}));
             gated[i - 1] = gate;
             if (below.kind == RCN_HIPX_DENSE_RELU && dropout_on(*n)) RTRY(launch_dropout_bwd(n, (size_t)i - 1, B));      // before anything reads that gradient
+            // The layer below feeds the skip of a RCN_HIPX_BN_ADD_RELU layer further up: its gradient has a second contribution, and HERE
+            // is where it is complete -- the launch above has just OVERWRITTEN dout[i - 1], and that layer's dout was finished on the main
+            // stream when the walk passed it.  Nothing else touches dout[i - 1] in between: the side stream reads out[i - 1] and dout[i]
+            // for this layer's weight gradient below, never dout[i - 1], and layer i - 1's own weight gradient is ordered behind this
+            // point (stream_after at its iteration); a source pool's dout is read (k_pool_bwd, or pooled[] in the convolution below it)
+            // only in the iterations below this one.  The add belongs to THIS iteration and gated[] lives in n->bw, so a bucket of
+            // rcn_hipx_gradients_bucket_dev may end anywhere inside a block.
+            if (below.skip_by >= 0) RTRY(launch_skip_bwd(n, (size_t)i - 1, B, gate));
         }
         int chunks = 0;
         if (on_side) n->stream = n->side;
@@ -980,7 +1025,7 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
             l.Cout = l.CoutP = layers[i].out; l.oH = H; l.oW = W; l.K = 9 * C;
             C = l.Cout;
         } else if (l.kind == RCN_HIPX_MAXPOOL2) {
-            if (flat || i == 0 || (n->L.back().kind != RCN_HIPX_CONV3X3_RELU && n->L.back().kind != RCN_HIPX_BN_RELU)) return fail(n, -2, "max-pool must follow a convolution");
+            if (flat || i == 0 || (n->L.back().kind != RCN_HIPX_CONV3X3_RELU && !is_bn(n->L.back().kind))) return fail(n, -2, "max-pool must follow a convolution");
             if (H % 2 || W % 2) return fail(n, -3, "max-pool needs even height and width");
             l.Cout = l.CoutP = C; l.oH = H / 2; l.oW = W / 2; l.K = 0;
             n->L.back().pool_follows = true;
@@ -988,6 +1033,27 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
         } else if (l.kind == RCN_HIPX_BN_RELU) {
             if (i == 0 || n->L.back().kind != RCN_HIPX_CONV3X3) return fail(n, -2, "batch normalisation (RCN_HIPX_BN_RELU) must directly follow a RCN_HIPX_CONV3X3 layer");
             l.Cout = l.CoutP = C; l.oH = H; l.oW = W; l.K = 1;      // [gamma | beta]: a [W | b] block with K = 1
+        } else if (l.kind == RCN_HIPX_BN_ADD_RELU) {
+            // `out` is the distance to the skip's source, the output of layer i - out.  The source needs a gradient buffer that the
+            // input-gradient kernel of the layer above it writes in full (backward_layers adds the skip's share behind that launch) and an
+            // output that the forward pass writes: a ReLU layer or a pool of this layer's shape, not a convolution whose pool is fused away.
+            const int d = layers[i].out;
+            const std::string at = "layer " + std::to_string(i) + " (RCN_HIPX_BN_ADD_RELU): ";
+            if (i == 0 || n->L.back().kind != RCN_HIPX_CONV3X3) return fail(n, -2, at + "it must directly follow a RCN_HIPX_CONV3X3 layer");
+            if (d < 2) return fail(n, -1, at + "out is the distance to the skip's source and must be at least 2, not " + std::to_string(d));
+            const int src = i - d;
+            if (src < 0) return fail(n, -2, at + "the skip's source would lie in front of layer 0 (the net's input has no gradient buffer to add into)");
+            l.Cout = l.CoutP = C; l.oH = H; l.oW = W; l.K = 1;
+            Layer& s = n->L[src];
+            const std::string from = at + "the skip's source, layer " + std::to_string(src) + ", ";
+            if (s.kind != RCN_HIPX_CONV3X3_RELU && s.kind != RCN_HIPX_MAXPOOL2 && !is_bn(s.kind))
+                return fail(n, -2, from + "must be a RCN_HIPX_CONV3X3_RELU, RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_MAXPOOL2 layer (a RCN_HIPX_CONV3X3 map is not yet normalised)");
+            if (s.pool_follows) return fail(n, -2, from + "has a max-pool behind it: its own output is not written when the two fuse -- the source must be the pool");
+            if (s.oH != l.oH || s.oW != l.oW || s.CoutP != l.CoutP)
+                return fail(n, -2, from + "has another output shape (" + std::to_string(s.oH) + "x" + std::to_string(s.oW) + "x" + std::to_string(s.CoutP) + ", not " +
+                                   std::to_string(l.oH) + "x" + std::to_string(l.oW) + "x" + std::to_string(l.CoutP) + "): an identity skip crosses no pool and changes no width");
+            if (s.skip_by >= 0) return fail(n, -3, from + "already feeds the skip of layer " + std::to_string(s.skip_by) + ": one skip per source");
+            l.skip_src = src; s.skip_by = i;
         } else if (l.kind == RCN_HIPX_DENSE_RELU || l.kind == RCN_HIPX_DENSE) {
             const long long feat = flat ? C : (long long)H * W * C;
             if (feat % 32 || feat > 0x7fffffff) return fail(n, -3, "dense input features must be a multiple of 32");
@@ -997,7 +1063,7 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
             l.K = (int)feat; l.H = 1; l.W = 1; l.Cin = (int)feat; l.Cout = layers[i].out; l.CoutP = (l.Cout + 31) / 32 * 32; l.oH = l.oW = 1;
             C = l.Cout; flat = true; H = W = 1;
         } else return fail(n, -1, "unknown layer kind");
-        if (l.kind != RCN_HIPX_BN_RELU && i > 0 && n->L.back().kind == RCN_HIPX_CONV3X3) return fail(n, -2, "a RCN_HIPX_CONV3X3 layer must be followed by RCN_HIPX_BN_RELU");
+        if (!is_bn(l.kind) && i > 0 && n->L.back().kind == RCN_HIPX_CONV3X3) return fail(n, -2, "a RCN_HIPX_CONV3X3 layer must be followed by RCN_HIPX_BN_RELU or RCN_HIPX_BN_ADD_RELU");
         if (l.kind != RCN_HIPX_MAXPOOL2) {
             l.w_off = n->n_pad; n->n_pad += (long long)l.K * l.CoutP; l.b_off = n->n_pad; n->n_pad += l.CoutP;
             l.lw_off = n->n_log; n->n_log += (long long)l.K * l.Cout; l.lb_off = n->n_log; n->n_log += l.Cout;
@@ -1089,7 +1155,7 @@ int rcn_hipx_create(int device, int in_h, int in_w, int in_c, const rcn_hipx_lay
         XTRY(n, l.out.ensure(elems * sizeof(float)));
         XTRY(n, l.dout.ensure(elems * sizeof(float)));
         if (l.kind == RCN_HIPX_MAXPOOL2) XTRY(n, l.idx.ensure(elems));
-        if (l.kind == RCN_HIPX_BN_RELU) {
+        if (is_bn(l.kind)) {
             XTRY(n, l.bn.ensure((size_t)4 * l.CoutP * sizeof(float)));
             XTRY(n, l.bn_part.ensure((size_t)bn_parts_cap((long long)max_batch * l.oH * l.oW) * 2 * l.CoutP * sizeof(double)));
             XTRY(n, l.slab.ensure((size_t)2 * l.CoutP * sizeof(float)));
@@ -1217,7 +1283,7 @@ int rcn_hipx_init_params(rcn_hipx_net* n, uint64_t seed) {
     std::vector<float> flat((size_t)n->n_log, 0.f);
     for (const Layer& l : n->L) {
         if (l.kind == RCN_HIPX_MAXPOOL2) continue;
-        if (l.kind == RCN_HIPX_BN_RELU) { for (int c = 0; c < l.Cout; ++c) flat[l.lw_off + c] = 1.f; continue; }      // gamma = 1, beta = 0
+        if (is_bn(l.kind)) { for (int c = 0; c < l.Cout; ++c) flat[l.lw_off + c] = 1.f; continue; }      // gamma = 1, beta = 0
         std::normal_distribution<float> nd(0.f, std::sqrt(2.0f / (float)l.K));
         for (long long i = 0; i < (long long)l.K * l.Cout; ++i) flat[l.lw_off + i] = nd(gen);
     }
