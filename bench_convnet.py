@@ -7,6 +7,7 @@ network BASELINE.json's north_star asks for, on the configs SURVEY.md §8(d) fix
   mnist   MNIST shape 28x28x1 LeNet-style: conv 1->32, pool, conv 32->64, pool -> 3136 -> 128 -> 10, B = 256      (configs[1], trainable form)
   cifar_bn  cifar with every conv + ReLU written Conv2d -> BatchNorm2d -> ReLU: ("conv_linear", n), ("bn_relu",) (not bf16_stored)
   cifar_res cifar_bn with a basic residual block (identity shortcut) behind each conv_linear, bn_relu pair: ... ("bn_add_relu", 4)
+  cifar_res_gap  cifar_res ending as a ResNet does: its last pool and the 2048 -> 256 dense layer replaced by ("global_avgpool",), 8x8x128 -> 128 -> 10
 
 fp32 activations / weights, fp32 MFMA (v_mfma_f32_32x32x2_f32; peak 157.3 TFLOP/s).  Reports achieved TFLOP/s of the whole
 training step (algorithmic 2*MACs of forward + dgrad + wgrad) and its fraction of the fp32 MFMA peak.  The reference has no
@@ -30,6 +31,10 @@ CONFIGS["cifar_bn"] = (CONFIGS["cifar"][0], tuple(m for l in CONFIGS["cifar"][1]
 # conv_linear n, bn_relu, conv_linear n, ("bn_add_relu", 4) -- relu(bn(conv(relu(bn(conv(x))))) + x), x the pair's output four layers back
 CONFIGS["cifar_res"] = (CONFIGS["cifar"][0], tuple(m for l in CONFIGS["cifar"][1] for m in ((("conv_linear", l[1]), ("bn_relu",), ("conv_linear", l[1]), ("bn_relu",), ("conv_linear", l[1]),
                                                                                                   ("bn_add_relu", 4)) if l[0] == "conv" else (l,))), CONFIGS["cifar"][2])
+# cifar_res with a ResNet's ending: global average pooling over the last stage's 8x8x128 map in place of the last pool and the hidden dense
+# layer, in front of a 128 x 10 logits layer
+_res, _last_pool = CONFIGS["cifar_res"][1], max(i for i, l in enumerate(CONFIGS["cifar_res"][1]) if l[0] == "pool")
+CONFIGS["cifar_res_gap"] = (CONFIGS["cifar"][0], _res[:_last_pool] + (("global_avgpool",),) + tuple(l for l in _res[_last_pool + 1:] if l[0] != "dense_relu"), CONFIGS["cifar"][2])
 F32_MFMA_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD
 BF16_MFMA_PEAK_TFLOPS = 2516.8    # same guide: dense bf16 MFMA = 16x the fp32 MFMA rate (~2.5 PFLOP/s; never the 2:1-sparsity figure)
 HBM_PEAK_GBS = 8000.0

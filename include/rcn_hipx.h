@@ -35,7 +35,7 @@ typedef enum {
     RCN_HIPX_BN_RELU = 5,        /* torch.nn.BatchNorm2d(C) + ReLU over the map of the RCN_HIPX_CONV3X3 layer directly in
                                     front of it (anything else in front: -2 from rcn_hipx_create); out ignored.  Its
                                     parameters are one [W | b] block with K = 1: W[1][C] = gamma, b[C] = beta               */
-    RCN_HIPX_BN_ADD_RELU = 6     /* the end of a residual block with an identity shortcut (torchvision's BasicBlock):
+    RCN_HIPX_BN_ADD_RELU = 6,    /* the end of a residual block with an identity shortcut (torchvision's BasicBlock):
                                     y = relu(BatchNorm2d(z) + s) over the map z of the RCN_HIPX_CONV3X3 layer directly in
                                     front of it; parameters, running statistics and every rcn_hipx_*bn* call as for
                                     RCN_HIPX_BN_RELU.  out is NOT a width: it is the distance d >= 2 to the skip's source,
@@ -46,6 +46,14 @@ typedef enum {
                                     max-pool behind it (-2: name the pool), and feed no other RCN_HIPX_BN_ADD_RELU (-3).
                                     d < 2: -1.  A basic block behind any such layer: CONV3X3 C, BN_RELU, CONV3X3 C,
                                     BN_ADD_RELU 4.  Not with RCN_HIPX_BF16_STORED (-3), as RCN_HIPX_BN_RELU                 */
+    RCN_HIPX_GLOBAL_AVGPOOL = 7  /* torch.nn.AdaptiveAvgPool2d(1) + flatten(1) in front of the dense stage: y[b][c] = the
+                                    mean over (h, w) of the map x[b][h][w][c] of the layer directly in front of it, which
+                                    must be a RCN_HIPX_CONV3X3_RELU, RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or
+                                    RCN_HIPX_MAXPOOL2 layer (as layer 0, or behind a dense layer or another global average
+                                    pool: -2); out ignored, no parameters.  The dense layer behind it has K = C inputs,
+                                    whatever the input's height and width, and only dense layers may follow.  In the
+                                    backward pass it gates for the ReLU layer below it (a max-pool below gates itself).
+                                    Not with RCN_HIPX_BF16_STORED (-3): it reads an fp32 map (csrc/convnet_gap.hpp)          */
 } rcn_hipx_layer_kind;
 
 typedef struct rcn_hipx_layer { int32_t kind; int32_t out; } rcn_hipx_layer;
@@ -72,7 +80,8 @@ int  rcn_hipx_classes(const rcn_hipx_net* net);
  * now see dZ already rounded.  The stage's HBM traffic halves.  Covers nets whose first layer has 1 or 3 input channels, whose other
  * convolutions run on the LDS-tiled bf16 kernels (32 or a multiple of 64 input channels, options "halo" and "bf16_pipe" on) and
  * whose pools are fused into the convolution in front of them (even maps); rcn_hipx_set_precision walks the net's plan first and
- * returns -3 -- nothing changed -- with the reason in rcn_hipx_last_error if a layer is not covered. */
+ * returns -3 -- nothing changed -- with the reason in rcn_hipx_last_error if a layer is not covered (batch normalisation and
+ * RCN_HIPX_GLOBAL_AVGPOOL never are: they read fp32 maps). */
 enum { RCN_HIPX_FP32 = 0, RCN_HIPX_BF16 = 1, RCN_HIPX_BF16_STORED = 2 };
 int  rcn_hipx_set_precision(rcn_hipx_net* net, int mode);
 /* logical layout, host memory, all layers back to back: W_0[K][Cout], b_0[Cout], W_1 ... */

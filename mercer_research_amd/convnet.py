@@ -15,7 +15,7 @@ from . import _lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBX_PATH = os.path.join(HERE, "librcn_hipx.so")
-KIND = {"conv": 0, "pool": 1, "dense_relu": 2, "dense": 3, "conv_linear": 4, "bn_relu": 5, "bn_add_relu": 6}
+KIND = {"conv": 0, "pool": 1, "dense_relu": 2, "dense": 3, "conv_linear": 4, "bn_relu": 5, "bn_add_relu": 6, "global_avgpool": 7}
 
 
 class XLayer(C.Structure):
@@ -84,7 +84,7 @@ class StateDesc(C.Structure):
     def shape_and_layers(self):
         """(in_shape, layers) as ConvNet takes them; ("bn_add_relu", d) comes back with its distance: the descriptor stores it as `out`"""
         names = {v: k for k, v in KIND.items()}
-        layers = [(names[self.layers[i].kind],) if self.layers[i].kind in (KIND["pool"], KIND["bn_relu"]) else (names[self.layers[i].kind], int(self.layers[i].out))
+        layers = [(names[self.layers[i].kind],) if self.layers[i].kind in (KIND["pool"], KIND["bn_relu"], KIND["global_avgpool"]) else (names[self.layers[i].kind], int(self.layers[i].out))
                   for i in range(self.n_layers)]
         return (int(self.in_h), int(self.in_w), int(self.in_c)), layers
 
@@ -504,9 +504,11 @@ def warmup_cosine(n_steps: int, peak: float, warmup_steps: int, floor: float = 0
 
 class ConvNet:
     """layers: sequence of ("conv", Cout) | ("pool",) | ("dense_relu", units) | ("dense", classes) | ("conv_linear", Cout) | ("bn_relu",) |
-    ("bn_add_relu", d): torch's Conv2d -> BatchNorm2d -> ReLU is ("conv_linear", Cout), ("bn_relu",).  ("bn_add_relu", d) is
+    ("bn_add_relu", d) | ("global_avgpool",): torch's Conv2d -> BatchNorm2d -> ReLU is ("conv_linear", Cout), ("bn_relu",).  ("bn_add_relu", d) is
     relu(BatchNorm2d(z) + s) with s the output of the layer d places in front of it (d >= 2): torchvision's BasicBlock with an identity
-    shortcut is ("conv_linear", C), ("bn_relu",), ("conv_linear", C), ("bn_add_relu", 4) behind the layer that made the block's input."""
+    shortcut is ("conv_linear", C), ("bn_relu",), ("conv_linear", C), ("bn_add_relu", 4) behind the layer that made the block's input.
+    ("global_avgpool",) is AdaptiveAvgPool2d(1) -> flatten(1) behind the last map (a "conv", "bn_relu", "bn_add_relu" or "pool" layer): the
+    dense layer behind it has K = C inputs at any input resolution, and only dense layers may follow."""
 
     def __init__(self, in_shape: Tuple[int, int, int], layers: Sequence[tuple], max_batch: int, device: int = 0):
         import torch
@@ -1238,6 +1240,12 @@ class ConvNet:
                 # gradient and this layer's and writes the source's (the gate maps are not counted, as above)
                 m = H * W * Cc * 4
                 total += B * (3 * m + 4 * m + m + 3 * m)
+            elif l[0] == "global_avgpool":
+                # forward: the map read once and [B][C] written; backward: the map's gradient written once ([B][C] read; the gate map is
+                # not counted, as above)
+                m, o = H * W * Cc * 4, Cc * 4
+                total += B * ((m + o) + (o + m))
+                H, W, es_in = 1, 1, 4
             elif l[0] == "pool":
                 i, o = H * W * Cc * es_stage, (H // 2) * (W // 2) * Cc * es_stage
                 total += B * 2 * (i + o)

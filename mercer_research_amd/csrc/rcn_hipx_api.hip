@@ -30,6 +30,7 @@
 #include "convnet_dropout.hpp"
 #include "convnet_state.hpp"
 #include "convnet_bn.hpp"
+#include "convnet_gap.hpp"
 
 using namespace rcnx;
 
@@ -71,7 +72,9 @@ struct LayerShape {
 inline bool is_conv(int kind) { return kind == RCN_HIPX_CONV3X3_RELU || kind == RCN_HIPX_CONV3X3; }
 // batch normalisation, with or without a skip added in front of its ReLU: one [gamma | beta] block, statistics and buffers either way
 inline bool is_bn(int kind) { return kind == RCN_HIPX_BN_RELU || kind == RCN_HIPX_BN_ADD_RELU; }
-inline bool has_matrix(int kind) { return kind != RCN_HIPX_MAXPOOL2 && !is_bn(kind); }
+// a layer with a parameter block ([W | b] or [gamma | beta]): every kind but the two pools, which also take no `out`
+inline bool has_params(int kind) { return kind != RCN_HIPX_MAXPOOL2 && kind != RCN_HIPX_GLOBAL_AVGPOOL; }
+inline bool has_matrix(int kind) { return has_params(kind) && !is_bn(kind); }
 // ... and what it holds on the device
 struct Layer : LayerShape {
     Buf out, idx, dout;     // activation (post-ReLU / pooled), pool arg-max, gradient wrt the layer's OUTPUT
@@ -577,6 +580,38 @@ int launch_bn_forward(rcn_hipx_net* n, size_t i, const float* x, int B, bool tra
     return 0;
 }
 
+// ---- global average pooling (convnet_gap.hpp): a RCN_HIPX_GLOBAL_AVGPOOL layer turns the fp32 map in front of it into the dense stage's [B][C]
+inline const char* const kGapStoreGap = "bf16 storage (RCN_HIPX_BF16_STORED) does not cover global average pooling: it reads an fp32 map (RCN_HIPX_BF16 rounds the convolutions' operands and works)";
+// layer i (RCN_HIPX_GLOBAL_AVGPOOL) of a forward pass over x[B][H * W][C], training and evaluation alike
+int launch_gap_forward(rcn_hipx_net* n, size_t i, const float* x, int B) {
+    Layer& l = n->L[i];
+    const int C = l.CoutP, HW = l.H * l.W;
+    const dim3 grid((unsigned)B, (unsigned)gap_col_blocks(C));
+    if (dry_note(n, "  gap-fwd %dx%dx%d: k_gap_fwd, %u workgroups", l.H, l.W, C, grid.x * grid.y)) return 0;
+    hipLaunchKernelGGL(k_gap_fwd, grid, dim3(kGapThreads), 0, n->stream, x, (float*)l.out.p, HW, C);
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+// ... and of the backward pass: its dout[B][C], which the dense layer above wrote ungated, spread over the map into the dout of the layer
+// below.  gate: that layer is a ReLU layer and finds its dZ ready (the caller sets n->bw.gated); a max-pool below gates in its own backward.
+int launch_gap_backward(rcn_hipx_net* n, size_t i, int B, bool gate) {
+    Layer& l = n->L[i];
+    Layer& below = n->L[i - 1];
+    const int C = l.CoutP, HW = l.H * l.W;
+    const long long n4 = (long long)B * HW * (C / 4);
+    const unsigned blocks = bn_stream_blocks(n4, C / 4);
+    if (dry_note(n, "  gap-bwd %dx%dx%d: k_gap_bwd, %u workgroups (%s)", l.H, l.W, C, blocks,
+                 (gate ? "gated here with layer " + std::to_string(i - 1) + "'s output (out > 0)" : "ungated: layer " + std::to_string(i - 1) + " is a pool").c_str())) return 0;
+    if (gate) hipLaunchKernelGGL(k_gap_bwd<true>, dim3(blocks), dim3(kBnThreads), 0, n->stream, (const float*)l.dout.p, (const float*)below.out.p, (float*)below.dout.p, n4, HW, C);
+    else hipLaunchKernelGGL(k_gap_bwd<false>, dim3(blocks), dim3(kBnThreads), 0, n->stream, (const float*)l.dout.p, (const float*)nullptr, (float*)below.dout.p, n4, HW, C);
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+// who gated the dout of layer i when it is not the layer itself or a pool's backward: the layer above, in the plan's words
+const char* gated_above_words(const rcn_hipx_net* n, size_t i) {
+    return i + 1 < n->L.size() && n->L[i + 1].kind == RCN_HIPX_GLOBAL_AVGPOOL ? "gated by the global average pool above" : "gated by the convolution above";
+}
+
 // forward for batch B; returns pointer to logits (padded rows of CoutP)
 // train: the forward of a training step (step_front) -- with dropout on, every RCN_HIPX_DENSE_RELU layer's output goes through its site's
 // mask; every other forward (rcn_hipx_forward_dev, evaluation) never drops and never scales
@@ -586,6 +621,8 @@ int forward(rcn_hipx_net* n, const float* x, int B, size_t n_layers = (size_t)-1
     const float* cur = x;
     bool cur16 = false;                                  // `cur` is a bf16 tensor (RCN_HIPX_BF16_STORED)
     if (n_layers > n->L.size()) n_layers = n->L.size();
+    // (bf16 storage and a global average pool: refused with the pool's own reason, whatever the layers in front of it would say)
+    if (n->store16) for (const Layer& l : n->L) if (l.kind == RCN_HIPX_GLOBAL_AVGPOOL) return fail(n, -3, kGapStoreGap);
     for (size_t i = 0; i < n_layers; ++i) {
         Layer& l = n->L[i];
         if (l.kind == RCN_HIPX_MAXPOOL2) {
@@ -616,6 +653,8 @@ int forward(rcn_hipx_net* n, const float* x, int B, size_t n_layers = (size_t)-1
         } else if (is_bn(l.kind)) {
             if (n->store16) return fail(n, -3, kBnStoreGap);
             RTRY(launch_bn_forward(n, i, cur, B, train));
+        } else if (l.kind == RCN_HIPX_GLOBAL_AVGPOOL) {
+            RTRY(launch_gap_forward(n, i, cur, B));
         } else {
             // (the logits layer of a head that training runs as k_head_f32 is fp32 here too: what bf16 mode rounds is a matter of shape)
             RTRY(launch_conv(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShape{B, 1, 1, l.K, l.CoutP}, 1, l.kind == RCN_HIPX_DENSE_RELU ? 2 : 1, nullptr, nullptr,
@@ -660,7 +699,7 @@ int launch_bn_backward(rcn_hipx_net* n, size_t i, int B, bool gated, float* grad
     const int parts = bn_parts(M);
     const unsigned blocks = bn_stream_blocks(n4, C / 4);
     if (!n->dry && (size_t)parts * 2 * C * sizeof(double) > l.bn_part.cap) return fail(n, -3, "internal: more partial sums than the layer's buffer holds");
-    const char* const who = l.pool_follows ? "gated by the pool's backward" : gated ? "gated by the convolution above" : "gates itself (out > 0)";
+    const char* const who = l.pool_follows ? "gated by the pool's backward" : gated ? gated_above_words(n, i) : "gates itself (out > 0)";
     const float* const x = (const float*)cl.out.p;
     const float* const dy = (const float*)l.dout.p;
     const float* const y = (const float*)l.out.p;
@@ -695,7 +734,7 @@ int launch_skip_bwd(rcn_hipx_net* n, size_t src, int B, bool src_gated) {
     const long long n4 = (long long)B * l.oH * l.oW * (C / 4);
     const unsigned blocks = bn_stream_blocks(n4, C / 4);
     if (dry_note(n, "  skip-bwd %dx%dx%d: k_skip_bwd_add, %u workgroups into layer %d's gradient (the skip's gradient %s; %s)", l.oH, l.oW, C, blocks, (int)src,
-                 l.pool_follows ? "gated by the pool's backward" : gated ? "gated by the convolution above" : "gated here (out > 0)",
+                 l.pool_follows ? "gated by the pool's backward" : gated ? gated_above_words(n, (size_t)s.skip_by) : "gated here (out > 0)",
                  (src_gated ? "then gated by layer " + std::to_string(src) + "'s output" : "ungated: layer " + std::to_string(src) + " is a pool").c_str())) return 0;
     auto add = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBnThreads), 0, n->stream, (float*)s.dout.p, (const float*)l.dout.p, (const float*)l.out.p, (const float*)s.out.p, n4);
@@ -748,8 +787,17 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             XTRY(n, hipGetLastError());
             continue;
         }
+        if (l.kind == RCN_HIPX_GLOBAL_AVGPOOL) {
+            // the layer below is a ReLU layer (describe_layers: a ReLU convolution or batch normalisation of either kind): gated here with
+            // its output, so it finds its dZ ready -- no k_relu_bwd pass, the "gated" forms of the batch normalisation and skip kernels.  A
+            // max-pool below gates in its own backward (k_pool_bwd, or pooled[] in the convolution below it); its dout is complete here.
+            const bool gate = n->L[i - 1].kind != RCN_HIPX_MAXPOOL2;
+            RTRY(launch_gap_backward(n, (size_t)i, B, gate));
+            gated[i - 1] = gate;
+            continue;
+        }
         if (is_bn(l.kind)) {
-            // its dout is gated by the pool's backward or by the convolution above (n->bw.gated); otherwise it gates itself
+            // its dout is gated by the pool's backward, by the convolution or by the global average pool above (n->bw.gated); otherwise it gates itself
             RTRY(launch_bn_backward(n, (size_t)i, B, l.pool_follows || gated[i], grad, apply));
             continue;
         }
@@ -779,7 +827,8 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             // the layer below is a ReLU layer feeding this one directly (no pool in between): gate the gradient with its output in
             // this kernel's epilogue, so that layer finds its dZ ready instead of running a k_relu_bwd pass over the tensor
             const Layer& below = n->L[i - 1];
-            // (batch normalisation below a convolution: gated here with its output, the same out > 0 rule; below a dense layer it gates itself)
+            // (batch normalisation below a convolution: gated here with its output, the same out > 0 rule; below a dense layer it gates itself;
+            // a global average pool below has no ReLU of its own and is NOT named here: its dout stays the plain gradient of the means)
             const bool gate = below.kind == RCN_HIPX_CONV3X3_RELU || below.kind == RCN_HIPX_DENSE_RELU || (is_bn(below.kind) && conv);
             RTRY(launch_conv(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, ConvShape{s.N, s.H, s.W, s.Cout, s.Cin}, ks, gate ? 3 : 0,
                              nullptr, pooled[i].dP ? &pooled[i] : nullptr, false, wb_of(n, l.wbb_off), Store{stage16(n, i), stage16(n, i - 1)}));
@@ -961,10 +1010,10 @@ int bucket_layout(rcn_hipx_net* n, long long min_bytes) {
     long long acc = 0, end = n->n_pad;
     int first_param = -1;
     for (int i = 0; i < (int)n->L.size(); ++i)
-        if (n->L[i].kind != RCN_HIPX_MAXPOOL2) { first_param = i; break; }
+        if (has_params(n->L[i].kind)) { first_param = i; break; }
     for (int i = (int)n->L.size() - 1; i >= 0; --i) {
         const Layer& l = n->L[i];
-        if (l.kind == RCN_HIPX_MAXPOOL2) continue;
+        if (!has_params(l.kind)) continue;
         acc = (end - l.w_off) * (long long)sizeof(float);
         if (acc >= min_bytes || i == first_param) {
             bw.lo.push_back(i); bw.off.push_back(l.w_off); bw.len.push_back(end - l.w_off);
@@ -1019,7 +1068,7 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
         Layer l{};
         l.kind = layers[i].kind; l.H = H; l.W = W; l.Cin = C;
         if (is_conv(l.kind)) {
-            if (flat) return fail(n, -2, "convolution after a dense layer");
+            if (flat) return fail(n, -2, "convolution after a dense layer or a global average pool");
             if (layers[i].out < 32 || layers[i].out % 32) return fail(n, -3, "conv output channels must be a positive multiple of 32");
             if (!(9 * C <= 32) && C % 32) return fail(n, -3, "conv input channels must be a multiple of 32 (or 9*Cin <= 32 for the first layer)");
             l.Cout = l.CoutP = layers[i].out; l.oH = H; l.oW = W; l.K = 9 * C;
@@ -1054,6 +1103,17 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
                                    std::to_string(l.oH) + "x" + std::to_string(l.oW) + "x" + std::to_string(l.CoutP) + "): an identity skip crosses no pool and changes no width");
             if (s.skip_by >= 0) return fail(n, -3, from + "already feeds the skip of layer " + std::to_string(s.skip_by) + ": one skip per source");
             l.skip_src = src; s.skip_by = i;
+        } else if (l.kind == RCN_HIPX_GLOBAL_AVGPOOL) {
+            // [B][H][W][C] -> [B][C]: the dense stage begins (flat), C unchanged, so the dense layer behind has K = C; no parameter block.  The
+            // map in front must be one the forward pass writes in fp32 behind a ReLU or a max-pool (a bare RCN_HIPX_CONV3X3 is refused below)
+            const std::string at = "layer " + std::to_string(i) + " (RCN_HIPX_GLOBAL_AVGPOOL): ";
+            if (i == 0) return fail(n, -2, at + "it cannot be the first layer: it pools the map of a convolution, batch normalisation or max-pool layer");
+            if (flat) return fail(n, -2, at + "it must follow a map, not a dense layer or another global average pool (layer " + std::to_string(i - 1) + ")");
+            const int bk = n->L.back().kind;
+            if (bk != RCN_HIPX_CONV3X3 && bk != RCN_HIPX_CONV3X3_RELU && bk != RCN_HIPX_MAXPOOL2 && !is_bn(bk))
+                return fail(n, -2, at + "it must directly follow a RCN_HIPX_CONV3X3_RELU, RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_MAXPOOL2 layer");
+            l.Cout = l.CoutP = C; l.oH = l.oW = 1; l.K = 0;
+            flat = true; H = W = 1;
         } else if (l.kind == RCN_HIPX_DENSE_RELU || l.kind == RCN_HIPX_DENSE) {
             const long long feat = flat ? C : (long long)H * W * C;
             if (feat % 32 || feat > 0x7fffffff) return fail(n, -3, "dense input features must be a multiple of 32");
@@ -1063,8 +1123,8 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
             l.K = (int)feat; l.H = 1; l.W = 1; l.Cin = (int)feat; l.Cout = layers[i].out; l.CoutP = (l.Cout + 31) / 32 * 32; l.oH = l.oW = 1;
             C = l.Cout; flat = true; H = W = 1;
         } else return fail(n, -1, "unknown layer kind");
-        if (!is_bn(l.kind) && i > 0 && n->L.back().kind == RCN_HIPX_CONV3X3) return fail(n, -2, "a RCN_HIPX_CONV3X3 layer must be followed by RCN_HIPX_BN_RELU or RCN_HIPX_BN_ADD_RELU");
-        if (l.kind != RCN_HIPX_MAXPOOL2) {
+        if (!is_bn(l.kind) && i > 0 && n->L.back().kind == RCN_HIPX_CONV3X3) return fail(n, -2, "layer " + std::to_string(i - 1) + ": a RCN_HIPX_CONV3X3 layer must be followed by RCN_HIPX_BN_RELU or RCN_HIPX_BN_ADD_RELU");
+        if (has_params(l.kind)) {
             l.w_off = n->n_pad; n->n_pad += (long long)l.K * l.CoutP; l.b_off = n->n_pad; n->n_pad += l.CoutP;
             l.lw_off = n->n_log; n->n_log += (long long)l.K * l.Cout; l.lb_off = n->n_log; n->n_log += l.Cout;
         }
@@ -1244,7 +1304,7 @@ int rcn_hipx_get_option(const rcn_hipx_net* n, const char* name, int* value) {
 static int upload_padded(rcn_hipx_net* n, Buf& to, const float* flat) {
     std::vector<float> pad((size_t)n->n_pad, 0.f);
     for (const Layer& l : n->L) {
-        if (l.kind == RCN_HIPX_MAXPOOL2) continue;
+        if (!has_params(l.kind)) continue;
         for (int k = 0; k < l.K; ++k) std::memcpy(&pad[l.w_off + (long long)k * l.CoutP], &flat[l.lw_off + (long long)k * l.Cout], sizeof(float) * l.Cout);
         std::memcpy(&pad[l.b_off], &flat[l.lb_off], sizeof(float) * l.Cout);
     }
@@ -1267,7 +1327,7 @@ static int unpad(rcn_hipx_net* n, const float* dev, float* flat) {
     XTRY(n, hipMemcpyAsync(pad.data(), dev, pad.size() * sizeof(float), hipMemcpyDeviceToHost, n->stream));
     XTRY(n, hipStreamSynchronize(n->stream));
     for (const Layer& l : n->L) {
-        if (l.kind == RCN_HIPX_MAXPOOL2) continue;
+        if (!has_params(l.kind)) continue;
         for (int k = 0; k < l.K; ++k) std::memcpy(&flat[l.lw_off + (long long)k * l.Cout], &pad[l.w_off + (long long)k * l.CoutP], sizeof(float) * l.Cout);
         std::memcpy(&flat[l.lb_off], &pad[l.b_off], sizeof(float) * l.Cout);
     }
@@ -1282,7 +1342,7 @@ int rcn_hipx_init_params(rcn_hipx_net* n, uint64_t seed) {
     std::mt19937_64 gen(seed ? seed : std::random_device{}());
     std::vector<float> flat((size_t)n->n_log, 0.f);
     for (const Layer& l : n->L) {
-        if (l.kind == RCN_HIPX_MAXPOOL2) continue;
+        if (!has_params(l.kind)) continue;
         if (is_bn(l.kind)) { for (int c = 0; c < l.Cout; ++c) flat[l.lw_off + c] = 1.f; continue; }      // gamma = 1, beta = 0
         std::normal_distribution<float> nd(0.f, std::sqrt(2.0f / (float)l.K));
         for (long long i = 0; i < (long long)l.K * l.Cout; ++i) flat[l.lw_off + i] = nd(gen);
