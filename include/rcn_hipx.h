@@ -58,7 +58,9 @@ typedef enum {
 
 typedef struct rcn_hipx_layer { int32_t kind; int32_t out; } rcn_hipx_layer;
 
-/* status: 0 ok, -1 invalid argument, -2 shape, -3 unsupported, -4 HIP error, -5 no device, -6 state, -7 out of memory */
+/* status: 0 ok, -1 invalid argument, -2 shape, -3 unsupported, -4 HIP error, -5 no device, -6 state, -7 out of memory
+ * A net has at most 32 layers with parameters (every kind but the two pools): one reduction launch and one state pack take as many
+ * jobs.  rcn_hipx_create, every plan and rcn_hipx_state_layout refuse more with -3, the message naming the count and the limit. */
 int  rcn_hipx_create(int device, int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, int n_layers, int max_batch,
                      void* hip_stream /* NULL: own stream */, rcn_hipx_net** out);
 void rcn_hipx_destroy(rcn_hipx_net* net);
@@ -580,7 +582,7 @@ int  rcn_hipx_dropout_apply_dev(rcn_hipx_net* net, int site, int64_t t, float* a
  * or dropped -- the net's graphs, their keys, rcn_hipx_graphs_instantiated and the plan texts are what they were.  The body is valid once the
  * net's stream has got there (an event recorded behind the call).  -1: a NULL argument, unknown section bits, a body that is not 16-byte
  * aligned, cap_bytes < body_bytes; -6: a named section whose buffer the net does not have, or an open bucket walk
- * (rcn_hipx_gradients_begin_dev); -3: more than RCN_HIPX_STATE_MAX_LAYERS layers, or more than 16 with parameters.  Nothing is enqueued
+ * (rcn_hipx_gradients_begin_dev); -3: more than RCN_HIPX_STATE_MAX_LAYERS layers (rcn_hipx_create already refuses more than 32 with parameters).  Nothing is enqueued
  * then.  A caller that wants the parameters alone names RCN_HIPX_STATE_PARAMS and clears `flags`.
  * rcn_hipx_restore_dev: checks everything on the host BEFORE anything changes -- a wrong magic or version, unknown bits, a section outside
  * body_bytes or not 256-byte aligned, body_bytes smaller than the descriptor's, a body that is not 16-byte aligned, a recipe value its

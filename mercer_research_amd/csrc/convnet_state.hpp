@@ -52,7 +52,7 @@ struct StateJobs {
 
 inline int state_units(long long n) { return (int)((n + kStateUnit - 1) / kStateUnit); }
 
-// the layer a unit belongs to (at most 16 jobs: a scan)
+// the layer a unit belongs to (at most kStateMaxJobs = 32 jobs: a scan)
 __device__ __forceinline__ int state_job_of(const StateJobs& J, int unit) {
     int q = 0;
     while (q + 1 < J.njobs && unit >= J.j[q + 1].first_unit) ++q;

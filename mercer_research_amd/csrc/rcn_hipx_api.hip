@@ -444,6 +444,16 @@ const __bf16* wb_of(const rcn_hipx_net* n, long long off) {
 // (fp32 kernels in either mode) has none.
 int prep_bf16_weights(rcn_hipx_net* n) {
     if (n->precision != RCN_HIPX_BF16) return 0;
+    // the path is decided before the plan is noted: two jobs per matrix layer behind layer 0, and one launch takes kMaxPrepJobs of them
+    int matrices = 0;
+    for (size_t i = 1; i < n->L.size(); ++i) matrices += has_matrix(n->L[i].kind);
+    if (2 * matrices > kMaxPrepJobs) {
+        // more than one launch takes: no prepared copies -- every bf16 launch makes its own in front of itself (launch_conv), all into the
+        // one scratch n->wb, which the stream's order keeps whole until that launch has read it
+        (void)dry_note(n, "  bf16 operand copies: none prepared (%d matrix layers behind layer 0, one launch takes %d): k_prep_weights_bf16 in front of every bf16 launch, into one shared scratch",
+                       matrices, kMaxPrepJobs / 2);
+        return 0;
+    }
     if (dry_note(n, "  bf16 operand copies of every layer's weights, both orientations: k_prep_all_bf16 (one launch)")) return 0;
     if (!n->wb16.p) {
         long long off = 0;
@@ -1132,6 +1142,12 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
     }
     if (n->L.back().kind != RCN_HIPX_DENSE) return fail(n, -2, "the last layer must be RCN_HIPX_DENSE (logits)");
     n->classes = n->L.back().Cout;
+    // one reduction launch, and one state pack, take kMaxReduceJobs layers with parameters: refused here, so create, every plan and the
+    // state layout agree before anything is enqueued (reduce_slab and make_state_jobs keep their own guards)
+    int with_params = 0;
+    for (const Layer& l : n->L) with_params += has_params(l.kind);
+    if (with_params > kMaxReduceJobs)
+        return fail(n, -3, std::to_string(with_params) + " layers with parameters: one reduction launch and one state pack take at most " + std::to_string(kMaxReduceJobs));
     return 0;
 }
 

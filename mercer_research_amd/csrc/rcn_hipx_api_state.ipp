@@ -55,6 +55,7 @@ const char* const kSectionName[kStateSections] = {"parameters", "velocity", "Ada
 
 // The job table of a pack (units of logical elements) or an unpack (units of padded elements) over the sections of d.  The three scalar
 // pointers are left for the caller.  false: more layers with parameters than one launch takes.
+static_assert(kStateMaxJobs == kMaxReduceJobs, "describe_layers refuses by kMaxReduceJobs for both tables");
 bool make_state_jobs(rcn_hipx_net* n, const rcn_hipx_state_desc& d, bool unpack, StateJobs* J) {
     *J = StateJobs{};
     int unit = 0;

@@ -7,7 +7,8 @@ from fractions import Fraction
 
 import numpy as np
 import pytest
-from _convnet_util import LR, convnet_loaded, plan_lines  # noqa: F401  (fixture)
+from _convnet_util import convnet_loaded, plan_lines  # noqa: F401  (fixture)
+from _twin_checks import twin_schedule
 from _gap_ref import (GapTorchNet, exact_forward, exact_gate_case, exact_logit_case, im2col, n_logical, param_shapes, random_params, rows_seen,
                       tensor_slices)
 
@@ -61,17 +62,7 @@ def twin_run(name, precision):
     in_shape, layers, B = spec
     flat, x, y = data(spec, SEEDS[name])
     ref = GapTorchNet(in_shape, layers, flat, operand="bf16" if precision == "bf16" else "f64")
-    out = {}
-    out["loss"], out["logits"], out["grad"] = ref.loss_and_grads(x, y)
-    out["stats1"] = ref.bn_stats().copy()
-    out["losses"] = [ref.sgd_step(x, y, LR) for _ in range(STEPS)]
-    out["params"], out["stats"] = ref.params(), ref.bn_stats().copy()
-    zr = out["eval_logits"] = ref.logits(x, train=False)
-    lse = np.log(np.exp(zr - zr.max(1, keepdims=True)).sum(1)) + zr.max(1)
-    out["eval"] = (float((lse - zr[np.arange(B), y]).mean()), int((zr.argmax(1) == y).sum()))
-    top = np.sort(zr, axis=1)
-    out["margin"], out["scale"] = float(np.min(top[:, -1] - top[:, -2])), float(np.abs(zr).max())
-    return out
+    return twin_schedule(ref, x, y, STEPS)
 
 
 def _tags(lines):

@@ -9,6 +9,7 @@ operands 5e-3 / 2e-2 against the twin with the SAME operand rounding, the traini
 import numpy as np
 import pytest
 from _convnet_util import LR, batches, dev, epoch, make_net, same_bits, step, twins
+from _twin_checks import compare, device_run, grads as _grads, stats as _stats
 from _gap_ref import GapTorchNet, close, close_per_tensor, exact_forward, exact_gate_case, exact_logit_case, rows_seen, tensor_slices
 from test_convnet_gap_plan import (EXACT_SHAPES, GAP_A, GAP_B, GAP_C, GAP_LOOP, GAP_NETS, GATE_PIXELS, RTOL, RTOL_2, SEEDS, STEPS, data, gate_case,
                                    twin_run)
@@ -19,76 +20,20 @@ CASES = [(n, p) for n in sorted(GAP_NETS) for p in ("fp32", "bf16")]
 LAYERS = (("conv", 32), ("global_avgpool",), ("dense", 10))         # of the exact nets
 
 
-def _grads(net, xd, yd, B):
-    """(logical gradient, loss, training logits) of one gradients call"""
-    import torch
-    loss = torch.zeros(1, dtype=torch.float32, device=net.device)
-    with torch.cuda.stream(net.stream):
-        g = net.gradients(xd, yd, loss=loss)
-        z = net.last_logits(B)
-    net.synchronize()
-    return net.unpad(g), float(loss.item()), z.cpu().numpy()
-
-
-def _stats(net):
-    return net.get_bn_stats() if net.get_bn()[2] else np.zeros(0, dtype=np.float32)
-
-
 def _run(name, precision, tiling=None, options=()):
     """What the device makes of twin_run's schedule: one gradients call, STEPS plain SGD steps, a forward and an evaluation"""
-    import torch
     spec = GAP_NETS[name]
-    B = spec[2]
-    flat, x, y = data(spec, SEEDS[name])
-    net = make_net(spec, precision, tiling=tiling)
-    for k, v in options:
-        net.set_option(k, v)
-    net.set_params(flat)
-    xd, yd = dev(net, x), dev(net, y)
-    out = {}
-    out["grad"], out["loss"], out["logits"] = _grads(net, xd, yd, B)
-    out["stats1"] = _stats(net)
-    loss = torch.zeros(1, dtype=torch.float32, device=net.device)
-    out["losses"] = []
-    for _ in range(STEPS):
-        step(net, xd, yd, LR, loss)
-        out["losses"].append(float(loss.item()))
-    out["params"], out["stats"] = net.get_params(), _stats(net)
-    with torch.cuda.stream(net.stream):
-        ze = net.forward(xd)
-    net.synchronize()
-    out["eval_logits"] = ze.cpu().numpy()
-    out["eval"] = net.evaluate(xd, yd, x_scale=1.0, x_shift=0.0)
-    net.close()
-    return out
+    return device_run(spec, precision, *data(spec, SEEDS[name]), STEPS, tiling=tiling, options=options)
 
 
 def _compare(name, precision, r, tag=""):
-    """every comparison of the issue's list; returns the worst share of an allowance"""
+    """every comparison of tests/_twin_checks.py: compare; returns the worst share of an allowance"""
     spec = GAP_NETS[name]
-    ref = twin_run(name, precision)
-    t = f"{name} {precision}{tag}"
-    used = [close(r["logits"], ref["logits"], RTOL[precision], f"{t} training logits"), close([r["loss"]], [ref["loss"]], RTOL[precision], f"{t} loss")]
+    unrounded = None
     if precision == "bf16":
         flat, x, y = data(spec, SEEDS[name])
-        close(r["logits"], GapTorchNet(spec[0], spec[1], flat).logits(x, train=True), 3e-2, f"{t} training logits against the unrounded twin")
-    assert np.isfinite(r["grad"]).all()
-    used.append(close_per_tensor(r["grad"], ref["grad"], spec[0], spec[1], RTOL[precision], f"{t} gradient"))
-    if ref["stats"].size:
-        used.append(close(r["stats1"], ref["stats1"], RTOL[precision], f"{t} running statistics after gradients()"))
-        used.append(close(r["stats"], ref["stats"], RTOL_2[precision], f"{t} running statistics after {STEPS} steps"))
-    assert len(r["losses"]) == STEPS
-    used.append(close([r["losses"][0]], [ref["losses"][0]], RTOL[precision], f"{t} loss of step 1"))
-    used.append(close([r["losses"][1]], [ref["losses"][1]], RTOL_2[precision], f"{t} loss of step 2"))
-    used.append(close_per_tensor(r["params"], ref["params"], spec[0], spec[1], RTOL_2[precision], f"{t} parameters after {STEPS} steps"))
-    used.append(close(r["eval_logits"], ref["eval_logits"], RTOL_2[precision], f"{t} evaluation logits"))
-    (loss, correct), (rloss, rcorrect) = r["eval"], ref["eval"]
-    used.append(close([loss], [rloss], RTOL_2[precision], f"{t} evaluation loss"))
-    # (tests/test_convnet_gap_plan.py asserts the margin from the twin alone: the count is always compared)
-    assert ref["margin"] > 4 * RTOL_2[precision] * ref["scale"]
-    assert correct == rcorrect, (correct, rcorrect)
-    print(f"{t}: worst share of an allowance = {max(used):.3f}")
-    return max(used)
+        unrounded = (GapTorchNet(spec[0], spec[1], flat).logits(x, train=True), 3e-2)
+    return compare(spec, r, twin_run(name, precision), RTOL[precision], RTOL_2[precision], STEPS, f"{name} {precision}{tag}", unrounded)
 
 
 @pytest.mark.parametrize("name,precision", CASES, ids=[f"{n}-{p}" for n, p in CASES])

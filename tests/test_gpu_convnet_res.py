@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 from _convnet_util import LR, batches, dev, epoch, make_net, plan_lines, same_bits, step, twins
 from _res_ref import ResTorchNet, close, close_per_tensor, plain, random_params, tensor_slices
+from _twin_checks import against_torch
 from test_convnet_res_plan import RES_A, RES_B, RES_C, RES_NETS
 
 pytestmark = pytest.mark.gpu
@@ -293,30 +294,8 @@ def test_epoch_equals_steps_and_adds_no_graph():
 
 
 def _against_torch(configure, make_optim, micro=1, rtol=4e-4, tag=""):
-    """ONE update of `micro` micro-batches on net a on the device and in float64 torch: parameters per tensor and running statistics at the
-    bound of tests/test_gpu_convnet_bn_recipe.py"""
-    import torch
-    in_shape, layers, B = RES_A
-    flat = random_params(np.random.default_rng(6), in_shape, layers)
-    rng = np.random.default_rng(11)
-    data = [(rng.standard_normal((B,) + in_shape).astype(np.float32), rng.integers(0, 10, B).astype(np.int32)) for _ in range(micro)]
-    net = make_net(RES_A, "fp32")
-    net.set_params(flat)
-    configure(net)
-    ref = ResTorchNet(in_shape, layers, flat)
-    opt, lr, clip = make_optim(ref.parameters())
-    opt.zero_grad()
-    for x, y in data:
-        step(net, dev(net, x), dev(net, y), lr)
-        z = ref.forward(x, True)
-        (torch.nn.functional.cross_entropy(z, torch.from_numpy(y.astype(np.int64))) / micro).backward()
-    if clip:
-        torch.nn.utils.clip_grad_norm_(ref.parameters(), clip)
-    opt.step()
-    assert not same_bits(net.get_params(), flat)
-    close_per_tensor(net.get_params(), ref.params(), in_shape, layers, rtol, f"{tag} parameters")
-    close(net.get_bn_stats(), ref.bn_stats(), rtol, f"{tag} running statistics")
-    net.close()
+    """ONE update of `micro` micro-batches on net a on the device and in float64 torch (tests/_twin_checks.py: against_torch)"""
+    against_torch(RES_A, ResTorchNet, configure, make_optim, micro, rtol, tag)
 
 
 def test_adamw_step_against_torch():
