@@ -1,4 +1,4 @@
-"""The cases of tests/test_gpu_convnet_bn_forms.py (GPU, against float64 torch: tests/_bn_ref.py) and tests/test_convnet_bn_forms_plan.py
+"""The cases of tests/test_gpu_convnet_bn_forms.py (GPU, against float64 torch: tests/_torch_ref.py) and tests/test_convnet_bn_forms_plan.py
 (CPU: the proof, by rcn_hipx_plan, that every case reaches what it names, and that the exact-statistics reference has teeth).  ONE table,
 so that the two files cannot drift apart; Case, names, env_name and SLOTS are tests/_forms_cases.py's.  Not a test file and not a conftest.
 
@@ -11,7 +11,7 @@ Two groups:
 from collections import namedtuple
 
 import numpy as np
-from _bn_ref import random_params, tensor_slices
+from _torch_ref import random_params, tensor_slices
 from _forms_cases import Case
 
 CL, BN, POOL = "conv_linear", ("bn_relu",), ("pool",)

@@ -205,12 +205,15 @@ def oracle_params(rng, in_shape, layers):
 
 
 # ---- checks ------------------------------------------------------------------------------------------------------------------------------
-def close(a, b, rtol=2e-4):
-    """tests/test_gpu_convnet.py's rule, fp32 MFMA against f64: |d| <= rtol * scale + 1e-6"""
+def close(a, b, rtol=2e-4, tag=""):
+    """tests/test_gpu_convnet.py's rule, fp32 MFMA against f64: |d| <= rtol * max(1e-3, max |ref|) + 1e-6, printing the figure first;
+    returns |d| / allowance"""
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     scale = max(1e-3, float(np.abs(b).max()))
-    print("max |d| =", float(np.abs(a - b).max()), "scale =", scale, "rtol =", rtol)
-    assert np.abs(a - b).max() <= rtol * scale + 1e-6, (float(np.abs(a - b).max()), scale)
+    d = float(np.abs(a - b).max())
+    print(f"{tag + ': ' if tag else ''}max |d| = {d:.3e} scale = {scale:.3e} rtol = {rtol} used = {d / (rtol * scale + 1e-6):.3f}")
+    assert d <= rtol * scale + 1e-6, (tag, d, scale, rtol)
+    return d / (rtol * scale + 1e-6)
 
 
 def tensor_slices(in_shape, layers):

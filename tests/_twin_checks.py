@@ -5,8 +5,8 @@ statistics -- run on the device (`device_run`) and on a twin (`twin_schedule`), 
 update of an optimiser family against torch.optim on the twin (`against_torch`).  Not a test file and not a conftest: every assert
 carries its message."""
 import numpy as np
-from _convnet_util import LR, dev, make_net, same_bits, step
-from _gap_ref import close, close_per_tensor
+from _convnet_util import LR, close, dev, make_net, same_bits, step
+from _torch_ref import TorchNet, close_per_tensor, random_params
 
 
 def grads(net, xd, yd, B):
@@ -52,7 +52,7 @@ def device_run(spec, precision, flat, x, y, steps, tiling=None, options=()):
 
 
 def twin_schedule(ref, x, y, steps):
-    """What a twin (tests/_res_ref.py, tests/_gap_ref.py) makes of the schedule: one gradients call, `steps` plain SGD steps at LR, then a
+    """What a twin (tests/_torch_ref.py) makes of the schedule: one gradients call, `steps` plain SGD steps at LR, then a
     forward and an evaluation on the running statistics; and the margin between a row's two best evaluation logits with their scale"""
     B = len(y)
     out = {}
@@ -71,14 +71,14 @@ def twin_schedule(ref, x, y, steps):
 def compare(spec, r, ref, rtol, rtol2, steps, tag, unrounded_logits=None, widened_gradients=None):
     """Every quantity of a device_run `r` against the twin_schedule `ref` of the same data: rtol of a tensor's scale + 1e-6 for what one
     pass makes, rtol2 for what a second step has touched.  unrounded_logits: (the unrounded twin's training logits, their bound) for a bf16
-    run.  widened_gradients: _gap_ref.close_per_tensor's `widened`, for the gradient alone.  The correct count is always compared: the
+    run.  widened_gradients: _torch_ref.close_per_tensor's `widened`, for the gradient alone.  The correct count is always compared: the
     caller's CPU file asserts the margin from the twin alone.  Prints and returns the worst share of an allowance."""
     t = tag
     used = [close(r["logits"], ref["logits"], rtol, f"{t} training logits"), close([r["loss"]], [ref["loss"]], rtol, f"{t} loss")]
     if unrounded_logits is not None:
         close(r["logits"], unrounded_logits[0], unrounded_logits[1], f"{t} training logits against the unrounded twin")
     assert np.isfinite(r["grad"]).all(), f"{t}: a gradient is not finite"
-    used.append(close_per_tensor(r["grad"], ref["grad"], spec[0], spec[1], rtol, f"{t} gradient", widened_gradients))
+    used.append(close_per_tensor(r["grad"], ref["grad"], spec[0], spec[1], rtol, f"{t} gradient", widened=widened_gradients))
     if ref["stats"].size:
         used.append(close(r["stats1"], ref["stats1"], rtol, f"{t} running statistics after gradients()"))
         used.append(close(r["stats"], ref["stats"], rtol2, f"{t} running statistics after {steps} steps"))
@@ -97,7 +97,6 @@ def compare(spec, r, ref, rtol, rtol2, steps, tag, unrounded_logits=None, widene
 
 def update_case(spec, micro=1):
     """(parameters, `micro` batches) of against_torch's one update: seeds 6 and 11"""
-    from _gap_ref import random_params
     in_shape, layers, B = spec
     flat = random_params(np.random.default_rng(6), in_shape, layers)
     rng = np.random.default_rng(11)
@@ -119,21 +118,21 @@ def twin_update(ref, data, make_optim):
     return lr
 
 
-def against_torch(spec, make_twin, configure, make_optim, micro=1, rtol=4e-4, tag="", widened=None):
-    """ONE update of `micro` micro-batches on the net `spec` on the device and in float64 torch (make_twin(in_shape, layers, flat)):
-    parameters per tensor and running statistics at the bound of tests/test_gpu_convnet_bn_recipe.py.  widened: _gap_ref.close_per_tensor's,
+def against_torch(spec, configure, make_optim, micro=1, rtol=4e-4, tag="", widened=None):
+    """ONE update of `micro` micro-batches on the net `spec` on the device and in float64 torch (the twin):
+    parameters per tensor and running statistics at the bound of tests/test_gpu_convnet_bn_recipe.py.  widened: _torch_ref.close_per_tensor's,
     for the parameters."""
     in_shape, layers, B = spec
     flat, data = update_case(spec, micro)
     net = make_net(spec, "fp32")
     net.set_params(flat)
     configure(net)
-    ref = make_twin(in_shape, layers, flat)
+    ref = TorchNet(in_shape, layers, flat)
     lr = twin_update(ref, data, make_optim)
     for x, y in data:
         step(net, dev(net, x), dev(net, y), lr)
     assert not same_bits(net.get_params(), flat), f"{tag}: the update changed nothing"
-    worst = close_per_tensor(net.get_params(), ref.params(), in_shape, layers, rtol, f"{tag} parameters", widened)
+    worst = close_per_tensor(net.get_params(), ref.params(), in_shape, layers, rtol, f"{tag} parameters", widened=widened)
     worst = max(worst, close(net.get_bn_stats(), ref.bn_stats(), rtol, f"{tag} running statistics"))
     print(f"{tag}: worst share of an allowance = {worst:.3f}")
     net.close()

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 from _bn_cases import (BF16P_TWIN_LINES, BN_MOMENTUM, FORMS, LOOPING, SHAPES, channel_weights, conv_output, exact_data, host_stats, rows_of,
                        shape_id, shape_spec)
-from _bn_ref import TorchNet
+from _torch_ref import TorchNet
 from _convnet_util import convnet_built, plan_lines  # noqa: F401  (convnet_built: the fixture `convnet`)
 from _forms_cases import SLOTS, env_name, names
 

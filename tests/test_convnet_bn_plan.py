@@ -3,7 +3,7 @@ fusion across a BN layer, who gates, one reduce job per BN layer), the state lay
 torch helper of the GPU tests pinned on a case worked out by hand."""
 import numpy as np
 import pytest
-from _bn_ref import TorchNet, n_logical, param_shapes, tensor_slices
+from _torch_ref import TorchNet, n_logical, param_shapes, tensor_slices
 from _convnet_util import convnet_loaded, plan_lines  # noqa: F401  (fixture)
 
 # the nets of tests/test_gpu_convnet_bn.py: (input shape, layers, batch)

@@ -24,8 +24,7 @@ import numpy as np
 import pytest
 from _convnet_util import LR, convnet_loaded, plan_lines  # noqa: F401  (fixture)
 from _exact_nets import MODES, certificate, exact_net, worst_move
-from _gap_ref import GapTorchNet, random_params, tensor_slices
-from _res_ref import ResTorchNet, plain
+from _torch_ref import NO_PARAMS, TorchNet, kinds_with_params, random_params, tensor_slices
 from _twin_checks import twin_schedule
 from bench_convnet import CONFIGS
 
@@ -46,7 +45,6 @@ DEEP_NETS = {"P17": P17, "P18": P18, "P32": P32, "RES20": RES20, "RESGAP19": RES
 JOBS = {"P17": 17, "P18": 18, "P32": 32, "RES20": 20, "RESGAP19": 19}
 SEEDS = {"P17": 4, "P18": 27, "P32": 3, "RES20": 3, "RESGAP19": 3}
 RTOL, RTOL_2, STEPS = 2e-4, 4e-4, 2
-NO_PARAMS = ("pool", "global_avgpool")
 LIMIT = 32                                              # kMaxReduceJobs = kStateMaxJobs
 
 # The one quantity whose bound the float32 evaluation sets (the module docstring): the share of its 1.2e-6 allowance that the float32 CPU
@@ -56,24 +54,14 @@ ZERO_BIAS_FLOAT32_SHARE = 0.795
 ZERO_BIAS_FACTOR = {"P17": 1.0, "P18": 1.0, "P32": 4 * ZERO_BIAS_FLOAT32_SHARE, "RES20": 1.0, "RESGAP19": 1.0}
 
 
-def kinds_with_params(layers):
-    return [l[0] for l in plain(layers) if l[0] not in NO_PARAMS]
-
-
 def zero_bias_tensors(layers):
     """{(index among the layers with parameters, "biases")} of the conv_linear layers: their gradient is exactly zero"""
     return {(i, "biases") for i, k in enumerate(kinds_with_params(layers)) if k == "conv_linear"}
 
 
-def make_twin(in_shape, layers, flat, **kw):
-    """the float64 torch twin of a description: tests/_gap_ref.py's where it has a global average pool, else tests/_res_ref.py's"""
-    cls = GapTorchNet if any(l[0] == "global_avgpool" for l in layers) else ResTorchNet
-    return cls(in_shape, layers, flat, **kw)
-
-
 def float32_twin(in_shape, layers, flat):
     """the same torch modules evaluated in float32: another float32 evaluation of the net, in torch's summation order"""
-    t = make_twin(in_shape, layers, flat)
+    t = TorchNet(in_shape, layers, flat)
     for m in t.mods:
         m.float()
     t.mods[0].register_forward_pre_hook(lambda mod, args: (args[0].float(),))
@@ -95,7 +83,7 @@ def twin_run(name, float32=False):
     """tests/_twin_checks.py's schedule on the twin of net `name`; computed once per process, shared with the GPU file, never written"""
     spec = DEEP_NETS[name]
     flat, x, y = data(spec, SEEDS[name])
-    return twin_schedule((float32_twin if float32 else make_twin)(spec[0], spec[1], flat), x, y, STEPS)
+    return twin_schedule((float32_twin if float32 else TorchNet)(spec[0], spec[1], flat), x, y, STEPS)
 
 
 def _allowance(ref, rtol):
@@ -272,7 +260,7 @@ ADAMW_FLOAT32_SHARE = {("conv_linear", "weights"): 1.693, ("conv_linear", "biase
 
 
 def adamw_widened():
-    """_gap_ref.close_per_tensor's `widened` for the AdamW update of P32"""
+    """_torch_ref.close_per_tensor's `widened` for the AdamW update of P32"""
     return {(li, part): 4 * ADAMW_FLOAT32_SHARE[(k, part)] for li, k in enumerate(kinds_with_params(P32[1])) for part in ("weights", "biases")
             if (k, part) in ADAMW_FLOAT32_SHARE}
 
@@ -284,7 +272,7 @@ def test_the_update_bounds_can_hold(family):
     make_optim, micro = _optimisers()[family]
     in_shape, layers, _ = P32
     flat, batches = update_case(P32, micro)
-    twin, f32 = make_twin(in_shape, layers, flat), float32_twin(in_shape, layers, flat)
+    twin, f32 = TorchNet(in_shape, layers, flat), float32_twin(in_shape, layers, flat)
     twin_update(twin, batches, make_optim)
     twin_update(f32, batches, make_optim)
     kinds, shares = kinds_with_params(layers), {}

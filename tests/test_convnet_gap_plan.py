@@ -1,16 +1,16 @@
 """Global average pooling without a GPU: ("global_avgpool",) = AdaptiveAvgPool2d(1) + flatten(1) in front of the dense stage
 (include/rcn_hipx.h: RCN_HIPX_GLOBAL_AVGPOOL; csrc/convnet_gap.hpp).  The plans of the nets of tests/test_gpu_convnet_gap.py (the two
 launches, who gates what), the head's K = C, every refusal of a description, the state layout, the float64 torch twin of the GPU tests
-(tests/_gap_ref.py) pinned on a case worked out by hand, and the premises of the GPU file's exact, gate and count checks."""
+(tests/_torch_ref.py) pinned on a case worked out by hand, and the premises of the GPU file's exact, gate and count checks."""
 import functools
 from fractions import Fraction
 
 import numpy as np
 import pytest
 from _convnet_util import convnet_loaded, plan_lines  # noqa: F401  (fixture)
+from _gap_cases import exact_forward, exact_gate_case, exact_logit_case, im2col, rows_seen
+from _torch_ref import TorchNet, n_logical, param_shapes, random_params, tensor_slices
 from _twin_checks import twin_schedule
-from _gap_ref import (GapTorchNet, exact_forward, exact_gate_case, exact_logit_case, im2col, n_logical, param_shapes, random_params, rows_seen,
-                      tensor_slices)
 
 # (input shape, layers, batch): the smallest nets at which each path of the two kernels can go wrong
 # a: a ReLU convolution below: gated by the pool, no k_relu_bwd; HW = 16
@@ -61,7 +61,7 @@ def twin_run(name, precision):
     spec = GAP_NETS[name]
     in_shape, layers, B = spec
     flat, x, y = data(spec, SEEDS[name])
-    ref = GapTorchNet(in_shape, layers, flat, operand="bf16" if precision == "bf16" else "f64")
+    ref = TorchNet(in_shape, layers, flat, operand="bf16" if precision == "bf16" else "f64")
     return twin_schedule(ref, x, y, STEPS)
 
 
@@ -259,7 +259,7 @@ def test_gap_ref_on_a_hand_computed_case():
     layers = (("conv", 2), ("global_avgpool",), ("dense", 1))
     flat = np.concatenate([eye.ravel(), np.zeros(2), [2.0, -4.0], [0.5]])
     assert n_logical((2, 2, 2), layers) == flat.size and param_shapes((2, 2, 2), layers) == [(18, 2), (2, 1)]
-    net = GapTorchNet((2, 2, 2), layers, flat)
+    net = TorchNet((2, 2, 2), layers, flat)
     z = net.forward(x, True)
     assert np.array_equal(net.outs[1].detach().numpy(), [[3.0, 1.5], [2.0, 4.0]])
     assert np.array_equal(z.detach().numpy().ravel(), [0.5, -11.5])
@@ -271,7 +271,7 @@ def test_gap_ref_on_a_hand_computed_case():
     want[1, :, :, 0], want[1, :, :, 1] = 1.5, -3.0
     assert np.array_equal(got, want)
     # the gradient INTO the convolution's pre-activation is gated: the closed position gets nothing
-    loose = GapTorchNet((2, 2, 2), layers, flat, gate_below=False)
+    loose = TorchNet((2, 2, 2), layers, flat, gate_below=False)
     zl = loose.forward(x, True)
     assert np.array_equal(zl.detach().numpy(), z.detach().numpy())
     # the closed position is pixel (0, 1) of channel 1 of sample 0 (x = -8): the convolution's bias gradient counts it only without the gate
@@ -281,7 +281,7 @@ def test_gap_ref_on_a_hand_computed_case():
             m.zero_grad()
         (n.forward(x, True)[:, 0] * n.torch.tensor([1.0, 3.0], dtype=n.torch.float64)).sum().backward()
         return n.mods[0].bias.grad.numpy()
-    assert np.array_equal(conv_bias_grad(GapTorchNet((2, 2, 2), layers, flat)), [4 * 0.5 + 4 * 1.5, 3 * -1.0 + 4 * -3.0])
+    assert np.array_equal(conv_bias_grad(TorchNet((2, 2, 2), layers, flat)), [4 * 0.5 + 4 * 1.5, 3 * -1.0 + 4 * -3.0])
     assert np.array_equal(conv_bias_grad(loose), [4 * 0.5 + 4 * 1.5, 4 * -1.0 + 4 * -3.0])
     assert np.array_equal(net.params(), flat)
 
@@ -367,12 +367,12 @@ def test_gate_case_closes_between_a_fifth_and_four_fifths():
     """the data of the GPU file's gate test: net a, and the twin without the pool's gate is many allowances away from the true gradient"""
     flat, x, y = gate_case()
     in_shape, layers, _ = GAP_A
-    ref = GapTorchNet(in_shape, layers, flat)
+    ref = TorchNet(in_shape, layers, flat)
     _, _, g_true = ref.loss_and_grads(x, y)
     zero = float((ref.outs[0].detach().numpy() == 0).mean())
     print(f"{zero:.2f} of the convolution's output is zero")
     assert 0.2 <= zero <= 0.8, zero
-    _, _, g_loose = GapTorchNet(in_shape, layers, flat, gate_below=False).loss_and_grads(x, y)
+    _, _, g_loose = TorchNet(in_shape, layers, flat, gate_below=False).loss_and_grads(x, y)
     worst = 0.0
     for ws, bs in tensor_slices(in_shape, layers)[:1]:
         for t in (ws, bs):

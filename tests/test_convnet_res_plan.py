@@ -1,11 +1,11 @@
 """Residual blocks without a GPU: ("bn_add_relu", d) = relu(BatchNorm2d(z) + s), s the output of the layer d places in front
 (include/rcn_hipx.h: RCN_HIPX_BN_ADD_RELU).  The plans of the four nets of tests/test_gpu_convnet_res.py (the apply launch with its skip,
 the add pass of the backward walk directly behind the input-gradient launch of the layer above the source, who gates what), every refusal
-of a description, the state layout, and the float64 torch twin of the GPU tests (tests/_res_ref.py) pinned on a case worked out by hand."""
+of a description, the state layout, and the float64 torch twin of the GPU tests (tests/_torch_ref.py) pinned on a case worked out by hand."""
 import numpy as np
 import pytest
 from _convnet_util import convnet_loaded, plan_lines  # noqa: F401  (fixture)
-from _res_ref import ResTorchNet, n_logical, plain, skips, tensor_slices
+from _torch_ref import TorchNet, n_logical, plain, skips, tensor_slices
 
 
 def block(c):
@@ -180,7 +180,7 @@ def test_res_ref_on_a_hand_computed_case():
     eye = np.zeros((9 * C, C)); eye[4 * C:5 * C] = np.eye(C)
     layers = (("conv", C),) + block(C) + (("dense", 1),)
     flat = np.concatenate([eye.ravel(), np.zeros(C), eye.ravel(), np.zeros(C), g1, b1, eye.ravel(), np.zeros(C), g2, b2, w, [0.5]])
-    net = ResTorchNet((1, 1, C), layers, flat, eps=eps)
+    net = TorchNet((1, 1, C), layers, flat, eps=eps)
     z = net.forward(s.reshape(2, 1, 1, C), True)
     net.outs[0].retain_grad()
     (z[:, 0] * net.torch.from_numpy(v)).sum().backward()
@@ -203,6 +203,6 @@ def test_res_ref_on_a_hand_computed_case():
     assert np.allclose(got, want, rtol=0, atol=1e-12), np.abs(got - want).max()
     assert np.abs(main_0).min() > 1e-4 and np.abs(dsum).max() > 0.1          # both paths carry something: neither could be dropped unnoticed
     # without the source's gate on the skip path the VALUES are the same (gate_source only changes the gradient)
-    loose = ResTorchNet((1, 1, C), layers, flat, eps=eps, gate_source=False)
+    loose = TorchNet((1, 1, C), layers, flat, eps=eps, gate_source=False)
     assert np.array_equal(loose.forward(s.reshape(2, 1, 1, C), True).detach().numpy(), z.detach().numpy())
     assert np.array_equal(net.params(), flat)

@@ -1,5 +1,5 @@
 """GPU tests of Track X's batch normalisation (include/rcn_hipx.h: RCN_HIPX_CONV3X3, RCN_HIPX_BN_RELU; csrc/convnet_bn.hpp) against PyTorch
-on the CPU in float64 (tests/_bn_ref.py): the logits of a training forward, the loss, the gradients per tensor, the parameters and the
+on the CPU in float64 (tests/_torch_ref.py): the logits of a training forward, the loss, the gradients per tensor, the parameters and the
 running statistics after two steps, and the forward / evaluation on the running statistics afterwards, on the four nets of
 tests/test_convnet_bn_plan.py -- the smallest at which each path (pool-gated, gated by the convolution above, self-gated, many partials
 per channel) can go wrong.
@@ -12,8 +12,8 @@ tests/test_gpu_convnet.py's 3e-2 against the unrounded twin.  (Rounding the oper
 8 % of its scale in float64 torch itself -- invstd and the two mean subtractions amplify -- so the unrounded twin says nothing at 5e-3.)"""
 import numpy as np
 import pytest
-from _bn_ref import TorchNet, close, close_per_tensor, random_params, tensor_slices
-from _convnet_util import LR, dev, make_net, same_bits, step, sync
+from _convnet_util import LR, close, dev, make_net, same_bits, step, sync
+from _torch_ref import TorchNet, close_per_tensor, random_params, tensor_slices
 from test_convnet_bn_plan import BN_B, BN_C, BN_NETS
 
 pytestmark = pytest.mark.gpu

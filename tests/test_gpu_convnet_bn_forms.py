@@ -1,7 +1,7 @@
 """GPU tests of batch normalisation at the workload's shapes and kernel forms (cases: tests/_bn_cases.py; tests/test_convnet_bn_forms_plan.py
 proves on the CPU that each case reaches what it names, and that the exact reference has teeth):
   A  FORMS: epilogue 1 (bias only) of the LDS-tiled convolution kernels, their epilogue-3 input gradients gated by a BN layer's output,
-     and partials of 128 rows, against tests/_bn_ref.TorchNet in float64 -- with the operands rounded to bf16 where "bf16" precision
+     and partials of 128 rows, against tests/_torch_ref.TorchNet in float64 -- with the operands rounded to bf16 where "bf16" precision
      rounds them: training logits and loss, the gradient per tensor, parameters per tensor and running statistics after two plain SGD
      steps, evaluation logits on the running statistics.
   B  the looping forms of those kernels on grids of 1, 2, 3, 5 and 7 workgroups ("halo_f32_slots"): bit for bit the one-item-per-workgroup
@@ -22,10 +22,10 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 from _bn_cases import BF16P_TWIN_LINES, BN_EPS, BN_MOMENTUM, FORMS, LOOPING, SHAPES, conv_linear_layers, conv_output, exact_data, host_stats, rows_of, shape_id, shape_spec
-from _bn_ref import TorchNet, close, close_per_tensor, random_params
-from _convnet_util import dev, make_net, same_bits, zeros
+from _convnet_util import close, dev, make_net, same_bits, zeros
 from _forms_cases import SLOTS, names
 from _oracle_steps import LR
+from _torch_ref import TorchNet, close_per_tensor, random_params
 from test_convnet_bn_plan import BN_A
 
 pytestmark = pytest.mark.gpu

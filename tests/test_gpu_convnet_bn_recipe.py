@@ -1,10 +1,10 @@
 """GPU tests of batch normalisation inside the training recipe, on net a of tests/test_convnet_bn_plan.py: determinism of the fixed-order
 sums, the epoch's one graph, the running statistics under graph replay, the optimisers, clipping and accumulation against torch in
-float64 (tests/_bn_ref.py; the bounds of tests/test_gpu_convnet_bn.py), evaluation on the average, snapshot / restore and save / load."""
+float64 (tests/_torch_ref.py; the bounds of tests/test_gpu_convnet_bn.py), evaluation on the average, snapshot / restore and save / load."""
 import numpy as np
 import pytest
-from _bn_ref import TorchNet, close, close_per_tensor, random_params, tensor_slices
-from _convnet_util import LR, batches, dev, epoch, make_net, same_bits, step, twins
+from _convnet_util import LR, batches, close, dev, epoch, make_net, same_bits, step, twins
+from _torch_ref import TorchNet, close_per_tensor, random_params, tensor_slices
 from test_convnet_bn_plan import BN_A
 
 pytestmark = pytest.mark.gpu

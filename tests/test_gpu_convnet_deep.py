@@ -3,7 +3,7 @@ the references must meet): the job tables of the reduction launch (k_reduce_all.
 (k_state_pack / k_state_unpack: StateJobs) and of the bf16 operand copies (k_prep_all_bf16: PrepJobs) past entry 15, and the per-launch
 k_prep_weights_bf16 copies a net with more than 16 matrix layers behind layer 0 falls back to.
 
-fp32: against PyTorch on the CPU in float64 (tests/_res_ref.py, tests/_gap_ref.py) at the project's bound, 2e-4 of a tensor's scale + 1e-6
+fp32: against PyTorch on the CPU in float64 (tests/_torch_ref.py) at the project's bound, 2e-4 of a tensor's scale + 1e-6
 and 4e-4 after a second step -- but for the gradient of P32's conv_linear biases, exactly zero in the twin, whose allowance is 4 x what a
 float32 CPU evaluation of the same net needs (tests/test_convnet_deep_plan.py: ZERO_BIAS_FACTOR).  bf16: the exact integer nets of P17 and
 P18 against the oracle, logits bit for bit; P32 and RES20 device against device only -- the bf16-operand twin moves by 96 (P32) and 1.0
@@ -13,11 +13,11 @@ import pytest
 from _convnet_util import LR, NESTEROV, batches, close_per_tensor, dev, epoch, make_net, same_bits, step, twins
 from _ema_ref import ema_update
 from _exact_nets import MODES
-from _gap_ref import tensor_slices
 from _oracle_steps import LR as EXACT_LR
+from _torch_ref import tensor_slices
 from _twin_checks import against_torch, compare, device_run, grads, stats
 from test_convnet_deep_plan import (DEEP_NETS, EXACT_NETS, P18, P32, P33, RTOL, RTOL_2, SEEDS, STEPS, ZERO_BIAS_FACTOR, _optimisers, adamw_widened, data,
-                                    exact_case, exact_reference, make_twin, twin_run, zero_bias_tensors)
+                                    exact_case, exact_reference, twin_run, zero_bias_tensors)
 
 pytestmark = pytest.mark.gpu
 
@@ -40,7 +40,7 @@ def _buffered(net, launches):
 
 def _family(name, configure, widened=None):
     make_optim, micro = _optimisers()[name]
-    against_torch(P32, make_twin, configure, make_optim, micro, RTOL_2, f"P32 {name}", widened)
+    against_torch(P32, configure, make_optim, micro, RTOL_2, f"P32 {name}", widened)
 
 
 def test_nesterov_momentum_and_weight_decay_against_torch():

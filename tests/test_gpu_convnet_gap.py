@@ -1,5 +1,5 @@
 """GPU tests of Track X's global average pooling (include/rcn_hipx.h: RCN_HIPX_GLOBAL_AVGPOOL; csrc/convnet_gap.hpp: k_gap_fwd,
-k_gap_bwd<GATE>) on the nets of tests/test_convnet_gap_plan.py: against PyTorch on the CPU in float64 (tests/_gap_ref.py) -- the logits of
+k_gap_bwd<GATE>) on the nets of tests/test_convnet_gap_plan.py: against PyTorch on the CPU in float64 (tests/_torch_ref.py) -- the logits of
 a training forward, the loss, the gradients per tensor, parameters and running statistics after plain SGD steps, the forward and the
 evaluation; bit for bit on integer nets whose sums and quotients are exact; the gate for the ReLU below the pool; and the layer inside the
 recipe (twins, overlap, buckets, the epoch's one graph, metrics, save / load, dropout).
@@ -8,9 +8,10 @@ Tolerances are those of tests/test_gpu_convnet_res.py: fp32 against f64 2e-4 of 
 operands 5e-3 / 2e-2 against the twin with the SAME operand rounding, the training logits also 3e-2 against the unrounded twin."""
 import numpy as np
 import pytest
-from _convnet_util import LR, batches, dev, epoch, make_net, same_bits, step, twins
+from _convnet_util import LR, batches, close, dev, epoch, make_net, same_bits, step, twins
+from _gap_cases import exact_forward, exact_gate_case, exact_logit_case, rows_seen
+from _torch_ref import TorchNet, close_per_tensor, tensor_slices
 from _twin_checks import compare, device_run, grads as _grads, stats as _stats
-from _gap_ref import GapTorchNet, close, close_per_tensor, exact_forward, exact_gate_case, exact_logit_case, rows_seen, tensor_slices
 from test_convnet_gap_plan import (EXACT_SHAPES, GAP_A, GAP_B, GAP_C, GAP_LOOP, GAP_NETS, GATE_PIXELS, RTOL, RTOL_2, SEEDS, STEPS, data, gate_case,
                                    twin_run)
 
@@ -32,7 +33,7 @@ def _compare(name, precision, r, tag=""):
     unrounded = None
     if precision == "bf16":
         flat, x, y = data(spec, SEEDS[name])
-        unrounded = (GapTorchNet(spec[0], spec[1], flat).logits(x, train=True), 3e-2)
+        unrounded = (TorchNet(spec[0], spec[1], flat).logits(x, train=True), 3e-2)
     return compare(spec, r, twin_run(name, precision), RTOL[precision], RTOL_2[precision], STEPS, f"{name} {precision}{tag}", unrounded)
 
 
@@ -63,7 +64,7 @@ def test_loop_case_against_the_twin():
     net.set_params(flat)
     g, loss, z = _grads(net, dev(net, x), dev(net, y), B)
     net.close()
-    rloss, rz, rg = GapTorchNet(in_shape, layers, flat).loss_and_grads(x, y)
+    rloss, rz, rg = TorchNet(in_shape, layers, flat).loss_and_grads(x, y)
     close(z, rz, RTOL["fp32"], "loop training logits")
     close([loss], [rloss], RTOL["fp32"], "loop loss")
     close_per_tensor(g, rg, in_shape, layers, RTOL["fp32"], "loop gradient")
@@ -92,7 +93,7 @@ def test_exact_logits_bit_for_bit(name):
 
 @pytest.mark.parametrize("name", sorted(EXACT_SHAPES))
 def test_exact_input_gradient_is_g_over_hw_or_zero(name):
-    """One sample with one non-zero input value (tests/_gap_ref.py: exact_gate_case): the dense layer's bias gradient IS d logits, the pool's
+    """One sample with one non-zero input value (tests/_gap_cases.py: exact_gate_case): the dense layer's bias gradient IS d logits, the pool's
     gradient is g[c] = +-1/2 of ONE d logit, and the first convolution's weight gradient at (tap, channel 0) has ONE non-zero term -- the
     pool's input gradient at the row that tap reaches from the pixel: fl(g[c] / HW) where the map is positive there, 0 where the ReLU is shut."""
     in_shape, C, classes, _ = EXACT_SHAPES[name]
@@ -132,8 +133,8 @@ def test_the_gate_is_seen():
     net.set_params(flat)
     g, _, _ = _grads(net, dev(net, x), dev(net, y), B)
     net.close()
-    _, _, g_true = GapTorchNet(in_shape, layers, flat).loss_and_grads(x, y)
-    _, _, g_loose = GapTorchNet(in_shape, layers, flat, gate_below=False).loss_and_grads(x, y)
+    _, _, g_true = TorchNet(in_shape, layers, flat).loss_and_grads(x, y)
+    _, _, g_loose = TorchNet(in_shape, layers, flat, gate_below=False).loss_and_grads(x, y)
     close_per_tensor(g, g_true, in_shape, layers, RTOL["fp32"], "net a, gated below the pool: gradient")
     ws, bs = tensor_slices(in_shape, layers)[0]
     factor = max(float(np.abs(g[t] - g_loose[t]).max()) / (2e-4 * max(1e-3, float(np.abs(g_loose[t]).max())) + 1e-6) for t in (ws, bs))

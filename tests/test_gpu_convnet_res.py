@@ -1,5 +1,5 @@
 """GPU tests of Track X's residual blocks (include/rcn_hipx.h: RCN_HIPX_BN_ADD_RELU; csrc/convnet_bn.hpp: k_bn_apply_relu<EVAL, ADD>,
-k_skip_bwd_add) against PyTorch on the CPU in float64 (tests/_res_ref.py) on the four nets of tests/test_convnet_res_plan.py: the logits
+k_skip_bwd_add) against PyTorch on the CPU in float64 (tests/_torch_ref.py) on the four nets of tests/test_convnet_res_plan.py: the logits
 of a training forward, the loss, the gradients per tensor, the running statistics, parameters and losses after plain SGD steps and the
 forward / evaluation on the running statistics; the identity block (equal bits with the net without it), the gate of the skip's source,
 and the skip inside the training recipe.
@@ -9,8 +9,8 @@ a second step; bf16 operands 5e-3 / 2e-2 against the twin with the SAME operand 
 unrounded twin."""
 import numpy as np
 import pytest
-from _convnet_util import LR, batches, dev, epoch, make_net, plan_lines, same_bits, step, twins
-from _res_ref import ResTorchNet, close, close_per_tensor, plain, random_params, tensor_slices
+from _convnet_util import LR, batches, close, dev, epoch, make_net, plan_lines, same_bits, step, twins
+from _torch_ref import TorchNet, close_per_tensor, plain, random_params, tensor_slices
 from _twin_checks import against_torch
 from test_convnet_res_plan import RES_A, RES_B, RES_C, RES_NETS
 
@@ -47,7 +47,7 @@ def _run(spec, precision, flat, x, y, steps):
     import torch
     in_shape, layers, B = spec
     net = make_net(spec, precision)
-    ref = ResTorchNet(in_shape, layers, flat, operand="bf16" if precision == "bf16" else "f64")
+    ref = TorchNet(in_shape, layers, flat, operand="bf16" if precision == "bf16" else "f64")
     net.set_params(flat)
     xd, yd = dev(net, x), dev(net, y)
     out = {}
@@ -89,7 +89,7 @@ def test_training_forward_logits_and_loss(case):
     close([r["loss"]], [r["ref_loss"]], RTOL[precision], f"{name} {precision} loss")
     if precision == "bf16":
         flat, x, y = _data(spec)
-        close(r["logits"], ResTorchNet(spec[0], spec[1], flat).logits(x, train=True), 3e-2, f"{name} bf16 training logits against the unrounded twin")
+        close(r["logits"], TorchNet(spec[0], spec[1], flat).logits(x, train=True), 3e-2, f"{name} bf16 training logits against the unrounded twin")
 
 
 def test_gradients_per_tensor(case):
@@ -197,13 +197,13 @@ def test_the_source_gate_shows():
     on the skip path differs from the true one by more than 10 x the tolerance in some tensor: the comparison below tells the two apart."""
     in_shape, layers, B = RES_C
     flat, x, y = _data(RES_C, seed=13)
-    ref = ResTorchNet(in_shape, layers, flat)
+    ref = TorchNet(in_shape, layers, flat)
     _, _, g_true = ref.loss_and_grads(x, y)
     for s in (1, 5):
         zero = float((ref.outs[s].detach().numpy() == 0).mean())
         print(f"layer {s}: {zero:.2f} of the output is zero")
         assert 0.2 <= zero <= 0.8, (s, zero)
-    _, _, g_loose = ResTorchNet(in_shape, layers, flat, gate_source=False).loss_and_grads(x, y)
+    _, _, g_loose = TorchNet(in_shape, layers, flat, gate_source=False).loss_and_grads(x, y)
     worst = 0.0
     for ws, bs in tensor_slices(in_shape, layers):
         for t in (ws, bs):
@@ -295,7 +295,7 @@ def test_epoch_equals_steps_and_adds_no_graph():
 
 def _against_torch(configure, make_optim, micro=1, rtol=4e-4, tag=""):
     """ONE update of `micro` micro-batches on net a on the device and in float64 torch (tests/_twin_checks.py: against_torch)"""
-    against_torch(RES_A, ResTorchNet, configure, make_optim, micro, rtol, tag)
+    against_torch(RES_A, configure, make_optim, micro, rtol, tag)
 
 
 def test_adamw_step_against_torch():
