@@ -15,8 +15,7 @@
 //                  chunks whose partial tiles go to a slab; the reduction launch (convnet_update.hpp) sums every layer's slab in chunk order (bit-
 //                  reproducible) and applies the SGD step.
 //   k_pool_fwd/bwd 2x2/2 max-pool with a 2-bit arg-max image; backward also applies the ReLU mask.
-//   k_softmax_ce   fused softmax + cross-entropy forward and (p - onehot)/B backward.
-//   k_softmax_ce_soft  the same on a soft target: label smoothing and / or a weighted pair of labels (SoftTarget).
+// The loss kernel (k_softmax_ce) and what it shares with the evaluation and the fused head are in convnet_loss.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -631,133 +630,6 @@ __global__ void k_pool_bwd(const TS* __restrict__ dP, const TS* __restrict__ P, 
 // dZ = dY where the ReLU output is positive (layers without pooling)
 __global__ void k_relu_bwd(const float* __restrict__ dY, const float* __restrict__ Y, float* __restrict__ dZ, long long n) {
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) dZ[e] = Y[e] > 0.f ? dY[e] : 0.f;
-}
-
-// fused softmax + cross-entropy: 32 lanes per sample (lane c takes classes c, c + 32, ...; the padded logits row is ldl wide), eight
-// samples per 256-thread workgroup.  loss_part[block] = sum of -log p[label] over the block's samples in order; the workgroup that
-// finishes LAST (a counter behind the partials, which it leaves at zero for the next launch) adds the partials in block order and
-// writes the mean loss -- no second launch, and the sum does not depend on which workgroup that was.
-// (One thread per sample -- three serial passes over the classes on two CUs -- took 11 us for 512 samples, plus 5 us for the
-// one-thread k_sum_small behind it.)
-__global__ __launch_bounds__(256) void k_softmax_ce(const float* __restrict__ logits, const int* __restrict__ labels, int B, int C, int ldl,
-                                                    float* __restrict__ dlogits, float* loss_part, unsigned* counter, float inv_b, float* __restrict__ loss_out) {
-    __shared__ float red[256];
-    __shared__ int last;
-    const int grp = threadIdx.x >> 5, ln = threadIdx.x & 31;
-    const int s = blockIdx.x * 8 + grp;
-    float loss = 0.f;
-    if (s < B) {
-        const float* z = logits + (long long)s * ldl;
-        const int y = labels[s];
-        float mx = -3.0e38f;
-        for (int c = ln; c < C; c += 32) mx = z[c] > mx ? z[c] : mx;
-#pragma unroll
-        for (int off = 16; off > 0; off >>= 1) { const float o = __shfl_xor(mx, off, 32); mx = o > mx ? o : mx; }
-        float sum = 0.f;
-        for (int c = ln; c < C; c += 32) sum += expf(z[c] - mx);
-#pragma unroll
-        for (int off = 16; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 32);
-        loss = -(z[y] - mx - logf(sum));
-        if (dlogits) {
-            float* d = dlogits + (long long)s * ldl;
-            for (int c = ln; c < ldl; c += 32) d[c] = c < C ? (expf(z[c] - mx) / sum - (c == y ? 1.f : 0.f)) * inv_b : 0.f;
-        }
-    }
-    if (ln == 0) red[grp] = loss;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int g = 0; g < 8; ++g) t += red[g];
-        __hip_atomic_store(&loss_part[blockIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last || !loss_out) {
-        if (last && threadIdx.x == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    float t = 0.f;
-    for (int b = threadIdx.x; b < (int)gridDim.x; b += 256) t += __hip_atomic_load(&loss_part[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    red[threadIdx.x] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float tot = 0.f;
-        for (int i = 0; i < 256; ++i) tot += red[i];
-        *loss_out = tot * inv_b;
-        __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// What a soft-target loss takes beyond the hard one's labels (rcn_hipx_set_loss, rcn_hipx_train_step_pair_dev): per sample the target is
-//     t_c = (1 - eps) * (w * [c == ya] + (1 - w) * [c == yb]) + eps / C
-// labels_b == nullptr: yb = ya; weight (ONE device scalar, the weight of the row's own label ya) == nullptr: w = 1.
-struct SoftTarget { const int* labels_b; const float* weight; float eps; };
-
-// k_softmax_ce on a soft target: the same 32 lanes per sample, the same partials in sample order and the same last-arriver sum.  With
-// lp_c = (z_c - mx) - logf(sum), every operation rounded once (no fused multiply-add):
-//     loss = -((1 - eps) * (w * lp_ya + (1 - w) * lp_yb) + (eps / C) * sum_c lp_c)        d_c = (p_c - t_c) * inv_b
-// A label outside [0, C) never indexes the row: its indicator is 0 everywhere and its lp term is dropped (k_eval_ce's rule).  At eps = 0,
-// w = 1 the expressions give k_softmax_ce's bits without a special case: 1 * x, x + 0 and 0 * x (x finite) are exact.
-__global__ __launch_bounds__(256) void k_softmax_ce_soft(const float* __restrict__ logits, const int* __restrict__ labels, SoftTarget tg, int B, int C, int ldl,
-                                                         float* __restrict__ dlogits, float* loss_part, unsigned* counter, float inv_b, float* __restrict__ loss_out) {
-#pragma clang fp contract(off)
-    __shared__ float red[256];
-    __shared__ int last;
-    const int grp = threadIdx.x >> 5, ln = threadIdx.x & 31;
-    const int s = blockIdx.x * 8 + grp;
-    float loss = 0.f;
-    if (s < B) {
-        const float* z = logits + (long long)s * ldl;
-        const int ya = labels[s], yb = tg.labels_b ? tg.labels_b[s] : ya;
-        const float w = tg.weight ? *tg.weight : 1.f;
-        float mx = -3.0e38f;
-        for (int c = ln; c < C; c += 32) mx = z[c] > mx ? z[c] : mx;
-#pragma unroll
-        for (int off = 16; off > 0; off >>= 1) { const float o = __shfl_xor(mx, off, 32); mx = o > mx ? o : mx; }
-        float sum = 0.f;
-        for (int c = ln; c < C; c += 32) sum += expf(z[c] - mx);
-#pragma unroll
-        for (int off = 16; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 32);
-        const float lse = logf(sum);
-        float slp = 0.f;                                    // sum over the classes of lp_c
-        for (int c = ln; c < C; c += 32) slp += (z[c] - mx) - lse;
-#pragma unroll
-        for (int off = 16; off > 0; off >>= 1) slp += __shfl_xor(slp, off, 32);
-        const float lpa = (ya >= 0 && ya < C) ? (z[ya] - mx) - lse : 0.f;
-        const float lpb = (yb >= 0 && yb < C) ? (z[yb] - mx) - lse : 0.f;
-        const float keep = 1.f - tg.eps, wb = 1.f - w, u = tg.eps / (float)C;
-        loss = -(keep * (w * lpa + wb * lpb) + u * slp);
-        if (dlogits) {
-            float* d = dlogits + (long long)s * ldl;
-            for (int c = ln; c < ldl; c += 32) {
-                const float t = keep * (w * (c == ya ? 1.f : 0.f) + wb * (c == yb ? 1.f : 0.f)) + u;
-                d[c] = c < C ? (expf(z[c] - mx) / sum - t) * inv_b : 0.f;
-            }
-        }
-    }
-    if (ln == 0) red[grp] = loss;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int g = 0; g < 8; ++g) t += red[g];
-        __hip_atomic_store(&loss_part[blockIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last || !loss_out) {
-        if (last && threadIdx.x == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    float t = 0.f;
-    for (int b = threadIdx.x; b < (int)gridDim.x; b += 256) t += __hip_atomic_load(&loss_part[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    red[threadIdx.x] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float tot = 0.f;
-        for (int i = 0; i < 256; ++i) tot += red[i];
-        *loss_out = tot * inv_b;
-        __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
 }
 
 }  // namespace rcnx

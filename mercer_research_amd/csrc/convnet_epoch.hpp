@@ -9,8 +9,7 @@
 //                           16-byte stores on the write side.
 //   k_gather_mix<TS, VEC>   mixup / CutMix (rcn_hipx_mix_step): every output row blended with, or inside a box replaced by, the row that
 //                           mirrors it in the SAME batch, each gathered (and augmented) as the kernels above would; both labels out.
-//   k_eval_ce               soft-max cross-entropy, first-maximum arg-max and correct count of one chunk of logits, without d logits;
-//                           its last-arriving workgroup ADDS the chunk's totals into a double / int64 pair.
+// The evaluation kernel behind rcn_hipx_evaluate_dev is k_eval<false> (convnet_metrics.hpp).
 #pragma once
 
 #include <type_traits>
@@ -245,96 +244,6 @@ inline GatherChoice select_gather(bool u8, int B, int E, bool src_aligned16, boo
     c.vec = (E % piece == 0 && src_aligned16 && dst_aligned16) ? piece : 1;
     c.blocks = gather_blocks(B, E, c.vec);
     return c;
-}
-
-constexpr int kEvalSamples = 8;        // samples per 256-thread workgroup of k_eval_ce (k_softmax_ce's grouping)
-inline int eval_blocks(int B) { return (B + kEvalSamples - 1) / kEvalSamples; }
-
-// One sample's share of an evaluation, run by the 32 lanes (ln) of its group on its logits row z: the maximum, the FIRST class that
-// attains it (ix; written to pred[s] where pred is given), and with labels the label y, loss = -(z[y] - max - log(sum exp)) and
-// ok = (ix == y); a label outside [0, C) never indexes the row and leaves loss and ok at the caller's zeros.  The one routine of
-// k_eval_ce and k_eval_metrics (convnet_metrics.hpp): both add the same float into their workgroup's partial.
-__device__ __forceinline__ void eval_sample(const float* __restrict__ z, int C, int ln, const int* __restrict__ labels, int s, int* __restrict__ pred, float& loss, int& ok,
-                                            int& ix_out, int& y_out) {
-    float mx = -3.0e38f;
-    int ix = 0x7fffffff;
-    for (int c = ln; c < C; c += 32)
-        if (z[c] > mx) { mx = z[c]; ix = c; }           // strictly greater: the first maximum of this lane's classes
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) {
-        const float o = __shfl_xor(mx, off, 32);
-        const int oi = __shfl_xor(ix, off, 32);
-        if (o > mx || (o == mx && oi < ix)) { mx = o; ix = oi; }
-    }
-    if (ix >= C) ix = 0;                                // (no class above -3e38: a row of NaN or -inf)
-    if (pred && ln == 0) pred[s] = ix;
-    ix_out = ix;
-    if (labels) {
-        const int y = labels[s];
-        y_out = y;
-        if (y >= 0 && y < C) {
-            float sum = 0.f;
-            for (int c = ln; c < C; c += 32) sum += expf(z[c] - mx);
-#pragma unroll
-            for (int off = 16; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 32);
-            loss = -(z[y] - mx - logf(sum));
-            ok = ix == y;
-        }
-    }
-}
-
-// Evaluation of one chunk of B logits rows (ldl floats apart): 32 lanes per sample as in k_softmax_ce, no d logits.  Per sample the
-// maximum, the FIRST class that attains it (pred, nullable), and -(z[y] - max - log(sum exp)); a label outside [0, C) never indexes the
-// row: the sample counts as incorrect and adds nothing to the loss (eval_sample).  loss_part[block] = the block's losses summed in sample order,
-// correct_part[block] its correct count; the workgroup that arrives LAST adds the partials in a fixed order (thread t takes blocks
-// t, t + 256, ...; thread 0 adds the 256 sums in order), in double, and ADDS the chunk's totals into *loss_sum / *correct -- chunks run
-// one after the other on the net's stream, so the accumulators need no atomics.  It leaves the counter at zero.  labels == nullptr:
-// prediction only, no partials and no counter.
-__global__ __launch_bounds__(256) void k_eval_ce(const float* __restrict__ logits, const int* __restrict__ labels, int B, int C, int ldl, float* loss_part, int* correct_part,
-                                                 unsigned* counter, double* loss_sum, long long* correct, int* __restrict__ pred) {
-    __shared__ float red[kEvalSamples];
-    __shared__ int hit[kEvalSamples];
-    __shared__ double dsum[256];
-    __shared__ long long csum[256];
-    __shared__ int last;
-    const int grp = threadIdx.x >> 5, ln = threadIdx.x & 31;
-    const int s = blockIdx.x * kEvalSamples + grp;
-    float loss = 0.f;
-    int ok = 0;
-    if (s < B) {
-        int ix, y;
-        eval_sample(logits + (long long)s * ldl, C, ln, labels, s, pred, loss, ok, ix, y);
-    }
-    if (!labels) return;
-    if (ln == 0) { red[grp] = loss; hit[grp] = ok; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        int h = 0;
-        for (int g = 0; g < kEvalSamples; ++g) { t += red[g]; h += hit[g]; }
-        __hip_atomic_store(&loss_part[blockIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&correct_part[blockIdx.x], h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    double t = 0.0;
-    long long h = 0;
-    for (int b = threadIdx.x; b < (int)gridDim.x; b += 256) {
-        t += (double)__hip_atomic_load(&loss_part[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        h += __hip_atomic_load(&correct_part[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    dsum[threadIdx.x] = t;
-    csum[threadIdx.x] = h;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = 0.0;
-        long long hits = 0;
-        for (int i = 0; i < 256; ++i) { tot += dsum[i]; hits += csum[i]; }
-        *loss_sum = *loss_sum + tot;
-        *correct = *correct + hits;
-        __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
 }
 
 }  // namespace rcnx

@@ -13,7 +13,7 @@
 //                         activations: the weights live in registers, the input halo of a block is a few hundred floats
 #pragma once
 
-#include "convnet.hpp"
+#include "convnet_loss.hpp"
 
 // Timeline instrumentation for tools/halo_stamps.hip (never defined in the library build): thread 0 of a workgroup records the
 // 100 MHz wall clock at a few points of its life.
@@ -969,10 +969,9 @@ __global__ __launch_bounds__(kThreads) void k_conv1_wgrad_f32(const float* __res
 // gradient 14.8, weight gradient 10.6 us: latency, not arithmetic).  Here a workgroup owns 32 samples: their hidden activations,
 // the weights in both orientations (the flipped copy is kept current by the update kernels) and d logits stay in LDS between the
 // steps.  F = hidden width (multiple of 32, <= 256: LDS), classes <= 32 (one padded column block).  The weight-gradient partials go
-// to slab[workgroup][F + 1][32] like k_conv_wgrad's, so the reduction launch finishes; the loss like k_softmax_ce (last workgroup
-// adds the partials in order).
-// SOFT: the soft-max stage takes a soft target (k_softmax_ce_soft's expressions and label guard) from ONE trailing SoftTarget argument;
-// the hard instantiation has no such argument: its launch is unchanged.
+// to slab[workgroup][F + 1][32] like k_conv_wgrad's, so the reduction launch finishes; the loss by arrive_last / finish_mean.
+// SOFT: the soft-max stage takes a soft target (convnet_loss.hpp) from ONE trailing SoftTarget argument; the hard instantiation has no
+// such argument.  In the plans: k_head_f32<true> is `k_head_f32`, k_head_f32<true, true, SoftTarget> is `k_head_f32<true, true>`.
 template <bool GATE, bool SOFT = false, typename... Soft>
 __global__ __launch_bounds__(kThreads) void k_head_f32(const float* __restrict__ Hin, const float* __restrict__ Wk, const float* __restrict__ Wt,
                                                        const float* __restrict__ bias, const int* __restrict__ labels, int B, int F, int C,
@@ -987,7 +986,6 @@ __global__ __launch_bounds__(kThreads) void k_head_f32(const float* __restrict__
     float* Ds = Ls + 4 * 1024;                   // [32 samples][32]: d logits, B operand of the weight gradient
     float* DsA = Ds + 1024;                      // [32][33]: the same, A operand of the input gradient
     __shared__ float red[kThreads];
-    __shared__ int last;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
     const int s0 = blockIdx.x * 32, F4 = F >> 2;
     for (int e = tid; e < 32 * F4; e += kThreads) {
@@ -1031,8 +1029,8 @@ __global__ __launch_bounds__(kThreads) void k_head_f32(const float* __restrict__
 #pragma clang fp contract(off)
             const SoftTarget tg{soft...};
             const int ya = s < B ? labels[s] : 0, yb = (s < B && tg.labels_b) ? tg.labels_b[s] : ya;
-            const float w = tg.weight ? *tg.weight : 1.f;
-            const float lse = logf(sum), keep = 1.f - tg.eps, wb = 1.f - w, u = tg.eps / (float)C;
+            const float lse = logf(sum);
+            const SoftCoef k = soft_coef(tg, C);
             float slp = 0.f, lpa = 0.f, lpb = 0.f;              // sum over the classes of lp_c; lp of the two labels (0: outside [0, C))
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -1043,10 +1041,10 @@ __global__ __launch_bounds__(kThreads) void k_head_f32(const float* __restrict__
             }
 #pragma unroll
             for (int off = 4; off > 0; off >>= 1) { slp += __shfl_xor(slp, off, 8); lpa += __shfl_xor(lpa, off, 8); lpb += __shfl_xor(lpb, off, 8); }
-            if ((tid & 7) == 0) red[sm] = s < B ? -(keep * (w * lpa + wb * lpb) + u * slp) : 0.f;
+            if ((tid & 7) == 0) red[sm] = s < B ? soft_loss_of(k, lpa, lpb, slp) : 0.f;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float t = keep * (w * (cg + j == ya ? 1.f : 0.f) + wb * (cg + j == yb ? 1.f : 0.f)) + u;
+                const float t = soft_t(k, cg + j, ya, yb);
                 const float d = (s < B && cg + j < C) ? (ex[j] / sum - t) * inv_b : 0.f;
                 Ds[sm * 32 + cg + j] = d;
                 DsA[sm * 33 + cg + j] = d;
@@ -1104,26 +1102,12 @@ __global__ __launch_bounds__(kThreads) void k_head_f32(const float* __restrict__
         out[(long long)F * 32 + tid] = t;
     }
     // ---- loss: this workgroup's samples in order, then (last workgroup) the workgroups in order
-    if (tid == 0) {
-        float t = 0.f;
-        for (int g = 0; g < 32; ++g) t += red[g];
-        __hip_atomic_store(&loss_part[blockIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    float t = 0.f;
-    if (loss_out)
-        for (int b = tid; b < (int)gridDim.x; b += kThreads) t += __hip_atomic_load(&loss_part[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    red[tid] = t;
-    __syncthreads();
-    if (tid == 0) {
-        float tot = 0.f;
-        for (int i = 0; i < kThreads; ++i) tot += red[i];
-        if (loss_out) *loss_out = tot * inv_b;
-        __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (!arrive_last(counter, [&] {
+            float t = 0.f;
+            for (int g = 0; g < 32; ++g) t += red[g];
+            put_partial(loss_part, t);
+        })) return;
+    finish_mean(loss_part, counter, inv_b, loss_out, red);
 }
 
 }  // namespace rcnx

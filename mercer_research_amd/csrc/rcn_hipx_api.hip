@@ -20,6 +20,7 @@
 
 #include "convnet.hpp"
 #include "convnet_bf16.hpp"
+#include "convnet_loss.hpp"
 #include "convnet_epoch.hpp"
 #include "convnet_metrics.hpp"
 #include "convnet_halo.hpp"
@@ -157,8 +158,7 @@ struct rcn_hipx_net : Selection, Recipe {
     // mixed samples (rcn_hipx_train_epoch_mix_dev with records): the partners' labels beside yb and the step's target weight, allocated
     // once and never moved; the mixed step's loss launch reads (yb, yb2, emixw), so ONE more graph per (B, lr) / per B serves every record
     Buf yb2, emixw;
-    Buf eval_part;                          // k_eval_ce: [loss partials][correct partials][counter: zero between launches]
-    Buf eval_mpart;                         // k_eval_metrics, its own: [loss partials][correct partials][counter][top-k partials: 8 rows]; sized by max_batch, never moved
+    Buf eval_part;                          // k_eval: [loss partials][correct partials][counter: zero between launches][top-k partials: 8 rows]; sized by max_batch, never moved
     long long n_instantiated = 0;           // hipGraphs instantiated since the net was created (rcn_hipx_graphs_instantiated)
     int last_rows = 0;                      // the batch of the last forward pass (rcn_hipx_last_logits_dev); 0: none yet
     bool walk_open = false;                 // between rcn_hipx_gradients_begin_dev and its last bucket: the activations belong to that walk
@@ -907,9 +907,12 @@ int loss_and_dlogits(rcn_hipx_net* n, const int32_t* labels, int B, float* loss_
     float* const dlogits = want_grad ? (float*)l.dout.p : (float*)nullptr;
     float* const part = (float*)n->loss_part.p;
     const float inv_b = 1.0f / (float)B;
-    if (soft) hipLaunchKernelGGL(k_softmax_ce_soft, dim3(blocks), dim3(256), 0, n->stream, logits, labels, SoftTarget{pair.labels_b, pair.weight, n->loss_eps}, B, n->classes, l.CoutP,
-                                 dlogits, part, counter, inv_b, loss_dev);
-    else hipLaunchKernelGGL(k_softmax_ce, dim3(blocks), dim3(256), 0, n->stream, logits, labels, B, n->classes, l.CoutP, dlogits, part, counter, inv_b, loss_dev);
+    // the hard kernel, or the soft one with its one trailing argument
+    auto launch = [&](auto kernel, auto... target) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, n->stream, logits, labels, B, n->classes, l.CoutP, dlogits, part, counter, inv_b, loss_dev, target...);
+    };
+    if (soft) launch(k_softmax_ce<true, SoftTarget>, SoftTarget{pair.labels_b, pair.weight, n->loss_eps});
+    else launch(k_softmax_ce<false>);
     XTRY(n, hipGetLastError());
     return 0;
 }
@@ -1538,23 +1541,6 @@ int launch_gather(rcn_hipx_net* n, const void* X, int x_kind, float x_scale, flo
 #undef CT
 #undef CV
 
-// loss sum, correct count and arg-max of the B logits rows the forward pass has just left in the last layer's output
-int launch_eval(rcn_hipx_net* n, const int32_t* labels, int B, double* loss_sum, long long* correct, int32_t* pred) {
-    const int blocks = eval_blocks(B);
-    if (dry_note(n, "  eval: k_eval_ce, %d workgroups (loss sum, correct count, first-maximum arg-max; no gradient)", blocks)) return 0;
-    const Layer& l = n->L.back();
-    const size_t parts = (size_t)eval_blocks(n->max_batch);
-    if (!n->eval_part.p) {
-        XTRY(n, n->eval_part.ensure((2 * parts + 1) * sizeof(float)));
-        XTRY(n, hipMemsetAsync(n->eval_part.p, 0, n->eval_part.cap, n->stream));
-    }
-    float* const lp = (float*)n->eval_part.p;
-    hipLaunchKernelGGL(k_eval_ce, dim3(blocks), dim3(256), 0, n->stream, (const float*)l.out.p, labels, B, n->classes, l.CoutP, lp, (int*)(lp + parts), (unsigned*)(lp + 2 * parts),
-                       loss_sum, correct, pred);
-    XTRY(n, hipGetLastError());
-    return 0;
-}
-
 // what a metrics call asked for, in the words of its plan line
 void metrics_asked(const rcn_hipx_eval_out& o, std::string& t) {
     if (o.n_topk > 0) t += "; top-k counts for " + std::to_string(o.n_topk) + (o.n_topk == 1 ? " k" : " ks");
@@ -1563,46 +1549,54 @@ void metrics_asked(const rcn_hipx_eval_out& o, std::string& t) {
     if (o.logits) t += "; logits copy";
 }
 
-// launch_eval's launch with the outputs of `o` for the chunk's B rows, which begin at row `off` of the call: k_eval_metrics in the place of
-// k_eval_ce, on partials of its own
-int launch_eval_metrics(rcn_hipx_net* n, const int32_t* labels, int B, int64_t off, const rcn_hipx_eval_out& o) {
+// loss sum, correct count and arg-max of the B logits rows the forward pass has just left in the last layer's output; with `o` (a metrics
+// call's outputs; the chunk's rows begin at row `off` of them) also what it asks for, in the same launch
+int launch_eval(rcn_hipx_net* n, const int32_t* labels, int B, double* loss_sum, long long* correct, int32_t* pred, const rcn_hipx_eval_out* o, int64_t off) {
     const int blocks = eval_blocks(B);
-    if (n->dry) {
+    if (n->dry && o) {
         std::string asked;
-        metrics_asked(o, asked);
-        return dry_note(n, "  eval: k_eval_metrics, %d workgroups (loss sum, correct count, first-maximum arg-max%s; no gradient)", blocks, asked.c_str()) ? 0 : -4;
+        metrics_asked(*o, asked);
+        dry_note(n, "  eval: k_eval_metrics, %d workgroups (loss sum, correct count, first-maximum arg-max%s; no gradient)", blocks, asked.c_str());
+        return 0;
     }
+    if (dry_note(n, "  eval: k_eval_ce, %d workgroups (loss sum, correct count, first-maximum arg-max; no gradient)", blocks)) return 0;
     const Layer& l = n->L.back();
     const size_t parts = (size_t)eval_blocks(n->max_batch);
-    if (!n->eval_mpart.p) {
-        XTRY(n, n->eval_mpart.ensure(((2 + kEvalMaxTopk) * parts + 1) * sizeof(float)));
-        XTRY(n, hipMemsetAsync(n->eval_mpart.p, 0, n->eval_mpart.cap, n->stream));
+    if (!n->eval_part.p) {
+        XTRY(n, n->eval_part.ensure(((2 + kEvalMaxTopk) * parts + 1) * sizeof(float)));
+        XTRY(n, hipMemsetAsync(n->eval_part.p, 0, n->eval_part.cap, n->stream));
     }
-    float* const lp = (float*)n->eval_mpart.p;
-    const bool with_labels = labels != nullptr;
-    const long long C = n->classes;
-    EvalMetrics m{};
-    m.n_topk = with_labels ? o.n_topk : 0;
-    for (int j = 0; j < m.n_topk; ++j) m.topk[j] = o.topk[j];
-    m.topk_part = (int*)(lp + 2 * parts + 1);
-    m.part_stride = (int)parts;
-    m.topk_correct = (long long*)o.topk_correct;
-    m.confusion = (long long*)o.confusion;
-    m.loss_each = o.loss_each ? o.loss_each + off : nullptr;
-    m.rank = o.rank ? o.rank + off : nullptr;
-    m.logits_out = o.logits ? o.logits + off * C : nullptr;
-    hipLaunchKernelGGL(k_eval_metrics, dim3(blocks), dim3(256), 0, n->stream, (const float*)l.out.p, labels, B, n->classes, l.CoutP, lp, (int*)(lp + parts), (unsigned*)(lp + 2 * parts),
-                       o.loss_sum, (long long*)o.correct, o.pred ? o.pred + off : nullptr, m);
+    float* const lp = (float*)n->eval_part.p;
+    // the plain kernel, or the metrics one with its one trailing argument
+    auto launch = [&](auto kernel, auto... metrics) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, n->stream, (const float*)l.out.p, labels, B, n->classes, l.CoutP, lp, (int*)(lp + parts), (unsigned*)(lp + 2 * parts),
+                           loss_sum, correct, pred, metrics...);
+    };
+    if (o) {
+        const long long C = n->classes;
+        EvalMetrics m{};
+        m.n_topk = labels ? o->n_topk : 0;
+        for (int j = 0; j < m.n_topk; ++j) m.topk[j] = o->topk[j];
+        m.topk_part = (int*)(lp + 2 * parts + 1);
+        m.part_stride = (int)parts;
+        m.topk_correct = (long long*)o->topk_correct;
+        m.confusion = (long long*)o->confusion;
+        m.loss_each = o->loss_each ? o->loss_each + off : nullptr;
+        m.rank = o->rank ? o->rank + off : nullptr;
+        m.logits_out = o->logits ? o->logits + off * C : nullptr;
+        launch(k_eval<true, EvalMetrics>, m);
+    } else {
+        launch(k_eval<false>);
+    }
     XTRY(n, hipGetLastError());
     return 0;
 }
 
-// one evaluation chunk: the forward pass over all layers (rcn_hipx_forward_dev's) and the evaluation kernel -- k_eval_ce, or with
-// `metrics` (the call's outputs; the chunk begins at row `off` of them) k_eval_metrics
+// one evaluation chunk: the forward pass over all layers (rcn_hipx_forward_dev's) and the evaluation kernel
 int eval_chunk(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, double* loss_sum, long long* correct, int32_t* pred, const rcn_hipx_eval_out* metrics = nullptr,
                int64_t off = 0) {
     RTRY(forward(n, x, B));
-    return metrics ? launch_eval_metrics(n, labels, B, off, *metrics) : launch_eval(n, labels, B, loss_sum, correct, pred);
+    return launch_eval(n, labels, B, loss_sum, correct, pred, metrics, off);
 }
 
 // params <-> average, on the net's stream

@@ -65,6 +65,26 @@ def loss_sum_from_rows(loss_each, max_batch):
     return np.float64(total)
 
 
+def step_loss_from_rows(loss_each):
+    """A training step's loss (float32) rebuilt from the per-row floats of its batch in the loss kernel's order: blocks of 8 rows, each summed
+    in row order; "thread t" adds blocks t, t + 256, ...; the 256 sums are added in order; the total times fl(1 / B).  All in float32."""
+    rows = np.asarray(loss_each)
+    assert rows.dtype == np.float32 and rows.ndim == 1, (rows.dtype, rows.shape)
+    blocks = []
+    for b in range(0, rows.size, 8):
+        t = np.float32(0.0)
+        for v in rows[b:b + 8]:
+            t = np.float32(t + v)
+        blocks.append(t)
+    tot = np.float32(0.0)
+    for t in range(256):
+        acc = np.float32(0.0)
+        for v in blocks[t::256]:
+            acc = np.float32(acc + v)
+        tot = np.float32(tot + acc)
+    return np.float32(tot * (np.float32(1.0) / np.float32(rows.size)))
+
+
 def cross_entropy(logits, y):
     """[n] float64 soft-max cross-entropy of every row with a label inside [0, classes); 0 for the others"""
     z = np.asarray(logits, dtype=np.float64)

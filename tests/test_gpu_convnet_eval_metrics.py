@@ -15,7 +15,7 @@ from types import SimpleNamespace
 import _eval_ref
 import numpy as np
 import pytest
-from _convnet_util import CONVNET_NETS, FUSED_HEAD, KW, PLAIN_HEAD, POOL_PAIRS, dev, epoch, make_net, plan_lines, random_set, sync, twins, widen
+from _convnet_util import CONVNET_NETS, FUSED_HEAD, KW, ODD_WIDTH, PLAIN_HEAD, POOL_PAIRS, dev, epoch, make_net, plan_lines, random_set, sync, twins, widen
 from _exact_nets import EVAL_ROWS, certificate, eval_set, exact_case
 
 from oracle import convnet_oracle as co
@@ -193,6 +193,29 @@ def test_per_row_loss_rebuilds_the_sum_and_is_the_cross_entropy(name, precision,
     worst = int(np.argmax(dev_ / np.maximum(1.0, ref)))
     print(f"per-row loss: largest deviation {dev_[worst]:.3e} at row {worst} (reference {ref[worst]:.6g}, bound {2e-4 * max(1.0, ref[worst]):.3e})")
     assert (dev_ <= 2e-4 * np.maximum(1.0, ref)).all(), (worst, float(each[worst]), float(ref[worst]))
+
+
+def test_a_chunk_of_257_workgroups_sums_its_partials_in_the_documented_order():
+    """max_batch = 2049 rows in ONE chunk: 257 workgroups of 8 rows, the last with one row, so "thread 0" of the last-arriving workgroup takes
+    the partials of blocks 0 and 256 (the second trip of the final sum).  loss_sum is the restated sum of loss_each bit for bit, the
+    integers are exact, and evaluate_async before and after the metrics call gives the metrics call's bytes."""
+    spec, B = ODD_WIDTH, 2049
+    net = make_net(spec, max_batch=B)
+    net.init_params(3)
+    assert "k_eval_ce, 257 workgroups" in net.plan_eval_of_this_net(B) and "k_eval_metrics, 257 workgroups" in net.plan_eval_metrics_of_this_net(B)
+    X, y = random_set(net, spec, B, seed=7)
+    before = _eval_bytes(net, X, y)
+    m = _metrics(net, X, y, (1, 2))
+    after = _eval_bytes(net, X, y)
+    net.close()
+    rebuilt = _eval_ref.loss_sum_from_rows(m["loss_each"], B)
+    print(f"loss_sum {float(m['loss_sum'][0])!r} rebuilt {float(rebuilt)!r} plain float64 sum {float(m['loss_each'].astype(np.float64).sum())!r}")
+    assert m["loss_each"].shape == (B,) and (m["loss_each"] > 0).all()
+    assert rebuilt.tobytes() == m["loss_sum"].tobytes(), (float(rebuilt), float(m["loss_sum"][0]))
+    assert before == after == (m["loss_sum"].tobytes(), m["correct"].tobytes(), m["pred"].tobytes())
+    want_rank = _eval_ref.rank(m["logits"], y.cpu().numpy())
+    assert np.array_equal(m["rank"], want_rank) and np.array_equal(m["topk_correct"], _eval_ref.topk_counts(want_rank, (1, 2)))
+    assert int(m["correct"][0]) == int(m["topk_correct"][0]) == int(np.trace(m["confusion"])) and int(m["confusion"].sum()) == B
 
 
 # ---- 5. ties -----------------------------------------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@ pooled-resolution gradients into the input-gradient and weight-gradient kernels,
 No reference counterpart ("parity unpinned"); tolerance as tests/test_gpu_convnet.py: |d| <= 2e-4 * scale + 1e-6."""
 import numpy as np
 import pytest
-from _convnet_util import HALO_NETS, close, close_per_tensor, make_net, oracle_params
+from _convnet_util import FUSED_HEAD, HALO_NETS, close, close_per_tensor, make_net, oracle_params
 
 from oracle import convnet_oracle as co
 
@@ -79,6 +79,29 @@ def test_tiling_modes_agree(in_shape, layers, B):
     for mode in ("auto", "lds"):
         close(out[mode][0], out["gemm"][0], rtol=1e-5)
         close(out[mode][1], out["gemm"][1], rtol=2e-5)
+
+
+def test_fused_head_loss_of_257_workgroups_agrees_with_the_plain_path():
+    """B = 8193 on FUSED_HEAD: 257 workgroups of 32 samples, the last with one, so "thread 0" of the last-arriving workgroup takes the
+    partials of blocks 0 and 256.  The head sums a row's exponentials with 8 lanes, the plain path (option head = 0: k_softmax_ce) with 32,
+    so the two losses are held as test_tiling_modes_agree holds two routes to the same logits: rtol 1e-5."""
+    in_shape, layers, _ = FUSED_HEAD
+    B = 8193
+    loss = {}
+    for head in (1, 0):
+        torch, net, flat, x, y, _, _ = _setup(in_shape, layers, B, "auto")
+        net.set_option("head", head)
+        plan = net.plan_of_this_net(B)
+        assert ("k_head_f32, 257 workgroups" if head else "k_softmax_ce, 1025 workgroups") in plan, plan
+        xd, yd = net.to_device(x), net.to_device(y)
+        with torch.cuda.stream(net.stream):
+            out = torch.zeros(1, dtype=torch.float32, device=net.device)
+            net.gradients(xd, yd, loss=out)
+        net.synchronize()
+        loss[head] = out.item()
+        net.close()
+    print("fused", repr(loss[1]), "plain", repr(loss[0]))
+    close([loss[1]], [loss[0]], rtol=1e-5)
 
 
 def test_set_tiling_rejects_unknown_modes():

@@ -272,6 +272,35 @@ def test_records_that_mix_nothing_give_the_unmixed_epoch_bit_for_bit(spec, preci
     a.close(); b.close()
 
 
+def test_a_loss_of_257_workgroups_is_the_restated_sum_of_its_rows_hard_and_soft():
+    """B = 2049 on ODD_WIDTH (no fused head): 257 workgroups of 8 samples, the last with one, so "thread 0" of the last-arriving workgroup
+    takes the partials of blocks 0 and 256.  The pair step at eps = 0, w = 1 gives the hard step's bits; and the step's loss is the
+    float32 restatement, in the kernel's order, of the per-row losses evaluate_metrics returns for the same parameters and batch before
+    the step (the row expression is the one routine of both kernels)."""
+    import _eval_ref
+    import torch
+    B = 2049
+    spec = (ODD_WIDTH[0], ODD_WIDTH[1], B)
+    a, b = twins(spec, "fp32")
+    assert "k_softmax_ce, 257 workgroups" in a.plan_of_this_net(B)
+    x, ya, yb, xd, yad, ybd = _pair_batch(a, spec, 97)
+    out = a.evaluate_metrics_async(xd, yad, topk=(1,), confusion=False, per_row=True)
+    a.synchronize()
+    each = out["loss_each"].cpu().numpy().copy()
+    one = dev(b, np.array([1.0], dtype=np.float32))
+    la, lb = zeros(a, 1), zeros(b, 1)
+    with torch.cuda.stream(a.stream):
+        a.train_step(xd, yad, 0.05, la)
+    with torch.cuda.stream(b.stream):
+        b.train_step_pair(xd, yad, ybd, one, 0.05, lb)
+    a.synchronize(); b.synchronize()
+    hard, soft, want = la.cpu().numpy(), lb.cpu().numpy(), _eval_ref.step_loss_from_rows(each)
+    print(f"hard {hard[0]!r} soft {soft[0]!r} restated {want!r} float64 mean {float(each.astype(np.float64).mean())!r}")
+    assert hard.tobytes() == soft.tobytes() and same_state(a, b)
+    assert hard.tobytes() == want.tobytes(), (hard, want)
+    a.close(); b.close()
+
+
 # ---- 7. set_loss -----------------------------------------------------------------------------------------------------------------------
 
 def test_set_loss_refusals_round_trip_evaluation_and_plans():

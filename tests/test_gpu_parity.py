@@ -1121,7 +1121,7 @@ def test_device_shuffle_writes_permutations(amd):
     d = DeviceRCN()
     for n, passes in ((16384, 8), (1000, 3), (7, 5), (1, 2), (65537, 2)):
         perm = torch.full((n * passes,), -1, dtype=torch.int32, device=d.device)
-        d.synchronize()
+        torch.cuda.synchronize()                         # the fill runs on torch's stream, the shuffle on the context's own
         d.shuffle(perm, n, passes, seed=1234)
         d.synchronize()
         p = perm.cpu().numpy().reshape(passes, n)
