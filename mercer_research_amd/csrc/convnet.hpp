@@ -40,9 +40,12 @@ __device__ inline f32x4 widen4(const bf16x4& v) { return f32x4{(float)v[0], (flo
 __device__ inline float widen(float v) { return v; }
 __device__ inline float widen(__bf16 v) { return (float)v; }
 template <typename TS> __device__ inline TS narrow(float v) { return (TS)v; }                      // (float -> __bf16: round to nearest even)
-template <typename TS> __device__ inline chunk4_t<TS> narrow4(const f32x4& v);
-template <> __device__ inline f32x4 narrow4<float>(const f32x4& v) { return v; }
-template <> __device__ inline bf16x4 narrow4<__bf16>(const f32x4& v) { return bf16x4{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]}; }
+__device__ inline bf16x4 to_bf16x4(const f32x4& v) {
+    bf16x4 h;
+    h[0] = (__bf16)v[0]; h[1] = (__bf16)v[1]; h[2] = (__bf16)v[2]; h[3] = (__bf16)v[3];
+    return h;
+}
+__device__ inline bf16x4 to_bf16x4(const bf16x4& v) { return v; }         // a chunk that is stored as bf16 already
 
 
 constexpr int kBM = 128, kBK = 32, kThreads = 256;
@@ -276,6 +279,20 @@ struct WgradGrid {
     }
 };
 
+// The pixel row a weight-gradient thread loads next.  Its rows are pixels m, m + STEP, m + 2 STEP, ... across the chunks of a stage AND
+// across stages, so (oh, ow) is running state advanced by STEP pixels per load -- one 32-bit division per kernel instead of two 64-bit
+// ones per load (which used to cost more than the MFMAs).
+template <int STEP> struct PixelRow {
+    int m, ow, oh, adv_h, adv_w;
+    __device__ __forceinline__ PixelRow(int m_first, const ConvShape& s)
+        : m(m_first), ow(m_first % s.W), oh((m_first / s.W) % s.H), adv_h(STEP / s.W), adv_w(STEP % s.W) {}
+    __device__ __forceinline__ void advance(const ConvShape& s) {
+        m += STEP; ow += adv_w; oh += adv_h;
+        if (ow >= s.W) { ow -= s.W; ++oh; }
+        if (oh >= s.H) oh %= s.H;
+    }
+};
+
 // dW partial tiles: workgroup (kb, nb, chunk) computes rows [32 kb, +32) x cols [BN nb, +BN) of dW over the pixels of
 // its chunk and writes them to slab[chunk][K + 1][Cout]; row K is the chunk's partial bias gradient (column sums of dZ,
 // taken by the kb == 0 workgroups from the dZ tiles they stage anyway).  [W | b] is contiguous in the parameter buffer,
@@ -337,20 +354,14 @@ __global__ __launch_bounds__(kThreads) void k_conv_wgrad(const float* __restrict
         else decode(std::integral_constant<int, 0>{});
     }
     f32x4 xv[4], dv[BN / 8];                             // 128 x 32 floats / 256 thr = 4 float4; 128 x BN / 256 = BN/8 float4
-    // The thread's X rows are pixels m_first, m_first + 32, ... across q AND across stages (128 = 4 * 32): (oh, ow) of the next
-    // row is running state advanced by 32 pixels per load -- one 32-bit division per kernel instead of two 64-bit ones per load.
-    int row_m = (int)p0 + (tid >> 3);
-    int row_ow = row_m % s.W, row_oh = (row_m / s.W) % s.H;
-    const int adv_h = 32 / s.W, adv_w = 32 % s.W;
+    PixelRow<32> row((int)p0 + (tid >> 3), s);           // the thread's X rows: 32 pixels apart across q AND across stages (128 = 4 * 32)
     auto gload = [&](long long pb) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const bool in = row_m < (int)p1;
-            const long long mc = in ? row_m : p0;
-            const int ow = row_ow, oh = row_oh;
-            row_m += 32; row_ow += adv_w; row_oh += adv_h;
-            if (row_ow >= s.W) { row_ow -= s.W; ++row_oh; }
-            if (row_oh >= s.H) row_oh %= s.H;
+            const bool in = row.m < (int)p1;
+            const long long mc = in ? row.m : p0;
+            const int ow = row.ow, oh = row.oh;
+            row.advance(s);
             if (!SMALLC) {
                 const bool ok = in && (unsigned)(oh + dh) < (unsigned)s.H && (unsigned)(ow + dw) < (unsigned)s.W;
                 const f32x4 val = *reinterpret_cast<const f32x4*>(X + (ok ? mc * (long long)s.Cin + toff : 0));
@@ -631,10 +642,6 @@ __global__ void k_pool_bwd(const TS* __restrict__ dP, const TS* __restrict__ P, 
 __global__ void k_relu_bwd(const float* __restrict__ dY, const float* __restrict__ Y, float* __restrict__ dZ, long long n) {
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) dZ[e] = Y[e] > 0.f ? dY[e] : 0.f;
 }
-
-}  // namespace rcnx
-
-namespace rcnx {
 
 // A gradient tensor that exists only at pooled resolution.  dZ of a conv layer followed by a 2x2 max-pool is
 //     dZ[n, y, x, c] = (arg-max of its window == (y & 1, x & 1) && pooled value > 0) ? dP[n, y/2, x/2, c] : 0

@@ -11,6 +11,8 @@
 //   k_wgrad3x3_halo_f32   weight gradient: one staged halo + dZ block serves all nine taps of a 32 x 32 (ci, co) tile
 //   k_conv1_fwd_f32 / k_conv1_wgrad_f32   the first layer (9 * Cin <= 32: the whole patch is ONE k-block), organised around its
 //                         activations: the weights live in registers, the input halo of a block is a few hundred floats
+// Shared with the bf16 LDS-tiled kernels (convnet_halo_bf16.hpp): the block geometry (HaloGeom, kHaloTH / kHaloTW), the walk of a
+// persistent workgroup over its work items (ItemWalk), the staging decode (StageMap) and the epilogues (halo_epilogue).
 #pragma once
 
 #include "convnet_loss.hpp"
@@ -30,15 +32,40 @@ __device__ unsigned long long* g_rcnx_stamps = nullptr;      // [workgroup][32]:
 
 namespace rcnx {
 
-template <int TW> struct HaloGeom {
+// A pixel block and its halo.  TW_: block columns per image; MG: block rows in units of eight (the pipelined bf16 kernel's 16 x 16 blocks).
+template <int TW_, int MG = 1> struct HaloGeom {
+    static constexpr int TW = TW_;
     static constexpr int NIMG = 16 / TW;                  // images per block (TW = 16: one, TW = 8: two side by side)
-    static constexpr int TH = 8, HH = TH + 2, HWD = TW + 2, IMG_PIX = HH * HWD;
+    static constexpr int TH = 8 * MG, HH = TH + 2, HWD = TW + 2, IMG_PIX = HH * HWD;
     // LDS pixel stride between the two images of a TW = 8 block: 104 = 8 (mod 16), so that the 16 lanes of one ds_read_b128 pass
     // (8 pixels of image 0, 8 of image 1, 36-float rows) fall into 16 different 4-bank groups
     static constexpr int IS = TW == 16 ? IMG_PIX : 104;
     static constexpr int NPIX = NIMG * IMG_PIX;            // staged pixels
     static constexpr int LPIX = (NIMG - 1) * IS + IMG_PIX; // LDS pixel slots
     __device__ static int lds_pix(int pix) { return TW == 16 ? pix : pix + (pix >= IMG_PIX ? IS - IMG_PIX : 0); }
+};
+constexpr int kHaloTH = HaloGeom<16>::TH, kHaloTW = HaloGeom<16>::TW;      // the 8 x 16 block of one image, as the selectors count it
+
+// The work items of a persistent workgroup: item, item + gridDim.x, ...  An item is four digits (d0 fastest; radices r0, r1, r2; d3
+// unbounded), kept as a mixed-radix counter that is advanced by the (decomposed) grid size -- scalar adds and compares per item
+// instead of three integer divisions (which compile to dozens of VALU instructions each, even for uniform operands).  Which digit is
+// the column block, the block column, the block row and the image group is the kernel's own item_of.
+struct Item { int img0, oh0, ow0, n0; };
+struct Pos { int d0, d1, d2, d3; };
+struct ItemWalk {
+    int r0, r1, r2;
+    Pos stride;
+    __device__ inline ItemWalk(int r0_, int r1_, int r2_) : r0(r0_), r1(r1_), r2(r2_), stride(split((int)gridDim.x)) {}
+    __device__ inline Pos split(int item) const {
+        Pos p; p.d0 = item % r0; item /= r0; p.d1 = item % r1; item /= r1; p.d2 = item % r2; p.d3 = item / r2; return p;
+    }
+    __device__ inline Pos advance(Pos p) const {
+        p.d0 += stride.d0; if (p.d0 >= r0) { p.d0 -= r0; ++p.d1; }
+        p.d1 += stride.d1; if (p.d1 >= r1) { p.d1 -= r1; ++p.d2; }
+        p.d2 += stride.d2; if (p.d2 >= r2) { p.d2 -= r2; ++p.d3; }
+        p.d3 += stride.d3;
+        return p;
+    }
 };
 
 // Reading the thread index through an empty asm makes it opaque: what is computed from it is redone where it is used instead of
@@ -311,21 +338,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) v
     if (BN == 64) { bt[0] = Bs + 256 * h + r + 32 * h; bt[NT - 1] = Bs + 256 * h + r + 32 * (1 - h); }
     else bt[0] = Bs + 32 * h + r;
 
-    // Work item = (column block nb fastest, block column tw, block row th, image group g): kept as a mixed-radix counter that is
-    // advanced by the (decomposed) grid size -- scalar adds and compares per item instead of three integer divisions (which
-    // compile to dozens of VALU instructions each, even for uniform operands).
-    struct Item { int img0, oh0, ow0, n0; };
-    struct Pos { int nb, tw, th, g; };
-    auto split = [&](int item) { Pos p; p.nb = item % nblk; item /= nblk; p.tw = item % tiles_w; item /= tiles_w; p.th = item % tiles_h; p.g = item / tiles_h; return p; };
-    const Pos stride = split((int)gridDim.x);
-    auto advance = [&](Pos p) {
-        p.nb += stride.nb; if (p.nb >= nblk) { p.nb -= nblk; ++p.tw; }
-        p.tw += stride.tw; if (p.tw >= tiles_w) { p.tw -= tiles_w; ++p.th; }
-        p.th += stride.th; if (p.th >= tiles_h) { p.th -= tiles_h; ++p.g; }
-        p.g += stride.g;
-        return p;
-    };
-    auto item_of = [&](const Pos& p) { return Item{p.g * Gm::NIMG, p.th * Gm::TH, p.tw * TW, p.nb * BN}; };
+    // work item = (column block nb fastest, block column tw, block row th, image group g)
+    const ItemWalk walk(nblk, tiles_w, tiles_h);
+    // (through lambdas of the kernel's own: called directly, the walk is inlined ahead of the loaders, and the pooled-in instances with
+    // BN = 64 issue their dP and P loads in the other order, with another wait count in front of the LDS stores)
+    auto split = [&](int item) { return walk.split(item); };
+    auto advance = [&](Pos p) { return walk.advance(p); };
+    auto item_of = [&](const Pos& p) { return Item{p.d3 * Gm::NIMG, p.d2 * Gm::TH, p.d1 * TW, p.d0 * BN}; };
 
     // ---- staging: registers first (loads fly under the MFMAs), LDS after the barrier
     StageMap<NH> hm;
@@ -687,20 +706,9 @@ __global__ __launch_bounds__(kThreads) void k_conv1_fwd_f32(const float* __restr
     const float* hb = Hs + ((pxb / TW) * Gm::IS + py * Gm::HWD + pxb % TW) * CIN;
     const int n_groups = (s.N + Gm::NIMG - 1) / Gm::NIMG;
 
-    // work item = (block column tw fastest, block row th, image group g, column block nb): a mixed-radix counter advanced by the
-    // decomposed grid size, as in k_conv3x3_halo_f32
-    struct Item { int img0, oh0, ow0, n0; };
-    struct Pos { int tw, th, g, nb; };
-    auto split = [&](int item) { Pos p; p.tw = item % tiles_w; item /= tiles_w; p.th = item % tiles_h; item /= tiles_h; p.g = item % n_groups; p.nb = item / n_groups; return p; };
-    const Pos stride = split((int)gridDim.x);
-    auto advance = [&](Pos p) {
-        p.tw += stride.tw; if (p.tw >= tiles_w) { p.tw -= tiles_w; ++p.th; }
-        p.th += stride.th; if (p.th >= tiles_h) { p.th -= tiles_h; ++p.g; }
-        p.g += stride.g; if (p.g >= n_groups) { p.g -= n_groups; ++p.nb; }
-        p.nb += stride.nb;
-        return p;
-    };
-    auto item_of = [&](const Pos& p) { return Item{p.g * Gm::NIMG, p.th * Gm::TH, p.tw * TW, p.nb * 32}; };
+    // work item = (block column tw fastest, block row th, image group g, column block nb)
+    const ItemWalk walk(tiles_w, tiles_h, n_groups);
+    auto item_of = [&](const Pos& p) { return Item{p.d2 * Gm::NIMG, p.d1 * Gm::TH, p.d0 * TW, p.d3 * 32}; };
 
     Stage1Map<NL> hm;
     stage1_init<NL, CIN, TW>(hm, tid, s.H, s.W);
@@ -727,7 +735,7 @@ __global__ __launch_bounds__(kThreads) void k_conv1_fwd_f32(const float* __restr
     RCNX_STAMP(0);
     RCNX_STAMP_HW();
     int stamp_slot = 1;
-    Pos pos = split(item);
+    Pos pos = walk.split(item);
     Item cur = item_of(pos);
     halo_load(cur);
     float wreg[KS2];
@@ -750,7 +758,7 @@ __global__ __launch_bounds__(kThreads) void k_conv1_fwd_f32(const float* __restr
             __builtin_amdgcn_s_waitcnt(0x0F70);                       // vmcnt(0), expcnt and lgkmcnt untouched
         }
         const int nitem = item + gridDim.x;
-        pos = advance(pos);
+        pos = walk.advance(pos);
         const Item nxt = item_of(pos);
         if (!first) __syncthreads();                                  // the previous block's halo has been consumed
         first = false;

@@ -12,6 +12,7 @@
 #include "../../include/rcn_hipx.h"
 #include "convnet.hpp"
 #include "convnet_bf16.hpp"
+#include "convnet_halo.hpp"
 
 namespace rcnx {
 
@@ -334,7 +335,7 @@ inline WgradChoice select_wgrad(const Selection& sel, const ConvShape& s, int ks
         return c;
     }
     case WgradKernel::halo_bf16: {
-        // LDS-tiled: input halo + dZ block staged once per 8x16 pixel block, nine waves = nine filter taps (convnet_bf16.hpp)
+        // LDS-tiled: input halo + dZ block staged once per 8x16 pixel block, nine waves = nine filter taps (convnet_halo_bf16.hpp)
         if (st.x16 != st.y16) return refuse(kStoreGap);
         c.tiles_w = (s.W + kHaloTW - 1) / kHaloTW; c.tiles_h = (s.H + kHaloTH - 1) / kHaloTH;
         const long long blocks = (long long)c.tiles_w * c.tiles_h * s.N;

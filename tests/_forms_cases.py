@@ -28,6 +28,9 @@ PAIRS8 = ((24, 24, 1), (("conv", 32), ("conv", 64), ("pool",), ("conv", 64), ("p
 STORED = ((24, 32, 1), (("conv", 32), ("conv", 32), ("pool",), ("conv", 64), ("conv", 64), ("pool",), ("dense_relu", 64), ("dense", 10)), 7)
 STORED_ITEMS = ["24x32x1->32 epi 2: k_conv1_fwd_f32<1, 16>", "epi 2: k_conv3x3_halo_bf16p,", "12x16x64->64 epi 4: k_conv3x3_halo_bf16p,",
                 "12x16x64->64 epi 3 pooled-in: k_conv3x3_halo_bf16p,", "12x16x64->32 epi 0: k_conv3x3_halo_bf16p,"]
+# (also a net of OPTIONS, below)
+# 264 output tiles in 32 -> 96 and in the input gradient of 96 -> 64 (64 -> 96): no split-K, so the bf16 LDS-tiled kernels with epilogues 2 and 3
+BF16_HALO_PLAIN = ((16, 32, 3), (("conv", 32), ("conv", 96), ("conv", 64), ("pool",), ("dense", 10)), 22)
 
 LOOPS = [
     Case("fp32-16wide", WIDE16, "fp32", "lds", {},
@@ -44,6 +47,9 @@ LOOPS = [
          STORED_ITEMS + ["24x32x32->32 epi 4: k_conv3x3_halo_bf16_1cb<32>,", "24x32x32->32 epi 3 pooled-in: k_conv3x3_halo_bf16_1cb<32>,"]),
     Case("stored-pipelined", STORED, "bf16_stored", "auto", {"bf16_1cb": 0},
          STORED_ITEMS + ["24x32x32->32 epi 4: k_conv3x3_halo_bf16p,", "24x32x32->32 epi 3 pooled-in: k_conv3x3_halo_bf16p,"]),
+    # the pipelined kernel with THREE column blocks (the stored cases have one: the carry out of the column-block digit never runs there)
+    Case("bf16-pipelined-3-column-blocks", BF16_HALO_PLAIN, "bf16", "auto", {},
+         ["epi 2: k_conv1_fwd_f32<3, 16>, 88 items", "16x32x32->96 epi 2: k_conv3x3_halo_bf16_1cb<32>, 264 items", "16x32x64->96 epi 3: k_conv3x3_halo_bf16p, 264 items"]),
 ]
 
 # ---- weight-gradient chunks of several pixel blocks --------------------------------------------------------------------------------------------
@@ -86,8 +92,6 @@ DENSE_NK = ((4, 4, 3), (("conv", 32), ("pool",), ("dense_relu", 64), ("dense_rel
 # a 32-channel and a 64-channel layer on the bf16 LDS-tiled kernels with the pool fused (at this size the layers without a pool split K on
 # the implicit-GEMM kernel)
 BF16_HALO = ((16, 16, 3), (("conv", 32), ("conv", 64), ("pool",), ("conv", 64), ("conv", 32), ("pool",), ("dense", 10)), 4)
-# 264 output tiles in 32 -> 96 and in the input gradient of 96 -> 64 (64 -> 96): no split-K, so the bf16 LDS-tiled kernels with epilogues 2 and 3
-BF16_HALO_PLAIN = ((16, 32, 3), (("conv", 32), ("conv", 96), ("conv", 64), ("pool",), ("dense", 10)), 22)
 
 _REMAP = {"xcd_remap": 1, "pix_per_chunk": 128}
 OPTIONS = [

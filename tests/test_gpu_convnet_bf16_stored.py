@@ -160,6 +160,23 @@ def test_trackx_bf16_storage_16x16_pixel_blocks_compute_the_same_bits():
     a, b = res
     assert np.array_equal(a[0], b[0]) and a[1] == b[1] and np.array_equal(a[2], b[2]) and np.array_equal(a[3], b[3]) and a[4] == b[4]
     assert np.isfinite(b[3]).all() and np.isfinite(b[4])
+    # the 16-row form on a grid smaller than its item count ("halo_f32_slots"): every workgroup walks several items, with carries
+    for slots in (3, 7):
+        net = ConvNet(in_shape, layers, B)
+        net.init_params(4)
+        net.set_option("bf16_rows16", 1)
+        net.set_precision("bf16_stored")
+        unforced = net.plan_of_this_net(B)
+        net.set_option("halo_f32_slots", slots)
+        plan = net.plan_of_this_net(B)
+        assert plan == unforced and "16 x 16 pixel blocks" in plan, plan
+        xd, yd = net.to_device(x), net.to_device(y)
+        logits = net.forward(xd)
+        loss = torch.zeros(1, dtype=torch.float32, device=net.device)
+        g = net.gradients(xd, yd, None, loss)
+        net.synchronize()
+        assert np.array_equal(logits.cpu().numpy(), b[0]) and float(loss.item()) == b[1] and np.array_equal(g.cpu().numpy(), b[2]), slots
+        net.close()
 
 
 def test_trackx_bf16_storage_partial_batches_and_mode_switches():
