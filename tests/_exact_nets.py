@@ -10,14 +10,23 @@ certificate  the proof, from the oracle alone, that the forward pass is exact in
 degeneracy   how many pooling windows tie at a positive maximum, how many pre-activations are exactly 0
 walk         the oracle's loss and backward walk restated (as tests/_mix_ref.py does) for a dense target, with the two rules as flags:
              tie = "first" | "last" maximum of a window, gate = ">" | ">=" on the pre-activation.  The defaults are the oracle, bit for
-             bit (tests/test_convnet_exact_nets.py); the others are the mutants a test on such a net has to tell from it."""
+             bit (tests/test_convnet_exact_nets.py); the others are the mutants a test on such a net has to tell from it.  p = starts
+             it from given probabilities instead of its own softmax; drop = takes a row, a column, an image, a tap or a pixel out of one
+             convolution's backward kernels (DROPS)
+
+The second half makes the BACKWARD pass exact too (the comment above GAP):
+exact_backward_net    a net whose softmax is 1 / t on t tied classes and 0 elsewhere to a float32 device, at a power-of-two batch
+backward_case         that net for a spec with its f64 reference: gradient, parameters after a plain / momentum / accumulated step, average
+backward_certificate  the proof, from the reference alone, that the device owes that reference element for element in a precision mode
+coverage, mutants     dZ is alive at the borders, in every image and channel; every mutant changes the reference
+BACKWARD_CASES        the cases of part E of the GPU file, with the plan lines of their batches"""
 import functools
 from collections import namedtuple
 from types import SimpleNamespace
 
 import _forms_cases
 import numpy as np
-from _convnet_util import CONVNET_BF16_NETS, CONVNET_NETS, FUSED_HEAD, HALO_NETS, PLAIN_HEAD, POOL_PAIRS
+from _convnet_util import CIFAR, CONVNET_BF16_NETS, CONVNET_NETS, FUSED_HEAD, HALO_NETS, MNIST, PLAIN_HEAD, POOL_PAIRS
 
 from oracle import convnet_oracle as co
 
@@ -147,19 +156,52 @@ def logit_gap(logits):
     return float((z.max(axis=1) - z.min(axis=1)).max())
 
 
-def walk(x, T, ws, bs, layers, operand="f64", stored=False, tie="first", gate=">"):
+# The mutants of a convolution's backward kernels.  "dw-pixel" leaves out the last pixel of the last image AT WHICH dZ IS NOT 0: behind a
+# pool the map's corner pixel carries gradient only where it is the first maximum of its window, so on most layers an exact comparison
+# (or any other) cannot see the corner itself; the last live pixel is the nearest thing it can see.
+# "dx-tap" is the smallest of them: ONE tap of ONE input-gradient element -- tap (0, 0) at the last pixel and input channel of the last image
+# at which that tap contributes and the input is positive (where it is 0, the ReLU gate or the pool below discards the element).
+DROPS = ("dx-row", "dx-col", "dx-image", "dx-tap", "dw-pixel", "dw-image")
+
+
+def _note(cert, name, a, b):
+    """one backward GEMM a @ b for the certificate: (name, the sum of the absolute values of its terms in quanta of its two operands)"""
+    if cert is not None:
+        a, b = np.abs(a), np.abs(b)
+        cert.append((name, float((a @ b).max()) / (quantum(a) * quantum(b)) if a.size and b.size else 0.0))
+
+
+def walk(x, T, ws, bs, layers, operand="f64", stored=False, tie="first", gate=">", p=None, drop=None, trace=None, cert=None, forward=None):
     """(loss, logits, gws, gbs) for a dense target T [B, C]: tests/_mix_ref.soft_loss_and_grads, and with a one-hot T the oracle's
     loss_and_grads, restated with the pooling rule and the ReLU gate as flags.  gate ">=" lets the gradient through where the
-    pre-activation is exactly 0; tie "last" routes a window's gradient to the last of its equal maxima."""
+    pre-activation is exactly 0; tie "last" routes a window's gradient to the last of its equal maxima.
+    p [B, C]: the class probabilities the walk starts from INSTEAD of its own softmax (the loss is then taken from the log-softmax of
+    the logits, which stays finite where p is 0).  drop = (parameter layer, one of DROPS): that convolution's input gradient without the
+    contributions of dZ's last row / last column / last image / of one tap at one pixel and channel, or its weight gradient without dZ's last pixel of the last image /
+    without the last image -- the mutants an exact comparison has to tell from the walk.  trace: a list that receives (parameter
+    layer, dZ [N, H, W, Cout]) of every convolution; cert: a list that receives _note's record of every backward GEMM and bias sum;
+    forward: (*_forward's result for the same values, mode and tie, a dict) where the caller walks them more than once."""
     assert tie in ("first", "last") and gate in (">", ">="), (tie, gate)
-    logits, cache = _forward(x, ws, bs, layers, operand, stored, tie)
+    assert drop is None or drop[1] in DROPS, drop
+    logits, cache, memo = forward if forward is not None else (*_forward(x, ws, bs, layers, operand, stored, tie), None)
+
+    def opc(a, op):                                                  # _op of an array that every walk over `forward` rounds alike: rounded once
+        if memo is None or op == "f64":
+            return co._op(a, op)
+        if id(a) not in memo:
+            memo[id(a)] = (a, co._op(a, op))
+        return memo[id(a)][1]
     open_ = (lambda y, z: y > 0) if gate == ">" else (lambda y, z: z >= 0)
     B = logits.shape[0]
     z = logits - logits.max(axis=1, keepdims=True)
-    p = np.exp(z); p /= p.sum(axis=1, keepdims=True)
     T = np.asarray(T, dtype=np.float64)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        terms = np.where(T != 0, T * np.log(p), 0.0)
+    if p is None:
+        p = np.exp(z); p /= p.sum(axis=1, keepdims=True)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            terms = np.where(T != 0, T * np.log(p), 0.0)
+    else:
+        p = np.asarray(p, dtype=np.float64)
+        terms = T * (z - np.log(np.exp(z).sum(axis=1, keepdims=True)))
     loss = float((-terms.sum(axis=1)).mean())
     d = (p - T) / B
     gws, gbs = [None] * len(ws), [None] * len(bs)
@@ -176,23 +218,52 @@ def walk(x, T, ws, bs, layers, operand="f64", stored=False, tie="first", gate=">
         elif c[0] == "conv":
             _, cols, y, shp, pre = c
             N, H, W, C = shp
-            dz = (d * open_(y, pre)).reshape(N * H * W, -1)
+            dz4 = d * open_(y, pre)
+            dz = dz4.reshape(N * H * W, -1)
+            if trace is not None:
+                trace.append((pi, dz4))
+            dzx = dzw = dz
+            if drop is not None and drop[0] == pi and drop[1] != "dx-tap":   # ("dx-tap" is taken out of dcols below)
+                keep = np.ones((N, H, W, 1))
+                if drop[1] == "dw-pixel":                            # (the last pixel of the last image that carries gradient: see DROPS)
+                    live = np.flatnonzero((dz4[N - 1] != 0).any(axis=2))
+                    keep[N - 1].reshape(H * W)[live[-1:]] = 0.0
+                else:
+                    keep[{"dx-row": np.s_[:, H - 1], "dx-col": np.s_[:, :, W - 1], "dx-image": np.s_[N - 1], "dw-image": np.s_[N - 1]}[drop[1]]] = 0.0
+                if drop[1].startswith("dx"):
+                    dzx = (dz4 * keep).reshape(dz.shape)
+                else:
+                    dzw = (dz4 * keep).reshape(dz.shape)
             small = cols.shape[1] <= 32
-            gws[pi] = cols.T @ dz if small else _op(cols, operand).T @ _op(dz, operand); gbs[pi] = dz.sum(axis=0)
-            dcols = (_op(dz, operand) @ _op(ws[pi], operand).T).reshape(N, H, W, 9, C)
+            gws[pi] = cols.T @ dzw if small else opc(cols, operand).T @ _op(dzw, operand); gbs[pi] = dz.sum(axis=0)
+            dcols = (_op(dzx, operand) @ opc(ws[pi], operand).T).reshape(N, H, W, 9, C)
+            _note(cert, (pi, "wgrad"), cols.T, dz); _note(cert, (pi, "bias"), np.ones((1, dz.shape[0])), dz); _note(cert, (pi, "dgrad"), dz, ws[pi].T)
+            if drop is not None and drop == (pi, "dx-tap"):           # tap (0, 0) of dZ's pixel (h, w) lands on the input's pixel (h - 1, w - 1)
+                a = cols.reshape(N, H, W, 9, C)[N - 1, :-1, :-1, 4, :]    # the input there: at 0 the gate below discards the element, for any test
+                live = np.argwhere((dcols[N - 1, 1:, 1:, 0, :] != 0) & (a > 0))
+                if len(live):
+                    h, w, ci = live[-1]
+                    dcols[N - 1, h + 1, w + 1, 0, ci] = 0.0
             dxp = np.zeros((N, H + 2, W + 2, C))
             t = 0
             for kh in range(3):
                 for kw in range(3):
                     dxp[:, kh:kh + H, kw:kw + W, :] += dcols[:, :, :, t, :]; t += 1
+            if cert is not None:                                     # the nine taps of one input pixel are one sum on the device
+                a = np.abs(dcols); ap = np.zeros_like(dxp); t = 0
+                for kh in range(3):
+                    for kw in range(3):
+                        ap[:, kh:kh + H, kw:kw + W, :] += a[:, :, :, t, :]; t += 1
+                cert.append(((pi, "dgrad taps"), float(ap.max()) / (quantum(dz) * quantum(ws[pi]))))
             d = dxp[:, 1:-1, 1:-1, :]
             pi -= 1
         else:
             kind, f, y, shp, pre = c
             dz = d * open_(y, pre) if kind == "dense_relu" else d
             op = "f64" if (bi == 0 and head32) else operand
-            gws[pi] = _op(f, op).T @ _op(dz, op); gbs[pi] = dz.sum(axis=0)
-            d = (_op(dz, op) @ _op(ws[pi], op).T).reshape(shp)
+            gws[pi] = opc(f, op).T @ _op(dz, op); gbs[pi] = dz.sum(axis=0)
+            d = (_op(dz, op) @ opc(ws[pi], op).T).reshape(shp)
+            _note(cert, (pi, "wgrad"), f.T, dz); _note(cert, (pi, "bias"), np.ones((1, dz.shape[0])), dz); _note(cert, (pi, "dgrad"), dz, ws[pi].T)
             pi -= 1
         li = len(layers) - 1 - bi
         if stored and c[0] != "pool" and li > 0 and layers[li - 1][0] in ("conv", "pool"):
@@ -344,3 +415,341 @@ def reference(spec, precision, lr, backward=True):
         for a in (ref.grad, ref.params1, ref.params2):
             a.setflags(write=False)
     return ref
+
+
+# ---- the backward pass made exact too ---------------------------------------------------------------------------------------------------------
+# The softmax is the one inexact quantity at the top of the backward walk.  Here the first t columns of the logits layer are identical (t a
+# power of two: those classes tie at the maximum of every sample) and every other class has its bias lowered by a power of two until it
+# sits at least 120 below them, where expf underflows: exp(z - max) is 1 on the tied classes and 0 elsewhere, p = 1 / t, and with a
+# power-of-two batch d = (p - T) / B is a multiple of 1 / (t B).  Below that every operand is a small multiple of a power of two, so every
+# sum of the backward walk is exact in fp32 in any order and survives bf16 rounding: the device's gradient must EQUAL the f64 reference's.
+GAP = 120.0                                              # expf(-120) is 0 in float32 (the smallest subnormal is exp(-103.3))
+STEP_LR = 2.0 ** -3                                      # the rate of every step on these nets
+SGD = (0.5, 2.0 ** -4, True)                             # set_sgd(momentum, weight decay, nesterov) of the "sgd" cases
+EMA, ACCUM = 0.5, 2                                      # set_ema's decay, set_accumulate's k (accum_c = 0.5)
+SMOOTH, PAIR_W = 0.125, 0.25                             # the soft cases: eps / C = 2 ** -6 on 8 classes; the pair step's weight
+BACKWARD_NNZ = {"conv": 3.5, "dense_relu": 20, "dense": None}      # non-zeros per column by layer kind; the logits layer is dense
+
+
+def tied_classes(classes):
+    """t: 4, or where the net has fewer than 5 classes the largest power of two that leaves one class to push down"""
+    t = 4
+    while t >= classes:
+        t //= 2
+    assert t >= 1, classes
+    return t
+
+
+def exact_backward_net(spec, seed=0, nnz=None, batches=1):
+    """(x, y, ws, bs, flat, push, t) of spec = (in_shape, layers, B), B a power of two: x float32 in {-1, 0, 1} ([batches * B, ...]: that
+    many batches of B rows, one after the other), weights in {-1, 0, 1} with about nnz non-zeros per column (one number per parameter
+    layer; None: BACKWARD_NNZ by layer kind), biases in {0, 1, 2}, a dense +-1 logits layer whose first t columns are one column, the other
+    classes' biases lowered by `push` (a power of two) so that on every row each sits at least GAP below the tied ones, and int32 labels
+    y drawn from the lowered classes."""
+    in_shape, layers, B = spec
+    assert B >= 1 and B & (B - 1) == 0, ("the batch is no power of two", B)
+    rng = np.random.default_rng(seed)
+    shapes = co.param_shapes(in_shape, layers)
+    kinds = [l[0] for l in layers if l[0] != "pool"]
+    per_layer = list(nnz) if nnz is not None else [BACKWARD_NNZ[k] for k in kinds]
+    assert len(per_layer) == len(shapes), (per_layer, len(shapes))
+    classes = layers[-1][1]
+    t = tied_classes(classes)
+    x = rng.integers(-1, 2, (batches * B,) + tuple(in_shape)).astype(np.float32)
+    ws, bs = [], []
+    for ((k, c), nb), d in zip(shapes[:-1], per_layer):
+        ws.append(np.where(rng.random((k, c)) < d / k, rng.choice([-1.0, 1.0], (k, c)), 0.0))
+        bs.append(rng.integers(0, 3, nb).astype(np.float64))
+    (k, c), nb = shapes[-1]
+    w, b = rng.choice([-1.0, 1.0], (k, c)), rng.integers(0, 3, nb).astype(np.float64)
+    w[:, :t] = w[:, :1]; b[:t] = b[0]
+    raw = co.forward(x.astype(np.float64), ws + [w], bs + [b], layers)
+    assert (raw[:, :t] == raw[:, :1]).all(), "the tied classes do not tie"
+    excess = float((raw[:, t:].max(axis=1) - raw[:, 0]).max()) + GAP
+    push = 2.0 ** max(0, int(np.ceil(np.log2(max(excess, 1.0)))))
+    b[t:] -= push
+    ws.append(w); bs.append(b)
+    y = (t + rng.integers(0, classes - t, batches * B)).astype(np.int32)
+    flat = co.flatten(ws, bs).astype(np.float32)
+    assert np.array_equal(flat.astype(np.float64), co.flatten(ws, bs)), "parameters are not float32 values"
+    return x, y, ws, bs, flat, push, t
+
+
+def limit_softmax(B, classes, t):
+    """what the softmax of such logits is to a float32 device: 1 / t on the tied classes, 0 elsewhere"""
+    p = np.zeros((B, classes))
+    p[:, :t] = 1.0 / t
+    return p
+
+
+def is_f32(a):
+    a = np.asarray(a, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        return bool(np.array_equal(a.astype(np.float32).astype(np.float64), a))
+
+
+# (id, net, precision, tiling, options, plan lines, slots, extra: None | "sgd" | "ema" | "accum" | "soft")
+Back = namedtuple("Back", "id spec precision tiling options lines slots extra", defaults=((), None, None))
+
+
+@functools.lru_cache(maxsize=None)
+def backward_case(spec, extra=None, seed=0):
+    """The exact-backward net of `spec` with its reference, everything in f64 and from the restated walk started at the limit softmax:
+    x, y, ws, bs, flat, push, t, T (the dense target), p, logits, loss, gws, gbs, grad (flat), params1 (after one plain step at STEP_LR);
+    extra "sgd": sgd_params, sgd_velocity after one step under set_sgd(*SGD); "ema": ema after one plain step under set_ema(EMA);
+    "accum": a second batch x2, y2 with T2, grad2, acc1 (the accumulator after the first micro-step) and accum_params (after the second);
+    "soft": T is the target smoothed by SMOOTH, and yb, pair_T, pair_loss, pair_params are a pair step at weight PAIR_W under it.
+    Arrays are read-only and shared."""
+    from _sgd_ref import sgd_update
+    in_shape, layers, B = spec
+    classes = layers[-1][1]
+    x, y, ws, bs, flat, push, t = exact_backward_net(spec, seed, BACKWARD_NNZ_OF.get(layers), 2 if extra == "accum" else 1)
+    c = SimpleNamespace(spec=spec, extra=extra, x=x[:B], y=y[:B], ws=tuple(ws), bs=tuple(bs), flat=flat, push=push, t=t, p=limit_softmax(B, classes, t))
+    x64 = c.x.astype(np.float64)
+    eps = SMOOTH if extra == "soft" else 0.0
+    c.T = soft_targets(c.y, c.y, 1.0, eps, classes)
+    c.loss, c.logits, gws, gbs = walk(x64, c.T, ws, bs, layers, p=c.p)
+    c.gws, c.gbs, c.grad = tuple(gws), tuple(gbs), co.flatten(gws, gbs)
+    flat64 = co.flatten(ws, bs)
+    c.params1 = flat64 - STEP_LR * c.grad
+    if extra == "sgd":
+        c.sgd_params, c.sgd_velocity = sgd_update(flat64, c.grad, np.zeros_like(flat64), STEP_LR, *SGD)
+    elif extra == "ema":
+        c.ema = flat64 + (1.0 - EMA) * (c.params1 - flat64)
+    elif extra == "accum":
+        c.x2, c.y2 = x[B:], y[B:]
+        c.T2 = one_hot(c.y2, classes)
+        _, c.logits2, g2w, g2b = walk(c.x2.astype(np.float64), c.T2, ws, bs, layers, p=c.p)
+        c.grad2 = co.flatten(g2w, g2b)
+        c.acc1 = c.grad / ACCUM
+        c.accum_params = flat64 - STEP_LR * (c.acc1 + c.grad2 / ACCUM)
+    elif extra == "soft":
+        c.yb = (t + np.random.default_rng(seed + 7).integers(0, classes - t, B)).astype(np.int32)
+        c.pair_T = soft_targets(c.y, c.yb, PAIR_W, eps, classes)
+        c.pair_loss, _, pw, pb = walk(x64, c.pair_T, ws, bs, layers, p=c.p)
+        c.pair_grad = co.flatten(pw, pb)
+        c.pair_params = flat64 - STEP_LR * c.pair_grad
+    for a in vars(c).values():
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    for a in [*ws, *bs, *gws, *gbs]:
+        a.setflags(write=False)
+    return c
+
+
+def soft_targets(ya, yb, w, eps, C):
+    """tests/_mix_ref.soft_targets (not imported: that module pulls in the recipe restatements)"""
+    ya, yb = np.asarray(ya), np.asarray(yb)
+    return (1.0 - eps) * (w * one_hot(ya, C) + (1.0 - w) * one_hot(yb, C)) + eps / C
+
+
+def backward_certificate(c, mode):
+    """Asserts, from the reference alone, that the backward pass of backward_case `c` is exact in `mode` and that the limit softmax is
+    the right reference for a float32 device:
+      the forward certificate (so the logits are the f64 ones in the mode);
+      the f64 softmax of the logits differs from the limit by less than 2 ** -149, the smallest float32, in every entry;
+      every backward GEMM (dZ . W^T with the nine taps of a pixel as one sum, cols^T . dZ, the bias sums, the dense layers) has operands on
+      one quantum and a sum of absolute terms below 2 ** 20 quanta -- the forward certificate's rule and margin;
+      the walk in `mode` gives the f64 gradient, element for element;
+      the gradient, the parameters after one update and the case's velocity / average / accumulator are float32 values.
+    Returns the largest backward sum in quanta."""
+    in_shape, layers, B = c.spec
+    kw = MODES[mode][0]
+    ws, bs = list(c.ws), list(c.bs)
+    batches = [(c.x, c.T, c.logits, (c.gws, c.gbs))] + ([(c.x2, c.T2, c.logits2, None)] if c.extra == "accum" else [])
+    worst = 0.0
+    for x, T, logits, grads in batches:
+        x64 = x.astype(np.float64)
+        certificate(x, ws, bs, layers, mode)
+        z = logits - logits.max(axis=1, keepdims=True)
+        soft = np.exp(z) / np.exp(z).sum(axis=1, keepdims=True)
+        assert float(np.abs(soft - c.p).max()) < 2.0 ** -149, ("the f64 softmax is not the limit to a float32", float(np.abs(soft - c.p).max()))
+        assert (np.exp(z.astype(np.float32)) == (z == 0)).all(), "float32 exp is not 1 on the tied classes and 0 elsewhere"
+        cert = []
+        _, _, gws, gbs = walk(x64, T, ws, bs, layers, p=c.p, cert=cert)
+        worst = max([worst] + [s for _, s in cert])
+        assert worst < 2 ** 20, ("sum of absolute terms in quanta", max(cert, key=lambda r: r[1]))
+        if kw["operand"] != "f64":
+            _, m_logits, m_gws, m_gbs = walk(x64, T, ws, bs, layers, p=c.p, **kw)
+            assert np.array_equal(m_logits, logits), f"rounding to bf16 changes the logits ({mode})"
+            for k, (a, b) in enumerate(zip(m_gws + m_gbs, gws + gbs)):
+                assert np.array_equal(a, b), f"rounding to bf16 changes gradient tensor {k} ({mode})"
+        if grads is not None:
+            assert all(np.array_equal(a, b) for a, b in zip(gws + gbs, list(grads[0]) + list(grads[1]))), "the reference is not the walk's gradient"
+    names = ["grad", "params1"] + {"sgd": ["sgd_params", "sgd_velocity"], "ema": ["ema"], "accum": ["grad2", "acc1", "accum_params"],
+                                   "soft": ["pair_grad", "pair_params"]}.get(c.extra, [])
+    for name in names:
+        assert is_f32(getattr(c, name)), f"{name} is not an array of float32 values"
+    return worst
+
+
+COVERAGE = dict(pixels=0.45, border=0.20, channels=0.45)  # the least shares of dZ != 0 per convolution layer (conditions, not measurements)
+
+
+def coverage(c):
+    """Per convolution layer (parameter layer, shares): dZ != 0 at which share of the pixels, of the pixels of each of the map's four
+    borders over the batch (the least of the four), of the images, of the channels.  Asserts COVERAGE and every image."""
+    in_shape, layers, B = c.spec
+    trace = []
+    walk(c.x.astype(np.float64), c.T, list(c.ws), list(c.bs), layers, p=c.p, trace=trace)
+    out = []
+    for pi, dz in trace:
+        live = (dz != 0).any(axis=3)                                 # [N, H, W]: some channel of the pixel
+        borders = min(float(live[:, 0].mean()), float(live[:, -1].mean()), float(live[:, :, 0].mean()), float(live[:, :, -1].mean()))
+        shares = dict(pixels=float(live.mean()), border=borders, images=float(live.any(axis=(1, 2)).mean()), channels=float((dz != 0).any(axis=(0, 1, 2)).mean()))
+        assert shares["pixels"] >= COVERAGE["pixels"] and shares["border"] >= COVERAGE["border"] and shares["images"] == 1.0 \
+            and shares["channels"] >= COVERAGE["channels"], ("dZ is not alive enough in parameter layer", pi, shares)
+        out.append((pi, shares))
+    return out
+
+
+def mutants(c, mode="fp32"):
+    """[(flags of walk, tensors of the gradient that differ from the reference's)] of every mutant that applies to the case: the last
+    maximum (nets with a pool), the gate at zero, and per convolution layer the five DROPS (the input-gradient ones where a parameter
+    layer lies in front of the convolution).  The comparison is exact: one differing tensor is a detection."""
+    in_shape, layers, B = c.spec
+    kw = MODES[mode][0]
+    x64, ws, bs = c.x.astype(np.float64), list(c.ws), list(c.bs)
+    flags = [dict(gate=">=")] + ([dict(tie="last")] if any(l[0] == "pool" for l in layers) else [])
+    pi = 0
+    for l in layers:
+        if l[0] == "conv":
+            flags += [dict(drop=(pi, what)) for what in DROPS if pi > 0 or what.startswith("dw")]
+        pi += l[0] != "pool"
+    ref = list(c.gws) + list(c.gbs)
+    out = []
+    first = (*_forward(x64, ws, bs, layers, kw["operand"], kw["stored"], "first"), {})
+    for f in flags:
+        _, _, gws, gbs = walk(x64, c.T, ws, bs, layers, p=c.p, **kw, **f, forward=None if "tie" in f else first)
+        out.append((f, [k for k, (a, b) in enumerate(zip(gws + gbs, ref)) if not np.array_equal(a, b)]))
+    return out
+
+
+def at(spec, B):
+    return (spec[0], spec[1], B)
+
+
+# the soft cases' net: 8 classes (SMOOTH / 8 = 2 ** -6), a head the library fuses (k_head_f32) unless "head" is 0 (k_softmax_ce_soft)
+SOFT8 = ((8, 8, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense_relu", 32), ("dense", 8)), 4)
+# non-zeros per column where BACKWARD_NNZ is too many or too few for a net (keyed by its layers)
+BACKWARD_NNZ_OF = {}
+
+_F = _forms_cases
+_W4, _P8, _S8 = at(_F.WIDE16, 4), at(_F.PAIRS8, 8), at(_F.STORED, 8)
+# BF16_HALO_PLAIN: below 22 images its 3 x 3 layers have fewer than 256 output tiles and split K on the implicit-GEMM kernels; 32 is the
+# smallest power of two at which they run on the LDS-tiled bf16 kernels with epilogues 2 and 3 (what its forms cases are there for).  16 is kept
+# as a case of its own: the split-K input gradients with epilogue 3.
+_PL16, _PL32 = at(_F.BF16_HALO_PLAIN, 16), at(_F.BF16_HALO_PLAIN, 32)
+# The first layer's weight gradient aims at 1024 workgroups, 128 chunks of its 8 tiles.  WG_FIRST's 24 x 16 map has 3 pixel blocks per image:
+# at a power-of-two batch its chunks come out even (64 images: 96 chunks of 2).  A 40 x 16 map has 5: 320 blocks in 107 chunks of 3, the last of 2.
+_WG_FIRST40 = ((40, 16, 3), _F.WG_FIRST[1], 64)
+_REMAP16 = {"xcd_remap": 1, "pix_per_chunk": 128}
+_REMAP16H = dict(_REMAP16, halo_wgrad=0)
+
+
+# texts some line of the case's plan must contain (tests/_forms_cases.names): the backward kernel forms the case is there for, with the item
+# and chunk counts of ITS batch
+_W4_LINES = ["8x16x96->96 epi 0 pooled-in: k_conv3x3_halo_f32<16, 32>, 12 items", "16x32x96->32 epi 3 pooled-in: k_conv3x3_halo_f32<16, 32>, 16 items",
+             "8x16x96->96 pooled-dZ: k_wgrad3x3_halo_f32<16>, 4 chunks x 9 tiles", "16x32x32->96 pooled-dZ: k_wgrad3x3_halo_f32<16>, 16 chunks x 3 tiles",
+             "16x32x3->32: k_conv1_wgrad_f32<3, 16>, 16 chunks", "k_reduce_all"]
+_P8_LINES = ["12x12x64->64 epi 0 pooled-in: k_conv3x3_halo_f32<16, 64>, 16 items", "24x24x64->32 epi 3 pooled-in: k_conv3x3_halo_f32<8, 32>, 36 items",
+             "24x24x32->64 pooled-dZ: k_wgrad3x3_halo_f32<8>, 36 chunks x 2 tiles", "24x24x1->32: k_conv1_wgrad_f32<1, 8>, 36 chunks"]
+_W4_BF16_LINES = ["16x32x32->96 epi 4: k_conv3x3_halo_bf16_1cb<32>, 48 items", "16x32x96->32 epi 3: k_conv_fwd_bf16<3, tile, 32> split-K 6", "k_pool_bwd",
+                  "16x32x32->96: k_wgrad3x3_halo_bf16<32, 32>, 2 chunks x 3 tiles", "8x16x96->96: k_conv_wgrad_bf16<3, 32, 3>, 2 chunks"]
+_S8_LINES = ["12x16x64->64 epi 3 pooled-in: k_conv3x3_halo_bf16p, 16 items", "12x16x64->32 epi 0: k_conv3x3_halo_bf16p, 16 items",
+             "12x16x64->64 pooled-dZ: k_wgrad3x3_halo_bf16<64, 64>, 2 chunks x 1 tiles", "24x32x32->32 pooled-dZ: k_wgrad3x3_halo_bf16<32, 32>, 6 chunks x 1 tiles",
+             "24x32x1->32: k_conv1_wgrad_f32<1, 16>, 48 chunks", "bf16 output map"]
+_PL32_LINES = ["16x32x96->32 epi 3: k_conv_fwd_bf16<3, tile, 32> split-K 4", "16x32x32->96: k_wgrad3x3_halo_bf16<32, 32>, 16 chunks x 3 tiles",
+               "16x32x96->64: k_conv_wgrad_bf16<3, 32, 3>, 32 chunks", "k_pool_bwd"]
+_LOOP_LINES = {
+    "fp32-16wide": _W4_LINES, "fp32-8wide-pairs": _P8_LINES, "bf16-1cb-reload": _W4_BF16_LINES,
+    "stored-1cb": _S8_LINES + ["24x32x32->32 epi 3 pooled-in: k_conv3x3_halo_bf16_1cb<32>, 48 items"],
+    "stored-pipelined": _S8_LINES + ["24x32x32->32 epi 3 pooled-in: k_conv3x3_halo_bf16p, 48 items"],
+    "bf16-pipelined-3-column-blocks": _PL32_LINES + ["16x32x32->96 epi 2: k_conv3x3_halo_bf16_1cb<32>, 384 items", "16x32x64->96 epi 3: k_conv3x3_halo_bf16p, 384 items"],
+}
+BACKWARD_LINES = dict(_LOOP_LINES)
+BACKWARD_LINES.update({f"{k}-{s}slots": v for k, v in _LOOP_LINES.items() for s in (2, 3)})
+BACKWARD_LINES.update({
+    # 16 pixel blocks in chunks of 3 (the last of 1) and of 6 (the last of 4); 18 in chunks of 5 (the last of 3)
+    "wg16-ragged": ["16x32x32->32: k_wgrad3x3_halo_f32<16>, 6 chunks x 1 tiles", "16x32x32->96 pooled-dZ: k_wgrad3x3_halo_f32<16>, 3 chunks x 3 tiles"],
+    "wg8-ragged": ["24x24x32->32: k_wgrad3x3_halo_f32<8>, 6 chunks x 1 tiles", "24x24x32->64 pooled-dZ: k_wgrad3x3_halo_f32<8>, 4 chunks x 2 tiles"],
+    # 192 pixel blocks in 96 chunks of 2; 320 in 107 chunks of 3, the last of 2
+    "wg-first-layer": ["24x16x3->256 pooled-dZ: k_conv1_wgrad_f32<3, 16>, 96 chunks"],
+    "wg-first-layer-ragged": ["40x16x3->256 pooled-dZ: k_conv1_wgrad_f32<3, 16>, 107 chunks"],
+    # bf16 storage: 16 pixel blocks in 2 chunks of 8 (the kernel's least chunk: no power-of-two batch leaves this net a shorter one)
+    "wg-stored-2-chunks": ["16x32x32->32 pooled-dZ: k_wgrad3x3_halo_bf16<32, 32>, 2 chunks x 1 tiles", "16x32x32->32 epi 3 pooled-in: k_conv3x3_halo_bf16_1cb<32>, 16 items",
+                         "8x16x64->32 epi 0: k_conv3x3_halo_bf16p, 4 items"],
+    "bf16-not-pipelined": ["16x16x32->64 epi 4: k_conv3x3_halo_bf16", "8x8x64->32 epi 4: k_conv3x3_halo_bf16", "8x8x64->32: k_wgrad3x3_halo_bf16<64, 32>, 1 chunks x 1 tiles"],
+    "bf16-not-pipelined-plain": _PL32_LINES + ["16x32x32->96 epi 2: k_conv3x3_halo_bf16", "16x32x64->96 epi 3: k_conv3x3_halo_bf16"],
+    "bf16-plain-b16-split-k": ["16x32x64->96 epi 3: k_conv_fwd_bf16<3, tile, 32> split-K 2", "16x32x32->96: k_wgrad3x3_halo_bf16<32, 32>, 8 chunks x 3 tiles"],
+    "bf16-no-lds-tiling": ["16x16x32->64 epi 2: k_conv_fwd_bf16<3, tile,", "8x8x32->64 epi 3: k_conv_fwd_bf16<3, tile, 64> split-K 2", "k_pool_fwd", "k_pool_bwd"],
+    "bf16-implicit-gemm-wgrad": ["16x16x32->64: k_conv_wgrad_bf16<3, 32, 3>, 4 chunks", "8x8x64->32: k_conv_wgrad_bf16<3, 32, 3>, 1 chunks", "k_pool_bwd"],
+    "fp32-implicit-gemm-wgrad": ["epi 3: k_conv3x3_halo_f32<16, 32>, 16 items", "k_pool_bwd", "16x32x3->32: k_conv_wgrad<3, gather, 32>, 2 chunks",
+                                 "16x32x32->96: k_conv_wgrad<3, tile, 32>, 2 chunks", "8x16x96->96: k_conv_wgrad<3, tile, 32>, 1 chunks"],
+    "fp32-unfused-pool-bwd": ["k_pool_bwd", "8x16x96->96 epi 0: k_conv3x3_halo_f32<16, 32>, 12 items", "16x32x96->32 epi 3: k_conv3x3_halo_f32<16, 32>, 16 items",
+                              "16x32x32->96: k_wgrad3x3_halo_f32<16>, 16 chunks x 3 tiles", "8x16x96->96: k_wgrad3x3_halo_f32<16>, 4 chunks x 9 tiles"],
+    "fp32-64wide-wgrad": ["8x8x64->64: k_conv_wgrad<3, tile, 64>", "1x1x1024->64: k_conv_wgrad<1, tile, 64>"],
+    "bf16-64wide-wgrad": ["8x8x64->64: k_conv_wgrad_bf16<3, 64, 3>", "1x1x1024->64: k_conv_wgrad_bf16<1, 64, 4>"],
+    "fp32-dense-nk": ["1x1x128->64: k_conv_wgrad<1, tile, 32>", "k_softmax_ce"],
+    "bf16-dense-nk": ["1x1x128->64: k_conv_wgrad_bf16<1, 32, 4>", "1x1x64->32: k_conv_wgrad_bf16<1, 32, 2>", "1x1x32->64: k_conv_wgrad_bf16<1, 32, 1>", "k_softmax_ce"],
+    "halo-0-lds": ["6x10x64->32 epi 0 pooled-in: k_conv3x3_halo_f32<16, 32>, 4 items", "6x10x32->64 pooled-dZ: k_wgrad3x3_halo_f32<16>, 4 chunks x 2 tiles",
+                   "12x20x3->32 pooled-dZ: k_conv1_wgrad_f32<3, 8>, 12 chunks"],
+    "halo-1-lds": ["4x4x64->32 epi 0 pooled-in: k_conv3x3_halo_f32<8, 32>, 2 items", "8x8x32->32 epi 3 pooled-in: k_conv3x3_halo_f32<8, 32>, 2 items",
+                   "8x8x32->32 pooled-dZ: k_wgrad3x3_halo_f32<8>, 2 chunks x 1 tiles", "8x8x1->32: k_conv1_wgrad_f32<1, 8>, 2 chunks"],
+    "halo-5-lds": ["14x6x32->64 epi 0 pooled-in: k_conv3x3_halo_f32<8, 64>, 8 items", "14x6x64->32 pooled-dZ: k_wgrad3x3_halo_f32<8>, 8 chunks x 2 tiles",
+                   "28x12x1->64 pooled-dZ: k_conv1_wgrad_f32<1, 16>, 32 chunks"],
+    "convnet-0-auto": ["4x4x64->32 epi 0: k_conv_fwd<3, tile, 32> split-K 4", "k_pool_bwd", "k_head_f32", "8x8x3->32 pooled-dZ: k_conv1_wgrad_f32<3, 8>, 2 chunks"],
+    "convnet-1-auto": ["6x6x32->32 epi 3: k_conv_fwd<3, tile, 32> split-K 2", "k_pool_bwd", "6x6x1->32: k_conv_wgrad<3, gather, 32>, 1 chunks", "k_softmax_ce"],
+    "convnet-2-auto": ["k_head_f32, 4 workgroups", "4x8x3->64: k_conv_wgrad<3, gather, 64>, 4 chunks", "k_pool_bwd"],
+    "convnet-3-auto": ["8x8x32->32 pooled-dZ: k_wgrad3x3_halo_f32<8>, 2 chunks x 1 tiles"],
+    "convnet-4-auto": ["2x2x256->256 epi 3: k_conv_fwd<3, tile, 64> split-K 18", "4x4x128->64 epi 0: k_conv_fwd<3, tile, 64> split-K 9", "k_pool_bwd",
+                       "8x8x64->64: k_wgrad3x3_halo_f32<8>, 2 chunks x 4 tiles", "2x2x256->256: k_conv_wgrad<3, tile, 32>, 1 chunks"],
+    "mnist-b8-fp32": ["14x14x64->32 epi 0: k_conv_fwd<3, tile, 32> split-K 4", "14x14x32->64: k_wgrad3x3_halo_f32<16>, 16 chunks x 2 tiles",
+                      "28x28x1->32 pooled-dZ: k_conv1_wgrad_f32<1, 16>, 64 chunks", "1x1x3136->128: k_conv_wgrad<1, tile, 32>", "k_head_f32"],
+    "mnist-b8-bf16": ["14x14x64->32 epi 0: k_conv_fwd_bf16<3, tile, 32> split-K 4", "14x14x32->64: k_wgrad3x3_halo_bf16<32, 64>, 2 chunks x 1 tiles",
+                      "1x1x3136->128: k_conv_wgrad_bf16<1, 32, 2>", "k_head_f32"],
+    "mnist-b8-bf16_stored": ["14x14x64->32 epi 0 pooled-in: k_conv3x3_halo_bf16p, 16 items", "14x14x32->64 pooled-dZ: k_wgrad3x3_halo_bf16<32, 64>, 2 chunks x 1 tiles",
+                             "bf16 output map"],
+    "cifar-b8-fp32": ["8x8x128->64 epi 0: k_conv_fwd<3, tile, 64> split-K 9", "8x8x64->128: k_wgrad3x3_halo_f32<8>, 4 chunks x 8 tiles",
+                      "16x16x32->64: k_wgrad3x3_halo_f32<16>, 16 chunks x 2 tiles", "32x32x3->32 pooled-dZ: k_conv1_wgrad_f32<3, 16>, 64 chunks", "k_head_f32"],
+    "cifar-b8-bf16": ["8x8x128->64 epi 0: k_conv_fwd_bf16<3, tile, 64> split-K 9", "8x8x64->128: k_wgrad3x3_halo_bf16<64, 64>, 1 chunks x 2 tiles",
+                      "1x1x2048->256: k_conv_wgrad_bf16<1, 32, 4>"],
+    "cifar-b8-bf16_stored": ["8x8x128->64 epi 0 pooled-in: k_conv3x3_halo_bf16p, 8 items", "16x16x64->32 epi 0 pooled-in: k_conv3x3_halo_bf16p, 16 items",
+                             "16x16x32->64 pooled-dZ: k_wgrad3x3_halo_bf16<32, 64>, 2 chunks x 1 tiles"],
+    "soft-fused-head": ["k_head_f32"], "soft-plain-head": ["dense 1x1x32->32 epi 1: k_conv_fwd<1, tile, 32>"],
+})
+BACKWARD_LINES.update({f"xcd-remap-fp32-b{B}": [f"4x8x3->32: k_conv_wgrad<3, gather, 32>, {c} chunks", f"4x8x32->64: k_conv_wgrad<3, tile, 32>, {c} chunks"]
+                       for B, c in ((4, 1), (16, 4), (32, 8))})
+BACKWARD_LINES.update({f"xcd-remap-bf16-b{B}": [f"4x8x3->32: k_conv_wgrad<3, gather, 32>, {c} chunks", f"4x8x32->64: k_conv_wgrad_bf16<3, 32, 3>, {c} chunks"]
+                       for B, c in ((4, 1), (16, 4), (32, 8))})
+
+def _backward_cases():
+    looping = [Back("fp32-16wide", _W4, "fp32", "lds", {}), Back("fp32-8wide-pairs", _P8, "fp32", "lds", {}), Back("bf16-1cb-reload", _W4, "bf16", "auto", {}),
+               Back("stored-1cb", _S8, "bf16_stored", "auto", {"bf16_1cb": 1}), Back("stored-pipelined", _S8, "bf16_stored", "auto", {"bf16_1cb": 0}),
+               Back("bf16-pipelined-3-column-blocks", _PL32, "bf16", "auto", {})]
+    cases = list(looping)
+    cases += [c._replace(id=f"{c.id}-{s}slots", slots=s) for c in looping for s in (2, 3)]
+    cases += [
+        # weight-gradient chunks of several pixel blocks, one chunk shorter than the others
+        Back("wg16-ragged", at(_F.WG16, 4), "fp32", "lds", {"wgh_f32_target": 7}), Back("wg8-ragged", at(_F.WG8, 4), "fp32", "lds", {"wgh_f32_target": 7}),
+        Back("wg-first-layer", at(_F.WG_FIRST, 64), "fp32", "lds", {}), Back("wg-first-layer-ragged", _WG_FIRST40, "fp32", "lds", {}), Back("wg-stored-2-chunks", at(_F.WG_STORED, 4), "bf16_stored", "auto", {}),
+    ]
+    cases += [Back(f"xcd-remap-fp32-b{B}", _F._flat48(B), "fp32", "gemm", _REMAP16) for B in (4, 16, 32)]
+    cases += [Back(f"xcd-remap-bf16-b{B}", _F._flat48(B), "bf16", "auto", _REMAP16H) for B in (4, 16, 32)]
+    cases += [
+        Back("bf16-not-pipelined", _F.BF16_HALO, "bf16", "auto", {"bf16_pipe": 0}), Back("bf16-not-pipelined-plain", _PL32, "bf16", "auto", {"bf16_pipe": 0}), Back("bf16-plain-b16-split-k", _PL16, "bf16", "auto", {}),
+        Back("bf16-no-lds-tiling", _F.BF16_HALO, "bf16", "auto", {"halo": 0}), Back("bf16-implicit-gemm-wgrad", _F.BF16_HALO, "bf16", "auto", {"halo_wgrad": 0}),
+        Back("fp32-implicit-gemm-wgrad", _W4, "fp32", "lds", {"halo_wgrad": 0}), Back("fp32-unfused-pool-bwd", _W4, "fp32", "lds", {"fuse_pool_bwd": 0}),
+        Back("fp32-64wide-wgrad", _F.WIDTHS64, "fp32", "gemm", {"wgf_policy": 0}), Back("bf16-64wide-wgrad", _F.WIDTHS64, "bf16", "auto", {"wgb_policy": 0, "halo_wgrad": 0}),
+        Back("fp32-dense-nk", _F.DENSE_NK, "fp32", "auto", {"head": 0}), Back("bf16-dense-nk", _F.DENSE_NK, "bf16", "auto", {"head": 0}),
+    ]
+    cases += [Back(f"halo-{i}-lds", at(HALO_NETS[i], B), "fp32", "lds", {}) for i, B in ((0, 4), (1, 4), (5, 8))]
+    cases += [Back(f"convnet-{i}-auto", at(CONVNET_NETS[i], B), "fp32", "auto", {}) for i, B in enumerate((4, 4, 128, 4, 4))]
+    cases += [Back(f"{name}-b8-{p}", at(spec, 8), p, "auto", {}) for name, spec in (("mnist", MNIST), ("cifar", CIFAR)) for p in MODES]
+    cases += [Back("soft-fused-head", SOFT8, "fp32", "auto", {}, extra="soft"), Back("soft-plain-head", SOFT8, "fp32", "auto", {"head": 0}, extra="soft")]
+    extras = {"fp32-16wide": "sgd", "bf16-1cb-reload": "sgd", "stored-pipelined": "sgd", "mnist-b8-fp32": "ema", "cifar-b8-bf16_stored": "ema",
+              "cifar-b8-bf16": "accum", "halo-5-lds": "accum"}
+    return [c._replace(extra=extras.get(c.id, c.extra), lines=BACKWARD_LINES.get(c.id, [])) for c in cases]
+
+
+BACKWARD_CASES = _backward_cases()

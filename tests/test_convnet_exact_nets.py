@@ -21,13 +21,21 @@ Measured (printed by the tests; seed 0 everywhere):
   mutants, move of the most-moved tensor as a fraction of that tensor's scale, smallest .. largest over the backward cases:
     last maximum  fp32 0.267 .. 0.886 (18 cases)   bf16 0.384 .. 0.756 (9)   bf16 storage 0.267 .. 0.411 (3)
     gate >= 0     fp32 0.151 .. 1.03  (19)         bf16 0.247 .. 1.03  (10)  bf16 storage 0.151 .. 0.569 (3)
-  against 10 x tolerance = 2e-3 (fp32) and 5e-2 (bf16 modes)."""
+  against 10 x tolerance = 2e-3 (fp32) and 5e-2 (bf16 modes).
+  5  the exact BACKWARD cases (_exact_nets.BACKWARD_CASES: tied classes at the maximum, the others 120 or more below, power-of-two batches):
+     every (net, precision) is certified forward and backward -- every backward GEMM on one quantum with its sum of absolute terms below
+     2**20 quanta, the walk the same array in the mode as in f64, every reference array float32 values, the f64 softmax within 2**-149 of
+     the limit 1/t | 0 the walk starts from; dZ is alive in every convolution layer (COVERAGE); and every mutant -- last maximum, gate at
+     zero, per convolution layer an input gradient without dZ's last row, last column, last image or without ONE tap at one pixel and
+     channel, and a weight gradient without dZ's last live pixel of the last image or without the last image -- changes at least one tensor of the gradient, which an exact comparison
+     then tells.  The plans name the backward kernel forms each case is there for.
+  Measured: largest backward sum 18606 quanta (the 3-class net at a batch of 128), elsewhere 52 to 9339."""
 import numpy as np
 import pytest
 from _convnet_util import FUSED_HEAD, HALO_NETS, PLAIN_HEAD, POOL_PAIRS, convnet_loaded  # noqa: F401  (convnet_loaded: the fixture `convnet`)
-from _exact_nets import (EVAL_ROWS, MODES, STORED_TILING, certificate, degeneracy, eval_set, exact_case, gpu_cases, logit_gap, one_hot, plain_nets, walk,
-                         worst_move)
-from _forms_cases import DENSE_NK
+from _exact_nets import (BACKWARD_CASES, COVERAGE, EVAL_ROWS, MODES, STORED_TILING, backward_case, backward_certificate, certificate, coverage, degeneracy,
+                         eval_set, exact_case, gpu_cases, logit_gap, mutants, one_hot, plain_nets, walk, worst_move)
+from _forms_cases import DENSE_NK, env_name, names
 from _mix_ref import soft_loss_and_grads, soft_targets
 
 from oracle import convnet_oracle as co
@@ -189,3 +197,56 @@ def test_oracle_is_torch_on_an_exact_net(smoothing):
         d, scale = float(np.abs(a - b).max()), float(np.abs(b).max())
         print("tensor", k, "max |d| =", d, "scale =", scale)
         assert a.shape == b.shape and d <= 1e-12 * scale, (k, d, scale)
+
+
+# ---- 5. the exact backward cases -------------------------------------------------------------------------------------------------------------
+
+def _backward_nets():
+    """(spec, extra) -> the precisions its cases run in"""
+    nets = {}
+    for c in BACKWARD_CASES:
+        modes = nets.setdefault((c.spec, c.extra), [])
+        if c.precision not in modes:
+            modes.append(c.precision)
+    return [pytest.param(spec, extra, tuple(modes), id=next(c.id for c in BACKWARD_CASES if (c.spec, c.extra) == (spec, extra))) for (spec, extra), modes in nets.items()]
+
+
+def test_backward_cases_cover_what_the_suite_promises():
+    ids = [c.id for c in BACKWARD_CASES]
+    assert len(ids) == len(set(ids)), ids
+    assert all(c.spec[2] & (c.spec[2] - 1) == 0 for c in BACKWARD_CASES)
+    for extra, least in (("sgd", 3), ("ema", 2), ("accum", 2), ("soft", 2)):
+        assert sum(c.extra == extra for c in BACKWARD_CASES) >= least, extra
+    assert {c.precision for c in BACKWARD_CASES if c.extra == "sgd"} == set(MODES)
+
+
+@pytest.mark.parametrize("spec,extra,modes", _backward_nets())
+def test_backward_case_is_certified_alive_and_tells_every_mutant(spec, extra, modes):
+    _, layers, _ = spec
+    c = backward_case(spec, extra)
+    assert ((c.t <= c.y) & (c.y < layers[-1][1])).all()             # labels among the classes pushed down
+    for mode in modes:
+        worst = backward_certificate(c, mode)
+        print(f"{mode}: largest backward sum {worst:.0f} quanta; push {c.push}, t {c.t}, loss {c.loss:.6g}")
+    for pi, shares in coverage(c):
+        print(f"parameter layer {pi}: dZ != 0 at", {k: round(v, 3) for k, v in shares.items()}, "least:", COVERAGE)
+    if extra != "soft":
+        # the flagged walk with its OWN softmax is still the oracle, bit for bit, on these values too
+        x64, ws, bs = c.x.astype(np.float64), list(c.ws), list(c.bs)
+        loss, logits, gws, gbs = walk(x64, c.T, ws, bs, layers)
+        with np.errstate(divide="ignore"):                          # (f64's exp underflows too where the gap is above 745: both losses are inf)
+            o_loss, o_logits, o_gws, o_gbs = co.loss_and_grads(x64, c.y, ws, bs, layers)
+        assert loss == o_loss and np.array_equal(logits, o_logits) and all(np.array_equal(a, b) for a, b in zip(gws + gbs, o_gws + o_gbs))
+    for mode in modes:
+        for flags, changed in mutants(c, mode):
+            assert changed, (mode, flags, "the mutant changes no tensor of the gradient")
+
+
+@pytest.mark.parametrize("case", BACKWARD_CASES, ids=[c.id for c in BACKWARD_CASES])
+def test_backward_case_plan_names_its_kernel_forms(convnet, monkeypatch, case):
+    for name, value in case.options.items():
+        monkeypatch.setenv(env_name(name), str(value))
+    L = convnet.plan(*case.spec, precision=case.precision, tiling=case.tiling or "auto").splitlines()
+    assert case.lines, case.id
+    for text in case.lines:
+        assert any(names(l, text) for l in L), (text, L)
