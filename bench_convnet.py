@@ -8,6 +8,8 @@ network BASELINE.json's north_star asks for, on the configs SURVEY.md §8(d) fix
   cifar_bn  cifar with every conv + ReLU written Conv2d -> BatchNorm2d -> ReLU: ("conv_linear", n), ("bn_relu",) (not bf16_stored)
   cifar_res cifar_bn with a basic residual block (identity shortcut) behind each conv_linear, bn_relu pair: ... ("bn_add_relu", 4)
   cifar_res_gap  cifar_res ending as a ResNet does: its last pool and the 2048 -> 256 dense layer replaced by ("global_avgpool",), 8x8x128 -> 128 -> 10
+  cifar_resnet14  the CIFAR ResNet of 6n + 2 layers (He et al., section 4.2, option-A shortcuts), n = 2, at widths 32 / 64 / 128: stride-2
+                  convolutions and ("bn_add_relu_down", 4) shortcuts between the stages, no pool; 27 layers with parameters, B = 512
 
 fp32 activations / weights, fp32 MFMA (v_mfma_f32_32x32x2_f32; peak 157.3 TFLOP/s).  Reports achieved TFLOP/s of the whole
 training step (algorithmic 2*MACs of forward + dgrad + wgrad) and its fraction of the fp32 MFMA peak.  The reference has no
@@ -35,6 +37,13 @@ CONFIGS["cifar_res"] = (CONFIGS["cifar"][0], tuple(m for l in CONFIGS["cifar"][1
 # layer, in front of a 128 x 10 logits layer
 _res, _last_pool = CONFIGS["cifar_res"][1], max(i for i, l in enumerate(CONFIGS["cifar_res"][1]) if l[0] == "pool")
 CONFIGS["cifar_res_gap"] = (CONFIGS["cifar"][0], _res[:_last_pool] + (("global_avgpool",),) + tuple(l for l in _res[_last_pool + 1:] if l[0] != "dense_relu"), CONFIGS["cifar"][2])
+# The CIFAR ResNet of 6n + 2 layers with n = 2 (widths 32 / 64 / 128: widths are multiples of 32): conv_linear 32, bn_relu; two identity
+# blocks at 32x32x32; a down block (conv_linear_s2 64, bn_relu, conv_linear 64, bn_add_relu_down 4) and one identity block at 16x16x64; the
+# same at 8x8x128; global_avgpool, dense 10.  27 layers with parameters (the job tables take 32; ResNet-20 would need 39).
+_block = lambda c: (("conv_linear", c), ("bn_relu",), ("conv_linear", c), ("bn_add_relu", 4))
+_down = lambda c: (("conv_linear_s2", c), ("bn_relu",), ("conv_linear", c), ("bn_add_relu_down", 4))
+CONFIGS["cifar_resnet14"] = (CONFIGS["cifar"][0], (("conv_linear", 32), ("bn_relu",)) + _block(32) + _block(32) + _down(64) + _block(64) + _down(128) + _block(128) +
+                             (("global_avgpool",), ("dense", 10)), CONFIGS["cifar"][2])
 F32_MFMA_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD
 BF16_MFMA_PEAK_TFLOPS = 2516.8    # same guide: dense bf16 MFMA = 16x the fp32 MFMA rate (~2.5 PFLOP/s; never the 2:1-sparsity figure)
 HBM_PEAK_GBS = 8000.0

@@ -46,7 +46,7 @@ typedef enum {
                                     max-pool behind it (-2: name the pool), and feed no other RCN_HIPX_BN_ADD_RELU (-3).
                                     d < 2: -1.  A basic block behind any such layer: CONV3X3 C, BN_RELU, CONV3X3 C,
                                     BN_ADD_RELU 4.  Not with RCN_HIPX_BF16_STORED (-3), as RCN_HIPX_BN_RELU                 */
-    RCN_HIPX_GLOBAL_AVGPOOL = 7  /* torch.nn.AdaptiveAvgPool2d(1) + flatten(1) in front of the dense stage: y[b][c] = the
+    RCN_HIPX_GLOBAL_AVGPOOL = 7, /* torch.nn.AdaptiveAvgPool2d(1) + flatten(1) in front of the dense stage: y[b][c] = the
                                     mean over (h, w) of the map x[b][h][w][c] of the layer directly in front of it, which
                                     must be a RCN_HIPX_CONV3X3_RELU, RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or
                                     RCN_HIPX_MAXPOOL2 layer (as layer 0, or behind a dense layer or another global average
@@ -54,6 +54,25 @@ typedef enum {
                                     whatever the input's height and width, and only dense layers may follow.  In the
                                     backward pass it gates for the ReLU layer below it (a max-pool below gates itself).
                                     Not with RCN_HIPX_BF16_STORED (-3): it reads an fp32 map (csrc/convnet_gap.hpp)          */
+    RCN_HIPX_CONV3X3_S2 = 8,     /* torch.nn.Conv2d(Cin, out, 3, stride=2, padding=1): + bias, NO activation, output
+                                    (H/2) x (W/2); output pixel (oh, ow) reads input rows 2 oh - 1 + kh and columns
+                                    2 ow - 1 + kw, out-of-range taps are zero.  [W | b] laid out as RCN_HIPX_CONV3X3's,
+                                    K = 9 Cin.  Like RCN_HIPX_CONV3X3 it must be followed directly by a batch-normalisation
+                                    layer of any kind (-2).  Odd H or W: -3; Cin % 32 != 0: -3 (no strided first layer);
+                                    out not a positive multiple of 32: -3; behind the dense stage or a global average
+                                    pool: -2.  Implicit-GEMM kernels only, in both operand precisions; its input gradient
+                                    is one launch over the four parity classes of input pixels (csrc/convnet.hpp).
+                                    Not with RCN_HIPX_BF16_STORED (-3), through the batch-normalisation layer behind it      */
+    RCN_HIPX_BN_ADD_RELU_DOWN = 9 /* the end of a residual block that halves the map: y = relu(BatchNorm2d(z) + s') over the
+                                    map z of the RCN_HIPX_CONV3X3 or RCN_HIPX_CONV3X3_S2 layer directly in front of it, s' the
+                                    parameter-free "option A" shortcut of the output s (Cs channels) of layer i - out:
+                                    s'[b][h][w][c] = s[b][2h][2w][c - lo] for lo <= c < lo + Cs, else 0, lo = (C - Cs) / 2 --
+                                    in torch (NCHW) F.pad(s[:, :, ::2, ::2], (0, 0, 0, 0, lo, C - Cs - lo)).  In everything
+                                    else it is RCN_HIPX_BN_ADD_RELU (parameters, running statistics, rcn_hipx_*bn* calls,
+                                    the rules for out and for the source), except the source's shape: its height and width
+                                    must be exactly twice this layer's (-2), Cs <= C (-2) and (C - Cs) % 8 == 0 (-3).
+                                    Cs == C is a plain subsample.  A down block behind a layer of C channels: CONV3X3_S2 2C,
+                                    BN_RELU, CONV3X3 2C, BN_ADD_RELU_DOWN 4                                                  */
 } rcn_hipx_layer_kind;
 
 typedef struct rcn_hipx_layer { int32_t kind; int32_t out; } rcn_hipx_layer;

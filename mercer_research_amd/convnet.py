@@ -15,7 +15,8 @@ from . import _lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBX_PATH = os.path.join(HERE, "librcn_hipx.so")
-KIND = {"conv": 0, "pool": 1, "dense_relu": 2, "dense": 3, "conv_linear": 4, "bn_relu": 5, "bn_add_relu": 6, "global_avgpool": 7}
+KIND = {"conv": 0, "pool": 1, "dense_relu": 2, "dense": 3, "conv_linear": 4, "bn_relu": 5, "bn_add_relu": 6, "global_avgpool": 7,
+        "conv_linear_s2": 8, "bn_add_relu_down": 9}
 
 
 class XLayer(C.Structure):
@@ -82,7 +83,8 @@ class StateDesc(C.Structure):
                 ("dropout_seed", C.c_uint64)]
 
     def shape_and_layers(self):
-        """(in_shape, layers) as ConvNet takes them; ("bn_add_relu", d) comes back with its distance: the descriptor stores it as `out`"""
+        """(in_shape, layers) as ConvNet takes them; ("bn_add_relu", d) and ("bn_add_relu_down", d) come back with their distance and
+        ("conv_linear_s2", Cout) with its width: the descriptor stores either as `out`"""
         names = {v: k for k, v in KIND.items()}
         layers = [(names[self.layers[i].kind],) if self.layers[i].kind in (KIND["pool"], KIND["bn_relu"], KIND["global_avgpool"]) else (names[self.layers[i].kind], int(self.layers[i].out))
                   for i in range(self.n_layers)]
@@ -508,7 +510,12 @@ class ConvNet:
     relu(BatchNorm2d(z) + s) with s the output of the layer d places in front of it (d >= 2): torchvision's BasicBlock with an identity
     shortcut is ("conv_linear", C), ("bn_relu",), ("conv_linear", C), ("bn_add_relu", 4) behind the layer that made the block's input.
     ("global_avgpool",) is AdaptiveAvgPool2d(1) -> flatten(1) behind the last map (a "conv", "bn_relu", "bn_add_relu" or "pool" layer): the
-    dense layer behind it has K = C inputs at any input resolution, and only dense layers may follow."""
+    dense layer behind it has K = C inputs at any input resolution, and only dense layers may follow.
+    ("conv_linear_s2", Cout) is Conv2d(Cin, Cout, 3, stride=2, padding=1) on an even map of Cin % 32 == 0 channels, followed by a bn layer
+    like "conv_linear".  ("bn_add_relu_down", d) is relu(BatchNorm2d(z) + s') with s' the parameter-free option-A shortcut of the output s
+    (Cs <= C channels, twice this layer's height and width) of the layer d places in front:
+    F.pad(s[:, :, ::2, ::2], (0, 0, 0, 0, lo, C - Cs - lo)), lo = (C - Cs) / 2.  The down block of the CIFAR ResNet behind a layer of C
+    channels is ("conv_linear_s2", 2C), ("bn_relu",), ("conv_linear", 2C), ("bn_add_relu_down", 4)."""
 
     def __init__(self, in_shape: Tuple[int, int, int], layers: Sequence[tuple], max_batch: int, device: int = 0):
         import torch
@@ -1221,8 +1228,21 @@ class ConvNet:
         total, first = 0.0, True
         es_in = 4                                            # bytes per element of the current layer's input tensor
         es_stage = 2 if stored16 else 4
+        maps = []                                            # every layer's output (H, W, C): a down shortcut reads its source's
         for l in self.layers:
-            if l[0] == "conv":
+            maps.append(None)
+            if l[0] == "conv_linear_s2":
+                # as conv_linear with the output map a quarter of the input's
+                i, o = H * W * Cc * es_in, (H // 2) * (W // 2) * l[1] * 4
+                total += B * ((i + o) + (0 if first else (i + o)) + (i + o)) + 3 * (9 * Cc * l[1] + l[1]) * 4
+                H, W, Cc, first, es_in = H // 2, W // 2, l[1], False, 4
+            elif l[0] == "bn_add_relu_down":
+                # as bn_relu, and the shortcut: a quarter of the source's map (its Cs channels at every second pixel) read by the apply pass;
+                # the add pass of the backward reads that quarter of the source's gradient and this layer's window and writes the quarter
+                m = H * W * Cc * 4
+                sm = H * W * maps[len(maps) - 1 - l[1]][2] * 4
+                total += B * (3 * m + 4 * m + sm + 3 * sm)
+            elif l[0] == "conv":
                 i, o = H * W * Cc * es_in, H * W * l[1] * es_stage
                 total += B * ((i + o) + (0 if first else (i + o)) + (i + o)) + 3 * (9 * Cc * l[1] + l[1]) * 4
                 Cc, first, es_in = l[1], False, es_stage
@@ -1254,6 +1274,7 @@ class ConvNet:
                 i, o = H * W * Cc * es_in, l[1] * 4
                 total += B * ((i + o) + (0 if first else (i + o)) + (i + o)) + 3 * (H * W * Cc * l[1] + l[1]) * 4
                 H, W, Cc, first, es_in = 1, 1, l[1], False, 4
+            maps[-1] = (H, W, Cc)
         return total
 
     def step_flops(self, B: int) -> float:

@@ -57,6 +57,42 @@ __device__ inline int mfma32_row(int lane, int r) { return (r & 3) + 8 * (r >> 2
 struct ConvShape {
     int N, H, W, Cin, Cout;     // stride 1, pad = KS/2, output H x W
 };
+// The 3x3 convolution of stride 2, pad 1 (RCN_HIPX_CONV3X3_S2): input H x W (both even), output H/2 x W/2; output pixel (oh, ow) reads input
+// rows 2 oh - 1 + kh and columns 2 ow - 1 + kw.  Shape types of their own, not a field of ConvShape: the stride-1 instantiations keep
+// their argument and their code.  ConvShapeS2: the forward pass and the weight gradient (rows = output pixels).  ConvShapeS2T: the input
+// gradient by parity class (k_conv_fwd) -- H x W is the map the gradient is written FOR (the layer's input), Cin the channels of dZ
+// (the layer's Cout, the contraction) and Cout the layer's Cin.
+struct ConvShapeS2 { int N, H, W, Cin, Cout; };
+struct ConvShapeS2T { int N, H, W, Cin, Cout; };
+template <class SH> constexpr bool kIsS2 = std::is_same<SH, ConvShapeS2>::value;
+template <class SH> constexpr bool kIsS2T = std::is_same<SH, ConvShapeS2T>::value;
+// rows of the implicit GEMM: output pixels; ConvShapeS2T: the input pixels of ONE parity class
+__host__ __device__ inline long long gemm_rows(const ConvShape& s) { return (long long)s.N * s.H * s.W; }
+__host__ __device__ inline long long gemm_rows(const ConvShapeS2& s) { return (long long)s.N * (s.H / 2) * (s.W / 2); }
+__host__ __device__ inline long long gemm_rows(const ConvShapeS2T& s) { return (long long)s.N * (s.H / 2) * (s.W / 2); }
+
+// Parity classes of the strided input gradient.  Input pixel (ih, iw) = (2 i + ph, 2 j + pw) of class cls = 2 ph + pw receives only the
+// taps with ih + 1 - kh and iw + 1 - kw even: on the tap-flipped weights Wt (tap kh' = 2 - kh) an even coordinate takes kh' = 1 from
+// dZ row i, an odd one kh' = 0 from row i and kh' = 2 from row i + 1 (zero where i + 1 == H/2).  1, 2, 2 and 4 live taps: nine per four
+// input pixels, the forward pass's MACs.  Live tap lt of a class -> its tap in Wt and the offset (dh, dw) in {0, 1}^2 of its dZ pixel.
+struct ParityTap { int tap, dh, dw; };
+__host__ __device__ inline int parity_taps(int cls) { return (1 + (cls >> 1)) * (1 + (cls & 1)); }
+__host__ __device__ inline ParityTap parity_tap(int cls, int lt) {
+    const int ph = cls >> 1, pw = cls & 1;
+    const int th = ph ? 2 * (lt / (1 + pw)) : 1, tw = pw ? 2 * (lt % (1 + pw)) : 1;
+    return ParityTap{th * 3 + tw, th >> 1, tw >> 1};
+}
+// block order of the one launch: the heaviest class first (class 3, four taps, then 2, 1, 0)
+__host__ __device__ inline int parity_class_of_block(unsigned bx, unsigned tiles_per_class) { return 3 - (int)(bx / tiles_per_class); }
+// the row (pixel index of the H x W map) that row m of class cls writes
+__host__ __device__ inline long long parity_out_row(const ConvShapeS2T& s, int cls, long long m) {
+    const int oW = s.W / 2, oH = s.H / 2;
+    const int j = (int)(m % oW);
+    const long long t2 = m / oW;
+    const int i = (int)(t2 % oH);
+    const long long n = t2 / oH;
+    return (n * s.H + 2 * i + (cls >> 1)) * s.W + 2 * j + (cls & 1);
+}
 
 // Per-thread description of the 4 rows of the 128 x 32 A tile it stages: decoded ONCE per workgroup (the pixel of a row does
 // not change along K), so that per K-tile only the tap offset -- uniform over the workgroup -- is applied.
@@ -80,23 +116,52 @@ __device__ inline ARows decode_rows(const ConvShape& s, long long M, long long m
     }
     return r;
 }
+// stride 2: row m is OUTPUT pixel (n, oh, ow); base, oh and ow describe the input pixel (2 oh, 2 ow) its taps are centred on, so the
+// loader's border test and tap offset are the stride-1 ones on the input map
+__device__ inline ARows decode_rows(const ConvShapeS2& s, long long M, long long m0, int tid) {
+    ARows r;
+    const int oW = s.W / 2, oH = s.H / 2;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const long long m = m0 + (tid >> 3) + 32 * q;
+        if (m < M) {
+            const int ow = (int)(m % oW);
+            const long long t2 = m / oW;
+            const int oh = (int)(t2 % oH);
+            const long long n = t2 / oH;
+            r.base[q] = ((n * s.H + 2 * oh) * s.W + 2 * ow) * (long long)s.Cin;
+            r.oh[q] = 2 * oh; r.ow[q] = 2 * ow;
+        } else { r.base[q] = -1; r.oh[q] = 0; r.ow[q] = 0; }
+    }
+    return r;
+}
+// parity classes: row m is pixel (n, i, j) of the H/2 x W/2 map of dZ -- the stride-1 decode on that map
+__device__ inline ARows decode_rows(const ConvShapeS2T& s, long long M, long long m0, int tid) {
+    return decode_rows(ConvShape{s.N, s.H / 2, s.W / 2, s.Cin, s.Cout}, M, m0, tid);
+}
+
+// the four rows' 16-byte pieces of ONE tap: channels ci .. ci + 3 of the pixel (dh, dw) away on an H x W map of Cin channels
+template <typename TX>
+__device__ inline void load_a_tap(const TX* __restrict__ X, int H, int W, int Cin, const ARows& rows, int dh, int dw, int ci, f32x4 (&v)[4]) {
+    const long long toff = ((long long)dh * W + dw) * Cin + ci;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const bool ok = rows.base[q] >= 0 && (unsigned)(rows.oh[q] + dh) < (unsigned)H && (unsigned)(rows.ow[q] + dw) < (unsigned)W;
+        const f32x4 val = widen4(*reinterpret_cast<const chunk4_t<TX>*>(X + (ok ? rows.base[q] + toff : 0)));     // unconditional load, masked by value
+        v[q] = ok ? val : f32x4{0, 0, 0, 0};
+    }
+}
 
 // A-tile element source: row m of the implicit im2col matrix, K-tile kt (32 consecutive k)
-template <int KS, bool SMALLC, typename TX = float>
-__device__ inline void load_a_regs(const TX* __restrict__ X, const ConvShape& s, const ARows& rows, int kt, int tid, f32x4 (&v)[4]) {
+template <int KS, bool SMALLC, typename TX = float, class SH = ConvShape>
+__device__ inline void load_a_regs(const TX* __restrict__ X, const SH& s, const ARows& rows, int kt, int tid, f32x4 (&v)[4]) {
     // thread t loads rows (t>>3) + 32 q, q = 0..3, columns 4*(t&7) .. +3 of the 128 x 32 tile
     const int c4 = (tid & 7) * 4;
     if (!SMALLC) {
         const int k0 = kt * kBK;                                    // Cin % 32 == 0: the whole K-tile lies in one tap
         const int tap = k0 / s.Cin, ci = k0 - tap * s.Cin + c4;
         const int dh = tap / KS - KS / 2, dw = tap % KS - KS / 2;
-        const long long toff = ((long long)dh * s.W + dw) * s.Cin + ci;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const bool ok = rows.base[q] >= 0 && (unsigned)(rows.oh[q] + dh) < (unsigned)s.H && (unsigned)(rows.ow[q] + dw) < (unsigned)s.W;
-            const f32x4 val = widen4(*reinterpret_cast<const chunk4_t<TX>*>(X + (ok ? rows.base[q] + toff : 0)));     // unconditional load, masked by value
-            v[q] = ok ? val : f32x4{0, 0, 0, 0};
-        }
+        load_a_tap(X, s.H, s.W, s.Cin, rows, dh, dw, ci, v);
     } else {
         // whole K (= KS*KS*Cin <= 32) in one tile.  The tap of column k does not depend on the row: decoded ONCE per thread (four
         // columns), with the division by a compile-time 3 for RGB input -- as a per-element k / s.Cin this loader issued ~100 VALU
@@ -135,18 +200,32 @@ __device__ inline void load_a_regs(const TX* __restrict__ X, const ConvShape& s,
 
 // EPI: 0 = raw, 1 = + bias, 2 = + bias, ReLU, 3 = raw gated by (G > 0) where `bias` points at a tensor G shaped like Y (the
 // input-gradient pass writes dZ of the layer below directly: G = that layer's post-ReLU output)
-template <int KS, bool SMALLC, int BN, int EPI>
+// 128 ints of LDS in the parity-class instantiations only
+template <bool ON> __device__ __forceinline__ int* parity_row_table() {
+    if constexpr (ON) { __shared__ int table[kBM]; return table; }
+    else return nullptr;
+}
+
+// SH, the geometry: ConvShape, stride 1 (every instantiation there was: same arguments, same code); ConvShapeS2, the strided forward pass
+// (only the row decode differs); ConvShapeS2T, the strided layer's input gradient by parity class -- X is dZ, Wk the tap-flipped
+// transposed weights, grid.x = 4 x the tiles of a class with the heaviest class first, a workgroup belongs to ONE class (uniform), its 128
+// rows are input pixels of that class, its K loop runs over the class's live taps x Cin / 32 K-tiles, and every element of Y is written
+// exactly once by one thread (no atomics, one summation order).
+template <int KS, bool SMALLC, int BN, int EPI, class SH = ConvShape>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) void k_conv_fwd(const float* __restrict__ X, const float* __restrict__ Wk,
-                                                       const float* __restrict__ bias, float* __restrict__ Y, ConvShape s) {
+                                                       const float* __restrict__ bias, float* __restrict__ Y, SH s) {
     constexpr int kLdB = BN + 1, NT = BN / 32;
     __shared__ float As[2][kBM * kLdA];
     __shared__ float Bs[2][kBK * kLdB];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const long long M = (long long)s.N * s.H * s.W;
-    const long long m0 = (long long)blockIdx.x * kBM;
+    const long long M = gemm_rows(s);
+    unsigned bx = blockIdx.x;
+    int cls = 0;                                         // parity class (ConvShapeS2T): uniform over the workgroup
+    if constexpr (kIsS2T<SH>) { const unsigned tpc = gridDim.x / 4; cls = parity_class_of_block(bx, tpc); bx %= tpc; }
+    const long long m0 = (long long)bx * kBM;
     const int n0 = blockIdx.y * BN;
     const int K = KS * KS * s.Cin;
-    const int nkt_all = SMALLC ? 1 : K / kBK;
+    const int nkt_all = kIsS2T<SH> ? parity_taps(cls) * (s.Cin / kBK) : SMALLC ? 1 : K / kBK;
     // split-K: workgroup z of gridDim.z contracts K-tiles [kt0, kt1) and writes a raw partial tile to Y + z * M * Cout
     const int kt0 = (int)((long long)nkt_all * blockIdx.z / gridDim.z), kt1 = (int)((long long)nkt_all * (blockIdx.z + 1) / gridDim.z);
     const int nkt = kt1 - kt0;
@@ -163,12 +242,26 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) v
     // (PMC, CIFAR shape, one stage: SQ_WAIT_INST_ANY 48 % of the wave cycles, SQ_WAIT_INST_LDS 2 %: the waves sat on vmcnt.)
     f32x4 av[2][4];
     f32x4 bv[2][BN / 32];                                // B tile: 32 x BN floats = 8*BN float4 / 256 threads
+    // K-tile kt: its first row of Wk, and (parity classes) its tap's dZ pixel offset and first channel
+    struct Tile { int k0, dh, dw, c0; };
+    auto tile_of = [&](int kt) {
+        if constexpr (kIsS2T<SH>) {
+            const int cpt = s.Cin / kBK, lt = kt / cpt, c0 = (kt - lt * cpt) * kBK;
+            const ParityTap pt = parity_tap(cls, lt);
+            return Tile{pt.tap * s.Cin + c0, pt.dh, pt.dw, c0};
+        } else return Tile{kt * kBK, 0, 0, 0};
+    };
+    auto load_a = [&](const ARows& rows, int kt, f32x4 (&a)[4]) {
+        if constexpr (kIsS2T<SH>) { const Tile t = tile_of(kt); load_a_tap(X, s.H / 2, s.W / 2, s.Cin, rows, t.dh, t.dw, t.c0 + (tid & 7) * 4, a); }
+        else load_a_regs<KS, SMALLC>(X, s, rows, kt, tid, a);
+    };
     auto load_b = [&](int kt, f32x4 (&b)[BN / 32]) {
+        const int kfirst = tile_of(kt).k0;
 #pragma unroll
         for (int q = 0; q < BN / 32; ++q) {
             const int e = tid + kThreads * q;            // float4 index in the 32 x (BN/4) tile
             const int kr = e / (BN / 4), c4 = (e - kr * (BN / 4)) * 4;
-            const int k = kt * kBK + kr;
+            const int k = kfirst + kr;
             b[q] = (k < K) ? *reinterpret_cast<const f32x4*>(Wk + (long long)k * s.Cout + n0 + c4) : f32x4{0, 0, 0, 0};
         }
     };
@@ -198,11 +291,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) v
         }
     };
 
+    // parity classes: where each of the workgroup's 128 rows is written (decoded once, read by the epilogue behind the barriers below)
+    int* const orow_s = parity_row_table<kIsS2T<SH>>();
+    if constexpr (kIsS2T<SH>) { if (tid < kBM && m0 + tid < M) orow_s[tid] = (int)parity_out_row(s, cls, m0 + tid); }
     const ARows rows = decode_rows(s, M, m0, tid);
-    load_a_regs<KS, SMALLC>(X, s, rows, kt0, tid, av[0]);
+    load_a(rows, kt0, av[0]);
     load_b(kt0, bv[0]);
     if (nkt > 1) {
-        load_a_regs<KS, SMALLC>(X, s, rows, kt0 + 1, tid, av[1]);
+        load_a(rows, kt0 + 1, av[1]);
         load_b(kt0 + 1, bv[1]);
     }
     store_tiles(0, av[0], bv[0]);
@@ -210,7 +306,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) v
     // tile kt sits in LDS buffer kt & 1 and came through register stage kt & 1: that stage is free for tile kt + 2
     for (int kt = 0; kt < nkt; kt += 2) {
         if (kt + 2 < nkt) {
-            load_a_regs<KS, SMALLC>(X, s, rows, kt0 + kt + 2, tid, av[0]);
+            load_a(rows, kt0 + kt + 2, av[0]);
             load_b(kt0 + kt + 2, bv[0]);
         }
         contract(0);
@@ -218,7 +314,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) v
             store_tiles(1, av[1], bv[1]);
             __syncthreads();
             if (kt + 3 < nkt) {
-                load_a_regs<KS, SMALLC>(X, s, rows, kt0 + kt + 3, tid, av[1]);
+                load_a(rows, kt0 + kt + 3, av[1]);
                 load_b(kt0 + kt + 3, bv[1]);
             }
             contract(1);
@@ -235,8 +331,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) v
         const float bb = (EPI == 1 || EPI == 2) ? bias[co] : 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const long long m = m0 + wave * 32 + mfma32_row(lane, r);
+            long long m = m0 + wave * 32 + mfma32_row(lane, r);
             if (m < M) {
+                if constexpr (kIsS2T<SH>) m = orow_s[wave * 32 + mfma32_row(lane, r)];      // the input pixel of this class's row
                 float v = acc[t][r] + bb;
                 if (EPI == 2) v = v > 0.f ? v : 0.f;
                 if (EPI == 3) v = bias[m * s.Cout + co] > 0.f ? v : 0.f;      // dgrad: ReLU mask of the layer below, `bias` = its output
@@ -293,13 +390,19 @@ template <int STEP> struct PixelRow {
     }
 };
 
+// the map the rows of a weight gradient walk
+__device__ inline const ConvShape& out_map(const ConvShape& s) { return s; }
+__device__ inline ConvShape out_map(const ConvShapeS2& s) { return ConvShape{s.N, s.H / 2, s.W / 2, s.Cin, s.Cout}; }
+
 // dW partial tiles: workgroup (kb, nb, chunk) computes rows [32 kb, +32) x cols [BN nb, +BN) of dW over the pixels of
 // its chunk and writes them to slab[chunk][K + 1][Cout]; row K is the chunk's partial bias gradient (column sums of dZ,
 // taken by the kb == 0 workgroups from the dZ tiles they stage anyway).  [W | b] is contiguous in the parameter buffer,
 // so ONE reduction job over (K + 1) * Cout elements finishes both.
-template <int KS, bool SMALLC, int BN>
+// SH = ConvShapeS2 (RCN_HIPX_CONV3X3_S2): the contraction runs over OUTPUT pixels, PixelRow walks the output map and X is gathered at the
+// strided position; chunks, slab, bias row and reduction are the same.
+template <int KS, bool SMALLC, int BN, class SH = ConvShape>
 __global__ __launch_bounds__(kThreads) void k_conv_wgrad(const float* __restrict__ X, const float* __restrict__ dZ,
-                                                         float* __restrict__ slab, ConvShape s, int pix_per_chunk, WgradGrid gd) {
+                                                         float* __restrict__ slab, SH s, int pix_per_chunk, WgradGrid gd) {
     // Both MFMA operands are read along a staged row (A[m = k][kk = pixel] = Xs[pixel][k], B[kk = pixel][n] = Ds[pixel][n]:
     // a half-wave reads 32 consecutive floats of one row), so the LDS images need no padding and are filled with 16-byte
     // stores.  128 pixels per iteration in ONE LDS buffer (48 KB at BN = 64 -> three workgroups per CU); the next 128 are
@@ -309,7 +412,7 @@ __global__ __launch_bounds__(kThreads) void k_conv_wgrad(const float* __restrict
     float* Xs = smem;                                    // [pixel][k]
     float* Ds = smem + kPT * 32;                         // [pixel][co]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const long long M = (long long)s.N * s.H * s.W;
+    const long long M = gemm_rows(s);
     const int K = KS * KS * s.Cin;
     int kb, nby, chunk;
     if (!gd.decode((int)blockIdx.x, kb, nby, chunk)) return;             // padding of the XCD-aware grid (uniform per workgroup)
@@ -354,14 +457,16 @@ __global__ __launch_bounds__(kThreads) void k_conv_wgrad(const float* __restrict
         else decode(std::integral_constant<int, 0>{});
     }
     f32x4 xv[4], dv[BN / 8];                             // 128 x 32 floats / 256 thr = 4 float4; 128 x BN / 256 = BN/8 float4
-    PixelRow<32> row((int)p0 + (tid >> 3), s);           // the thread's X rows: 32 pixels apart across q AND across stages (128 = 4 * 32)
+    const auto& so = out_map(s);                          // the map PixelRow walks: the output's
+    PixelRow<32> row((int)p0 + (tid >> 3), so);          // the thread's X rows: 32 pixels apart across q AND across stages (128 = 4 * 32)
     auto gload = [&](long long pb) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const bool in = row.m < (int)p1;
-            const long long mc = in ? row.m : p0;
-            const int ow = row.ow, oh = row.oh;
-            row.advance(s);
+            long long mc = in ? row.m : p0;
+            int ow = row.ow, oh = row.oh;
+            row.advance(so);
+            if constexpr (kIsS2<SH>) { mc = 4 * mc - 2 * ow; oh *= 2; ow *= 2; }      // input pixel (n, 2 oh, 2 ow): (n H + 2 oh) W + 2 ow = 4 m - 2 ow
             if (!SMALLC) {
                 const bool ok = in && (unsigned)(oh + dh) < (unsigned)s.H && (unsigned)(ow + dw) < (unsigned)s.W;
                 const f32x4 val = *reinterpret_cast<const f32x4*>(X + (ok ? mc * (long long)s.Cin + toff : 0));

@@ -65,20 +65,24 @@ __global__ __launch_bounds__(256) void k_prep_all_bf16(PrepJobs J) {
 
 // Same tiling, split-K and epilogues as k_conv_fwd; WB = weights as bf16 [Cout][Kp], Kp = K rounded up to 32
 // TX / TY: storage types of X and of Y (and of EPI 3's gate tensor, which arrives through `bias`); a split-K launch writes float partials
-template <int KS, bool SMALLC, int BN, int EPI, typename TX = float, typename TY = float>
+// SH: k_conv_fwd's three geometries (ConvShapeS2T: WB is the bf16 copy of the tap-flipped transposed weights)
+template <int KS, bool SMALLC, int BN, int EPI, typename TX = float, typename TY = float, class SH = ConvShape>
 __global__ __launch_bounds__(kThreads) void k_conv_fwd_bf16(const TX* __restrict__ X, const __bf16* __restrict__ WB,
-                                                            const float* __restrict__ bias, TY* __restrict__ Y, ConvShape s) {
+                                                            const float* __restrict__ bias, TY* __restrict__ Y, SH s) {
     constexpr int NT = BN / 32;
     constexpr int BCH = (BN * 4 + kThreads - 1) / kThreads;          // 16-byte chunks of the B tile per thread
     __shared__ __attribute__((aligned(16))) __bf16 As[2][kBM * kLdH];
     __shared__ __attribute__((aligned(16))) __bf16 Bs[2][BN * kLdH];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const long long M = (long long)s.N * s.H * s.W;
-    const long long m0 = (long long)blockIdx.x * kBM;
+    const long long M = gemm_rows(s);
+    unsigned bx = blockIdx.x;
+    int cls = 0;                                         // parity class (ConvShapeS2T): uniform over the workgroup
+    if constexpr (kIsS2T<SH>) { const unsigned tpc = gridDim.x / 4; cls = parity_class_of_block(bx, tpc); bx %= tpc; }
+    const long long m0 = (long long)bx * kBM;
     const int n0 = blockIdx.y * BN;
     const int K = KS * KS * s.Cin;
     const int Kp = (K + kBK - 1) / kBK * kBK;
-    const int nkt_all = Kp / kBK;
+    const int nkt_all = kIsS2T<SH> ? parity_taps(cls) * (s.Cin / kBK) : Kp / kBK;
     const int kt0 = (int)((long long)nkt_all * blockIdx.z / gridDim.z), kt1 = (int)((long long)nkt_all * (blockIdx.z + 1) / gridDim.z);
     const int nkt = kt1 - kt0;
     Y += (long long)blockIdx.z * M * s.Cout;
@@ -91,13 +95,27 @@ __global__ __launch_bounds__(kThreads) void k_conv_fwd_bf16(const TX* __restrict
 
     f32x4 av[4];
     bf16x8 bv[BCH];
+    // K-tile kt: its first column of WB, and (parity classes) its tap's dZ pixel offset and first channel
+    struct Tile { int k0, dh, dw, c0; };
+    auto tile_of = [&](int kt) {
+        if constexpr (kIsS2T<SH>) {
+            const int cpt = s.Cin / kBK, lt = kt / cpt, c0 = (kt - lt * cpt) * kBK;
+            const ParityTap pt = parity_tap(cls, lt);
+            return Tile{pt.tap * s.Cin + c0, pt.dh, pt.dw, c0};
+        } else return Tile{kt * kBK, 0, 0, 0};
+    };
+    auto load_a = [&](const ARows& rows, int kt) {
+        if constexpr (kIsS2T<SH>) { const Tile t = tile_of(kt); load_a_tap(X, s.H / 2, s.W / 2, s.Cin, rows, t.dh, t.dw, t.c0 + (tid & 7) * 4, av); }
+        else load_a_regs<KS, SMALLC, TX>(X, s, rows, kt, tid, av);
+    };
     auto load_b = [&](int kt) {
+        const int kfirst = tile_of(kt).k0;
 #pragma unroll
         for (int q = 0; q < BCH; ++q) {
             const int e = tid + kThreads * q;
             const int ec = e < BN * 4 ? e : 0;                        // unconditional load from a clamped address
             const int col = ec >> 2, kq = ec & 3;
-            bv[q] = *reinterpret_cast<const bf16x8*>(WB + (long long)(n0 + col) * Kp + kt * kBK + kq * 8);
+            bv[q] = *reinterpret_cast<const bf16x8*>(WB + (long long)(n0 + col) * Kp + kfirst + kq * 8);
         }
     };
     auto store_tiles = [&](int buf) {
@@ -112,15 +130,17 @@ __global__ __launch_bounds__(kThreads) void k_conv_fwd_bf16(const TX* __restrict
         }
     };
 
+    int* const orow_s = parity_row_table<kIsS2T<SH>>();      // parity classes: where each of the workgroup's 128 rows is written
+    if constexpr (kIsS2T<SH>) { if (tid < kBM && m0 + tid < M) orow_s[tid] = (int)parity_out_row(s, cls, m0 + tid); }
     const ARows rows = decode_rows(s, M, m0, tid);
-    load_a_regs<KS, SMALLC, TX>(X, s, rows, kt0, tid, av);
+    load_a(rows, kt0);
     load_b(kt0);
     store_tiles(0);
     __syncthreads();
     for (int kt = 0; kt < nkt; ++kt) {
         const int cur = kt & 1;
         if (kt + 1 < nkt) {
-            load_a_regs<KS, SMALLC, TX>(X, s, rows, kt0 + kt + 1, tid, av);
+            load_a(rows, kt0 + kt + 1);
             load_b(kt0 + kt + 1);
         }
         const __bf16* a = &As[cur][(wave * 32 + (lane & 31)) * kLdH + 8 * (lane >> 5)];
@@ -145,8 +165,9 @@ __global__ __launch_bounds__(kThreads) void k_conv_fwd_bf16(const TX* __restrict
         const float bb = (EPI == 1 || EPI == 2) ? bias[co] : 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const long long m = m0 + wave * 32 + mfma32_row(lane, r);
+            long long m = m0 + wave * 32 + mfma32_row(lane, r);
             if (m < M) {
+                if constexpr (kIsS2T<SH>) m = orow_s[wave * 32 + mfma32_row(lane, r)];      // the input pixel of this class's row
                 float v = acc[t][r] + bb;
                 if (EPI == 2) v = v > 0.f ? v : 0.f;
                 if (EPI == 3) v = widen(reinterpret_cast<const TY*>(bias)[m * s.Cout + co]) > 0.f ? v : 0.f;      // dgrad: ReLU mask of the layer below, `bias` = its output
@@ -187,9 +208,10 @@ __device__ inline bf16x8 tr_fragment(const __bf16* img, int ld, int px0, int col
 // those images -- the hardware transposed read delivers exactly that, so no operand is ever transposed by software.
 // A k-block lies inside one filter tap (Cin % 32 == 0), different waves' blocks may be different taps.
 // TX: storage type of X (the first dense layer's input is the convolutional stage's last map)
-template <int KS, int BN, int NKB, typename TX = float>
+// SH = ConvShapeS2: X gathered at the strided position, as in k_conv_wgrad (a strided layer's 9 Cin / 32 k-blocks are a multiple of three: NKB = 3)
+template <int KS, int BN, int NKB, typename TX = float, class SH = ConvShape>
 __global__ __launch_bounds__(64 * NKB) void k_conv_wgrad_bf16(const TX* __restrict__ X, const float* __restrict__ dZ,
-                                                              float* __restrict__ slab, ConvShape s, int pix_per_chunk, WgradGrid gd) {
+                                                              float* __restrict__ slab, SH s, int pix_per_chunk, WgradGrid gd) {
     constexpr int NT = BN / 32, kPT = 128, NTHR = 64 * NKB;
     constexpr int LDX = 32 * NKB + 8, LDD = BN + 8;
     constexpr int XCH = kPT * 8 * NKB / NTHR;                              // f32x4 chunks of the X tile per thread (= 16)
@@ -198,7 +220,7 @@ __global__ __launch_bounds__(64 * NKB) void k_conv_wgrad_bf16(const TX* __restri
     __shared__ __attribute__((aligned(16))) __bf16 Ds[kPT * LDD];
     __shared__ __attribute__((aligned(16))) float red[NTHR * 4];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const long long M = (long long)s.N * s.H * s.W;
+    const long long M = gemm_rows(s);
     const int K = KS * KS * s.Cin, nkb = K / 32;
     int kgx, nby, chunk;
     if (!gd.decode((int)blockIdx.x, kgx, nby, chunk)) return;            // padding of the XCD-aware grid (uniform per workgroup)
@@ -222,15 +244,23 @@ __global__ __launch_bounds__(64 * NKB) void k_conv_wgrad_bf16(const TX* __restri
     const int dh = tap / KS - KS / 2, dw = tap % KS - KS / 2;
     const long long toff = ((long long)dh * s.W + dw) * s.Cin + (k0 - tap * s.Cin) + (xcol & 31);
     f32x4 xv[XCH], dv[DCH];
-    PixelRow<8> row((int)p0 + tid / (8 * NKB), s);                        // the thread's X rows: 8 pixels apart across q AND across stages (128 = 16 * 8)
+    const auto& so = out_map(s);                                           // the map PixelRow walks: the output's
+    PixelRow<8> row((int)p0 + tid / (8 * NKB), so);                       // the thread's X rows: 8 pixels apart across q AND across stages (128 = 16 * 8)
     auto gload = [&](long long pb) {
 #pragma unroll
         for (int q = 0; q < XCH; ++q) {
             const bool in = xlive && row.m < (int)p1;
-            const bool ok = in && (unsigned)(row.oh + dh) < (unsigned)s.H && (unsigned)(row.ow + dw) < (unsigned)s.W;
-            const f32x4 val = widen4(*reinterpret_cast<const chunk4_t<TX>*>(X + (ok ? (long long)row.m * s.Cin + toff : 0)));   // unconditional, masked by value
-            xv[q] = ok ? val : f32x4{0, 0, 0, 0};
-            row.advance(s);
+            if constexpr (kIsS2<SH>) {
+                // the taps are centred on input pixel (n, 2 oh, 2 ow), whose index is (n H + 2 oh) W + 2 ow = 4 m - 2 ow
+                const bool ok = in && (unsigned)(2 * row.oh + dh) < (unsigned)s.H && (unsigned)(2 * row.ow + dw) < (unsigned)s.W;
+                const f32x4 val = widen4(*reinterpret_cast<const chunk4_t<TX>*>(X + (ok ? (4LL * row.m - 2 * row.ow) * s.Cin + toff : 0)));
+                xv[q] = ok ? val : f32x4{0, 0, 0, 0};
+            } else {
+                const bool ok = in && (unsigned)(row.oh + dh) < (unsigned)s.H && (unsigned)(row.ow + dw) < (unsigned)s.W;
+                const f32x4 val = widen4(*reinterpret_cast<const chunk4_t<TX>*>(X + (ok ? (long long)row.m * s.Cin + toff : 0)));   // unconditional, masked by value
+                xv[q] = ok ? val : f32x4{0, 0, 0, 0};
+            }
+            row.advance(so);
         }
 #pragma unroll
         for (int q = 0; q < DCH; ++q) {

@@ -183,10 +183,17 @@ __global__ __launch_bounds__(kBnFinishThreads) void k_bn_stats_finish(const doub
 
 // y = max(0, fl(fl(xh * gamma) + beta)), xh = fl(fl(x - mean) * invstd); EVAL: stat2 is the running variance, else the batch's invstd.
 // ADD (RCN_HIPX_BN_ADD_RELU): y = max(0, fl(fl(fl(xh * gamma) + beta) + s)), s the skip's map, loaded as 16 bytes beside x
-template <bool EVAL, bool ADD>
+// ADD 2 (RCN_HIPX_BN_ADD_RELU_DOWN): s is the output of a layer of twice the height and width and Cs <= C channels, added through the
+// parameter-free option-A shortcut s'[b][h][w][c] = s[b][2h][2w][c - lo] for lo <= c < lo + Cs, else 0: one 16-byte load at the strided
+// pixel where the thread's four channels lie in the window (lo % 4 == 0 and Cs % 4 == 0: never split), zeros elsewhere
+struct SkipDown { int oH, oW, Cs, lo; };      // this layer's map; the source's channels; the first channel of the window
+__device__ inline SkipDown skip_geom() { return SkipDown{}; }
+__device__ inline SkipDown skip_geom(const SkipDown& d) { return d; }
+// DOWN...: empty (RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU: the kernel's arguments are what they were), or one SkipDown behind eps
+template <bool EVAL, bool ADD, class... DOWN>
 __global__ __launch_bounds__(kBnThreads) void k_bn_apply_relu(const float* __restrict__ x, const float* __restrict__ s, float* __restrict__ y, long long n4, int C,
                                                               const float* __restrict__ mean, const float* __restrict__ stat2, const float* __restrict__ gamma,
-                                                              const float* __restrict__ beta, float eps) {
+                                                              const float* __restrict__ beta, float eps, DOWN... down) {
 #pragma clang fp contract(off)
     const int C4 = C / 4;
     long long e = (long long)blockIdx.x * kBnThreads + threadIdx.x;
@@ -198,7 +205,18 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_apply_relu(const float* __res
     for (; e < n4; e += (long long)gridDim.x * kBnThreads) {
         const f32x4 xv = bn_load4(x + e * 4);
         f32x4 sv;
-        if (ADD) sv = bn_load4(s + e * 4);
+        if (ADD && sizeof...(DOWN) == 0) sv = bn_load4(s + e * 4);
+        if constexpr (sizeof...(DOWN) == 1) {
+            const SkipDown d = skip_geom(down...);
+            const long long px = e / C4;
+            const int w = (int)(px % d.oW);
+            const long long t = px / d.oW;
+            const int h = (int)(t % d.oH);
+            const long long b = t / d.oH;
+            const bool in = c >= d.lo && c < d.lo + d.Cs;
+            const f32x4 v = bn_load4(s + (in ? ((b * (2 * d.oH) + 2 * h) * (2 * d.oW) + 2 * w) * d.Cs + (c - d.lo) : 0));      // unconditional load, masked by value
+            sv = in ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
         const f32x4 xh = bn_xhat(xv, mu, is);
         f32x4 v;
 #pragma unroll
@@ -308,6 +326,39 @@ __global__ __launch_bounds__(kBnThreads) void k_skip_bwd_add(float* __restrict__
 #pragma unroll
         for (int k = 0; k < 4; ++k) a[k] = a[k] + g[k];
         *reinterpret_cast<f32x4*>(dsrc + e * 4) = a;
+    }
+}
+// The same for a RCN_HIPX_BN_ADD_RELU_DOWN layer: one thread per four floats of the SMALL map's Cs-channel window,
+//     dsrc[b][2h][2w][c'] = fl(dsrc[b][2h][2w][c'] + g[b][h][w][c' + lo])
+// with the identity skip's gate table, the source's gate read at the strided position.  A quarter of the source map is touched, each
+// element by one thread.  n4 = B * oH * oW * Cs / 4; C: the channels of dy and y_self.
+template <bool GATE_SELF, bool GATE_SRC>
+__global__ __launch_bounds__(kBnThreads) void k_skip_bwd_add_down(float* __restrict__ dsrc, const float* __restrict__ dy, const float* __restrict__ y_self,
+                                                                  const float* __restrict__ y_src, long long n4, int C, SkipDown d) {
+    const int Cs4 = d.Cs / 4;
+    for (long long e = (long long)blockIdx.x * kBnThreads + threadIdx.x; e < n4; e += (long long)gridDim.x * kBnThreads) {
+        const int c = (int)(e % Cs4) * 4;
+        const long long px = e / Cs4;
+        const int w = (int)(px % d.oW);
+        const long long t = px / d.oW;
+        const int h = (int)(t % d.oH);
+        const long long b = t / d.oH;
+        const long long so = ((b * (2 * d.oH) + 2 * h) * (2 * d.oW) + 2 * w) * d.Cs + c, go = px * C + d.lo + c;
+        f32x4 a = bn_load4(dsrc + so);
+        f32x4 g = bn_load4(dy + go);
+        if (GATE_SELF) {
+            const f32x4 yv = bn_load4(y_self + go);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g[k] = yv[k] > 0.f ? g[k] : 0.f;
+        }
+        if (GATE_SRC) {
+            const f32x4 yv = bn_load4(y_src + so);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g[k] = yv[k] > 0.f ? g[k] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a[k] = a[k] + g[k];
+        *reinterpret_cast<f32x4*>(dsrc + so) = a;
     }
 }
 

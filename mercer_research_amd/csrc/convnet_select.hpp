@@ -393,6 +393,84 @@ inline std::string describe(const WgradChoice& c, const ConvShape& s, int ks, bo
 // does an LDS-tiled kernel run this layer's weight gradient?
 inline bool wgrad_halo_runs(const Selection& sel, const ConvShape& s, int ks) { return lds_tiled(select_wgrad(sel, s, ks, false, Store{}).kernel); }
 
+// ---- RCN_HIPX_CONV3X3_S2: all three GEMMs of a strided layer on the implicit-GEMM family, in both operand precisions.  The LDS-tiled
+// (halo) families assume stride 1; these selectors take the strided shape types and hold no LDS-tiled kernel, no fused pool and no
+// pooled-resolution operand to hand out -- conv_halo_runs, wgrad_halo_runs and conv_pool_fusable take a ConvShape and are never asked of
+// a strided layer.
+struct ConvS2Choice {
+    const char* error = nullptr;    // or: the layer cannot run (status -3 with this message)
+    bool bf16 = false;              // operands rounded to bf16
+    int bn = 32;                    // the kernel's column-block width
+    int Z = 1, kepi = 0;            // forward: split-K factor and the kernel's own epilogue, as ConvChoice's
+    long long tiles = 0;            // 128-row tiles: of the output map (forward), of ONE parity class (input gradient: four classes of as many)
+};
+// forward: Y = conv(X) + b (epi 1).  Split-K applies as to the stride-1 kernel -- same body, M = the OUTPUT pixels: a small strided map
+// has few output tiles and a contraction of 9 Cin / 32 >= 9 K-tiles
+inline ConvS2Choice select_conv_s2(const Selection& sel, const ConvShapeS2& s, int epi) {
+    ConvS2Choice c;
+    const auto refuse = [&c](const char* why) { c.error = why; return c; };
+    if (s.H % 2 || s.W % 2) return refuse("a strided convolution needs even height and width");
+    if (s.Cin % 32) return refuse("a strided convolution's input channels must be a multiple of 32");
+    if (s.Cout % 32) return refuse("output channels must be a multiple of 32");
+    const long long M = gemm_rows(s);
+    c.bf16 = sel.precision == RCN_HIPX_BF16;
+    c.bn = (c.bf16 && s.Cout % 128 == 0) ? 128 : (s.Cout % 64 == 0) ? 64 : 32;
+    c.Z = splitk_z(M, s.Cout, c.bn, 9 * s.Cin / 32);
+    c.kepi = c.Z > 1 ? 0 : epi;
+    c.tiles = (M + kBM - 1) / kBM;
+    return c;
+}
+inline std::string describe(const ConvS2Choice& c, const ConvShapeS2& s, int epi) {
+    return strf("  conv3x3/2 %dx%dx%d->%dx%dx%d epi %d: %s<3, tile, %d, ConvShapeS2>, %lld output tiles", s.H, s.W, s.Cin, s.H / 2, s.W / 2, s.Cout, epi, c.bf16 ? "k_conv_fwd_bf16" : "k_conv_fwd", c.bn, c.tiles) +
+           (c.Z > 1 ? " split-K " + std::to_string(c.Z) + " + k_splitk_epilogue" : std::string(", no split-K"));
+}
+// input gradient: one launch over the four parity classes of input pixels (convnet.hpp), epi 0 (raw) or 3 (gated by the layer below's
+// output).  No split-K: the classes' contractions differ in length.  Column blocks of 64 or 32 in either precision.
+inline ConvS2Choice select_dgrad_s2(const Selection& sel, const ConvShapeS2T& s, int epi) {
+    ConvS2Choice c;
+    const auto refuse = [&c](const char* why) { c.error = why; return c; };
+    if (s.H % 2 || s.W % 2 || s.Cin % 32 || s.Cout % 32) return refuse("internal: a strided input gradient of a shape the layer table refuses");
+    if ((long long)s.N * s.H * s.W > 0x7fff0000LL) return refuse("too many input pixels in one strided layer (N*H*W must stay below 2^31)");
+    c.bf16 = sel.precision == RCN_HIPX_BF16;
+    c.bn = (s.Cout % 64 == 0) ? 64 : 32;
+    c.kepi = epi;
+    c.tiles = (gemm_rows(s) + kBM - 1) / kBM;
+    return c;
+}
+inline std::string describe(const ConvS2Choice& c, const ConvShapeS2T& s, int epi) {
+    return strf("  dgrad conv3x3/2 %dx%dx%d->%dx%dx%d epi %d: %s<3, tile, %d, ConvShapeS2T>, one launch, parity classes (odd,odd) 4 taps: %lld tiles, (odd,even) 2 taps: %lld tiles, (even,odd) 2 taps: %lld tiles, (even,even) 1 tap: %lld tiles",
+                s.H / 2, s.W / 2, s.Cin, s.H, s.W, s.Cout, epi, c.bf16 ? "k_conv_fwd_bf16" : "k_conv_fwd", c.bn, c.tiles, c.tiles, c.tiles, c.tiles);
+}
+// weight gradient: the implicit-GEMM kernels' chunks of OUTPUT pixels; bf16: always three waves (9 Cin / 32 k-blocks)
+inline WgradChoice select_wgrad_s2(const Selection& sel, const ConvShapeS2& s) {
+    WgradChoice c;
+    const auto refuse = [&c](const char* why) { c.error = why; return c; };
+    const long long M = gemm_rows(s);
+    const int nkb = 9 * s.Cin / 32;
+    const bool bf16 = sel.precision == RCN_HIPX_BF16;
+    c.kernel = bf16 ? WgradKernel::wgrad_bf16 : WgradKernel::wgrad_f32;
+    if (s.H % 2 || s.W % 2 || s.Cin % 32 || s.Cout % 32) return refuse("internal: a strided weight gradient of a shape the layer table refuses");
+    if ((long long)s.N * s.H * s.W > 0x7fff0000LL) return refuse("too many input pixels in one strided layer (N*H*W must stay below 2^31)");
+    const int bn0 = (s.Cout % 64 == 0) ? 64 : 32;
+    c.bn = bn0;
+    c.ppc = pix_per_chunk(sel, M, (long long)nkb * (s.Cout / bn0));
+    c.chunks = (int)((M + c.ppc - 1) / c.ppc);
+    if (bf16) {
+        c.nk = 3;
+        if (sel.opt.wgb_policy) {         // (select_wgrad's policy: narrower tiles below two waves per SIMD, shorter chunks below one)
+            if ((long long)nkb * (s.Cout / c.bn) * c.chunks < 2048) c.bn = 32;
+            while ((long long)nkb * (s.Cout / c.bn) * c.chunks < 1024 && c.ppc > 256) { c.ppc /= 2; c.chunks = (int)((M + c.ppc - 1) / c.ppc); }
+        }
+        return c;
+    }
+    if (sel.opt.wgf_policy && 4LL * nkb * (s.Cout / bn0) * c.chunks < 2048) c.bn = 32;
+    return c;
+}
+inline std::string describe(const WgradChoice& c, const ConvShapeS2& s) {
+    const std::string head = strf("  wgrad conv3x3/2 %dx%dx%d->%dx%dx%d: ", s.H, s.W, s.Cin, s.H / 2, s.W / 2, s.Cout);
+    return c.kernel == WgradKernel::wgrad_bf16 ? head + strf("k_conv_wgrad_bf16<3, %d, 3, ConvShapeS2>, %d chunks", c.bn, c.chunks) : head + strf("k_conv_wgrad<3, tile, %d, ConvShapeS2>, %d chunks", c.bn, c.chunks);
+}
+
 // ---- the step's update launch (convnet_update.hpp)
 // what a training step does with its gradient: the whole update (a net that does not accumulate), or one micro-step of a cycle of
 // rcn_hipx_set_accumulate -- the first stores into the accumulator, a middle one adds, the last adds and applies the update

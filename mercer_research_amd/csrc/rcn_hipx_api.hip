@@ -64,15 +64,17 @@ struct LayerShape {
     long long w_off = 0, b_off = 0;       // padded flat layout
     long long lw_off = 0, lb_off = 0;     // logical flat layout
     bool pool_follows = false;
-    // an identity skip (RCN_HIPX_BN_ADD_RELU): the layer whose output this layer adds in front of its ReLU, and -- in that source -- the
-    // layer that adds its output; -1: none
+    // a skip (RCN_HIPX_BN_ADD_RELU: identity; RCN_HIPX_BN_ADD_RELU_DOWN: subsampled and zero-padded): the layer whose output this layer
+    // adds in front of its ReLU, and -- in that source -- the layer that adds its output; -1: none
     int skip_src = -1, skip_by = -1;
 };
 // the kinds by what the walks ask of them: a 3x3 convolution (with or without ReLU), and a layer whose W is a matrix with a tap-flipped
 // copy and bf16 operand copies (every layer with a [W | b] block but batch normalisation, whose block is [gamma | beta])
-inline bool is_conv(int kind) { return kind == RCN_HIPX_CONV3X3_RELU || kind == RCN_HIPX_CONV3X3; }
+inline bool is_conv(int kind) { return kind == RCN_HIPX_CONV3X3_RELU || kind == RCN_HIPX_CONV3X3 || kind == RCN_HIPX_CONV3X3_S2; }
+// a bias-only convolution in front of batch normalisation, of either stride: no activation, no ReLU gate of its own, BN must follow
+inline bool is_conv_linear(int kind) { return kind == RCN_HIPX_CONV3X3 || kind == RCN_HIPX_CONV3X3_S2; }
 // batch normalisation, with or without a skip added in front of its ReLU: one [gamma | beta] block, statistics and buffers either way
-inline bool is_bn(int kind) { return kind == RCN_HIPX_BN_RELU || kind == RCN_HIPX_BN_ADD_RELU; }
+inline bool is_bn(int kind) { return kind == RCN_HIPX_BN_RELU || kind == RCN_HIPX_BN_ADD_RELU || kind == RCN_HIPX_BN_ADD_RELU_DOWN; }
 // a layer with a parameter block ([W | b] or [gamma | beta]): every kind but the two pools, which also take no `out`
 inline bool has_params(int kind) { return kind != RCN_HIPX_MAXPOOL2 && kind != RCN_HIPX_GLOBAL_AVGPOOL; }
 inline bool has_matrix(int kind) { return has_params(kind) && !is_bn(kind); }
@@ -263,6 +265,17 @@ template <typename F> bool with_epi_pin(int kepi, bool pin, F&& f) {
 #define CV(c_) (decltype(c_)::value)        /* the value of one of those constants, as a template argument */
 #define CT(t_) typename decltype(t_)::type   /* ... and the type in a Type<> */
 
+// operands rounded to bf16: *WB is the prepared transposed copy [Cout][Kp] of the K x Cout weights (prep_bf16_weights), or -- none prepared --
+// made here into the shared scratch, in front of the launch that reads it; the activations are rounded inside the kernel
+int bf16_operand(rcn_hipx_net* n, const float* Wk, int K, int Cout, const __bf16** WB) {
+    if (*WB) return 0;
+    const int Kp = (K + 31) / 32 * 32;
+    XTRY(n, scratch_ensure(n, n->wb, (size_t)Cout * Kp * sizeof(__bf16)));
+    hipLaunchKernelGGL(k_prep_weights_bf16, dim3(grid1d((long long)Cout * Kp, 256)), dim3(256), 0, n->stream, Wk, K, Cout, (__bf16*)n->wb.p, Kp);
+    *WB = (const __bf16*)n->wb.p;
+    return 0;
+}
+
 // Y = act(conv(X) + b): the kernel select_conv chooses (convnet_select.hpp).  Split-K launches leave raw partial tiles in `skbuf` that
 // k_splitk_epilogue sums in order.
 int launch_conv(rcn_hipx_net* n, const float* X, const float* Wk, const float* bias, float* Y, ConvShape s, int ks, int epi, uint8_t* pool_idx = nullptr,
@@ -278,13 +291,7 @@ int launch_conv(rcn_hipx_net* n, const float* X, const float* Wk, const float* b
         out = (float*)n->skbuf.p;
     }
     const __bf16* WB = wb_ready;                    // made for all layers at the start of the step (prep_bf16_weights)
-    if (c.bf16 && !WB) {
-        // operands rounded to bf16: the weights once here, transposed to [Cout][Kp]; the activations inside the kernel
-        const int K = ks * ks * s.Cin, Kp = (K + 31) / 32 * 32;
-        XTRY(n, scratch_ensure(n, n->wb, (size_t)s.Cout * Kp * sizeof(__bf16)));
-        hipLaunchKernelGGL(k_prep_weights_bf16, dim3(grid1d((long long)s.Cout * Kp, 256)), dim3(256), 0, n->stream, Wk, K, s.Cout, (__bf16*)n->wb.p, Kp);
-        WB = (const __bf16*)n->wb.p;
-    }
+    if (c.bf16) RTRY(bf16_operand(n, Wk, ks * ks * s.Cin, s.Cout, &WB));
     const PooledGrad pg = pin ? *pin : PooledGrad{nullptr, nullptr, nullptr};
     const dim3 grid((unsigned)((M + kBM - 1) / kBM), (unsigned)(s.Cout / c.bn), (unsigned)c.Z);      // the implicit-GEMM kernels'
     const int items = (int)c.items;
@@ -334,17 +341,20 @@ int launch_conv(rcn_hipx_net* n, const float* X, const float* Wk, const float* b
         }); });
         break;
     case ConvKernel::fwd_bf16:
+        // (no dense gather form: a dense layer's inputs are a multiple of 32 -- describe_layers -- so select_conv never asks for <1, gather>)
         with_const<3, 1>(ks, [&](auto KS) { with_bool(c.smallc, [&](auto SM) { with_const<128, 64, 32>(c.bn, [&](auto BN) { with_const<0, 1, 2, 3>(c.kepi, [&](auto EPI) {
-            hipLaunchKernelGGL((k_conv_fwd_bf16<CV(KS), CV(SM), CV(BN), CV(EPI)>), grid, dim3(kThreads), 0, n->stream, X, WB, bias, out, s);
+            if constexpr (CV(KS) == 1 && CV(SM)) found = false;
+            else hipLaunchKernelGGL((k_conv_fwd_bf16<CV(KS), CV(SM), CV(BN), CV(EPI)>), grid, dim3(kThreads), 0, n->stream, X, WB, bias, out, s);
         }); }); }); });
         break;
     case ConvKernel::fwd_f32:
         with_const<3, 1>(ks, [&](auto KS) { with_bool(c.smallc, [&](auto SM) { with_const<64, 32>(c.bn, [&](auto BN) { with_const<0, 1, 2, 3>(c.kepi, [&](auto EPI) {
-            hipLaunchKernelGGL((k_conv_fwd<CV(KS), CV(SM), CV(BN), CV(EPI)>), grid, dim3(kThreads), 0, n->stream, X, Wk, bias, out, s);
+            if constexpr (CV(KS) == 1 && CV(SM)) found = false;      // (no dense gather form, as above)
+            else hipLaunchKernelGGL((k_conv_fwd<CV(KS), CV(SM), CV(BN), CV(EPI)>), grid, dim3(kThreads), 0, n->stream, X, Wk, bias, out, s);
         }); }); }); });
         break;
     }
-    if (!found) return fail(n, -3, "internal: pooled-resolution input with a forward epilogue");
+    if (!found) return fail(n, -3, "internal: no kernel of this form (a pooled-resolution input with a forward epilogue, or a dense layer on the gather loader)");
     XTRY(n, hipGetLastError());
     if (c.Z > 1) {
         if (st.y16) hipLaunchKernelGGL(k_splitk_epilogue<__bf16>, dim3(grid1d(M * s.Cout, 256)), dim3(256), 0, n->stream, (const float*)n->skbuf.p, bias, (__bf16*)Y, M * s.Cout, s.Cout, c.Z, epi);
@@ -405,6 +415,82 @@ int launch_wgrad(rcn_hipx_net* n, const float* X, const float* dZ, ConvShape s, 
         with_const<3, 1>(ks, [&](auto KS) { with_bool(c.smallc, [&](auto SM) { with_const<64, 32>(c.bn, [&](auto BN) {
             hipLaunchKernelGGL((k_conv_wgrad<CV(KS), CV(SM), CV(BN)>), grid, dim3(kThreads), 0, n->stream, X, dZ, slab, s, c.ppc, gd);
         }); }); });
+        break;
+    }
+    }
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+
+// ---- RCN_HIPX_CONV3X3_S2 (convnet_select.hpp: implicit GEMM only)
+// forward: Y = conv(X) + b over the (H/2) x (W/2) output map
+int launch_conv_s2(rcn_hipx_net* n, const float* X, const float* Wk, const float* bias, float* Y, ConvShapeS2 s, int epi, const __bf16* WB) {
+    const ConvS2Choice c = select_conv_s2(*n, s, epi);
+    if (c.error) return fail(n, -3, c.error);
+    if (dry_note(n, "%s", describe(c, s, epi).c_str())) return 0;
+    const long long M = gemm_rows(s);
+    float* out = Y;
+    if (c.Z > 1) {
+        XTRY(n, scratch_ensure(n, n->skbuf, (size_t)c.Z * M * s.Cout * sizeof(float)));
+        out = (float*)n->skbuf.p;
+    }
+    if (c.bf16) RTRY(bf16_operand(n, Wk, 9 * s.Cin, s.Cout, &WB));
+    const dim3 grid((unsigned)c.tiles, (unsigned)(s.Cout / c.bn), (unsigned)c.Z);
+    if (c.bf16)
+        with_const<128, 64, 32>(c.bn, [&](auto BN) { with_const<0, 1>(c.kepi, [&](auto EPI) {
+            hipLaunchKernelGGL((k_conv_fwd_bf16<3, false, CV(BN), CV(EPI), float, float, ConvShapeS2>), grid, dim3(kThreads), 0, n->stream, X, WB, bias, out, s);
+        }); });
+    else
+        with_const<64, 32>(c.bn, [&](auto BN) { with_const<0, 1>(c.kepi, [&](auto EPI) {
+            hipLaunchKernelGGL((k_conv_fwd<3, false, CV(BN), CV(EPI), ConvShapeS2>), grid, dim3(kThreads), 0, n->stream, X, Wk, bias, out, s);
+        }); });
+    XTRY(n, hipGetLastError());
+    if (c.Z > 1) {
+        hipLaunchKernelGGL(k_splitk_epilogue<float>, dim3(grid1d(M * s.Cout, 256)), dim3(256), 0, n->stream, (const float*)n->skbuf.p, bias, Y, M * s.Cout, s.Cout, c.Z, epi);
+        XTRY(n, hipGetLastError());
+    }
+    return 0;
+}
+// input gradient: dX (the whole H x W map, every element once) from dZ and the tap-flipped transposed weights, one launch over the parity classes
+int launch_dgrad_s2(rcn_hipx_net* n, const float* dZ, const float* Wt, const float* gate, float* dX, ConvShapeS2T s, int epi, const __bf16* WB) {
+    const ConvS2Choice c = select_dgrad_s2(*n, s, epi);
+    if (c.error) return fail(n, -3, c.error);
+    if (dry_note(n, "%s", describe(c, s, epi).c_str())) return 0;
+    if (c.bf16) RTRY(bf16_operand(n, Wt, 9 * s.Cin, s.Cout, &WB));
+    const dim3 grid((unsigned)(4 * c.tiles), (unsigned)(s.Cout / c.bn));
+    if (c.bf16)
+        with_const<64, 32>(c.bn, [&](auto BN) { with_const<3, 0>(c.kepi, [&](auto EPI) {
+            hipLaunchKernelGGL((k_conv_fwd_bf16<3, false, CV(BN), CV(EPI), float, float, ConvShapeS2T>), grid, dim3(kThreads), 0, n->stream, dZ, WB, gate, dX, s);
+        }); });
+    else
+        with_const<64, 32>(c.bn, [&](auto BN) { with_const<3, 0>(c.kepi, [&](auto EPI) {
+            hipLaunchKernelGGL((k_conv_fwd<3, false, CV(BN), CV(EPI), ConvShapeS2T>), grid, dim3(kThreads), 0, n->stream, dZ, Wt, gate, dX, s);
+        }); });
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+// weight gradient into the layer's slab (n->slab_sel), as launch_wgrad
+int launch_wgrad_s2(rcn_hipx_net* n, const float* X, const float* dZ, ConvShapeS2 s, int* chunks_out) {
+    const WgradChoice c = select_wgrad_s2(*n, s);
+    if (c.error) return fail(n, -3, c.error);
+    *chunks_out = c.chunks;
+    if (dry_note(n, "%s", describe(c, s).c_str())) return 0;
+    const int K = 9 * s.Cin;
+    XTRY(n, scratch_ensure(n, *n->slab_sel, (size_t)c.chunks * (K + 1) * s.Cout * sizeof(float)));
+    float* const slab = (float*)n->slab_sel->p;
+    switch (c.kernel) {
+    case WgradKernel::wgrad_bf16: {
+        const WgradGrid gd{K / 32 / 3, s.Cout / c.bn, c.chunks, n->opt.xcd_remap};
+        with_const<64, 32>(c.bn, [&](auto BN) {
+            hipLaunchKernelGGL((k_conv_wgrad_bf16<3, CV(BN), 3, float, ConvShapeS2>), dim3(gd.launch_blocks()), dim3(64 * 3), 0, n->stream, X, dZ, slab, s, c.ppc, gd);
+        });
+        break;
+    }
+    default: {
+        const WgradGrid gd{K / 32, s.Cout / c.bn, c.chunks, n->opt.xcd_remap};
+        with_const<64, 32>(c.bn, [&](auto BN) {
+            hipLaunchKernelGGL((k_conv_wgrad<3, false, CV(BN), ConvShapeS2>), dim3(gd.launch_blocks()), dim3(kThreads), 0, n->stream, X, dZ, slab, s, c.ppc, gd);
+        });
         break;
     }
     }
@@ -561,11 +647,17 @@ int launch_bn_forward(rcn_hipx_net* n, size_t i, const float* x, int B, bool tra
     const unsigned blocks = bn_stream_blocks(n4, C / 4);
     if (train && !n->dry && (size_t)parts * 2 * C * sizeof(double) > l.bn_part.cap) return fail(n, -3, "internal: more partial sums than the layer's buffer holds");
     // RCN_HIPX_BN_ADD_RELU: the skip's map (the source layer's output, of this layer's shape: describe_layers) is added in front of the ReLU
-    const bool add = l.skip_src >= 0;
+    // RCN_HIPX_BN_ADD_RELU_DOWN: the source is twice as high and wide and has Cs <= C channels; it comes in through the option-A shortcut
+    const bool add = l.skip_src >= 0, down = l.kind == RCN_HIPX_BN_ADD_RELU_DOWN;
     const float* const skip = add ? (const float*)n->L[l.skip_src].out.p : (const float*)nullptr;
-    auto apply = [&](auto kernel, const float* mean, const float* stat2) {
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBnThreads), 0, n->stream, x, skip, (float*)l.out.p, n4, C, mean, stat2, (const float*)P(n, l.w_off), (const float*)P(n, l.b_off), n->bn_eps);
+    const int Cs = down ? n->L[l.skip_src].CoutP : C;
+    const SkipDown sd{l.oH, l.oW, Cs, (C - Cs) / 2};
+    // geom...: nothing for k_bn_apply_relu<EVAL, ADD> (the two modes there were: their kernels take the arguments they took), or the one
+    // SkipDown that k_bn_apply_relu<EVAL, true, SkipDown> takes behind eps -- the kernel's trailing parameter pack (convnet_bn.hpp)
+    auto apply = [&](auto kernel, const float* mean, const float* stat2, auto... geom) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBnThreads), 0, n->stream, x, skip, (float*)l.out.p, n4, C, mean, stat2, (const float*)P(n, l.w_off), (const float*)P(n, l.b_off), n->bn_eps, geom...);
     };
+    const std::string down_words = down ? strf(", subsampled (2h, 2w), its %d channels at %d .. %d", Cs, sd.lo, sd.lo + Cs - 1) : std::string();
     if (train) {
         if (!dry_note(n, "  bn-stats %dx%dx%d: k_bn_stats, %d partials of %lld rows, then k_bn_stats_finish (one workgroup, %d threads per channel; momentum %g, eps %g)",
                       l.oH, l.oW, C, parts, bn_rows_per_part(M), bn_team(C), (double)n->bn_momentum, (double)n->bn_eps)) {
@@ -575,15 +667,18 @@ int launch_bn_forward(rcn_hipx_net* n, size_t i, const float* x, int B, bool tra
                                bn_mean(l), bn_invstd(l), bn_run_mean(l), bn_run_var(l));
             XTRY(n, hipGetLastError());
         }
-        if (add ? dry_note(n, "  bn-add-relu %dx%dx%d: k_bn_apply_add_relu, %u workgroups (the batch's mean and invstd; skip: the output of layer %d)", l.oH, l.oW, C, blocks, l.skip_src)
+        if (add ? dry_note(n, "  bn-add-relu %dx%dx%d: k_bn_apply_add_relu%s, %u workgroups (the batch's mean and invstd; skip: the output of layer %d%s)", l.oH, l.oW, C, down ? "_down" : "", blocks,
+                           l.skip_src, down_words.c_str())
                 : dry_note(n, "  bn-relu %dx%dx%d: k_bn_apply_relu, %u workgroups (the batch's mean and invstd)", l.oH, l.oW, C, blocks)) return 0;
-        if (add) apply(k_bn_apply_relu<false, true>, bn_mean(l), bn_invstd(l));
+        if (down) apply(k_bn_apply_relu<false, true, SkipDown>, bn_mean(l), bn_invstd(l), sd);
+        else if (add) apply(k_bn_apply_relu<false, true>, bn_mean(l), bn_invstd(l));
         else apply(k_bn_apply_relu<false, false>, bn_mean(l), bn_invstd(l));
     } else {
-        if (add ? dry_note(n, "  bn-add-relu %dx%dx%d: k_bn_apply_add_relu<eval>, %u workgroups (scale and shift from the running statistics, eps %g; skip: the output of layer %d)",
-                           l.oH, l.oW, C, blocks, (double)n->bn_eps, l.skip_src)
+        if (add ? dry_note(n, "  bn-add-relu %dx%dx%d: k_bn_apply_add_relu%s<eval>, %u workgroups (scale and shift from the running statistics, eps %g; skip: the output of layer %d%s)",
+                           l.oH, l.oW, C, down ? "_down" : "", blocks, (double)n->bn_eps, l.skip_src, down_words.c_str())
                 : dry_note(n, "  bn-relu %dx%dx%d: k_bn_apply_relu<eval>, %u workgroups (scale and shift from the running statistics, eps %g)", l.oH, l.oW, C, blocks, (double)n->bn_eps)) return 0;
-        if (add) apply(k_bn_apply_relu<true, true>, bn_run_mean(l), bn_run_var(l));
+        if (down) apply(k_bn_apply_relu<true, true, SkipDown>, bn_run_mean(l), bn_run_var(l), sd);
+        else if (add) apply(k_bn_apply_relu<true, true>, bn_run_mean(l), bn_run_var(l));
         else apply(k_bn_apply_relu<true, false>, bn_run_mean(l), bn_run_var(l));
     }
     XTRY(n, hipGetLastError());
@@ -656,10 +751,11 @@ int forward(rcn_hipx_net* n, const float* x, int B, size_t n_layers = (size_t)-1
             cur = (const float*)l.out.p;
             cur16 = n->store16;
             continue;
-        } else if (l.kind == RCN_HIPX_CONV3X3) {
+        } else if (is_conv_linear(l.kind)) {
             // bias only (epilogue 1), no conv+pool fusion: what follows is batch normalisation, on an fp32 map
             if (n->store16) return fail(n, -3, kBnStoreGap);
-            RTRY(launch_conv(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShape{B, l.H, l.W, l.Cin, l.CoutP}, 3, 1, nullptr, nullptr, false, wb_of(n, l.wbf_off)));
+            if (l.kind == RCN_HIPX_CONV3X3_S2) RTRY(launch_conv_s2(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShapeS2{B, l.H, l.W, l.Cin, l.CoutP}, 1, wb_of(n, l.wbf_off)));
+            else RTRY(launch_conv(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShape{B, l.H, l.W, l.Cin, l.CoutP}, 3, 1, nullptr, nullptr, false, wb_of(n, l.wbf_off)));
         } else if (is_bn(l.kind)) {
             if (n->store16) return fail(n, -3, kBnStoreGap);
             RTRY(launch_bn_forward(n, i, cur, B, train));
@@ -740,17 +836,24 @@ int launch_skip_bwd(rcn_hipx_net* n, size_t src, int B, bool src_gated) {
     Layer& s = n->L[src];
     Layer& l = n->L[s.skip_by];
     const bool gated = l.pool_follows || n->bw.gated[s.skip_by];
-    const int C = l.CoutP;
-    const long long n4 = (long long)B * l.oH * l.oW * (C / 4);
-    const unsigned blocks = bn_stream_blocks(n4, C / 4);
-    if (dry_note(n, "  skip-bwd %dx%dx%d: k_skip_bwd_add, %u workgroups into layer %d's gradient (the skip's gradient %s; %s)", l.oH, l.oW, C, blocks, (int)src,
+    // RCN_HIPX_BN_ADD_RELU_DOWN: one thread per four floats of the SMALL map's window of the source's Cs channels -- a quarter of the source map
+    const bool down = l.kind == RCN_HIPX_BN_ADD_RELU_DOWN;
+    const int C = l.CoutP, Cw = down ? s.CoutP : C;
+    const long long n4 = (long long)B * l.oH * l.oW * (Cw / 4);
+    const unsigned blocks = bn_stream_blocks(n4, Cw / 4);
+    if (dry_note(n, "  skip-bwd %dx%dx%d: k_skip_bwd_add%s, %u workgroups into layer %d's gradient (the skip's gradient %s; %s)", l.oH, l.oW, Cw, down ? "_down (at (2h, 2w) of the source)" : "", blocks, (int)src,
                  l.pool_follows ? "gated by the pool's backward" : gated ? gated_above_words(n, (size_t)s.skip_by) : "gated here (out > 0)",
                  (src_gated ? "then gated by layer " + std::to_string(src) + "'s output" : "ungated: layer " + std::to_string(src) + " is a pool").c_str())) return 0;
     auto add = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBnThreads), 0, n->stream, (float*)s.dout.p, (const float*)l.dout.p, (const float*)l.out.p, (const float*)s.out.p, n4);
     };
-    if (gated) { if (src_gated) add(k_skip_bwd_add<false, true>); else add(k_skip_bwd_add<false, false>); }
-    else { if (src_gated) add(k_skip_bwd_add<true, true>); else add(k_skip_bwd_add<true, false>); }
+    auto add_down = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBnThreads), 0, n->stream, (float*)s.dout.p, (const float*)l.dout.p, (const float*)l.out.p, (const float*)s.out.p, n4, C,
+                           SkipDown{l.oH, l.oW, Cw, (C - Cw) / 2});
+    };
+    with_bool(!gated, [&](auto SELF) { with_bool(src_gated, [&](auto SRC) {
+        if (down) add_down(k_skip_bwd_add_down<CV(SELF), CV(SRC)>); else add(k_skip_bwd_add<CV(SELF), CV(SRC)>);
+    }); });
     XTRY(n, hipGetLastError());
     return 0;
 }
@@ -811,13 +914,13 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             RTRY(launch_bn_backward(n, (size_t)i, B, l.pool_follows || gated[i], grad, apply));
             continue;
         }
-        const bool conv = is_conv(l.kind);
+        const bool conv = is_conv(l.kind), strided = l.kind == RCN_HIPX_CONV3X3_S2;
         const int ks = conv ? 3 : 1;
-        const ConvShape s = conv ? ConvShape{B, l.H, l.W, l.Cin, l.CoutP} : ConvShape{B, 1, 1, l.K, l.CoutP};
-        const long long M = (long long)s.N * s.H * s.W;
+        const ConvShape s = conv ? ConvShape{B, l.H, l.W, l.Cin, l.CoutP} : ConvShape{B, 1, 1, l.K, l.CoutP};      // (H x W: the layer's INPUT map; a strided layer's output is l.oH x l.oW)
+        const long long M = (long long)s.N * l.oH * l.oW;
         // dZ: gradient wrt the pre-activation
         const float* dZ = (const float*)l.dout.p;
-        if (l.kind != RCN_HIPX_DENSE && l.kind != RCN_HIPX_CONV3X3 && !l.pool_follows && !gated[i]) {
+        if (l.kind != RCN_HIPX_DENSE && !is_conv_linear(l.kind) && !l.pool_follows && !gated[i]) {
             if (stage16(n, i)) return fail(n, -3, kStoreGap);
             XTRY(n, scratch_ensure(n, n->dz, (size_t)M * l.CoutP * sizeof(float)));
             if (!dry_note(n, "  relu-bwd: k_relu_bwd")) {
@@ -840,7 +943,9 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             // (batch normalisation below a convolution: gated here with its output, the same out > 0 rule; below a dense layer it gates itself;
             // a global average pool below has no ReLU of its own and is NOT named here: its dout stays the plain gradient of the means)
             const bool gate = below.kind == RCN_HIPX_CONV3X3_RELU || below.kind == RCN_HIPX_DENSE_RELU || (is_bn(below.kind) && conv);
-            RTRY(launch_conv(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, ConvShape{s.N, s.H, s.W, s.Cout, s.Cin}, ks, gate ? 3 : 0,
+            // (a strided layer: one launch over the four parity classes of the input pixels writes ALL of dout[i - 1], every element once)
+            if (strided) RTRY(launch_dgrad_s2(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, ConvShapeS2T{s.N, s.H, s.W, s.Cout, s.Cin}, gate ? 3 : 0, wb_of(n, l.wbb_off)));
+            else RTRY(launch_conv(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, ConvShape{s.N, s.H, s.W, s.Cout, s.Cin}, ks, gate ? 3 : 0,
                              nullptr, pooled[i].dP ? &pooled[i] : nullptr, false, wb_of(n, l.wbb_off), Store{stage16(n, i), stage16(n, i - 1)}));
             gated[i - 1] = gate;
             if (below.kind == RCN_HIPX_DENSE_RELU && dropout_on(*n)) RTRY(launch_dropout_bwd(n, (size_t)i - 1, B));      // before anything reads that gradient
@@ -856,7 +961,8 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
         int chunks = 0;
         if (on_side) n->stream = n->side;
         n->slab_sel = &l.slab;
-        RTRY(launch_wgrad(n, in, dZ, s, ks, &chunks, pooled[i].dP ? &pooled[i] : nullptr, Store{stage16(n, i - 1), stage16(n, i)}));
+        if (strided) RTRY(launch_wgrad_s2(n, in, dZ, ConvShapeS2{s.N, s.H, s.W, s.Cin, s.Cout}, &chunks));
+        else RTRY(launch_wgrad(n, in, dZ, s, ks, &chunks, pooled[i].dP ? &pooled[i] : nullptr, Store{stage16(n, i - 1), stage16(n, i)}));
         RTRY(reduce_slab(n, (size_t)i, chunks, ks, s, grad, apply));
         n->stream = main_s;
     }
@@ -1080,11 +1186,24 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
     for (int i = 0; i < n_layers; ++i) {
         Layer l{};
         l.kind = layers[i].kind; l.H = H; l.W = W; l.Cin = C;
+        if (i > 0 && n->L.back().kind == RCN_HIPX_CONV3X3_S2 && !is_bn(l.kind))
+            return fail(n, -2, "layer " + std::to_string(i - 1) + " (RCN_HIPX_CONV3X3_S2): it must be followed directly by a batch-normalisation layer (RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_BN_ADD_RELU_DOWN)");
         if (is_conv(l.kind)) {
-            if (flat) return fail(n, -2, "convolution after a dense layer or a global average pool");
-            if (layers[i].out < 32 || layers[i].out % 32) return fail(n, -3, "conv output channels must be a positive multiple of 32");
+            if (flat) return fail(n, -2, l.kind == RCN_HIPX_CONV3X3_S2 ? "layer " + std::to_string(i) + " (RCN_HIPX_CONV3X3_S2): convolution after a dense layer or a global average pool"
+                                                                       : std::string("convolution after a dense layer or a global average pool"));
+            if (layers[i].out < 32 || layers[i].out % 32)
+                return fail(n, -3, l.kind == RCN_HIPX_CONV3X3_S2 ? "layer " + std::to_string(i) + " (RCN_HIPX_CONV3X3_S2): conv output channels must be a positive multiple of 32"
+                                                                 : std::string("conv output channels must be a positive multiple of 32"));
             if (!(9 * C <= 32) && C % 32) return fail(n, -3, "conv input channels must be a multiple of 32 (or 9*Cin <= 32 for the first layer)");
             l.Cout = l.CoutP = layers[i].out; l.oH = H; l.oW = W; l.K = 9 * C;
+            if (l.kind == RCN_HIPX_CONV3X3_S2) {
+                // stride 2, pad 1: the output is (H/2) x (W/2).  No strided first-layer gather form, no odd maps in this version.
+                const std::string at = "layer " + std::to_string(i) + " (RCN_HIPX_CONV3X3_S2): ";
+                if (H % 2 || W % 2) return fail(n, -3, at + "a strided convolution needs even height and width, not " + std::to_string(H) + "x" + std::to_string(W));
+                if (C % 32) return fail(n, -3, at + "its input channels must be a multiple of 32, not " + std::to_string(C) + " (no strided first-layer form)");
+                l.oH = H / 2; l.oW = W / 2;
+                H = l.oH; W = l.oW;
+            }
             C = l.Cout;
         } else if (l.kind == RCN_HIPX_MAXPOOL2) {
             if (flat || i == 0 || (n->L.back().kind != RCN_HIPX_CONV3X3_RELU && !is_bn(n->L.back().kind))) return fail(n, -2, "max-pool must follow a convolution");
@@ -1093,15 +1212,17 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
             n->L.back().pool_follows = true;
             H = l.oH; W = l.oW;
         } else if (l.kind == RCN_HIPX_BN_RELU) {
-            if (i == 0 || n->L.back().kind != RCN_HIPX_CONV3X3) return fail(n, -2, "batch normalisation (RCN_HIPX_BN_RELU) must directly follow a RCN_HIPX_CONV3X3 layer");
+            if (i == 0 || !is_conv_linear(n->L.back().kind)) return fail(n, -2, "batch normalisation (RCN_HIPX_BN_RELU) must directly follow a RCN_HIPX_CONV3X3 layer");
             l.Cout = l.CoutP = C; l.oH = H; l.oW = W; l.K = 1;      // [gamma | beta]: a [W | b] block with K = 1
-        } else if (l.kind == RCN_HIPX_BN_ADD_RELU) {
+        } else if (l.kind == RCN_HIPX_BN_ADD_RELU || l.kind == RCN_HIPX_BN_ADD_RELU_DOWN) {
             // `out` is the distance to the skip's source, the output of layer i - out.  The source needs a gradient buffer that the
             // input-gradient kernel of the layer above it writes in full (backward_layers adds the skip's share behind that launch) and an
             // output that the forward pass writes: a ReLU layer or a pool of this layer's shape, not a convolution whose pool is fused away.
             const int d = layers[i].out;
-            const std::string at = "layer " + std::to_string(i) + " (RCN_HIPX_BN_ADD_RELU): ";
-            if (i == 0 || n->L.back().kind != RCN_HIPX_CONV3X3) return fail(n, -2, at + "it must directly follow a RCN_HIPX_CONV3X3 layer");
+            // RCN_HIPX_BN_ADD_RELU_DOWN: the same, but the source is twice this layer's height and width and may be narrower (option-A shortcut)
+            const bool down = l.kind == RCN_HIPX_BN_ADD_RELU_DOWN;
+            const std::string at = "layer " + std::to_string(i) + (down ? " (RCN_HIPX_BN_ADD_RELU_DOWN): " : " (RCN_HIPX_BN_ADD_RELU): ");
+            if (i == 0 || !is_conv_linear(n->L.back().kind)) return fail(n, -2, at + "it must directly follow a RCN_HIPX_CONV3X3 layer");
             if (d < 2) return fail(n, -1, at + "out is the distance to the skip's source and must be at least 2, not " + std::to_string(d));
             const int src = i - d;
             if (src < 0) return fail(n, -2, at + "the skip's source would lie in front of layer 0 (the net's input has no gradient buffer to add into)");
@@ -1111,7 +1232,13 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
             if (s.kind != RCN_HIPX_CONV3X3_RELU && s.kind != RCN_HIPX_MAXPOOL2 && !is_bn(s.kind))
                 return fail(n, -2, from + "must be a RCN_HIPX_CONV3X3_RELU, RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_MAXPOOL2 layer (a RCN_HIPX_CONV3X3 map is not yet normalised)");
             if (s.pool_follows) return fail(n, -2, from + "has a max-pool behind it: its own output is not written when the two fuse -- the source must be the pool");
-            if (s.oH != l.oH || s.oW != l.oW || s.CoutP != l.CoutP)
+            if (down) {
+                const std::string shape = std::to_string(s.oH) + "x" + std::to_string(s.oW) + "x" + std::to_string(s.CoutP);
+                if (s.oH != 2 * l.oH || s.oW != 2 * l.oW)
+                    return fail(n, -2, from + "has the output shape " + shape + ": a downsampling shortcut needs exactly twice this layer's " + std::to_string(l.oH) + "x" + std::to_string(l.oW));
+                if (s.CoutP > l.CoutP) return fail(n, -2, from + "has more channels (" + std::to_string(s.CoutP) + ") than this layer (" + std::to_string(l.CoutP) + "): the shortcut pads, it does not project");
+                if ((l.CoutP - s.CoutP) % 8) return fail(n, -3, from + "leaves " + std::to_string(l.CoutP - s.CoutP) + " channels to pad: (C - Cs) must be a multiple of 8 (the window starts at a multiple of 4)");
+            } else if (s.oH != l.oH || s.oW != l.oW || s.CoutP != l.CoutP)
                 return fail(n, -2, from + "has another output shape (" + std::to_string(s.oH) + "x" + std::to_string(s.oW) + "x" + std::to_string(s.CoutP) + ", not " +
                                    std::to_string(l.oH) + "x" + std::to_string(l.oW) + "x" + std::to_string(l.CoutP) + "): an identity skip crosses no pool and changes no width");
             if (s.skip_by >= 0) return fail(n, -3, from + "already feeds the skip of layer " + std::to_string(s.skip_by) + ": one skip per source");
@@ -1136,13 +1263,16 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
             l.K = (int)feat; l.H = 1; l.W = 1; l.Cin = (int)feat; l.Cout = layers[i].out; l.CoutP = (l.Cout + 31) / 32 * 32; l.oH = l.oW = 1;
             C = l.Cout; flat = true; H = W = 1;
         } else return fail(n, -1, "unknown layer kind");
-        if (!is_bn(l.kind) && i > 0 && n->L.back().kind == RCN_HIPX_CONV3X3) return fail(n, -2, "layer " + std::to_string(i - 1) + ": a RCN_HIPX_CONV3X3 layer must be followed by RCN_HIPX_BN_RELU or RCN_HIPX_BN_ADD_RELU");
+        if (!is_bn(l.kind) && i > 0 && is_conv_linear(n->L.back().kind))
+            return fail(n, -2, "layer " + std::to_string(i - 1) + ": a " + (n->L.back().kind == RCN_HIPX_CONV3X3_S2 ? "RCN_HIPX_CONV3X3_S2" : "RCN_HIPX_CONV3X3") + " layer must be followed by RCN_HIPX_BN_RELU or RCN_HIPX_BN_ADD_RELU");
         if (has_params(l.kind)) {
             l.w_off = n->n_pad; n->n_pad += (long long)l.K * l.CoutP; l.b_off = n->n_pad; n->n_pad += l.CoutP;
             l.lw_off = n->n_log; n->n_log += (long long)l.K * l.Cout; l.lb_off = n->n_log; n->n_log += l.Cout;
         }
         n->L.push_back(std::move(l));
     }
+    if (n->L.back().kind == RCN_HIPX_CONV3X3_S2)
+        return fail(n, -2, "layer " + std::to_string(n_layers - 1) + " (RCN_HIPX_CONV3X3_S2): it must be followed directly by a batch-normalisation layer, and the last layer must be RCN_HIPX_DENSE (logits)");
     if (n->L.back().kind != RCN_HIPX_DENSE) return fail(n, -2, "the last layer must be RCN_HIPX_DENSE (logits)");
     n->classes = n->L.back().Cout;
     // one reduction launch, and one state pack, take kMaxReduceJobs layers with parameters: refused here, so create, every plan and the

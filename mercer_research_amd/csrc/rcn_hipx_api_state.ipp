@@ -14,7 +14,7 @@ long long round256(long long bytes) { return (bytes + 255) / 256 * 256; }
 // the skip's source for RCN_HIPX_BN_ADD_RELU, the output width otherwise
 int desc_out(const rcn_hipx_net& n, size_t i) {
     const Layer& l = n.L[i];
-    return !has_params(l.kind) ? 0 : l.kind == RCN_HIPX_BN_ADD_RELU ? (int)i - l.skip_src : l.Cout;
+    return !has_params(l.kind) ? 0 : l.skip_src >= 0 ? (int)i - l.skip_src : l.Cout;
 }
 
 // shape, layer offsets, section offsets and body size of a body with `sections` for the layer table of `n`; everything else at its default
