@@ -10,6 +10,9 @@ network BASELINE.json's north_star asks for, on the configs SURVEY.md §8(d) fix
   cifar_res_gap  cifar_res ending as a ResNet does: its last pool and the 2048 -> 256 dense layer replaced by ("global_avgpool",), 8x8x128 -> 128 -> 10
   cifar_resnet14  the CIFAR ResNet of 6n + 2 layers (He et al., section 4.2, option-A shortcuts), n = 2, at widths 32 / 64 / 128: stride-2
                   convolutions and ("bn_add_relu_down", 4) shortcuts between the stages, no pool; 27 layers with parameters, B = 512
+  cifar_bottleneck  bottleneck residual blocks on ("conv1x1_linear", C) layers: conv_linear 128, bn_relu; two blocks of width 128 (1x1 to 32,
+                  3x3 at 32, 1x1 to 128, ("bn_add_relu", 6)); pool; conv1x1_linear 256, bn_relu; two blocks of width 256; pool, global_avgpool,
+                  dense 10; 29 layers with parameters, B = 512; --set pw=1 runs the 1x1 layers on the streaming kernel k_pw
 
 fp32 activations / weights, fp32 MFMA (v_mfma_f32_32x32x2_f32; peak 157.3 TFLOP/s).  Reports achieved TFLOP/s of the whole
 training step (algorithmic 2*MACs of forward + dgrad + wgrad) and its fraction of the fp32 MFMA peak.  The reference has no
@@ -44,6 +47,12 @@ _block = lambda c: (("conv_linear", c), ("bn_relu",), ("conv_linear", c), ("bn_a
 _down = lambda c: (("conv_linear_s2", c), ("bn_relu",), ("conv_linear", c), ("bn_add_relu_down", 4))
 CONFIGS["cifar_resnet14"] = (CONFIGS["cifar"][0], (("conv_linear", 32), ("bn_relu",)) + _block(32) + _block(32) + _down(64) + _block(64) + _down(128) + _block(128) +
                              (("global_avgpool",), ("dense", 10)), CONFIGS["cifar"][2])
+# A bottleneck net at the CIFAR shape: conv_linear 128, bn_relu; two bottleneck blocks of width 128 (conv1x1_linear 32, bn_relu, conv_linear 32,
+# bn_relu, conv1x1_linear 128, ("bn_add_relu", 6)); pool; a plain widening conv1x1_linear 256, bn_relu; two bottleneck blocks of width 256;
+# pool, global_avgpool, dense 10.  29 layers with parameters.
+_bottleneck = lambda c: (("conv1x1_linear", c // 4), ("bn_relu",), ("conv_linear", c // 4), ("bn_relu",), ("conv1x1_linear", c), ("bn_add_relu", 6))
+CONFIGS["cifar_bottleneck"] = (CONFIGS["cifar"][0], (("conv_linear", 128), ("bn_relu",)) + _bottleneck(128) + _bottleneck(128) + (("pool",), ("conv1x1_linear", 256), ("bn_relu",)) +
+                               _bottleneck(256) + _bottleneck(256) + (("pool",), ("global_avgpool",), ("dense", 10)), CONFIGS["cifar"][2])
 F32_MFMA_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD
 BF16_MFMA_PEAK_TFLOPS = 2516.8    # same guide: dense bf16 MFMA = 16x the fp32 MFMA rate (~2.5 PFLOP/s; never the 2:1-sparsity figure)
 HBM_PEAK_GBS = 8000.0

@@ -63,7 +63,7 @@ typedef enum {
                                     pool: -2.  Implicit-GEMM kernels only, in both operand precisions; its input gradient
                                     is one launch over the four parity classes of input pixels (csrc/convnet.hpp).
                                     Not with RCN_HIPX_BF16_STORED (-3), through the batch-normalisation layer behind it      */
-    RCN_HIPX_BN_ADD_RELU_DOWN = 9 /* the end of a residual block that halves the map: y = relu(BatchNorm2d(z) + s') over the
+    RCN_HIPX_BN_ADD_RELU_DOWN = 9, /* the end of a residual block that halves the map: y = relu(BatchNorm2d(z) + s') over the
                                     map z of the RCN_HIPX_CONV3X3 or RCN_HIPX_CONV3X3_S2 layer directly in front of it, s' the
                                     parameter-free "option A" shortcut of the output s (Cs channels) of layer i - out:
                                     s'[b][h][w][c] = s[b][2h][2w][c - lo] for lo <= c < lo + Cs, else 0, lo = (C - Cs) / 2 --
@@ -73,6 +73,19 @@ typedef enum {
                                     must be exactly twice this layer's (-2), Cs <= C (-2) and (C - Cs) % 8 == 0 (-3).
                                     Cs == C is a plain subsample.  A down block behind a layer of C channels: CONV3X3_S2 2C,
                                     BN_RELU, CONV3X3 2C, BN_ADD_RELU_DOWN 4                                                  */
+    RCN_HIPX_CONV1X1 = 10        /* torch.nn.Conv2d(Cin, out, 1): + bias, NO activation, output H x W.  [W | b] with W[K][out],
+                                    K = Cin, then b[out], laid out like every other layer.  Like RCN_HIPX_CONV3X3 it exists in
+                                    front of batch normalisation: the layer directly behind it must be RCN_HIPX_BN_RELU,
+                                    RCN_HIPX_BN_ADD_RELU or RCN_HIPX_BN_ADD_RELU_DOWN (-2; so it is never last and never a
+                                    skip's source).  Cin % 32 != 0: -3 (no gather form: not the first layer of a 1- or
+                                    3-channel input; as layer 0 of an input of a multiple of 32 channels it computes no
+                                    input gradient); out not a positive multiple of 32: -3; behind the dense stage or a
+                                    global average pool: -2.  A bottleneck block behind a layer of C channels: CONV1X1 C/4,
+                                    BN_RELU, CONV3X3 C/4, BN_RELU, CONV1X1 C, BN_ADD_RELU 6; a plain widening: CONV1X1 2C,
+                                    BN_RELU.  Forward pass and input gradient: the implicit-GEMM kernels on the map or,
+                                    option "pw" = 1, the streaming kernel of csrc/convnet_pw.hpp (weights staged once in
+                                    LDS, the input read once where they fit); weight gradient: the KS = 1 implicit-GEMM kernels.
+                                    Not with RCN_HIPX_BF16_STORED (-3), through the batch-normalisation layer behind it      */
 } rcn_hipx_layer_kind;
 
 typedef struct rcn_hipx_layer { int32_t kind; int32_t out; } rcn_hipx_layer;
@@ -128,6 +141,7 @@ int  rcn_hipx_set_overlap(rcn_hipx_net* net, int on);
  *   "fuse_pool_bwd"   RCN_HIPX_FUSE_POOL_BWD   0 | 1   the gradient kernels unpool while staging (1)
  *   "head"            RCN_HIPX_HEAD            0 | 1   the classifier head as one launch (1)
  *   "xcd_remap"       RCN_HIPX_XCD_REMAP       0 | 1   implicit-GEMM weight gradient: XCD-aware block order (0)
+ *   "pw"              RCN_HIPX_PW              0 | 1   1x1 convolution: 1 = the streaming kernel k_pw, 0 = the implicit-GEMM form on the map (0: measured faster)
  *   "pix_per_chunk" "wg_target" "wgh_f32_target" "wgh_target" "wgb_policy" "wgf_policy" "halo_f32_slots"
  *                                                      weight-gradient chunking and the resident-grid size (csrc/rcn_hipx_api.hip: XOptions) */
 int  rcn_hipx_set_option(rcn_hipx_net* net, const char* name, int value);

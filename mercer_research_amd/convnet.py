@@ -16,7 +16,7 @@ from . import _lib
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBX_PATH = os.path.join(HERE, "librcn_hipx.so")
 KIND = {"conv": 0, "pool": 1, "dense_relu": 2, "dense": 3, "conv_linear": 4, "bn_relu": 5, "bn_add_relu": 6, "global_avgpool": 7,
-        "conv_linear_s2": 8, "bn_add_relu_down": 9}
+        "conv_linear_s2": 8, "bn_add_relu_down": 9, "conv1x1_linear": 10}
 
 
 class XLayer(C.Structure):
@@ -515,7 +515,10 @@ class ConvNet:
     like "conv_linear".  ("bn_add_relu_down", d) is relu(BatchNorm2d(z) + s') with s' the parameter-free option-A shortcut of the output s
     (Cs <= C channels, twice this layer's height and width) of the layer d places in front:
     F.pad(s[:, :, ::2, ::2], (0, 0, 0, 0, lo, C - Cs - lo)), lo = (C - Cs) / 2.  The down block of the CIFAR ResNet behind a layer of C
-    channels is ("conv_linear_s2", 2C), ("bn_relu",), ("conv_linear", 2C), ("bn_add_relu_down", 4)."""
+    channels is ("conv_linear_s2", 2C), ("bn_relu",), ("conv_linear", 2C), ("bn_add_relu_down", 4).
+    ("conv1x1_linear", Cout) is Conv2d(Cin, Cout, 1) on a map of Cin % 32 == 0 channels, followed by a bn layer like "conv_linear"; a
+    bottleneck block behind a layer of C channels is ("conv1x1_linear", C/4), ("bn_relu",), ("conv_linear", C/4), ("bn_relu",),
+    ("conv1x1_linear", C), ("bn_add_relu", 6); the option "pw" (set_option) chooses between the implicit GEMM (0, the default) and its streaming kernel (1)."""
 
     def __init__(self, in_shape: Tuple[int, int, int], layers: Sequence[tuple], max_batch: int, device: int = 0):
         import torch
@@ -1249,6 +1252,11 @@ class ConvNet:
             elif l[0] == "conv_linear":
                 i, o = H * W * Cc * es_in, H * W * l[1] * 4
                 total += B * ((i + o) + (0 if first else (i + o)) + (i + o)) + 3 * (9 * Cc * l[1] + l[1]) * 4
+                Cc, first, es_in = l[1], False, 4
+            elif l[0] == "conv1x1_linear":
+                # as conv_linear with a [Cin][Cout] matrix
+                i, o = H * W * Cc * es_in, H * W * l[1] * 4
+                total += B * ((i + o) + (0 if first else (i + o)) + (i + o)) + 3 * (Cc * l[1] + l[1]) * 4
                 Cc, first, es_in = l[1], False, 4
             elif l[0] == "bn_relu":
                 # forward: the map read twice (statistics, apply) and written once; backward: three maps read over its two passes (x and dy

@@ -13,6 +13,7 @@
 #include "convnet.hpp"
 #include "convnet_bf16.hpp"
 #include "convnet_halo.hpp"
+#include "convnet_pw.hpp"
 
 namespace rcnx {
 
@@ -35,6 +36,8 @@ struct XOptions {
     int wgb_policy = 1;       // "wgb_policy"      RCN_HIPX_WGB_POLICY      bf16 implicit-GEMM weight gradient: narrower tiles / shorter chunks below 2 waves per SIMD
     int wgf_policy = 1;       // "wgf_policy"      RCN_HIPX_WGF_POLICY      fp32: the same
     int halo_f32_slots = 0;   // "halo_f32_slots"  RCN_HIPX_HALO_F32_SLOTS  resident workgroups assumed for the looping kernels (0: asked from the runtime)
+    int pw = 0;               // "pw"              RCN_HIPX_PW              1x1 convolution: 1 = the streaming kernel k_pw, 0 = the implicit-GEMM form (the default in both
+                              //                                            precisions: measured faster over the cifar_bottleneck step)
 };
 struct XOptDesc { const char* name; const char* env; int XOptions::*field; int lo, hi; };
 inline const XOptDesc kXOptTable[] = {
@@ -53,6 +56,7 @@ inline const XOptDesc kXOptTable[] = {
     {"wgb_policy", "RCN_HIPX_WGB_POLICY", &XOptions::wgb_policy, 0, 1},
     {"wgf_policy", "RCN_HIPX_WGF_POLICY", &XOptions::wgf_policy, 0, 1},
     {"halo_f32_slots", "RCN_HIPX_HALO_F32_SLOTS", &XOptions::halo_f32_slots, 0, 1 << 20},
+    {"pw", "RCN_HIPX_PW", &XOptions::pw, 0, 1},
 };
 inline void seed_options(XOptions& o) {
     for (const XOptDesc& d : kXOptTable) {
@@ -379,8 +383,9 @@ inline WgradChoice select_wgrad(const Selection& sel, const ConvShape& s, int ks
     return c;
 }
 
-inline std::string describe(const WgradChoice& c, const ConvShape& s, int ks, bool pooled_dz) {
-    const std::string head = strf("  wgrad %s %dx%dx%d->%d%s: ", ks == 3 ? "conv3x3" : "dense", s.H, s.W, s.Cin, s.Cout, pooled_dz ? " pooled-dZ" : "");
+// (on_map: a 1x1 convolution, the KS = 1 kernels with rows walking the H x W map)
+inline std::string describe(const WgradChoice& c, const ConvShape& s, int ks, bool pooled_dz, bool on_map = false) {
+    const std::string head = strf("  wgrad %s %dx%dx%d->%d%s: ", ks == 3 ? "conv3x3" : on_map ? "conv1x1" : "dense", s.H, s.W, s.Cin, s.Cout, pooled_dz ? " pooled-dZ" : "");
     switch (c.kernel) {
     case WgradKernel::conv1_wgrad_f32: return head + strf("k_conv1_wgrad_f32<%d, %d>, %d chunks", s.Cin, c.tile_w, c.chunks);
     case WgradKernel::halo_f32: return head + strf("k_wgrad3x3_halo_f32<%d>, %d chunks x %lld tiles", c.tile_w, c.chunks, c.tiles);
@@ -469,6 +474,52 @@ inline WgradChoice select_wgrad_s2(const Selection& sel, const ConvShapeS2& s) {
 inline std::string describe(const WgradChoice& c, const ConvShapeS2& s) {
     const std::string head = strf("  wgrad conv3x3/2 %dx%dx%d->%dx%dx%d: ", s.H, s.W, s.Cin, s.H / 2, s.W / 2, s.Cout);
     return c.kernel == WgradKernel::wgrad_bf16 ? head + strf("k_conv_wgrad_bf16<3, %d, 3, ConvShapeS2>, %d chunks", c.bn, c.chunks) : head + strf("k_conv_wgrad<3, tile, %d, ConvShapeS2>, %d chunks", c.bn, c.chunks);
+}
+
+// ---- RCN_HIPX_CONV1X1: the forward pass (epi 1) and the input gradient (epi 0 / 3) of a 1x1 convolution on an H x W map, s.Cin the
+// contraction and s.Cout the columns of the launch (the input gradient: the layer's Cout and Cin).  Option pw = 1: the streaming kernel
+// k_pw (convnet_pw.hpp) -- the whole [K][nb] weight slice in LDS, nb the widest multiple of 32 that divides Cout, fits the slice and the
+// accumulators, and `passes` = Cout / nb reads of the input.  Otherwise (pw = 0, the measured default; or a contraction no 32-wide slice
+// holds) the implicit-GEMM form: select_conv's choice for ks = 1 on the map, split-K as splitk_z decides; `gemm` is that choice.
+struct PwChoice {
+    const char* error = nullptr;    // or: the layer cannot run (status -3 with this message)
+    bool stream = false;            // k_pw; false: the implicit-GEMM form in `gemm`
+    bool bf16 = false;              // operands rounded to bf16
+    int nb = 32, passes = 1;        // k_pw: column slice and workgroup columns (reads of the input)
+    long long items = 0;            // k_pw: row blocks of kPwRows rows, dealt over the resident grid
+    long long grid = 0;             // k_pw: workgroups per column slice where the option halo_f32_slots fixes them (0: as many as the runtime says the chip holds)
+    ConvChoice gemm;
+};
+inline PwChoice select_pw(const Selection& sel, const ConvShape& s, int epi) {
+    PwChoice c;
+    const auto refuse = [&c](const char* why) { c.error = why; return c; };
+    if (s.Cin % 32 || s.Cout % 32) return refuse("a 1x1 convolution's input and output channels must be multiples of 32");
+    if (epi != 0 && epi != 1 && epi != 3) return refuse("internal: a 1x1 convolution has epilogues 0, 1 and 3");
+    c.bf16 = sel.precision == RCN_HIPX_BF16;
+    c.items = ((long long)s.N * s.H * s.W + kPwRows - 1) / kPwRows;
+    if (sel.opt.pw && (long long)s.Cin * 32 <= pw_slice_elems(c.bf16)) {
+        // (64-bit row offsets in the kernel: no bound on M)
+        int nt = 0;
+        for (int t = 1; t <= kPwMaxNB / 32; ++t)
+            if ((s.Cout / 32) % t == 0 && (long long)s.Cin * 32 * t <= pw_slice_elems(c.bf16)) nt = t;
+        c.stream = true; c.nb = 32 * nt; c.passes = s.Cout / c.nb;
+        if (sel.opt.halo_f32_slots > 0) { c.grid = sel.opt.halo_f32_slots / c.passes; if (c.grid < 1) c.grid = 1; if (c.grid > c.items) c.grid = c.items; }
+        return c;
+    }
+    c.gemm = select_conv(sel, s, 1, epi, false, false, Store{});
+    c.error = c.gemm.error;
+    return c;
+}
+inline std::string describe(const PwChoice& c, const ConvShape& s, int epi) {
+    const std::string head = strf("  conv1x1 %dx%dx%d->%d epi %d: ", s.H, s.W, s.Cin, s.Cout, epi);
+    if (c.stream)
+        return head + strf("k_pw<%s, %d>, weights [%d][%d] staged once in LDS, %lld row blocks of %d rows on %s, input read %s", c.bf16 ? "bf16" : "f32", c.nb / 32, s.Cin, c.nb,
+                           c.items, kPwRows, c.grid ? (std::to_string(c.grid) + " looping workgroups per slice").c_str() : "a resident grid",
+                           c.passes == 1 ? "once" : (std::to_string(c.passes) + " times (" + std::to_string(c.passes) + " column slices)").c_str());
+    const int bn = c.gemm.bn;
+    const long long tiles = ((long long)s.N * s.H * s.W + kBM - 1) / kBM;
+    return head + strf("%s<1, tile, %d>", c.gemm.bf16 ? "k_conv_fwd_bf16" : "k_conv_fwd", bn) + (c.gemm.Z > 1 ? " split-K " + std::to_string(c.gemm.Z) + " + k_splitk_epilogue" : std::string()) +
+           strf(", %d-wide column blocks, %lld row tiles, input read %d times", bn, tiles, s.Cout / bn);
 }
 
 // ---- the step's update launch (convnet_update.hpp)

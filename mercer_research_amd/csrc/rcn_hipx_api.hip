@@ -32,6 +32,7 @@
 #include "convnet_state.hpp"
 #include "convnet_bn.hpp"
 #include "convnet_gap.hpp"
+#include "convnet_pw.hpp"
 
 using namespace rcnx;
 
@@ -68,11 +69,16 @@ struct LayerShape {
     // adds in front of its ReLU, and -- in that source -- the layer that adds its output; -1: none
     int skip_src = -1, skip_by = -1;
 };
-// the kinds by what the walks ask of them: a 3x3 convolution (with or without ReLU), and a layer whose W is a matrix with a tap-flipped
+// the kinds by what the walks ask of them: a 3x3 convolution (with or without ReLU; NOT the 1x1 convolution: is_conv means "3x3" wherever
+// it is asked -- filter_size and on_map below say the rest), and a layer whose W is a matrix with a tap-flipped
 // copy and bf16 operand copies (every layer with a [W | b] block but batch normalisation, whose block is [gamma | beta])
 inline bool is_conv(int kind) { return kind == RCN_HIPX_CONV3X3_RELU || kind == RCN_HIPX_CONV3X3 || kind == RCN_HIPX_CONV3X3_S2; }
-// a bias-only convolution in front of batch normalisation, of either stride: no activation, no ReLU gate of its own, BN must follow
-inline bool is_conv_linear(int kind) { return kind == RCN_HIPX_CONV3X3 || kind == RCN_HIPX_CONV3X3_S2; }
+// a bias-only convolution in front of batch normalisation, of either stride or filter size: no activation, no ReLU gate of its own, BN must follow
+inline bool is_conv_linear(int kind) { return kind == RCN_HIPX_CONV3X3 || kind == RCN_HIPX_CONV3X3_S2 || kind == RCN_HIPX_CONV1X1; }
+// a layer whose GEMM rows are the pixels of a map (a convolution of either filter size), not the samples of a batch (a dense layer)
+inline bool on_map(int kind) { return is_conv(kind) || kind == RCN_HIPX_CONV1X1; }
+// the filter size of a kind with a matrix: 3 for the 3x3 convolutions, 1 for the 1x1 convolution and the dense layers
+inline int filter_size(int kind) { return is_conv(kind) ? 3 : 1; }
 // batch normalisation, with or without a skip added in front of its ReLU: one [gamma | beta] block, statistics and buffers either way
 inline bool is_bn(int kind) { return kind == RCN_HIPX_BN_RELU || kind == RCN_HIPX_BN_ADD_RELU || kind == RCN_HIPX_BN_ADD_RELU_DOWN; }
 // a layer with a parameter block ([W | b] or [gamma | beta]): every kind but the two pools, which also take no `out`
@@ -279,11 +285,11 @@ int bf16_operand(rcn_hipx_net* n, const float* Wk, int K, int Cout, const __bf16
 // Y = act(conv(X) + b): the kernel select_conv chooses (convnet_select.hpp).  Split-K launches leave raw partial tiles in `skbuf` that
 // k_splitk_epilogue sums in order.
 int launch_conv(rcn_hipx_net* n, const float* X, const float* Wk, const float* bias, float* Y, ConvShape s, int ks, int epi, uint8_t* pool_idx = nullptr,
-                const PooledGrad* pin = nullptr, bool force_fp32 = false, const __bf16* wb_ready = nullptr, Store st = Store{}) {
+                const PooledGrad* pin = nullptr, bool force_fp32 = false, const __bf16* wb_ready = nullptr, Store st = Store{}, const std::string* note = nullptr) {
     const bool pooled = pin != nullptr;
     const ConvChoice c = select_conv(*n, s, ks, epi, pooled, force_fp32, st);
     if (c.error) return fail(n, -3, c.error);
-    if (dry_note(n, "%s", describe(c, s, ks, epi, pooled).c_str())) return 0;
+    if (dry_note(n, "%s", (note ? *note : describe(c, s, ks, epi, pooled)).c_str())) return 0;      // (note: the plan line of a caller's own selector, launch_pw)
     const long long M = (long long)s.N * s.H * s.W;
     float* out = Y;
     if (c.Z > 1) {
@@ -366,12 +372,12 @@ int launch_conv(rcn_hipx_net* n, const float* X, const float* Wk, const float* b
 
 // the partial [W | b] tiles of a layer's weight gradient into its slab (n->slab_sel), by the kernel select_wgrad chooses; *chunks_out: how many
 // st.x16: X is a bf16 tensor; st.y16: dZ (and a pooled-resolution dZ) is
-int launch_wgrad(rcn_hipx_net* n, const float* X, const float* dZ, ConvShape s, int ks, int* chunks_out, const PooledGrad* pdz = nullptr, Store st = Store{}) {
+int launch_wgrad(rcn_hipx_net* n, const float* X, const float* dZ, ConvShape s, int ks, int* chunks_out, const PooledGrad* pdz = nullptr, Store st = Store{}, bool map1x1 = false) {
     const bool pooled = pdz != nullptr;
     const WgradChoice c = select_wgrad(*n, s, ks, pooled, st);
     if (c.error) return fail(n, -3, c.error);
     *chunks_out = c.chunks;
-    if (dry_note(n, "%s", describe(c, s, ks, pooled).c_str())) return 0;
+    if (dry_note(n, "%s", describe(c, s, ks, pooled, map1x1).c_str())) return 0;
     const int K = ks * ks * s.Cin;
     XTRY(n, scratch_ensure(n, *n->slab_sel, (size_t)c.chunks * (K + 1) * s.Cout * sizeof(float)));
     float* const slab = (float*)n->slab_sel->p;
@@ -498,6 +504,68 @@ int launch_wgrad_s2(rcn_hipx_net* n, const float* X, const float* dZ, ConvShapeS
     return 0;
 }
 
+// hipFuncAttributeMaxDynamicSharedMemorySize of a k_pw instantiation, set once per (device, kernel): a function's attribute belongs to
+// the device's copy of it, so a net on a second device asks again (the net's device is current: every entry point holds a Dev)
+hipError_t pw_allow_lds(rcn_hipx_net* n, const void* kernel) {
+    static std::mutex mu;
+    static std::map<std::pair<int, const void*>, hipError_t> done;
+    const std::lock_guard<std::mutex> lock(mu);
+    const std::pair<int, const void*> key{n->device, kernel};
+    auto it = done.find(key);
+    if (it != done.end()) return it->second;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    done.emplace(key, e);
+    return e;
+}
+// workgroups of a k_pw instantiation (256 threads, `lds` bytes of dynamic LDS) the device holds at once; asked from the runtime once per
+// (kernel, LDS size), as resident_slots does for the kernels with static LDS
+long long pw_slots(rcn_hipx_net* n, const void* kernel, size_t lds) {
+    static std::mutex mu;
+    static std::map<std::tuple<int, const void*, size_t>, long long> cache;
+    const std::lock_guard<std::mutex> lock(mu);
+    const std::tuple<int, const void*, size_t> key{n->device, kernel, lds};
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kThreads, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, n->device) != hipSuccess || cus < 1) cus = 256;
+    const long long v = (long long)per_cu * cus;
+    cache.emplace(key, v);
+    return v;
+}
+
+// ---- RCN_HIPX_CONV1X1 (convnet_select.hpp: select_pw): Y = X W + b (epi 1) or the input gradient dZ Wt (epi 0 raw, 3 gated by `bias`, a tensor
+// shaped like Y) over the H x W map; every element of Y is written exactly once.  s.Cin: the contraction, s.Cout: the launch's columns.
+int launch_pw(rcn_hipx_net* n, const float* X, const float* Wk, const float* bias, float* Y, ConvShape s, int epi, const __bf16* WB) {
+    const PwChoice c = select_pw(*n, s, epi);
+    if (c.error) return fail(n, -3, c.error);
+    const std::string line = describe(c, s, epi);
+    if (!c.stream) return launch_conv(n, X, Wk, bias, Y, s, 1, epi, nullptr, nullptr, false, WB, Store{}, &line);
+    if (dry_note(n, "%s", line.c_str())) return 0;
+    if (c.bf16) RTRY(bf16_operand(n, Wk, s.Cin, s.Cout, &WB));
+    const long long M = (long long)s.N * s.H * s.W;
+    const size_t lds = pw_lds_bytes(c.bf16, s.Cin, c.nb);
+    const void* const W = c.bf16 ? (const void*)WB : (const void*)Wk;
+    int status = 0;
+    with_bool(c.bf16, [&](auto B16) { with_const<1, 2, 3, 4, 5, 6, 7, 8>(c.nb / 32, [&](auto NT) { with_const<1, 3, 0>(epi, [&](auto EPI) {
+        auto* const kernel = k_pw<CV(B16), CV(NT), CV(EPI)>;
+        // more than 64 KB of dynamic LDS has to be asked for (at most 80 KB here), once per (device, kernel)
+        const hipError_t attr = pw_allow_lds(n, (const void*)kernel);
+        if (attr != hipSuccess) { status = fail(n, -4, std::string("hipFuncSetAttribute(k_pw): ") + hipGetErrorString(attr)); return; }
+        // the resident grid: as many workgroups as the chip holds of this kernel with this much LDS, dealt over the column slices
+        long long gx = c.grid;
+        if (!gx) {
+            gx = pw_slots(n, (const void*)kernel, lds) / c.passes;
+            if (gx < 1) gx = 1;
+            if (gx > c.items) gx = c.items;
+        }
+        hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)c.passes), dim3(kThreads), lds, n->stream, X, W, bias, Y, M, s.Cin, s.Cout);
+    }); }); });
+    if (status) return status;
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+
 float* P(rcn_hipx_net* n, long long off) { return (float*)n->params.p + off; }
 
 int ensure_batch(rcn_hipx_net* n, int B) {
@@ -549,8 +617,8 @@ int prep_bf16_weights(rcn_hipx_net* n) {
         for (size_t i = 1; i < n->L.size(); ++i) {
             Layer& l = n->L[i];
             if (!has_matrix(l.kind)) continue;
-            const int ks = is_conv(l.kind) ? 3 : 1;
-            const long long cin = is_conv(l.kind) ? l.Cin : l.K;
+            const int ks = filter_size(l.kind);
+            const long long cin = l.K / (ks * ks);
             const long long Kf = (long long)ks * ks * cin, Kpf = (Kf + 31) / 32 * 32;                 // forward: [CoutP][Kpf]
             const long long Kb = (long long)ks * ks * l.CoutP, Kpb = (Kb + 31) / 32 * 32;              // input gradient: [cin][Kpb]
             l.wbf_off = off; off += (long long)l.CoutP * Kpf;
@@ -564,8 +632,8 @@ int prep_bf16_weights(rcn_hipx_net* n) {
         for (size_t i = 1; i < n->L.size(); ++i) {
             Layer& l = n->L[i];
             if (!has_matrix(l.kind)) continue;
-            const int ks = is_conv(l.kind) ? 3 : 1;
-            const long long cin = is_conv(l.kind) ? l.Cin : l.K;
+            const int ks = filter_size(l.kind);
+            const long long cin = l.K / (ks * ks);
             const long long Kf = (long long)ks * ks * cin, Kpf = (Kf + 31) / 32 * 32, Kb = (long long)ks * ks * l.CoutP, Kpb = (Kb + 31) / 32 * 32;
             PrepJob& a = n->prep.j[n->prep.njobs++];
             a = PrepJob{(const float*)P(n, l.w_off), (__bf16*)n->wb16.p + l.wbf_off, (int)Kf, l.CoutP, (int)Kpf, (int)blocks};
@@ -755,6 +823,7 @@ int forward(rcn_hipx_net* n, const float* x, int B, size_t n_layers = (size_t)-1
             // bias only (epilogue 1), no conv+pool fusion: what follows is batch normalisation, on an fp32 map
             if (n->store16) return fail(n, -3, kBnStoreGap);
             if (l.kind == RCN_HIPX_CONV3X3_S2) RTRY(launch_conv_s2(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShapeS2{B, l.H, l.W, l.Cin, l.CoutP}, 1, wb_of(n, l.wbf_off)));
+            else if (l.kind == RCN_HIPX_CONV1X1) RTRY(launch_pw(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShape{B, l.H, l.W, l.Cin, l.CoutP}, 1, wb_of(n, l.wbf_off)));
             else RTRY(launch_conv(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShape{B, l.H, l.W, l.Cin, l.CoutP}, 3, 1, nullptr, nullptr, false, wb_of(n, l.wbf_off)));
         } else if (is_bn(l.kind)) {
             if (n->store16) return fail(n, -3, kBnStoreGap);
@@ -914,8 +983,10 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             RTRY(launch_bn_backward(n, (size_t)i, B, l.pool_follows || gated[i], grad, apply));
             continue;
         }
-        const bool conv = is_conv(l.kind), strided = l.kind == RCN_HIPX_CONV3X3_S2;
-        const int ks = conv ? 3 : 1;
+        // conv: the layer's rows are the pixels of a map (a 3x3 or a 1x1 convolution); pw: the 1x1 convolution, whose forward pass and input
+        // gradient have their own selector (launch_pw) and whose weight gradient is the KS = 1 kernels' with rows walking the H x W map
+        const bool conv = on_map(l.kind), strided = l.kind == RCN_HIPX_CONV3X3_S2, pw = l.kind == RCN_HIPX_CONV1X1;
+        const int ks = filter_size(l.kind);
         const ConvShape s = conv ? ConvShape{B, l.H, l.W, l.Cin, l.CoutP} : ConvShape{B, 1, 1, l.K, l.CoutP};      // (H x W: the layer's INPUT map; a strided layer's output is l.oH x l.oW)
         const long long M = (long long)s.N * l.oH * l.oW;
         // dZ: gradient wrt the pre-activation
@@ -945,6 +1016,8 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             const bool gate = below.kind == RCN_HIPX_CONV3X3_RELU || below.kind == RCN_HIPX_DENSE_RELU || (is_bn(below.kind) && conv);
             // (a strided layer: one launch over the four parity classes of the input pixels writes ALL of dout[i - 1], every element once)
             if (strided) RTRY(launch_dgrad_s2(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, ConvShapeS2T{s.N, s.H, s.W, s.Cout, s.Cin}, gate ? 3 : 0, wb_of(n, l.wbb_off)));
+            // (a 1x1 layer: k_pw, or the implicit GEMM on the map, writes ALL of dout[i - 1], every element once -- what the skip's add below rests on)
+            else if (pw) RTRY(launch_pw(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, ConvShape{s.N, s.H, s.W, s.Cout, s.Cin}, gate ? 3 : 0, wb_of(n, l.wbb_off)));
             else RTRY(launch_conv(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, ConvShape{s.N, s.H, s.W, s.Cout, s.Cin}, ks, gate ? 3 : 0,
                              nullptr, pooled[i].dP ? &pooled[i] : nullptr, false, wb_of(n, l.wbb_off), Store{stage16(n, i), stage16(n, i - 1)}));
             gated[i - 1] = gate;
@@ -962,7 +1035,7 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
         if (on_side) n->stream = n->side;
         n->slab_sel = &l.slab;
         if (strided) RTRY(launch_wgrad_s2(n, in, dZ, ConvShapeS2{s.N, s.H, s.W, s.Cin, s.Cout}, &chunks));
-        else RTRY(launch_wgrad(n, in, dZ, s, ks, &chunks, pooled[i].dP ? &pooled[i] : nullptr, Store{stage16(n, i - 1), stage16(n, i)}));
+        else RTRY(launch_wgrad(n, in, dZ, s, ks, &chunks, pooled[i].dP ? &pooled[i] : nullptr, Store{stage16(n, i - 1), stage16(n, i)}, pw));
         RTRY(reduce_slab(n, (size_t)i, chunks, ks, s, grad, apply));
         n->stream = main_s;
     }
@@ -1073,8 +1146,8 @@ int refresh_flipped(rcn_hipx_net* n) {
     for (size_t i = 1; i < n->L.size(); ++i) {
         const Layer& l = n->L[i];
         if (!has_matrix(l.kind)) continue;
-        const int ks = is_conv(l.kind) ? 3 : 1;
-        const int cin = is_conv(l.kind) ? l.Cin : l.K;
+        const int ks = filter_size(l.kind);
+        const int cin = l.K / (ks * ks);
         const long long wn = (long long)l.K * l.CoutP;
         hipLaunchKernelGGL(k_flip_weights, dim3(grid1d(wn, 256)), dim3(256), 0, n->stream, (const float*)P(n, l.w_off), (float*)n->wt.p + l.w_off, ks, cin, l.CoutP);
     }
@@ -1188,7 +1261,18 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
         l.kind = layers[i].kind; l.H = H; l.W = W; l.Cin = C;
         if (i > 0 && n->L.back().kind == RCN_HIPX_CONV3X3_S2 && !is_bn(l.kind))
             return fail(n, -2, "layer " + std::to_string(i - 1) + " (RCN_HIPX_CONV3X3_S2): it must be followed directly by a batch-normalisation layer (RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_BN_ADD_RELU_DOWN)");
-        if (is_conv(l.kind)) {
+        if (i > 0 && n->L.back().kind == RCN_HIPX_CONV1X1 && !is_bn(l.kind))
+            return fail(n, -2, "layer " + std::to_string(i - 1) + " (RCN_HIPX_CONV1X1): it must be followed directly by a batch-normalisation layer (RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_BN_ADD_RELU_DOWN)");
+        if (l.kind == RCN_HIPX_CONV1X1) {
+            // torch.nn.Conv2d(C, out, 1): a [W | b] block with K = C on the H x W map, in front of batch normalisation.  No gather form:
+            // the rows are whole 16-byte pieces of a map of a multiple of 32 channels (so not the first layer of a 1- or 3-channel input)
+            const std::string at = "layer " + std::to_string(i) + " (RCN_HIPX_CONV1X1): ";
+            if (flat) return fail(n, -2, at + "convolution after a dense layer or a global average pool");
+            if (layers[i].out < 32 || layers[i].out % 32) return fail(n, -3, at + "conv output channels must be a positive multiple of 32");
+            if (C % 32) return fail(n, -3, at + "its input channels must be a multiple of 32, not " + std::to_string(C) + " (no first-layer gather form)");
+            l.Cout = l.CoutP = layers[i].out; l.oH = H; l.oW = W; l.K = C;
+            C = l.Cout;
+        } else if (is_conv(l.kind)) {
             if (flat) return fail(n, -2, l.kind == RCN_HIPX_CONV3X3_S2 ? "layer " + std::to_string(i) + " (RCN_HIPX_CONV3X3_S2): convolution after a dense layer or a global average pool"
                                                                        : std::string("convolution after a dense layer or a global average pool"));
             if (layers[i].out < 32 || layers[i].out % 32)
@@ -1212,7 +1296,7 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
             n->L.back().pool_follows = true;
             H = l.oH; W = l.oW;
         } else if (l.kind == RCN_HIPX_BN_RELU) {
-            if (i == 0 || !is_conv_linear(n->L.back().kind)) return fail(n, -2, "batch normalisation (RCN_HIPX_BN_RELU) must directly follow a RCN_HIPX_CONV3X3 layer");
+            if (i == 0 || !is_conv_linear(n->L.back().kind)) return fail(n, -2, "batch normalisation (RCN_HIPX_BN_RELU) must directly follow a RCN_HIPX_CONV3X3 layer (of either stride) or a RCN_HIPX_CONV1X1 layer");
             l.Cout = l.CoutP = C; l.oH = H; l.oW = W; l.K = 1;      // [gamma | beta]: a [W | b] block with K = 1
         } else if (l.kind == RCN_HIPX_BN_ADD_RELU || l.kind == RCN_HIPX_BN_ADD_RELU_DOWN) {
             // `out` is the distance to the skip's source, the output of layer i - out.  The source needs a gradient buffer that the
@@ -1222,7 +1306,7 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
             // RCN_HIPX_BN_ADD_RELU_DOWN: the same, but the source is twice this layer's height and width and may be narrower (option-A shortcut)
             const bool down = l.kind == RCN_HIPX_BN_ADD_RELU_DOWN;
             const std::string at = "layer " + std::to_string(i) + (down ? " (RCN_HIPX_BN_ADD_RELU_DOWN): " : " (RCN_HIPX_BN_ADD_RELU): ");
-            if (i == 0 || !is_conv_linear(n->L.back().kind)) return fail(n, -2, at + "it must directly follow a RCN_HIPX_CONV3X3 layer");
+            if (i == 0 || !is_conv_linear(n->L.back().kind)) return fail(n, -2, at + "it must directly follow a RCN_HIPX_CONV3X3 layer (of either stride) or a RCN_HIPX_CONV1X1 layer");
             if (d < 2) return fail(n, -1, at + "out is the distance to the skip's source and must be at least 2, not " + std::to_string(d));
             const int src = i - d;
             if (src < 0) return fail(n, -2, at + "the skip's source would lie in front of layer 0 (the net's input has no gradient buffer to add into)");
@@ -1264,13 +1348,15 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
             C = l.Cout; flat = true; H = W = 1;
         } else return fail(n, -1, "unknown layer kind");
         if (!is_bn(l.kind) && i > 0 && is_conv_linear(n->L.back().kind))
-            return fail(n, -2, "layer " + std::to_string(i - 1) + ": a " + (n->L.back().kind == RCN_HIPX_CONV3X3_S2 ? "RCN_HIPX_CONV3X3_S2" : "RCN_HIPX_CONV3X3") + " layer must be followed by RCN_HIPX_BN_RELU or RCN_HIPX_BN_ADD_RELU");
+            return fail(n, -2, "layer " + std::to_string(i - 1) + ": a " + (n->L.back().kind == RCN_HIPX_CONV3X3_S2 ? "RCN_HIPX_CONV3X3_S2" : n->L.back().kind == RCN_HIPX_CONV1X1 ? "RCN_HIPX_CONV1X1" : "RCN_HIPX_CONV3X3") + " layer must be followed by RCN_HIPX_BN_RELU or RCN_HIPX_BN_ADD_RELU");
         if (has_params(l.kind)) {
             l.w_off = n->n_pad; n->n_pad += (long long)l.K * l.CoutP; l.b_off = n->n_pad; n->n_pad += l.CoutP;
             l.lw_off = n->n_log; n->n_log += (long long)l.K * l.Cout; l.lb_off = n->n_log; n->n_log += l.Cout;
         }
         n->L.push_back(std::move(l));
     }
+    if (n->L.back().kind == RCN_HIPX_CONV1X1)
+        return fail(n, -2, "layer " + std::to_string(n_layers - 1) + " (RCN_HIPX_CONV1X1): it must be followed directly by a batch-normalisation layer, and the last layer must be RCN_HIPX_DENSE (logits)");
     if (n->L.back().kind == RCN_HIPX_CONV3X3_S2)
         return fail(n, -2, "layer " + std::to_string(n_layers - 1) + " (RCN_HIPX_CONV3X3_S2): it must be followed directly by a batch-normalisation layer, and the last layer must be RCN_HIPX_DENSE (logits)");
     if (n->L.back().kind != RCN_HIPX_DENSE) return fail(n, -2, "the last layer must be RCN_HIPX_DENSE (logits)");
