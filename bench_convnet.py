@@ -13,6 +13,9 @@ network BASELINE.json's north_star asks for, on the configs SURVEY.md §8(d) fix
   cifar_bottleneck  bottleneck residual blocks on ("conv1x1_linear", C) layers: conv_linear 128, bn_relu; two blocks of width 128 (1x1 to 32,
                   3x3 at 32, 1x1 to 128, ("bn_add_relu", 6)); pool; conv1x1_linear 256, bn_relu; two blocks of width 256; pool, global_avgpool,
                   dense 10; 29 layers with parameters, B = 512; --set pw=1 runs the 1x1 layers on the streaming kernel k_pw
+  cifar_sep       depthwise-separable layers on ("dwconv_linear",) and ("conv1x1_linear", C): conv_linear 64, bn_relu; a residual separable
+                  block at 64, a separable layer to 128, pool; the same at 128 and to 256, pool; two residual separable blocks at 256;
+                  global_avgpool, dense 10; 27 layers with parameters, B = 512
 
 fp32 activations / weights, fp32 MFMA (v_mfma_f32_32x32x2_f32; peak 157.3 TFLOP/s).  Reports achieved TFLOP/s of the whole
 training step (algorithmic 2*MACs of forward + dgrad + wgrad) and its fraction of the fp32 MFMA peak.  The reference has no
@@ -53,6 +56,13 @@ CONFIGS["cifar_resnet14"] = (CONFIGS["cifar"][0], (("conv_linear", 32), ("bn_rel
 _bottleneck = lambda c: (("conv1x1_linear", c // 4), ("bn_relu",), ("conv_linear", c // 4), ("bn_relu",), ("conv1x1_linear", c), ("bn_add_relu", 6))
 CONFIGS["cifar_bottleneck"] = (CONFIGS["cifar"][0], (("conv_linear", 128), ("bn_relu",)) + _bottleneck(128) + _bottleneck(128) + (("pool",), ("conv1x1_linear", 256), ("bn_relu",)) +
                                _bottleneck(256) + _bottleneck(256) + (("pool",), ("global_avgpool",), ("dense", 10)), CONFIGS["cifar"][2])
+# A depthwise-separable net at the CIFAR shape: conv_linear 64, bn_relu; a residual separable block (dwconv_linear, bn_relu, conv1x1_linear C,
+# ("bn_add_relu", 4)) at 64 and a separable layer (dwconv_linear, bn_relu, conv1x1_linear C', bn_relu) to 128; pool; the same at 128 and to 256;
+# pool; two residual separable blocks at 256; global_avgpool, dense 10.  27 layers with parameters.
+_sep = lambda c: (("dwconv_linear",), ("bn_relu",), ("conv1x1_linear", c), ("bn_relu",))
+_sep_res = lambda c: (("dwconv_linear",), ("bn_relu",), ("conv1x1_linear", c), ("bn_add_relu", 4))
+CONFIGS["cifar_sep"] = (CONFIGS["cifar"][0], (("conv_linear", 64), ("bn_relu",)) + _sep_res(64) + _sep(128) + (("pool",),) + _sep_res(128) + _sep(256) + (("pool",),) +
+                        _sep_res(256) + _sep_res(256) + (("global_avgpool",), ("dense", 10)), CONFIGS["cifar"][2])
 F32_MFMA_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD
 BF16_MFMA_PEAK_TFLOPS = 2516.8    # same guide: dense bf16 MFMA = 16x the fp32 MFMA rate (~2.5 PFLOP/s; never the 2:1-sparsity figure)
 HBM_PEAK_GBS = 8000.0

@@ -16,7 +16,7 @@ from . import _lib
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBX_PATH = os.path.join(HERE, "librcn_hipx.so")
 KIND = {"conv": 0, "pool": 1, "dense_relu": 2, "dense": 3, "conv_linear": 4, "bn_relu": 5, "bn_add_relu": 6, "global_avgpool": 7,
-        "conv_linear_s2": 8, "bn_add_relu_down": 9, "conv1x1_linear": 10}
+        "conv_linear_s2": 8, "bn_add_relu_down": 9, "conv1x1_linear": 10, "dwconv_linear": 11}
 
 
 class XLayer(C.Structure):
@@ -518,7 +518,11 @@ class ConvNet:
     channels is ("conv_linear_s2", 2C), ("bn_relu",), ("conv_linear", 2C), ("bn_add_relu_down", 4).
     ("conv1x1_linear", Cout) is Conv2d(Cin, Cout, 1) on a map of Cin % 32 == 0 channels, followed by a bn layer like "conv_linear"; a
     bottleneck block behind a layer of C channels is ("conv1x1_linear", C/4), ("bn_relu",), ("conv_linear", C/4), ("bn_relu",),
-    ("conv1x1_linear", C), ("bn_add_relu", 6); the option "pw" (set_option) chooses between the implicit GEMM (0, the default) and its streaming kernel (1)."""
+    ("conv1x1_linear", C), ("bn_add_relu", 6); the option "pw" (set_option) chooses between the implicit GEMM (0, the default) and its streaming kernel (1).
+    ("dwconv_linear",) is Conv2d(C, C, 3, padding=1, groups=C), the depthwise 3x3 convolution, on a map of C % 32 == 0 channels, followed by a
+    bn layer like "conv_linear" (("dwconv_linear", C) says the same; any other width is refused); fp32 arithmetic in either precision mode.
+    A separable layer is ("dwconv_linear",), ("bn_relu",), ("conv1x1_linear", C'), ("bn_relu",); a residual separable block behind a layer
+    of C channels is ("dwconv_linear",), ("bn_relu",), ("conv1x1_linear", C), ("bn_add_relu", 4)."""
 
     def __init__(self, in_shape: Tuple[int, int, int], layers: Sequence[tuple], max_batch: int, device: int = 0):
         import torch
@@ -1258,6 +1262,11 @@ class ConvNet:
                 i, o = H * W * Cc * es_in, H * W * l[1] * 4
                 total += B * ((i + o) + (0 if first else (i + o)) + (i + o)) + 3 * (Cc * l[1] + l[1]) * 4
                 Cc, first, es_in = l[1], False, 4
+            elif l[0] == "dwconv_linear":
+                # as conv_linear on the same maps (C -> C), with 10 C parameters
+                i, o = H * W * Cc * es_in, H * W * Cc * 4
+                total += B * ((i + o) + (0 if first else (i + o)) + (i + o)) + 3 * (10 * Cc) * 4
+                first, es_in = False, 4
             elif l[0] == "bn_relu":
                 # forward: the map read twice (statistics, apply) and written once; backward: three maps read over its two passes (x and dy
                 # by the sums, then one more pass's worth -- a re-read that hits the cache, the gate map -- is not counted) and one written

@@ -14,6 +14,7 @@
 #include "convnet_bf16.hpp"
 #include "convnet_halo.hpp"
 #include "convnet_pw.hpp"
+#include "convnet_dw.hpp"
 
 namespace rcnx {
 
@@ -520,6 +521,63 @@ inline std::string describe(const PwChoice& c, const ConvShape& s, int epi) {
     const long long tiles = ((long long)s.N * s.H * s.W + kBM - 1) / kBM;
     return head + strf("%s<1, tile, %d>", c.gemm.bf16 ? "k_conv_fwd_bf16" : "k_conv_fwd", bn) + (c.gemm.Z > 1 ? " split-K " + std::to_string(c.gemm.Z) + " + k_splitk_epilogue" : std::string()) +
            strf(", %d-wide column blocks, %lld row tiles, input read %d times", bn, tiles, s.Cout / bn);
+}
+
+// ---- RCN_HIPX_DWCONV3X3 (convnet_dw.hpp): the forward pass (epi 1) and the input gradient (epi 0 / 3) of a depthwise 3x3 convolution on an
+// H x W map of s.Cin == s.Cout channels, fp32 in either precision mode.  A tile is (image, band of `th` rows, slab of 256 16-byte pieces of a
+// row); th is the tallest of 32 / 16 / 8 that still gives the chip kDwMinTiles tiles (a taller band re-reads fewer halo rows; a
+// whole-height band none), else 8.  The grid loops over the tiles: `grid` workgroups where the option halo_f32_slots fixes them,
+// else (0) as many as the runtime says the chip holds.
+constexpr long long kDwMinTiles = 1024;      // 256 CUs x 4 workgroups of 256 threads (k_dw holds about 100 VGPRs: four waves per SIMD)
+struct DwChoice {
+    const char* error = nullptr;    // or: the layer cannot run (status -3 with this message)
+    int th = 8, bands = 1, slabs = 1;
+    long long items = 0, grid = 0;
+};
+inline DwChoice select_dw(const Selection& sel, const ConvShape& s, int epi) {
+    DwChoice c;
+    const auto refuse = [&c](const char* why) { c.error = why; return c; };
+    if (s.Cin != s.Cout) return refuse("internal: a depthwise convolution keeps its channel count");
+    if (s.Cin % 32) return refuse("a depthwise convolution's channels must be a multiple of 32");
+    if (epi != 0 && epi != 1 && epi != 3) return refuse("internal: a depthwise convolution has epilogues 0, 1 and 3");
+    if ((long long)s.W * (s.Cin / 4) > 0x3fffffffLL) return refuse("a depthwise convolution's map row must hold fewer than 2^30 16-byte pieces");
+    c.slabs = (int)(((long long)s.W * (s.Cin / 4) + kDwSlab - 1) / kDwSlab);
+    c.th = 8;
+    for (int th = 32; th > 8; th /= 2)
+        if (th < s.H + 8 && (long long)s.N * ((s.H + th - 1) / th) * c.slabs >= kDwMinTiles) { c.th = th; break; }
+    c.bands = (s.H + c.th - 1) / c.th;
+    c.items = (long long)s.N * c.bands * c.slabs;
+    if (sel.opt.halo_f32_slots > 0) c.grid = sel.opt.halo_f32_slots < c.items ? sel.opt.halo_f32_slots : c.items;
+    return c;
+}
+inline std::string describe(const DwChoice& c, const ConvShape& s, int epi) {
+    return strf("  dwconv 3x3 %dx%dx%d epi %d: k_dw<%d> (fp32 arithmetic), tiles of %d rows x %d pieces of 16 bytes (%d bands x %d slabs per image, %lld tiles), workgroups %s", s.H, s.W, s.Cin, epi,
+                epi, c.th, kDwSlab, c.bands, c.slabs, c.items, c.grid ? (std::to_string(c.grid) + " looping over the tiles").c_str() : "a resident grid looping over the tiles");
+}
+// ... and its weight gradient: partial [10][C] tiles, one per chunk of `ppc` consecutive pixels, by workgroups (chunk, 32-channel group)
+struct DwWgradChoice {
+    const char* error = nullptr;
+    int ppc = 0, chunks = 0, groups = 0;
+};
+inline DwWgradChoice select_dw_wgrad(const Selection& sel, const ConvShape& s) {
+    DwWgradChoice c;
+    if (s.Cin != s.Cout || s.Cin % 32) { c.error = "a depthwise convolution's channels must be a multiple of 32"; return c; }
+    const long long M = (long long)s.N * s.H * s.W;
+    c.groups = s.Cin / kDwGroup;
+    // the option pix_per_chunk as for every weight gradient; else aimed at wg_target workgroups like the implicit-GEMM kernels, but with a
+    // floor of 128 pixels, not their 1024: a chunk costs this kernel one [10][32] tile per workgroup (1.3 KB against 20 KB of input per
+    // 128 pixels), and at 1024 the 8 x 8 x 256 map of cifar_sep was 256 workgroups for 1024 resident slots
+    const int opt = sel.opt.pix_per_chunk >= 128 ? sel.opt.pix_per_chunk / 128 * 128 : 0;
+    long long pix = opt ? opt : (M * c.groups / sel.opt.wg_target + 127) / 128 * 128;
+    if (pix < 128) pix = 128;
+    if (pix > 32768) pix = 32768;
+    c.ppc = (int)pix;
+    if ((M + c.ppc - 1) / c.ppc > 0x7fffffffLL) { c.error = "a depthwise weight gradient of more than 2^31 chunks"; return c; }
+    c.chunks = (int)((M + c.ppc - 1) / c.ppc);
+    return c;
+}
+inline std::string describe(const DwWgradChoice& c, const ConvShape& s) {
+    return strf("  wgrad dwconv 3x3 %dx%dx%d: k_dw_wgrad (fp32 arithmetic), %d channel groups x %d chunks of %d pixels", s.H, s.W, s.Cin, c.groups, c.chunks, c.ppc);
 }
 
 // ---- the step's update launch (convnet_update.hpp)

@@ -33,6 +33,7 @@
 #include "convnet_bn.hpp"
 #include "convnet_gap.hpp"
 #include "convnet_pw.hpp"
+#include "convnet_dw.hpp"
 
 using namespace rcnx;
 
@@ -69,21 +70,24 @@ struct LayerShape {
     // adds in front of its ReLU, and -- in that source -- the layer that adds its output; -1: none
     int skip_src = -1, skip_by = -1;
 };
-// the kinds by what the walks ask of them: a 3x3 convolution (with or without ReLU; NOT the 1x1 convolution: is_conv means "3x3" wherever
-// it is asked -- filter_size and on_map below say the rest), and a layer whose W is a matrix with a tap-flipped
+// the kinds by what the walks ask of them: a 3x3 GEMM convolution (with or without ReLU; NOT the 1x1 convolution and NOT the depthwise
+// 3x3 convolution, which is no GEMM: is_conv means "3x3 GEMM convolution" wherever it is asked -- filter_size and on_map below say the
+// rest), and a layer whose W is a matrix with a tap-flipped
 // copy and bf16 operand copies (every layer with a [W | b] block but batch normalisation, whose block is [gamma | beta])
 inline bool is_conv(int kind) { return kind == RCN_HIPX_CONV3X3_RELU || kind == RCN_HIPX_CONV3X3 || kind == RCN_HIPX_CONV3X3_S2; }
-// a bias-only convolution in front of batch normalisation, of either stride or filter size: no activation, no ReLU gate of its own, BN must follow
-inline bool is_conv_linear(int kind) { return kind == RCN_HIPX_CONV3X3 || kind == RCN_HIPX_CONV3X3_S2 || kind == RCN_HIPX_CONV1X1; }
-// a layer whose GEMM rows are the pixels of a map (a convolution of either filter size), not the samples of a batch (a dense layer)
-inline bool on_map(int kind) { return is_conv(kind) || kind == RCN_HIPX_CONV1X1; }
-// the filter size of a kind with a matrix: 3 for the 3x3 convolutions, 1 for the 1x1 convolution and the dense layers
-inline int filter_size(int kind) { return is_conv(kind) ? 3 : 1; }
+// a bias-only convolution in front of batch normalisation, of either stride or filter size, dense or depthwise: no activation, no ReLU gate of its own, BN must follow
+inline bool is_conv_linear(int kind) { return kind == RCN_HIPX_CONV3X3 || kind == RCN_HIPX_CONV3X3_S2 || kind == RCN_HIPX_CONV1X1 || kind == RCN_HIPX_DWCONV3X3; }
+// a layer whose rows are the pixels of a map (a convolution of either filter size, dense or depthwise), not the samples of a batch (a dense layer)
+inline bool on_map(int kind) { return is_conv(kind) || kind == RCN_HIPX_CONV1X1 || kind == RCN_HIPX_DWCONV3X3; }
+// the filter size of a kind with a [W | b] block: 3 for the 3x3 convolutions (the depthwise one too: K = 9 = 3 x 3 x 1), 1 for the 1x1 convolution and the dense layers
+inline int filter_size(int kind) { return is_conv(kind) || kind == RCN_HIPX_DWCONV3X3 ? 3 : 1; }
 // batch normalisation, with or without a skip added in front of its ReLU: one [gamma | beta] block, statistics and buffers either way
 inline bool is_bn(int kind) { return kind == RCN_HIPX_BN_RELU || kind == RCN_HIPX_BN_ADD_RELU || kind == RCN_HIPX_BN_ADD_RELU_DOWN; }
 // a layer with a parameter block ([W | b] or [gamma | beta]): every kind but the two pools, which also take no `out`
 inline bool has_params(int kind) { return kind != RCN_HIPX_MAXPOOL2 && kind != RCN_HIPX_GLOBAL_AVGPOOL; }
 inline bool has_matrix(int kind) { return has_params(kind) && !is_bn(kind); }
+// ... of which the GEMM layers have bf16 operand copies (prep_bf16_weights); the depthwise convolution has no GEMM and computes in fp32 in either mode
+inline bool has_bf16_copies(int kind) { return has_matrix(kind) && kind != RCN_HIPX_DWCONV3X3; }
 // ... and what it holds on the device
 struct Layer : LayerShape {
     Buf out, idx, dout;     // activation (post-ReLU / pooled), pool arg-max, gradient wrt the layer's OUTPUT
@@ -566,6 +570,36 @@ int launch_pw(rcn_hipx_net* n, const float* X, const float* Wk, const float* bia
     return 0;
 }
 
+// ---- RCN_HIPX_DWCONV3X3 (convnet_select.hpp: select_dw): Y = dwconv(X, W) + b (epi 1), or the input gradient -- the same stencil over dZ on the
+// tap-reversed copy (epi 0 raw, 3 gated by `bias`, a tensor shaped like Y); fp32 in either precision mode.  The tiles partition the map and
+// a lane stores each of its pieces once: every element of Y is written exactly once, by one thread.
+int launch_dw(rcn_hipx_net* n, const float* X, const float* Wk, const float* bias, float* Y, ConvShape s, int epi) {
+    const DwChoice c = select_dw(*n, s, epi);
+    if (c.error) return fail(n, -3, c.error);
+    if (dry_note(n, "%s", describe(c, s, epi).c_str())) return 0;
+    with_const<1, 3, 0>(epi, [&](auto EPI) {
+        auto* const kernel = k_dw<CV(EPI)>;
+        // the resident grid: as many workgroups as the chip holds of this kernel (the option halo_f32_slots: that many), looping over the tiles
+        long long gx = c.grid;
+        if (!gx) { gx = resident_slots(n, (const void*)kernel); if (gx > c.items) gx = c.items; }
+        hipLaunchKernelGGL(kernel, dim3((unsigned)gx), dim3(kThreads), 0, n->stream, X, Wk, bias, Y, s.H, s.W, s.Cin, c.th, c.items);
+    });
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+// ... and the partial [10][C] tiles of its weight gradient into the layer's slab (n->slab_sel), one per chunk of pixels; *chunks_out: how many
+int launch_dw_wgrad(rcn_hipx_net* n, const float* X, const float* dZ, ConvShape s, int* chunks_out) {
+    const DwWgradChoice c = select_dw_wgrad(*n, s);
+    if (c.error) return fail(n, -3, c.error);
+    *chunks_out = c.chunks;
+    if (dry_note(n, "%s", describe(c, s).c_str())) return 0;
+    XTRY(n, scratch_ensure(n, *n->slab_sel, (size_t)c.chunks * 10 * s.Cout * sizeof(float)));
+    hipLaunchKernelGGL(k_dw_wgrad, dim3((unsigned)c.chunks, (unsigned)c.groups), dim3(kThreads), 0, n->stream, X, dZ, (float*)n->slab_sel->p, (long long)s.N * s.H * s.W, s.H, s.W, s.Cin,
+                       c.ppc);
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+
 float* P(rcn_hipx_net* n, long long off) { return (float*)n->params.p + off; }
 
 int ensure_batch(rcn_hipx_net* n, int B) {
@@ -600,7 +634,7 @@ int prep_bf16_weights(rcn_hipx_net* n) {
     if (n->precision != RCN_HIPX_BF16) return 0;
     // the path is decided before the plan is noted: two jobs per matrix layer behind layer 0, and one launch takes kMaxPrepJobs of them
     int matrices = 0;
-    for (size_t i = 1; i < n->L.size(); ++i) matrices += has_matrix(n->L[i].kind);
+    for (size_t i = 1; i < n->L.size(); ++i) matrices += has_bf16_copies(n->L[i].kind);
     if (2 * matrices > kMaxPrepJobs) {
         // more than one launch takes: no prepared copies -- every bf16 launch makes its own in front of itself (launch_conv), all into the
         // one scratch n->wb, which the stream's order keeps whole until that launch has read it
@@ -616,7 +650,7 @@ int prep_bf16_weights(rcn_hipx_net* n) {
         std::vector<std::tuple<size_t, int, long long>> plan;      // (layer, orientation, offset)
         for (size_t i = 1; i < n->L.size(); ++i) {
             Layer& l = n->L[i];
-            if (!has_matrix(l.kind)) continue;
+            if (!has_bf16_copies(l.kind)) continue;
             const int ks = filter_size(l.kind);
             const long long cin = l.K / (ks * ks);
             const long long Kf = (long long)ks * ks * cin, Kpf = (Kf + 31) / 32 * 32;                 // forward: [CoutP][Kpf]
@@ -631,7 +665,7 @@ int prep_bf16_weights(rcn_hipx_net* n) {
         n->prep.njobs = 0;
         for (size_t i = 1; i < n->L.size(); ++i) {
             Layer& l = n->L[i];
-            if (!has_matrix(l.kind)) continue;
+            if (!has_bf16_copies(l.kind)) continue;
             const int ks = filter_size(l.kind);
             const long long cin = l.K / (ks * ks);
             const long long Kf = (long long)ks * ks * cin, Kpf = (Kf + 31) / 32 * 32, Kb = (long long)ks * ks * l.CoutP, Kpb = (Kb + 31) / 32 * 32;
@@ -824,6 +858,7 @@ int forward(rcn_hipx_net* n, const float* x, int B, size_t n_layers = (size_t)-1
             if (n->store16) return fail(n, -3, kBnStoreGap);
             if (l.kind == RCN_HIPX_CONV3X3_S2) RTRY(launch_conv_s2(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShapeS2{B, l.H, l.W, l.Cin, l.CoutP}, 1, wb_of(n, l.wbf_off)));
             else if (l.kind == RCN_HIPX_CONV1X1) RTRY(launch_pw(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShape{B, l.H, l.W, l.Cin, l.CoutP}, 1, wb_of(n, l.wbf_off)));
+            else if (l.kind == RCN_HIPX_DWCONV3X3) RTRY(launch_dw(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShape{B, l.H, l.W, l.Cin, l.CoutP}, 1));
             else RTRY(launch_conv(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShape{B, l.H, l.W, l.Cin, l.CoutP}, 3, 1, nullptr, nullptr, false, wb_of(n, l.wbf_off)));
         } else if (is_bn(l.kind)) {
             if (n->store16) return fail(n, -3, kBnStoreGap);
@@ -985,7 +1020,9 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
         }
         // conv: the layer's rows are the pixels of a map (a 3x3 or a 1x1 convolution); pw: the 1x1 convolution, whose forward pass and input
         // gradient have their own selector (launch_pw) and whose weight gradient is the KS = 1 kernels' with rows walking the H x W map
-        const bool conv = on_map(l.kind), strided = l.kind == RCN_HIPX_CONV3X3_S2, pw = l.kind == RCN_HIPX_CONV1X1;
+        // dw: the depthwise 3x3 convolution, no GEMM -- its own stencil and weight-gradient kernels (launch_dw, launch_dw_wgrad); its [W | b] block is
+        // that of a 3x3 convolution of ONE input channel, and as such (sr) it goes to reduce_slab: n = 10 C, FlipSpec{wt, 9, 1, C}
+        const bool conv = on_map(l.kind), strided = l.kind == RCN_HIPX_CONV3X3_S2, pw = l.kind == RCN_HIPX_CONV1X1, dw = l.kind == RCN_HIPX_DWCONV3X3;
         const int ks = filter_size(l.kind);
         const ConvShape s = conv ? ConvShape{B, l.H, l.W, l.Cin, l.CoutP} : ConvShape{B, 1, 1, l.K, l.CoutP};      // (H x W: the layer's INPUT map; a strided layer's output is l.oH x l.oW)
         const long long M = (long long)s.N * l.oH * l.oW;
@@ -1018,6 +1055,9 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             if (strided) RTRY(launch_dgrad_s2(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, ConvShapeS2T{s.N, s.H, s.W, s.Cout, s.Cin}, gate ? 3 : 0, wb_of(n, l.wbb_off)));
             // (a 1x1 layer: k_pw, or the implicit GEMM on the map, writes ALL of dout[i - 1], every element once -- what the skip's add below rests on)
             else if (pw) RTRY(launch_pw(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, ConvShape{s.N, s.H, s.W, s.Cout, s.Cin}, gate ? 3 : 0, wb_of(n, l.wbb_off)));
+            // (a depthwise layer: k_dw's tiles partition the map and a lane stores each of its pieces once -- ALL of dout[i - 1], every element
+            // once, by one thread, with no second launch and no accumulation: the same ground for the skip's add below)
+            else if (dw) RTRY(launch_dw(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, s, gate ? 3 : 0));
             else RTRY(launch_conv(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, ConvShape{s.N, s.H, s.W, s.Cout, s.Cin}, ks, gate ? 3 : 0,
                              nullptr, pooled[i].dP ? &pooled[i] : nullptr, false, wb_of(n, l.wbb_off), Store{stage16(n, i), stage16(n, i - 1)}));
             gated[i - 1] = gate;
@@ -1035,8 +1075,9 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
         if (on_side) n->stream = n->side;
         n->slab_sel = &l.slab;
         if (strided) RTRY(launch_wgrad_s2(n, in, dZ, ConvShapeS2{s.N, s.H, s.W, s.Cin, s.Cout}, &chunks));
+        else if (dw) RTRY(launch_dw_wgrad(n, in, dZ, s, &chunks));
         else RTRY(launch_wgrad(n, in, dZ, s, ks, &chunks, pooled[i].dP ? &pooled[i] : nullptr, Store{stage16(n, i - 1), stage16(n, i)}, pw));
-        RTRY(reduce_slab(n, (size_t)i, chunks, ks, s, grad, apply));
+        RTRY(reduce_slab(n, (size_t)i, chunks, ks, dw ? ConvShape{s.N, s.H, s.W, 1, s.Cout} : s, grad, apply));
         n->stream = main_s;
     }
     return 0;
@@ -1263,7 +1304,18 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
             return fail(n, -2, "layer " + std::to_string(i - 1) + " (RCN_HIPX_CONV3X3_S2): it must be followed directly by a batch-normalisation layer (RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_BN_ADD_RELU_DOWN)");
         if (i > 0 && n->L.back().kind == RCN_HIPX_CONV1X1 && !is_bn(l.kind))
             return fail(n, -2, "layer " + std::to_string(i - 1) + " (RCN_HIPX_CONV1X1): it must be followed directly by a batch-normalisation layer (RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_BN_ADD_RELU_DOWN)");
-        if (l.kind == RCN_HIPX_CONV1X1) {
+        if (i > 0 && n->L.back().kind == RCN_HIPX_DWCONV3X3 && !is_bn(l.kind))
+            return fail(n, -2, "layer " + std::to_string(i - 1) + " (RCN_HIPX_DWCONV3X3): it must be followed directly by a batch-normalisation layer (RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_BN_ADD_RELU_DOWN)");
+        if (l.kind == RCN_HIPX_DWCONV3X3) {
+            // torch.nn.Conv2d(C, C, 3, padding=1, groups=C): a [W | b] block with K = 9 and Cout = C on the H x W map, in front of batch
+            // normalisation.  `out`: 0 or C (the resolved width is what the state descriptor stores); no gather form
+            const std::string at = "layer " + std::to_string(i) + " (RCN_HIPX_DWCONV3X3): ";
+            if (flat) return fail(n, -2, at + "convolution after a dense layer or a global average pool");
+            if (layers[i].out != 0 && layers[i].out != C)
+                return fail(n, -2, at + "out must be 0 or the input channels " + std::to_string(C) + " (depth multiplier 1), not " + std::to_string(layers[i].out));
+            if (C % 32) return fail(n, -3, at + "its input channels must be a multiple of 32, not " + std::to_string(C) + " (no first-layer gather form)");
+            l.Cout = l.CoutP = C; l.oH = H; l.oW = W; l.K = 9;
+        } else if (l.kind == RCN_HIPX_CONV1X1) {
             // torch.nn.Conv2d(C, out, 1): a [W | b] block with K = C on the H x W map, in front of batch normalisation.  No gather form:
             // the rows are whole 16-byte pieces of a map of a multiple of 32 channels (so not the first layer of a 1- or 3-channel input)
             const std::string at = "layer " + std::to_string(i) + " (RCN_HIPX_CONV1X1): ";
@@ -1348,13 +1400,15 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
             C = l.Cout; flat = true; H = W = 1;
         } else return fail(n, -1, "unknown layer kind");
         if (!is_bn(l.kind) && i > 0 && is_conv_linear(n->L.back().kind))
-            return fail(n, -2, "layer " + std::to_string(i - 1) + ": a " + (n->L.back().kind == RCN_HIPX_CONV3X3_S2 ? "RCN_HIPX_CONV3X3_S2" : n->L.back().kind == RCN_HIPX_CONV1X1 ? "RCN_HIPX_CONV1X1" : "RCN_HIPX_CONV3X3") + " layer must be followed by RCN_HIPX_BN_RELU or RCN_HIPX_BN_ADD_RELU");
+            return fail(n, -2, "layer " + std::to_string(i - 1) + ": a " + (n->L.back().kind == RCN_HIPX_CONV3X3_S2 ? "RCN_HIPX_CONV3X3_S2" : n->L.back().kind == RCN_HIPX_CONV1X1 ? "RCN_HIPX_CONV1X1" : n->L.back().kind == RCN_HIPX_DWCONV3X3 ? "RCN_HIPX_DWCONV3X3" : "RCN_HIPX_CONV3X3") + " layer must be followed by RCN_HIPX_BN_RELU or RCN_HIPX_BN_ADD_RELU");
         if (has_params(l.kind)) {
             l.w_off = n->n_pad; n->n_pad += (long long)l.K * l.CoutP; l.b_off = n->n_pad; n->n_pad += l.CoutP;
             l.lw_off = n->n_log; n->n_log += (long long)l.K * l.Cout; l.lb_off = n->n_log; n->n_log += l.Cout;
         }
         n->L.push_back(std::move(l));
     }
+    if (n->L.back().kind == RCN_HIPX_DWCONV3X3)
+        return fail(n, -2, "layer " + std::to_string(n_layers - 1) + " (RCN_HIPX_DWCONV3X3): it must be followed directly by a batch-normalisation layer, and the last layer must be RCN_HIPX_DENSE (logits)");
     if (n->L.back().kind == RCN_HIPX_CONV1X1)
         return fail(n, -2, "layer " + std::to_string(n_layers - 1) + " (RCN_HIPX_CONV1X1): it must be followed directly by a batch-normalisation layer, and the last layer must be RCN_HIPX_DENSE (logits)");
     if (n->L.back().kind == RCN_HIPX_CONV3X3_S2)
