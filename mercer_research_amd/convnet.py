@@ -460,6 +460,8 @@ class Snapshot:
         return len(data)
 
 
+# the convolution kinds as step_hbm_floor_bytes sees them: (filter taps, stride, depthwise: C -> C with one input channel per filter)
+_CONV_GEOMETRY = {"conv": (9, 1, False), "conv_linear": (9, 1, False), "conv_linear_s2": (9, 2, False), "conv1x1_linear": (1, 1, False), "dwconv_linear": (9, 1, True)}
 X_KIND = {"float32": 0, "uint8": 1}      # RCN_HIPX_X_F32 / RCN_HIPX_X_U8, by the set's torch dtype
 
 
@@ -1238,35 +1240,22 @@ class ConvNet:
         maps = []                                            # every layer's output (H, W, C): a down shortcut reads its source's
         for l in self.layers:
             maps.append(None)
-            if l[0] == "conv_linear_s2":
-                # as conv_linear with the output map a quarter of the input's
-                i, o = H * W * Cc * es_in, (H // 2) * (W // 2) * l[1] * 4
-                total += B * ((i + o) + (0 if first else (i + o)) + (i + o)) + 3 * (9 * Cc * l[1] + l[1]) * 4
-                H, W, Cc, first, es_in = H // 2, W // 2, l[1], False, 4
+            if l[0] in _CONV_GEOMETRY:
+                # input read and output written by the forward pass; dZ read and dX written by the input gradient (not for the first layer);
+                # input and dZ read by the weight gradient; [W | b] read twice and written once
+                taps, stride, depthwise = _CONV_GEOMETRY[l[0]]
+                oH, oW, Co = H // stride, W // stride, Cc if depthwise else l[1]
+                es_out = es_stage if l[0] == "conv" else 4       # only the ReLU convolution's map is stored as the stage's
+                params = (taps if depthwise else taps * Cc) * Co + Co
+                i, o = H * W * Cc * es_in, oH * oW * Co * es_out
+                total += B * ((i + o) + (0 if first else (i + o)) + (i + o)) + 3 * params * 4
+                H, W, Cc, first, es_in = oH, oW, Co, False, es_out
             elif l[0] == "bn_add_relu_down":
                 # as bn_relu, and the shortcut: a quarter of the source's map (its Cs channels at every second pixel) read by the apply pass;
                 # the add pass of the backward reads that quarter of the source's gradient and this layer's window and writes the quarter
                 m = H * W * Cc * 4
                 sm = H * W * maps[len(maps) - 1 - l[1]][2] * 4
                 total += B * (3 * m + 4 * m + sm + 3 * sm)
-            elif l[0] == "conv":
-                i, o = H * W * Cc * es_in, H * W * l[1] * es_stage
-                total += B * ((i + o) + (0 if first else (i + o)) + (i + o)) + 3 * (9 * Cc * l[1] + l[1]) * 4
-                Cc, first, es_in = l[1], False, es_stage
-            elif l[0] == "conv_linear":
-                i, o = H * W * Cc * es_in, H * W * l[1] * 4
-                total += B * ((i + o) + (0 if first else (i + o)) + (i + o)) + 3 * (9 * Cc * l[1] + l[1]) * 4
-                Cc, first, es_in = l[1], False, 4
-            elif l[0] == "conv1x1_linear":
-                # as conv_linear with a [Cin][Cout] matrix
-                i, o = H * W * Cc * es_in, H * W * l[1] * 4
-                total += B * ((i + o) + (0 if first else (i + o)) + (i + o)) + 3 * (Cc * l[1] + l[1]) * 4
-                Cc, first, es_in = l[1], False, 4
-            elif l[0] == "dwconv_linear":
-                # as conv_linear on the same maps (C -> C), with 10 C parameters
-                i, o = H * W * Cc * es_in, H * W * Cc * 4
-                total += B * ((i + o) + (0 if first else (i + o)) + (i + o)) + 3 * (10 * Cc) * 4
-                first, es_in = False, 4
             elif l[0] == "bn_relu":
                 # forward: the map read twice (statistics, apply) and written once; backward: three maps read over its two passes (x and dy
                 # by the sums, then one more pass's worth -- a re-read that hits the cache, the gate map -- is not counted) and one written

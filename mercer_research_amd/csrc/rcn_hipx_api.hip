@@ -34,6 +34,7 @@
 #include "convnet_gap.hpp"
 #include "convnet_pw.hpp"
 #include "convnet_dw.hpp"
+#include "convnet_kinds.hpp"
 
 using namespace rcnx;
 
@@ -69,25 +70,14 @@ struct LayerShape {
     // a skip (RCN_HIPX_BN_ADD_RELU: identity; RCN_HIPX_BN_ADD_RELU_DOWN: subsampled and zero-padded): the layer whose output this layer
     // adds in front of its ReLU, and -- in that source -- the layer that adds its output; -1: none
     int skip_src = -1, skip_by = -1;
+    const KindRow& row() const { return kind_row(kind); }
+    // its [W | b] block is taps x cin rows (+ the bias row) of CoutP columns: a 3x3 convolution 9 x Cin, the depthwise one 9 x 1, the 1x1
+    // convolution and a dense layer 1 x K, batch normalisation's [gamma | beta] 1 x 1 -- what a slab, the flipped copy and the bf16 copies hold
+    int taps() const { return row().ks * row().ks; }
+    int cin() const { return K / taps(); }
+    // the GEMM of its forward pass at batch B: over the pixels of its input map, or over the samples (a dense layer)
+    ConvShape gemm(int B) const { return row().map ? ConvShape{B, H, W, Cin, CoutP} : ConvShape{B, 1, 1, K, CoutP}; }
 };
-// the kinds by what the walks ask of them: a 3x3 GEMM convolution (with or without ReLU; NOT the 1x1 convolution and NOT the depthwise
-// 3x3 convolution, which is no GEMM: is_conv means "3x3 GEMM convolution" wherever it is asked -- filter_size and on_map below say the
-// rest), and a layer whose W is a matrix with a tap-flipped
-// copy and bf16 operand copies (every layer with a [W | b] block but batch normalisation, whose block is [gamma | beta])
-inline bool is_conv(int kind) { return kind == RCN_HIPX_CONV3X3_RELU || kind == RCN_HIPX_CONV3X3 || kind == RCN_HIPX_CONV3X3_S2; }
-// a bias-only convolution in front of batch normalisation, of either stride or filter size, dense or depthwise: no activation, no ReLU gate of its own, BN must follow
-inline bool is_conv_linear(int kind) { return kind == RCN_HIPX_CONV3X3 || kind == RCN_HIPX_CONV3X3_S2 || kind == RCN_HIPX_CONV1X1 || kind == RCN_HIPX_DWCONV3X3; }
-// a layer whose rows are the pixels of a map (a convolution of either filter size, dense or depthwise), not the samples of a batch (a dense layer)
-inline bool on_map(int kind) { return is_conv(kind) || kind == RCN_HIPX_CONV1X1 || kind == RCN_HIPX_DWCONV3X3; }
-// the filter size of a kind with a [W | b] block: 3 for the 3x3 convolutions (the depthwise one too: K = 9 = 3 x 3 x 1), 1 for the 1x1 convolution and the dense layers
-inline int filter_size(int kind) { return is_conv(kind) || kind == RCN_HIPX_DWCONV3X3 ? 3 : 1; }
-// batch normalisation, with or without a skip added in front of its ReLU: one [gamma | beta] block, statistics and buffers either way
-inline bool is_bn(int kind) { return kind == RCN_HIPX_BN_RELU || kind == RCN_HIPX_BN_ADD_RELU || kind == RCN_HIPX_BN_ADD_RELU_DOWN; }
-// a layer with a parameter block ([W | b] or [gamma | beta]): every kind but the two pools, which also take no `out`
-inline bool has_params(int kind) { return kind != RCN_HIPX_MAXPOOL2 && kind != RCN_HIPX_GLOBAL_AVGPOOL; }
-inline bool has_matrix(int kind) { return has_params(kind) && !is_bn(kind); }
-// ... of which the GEMM layers have bf16 operand copies (prep_bf16_weights); the depthwise convolution has no GEMM and computes in fp32 in either mode
-inline bool has_bf16_copies(int kind) { return has_matrix(kind) && kind != RCN_HIPX_DWCONV3X3; }
 // ... and what it holds on the device
 struct Layer : LayerShape {
     Buf out, idx, dout;     // activation (post-ReLU / pooled), pool arg-max, gradient wrt the layer's OUTPUT
@@ -225,18 +215,20 @@ int grid1d(long long total, int block) { long long g = (total + block - 1) / blo
 // RCN_HIPX_HALO_F32 only seeds a new net's tiling mode (rcn_hipx_create); rcn_hipx_set_tiling changes it per net
 static int halo_f32_default() { const char* e = std::getenv("RCN_HIPX_HALO_F32"); const int v = e ? std::atoi(e) : 1; return v < 0 || v > 2 ? 1 : v; }
 
-// workgroups of `kernel` (256 threads, static LDS only) the device holds at once: the grid of a kernel whose workgroups loop over
-// work items.  Asked from the runtime once per kernel.
-long long resident_slots(rcn_hipx_net* n, const void* kernel) {
-    if (n->opt.halo_f32_slots > 0) return n->opt.halo_f32_slots;
+// workgroups of `kernel` (256 threads; static LDS only, or -- a k_pw instantiation -- `dyn_lds` bytes of dynamic LDS) the device holds at
+// once: the grid of a kernel whose workgroups loop over work items.  Asked from the runtime once per (device, kernel, LDS size).  The
+// option halo_f32_slots stands for the answer for the static-LDS kernels, not for k_pw (select_pw sizes that grid from the option itself);
+// where the runtime gives none: two workgroups per CU of a static-LDS kernel, one of k_pw.
+long long resident_slots(rcn_hipx_net* n, const void* kernel, size_t dyn_lds = 0) {
+    if (!dyn_lds && n->opt.halo_f32_slots > 0) return n->opt.halo_f32_slots;
     static std::mutex mu;
-    static std::map<std::pair<int, const void*>, long long> cache;
+    static std::map<std::tuple<int, const void*, size_t>, long long> cache;
     const std::lock_guard<std::mutex> lock(mu);
-    const std::pair<int, const void*> key{n->device, kernel};
+    const std::tuple<int, const void*, size_t> key{n->device, kernel, dyn_lds};
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;
     int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kThreads, 0) != hipSuccess || per_cu < 1) per_cu = 2;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kThreads, dyn_lds) != hipSuccess || per_cu < 1) per_cu = dyn_lds ? 1 : 2;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, n->device) != hipSuccess || cus < 1) cus = 256;
     const long long v = (long long)per_cu * cus;
     cache.emplace(key, v);
@@ -521,22 +513,6 @@ hipError_t pw_allow_lds(rcn_hipx_net* n, const void* kernel) {
     done.emplace(key, e);
     return e;
 }
-// workgroups of a k_pw instantiation (256 threads, `lds` bytes of dynamic LDS) the device holds at once; asked from the runtime once per
-// (kernel, LDS size), as resident_slots does for the kernels with static LDS
-long long pw_slots(rcn_hipx_net* n, const void* kernel, size_t lds) {
-    static std::mutex mu;
-    static std::map<std::tuple<int, const void*, size_t>, long long> cache;
-    const std::lock_guard<std::mutex> lock(mu);
-    const std::tuple<int, const void*, size_t> key{n->device, kernel, lds};
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kThreads, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, n->device) != hipSuccess || cus < 1) cus = 256;
-    const long long v = (long long)per_cu * cus;
-    cache.emplace(key, v);
-    return v;
-}
 
 // ---- RCN_HIPX_CONV1X1 (convnet_select.hpp: select_pw): Y = X W + b (epi 1) or the input gradient dZ Wt (epi 0 raw, 3 gated by `bias`, a tensor
 // shaped like Y) over the H x W map; every element of Y is written exactly once.  s.Cin: the contraction, s.Cout: the launch's columns.
@@ -559,7 +535,7 @@ int launch_pw(rcn_hipx_net* n, const float* X, const float* Wk, const float* bia
         // the resident grid: as many workgroups as the chip holds of this kernel with this much LDS, dealt over the column slices
         long long gx = c.grid;
         if (!gx) {
-            gx = pw_slots(n, (const void*)kernel, lds) / c.passes;
+            gx = resident_slots(n, (const void*)kernel, lds) / c.passes;
             if (gx < 1) gx = 1;
             if (gx > c.items) gx = c.items;
         }
@@ -627,14 +603,58 @@ const __bf16* wb_of(const rcn_hipx_net* n, long long off) {
     return (n->precision == RCN_HIPX_BF16 && n->wb16.p && off >= 0) ? (const __bf16*)n->wb16.p + off : (const __bf16*)nullptr;
 }
 
+// ---- The three passes of a matrix layer, by kind: the only places that switch on the convolution kind.  Each builds the shape its kind's
+// launcher takes from the layer and the batch (H x W: the layer's INPUT map; a strided layer's output is l.oH x l.oW).
+// The forward pass of a bias-only layer in front of batch normalisation: Y = conv(X) + b (epilogue 1), no conv+pool fusion
+int layer_forward(rcn_hipx_net* n, const Layer& l, int B, const float* X, float* Y) {
+    const float *const W = P(n, l.w_off), *const b = P(n, l.b_off);
+    const __bf16* const WB = wb_of(n, l.wbf_off);
+    switch (l.kind) {
+    case RCN_HIPX_CONV3X3_S2: return launch_conv_s2(n, X, W, b, Y, ConvShapeS2{B, l.H, l.W, l.Cin, l.CoutP}, 1, WB);
+    case RCN_HIPX_CONV1X1: return launch_pw(n, X, W, b, Y, l.gemm(B), 1, WB);
+    case RCN_HIPX_DWCONV3X3: return launch_dw(n, X, W, b, Y, l.gemm(B), 1);
+    default: return launch_conv(n, X, W, b, Y, l.gemm(B), l.row().ks, 1, nullptr, nullptr, false, WB);
+    }
+}
+// Its input gradient: dX = conv(dZ, flip(W)^T) on the tap-flipped transposed weights, which every kernel that writes a weight keeps current
+// (FlipSpec, refresh_flipped).  gate_by (nullable): the ReLU layer below, whose output gates dX in the epilogue (3; else 0, raw).  pdz
+// (nullable): dZ exists only at pooled resolution; st: dZ / dX are bf16 tensors.  Whatever the kind, ONE launch writes ALL of dX, every element
+// once and with no accumulation: a strided layer over the four parity classes of the input pixels, k_dw's tiles partitioning the map.
+int layer_dgrad(rcn_hipx_net* n, const Layer& l, int B, const float* dZ, const Layer* gate_by, float* dX, const PooledGrad* pdz, Store st) {
+    const float *const wt = (const float*)n->wt.p + l.w_off, *const gate = gate_by ? (const float*)gate_by->out.p : nullptr;
+    const int epi = gate_by ? 3 : 0;
+    const __bf16* const WB = wb_of(n, l.wbb_off);
+    const ConvShape s = l.gemm(B), t{s.N, s.H, s.W, s.Cout, s.Cin};      // t: the transposed GEMM, dZ's channels contracted
+    switch (l.kind) {
+    case RCN_HIPX_CONV3X3_S2: return launch_dgrad_s2(n, dZ, wt, gate, dX, ConvShapeS2T{t.N, t.H, t.W, t.Cin, t.Cout}, epi, WB);
+    case RCN_HIPX_CONV1X1: return launch_pw(n, dZ, wt, gate, dX, t, epi, WB);
+    case RCN_HIPX_DWCONV3X3: return launch_dw(n, dZ, wt, gate, dX, s, epi);      // (the same stencil over dZ: C -> C)
+    default: return launch_conv(n, dZ, wt, gate, dX, t, l.row().ks, epi, nullptr, pdz, false, WB, st);
+    }
+}
+// Its weight gradient from its input X and dZ: the partial [W | b] tiles into n->slab_sel, *chunks of them (pdz, st: as above, X / dZ)
+int layer_wgrad(rcn_hipx_net* n, const Layer& l, int B, const float* X, const float* dZ, int* chunks, const PooledGrad* pdz, Store st) {
+    switch (l.kind) {
+    case RCN_HIPX_CONV3X3_S2: return launch_wgrad_s2(n, X, dZ, ConvShapeS2{B, l.H, l.W, l.Cin, l.CoutP}, chunks);
+    case RCN_HIPX_DWCONV3X3: return launch_dw_wgrad(n, X, dZ, l.gemm(B), chunks);
+    default: return launch_wgrad(n, X, dZ, l.gemm(B), l.row().ks, chunks, pdz, st, l.kind == RCN_HIPX_CONV1X1);      // (1x1: the KS = 1 kernels with rows walking the map)
+    }
+}
+
 // bf16 mode, once per step / forward call: the transposed bf16 copies of every layer's weights -- [Cout][Kp] for the forward pass from W,
 // [Cin][Kp'] for the input gradient from the flipped copy (which the update kernel keeps current) -- in ONE launch.  The first layer
 // (fp32 kernels in either mode) has none.
+// a layer's two copies: [CoutP][Kpf] of the Kf rows of W for the forward pass, [cin][Kpb] of the Kb rows of the flipped copy for the input gradient
+struct CopyShapes { long long cin, Kf, Kpf, Kb, Kpb; };
+CopyShapes copy_shapes(const Layer& l) {
+    const long long Kf = l.K, Kb = (long long)l.taps() * l.CoutP;
+    return {l.cin(), Kf, (Kf + 31) / 32 * 32, Kb, (Kb + 31) / 32 * 32};
+}
 int prep_bf16_weights(rcn_hipx_net* n) {
     if (n->precision != RCN_HIPX_BF16) return 0;
     // the path is decided before the plan is noted: two jobs per matrix layer behind layer 0, and one launch takes kMaxPrepJobs of them
     int matrices = 0;
-    for (size_t i = 1; i < n->L.size(); ++i) matrices += has_bf16_copies(n->L[i].kind);
+    for (size_t i = 1; i < n->L.size(); ++i) matrices += n->L[i].row().gemm;
     if (2 * matrices > kMaxPrepJobs) {
         // more than one launch takes: no prepared copies -- every bf16 launch makes its own in front of itself (launch_conv), all into the
         // one scratch n->wb, which the stream's order keeps whole until that launch has read it
@@ -644,37 +664,27 @@ int prep_bf16_weights(rcn_hipx_net* n) {
     }
     if (dry_note(n, "  bf16 operand copies of every layer's weights, both orientations: k_prep_all_bf16 (one launch)")) return 0;
     if (!n->wb16.p) {
-        long long off = 0;
-        int q = 0;
-        long long blocks = 0;
-        std::vector<std::tuple<size_t, int, long long>> plan;      // (layer, orientation, offset)
+        long long off = 0, blocks = 0;
         for (size_t i = 1; i < n->L.size(); ++i) {
             Layer& l = n->L[i];
-            if (!has_bf16_copies(l.kind)) continue;
-            const int ks = filter_size(l.kind);
-            const long long cin = l.K / (ks * ks);
-            const long long Kf = (long long)ks * ks * cin, Kpf = (Kf + 31) / 32 * 32;                 // forward: [CoutP][Kpf]
-            const long long Kb = (long long)ks * ks * l.CoutP, Kpb = (Kb + 31) / 32 * 32;              // input gradient: [cin][Kpb]
-            l.wbf_off = off; off += (long long)l.CoutP * Kpf;
-            l.wbb_off = off; off += cin * Kpb;
+            if (!l.row().gemm) continue;
+            const CopyShapes c = copy_shapes(l);
+            l.wbf_off = off; off += (long long)l.CoutP * c.Kpf;
+            l.wbb_off = off; off += c.cin * c.Kpb;
             off = (off + 63) / 64 * 64;
-            q += 2;
         }
-        if (q > kMaxPrepJobs) { for (Layer& l : n->L) l.wbf_off = l.wbb_off = -1; return 0; }       // more layers than one launch takes: per-layer copies as before
         XTRY(n, n->wb16.ensure((size_t)(off > 0 ? off : 1) * sizeof(__bf16)));
         n->prep.njobs = 0;
         for (size_t i = 1; i < n->L.size(); ++i) {
             Layer& l = n->L[i];
-            if (!has_bf16_copies(l.kind)) continue;
-            const int ks = filter_size(l.kind);
-            const long long cin = l.K / (ks * ks);
-            const long long Kf = (long long)ks * ks * cin, Kpf = (Kf + 31) / 32 * 32, Kb = (long long)ks * ks * l.CoutP, Kpb = (Kb + 31) / 32 * 32;
+            if (!l.row().gemm) continue;
+            const CopyShapes c = copy_shapes(l);
             PrepJob& a = n->prep.j[n->prep.njobs++];
-            a = PrepJob{(const float*)P(n, l.w_off), (__bf16*)n->wb16.p + l.wbf_off, (int)Kf, l.CoutP, (int)Kpf, (int)blocks};
-            blocks += prep_job_blocks(l.CoutP, (int)Kpf);
+            a = PrepJob{(const float*)P(n, l.w_off), (__bf16*)n->wb16.p + l.wbf_off, (int)c.Kf, l.CoutP, (int)c.Kpf, (int)blocks};
+            blocks += prep_job_blocks(l.CoutP, (int)c.Kpf);
             PrepJob& b = n->prep.j[n->prep.njobs++];
-            b = PrepJob{(const float*)n->wt.p + l.w_off, (__bf16*)n->wb16.p + l.wbb_off, (int)Kb, (int)cin, (int)Kpb, (int)blocks};
-            blocks += prep_job_blocks((int)cin, (int)Kpb);
+            b = PrepJob{(const float*)n->wt.p + l.w_off, (__bf16*)n->wb16.p + l.wbb_off, (int)c.Kb, (int)c.cin, (int)c.Kpb, (int)blocks};
+            blocks += prep_job_blocks((int)c.cin, (int)c.Kpb);
         }
         n->prep_blocks = blocks;
     }
@@ -718,11 +728,11 @@ int launch_dropout_bwd(rcn_hipx_net* n, size_t i, int B) {
 
 // ---- batch normalisation (convnet_bn.hpp): a RCN_HIPX_BN_RELU layer normalises the map of the RCN_HIPX_CONV3X3 layer in front of it
 inline const char* const kBnStoreGap = "bf16 storage (RCN_HIPX_BF16_STORED) does not cover batch normalisation: its maps are fp32 (RCN_HIPX_BF16 rounds the convolutions' operands and works)";
-int bn_layers(const rcn_hipx_net* n) { int k = 0; for (const Layer& l : n->L) k += is_bn(l.kind); return k; }
+int bn_layers(const rcn_hipx_net* n) { int k = 0; for (const Layer& l : n->L) k += l.row().bn; return k; }
 // a training forward needs two rows per channel at least (the unbiased variance): asked before anything is enqueued
 int bn_rows_ok(rcn_hipx_net* n, int B) {
     for (const Layer& l : n->L)
-        if (is_bn(l.kind) && (long long)B * l.oH * l.oW < 2) return fail(n, -2, "batch normalisation needs at least two rows (B * H * W >= 2) in a training forward");
+        if (l.row().bn && (long long)B * l.oH * l.oW < 2) return fail(n, -2, "batch normalisation needs at least two rows (B * H * W >= 2) in a training forward");
     return 0;
 }
 float* bn_mean(const Layer& l) { return (float*)l.bn.p; }
@@ -732,7 +742,7 @@ float* bn_run_var(const Layer& l) { return (float*)l.bn.p + 3 * l.CoutP; }
 // running mean 0, running variance 1 in every such layer, on the net's stream
 int bn_reset_stats(rcn_hipx_net* n) {
     for (const Layer& l : n->L) {
-        if (!is_bn(l.kind)) continue;
+        if (!l.row().bn) continue;
         const std::vector<float> init = [&] { std::vector<float> v((size_t)4 * l.CoutP, 0.f); for (int c = 0; c < l.CoutP; ++c) v[(size_t)3 * l.CoutP + c] = 1.f; return v; }();
         XTRY(n, hipMemcpyAsync(l.bn.p, init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice, n->stream));
         XTRY(n, hipStreamSynchronize(n->stream));       // (the staging vector ends here)
@@ -839,35 +849,24 @@ int forward(rcn_hipx_net* n, const float* x, int B, size_t n_layers = (size_t)-1
             hipLaunchKernelGGL(k_pool_fwd, dim3(grid1d(tot, 256)), dim3(256), 0, n->stream, cur, (float*)l.out.p, (uint8_t*)l.idx.p, B, l.H, l.W, l.Cin);
             XTRY(n, hipGetLastError());
         } else if (l.kind == RCN_HIPX_CONV3X3_RELU) {
-            const ConvShape cs{B, l.H, l.W, l.Cin, l.CoutP};
-            if (l.pool_follows && conv_pool_fusable(*n, cs)) {
-                // the pool that follows runs in this kernel's epilogue: only the pooled map (and its arg-max image) is written
-                Layer& pl = n->L[i + 1];
-                RTRY(launch_conv(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)pl.out.p, cs, 3, 4, (uint8_t*)pl.idx.p, nullptr, false, wb_of(n, l.wbf_off), Store{cur16, n->store16}));
-                cur = (const float*)pl.out.p;
-                cur16 = n->store16;
-                ++i;
-                continue;
-            }
-            RTRY(launch_conv(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, cs, 3, 2, nullptr, nullptr, false, wb_of(n, l.wbf_off), Store{cur16, n->store16}));
-            cur = (const float*)l.out.p;
+            // where the pool that follows runs in this kernel's epilogue (4), only the pooled map (and its arg-max image) is written: that layer's
+            const ConvShape cs = l.gemm(B);
+            const bool fused = l.pool_follows && conv_pool_fusable(*n, cs);
+            Layer& to = fused ? n->L[i + 1] : l;
+            RTRY(launch_conv(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)to.out.p, cs, 3, fused ? 4 : 2, fused ? (uint8_t*)to.idx.p : nullptr, nullptr, false, wb_of(n, l.wbf_off), Store{cur16, n->store16}));
+            cur = (const float*)to.out.p;
             cur16 = n->store16;
+            i += fused;
             continue;
-        } else if (is_conv_linear(l.kind)) {
-            // bias only (epilogue 1), no conv+pool fusion: what follows is batch normalisation, on an fp32 map
+        } else if (l.row().linear || l.row().bn) {
+            // a bias-only layer (epilogue 1, no conv+pool fusion) and the batch normalisation that follows it: on fp32 maps
             if (n->store16) return fail(n, -3, kBnStoreGap);
-            if (l.kind == RCN_HIPX_CONV3X3_S2) RTRY(launch_conv_s2(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShapeS2{B, l.H, l.W, l.Cin, l.CoutP}, 1, wb_of(n, l.wbf_off)));
-            else if (l.kind == RCN_HIPX_CONV1X1) RTRY(launch_pw(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShape{B, l.H, l.W, l.Cin, l.CoutP}, 1, wb_of(n, l.wbf_off)));
-            else if (l.kind == RCN_HIPX_DWCONV3X3) RTRY(launch_dw(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShape{B, l.H, l.W, l.Cin, l.CoutP}, 1));
-            else RTRY(launch_conv(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShape{B, l.H, l.W, l.Cin, l.CoutP}, 3, 1, nullptr, nullptr, false, wb_of(n, l.wbf_off)));
-        } else if (is_bn(l.kind)) {
-            if (n->store16) return fail(n, -3, kBnStoreGap);
-            RTRY(launch_bn_forward(n, i, cur, B, train));
+            if (l.row().bn) RTRY(launch_bn_forward(n, i, cur, B, train)); else RTRY(layer_forward(n, l, B, cur, (float*)l.out.p));
         } else if (l.kind == RCN_HIPX_GLOBAL_AVGPOOL) {
             RTRY(launch_gap_forward(n, i, cur, B));
         } else {
             // (the logits layer of a head that training runs as k_head_f32 is fp32 here too: what bf16 mode rounds is a matter of shape)
-            RTRY(launch_conv(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, ConvShape{B, 1, 1, l.K, l.CoutP}, 1, l.kind == RCN_HIPX_DENSE_RELU ? 2 : 1, nullptr, nullptr,
+            RTRY(launch_conv(n, cur, P(n, l.w_off), P(n, l.b_off), (float*)l.out.p, l.gemm(B), 1, l.kind == RCN_HIPX_DENSE_RELU ? 2 : 1, nullptr, nullptr,
                              i + 1 == n->L.size() && head_fusable(n), wb_of(n, l.wbf_off), Store{cur16, false}));
             if (drop && l.kind == RCN_HIPX_DENSE_RELU) RTRY(launch_dropout_fwd(n, dropout_site_of(n, i), (float*)l.out.p, B, l.CoutP, (const long long*)n->drop_tick.p, 0));
         }
@@ -879,16 +878,17 @@ int forward(rcn_hipx_net* n, const float* x, int B, size_t n_layers = (size_t)-1
 
 // The slab of partial [W | b] tiles of layer i (chunks x (K + 1) x Cout, as the weight-gradient kernels leave it in the layer's slab)
 // is queued for the step's ONE reduction launch (run_reduce_jobs): summed in chunk order, and either applied (p <- p - lr g, the flipped
-// copy of the weights kept current) or written to grad.  [W | b] is contiguous (b_off == w_off + K * CoutP): one job finishes both.
-int reduce_slab(rcn_hipx_net* n, size_t i, int chunks, int ks, const ConvShape& s, float* grad, bool apply) {
+// copy of the weights kept current) or written to grad.  [W | b] is contiguous (b_off == w_off + K * CoutP): one job finishes both.  Its
+// geometry is the layer's own (taps, cin): a depthwise layer's n = 10 C with FlipSpec{wt, 9, 1, C}, [d gamma | d beta] n = 2 C, no flipped copy.
+int reduce_slab(rcn_hipx_net* n, size_t i, int chunks, float* grad, bool apply) {
     Layer& l = n->L[i];
     if (n->jobs.njobs >= kMaxReduceJobs) return fail(n, -3, "too many layers with parameters for one reduction launch");
     ReduceJob& jb = n->jobs.j[n->jobs.njobs];
     jb.p = P(n, l.w_off);
     jb.grad = grad ? grad + l.w_off : (float*)nullptr;
     jb.slab = (const float*)l.slab.p;
-    jb.flip = FlipSpec{(apply && i > 0 && has_matrix(l.kind)) ? (float*)n->wt.p + l.w_off : (float*)nullptr, ks * ks, s.Cin, s.Cout};
-    jb.n = ((long long)s.Cin * ks * ks + 1) * s.Cout;
+    jb.flip = FlipSpec{(apply && i > 0 && l.row().matrix) ? (float*)n->wt.p + l.w_off : (float*)nullptr, l.taps(), l.cin(), l.CoutP};
+    jb.n = ((long long)l.K + 1) * l.CoutP;
     if (jb.n % 4 != 0 || l.w_off % 4 != 0) return fail(n, -3, "internal: a layer's [W | b] is not a whole number of 16-byte pieces");
     jb.chunks = chunks;
     int prev_end = 0;
@@ -929,7 +929,7 @@ int launch_bn_backward(rcn_hipx_net* n, size_t i, int B, bool gated, float* grad
                                 (const float*)bn_invstd(l), (const float*)P(n, l.w_off), (const float*)l.slab.p);
         XTRY(n, hipGetLastError());
     }
-    return reduce_slab(n, i, 1, 1, ConvShape{B, 1, 1, 1, C}, grad, apply);
+    return reduce_slab(n, i, 1, grad, apply);
 }
 
 // The skip's half of the backward pass of the RCN_HIPX_BN_ADD_RELU layer fed by layer `src`: that layer's dout (the gradient of the sum,
@@ -984,10 +984,9 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
         if (l.kind == RCN_HIPX_MAXPOOL2) {
             // When the LDS-tiled kernels run both consumers of the convolution's dZ (its weight gradient, and its input gradient if
             // it has one), they rebuild dZ from (dP, P, arg-max) at pooled resolution while staging: no k_pool_bwd, no full-size dZ.
-            const int fuse_on = n->opt.fuse_pool_bwd;
             const Layer& cl = n->L[i - 1];
-            const ConvShape cs{B, cl.H, cl.W, cl.Cin, cl.CoutP};
-            const bool fusable = fuse_on && cl.kind == RCN_HIPX_CONV3X3_RELU && wgrad_halo_runs(*n, cs, 3) && (i - 1 == 0 || conv_halo_runs(*n, ConvShape{B, cl.H, cl.W, cl.CoutP, cl.Cin}));
+            const ConvShape cs = cl.gemm(B);
+            const bool fusable = n->opt.fuse_pool_bwd && cl.kind == RCN_HIPX_CONV3X3_RELU && wgrad_halo_runs(*n, cs, 3) && (i - 1 == 0 || conv_halo_runs(*n, ConvShape{B, cl.H, cl.W, cl.CoutP, cl.Cin}));
             if (fusable) {
                 pooled[i - 1] = PooledGrad{(const float*)l.dout.p, (const float*)l.out.p, (const uint8_t*)l.idx.p};
                 if (dry_note(n, "  pool-bwd %dx%dx%d: none (the convolution's gradient kernels unpool while staging)", l.H, l.W, l.Cin))
@@ -997,10 +996,9 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             // gradient wrt the pool INPUT, with the preceding conv's (or batch normalisation's) ReLU mask folded in (pooled value > 0)
             const long long tot = (long long)B * l.oH * l.oW * (l.Cin / 4);
             if (dry_note(n, "  pool-bwd %dx%dx%d: k_pool_bwd", l.H, l.W, l.Cin)) continue;
-            if (n->store16) hipLaunchKernelGGL(k_pool_bwd<__bf16>, dim3(grid1d(tot, 256)), dim3(256), 0, n->stream, (const __bf16*)l.dout.p, (const __bf16*)l.out.p, (const uint8_t*)l.idx.p,
-                                               (__bf16*)din, B, l.H, l.W, l.Cin);
-            else hipLaunchKernelGGL(k_pool_bwd<float>, dim3(grid1d(tot, 256)), dim3(256), 0, n->stream, (const float*)l.dout.p, (const float*)l.out.p, (const uint8_t*)l.idx.p,
-                                    din, B, l.H, l.W, l.Cin);
+            with_storage(n->store16, [&](auto T) {
+                hipLaunchKernelGGL(k_pool_bwd<CT(T)>, dim3(grid1d(tot, 256)), dim3(256), 0, n->stream, (const CT(T)*)l.dout.p, (const CT(T)*)l.out.p, (const uint8_t*)l.idx.p, (CT(T)*)din, B, l.H, l.W, l.Cin);
+            });
             XTRY(n, hipGetLastError());
             continue;
         }
@@ -1013,22 +1011,17 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             gated[i - 1] = gate;
             continue;
         }
-        if (is_bn(l.kind)) {
+        if (l.row().bn) {
             // its dout is gated by the pool's backward, by the convolution or by the global average pool above (n->bw.gated); otherwise it gates itself
             RTRY(launch_bn_backward(n, (size_t)i, B, l.pool_follows || gated[i], grad, apply));
             continue;
         }
-        // conv: the layer's rows are the pixels of a map (a 3x3 or a 1x1 convolution); pw: the 1x1 convolution, whose forward pass and input
-        // gradient have their own selector (launch_pw) and whose weight gradient is the KS = 1 kernels' with rows walking the H x W map
-        // dw: the depthwise 3x3 convolution, no GEMM -- its own stencil and weight-gradient kernels (launch_dw, launch_dw_wgrad); its [W | b] block is
-        // that of a 3x3 convolution of ONE input channel, and as such (sr) it goes to reduce_slab: n = 10 C, FlipSpec{wt, 9, 1, C}
-        const bool conv = on_map(l.kind), strided = l.kind == RCN_HIPX_CONV3X3_S2, pw = l.kind == RCN_HIPX_CONV1X1, dw = l.kind == RCN_HIPX_DWCONV3X3;
-        const int ks = filter_size(l.kind);
-        const ConvShape s = conv ? ConvShape{B, l.H, l.W, l.Cin, l.CoutP} : ConvShape{B, 1, 1, l.K, l.CoutP};      // (H x W: the layer's INPUT map; a strided layer's output is l.oH x l.oW)
-        const long long M = (long long)s.N * l.oH * l.oW;
+        // a layer with a [W | b] block: a convolution of any kind, whose rows are the pixels of a map, or a dense layer
+        const bool conv = l.row().map;
+        const long long M = (long long)B * l.oH * l.oW;
         // dZ: gradient wrt the pre-activation
         const float* dZ = (const float*)l.dout.p;
-        if (l.kind != RCN_HIPX_DENSE && !is_conv_linear(l.kind) && !l.pool_follows && !gated[i]) {
+        if (l.row().relu && !l.pool_follows && !gated[i]) {
             if (stage16(n, i)) return fail(n, -3, kStoreGap);
             XTRY(n, scratch_ensure(n, n->dz, (size_t)M * l.CoutP * sizeof(float)));
             if (!dry_note(n, "  relu-bwd: k_relu_bwd")) {
@@ -1041,25 +1034,17 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
         // input.  Not when dZ sits in the shared scratch buffer, which the main stream reuses for the next layer.
         const bool on_side = ov && dZ != (const float*)n->dz.p && (n->overlap != 2 || !conv);     // 2: only the (latency-bound) dense layers
         if (on_side) { RTRY(stream_after(n, main_s, n->side)); side_busy = true; }
+        const PooledGrad* const pdz = pooled[i].dP ? &pooled[i] : nullptr;      // dZ exists only at pooled resolution (the pool above fused its backward away)
         // dgrad first (needs the weights BEFORE this step's update): dX = conv(dZ, flip(W)^T)
         if (din) {
-            // the tap-flipped transposed weights are kept current by every kernel that writes a weight (FlipSpec, refresh_flipped)
-            const float* wt = (const float*)n->wt.p + l.w_off;
             // the layer below is a ReLU layer feeding this one directly (no pool in between): gate the gradient with its output in
             // this kernel's epilogue, so that layer finds its dZ ready instead of running a k_relu_bwd pass over the tensor
             const Layer& below = n->L[i - 1];
             // (batch normalisation below a convolution: gated here with its output, the same out > 0 rule; below a dense layer it gates itself;
             // a global average pool below has no ReLU of its own and is NOT named here: its dout stays the plain gradient of the means)
-            const bool gate = below.kind == RCN_HIPX_CONV3X3_RELU || below.kind == RCN_HIPX_DENSE_RELU || (is_bn(below.kind) && conv);
-            // (a strided layer: one launch over the four parity classes of the input pixels writes ALL of dout[i - 1], every element once)
-            if (strided) RTRY(launch_dgrad_s2(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, ConvShapeS2T{s.N, s.H, s.W, s.Cout, s.Cin}, gate ? 3 : 0, wb_of(n, l.wbb_off)));
-            // (a 1x1 layer: k_pw, or the implicit GEMM on the map, writes ALL of dout[i - 1], every element once -- what the skip's add below rests on)
-            else if (pw) RTRY(launch_pw(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, ConvShape{s.N, s.H, s.W, s.Cout, s.Cin}, gate ? 3 : 0, wb_of(n, l.wbb_off)));
-            // (a depthwise layer: k_dw's tiles partition the map and a lane stores each of its pieces once -- ALL of dout[i - 1], every element
-            // once, by one thread, with no second launch and no accumulation: the same ground for the skip's add below)
-            else if (dw) RTRY(launch_dw(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, s, gate ? 3 : 0));
-            else RTRY(launch_conv(n, dZ, wt, gate ? (const float*)below.out.p : nullptr, din, ConvShape{s.N, s.H, s.W, s.Cout, s.Cin}, ks, gate ? 3 : 0,
-                             nullptr, pooled[i].dP ? &pooled[i] : nullptr, false, wb_of(n, l.wbb_off), Store{stage16(n, i), stage16(n, i - 1)}));
+            const bool gate = below.row().relu && (!below.row().bn || conv);
+            // (whatever the layer's kind, this launch writes ALL of dout[i - 1], every element once: what the skip's add below rests on)
+            RTRY(layer_dgrad(n, l, B, dZ, gate ? &below : nullptr, din, pdz, Store{stage16(n, i), stage16(n, i - 1)}));
             gated[i - 1] = gate;
             if (below.kind == RCN_HIPX_DENSE_RELU && dropout_on(*n)) RTRY(launch_dropout_bwd(n, (size_t)i - 1, B));      // before anything reads that gradient
             // The layer below feeds the skip of a RCN_HIPX_BN_ADD_RELU layer further up: its gradient has a second contribution, and HERE
@@ -1074,10 +1059,8 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
         int chunks = 0;
         if (on_side) n->stream = n->side;
         n->slab_sel = &l.slab;
-        if (strided) RTRY(launch_wgrad_s2(n, in, dZ, ConvShapeS2{s.N, s.H, s.W, s.Cin, s.Cout}, &chunks));
-        else if (dw) RTRY(launch_dw_wgrad(n, in, dZ, s, &chunks));
-        else RTRY(launch_wgrad(n, in, dZ, s, ks, &chunks, pooled[i].dP ? &pooled[i] : nullptr, Store{stage16(n, i - 1), stage16(n, i)}, pw));
-        RTRY(reduce_slab(n, (size_t)i, chunks, ks, dw ? ConvShape{s.N, s.H, s.W, 1, s.Cout} : s, grad, apply));
+        RTRY(layer_wgrad(n, l, B, in, dZ, &chunks, pdz, Store{stage16(n, i - 1), stage16(n, i)}));
+        RTRY(reduce_slab(n, (size_t)i, chunks, grad, apply));
         n->stream = main_s;
     }
     return 0;
@@ -1186,11 +1169,8 @@ int launch_head(rcn_hipx_net* n, const int32_t* labels, int B, float* loss_dev, 
 int refresh_flipped(rcn_hipx_net* n) {
     for (size_t i = 1; i < n->L.size(); ++i) {
         const Layer& l = n->L[i];
-        if (!has_matrix(l.kind)) continue;
-        const int ks = filter_size(l.kind);
-        const int cin = l.K / (ks * ks);
-        const long long wn = (long long)l.K * l.CoutP;
-        hipLaunchKernelGGL(k_flip_weights, dim3(grid1d(wn, 256)), dim3(256), 0, n->stream, (const float*)P(n, l.w_off), (float*)n->wt.p + l.w_off, ks, cin, l.CoutP);
+        if (!l.row().matrix) continue;
+        hipLaunchKernelGGL(k_flip_weights, dim3(grid1d((long long)l.K * l.CoutP, 256)), dim3(256), 0, n->stream, (const float*)P(n, l.w_off), (float*)n->wt.p + l.w_off, l.row().ks, l.cin(), l.CoutP);
     }
     XTRY(n, hipGetLastError());
     return 0;
@@ -1216,7 +1196,7 @@ int step_front(rcn_hipx_net* n, const float* x, const int32_t* labels, int B, fl
     n->slab_sel = &n->L[last].slab;
     RTRY(launch_head(n, labels, B, loss_dev, &chunks, pair));
     if (dropout_on(*n)) RTRY(launch_dropout_bwd(n, (size_t)last - 1, B));      // (the head wrote the gated gradient into the site layer's dout)
-    return reduce_slab(n, (size_t)last, chunks, 1, ConvShape{B, 1, 1, n->L[last].K, n->L[last].CoutP}, grad, apply);
+    return reduce_slab(n, (size_t)last, chunks, grad, apply);
 }
 
 // forward + loss + backward of one batch: parameters updated in place (apply) or gradients written to grad (padded layout)
@@ -1243,10 +1223,10 @@ int bucket_layout(rcn_hipx_net* n, long long min_bytes) {
     long long acc = 0, end = n->n_pad;
     int first_param = -1;
     for (int i = 0; i < (int)n->L.size(); ++i)
-        if (has_params(n->L[i].kind)) { first_param = i; break; }
+        if (n->L[i].row().params) { first_param = i; break; }
     for (int i = (int)n->L.size() - 1; i >= 0; --i) {
         const Layer& l = n->L[i];
-        if (!has_params(l.kind)) continue;
+        if (!l.row().params) continue;
         acc = (end - l.w_off) * (long long)sizeof(float);
         if (acc >= min_bytes || i == first_param) {
             bw.lo.push_back(i); bw.off.push_back(l.w_off); bw.len.push_back(end - l.w_off);
@@ -1290,82 +1270,60 @@ int grad_bucket(rcn_hipx_net* n, int k, long long* off, long long* len) {
     return 0;
 }
 
-}  // namespace
-
-namespace {
 // the layer table of a net (shapes, padded sizes, parameter offsets) from its description; no device involved
 int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hipx_layer* layers, int n_layers) {
     int H = in_h, W = in_w, C = in_c;
     bool flat = false;
+    // "layer i (KIND): " in front of the refusals of a kind that names its layer; the older kinds' refusals stand unprefixed
+    auto at_layer = [](int i, int kind) { return kind_row(kind).named ? "layer " + std::to_string(i) + " (" + kind_row(kind).name + "): " : std::string(); };
     for (int i = 0; i < n_layers; ++i) {
         Layer l{};
         l.kind = layers[i].kind; l.H = H; l.W = W; l.Cin = C;
-        if (i > 0 && n->L.back().kind == RCN_HIPX_CONV3X3_S2 && !is_bn(l.kind))
-            return fail(n, -2, "layer " + std::to_string(i - 1) + " (RCN_HIPX_CONV3X3_S2): it must be followed directly by a batch-normalisation layer (RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_BN_ADD_RELU_DOWN)");
-        if (i > 0 && n->L.back().kind == RCN_HIPX_CONV1X1 && !is_bn(l.kind))
-            return fail(n, -2, "layer " + std::to_string(i - 1) + " (RCN_HIPX_CONV1X1): it must be followed directly by a batch-normalisation layer (RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_BN_ADD_RELU_DOWN)");
-        if (i > 0 && n->L.back().kind == RCN_HIPX_DWCONV3X3 && !is_bn(l.kind))
-            return fail(n, -2, "layer " + std::to_string(i - 1) + " (RCN_HIPX_DWCONV3X3): it must be followed directly by a batch-normalisation layer (RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_BN_ADD_RELU_DOWN)");
-        if (l.kind == RCN_HIPX_DWCONV3X3) {
-            // torch.nn.Conv2d(C, C, 3, padding=1, groups=C): a [W | b] block with K = 9 and Cout = C on the H x W map, in front of batch
-            // normalisation.  `out`: 0 or C (the resolved width is what the state descriptor stores); no gather form
-            const std::string at = "layer " + std::to_string(i) + " (RCN_HIPX_DWCONV3X3): ";
+        const int pk = i > 0 ? n->L.back().kind : -1;          // the layer in front (-1: none, a row that is nothing)
+        const KindRow &k = l.row(), &prev = kind_row(pk);
+        const int out = layers[i].out;
+        const std::string at = at_layer(i, l.kind);
+        // A bias-only layer must be followed directly by batch normalisation.  For the kinds that name their layer this is said before the
+        // next layer's own checks run; for RCN_HIPX_CONV3X3 behind them (below the branches).
+        if (prev.linear && prev.named && !k.bn) return fail(n, -2, at_layer(i - 1, pk) + "it must be followed directly by a batch-normalisation layer (RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_BN_ADD_RELU_DOWN)");
+        if (k.map) {
+            // torch.nn.Conv2d(C, out, ks, stride, padding = ks / 2) on the H x W map: a [W | b] block with K = ks * ks * C.  The depthwise one
+            // (groups = C): K = 9 and Cout = C, `out` 0 or C (the resolved width is what the state descriptor stores).  Stride 2, pad 1: the
+            // output is (H/2) x (W/2), no odd maps in this version.  Only the stride-1 3x3 GEMM kinds have a gather form for a first layer of
+            // 9 * Cin <= 32; every other kind's rows are whole 16-byte pieces of a map of a multiple of 32 channels.
+            const bool dw = l.kind == RCN_HIPX_DWCONV3X3, conv3 = k.gemm && k.ks == 3;
             if (flat) return fail(n, -2, at + "convolution after a dense layer or a global average pool");
-            if (layers[i].out != 0 && layers[i].out != C)
-                return fail(n, -2, at + "out must be 0 or the input channels " + std::to_string(C) + " (depth multiplier 1), not " + std::to_string(layers[i].out));
-            if (C % 32) return fail(n, -3, at + "its input channels must be a multiple of 32, not " + std::to_string(C) + " (no first-layer gather form)");
-            l.Cout = l.CoutP = C; l.oH = H; l.oW = W; l.K = 9;
-        } else if (l.kind == RCN_HIPX_CONV1X1) {
-            // torch.nn.Conv2d(C, out, 1): a [W | b] block with K = C on the H x W map, in front of batch normalisation.  No gather form:
-            // the rows are whole 16-byte pieces of a map of a multiple of 32 channels (so not the first layer of a 1- or 3-channel input)
-            const std::string at = "layer " + std::to_string(i) + " (RCN_HIPX_CONV1X1): ";
-            if (flat) return fail(n, -2, at + "convolution after a dense layer or a global average pool");
-            if (layers[i].out < 32 || layers[i].out % 32) return fail(n, -3, at + "conv output channels must be a positive multiple of 32");
-            if (C % 32) return fail(n, -3, at + "its input channels must be a multiple of 32, not " + std::to_string(C) + " (no first-layer gather form)");
-            l.Cout = l.CoutP = layers[i].out; l.oH = H; l.oW = W; l.K = C;
-            C = l.Cout;
-        } else if (is_conv(l.kind)) {
-            if (flat) return fail(n, -2, l.kind == RCN_HIPX_CONV3X3_S2 ? "layer " + std::to_string(i) + " (RCN_HIPX_CONV3X3_S2): convolution after a dense layer or a global average pool"
-                                                                       : std::string("convolution after a dense layer or a global average pool"));
-            if (layers[i].out < 32 || layers[i].out % 32)
-                return fail(n, -3, l.kind == RCN_HIPX_CONV3X3_S2 ? "layer " + std::to_string(i) + " (RCN_HIPX_CONV3X3_S2): conv output channels must be a positive multiple of 32"
-                                                                 : std::string("conv output channels must be a positive multiple of 32"));
-            if (!(9 * C <= 32) && C % 32) return fail(n, -3, "conv input channels must be a multiple of 32 (or 9*Cin <= 32 for the first layer)");
-            l.Cout = l.CoutP = layers[i].out; l.oH = H; l.oW = W; l.K = 9 * C;
-            if (l.kind == RCN_HIPX_CONV3X3_S2) {
-                // stride 2, pad 1: the output is (H/2) x (W/2).  No strided first-layer gather form, no odd maps in this version.
-                const std::string at = "layer " + std::to_string(i) + " (RCN_HIPX_CONV3X3_S2): ";
-                if (H % 2 || W % 2) return fail(n, -3, at + "a strided convolution needs even height and width, not " + std::to_string(H) + "x" + std::to_string(W));
-                if (C % 32) return fail(n, -3, at + "its input channels must be a multiple of 32, not " + std::to_string(C) + " (no strided first-layer form)");
-                l.oH = H / 2; l.oW = W / 2;
-                H = l.oH; W = l.oW;
-            }
-            C = l.Cout;
+            if (dw && out != 0 && out != C) return fail(n, -2, at + "out must be 0 or the input channels " + std::to_string(C) + " (depth multiplier 1), not " + std::to_string(out));
+            if (!dw && (out < 32 || out % 32)) return fail(n, -3, at + "conv output channels must be a positive multiple of 32");
+            // (every 3x3 GEMM kind words this one the same way, the strided one too)
+            if (conv3 && !(9 * C <= 32) && C % 32) return fail(n, -3, "conv input channels must be a multiple of 32 (or 9*Cin <= 32 for the first layer)");
+            if (k.stride == 2 && (H % 2 || W % 2)) return fail(n, -3, at + "a strided convolution needs even height and width, not " + std::to_string(H) + "x" + std::to_string(W));
+            if (!(conv3 && k.stride == 1) && C % 32) return fail(n, -3, at + "its input channels must be a multiple of 32, not " + std::to_string(C) + (k.stride == 2 ? " (no strided first-layer form)" : " (no first-layer gather form)"));
+            l.Cout = l.CoutP = dw ? C : out; l.oH = H / k.stride; l.oW = W / k.stride; l.K = dw ? 9 : k.ks * k.ks * C;
+            H = l.oH; W = l.oW; C = l.Cout;
         } else if (l.kind == RCN_HIPX_MAXPOOL2) {
-            if (flat || i == 0 || (n->L.back().kind != RCN_HIPX_CONV3X3_RELU && !is_bn(n->L.back().kind))) return fail(n, -2, "max-pool must follow a convolution");
+            if (flat || i == 0 || (pk != RCN_HIPX_CONV3X3_RELU && !prev.bn)) return fail(n, -2, "max-pool must follow a convolution");
             if (H % 2 || W % 2) return fail(n, -3, "max-pool needs even height and width");
             l.Cout = l.CoutP = C; l.oH = H / 2; l.oW = W / 2; l.K = 0;
             n->L.back().pool_follows = true;
             H = l.oH; W = l.oW;
         } else if (l.kind == RCN_HIPX_BN_RELU) {
-            if (i == 0 || !is_conv_linear(n->L.back().kind)) return fail(n, -2, "batch normalisation (RCN_HIPX_BN_RELU) must directly follow a RCN_HIPX_CONV3X3 layer (of either stride) or a RCN_HIPX_CONV1X1 layer");
+            if (!prev.linear) return fail(n, -2, "batch normalisation (RCN_HIPX_BN_RELU) must directly follow a RCN_HIPX_CONV3X3 layer (of either stride) or a RCN_HIPX_CONV1X1 layer");
             l.Cout = l.CoutP = C; l.oH = H; l.oW = W; l.K = 1;      // [gamma | beta]: a [W | b] block with K = 1
         } else if (l.kind == RCN_HIPX_BN_ADD_RELU || l.kind == RCN_HIPX_BN_ADD_RELU_DOWN) {
             // `out` is the distance to the skip's source, the output of layer i - out.  The source needs a gradient buffer that the
             // input-gradient kernel of the layer above it writes in full (backward_layers adds the skip's share behind that launch) and an
             // output that the forward pass writes: a ReLU layer or a pool of this layer's shape, not a convolution whose pool is fused away.
-            const int d = layers[i].out;
             // RCN_HIPX_BN_ADD_RELU_DOWN: the same, but the source is twice this layer's height and width and may be narrower (option-A shortcut)
             const bool down = l.kind == RCN_HIPX_BN_ADD_RELU_DOWN;
-            const std::string at = "layer " + std::to_string(i) + (down ? " (RCN_HIPX_BN_ADD_RELU_DOWN): " : " (RCN_HIPX_BN_ADD_RELU): ");
-            if (i == 0 || !is_conv_linear(n->L.back().kind)) return fail(n, -2, at + "it must directly follow a RCN_HIPX_CONV3X3 layer (of either stride) or a RCN_HIPX_CONV1X1 layer");
-            if (d < 2) return fail(n, -1, at + "out is the distance to the skip's source and must be at least 2, not " + std::to_string(d));
-            const int src = i - d;
+            if (!prev.linear) return fail(n, -2, at + "it must directly follow a RCN_HIPX_CONV3X3 layer (of either stride) or a RCN_HIPX_CONV1X1 layer");
+            if (out < 2) return fail(n, -1, at + "out is the distance to the skip's source and must be at least 2, not " + std::to_string(out));
+            const int src = i - out;
             if (src < 0) return fail(n, -2, at + "the skip's source would lie in front of layer 0 (the net's input has no gradient buffer to add into)");
             l.Cout = l.CoutP = C; l.oH = H; l.oW = W; l.K = 1;
             Layer& s = n->L[src];
             const std::string from = at + "the skip's source, layer " + std::to_string(src) + ", ";
-            if (s.kind != RCN_HIPX_CONV3X3_RELU && s.kind != RCN_HIPX_MAXPOOL2 && !is_bn(s.kind))
+            if (s.kind != RCN_HIPX_CONV3X3_RELU && s.kind != RCN_HIPX_MAXPOOL2 && !s.row().bn)
                 return fail(n, -2, from + "must be a RCN_HIPX_CONV3X3_RELU, RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_MAXPOOL2 layer (a RCN_HIPX_CONV3X3 map is not yet normalised)");
             if (s.pool_follows) return fail(n, -2, from + "has a max-pool behind it: its own output is not written when the two fuse -- the source must be the pool");
             if (down) {
@@ -1382,43 +1340,37 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
         } else if (l.kind == RCN_HIPX_GLOBAL_AVGPOOL) {
             // [B][H][W][C] -> [B][C]: the dense stage begins (flat), C unchanged, so the dense layer behind has K = C; no parameter block.  The
             // map in front must be one the forward pass writes in fp32 behind a ReLU or a max-pool (a bare RCN_HIPX_CONV3X3 is refused below)
-            const std::string at = "layer " + std::to_string(i) + " (RCN_HIPX_GLOBAL_AVGPOOL): ";
             if (i == 0) return fail(n, -2, at + "it cannot be the first layer: it pools the map of a convolution, batch normalisation or max-pool layer");
             if (flat) return fail(n, -2, at + "it must follow a map, not a dense layer or another global average pool (layer " + std::to_string(i - 1) + ")");
-            const int bk = n->L.back().kind;
-            if (bk != RCN_HIPX_CONV3X3 && bk != RCN_HIPX_CONV3X3_RELU && bk != RCN_HIPX_MAXPOOL2 && !is_bn(bk))
+            if (pk != RCN_HIPX_CONV3X3 && pk != RCN_HIPX_CONV3X3_RELU && pk != RCN_HIPX_MAXPOOL2 && !prev.bn)
                 return fail(n, -2, at + "it must directly follow a RCN_HIPX_CONV3X3_RELU, RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_MAXPOOL2 layer");
             l.Cout = l.CoutP = C; l.oH = l.oW = 1; l.K = 0;
             flat = true; H = W = 1;
         } else if (l.kind == RCN_HIPX_DENSE_RELU || l.kind == RCN_HIPX_DENSE) {
             const long long feat = flat ? C : (long long)H * W * C;
             if (feat % 32 || feat > 0x7fffffff) return fail(n, -3, "dense input features must be a multiple of 32");
-            if (layers[i].out < 1) return fail(n, -1, "dense units must be positive");
-            if (l.kind == RCN_HIPX_DENSE_RELU && layers[i].out % 32) return fail(n, -3, "hidden dense units must be a multiple of 32");
+            if (out < 1) return fail(n, -1, "dense units must be positive");
+            if (l.kind == RCN_HIPX_DENSE_RELU && out % 32) return fail(n, -3, "hidden dense units must be a multiple of 32");
             if (l.kind == RCN_HIPX_DENSE && i != n_layers - 1) return fail(n, -2, "the logits layer must be last");
-            l.K = (int)feat; l.H = 1; l.W = 1; l.Cin = (int)feat; l.Cout = layers[i].out; l.CoutP = (l.Cout + 31) / 32 * 32; l.oH = l.oW = 1;
+            l.K = (int)feat; l.H = 1; l.W = 1; l.Cin = (int)feat; l.Cout = out; l.CoutP = (l.Cout + 31) / 32 * 32; l.oH = l.oW = 1;
             C = l.Cout; flat = true; H = W = 1;
         } else return fail(n, -1, "unknown layer kind");
-        if (!is_bn(l.kind) && i > 0 && is_conv_linear(n->L.back().kind))
-            return fail(n, -2, "layer " + std::to_string(i - 1) + ": a " + (n->L.back().kind == RCN_HIPX_CONV3X3_S2 ? "RCN_HIPX_CONV3X3_S2" : n->L.back().kind == RCN_HIPX_CONV1X1 ? "RCN_HIPX_CONV1X1" : n->L.back().kind == RCN_HIPX_DWCONV3X3 ? "RCN_HIPX_DWCONV3X3" : "RCN_HIPX_CONV3X3") + " layer must be followed by RCN_HIPX_BN_RELU or RCN_HIPX_BN_ADD_RELU");
-        if (has_params(l.kind)) {
+        // (RCN_HIPX_CONV3X3 only: behind a kind that names its layer the loop's first check has returned)
+        if (prev.linear && !k.bn) return fail(n, -2, "layer " + std::to_string(i - 1) + ": a " + prev.name + " layer must be followed by RCN_HIPX_BN_RELU or RCN_HIPX_BN_ADD_RELU");
+        if (k.params) {
             l.w_off = n->n_pad; n->n_pad += (long long)l.K * l.CoutP; l.b_off = n->n_pad; n->n_pad += l.CoutP;
             l.lw_off = n->n_log; n->n_log += (long long)l.K * l.Cout; l.lb_off = n->n_log; n->n_log += l.Cout;
         }
         n->L.push_back(std::move(l));
     }
-    if (n->L.back().kind == RCN_HIPX_DWCONV3X3)
-        return fail(n, -2, "layer " + std::to_string(n_layers - 1) + " (RCN_HIPX_DWCONV3X3): it must be followed directly by a batch-normalisation layer, and the last layer must be RCN_HIPX_DENSE (logits)");
-    if (n->L.back().kind == RCN_HIPX_CONV1X1)
-        return fail(n, -2, "layer " + std::to_string(n_layers - 1) + " (RCN_HIPX_CONV1X1): it must be followed directly by a batch-normalisation layer, and the last layer must be RCN_HIPX_DENSE (logits)");
-    if (n->L.back().kind == RCN_HIPX_CONV3X3_S2)
-        return fail(n, -2, "layer " + std::to_string(n_layers - 1) + " (RCN_HIPX_CONV3X3_S2): it must be followed directly by a batch-normalisation layer, and the last layer must be RCN_HIPX_DENSE (logits)");
+    const KindRow& last = n->L.back().row();
+    if (last.linear && last.named) return fail(n, -2, at_layer(n_layers - 1, n->L.back().kind) + "it must be followed directly by a batch-normalisation layer, and the last layer must be RCN_HIPX_DENSE (logits)");
     if (n->L.back().kind != RCN_HIPX_DENSE) return fail(n, -2, "the last layer must be RCN_HIPX_DENSE (logits)");
     n->classes = n->L.back().Cout;
     // one reduction launch, and one state pack, take kMaxReduceJobs layers with parameters: refused here, so create, every plan and the
     // state layout agree before anything is enqueued (reduce_slab and make_state_jobs keep their own guards)
     int with_params = 0;
-    for (const Layer& l : n->L) with_params += has_params(l.kind);
+    for (const Layer& l : n->L) with_params += l.row().params;
     if (with_params > kMaxReduceJobs)
         return fail(n, -3, std::to_string(with_params) + " layers with parameters: one reduction launch and one state pack take at most " + std::to_string(kMaxReduceJobs));
     return 0;
@@ -1504,7 +1456,7 @@ int rcn_hipx_create(int device, int in_h, int in_w, int in_c, const rcn_hipx_lay
         XTRY(n, l.out.ensure(elems * sizeof(float)));
         XTRY(n, l.dout.ensure(elems * sizeof(float)));
         if (l.kind == RCN_HIPX_MAXPOOL2) XTRY(n, l.idx.ensure(elems));
-        if (is_bn(l.kind)) {
+        if (l.row().bn) {
             XTRY(n, l.bn.ensure((size_t)4 * l.CoutP * sizeof(float)));
             XTRY(n, l.bn_part.ensure((size_t)bn_parts_cap((long long)max_batch * l.oH * l.oW) * 2 * l.CoutP * sizeof(double)));
             XTRY(n, l.slab.ensure((size_t)2 * l.CoutP * sizeof(float)));
@@ -1593,7 +1545,7 @@ int rcn_hipx_get_option(const rcn_hipx_net* n, const char* name, int* value) {
 static int upload_padded(rcn_hipx_net* n, Buf& to, const float* flat) {
     std::vector<float> pad((size_t)n->n_pad, 0.f);
     for (const Layer& l : n->L) {
-        if (!has_params(l.kind)) continue;
+        if (!l.row().params) continue;
         for (int k = 0; k < l.K; ++k) std::memcpy(&pad[l.w_off + (long long)k * l.CoutP], &flat[l.lw_off + (long long)k * l.Cout], sizeof(float) * l.Cout);
         std::memcpy(&pad[l.b_off], &flat[l.lb_off], sizeof(float) * l.Cout);
     }
@@ -1616,7 +1568,7 @@ static int unpad(rcn_hipx_net* n, const float* dev, float* flat) {
     XTRY(n, hipMemcpyAsync(pad.data(), dev, pad.size() * sizeof(float), hipMemcpyDeviceToHost, n->stream));
     XTRY(n, hipStreamSynchronize(n->stream));
     for (const Layer& l : n->L) {
-        if (!has_params(l.kind)) continue;
+        if (!l.row().params) continue;
         for (int k = 0; k < l.K; ++k) std::memcpy(&flat[l.lw_off + (long long)k * l.Cout], &pad[l.w_off + (long long)k * l.CoutP], sizeof(float) * l.Cout);
         std::memcpy(&flat[l.lb_off], &pad[l.b_off], sizeof(float) * l.Cout);
     }
@@ -1631,8 +1583,8 @@ int rcn_hipx_init_params(rcn_hipx_net* n, uint64_t seed) {
     std::mt19937_64 gen(seed ? seed : std::random_device{}());
     std::vector<float> flat((size_t)n->n_log, 0.f);
     for (const Layer& l : n->L) {
-        if (!has_params(l.kind)) continue;
-        if (is_bn(l.kind)) { for (int c = 0; c < l.Cout; ++c) flat[l.lw_off + c] = 1.f; continue; }      // gamma = 1, beta = 0
+        if (!l.row().params) continue;
+        if (l.row().bn) { for (int c = 0; c < l.Cout; ++c) flat[l.lw_off + c] = 1.f; continue; }      // gamma = 1, beta = 0
         std::normal_distribution<float> nd(0.f, std::sqrt(2.0f / (float)l.K));
         for (long long i = 0; i < (long long)l.K * l.Cout; ++i) flat[l.lw_off + i] = nd(gen);
     }
@@ -2095,7 +2047,7 @@ int rcn_hipx_step_flops(const rcn_hipx_net* n, int B, double* flops) {
     double f = 0;
     for (size_t i = 0; i < n->L.size(); ++i) {
         const Layer& l = n->L[i];
-        if (!has_matrix(l.kind)) continue;
+        if (!l.row().matrix) continue;
         const double macs = (double)B * l.oH * l.oW * (double)l.K * l.Cout * 1.0;
         f += 2.0 * macs * (i == 0 ? 2.0 : 3.0);         // forward + wgrad (+ dgrad except for the first layer)
     }

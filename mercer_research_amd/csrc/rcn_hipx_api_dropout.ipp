@@ -25,7 +25,7 @@ int rcn_hipx_set_dropout(rcn_hipx_net* n, float p, uint64_t seed) {
     if (!n) return -1;
     if (!(std::isfinite(p) && p >= 0.f && p < 1.f)) return fail(n, -1, "set_dropout: p must be finite and in [0, 1)");
     if (p == 0.f) p = 0.f;                              // (-0)
-    if (p > 0.f && dropout_sites(n) == 0) return fail(n, -3, "set_dropout: the net has no RCN_HIPX_DENSE_RELU layer to drop behind");
+    if (p > 0.f && dropout_sites(n) == 0) return fail(n, -3, std::string("set_dropout: the net has no ") + kind_row(RCN_HIPX_DENSE_RELU).name + " layer to drop behind");
     if (p == n->drop_p && (unsigned long long)seed == n->drop_seed) return 0;
     Dev g(n->device);
     RTRY(reconfigure(n, {{p != 0.f, &n->drop_tick, sizeof(long long), nullptr}}));

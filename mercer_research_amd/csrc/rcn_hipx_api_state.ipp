@@ -14,7 +14,7 @@ long long round256(long long bytes) { return (bytes + 255) / 256 * 256; }
 // the skip's source for RCN_HIPX_BN_ADD_RELU, the output width otherwise
 int desc_out(const rcn_hipx_net& n, size_t i) {
     const Layer& l = n.L[i];
-    return !has_params(l.kind) ? 0 : l.skip_src >= 0 ? (int)i - l.skip_src : l.Cout;
+    return !l.row().params ? 0 : l.skip_src >= 0 ? (int)i - l.skip_src : l.Cout;
 }
 
 // shape, layer offsets, section offsets and body size of a body with `sections` for the layer table of `n`; everything else at its default
@@ -26,7 +26,7 @@ int fill_layout(const rcn_hipx_net& n, int sections, rcn_hipx_state_desc* d) {
     for (int i = 0; i < RCN_HIPX_STATE_MAX_LAYERS; ++i) d->layer_off[i] = -1;
     for (size_t i = 0; i < n.L.size(); ++i) {
         d->layers[i].kind = n.L[i].kind; d->layers[i].out = desc_out(n, i);
-        if (has_params(n.L[i].kind)) d->layer_off[i] = n.L[i].lw_off;
+        if (n.L[i].row().params) d->layer_off[i] = n.L[i].lw_off;
     }
     d->classes = n.classes; d->n_log = n.n_log;
     d->precision = RCN_HIPX_FP32; d->tiling = RCN_HIPX_TILING_AUTO;
@@ -60,7 +60,7 @@ bool make_state_jobs(rcn_hipx_net* n, const rcn_hipx_state_desc& d, bool unpack,
     *J = StateJobs{};
     int unit = 0;
     for (const Layer& l : n->L) {
-        if (!has_params(l.kind)) continue;
+        if (!l.row().params) continue;
         if (J->njobs == kStateMaxJobs) return false;
         StateJob& jb = J->j[J->njobs++];
         jb.pad_off = l.w_off; jb.log_off = l.lw_off;
@@ -153,7 +153,7 @@ int rcn_hipx_restore_dev(rcn_hipx_net* n, const rcn_hipx_state_desc* desc, const
         return fail(n, -2, "restore: the descriptor's input shape, layer count or parameter count is not this net's");
     for (int i = 0; i < d.n_layers; ++i) {
         const Layer& l = n->L[i];
-        if (d.layers[i].kind != l.kind || (has_params(l.kind) && d.layers[i].out != desc_out(*n, (size_t)i))) return fail(n, -2, "restore: the descriptor's layer list is not this net's");
+        if (d.layers[i].kind != l.kind || (l.row().params && d.layers[i].out != desc_out(*n, (size_t)i))) return fail(n, -2, "restore: the descriptor's layer list is not this net's");
     }
     const long long sec_bytes = n->n_log * (long long)sizeof(float);
     if (d.body_bytes < kStateScalarsBytes || body_bytes < d.body_bytes) return fail(n, -1, "restore: body_bytes is smaller than the body the descriptor describes");

@@ -14,6 +14,8 @@ import sys
 
 CONV_TAIL = (("dense_relu", 128), ("dense", 10))
 # small nets that reach the branches the benchmark nets do not (name -> (input shape, layers))
+# (the nets of the layer kinds that came after it -- batch normalisation, skips, global average pooling, stride 2, 1x1, depthwise -- are the
+# tests' own: main() imports them)
 SMALL = {
     # maps too small for the LDS-tiled weight gradient: bf16 storage refuses this one
     "w8": ((8, 8, 3), (("conv", 32), ("pool",), ("conv", 64), ("pool",), ("dense", 10))),
@@ -36,6 +38,26 @@ SMALL = {
     "bad_cin4": ((16, 16, 4), (("conv", 32), ("pool",), ("dense", 10))),
     "bad_oddpool": ((7, 7, 1), (("conv", 32), ("pool",), ("dense", 10))),
 }
+# Descriptions that break TWO rules (input shape, layers): which refusal wins is part of the interface.  A bias-only kind that names its
+# layer is refused for what follows it before that layer's own checks run; plain conv_linear after them.
+S2, PW, DW = "conv_linear_s2", "conv1x1_linear", "dwconv_linear"
+PRECEDENCE = [
+    # ... followed by a pool on an odd map, and by a convolution of 48 channels
+    *[((6, 6, 32) if kind == S2 else (3, 3, 32), ((kind, 32), ("pool",), ("dense", 4))) for kind in (S2, PW, DW, "conv_linear")],
+    *[((4, 4, 32), ((kind, 32), ("conv", 48), ("dense", 4))) for kind in (S2, PW, DW, "conv_linear")],
+    *[((4, 4, 32), ((kind, 32), ("dense", 4))) for kind in (S2, PW, DW, "conv_linear")],
+    # ... as the last layer
+    *[((4, 4, 32), (("conv", 32), (kind, 32))) for kind in (S2, PW, DW, "conv_linear")],
+    # a depthwise layer with a bad `out` behind a dense layer, and on a map
+    ((4, 4, 32), (("conv", 32), ("dense_relu", 32), (DW, 48), ("bn_relu",), ("dense", 4))),
+    ((4, 4, 32), (("conv", 32), (DW, 48), ("bn_relu",), ("dense", 4))),
+    # a strided layer: 48 input channels on an odd map, 3 input channels on an odd map, 48 output channels behind a dense layer
+    ((5, 5, 48), ((S2, 32), ("bn_relu",), ("dense", 4))),
+    ((5, 5, 3), ((S2, 32), ("bn_relu",), ("dense", 4))),
+    ((4, 4, 32), (("conv", 32), ("dense_relu", 32), (S2, 48), ("bn_relu",), ("dense", 4))),
+    # a 1x1 layer: 48 output channels on 3 input channels
+    ((4, 4, 3), ((PW, 48), ("bn_relu",), ("dense", 4))),
+]
 BATCHES = (1, 2, 7, 16, 128, 512, 4096)
 PRECISIONS = ("fp32", "bf16", "bf16_stored")
 TILINGS = ("gemm", "auto", "lds")
@@ -49,8 +71,10 @@ def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="the checkout whose built library is asked (default: this one)")
     root = os.path.abspath(ap.parse_args().root)
-    sys.path.insert(0, root)
+    sys.path[:0] = [root, os.path.join(root, "tests")]
     import bench_convnet as bc
+    import _dw_ref, _pw_ref, _stride_ref                  # the twins' nets, and every description the plan tests expect refused
+    import test_convnet_bn_plan as bn, test_convnet_dw_plan as dw, test_convnet_gap_plan as gap, test_convnet_pw_plan as pw, test_convnet_res_plan as res, test_convnet_stride_plan as stride
     from mercer_research_amd.convnet import ConvNetError, plan, plan_eval
     for k in list(os.environ):
         if k.startswith("RCN_HIPX_"):
@@ -67,11 +91,17 @@ def main() -> None:
 
     nets = [(name, shape, layers, tuple(b for b in BATCHES if b <= 128) if name == "synth224" else BATCHES) for name, (shape, layers, _) in bc.CONFIGS.items()]
     nets += [(name, shape, layers, BATCHES) for name, (shape, layers) in SMALL.items()]
+    # the nets of the newer kinds' tests (input shape, layers, the test's own batch): at that batch and at the batches above
+    for tag, group in (("stride", _stride_ref.NETS), ("pw", _pw_ref.NETS), ("dw", _dw_ref.NETS), ("bn", bn.BN_NETS), ("res", res.RES_NETS), ("gap", gap.GAP_NETS)):
+        nets += [(f"{tag}_{name}", shape, layers, tuple(sorted({b0, *BATCHES}))) for name, (shape, layers, b0) in group.items()]
     for name, shape, layers, batches in nets:
         for b in batches:
             for p in PRECISIONS:
                 for t in TILINGS:
                     show(f"{name} B={b} {p} {t}", shape, layers, b, precision=p, tiling=t)
+    refused = [(r[0], r[1]) for m in (stride, pw, dw) for r in m.REFUSALS] + [((4, 4, 32), r[0]) for m in (res, gap) for r in m.REFUSALS] + PRECEDENCE
+    for k, (shape, layers) in enumerate(refused):
+        show(f"refusal {k}: {shape} {layers}", shape, layers, 2)
     for env, value in OPTIONS:
         os.environ["RCN_HIPX_" + env] = str(value)
         for name, (shape, layers, b0) in bc.CONFIGS.items():
