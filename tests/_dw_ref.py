@@ -90,16 +90,18 @@ def close_per_tensor(got, ref, in_shape, layers, rtol, tag=""):
         return _torch_ref.close_per_tensor(got, ref, in_shape, layout(layers), rtol, tag)
 
 
-def compare(spec, r, ref, rtol, rtol2, steps, tag):
-    """_twin_checks.compare, unchanged, on a description with the kind"""
+def compare(spec, r, ref, rtol, rtol2, steps, tag, **kw):
+    """_twin_checks.compare, unchanged, on a description with the kind (kw: its unrounded_logits / widened_gradients)"""
     with layouts():
-        return _twin_checks.compare(layout_spec(spec), r, ref, rtol, rtol2, steps, tag)
+        return _twin_checks.compare(layout_spec(spec), r, ref, rtol, rtol2, steps, tag, **kw)
 
 
 # (input shape, layers, batch): the smallest nets at which each thing can go wrong
 # A: H != W, and with H = 3 every output row touches a border; a ReLU convolution below (epilogue 3 gated by its output)
 W_A = ((3, 5, 3), (("conv", 32), (DW,), ("bn_relu",), ("global_avgpool",), ("dense", 7)), 3)
-# B: C = 96 (three channel groups, 24 quads: no power of two, so a lane's quad changes from tile to tile); M = 300: with pix_per_chunk = 128
+# B: C = 96 (three channel groups, 24 quads: no power of two, so a lane's quad is not tid % 24 in every tile and the kernel keys its weights by
+# the quad -- but the row is 10 x 24 = 240 pieces, ONE slab, so no lane's quad ever changes here: tests/_kinds_cases.py's net "quads" has the
+# second slab and runs the reload); M = 300: with pix_per_chunk = 128
 # three weight-gradient chunks, the last partial, whose edges fall mid-row and mid-image; the skip's add behind the dw input gradient
 W_B = ((6, 10, 3), (("conv_linear", 96), ("bn_relu",)) + residual(96) + (("pool",), ("global_avgpool",), ("dense", 10)), 5)
 # C: the dw layer on a 2 x 2 map (every tap of every pixel but the centre's own meets a border); a pool below (epilogue 0, raw); a dense
@@ -218,10 +220,11 @@ def _dw_int(x, W, b):
     return z
 
 
-def exact_case(seed=0):
-    """(parameters, running statistics, x, the integer logits by NumPy int64, the second map) of X_SPEC under evaluation, the batch
-    normalisation layers made the identity as _pw_ref.exact_case makes them"""
-    in_shape, layers, B = X_SPEC
+def exact_case(seed=0, spec=X_SPEC):
+    """(parameters, running statistics, x, the integer logits by NumPy int64, the second map) of X_SPEC (or of `spec`: the same five layers
+    on another map and batch) under evaluation, the batch normalisation layers made the identity as _pw_ref.exact_case makes them"""
+    in_shape, layers, B = spec
+    assert tuple(tuple(l) for l in layers) == X_SPEC[1] and in_shape[0] * in_shape[1] * in_shape[2] * 192 + 3 < 2 ** 24, spec
     rng = np.random.default_rng(seed)
     H, W, C = in_shape
     x = rng.integers(-2, 3, (B, H, W, C)).astype(np.int64)
