@@ -16,6 +16,9 @@ network BASELINE.json's north_star asks for, on the configs SURVEY.md §8(d) fix
   cifar_sep       depthwise-separable layers on ("dwconv_linear",) and ("conv1x1_linear", C): conv_linear 64, bn_relu; a residual separable
                   block at 64, a separable layer to 128, pool; the same at 128 and to 256, pool; two residual separable blocks at 256;
                   global_avgpool, dense 10; 27 layers with parameters, B = 512
+  cifar_mbv2      MobileNetV2's inverted residual blocks (expansion 6) on ("dwconv_linear",), ("dwconv_linear_s2",), ("bn",) and ("bn_add", 6):
+                  a stem of two conv_linear 32, bn_relu pairs; blocks 32 -> 32 (skip), 32 -> 64 stride 2, 64 -> 64 (skip), 64 -> 128 stride 2;
+                  conv1x1_linear 256, bn_relu, global_avgpool, dense 10; 31 layers with parameters, B = 512
 
 fp32 activations / weights, fp32 MFMA (v_mfma_f32_32x32x2_f32; peak 157.3 TFLOP/s).  Reports achieved TFLOP/s of the whole
 training step (algorithmic 2*MACs of forward + dgrad + wgrad) and its fraction of the fp32 MFMA peak.  The reference has no
@@ -63,6 +66,15 @@ _sep = lambda c: (("dwconv_linear",), ("bn_relu",), ("conv1x1_linear", c), ("bn_
 _sep_res = lambda c: (("dwconv_linear",), ("bn_relu",), ("conv1x1_linear", c), ("bn_add_relu", 4))
 CONFIGS["cifar_sep"] = (CONFIGS["cifar"][0], (("conv_linear", 64), ("bn_relu",)) + _sep_res(64) + _sep(128) + (("pool",),) + _sep_res(128) + _sep(256) + (("pool",),) +
                         _sep_res(256) + _sep_res(256) + (("global_avgpool",), ("dense", 10)), CONFIGS["cifar"][2])
+# An inverted-residual net at the CIFAR shape, expansion 6: a stem of two conv_linear 32, bn_relu pairs (two 3x3 layers: every config here
+# has at least two forward launches of the 3x3 / pool families, which tests/test_convnet_epoch_plan.py asks of each); four blocks
+# conv1x1_linear 6C, bn_relu, dwconv_linear[_s2], bn_relu, conv1x1_linear C', then ("bn_add", 6) where the block keeps shape and width (stride 1,
+# C' = C: the skip, no ReLU behind the sum) or ("bn",) where it does not: 32 -> 32, 32 -> 64 stride 2, 64 -> 64 (its source is the second
+# block's bn), 64 -> 128 stride 2; the head conv1x1_linear 256, bn_relu, global_avgpool, dense 10.  31 layers with parameters (the job tables take 32).
+_inverted = lambda c, co, s2: (("conv1x1_linear", 6 * c), ("bn_relu",), ("dwconv_linear_s2",) if s2 else ("dwconv_linear",), ("bn_relu",), ("conv1x1_linear", co),
+                               ("bn",) if s2 or co != c else ("bn_add", 6))
+CONFIGS["cifar_mbv2"] = (CONFIGS["cifar"][0], (("conv_linear", 32), ("bn_relu",), ("conv_linear", 32), ("bn_relu",)) + _inverted(32, 32, False) + _inverted(32, 64, True) + _inverted(64, 64, False) + _inverted(64, 128, True) +
+                         (("conv1x1_linear", 256), ("bn_relu",), ("global_avgpool",), ("dense", 10)), CONFIGS["cifar"][2])
 F32_MFMA_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD
 BF16_MFMA_PEAK_TFLOPS = 2516.8    # same guide: dense bf16 MFMA = 16x the fp32 MFMA rate (~2.5 PFLOP/s; never the 2:1-sparsity figure)
 HBM_PEAK_GBS = 8000.0

@@ -34,7 +34,7 @@ def stale() -> bool:
 
 LIBX = os.path.join(HERE, "librcn_hipx.so")          # Track X (trainable conv net; include/rcn_hipx.h)
 LIBX_SRC = os.path.join(CSRC, "rcn_hipx_api.hip")
-LIBX_DEPS = [LIBX_SRC, os.path.join(CSRC, "convnet.hpp"), os.path.join(CSRC, "convnet_bf16.hpp"), os.path.join(CSRC, "convnet_loss.hpp"), os.path.join(CSRC, "convnet_epoch.hpp"), os.path.join(CSRC, "convnet_metrics.hpp"),os.path.join(CSRC, "convnet_halo.hpp"), os.path.join(CSRC, "convnet_halo_bf16.hpp"), os.path.join(CSRC, "convnet_select.hpp"), os.path.join(CSRC, "convnet_sgd.hpp"), os.path.join(CSRC, "convnet_adam.hpp"), os.path.join(CSRC, "convnet_ema.hpp"), os.path.join(CSRC, "convnet_clip.hpp"), os.path.join(CSRC, "convnet_accum.hpp"), os.path.join(CSRC, "convnet_update.hpp"), os.path.join(CSRC, "convnet_dropout.hpp"), os.path.join(CSRC, "convnet_state.hpp"), os.path.join(CSRC, "rcn_hipx_api_update.ipp"), os.path.join(CSRC, "rcn_hipx_api_dropout.ipp"), os.path.join(CSRC, "rcn_hipx_api_state.ipp"), os.path.join(CSRC, "convnet_bn.hpp"), os.path.join(CSRC, "rcn_hipx_api_bn.ipp"), os.path.join(CSRC, "convnet_gap.hpp"), os.path.join(CSRC, "convnet_pw.hpp"), os.path.join(CSRC, "convnet_dw.hpp"), os.path.join(CSRC, "convnet_kinds.hpp"), os.path.join(HERE, "..", "include", "rcn_hipx.h")]
+LIBX_DEPS = [LIBX_SRC, os.path.join(CSRC, "convnet.hpp"), os.path.join(CSRC, "convnet_bf16.hpp"), os.path.join(CSRC, "convnet_loss.hpp"), os.path.join(CSRC, "convnet_epoch.hpp"), os.path.join(CSRC, "convnet_metrics.hpp"),os.path.join(CSRC, "convnet_halo.hpp"), os.path.join(CSRC, "convnet_halo_bf16.hpp"), os.path.join(CSRC, "convnet_select.hpp"), os.path.join(CSRC, "convnet_sgd.hpp"), os.path.join(CSRC, "convnet_adam.hpp"), os.path.join(CSRC, "convnet_ema.hpp"), os.path.join(CSRC, "convnet_clip.hpp"), os.path.join(CSRC, "convnet_accum.hpp"), os.path.join(CSRC, "convnet_update.hpp"), os.path.join(CSRC, "convnet_dropout.hpp"), os.path.join(CSRC, "convnet_state.hpp"), os.path.join(CSRC, "rcn_hipx_api_update.ipp"), os.path.join(CSRC, "rcn_hipx_api_dropout.ipp"), os.path.join(CSRC, "rcn_hipx_api_state.ipp"), os.path.join(CSRC, "convnet_bn.hpp"), os.path.join(CSRC, "rcn_hipx_api_bn.ipp"), os.path.join(CSRC, "convnet_gap.hpp"), os.path.join(CSRC, "convnet_pw.hpp"), os.path.join(CSRC, "convnet_dw.hpp"), os.path.join(CSRC, "convnet_dw_s2.hpp"), os.path.join(CSRC, "convnet_kinds.hpp"), os.path.join(HERE, "..", "include", "rcn_hipx.h")]
 
 
 def build_x(force: bool = False, verbose: bool = False) -> str:

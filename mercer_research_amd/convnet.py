@@ -16,7 +16,8 @@ from . import _lib
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBX_PATH = os.path.join(HERE, "librcn_hipx.so")
 KIND = {"conv": 0, "pool": 1, "dense_relu": 2, "dense": 3, "conv_linear": 4, "bn_relu": 5, "bn_add_relu": 6, "global_avgpool": 7,
-        "conv_linear_s2": 8, "bn_add_relu_down": 9, "conv1x1_linear": 10, "dwconv_linear": 11}
+        "conv_linear_s2": 8, "bn_add_relu_down": 9, "conv1x1_linear": 10, "dwconv_linear": 11,
+        "bn": 12, "bn_add": 13, "dwconv_linear_s2": 14}
 
 
 class XLayer(C.Structure):
@@ -83,10 +84,11 @@ class StateDesc(C.Structure):
                 ("dropout_seed", C.c_uint64)]
 
     def shape_and_layers(self):
-        """(in_shape, layers) as ConvNet takes them; ("bn_add_relu", d) and ("bn_add_relu_down", d) come back with their distance and
-        ("conv_linear_s2", Cout) with its width: the descriptor stores either as `out`"""
+        """(in_shape, layers) as ConvNet takes them; ("bn_add_relu", d), ("bn_add_relu_down", d) and ("bn_add", d) come back with their
+        distance and ("conv_linear_s2", Cout) with its width (a depthwise layer of either stride: its resolved width C): the descriptor
+        stores either as `out`"""
         names = {v: k for k, v in KIND.items()}
-        layers = [(names[self.layers[i].kind],) if self.layers[i].kind in (KIND["pool"], KIND["bn_relu"], KIND["global_avgpool"]) else (names[self.layers[i].kind], int(self.layers[i].out))
+        layers = [(names[self.layers[i].kind],) if self.layers[i].kind in (KIND["pool"], KIND["bn_relu"], KIND["bn"], KIND["global_avgpool"]) else (names[self.layers[i].kind], int(self.layers[i].out))
                   for i in range(self.n_layers)]
         return (int(self.in_h), int(self.in_w), int(self.in_c)), layers
 
@@ -461,7 +463,8 @@ class Snapshot:
 
 
 # the convolution kinds as step_hbm_floor_bytes sees them: (filter taps, stride, depthwise: C -> C with one input channel per filter)
-_CONV_GEOMETRY = {"conv": (9, 1, False), "conv_linear": (9, 1, False), "conv_linear_s2": (9, 2, False), "conv1x1_linear": (1, 1, False), "dwconv_linear": (9, 1, True)}
+_CONV_GEOMETRY = {"conv": (9, 1, False), "conv_linear": (9, 1, False), "conv_linear_s2": (9, 2, False), "conv1x1_linear": (1, 1, False), "dwconv_linear": (9, 1, True),
+                  "dwconv_linear_s2": (9, 2, True)}
 X_KIND = {"float32": 0, "uint8": 1}      # RCN_HIPX_X_F32 / RCN_HIPX_X_U8, by the set's torch dtype
 
 
@@ -524,7 +527,13 @@ class ConvNet:
     ("dwconv_linear",) is Conv2d(C, C, 3, padding=1, groups=C), the depthwise 3x3 convolution, on a map of C % 32 == 0 channels, followed by a
     bn layer like "conv_linear" (("dwconv_linear", C) says the same; any other width is refused); fp32 arithmetic in either precision mode.
     A separable layer is ("dwconv_linear",), ("bn_relu",), ("conv1x1_linear", C'), ("bn_relu",); a residual separable block behind a layer
-    of C channels is ("dwconv_linear",), ("bn_relu",), ("conv1x1_linear", C), ("bn_add_relu", 4)."""
+    of C channels is ("dwconv_linear",), ("bn_relu",), ("conv1x1_linear", C), ("bn_add_relu", 4).
+    ("dwconv_linear_s2",) is Conv2d(C, C, 3, stride=2, padding=1, groups=C) on an even map, under "dwconv_linear"'s rules otherwise.  ("bn",) is
+    BatchNorm2d(C) with no activation and ("bn_add", d) is BatchNorm2d(z) + s with none, s as for "bn_add_relu": MobileNetV2's linear
+    bottleneck.  Either may be a skip's source, and a convolution of any kind must follow directly (not "pool", "global_avgpool" or a dense
+    layer).  An inverted residual block of expansion t behind a layer of C channels is ("conv1x1_linear", tC), ("bn_relu",), ("dwconv_linear",),
+    ("bn_relu",), ("conv1x1_linear", C), ("bn_add", 6); one that changes the width or halves the map ends in ("dwconv_linear_s2",), ("bn_relu",),
+    ("conv1x1_linear", C'), ("bn",)."""
 
     def __init__(self, in_shape: Tuple[int, int, int], layers: Sequence[tuple], max_batch: int, device: int = 0):
         import torch
@@ -1256,12 +1265,12 @@ class ConvNet:
                 m = H * W * Cc * 4
                 sm = H * W * maps[len(maps) - 1 - l[1]][2] * 4
                 total += B * (3 * m + 4 * m + sm + 3 * sm)
-            elif l[0] == "bn_relu":
+            elif l[0] in ("bn_relu", "bn"):
                 # forward: the map read twice (statistics, apply) and written once; backward: three maps read over its two passes (x and dy
                 # by the sums, then one more pass's worth -- a re-read that hits the cache, the gate map -- is not counted) and one written
                 m = H * W * Cc * 4
                 total += B * (3 * m + 4 * m)
-            elif l[0] == "bn_add_relu":
+            elif l[0] in ("bn_add_relu", "bn_add"):
                 # as bn_relu, and the skip: its map read once more by the apply pass; the add pass of the backward reads the source's
                 # gradient and this layer's and writes the source's (the gate maps are not counted, as above)
                 m = H * W * Cc * 4

@@ -1,6 +1,8 @@
 // convnet_bn.hpp -- Track X: batch normalisation + ReLU behind a bias-only 3x3 convolution (RCN_HIPX_BN_RELU behind RCN_HIPX_CONV3X3),
 // and the same with an identity skip added in front of the ReLU (RCN_HIPX_BN_ADD_RELU: k_bn_apply_relu<EVAL, ADD>, k_skip_bwd_add),
-// torch.nn.BatchNorm2d(C) followed by ReLU over an NHWC fp32 map x[M][C], M = B * H * W rows, C % 32 == 0.  Every kernel is a streaming
+// torch.nn.BatchNorm2d(C) followed by ReLU over an NHWC fp32 map x[M][C], M = B * H * W rows, C % 32 == 0.  RCN_HIPX_BN and RCN_HIPX_BN_ADD are
+// the same two layers with NO activation (k_bn_apply<EVAL, ADD>: the apply expression without its max(0, .)); their backward pass is the
+// ungated form of the kernels below (g = dy as it stands) and their skip's share is never gated.  Every kernel is a streaming
 // pass: one thread per FOUR consecutive channels, 16-byte accesses, no atomics of any kind.
 //
 // The per-channel sums (the statistics of the forward pass, the two sums of the backward pass) are made in two launches:
@@ -190,10 +192,11 @@ struct SkipDown { int oH, oW, Cs, lo; };      // this layer's map; the source's 
 __device__ inline SkipDown skip_geom() { return SkipDown{}; }
 __device__ inline SkipDown skip_geom(const SkipDown& d) { return d; }
 // DOWN...: empty (RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU: the kernel's arguments are what they were), or one SkipDown behind eps
-template <bool EVAL, bool ADD, class... DOWN>
-__global__ __launch_bounds__(kBnThreads) void k_bn_apply_relu(const float* __restrict__ x, const float* __restrict__ s, float* __restrict__ y, long long n4, int C,
-                                                              const float* __restrict__ mean, const float* __restrict__ stat2, const float* __restrict__ gamma,
-                                                              const float* __restrict__ beta, float eps, DOWN... down) {
+// RELU false (RCN_HIPX_BN, RCN_HIPX_BN_ADD: k_bn_apply): the same expression without the max(0, .), y = fl(fl(xh * gamma) + beta) [+ s]
+template <bool EVAL, bool ADD, bool RELU, class... DOWN>
+__device__ __forceinline__ void bn_apply_body(const float* __restrict__ x, const float* __restrict__ s, float* __restrict__ y, long long n4, int C,
+                                              const float* __restrict__ mean, const float* __restrict__ stat2, const float* __restrict__ gamma,
+                                              const float* __restrict__ beta, float eps, DOWN... down) {
 #pragma clang fp contract(off)
     const int C4 = C / 4;
     long long e = (long long)blockIdx.x * kBnThreads + threadIdx.x;
@@ -224,10 +227,23 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_apply_relu(const float* __res
             const float t = xh[k] * ga[k];
             float u = t + be[k];
             if (ADD) u = u + sv[k];
-            v[k] = u > 0.f ? u : 0.f;
+            v[k] = RELU ? (u > 0.f ? u : 0.f) : u;
         }
         *reinterpret_cast<f32x4*>(y + e * 4) = v;
     }
+}
+template <bool EVAL, bool ADD, class... DOWN>
+__global__ __launch_bounds__(kBnThreads) void k_bn_apply_relu(const float* __restrict__ x, const float* __restrict__ s, float* __restrict__ y, long long n4, int C,
+                                                              const float* __restrict__ mean, const float* __restrict__ stat2, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, float eps, DOWN... down) {
+    bn_apply_body<EVAL, ADD, true>(x, s, y, n4, C, mean, stat2, gamma, beta, eps, down...);
+}
+// RCN_HIPX_BN (ADD false) and RCN_HIPX_BN_ADD (identity skip): batch normalisation with no activation behind it
+template <bool EVAL, bool ADD>
+__global__ __launch_bounds__(kBnThreads) void k_bn_apply(const float* __restrict__ x, const float* __restrict__ s, float* __restrict__ y, long long n4, int C,
+                                                         const float* __restrict__ mean, const float* __restrict__ stat2, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, float eps) {
+    bn_apply_body<EVAL, ADD, false>(x, s, y, n4, C, mean, stat2, gamma, beta, eps);
 }
 
 // ---- backward

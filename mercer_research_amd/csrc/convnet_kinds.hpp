@@ -16,7 +16,7 @@ struct KindRow {
     bool bn;                // batch normalisation, with or without a skip: a [gamma | beta] block (K = 1), statistics and buffers
     bool params;            // a parameter block, [W | b] or [gamma | beta]: every kind but the two pools, which also take no `out`
     bool matrix;            // ... whose W is a matrix with a tap-flipped transposed copy: every block but batch normalisation's
-    bool relu;              // a ReLU of its own on its output
+    bool relu;              // a ReLU of its own on its output (bn && !relu: RCN_HIPX_BN, RCN_HIPX_BN_ADD -- never gated, and a convolution must follow)
     bool named;             // its refusals name the layer, "layer i (KIND): ": the kinds from RCN_HIPX_GLOBAL_AVGPOOL on and the two skip kinds
 };
 
@@ -34,8 +34,11 @@ constexpr KindRow kKinds[] = {
     {"RCN_HIPX_BN_ADD_RELU_DOWN", 1, 1,  0,  0,  0,  1,  1,  0,  1,  1},      // 9
     {"RCN_HIPX_CONV1X1",          1, 1,  1,  1,  1,  0,  1,  1,  0,  1},      // 10
     {"RCN_HIPX_DWCONV3X3",        3, 1,  1,  0,  1,  0,  1,  1,  0,  1},      // 11
+    {"RCN_HIPX_BN",               1, 1,  0,  0,  0,  1,  1,  0,  0,  1},      // 12
+    {"RCN_HIPX_BN_ADD",           1, 1,  0,  0,  0,  1,  1,  0,  0,  1},      // 13
+    {"RCN_HIPX_DWCONV3X3_S2",     3, 2,  1,  0,  1,  0,  1,  1,  0,  1},      // 14
 };
-constexpr int kKindCount = RCN_HIPX_DWCONV3X3 + 1;          // (the enum's last value: a new kind moves it)
+constexpr int kKindCount = RCN_HIPX_DWCONV3X3_S2 + 1;         // (the enum's last value: a new kind moves it)
 static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kKindCount, "one row per rcn_hipx_layer_kind");
 
 // the row of a kind; a value that is no kind (describe_layers refuses it) reads as a layer that is nothing

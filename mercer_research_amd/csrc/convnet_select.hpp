@@ -580,6 +580,58 @@ inline std::string describe(const DwWgradChoice& c, const ConvShape& s) {
     return strf("  wgrad dwconv 3x3 %dx%dx%d: k_dw_wgrad (fp32 arithmetic), %d channel groups x %d chunks of %d pixels", s.H, s.W, s.Cin, c.groups, c.chunks, c.ppc);
 }
 
+// ---- RCN_HIPX_DWCONV3X3_S2 (convnet_dw_s2.hpp): the strided depthwise convolution on an even H x W map (s: the layer's INPUT map), output
+// oH x oW = (H/2) x (W/2), fp32 in either precision mode.  The forward pass (epi 1) and the input gradient (epi 0 / 3) tile the same
+// geometry: a tile is (image, band of `th` output rows -- for the input gradient: rows of 2 x 2 blocks of input pixels --, slab of 256
+// 16-byte output pieces / blocks); th by select_dw's rule over the output rows, the grid looping over the tiles as k_dw's.
+inline DwChoice dw_s2_tiles(const Selection& sel, const ConvShape& s) {
+    DwChoice c;
+    const auto refuse = [&c](const char* why) { c.error = why; return c; };
+    if (s.Cin != s.Cout) return refuse("internal: a depthwise convolution keeps its channel count");
+    if (s.Cin % 32) return refuse("a depthwise convolution's channels must be a multiple of 32");
+    if (s.H % 2 || s.W % 2) return refuse("a strided convolution needs even height and width");
+    if ((long long)s.W * (s.Cin / 4) > 0x3fffffffLL) return refuse("a depthwise convolution's map row must hold fewer than 2^30 16-byte pieces");
+    const int oH = s.H / 2, oW = s.W / 2;
+    c.slabs = (int)(((long long)oW * (s.Cin / 4) + kDwSlab - 1) / kDwSlab);
+    c.th = 8;
+    for (int th = 32; th > 8; th /= 2)
+        if (th < oH + 8 && (long long)s.N * ((oH + th - 1) / th) * c.slabs >= kDwMinTiles) { c.th = th; break; }
+    c.bands = (oH + c.th - 1) / c.th;
+    c.items = (long long)s.N * c.bands * c.slabs;
+    if (sel.opt.halo_f32_slots > 0) c.grid = sel.opt.halo_f32_slots < c.items ? sel.opt.halo_f32_slots : c.items;
+    return c;
+}
+inline DwChoice select_dw_s2(const Selection& sel, const ConvShape& s, int epi) {
+    DwChoice c = dw_s2_tiles(sel, s);
+    if (!c.error && epi != 1) c.error = "internal: a strided depthwise convolution's forward pass has epilogue 1";
+    return c;
+}
+inline DwChoice select_dw_s2_dgrad(const Selection& sel, const ConvShape& s, int epi) {
+    DwChoice c = dw_s2_tiles(sel, s);
+    if (!c.error && epi != 0 && epi != 3) c.error = "internal: a strided depthwise convolution's input gradient has epilogues 0 and 3";
+    return c;
+}
+inline std::string dw_s2_grid_words(const DwChoice& c) { return c.grid ? std::to_string(c.grid) + " looping over the tiles" : std::string("a resident grid looping over the tiles"); }
+inline std::string describe_dw_s2(const DwChoice& c, const ConvShape& s, int epi) {
+    return strf("  dwconv 3x3/2 %dx%dx%d->%dx%dx%d epi %d: k_dw_s2_fwd (fp32 arithmetic), tiles of %d output rows x %d pieces of 16 bytes (%d bands x %d slabs per image, %lld tiles), workgroups %s",
+                s.H, s.W, s.Cin, s.H / 2, s.W / 2, s.Cin, epi, c.th, kDwSlab, c.bands, c.slabs, c.items, dw_s2_grid_words(c).c_str());
+}
+inline std::string describe_dw_s2_dgrad(const DwChoice& c, const ConvShape& s, int epi) {
+    return strf("  dgrad dwconv 3x3/2 %dx%dx%d->%dx%dx%d epi %d: k_dw_s2_dgrad<%d> (fp32 arithmetic), one launch, every input element written once: 2x2 blocks with 1 / 2 / 2 / 4 taps, "
+                "tiles of %d block rows x %d blocks (%d bands x %d slabs per image, %lld tiles), workgroups %s",
+                s.H / 2, s.W / 2, s.Cin, s.H, s.W, s.Cin, epi, epi, c.th, kDwSlab, c.bands, c.slabs, c.items, dw_s2_grid_words(c).c_str());
+}
+// ... and its weight gradient: select_dw_wgrad's chunking (pix_per_chunk / wg_target, the 128-pixel floor) over the OUTPUT pixels
+inline DwWgradChoice select_dw_s2_wgrad(const Selection& sel, const ConvShape& s) {
+    DwWgradChoice c;
+    if (s.H % 2 || s.W % 2) { c.error = "a strided convolution needs even height and width"; return c; }
+    return select_dw_wgrad(sel, ConvShape{s.N, s.H / 2, s.W / 2, s.Cin, s.Cout});
+}
+inline std::string describe_dw_s2_wgrad(const DwWgradChoice& c, const ConvShape& s) {
+    return strf("  wgrad dwconv 3x3/2 %dx%dx%d->%dx%dx%d: k_dw_s2_wgrad (fp32 arithmetic), %d channel groups x %d chunks of %d output pixels", s.H, s.W, s.Cin, s.H / 2, s.W / 2, s.Cin, c.groups,
+                c.chunks, c.ppc);
+}
+
 // ---- the step's update launch (convnet_update.hpp)
 // what a training step does with its gradient: the whole update (a net that does not accumulate), or one micro-step of a cycle of
 // rcn_hipx_set_accumulate -- the first stores into the accumulator, a middle one adds, the last adds and applies the update

@@ -34,6 +34,7 @@
 #include "convnet_gap.hpp"
 #include "convnet_pw.hpp"
 #include "convnet_dw.hpp"
+#include "convnet_dw_s2.hpp"
 #include "convnet_kinds.hpp"
 
 using namespace rcnx;
@@ -576,6 +577,47 @@ int launch_dw_wgrad(rcn_hipx_net* n, const float* X, const float* dZ, ConvShape 
     return 0;
 }
 
+// ---- RCN_HIPX_DWCONV3X3_S2 (convnet_dw_s2.hpp; convnet_select.hpp: select_dw_s2*), s: the layer's INPUT map, fp32 in either precision mode.
+// forward: Y = dwconv(X, W, stride 2) + b over the (H/2) x (W/2) output map
+int launch_dw_s2(rcn_hipx_net* n, const float* X, const float* Wk, const float* bias, float* Y, ConvShape s) {
+    const DwChoice c = select_dw_s2(*n, s, 1);
+    if (c.error) return fail(n, -3, c.error);
+    if (dry_note(n, "%s", describe_dw_s2(c, s, 1).c_str())) return 0;
+    long long gx = c.grid;
+    if (!gx) { gx = resident_slots(n, (const void*)k_dw_s2_fwd); if (gx > c.items) gx = c.items; }
+    hipLaunchKernelGGL(k_dw_s2_fwd, dim3((unsigned)gx), dim3(kThreads), 0, n->stream, X, Wk, bias, Y, s.H, s.W, s.Cin, c.th, c.items);
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+// input gradient: dX (the whole H x W map) from dZ and W AS STORED (the kernel picks the taps of each parity class itself), epi 0 raw or 3
+// gated by `gate`, a tensor shaped like dX.  The 2 x 2 blocks partition the map and a lane stores each of its four pieces once: ONE launch
+// writes every element of dX exactly once, by one thread.
+int launch_dw_s2_dgrad(rcn_hipx_net* n, const float* dZ, const float* Wk, const float* gate, float* dX, ConvShape s, int epi) {
+    const DwChoice c = select_dw_s2_dgrad(*n, s, epi);
+    if (c.error) return fail(n, -3, c.error);
+    if (dry_note(n, "%s", describe_dw_s2_dgrad(c, s, epi).c_str())) return 0;
+    with_const<3, 0>(epi, [&](auto EPI) {
+        auto* const kernel = k_dw_s2_dgrad<CV(EPI)>;
+        long long gx = c.grid;
+        if (!gx) { gx = resident_slots(n, (const void*)kernel); if (gx > c.items) gx = c.items; }
+        hipLaunchKernelGGL(kernel, dim3((unsigned)gx), dim3(kThreads), 0, n->stream, dZ, Wk, gate, dX, s.H, s.W, s.Cin, c.th, c.items);
+    });
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+// the partial [10][C] tiles of its weight gradient into the layer's slab (n->slab_sel), one per chunk of OUTPUT pixels; *chunks_out: how many
+int launch_dw_s2_wgrad(rcn_hipx_net* n, const float* X, const float* dZ, ConvShape s, int* chunks_out) {
+    const DwWgradChoice c = select_dw_s2_wgrad(*n, s);
+    if (c.error) return fail(n, -3, c.error);
+    *chunks_out = c.chunks;
+    if (dry_note(n, "%s", describe_dw_s2_wgrad(c, s).c_str())) return 0;
+    XTRY(n, scratch_ensure(n, *n->slab_sel, (size_t)c.chunks * 10 * s.Cout * sizeof(float)));
+    hipLaunchKernelGGL(k_dw_s2_wgrad, dim3((unsigned)c.chunks, (unsigned)c.groups), dim3(kThreads), 0, n->stream, X, dZ, (float*)n->slab_sel->p, (long long)s.N * (s.H / 2) * (s.W / 2), s.H,
+                       s.W, s.Cin, c.ppc);
+    XTRY(n, hipGetLastError());
+    return 0;
+}
+
 float* P(rcn_hipx_net* n, long long off) { return (float*)n->params.p + off; }
 
 int ensure_batch(rcn_hipx_net* n, int B) {
@@ -613,13 +655,15 @@ int layer_forward(rcn_hipx_net* n, const Layer& l, int B, const float* X, float*
     case RCN_HIPX_CONV3X3_S2: return launch_conv_s2(n, X, W, b, Y, ConvShapeS2{B, l.H, l.W, l.Cin, l.CoutP}, 1, WB);
     case RCN_HIPX_CONV1X1: return launch_pw(n, X, W, b, Y, l.gemm(B), 1, WB);
     case RCN_HIPX_DWCONV3X3: return launch_dw(n, X, W, b, Y, l.gemm(B), 1);
+    case RCN_HIPX_DWCONV3X3_S2: return launch_dw_s2(n, X, W, b, Y, l.gemm(B));
     default: return launch_conv(n, X, W, b, Y, l.gemm(B), l.row().ks, 1, nullptr, nullptr, false, WB);
     }
 }
 // Its input gradient: dX = conv(dZ, flip(W)^T) on the tap-flipped transposed weights, which every kernel that writes a weight keeps current
 // (FlipSpec, refresh_flipped).  gate_by (nullable): the ReLU layer below, whose output gates dX in the epilogue (3; else 0, raw).  pdz
 // (nullable): dZ exists only at pooled resolution; st: dZ / dX are bf16 tensors.  Whatever the kind, ONE launch writes ALL of dX, every element
-// once and with no accumulation: a strided layer over the four parity classes of the input pixels, k_dw's tiles partitioning the map.
+// once and with no accumulation: a strided layer over the four parity classes of the input pixels, k_dw's tiles partitioning the map,
+// k_dw_s2_dgrad's 2 x 2 blocks partitioning it.
 int layer_dgrad(rcn_hipx_net* n, const Layer& l, int B, const float* dZ, const Layer* gate_by, float* dX, const PooledGrad* pdz, Store st) {
     const float *const wt = (const float*)n->wt.p + l.w_off, *const gate = gate_by ? (const float*)gate_by->out.p : nullptr;
     const int epi = gate_by ? 3 : 0;
@@ -629,6 +673,7 @@ int layer_dgrad(rcn_hipx_net* n, const Layer& l, int B, const float* dZ, const L
     case RCN_HIPX_CONV3X3_S2: return launch_dgrad_s2(n, dZ, wt, gate, dX, ConvShapeS2T{t.N, t.H, t.W, t.Cin, t.Cout}, epi, WB);
     case RCN_HIPX_CONV1X1: return launch_pw(n, dZ, wt, gate, dX, t, epi, WB);
     case RCN_HIPX_DWCONV3X3: return launch_dw(n, dZ, wt, gate, dX, s, epi);      // (the same stencil over dZ: C -> C)
+    case RCN_HIPX_DWCONV3X3_S2: return launch_dw_s2_dgrad(n, dZ, P(n, l.w_off), gate, dX, s, epi);      // (W as stored: k_dw_s2_dgrad picks each parity class's taps)
     default: return launch_conv(n, dZ, wt, gate, dX, t, l.row().ks, epi, nullptr, pdz, false, WB, st);
     }
 }
@@ -637,6 +682,7 @@ int layer_wgrad(rcn_hipx_net* n, const Layer& l, int B, const float* X, const fl
     switch (l.kind) {
     case RCN_HIPX_CONV3X3_S2: return launch_wgrad_s2(n, X, dZ, ConvShapeS2{B, l.H, l.W, l.Cin, l.CoutP}, chunks);
     case RCN_HIPX_DWCONV3X3: return launch_dw_wgrad(n, X, dZ, l.gemm(B), chunks);
+    case RCN_HIPX_DWCONV3X3_S2: return launch_dw_s2_wgrad(n, X, dZ, l.gemm(B), chunks);
     default: return launch_wgrad(n, X, dZ, l.gemm(B), l.row().ks, chunks, pdz, st, l.kind == RCN_HIPX_CONV1X1);      // (1x1: the KS = 1 kernels with rows walking the map)
     }
 }
@@ -760,7 +806,8 @@ int launch_bn_forward(rcn_hipx_net* n, size_t i, const float* x, int B, bool tra
     if (train && !n->dry && (size_t)parts * 2 * C * sizeof(double) > l.bn_part.cap) return fail(n, -3, "internal: more partial sums than the layer's buffer holds");
     // RCN_HIPX_BN_ADD_RELU: the skip's map (the source layer's output, of this layer's shape: describe_layers) is added in front of the ReLU
     // RCN_HIPX_BN_ADD_RELU_DOWN: the source is twice as high and wide and has Cs <= C channels; it comes in through the option-A shortcut
-    const bool add = l.skip_src >= 0, down = l.kind == RCN_HIPX_BN_ADD_RELU_DOWN;
+    // RCN_HIPX_BN, RCN_HIPX_BN_ADD: the same statistics and the same expression without the ReLU, k_bn_apply<EVAL, ADD> (identity skip only)
+    const bool add = l.skip_src >= 0, down = l.kind == RCN_HIPX_BN_ADD_RELU_DOWN, linear = !l.row().relu;
     const float* const skip = add ? (const float*)n->L[l.skip_src].out.p : (const float*)nullptr;
     const int Cs = down ? n->L[l.skip_src].CoutP : C;
     const SkipDown sd{l.oH, l.oW, Cs, (C - Cs) / 2};
@@ -779,6 +826,13 @@ int launch_bn_forward(rcn_hipx_net* n, size_t i, const float* x, int B, bool tra
                                bn_mean(l), bn_invstd(l), bn_run_mean(l), bn_run_var(l));
             XTRY(n, hipGetLastError());
         }
+        if (linear) {
+            if (add ? dry_note(n, "  bn-add %dx%dx%d: k_bn_apply_add, %u workgroups (no activation; the batch's mean and invstd; skip: the output of layer %d)", l.oH, l.oW, C, blocks, l.skip_src)
+                    : dry_note(n, "  bn %dx%dx%d: k_bn_apply, %u workgroups (no activation; the batch's mean and invstd)", l.oH, l.oW, C, blocks)) return 0;
+            if (add) apply(k_bn_apply<false, true>, bn_mean(l), bn_invstd(l)); else apply(k_bn_apply<false, false>, bn_mean(l), bn_invstd(l));
+            XTRY(n, hipGetLastError());
+            return 0;
+        }
         if (add ? dry_note(n, "  bn-add-relu %dx%dx%d: k_bn_apply_add_relu%s, %u workgroups (the batch's mean and invstd; skip: the output of layer %d%s)", l.oH, l.oW, C, down ? "_down" : "", blocks,
                            l.skip_src, down_words.c_str())
                 : dry_note(n, "  bn-relu %dx%dx%d: k_bn_apply_relu, %u workgroups (the batch's mean and invstd)", l.oH, l.oW, C, blocks)) return 0;
@@ -786,6 +840,14 @@ int launch_bn_forward(rcn_hipx_net* n, size_t i, const float* x, int B, bool tra
         else if (add) apply(k_bn_apply_relu<false, true>, bn_mean(l), bn_invstd(l));
         else apply(k_bn_apply_relu<false, false>, bn_mean(l), bn_invstd(l));
     } else {
+        if (linear) {
+            if (add ? dry_note(n, "  bn-add %dx%dx%d: k_bn_apply_add<eval>, %u workgroups (no activation; scale and shift from the running statistics, eps %g; skip: the output of layer %d)", l.oH, l.oW, C,
+                               blocks, (double)n->bn_eps, l.skip_src)
+                    : dry_note(n, "  bn %dx%dx%d: k_bn_apply<eval>, %u workgroups (no activation; scale and shift from the running statistics, eps %g)", l.oH, l.oW, C, blocks, (double)n->bn_eps)) return 0;
+            if (add) apply(k_bn_apply<true, true>, bn_run_mean(l), bn_run_var(l)); else apply(k_bn_apply<true, false>, bn_run_mean(l), bn_run_var(l));
+            XTRY(n, hipGetLastError());
+            return 0;
+        }
         if (add ? dry_note(n, "  bn-add-relu %dx%dx%d: k_bn_apply_add_relu%s<eval>, %u workgroups (scale and shift from the running statistics, eps %g; skip: the output of layer %d%s)",
                            l.oH, l.oW, C, down ? "_down" : "", blocks, (double)n->bn_eps, l.skip_src, down_words.c_str())
                 : dry_note(n, "  bn-relu %dx%dx%d: k_bn_apply_relu<eval>, %u workgroups (scale and shift from the running statistics, eps %g)", l.oH, l.oW, C, blocks, (double)n->bn_eps)) return 0;
@@ -909,7 +971,8 @@ int launch_bn_backward(rcn_hipx_net* n, size_t i, int B, bool gated, float* grad
     const int parts = bn_parts(M);
     const unsigned blocks = bn_stream_blocks(n4, C / 4);
     if (!n->dry && (size_t)parts * 2 * C * sizeof(double) > l.bn_part.cap) return fail(n, -3, "internal: more partial sums than the layer's buffer holds");
-    const char* const who = l.pool_follows ? "gated by the pool's backward" : gated ? gated_above_words(n, i) : "gates itself (out > 0)";
+    // (RCN_HIPX_BN, RCN_HIPX_BN_ADD: the caller passes gated = true for "no gate here" -- the raw dout IS the gradient of its output)
+    const char* const who = !l.row().relu ? "linear: no gate" : l.pool_follows ? "gated by the pool's backward" : gated ? gated_above_words(n, i) : "gates itself (out > 0)";
     const float* const x = (const float*)cl.out.p;
     const float* const dy = (const float*)l.dout.p;
     const float* const y = (const float*)l.out.p;
@@ -939,15 +1002,17 @@ int launch_bn_backward(rcn_hipx_net* n, size_t i, int B, bool gated, float* grad
 int launch_skip_bwd(rcn_hipx_net* n, size_t src, int B, bool src_gated) {
     Layer& s = n->L[src];
     Layer& l = n->L[s.skip_by];
-    const bool gated = l.pool_follows || n->bw.gated[s.skip_by];
+    const bool linear = !l.row().relu;                   // RCN_HIPX_BN_ADD: the sum has no ReLU behind it, its dout is the skip's share as it stands
+    const bool gated = linear || l.pool_follows || n->bw.gated[s.skip_by];
     // RCN_HIPX_BN_ADD_RELU_DOWN: one thread per four floats of the SMALL map's window of the source's Cs channels -- a quarter of the source map
     const bool down = l.kind == RCN_HIPX_BN_ADD_RELU_DOWN;
     const int C = l.CoutP, Cw = down ? s.CoutP : C;
     const long long n4 = (long long)B * l.oH * l.oW * (Cw / 4);
     const unsigned blocks = bn_stream_blocks(n4, Cw / 4);
     if (dry_note(n, "  skip-bwd %dx%dx%d: k_skip_bwd_add%s, %u workgroups into layer %d's gradient (the skip's gradient %s; %s)", l.oH, l.oW, Cw, down ? "_down (at (2h, 2w) of the source)" : "", blocks, (int)src,
-                 l.pool_follows ? "gated by the pool's backward" : gated ? gated_above_words(n, (size_t)s.skip_by) : "gated here (out > 0)",
-                 (src_gated ? "then gated by layer " + std::to_string(src) + "'s output" : "ungated: layer " + std::to_string(src) + " is a pool").c_str())) return 0;
+                 linear ? "ungated: the sum has no ReLU behind it" : l.pool_follows ? "gated by the pool's backward" : gated ? gated_above_words(n, (size_t)s.skip_by) : "gated here (out > 0)",
+                 (src_gated ? "then gated by layer " + std::to_string(src) + "'s output"
+                            : "ungated: layer " + std::to_string(src) + (s.row().bn ? " is a batch normalisation without a ReLU" : " is a pool")).c_str())) return 0;
     auto add = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBnThreads), 0, n->stream, (float*)s.dout.p, (const float*)l.dout.p, (const float*)l.out.p, (const float*)s.out.p, n4);
     };
@@ -1013,7 +1078,8 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
         }
         if (l.row().bn) {
             // its dout is gated by the pool's backward, by the convolution or by the global average pool above (n->bw.gated); otherwise it gates itself
-            RTRY(launch_bn_backward(n, (size_t)i, B, l.pool_follows || gated[i], grad, apply));
+            // RCN_HIPX_BN, RCN_HIPX_BN_ADD (no ReLU): never gated from above (the convolution above saw relu = 0: epilogue 0) and it gates nothing itself
+            RTRY(launch_bn_backward(n, (size_t)i, B, !l.row().relu || l.pool_follows || gated[i], grad, apply));
             continue;
         }
         // a layer with a [W | b] block: a convolution of any kind, whose rows are the pixels of a map, or a dense layer
@@ -1054,6 +1120,11 @@ int backward_layers(rcn_hipx_net* n, const float* x, int B, float lr, float* gra
             // point (stream_after at its iteration); a source pool's dout is read (k_pool_bwd, or pooled[] in the convolution below it)
             // only in the iterations below this one.  The add belongs to THIS iteration and gated[] lives in n->bw, so a bucket of
             // rcn_hipx_gradients_bucket_dev may end anywhere inside a block.
+            // A source that is itself RCN_HIPX_BN_ADD (inverted residual blocks back to back: layer i - 1 ends block one and feeds the
+            // skip of block two's RCN_HIPX_BN_ADD at skip_by > i): the add reads dout[skip_by], which was complete when the walk passed
+            // skip_by + 1 -- every layer's dout is complete before the walk reaches the layer, by this same argument one block up -- and
+            // completes dout[i - 1] here, BEFORE iteration i - 1 runs that layer's own batch-normalisation backward and, further down,
+            // hands dout[i - 1] on as the skip's share of block one's source.  Neither share is gated: no ReLU at either sum.
             if (below.skip_by >= 0) RTRY(launch_skip_bwd(n, (size_t)i - 1, B, gate));
         }
         int chunks = 0;
@@ -1285,13 +1356,22 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
         const std::string at = at_layer(i, l.kind);
         // A bias-only layer must be followed directly by batch normalisation.  For the kinds that name their layer this is said before the
         // next layer's own checks run; for RCN_HIPX_CONV3X3 behind them (below the branches).
+        // (RCN_HIPX_DWCONV3X3_S2 says it in a sentence of its own, which names all five batch-normalisation kinds)
+        if (pk == RCN_HIPX_DWCONV3X3_S2 && !k.bn)
+            return fail(n, -2, at_layer(i - 1, pk) + "it must be followed directly by a batch-normalisation layer (RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU, RCN_HIPX_BN_ADD_RELU_DOWN, RCN_HIPX_BN or RCN_HIPX_BN_ADD)");
         if (prev.linear && prev.named && !k.bn) return fail(n, -2, at_layer(i - 1, pk) + "it must be followed directly by a batch-normalisation layer (RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_BN_ADD_RELU_DOWN)");
+        // A batch normalisation without a ReLU (RCN_HIPX_BN, RCN_HIPX_BN_ADD) feeds a convolution only: k_pool_bwd folds the mask "pooled value
+        // > 0" in, launch_gap_backward gates the layer below, and a dense layer above a batch normalisation leaves it to gate itself -- all
+        // three read a batch-normalisation map as a ReLU map.  (A value that is no kind goes on to its own refusal below.)
+        if (prev.bn && !prev.relu && !k.map && l.kind >= 0 && l.kind < kKindCount)
+            return fail(n, -2, at_layer(i - 1, pk) + "a batch normalisation without a ReLU must be followed directly by a convolution of any kind, not by a " + k.name +
+                               " layer (the backward pass of a pool, a global average pool or a dense layer gates for a ReLU below it)");
         if (k.map) {
             // torch.nn.Conv2d(C, out, ks, stride, padding = ks / 2) on the H x W map: a [W | b] block with K = ks * ks * C.  The depthwise one
             // (groups = C): K = 9 and Cout = C, `out` 0 or C (the resolved width is what the state descriptor stores).  Stride 2, pad 1: the
             // output is (H/2) x (W/2), no odd maps in this version.  Only the stride-1 3x3 GEMM kinds have a gather form for a first layer of
             // 9 * Cin <= 32; every other kind's rows are whole 16-byte pieces of a map of a multiple of 32 channels.
-            const bool dw = l.kind == RCN_HIPX_DWCONV3X3, conv3 = k.gemm && k.ks == 3;
+            const bool dw = l.kind == RCN_HIPX_DWCONV3X3 || l.kind == RCN_HIPX_DWCONV3X3_S2, conv3 = k.gemm && k.ks == 3;
             if (flat) return fail(n, -2, at + "convolution after a dense layer or a global average pool");
             if (dw && out != 0 && out != C) return fail(n, -2, at + "out must be 0 or the input channels " + std::to_string(C) + " (depth multiplier 1), not " + std::to_string(out));
             if (!dw && (out < 32 || out % 32)) return fail(n, -3, at + "conv output channels must be a positive multiple of 32");
@@ -1310,12 +1390,20 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
         } else if (l.kind == RCN_HIPX_BN_RELU) {
             if (!prev.linear) return fail(n, -2, "batch normalisation (RCN_HIPX_BN_RELU) must directly follow a RCN_HIPX_CONV3X3 layer (of either stride) or a RCN_HIPX_CONV1X1 layer");
             l.Cout = l.CoutP = C; l.oH = H; l.oW = W; l.K = 1;      // [gamma | beta]: a [W | b] block with K = 1
-        } else if (l.kind == RCN_HIPX_BN_ADD_RELU || l.kind == RCN_HIPX_BN_ADD_RELU_DOWN) {
+        } else if (l.kind == RCN_HIPX_BN) {
+            // torch.nn.BatchNorm2d(C) and nothing behind it: RCN_HIPX_BN_RELU's block, statistics and buffers
+            if (!prev.linear)
+                return fail(n, -2, at + "it must directly follow a bias-only convolution (RCN_HIPX_CONV3X3, RCN_HIPX_CONV3X3_S2, RCN_HIPX_CONV1X1, RCN_HIPX_DWCONV3X3 or RCN_HIPX_DWCONV3X3_S2)");
+            l.Cout = l.CoutP = C; l.oH = H; l.oW = W; l.K = 1;
+        } else if (l.kind == RCN_HIPX_BN_ADD_RELU || l.kind == RCN_HIPX_BN_ADD_RELU_DOWN || l.kind == RCN_HIPX_BN_ADD) {
             // `out` is the distance to the skip's source, the output of layer i - out.  The source needs a gradient buffer that the
             // input-gradient kernel of the layer above it writes in full (backward_layers adds the skip's share behind that launch) and an
             // output that the forward pass writes: a ReLU layer or a pool of this layer's shape, not a convolution whose pool is fused away.
             // RCN_HIPX_BN_ADD_RELU_DOWN: the same, but the source is twice this layer's height and width and may be narrower (option-A shortcut)
-            const bool down = l.kind == RCN_HIPX_BN_ADD_RELU_DOWN;
+            // RCN_HIPX_BN_ADD: RCN_HIPX_BN_ADD_RELU's rules (an identity skip); the two sentences that list kinds are its own
+            const bool down = l.kind == RCN_HIPX_BN_ADD_RELU_DOWN, lin = l.kind == RCN_HIPX_BN_ADD;
+            if (lin && !prev.linear)
+                return fail(n, -2, at + "it must directly follow a bias-only convolution (RCN_HIPX_CONV3X3, RCN_HIPX_CONV3X3_S2, RCN_HIPX_CONV1X1, RCN_HIPX_DWCONV3X3 or RCN_HIPX_DWCONV3X3_S2)");
             if (!prev.linear) return fail(n, -2, at + "it must directly follow a RCN_HIPX_CONV3X3 layer (of either stride) or a RCN_HIPX_CONV1X1 layer");
             if (out < 2) return fail(n, -1, at + "out is the distance to the skip's source and must be at least 2, not " + std::to_string(out));
             const int src = i - out;
@@ -1323,6 +1411,10 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
             l.Cout = l.CoutP = C; l.oH = H; l.oW = W; l.K = 1;
             Layer& s = n->L[src];
             const std::string from = at + "the skip's source, layer " + std::to_string(src) + ", ";
+            // (a source that is RCN_HIPX_BN or RCN_HIPX_BN_ADD passes for every kind that adds a skip: its share is not gated by the source's output)
+            if (lin && s.kind != RCN_HIPX_CONV3X3_RELU && s.kind != RCN_HIPX_MAXPOOL2 && !s.row().bn)
+                return fail(n, -2, from + "must be a RCN_HIPX_CONV3X3_RELU or RCN_HIPX_MAXPOOL2 layer or a batch-normalisation layer of any kind (RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU, "
+                                          "RCN_HIPX_BN_ADD_RELU_DOWN, RCN_HIPX_BN or RCN_HIPX_BN_ADD): a bias-only convolution's map is not yet normalised");
             if (s.kind != RCN_HIPX_CONV3X3_RELU && s.kind != RCN_HIPX_MAXPOOL2 && !s.row().bn)
                 return fail(n, -2, from + "must be a RCN_HIPX_CONV3X3_RELU, RCN_HIPX_BN_RELU, RCN_HIPX_BN_ADD_RELU or RCN_HIPX_MAXPOOL2 layer (a RCN_HIPX_CONV3X3 map is not yet normalised)");
             if (s.pool_follows) return fail(n, -2, from + "has a max-pool behind it: its own output is not written when the two fuse -- the source must be the pool");
@@ -1364,6 +1456,8 @@ int describe_layers(rcn_hipx_net* n, int in_h, int in_w, int in_c, const rcn_hip
         n->L.push_back(std::move(l));
     }
     const KindRow& last = n->L.back().row();
+    if (last.bn && !last.relu)
+        return fail(n, -2, at_layer(n_layers - 1, n->L.back().kind) + "a batch normalisation without a ReLU must be followed directly by a convolution of any kind, and the last layer must be RCN_HIPX_DENSE (logits)");
     if (last.linear && last.named) return fail(n, -2, at_layer(n_layers - 1, n->L.back().kind) + "it must be followed directly by a batch-normalisation layer, and the last layer must be RCN_HIPX_DENSE (logits)");
     if (n->L.back().kind != RCN_HIPX_DENSE) return fail(n, -2, "the last layer must be RCN_HIPX_DENSE (logits)");
     n->classes = n->L.back().Cout;

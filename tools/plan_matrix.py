@@ -73,8 +73,8 @@ def main() -> None:
     root = os.path.abspath(ap.parse_args().root)
     sys.path[:0] = [root, os.path.join(root, "tests")]
     import bench_convnet as bc
-    import _dw_ref, _kinds_cases, _pw_ref, _stride_ref    # the twins' nets, and every description the plan tests expect refused
-    import test_convnet_bn_plan as bn, test_convnet_dw_plan as dw, test_convnet_gap_plan as gap, test_convnet_pw_plan as pw, test_convnet_res_plan as res, test_convnet_stride_plan as stride
+    import _dw_ref, _kinds_cases, _mb_ref, _pw_ref, _stride_ref    # the twins' nets, and every description the plan tests expect refused
+    import test_convnet_bn_plan as bn, test_convnet_dw_plan as dw, test_convnet_gap_plan as gap, test_convnet_mb_plan as mb, test_convnet_pw_plan as pw, test_convnet_res_plan as res, test_convnet_stride_plan as stride
     from mercer_research_amd.convnet import ConvNetError, plan, plan_eval
     for k in list(os.environ):
         if k.startswith("RCN_HIPX_"):
@@ -92,7 +92,7 @@ def main() -> None:
     nets = [(name, shape, layers, tuple(b for b in BATCHES if b <= 128) if name == "synth224" else BATCHES) for name, (shape, layers, _) in bc.CONFIGS.items()]
     nets += [(name, shape, layers, BATCHES) for name, (shape, layers) in SMALL.items()]
     # the nets of the newer kinds' tests (input shape, layers, the test's own batch): at that batch and at the batches above
-    for tag, group in (("stride", _stride_ref.NETS), ("pw", _pw_ref.NETS), ("dw", _dw_ref.NETS), ("kinds", {**_kinds_cases.NETS, **{"X" + k: v for k, v in _kinds_cases.EXACT.items()}}),
+    for tag, group in (("stride", _stride_ref.NETS), ("pw", _pw_ref.NETS), ("dw", _dw_ref.NETS), ("mb", _mb_ref.NETS), ("kinds", {**_kinds_cases.NETS, **{"X" + k: v for k, v in _kinds_cases.EXACT.items()}}),
                        ("bn", bn.BN_NETS), ("res", res.RES_NETS), ("gap", gap.GAP_NETS)):
         nets += [(f"{tag}_{name}", shape, layers, tuple(sorted({b0, *BATCHES}))) for name, (shape, layers, b0) in group.items()]
     for name, shape, layers, batches in nets:
@@ -108,7 +108,7 @@ def main() -> None:
             show(f"kinds_{name} B={b0} {p} auto " + " ".join(f"RCN_HIPX_{k.upper()}={v}" for k, v in options), shape, layers, b0, precision=p)
             for k, _ in options:
                 del os.environ["RCN_HIPX_" + k.upper()]
-    refused = [(r[0], r[1]) for m in (stride, pw, dw) for r in m.REFUSALS] + [((4, 4, 32), r[0]) for m in (res, gap) for r in m.REFUSALS] + PRECEDENCE
+    refused = [(r[0], r[1]) for m in (stride, pw, dw, mb) for r in m.REFUSALS] + [((4, 4, 32), r[0]) for m in (res, gap) for r in m.REFUSALS] + PRECEDENCE
     for k, (shape, layers) in enumerate(refused):
         show(f"refusal {k}: {shape} {layers}", shape, layers, 2)
     for env, value in OPTIONS:
